@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- CRF mean-field iterations/s on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--workload c2|c1|c3|c4|c5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--workload c2|c1|c3|c4|c5] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch: DenseCRF::inference(n_iter, with_map)
 (densecrf_base.h:65-73: startInference + n_iter x stepInference + buildMap) for F independent
@@ -219,6 +219,28 @@ def emit(full, path=None, stream=None):
     stream.write(text + "\n")
     stream.flush()
     return text
+
+
+DUMP_LIMIT = 64 * 10 ** 6      # bytes of .npy data --dump-outputs may write
+
+
+def dump_outputs(path, batches, seed=0):
+    """--dump-outputs DIR: what the timed path's last step handed its caller -- per frame the marginals Q [N, L] and the MAP labels
+    [N] of every batch handle, in frame order -- as DIR/probability.npy and DIR/map.npy (float32), so that two builds can be compared
+    output for output.  A batch larger than DUMP_LIMIT is written as a fixed, seeded sample of its frames; DIR/frame_index.npy
+    (float64) names the frames written.  Returns the number of frames written."""
+    import numpy as np
+    Q = np.concatenate([b.probability() for b in batches])
+    M = np.concatenate([b.map() for b in batches])
+    F, N, L = Q.shape
+    per_frame = 4 * N * L + 4 * N + 8
+    S = min(F, (DUMP_LIMIT - 3 * 128) // per_frame)          # (128 bytes: one .npy header)
+    sel = np.arange(F) if S == F else np.sort(np.random.default_rng(seed).choice(F, S, replace=False))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "probability.npy"), np.ascontiguousarray(Q[sel], np.float32))
+    np.save(os.path.join(path, "map.npy"), M[sel].astype(np.float32))
+    np.save(os.path.join(path, "frame_index.npy"), sel.astype(np.float64))
+    return int(S)
 
 
 class CudaView:
@@ -1141,10 +1163,14 @@ def main():
     ap.add_argument("--lite", action="store_true",
                     help="counter-collection runs (rocprofv3 --pmc serialises every dispatch): one event-timed launch instead of "
                          "five, two one-launch batches instead of many -- the timed region itself is unchanged")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (Q and labels; rank 0's frames) to DIR/*.npy")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))          # before torch / HIP are touched
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1276,6 +1302,8 @@ def main():
         step()
     barrier()
     t1 = time.perf_counter()
+    if args.dump_outputs and rank == 0:             # before anything else launches on these handles
+        dump_outputs(args.dump_outputs, [ln.b for ln in lanes])
     for ln in lanes:
         ln.b.set_option(pkg.BatchCRF.OPT_EVENT_TIMING, 1)
     dt = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)

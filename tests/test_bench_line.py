@@ -92,3 +92,69 @@ def test_oversized_line_is_refused(monkeypatch):
     monkeypatch.setattr(bench, "COMPACT_LIMIT", 512)
     with pytest.raises(SystemExit):
         bench.emit(_full(), None, io.StringIO())
+
+
+class _Batch:
+    """Stand-in for a BatchCRF handle: the two host accessors --dump-outputs reads."""
+
+    def __init__(self, Q, M):
+        self.Q, self.M = Q, M
+
+    def probability(self):
+        return self.Q.copy()
+
+    def map(self):
+        return self.M.copy()
+
+
+def test_dump_outputs_writes_a_fixed_sample_within_the_budget(tmp_path, monkeypatch):
+    import numpy as np
+    rng = np.random.default_rng(1)
+    F, N, L = 2000, 100, 2
+    Q = rng.random((F, N, L), dtype=np.float32)
+    M = rng.integers(0, L, (F, N)).astype(np.int16)
+    batches = [_Batch(Q[:1200], M[:1200]), _Batch(Q[1200:], M[1200:])]
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 10 ** 6)
+    runs = []
+    for d in ("a", "b"):
+        S = bench.dump_outputs(str(tmp_path / d), batches)
+        assert 0 < S < F
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= 10 ** 6
+        runs.append({n: np.load(tmp_path / d / (n + ".npy")) for n in ("probability", "map", "frame_index")})
+    for n in runs[0]:
+        assert runs[0][n].dtype in (np.float32, np.float64), n
+        assert np.array_equal(runs[0][n], runs[1][n]), n                 # the same sample every run
+    sel = runs[0]["frame_index"].astype(np.int64)
+    assert len(np.unique(sel)) == sel.size == runs[0]["probability"].shape[0] and np.all(np.diff(sel) > 0)
+    assert np.array_equal(runs[0]["probability"], Q[sel]) and np.array_equal(runs[0]["map"], M[sel].astype(np.float32))
+    # a batch within the budget is written whole
+    assert bench.dump_outputs(str(tmp_path / "c"), [_Batch(Q[:50], M[:50])]) == 50
+    assert np.array_equal(np.load(tmp_path / "c" / "probability.npy"), Q[:50])
+
+
+@pytest.mark.gpu
+def test_bench_dumps_what_its_last_timed_step_computed(tmp_path, po, wl):
+    """bench.py --dump-outputs on a small C2 batch: --steps sets the timed steps, and the dumped Q and labels are the CPU checker's
+    for the frames they name, bit for bit."""
+    import subprocess
+    import numpy as np
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--frames", "256",
+                        "--no-extras", "--no-cpu-baseline", "--no-check", "--full-json", str(tmp_path / "full.json"),
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 2 and line["warmup"] == 1
+    Q, M, sel = (np.load(out / (n + ".npy")) for n in ("probability", "map", "frame_index"))
+    assert Q.dtype == M.dtype == np.float32 and Q.shape == (256, 2000, 2) and M.shape == (256, 2000)
+    assert np.array_equal(sel, np.arange(256))
+    for f in (0, 1, 63, 64, 255):
+        pb = wl.slam_problem(2000, f % 64 + 1)                            # bench.make_batch: 64 distinct frames, seeds 1.., tiled
+        o = po.OracleCRF(pb["N"], pb["L"])
+        o.set_unary_from_label(pb["label"], pb["conf"])
+        for feat, w in pb["kernels"]:
+            o.add_pairwise(feat, w)
+        o.inference_native(5, True)
+        assert np.array_equal(M[f], o.map().astype(np.float32)), f
+        assert np.array_equal(Q[f].view(np.int32), o.probability().view(np.int32)), f
+        o.close()
