@@ -273,7 +273,6 @@ struct Engine {
         sort.vcap = vcap;
         int vbits = 10;
         while (vbits < 21 && (1 << vbits) < 4 * vcap) ++vbits;
-        if (const char *e = ab_env("LCCRF_VBITS")) vbits = std::min(std::max(atoi(e), 10), 21);   // A/B switch (same results): buckets of the vertex sort
         sort.vbits = vbits;
         const size_t vnbk = ((size_t)1 << vbits) + 1;
         if ((rc = mem.alloc(&sort.vcode, Fz * vcap))) return rc;
@@ -416,9 +415,6 @@ struct Engine {
             if ((rc = mem.alloc(&k.fastn, Fz * E))) return rc;
             if ((rc = mem.alloc(&k.ndist, (size_t)kNdistAxes))) return rc;
             if ((rc = mem.alloc(&k.nearoff, Fz * 2 * E * 2))) return rc;
-            // (the window splat's 16-byte vertex records: measured +-1 % on C5 x 8, round 5 -- notes/r5_experiments.md; kept as an
-            // experiment of the instrumented library, LCCRF_SPLAT_REC=1)
-            if (maxN < (1 << 24) && ab_env("LCCRF_SPLAT_REC") && (rc = mem.alloc(&k.srec, Fz * E))) return rc;
             if (!ndist_host && (rc = mem.alloc_pinned(&ndist_host, (size_t)LCCRF_MAX_KERNELS * kNdistAxes))) return rc;
         }
         // large frames, a few in flight: the sorted build also leaves the neighbour table in its compact form (16-bit offsets), for
@@ -552,8 +548,7 @@ struct Engine {
                     if (kernels[k].dev.d > kernels[src].dev.d) src = k;
                 // with the sorted build the points follow the vertices: (coarse) row-major order of their cells in the lattice's own basis
                 // instead of the Z-order curve (C5 x 8: splat 30.5 -> 27.7, slice 24.2 -> 19.5 us, build 1.93 -> 1.76 ms)
-                static const bool env_z = ab_env("LCCRF_POINTS_ZORDER") != nullptr;        // A/B switch (same results)
-                sort.rm_points = (vorder_on && !env_z) ? 1 : 0;
+                sort.rm_points = vorder_on ? 1 : 0;
                 launch_sort_points(kdevs[src], crf, sort, stream);
                 HIP_TRY(hipGetLastError());
                 perm_on = true;
@@ -570,7 +565,7 @@ struct Engine {
             const bool small_ok = !no_small && !perm_on;
             if (small_ok && k + 1 < k0 + n && build_small_supported(&kdevs[k], 2, NA)) m = 2;
             if (small_ok && build_small_supported(&kdevs[k], m, NA)) {
-                for (int u = 0; u < m; ++u) kernels[k + u].dev.nbr2_ok = kernels[k + u].dev.nbrc_ok = kernels[k + u].dev.fast0_ok = kernels[k + u].dev.longrow_ok = kernels[k + u].dev.srec_ok = 0;
+                for (int u = 0; u < m; ++u) kernels[k + u].dev.nbr2_ok = kernels[k + u].dev.nbrc_ok = kernels[k + u].dev.fast0_ok = kernels[k + u].dev.longrow_ok = 0;
                 launch_build_small(&kdevs[k], m, NA, crf, stream);   // writes V / rowmax to the pinned mirrors itself
             } else {
                 m = 1;
@@ -578,7 +573,6 @@ struct Engine {
                 kernels[k].dev.longrow_ok = kdevs[k].longrow_ok = kernels[k].dev.longrow != nullptr;   // (... and lists the long rows: the normalisation below reads the list)
                 kernels[k].dev.nbrc_ok = kernels[k].dev.nbrc != nullptr && kernels[k].dev.vorder && F >= kNbrcMinFrames && F <= kNbrcMaxFrames;   // (... and the sorted build the compact one)
                 kernels[k].dev.fast0_ok = kernels[k].dev.tbl_bad != nullptr && kernels[k].dev.vorder;
-                kernels[k].dev.srec_ok = kernels[k].dev.srec != nullptr && kernels[k].dev.vorder;          // (the sorted build packs the splat records)
                 kernels[k].dev.nbr2_first = kernels[k].dev.fast0_ok;              // (what build_kernel_d derives from the same two fields)
                 launch_build_kernel(kdevs[k], crf, kernels[k].maxV, stream, perm_on ? &sort : nullptr);
                 launch_norm(kdevs[k], crf, kernels[k].maxV, stream);
@@ -1301,8 +1295,7 @@ int lccrf_create(lccrf_handle *out, int device_id, int n_points, int n_labels)
     h->eng.crf.map = h->map_pin;
     h->eng.map_host = h->map_pin;
     h->eng.crf.map_bits = nullptr;                       // the packed copy is the batch API's gather payload only
-    static const bool no_late = ab_env("LCCRF_NO_LATE") != nullptr;   // debugging aid: always size the fused kernel on the host
-    h->eng.late_ok = !no_late;
+    h->eng.late_ok = true;
     h->label_stage_busy = false;    // a parked engine's stream is idle (recycle() synchronised it or saw the frame kernel's done word, its last store)
     // the kernels read the point count where the host wrote it (pinned, device-visible): no upload command on a path
     // whose every DMA packet costs microseconds of stream time (a parked engine's stream is idle, nothing reads the old value)

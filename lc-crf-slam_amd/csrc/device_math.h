@@ -217,10 +217,6 @@ __device__ __forceinline__ float fast_exp_nonpos(float x)
     static_assert(kFe4 == 4.0f * kFe1 && kFe8 == 8.0f * kFe1, "thresholds are power-of-two multiples of one another");
     float a = -x;
     const bool cut = a > 20;
-#ifndef LCCRF_EXP_FREXP
-#define LCCRF_EXP_FREXP 1                 // A/B (scripts/gpu_ab_build.sh "" "-DLCCRF_EXP_FREXP=0"): 0 = the five compares
-#endif
-#if LCCRF_EXP_FREXP
     // ... and those five compares are a frexp: kFe1 = 0.69f is its own mantissa (in [0.5, 1), exponent 0), a = m * 2^e with m in
     // [0.5, 1), so  a > kFe1 * 2^i  <=>  e > i or (e == i and m > kFe1)  and the count over i = 0 .. 4 is clamp(e + [m > kFe1], 0, 5)
     // (a = 0: e = 0, m = 0 -> 0; a < 0.5: e <= -1 -> 0; a >= 16: e >= 5 -> 5).  Two frexp instructions, a compare, an add, a clamp
@@ -229,9 +225,6 @@ __device__ __forceinline__ float fast_exp_nonpos(float x)
     const int e2 = __builtin_amdgcn_frexp_expf(a);
     const float m2 = __builtin_amdgcn_frexp_mantf(a);
     const int mult = min(max(e2 + (m2 > kFe1 ? 1 : 0), 0), 5);
-#else
-    const int mult = (a > kFe1 ? 1 : 0) + (a > 2.0f * kFe1 ? 1 : 0) + (a > kFe4 ? 1 : 0) + (a > kFe8 ? 1 : 0) + (a > 16.0f * kFe1 ? 1 : 0);
-#endif
     a = __builtin_amdgcn_ldexpf(a, -mult);
     float r = very_fast_exp(a);
 #pragma unroll
@@ -285,9 +278,6 @@ __device__ __forceinline__ void exp_and_normalize_reg(const float (&in)[L], floa
 // single exp is evaluated; the sum and the two IEEE divisions are the reference's.
 // omr = 1 - relax, formed once by the caller (the same fp32 subtraction as densecrf3d.h:94, (1 - relax): a uniform value the
 // kernels would otherwise keep in a vector register for the whole launch)
-#ifndef LCCRF_QUOT_STEPS
-#define LCCRF_QUOT_STEPS 2                // A/B (scripts/gpu_ab_build.sh "" "-DLCCRF_QUOT_STEPS=1"): residual corrections per quotient
-#endif
 __device__ __forceinline__ float2 softmax2_fresh(float a, float b)
 {
     const bool lt = a < b;                            // mx = b iff a < b (densecrf3d.h:76-79)
@@ -300,17 +290,13 @@ __device__ __forceinline__ float2 softmax2_fresh(float a, float b)
     // (Round 6: ONE residual correction per quotient would do -- both quotients are functions of e alone, and
     // scripts/ubench/quotcheck.hip finds 0 differences from IEEE division over EVERY float e in {0} U [2^-60, 1] -- but the
     // four instructions it saves per point bought nothing measurable (C2 +-0, C4 / N500 +0.4 %) and cost two frame-kernel
-    // variants 8-12 bytes of scratch: LCCRF_QUOT_STEPS stays 2.)
+    // variants 8-12 bytes of scratch: two corrections stay -- notes/r6_experiments.md.)
     const float r0 = __builtin_amdgcn_rcpf(tt);
     const float r = __builtin_fmaf(__builtin_fmaf(-tt, r0, 1.0f), r0, r0);
     auto quot = [&](float n) {
         const float q = n * r;
-#if LCCRF_QUOT_STEPS == 2
         const float q2 = __builtin_fmaf(__builtin_fmaf(-tt, q, n), r, q);
         return __builtin_fmaf(__builtin_fmaf(-tt, q2, n), r, q2);
-#else
-        return __builtin_fmaf(__builtin_fmaf(-tt, q, n), r, q);
-#endif
     };
     const float pm = quot(1.0f), pe = quot(e);
     return make_float2(lt ? pe : pm, lt ? pm : pe);

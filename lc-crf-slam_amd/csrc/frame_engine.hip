@@ -640,7 +640,7 @@ __global__ void __launch_bounds__(NT, 4) k_frame(CrfDev c, FrameArgs a)
         normalise(std::integral_constant<int, 1>{});
         // still nothing from the helper is needed: Q0 = softmax(-unary) and kernel 0's first products
         begin_inference();
-        if (kFuseXP && PPT <= 2 && a.n_iter > 0) {
+        if (PPT <= 2 && a.n_iter > 0) {
 #pragma unroll
             for (int s = 0; s < PPT; ++s)                 // (the normalisation's row sums finished with the buffer four barriers ago)
                 if (tid + s * NT < N) point_products<PPT, K, 2>(smem, lay, pr, s, 0);
@@ -845,8 +845,7 @@ int launch_frame(const CrfDev &c, const KernelDev *kds, int n_iter, int with_map
     // vertices, a smoothness kernel of min(NA + 350, 1150) (734 vertices at 400 points, 985 at 700, 1071 at 1000 on
     // 640x480 images with an 18-pixel kernel) -- i.e. up to 1024 points.  Frames with larger lattices flag themselves and
     // are re-run; an engine that sees more than 1/8 of a batch flagged stops asking for this shape (allow_small).
-    static const bool no_small = ab_env("LCCRF_NO_SMALL_WG") != nullptr;   // A/B switch: same results either way
-    bool small = allow_small && !no_small && NA <= 2 * kNTSmall && c.F >= kSmallMinFrames;
+    bool small = allow_small && NA <= 2 * kNTSmall && c.F >= kSmallMinFrames;
     if (small) {
         int vest[kMaxFusedK], tables = 0;
         for (int k = 0; k < c.K; ++k) {

@@ -257,12 +257,10 @@ void launch_lean_ppt(const CrfDev &c, const FrameArgs &a, hipStream_t s)
 // Is the half-CU form worth asking for?  Frames of NA points with lattices of the usual SLAM proportions (frame_engine.hip: an appearance
 // kernel of ~112 vertices, a smoothness kernel of min(NA + 350, 1150)) must fit the loop's plan; frames with larger lattices flag
 // themselves and are re-run, and an engine that sees more than 1/8 of a batch flagged stops asking.
-#ifndef LCCRF_FRAME_LEAN_MIN_POINTS
-#define LCCRF_FRAME_LEAN_MIN_POINTS 0                 // A/B (scripts/gpu_ab_build.sh): batches of larger frames than this take the kernel (C1 +12 %, N500 +10 % against k_frame<512>)
-#endif
+// Frames of any size take it, small ones too (C1 +12 %, N500 +10 % against k_frame<512>).
 bool frame_lean_plausible(int NA, int K, int F)
 {
-    if (K != 2 || F < kSmallMinFrames || NA <= LCCRF_FRAME_LEAN_MIN_POINTS || NA > 4 * kNTSmall) return false;
+    if (K != 2 || F < kSmallMinFrames || NA <= 0 || NA > 4 * kNTSmall) return false;
     const int vest[2] = {112, std::min(NA + 350, 1150)};
     FusedLayout est;
     return layout_lean(NA, K, vest, kChainMinRow, &est, kNTSmall, kLdsHalf);

@@ -340,30 +340,30 @@ __global__ void __launch_bounds__(NT, NT == 384 ? 3 : 4) k_fused_lean(CrfDev c, 
         typedef unsigned lean_u4 __attribute__((ext_vector_type(4)));
 #pragma unroll
         for (int s = 0; s < PPT; ++s) {
-            const lean_u2 u = __builtin_amdgcn_raw_buffer_load_b64(src.unary, (tid + s * NT) * 8, 0, LEAN_AUX(1));   // (a lane past the frame reads 0 or a spare row: unused)
+            const lean_u2 u = __builtin_amdgcn_raw_buffer_load_b64(src.unary, (tid + s * NT) * 8, 0, 0);   // (a lane past the frame reads 0 or a spare row: unused)
             pr.un[s] = make_float2(__uint_as_float(u.x), __uint_as_float(u.y));
 #pragma unroll
             for (int k = 0; k < K; ++k) {
-                const lean_u3 w = __builtin_amdgcn_raw_buffer_load_b96(rp, tid * 12, ((s * K + k) * NT) * 12, LEAN_AUX(1));
+                const lean_u3 w = __builtin_amdgcn_raw_buffer_load_b96(rp, tid * 12, ((s * K + k) * NT) * 12, 0);
                 pr.ix[s][k][0] = w.x;
                 pr.ix[s][k][1] = w.y;
                 pr.ix[s][k][2] = w.z;
                 // (RELOAD: these are the first iteration's; mean_field_lean re-reads them from the second on)
-                const lean_u3 b = __builtin_amdgcn_raw_buffer_load_b96(src.bary[k], (tid + s * NT) * (D1 * 4), 0, LEAN_AUX(16));
+                const lean_u3 b = __builtin_amdgcn_raw_buffer_load_b96(src.bary[k], (tid + s * NT) * (D1 * 4), 0, 0);
                 pr.bary[s][k][0] = __uint_as_float(b.x);
                 pr.bary[s][k][1] = __uint_as_float(b.y);
                 pr.bary[s][k][2] = __uint_as_float(b.z);
-                pr.wn[s][k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(src.norm[k], (tid + s * NT) * 4, 0, LEAN_AUX(4)));
+                pr.wn[s][k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(src.norm[k], (tid + s * NT) * 4, 0, 0));
             }
         }
-        const lean_u2 clw = __builtin_amdgcn_raw_buffer_load_b64(rp, tid * 8, pp.cl_off, LEAN_AUX(1));
+        const lean_u2 clw = __builtin_amdgcn_raw_buffer_load_b64(rp, tid * 8, pp.cl_off, 0);
         // the LDS tables: every piece is at most 16 bytes per lane (launch_inference_fused checks the plan), all requested before any is stored
         lean_u4 trow[K], tnbr[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             trow[k] = tnbr[k] = lean_u4{0u, 0u, 0u, 0u};
-            if (tid * 16 < pp.row_bytes[k]) trow[k] = __builtin_amdgcn_raw_buffer_load_b128(rp, tid * 16, pp.row_off[k], LEAN_AUX(1));
-            if (tid * 16 < pp.nbr_bytes[k]) tnbr[k] = __builtin_amdgcn_raw_buffer_load_b128(rp, tid * 16, pp.nbr_off[k], LEAN_AUX(1));
+            if (tid * 16 < pp.row_bytes[k]) trow[k] = __builtin_amdgcn_raw_buffer_load_b128(rp, tid * 16, pp.row_off[k], 0);
+            if (tid * 16 < pp.nbr_bytes[k]) tnbr[k] = __builtin_amdgcn_raw_buffer_load_b128(rp, tid * 16, pp.nbr_off[k], 0);
         }
         FL_PSTAMP();                                      // (everything requested)
         if (N <= 0) {                                     // (the point count was requested first and is only needed here)
@@ -403,7 +403,7 @@ __global__ void __launch_bounds__(NT, NT == 384 ? 3 : 4) k_fused_lean(CrfDev c, 
         int t = lane_id();
         mean_field_lean<PPT, K, CH, NT, RELOAD, false, true>(smem, lay, V, N, t, pr, cl, alpha, wk, src, a.n_iter, a.relax, a.omr, ins);
         t = lane_id();
-        store_results<PPT, K, NT, (LCCRF_LEAN_NT & 8) != 0>(c, fo, N, t, pr, a.with_map);
+        store_results<PPT, K, NT>(c, fo, N, t, pr, a.with_map);
         FL_STAMP();
         if (kInstr && a.timing && (int)blockIdx.x == a.timing_block && t == a.timing_lane) a.timing[63] = ins.n;
         return;
@@ -538,9 +538,8 @@ bool make_layout(const CrfDev &c, const KernelDev *kds, const int *maxV, const i
 // kernel 0 has long rows -- few enough vertices for the chain lanes of four wavefront pairs.
 bool small_layout(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, FusedLayout *lay)
 {
-    static const bool off = ab_env("LCCRF_NO_SMALL_WG") != nullptr;      // A/B switch: same results either way
     const int NA = c.activeN > 0 ? c.activeN : c.maxN;
-    if (off || c.F < kSmallMinFrames || NA > 2 * kNTSmall || maxV[0] > kNTSmall) return false;
+    if (c.F < kSmallMinFrames || NA > 2 * kNTSmall || maxV[0] > kNTSmall) return false;
     const int row0 = maxRow ? maxRow[0] : 0;
     if (row0 >= kChainMinRow && !chain_wanted(NA, maxV[0], row0, kNTSmall)) return false;   // long rows need the chain path: keep 1024 lanes
     FusedLayout L;
@@ -569,9 +568,8 @@ bool lean_layout(const CrfDev &c, const KernelDev *kds, const int *maxV, const i
     // Frames of 513 .. 1024 points take the plan too (two points per lane, everything in registers -- no re-reads): C1 6.47 -> 7.03e7
     // iterations/s against the half-CU form of the 137 KB plan (shared product buffer there as well, but no fused X + P and no
     // overlapped blur schedule).  Up to 512 points both kernels' products fit half a CU with buffers of their OWN: 9.94e7 against 9.05e7
-    // on this plan -- those keep small_layout() (LCCRF_LEAN_SMALL, instrumented library, forces the plan for the A/B).
-    static const bool lean_small = ab_env("LCCRF_LEAN_SMALL") != nullptr;
-    if (c.L != 2 || c.K < 1 || c.K > kMaxFusedK || c.F < kSmallMinFrames || (NA <= kNTSmall && !lean_small) || NA > max_ppt * nt) return false;
+    // on this plan -- those keep small_layout().
+    if (c.L != 2 || c.K < 1 || c.K > kMaxFusedK || c.F < kSmallMinFrames || NA <= kNTSmall || NA > max_ppt * nt) return false;
     for (int k = 0; k < c.K; ++k)
         if (kds[k].d != 2 || kds[k].Epad >= 65535) return false;
     FusedLayout L;
@@ -691,7 +689,7 @@ static FusedShape choose_shape(const CrfDev &c, const KernelDev *kds, const int 
     FusedShape sh{false, false, false, kNT, 1};
     int lean_nt = 0;
     const int NAp = c.activeN > 0 ? c.activeN : c.maxN;
-    const bool lean_first = NAp <= 2 * kNTSmall && lean_layout(c, kds, maxV, maxRow, lay, &lean_nt);      // (LCCRF_LEAN_SMALL experiment)
+    const bool lean_first = NAp <= 2 * kNTSmall && lean_layout(c, kds, maxV, maxRow, lay, &lean_nt);      // (513 .. 1024 points: lean before small)
     sh.small = !lean_first && small_layout(c, kds, maxV, maxRow, lay);
     sh.lean = lean_first || (!sh.small && lean_layout(c, kds, maxV, maxRow, lay, &lean_nt));
     if (!sh.small && !sh.lean && !make_layout(c, kds, maxV, maxRow, lay)) return sh;
@@ -717,8 +715,6 @@ int launch_inference_fused(const CrfDev &c, const KernelDev *kds, const int *max
     const FusedShape sh = choose_shape(c, kds, maxV, maxRow, &a.lay);
     if (!sh.ok) return 0;
     const bool small = sh.small, lean = sh.lean;
-    static const bool no_chain = ab_env("LCCRF_NO_CHAIN") != nullptr;     // debugging aid: compiler-scheduled S phase
-    if (no_chain) a.lay.chain0 = 0;                                        // (the padded plane size is harmless)
     for (int k = 0; k < c.K; ++k) a.kd[k] = kds[k];
     a.n_iter = n_iter;
     a.with_map = with_map;
@@ -739,10 +735,9 @@ int launch_inference_fused(const CrfDev &c, const KernelDev *kds, const int *max
     // writes the blocks (MODE 1) and every inference from then on starts from them (MODE 2).
     for (int k = 0; k < c.K; ++k) a.Vcap[k] = maxV[k];
     const LeanPrepPlan pp = lean_prep_plan(a.lay, c.K, a.Vcap, sh.nt, sh.ppt);
-    static const bool no_prep = ab_env("LCCRF_NO_LEAN_PREP") != nullptr;    // A/B switches (instrumented library): same results either way
-    static const bool prep_now = ab_env("LCCRF_LEAN_PREP_NOW") != nullptr;  //   ... the blocks already in the first inference
+    static const bool no_prep = ab_env("LCCRF_NO_LEAN_PREP") != nullptr;    // A/B switch (instrumented library): same results either way
     int mode = 0;
-    bool pieces_ok = !no_chain;                           // (the run kernels move every table with one (lean) / two 16-byte loads per lane)
+    bool pieces_ok = true;                           // (the run kernels move every table with one (lean) / two 16-byte loads per lane)
     for (int k = 0; k < c.K; ++k) pieces_ok = pieces_ok && pp.row_bytes[k] <= (lean ? 1 : 2) * sh.nt * 16 && pp.nbr_bytes[k] <= (lean ? 1 : 2) * sh.nt * 16;
     if (prep && prep->buf && !no_prep && pieces_ok && c.F >= kPrepMinFrames && (size_t)pp.total * (size_t)c.F <= prep->bytes) {
         // what the blocks depend on besides the lattices themselves: the plan, the shape, the frame count
@@ -756,7 +751,7 @@ int launch_inference_fused(const CrfDev &c, const KernelDev *kds, const int *max
         a.prep_stride = pp.total;
         if (prep->valid && prep->key == key) {
             mode = 2;
-        } else if (prep->seen_key == key || prep_now) {      // the second inference on these lattices: write the blocks, then run from them
+        } else if (prep->seen_key == key) {      // the second inference on these lattices: write the blocks, then run from them
             if (prep->ev0) (void)hipEventRecord(prep->ev0, s);
             launch_shape(c, a, s, 1, NAp, small, lean);
             if (prep->ev1) (void)hipEventRecord(prep->ev1, s);

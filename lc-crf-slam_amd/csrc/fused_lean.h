@@ -25,14 +25,10 @@
 #define LCCRF_LEAN_SKIP 0
 #endif
 #define LEAN_SKIP(bit) ((LCCRF_LEAN_SKIP & (bit)) != 0)
-// Cache policy of the loop's HBM / L2 accesses (bit set = non-temporal, aux = 2): 1 the prologue's once-per-launch records, 2 the
-// large lattice's neighbour words, 4 norms + unary energies, 8 the results, 16 the barycentric weights.  What every iteration re-reads
-// is ~94 KB per frame, 64 frames per XCD: 6 MB cycling through a 4 MB L2 misses every time (FETCH_SIZE: profiles/r5_fused_c2); the
-// point of the hints is to keep a subset that FITS (the weights: 48 KB per frame) resident and stream the rest past it.
-#ifndef LCCRF_LEAN_NT
-#define LCCRF_LEAN_NT 0
-#endif
-#define LEAN_AUX(bit) ((LCCRF_LEAN_NT & (bit)) ? 2 : 0)
+// The loop's HBM / L2 accesses carry no cache-policy hints.  What every iteration re-reads is ~94 KB per frame, 64 frames per XCD: 6 MB
+// cycling through a 4 MB L2 misses every time (FETCH_SIZE: profiles/r5_fused_c2).  Non-temporal loads on everything but the barycentric
+// weights (48 KB per frame) keep those resident and cut the fetched bytes by 30 %, yet make the launch 6 % slower; on everything, 21 %
+// slower (round 6, notes/r6_experiments.md).
 
 namespace lccrf {
 namespace fl {
@@ -471,19 +467,12 @@ __device__ __forceinline__ void mean_field_lean(unsigned char *smem, const Fused
     // to live across a ring -- left to itself the allocator parks it in the clobbered range and spills it around the asm.
     const int wave_base = __builtin_amdgcn_readfirstlane(t & ~63);
     (void)wave_base;
-#ifndef LCCRF_LEAN_T_MBCNT
-#define LCCRF_LEAN_T_MBCNT 1              // A/B (scripts/gpu_ab_build.sh "" "-DLCCRF_LEAN_T_MBCNT=0"): 0 = one opaque copy kept through the loop
-#endif
-#if LCCRF_LEAN_T_MBCNT
 #define LEAN_FRESH_T()                                                                                               \
     do {                                                                                                             \
         int z_ = 0;                                                                                                  \
         asm volatile("" : "+v"(z_));                                                                                 \
         t = wave_base + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)z_));          \
     } while (0)
-#else
-#define LEAN_FRESH_T() asm volatile("" : "+v"(t))
-#endif
     auto load_weights = [&]() {
         if (!RELOAD) return;
 #pragma unroll
@@ -491,16 +480,16 @@ __device__ __forceinline__ void mean_field_lean(unsigned char *smem, const Fused
             const int i = t + s * NT;                   // (a lane without a point in this slot reads the slice's spare rows or 0: unused)
             if (!NORM) {
                 typedef unsigned lean_u2 __attribute__((ext_vector_type(2)));
-                const lean_u2 u = __builtin_amdgcn_raw_buffer_load_b64(src.unary, i * 8, src.off_unary, LEAN_AUX(4));
+                const lean_u2 u = __builtin_amdgcn_raw_buffer_load_b64(src.unary, i * 8, src.off_unary, 0);
                 pr.un[s] = make_float2(__uint_as_float(u.x), __uint_as_float(u.y));
             }
 #pragma unroll
             for (int k = 0; k < K; ++k) {
-                const lean_u3 b = __builtin_amdgcn_raw_buffer_load_b96(src.bary[k], i * (D1 * 4), src.off_bary[k], LEAN_AUX(16));
+                const lean_u3 b = __builtin_amdgcn_raw_buffer_load_b96(src.bary[k], i * (D1 * 4), src.off_bary[k], 0);
                 pr.bary[s][k][0] = __uint_as_float(b.x);
                 pr.bary[s][k][1] = __uint_as_float(b.y);
                 pr.bary[s][k][2] = __uint_as_float(b.z);
-                if (!NORM) pr.wn[s][k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(src.norm[k], i * 4, src.off_norm[k], LEAN_AUX(4)));
+                if (!NORM) pr.wn[s][k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(src.norm[k], i * 4, src.off_norm[k], 0));
             }
         }
         if (NORM) return;
@@ -601,7 +590,7 @@ __device__ __forceinline__ void mean_field_lean(unsigned char *smem, const Fused
                 for (int r = 0; r < R; ++r) {
                     w[k][j][r] = 0;
                     if (!(CH == 1 && k == 0) && (r == 0 || r * NT < V[k]))      // (uniform; v >= V: an unused word of the table)
-                        w[k][j][r] = __builtin_amdgcn_raw_buffer_load_b32(src.nbr[k], (t + r * NT) * 4, src.off_nbr[k] + j * src.nbr_axis_bytes[k], LEAN_AUX(2));
+                        w[k][j][r] = __builtin_amdgcn_raw_buffer_load_b32(src.nbr[k], (t + r * NT) * 4, src.off_nbr[k] + j * src.nbr_axis_bytes[k], 0);
                 }
             }
         }
@@ -642,7 +631,7 @@ __device__ __forceinline__ void mean_field_lean(unsigned char *smem, const Fused
         for (int r = 0; r < RA; ++r) {
             wa[r] = 0;
             if ((r == 0 || r * NA0 < V[K - 1]) && !LEAN_SKIP(512))
-                wa[r] = __builtin_amdgcn_raw_buffer_load_b32(src.nbr[K - 1], (t - 128 + r * NA0) * 4, src.off_nbr[K - 1], LEAN_AUX(2));      // (lanes < 128: out of range reads 0, unused)
+                wa[r] = __builtin_amdgcn_raw_buffer_load_b32(src.nbr[K - 1], (t - 128 + r * NA0) * 4, src.off_nbr[K - 1], 0);      // (lanes < 128: out of range reads 0, unused)
         }
 #pragma unroll
         for (int j = 1; j < D1; ++j) {
@@ -650,7 +639,7 @@ __device__ __forceinline__ void mean_field_lean(unsigned char *smem, const Fused
             for (int r = 0; r < RB; ++r) {
                 wb[j - 1][r] = 0;
                 if ((r == 0 || r * NB < V[K - 1]) && !LEAN_SKIP(512))
-                    wb[j - 1][r] = __builtin_amdgcn_raw_buffer_load_b32(src.nbr[K - 1], (t + r * NB) * 4, src.off_nbr[K - 1] + j * src.nbr_axis_bytes[K - 1], LEAN_AUX(2));
+                    wb[j - 1][r] = __builtin_amdgcn_raw_buffer_load_b32(src.nbr[K - 1], (t + r * NB) * 4, src.off_nbr[K - 1] + j * src.nbr_axis_bytes[K - 1], 0);
             }
         }
     };
@@ -740,14 +729,11 @@ __device__ __forceinline__ void mean_field_lean(unsigned char *smem, const Fused
             __syncthreads();
             FL_STAMP();
             LEAN_FRESH_T();
-#ifndef LCCRF_LEAN_EARLY_WEIGHTS
-#define LCCRF_LEAN_EARLY_WEIGHTS 0        // A/B (scripts/gpu_ab_build.sh): request the re-read records one blur phase earlier
-#endif
-            if (LCCRF_LEAN_EARLY_WEIGHTS && !NORM && !LEAN_SKIP(256)) load_weights();
             if (t >= NB) blur_small(t - NB, 0, 2);        // (two of its three dependent passes here, the third beside pass 2 below:
             else blur_big(1, t, NB, RB, wb[0]);           //  all three in one phase made that phase as long as this one wavefront)
             __syncthreads();
-            if (!LCCRF_LEAN_EARLY_WEIGHTS && !NORM && !LEAN_SKIP(256)) load_weights();   // (requested before the last pass: they land under it; a NORM pass has no next iteration)
+            if (!NORM && !LEAN_SKIP(256)) load_weights();   // (requested before the last pass: they land under it; a NORM pass has no next iteration;
+                                                            //  one phase earlier: 4.31 vs 4.32e7, notes/r5_experiments.md)
             if (t < NB) blur_big(2, t, NB, RB, wb[1]);
             else blur_small(t - NB, 2, D1);
             __syncthreads();

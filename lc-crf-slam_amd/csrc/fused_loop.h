@@ -26,19 +26,14 @@ constexpr int kNT = 1024;                 // lanes per workgroup (16 wavefronts)
 constexpr int kMaxFusedK = 2;
 constexpr int kD1 = 3;                    // 2-D kernels: three simplex corners per point
 constexpr int kChainGap = 14;             // product slots reserved per chain row beyond its products (see pst)
-#ifndef LCCRF_CHAIN_TOP
-#define LCCRF_CHAIN_TOP 16                // A/B (scripts/gpu_ab_build.sh "" "-DLCCRF_CHAIN_TOP=32"): 8, 16 or 32
-#endif
-constexpr int kChainTop = LCCRF_CHAIN_TOP; // rows of the first chain wavefront pair (see chain_setup)
+// rows of the first chain wavefront pair (see chain_setup); 32 rows: C2 -2 %, C4 +-0; 8 rows: C2 +-0, C4 -1 % (notes/r6_experiments.md)
+constexpr int kChainTop = 16;
 // which of the first pair's kChainTop rows lane `ln` of its wavefront sums (-1: none): the same number of lanes in each of the four
 // 16-lane groups a ds_read_b128 is served in
 __host__ __device__ constexpr int chain_top_rank(int ln)
 {
-    return kChainTop == 32 ? (((ln & 8) == 0) ? ((ln & 7) | ((ln >> 4) << 3)) : -1)
-         : kChainTop == 8  ? (((ln & 0x1c) == 0) ? ((ln & 3) | ((ln >> 5) << 2)) : -1)
-                           : (((ln & 0x18) == 0) ? ((ln & 7) | ((ln >> 5) << 3)) : -1);
+    return ((ln & 0x18) == 0) ? ((ln & 7) | ((ln >> 5) << 3)) : -1;
 }
-static_assert(kChainTop == 8 || kChainTop == 16 || kChainTop == 32, "chain_top_rank");
 constexpr size_t kLdsLimit = 160 * 1024;  // MI355X: 160 KiB LDS per CU, one workgroup may own it all
 constexpr int kChainMinRow = 64;          // kernel 0 runs chain_rows when its longest splat row has at least this many products ...
 // ... and it has at most this many vertices (one lane per (vertex,label) row: wavefront pair 0 takes the kChainTop longest
@@ -52,10 +47,6 @@ constexpr int kNTSmall = 512;
 constexpr int kSmallMinFrames = 256;       // fewer frames than CUs: nothing to share a CU with, 1024 lanes finish a frame sooner
 constexpr size_t kLdsHalf = kLdsLimit / 2;
 
-#ifndef LCCRF_FUSE_XP
-#define LCCRF_FUSE_XP 1
-#endif
-constexpr bool kFuseXP = LCCRF_FUSE_XP != 0;     // A/B switch (scripts/gpu_ab_build.sh): products written right behind each point's softmax
 #ifndef LCCRF_INSTRUMENT
 #define LCCRF_INSTRUMENT 0
 #endif
@@ -552,7 +543,7 @@ __device__ __forceinline__ void mean_field(unsigned char *smem, const FusedLayou
         }
         pr.q[s] = softmax2(nx[0], nx[1], pr.q[s], relax);        // densecrf3d.h:70-98 with L = 2: one exp, not two
     };
-    if (kFuseXP && PPT <= 2 && lay.prod_all) {            // (3-4 points per lane: the fused form costs registers the loop does not have)
+    if (PPT <= 2 && lay.prod_all) {            // (3-4 points per lane: the fused form costs registers the loop does not have)
         // Every kernel owns its product buffer: a point's next products go out right behind its softmax, so one
         // point's LDS stores drain while the next point's slice and softmax occupy the VALU (X is VALU-bound, P is
         // bound by the LDS store path; back to back they cost the sum).  The barrier that used to follow P now
@@ -605,25 +596,15 @@ __device__ __forceinline__ void clear_label_bits(const CrfDev &c, int f, int fir
 }
 
 // Q and the MAP labels (densecrf3d.h:136-151: first maximum wins, ties -> label 0) of this lane's points.
-// NTS: non-temporal stores (the results leave the XCD's L2 working set alone: fused_lean.h, LCCRF_LEAN_NT)
-template <int PPT, int K, int NT = kNT, bool NTS = false>
+template <int PPT, int K, int NT = kNT>
 __device__ __forceinline__ void store_results(const CrfDev &c, int f, int N, int tid, const PointRegs<PPT, K> &pr, int with_map)
 {
 #pragma unroll
     for (int s = 0; s < PPT; ++s) {
         const int i = tid + s * NT;
         if (i < N) {
-            if (NTS) {
-                typedef float nts_f2 __attribute__((ext_vector_type(2)));
-                nts_f2 q;
-                q.x = pr.q[s].x;
-                q.y = pr.q[s].y;
-                __builtin_nontemporal_store(q, reinterpret_cast<nts_f2 *>(c.Q) + (size_t)f * c.maxN + i);
-                if (with_map) __builtin_nontemporal_store((int16_t)((pr.q[s].x < pr.q[s].y) ? 1 : 0), c.map + (size_t)f * c.maxN + i);
-            } else {
-                reinterpret_cast<float2 *>(c.Q)[(size_t)f * c.maxN + i] = pr.q[s];
-                if (with_map) c.map[(size_t)f * c.maxN + i] = (pr.q[s].x < pr.q[s].y) ? 1 : 0;   // densecrf3d.h:145
-            }
+            reinterpret_cast<float2 *>(c.Q)[(size_t)f * c.maxN + i] = pr.q[s];
+            if (with_map) c.map[(size_t)f * c.maxN + i] = (pr.q[s].x < pr.q[s].y) ? 1 : 0;   // densecrf3d.h:145
         }
         if (with_map && c.map_bits && (i & ~63) < N) {                   // the same labels, one bit each (label gather payload)
             const unsigned long long m = __ballot(i < N && pr.q[s].x < pr.q[s].y);

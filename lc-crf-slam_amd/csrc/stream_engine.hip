@@ -51,12 +51,10 @@ __device__ __forceinline__ FrameBlock frame_block(XcdMap m)
 }
 // lanes per workgroup of the iteration kernels: 256; with one or two frames in flight a pass is a chain of latencies and smaller
 // workgroups drain sooner (scripts/ubench/phasecost.hip: 256 -> 64 lanes 6.8 -> 6.4 us per pass of one C5 frame; in the engine,
-// `FRAMES=1 WORKLOAD=c5 scripts/gpu_env_ab.sh LCCRF_SMALL_F_BLOCK=256 ""`: one frame 41.0 -> 40.2 us per iteration, two 32.8 -> 32.1, four +-0)
+// 256 -> 64 lanes: one frame 41.0 -> 40.2 us per iteration, two 32.8 -> 32.1, four +-0)
 inline int iter_block(int F)
 {
-    static const char *e = ab_env("LCCRF_SMALL_F_BLOCK");             // A/B switch: same results
-    static const int small = e ? std::min(std::max(atoi(e), 64), 256) & ~63 : kSmallFBlock;
-    return F <= 2 ? small : 256;
+    return F <= 2 ? kSmallFBlock : 256;
 }
 inline dim3 grid_xcd(long work, int F, XcdMap *m, int block = 256)
 {
@@ -823,28 +821,6 @@ __global__ void __launch_bounds__(kBlock) k_ebucket_vertices(KernelDev kd, SortS
     const int b = blockIdx.x * kBlock + threadIdx.x;
     if (b >= nbk) return;
     ss.vhist[(size_t)f * nbk + b] = kd.prefix[(size_t)f * (kd.Epad + 1) + ss.vstart[(size_t)f * nbk + b]];   // (prefix[live] = V)
-}
-
-// The window splat's per-vertex record (KernelDev::srec), packed once per build from the arrays the sorted build has just written.
-__global__ void __launch_bounds__(kBlock) k_pack_srec(KernelDev kd, int F, XcdMap nb)
-{
-    const FrameBlock fb = frame_block(nb);
-    const int f = fb.f;
-    if (f >= F) return;
-    const int V = kd.V[f];
-    const int v = fb.bx * kBlock + threadIdx.x;
-    if (v >= V) return;
-    const size_t fe = (size_t)f * kd.Epad, f1 = (size_t)f * (kd.Epad + 1);
-    const int s = kd.rowptr[f1 + v], t = kd.rowptr[f1 + v + 1];
-    const char2 *off1 = reinterpret_cast<const char2 *>(kd.nearoff) + (size_t)f * 2 * kd.Epad, *off2 = off1 + kd.Epad;
-    const char2 o1 = off1[v], o2 = off2[v];
-    const unsigned len7 = (unsigned)min(t - s, 127), nx = kd.fastn[fe + v] ? 1u : 0u;
-    uint4 r;
-    r.x = (unsigned)s;
-    r.y = (s < t ? ((unsigned)kd.csr_pt[fe + s] & 0xffffffu) : 0u) | (len7 << 24) | (nx << 31);
-    r.z = s < t ? __float_as_uint(kd.csr_w[fe + s]) : 0u;
-    r.w = (unsigned)(unsigned char)o1.x | ((unsigned)(unsigned char)o1.y << 8) | ((unsigned)(unsigned char)o2.x << 16) | ((unsigned)(unsigned char)o2.y << 24);
-    kd.srec[fe + v] = r;
 }
 
 // One thread per vertex v, all d + 1 axes at once: n2_j(v) by code -- +1 along grid coordinate j (j < d), -1 along every coordinate
@@ -1627,7 +1603,7 @@ __global__ void __launch_bounds__(kBlock) k_splat2(KernelDev kd, const float2 *_
 // outside the window reads as zero, which spoils its neighbours' values pass by pass -- by at most `halo` = 1 + dist_1 (+ dist_2)
 // positions from either end, so the inner B - 2 halo results are exactly what P launches of k_blur2 would have stored (the same
 // operations on the same values in the same order) and only those are written.  One launch, one table read per extra pass.
-template <int LANES, int U, bool REC = false, bool RNT = true>
+template <int LANES, int U>
 __global__ void __launch_bounds__(LANES) k_splat2w(KernelDev kd, const float2 *__restrict__ in, int in_stride, int F, XcdMap nb, int P, int halo)
 {
     constexpr int B = LANES * U;                          // the window: U vertices per lane, at stride LANES (coalesced)
@@ -1650,57 +1626,28 @@ __global__ void __launch_bounds__(LANES) k_splat2w(KernelDev kd, const float2 *_
     int pt0[U];
     float w0[U];
     float2 q0[U];
-    if (REC) {
-        // REC: one 16-byte record per vertex (KernelDev::srec) says what seven loads said -- row start and length, the first entry's
-        // point and weight, fastn and the four byte offsets; a row of 127 entries or more reads its end from the row pointers
-        uint4 r[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int v = v0 + tid + u * LANES;
-            typedef unsigned u4v __attribute__((ext_vector_type(4)));
-            r[u] = make_uint4(0u, 0u, 0u, 0u);
-            if (v >= 0 && v < V) {                        // (read once per iteration: non-temporal, out of the value arrays' way in L2)
-                const u4v *rp = reinterpret_cast<const u4v *>(kd.srec + fe + v);
-                const u4v q = RNT ? __builtin_nontemporal_load(rp) : *rp;
-                r[u] = make_uint4(q.x, q.y, q.z, q.w);
-            }
+    for (int u = 0; u < U; ++u) {
+        const int v = v0 + tid + u * LANES;
+        const bool live = v >= 0 && v < V;
+        s[u] = t[u] = 0;
+        nx[u] = 0;
+        o1[u] = o2[u] = make_char2(0, 0);
+        if (live) {
+            s[u] = kd.rowptr[f1 + v];
+            t[u] = kd.rowptr[f1 + v + 1];
+            nx[u] = kd.fastn[fe + v];
+            o1[u] = off1[v];
+            if (P > 2) o2[u] = off2[v];
         }
+    }
+    // the first entry of each of the lane's U rows together (rows hold 1.2 entries on average: most are done after this), then
+    // whatever is left of each row in order
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int len7 = (int)((r[u].y >> 24) & 127u);
-            s[u] = (int)r[u].x;
-            t[u] = s[u] + len7;
-            if (len7 == 127) t[u] = kd.rowptr[f1 + v0 + tid + u * LANES + 1];
-            nx[u] = (uint8_t)(r[u].y >> 31);
-            pt0[u] = (int)(r[u].y & 0xffffffu);
-            w0[u] = __uint_as_float(r[u].z);
-            o1[u] = make_char2((signed char)(r[u].w & 0xffu), (signed char)((r[u].w >> 8) & 0xffu));
-            o2[u] = make_char2((signed char)((r[u].w >> 16) & 0xffu), (signed char)(r[u].w >> 24));
-        }
-    } else {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int v = v0 + tid + u * LANES;
-            const bool live = v >= 0 && v < V;
-            s[u] = t[u] = 0;
-            nx[u] = 0;
-            o1[u] = o2[u] = make_char2(0, 0);
-            if (live) {
-                s[u] = kd.rowptr[f1 + v];
-                t[u] = kd.rowptr[f1 + v + 1];
-                nx[u] = kd.fastn[fe + v];
-                o1[u] = off1[v];
-                if (P > 2) o2[u] = off2[v];
-            }
-        }
-        // the first entry of each of the lane's U rows together (rows hold 1.2 entries on average: most are done after this), then
-        // whatever is left of each row in order
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const bool any = s[u] < t[u];
-            pt0[u] = any ? kd.csr_pt[fe + s[u]] : 0;
-            w0[u] = any ? kd.csr_w[fe + s[u]] : 0.0f;
-        }
+    for (int u = 0; u < U; ++u) {
+        const bool any = s[u] < t[u];
+        pt0[u] = any ? kd.csr_pt[fe + s[u]] : 0;
+        w0[u] = any ? kd.csr_w[fe + s[u]] : 0.0f;
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) q0[u] = x[pt0[u]];
@@ -1893,17 +1840,18 @@ __global__ void __launch_bounds__(kBlock) k_blur2x2t(KernelDev kd, const float *
     d[v] = make_float2(tv.x + 0.5f * (ta.x + tbv.x), tv.y + 0.5f * (ta.y + tbv.y));
 }
 
-constexpr int kSliceBlurMaxFrames = 1;       // the last blur pass inside the slice (k_slice2<D1, true>) when passes go one per launch, up to this many frames in flight (with the sorted build: two frames +2 % without it, four and eight +-0: `FRAMES=2 WORKLOAD=c5 scripts/gpu_env_ab.sh LCCRF_SLICE_BLUR_MAX=8 ""`)
-constexpr int kPairFuseMaxFrames = 1;        // (measured, `FRAMES=1 WORKLOAD=c5 scripts/gpu_env_ab.sh LCCRF_NO_PAIR_FUSE=1 ""`: one C5 frame 52.5 -> 45.2 us per iteration; two or four frames in flight: +-0)
+constexpr int kSliceBlurMaxFrames = 1;       // the last blur pass inside the slice (k_slice2<D1, true>) when passes go one per launch, up to this many frames in flight (with the sorted build: two frames +2 % without it, four and eight +-0)
+// the window splat: a lane per vertex up to this many frames in flight (two frames 25.3 / 24.5-25.1 / 25.0-26.4 us per frame-iteration
+// with the threshold at 1 / 2 / 3, three frames 20.6 / 20.7 / 21.1-21.5: notes/r4_experiments.md)
+constexpr int kSplatWideMaxFrames = 2;
+constexpr int kPairFuseMaxFrames = 1;        // (measured: one C5 frame 52.5 -> 45.2 us per iteration; two or four frames in flight: +-0)
 // ... or, whatever the number of frames, when the launch is SMALL: up to ~0.7 M vertices over all frames (one C5 frame: 0.59 M; two: +-0)
 // the passes are launch- and latency-bound, e.g. 8 frames of 5000 points (30 000 vertices each): 9 launches of ~3.8 us per iteration
 constexpr long kPairFuseMaxVertices = 700000;
 inline bool pair_fuse(int F, int maxV)
 {
     static const bool off = ab_env("LCCRF_NO_PAIR_FUSE") != nullptr;      // A/B switch: same results either way
-    static const char *force = ab_env("LCCRF_PAIR_FUSE_MAX");             //  (A/B: frames-in-flight threshold)
     if (off) return false;
-    if (force) return F <= atoi(force);
     return F <= kPairFuseMaxFrames || (long)F * maxV <= kPairFuseMaxVertices;
 }
 
@@ -1915,8 +1863,7 @@ inline void launch_blur2(const KernelDev &kd, const float *src, float *dst, int 
     const int blk = iter_block(F);
     const dim3 g = grid_xcd((maxV + 1) / 2, F, &nb, blk);
     static const bool no_compact = ab_env("LCCRF_NO_COMPACT_NBR") != nullptr;      // A/B switch: same results either way
-    static const char *env_nt = ab_env("LCCRF_BLUR_NT");                            // A/B: 0 plain loads, 1 non-temporal
-    const bool nt = env_nt ? atoi(env_nt) != 0 : F >= kBlurNtMinFrames;
+    const bool nt = F >= kBlurNtMinFrames;
     if (kd.nbrc && kd.nbrc_ok && !no_compact) {
         if (nt) k_blur2c<true><<<g, blk, 0, s>>>(kd, src, dst, j, F, nb);
         else k_blur2c<false><<<g, blk, 0, s>>>(kd, src, dst, j, F, nb);
@@ -2135,7 +2082,6 @@ void build_kernel_d(const KernelDev &kd, const CrfDev &c, hipStream_t s, const S
         if (kd.ndist) (void)hipMemsetAsync(kd.ndist, 0, kNdistAxes * sizeof(int), s);
         if (kd.nearoff) (void)hipMemsetAsync(kd.nearoff, 0, (size_t)F * 2 * kd.Epad * 2, s);
         k_eneighbors<D><<<g, kBlock, 0, s>>>(kd, F, nb, ss);
-        if (kd.srec && kd.nearoff && kd.fastn) k_pack_srec<<<g, kBlock, 0, s>>>(kd, F, nb);
         if (kd.nbrc && F >= kNbrcMinFrames && F <= kNbrcMaxFrames) {
             int limit = 0xffff;
 #if LCCRF_INSTRUMENT
@@ -2267,33 +2213,20 @@ void launch_step_stream(const CrfDev &c, const KernelDev *kds, const int *maxV, 
                 // many frames in flight: 256 lanes x 1 / 2 / 4 vertices (C5 x 8, window 1024: 20.6 -> 18.9 us per frame-iteration against
                 // 1024 lanes x 1: workgroups of four wavefronts wait less at the barriers); one or two frames: one or two vertices per lane
                 // (a lane's four row walks in a row cost a single frame 33.3 -> 36.1)
-                static const char *env_w = ab_env("LCCRF_SPLAT_WIDE_MAX");                  // (A/B: frames-in-flight threshold)
-                const bool wide = c.F <= (env_w ? atoi(env_w) : 2);
+                const bool wide = c.F <= kSplatWideMaxFrames;
                 const int lanes = wide ? B : kBlock;
                 const dim3 g = grid_xcd(((long)maxV[k] + core - 1) / core * lanes, c.F, &nb, lanes);
-                // (REC: the per-vertex records of the sorted build, one load instead of seven -- KernelDev::srec; allocated by the
-                // instrumented library under LCCRF_SPLAT_REC=1 only: +-1 % on two boxes)
-                const bool rec = kd.srec && kd.srec_ok;
-                static const bool rec_plain = ab_env("LCCRF_SPLAT_REC_PLAIN") != nullptr;      // A/B switch: records through plain (cached) loads
-#define LCCRF_SPLAT2W(LN, UU, GRID) do { if (rec && rec_plain) k_splat2w<LN, UU, true, false><<<GRID, LN, 0, s>>>(kd, q2, c.maxN, c.F, nb, j0, kd.splat_halo); \
-                                         else if (rec) k_splat2w<LN, UU, true><<<GRID, LN, 0, s>>>(kd, q2, c.maxN, c.F, nb, j0, kd.splat_halo); \
-                                         else k_splat2w<LN, UU, false><<<GRID, LN, 0, s>>>(kd, q2, c.maxN, c.F, nb, j0, kd.splat_halo); } while (0)
-                if (B == 256) LCCRF_SPLAT2W(256, 1, g);
-                else if (B == 512 && wide) LCCRF_SPLAT2W(512, 1, g);
-                else if (B == 512) LCCRF_SPLAT2W(256, 2, g);
+                // (one 16-byte record per vertex in place of seven loads, and 512 lanes x 2 vertices with many frames in flight: both
+                // +-noise, notes/r5_experiments.md section 3)
+                if (B == 256) k_splat2w<256, 1><<<g, 256, 0, s>>>(kd, q2, c.maxN, c.F, nb, j0, kd.splat_halo);
+                else if (B == 512 && wide) k_splat2w<512, 1><<<g, 512, 0, s>>>(kd, q2, c.maxN, c.F, nb, j0, kd.splat_halo);
+                else if (B == 512) k_splat2w<256, 2><<<g, 256, 0, s>>>(kd, q2, c.maxN, c.F, nb, j0, kd.splat_halo);
                 else if (c.F == 1) {                      // (one frame: 663 workgroups of 1024 lanes are 1.3 rounds of the chip's 512 slots;
                     const dim3 g5 = grid_xcd(((long)maxV[k] + core - 1) / core * 512, c.F, &nb, 512);    //  512 lanes x 2 vertices all run at once: 33.6 -> 32.5 us)
-                    LCCRF_SPLAT2W(512, 2, g5);
+                    k_splat2w<512, 2><<<g5, 512, 0, s>>>(kd, q2, c.maxN, c.F, nb, j0, kd.splat_halo);
                 }
-                else if (wide) LCCRF_SPLAT2W(1024, 1, g);
-                else {
-                    static const bool w512 = ab_env("LCCRF_SPLAT_512X2") != nullptr;            // A/B switch: 512 lanes x 2 vertices with many frames in flight
-                    if (w512) {
-                        const dim3 g5 = grid_xcd(((long)maxV[k] + core - 1) / core * 512, c.F, &nb, 512);
-                        LCCRF_SPLAT2W(512, 2, g5);
-                    } else LCCRF_SPLAT2W(256, 4, g);
-                }
-#undef LCCRF_SPLAT2W
+                else if (wide) k_splat2w<1024, 1><<<g, 1024, 0, s>>>(kd, q2, c.maxN, c.F, nb, j0, kd.splat_halo);
+                else k_splat2w<256, 4><<<g, 256, 0, s>>>(kd, q2, c.maxN, c.F, nb, j0, kd.splat_halo);
             } else if (j0 == 1) {
                 const dim3 g = grid_xcd(((long)maxV[k] + blk - 3) / (blk - 2) * blk, c.F, &nb, blk);
                 k_splat2<true><<<g, blk, 0, s>>>(kd, reinterpret_cast<const float2 *>(c.Q), c.maxN, c.F, nb);
@@ -2313,8 +2246,7 @@ void launch_step_stream(const CrfDev &c, const KernelDev *kds, const int *maxV, 
             const float *src = kd.val0;
             float *dst = kd.val1;
             // the pass left over by the pairs rides in the slice; with a few frames in flight (one pass per launch) the last pass does
-            static const char *sf = ab_env("LCCRF_SLICE_BLUR_MAX");                          // (A/B: frames-in-flight threshold)
-            const bool blur_in_slice = kd.D1 <= 9 && j0 < kd.D1 && (pairs ? ((kd.D1 - j0) & 1) && kd.D1 >= 3 : c.F <= (sf ? atoi(sf) : kSliceBlurMaxFrames));   // (j0 == d + 1: a 2-D lattice's three passes can all ride in the splat)
+            const bool blur_in_slice = kd.D1 <= 9 && j0 < kd.D1 && (pairs ? ((kd.D1 - j0) & 1) && kd.D1 >= 3 : c.F <= kSliceBlurMaxFrames);   // (j0 == d + 1: a 2-D lattice's three passes can all ride in the splat)
             const int n_own = blur_in_slice ? kd.D1 - 1 : kd.D1;                           // blur passes with a launch of their own
             for (int j = j0; j < n_own;) {
                 if (pairs && j + 1 < n_own) {             // one frame in flight: two passes per launch

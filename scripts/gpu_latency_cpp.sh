@@ -15,5 +15,5 @@ with open("/tmp/in_%d.bin" % N, "wb") as f:
         for a, dt in ((fr["obs"], np.float32), (fr["err"], np.float32), (fr["uv"], np.float32), (fr["init_label"], np.int16)):
             f.write(np.ascontiguousarray(a, dt).tobytes())
 PY
-env "$@" /tmp/latency_cpp /tmp/in_$N.bin 300
+env "$@" /tmp/latency_cpp /tmp/in_$N.bin 300 || exit 1
 done

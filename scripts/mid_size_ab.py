@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Mid-size frames on the streaming engine (launch-bound: 3000-6000 points, 6-D / 3-D kernels, 1 / 8 / 64 frames in flight): build and
-10-iteration inference time per batch.  A/B by environment, e.g. `LCCRF_PAIR_FUSE_MAX=1 python scripts/mid_size_ab.py` (two blur passes
-per launch for one frame only) against the default (also for small launches: <= 0.7 M vertices over all frames)."""
+10-iteration inference time per batch.  A/B by environment (instrumented library, LCCRF_LIB), e.g. `LCCRF_NO_PAIR_FUSE=1 python
+scripts/mid_size_ab.py` (one blur pass per launch) against the default (two per launch for one frame, and for small launches at any
+number of frames: <= 0.7 M vertices over all frames)."""
 import importlib, sys, time, numpy as np
 sys.path.insert(0, ".")
 pkg = importlib.import_module("lc-crf-slam_amd"); wl = importlib.import_module("lc-crf-slam_amd.workloads")
