@@ -172,6 +172,69 @@ int  lccrf_get_lattice(lccrf_handle h, int kernel, int32_t *offset_out, float *b
 int  lccrf_get_unary(lccrf_handle h, float *unary_out);
 
 /* ======================================================================================
+ * 1b. Object API on DEVICE arrays -- the reference's GPU interface (Thirdparty/DenseCRF/README.md "GPU Version": DenseCRFGPU<M>,
+ *     PottsPotentialGPU<M,F>::FromImage, "all pointers should be device pointers") on the same handles as section 1.
+ *
+ * Contract of every _device entry point (and of lccrf_add_image_kernel's image):
+ *   - device arrays are read and written in order on the handle's own stream (lccrf_get_stream); a call returns without waiting
+ *     for that work (a call behind an inference that has not been settled yet settles it first, as every entry point of section 1
+ *     does; the first use of new terms' lattices waits once for their sizes);
+ *   - inputs are consumed by work the call enqueues: the caller may overwrite or free them once the handle's stream has passed that
+ *     work (lccrf_synchronize, or an event recorded on lccrf_get_stream's stream).  Nothing keeps a pointer to a caller's array;
+ *   - the library does not synchronise with other streams: a producer on another stream must have finished, or the caller makes
+ *     the handle's stream wait for it (an event);
+ *   - every pointer is checked with hipPointerGetAttributes before anything is enqueued: device memory of the handle's device, or
+ *     host memory registered as pinned (hipHostMalloc / hipHostRegister) whose device address is the pointer itself.  Anything
+ *     else -- plain pageable host memory above all, which a kernel cannot read with XNACK off -- is refused with LCCRF_E_INVALID,
+ *     and so is an array the runtime knows to be shorter than what the call reads or writes.  NULL is accepted for n_points == 0.
+ * Results: after lccrf_inference the device results are complete behind lccrf_synchronize (which also settles the one-launch
+ * kernel's per-frame fallback, see lccrf_batch_run) or any call of section 1 that reads results.
+ *
+ * The reference's GPU example, its type names patched (include/lccrf_densecrf_gpu.hpp):
+ *      DenseCRFGPU<M> crf(W * H);                                              lccrf_create + lccrf_device_buffers
+ *      crf.setUnaryEnergyFromLabel(labelGPU, 0.5);                             lccrf_set_unary_from_label_device
+ *      crf.addPairwiseEnergy(PottsPotentialGPU<M, 2>::FromImage<>(W, H, 3, 3));                        lccrf_add_image_kernel, NONE
+ *      crf.addPairwiseEnergy(PottsPotentialGPU<M, 5>::FromImage<float>(W, H, 10, 60, rgbFeatGPU, 20)); lccrf_add_image_kernel, F32
+ *      crf.inference(10, true);                                                lccrf_inference (+ lccrf_synchronize)
+ *      short *mapGPU = crf.getMap();                                           lccrf_device_buffers' d_map
+ * ==================================================================================== */
+/* The handle's stream (a hipStream_t), as lccrf_batch_get_stream; lccrf_synchronize waits for that stream only.             */
+int  lccrf_get_stream(lccrf_handle h, void **stream);
+int  lccrf_synchronize(lccrf_handle h);
+
+/* DenseCRF::setUnaryEnergy on a device array [N][L] (copied into the handle on its stream).                                  */
+int  lccrf_set_unary_device(lccrf_handle h, const float *d_unary);
+/* setUnaryEnergyFromLabel on a device label array [N]: the unary kernel is enqueued at once (labels outside [0, L) count as
+ * unknown, as in the host path).  conf: n_labels values in host memory, or in device memory (read before the call returns).  */
+int  lccrf_set_unary_from_label_device(lccrf_handle h, const int16_t *d_label, const float *conf);
+/* new PottsPotential3D<M,F>(d_features, N, w) + addPairwiseEnergy: d_features [N][d] on the device, copied into the handle.   */
+int  lccrf_add_pairwise_device(lccrf_handle h, const float *d_features, int d, float w);
+/* PottsPotentialCPU<M,F>::FromImage(width, height, w, posdev, image, featuredev)   pairwise_cpu.h:33-51, the image on the device.
+ * Point i = y * width + x; width * height must equal n_points.
+ *   LCCRF_IMAGE_NONE : d = 2, features (x, y) / posdev; d_image must be NULL
+ *   LCCRF_IMAGE_U8   : d = 5, features (x, y) / posdev, (r, g, b) / featuredev from uint8 RGB [N][3] (HWC)
+ *   LCCRF_IMAGE_F32  : the same from float RGB [N][3]
+ * posdev (and featuredev with an image) must be positive and finite, else LCCRF_E_INVALID.                                    */
+#define LCCRF_IMAGE_NONE 0
+#define LCCRF_IMAGE_U8   1
+#define LCCRF_IMAGE_F32  2
+int  lccrf_add_image_kernel(lccrf_handle h, int width, int height, float w, float posdev, const void *d_image, int image_format,
+                            float featuredev);
+/* The handle-owned HBM arrays behind the reference's members unary_, current_, next_, tmp_, map_ (densecrf_base.h:27-28); any
+ * argument may be NULL.  The first call moves the handle's labels from pinned host memory to HBM (d_map, allocated with the
+ * handle): from then on inference(with_map), lccrf_build_map and the steps write them there, and lccrf_get_map copies them out.
+ * d_current is Q, d_next the engine's own next array (overwritten by every step, as next_ is), d_tmp a scratch array that the
+ * host-array plug-ins of section 1 use too.  The pointers stay valid until lccrf_destroy; a handle taken from the cache by
+ * lccrf_create starts with its labels in host memory again.                                                                   */
+int  lccrf_device_buffers(lccrf_handle h, const float **d_unary, float **d_current, float **d_next, float **d_tmp, int16_t **d_map);
+/* The plug-in points of section 1 (lccrf_pairwise_apply, lccrf_exp_and_normalize, lccrf_step_init, lccrf_map_of) on device
+ * arrays: the same kernels on the caller's pointers, no copy and no synchronisation.                                          */
+int  lccrf_pairwise_apply_device(lccrf_handle h, int kernel, float *d_out_values, const float *d_in_values);
+int  lccrf_exp_and_normalize_device(lccrf_handle h, float *d_out, const float *d_in, float scale, float relax);
+int  lccrf_step_init_device(lccrf_handle h, float *d_next_out);
+int  lccrf_map_of_device(lccrf_handle h, const float *d_prob, int16_t *d_map_out);
+
+/* ======================================================================================
  * 2. Batch API -- many independent frames in flight on one GPU.
  *    Every frame is one CRF of the object API; frames never interact.  Inputs may be
  *    handed over as host buffers (uploaded) or bound as DEVICE pointers (zero copy), so

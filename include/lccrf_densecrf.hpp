@@ -214,6 +214,22 @@ public:
         }
         return new PottsPotentialHIP<M, F>(std::move(all), N, weight);
     }
+
+    // pairwise_cpu.h:33-51 (PottsPotentialCPU<M,F>::FromImage), a HOST image: features (x, y) / posdev of pixel y * w + x, then its
+    // F - 2 channels / featuredev; features may be NULL for F = 2.  (The device image: lccrf_densecrf_gpu.hpp.)
+    template <class T = float>
+    static PottsPotentialHIP<M, F> *FromImage(int w, int h, float weight, float posdev, const T *features = nullptr, float featuredev = 0.0)
+    {
+        std::vector<float> all((size_t)F * w * h);
+        for (int hi = 0; hi < h; ++hi)
+            for (int wi = 0; wi < w; ++wi) {
+                const size_t idx = (size_t)hi * w + wi;
+                all[idx * F + 0] = (float)wi / posdev;
+                all[idx * F + 1] = (float)hi / posdev;
+                for (int i = 2; i < F; ++i) all[idx * F + i] = (float)features[idx * (F - 2) + (i - 2)] / featuredev;
+            }
+        return new PottsPotentialHIP<M, F>(std::move(all), w * h, weight);
+    }
 };
 
 // ---- DenseCRF3D<M> ---------------------------------------------------------------------

@@ -25,6 +25,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "lccrf.h")
 MAX_KERNELS = 8
 OPT_SINGLE_WORKGROUP = 1        # lccrf_option (include/lccrf.h)
 OPT_VERTEX_ORDER = 2
+IMAGE_NONE, IMAGE_U8, IMAGE_F32 = 0, 1, 2   # lccrf_add_image_kernel's image formats
 OK = 0
 _STATUS = {0: "OK", -1: "E_INVALID", -2: "E_NO_DEVICE", -3: "E_HIP", -4: "E_NOMEM", -5: "E_STATE",
            -6: "E_CAPACITY"}
@@ -103,6 +104,17 @@ def lib():
     L.lccrf_lattice_filter.argtypes = [C.c_int, _f32p, C.c_int, C.c_int, _f32p, C.c_int, _f32p, C.POINTER(C.c_int)]
     L.lccrf_get_norm.argtypes = [vp, C.c_int, _f32p]
     L.lccrf_get_lattice.argtypes = [vp, C.c_int, _i32p, _f32p, _i32p]
+    L.lccrf_get_stream.argtypes = [vp, C.POINTER(vp)]
+    L.lccrf_synchronize.argtypes = [vp]
+    L.lccrf_set_unary_device.argtypes = [vp, vp]
+    L.lccrf_set_unary_from_label_device.argtypes = [vp, vp, _f32p]
+    L.lccrf_add_pairwise_device.argtypes = [vp, vp, C.c_int, C.c_float]
+    L.lccrf_add_image_kernel.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_float, vp, C.c_int, C.c_float]
+    L.lccrf_device_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.lccrf_pairwise_apply_device.argtypes = [vp, C.c_int, vp, vp]
+    L.lccrf_exp_and_normalize_device.argtypes = [vp, vp, vp, C.c_float, C.c_float]
+    L.lccrf_step_init_device.argtypes = [vp, vp]
+    L.lccrf_map_of_device.argtypes = [vp, vp, vp]
     L.lccrf_batch_create.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(BatchDesc)]
     L.lccrf_batch_destroy.argtypes = [vp]
     L.lccrf_batch_destroy.restype = None
@@ -268,6 +280,54 @@ class DenseCRFHIP:
         m = np.empty(self.N, np.int16)
         _check(lib().lccrf_map_of(self.h, _p(p, _f32p), _p(m, _i16p)))
         return m
+
+    # -- device arrays (include/lccrf.h section 1b) ---------------------------------------
+    # Pointers are raw device addresses (e.g. torch_tensor.data_ptr()), read and written in order on the handle's stream
+    # (stream()); work on another stream that produces them must be ordered before it by the caller (an event, or
+    # torch.cuda.ExternalStream(h.stream()).wait_stream(producer)).
+    def stream(self):
+        """The handle's own stream (a hipStream_t address)."""
+        s = C.c_void_p()
+        _check(lib().lccrf_get_stream(self.h, C.byref(s)))
+        return s.value or 0
+
+    def synchronize(self):
+        _check(lib().lccrf_synchronize(self.h))
+
+    def set_unary_device(self, d_unary):
+        _check(lib().lccrf_set_unary_device(self.h, C.c_void_p(d_unary)))
+
+    def set_unary_from_label_device(self, d_label, conf):
+        cf = _f32(np.broadcast_to(np.asarray(conf, np.float32), (self.L,)))
+        _check(lib().lccrf_set_unary_from_label_device(self.h, C.c_void_p(d_label), _p(cf, _f32p)))
+
+    def add_pairwise_device(self, d_features, d, w):
+        _check(lib().lccrf_add_pairwise_device(self.h, C.c_void_p(d_features), int(d), float(w)))
+        self._d.append(int(d))
+
+    def add_image_kernel(self, width, height, w, posdev, d_image=None, image_format=IMAGE_NONE, featuredev=0.0):
+        """PottsPotentialCPU<M,F>::FromImage with the image (uint8 or float RGB, HWC) on the device."""
+        _check(lib().lccrf_add_image_kernel(self.h, int(width), int(height), float(w), float(posdev),
+                                            C.c_void_p(d_image) if d_image else None, int(image_format), float(featuredev)))
+        self._d.append(2 if image_format == IMAGE_NONE else 5)
+
+    def device_buffers(self):
+        """Addresses of the handle-owned HBM arrays: unary, current (Q), next, tmp, map.  Moves the labels to HBM."""
+        p = [C.c_void_p() for _ in range(5)]
+        _check(lib().lccrf_device_buffers(self.h, *[C.byref(x) for x in p]))
+        return dict(zip(("unary", "current", "next", "tmp", "map"), (x.value for x in p)))
+
+    def pairwise_apply_device(self, k, d_out, d_in):
+        _check(lib().lccrf_pairwise_apply_device(self.h, int(k), C.c_void_p(d_out), C.c_void_p(d_in)))
+
+    def exp_and_normalize_device(self, d_out, d_in, scale=1.0, relax=1.0):
+        _check(lib().lccrf_exp_and_normalize_device(self.h, C.c_void_p(d_out), C.c_void_p(d_in), float(scale), float(relax)))
+
+    def step_init_device(self, d_next):
+        _check(lib().lccrf_step_init_device(self.h, C.c_void_p(d_next)))
+
+    def map_of_device(self, d_prob, d_map):
+        _check(lib().lccrf_map_of_device(self.h, C.c_void_p(d_prob), C.c_void_p(d_map)))
 
     # -- results -----------------------------------------------------------------------
     def map(self):

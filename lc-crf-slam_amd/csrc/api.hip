@@ -686,7 +686,7 @@ struct Engine {
     // setUnaryEnergyFromLabel (densecrf3d.h:100-130) is deferred: the 2L+1 energies travel as a kernel
     // argument and either the one-launch-per-frame kernel derives the unaries itself or ensure_unary()
     // launches the small kernel when somebody needs the array.  `label` must stay readable until then.
-    void defer_unary_from_label(const int16_t *label, const float *conf)
+    UnaryTable label_table(const float *conf) const
     {
         // densecrf3d.h:109-115.  log(float) binds to the float overload at the reference's call
         // site (src/Tracking.cc:21-43 sees `using namespace std` from include/Tracking.h:55).
@@ -696,6 +696,12 @@ struct Engine {
             tb.v[1 + i] = -logf((1.0f - conf[i]) / (L - 1));
             tb.v[1 + L + i] = -logf(conf[i]);
         }
+        return tb;
+    }
+
+    void defer_unary_from_label(const int16_t *label, const float *conf)
+    {
+        const UnaryTable tb = label_table(conf);
         crf.unary = unary_own;
         unary_deferred = true;
         unary_is_label = true;
@@ -1038,6 +1044,7 @@ struct lccrf_crf {
     int *stage_n = nullptr;         // pinned [1]: the point count where the kernels of a SLAM frame read it (no upload command)
     bool label_stage_busy = false;  // a kernel that reads stage_i16 may still be pending
     int16_t *map_pin = nullptr;     // pinned [cap]: the kernels write the MAP labels straight into host memory
+    int16_t *map_dev = nullptr;     // device [cap]: where they go instead once lccrf_device_buffers has handed out the labels (section 1b)
 };
 
 namespace {
@@ -1275,6 +1282,7 @@ int lccrf_create(lccrf_handle *out, int device_id, int n_points, int n_labels)
         if (!h) return fail(LCCRF_E_NOMEM, "host allocation failed");
         h->cap = capacity_for(n_points);
         rc = h->eng.init(device_id, 1, h->cap, n_labels);
+        if (!rc) h->map_dev = h->eng.crf.map;             // (the engine's own label array; a handle starts with its labels in map_pin)
         // frames far beyond SLAM's (BASELINE config 5 through the reference's own interface): inference() in locality mode
         h->eng.allow_perm = h->eng.perm_scoped = h->cap >= Engine::perm_min_points();
         if (!rc) rc = h->eng.mem.alloc_pinned(&h->stage_i16, h->cap);
@@ -1666,6 +1674,10 @@ int lccrf_get_map(lccrf_handle h, int16_t *map_out)
     }
     bool seen_done = false;
     { int rl = e.resolve_late(&seen_done); if (rl) return rl; }
+    if (e.crf.map != h->map_pin) {                        // device labels (lccrf_device_buffers): a copy through the pinned array
+        if (h->N) HIP_TRY(hipMemcpyAsync(h->map_pin, e.crf.map, (size_t)h->N * sizeof(int16_t), hipMemcpyDeviceToHost, e.stream));
+        seen_done = false;
+    }
     if (!seen_done) HIP_TRY(hipStreamSynchronize(e.stream));
     if (h->N) memcpy(map_out, h->map_pin, (size_t)h->N * sizeof(int16_t));   // written there by the kernels
     e.idle_by_done = seen_done;
@@ -1740,6 +1752,236 @@ int lccrf_get_lattice(lccrf_handle h, int kernel, int32_t *offset_out, float *ba
             HIP_TRY(hipMemcpy(nbr_out + (size_t)j * V * 2, k.nbr + (size_t)j * k.Epad * 2, (size_t)V * 2 * sizeof(int),
                               hipMemcpyDeviceToHost));
     }
+    return LCCRF_OK;
+}
+
+// --------------------------------------------------------------------------------------
+// object API on device arrays (include/lccrf.h section 1b)
+// --------------------------------------------------------------------------------------
+// A caller's array that a kernel or copy of handle h is about to touch: device memory of h's device, or host memory registered as
+// pinned whose device address is the pointer itself -- anything else (plain pageable host memory above all) would fault the card
+// with XNACK off, so it is refused here, before anything is enqueued.  When the runtime knows the allocation's extent, the `bytes`
+// the call will touch must lie inside it.
+static int check_device_array(const lccrf_crf *h, const void *p, size_t bytes, const char *what)
+{
+    if (!bytes) return LCCRF_OK;
+    if (!p) return fail(LCCRF_E_INVALID, "%s is NULL", what);
+    hipPointerAttribute_t a{};
+    const hipError_t e = hipPointerGetAttributes(&a, p);
+    (void)hipGetLastError();                             // (an unknown pointer leaves an error behind; no later HIP_TRY may see it)
+    if (e != hipSuccess || a.isManaged)
+        return fail(LCCRF_E_INVALID, "%s (%p) is neither device memory nor pinned host memory", what, p);
+    if (a.type == hipMemoryTypeDevice) {
+        if (a.device != h->eng.device)
+            return fail(LCCRF_E_INVALID, "%s (%p) is memory of device %d, the handle's is device %d", what, p, a.device, h->eng.device);
+    } else if (a.type == hipMemoryTypeHost) {
+        if (a.devicePointer != p)
+            return fail(LCCRF_E_INVALID, "%s (%p) is pinned host memory whose device address differs (%p)", what, p, a.devicePointer);
+    } else {
+        return fail(LCCRF_E_INVALID, "%s (%p) is neither device memory nor pinned host memory", what, p);
+    }
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) == hipSuccess) {
+        const char *b = static_cast<const char *>(base), *q = static_cast<const char *>(p);
+        if (q < b || (size_t)(q - b) > size || size - (size_t)(q - b) < bytes)
+            return fail(LCCRF_E_INVALID, "%s: %zu bytes from %p run past the end of its allocation (%zu bytes from %p)", what, bytes, p,
+                        size, base);
+    } else {
+        (void)hipGetLastError();
+    }
+    return LCCRF_OK;
+}
+
+// the caller's features [N][d] (copy) or an image (position / RGB) -> a new term's own feature buffer, on the handle's stream
+static int add_kernel_staged(lccrf_crf *h, int d, float w, const void *src, int mode, int width, float posdev, float featuredev)
+{
+    Engine &e = h->eng;
+    { int rl = e.resolve_late(); if (rl) return rl; }
+    int rc = e.add_kernel(d, w, true, false);
+    if (rc) return rc;
+    KernelState &ks = e.kernels.back();
+    launch_stage_features(ks.feat_own, src, h->N, d, mode, width, posdev, featuredev, e.stream);
+    HIP_TRY(hipGetLastError());
+    ks.dev.feat = ks.feat_own;
+    e.sync_views();
+    e.sizes_known = false;                               // (built lazily with any other pending term, as by lccrf_add_pairwise)
+    return LCCRF_OK;
+}
+
+int lccrf_get_stream(lccrf_handle h, void **stream)
+{
+    if (!h || !stream) return fail(LCCRF_E_INVALID, "handle / stream is NULL");
+    *stream = (void *)h->eng.stream;
+    return LCCRF_OK;
+}
+
+int lccrf_synchronize(lccrf_handle h)
+{
+    CHECK_H(h);
+    { int rl = h->eng.resolve_late(); if (rl) return rl; }   // (settles a one-launch inference: its fallback re-run included)
+    HIP_TRY(hipStreamSynchronize(h->eng.stream));
+    return LCCRF_OK;
+}
+
+int lccrf_set_unary_device(lccrf_handle h, const float *d_unary)
+{
+    CHECK_H(h);
+    Engine &e = h->eng;
+    const size_t n = (size_t)h->N * e.L;
+    { int rc = check_device_array(h, d_unary, n * sizeof(float), "d_unary"); if (rc) return rc; }
+    { int rl = e.resolve_late(); if (rl) return rl; }
+    if (n) HIP_TRY(hipMemcpyAsync(e.unary_own, d_unary, n * sizeof(float), hipMemcpyDefault, e.stream));
+    e.crf.unary = e.unary_own;
+    e.unary_deferred = false;
+    e.unary_is_label = false;
+    e.unary_p_valid = false;
+    e.unary_set = true;
+    return LCCRF_OK;
+}
+
+int lccrf_set_unary_from_label_device(lccrf_handle h, const int16_t *d_label, const float *conf)
+{
+    CHECK_H(h);
+    Engine &e = h->eng;
+    if (!conf) return fail(LCCRF_E_INVALID, "conf is NULL");
+    if (e.L < 2) return fail(LCCRF_E_INVALID, "setUnaryEnergyFromLabel needs >= 2 labels");
+    { int rc = check_device_array(h, d_label, (size_t)h->N * sizeof(int16_t), "d_label"); if (rc) return rc; }
+    // conf: n_labels host values -- or device values (the reference's GPU interface hands device pointers only), read here
+    float cf[LCCRF_MAX_LABELS];
+    hipPointerAttribute_t a{};
+    const hipError_t ea = hipPointerGetAttributes(&a, conf);
+    (void)hipGetLastError();
+    if (ea == hipSuccess && !a.isManaged && a.type == hipMemoryTypeDevice) {
+        if (a.device != e.device) return fail(LCCRF_E_INVALID, "conf (%p) is memory of device %d, the handle's is device %d", conf, a.device, e.device);
+        { int rc = check_device_array(h, conf, (size_t)e.L * sizeof(float), "conf"); if (rc) return rc; }
+        HIP_TRY(hipMemcpy(cf, conf, (size_t)e.L * sizeof(float), hipMemcpyDeviceToHost));
+    } else {
+        memcpy(cf, conf, (size_t)e.L * sizeof(float));
+    }
+    { int rl = e.resolve_late(); if (rl) return rl; }
+    // enqueued now (not deferred like the host path's labels): the caller's array is read by this kernel only.  The energies go in
+    // the caller's point order whatever the lattices' order -- they are raw unaries from here on (permuted like lccrf_set_unary's).
+    CrfDev c = e.crf;
+    c.unary = e.unary_own;
+    c.perm = nullptr;
+    if (h->N) {
+        launch_unary_from_label_tbl(c, d_label, e.label_table(cf), e.stream);
+        HIP_TRY(hipGetLastError());
+    }
+    e.crf.unary = e.unary_own;
+    e.unary_deferred = false;
+    e.unary_is_label = false;
+    e.unary_p_valid = false;
+    e.unary_set = true;
+    return LCCRF_OK;
+}
+
+int lccrf_add_pairwise_device(lccrf_handle h, const float *d_features, int d, float w)
+{
+    CHECK_H(h);
+    if (d < 1 || d > LCCRF_MAX_DIMS) return fail(LCCRF_E_INVALID, "feature dims %d not in [1,%d]", d, LCCRF_MAX_DIMS);
+    { int rc = check_device_array(h, d_features, (size_t)h->N * d * sizeof(float), "d_features"); if (rc) return rc; }
+    return add_kernel_staged(h, d, w, d_features, kStageCopy, 1, 1.0f, 1.0f);
+}
+
+int lccrf_add_image_kernel(lccrf_handle h, int width, int height, float w, float posdev, const void *d_image, int image_format,
+                           float featuredev)
+{
+    CHECK_H(h);
+    if (width < 0 || height < 0 || (long)width * height != h->N)
+        return fail(LCCRF_E_INVALID, "width * height (%d x %d) must equal the handle's n_points (%d)", width, height, h->N);
+    if (!(posdev > 0.0f) || !std::isfinite(posdev)) return fail(LCCRF_E_INVALID, "posdev must be positive and finite");
+    if (image_format == LCCRF_IMAGE_NONE) {
+        if (d_image) return fail(LCCRF_E_INVALID, "LCCRF_IMAGE_NONE takes no image");
+        return add_kernel_staged(h, 2, w, nullptr, kStagePosition, width, posdev, 1.0f);
+    }
+    if (image_format != LCCRF_IMAGE_U8 && image_format != LCCRF_IMAGE_F32)
+        return fail(LCCRF_E_INVALID, "image_format %d is none of LCCRF_IMAGE_NONE / _U8 / _F32", image_format);
+    if (!(featuredev > 0.0f) || !std::isfinite(featuredev)) return fail(LCCRF_E_INVALID, "featuredev must be positive and finite");
+    const size_t elem = image_format == LCCRF_IMAGE_U8 ? 1 : sizeof(float);
+    { int rc = check_device_array(h, d_image, (size_t)h->N * 3 * elem, "d_image"); if (rc) return rc; }
+    return add_kernel_staged(h, 5, w, d_image, image_format == LCCRF_IMAGE_U8 ? kStageImageU8 : kStageImageF32, width, posdev,
+                             featuredev);
+}
+
+int lccrf_device_buffers(lccrf_handle h, const float **d_unary, float **d_current, float **d_next, float **d_tmp, int16_t **d_map)
+{
+    CHECK_H(h);
+    Engine &e = h->eng;
+    { int rl = e.resolve_late(); if (rl) return rl; }
+    if (d_tmp) { int rc = e.need_io(); if (rc) return rc; }
+    if (e.crf.map != h->map_dev) {                       // from now on the labels are written to HBM (map_host stays: no pinned fast path)
+        if (h->N) HIP_TRY(hipMemcpyAsync(h->map_dev, h->map_pin, (size_t)h->N * sizeof(int16_t), hipMemcpyHostToDevice, e.stream));
+        e.crf.map = h->map_dev;
+    }
+    if (d_unary) *d_unary = e.unary_own;
+    if (d_current) *d_current = e.crf.Q;
+    if (d_next) *d_next = e.crf.next;
+    if (d_tmp) *d_tmp = e.io_b;
+    if (d_map) *d_map = h->map_dev;
+    return LCCRF_OK;
+}
+
+int lccrf_pairwise_apply_device(lccrf_handle h, int kernel, float *d_out, const float *d_in)
+{
+    CHECK_H(h);
+    CHECK_K(h, kernel);
+    Engine &e = h->eng;
+    const size_t n = (size_t)h->N * e.L * sizeof(float);
+    { int rc = check_device_array(h, d_out, n, "d_out"); if (rc) return rc; }
+    { int rc = check_device_array(h, d_in, n, "d_in"); if (rc) return rc; }
+    int rc = e.resolve_late();
+    if (!rc) rc = e.ensure_plain();
+    if (!rc) rc = e.learn_sizes();                        // builds the lattice if it only exists as staged features
+    if (rc) return rc;
+    if (!n) return LCCRF_OK;
+    launch_filter(e.kdevs[kernel], e.crf, e.maxV[kernel], d_in, d_out, 1, e.stream);
+    HIP_TRY(hipGetLastError());
+    return LCCRF_OK;
+}
+
+int lccrf_exp_and_normalize_device(lccrf_handle h, float *d_out, const float *d_in, float scale, float relax)
+{
+    CHECK_H(h);
+    Engine &e = h->eng;
+    const size_t n = (size_t)h->N * e.L * sizeof(float);
+    { int rc = check_device_array(h, d_out, n, "d_out"); if (rc) return rc; }
+    { int rc = check_device_array(h, d_in, n, "d_in"); if (rc) return rc; }
+    { int rl = e.resolve_late(); if (rl) return rl; }
+    if (!n) return LCCRF_OK;
+    launch_exp_and_normalize(e.crf, d_in, d_out, scale, relax, e.stream);
+    HIP_TRY(hipGetLastError());
+    return LCCRF_OK;
+}
+
+int lccrf_step_init_device(lccrf_handle h, float *d_next)
+{
+    CHECK_H(h);
+    Engine &e = h->eng;
+    const size_t n = (size_t)h->N * e.L * sizeof(float);
+    { int rc = check_device_array(h, d_next, n, "d_next"); if (rc) return rc; }
+    if (!e.unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
+    int rc = e.resolve_late();
+    if (!rc) rc = e.ensure_plain();
+    if (!rc) rc = e.ensure_unary();
+    if (rc) return rc;
+    if (!n) return LCCRF_OK;
+    launch_step_init(e.crf, d_next, e.stream);
+    HIP_TRY(hipGetLastError());
+    return LCCRF_OK;
+}
+
+int lccrf_map_of_device(lccrf_handle h, const float *d_prob, int16_t *d_map)
+{
+    CHECK_H(h);
+    Engine &e = h->eng;
+    { int rc = check_device_array(h, d_prob, (size_t)h->N * e.L * sizeof(float), "d_prob"); if (rc) return rc; }
+    { int rc = check_device_array(h, d_map, (size_t)h->N * sizeof(int16_t), "d_map"); if (rc) return rc; }
+    { int rl = e.resolve_late(); if (rl) return rl; }
+    if (!h->N) return LCCRF_OK;
+    launch_map_of(e.crf, d_prob, d_map, e.stream);
+    HIP_TRY(hipGetLastError());
     return LCCRF_OK;
 }
 

@@ -186,6 +186,11 @@ void launch_exp_and_normalize(const CrfDev &c, const float *in, float *out, floa
 void launch_step_init(const CrfDev &c, float *out, hipStream_t s);
 void launch_filter(const KernelDev &kd, const CrfDev &c, int maxV, const float *in, float *out, int accumulate, hipStream_t s);
 hipError_t time_blur_pass(const KernelDev &kd, int F, int maxV, int L, int reps, hipStream_t s, float *ms_per_launch);
+// object API, device inputs (device_inputs.hip): dst[i][0..d) for i < n from a caller's [n][d] array (copy), from the pixel position
+// (x, y) / posdev of point i = y * width + x (position), or from that plus an RGB pixel [n][3] / featuredev (uint8 or float image)
+enum { kStageCopy = 0, kStagePosition = 1, kStageImageU8 = 2, kStageImageF32 = 3 };
+void launch_stage_features(float *dst, const void *src, int n, int d, int mode, int width, float posdev, float featuredev,
+                           hipStream_t s);
 // out[f] = clamp(in[f], 0, maxN); *bad (pinned host memory) is set to 1 if anything had to be clamped
 void launch_validate_npoints(const int *in, int *out, int F, int maxN, int *bad, hipStream_t s);
 
