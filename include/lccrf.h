@@ -235,6 +235,53 @@ int  lccrf_step_init_device(lccrf_handle h, float *d_next_out);
 int  lccrf_map_of_device(lccrf_handle h, const float *d_prob, int16_t *d_map_out);
 
 /* ======================================================================================
+ * 1c. Gradients of inference() -- reverse mode through DenseCRF::inference (densecrf_base.h:65-91) with respect to the unary
+ *     energies and the weight of every pairwise term (the reference's README: "does not support gradient computation").
+ *
+ * The forward, for unary U [N][L], T = n_iterations, r = relax, term k with norm n_k, weight w_k and lattice filter
+ * Phi_k = alpha S^T B_d .. B_1 B_0 S (S the splat, B_j the Jacobi blur pass along axis j, alpha = 1/(1+2^-d)):
+ *      Q_0 = softmax(-U)
+ *      x_t = -U + sum_k w_k n_k . Phi_k(Q_{t-1})                        t = 1 .. T
+ *      P_t = softmax(x_t),   Q_t = P_t (r == 1)   or   (1-r) Q_{t-1} + r P_t
+ * Given G_T = dL/dQ_T, with <.,.> the per-point sum over labels and P_0 = Q_0:
+ *      for t = T .. 1:
+ *          gamma_t   = r P_t . (G_t - <G_t, P_t>)
+ *          dL/dU    -= gamma_t
+ *          dL/dw_k  += sum_{i,l} gamma_t . n_k . Phi_k(Q_{t-1})
+ *          G_{t-1}   = (1-r) G_t + sum_k w_k Phi_k^T(n_k . gamma_t)
+ *      dL/dU -= P_0 . (G_0 - <G_0, P_0>)
+ * Phi_k^T = alpha S^T B_0 .. B_d S: the same splat and slice, the blur passes in REVERSE axis order (every pass is symmetric -- n1(v)
+ * = u exactly when n2(u) = v -- but the passes do not commute on a sparse lattice, so Phi_k is not).  The derivative treats the
+ * reference's polynomial fast_exp (densecrf3d.h:51-67) as exp: the softmax Jacobian is formed from the forward's own P_t, computed
+ * with the forward's arithmetic.  Not differentiated: the features (kernel bandwidths, positions), the MAP labels, and the label-
+ * and-confidence form of the unary (take dL/dU and chain through that formula yourself).                                          */
+
+/* PottsPotential3D::w_ of term `kernel` (set after construction).  The lattice and norm stay; the next inference equals, bit for
+ * bit, that of a handle built with weight w.  Anything derived from w (the fused engines' w*norm products, prepared launch records)
+ * is invalidated.                                                                                                              */
+int  lccrf_set_pairwise_weight(lccrf_handle h, int kernel, float w);
+/* Gradients of lccrf_inference(h, n_iterations, -, relax) on the handle's current unary and terms.
+ * d_grad_prob [N][L] = dL/dQ_T, d_grad_unary [N][L] (overwritten), d_grad_weights [K] (overwritten; may be NULL).  Device arrays,
+ * checked as in section 1b, on the handle's stream, no host synchronisation (but the first use of new terms' lattices, which waits
+ * once for their sizes, as every entry point does).
+ *   - Self-contained: the forward is replayed on the step path (lccrf_start_inference + n_iterations x lccrf_step_inference; frames
+ *     of >= 8192 points use the plain build, re-built once after a locality-mode inference()), keeping Q_0 .. Q_{T-1}; Phi_k(Q_{t-1})
+ *     and P_t are recomputed in the sweep.  No earlier lccrf_inference is needed.
+ *   - Afterwards Q (lccrf_device_buffers' d_current, lccrf_get_probability) holds exactly what lccrf_inference(h, n_iterations, 0,
+ *     relax) would have left, bit for bit.
+ *   - Deterministic: no float atomics; the weight gradient is a sum of per-workgroup partials in a fixed order -- the same bits
+ *     from run to run.
+ *   - Memory: a handle-owned HBM area of 4 * (N4*L*(T + K + 1) + max(T,1) * K * B) bytes, N4 = N rounded up to a multiple of 4
+ *     (the phantom points' rows, kept zero), B = ceil(N / R) workgroups of
+ *     R = 256, 128, 64, 32, 16 points for L <= 4, 8, 16, 32, 64 (N = 2000, L = 2, K = 2, T = 5: 128 KB; 320 x 240, L = 21, K = 2,
+ *     T = 10: 84 MB).  Allocated by the first call that needs more, freed by lccrf_destroy (and lccrf_trim_cache); a failed
+ *     allocation returns LCCRF_E_NOMEM and leaves the handle as it was.  lccrf_inference never allocates it.
+ *   - Errors: LCCRF_E_INVALID for n_iterations < 0, a relax that is not finite, or a device array that section 1b refuses;
+ *     LCCRF_E_STATE without unary energies.  K = 0 is legal (d_grad_weights then receives nothing).                             */
+int  lccrf_inference_backward(lccrf_handle h, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
+                              float *d_grad_weights);
+
+/* ======================================================================================
  * 2. Batch API -- many independent frames in flight on one GPU.
  *    Every frame is one CRF of the object API; frames never interact.  Inputs may be
  *    handed over as host buffers (uploaded) or bound as DEVICE pointers (zero copy), so

@@ -115,6 +115,8 @@ def lib():
     L.lccrf_exp_and_normalize_device.argtypes = [vp, vp, vp, C.c_float, C.c_float]
     L.lccrf_step_init_device.argtypes = [vp, vp]
     L.lccrf_map_of_device.argtypes = [vp, vp, vp]
+    L.lccrf_set_pairwise_weight.argtypes = [vp, C.c_int, C.c_float]
+    L.lccrf_inference_backward.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp]
     L.lccrf_batch_create.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(BatchDesc)]
     L.lccrf_batch_destroy.argtypes = [vp]
     L.lccrf_batch_destroy.restype = None
@@ -328,6 +330,16 @@ class DenseCRFHIP:
 
     def map_of_device(self, d_prob, d_map):
         _check(lib().lccrf_map_of_device(self.h, C.c_void_p(d_prob), C.c_void_p(d_map)))
+
+    # -- gradients of inference() (include/lccrf.h section 1c; the torch layer: autograd.py) ----------------------------------
+    def set_pairwise_weight(self, k, w):
+        """PottsPotential3D::w_ of term k; the next inference equals that of a handle built with weight w."""
+        _check(lib().lccrf_set_pairwise_weight(self.h, int(k), float(w)))
+
+    def inference_backward_device(self, n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights=None):
+        """dL/dU [N][L] and dL/dw [K] of inference(n_iterations, relax) from dL/dQ [N][L]; device addresses, on stream()."""
+        _check(lib().lccrf_inference_backward(self.h, int(n_iterations), float(relax), C.c_void_p(d_grad_prob),
+                                              C.c_void_p(d_grad_unary), C.c_void_p(d_grad_weights) if d_grad_weights else None))
 
     # -- results -----------------------------------------------------------------------
     def map(self):

@@ -158,6 +158,18 @@ struct Engine {
     int *npoints_bad = nullptr;        // pinned: set by the validation kernel when a bound n_points[f] is outside [0, maxN]
     float *io_a = nullptr, *io_b = nullptr;   // device [Fcap][maxN][L] each: caller buffers of apply / expAndNormalize / ... (lazy)
     int16_t *io_map = nullptr;
+    // lccrf_inference_backward's area (engine.h: BackwardArea): its own allocation, grown on demand and freed with the handle's use
+    // (recycle) -- a parked handle does not keep it
+    unsigned char *bwd_area = nullptr;
+    size_t bwd_area_bytes = 0;
+    void free_backward_area()
+    {
+        if (!bwd_area) return;
+        if (stream) (void)hipStreamSynchronize(stream);
+        (void)hipFree(bwd_area);
+        bwd_area = nullptr;
+        bwd_area_bytes = 0;
+    }
 
     int need_io()
     {
@@ -336,6 +348,7 @@ struct Engine {
     {
         park_check = false;
         if (stream) (void)hipStreamSynchronize(stream);
+        free_backward_area();
         if (fb) {
             fb->destroy();
             delete fb;
@@ -480,6 +493,7 @@ struct Engine {
         else if (stream && !idle_by_done) (void)hipStreamSynchronize(stream);
         idle_by_done = idle_needs_done = false;
         labels_armed = done_armed = false;
+        free_backward_area();
         for (auto &ks : kernels) spare.push_back(ks);
         kernels.clear();
         F = Fcap;
@@ -1981,6 +1995,75 @@ int lccrf_map_of_device(lccrf_handle h, const float *d_prob, int16_t *d_map)
     { int rl = e.resolve_late(); if (rl) return rl; }
     if (!h->N) return LCCRF_OK;
     launch_map_of(e.crf, d_prob, d_map, e.stream);
+    HIP_TRY(hipGetLastError());
+    return LCCRF_OK;
+}
+
+// --------------------------------------------------------------------------------------
+// section 1c: gradients of inference()
+
+int lccrf_set_pairwise_weight(lccrf_handle h, int kernel, float w)
+{
+    CHECK_H(h);
+    CHECK_K(h, kernel);
+    Engine &e = h->eng;
+    { int rl = e.resolve_late(); if (rl) return rl; }   // (a pending one-launch inference may still be re-run with the old weight)
+    e.kernels[kernel].dev.w = w;
+    e.sync_views();
+    e.lean_prep.valid = false;                            // whatever was prepared for the old weights is rewritten
+    e.lean_prep.seen_key = 0;
+    return LCCRF_OK;
+}
+
+int lccrf_inference_backward(lccrf_handle h, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
+                             float *d_grad_weights)
+{
+    CHECK_H(h);
+    Engine &e = h->eng;
+    if (n_iterations < 0) return fail(LCCRF_E_INVALID, "n_iterations < 0");
+    if (!std::isfinite(relax)) return fail(LCCRF_E_INVALID, "relax must be finite");
+    const int K = (int)e.kernels.size(), T = n_iterations;
+    const size_t nl = (size_t)h->N * e.L;
+    { int rc = check_device_array(h, d_grad_prob, nl * sizeof(float), "d_grad_prob"); if (rc) return rc; }
+    { int rc = check_device_array(h, d_grad_unary, nl * sizeof(float), "d_grad_unary"); if (rc) return rc; }
+    if (d_grad_weights) { int rc = check_device_array(h, d_grad_weights, (size_t)K * sizeof(float), "d_grad_weights"); if (rc) return rc; }
+    if (!e.unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
+    { int rl = e.resolve_late(); if (rl) return rl; }
+    // the area first: a handle that cannot have it is left as it was
+    const size_t need = backward_bytes(h->N, e.L, K, T);
+    if (need > e.bwd_area_bytes) {
+        e.free_backward_area();
+        void *p = nullptr;
+        const hipError_t ea = hipMalloc(&p, need);
+        if (ea != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ea == hipErrorOutOfMemory ? LCCRF_E_NOMEM : LCCRF_E_HIP, "hipMalloc(%zu bytes) for the backward area: %s", need,
+                        hipGetErrorString(ea));
+        }
+        e.bwd_area = static_cast<unsigned char *>(p);
+        e.bwd_area_bytes = need;
+        HIP_TRY(hipMemsetAsync(p, 0, need, e.stream));   // (the phantom rows stay zero: engine.h, BackwardArea)
+    }
+    BackwardArea ar;
+    const size_t ns = backward_stride(h->N, e.L);
+    ar.hist = reinterpret_cast<float *>(e.bwd_area);
+    ar.phi = ar.hist + (size_t)T * ns;
+    ar.G = ar.phi + (size_t)K * ns;
+    ar.partial = ar.G + ns;
+    // replay: inference(T, 0, relax) on the step path (Engine::step), Q_0 .. Q_{T-1} kept
+    int rc = e.start();                                   // (ensure_plain: frames in locality mode are re-built the plain way once)
+    if (!rc) rc = e.learn_sizes();
+    if (rc) return rc;
+    for (int t = 0; t < T; ++t) {
+        if (nl) HIP_TRY(hipMemcpyAsync(ar.hist + (size_t)t * ns, e.crf.Q, nl * sizeof(float), hipMemcpyDeviceToDevice, e.stream));
+        if ((rc = e.step(relax))) return rc;
+    }
+    if (nl) HIP_TRY(hipMemcpyAsync(ar.G, d_grad_prob, nl * sizeof(float), hipMemcpyDeviceToDevice, e.stream));
+    if (!nl) {                                            // nothing to differentiate: dL/dw = 0
+        if (d_grad_weights && K) HIP_TRY(hipMemsetAsync(d_grad_weights, 0, (size_t)K * sizeof(float), e.stream));
+        return LCCRF_OK;
+    }
+    launch_backward_sweep(e.crf, e.kdevs.data(), e.maxV.data(), h->N, T, relax, ar, d_grad_unary, d_grad_weights, e.stream);
     HIP_TRY(hipGetLastError());
     return LCCRF_OK;
 }

@@ -184,7 +184,10 @@ void launch_map(const CrfDev &c, hipStream_t s);
 void launch_map_of(const CrfDev &c, const float *prob, int16_t *map, hipStream_t s);
 void launch_exp_and_normalize(const CrfDev &c, const float *in, float *out, float scale, float relax, hipStream_t s);
 void launch_step_init(const CrfDev &c, float *out, hipStream_t s);
-void launch_filter(const KernelDev &kd, const CrfDev &c, int maxV, const float *in, float *out, int accumulate, hipStream_t s);
+// reverse = 1: the blur passes in reverse axis order (d .. 0) -- the TRANSPOSED filter alpha S^T B_0 .. B_d S of the one the
+// forward applies (alpha S^T B_d .. B_0 S; every pass is symmetric, their product is not).  `out` may be `in` (the splat reads it first).
+void launch_filter(const KernelDev &kd, const CrfDev &c, int maxV, const float *in, float *out, int accumulate, hipStream_t s,
+                   int reverse = 0);
 hipError_t time_blur_pass(const KernelDev &kd, int F, int maxV, int L, int reps, hipStream_t s, float *ms_per_launch);
 // object API, device inputs (device_inputs.hip): dst[i][0..d) for i < n from a caller's [n][d] array (copy), from the pixel position
 // (x, y) / posdev of point i = y * width + x (position), or from that plus an RGB pixel [n][3] / featuredev (uint8 or float image)
@@ -193,6 +196,24 @@ void launch_stage_features(float *dst, const void *src, int n, int d, int mode, 
                            hipStream_t s);
 // out[f] = clamp(in[f], 0, maxN); *bad (pinned host memory) is set to 1 if anything had to be clamped
 void launch_validate_npoints(const int *in, int *out, int F, int maxN, int *bad, hipStream_t s);
+
+// ---- mean-field backward (csrc/meanfield_backward.hip; include/lccrf.h section 1c) ---------------------------------
+// The handle-owned area of one lccrf_inference_backward: Q_0 .. Q_{T-1} of the replay, one [N][L] array per term, dL/dQ_t and the
+// per-workgroup partials of the weight gradient -- backward_bytes() in all, zeroed when allocated.  The [N][L] arrays are
+// backward_stride() floats apart: N rounded up to a multiple of 4 rows, the phantom points' rows (quirk Q1) staying zero -- a splat
+// over a lattice whose rows list them reads 0 there, as it reads the engine's own Q.
+struct BackwardArea {
+    float *hist;          // [T][N][L]
+    float *phi;           // [K][N][L]
+    float *G;             // [N][L]
+    float *partial;       // [max(T,1)][K][backward_blocks(N, L)]
+};
+int backward_blocks(int n, int L);
+size_t backward_stride(int n, int L);
+size_t backward_bytes(int n, int L, int K, int T);
+// the reverse sweep (the replay has filled ar.hist and ar.G = dL/dQ_T); grad_weights may be null
+void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int n, int T, float relax, const BackwardArea &ar,
+                           float *grad_unary, float *grad_weights, hipStream_t s);
 
 // ---- fused build (SLAM sizes; one workgroup per (frame, kernel), hash table in LDS) ------
 bool build_small_supported(const KernelDev *kds, int n, int max_points);

@@ -1,0 +1,257 @@
+// meanfield_backward.hip -- reverse-mode gradients of DenseCRF::inference (densecrf_base.h:65-91): include/lccrf.h section 1c.
+//
+// The C-ABI layer (api.hip: lccrf_inference_backward) replays the forward on the step path, keeping Q_0 .. Q_{T-1}, and then runs
+// the sweep below on the handle's stream.  Per iteration t = T .. 1:
+//   Phi_k(Q_{t-1})                          launch_filter, forward blur order (the streaming engine's splat / blur / slice)
+//   x_t, P_t, gamma_t, dL/dU, n_k gamma_t   k_softmax_bwd (+ the per-workgroup partials of the K weight-gradient dot products)
+//   Phi_k^T(n_k gamma_t)                    launch_filter, blur passes in REVERSE axis order (each pass is symmetric, their product
+//                                           is not: the transpose of B_d .. B_0 is B_0 .. B_d)
+//   G_{t-1} = (1 - r) G_t + sum_k w_k .     k_bwd_combine
+// then the softmax backward of Q_0 = softmax(-U) and the fixed-order reduction of the partials (k_bwd_reduce).  No float atomics:
+// every sum is formed in an order fixed by N and L alone, so the results are the same bits from run to run.
+#include "engine.h"
+#include "device_math.h"
+
+namespace lccrf {
+namespace {
+
+constexpr int kBwdBlock = 256;
+constexpr int kBwdMaxK = LCCRF_MAX_KERNELS;
+
+struct BwdWeights { float w[kBwdMaxK]; };
+struct BwdArgs {
+    const int *n_points;
+    int L, K, first;             // first: the sweep's first iteration writes dL/dU, the others accumulate into it
+    float relax;
+    const float *unary;          // [N][L]
+    float *phi;                  // [K][nl]: Phi_k(Q_{t-1}) in, n_k * gamma_t out
+    size_t nl;                   // backward_stride(N, L)
+    const float *G;              // [N][L] dL/dQ_t
+    float *gU;                   // [N][L] dL/dU
+    float *partial;              // [K][gridDim.x] or null
+    const float *norm[kBwdMaxK];
+    float w[kBwdMaxK];
+};
+
+// lanes per row: one row per lane up to 4 labels, then four labels per lane over a power-of-two group of lanes
+inline int bwd_lanes(int L) { return L <= 4 ? 1 : L <= 8 ? 2 : L <= 16 ? 4 : L <= 32 ? 8 : 16; }
+
+// the label-ordered sum of one value per label over the row's lanes (lane first + c holds labels 4c .. 4c+3): every lane of the row
+// ends with the same sum, added one label at a time in label order 0 .. L-1, as densecrf3d.h:80-84 adds the row sum
+template <int G>
+__device__ __forceinline__ float row_sum_ordered(const float (&v)[4], int L, int first)
+{
+    float s = 0.0f;
+    for (int t = 0; t < L; ++t) {
+        const int u = t & 3;
+        const float src = u == 0 ? v[0] : u == 1 ? v[1] : u == 2 ? v[2] : v[3];
+        s += G == 1 ? src : __shfl(src, first + (t >> 2), 64);
+    }
+    return s;
+}
+
+// One iteration's softmax backward.  A row (point) is G lanes; lane c of the row holds labels 4c .. 4c+3.
+//   x   = -U + sum_k (w_k * n_k) * Phi_k          the forward's own expression (k_slice / k_slice2: base + w * norm * t)
+//   P   = softmax(x)                              fast_exp as expAndNormalize (densecrf3d.h:70-98) forms it
+//   gam = r * P * (G - <G, P>)                    (in a form that keeps the bits of saturated rows, below)
+//   gU  = -gam (first) or gU - gam
+//   phi_k <- n_k * gam (in place: the transposed filter's input), partial[k][block] = sum over the block of n_k * gam * Phi_k
+// K = 0: x = -U (the start, densecrf_base.h:78-80, or a CRF without terms).
+template <int G>
+__global__ void __launch_bounds__(kBwdBlock) k_softmax_bwd(BwdArgs a)
+{
+    const int N = *a.n_points, L = a.L, K = a.K;
+    const int lane = threadIdx.x & 63;
+    const int sub = lane % G, first = lane - sub;
+    const int i = blockIdx.x * (kBwdBlock / G) + (int)threadIdx.x / G;
+    const bool live = i < N;
+    const int l0 = sub * 4;
+    bool has[4];
+    float x[4], g[4];
+    const size_t q = (size_t)(live ? i : 0) * L + l0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        has[u] = live && l0 + u < L;
+        x[u] = has[u] ? -a.unary[q + u] : 0.0f;
+        g[u] = has[u] ? a.G[q + u] : 0.0f;
+    }
+    float ph[kBwdMaxK][4];
+    float nk[kBwdMaxK];
+#pragma unroll
+    for (int k = 0; k < kBwdMaxK; ++k) {
+        nk[k] = 0.0f;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) ph[k][u] = 0.0f;
+        if (k < K) {
+            nk[k] = live ? a.norm[k][i] : 0.0f;
+            const float wn = a.w[k] * nk[k];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                ph[k][u] = has[u] ? a.phi[k * a.nl + q + u] : 0.0f;
+                x[u] = x[u] + wn * ph[k][u];
+            }
+        }
+    }
+    // row maximum (order-free), exponentials, the row sum in label order
+    float mx = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+        if (has[u] && mx < x[u]) mx = x[u];
+#pragma unroll
+    for (int m = 1; m < G; m <<= 1) mx = fmaxf(mx, __shfl_xor(mx, m, 64));
+    float e[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) e[u] = has[u] ? fast_exp_nonpos(x[u] - mx) : 0.0f;
+    const float tt = row_sum_ordered<G>(e, L, first);
+    // G_l - <G, P> is formed as (G_l - G_a) - sum_m P_m (G_m - G_a), a = the row's first largest label (sum_m P_m = 1): a saturated
+    // row (P_a = 1 - 1e-8) keeps its gradient's few significant bits, which G_l - <G, P> would cancel in fp32
+    float ga = 0.0f;
+    bool found = false;
+    for (int t = 0; t < L; ++t) {
+        const int u = t & 3;
+        const float xs = u == 0 ? x[0] : u == 1 ? x[1] : u == 2 ? x[2] : x[3];
+        const float gs = u == 0 ? g[0] : u == 1 ? g[1] : u == 2 ? g[2] : g[3];
+        const float xv = G == 1 ? xs : __shfl(xs, first + (t >> 2), 64);
+        const float gv = G == 1 ? gs : __shfl(gs, first + (t >> 2), 64);
+        if (!found && xv == mx) { ga = gv; found = true; }
+    }
+    float p[4], gp[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        p[u] = has[u] ? e[u] / tt : 0.0f;
+        gp[u] = p[u] * (g[u] - ga);
+    }
+    const float dev = row_sum_ordered<G>(gp, L, first);
+    float wsum[kBwdMaxK];
+#pragma unroll
+    for (int k = 0; k < kBwdMaxK; ++k) wsum[k] = 0.0f;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        if (!has[u]) continue;
+        const float gam = a.relax * (p[u] * ((g[u] - ga) - dev));
+        a.gU[q + u] = a.first ? -gam : a.gU[q + u] - gam;
+#pragma unroll
+        for (int k = 0; k < kBwdMaxK; ++k)
+            if (k < K) {
+                const float gn = nk[k] * gam;
+                wsum[k] += gn * ph[k][u];
+                a.phi[k * a.nl + q + u] = gn;
+            }
+    }
+    if (!a.partial) return;
+    // per-workgroup partials: a fixed butterfly over the wavefront, then the four wavefronts in order
+    __shared__ float red[kBwdMaxK][kBwdBlock / 64];
+#pragma unroll
+    for (int k = 0; k < kBwdMaxK; ++k) {
+        if (k >= K) break;
+        float s = wsum[k];
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+        if (lane == 0) red[k][threadIdx.x >> 6] = s;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < K) {
+        float s = 0.0f;
+        for (int w = 0; w < kBwdBlock / 64; ++w) s += red[threadIdx.x][w];
+        a.partial[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+// G = keep * G + sum_k w_k * buf_k, element by element (keep = 1 - relax)
+__global__ void __launch_bounds__(kBwdBlock) k_bwd_combine(const int *__restrict__ n_points, int L, int K, const float *__restrict__ buf,
+                                                         size_t nl, BwdWeights wk, float keep, float *__restrict__ G)
+{
+    const long idx = (long)blockIdx.x * kBwdBlock + threadIdx.x;
+    if (idx >= (long)*n_points * L) return;
+    float acc = keep * G[idx];
+    for (int k = 0; k < K; ++k) acc = acc + wk.w[k] * buf[k * nl + idx];
+    G[idx] = acc;
+}
+
+// out[k] = sum over the iterations and workgroups of partial[t][k][b]: one workgroup per term, a strided walk in a fixed order and a
+// fixed tree in LDS (store and sum: no atomics, the same bits every run)
+__global__ void __launch_bounds__(kBwdBlock) k_bwd_reduce(const float *__restrict__ partial, int K, int T, int nblk, float *__restrict__ out)
+{
+    __shared__ float s[kBwdBlock];
+    const int k = blockIdx.x;
+    const long n = (long)T * nblk;
+    float acc = 0.0f;
+    for (long idx = threadIdx.x; idx < n; idx += kBwdBlock) {
+        const long t = idx / nblk, b = idx - t * nblk;
+        acc += partial[(t * K + k) * nblk + b];
+    }
+    s[threadIdx.x] = acc;
+    __syncthreads();
+    for (int m = kBwdBlock / 2; m >= 1; m >>= 1) {
+        if ((int)threadIdx.x < m) s[threadIdx.x] += s[threadIdx.x + m];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[k] = s[0];
+}
+
+void launch_softmax_bwd(const BwdArgs &a, int n, hipStream_t s)
+{
+    const int G = bwd_lanes(a.L);
+    const dim3 grid((unsigned)std::max(backward_blocks(n, a.L), 1));
+    switch (G) {
+    case 1: k_softmax_bwd<1><<<grid, kBwdBlock, 0, s>>>(a); break;
+    case 2: k_softmax_bwd<2><<<grid, kBwdBlock, 0, s>>>(a); break;
+    case 4: k_softmax_bwd<4><<<grid, kBwdBlock, 0, s>>>(a); break;
+    case 8: k_softmax_bwd<8><<<grid, kBwdBlock, 0, s>>>(a); break;
+    default: k_softmax_bwd<16><<<grid, kBwdBlock, 0, s>>>(a); break;
+    }
+}
+
+}  // namespace
+
+size_t backward_stride(int n, int L) { return (size_t)((n + 3) & ~3) * L; }
+
+int backward_blocks(int n, int L) { return (n + kBwdBlock / bwd_lanes(L) - 1) / (kBwdBlock / bwd_lanes(L)); }
+
+size_t backward_bytes(int n, int L, int K, int T)
+{
+    const size_t nl = backward_stride(n, L);
+    return sizeof(float) * (nl * ((size_t)T + K + 1) + (size_t)std::max(T, 1) * K * std::max(backward_blocks(n, L), 1));
+}
+
+void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int n, int T, float relax, const BackwardArea &ar,
+                           float *grad_unary, float *grad_weights, hipStream_t s)
+{
+    const int K = c.K, L = c.L;
+    const size_t nl = backward_stride(n, L);
+    const int nblk = std::max(backward_blocks(n, L), 1);
+    BwdArgs a{};
+    a.n_points = c.n_points;
+    a.L = L;
+    a.unary = c.unary;
+    a.phi = ar.phi;
+    a.nl = nl;
+    a.G = ar.G;
+    a.gU = grad_unary;
+    BwdWeights wk{};
+    for (int k = 0; k < K; ++k) {
+        a.norm[k] = kds[k].norm;
+        a.w[k] = wk.w[k] = kds[k].w;
+    }
+    const unsigned cgrid = (unsigned)std::max<size_t>((nl + kBwdBlock - 1) / kBwdBlock, 1);
+    for (int t = T; t >= 1; --t) {
+        const float *qprev = ar.hist + (size_t)(t - 1) * nl;
+        for (int k = 0; k < K; ++k) launch_filter(kds[k], c, maxV[k], qprev, ar.phi + k * nl, 0, s);
+        a.K = K;
+        a.relax = relax;
+        a.first = t == T;
+        a.partial = K ? ar.partial + (size_t)(t - 1) * K * nblk : nullptr;
+        launch_softmax_bwd(a, n, s);
+        for (int k = 0; k < K; ++k) launch_filter(kds[k], c, maxV[k], ar.phi + k * nl, ar.phi + k * nl, 0, s, 1);
+        k_bwd_combine<<<cgrid, kBwdBlock, 0, s>>>(c.n_points, L, K, ar.phi, nl, wk, 1.0f - relax, ar.G);
+    }
+    // dL/dU -= P_0 (G_0 - <G_0, P_0>), P_0 = Q_0 = softmax(-U)
+    a.K = 0;
+    a.relax = 1.0f;
+    a.first = T == 0;
+    a.partial = nullptr;
+    launch_softmax_bwd(a, n, s);
+    if (grad_weights && K) k_bwd_reduce<<<K, kBwdBlock, 0, s>>>(ar.partial, K, T, nblk, grad_weights);
+}
+
+}  // namespace lccrf

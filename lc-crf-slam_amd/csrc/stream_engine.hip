@@ -2145,11 +2145,12 @@ void launch_build_kernel(const KernelDev &kd, const CrfDev &c, int, hipStream_t 
     }
 }
 
-static void filter_passes(const KernelDev &kd, int F, int maxV, int L, hipStream_t s, const float **result)
+static void filter_passes(const KernelDev &kd, int F, int maxV, int L, hipStream_t s, const float **result, int reverse = 0)
 {
     const float *src = kd.val0;
     float *dst = kd.val1;
-    for (int j = 0; j < kd.D1; ++j) {
+    for (int jj = 0; jj < kd.D1; ++jj) {
+        const int j = reverse ? kd.D1 - 1 - jj : jj;     // (reverse: the transposed filter, launch_filter)
         if (L >= 4) k_blur4<<<grid_for((long)maxV * ((L + 3) / 4), F), kBlock, 0, s>>>(kd, src, dst, j, L, (L + 3) / 4);
         else if (L == 1) k_blur1x4<<<grid_for(((long)maxV + 3) / 4, F), kBlock, 0, s>>>(kd, src, dst, j);
         else k_blur<<<grid_for((long)maxV * L, F), kBlock, 0, s>>>(kd, src, dst, j, L);
@@ -2412,13 +2413,14 @@ void launch_step_init(const CrfDev &c, float *out, hipStream_t s)
 }
 
 // out (+)= [w * norm *] compute(in) with value width c.L: PairwisePotential::apply (accumulate = 1, pairwise3d.h:73-78)
-// or the bare PermutohedralLatticeCPU::compute (accumulate = 0, permutohedral_cpu.h:634-699)
-void launch_filter(const KernelDev &kd, const CrfDev &c, int maxV, const float *in, float *out, int accumulate, hipStream_t s)
+// or the bare PermutohedralLatticeCPU::compute (accumulate = 0, permutohedral_cpu.h:634-699); reverse = 1: its transpose (engine.h)
+void launch_filter(const KernelDev &kd, const CrfDev &c, int maxV, const float *in, float *out, int accumulate, hipStream_t s,
+                   int reverse)
 {
     const int L = c.L;
     launch_splat(kd, in, c.maxN * L, L, c.F, maxV, s);
     const float *res;
-    filter_passes(kd, c.F, maxV, L, s, &res);
+    filter_passes(kd, c.F, maxV, L, s, &res, reverse);
     CrfDev c2 = c;
     c2.next = out;
     k_slice<<<grid_for((long)c.maxN * L, c.F), kBlock, 0, s>>>(kd, c2, res, L, accumulate ? SLICE_APPLY : SLICE_PLAIN);

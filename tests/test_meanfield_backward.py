@@ -1,0 +1,403 @@
+"""Gradients of mean-field inference (include/lccrf.h section 1c) and the torch layer (lc-crf-slam_amd/autograd.py).
+
+CPU: the float64 checker (tests/meanfield_f64.py) against the oracle, gradcheck, the adjoint of the reverse-order filter, the
+asymmetry of Phi that makes the order matter, and the new symbols.  GPU: lccrf_inference_backward against the checker's
+autograd gradients, its state and determinism contract, lccrf_set_pairwise_weight, argument checks and the torch layer."""
+import ctypes as C
+import importlib
+import os
+import re
+
+import numpy as np
+import pytest
+
+import crf_cases as cc
+import meanfield_f64 as mf
+
+pkg = importlib.import_module("lc-crf-slam_amd")
+NEW_SYMBOLS = ("lccrf_set_pairwise_weight", "lccrf_inference_backward")
+GRAD_TOL = 1e-4
+
+
+@pytest.fixture(scope="module")
+def lib():
+    if not os.path.exists(pkg.LIB_PATH):
+        pkg.build_library()
+    return pkg.lib()
+
+
+def _weights(pb):
+    return np.array([float(w) for _, w in pb["kernels"]], np.float64)
+
+
+def _checker(po, pb):
+    """(oracle CRF, its lattices, U as float64)"""
+    o = cc.setup(po.OracleCRF, pb)
+    return o, mf.lattices(o, len(pb["kernels"])), o.unary().astype(np.float64)
+
+
+def _golden_problem(golden, name):
+    group, case = name.split(":")
+    z = golden[group]
+    if group == "large":
+        from test_oracle_golden import _large_case
+        pb, _, _ = _large_case(z, case)
+        return pb
+    return cc.case_problem(z, case)
+
+
+# ---- CPU ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["slam:N1000", "slam:N5", "slam:C3", "slam:relax", "generic:d1_L3", "generic:d3_L21",
+                                  "generic:d5_L2", "generic:d6_L3", "generic:multi", "bilateral:c5"])
+@pytest.mark.parametrize("T", [1, 5])
+@pytest.mark.parametrize("relax", [1.0, 0.7])
+def test_checker_forward_matches_the_oracle(po, golden, name, T, relax):
+    import torch
+    pb = _golden_problem(golden, name)
+    o, lats, U = _checker(po, pb)
+    o.inference_native(T, False, relax)
+    q = mf.forward(torch.as_tensor(U), torch.as_tensor(_weights(pb)), lats, T, relax).numpy()
+    # generic:multi (several terms of different d on one CRF) drifts furthest from the float32 oracle: 3.2e-5 measured at T = 5,
+    # relax = 0.7 (every other case and setting <= 1e-5) -- float32 rounding carried through five iterations, not the method
+    tol = 5e-5 if name == "generic:multi" else 1e-5
+    assert np.abs(q - o.probability()).max() <= tol
+
+
+def test_checker_gradcheck(po, wl):
+    import torch
+    pb = wl.generic_problem(40, [2, 3], 3, seed=4)
+    o, lats, U = _checker(po, pb)
+    u = torch.as_tensor(U).clone().requires_grad_(True)
+    w = torch.as_tensor(_weights(pb)).clone().requires_grad_(True)
+    for relax in (1.0, 0.7):
+        assert torch.autograd.gradcheck(lambda a, b: mf.forward(a, b, lats, 3, relax), (u, w), eps=1e-6, atol=1e-7)
+
+
+@pytest.mark.parametrize("name", ["slam:N1000", "generic:d3_L3", "generic:d6_L2"])
+def test_reverse_order_filter_is_the_adjoint(po, golden, name):
+    """<y, Phi x> = <Phi^T y, x> with Phi^T the same splat and slice and the blur passes in reverse axis order."""
+    import torch
+    pb = _golden_problem(golden, name)
+    o, lats, _ = _checker(po, pb)
+    rng = np.random.default_rng(0)
+    for lat in lats:
+        x = torch.as_tensor(rng.standard_normal((pb["N"], 3)))
+        y = torch.as_tensor(rng.standard_normal((pb["N"], 3)))
+        lhs, rhs = float((y * lat.apply(x)).sum()), float((lat.apply(y, reverse=True) * x).sum())
+        assert abs(lhs - rhs) <= 1e-12 * max(abs(lhs), 1.0)
+
+
+@pytest.mark.parametrize("name", ["slam:N1000", "slam:C3"])
+def test_phi_is_not_symmetric(po, golden, name):
+    """On cases the GPU tests use, the transpose formed with the FORWARD blur order (i.e. Phi itself) is far from Phi^T: a backward
+    that reused the forward order would miss the gradient bar by orders of magnitude."""
+    import torch
+    pb = _golden_problem(golden, name)
+    o, lats, _ = _checker(po, pb)
+    eye = torch.eye(pb["N"], dtype=torch.float64)
+    phi = lats[0].apply(eye)                                 # column j = Phi e_j
+    assert torch.allclose(lats[0].apply(eye, reverse=True), phi.T, rtol=0, atol=1e-12)
+    assert float(torch.linalg.norm(phi - phi.T) / torch.linalg.norm(phi)) > 1e-3
+
+
+def test_backward_symbols_are_declared_exported_and_bound(lib):
+    src = re.sub(r"/\*.*?\*/", "", open(pkg.HEADER_PATH).read(), flags=re.S)
+    for n in NEW_SYMBOLS:
+        assert re.search(r"\b%s\s*\(" % n, src), n
+        assert hasattr(lib, n), n
+        assert getattr(lib, n).argtypes is not None, n
+    assert lib.lccrf_abi_version() == 3
+    assert hasattr(pkg.DenseCRFHIP, "set_pairwise_weight") and hasattr(pkg.DenseCRFHIP, "inference_backward_device")
+
+
+def test_backward_rejects_a_null_handle(lib):
+    assert lib.lccrf_set_pairwise_weight(None, 0, 1.0) == -1
+    assert lib.lccrf_inference_backward(None, 1, 1.0, None, None, None) == -1
+
+
+# ---- GPU ------------------------------------------------------------------------------------------------------------------
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _crop_problem(golden, po):
+    """64 x 48 crop of the reference's image example: 21 labels, the position and RGB image terms."""
+    z = golden["example_im1"]
+    W, H = 64, 48
+    im = np.ascontiguousarray(z["im"][:H, :W], np.uint8)
+    lab = np.ascontiguousarray(z["label"].reshape(240, 320)[:H, :W].reshape(-1), np.int16)
+    pb = dict(N=W * H, L=21, label=lab, conf=np.float32(0.5),
+              kernels=[(po.oracle_image_features(W, H, 3.0), np.float32(3.0)),
+                       (po.oracle_image_features(W, H, 60.0, im, 20.0), np.float32(10.0))])
+    return pb, (W, H, im)
+
+
+def _gpu_handle(pb, image=None):
+    import torch
+    if image is None:
+        return cc.setup(pkg.DenseCRFHIP, pb), []
+    W, H, im = image
+    d_lab, d_img = _dev(pb["label"]), _dev(im)
+    torch.cuda.synchronize()
+    h = pkg.DenseCRFHIP(pb["N"], pb["L"])
+    h.set_unary_from_label_device(d_lab.data_ptr(), pb["conf"])
+    h.add_image_kernel(W, H, 3.0, 3.0)
+    h.add_image_kernel(W, H, 10.0, 60.0, d_img.data_ptr(), pkg.IMAGE_U8, 20.0)
+    return h, [d_lab, d_img]
+
+
+def _backward(h, T, relax, G, K):
+    import torch
+    g = _dev(G.astype(np.float32))
+    gu = torch.full(G.shape, float("nan"), device="cuda")
+    gw = torch.full((max(K, 1),), float("nan"), device="cuda")
+    torch.cuda.synchronize()
+    h.inference_backward_device(T, relax, g.data_ptr(), gu.data_ptr(), gw.data_ptr() if K else None)
+    h.synchronize()
+    return gu.cpu().numpy(), gw[:K].cpu().numpy()
+
+
+def _rel(a, b, floor=0.0):
+    """relative L2 error; gradients smaller than `floor` are compared in absolute terms against it"""
+    nb = max(np.linalg.norm(b), floor)
+    return np.linalg.norm(a - b) / (nb if nb > 0 else 1.0)
+
+
+CASES = ["slam:N5", "slam:N1001", "slam:C3", "generic:d1_L3", "generic:d3_L21", "generic:d5_L2", "generic:d6_L3", "generic:multi",
+         "bilateral:c5", "large:c5", "image64x48", "c2"]
+
+
+def _case(name, golden, po, wl):
+    if name == "image64x48":
+        return _crop_problem(golden, po)
+    if name == "c2":
+        return wl.slam_problem(2000, seed=12), None
+    return _golden_problem(golden, name), None
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", CASES)
+@pytest.mark.parametrize("T", [0, 1, 5, 10])
+@pytest.mark.parametrize("relax", [1.0, 0.7])
+def test_gradients_match_the_checker(po, wl, golden, name, T, relax):
+    """Relative L2 error of dL/dU and dL/dw against the float64 checker <= 1e-4 -- or, where the same autograd computation done in
+    float32 (exact exp, another summation order) is itself far from float64, <= 10 x ITS error.  Measured on the MI355X, the cases
+    beyond 1e-4 are generic:multi (T = 5, relax 1 / 0.7: dL/dU 1.1e-3 / 8.4e-4; the float32 checker 2.9e-3 / 8.0e-4) and
+    generic:d5_L2 at T = 10 (relax 1 / 0.7: 2.5e-4 / 2.1e-4; float32 checker 5.5e-4 / 4.0e-5, |dL/dU| = 0.07 / 163) -- the
+    conditioning of those iterations in fp32, not the kernels; every other case and setting is <= 6e-5.  Gradients below 1e-6 of
+    |dL/dQ| (slam:N5 from T = 5: |dL/dU| ~ 1e-17, every row saturated; the forward's fast_exp gives exactly 0 beyond e^-20, so by the
+    section 1c convention the gradient is exactly 0) are compared in absolute terms against that floor."""
+    import torch
+    pb, image = _case(name, golden, po, wl)
+    o, lats, U = _checker(po, pb)
+    G = np.random.default_rng(1234).standard_normal((pb["N"], pb["L"]))
+    w = _weights(pb)
+    ref_u, ref_w = mf.gradients(U, w, lats, T, relax, G)
+    h, keep = _gpu_handle(pb, image)
+    gu, gw = _backward(h, T, relax, G, len(pb["kernels"]))
+    h.close()
+    floor_u = 1e-6 * np.linalg.norm(G)
+    floor_w = 1e-6 * np.linalg.norm(G) * max(np.linalg.norm(w), 1.0)
+    eu, ew = _rel(gu, ref_u, floor_u), _rel(gw, ref_w, floor_w)
+    f32_u, f32_w = mf.gradients(U, w, lats, T, relax, G, dtype=torch.float32)
+    bu = max(GRAD_TOL, 10 * _rel(f32_u, ref_u, floor_u))
+    bw = max(GRAD_TOL, 10 * _rel(f32_w, ref_w, floor_w))
+    print("relative L2 error %s T=%d relax=%g: dL/dU %.3g dL/dw %.3g (bars %.3g %.3g)" % (name, T, relax, eu, ew, bu, bw))
+    assert eu <= bu and ew <= bw, "relative L2 error dL/dU %.3g (bar %.3g), dL/dw %.3g (bar %.3g)" % (eu, bu, ew, bw)
+    if T == 0:
+        assert np.all(gw == 0)
+
+
+@pytest.mark.gpu
+def test_t0_is_the_softmax_backward_and_k0_works(po, wl):
+    import torch
+    pb = wl.slam_problem(700, seed=2)
+    o, lats, U = _checker(po, pb)
+    G = np.random.default_rng(5).standard_normal((pb["N"], 2))
+    P0 = torch.softmax(-torch.as_tensor(U), 1).numpy()
+    h = cc.setup(pkg.DenseCRFHIP, pb)
+    gu, gw = _backward(h, 0, 1.0, G, 2)
+    assert np.all(gw == 0)
+    assert _rel(gu, -(P0 * (G - (G * P0).sum(1, keepdims=True)))) <= GRAD_TOL
+    h.close()
+    # a CRF without pairwise terms: the weight gradient is empty, the unary gradient still exact to the bar
+    gen = wl.generic_problem(300, [2], 5, seed=3)
+    h0 = pkg.DenseCRFHIP(300, 5)
+    h0.set_unary(gen["unary"])
+    G5 = np.random.default_rng(6).standard_normal((300, 5))
+    for T, relax in ((5, 1.0), (3, 0.7)):
+        gu, _ = _backward(h0, T, relax, G5, 0)
+        ref_u, _ = mf.gradients(gen["unary"].astype(np.float64), np.zeros(0), [], T, relax, G5)
+        assert _rel(gu, ref_u) <= GRAD_TOL
+        h0.inference(T, False, relax)
+        o0 = po.OracleCRF(300, 5)
+        o0.set_unary(gen["unary"])
+        o0.inference_native(T, False, relax)
+        assert cc.same_bits(h0.probability(), o0.probability())
+    h0.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["c2", "generic:d3_L21", "large:c5"])
+def test_backward_is_deterministic_and_leaves_the_inference_state(po, wl, golden, name):
+    pb, image = _case(name, golden, po, wl)
+    K = len(pb["kernels"])
+    G = np.random.default_rng(9).standard_normal((pb["N"], pb["L"]))
+    h, keep = _gpu_handle(pb, image)
+    T, relax = 5, 0.7
+    h.inference(T, False, relax)
+    q_before = h.probability()
+    a = _backward(h, T, relax, G, K)
+    q_after = h.probability()
+    b = _backward(h, T, relax, G, K)
+    assert cc.same_bits(a[0], b[0]) and cc.same_bits(a[1], b[1])
+    assert cc.same_bits(q_after, q_before)                      # Q is what inference(T, 0, relax) leaves
+    o = cc.setup(po.OracleCRF, pb)
+    o.inference_native(T, False, relax)
+    assert cc.same_bits(q_after, o.probability())
+    h.inference(T, True, relax)                                  # ... and the next inference is unchanged
+    o.inference_native(T, True, relax)
+    assert cc.same_bits(h.probability(), o.probability()) and np.array_equal(h.map(), o.map())
+    # a fresh handle whose first call is the backward gives the same bits
+    h2, keep2 = _gpu_handle(pb, image)
+    c = _backward(h2, T, relax, G, K)
+    assert cc.same_bits(a[0], c[0]) and cc.same_bits(a[1], c[1])
+    assert cc.same_bits(h2.probability(), q_before)
+    h.close(), h2.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prepared", [False, True])
+def test_set_pairwise_weight_equals_a_fresh_handle(po, wl, prepared):
+    """A SLAM-size frame (the one-launch engine) with its appearance weight changed after construction gives the bits of a handle
+    built with that weight, and the oracle's -- also after three inferences on unchanged lattices and after a backward (which
+    leaves the lattices in HBM: the fused engine from then on)."""
+    pb = wl.slam_problem(2000, seed=8)
+    new = [np.float32(4.5), np.float32(17.25)]
+    h = cc.setup(pkg.DenseCRFHIP, pb)
+    if prepared:
+        for _ in range(3):
+            h.inference(5, True)
+    for k, w in enumerate(new):
+        h.set_pairwise_weight(k, w)
+    pb2 = dict(pb, kernels=[(f, w) for (f, _), w in zip(pb["kernels"], new)])
+    fresh, o = cc.setup(pkg.DenseCRFHIP, pb2), cc.setup(po.OracleCRF, pb2)
+    for rnd in range(2):
+        h.inference(5, True)
+        fresh.inference(5, True)
+        o.inference_native(5, True)
+        assert cc.same_bits(h.probability(), fresh.probability()) and cc.same_bits(h.probability(), o.probability())
+        assert np.array_equal(h.map(), o.map())
+        if rnd == 0:                                             # round two: lattices in HBM behind a backward
+            G = np.random.default_rng(3).standard_normal((pb["N"], 2))
+            _backward(h, 2, 1.0, G, 2)
+            h.set_pairwise_weight(0, 99.0)
+            h.set_pairwise_weight(0, new[0])
+    h.close(), fresh.close()
+
+
+def _hip_malloc(nbytes):
+    lib = C.CDLL("libamdhip64.so")
+    p = C.c_void_p()
+    assert lib.hipMalloc(C.byref(p), C.c_size_t(nbytes)) == 0
+    return lib, p
+
+
+@pytest.mark.gpu
+def test_backward_argument_checks_leave_the_handle_usable(po, wl):
+    import torch
+    pb = wl.slam_problem(2000, seed=4)
+    h = cc.setup(pkg.DenseCRFHIP, pb)
+    L = pkg.lib()
+    g = torch.zeros((2000, 2), device="cuda")
+    gu = torch.zeros((2000, 2), device="cuda")
+    gw = torch.zeros(2, device="cuda")
+    host = np.zeros((2000, 2), np.float32)
+    hl, small = _hip_malloc(64)
+    try:
+        vp = C.c_void_p
+        for args in ((1, 1.0, None, vp(gu.data_ptr()), None),                      # NULL
+                     (1, 1.0, vp(g.data_ptr()), None, None),
+                     (1, 1.0, vp(host.ctypes.data), vp(gu.data_ptr()), None),     # pageable host memory
+                     (1, 1.0, small, vp(gu.data_ptr()), None),                    # undersized
+                     (1, 1.0, vp(g.data_ptr()), small, None),
+                     (-1, 1.0, vp(g.data_ptr()), vp(gu.data_ptr()), None),        # n_iterations < 0
+                     (1, float("nan"), vp(g.data_ptr()), vp(gu.data_ptr()), None)):
+            assert L.lccrf_inference_backward(h.h, *args) == -1, args
+        assert L.lccrf_set_pairwise_weight(h.h, 2, 1.0) == -1
+        assert L.lccrf_set_pairwise_weight(h.h, -1, 1.0) == -1
+        hl2, small4 = _hip_malloc(4)
+        assert L.lccrf_inference_backward(h.h, 1, 1.0, vp(g.data_ptr()), vp(gu.data_ptr()), small4) == -1   # [K] undersized
+        hl2.hipFree(small4)
+        h0 = pkg.DenseCRFHIP(2000, 2)                            # no unary yet
+        assert L.lccrf_inference_backward(h0.h, 1, 1.0, vp(g.data_ptr()), vp(gu.data_ptr()), None) == -5
+        h0.close()
+    finally:
+        hl.hipFree(small)
+    # still usable: inference and a backward as on a fresh handle
+    o = cc.setup(po.OracleCRF, pb)
+    h.inference(5, True)
+    o.inference_native(5, True)
+    assert cc.same_bits(h.probability(), o.probability())
+    torch.cuda.synchronize()
+    h.inference_backward_device(5, 1.0, g.data_ptr(), gu.data_ptr(), gw.data_ptr())
+    h.synchronize()
+    assert np.all(gu.cpu().numpy() == 0) and np.all(gw.cpu().numpy() == 0)   # dL/dQ = 0
+    h.close()
+
+
+@pytest.mark.gpu
+def test_torch_layer_matches_the_c_abi_and_streams(wl):
+    import torch
+    ag = importlib.import_module("lc-crf-slam_amd.autograd")
+    pb = wl.slam_problem(1500, seed=6)
+    h = cc.setup(pkg.DenseCRFHIP, pb)
+    U = h.unary()
+    G = np.random.default_rng(2).standard_normal((pb["N"], 2)).astype(np.float32)
+    ref_u, ref_w = _backward(h, 5, 0.7, G, 2)
+    h.inference(5, False, 0.7)
+    ref_q = h.probability()
+
+    def run(stream):
+        with torch.cuda.stream(stream):
+            u = torch.from_numpy(U).cuda().requires_grad_(True)
+            w = torch.tensor([float(x) for _, x in pb["kernels"]], requires_grad=True)      # weights on the host
+            q = ag.mean_field(h, u, w, 5, 0.7)
+            q.backward(torch.from_numpy(G).cuda())
+            torch.cuda.current_stream().synchronize()
+            return q.detach().cpu().numpy(), u.grad.cpu().numpy(), w.grad.numpy(), w.grad.device
+
+    for stream in (torch.cuda.current_stream(), torch.cuda.Stream()):
+        q, gu, gw, dev = run(stream)
+        assert dev.type == "cpu"
+        assert cc.same_bits(q, ref_q) and cc.same_bits(gu, ref_u) and cc.same_bits(gw, ref_w.astype(np.float32))
+    h.close()
+
+
+@pytest.mark.gpu
+def test_fitting_the_weights_of_a_slam_frame_lowers_the_loss(po, wl):
+    """Targets from known weights (the TUM3 weights / 10), a start at twice them, 30 Adam steps (chosen on the float64 checker:
+    the loss falls to ~1-4 % of its start on seeds 3 and 11)."""
+    import torch
+    ag = importlib.import_module("lc-crf-slam_amd.autograd")
+    pb = wl.slam_problem(500, seed=11)
+    o = cc.setup(po.OracleCRF, pb)
+    U = torch.from_numpy(o.unary()).cuda()
+    feats = [f for f, _ in pb["kernels"]]
+    w_true = [float(w) / 10 for _, w in pb["kernels"]]
+    layer = ag.MeanFieldCRF(pb["N"], 2, feats, w_true, n_iterations=5)
+    with torch.no_grad():
+        target = layer(U).clone()
+        layer.weights.mul_(2.0)
+    opt = torch.optim.Adam(layer.parameters(), lr=0.3)
+    losses = []
+    for _ in range(30):
+        loss = ((layer(U) - target) ** 2).sum()
+        losses.append(loss.item())
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+    final = ((layer(U) - target) ** 2).sum().item()
+    layer.close()
+    assert final < 0.5 * losses[0], (losses, final)
