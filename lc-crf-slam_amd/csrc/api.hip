@@ -56,6 +56,21 @@ inline void cpu_relax()
 #endif
 }
 
+// Bounded spin on a pinned done word: true once it shows `epoch` (the frame kernel's last store), false after `limit`; the clock is
+// read every `check_every` spins (a power of two).  Either way an acquire fence orders the reads that follow behind the word.
+inline bool poll_done_word(const unsigned *word, unsigned epoch, std::chrono::microseconds limit, unsigned check_every)
+{
+    const volatile unsigned *w = word;
+    const auto t0 = std::chrono::steady_clock::now();
+    bool seen = false;
+    for (unsigned spins = 1; !(seen = (*w == epoch)); ++spins) {
+        if ((spins & (check_every - 1)) == 0 && std::chrono::steady_clock::now() - t0 > limit) break;
+        cpu_relax();
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return seen;
+}
+
 int next_pow2(long v)
 {
     long p = 16;
@@ -470,15 +485,7 @@ struct Engine {
     {
         if (!park_check) return;
         park_check = false;
-        const volatile unsigned *w = done_word;
-        const auto t0 = std::chrono::steady_clock::now();
-        bool seen = false;
-        for (unsigned spins = 1; !(seen = (*w == done_epoch)); ++spins) {
-            if ((spins & 0x3f) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(50)) break;
-            cpu_relax();
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        if (!seen && stream) (void)hipStreamSynchronize(stream);
+        if (!poll_done_word(done_word, done_epoch, std::chrono::microseconds(50), 64) && stream) (void)hipStreamSynchronize(stream);
     }
 
     // Park everything for the next user of this engine (object API handle cache).
@@ -499,12 +506,12 @@ struct Engine {
         F = Fcap;
         crf.unary = unary_own;
         crf.n_points = npoints_own;
-        unary_set = built = sizes_known = started = false;
+        unary_set = built = started = false;
         late_pending = false;
         unary_deferred = false;
         perm_on = vorder_on = perm_banned = perm_scope = false;      // (the next user's lattices decide afresh)
         unary_is_label = unary_p_valid = false;
-        built_upto = 0;
+        invalidate_lattices();
         engine_pref = 0;
         engine_used = 1;
         sync_views();
@@ -531,6 +538,10 @@ struct Engine {
         crf.perm = perm_on ? sort.perm : nullptr;
         crf.perm_stride = maxNpad;
     }
+
+    // every lattice is re-built (and its sizes learnt) by the next call that needs it; the prepared launch records are rewritten
+    void invalidate_lattices() { built_upto = 0; sizes_known = false; }
+    void invalidate_lean_prep() { lean_prep.valid = false; lean_prep.seen_key = 0; }
 
     // Lattice + normalisation of kernels [k0, k0+n) for every frame (PottsPotential3D ctor).
     // SLAM-size frames take the fused build (one launch for all of them when they share d);
@@ -688,8 +699,7 @@ struct Engine {
         }
         sync_views();
         sizes_known = true;
-        lean_prep.valid = false;                           // (every path that changes a lattice clears sizes_known and so comes through here)
-        lean_prep.seen_key = 0;
+        invalidate_lean_prep();                            // (every path that changes a lattice clears sizes_known and so comes through here)
         sized_engine = 1;
         if (engine_pref != 1 && !perm_on && fused_supported(crf, kdevs.data(), maxV.data(), maxRow.data(), &fused_lds)) sized_engine = 2;
         if (engine_pref == 2 && sized_engine != 2)
@@ -721,6 +731,14 @@ struct Engine {
         unary_is_label = true;
         deferred_label = label;
         deferred_tbl = tb;
+        unary_set = true;
+    }
+
+    // raw unary energies [F][maxN][L] at `p` (the engine's own array, filled by the caller's copy, or a bound device array: read only)
+    void bind_unary(const float *p)
+    {
+        crf.unary = const_cast<float *>(p);
+        unary_deferred = unary_is_label = unary_p_valid = false;
         unary_set = true;
     }
 
@@ -845,8 +863,7 @@ struct Engine {
     {
         if (!perm_on || !perm_scoped) return LCCRF_OK;
         perm_banned = true;
-        built_upto = 0;
-        sizes_known = false;
+        invalidate_lattices();
         return flush_builds();
     }
 
@@ -858,8 +875,7 @@ struct Engine {
         int rc = resolve_late();
         if (rc) return rc;
         if (frame_ok()) return run_frame(n_iter, with_map, relax);
-        built_upto = 0;                                   // two-kernel path: rebuild for the current inputs, then infer
-        sizes_known = false;
+        invalidate_lattices();                            // two-kernel path: rebuild for the current inputs, then infer
         return inference_sized(n_iter, with_map, relax);
     }
 
@@ -931,13 +947,7 @@ struct Engine {
         bool seen = false;
         if (done_armed) {                                  // bounded poll; a word that never comes is waited for the ordinary way
             done_armed = false;
-            const volatile unsigned *w = done_word;
-            const auto t0 = std::chrono::steady_clock::now();
-            for (unsigned spins = 1; !(seen = (*w == done_epoch)); ++spins) {
-                if ((spins & 0x3ff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-                cpu_relax();
-            }
-            std::atomic_thread_fence(std::memory_order_acquire);
+            seen = poll_done_word(done_word, done_epoch, std::chrono::milliseconds(2), 1024);
         }
         if (!seen) HIP_TRY(hipStreamSynchronize(stream));
         if (*npoints_bad) {                                // (the one-launch path never passes through learn_sizes())
@@ -959,8 +969,7 @@ struct Engine {
         if (frame_lean_used && 8 * n > F) frame_lean_ok = false;
         int rc = LCCRF_OK;
         if (n >= F || n == 0) {                            // every frame (always so for the object API): two-kernel path in place
-            built_upto = 0;
-            sizes_known = false;
+            invalidate_lattices();
             rc = inference_sized(late_iter, late_map, late_relax);
         } else {
             rc = rerun_frames(n);                          // the batch stays a one-launch batch; only the flagged frames pay twice
@@ -1022,8 +1031,7 @@ struct Engine {
             g.unary_deferred = false;
         }
         g.unary_set = true;
-        g.built_upto = 0;
-        g.sizes_known = false;
+        g.invalidate_lattices();
         g.sync_views();
         HIP_TRY(hipGetLastError());
         int rc = g.inference_sized(late_iter, late_map, late_relax);
@@ -1433,11 +1441,7 @@ int lccrf_set_unary(lccrf_handle h, const float *unary)
         memcpy(h->stage_f32, unary, n * sizeof(float));
         HIP_TRY(hipMemcpyAsync(e.unary_own, h->stage_f32, n * sizeof(float), hipMemcpyHostToDevice, e.stream));
     }
-    e.crf.unary = e.unary_own;
-    e.unary_deferred = false;
-    e.unary_is_label = false;
-    e.unary_p_valid = false;
-    e.unary_set = true;
+    e.bind_unary(e.unary_own);
     return LCCRF_OK;
 }
 
@@ -1543,28 +1547,82 @@ int lccrf_inference(lccrf_handle h, int n_iterations, int with_map, float relax)
     return h->eng.inference(n_iterations, with_map, relax);
 }
 
-// ---- the reference's plug-in points on host arrays: PairwisePotential::apply and DenseCRF's protected virtuals --------
+// ---- the reference's plug-in points: PairwisePotential::apply and DenseCRF's protected virtuals -------------------------------
+// One body per operation, shared by the host-array form (on the handle's io buffers) and the device-array form (section 1b): settle
+// a pending inference, make the handle ready, then enqueue the kernel on the handle's stream (nothing for a handle of 0 points).
+static int pairwise_apply_on(lccrf_crf *h, int kernel, float *d_out, const float *d_in, int accumulate)
+{
+    Engine &e = h->eng;
+    int rc = e.resolve_late();
+    if (!rc) rc = e.ensure_plain();
+    if (!rc) rc = e.learn_sizes();                        // builds the lattice if it only exists as staged features
+    if (rc || !h->N) return rc;
+    launch_filter(e.kdevs[kernel], e.crf, e.maxV[kernel], d_in, d_out, accumulate, e.stream);
+    HIP_TRY(hipGetLastError());
+    return LCCRF_OK;
+}
+
+static int exp_and_normalize_on(lccrf_crf *h, float *d_out, const float *d_in, float scale, float relax)
+{
+    const int rc = h->eng.resolve_late();
+    if (rc || !h->N) return rc;
+    launch_exp_and_normalize(h->eng.crf, d_in, d_out, scale, relax, h->eng.stream);
+    HIP_TRY(hipGetLastError());
+    return LCCRF_OK;
+}
+
+static int step_init_on(lccrf_crf *h, float *d_next)
+{
+    Engine &e = h->eng;
+    if (!e.unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
+    int rc = e.resolve_late();
+    if (!rc) rc = e.ensure_plain();
+    if (!rc) rc = e.ensure_unary();
+    if (rc || !h->N) return rc;
+    launch_step_init(e.crf, d_next, e.stream);
+    HIP_TRY(hipGetLastError());
+    return LCCRF_OK;
+}
+
+static int map_of_on(lccrf_crf *h, const float *d_prob, int16_t *d_map)
+{
+    const int rc = h->eng.resolve_late();
+    if (rc || !h->N) return rc;
+    launch_map_of(h->eng.crf, d_prob, d_map, h->eng.stream);
+    HIP_TRY(hipGetLastError());
+    return LCCRF_OK;
+}
+
+// host forms: the caller's `in` (and `out`, where the kernel reads it) -> the handle's io buffers io_a (io_b), behind everything
+// queued on its stream; a result -> the caller's array
+static int io_in(Engine &e, const void *in, const void *out, size_t bytes)
+{
+    const int rc = e.need_io();
+    if (rc || !bytes) return rc;
+    HIP_TRY(hipStreamSynchronize(e.stream));
+    HIP_TRY(hipMemcpy(e.io_a, in, bytes, hipMemcpyHostToDevice));
+    if (out) HIP_TRY(hipMemcpy(e.io_b, out, bytes, hipMemcpyHostToDevice));
+    return LCCRF_OK;
+}
+
+static int io_out(Engine &e, void *out, const void *d_src, size_t bytes)
+{
+    if (!bytes) return LCCRF_OK;
+    HIP_TRY(hipStreamSynchronize(e.stream));
+    HIP_TRY(hipMemcpy(out, d_src, bytes, hipMemcpyDeviceToHost));
+    return LCCRF_OK;
+}
+
 int lccrf_pairwise_apply(lccrf_handle h, int kernel, float *out_values, const float *in_values)
 {
     CHECK_H(h);
     CHECK_K(h, kernel);
     if ((!out_values || !in_values) && h->N) return fail(LCCRF_E_INVALID, "out_values / in_values is NULL");
     Engine &e = h->eng;
-    int rc = e.resolve_late();
-    if (!rc) rc = e.ensure_plain();
-    if (!rc) rc = e.learn_sizes();                        // builds the lattice if it only exists as staged features
-    if (!rc) rc = e.need_io();
-    if (rc) return rc;
     const size_t n = (size_t)h->N * e.L * sizeof(float);
-    if (!n) return LCCRF_OK;
-    HIP_TRY(hipStreamSynchronize(e.stream));
-    HIP_TRY(hipMemcpy(e.io_a, in_values, n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e.io_b, out_values, n, hipMemcpyHostToDevice));
-    launch_filter(e.kdevs[kernel], e.crf, e.maxV[kernel], e.io_a, e.io_b, 1, e.stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e.stream));
-    HIP_TRY(hipMemcpy(out_values, e.io_b, n, hipMemcpyDeviceToHost));
-    return LCCRF_OK;
+    int rc = io_in(e, in_values, out_values, n);          // (the filter adds to out)
+    if (!rc) rc = pairwise_apply_on(h, kernel, e.io_b, e.io_a, 1);
+    return rc ? rc : io_out(e, out_values, e.io_b, n);
 }
 
 int lccrf_exp_and_normalize(lccrf_handle h, float *out, const float *in, float scale, float relax)
@@ -1572,19 +1630,10 @@ int lccrf_exp_and_normalize(lccrf_handle h, float *out, const float *in, float s
     CHECK_H(h);
     if ((!out || !in) && h->N) return fail(LCCRF_E_INVALID, "out / in is NULL");
     Engine &e = h->eng;
-    int rc = e.resolve_late();
-    if (!rc) rc = e.need_io();
-    if (rc) return rc;
     const size_t n = (size_t)h->N * e.L * sizeof(float);
-    if (!n) return LCCRF_OK;
-    HIP_TRY(hipStreamSynchronize(e.stream));
-    HIP_TRY(hipMemcpy(e.io_a, in, n, hipMemcpyHostToDevice));
-    if (relax != 1.0f) HIP_TRY(hipMemcpy(e.io_b, out, n, hipMemcpyHostToDevice));   // the blend reads the old out (densecrf3d.h:91-94)
-    launch_exp_and_normalize(e.crf, e.io_a, e.io_b, scale, relax, e.stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e.stream));
-    HIP_TRY(hipMemcpy(out, e.io_b, n, hipMemcpyDeviceToHost));
-    return LCCRF_OK;
+    int rc = io_in(e, in, relax != 1.0f ? out : nullptr, n);   // the blend reads the old out (densecrf3d.h:91-94)
+    if (!rc) rc = exp_and_normalize_on(h, e.io_b, e.io_a, scale, relax);
+    return rc ? rc : io_out(e, out, e.io_b, n);
 }
 
 int lccrf_step_init(lccrf_handle h, float *next_out)
@@ -1592,19 +1641,9 @@ int lccrf_step_init(lccrf_handle h, float *next_out)
     CHECK_H(h);
     if (!next_out && h->N) return fail(LCCRF_E_INVALID, "next_out is NULL");
     Engine &e = h->eng;
-    if (!e.unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
-    int rc = e.resolve_late();
-    if (!rc) rc = e.ensure_plain();
-    if (!rc) rc = e.ensure_unary();
-    if (!rc) rc = e.need_io();
-    if (rc) return rc;
-    const size_t n = (size_t)h->N * e.L * sizeof(float);
-    if (!n) return LCCRF_OK;
-    launch_step_init(e.crf, e.io_a, e.stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e.stream));
-    HIP_TRY(hipMemcpy(next_out, e.io_a, n, hipMemcpyDeviceToHost));
-    return LCCRF_OK;
+    int rc = e.need_io();
+    if (!rc) rc = step_init_on(h, e.io_a);
+    return rc ? rc : io_out(e, next_out, e.io_a, (size_t)h->N * e.L * sizeof(float));
 }
 
 int lccrf_map_of(lccrf_handle h, const float *prob, int16_t *map_out)
@@ -1612,17 +1651,9 @@ int lccrf_map_of(lccrf_handle h, const float *prob, int16_t *map_out)
     CHECK_H(h);
     if ((!prob || !map_out) && h->N) return fail(LCCRF_E_INVALID, "prob / map_out is NULL");
     Engine &e = h->eng;
-    int rc = e.resolve_late();
-    if (!rc) rc = e.need_io();
-    if (rc) return rc;
-    if (!h->N) return LCCRF_OK;
-    HIP_TRY(hipStreamSynchronize(e.stream));
-    HIP_TRY(hipMemcpy(e.io_a, prob, (size_t)h->N * e.L * sizeof(float), hipMemcpyHostToDevice));
-    launch_map_of(e.crf, e.io_a, e.io_map, e.stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e.stream));
-    HIP_TRY(hipMemcpy(map_out, e.io_map, (size_t)h->N * sizeof(int16_t), hipMemcpyDeviceToHost));
-    return LCCRF_OK;
+    int rc = io_in(e, prob, nullptr, (size_t)h->N * e.L * sizeof(float));
+    if (!rc) rc = map_of_on(h, e.io_a, e.io_map);
+    return rc ? rc : io_out(e, map_out, e.io_map, (size_t)h->N * sizeof(int16_t));
 }
 
 int lccrf_lattice_filter(int device_id, const float *features, int n_points, int d, const float *in, int value_size,
@@ -1633,22 +1664,12 @@ int lccrf_lattice_filter(int device_id, const float *features, int n_points, int
     lccrf_handle h = nullptr;
     int rc = lccrf_create(&h, device_id, n_points, value_size);        // value_size plays the part of the label count
     if (rc) return rc;
-    rc = lccrf_add_pairwise(h, features, d, 1.0f);
     Engine &e = h->eng;
-    if (!rc) rc = e.learn_sizes();
-    if (!rc) rc = e.need_io();
     const size_t n = (size_t)n_points * value_size * sizeof(float);
-    hipError_t er = hipSuccess;
-    if (!rc && n) {
-        er = hipStreamSynchronize(e.stream);
-        if (er == hipSuccess) er = hipMemcpy(e.io_a, in, n, hipMemcpyHostToDevice);
-        if (er == hipSuccess) {
-            launch_filter(e.kdevs[0], e.crf, e.maxV[0], e.io_a, e.io_b, 0, e.stream);
-            er = hipStreamSynchronize(e.stream);
-        }
-        if (er == hipSuccess) er = hipMemcpy(out, e.io_b, n, hipMemcpyDeviceToHost);
-        if (er != hipSuccess) rc = fail(LCCRF_E_HIP, "lccrf_lattice_filter: %s", hipGetErrorString(er));
-    }
+    rc = lccrf_add_pairwise(h, features, d, 1.0f);
+    if (!rc) rc = io_in(e, in, nullptr, n);
+    if (!rc) rc = pairwise_apply_on(h, 0, e.io_b, e.io_a, 0);
+    if (!rc) rc = io_out(e, out, e.io_b, n);
     if (!rc && n_vertices) *n_vertices = e.V_host[0];
     lccrf_destroy(h);
     return rc;
@@ -1846,11 +1867,7 @@ int lccrf_set_unary_device(lccrf_handle h, const float *d_unary)
     { int rc = check_device_array(h, d_unary, n * sizeof(float), "d_unary"); if (rc) return rc; }
     { int rl = e.resolve_late(); if (rl) return rl; }
     if (n) HIP_TRY(hipMemcpyAsync(e.unary_own, d_unary, n * sizeof(float), hipMemcpyDefault, e.stream));
-    e.crf.unary = e.unary_own;
-    e.unary_deferred = false;
-    e.unary_is_label = false;
-    e.unary_p_valid = false;
-    e.unary_set = true;
+    e.bind_unary(e.unary_own);
     return LCCRF_OK;
 }
 
@@ -1883,11 +1900,7 @@ int lccrf_set_unary_from_label_device(lccrf_handle h, const int16_t *d_label, co
         launch_unary_from_label_tbl(c, d_label, e.label_table(cf), e.stream);
         HIP_TRY(hipGetLastError());
     }
-    e.crf.unary = e.unary_own;
-    e.unary_deferred = false;
-    e.unary_is_label = false;
-    e.unary_p_valid = false;
-    e.unary_set = true;
+    e.bind_unary(e.unary_own);
     return LCCRF_OK;
 }
 
@@ -1941,62 +1954,35 @@ int lccrf_pairwise_apply_device(lccrf_handle h, int kernel, float *d_out, const 
 {
     CHECK_H(h);
     CHECK_K(h, kernel);
-    Engine &e = h->eng;
-    const size_t n = (size_t)h->N * e.L * sizeof(float);
+    const size_t n = (size_t)h->N * h->eng.L * sizeof(float);
     { int rc = check_device_array(h, d_out, n, "d_out"); if (rc) return rc; }
     { int rc = check_device_array(h, d_in, n, "d_in"); if (rc) return rc; }
-    int rc = e.resolve_late();
-    if (!rc) rc = e.ensure_plain();
-    if (!rc) rc = e.learn_sizes();                        // builds the lattice if it only exists as staged features
-    if (rc) return rc;
-    if (!n) return LCCRF_OK;
-    launch_filter(e.kdevs[kernel], e.crf, e.maxV[kernel], d_in, d_out, 1, e.stream);
-    HIP_TRY(hipGetLastError());
-    return LCCRF_OK;
+    return pairwise_apply_on(h, kernel, d_out, d_in, 1);
 }
 
 int lccrf_exp_and_normalize_device(lccrf_handle h, float *d_out, const float *d_in, float scale, float relax)
 {
     CHECK_H(h);
-    Engine &e = h->eng;
-    const size_t n = (size_t)h->N * e.L * sizeof(float);
+    const size_t n = (size_t)h->N * h->eng.L * sizeof(float);
     { int rc = check_device_array(h, d_out, n, "d_out"); if (rc) return rc; }
     { int rc = check_device_array(h, d_in, n, "d_in"); if (rc) return rc; }
-    { int rl = e.resolve_late(); if (rl) return rl; }
-    if (!n) return LCCRF_OK;
-    launch_exp_and_normalize(e.crf, d_in, d_out, scale, relax, e.stream);
-    HIP_TRY(hipGetLastError());
-    return LCCRF_OK;
+    return exp_and_normalize_on(h, d_out, d_in, scale, relax);
 }
 
 int lccrf_step_init_device(lccrf_handle h, float *d_next)
 {
     CHECK_H(h);
-    Engine &e = h->eng;
-    const size_t n = (size_t)h->N * e.L * sizeof(float);
+    const size_t n = (size_t)h->N * h->eng.L * sizeof(float);
     { int rc = check_device_array(h, d_next, n, "d_next"); if (rc) return rc; }
-    if (!e.unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
-    int rc = e.resolve_late();
-    if (!rc) rc = e.ensure_plain();
-    if (!rc) rc = e.ensure_unary();
-    if (rc) return rc;
-    if (!n) return LCCRF_OK;
-    launch_step_init(e.crf, d_next, e.stream);
-    HIP_TRY(hipGetLastError());
-    return LCCRF_OK;
+    return step_init_on(h, d_next);
 }
 
 int lccrf_map_of_device(lccrf_handle h, const float *d_prob, int16_t *d_map)
 {
     CHECK_H(h);
-    Engine &e = h->eng;
-    { int rc = check_device_array(h, d_prob, (size_t)h->N * e.L * sizeof(float), "d_prob"); if (rc) return rc; }
+    { int rc = check_device_array(h, d_prob, (size_t)h->N * h->eng.L * sizeof(float), "d_prob"); if (rc) return rc; }
     { int rc = check_device_array(h, d_map, (size_t)h->N * sizeof(int16_t), "d_map"); if (rc) return rc; }
-    { int rl = e.resolve_late(); if (rl) return rl; }
-    if (!h->N) return LCCRF_OK;
-    launch_map_of(e.crf, d_prob, d_map, e.stream);
-    HIP_TRY(hipGetLastError());
-    return LCCRF_OK;
+    return map_of_on(h, d_prob, d_map);
 }
 
 // --------------------------------------------------------------------------------------
@@ -2010,8 +1996,7 @@ int lccrf_set_pairwise_weight(lccrf_handle h, int kernel, float w)
     { int rl = e.resolve_late(); if (rl) return rl; }   // (a pending one-launch inference may still be re-run with the old weight)
     e.kernels[kernel].dev.w = w;
     e.sync_views();
-    e.lean_prep.valid = false;                            // whatever was prepared for the old weights is rewritten
-    e.lean_prep.seen_key = 0;
+    e.invalidate_lean_prep();                             // whatever was prepared for the old weights is rewritten
     return LCCRF_OK;
 }
 
@@ -2109,21 +2094,47 @@ void lccrf_batch_destroy(lccrf_batch_handle b)
     delete b;
 }
 
-static int batch_common_inputs(lccrf_batch *b, int n_frames, const float *conf, bool have_unary, bool have_label)
+// The three batch-input entry points (lccrf_batch_set_inputs_host, _host_async, lccrf_batch_bind_inputs_device) run one sequence:
+// (a) every argument check, with nothing touched yet -- a rejected call leaves the previous inputs bound and usable; (b) settle what
+// the previous batch left pending and reset the batch; (c) the path's own copies; (d) batch_bind_inputs.
+// n_points: the caller's host counts, checked against max_points (*active: the largest), or null for counts on the device.
+static int batch_begin_inputs(lccrf_batch *b, int n_frames, const int32_t *n_points, bool have_unary, bool have_label,
+                              const float *conf, int flags, const float *const *features, const char *features_name, int *active)
 {
     Engine &e = b->eng;
     if (n_frames < 1 || n_frames > e.Fcap) return fail(LCCRF_E_CAPACITY, "n_frames %d not in [1,%d]", n_frames, e.Fcap);
     if (have_unary == have_label) return fail(LCCRF_E_INVALID, "exactly one of unary / label must be given");
     if (have_label && (!conf || e.L < 2)) return fail(LCCRF_E_INVALID, "label input needs conf[n_labels] and >= 2 labels");
+    if (flags & ~LCCRF_HOST_PINNED) return fail(LCCRF_E_INVALID, "unknown flags 0x%x", flags);
+    for (int k = 0; k < b->desc.n_kernels; ++k)
+        if (!features[k]) return fail(LCCRF_E_INVALID, "%s[%d] is NULL", features_name, k);
+    *active = 0;
+    for (int f = 0; n_points && f < n_frames; ++f) {
+        if (n_points[f] < 0 || n_points[f] > e.maxN) return fail(LCCRF_E_CAPACITY, "n_points[%d]=%d not in [0,%d]", f, n_points[f], e.maxN);
+        *active = std::max(*active, n_points[f]);
+    }
     { int rl = e.resolve_late(); if (rl) return rl; }
     e.F = n_frames;
     e.sync_views();
-    e.unary_set = false;
-    e.built = false;
-    e.built_upto = 0;
-    e.sizes_known = false;
-    e.started = false;
+    e.unary_set = e.built = e.started = false;
+    e.invalidate_lattices();
+    b->inputs_set = false;
     return LCCRF_OK;
+}
+
+// (d): bind the unaries (or the labels they are derived from) and the features -- the caller's device arrays, or with
+// features == null the batch's own copies -- and publish the new inputs
+static void batch_bind_inputs(lccrf_batch *b, int active, const float *unary, const int16_t *label, const float *conf,
+                              const float *const *features)
+{
+    Engine &e = b->eng;
+    e.activeN = active;
+    e.crf.n_points = e.npoints_own;
+    if (unary) e.bind_unary(unary);
+    else e.defer_unary_from_label(label, conf);
+    for (int k = 0; k < b->desc.n_kernels; ++k) e.kernels[k].dev.feat = features ? features[k] : e.kernels[k].feat_own;
+    e.sync_views();
+    b->inputs_set = true;
 }
 
 int lccrf_batch_set_inputs_host(lccrf_batch_handle b, int n_frames, const int32_t *n_points, const float *unary,
@@ -2132,36 +2143,20 @@ int lccrf_batch_set_inputs_host(lccrf_batch_handle b, int n_frames, const int32_
     CHECK_H(b);
     if (!n_points) return fail(LCCRF_E_INVALID, "n_points is NULL");
     if (b->desc.n_kernels && !features) return fail(LCCRF_E_INVALID, "features is NULL");
-    int rc = batch_common_inputs(b, n_frames, conf, unary != nullptr, label != nullptr);
+    int active = 0;
+    int rc = batch_begin_inputs(b, n_frames, n_points, unary != nullptr, label != nullptr, conf, 0, features, "features", &active);
     if (rc) return rc;
     Engine &e = b->eng;
-    for (int f = 0; f < n_frames; ++f)
-        if (n_points[f] < 0 || n_points[f] > e.maxN) return fail(LCCRF_E_CAPACITY, "n_points[%d]=%d not in [0,%d]", f, n_points[f], e.maxN);
-    e.activeN = 0;
-    for (int f = 0; f < n_frames; ++f) e.activeN = std::max(e.activeN, n_points[f]);
     HIP_TRY(hipStreamSynchronize(e.stream));
     HIP_TRY(hipMemcpy(e.npoints_own, n_points, sizeof(int) * n_frames, hipMemcpyHostToDevice));
-    e.crf.n_points = e.npoints_own;
-    e.crf.unary = e.unary_own;
     const size_t per = (size_t)e.maxN;
-    if (unary) {
-        HIP_TRY(hipMemcpy(e.unary_own, unary, sizeof(float) * n_frames * per * e.L, hipMemcpyHostToDevice));
-        e.unary_deferred = false;
-        e.unary_is_label = false;
-        e.unary_p_valid = false;
-    } else {
-        HIP_TRY(hipMemcpy(e.label_own, label, sizeof(int16_t) * n_frames * per, hipMemcpyHostToDevice));
-        e.defer_unary_from_label(e.label_own, conf);
-    }
+    if (unary) HIP_TRY(hipMemcpy(e.unary_own, unary, sizeof(float) * n_frames * per * e.L, hipMemcpyHostToDevice));
+    else HIP_TRY(hipMemcpy(e.label_own, label, sizeof(int16_t) * n_frames * per, hipMemcpyHostToDevice));
     for (int k = 0; k < b->desc.n_kernels; ++k) {
-        if (!features[k]) return fail(LCCRF_E_INVALID, "features[%d] is NULL", k);
-        KernelState &ks = e.kernels[k];
+        const KernelState &ks = e.kernels[k];
         HIP_TRY(hipMemcpy(ks.feat_own, features[k], sizeof(float) * n_frames * per * ks.dev.d, hipMemcpyHostToDevice));
-        ks.dev.feat = ks.feat_own;
     }
-    e.sync_views();
-    e.unary_set = true;
-    b->inputs_set = true;
+    batch_bind_inputs(b, active, unary ? e.unary_own : nullptr, e.label_own, conf, nullptr);
     return LCCRF_OK;
 }
 
@@ -2188,17 +2183,11 @@ int lccrf_batch_set_inputs_host_async(lccrf_batch_handle b, int n_frames, const 
     CHECK_H(b);
     if (!n_points) return fail(LCCRF_E_INVALID, "n_points is NULL");
     if (b->desc.n_kernels && !features) return fail(LCCRF_E_INVALID, "features is NULL");
-    if (flags & ~LCCRF_HOST_PINNED) return fail(LCCRF_E_INVALID, "unknown flags 0x%x", flags);
-    for (int k = 0; k < b->desc.n_kernels; ++k)
-        if (!features[k]) return fail(LCCRF_E_INVALID, "features[%d] is NULL", k);
-    int rc = batch_common_inputs(b, n_frames, conf, unary != nullptr, label != nullptr);   // (settles what the previous batch on this handle left pending)
-    if (rc) return rc;
+    int active = 0;
+    int rc = batch_begin_inputs(b, n_frames, n_points, unary != nullptr, label != nullptr, conf, flags, features, "features", &active);
+    if (rc) return rc;                                 // (this settled what the previous batch on this handle left pending)
     Engine &e = b->eng;
     HostPipe &p = b->pipe;
-    for (int f = 0; f < n_frames; ++f)
-        if (n_points[f] < 0 || n_points[f] > e.maxN) return fail(LCCRF_E_CAPACITY, "n_points[%d]=%d not in [0,%d]", f, n_points[f], e.maxN);
-    e.activeN = 0;
-    for (int f = 0; f < n_frames; ++f) e.activeN = std::max(e.activeN, n_points[f]);
     if ((rc = pipe_init(b))) return rc;
     const bool direct = (flags & LCCRF_HOST_PINNED) != 0;
     const size_t per = (size_t)e.maxN, Fz = (size_t)n_frames, Fc = (size_t)e.Fcap;
@@ -2206,14 +2195,12 @@ int lccrf_batch_set_inputs_host_async(lccrf_batch_handle b, int n_frames, const 
         HIP_TRY(hipEventSynchronize(p.ev_up));
         p.up_pending = false;
     }
-    const int32_t *src_np = n_points;
     const float *src_un = unary;
     const int16_t *src_lb = label;
     std::vector<const float *> src_ft(features, features + b->desc.n_kernels);
     // (the point counts are always staged: a few bytes per frame, and the caller's array is usually a local one)
     if (!p.npoints && (rc = pinned_plain(e.mem, &p.npoints, Fc))) return rc;
     memcpy(p.npoints, n_points, sizeof(int) * Fz);
-    src_np = p.npoints;
     if (!direct) {                                     // copy out of the caller's buffers before returning
         std::vector<CopyPool::Job> jobs;
         if (unary) {
@@ -2240,29 +2227,17 @@ int lccrf_batch_set_inputs_host_async(lccrf_batch_handle b, int n_frames, const 
     // device copies), and whatever is queued from here on waits for the upload
     HIP_TRY(hipEventRecord(p.ev_q, e.stream));
     HIP_TRY(hipStreamWaitEvent(p.up, p.ev_q, 0));
-    HIP_TRY(hipMemcpyAsync(e.npoints_own, src_np, sizeof(int) * Fz, hipMemcpyHostToDevice, p.up));
-    e.crf.n_points = e.npoints_own;
-    e.crf.unary = e.unary_own;
-    if (unary) {
-        HIP_TRY(hipMemcpyAsync(e.unary_own, src_un, sizeof(float) * Fz * per * e.L, hipMemcpyHostToDevice, p.up));
-        e.unary_deferred = false;
-        e.unary_is_label = false;
-        e.unary_p_valid = false;
-    } else {
-        HIP_TRY(hipMemcpyAsync(e.label_own, src_lb, sizeof(int16_t) * Fz * per, hipMemcpyHostToDevice, p.up));
-        e.defer_unary_from_label(e.label_own, conf);
-    }
+    HIP_TRY(hipMemcpyAsync(e.npoints_own, p.npoints, sizeof(int) * Fz, hipMemcpyHostToDevice, p.up));
+    if (unary) HIP_TRY(hipMemcpyAsync(e.unary_own, src_un, sizeof(float) * Fz * per * e.L, hipMemcpyHostToDevice, p.up));
+    else HIP_TRY(hipMemcpyAsync(e.label_own, src_lb, sizeof(int16_t) * Fz * per, hipMemcpyHostToDevice, p.up));
     for (int k = 0; k < b->desc.n_kernels; ++k) {
-        KernelState &ks = e.kernels[k];
+        const KernelState &ks = e.kernels[k];
         HIP_TRY(hipMemcpyAsync(ks.feat_own, src_ft[k], sizeof(float) * Fz * per * ks.dev.d, hipMemcpyHostToDevice, p.up));
-        ks.dev.feat = ks.feat_own;
     }
     HIP_TRY(hipEventRecord(p.ev_up, p.up));
     HIP_TRY(hipStreamWaitEvent(e.stream, p.ev_up, 0));
     p.up_pending = true;
-    e.sync_views();
-    e.unary_set = true;
-    b->inputs_set = true;
+    batch_bind_inputs(b, active, unary ? e.unary_own : nullptr, e.label_own, conf, nullptr);
     return LCCRF_OK;
 }
 
@@ -2363,30 +2338,15 @@ int lccrf_batch_bind_inputs_device(lccrf_batch_handle b, int n_frames, const int
     CHECK_H(b);
     if (!d_n_points) return fail(LCCRF_E_INVALID, "d_n_points is NULL");
     if (b->desc.n_kernels && !d_features) return fail(LCCRF_E_INVALID, "d_features is NULL");
-    int rc = batch_common_inputs(b, n_frames, conf, d_unary != nullptr, d_label != nullptr);
+    int active = 0;                                   // per-frame sizes live on the device: unknown here
+    int rc = batch_begin_inputs(b, n_frames, nullptr, d_unary != nullptr, d_label != nullptr, conf, 0, d_features, "d_features", &active);
     if (rc) return rc;
     Engine &e = b->eng;
-    e.activeN = 0;                                    // per-frame sizes live on the device: unknown here
     // the kernels index every per-frame array with n_points[f]: work on a validated copy (clamped to
     // [0, max_points]; an out-of-range entry raises LCCRF_E_CAPACITY at the next synchronisation point)
     launch_validate_npoints(d_n_points, e.npoints_own, n_frames, e.maxN, e.npoints_bad, e.stream);
-    e.crf.n_points = e.npoints_own;
-    if (d_unary) {
-        e.crf.unary = const_cast<float *>(d_unary);   // read-only use
-        e.unary_deferred = false;
-        e.unary_is_label = false;
-        e.unary_p_valid = false;
-    } else {
-        e.defer_unary_from_label(d_label, conf);
-    }
-    for (int k = 0; k < b->desc.n_kernels; ++k) {
-        if (!d_features[k]) return fail(LCCRF_E_INVALID, "d_features[%d] is NULL", k);
-        e.kernels[k].dev.feat = d_features[k];
-    }
-    e.sync_views();
     HIP_TRY(hipGetLastError());
-    e.unary_set = true;
-    b->inputs_set = true;
+    batch_bind_inputs(b, active, d_unary, d_label, conf, d_features);
     return LCCRF_OK;
 }
 
@@ -2418,22 +2378,36 @@ struct StreamScope {
     }
 };
 
+// The timed batch calls (build, inference, run): `body` runs in a StreamScope on the call's stream, between the events `begin` and
+// `end` when event timing is on; `timed` tells lccrf_batch_last_timing whether that pair now holds this call's time.
+extern "C++" {
+template <typename Body>
+static int timed_batch_call(Engine &e, void *stream, hipEvent_t begin, hipEvent_t end, bool &timed, Body body)
+{
+    StreamScope scope(e, stream);
+    int rc = scope.enter();
+    if (rc) return rc;
+    if (e.event_timing) HIP_TRY(hipEventRecord(begin, e.stream));
+    rc = body();
+    if (!rc && e.event_timing) {
+        hipError_t er = hipEventRecord(end, e.stream);
+        if (er != hipSuccess) rc = fail(LCCRF_E_HIP, "hipEventRecord: %s", hipGetErrorString(er));
+    }
+    timed = !rc && e.event_timing;
+    return rc;
+}
+}  // extern "C++"
+
 int lccrf_batch_build(lccrf_batch_handle b, void *stream)
 {
     CHECK_H(b);
     if (!b->inputs_set) return fail(LCCRF_E_STATE, "inputs not set");
     Engine &e = b->eng;
-    StreamScope scope(e, stream);
-    int rc = scope.enter();
-    if (rc) return rc;
-    if (e.event_timing) HIP_TRY(hipEventRecord(e.ev[0], e.stream));
-    if (!e.kernels.empty()) rc = e.build_kernels(0, (int)e.kernels.size());
-    e.built_upto = (int)e.kernels.size();
-    if (!rc && e.event_timing) {
-        hipError_t er = hipEventRecord(e.ev[1], e.stream);
-        if (er != hipSuccess) rc = fail(LCCRF_E_HIP, "hipEventRecord: %s", hipGetErrorString(er));
-    }
-    e.timed_build = !rc && e.event_timing;
+    const int rc = timed_batch_call(e, stream, e.ev[0], e.ev[1], e.timed_build, [&] {
+        const int rb = e.kernels.empty() ? LCCRF_OK : e.build_kernels(0, (int)e.kernels.size());
+        e.built_upto = (int)e.kernels.size();
+        return rb;
+    });
     e.built = !rc;
     return rc;                                        // (learn_sizes() waits on the own stream, which ~StreamScope orders behind this one)
 }
@@ -2445,16 +2419,7 @@ int lccrf_batch_inference(lccrf_batch_handle b, int n_iterations, int with_map, 
     if (!e.built) return fail(LCCRF_E_STATE, "lccrf_batch_build has not run for these inputs");
     int rc = e.learn_sizes();
     if (rc) return rc;
-    StreamScope scope(e, stream);
-    if ((rc = scope.enter())) return rc;
-    if (e.event_timing) HIP_TRY(hipEventRecord(e.ev[2], e.stream));
-    rc = e.inference(n_iterations, with_map, relax);
-    if (!rc && e.event_timing) {
-        hipError_t er = hipEventRecord(e.ev[3], e.stream);
-        if (er != hipSuccess) rc = fail(LCCRF_E_HIP, "hipEventRecord: %s", hipGetErrorString(er));
-    }
-    e.timed_inf = !rc && e.event_timing;
-    return rc;
+    return timed_batch_call(e, stream, e.ev[2], e.ev[3], e.timed_inf, [&] { return e.inference(n_iterations, with_map, relax); });
 }
 
 int lccrf_batch_run(lccrf_batch_handle b, int n_iterations, int with_map, float relax, void *stream)
@@ -2462,16 +2427,7 @@ int lccrf_batch_run(lccrf_batch_handle b, int n_iterations, int with_map, float 
     CHECK_H(b);
     if (!b->inputs_set) return fail(LCCRF_E_STATE, "inputs not set");
     Engine &e = b->eng;
-    StreamScope scope(e, stream);
-    int rc = scope.enter();
-    if (rc) return rc;
-    if (e.event_timing) HIP_TRY(hipEventRecord(e.ev[2], e.stream));
-    rc = e.run(n_iterations, with_map, relax);
-    if (!rc && e.event_timing) {
-        hipError_t er = hipEventRecord(e.ev[3], e.stream);
-        if (er != hipSuccess) rc = fail(LCCRF_E_HIP, "hipEventRecord: %s", hipGetErrorString(er));
-    }
-    e.timed_inf = !rc && e.event_timing;
+    const int rc = timed_batch_call(e, stream, e.ev[2], e.ev[3], e.timed_inf, [&] { return e.run(n_iterations, with_map, relax); });
     e.built = e.built_upto == (int)e.kernels.size() && !e.kernels.empty();
     return rc;
 }
@@ -2488,26 +2444,28 @@ int lccrf_batch_synchronize(lccrf_batch_handle b)
     return b->eng.resolve_late();
 }
 
+// The batch read-backs: settle a pending one-launch run (its re-run of flagged frames included), then copy `bytes` of a device array
+// of the batch to the caller.
+static int batch_read_back(lccrf_batch *b, void *out, const void *d_src, size_t bytes)
+{
+    { int rl = b->eng.resolve_late(); if (rl) return rl; }
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, d_src, bytes, hipMemcpyDeviceToHost));
+    return LCCRF_OK;
+}
+
 int lccrf_batch_get_map_host(lccrf_batch_handle b, int16_t *map_out)
 {
     CHECK_H(b);
     if (!map_out) return fail(LCCRF_E_INVALID, "map_out is NULL");
-    Engine &e = b->eng;
-    { int rl = b->eng.resolve_late(); if (rl) return rl; }
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(map_out, e.crf.map, sizeof(int16_t) * (size_t)e.F * e.maxN, hipMemcpyDeviceToHost));
-    return LCCRF_OK;
+    return batch_read_back(b, map_out, b->eng.crf.map, sizeof(int16_t) * (size_t)b->eng.F * b->eng.maxN);
 }
 
 int lccrf_batch_get_probability_host(lccrf_batch_handle b, float *prob_out)
 {
     CHECK_H(b);
     if (!prob_out) return fail(LCCRF_E_INVALID, "prob_out is NULL");
-    Engine &e = b->eng;
-    { int rl = b->eng.resolve_late(); if (rl) return rl; }
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(prob_out, e.crf.Q, sizeof(float) * (size_t)e.F * e.maxN * e.L, hipMemcpyDeviceToHost));
-    return LCCRF_OK;
+    return batch_read_back(b, prob_out, b->eng.crf.Q, sizeof(float) * (size_t)b->eng.F * b->eng.maxN * b->eng.L);
 }
 
 int lccrf_batch_get_lattice_sizes_host(lccrf_batch_handle b, int kernel, int32_t *n_vertices_out)
@@ -2515,11 +2473,7 @@ int lccrf_batch_get_lattice_sizes_host(lccrf_batch_handle b, int kernel, int32_t
     CHECK_H(b);
     CHECK_K(b, kernel);
     if (!n_vertices_out) return fail(LCCRF_E_INVALID, "n_vertices_out is NULL");
-    Engine &e = b->eng;
-    { int rl = b->eng.resolve_late(); if (rl) return rl; }
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(n_vertices_out, e.kernels[kernel].dev.V, sizeof(int) * e.F, hipMemcpyDeviceToHost));
-    return LCCRF_OK;
+    return batch_read_back(b, n_vertices_out, b->eng.kernels[kernel].dev.V, sizeof(int) * b->eng.F);
 }
 
 int lccrf_batch_get_norm_host(lccrf_batch_handle b, int kernel, float *norm_out)
@@ -2539,9 +2493,7 @@ int lccrf_batch_get_norm_host(lccrf_batch_handle b, int kernel, float *norm_out)
         HIP_TRY(hipGetLastError());
         src = e.io_a;
     }
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(norm_out, src, sizeof(float) * (size_t)e.F * e.maxN, hipMemcpyDeviceToHost));
-    return LCCRF_OK;
+    return batch_read_back(b, norm_out, src, sizeof(float) * (size_t)e.F * e.maxN);   // (nothing left to settle)
 }
 
 int lccrf_batch_device_buffers(lccrf_batch_handle b, const int16_t **d_map, const float **d_prob)

@@ -530,6 +530,48 @@ def test_bound_n_points_out_of_range_is_reported_not_followed(wl):
     b.close()
 
 
+def test_rejected_batch_inputs_leave_the_bound_inputs_usable(wl):
+    """A batch-input call that is rejected touches nothing: the inputs bound before it still run, bit for bit, on the
+    one-launch path and on build + inference."""
+    import torch
+    F, N = 4, 600
+    pbs = [wl.slam_problem(N, seed=330 + i) for i in range(F)]
+    feats = [np.stack([pb["kernels"][k][0] for pb in pbs]) for k in range(2)]
+    label = np.stack([pb["label"] for pb in pbs])
+    b = pkg.BatchCRF(F, N, 2, [2, 2], [10.0, 30.0])
+    b.set_inputs_host([N] * F, feats, label=label, conf=0.7)
+    b.run(5, True)
+    ran = (b.probability(), b.map())
+    b.build()
+    b.inference(5, True)
+    inferred = (b.probability(), b.map())
+
+    def still_bound():
+        b.run(5, True)
+        assert cc.same_bits(b.probability(), ran[0]) and np.array_equal(b.map(), ran[1])
+        b.build()
+        b.inference(5, True)
+        assert cc.same_bits(b.probability(), inferred[0]) and np.array_equal(b.map(), inferred[1])
+
+    # other inputs on fewer frames: none of them may be bound by a call that is rejected
+    other = [np.ascontiguousarray(f[:0:-1]) for f in feats]
+    other_label = np.ascontiguousarray(label[:0:-1])
+    with pytest.raises(pkg.LccrfError) as ei:
+        b.set_inputs_host([N, N + 1, N], other, label=other_label, conf=0.7)
+    assert ei.value.code == -6
+    still_bound()
+    dev = torch.device("cuda", 0)
+    d_f0 = torch.from_numpy(other[0]).to(dev)
+    d_label = torch.from_numpy(other_label).to(dev)
+    d_np = torch.full((F - 1,), N, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    with pytest.raises(pkg.LccrfError) as ei:
+        b.bind_inputs_device(F - 1, d_np.data_ptr(), [d_f0.data_ptr(), 0], d_label=d_label.data_ptr(), conf=0.7)
+    assert ei.value.code == -1
+    still_bound()
+    b.close()
+
+
 def test_hip_c5_full_size_matches_oracle(po, wl):
     """BASELINE config 5 at FULL size: 100 000 points, one 6-D kernel (V ~ 5.9e5: hash capacity
     2^21, 700k-entry scans, the multi-launch iteration), 20 iterations -- one frame through the object API and one
