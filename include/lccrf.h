@@ -422,6 +422,48 @@ int  lccrf_batch_time_blur_pass(lccrf_batch_handle b, int kernel, int reps, floa
                                 int64_t *vertices_per_launch);
 
 /* ======================================================================================
+ * 2c. Gradients of a batch's inference -- section 1c for every frame of a batch at once: one reverse sweep over the F frames, in
+ *     the number of launches section 1c takes for one frame.  The formulas are section 1c's, per frame; the weights w_k are the
+ *     batch's (lccrf_batch_desc.weights, shared by every frame), and so are the parameters fitted.
+ * ==================================================================================== */
+/* lccrf_set_pairwise_weight for a batch: the weight of term `kernel` in every frame.  The lattices, norms and prepared launch records'
+ * lattice part stay; everything derived from w (the fused engines' w*norm products, the prepared launch records) is invalidated, and
+ * the next lccrf_batch_inference / _run equals, bit for bit, that of a batch created with weight w.  A pending one-launch run is
+ * settled first (its fallback frames re-run with the old weight).                                                               */
+int  lccrf_batch_set_pairwise_weight(lccrf_batch_handle b, int kernel, float w);
+/* Replaces the unary energies of the n_frames frames now bound: d_unary [n_frames][max_points][L], device memory (checked as in
+ * section 1b), COPIED into the batch's own array on the batch's stream -- the caller's array may be freed behind that copy.  Labels
+ * the inputs came from are forgotten; lattices, norms and prepared launch records stay.  LCCRF_E_STATE before inputs are set.      */
+int  lccrf_batch_set_unary_device(lccrf_batch_handle b, const float *d_unary);
+/* Gradients of lccrf_batch_inference(b, n_iterations, -, relax, -) on the batch's current inputs and weights, per frame:
+ * d_grad_prob [n_frames][max_points][L] = dL/dQ_T, d_grad_unary [n_frames][max_points][L] (overwritten), d_grad_weights
+ * [n_frames][n_kernels] (overwritten; may be NULL).  Device arrays, checked as in section 1b against n_frames * max_points * L
+ * (n_frames * n_kernels) floats.
+ *   - Per frame, the bits of section 1c: d_grad_unary[f] and d_grad_weights[f][:] are exactly what lccrf_inference_backward returns
+ *     for a handle holding frame f's n_points[f] points, unary and features and the batch's weights (the weight gradient is reduced
+ *     over the same T x B partials in the same order, B = backward_blocks of n_points[f] as section 1c counts them).  Rows at or
+ *     beyond n_points[f] of d_grad_unary are written 0; a frame of 0 points gets zero gradients.
+ *   - Self-contained, as section 1c: the forward is replayed on the step path, keeping Q_0 .. Q_{T-1} of every frame (one copy of
+ *     the whole [n_frames][max_points][L] array per iteration).  Afterwards the batch's Q (lccrf_batch_device_buffers,
+ *     lccrf_batch_get_probability_host) holds exactly what lccrf_batch_inference(b, n_iterations, 0, relax, stream) would have left;
+ *     the labels are untouched.
+ *   - Needs lccrf_batch_build or lccrf_batch_run on the current inputs (LCCRF_E_STATE otherwise); a pending one-launch run is
+ *     settled first (its fallback frames included), and lattices the one-launch kernel kept on chip are built in HBM.  Frames in
+ *     locality mode (>= 8192 points) are handled as section 1c handles them: the lattices are re-built the plain way for this call
+ *     (the next lccrf_batch_build / _run decides afresh); results are in the caller's point order.
+ *   - Deterministic: no float atomics; the same bits from run to run.
+ *   - Streams: `stream` is a hipStream_t or NULL, as for lccrf_batch_inference; no host synchronisation beyond the one-time learning
+ *     of new lattices' sizes every entry point does.  lccrf_batch_last_timing's inference_ms then times this call.
+ *   - Memory: a batch-owned HBM area of 4 * (F*S*(T + K + 1) + max(T,1)*K*F*B) bytes, F = n_frames, S = max_points * L,
+ *     B = backward_blocks(max_points, L) as section 1c counts them (16384 frames of max_points = 2000, L = 2, K = 2, T = 5: 2.1 GB).
+ *     Zeroed when allocated, grown by the first call that needs more, freed by lccrf_batch_destroy; a failed allocation returns
+ *     LCCRF_E_NOMEM and leaves the batch usable.  lccrf_batch_inference / _run never allocate it.
+ *   - Errors: LCCRF_E_INVALID for n_iterations < 0, a relax that is not finite, or a device array section 1b refuses; a rejected
+ *     call leaves the batch's inputs, lattices and Q as they were.  K = 0 is legal (d_grad_weights then receives nothing).       */
+int  lccrf_batch_inference_backward(lccrf_batch_handle b, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
+                                    float *d_grad_weights, void *stream);
+
+/* ======================================================================================
  * 3. Unary builder -- the step right before the CRF (first "next" row):
  *    Tracking::ComputeMapPointErrAndObserv (src/Tracking.cc:1803-1839) for every candidate map
  *    point, then Tracking::RroughClassify (src/Tracking.cc:1961-2013).  The caller flattens the

@@ -146,6 +146,9 @@ def lib():
     L.lccrf_batch_last_prepare.argtypes = [vp, _f32p, C.POINTER(C.c_int)]
     L.lccrf_batch_get_stream.argtypes = [vp, C.POINTER(vp)]
     L.lccrf_batch_time_blur_pass.argtypes = [vp, C.c_int, C.c_int, _f32p, C.POINTER(C.c_int64)]
+    L.lccrf_batch_set_pairwise_weight.argtypes = [vp, C.c_int, C.c_float]
+    L.lccrf_batch_set_unary_device.argtypes = [vp, vp]
+    L.lccrf_batch_inference_backward.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, vp]
     L.lccrf_bf_match.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_double, _i32p, _i32p]
     L.lccrf_pose_optimization.argtypes = [C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, C.c_void_p, _i16p, _f32p, C.c_float,
                                           _f32p, _f32p, C.c_void_p, _i32p]
@@ -383,7 +386,7 @@ class BatchCRF:
             d.feat_dims[i] = fd
             d.weights[i] = float(w)
         self.h = C.c_void_p()
-        self.n_frames = 0
+        self.n_frames, self.n_points = 0, None        # n_points: the host counts of the inputs bound, when they came from the host
         _check(lib().lccrf_batch_create(C.byref(self.h), int(device), C.byref(d)))
         self._keep = None
 
@@ -411,7 +414,7 @@ class BatchCRF:
         _check(lib().lccrf_batch_set_inputs_host(
             self.h, F, _p(npts, _i32p), _p(u, _f32p) if u is not None else None,
             _p(l, _i16p) if l is not None else None, _p(cf, _f32p) if cf is not None else None, arr))
-        self.n_frames = F
+        self.n_frames, self.n_points = F, npts.copy()
 
     HOST_PINNED = 1
     DOWNLOAD_LABEL_BITS, DOWNLOAD_MAP, DOWNLOAD_PROBABILITY = 1, 2, 4
@@ -438,7 +441,7 @@ class BatchCRF:
         _check(lib().lccrf_batch_set_inputs_host_async(
             self.h, F, C.c_void_p(npts.ctypes.data), u, l, _p(cf, _f32p) if cf is not None else None, arr,
             self.HOST_PINNED if pinned else 0))
-        self.n_frames = F
+        self.n_frames, self.n_points = F, npts.copy()
 
     def wait_inputs(self):
         _check(lib().lccrf_batch_wait_inputs(self.h))
@@ -476,7 +479,7 @@ class BatchCRF:
             C.c_void_p(int(d_unary)) if d_unary is not None else None,
             C.c_void_p(int(d_label)) if d_label is not None else None,
             _p(cf, _f32p) if cf is not None else None, arr))
-        self.n_frames = int(n_frames)
+        self.n_frames, self.n_points = int(n_frames), None        # (the counts live on the device)
 
     def build(self, stream=None):
         _check(lib().lccrf_batch_build(self.h, C.c_void_p(stream) if stream else None))
@@ -492,6 +495,22 @@ class BatchCRF:
 
     def synchronize(self):
         _check(lib().lccrf_batch_synchronize(self.h))
+
+    def set_pairwise_weight(self, k, w):
+        """The weight of term k in every frame; the next inference equals that of a batch created with weight w."""
+        _check(lib().lccrf_batch_set_pairwise_weight(self.h, int(k), float(w)))
+
+    def set_unary_device(self, d_unary):
+        """Unaries [n_frames][max_points][L] of the frames now bound, copied from a device address on the batch's stream."""
+        _check(lib().lccrf_batch_set_unary_device(self.h, C.c_void_p(int(d_unary))))
+
+    def inference_backward_device(self, n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights=None, stream=None):
+        """Per frame dL/dU [n_frames][max_points][L] and dL/dw [n_frames][K] of inference(n_iterations, relax) from dL/dQ
+        [n_frames][max_points][L]; device addresses (include/lccrf.h section 2c)."""
+        _check(lib().lccrf_batch_inference_backward(self.h, int(n_iterations), float(relax), C.c_void_p(int(d_grad_prob)),
+                                                    C.c_void_p(int(d_grad_unary)),
+                                                    C.c_void_p(int(d_grad_weights)) if d_grad_weights else None,
+                                                    C.c_void_p(stream) if stream else None))
 
     def set_engine(self, engine):
         _check(lib().lccrf_batch_set_engine(self.h, int(engine)))

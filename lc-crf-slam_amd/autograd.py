@@ -1,7 +1,10 @@
-"""torch autograd through DenseCRF::inference on the HIP path (include/lccrf.h section 1c).
+"""torch autograd through DenseCRF::inference on the HIP path (include/lccrf.h sections 1c and 2c).
 
     Q = mean_field(crf, unary, weights, n_iterations=5, relax=1.0)
     Q.backward(g)      # -> unary.grad = dL/dU, weights.grad = dL/dw
+
+    Q = mean_field_batch(batch, unary, weights, n_iterations=5, relax=1.0)     # every frame of a BatchCRF at once
+    Q.backward(g)      # -> unary.grad [F, max_points, L], weights.grad = sum over the frames of dL/dw
 
 `crf` is a DenseCRFHIP whose pairwise terms are already added (their features fix the lattices; only the weights are
 inputs here).  Forward: lccrf_set_pairwise_weight + lccrf_set_unary_device + lccrf_inference.  Backward:
@@ -9,7 +12,8 @@ lccrf_inference_backward, which replays the forward itself, so nothing but the i
 
 Streams (the pattern of section 1b): on entry the handle's stream waits for torch's current stream (the inputs and the
 incoming gradient are produced there); on exit torch's current stream waits for the handle's stream.  inference()
-results are complete behind lccrf_synchronize, so the forward synchronises the handle before it copies Q out.
+results are complete behind lccrf_synchronize, so the forward synchronises the handle before it copies Q out.  The batch
+layer follows the same pattern on the batch's own stream (lccrf_batch_inference leaves nothing to settle).
 """
 import importlib
 
@@ -111,3 +115,94 @@ class MeanFieldCRF(torch.nn.Module):
 
     def close(self):
         self.crf.close()
+
+
+class _MeanFieldBatch(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, batch, unary, weights, n_iterations, relax, n_points):
+        F, N, L = batch.n_frames, batch.maxN, batch.L
+        if not unary.is_cuda or unary.dtype != torch.float32 or tuple(unary.shape) != (F, N, L):
+            raise ValueError("unary must be a float32 GPU tensor of shape [%d, %d, %d]" % (F, N, L))
+        K = len(batch.dims)
+        if weights.dtype != torch.float32 or tuple(weights.shape) != (K,):
+            raise ValueError("weights must be a float32 tensor of shape [%d]" % K)
+        if n_iterations < 0:
+            raise ValueError("n_iterations must be >= 0")
+        dev = unary.device
+        u = unary.detach().contiguous()
+        for k, w in enumerate(weights.detach().cpu().tolist()):
+            batch.set_pairwise_weight(k, w)
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(batch.own_stream(), device=dev)
+        ext.wait_stream(cur)
+        batch.set_unary_device(u.data_ptr())
+        batch.inference(int(n_iterations), False, float(relax))
+        with torch.cuda.stream(ext):
+            q = _device_view(batch.device_buffers()[1], (F, N, L), dev).clone()
+        cur.wait_stream(ext)
+        q.record_stream(cur)
+        live = torch.arange(N, device=dev)[None, :] < torch.as_tensor(n_points, device=dev)[:, None]
+        q = torch.where(live[:, :, None], q, torch.zeros((), device=dev))    # rows beyond a frame's points: 0
+        ctx.batch, ctx.n_iterations, ctx.relax = batch, int(n_iterations), float(relax)
+        ctx.weights_device = weights.device
+        ctx.save_for_backward(u, weights.detach().clone())
+        return q
+
+    @staticmethod
+    def backward(ctx, grad_q):
+        u, w = ctx.saved_tensors
+        batch = ctx.batch
+        dev = u.device
+        g = grad_q.detach().to(device=dev, dtype=torch.float32).contiguous()
+        cur = torch.cuda.current_stream(dev)
+        K = int(w.numel())
+        # the batch is re-armed with the inputs of this forward (it may have run other unaries or weights since)
+        for k, wk in enumerate(w.cpu().tolist()):
+            batch.set_pairwise_weight(k, wk)
+        grad_u = torch.empty_like(u)
+        grad_w = torch.empty((batch.n_frames, max(K, 1)), dtype=torch.float32, device=dev)
+        ext = torch.cuda.ExternalStream(batch.own_stream(), device=dev)
+        ext.wait_stream(cur)
+        batch.set_unary_device(u.data_ptr())
+        batch.inference_backward_device(ctx.n_iterations, ctx.relax, g.data_ptr(), grad_u.data_ptr(),
+                                        grad_w.data_ptr() if K else None)
+        cur.wait_stream(ext)
+        return None, grad_u, grad_w[:, :K].sum(0).to(ctx.weights_device), None, None, None
+
+
+def mean_field_batch(batch, unary, weights, n_iterations=5, relax=1.0):
+    """Q_T [F, max_points, L] of every frame's DenseCRF::inference(n_iterations, relax) on a built BatchCRF (inputs set with host
+    point counts, lattices built: build() or run()), with unary energies `unary` [F, max_points, L] (float32, GPU) and the batch's
+    term weights `weights` [K] (float32, any device); differentiable in both.  Rows beyond a frame's points are 0 in Q and in
+    unary.grad; weights.grad is the sum over the frames of their dL/dw."""
+    if batch.n_points is None:
+        raise ValueError("the batch's point counts are on the device only (bind_inputs_device): set its inputs from the host")
+    return _MeanFieldBatch.apply(batch, unary, weights, n_iterations, relax, batch.n_points)
+
+
+class BatchMeanFieldCRF(torch.nn.Module):
+    """A dense CRF layer over many frames: one BatchCRF over fixed per-frame features, the term weights (shared by every frame) an
+    nn.Parameter.  The features are uploaded and the lattices built once, here; forward() only sets weights and unaries.
+
+    n_points: [F] points per frame; features: list of [F, max_points, d_k] arrays (already divided by the kernel's standard
+    deviation); weights: their initial weights.  forward(unary [F, max_points, L]) -> Q [F, max_points, L]."""
+
+    def __init__(self, n_points, features, weights, n_iterations=5, relax=1.0, device=0, n_labels=2):
+        super().__init__()
+        if len(features) != len(weights):
+            raise ValueError("one weight per feature array")
+        feats = [np.ascontiguousarray(f.detach().cpu().numpy() if isinstance(f, torch.Tensor) else f, np.float32) for f in features]
+        n_points = np.ascontiguousarray(n_points, np.int32)
+        F = int(n_points.size)
+        N = int(feats[0].shape[1]) if feats else int(n_points.max(initial=0))
+        self.batch = _pkg.BatchCRF(F, N, n_labels, [f.shape[2] for f in feats], [float(w) for w in weights], device=device)
+        self.batch.set_inputs_host(n_points, feats, unary=np.zeros((F, N, n_labels), np.float32))
+        self.batch.build()
+        self.weights = torch.nn.Parameter(torch.tensor([float(w) for w in weights], dtype=torch.float32))
+        self.n_iterations, self.relax = int(n_iterations), float(relax)
+
+    def forward(self, unary):
+        return mean_field_batch(self.batch, unary, self.weights, self.n_iterations, self.relax)
+
+    def close(self):
+        self.batch.close()

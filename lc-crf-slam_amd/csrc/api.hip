@@ -173,8 +173,8 @@ struct Engine {
     int *npoints_bad = nullptr;        // pinned: set by the validation kernel when a bound n_points[f] is outside [0, maxN]
     float *io_a = nullptr, *io_b = nullptr;   // device [Fcap][maxN][L] each: caller buffers of apply / expAndNormalize / ... (lazy)
     int16_t *io_map = nullptr;
-    // lccrf_inference_backward's area (engine.h: BackwardArea): its own allocation, grown on demand and freed with the handle's use
-    // (recycle) -- a parked handle does not keep it
+    // the area of lccrf_inference_backward / lccrf_batch_inference_backward (engine.h: BackwardArea): its own allocation, grown on
+    // demand and freed with the handle's use (recycle) -- a parked handle does not keep it -- or with the batch
     unsigned char *bwd_area = nullptr;
     size_t bwd_area_bytes = 0;
     void free_backward_area()
@@ -184,6 +184,51 @@ struct Engine {
         (void)hipFree(bwd_area);
         bwd_area = nullptr;
         bwd_area_bytes = 0;
+    }
+    // at least `need` bytes of area, zeroed on the call's stream when (re)allocated; a failed allocation leaves the engine without one
+    // and changes nothing else
+    int ensure_backward_area(size_t need)
+    {
+        if (need <= bwd_area_bytes) return LCCRF_OK;
+        free_backward_area();
+        void *p = nullptr;
+        const hipError_t ea = hipMalloc(&p, need);
+        if (ea != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ea == hipErrorOutOfMemory ? LCCRF_E_NOMEM : LCCRF_E_HIP, "hipMalloc(%zu bytes) for the backward area: %s", need,
+                        hipGetErrorString(ea));
+        }
+        bwd_area = static_cast<unsigned char *>(p);
+        bwd_area_bytes = need;
+        HIP_TRY(hipMemsetAsync(p, 0, need, stream));
+        return LCCRF_OK;
+    }
+    // The backward on the area: inference(T, 0, relax) replayed on the step path (start + T x step), `count` floats of Q kept per
+    // iteration in arrays of `slice` floats, dL/dQ_T copied in, then the reverse sweep over frames of up to `rows` points.
+    int backward(size_t slice, size_t count, int rows, int T, float relax, const float *grad_prob, float *grad_unary, float *grad_weights)
+    {
+        const int K = (int)kernels.size();
+        BackwardArea ar;
+        ar.slice = slice;
+        ar.hist = reinterpret_cast<float *>(bwd_area);
+        ar.phi = ar.hist + (size_t)T * slice;
+        ar.G = ar.phi + (size_t)K * slice;
+        ar.partial = ar.G + slice;
+        int rc = start();                                 // (ensure_plain: a handle's frames in locality mode are re-built the plain way once)
+        if (!rc) rc = learn_sizes();
+        if (rc) return rc;
+        for (int t = 0; t < T; ++t) {
+            if (count) HIP_TRY(hipMemcpyAsync(ar.hist + (size_t)t * slice, crf.Q, count * sizeof(float), hipMemcpyDeviceToDevice, stream));
+            if ((rc = step(relax))) return rc;
+        }
+        if (!count) {                                     // nothing to differentiate: dL/dw = 0
+            if (grad_weights && K) HIP_TRY(hipMemsetAsync(grad_weights, 0, (size_t)F * K * sizeof(float), stream));
+            return LCCRF_OK;
+        }
+        HIP_TRY(hipMemcpyAsync(ar.G, grad_prob, count * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        launch_backward_sweep(crf, kdevs.data(), maxV.data(), rows, T, relax, ar, grad_unary, grad_weights, stream);
+        HIP_TRY(hipGetLastError());
+        return LCCRF_OK;
     }
 
     int need_io()
@@ -865,6 +910,16 @@ struct Engine {
         perm_banned = true;
         invalidate_lattices();
         return flush_builds();
+    }
+    // ... and the same for a batch's backward (lccrf_batch_inference_backward): every frame's lattices in HBM, built the plain way --
+    // re-built if they are in locality mode.  For this call only: the next lccrf_batch_build / _run decides the point order afresh.
+    int ensure_plain_batch()
+    {
+        perm_banned = true;
+        if (perm_on) invalidate_lattices();
+        const int rc = learn_sizes();
+        perm_banned = false;
+        return rc;
     }
 
     // lccrf_batch_run: per frame the PottsPotential ctors + inference(n, with_map)
@@ -1797,7 +1852,7 @@ int lccrf_get_lattice(lccrf_handle h, int kernel, int32_t *offset_out, float *ba
 // pinned whose device address is the pointer itself -- anything else (plain pageable host memory above all) would fault the card
 // with XNACK off, so it is refused here, before anything is enqueued.  When the runtime knows the allocation's extent, the `bytes`
 // the call will touch must lie inside it.
-static int check_device_array(const lccrf_crf *h, const void *p, size_t bytes, const char *what)
+static int check_device_array(const Engine &eng, const void *p, size_t bytes, const char *what)
 {
     if (!bytes) return LCCRF_OK;
     if (!p) return fail(LCCRF_E_INVALID, "%s is NULL", what);
@@ -1807,8 +1862,8 @@ static int check_device_array(const lccrf_crf *h, const void *p, size_t bytes, c
     if (e != hipSuccess || a.isManaged)
         return fail(LCCRF_E_INVALID, "%s (%p) is neither device memory nor pinned host memory", what, p);
     if (a.type == hipMemoryTypeDevice) {
-        if (a.device != h->eng.device)
-            return fail(LCCRF_E_INVALID, "%s (%p) is memory of device %d, the handle's is device %d", what, p, a.device, h->eng.device);
+        if (a.device != eng.device)
+            return fail(LCCRF_E_INVALID, "%s (%p) is memory of device %d, the handle's is device %d", what, p, a.device, eng.device);
     } else if (a.type == hipMemoryTypeHost) {
         if (a.devicePointer != p)
             return fail(LCCRF_E_INVALID, "%s (%p) is pinned host memory whose device address differs (%p)", what, p, a.devicePointer);
@@ -1826,6 +1881,10 @@ static int check_device_array(const lccrf_crf *h, const void *p, size_t bytes, c
         (void)hipGetLastError();
     }
     return LCCRF_OK;
+}
+static int check_device_array(const lccrf_crf *h, const void *p, size_t bytes, const char *what)
+{
+    return check_device_array(h->eng, p, bytes, what);
 }
 
 // the caller's features [N][d] (copy) or an image (position / RGB) -> a new term's own feature buffer, on the handle's stream
@@ -2015,42 +2074,9 @@ int lccrf_inference_backward(lccrf_handle h, int n_iterations, float relax, cons
     if (!e.unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
     { int rl = e.resolve_late(); if (rl) return rl; }
     // the area first: a handle that cannot have it is left as it was
-    const size_t need = backward_bytes(h->N, e.L, K, T);
-    if (need > e.bwd_area_bytes) {
-        e.free_backward_area();
-        void *p = nullptr;
-        const hipError_t ea = hipMalloc(&p, need);
-        if (ea != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ea == hipErrorOutOfMemory ? LCCRF_E_NOMEM : LCCRF_E_HIP, "hipMalloc(%zu bytes) for the backward area: %s", need,
-                        hipGetErrorString(ea));
-        }
-        e.bwd_area = static_cast<unsigned char *>(p);
-        e.bwd_area_bytes = need;
-        HIP_TRY(hipMemsetAsync(p, 0, need, e.stream));   // (the phantom rows stay zero: engine.h, BackwardArea)
-    }
-    BackwardArea ar;
     const size_t ns = backward_stride(h->N, e.L);
-    ar.hist = reinterpret_cast<float *>(e.bwd_area);
-    ar.phi = ar.hist + (size_t)T * ns;
-    ar.G = ar.phi + (size_t)K * ns;
-    ar.partial = ar.G + ns;
-    // replay: inference(T, 0, relax) on the step path (Engine::step), Q_0 .. Q_{T-1} kept
-    int rc = e.start();                                   // (ensure_plain: frames in locality mode are re-built the plain way once)
-    if (!rc) rc = e.learn_sizes();
-    if (rc) return rc;
-    for (int t = 0; t < T; ++t) {
-        if (nl) HIP_TRY(hipMemcpyAsync(ar.hist + (size_t)t * ns, e.crf.Q, nl * sizeof(float), hipMemcpyDeviceToDevice, e.stream));
-        if ((rc = e.step(relax))) return rc;
-    }
-    if (nl) HIP_TRY(hipMemcpyAsync(ar.G, d_grad_prob, nl * sizeof(float), hipMemcpyDeviceToDevice, e.stream));
-    if (!nl) {                                            // nothing to differentiate: dL/dw = 0
-        if (d_grad_weights && K) HIP_TRY(hipMemsetAsync(d_grad_weights, 0, (size_t)K * sizeof(float), e.stream));
-        return LCCRF_OK;
-    }
-    launch_backward_sweep(e.crf, e.kdevs.data(), e.maxV.data(), h->N, T, relax, ar, d_grad_unary, d_grad_weights, e.stream);
-    HIP_TRY(hipGetLastError());
-    return LCCRF_OK;
+    { int ra = e.ensure_backward_area(backward_bytes(ns, 1, h->N, e.L, K, T)); if (ra) return ra; }   // (the phantom rows stay zero: engine.h)
+    return e.backward(ns, nl, h->N, T, relax, d_grad_prob, d_grad_unary, d_grad_weights);
 }
 
 // --------------------------------------------------------------------------------------
@@ -2567,6 +2593,57 @@ int lccrf_batch_get_fallback_frames(lccrf_batch_handle b, int *n_frames)
     { int rl = b->eng.resolve_late(); if (rl) return rl; }
     *n_frames = b->eng.fallback_frames;
     return LCCRF_OK;
+}
+
+// --------------------------------------------------------------------------------------
+// section 2c: gradients of a batch's inference
+
+int lccrf_batch_set_pairwise_weight(lccrf_batch_handle b, int kernel, float w)
+{
+    CHECK_H(b);
+    CHECK_K(b, kernel);
+    Engine &e = b->eng;
+    { int rl = e.resolve_late(); if (rl) return rl; }   // (a pending one-launch run may still re-run frames with the old weight)
+    e.kernels[kernel].dev.w = w;
+    e.sync_views();
+    e.invalidate_lean_prep();                             // whatever was prepared for the old weights is rewritten
+    return LCCRF_OK;
+}
+
+int lccrf_batch_set_unary_device(lccrf_batch_handle b, const float *d_unary)
+{
+    CHECK_H(b);
+    Engine &e = b->eng;
+    const size_t n = (size_t)e.F * e.maxN * e.L;
+    { int rc = check_device_array(e, d_unary, n * sizeof(float), "d_unary"); if (rc) return rc; }
+    if (!b->inputs_set) return fail(LCCRF_E_STATE, "inputs not set");
+    { int rl = e.resolve_late(); if (rl) return rl; }
+    if (n) HIP_TRY(hipMemcpyAsync(e.unary_own, d_unary, n * sizeof(float), hipMemcpyDefault, e.stream));
+    e.bind_unary(e.unary_own);                            // (drops label-derived and permuted unary state; lattices and records stay)
+    return LCCRF_OK;
+}
+
+int lccrf_batch_inference_backward(lccrf_batch_handle b, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
+                                   float *d_grad_weights, void *stream)
+{
+    CHECK_H(b);
+    Engine &e = b->eng;
+    if (n_iterations < 0) return fail(LCCRF_E_INVALID, "n_iterations < 0");
+    if (!std::isfinite(relax)) return fail(LCCRF_E_INVALID, "relax must be finite");
+    const int K = (int)e.kernels.size(), T = n_iterations;
+    const size_t nl = (size_t)e.F * e.maxN * e.L;
+    { int rc = check_device_array(e, d_grad_prob, nl * sizeof(float), "d_grad_prob"); if (rc) return rc; }
+    { int rc = check_device_array(e, d_grad_unary, nl * sizeof(float), "d_grad_unary"); if (rc) return rc; }
+    if (d_grad_weights) { int rc = check_device_array(e, d_grad_weights, (size_t)e.F * K * sizeof(float), "d_grad_weights"); if (rc) return rc; }
+    // (started: lccrf_batch_run on the one-launch kernel leaves no lattice in HBM -- they are built here)
+    if (!b->inputs_set || !(e.built || e.started)) return fail(LCCRF_E_STATE, "lccrf_batch_build or lccrf_batch_run has not run for these inputs");
+    return timed_batch_call(e, stream, e.ev[2], e.ev[3], e.timed_inf, [&] {
+        int rc = e.resolve_late();
+        if (rc) return rc;
+        if ((rc = e.ensure_backward_area(backward_bytes(nl, e.F, e.maxN, e.L, K, T)))) return rc;
+        if ((rc = e.ensure_plain_batch())) return rc;
+        return e.backward(nl, nl, e.maxN, T, relax, d_grad_prob, d_grad_unary, d_grad_weights);
+    });
 }
 
 void lccrf_default_params(lccrf_crf_params *p)       // Examples/RGB-D/TUM3.yaml:78-101

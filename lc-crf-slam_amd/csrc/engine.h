@@ -197,22 +197,25 @@ void launch_stage_features(float *dst, const void *src, int n, int d, int mode, 
 // out[f] = clamp(in[f], 0, maxN); *bad (pinned host memory) is set to 1 if anything had to be clamped
 void launch_validate_npoints(const int *in, int *out, int F, int maxN, int *bad, hipStream_t s);
 
-// ---- mean-field backward (csrc/meanfield_backward.hip; include/lccrf.h section 1c) ---------------------------------
-// The handle-owned area of one lccrf_inference_backward: Q_0 .. Q_{T-1} of the replay, one [N][L] array per term, dL/dQ_t and the
-// per-workgroup partials of the weight gradient -- backward_bytes() in all, zeroed when allocated.  The [N][L] arrays are
-// backward_stride() floats apart: N rounded up to a multiple of 4 rows, the phantom points' rows (quirk Q1) staying zero -- a splat
-// over a lattice whose rows list them reads 0 there, as it reads the engine's own Q.
+// ---- mean-field backward (csrc/meanfield_backward.hip; include/lccrf.h sections 1c and 2c) ---------------------------------
+// The area of one lccrf_inference_backward / lccrf_batch_inference_backward, owned by the engine: Q_0 .. Q_{T-1} of the replay, one
+// [F][.][L] array per term, dL/dQ_t and the per-workgroup partials of the weight gradient -- backward_bytes() in all, zeroed when
+// allocated.  Every array is `slice` floats: for a handle backward_stride(N, L) (N rounded up to a multiple of 4 rows, the phantom
+// points' rows of quirk Q1 staying zero), for a batch F * maxN * L (the engine's own [F][maxN][L] layout).  The sweep reads no row at
+// or beyond a frame's n_points (meanfield_backward.hip).
 struct BackwardArea {
-    float *hist;          // [T][N][L]
-    float *phi;           // [K][N][L]
-    float *G;             // [N][L]
-    float *partial;       // [max(T,1)][K][backward_blocks(N, L)]
+    size_t slice;         // floats per array
+    float *hist;          // [T][slice]
+    float *phi;           // [K][slice]
+    float *G;             // [slice]
+    float *partial;       // [max(T,1)][K][F][backward_blocks(rows, L)]
 };
 int backward_blocks(int n, int L);
 size_t backward_stride(int n, int L);
-size_t backward_bytes(int n, int L, int K, int T);
-// the reverse sweep (the replay has filled ar.hist and ar.G = dL/dQ_T); grad_weights may be null
-void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int n, int T, float relax, const BackwardArea &ar,
+size_t backward_bytes(size_t slice, int F, int rows, int L, int K, int T);
+// the reverse sweep over the F = c.F frames of up to `rows` points each (the replay has filled ar.hist and ar.G = dL/dQ_T);
+// grad_unary [F][c.maxN][L] (rows [n_points[f], rows) written 0), grad_weights [F][K] or null
+void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int rows, int T, float relax, const BackwardArea &ar,
                            float *grad_unary, float *grad_weights, hipStream_t s);
 
 // ---- fused build (SLAM sizes; one workgroup per (frame, kernel), hash table in LDS) ------

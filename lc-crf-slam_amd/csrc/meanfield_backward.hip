@@ -1,14 +1,22 @@
 // meanfield_backward.hip -- reverse-mode gradients of DenseCRF::inference (densecrf_base.h:65-91): include/lccrf.h section 1c.
 //
-// The C-ABI layer (api.hip: lccrf_inference_backward) replays the forward on the step path, keeping Q_0 .. Q_{T-1}, and then runs
-// the sweep below on the handle's stream.  Per iteration t = T .. 1:
+// The C-ABI layer (api.hip: lccrf_inference_backward, lccrf_batch_inference_backward) replays the forward on the step path, keeping
+// Q_0 .. Q_{T-1}, and then runs the sweep below on the call's stream, for every frame at once (the frame is blockIdx.y; a handle is a
+// batch of one).  Per iteration t = T .. 1:
 //   Phi_k(Q_{t-1})                          launch_filter, forward blur order (the streaming engine's splat / blur / slice)
 //   x_t, P_t, gamma_t, dL/dU, n_k gamma_t   k_softmax_bwd (+ the per-workgroup partials of the K weight-gradient dot products)
 //   Phi_k^T(n_k gamma_t)                    launch_filter, blur passes in REVERSE axis order (each pass is symmetric, their product
 //                                           is not: the transpose of B_d .. B_0 is B_0 .. B_d)
 //   G_{t-1} = (1 - r) G_t + sum_k w_k .     k_bwd_combine
 // then the softmax backward of Q_0 = softmax(-U) and the fixed-order reduction of the partials (k_bwd_reduce).  No float atomics:
-// every sum is formed in an order fixed by N and L alone, so the results are the same bits from run to run.
+// every sum is formed in an order fixed by N and L alone, so the results are the same bits from run to run -- and a frame of a
+// batch gets the bits a handle of its n_points[f] points gets (the weight gradient's partials included: backward_blocks(n_points[f])
+// of them per iteration, reduced in the handle's order).
+//
+// Rows at or beyond n_points[f] (the phantom points of quirk Q1 among them) are never read: every lattice build lists real points
+// only in its splat rows (k_csr_count / k_eoffsets in stream_engine.hip, E = N (d+1) in build_small.hip), the slice writes rows
+// i < n_points[f] only, and the kernels below stop at n_points[f].  A batch rebound with fewer points than an earlier call leaves
+// stale rows in its area; nothing reads them.
 #include "engine.h"
 #include "device_math.h"
 
@@ -20,15 +28,18 @@ constexpr int kBwdMaxK = LCCRF_MAX_KERNELS;
 
 struct BwdWeights { float w[kBwdMaxK]; };
 struct BwdArgs {
-    const int *n_points;
+    const int *n_points;         // [F]
     int L, K, first;             // first: the sweep's first iteration writes dL/dU, the others accumulate into it
+    int rows;                    // rows per frame of gU: the first iteration writes rows [n_points[f], rows) as 0
+    int nstride;                 // points between frames of norm (c.maxN)
     float relax;
-    const float *unary;          // [N][L]
-    float *phi;                  // [K][nl]: Phi_k(Q_{t-1}) in, n_k * gamma_t out
-    size_t nl;                   // backward_stride(N, L)
-    const float *G;              // [N][L] dL/dQ_t
-    float *gU;                   // [N][L] dL/dU
-    float *partial;              // [K][gridDim.x] or null
+    size_t fs;                   // floats between frames of unary, phi, G and gU (c.maxN * L)
+    size_t slice;                // floats between the terms of phi (BackwardArea::slice)
+    const float *unary;          // [F][maxN][L]
+    float *phi;                  // [K][slice]: Phi_k(Q_{t-1}) in, n_k * gamma_t out
+    const float *G;              // [F][maxN][L] dL/dQ_t
+    float *gU;                   // [F][maxN][L] dL/dU
+    float *partial;              // [K][F][gridDim.x] or null
     const float *norm[kBwdMaxK];
     float w[kBwdMaxK];
 };
@@ -55,20 +66,27 @@ __device__ __forceinline__ float row_sum_ordered(const float (&v)[4], int L, int
 //   P   = softmax(x)                              fast_exp as expAndNormalize (densecrf3d.h:70-98) forms it
 //   gam = r * P * (G - <G, P>)                    (in a form that keeps the bits of saturated rows, below)
 //   gU  = -gam (first) or gU - gam
-//   phi_k <- n_k * gam (in place: the transposed filter's input), partial[k][block] = sum over the block of n_k * gam * Phi_k
+//   phi_k <- n_k * gam (in place: the transposed filter's input), partial[k][f][block] = sum over the block of n_k * gam * Phi_k
 // K = 0: x = -U (the start, densecrf_base.h:78-80, or a CRF without terms).
 template <int G>
 __global__ void __launch_bounds__(kBwdBlock) k_softmax_bwd(BwdArgs a)
 {
-    const int N = *a.n_points, L = a.L, K = a.K;
+    const int f = blockIdx.y;
+    const int N = a.n_points[f], L = a.L, K = a.K;
     const int lane = threadIdx.x & 63;
     const int sub = lane % G, first = lane - sub;
     const int i = blockIdx.x * (kBwdBlock / G) + (int)threadIdx.x / G;
     const bool live = i < N;
     const int l0 = sub * 4;
+    if (a.first && !live && i < a.rows) {                 // rows beyond the frame's points: dL/dU = 0
+        const size_t z = f * a.fs + (size_t)i * L + l0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (l0 + u < L) a.gU[z + u] = 0.0f;
+    }
     bool has[4];
     float x[4], g[4];
-    const size_t q = (size_t)(live ? i : 0) * L + l0;
+    const size_t q = f * a.fs + (size_t)(live ? i : 0) * L + l0;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         has[u] = live && l0 + u < L;
@@ -83,11 +101,11 @@ __global__ void __launch_bounds__(kBwdBlock) k_softmax_bwd(BwdArgs a)
 #pragma unroll
         for (int u = 0; u < 4; ++u) ph[k][u] = 0.0f;
         if (k < K) {
-            nk[k] = live ? a.norm[k][i] : 0.0f;
+            nk[k] = live ? a.norm[k][(size_t)f * a.nstride + i] : 0.0f;
             const float wn = a.w[k] * nk[k];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                ph[k][u] = has[u] ? a.phi[k * a.nl + q + u] : 0.0f;
+                ph[k][u] = has[u] ? a.phi[k * a.slice + q + u] : 0.0f;
                 x[u] = x[u] + wn * ph[k][u];
             }
         }
@@ -135,7 +153,7 @@ __global__ void __launch_bounds__(kBwdBlock) k_softmax_bwd(BwdArgs a)
             if (k < K) {
                 const float gn = nk[k] * gam;
                 wsum[k] += gn * ph[k][u];
-                a.phi[k * a.nl + q + u] = gn;
+                a.phi[k * a.slice + q + u] = gn;
             }
     }
     if (!a.partial) return;
@@ -153,32 +171,37 @@ __global__ void __launch_bounds__(kBwdBlock) k_softmax_bwd(BwdArgs a)
     if ((int)threadIdx.x < K) {
         float s = 0.0f;
         for (int w = 0; w < kBwdBlock / 64; ++w) s += red[threadIdx.x][w];
-        a.partial[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = s;
+        a.partial[((size_t)threadIdx.x * gridDim.y + f) * gridDim.x + blockIdx.x] = s;
     }
 }
 
-// G = keep * G + sum_k w_k * buf_k, element by element (keep = 1 - relax)
+// G = keep * G + sum_k w_k * buf_k, element by element (keep = 1 - relax); frame blockIdx.y
 __global__ void __launch_bounds__(kBwdBlock) k_bwd_combine(const int *__restrict__ n_points, int L, int K, const float *__restrict__ buf,
-                                                         size_t nl, BwdWeights wk, float keep, float *__restrict__ G)
+                                                         size_t slice, size_t fs, BwdWeights wk, float keep, float *__restrict__ G)
 {
+    const int f = blockIdx.y;
     const long idx = (long)blockIdx.x * kBwdBlock + threadIdx.x;
-    if (idx >= (long)*n_points * L) return;
-    float acc = keep * G[idx];
-    for (int k = 0; k < K; ++k) acc = acc + wk.w[k] * buf[k * nl + idx];
-    G[idx] = acc;
+    if (idx >= (long)n_points[f] * L) return;
+    const size_t o = f * fs + idx;
+    float acc = keep * G[o];
+    for (int k = 0; k < K; ++k) acc = acc + wk.w[k] * buf[k * slice + o];
+    G[o] = acc;
 }
 
-// out[k] = sum over the iterations and workgroups of partial[t][k][b]: one workgroup per term, a strided walk in a fixed order and a
-// fixed tree in LDS (store and sum: no atomics, the same bits every run)
-__global__ void __launch_bounds__(kBwdBlock) k_bwd_reduce(const float *__restrict__ partial, int K, int T, int nblk, float *__restrict__ out)
+// out[f][k] = sum over the iterations and the frame's workgroups of partial[t][k][f][b]: one workgroup per (term, frame), a strided
+// walk over the T x backward_blocks(n_points[f]) partials of the frame in a fixed order and a fixed tree in LDS (store and sum: no
+// atomics, the same bits every run, and those of a handle of n_points[f] points).  bstride: the partials' row (the sweep's grid).
+__global__ void __launch_bounds__(kBwdBlock) k_bwd_reduce(const float *__restrict__ partial, const int *__restrict__ n_points, int K,
+                                                        int T, int rows_per_block, int bstride, float *__restrict__ out)
 {
     __shared__ float s[kBwdBlock];
-    const int k = blockIdx.x;
+    const int k = blockIdx.x, f = blockIdx.y, F = gridDim.y;
+    const int nblk = max((n_points[f] + rows_per_block - 1) / rows_per_block, 1);
     const long n = (long)T * nblk;
     float acc = 0.0f;
     for (long idx = threadIdx.x; idx < n; idx += kBwdBlock) {
         const long t = idx / nblk, b = idx - t * nblk;
-        acc += partial[(t * K + k) * nblk + b];
+        acc += partial[((t * K + k) * F + f) * bstride + b];
     }
     s[threadIdx.x] = acc;
     __syncthreads();
@@ -186,13 +209,13 @@ __global__ void __launch_bounds__(kBwdBlock) k_bwd_reduce(const float *__restric
         if ((int)threadIdx.x < m) s[threadIdx.x] += s[threadIdx.x + m];
         __syncthreads();
     }
-    if (threadIdx.x == 0) out[k] = s[0];
+    if (threadIdx.x == 0) out[(size_t)f * K + k] = s[0];
 }
 
-void launch_softmax_bwd(const BwdArgs &a, int n, hipStream_t s)
+void launch_softmax_bwd(const BwdArgs &a, int F, hipStream_t s)
 {
     const int G = bwd_lanes(a.L);
-    const dim3 grid((unsigned)std::max(backward_blocks(n, a.L), 1));
+    const dim3 grid((unsigned)std::max(backward_blocks(a.rows, a.L), 1), (unsigned)F);
     switch (G) {
     case 1: k_softmax_bwd<1><<<grid, kBwdBlock, 0, s>>>(a); break;
     case 2: k_softmax_bwd<2><<<grid, kBwdBlock, 0, s>>>(a); break;
@@ -208,24 +231,26 @@ size_t backward_stride(int n, int L) { return (size_t)((n + 3) & ~3) * L; }
 
 int backward_blocks(int n, int L) { return (n + kBwdBlock / bwd_lanes(L) - 1) / (kBwdBlock / bwd_lanes(L)); }
 
-size_t backward_bytes(int n, int L, int K, int T)
+size_t backward_bytes(size_t slice, int F, int rows, int L, int K, int T)
 {
-    const size_t nl = backward_stride(n, L);
-    return sizeof(float) * (nl * ((size_t)T + K + 1) + (size_t)std::max(T, 1) * K * std::max(backward_blocks(n, L), 1));
+    return sizeof(float) * (slice * ((size_t)T + K + 1) + (size_t)std::max(T, 1) * K * F * std::max(backward_blocks(rows, L), 1));
 }
 
-void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int n, int T, float relax, const BackwardArea &ar,
+void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int rows, int T, float relax, const BackwardArea &ar,
                            float *grad_unary, float *grad_weights, hipStream_t s)
 {
-    const int K = c.K, L = c.L;
-    const size_t nl = backward_stride(n, L);
-    const int nblk = std::max(backward_blocks(n, L), 1);
+    const int K = c.K, L = c.L, F = c.F;
+    const size_t slice = ar.slice, fs = (size_t)c.maxN * L;
+    const int nblk = std::max(backward_blocks(rows, L), 1);
     BwdArgs a{};
     a.n_points = c.n_points;
     a.L = L;
+    a.rows = rows;
+    a.nstride = c.maxN;
+    a.fs = fs;
+    a.slice = slice;
     a.unary = c.unary;
     a.phi = ar.phi;
-    a.nl = nl;
     a.G = ar.G;
     a.gU = grad_unary;
     BwdWeights wk{};
@@ -233,25 +258,27 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
         a.norm[k] = kds[k].norm;
         a.w[k] = wk.w[k] = kds[k].w;
     }
-    const unsigned cgrid = (unsigned)std::max<size_t>((nl + kBwdBlock - 1) / kBwdBlock, 1);
+    const dim3 cgrid((unsigned)std::max<size_t>(((size_t)rows * L + kBwdBlock - 1) / kBwdBlock, 1), (unsigned)F);
     for (int t = T; t >= 1; --t) {
-        const float *qprev = ar.hist + (size_t)(t - 1) * nl;
-        for (int k = 0; k < K; ++k) launch_filter(kds[k], c, maxV[k], qprev, ar.phi + k * nl, 0, s);
+        const float *qprev = ar.hist + (size_t)(t - 1) * slice;
+        for (int k = 0; k < K; ++k) launch_filter(kds[k], c, maxV[k], qprev, ar.phi + k * slice, 0, s);
         a.K = K;
         a.relax = relax;
         a.first = t == T;
-        a.partial = K ? ar.partial + (size_t)(t - 1) * K * nblk : nullptr;
-        launch_softmax_bwd(a, n, s);
-        for (int k = 0; k < K; ++k) launch_filter(kds[k], c, maxV[k], ar.phi + k * nl, ar.phi + k * nl, 0, s, 1);
-        k_bwd_combine<<<cgrid, kBwdBlock, 0, s>>>(c.n_points, L, K, ar.phi, nl, wk, 1.0f - relax, ar.G);
+        a.partial = K ? ar.partial + (size_t)(t - 1) * K * F * nblk : nullptr;
+        launch_softmax_bwd(a, F, s);
+        for (int k = 0; k < K; ++k) launch_filter(kds[k], c, maxV[k], ar.phi + k * slice, ar.phi + k * slice, 0, s, 1);
+        k_bwd_combine<<<cgrid, kBwdBlock, 0, s>>>(c.n_points, L, K, ar.phi, slice, fs, wk, 1.0f - relax, ar.G);
     }
     // dL/dU -= P_0 (G_0 - <G_0, P_0>), P_0 = Q_0 = softmax(-U)
     a.K = 0;
     a.relax = 1.0f;
     a.first = T == 0;
     a.partial = nullptr;
-    launch_softmax_bwd(a, n, s);
-    if (grad_weights && K) k_bwd_reduce<<<K, kBwdBlock, 0, s>>>(ar.partial, K, T, nblk, grad_weights);
+    launch_softmax_bwd(a, F, s);
+    if (grad_weights && K)
+        k_bwd_reduce<<<dim3((unsigned)K, (unsigned)F), kBwdBlock, 0, s>>>(ar.partial, c.n_points, K, T, kBwdBlock / bwd_lanes(L), nblk,
+                                                                       grad_weights);
 }
 
 }  // namespace lccrf
