@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- CRF mean-field iterations/s on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--workload c2|c1|c3|c4|c5] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--workload c2|c1|c3|c4|c5] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch: DenseCRF::inference(n_iter, with_map)
 (densecrf_base.h:65-73: startInference + n_iter x stepInference + buildMap) for F independent
@@ -15,12 +15,17 @@ the timed region.
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (child
 processes under torch.distributed.run, started before this process touches torch or the GPU).
 
-Prints ONE JSON line on rank 0.  Besides the contract's keys it carries
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints that line:
+the contract's keys and the configuration they were measured on.  With --full the same run goes on to everything else
+the benchmark measures and checks, and the line also carries
   roofline          the dominant kernel against the roof that actually binds it (LDS for the
                     one-workgroup-per-frame engine, HBM for the streaming engine), frac <= 1
-  c5                the HBM-roofline configuration (100k points, 6-D kernel) timed in the same run
+  label_match_vs_cpu_reference, tiles_identical   the parity gate against the CPU checker
+  end_to_end        one launch per frame (lattice builds + inference), and host to host
+  c1 c3 c4 n500 c5  the other configurations, each timed in the same run (--no-extras leaves them out)
   single_frame_latency_us   the plug-in surface as the tracker uses it: one frame, host to host
-  cpu_baseline      the reference's own CPU path on this box's cores (1 pinned core, and all cores)
+  cpu_baseline      the reference's own CPU path on this box's cores (1 pinned core, and all cores; --no-cpu-baseline)
+  multi_gpu         N > 1: per-rank times and the label gather's own cost
 """
 import argparse
 import importlib
@@ -51,7 +56,7 @@ WORKLOADS = {
     # not a BASELINE.json config: the size live SLAM mostly sees (N = matched, observed map points, "typically hundreds")
     "n500": (500, 5, None, "N500: 500 keypoints (live-SLAM-typical), 5 iters, two 2-D kernels (TUM3.yaml), L=2"),
 }
-SUB_FRAMES = {"c1": 16384, "c3": 8192, "c4": 8192, "n500": 32768}    # frames in flight of the sub-records of the default line
+SUB_FRAMES = {"c1": 16384, "c3": 8192, "c4": 8192, "n500": 32768}    # frames in flight of the sub-records of the --full line
 
 
 def algorithmic_bytes_per_iter(N, L, dims, Vs):
@@ -95,6 +100,7 @@ def fused_lds_model(N, dims, Vs, chain0, lean=False):
 # Output discipline: the driver parses the LAST stdout line and captures a bounded tail, so that line is compact
 # (< 4 KB, no note strings).  Everything else -- the sub-workload records, the latency records, the notes -- is printed BEFORE it,
 # one `{"record": name, ...}` line each, and the complete nested record goes to a file (`--full-json`, default bench_full.json).
+# All of that is --full's; a plain run prints the compact line alone.
 # ---------------------------------------------------------------------------------------------
 COMPACT_LIMIT = 4096
 
@@ -128,9 +134,10 @@ def compact_line(full):
     cfg = full.get("config") or {}
     line["config"] = {k: _r(cfg.get(k)) for k in ("workload", "frames_in_flight_per_gpu", "handles", "distinct_frames", "n_points", "n_iters",
                                                   "n_labels", "kernel_dims", "mean_lattice_vertices", "engine") if k in cfg}
-    line["roofline"] = {k: _r(roof.get(k)) for k in ("bound", "achieved", "peak", "unit", "frac", "launch_ms", "traffic",
-                                                     "hbm_counter_frac", "frames_per_launch", "lanes_per_frame", "frames_per_cu",
-                                                     "algorithmic_hbm_bytes_per_launch", "algorithmic_bytes_per_launch") if k in roof}
+    if roof:                                                     # (a plain run has none: bench.py --full)
+        line["roofline"] = {k: _r(roof.get(k)) for k in ("bound", "achieved", "peak", "unit", "frac", "launch_ms", "traffic",
+                                                         "hbm_counter_frac", "frames_per_launch", "lanes_per_frame", "frames_per_cu",
+                                                         "algorithmic_hbm_bytes_per_launch", "algorithmic_bytes_per_launch") if k in roof}
     if _pick(roof, "valu_issue", "frac") is not None:
         line["roofline"]["valu_issue_frac"] = g("roofline", "valu_issue", "frac")
     cb = full.get("cpu_baseline")
@@ -510,7 +517,7 @@ def cpp_caller_latency(pbs, reps):
 
 def slam_subrecord(pkg, wl, torch, dev, name, steps=10, warmup=3, distinct=32, handles=1):
     """One more SLAM-shaped configuration, timed exactly like the headline (lccrf_batch_inference over F frames resident
-    in HBM, wall clock over `steps` back-to-back batches, HIP events for the launch) -- the default line's C1 / C3 / C4 /
+    in HBM, wall clock over `steps` back-to-back batches, HIP events for the launch) -- the --full line's C1 / C3 / C4 /
     N500 sub-records, so that every configuration of BASELINE.json is driver-timed."""
     import numpy as np
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -1148,20 +1155,23 @@ def main():
     ap.add_argument("--frames", type=int, default=0, help="frames in flight per GPU (0 = workload default)")
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
     ap.add_argument("--engine", type=int, default=0, help="0 auto, 1 streaming, 2 fused")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-check", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the c5 and single-frame-latency records")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything else the benchmark measures and checks: kernel timings and roofline, the "
+                         "parity gate, the end-to-end and multi-GPU records, the other configurations and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-check", action="store_true", help="--full: skip the parity gate against the CPU checker")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the other configurations and the latency records")
     ap.add_argument("--serial-gather", action="store_true",
                     help="N > 1: wait for each step's label gather before the next launch instead of overlapping them")
     ap.add_argument("--distinct", type=int, default=64, help="distinct synthetic frames tiled into the batch")
     ap.add_argument("--rehearse-cpu", action="store_true", help="launcher test: gloo, no GPU, no compute, no metric")
     ap.add_argument("--host-to-host", action="store_true", help="only the pipelined host-to-host record (end_to_end.host_to_host)")
     ap.add_argument("--full-json", default=os.path.join(ROOT, "bench_full.json"),
-                    help="where the complete nested record goes (the LAST stdout line is the compact one the driver parses)")
+                    help="--full: where the complete nested record goes (the LAST stdout line is the compact one the driver parses)")
     ap.add_argument("--handles", type=int, default=0,
-                    help="batch handles (each on its own stream) that share the frames in flight (default 1; the default line reports the two-handle schedule as `two_handles`)")
+                    help="batch handles (each on its own stream) that share the frames in flight (default 1; the --full line reports the two-handle schedule as `two_handles`)")
     ap.add_argument("--lite", action="store_true",
-                    help="counter-collection runs (rocprofv3 --pmc serialises every dispatch): one event-timed launch instead of "
+                    help="--full, counter-collection runs (rocprofv3 --pmc serialises every dispatch): one event-timed launch instead of "
                          "five, two one-launch batches instead of many -- the timed region itself is unchanged")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (Q and labels; rank 0's frames) to DIR/*.npy")
@@ -1291,7 +1301,7 @@ def main():
                     ln.gather.push()
 
     # the timed region records no HIP events between its launches (LCCRF_OPT_EVENT_TIMING = 0: what a replay loop that does not read
-    # per-batch timings sets); the kernel's own duration is event-timed afterwards, on the same stream
+    # per-batch timings sets); with --full the kernel's own duration is event-timed afterwards, on the same stream
     for ln in lanes:
         ln.b.set_option(pkg.BatchCRF.OPT_EVENT_TIMING, 0)
     for _ in range(args.warmup):                    # (RCCL sets its rings up on first use)
@@ -1304,11 +1314,56 @@ def main():
     t1 = time.perf_counter()
     if args.dump_outputs and rank == 0:             # before anything else launches on these handles
         dump_outputs(args.dump_outputs, [ln.b for ln in lanes])
+    dt = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)
+    words = lanes[0].bits_view.shape[1]
+    # the fused engine's prepared launch records (include/lccrf.h: lccrf_batch_last_prepare): written once behind the build, by the
+    # second inference on its lattices (inside the warm-up here) -- part of the lattice construction, reported beside build_ms
+    prepare_ms = sum(ln.b.last_prepare()[0] for ln in lanes)
+    prepare_runs = sum(ln.b.last_prepare()[1] for ln in lanes)
+
+    def headline(dt):
+        """The record of the timed steps: the contract's keys and the configuration they ran."""
+        out = {
+            "metric": "CRF mean-field iters/sec",
+            "value": float(F) * n_iter * args.steps * world / dt,
+            "unit": "iters/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": desc, "frames_in_flight_per_gpu": F, "handles": H, "distinct_frames": distinct, "n_points": N,
+                       "n_iters": n_iter, "n_labels": L, "kernel_dims": dims, "mean_lattice_vertices": Vs,
+                       "engine": {1: "streaming", 2: "fused"}.get(engine, str(engine)),
+                       "sharding": "frames over ranks, no data-path collective; one RCCL all_gather of the bit-packed "
+                                   "labels per handle and step (%d bytes per rank and step), %s" % (F * words * 8, "serial" if args.serial_gather else "overlapped with the next step's launch (double-buffered)")},
+            "build_ms_per_batch": build_ms,
+            "prepare_ms_per_batch": prepare_ms,      # once per build: the launch records every later inference on these lattices starts from
+            "prepare_runs": prepare_runs,
+        }
+        # a scaling curve needs the 1/2/4/8-GPU lines of one node side by side: this line alone never is one
+        out["scaling_measured"] = False
+        props = torch.cuda.get_device_properties(dev)        # which box a number comes from (profiles carry the same string)
+        out["device"] = "%s pci %04x:%02x:%02x uuid %s" % (props.name, getattr(props, "pci_domain_id", 0), getattr(props, "pci_bus_id", 0),
+                                                          getattr(props, "pci_device_id", 0), str(getattr(props, "uuid", ""))[:13])
+        return out
+
+    if not args.full:                               # a plain run: the line needs nothing more than the timed steps
+        if world > 1:
+            dist.all_reduce(dt, op=dist.ReduceOp.MAX)   # (the value uses the slowest rank)
+        if rank == 0:
+            emit(headline(float(dt.item())))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     for ln in lanes:
         ln.b.set_option(pkg.BatchCRF.OPT_EVENT_TIMING, 1)
-    dt = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)
     multi = None
-    words = lanes[0].bits_view.shape[1]
     if world > 1:
         # what every rank measured (the value uses the slowest), what the collective library itself spans, and the label
         # gather's own cost: the same steps once more with gather-then-launch instead of the overlapped form
@@ -1359,10 +1414,6 @@ def main():
         kernel_ms.append(b.last_timing()["inference_ms"])
     inf_ms = float(np.median(kernel_ms))
     inf_shape = b.fused_shape()            # (lanes per frame, frames per CU) of the inference kernel just timed
-    # the fused engine's prepared launch records (include/lccrf.h: lccrf_batch_last_prepare): written once behind the build, by the
-    # second inference on its lattices (inside the warm-up here) -- part of the lattice construction, reported beside build_ms
-    prepare_ms = sum(ln.b.last_prepare()[0] for ln in lanes)
-    prepare_runs = sum(ln.b.last_prepare()[1] for ln in lanes)
 
     # end to end per frame = PottsPotential ctors + inference, as the reference pays per frame: ONE launch per frame
     run_ms = None
@@ -1401,8 +1452,6 @@ def main():
             tiles_ok = tiles_ok and all(np.array_equal(Q[ln.lo + idx[ln.lo:ln.hi].index(idx[0])].view(np.int32), Q[0].view(np.int32)) for ln in lanes if idx[0] in idx[ln.lo:ln.hi])
 
     if rank == 0:
-        total_iters = float(F) * n_iter * args.steps * world
-        value = total_iters / dt
         bytes_iter = algorithmic_bytes_per_iter(N, L, dims, Vs)
         alg_launch = bytes_iter * n_iter * Fh            # (per LAUNCH: one handle's frames)
         launch_s = inf_ms * 1e-3
@@ -1449,28 +1498,9 @@ def main():
                     "frac": achieved / HBM_PEAK_GBS, "traffic": None,
                     "kernel": "inference (start + %d mean-field iterations + map), HIP events" % n_iter,
                     "algorithmic_bytes_per_launch": alg_launch, "launch_ms": inf_ms}
-        out = {
-            "metric": "CRF mean-field iters/sec",
-            "value": value,
-            "unit": "iters/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": desc, "frames_in_flight_per_gpu": F, "handles": H, "distinct_frames": distinct, "n_points": N,
-                       "n_iters": n_iter, "n_labels": L, "kernel_dims": dims, "mean_lattice_vertices": Vs,
-                       "engine": {1: "streaming", 2: "fused"}.get(engine, str(engine)),
-                       "sharding": "frames over ranks, no data-path collective; one RCCL all_gather of the bit-packed "
-                                   "labels per handle and step (%d bytes per rank and step), %s" % (F * words * 8, "serial" if args.serial_gather else "overlapped with the next step's launch (double-buffered)")},
+        out = headline(dt)
+        out.update({
             "roofline": roof,
-            "build_ms_per_batch": build_ms,
-            "prepare_ms_per_batch": prepare_ms,      # once per build: the launch records every later inference on these lattices starts from
-            "prepare_runs": prepare_runs,
             "frames_per_s_end_to_end": (F * world / (run_ms * 1e-3)) if (run_ms and run_engine == 3) else F * world / ((build_ms + prepare_ms + inf_ms) * 1e-3),
             "end_to_end": {"one_launch_ms_per_batch": run_ms, "one_launch_engine": (run_engine if run_ms else None),
                            "fallback_frames": (run_fallback if run_ms else None),
@@ -1485,12 +1515,7 @@ def main():
             "max_abs_dQ_vs_cpu_reference": max_dq,
             "frames_checked": frames_checked,        # distinct frames compared with the CPU checker (all of them)
             "tiles_identical": tiles_ok,             # every one of the F slots equals its source frame bit for bit (Q and labels, on the device)
-        }
-        # a scaling curve needs the 1/2/4/8-GPU lines of one node side by side: this line alone never is one
-        out["scaling_measured"] = False
-        props = torch.cuda.get_device_properties(dev)        # which box a number comes from (profiles carry the same string)
-        out["device"] = "%s pci %04x:%02x:%02x uuid %s" % (props.name, getattr(props, "pci_domain_id", 0), getattr(props, "pci_bus_id", 0),
-                                                          getattr(props, "pci_device_id", 0), str(getattr(props, "uuid", ""))[:13])
+        })
         if gather_ok is not None:
             out["label_gather_ok"] = gather_ok
         if multi is not None:

@@ -26,7 +26,7 @@ for rep in 1 2; do
     if [ -n "$LATENCY" ]; then echo "== [$FL]"; timeout -k 10 900 bash scripts/gpu_latency_cpp.sh LD_LIBRARY_PATH=$(dirname $lib) || exit 1; continue; fi
     for w in ${WORKLOAD:-c2}; do
       extra=""; [ $w = c5 ] && extra="--frames ${FRAMES:-8} --steps 3 --warmup 1"
-      LCCRF_LIB=$lib timeout -k 10 300 python bench.py --workload $w $extra --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
+      LCCRF_LIB=$lib timeout -k 10 300 python bench.py --full --workload $w $extra --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 e2e=d.get('end_to_end',{}).get('one_launch_ms_per_batch')

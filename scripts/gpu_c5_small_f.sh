@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/${TAG:-c5f}; mkdir -p $O
 for F in ${FRAMES:-1 2 4}; do
-  env "$@" timeout 300 python bench.py --workload c5 --frames $F --steps 5 --warmup 2 --no-cpu-baseline --no-extras 2>$O/f$F.err | python3 -c "
+  env "$@" timeout 300 python bench.py --full --workload c5 --frames $F --steps 5 --warmup 2 --no-cpu-baseline --no-extras 2>$O/f$F.err | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

@@ -1,17 +1,17 @@
 #!/bin/bash
-# the round-end cycle on one box: every -m gpu test, smoke(), the default bench line exactly as the driver runs it
+# the round-end cycle on one box: every -m gpu test, smoke(), the bench line as the driver runs it, with --full (under $OUT_DIR/bench, default out/bench)
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out/bench
+O=${OUT_DIR:-out}/bench; mkdir -p $O
 [ -n "$SKIP_TESTS" ] || timeout 2400 python -m pytest tests -x -q -m gpu 2>&1 | tail -5
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full-json gpurun_out/bench/bench_full.json > gpurun_out/bench/bench_default.out 2> gpurun_out/bench/bench_default.err; echo "bench rc=$?"
-tail -n 1 gpurun_out/bench/bench_default.out > gpurun_out/bench/bench_line.json
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full --full-json $O/bench_full.json > $O/bench_default.out 2> $O/bench_default.err; echo "bench rc=$?"
+tail -n 1 $O/bench_default.out > $O/bench_line.json
 python3 - <<PY
 import json
-last=open("gpurun_out/bench/bench_default.out").read().strip().splitlines()[-1]
+last=open("$O/bench_default.out").read().strip().splitlines()[-1]
 print("compact line: %d bytes; stdout tail(8192) starts inside it: %s" % (len(last), len(last) > 8192))
 print(last)
-d=json.load(open("gpurun_out/bench/bench_full.json"))
+d=json.load(open("$O/bench_full.json"))
 r=d["roofline"]
 print("C2 value %.4g ms/step %.3f frac %.3f chain_floor_ms %.3f lds_floor_ms %.3f launch_ms %.3f match %s frames_checked %s tiles %s" % (d["value"], d["ms_per_step"], r["frac"], r["chain_floor_ms"], r["lds_floor_ms"], r["launch_ms"], d["label_match_vs_cpu_reference"], d["frames_checked"], d["tiles_identical"]))
 print("e2e frames/s %.4g" % d["frames_per_s_end_to_end"])

@@ -10,7 +10,7 @@ export LCCRF_LIB=$PWD/lc-crf-slam_amd/liblccrf_hip_instr.so
 [ -f "$LCCRF_LIB" ] || make -C lc-crf-slam_amd -j8 INSTRUMENT=1 >/dev/null || exit 1
 args_of() { if [ "$1" = c5 ]; then echo "--workload c5 --frames ${FRAMES:-8} --steps 5 --warmup 2"; else echo "--workload $1 ${FRAMES:+--frames $FRAMES}"; fi; }
 for rep in 1 2; do for w in ${WORKLOAD:-c5}; do for E in "$@"; do
-  env $E timeout 300 python bench.py $(args_of $w) --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
+  env $E timeout 300 python bench.py --full $(args_of $w) --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 e2e=d.get('end_to_end',{}).get('one_launch_ms_per_batch')
@@ -20,7 +20,7 @@ if [ -n "$TRACE" ]; then
   O=gpurun_out/${TAG:-envab}; mkdir -p $O; last="${@: -1}"; w=$(echo ${WORKLOAD:-c5} | cut -d' ' -f1)
   # (the program itself after `--`, never `env`: the profiler's preloaded library has initialised the GPU by then)
   for kv in $last; do export "$kv"; done
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python3 bench.py $(args_of $w) --no-cpu-baseline --no-extras --no-check > $O/bench.json 2> $O/err.log
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python3 bench.py --full $(args_of $w) --no-cpu-baseline --no-extras --no-check > $O/bench.json 2> $O/err.log
   python3 - <<PY
 import csv, glob
 for fn in glob.glob('$O/stats/**/run_kernel_stats.csv', recursive=True) + glob.glob('$O/stats/run_kernel_stats.csv'):

@@ -8,7 +8,7 @@
 cd "$GRAFT_REPO_ROOT" 2>/dev/null
 make -C lc-crf-slam_amd -j8 INSTRUMENT=1 EXTRA="$EXTRA" >/dev/null || exit 1
 export LCCRF_LIB=$PWD/lc-crf-slam_amd/liblccrf_hip_instr.so
-B="timeout 200 python bench.py --workload ${WORKLOAD:-c2} --steps 2 --warmup 1 --no-cpu-baseline --no-check --no-extras"
+B="timeout 200 python bench.py --full --workload ${WORKLOAD:-c2} --steps 2 --warmup 1 --no-cpu-baseline --no-check --no-extras"
 case "${KERNEL:-fused}" in
 fused) for lane in ${LANES:-0 200 960}; do echo "lane $lane"; LCCRF_FUSED_DBG=${DBG:-8} LCCRF_FUSED_TIMING_LANE=$lane LCCRF_FUSED_TIMING=${BLOCK:-1} $B 2>&1 | grep "fused timing" | tail -1; done ;;
 frame) for lane in ${LANES:-0 64 512 960}; do echo "lane $lane"; LCCRF_FRAME_TIMING_LANE=$lane LCCRF_FRAME_TIMING=${BLOCK:-1} $B 2>&1 | grep "frame timing" | tail -1; done ;;

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof/icache
 rm -rf $OUT; mkdir -p $OUT
 timeout 300 rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_IFETCH SQ_WAIT_INST_ANY SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY \
-  --kernel-trace --output-format csv -d $OUT/p1 -o run -- python3 bench.py --steps 2 --warmup 1 --lite --no-cpu-baseline --no-check --no-extras "$@" > /dev/null 2> $OUT/p1.err
+  --kernel-trace --output-format csv -d $OUT/p1 -o run -- python3 bench.py --full --steps 2 --warmup 1 --lite --no-cpu-baseline --no-check --no-extras "$@" > /dev/null 2> $OUT/p1.err
 python3 - <<'PY'
 import csv, collections, glob
 for fn in glob.glob("gpurun_out/prof/icache/p1/*counter_collection.csv"):

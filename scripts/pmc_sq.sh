@@ -5,9 +5,9 @@ cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof/sq
 rm -rf $OUT/p1 $OUT/p2; mkdir -p $OUT
 timeout 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE \
-  --kernel-trace --output-format csv -d $OUT/p1 -o run -- python3 bench.py --steps 2 --warmup 1 --lite --no-cpu-baseline --no-check --no-extras "$@" > /dev/null 2> $OUT/p1.err
+  --kernel-trace --output-format csv -d $OUT/p1 -o run -- python3 bench.py --full --steps 2 --warmup 1 --lite --no-cpu-baseline --no-check --no-extras "$@" > /dev/null 2> $OUT/p1.err
 timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_VMEM SQ_WAVES \
-  --kernel-trace --output-format csv -d $OUT/p2 -o run -- python3 bench.py --steps 2 --warmup 1 --lite --no-cpu-baseline --no-check --no-extras "$@" > /dev/null 2> $OUT/p2.err
+  --kernel-trace --output-format csv -d $OUT/p2 -o run -- python3 bench.py --full --steps 2 --warmup 1 --lite --no-cpu-baseline --no-check --no-extras "$@" > /dev/null 2> $OUT/p2.err
 python3 - <<'PY'
 import csv, collections, glob
 for p in ("p1","p2"):

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof/tcc
 rm -rf $OUT; mkdir -p $OUT
-run() { timeout 300 rocprofv3 --pmc $2 --kernel-trace --output-format csv -d $OUT/$1 -o run -- python3 bench.py --steps 2 --warmup 1 --lite --no-cpu-baseline --no-check --no-extras "${@:3}" > /dev/null 2> $OUT/$1.err; }
+run() { timeout 300 rocprofv3 --pmc $2 --kernel-trace --output-format csv -d $OUT/$1 -o run -- python3 bench.py --full --steps 2 --warmup 1 --lite --no-cpu-baseline --no-check --no-extras "${@:3}" > /dev/null 2> $OUT/$1.err; }
 run p1 "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_READ_sum" "$@"
 run p2 "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_DRAM_sum TCC_BUBBLE_sum" "$@"
 run p3 "TCC_EA0_RDREQ_LEVEL_sum TCC_EA0_RDREQ_DRAM_CREDIT_STALL_sum TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum" "$@"

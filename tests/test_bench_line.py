@@ -88,6 +88,20 @@ def test_compact_line_stays_small_with_long_numbers_and_multi_gpu():
     assert json.loads(text)["multi_gpu"]["ranks_in_collective"] == 8
 
 
+def test_plain_record_prints_the_compact_line_alone():
+    """A plain run (no --full) records the timed steps and their configuration only: the compact line is all it prints, with no
+    empty sections for what only --full measures."""
+    full = _full()
+    plain = {k: full[k] for k in CONTRACT[:-2] + ("build_ms_per_batch", "scaling_measured")}
+    buf = io.StringIO()
+    text = bench.emit(plain, None, buf)
+    assert buf.getvalue() == text + "\n"
+    line = json.loads(text)
+    assert set(line) == set(plain)
+    assert line["value"] == pytest.approx(full["value"], rel=1e-5)
+    assert line["ms_per_step"] == pytest.approx(full["ms_per_step"], rel=1e-5)
+
+
 def test_oversized_line_is_refused(monkeypatch):
     monkeypatch.setattr(bench, "COMPACT_LIMIT", 512)
     with pytest.raises(SystemExit):
@@ -158,3 +172,32 @@ def test_bench_dumps_what_its_last_timed_step_computed(tmp_path, po, wl):
         assert np.array_equal(M[f], o.map().astype(np.float32)), f
         assert np.array_equal(Q[f].view(np.int32), o.probability().view(np.int32)), f
         o.close()
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_full_adds_the_records(tmp_path):
+    """bench.py without --full prints the headline line alone and writes no full record; with --full the same command adds the
+    kernel timing and roofline, the parity gate and the end-to-end record, and writes the full record."""
+    import subprocess
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--frames", "256",
+           "--distinct", "4", "--full-json", str(tmp_path / "full.json")]
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-extras", "--no-cpu-baseline"])):
+        r = subprocess.run(cmd + extra, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        out = r.stdout.strip().splitlines()
+        lines[mode] = json.loads(out[-1])
+        records = [l for l in out[:-1] if l.startswith('{"record"')]
+        if mode == "plain":
+            assert not records and not (tmp_path / "full.json").exists()
+        else:
+            assert "roofline_detail" in [json.loads(l)["record"] for l in records]
+            assert json.load(open(tmp_path / "full.json"))["value"] == pytest.approx(lines[mode]["value"], rel=1e-5)
+    for line in lines.values():
+        for k in CONTRACT[:-2]:
+            assert k in line, k
+        assert line["steps"] == 2 and line["warmup"] == 1 and line["config"]["frames_in_flight_per_gpu"] == 256
+    assert not {"roofline", "label_match_vs_cpu_reference", "tiles_identical", "end_to_end", "cpu_baseline"} & set(lines["plain"])
+    full = lines["full"]
+    assert full["roofline"]["launch_ms"] > 0 and full["end_to_end"]["one_launch_ms_per_batch"] > 0
+    assert full["label_match_vs_cpu_reference"] == 1.0 and full["tiles_identical"] is True and full["frames_checked"] == 4
