@@ -380,6 +380,8 @@ class BatchCRF:
     def __init__(self, max_frames, max_points, n_labels, feat_dims, weights, device=0):
         self.F, self.maxN, self.L = int(max_frames), int(max_points), int(n_labels)
         self.dims = [int(d) for d in feat_dims]
+        if len(self.dims) > MAX_KERNELS:
+            raise LccrfError(-1, "%d pairwise kernels: at most %d" % (len(self.dims), MAX_KERNELS))
         d = BatchDesc()
         d.max_frames, d.max_points, d.n_labels, d.n_kernels = self.F, self.maxN, self.L, len(self.dims)
         for i, (fd, w) in enumerate(zip(self.dims, weights)):

@@ -1716,6 +1716,7 @@ int lccrf_lattice_filter(int device_id, const float *features, int n_points, int
 {
     if (n_points < 0) return fail(LCCRF_E_INVALID, "n_points < 0");
     if ((!features || !in || !out) && n_points) return fail(LCCRF_E_INVALID, "features / in / out is NULL");
+    if (d < 1 || d > LCCRF_MAX_DIMS) return fail(LCCRF_E_INVALID, "feature dims %d not in [1,%d]", d, LCCRF_MAX_DIMS);
     lccrf_handle h = nullptr;
     int rc = lccrf_create(&h, device_id, n_points, value_size);        // value_size plays the part of the label count
     if (rc) return rc;
@@ -2089,6 +2090,9 @@ int lccrf_batch_create(lccrf_batch_handle *out, int device_id, const lccrf_batch
     if (desc->max_frames < 1 || desc->max_points < 0) return fail(LCCRF_E_INVALID, "max_frames < 1 or max_points < 0");
     if (desc->n_labels < 1 || desc->n_labels > LCCRF_MAX_LABELS) return fail(LCCRF_E_INVALID, "n_labels out of range");
     if (desc->n_kernels < 0 || desc->n_kernels > LCCRF_MAX_KERNELS) return fail(LCCRF_E_INVALID, "n_kernels out of range");
+    for (int k = 0; k < desc->n_kernels; ++k)
+        if (desc->feat_dims[k] < 1 || desc->feat_dims[k] > LCCRF_MAX_DIMS)
+            return fail(LCCRF_E_INVALID, "feat_dims[%d] = %d not in [1,%d]", k, desc->feat_dims[k], LCCRF_MAX_DIMS);
     int rc = use_device(device_id);
     if (rc) return rc;
     lccrf_batch *b = new (std::nothrow) lccrf_batch;

@@ -18,6 +18,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 ORACLE_SO = os.path.join(_HERE, "liblccrf_oracle.so")
 REF_SO = os.path.join(_HERE, "_ref", "liblccrf_ref.so")
 
+# the label counts oracle/ref_driver.cpp instantiates DenseCRF3D<M> for (its REF_LABELS); features of 1..8 dimensions
+REF_LABELS = (1, 2, 3, 4, 5, 7, 8, 9, 16, 17, 21, 22, 31, 32, 33, 63, 64)
+
 _f32p = C.POINTER(C.c_float)
 _i16p = C.POINTER(C.c_int16)
 _i32p = C.POINTER(C.c_int)
@@ -251,7 +254,7 @@ class RefCRF(_CrfBase):
         self.N, self.L = int(N), int(L)
         self.h = self.lib.ref_crf_create(self.N, self.L)
         if not self.h:
-            raise ValueError("reference shim instantiates L in {2,3,4,21} only")
+            raise ValueError("reference shim instantiates L in %s only" % (REF_LABELS,))
         self._d = []
 
     def close(self):
@@ -276,7 +279,7 @@ class RefCRF(_CrfBase):
         f = f.reshape(self.N, f.shape[-1] if f.ndim == 2 else -1)
         rc = self.lib.ref_crf_add_pairwise(self.h, _ptr(f, _f32p), f.shape[1], float(w))
         if rc:
-            raise ValueError("reference shim instantiates d in 1..6 only")
+            raise ValueError("reference shim instantiates d in 1..8 only")
         self._d.append(f.shape[1])
 
     def apply(self, k, out, x):

@@ -114,9 +114,14 @@ int add_kernel_d(Handle *h, const float *feat, int d, float w)
     case 4: return add_kernel<M, 4>(h, feat, w);
     case 5: return add_kernel<M, 5>(h, feat, w);
     case 6: return add_kernel<M, 6>(h, feat, w);
+    case 7: return add_kernel<M, 7>(h, feat, w);
+    case 8: return add_kernel<M, 8>(h, feat, w);
     default: return -1;
     }
 }
+
+/* the label counts instantiated: every lane group and chunk boundary of the HIP engines (1..64, include/lccrf.h) */
+#define REF_LABELS(X) X(1) X(2) X(3) X(4) X(5) X(7) X(8) X(9) X(16) X(17) X(21) X(22) X(31) X(32) X(33) X(63) X(64)
 
 }  // namespace
 
@@ -128,10 +133,9 @@ void *ref_crf_create(int N, int L)
     h->N = N;
     h->L = L;
     switch (L) {
-    case 2: make_crf<2>(h, N); break;
-    case 3: make_crf<3>(h, N); break;
-    case 4: make_crf<4>(h, N); break;
-    case 21: make_crf<21>(h, N); break;
+#define REF_CREATE(M) case M: make_crf<M>(h, N); break;
+    REF_LABELS(REF_CREATE)
+#undef REF_CREATE
     default: delete h; return nullptr;
     }
     return h;
@@ -159,10 +163,9 @@ int ref_crf_add_pairwise(void *hv, const float *feat, int d, float w)
 {
     Handle *h = static_cast<Handle *>(hv);
     switch (h->L) {
-    case 2: return add_kernel_d<2>(h, feat, d, w);
-    case 3: return add_kernel_d<3>(h, feat, d, w);
-    case 4: return add_kernel_d<4>(h, feat, d, w);
-    case 21: return add_kernel_d<21>(h, feat, d, w);
+#define REF_ADD(M) case M: return add_kernel_d<M>(h, feat, d, w);
+    REF_LABELS(REF_ADD)
+#undef REF_ADD
     default: return -1;
     }
 }

@@ -104,3 +104,31 @@ def check_against_expected(c, exp, q_tol=None):
                     assert np.abs(q - exp["Q"][t]).max() <= q_tol
             c.build_map()
             assert np.array_equal(c.map(), exp["map"][t]), "labels differ after %d iterations" % t
+
+
+def label_problem(N, L, dims, seed, label=False, spread=3.0):
+    """A generic frame for any label count (tests/golden/make_golden_labels.py, tests/test_labels.py): terms of the given feature
+    dimensions, with points on lattice-cell boundaries; raw unaries whose first and last columns are equal (Q's columns 0 and L-1
+    then stay equal bit for bit: exact ties for the argmax, taken on about half of the rows) or, with label=True, labels in
+    [-1, L) with one confidence.  The weights sum to about 6.5 whatever the number of terms, so that even eight terms leave most
+    rows unsaturated."""
+    rng = np.random.default_rng([int(seed), int(N), int(L)] + [int(d) for d in dims])
+    kernels = []
+    for d in dims:
+        f = rng.normal(0.0, spread, (N, d)).astype(np.float32)
+        q = rng.random(N) < 0.5
+        f[q] = np.round(f[q] * 2) / 2
+        f[rng.random(N) < 0.1] = 0.0
+        kernels.append((f, np.float32(rng.uniform(1.0, 12.0) / len(dims))))
+    pb = dict(N=N, L=L, kernels=kernels)
+    if label:
+        assert L >= 2, "setUnaryEnergyFromLabel divides by L - 1"
+        pb["label"] = rng.integers(-1, L, N).astype(np.int16)
+        pb["conf"] = np.float32(rng.uniform(0.4, 0.8))
+    else:
+        u = (np.round(rng.uniform(0.05, 3.0, (N, L)) * 256) / 256).astype(np.float32)
+        low = rng.random(N) < 0.5
+        u[low, 0] = u[low].min(1) - np.float32(0.5)
+        u[:, L - 1] = u[:, 0]
+        pb["unary"] = u
+    return pb

@@ -170,12 +170,27 @@ def _generic_frames(wl, Ns=(300, 0, 1500, 77, 2500)):
     return Frames(probs, [2.5])
 
 
+def _label_frames(L, Ns, seed):
+    """ragged frames of eight terms (d = 1 .. 8, tests/crf_cases.py: label_problem) with the first frame's weights"""
+    EIGHT = list(range(1, 9))
+    probs = [cc.label_problem(n, L, EIGHT, seed=seed + i) if n else _empty(L, EIGHT) for i, n in enumerate(Ns)]
+    w = [float(x) for _, x in probs[0]["kernels"]]
+    return Frames([dict(pb, kernels=[(f, x) for (f, _), x in zip(pb["kernels"], w)]) for pb in probs], w)
+
+
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
-@pytest.mark.parametrize("kind", ["slam", "generic"])
+@pytest.mark.parametrize("kind", ["slam", "generic", "K8_L9", "K8_L33", "K8_L64"])
 def test_every_frame_has_the_bits_of_its_handle(wl, golden, kind):
-    fr = _slam_frames(golden, wl) if kind == "slam" else _generic_frames(wl)
-    assert fr.K == (2 if kind == "slam" else 1)
+    """every frame of a ragged batch (0-point frames among them) gets the bits of a handle of its own points; the K8_L* kinds:
+    eight terms of d = 1 .. 8 at 9, 33 and 64 labels (the backward's lane groups of 4 and 16 lanes, its partials at K = 8)"""
+    if kind == "slam":
+        fr = _slam_frames(golden, wl)
+    elif kind == "generic":
+        fr = _generic_frames(wl)
+    else:
+        fr = _label_frames(int(kind[4:]), (300, 0, 1100, 77, 650), seed=400)
+    assert fr.K == {"slam": 2, "generic": 1}.get(kind, 8)
     b = fr.batch()
     handles = {f: fr.handle(f) for f, n in enumerate(fr.N) if n}
     for T in (0, 1, 5, 10):

@@ -38,6 +38,8 @@ def _checker(po, pb):
 
 def _golden_problem(golden, name):
     group, case = name.split(":")
+    if group == "labels":                                       # (not among conftest's fixtures)
+        return cc.case_problem(np.load(os.path.join(os.path.dirname(__file__), "golden", "labels.npz")), case)
     z = golden[group]
     if group == "large":
         from test_oracle_golden import _large_case
@@ -73,7 +75,7 @@ def test_checker_gradcheck(po, wl):
         assert torch.autograd.gradcheck(lambda a, b: mf.forward(a, b, lats, 3, relax), (u, w), eps=1e-6, atol=1e-7)
 
 
-@pytest.mark.parametrize("name", ["slam:N1000", "generic:d3_L3", "generic:d6_L2"])
+@pytest.mark.parametrize("name", ["slam:N1000", "generic:d3_L3", "generic:d6_L2", "labels:d7_L2", "labels:d8_L2", "labels:K8_L5"])
 def test_reverse_order_filter_is_the_adjoint(po, golden, name):
     """<y, Phi x> = <Phi^T y, x> with Phi^T the same splat and slice and the blur passes in reverse axis order."""
     import torch
@@ -171,6 +173,8 @@ CASES = ["slam:N5", "slam:N1001", "slam:C3", "generic:d1_L3", "generic:d3_L21", 
 def _case(name, golden, po, wl):
     if name == "image64x48":
         return _crop_problem(golden, po)
+    if name.startswith("K8_L"):                                  # eight terms of d = 1 .. 8
+        return cc.label_problem(900, int(name[4:]), list(range(1, 9)), seed=6), None
     if name == "c2":
         return wl.slam_problem(2000, seed=12), None
     return _golden_problem(golden, name), None
@@ -188,15 +192,21 @@ def test_gradients_match_the_checker(po, wl, golden, name, T, relax):
     conditioning of those iterations in fp32, not the kernels; every other case and setting is <= 6e-5.  Gradients below 1e-6 of
     |dL/dQ| (slam:N5 from T = 5: |dL/dU| ~ 1e-17, every row saturated; the forward's fast_exp gives exactly 0 beyond e^-20, so by the
     section 1c convention the gradient is exactly 0) are compared in absolute terms against that floor."""
-    import torch
     pb, image = _case(name, golden, po, wl)
     o, lats, U = _checker(po, pb)
     G = np.random.default_rng(1234).standard_normal((pb["N"], pb["L"]))
-    w = _weights(pb)
-    ref_u, ref_w = mf.gradients(U, w, lats, T, relax, G)
     h, keep = _gpu_handle(pb, image)
     gu, gw = _backward(h, T, relax, G, len(pb["kernels"]))
     h.close()
+    assert_matches_checker(gu, gw, U, _weights(pb), lats, T, relax, G, name)
+
+
+def assert_matches_checker(gu, gw, U, w, lats, T, relax, G, name=""):
+    """The bar of test_gradients_match_the_checker: relative L2 error against the float64 checker <= max(1e-4, 10 x that of the
+    float32 checker), gradients below 1e-6 of |dL/dQ| compared in absolute terms against that floor; at T = 0 dL/dw is 0.
+    Returns the checker's (dL/dU, dL/dw)."""
+    import torch
+    ref_u, ref_w = mf.gradients(U, w, lats, T, relax, G)
     floor_u = 1e-6 * np.linalg.norm(G)
     floor_w = 1e-6 * np.linalg.norm(G) * max(np.linalg.norm(w), 1.0)
     eu, ew = _rel(gu, ref_u, floor_u), _rel(gw, ref_w, floor_w)
@@ -207,6 +217,7 @@ def test_gradients_match_the_checker(po, wl, golden, name, T, relax):
     assert eu <= bu and ew <= bw, "relative L2 error dL/dU %.3g (bar %.3g), dL/dw %.3g (bar %.3g)" % (eu, bu, ew, bw)
     if T == 0:
         assert np.all(gw == 0)
+    return ref_u, ref_w
 
 
 @pytest.mark.gpu
@@ -239,7 +250,7 @@ def test_t0_is_the_softmax_backward_and_k0_works(po, wl):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["c2", "generic:d3_L21", "large:c5"])
+@pytest.mark.parametrize("name", ["c2", "generic:d3_L21", "large:c5", "K8_L33", "K8_L64"])
 def test_backward_is_deterministic_and_leaves_the_inference_state(po, wl, golden, name):
     pb, image = _case(name, golden, po, wl)
     K = len(pb["kernels"])
