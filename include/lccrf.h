@@ -253,8 +253,8 @@ int  lccrf_map_of_device(lccrf_handle h, const float *d_prob, int16_t *d_map_out
  * Phi_k^T = alpha S^T B_0 .. B_d S: the same splat and slice, the blur passes in REVERSE axis order (every pass is symmetric -- n1(v)
  * = u exactly when n2(u) = v -- but the passes do not commute on a sparse lattice, so Phi_k is not).  The derivative treats the
  * reference's polynomial fast_exp (densecrf3d.h:51-67) as exp: the softmax Jacobian is formed from the forward's own P_t, computed
- * with the forward's arithmetic.  Not differentiated: the features (kernel bandwidths, positions), the MAP labels, and the label-
- * and-confidence form of the unary (take dL/dU and chain through that formula yourself).                                          */
+ * with the forward's arithmetic.  Not differentiated: the MAP labels, and the label-and-confidence form of the unary (take dL/dU
+ * and chain through that formula yourself).  The features (kernel bandwidths, positions, embeddings): section 1d.                 */
 
 /* PottsPotential3D::w_ of term `kernel` (set after construction).  The lattice and norm stay; the next inference equals, bit for
  * bit, that of a handle built with weight w.  Anything derived from w (the fused engines' w*norm products, prepared launch records)
@@ -280,6 +280,43 @@ int  lccrf_set_pairwise_weight(lccrf_handle h, int kernel, float w);
  *     LCCRF_E_STATE without unary energies.  K = 0 is legal (d_grad_weights then receives nothing).                             */
 int  lccrf_inference_backward(lccrf_handle h, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
                               float *d_grad_weights);
+
+/* ======================================================================================
+ * 1d. Gradients of inference() with respect to the FEATURES of the pairwise terms: one [N][d_k] array per term.  Everything a caller
+ *     derives features from -- the kernel standard deviations (feature = raw / stdev), an embedding network -- is a chain rule on
+ *     top of it (lc-crf-slam_amd/autograd.py: mean_field_features, LearnedKernelCRF).
+ *     Sections 1d and 2d were added WITHOUT a step of LCCRF_ABI_VERSION (it stays 3): probe for them by symbol.
+ *
+ * What is differentiated.  The lattice filter is continuous in the features and piecewise smooth: while no point leaves its simplex
+ * the vertices, the neighbour tables and every rank are constant, and the barycentric weight b_ic of point i at corner c (vertex
+ * v_ic) is LINEAR in the point's features (permutohedral_cpu.h:304-366).  The gradient is that derivative -- one-sided where a point
+ * sits exactly on a simplex face or a rounding tie -- i.e. the exact derivative of what the library computes, not that of the
+ * Gaussian the lattice approximates.  With section 1c's notation, V = S x the splat, B = B_d .. B_0, B^T = B_0 .. B_d:
+ *      d<y, Phi_k(x)> / d b_ic = alpha_k (<y_i, (B S x)[v_ic]> + <x_i, (B^T S y)[v_ic]>)              <.,.> over the labels
+ *      for t = T .. 1:   g_b[k][i][c] += alpha_k w_k (<y_i, (B S Q_{t-1})[v_ic]> + <Q_{t-1},i, (B^T S y)[v_ic]>),   y = n_k . gamma_t
+ *                        g_n[k][i]    += w_k <gamma_t,i, Phi_k(Q_{t-1})_i>
+ *      the norm n_k = 1 / (Phi_k(1) + 1e-20), with a_k = -n_k^2 . g_n[k]:
+ *                        g_b[k][i][c] += alpha_k (a_k,i (B S 1)[v_ic] + (B^T S a_k)[v_ic])
+ *      dL/df_im = sum_q g_b[k][i][q] . scale_m / (d+1) . (E[e(q)][m] - E[e(q-1)][m]),   E[j][m] = [m >= j] - j [m == j-1], E[0][m] = 1,
+ *      e(q) the coordinate of the elevated point whose rank is d - q (indices mod d+1), scale_m as permutohedral_cpu.h:282-285.
+ * At n_iterations = 0 nothing depends on the features: the gradient is exactly 0.
+ *
+ * d_grad_features: HOST array of K device pointers; d_grad_features[k] is [N][d_k], overwritten.  An entry may be NULL: that term's
+ * feature gradient (and its extra launches) is skipped, the other terms' bits do not change.  d_grad_features == NULL makes the
+ * call lccrf_inference_backward.  d_grad_unary and d_grad_weights receive the bits lccrf_inference_backward gives; either may be
+ * NULL here.  Everything else is section 1c's contract: self-contained (the forward is replayed), device arrays checked as in
+ * section 1b, on the handle's stream, no host synchronisation beyond the one-time learning of new lattices' sizes, frames in
+ * locality mode re-built the plain way with results in the caller's point order, Q afterwards as lccrf_inference(h, T, 0, relax)
+ * leaves it, the same errors, and a rejected call leaves the handle as it was.
+ *   - Deterministic: no float atomics.  Every g_b[k][i][c] has one owner and is accumulated in the order t = T .. 1, slice-side
+ *     part before splat-side part, the norm part last, labels 0 .. L-1 inside a dot product: the same bits from run to run.
+ *   - Launches: per iteration and term two corner-dot kernels more than section 1c; per term, after the loop, two filters of value
+ *     width 1 (splat + d+1 blur passes each), two corner-dot kernels, and two small per-point kernels.
+ *   - Memory: section 1c's area grows by 4 * sum over the terms asked for of N4 * (d_k + 2) bytes (g_b and g_n), and by 4 * N4 * L
+ *     when d_grad_unary is NULL: 4 * (N4*L*(T + K + 1) + max(T,1)*K*B + sum_k N4*(d_k + 2)) bytes in all (N = 2000, L = 2, K = 2
+ *     of d = 2, T = 5: 128 KB + 64 KB).  Allocated as section 1c's: by the first call that needs more, never by lccrf_inference.     */
+int  lccrf_inference_backward_features(lccrf_handle h, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
+                                       float *d_grad_weights, float *const *d_grad_features);
 
 /* ======================================================================================
  * 2. Batch API -- many independent frames in flight on one GPU.
@@ -462,6 +499,18 @@ int  lccrf_batch_set_unary_device(lccrf_batch_handle b, const float *d_unary);
  *     call leaves the batch's inputs, lattices and Q as they were.  K = 0 is legal (d_grad_weights then receives nothing).       */
 int  lccrf_batch_inference_backward(lccrf_batch_handle b, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
                                     float *d_grad_weights, void *stream);
+
+/* ======================================================================================
+ * 2d. Section 1d for every frame of a batch at once, in the launches section 1d takes for one frame.  d_grad_features: host array of
+ *     n_kernels device pointers, d_grad_features[k] [n_frames][max_points][d_k], overwritten (rows at or beyond a frame's n_points
+ *     are written 0; a frame of 0 points gets zeros); entries, or the array, may be NULL as in section 1d, and so may d_grad_unary
+ *     and d_grad_weights.  Per frame, the bits of section 1d for a handle holding that frame -- for dL/df as for dL/dU and dL/dw --
+ *     and everything else is section 2c's contract (streams, state, errors, what is needed beforehand).  The feature arrays the
+ *     batch was given (lccrf_batch_bind_inputs_device: the caller's own) are read again by this call.
+ *     Memory: section 2c's area plus 4 * F * sum over the terms asked for of P4 * (d_k + 2) bytes, P4 = max_points rounded up to
+ *     a multiple of 4 (plus 4 * F * max_points * L when d_grad_unary is NULL).  Added without a step of LCCRF_ABI_VERSION.         */
+int  lccrf_batch_inference_backward_features(lccrf_batch_handle b, int n_iterations, float relax, const float *d_grad_prob,
+                                             float *d_grad_unary, float *d_grad_weights, float *const *d_grad_features, void *stream);
 
 /* ======================================================================================
  * 3. Unary builder -- the step right before the CRF (first "next" row):

@@ -117,6 +117,7 @@ def lib():
     L.lccrf_map_of_device.argtypes = [vp, vp, vp]
     L.lccrf_set_pairwise_weight.argtypes = [vp, C.c_int, C.c_float]
     L.lccrf_inference_backward.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp]
+    L.lccrf_inference_backward_features.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, C.POINTER(vp)]
     L.lccrf_batch_create.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(BatchDesc)]
     L.lccrf_batch_destroy.argtypes = [vp]
     L.lccrf_batch_destroy.restype = None
@@ -149,6 +150,7 @@ def lib():
     L.lccrf_batch_set_pairwise_weight.argtypes = [vp, C.c_int, C.c_float]
     L.lccrf_batch_set_unary_device.argtypes = [vp, vp]
     L.lccrf_batch_inference_backward.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, vp]
+    L.lccrf_batch_inference_backward_features.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, C.POINTER(vp), vp]
     L.lccrf_bf_match.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_double, _i32p, _i32p]
     L.lccrf_pose_optimization.argtypes = [C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, C.c_void_p, _i16p, _f32p, C.c_float,
                                           _f32p, _f32p, C.c_void_p, _i32p]
@@ -165,6 +167,18 @@ def lib():
 def _check(rc):
     if rc != OK:
         raise LccrfError(rc, lib().lccrf_last_error().decode("utf-8", "replace"))
+
+
+def _addr(p):
+    """a raw device address (or None / 0: NULL) as a C pointer argument"""
+    return C.c_void_p(int(p)) if p else None
+
+
+def _addr_list(ps):
+    """a list of raw device addresses (None entries: NULL) as a host array of pointers; None: NULL"""
+    if ps is None:
+        return None
+    return (C.c_void_p * max(len(ps), 1))(*[_addr(p) for p in ps])
 
 
 def set_default_option(option, value):
@@ -344,6 +358,13 @@ class DenseCRFHIP:
         _check(lib().lccrf_inference_backward(self.h, int(n_iterations), float(relax), C.c_void_p(d_grad_prob),
                                               C.c_void_p(d_grad_unary), C.c_void_p(d_grad_weights) if d_grad_weights else None))
 
+    def inference_backward_features_device(self, n_iterations, relax, d_grad_prob, d_grad_unary=None, d_grad_weights=None,
+                                           d_grad_features=None):
+        """inference_backward_device plus dL/d features: d_grad_features is a list of K device addresses ([N][d_k] each) or None
+        entries (that term is skipped); d_grad_unary / d_grad_weights may be None (include/lccrf.h section 1d)."""
+        _check(lib().lccrf_inference_backward_features(self.h, int(n_iterations), float(relax), C.c_void_p(d_grad_prob),
+                                                       _addr(d_grad_unary), _addr(d_grad_weights), _addr_list(d_grad_features)))
+
     # -- results -----------------------------------------------------------------------
     def map(self):
         out = np.empty(self.N, np.int16)
@@ -513,6 +534,14 @@ class BatchCRF:
                                                     C.c_void_p(int(d_grad_unary)),
                                                     C.c_void_p(int(d_grad_weights)) if d_grad_weights else None,
                                                     C.c_void_p(stream) if stream else None))
+
+    def inference_backward_features_device(self, n_iterations, relax, d_grad_prob, d_grad_unary=None, d_grad_weights=None,
+                                           d_grad_features=None, stream=None):
+        """inference_backward_device plus dL/d features: d_grad_features is a list of K device addresses
+        ([n_frames][max_points][d_k] each) or None entries (include/lccrf.h section 2d)."""
+        _check(lib().lccrf_batch_inference_backward_features(self.h, int(n_iterations), float(relax), C.c_void_p(int(d_grad_prob)),
+                                                             _addr(d_grad_unary), _addr(d_grad_weights), _addr_list(d_grad_features),
+                                                             C.c_void_p(stream) if stream else None))
 
     def set_engine(self, engine):
         _check(lib().lccrf_batch_set_engine(self.h, int(engine)))

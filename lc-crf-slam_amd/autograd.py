@@ -1,10 +1,13 @@
-"""torch autograd through DenseCRF::inference on the HIP path (include/lccrf.h sections 1c and 2c).
+"""torch autograd through DenseCRF::inference on the HIP path (include/lccrf.h sections 1c, 1d and 2c).
 
     Q = mean_field(crf, unary, weights, n_iterations=5, relax=1.0)
     Q.backward(g)      # -> unary.grad = dL/dU, weights.grad = dL/dw
 
     Q = mean_field_batch(batch, unary, weights, n_iterations=5, relax=1.0)     # every frame of a BatchCRF at once
     Q.backward(g)      # -> unary.grad [F, max_points, L], weights.grad = sum over the frames of dL/dw
+
+    Q = mean_field_features(unary, [f_0, f_1, ..], weights, n_iterations=5, relax=1.0)        # the features are inputs too
+    Q.backward(g)      # -> also f_k.grad = dL/d features [N, d_k] (section 1d); LearnedKernelCRF fits kernel bandwidths with it
 
 `crf` is a DenseCRFHIP whose pairwise terms are already added (their features fix the lattices; only the weights are
 inputs here).  Forward: lccrf_set_pairwise_weight + lccrf_set_unary_device + lccrf_inference.  Backward:
@@ -206,3 +209,120 @@ class BatchMeanFieldCRF(torch.nn.Module):
 
     def close(self):
         self.batch.close()
+
+
+class _MeanFieldFeatures(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, unary, weights, n_iterations, relax, device, *features):
+        if not unary.is_cuda or unary.dtype != torch.float32 or unary.dim() != 2:
+            raise ValueError("unary must be a float32 GPU tensor of shape [N, L]")
+        N, L = (int(x) for x in unary.shape)
+        K = len(features)
+        if weights.dtype != torch.float32 or tuple(weights.shape) != (K,):
+            raise ValueError("weights must be a float32 tensor of shape [%d]" % K)
+        for f in features:
+            if not f.is_cuda or f.dtype != torch.float32 or f.dim() != 2 or int(f.shape[0]) != N:
+                raise ValueError("every feature array must be a float32 GPU tensor of shape [%d, d_k]" % N)
+        if n_iterations < 0:
+            raise ValueError("n_iterations must be >= 0")
+        dev = unary.device
+        u = unary.detach().contiguous()
+        fs = [f.detach().contiguous() for f in features]
+        # the lattices depend on the features: a handle per forward (lccrf_create re-uses parked handles), closed by the backward
+        crf = _pkg.DenseCRFHIP(N, L, device=device)
+        cur = torch.cuda.current_stream(dev)
+        ext = _handle_stream(crf, dev)
+        ext.wait_stream(cur)
+        crf.set_unary_device(u.data_ptr())
+        for f, w in zip(fs, weights.detach().cpu().tolist()):
+            crf.add_pairwise_device(f.data_ptr(), int(f.shape[1]), w)
+        crf.inference(int(n_iterations), False, float(relax))
+        crf.synchronize()                                     # the completion rule of inference() results
+        with torch.cuda.stream(ext):
+            q = _device_view(crf.device_buffers()["current"], (N, L), dev).clone()
+        cur.wait_stream(ext)
+        q.record_stream(cur)
+        ctx.crf, ctx.n_iterations, ctx.relax = crf, int(n_iterations), float(relax)
+        ctx.weights_device = weights.device
+        ctx.save_for_backward(u, *fs)
+        return q
+
+    @staticmethod
+    def backward(ctx, grad_q):
+        u, fs = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        crf = ctx.crf
+        if crf is None:
+            raise RuntimeError("mean_field_features: backward a second time (the handle is closed by the first)")
+        dev = u.device
+        g = grad_q.detach().to(device=dev, dtype=torch.float32).contiguous()
+        cur = torch.cuda.current_stream(dev)
+        K = len(fs)
+        need = ctx.needs_input_grad
+        grad_u = torch.empty_like(u)
+        grad_w = torch.empty(max(K, 1), dtype=torch.float32, device=dev)
+        grad_f = [torch.empty_like(f) if need[5 + k] else None for k, f in enumerate(fs)]
+        ext = _handle_stream(crf, dev)
+        ext.wait_stream(cur)
+        crf.inference_backward_features_device(ctx.n_iterations, ctx.relax, g.data_ptr(), grad_u.data_ptr(),
+                                               grad_w.data_ptr() if K else None,
+                                               [t.data_ptr() if t is not None else None for t in grad_f])
+        cur.wait_stream(ext)
+        crf.synchronize()                                     # (the handle goes back to the cache: nothing of this call may be in flight)
+        crf.close()
+        ctx.crf = None
+        if K == 0:
+            grad_w = torch.zeros(0, dtype=torch.float32, device=dev)
+        return (grad_u, grad_w[:K].to(ctx.weights_device), None, None, None) + tuple(grad_f)
+
+
+def mean_field_features(unary, features, weights, n_iterations=5, relax=1.0, device=0):
+    """Q_T of DenseCRF::inference(n_iterations, relax) with unary energies `unary` [N, L] (float32, GPU), pairwise terms over
+    `features` (a list of [N, d_k] float32 GPU tensors, already divided by the kernels' standard deviations) and their weights
+    `weights` [K] (float32, any device); differentiable in all three.  The feature gradient is the exact derivative of the lattice
+    filter inside the simplices the points sit in (include/lccrf.h section 1d).  Every forward builds the lattices afresh on a
+    handle of its own, which its backward closes: one backward per forward."""
+    return _MeanFieldFeatures.apply(unary, weights, n_iterations, relax, device, *features)
+
+
+class LearnedKernelCRF(torch.nn.Module):
+    """A dense CRF layer whose kernel standard deviations are learned with the term weights.
+
+    raw_features: list of [N, d_k] arrays or tensors, NOT divided by any standard deviation; sd: per term, the initial standard
+    deviations -- one value per feature column, or one per group with `groups` (per term a list of column-index lists, e.g.
+    [[0, 1], [2, 3, 4]] so that (x, y) share posdev and (r, g, b) share featuredev; None: every column its own).  The parameters
+    are log_sd[k] (one value per group) and weights; forward(unary [N, L]) forms raw * exp(-log_sd) and calls mean_field_features,
+    so autograd carries dL/d features to the bandwidths."""
+
+    def __init__(self, raw_features, sd, weights, groups=None, n_iterations=5, relax=1.0, device=0):
+        super().__init__()
+        if not (len(raw_features) == len(sd) == len(weights)):
+            raise ValueError("one list of standard deviations and one weight per feature array")
+        dev = torch.device("cuda", device)
+        self.raw = [torch.as_tensor(np.ascontiguousarray(f.detach().cpu().numpy() if isinstance(f, torch.Tensor) else f, np.float32),
+                                    device=dev) for f in raw_features]
+        groups = groups if groups is not None else [None] * len(self.raw)
+        self.log_sd = torch.nn.ParameterList()
+        self._col = []                                        # per term: group of every column
+        for f, s, g in zip(self.raw, sd, groups):
+            d = int(f.shape[1])
+            g = [[c] for c in range(d)] if g is None else [list(x) for x in g]
+            if sorted(c for x in g for c in x) != list(range(d)):
+                raise ValueError("the groups of a term must partition its %d columns" % d)
+            s = np.broadcast_to(np.asarray(s, np.float64), (len(g),))
+            col = np.empty(d, np.int64)
+            for j, x in enumerate(g):
+                col[x] = j
+            self._col.append(torch.as_tensor(col, device=dev))
+            self.log_sd.append(torch.nn.Parameter(torch.tensor(np.log(s), dtype=torch.float32, device=dev)))
+        self.weights = torch.nn.Parameter(torch.tensor([float(w) for w in weights], dtype=torch.float32))
+        self.n_iterations, self.relax, self.device = int(n_iterations), float(relax), int(device)
+
+    def features(self):
+        """the features the CRF sees: raw / sd, column by column"""
+        return [f * torch.exp(-ls)[col] for f, ls, col in zip(self.raw, self.log_sd, self._col)]
+
+    def sd(self):
+        return [torch.exp(ls.detach()).cpu().numpy() for ls in self.log_sd]
+
+    def forward(self, unary):
+        return mean_field_features(unary, self.features(), self.weights, self.n_iterations, self.relax, self.device)

@@ -205,15 +205,31 @@ struct Engine {
     }
     // The backward on the area: inference(T, 0, relax) replayed on the step path (start + T x step), `count` floats of Q kept per
     // iteration in arrays of `slice` floats, dL/dQ_T copied in, then the reverse sweep over frames of up to `rows` points.
-    int backward(size_t slice, size_t count, int rows, int T, float relax, const float *grad_prob, float *grad_unary, float *grad_weights)
+    // grad_features (sections 1d / 2d): K device pointers or null; grad_unary may then be null (the area holds one more array).
+    // backward_need() is the area this takes.
+    size_t backward_need(size_t slice, int rows, int T, bool scratch_unary, float *const *grad_features) const
     {
         const int K = (int)kernels.size();
-        BackwardArea ar;
+        size_t extra = scratch_unary ? slice : 0;
+        for (int k = 0; k < K && grad_features; ++k)
+            if (grad_features[k]) extra += backward_feature_floats(kernels[k].dev, F);
+        return backward_bytes(slice, F, rows, L, K, T) + extra * sizeof(float);
+    }
+    int backward(size_t slice, size_t count, int rows, int T, float relax, const float *grad_prob, float *grad_unary, float *grad_weights,
+                 float *const *grad_features = nullptr)
+    {
+        const int K = (int)kernels.size();
+        BackwardArea ar{};
         ar.slice = slice;
         ar.hist = reinterpret_cast<float *>(bwd_area);
         ar.phi = ar.hist + (size_t)T * slice;
         ar.G = ar.phi + (size_t)K * slice;
         ar.partial = ar.G + slice;
+        float *extra = ar.partial + (size_t)std::max(T, 1) * K * F * std::max(backward_blocks(rows, L), 1);
+        if (!grad_unary) {
+            grad_unary = extra;
+            extra += slice;
+        }
         int rc = start();                                 // (ensure_plain: a handle's frames in locality mode are re-built the plain way once)
         if (!rc) rc = learn_sizes();
         if (rc) return rc;
@@ -225,8 +241,20 @@ struct Engine {
             if (grad_weights && K) HIP_TRY(hipMemsetAsync(grad_weights, 0, (size_t)F * K * sizeof(float), stream));
             return LCCRF_OK;
         }
+        for (int k = 0; k < K && grad_features; ++k) {
+            if (!grad_features[k]) continue;
+            const KernelDev &kd = kernels[k].dev;
+            if (T == 0) {                                 // nothing depends on the features: exactly 0
+                HIP_TRY(hipMemsetAsync(grad_features[k], 0, (size_t)F * rows * kd.d * sizeof(float), stream));
+                continue;
+            }
+            ar.gb[k] = extra;
+            ar.gn[k] = extra + (size_t)F * kd.Epad;
+            HIP_TRY(hipMemsetAsync(extra, 0, backward_feature_floats(kd, F) * sizeof(float), stream));
+            extra += backward_feature_floats(kd, F);
+        }
         HIP_TRY(hipMemcpyAsync(ar.G, grad_prob, count * sizeof(float), hipMemcpyDeviceToDevice, stream));
-        launch_backward_sweep(crf, kdevs.data(), maxV.data(), rows, T, relax, ar, grad_unary, grad_weights, stream);
+        launch_backward_sweep(crf, kdevs.data(), maxV.data(), rows, T, relax, ar, grad_unary, grad_weights, stream, grad_features);
         HIP_TRY(hipGetLastError());
         return LCCRF_OK;
     }
@@ -2081,6 +2109,33 @@ int lccrf_inference_backward(lccrf_handle h, int n_iterations, float relax, cons
 }
 
 // --------------------------------------------------------------------------------------
+// section 1d: ... and with respect to the features of the pairwise terms
+
+int lccrf_inference_backward_features(lccrf_handle h, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
+                                      float *d_grad_weights, float *const *d_grad_features)
+{
+    CHECK_H(h);
+    Engine &e = h->eng;
+    if (n_iterations < 0) return fail(LCCRF_E_INVALID, "n_iterations < 0");
+    if (!std::isfinite(relax)) return fail(LCCRF_E_INVALID, "relax must be finite");
+    const int K = (int)e.kernels.size(), T = n_iterations;
+    const size_t nl = (size_t)h->N * e.L;
+    { int rc = check_device_array(h, d_grad_prob, nl * sizeof(float), "d_grad_prob"); if (rc) return rc; }
+    if (d_grad_unary) { int rc = check_device_array(h, d_grad_unary, nl * sizeof(float), "d_grad_unary"); if (rc) return rc; }
+    if (d_grad_weights) { int rc = check_device_array(h, d_grad_weights, (size_t)K * sizeof(float), "d_grad_weights"); if (rc) return rc; }
+    for (int k = 0; k < K && d_grad_features; ++k)
+        if (d_grad_features[k]) {
+            int rc = check_device_array(h, d_grad_features[k], (size_t)h->N * e.kernels[k].dev.d * sizeof(float), "d_grad_features[k]");
+            if (rc) return rc;
+        }
+    if (!e.unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
+    { int rl = e.resolve_late(); if (rl) return rl; }
+    const size_t ns = backward_stride(h->N, e.L);
+    { int ra = e.ensure_backward_area(e.backward_need(ns, h->N, T, !d_grad_unary, d_grad_features)); if (ra) return ra; }
+    return e.backward(ns, nl, h->N, T, relax, d_grad_prob, d_grad_unary, d_grad_weights, d_grad_features);
+}
+
+// --------------------------------------------------------------------------------------
 // batch API
 // --------------------------------------------------------------------------------------
 int lccrf_batch_create(lccrf_batch_handle *out, int device_id, const lccrf_batch_desc *desc)
@@ -2647,6 +2702,36 @@ int lccrf_batch_inference_backward(lccrf_batch_handle b, int n_iterations, float
         if ((rc = e.ensure_backward_area(backward_bytes(nl, e.F, e.maxN, e.L, K, T)))) return rc;
         if ((rc = e.ensure_plain_batch())) return rc;
         return e.backward(nl, nl, e.maxN, T, relax, d_grad_prob, d_grad_unary, d_grad_weights);
+    });
+}
+
+// --------------------------------------------------------------------------------------
+// section 2d: ... and with respect to the features of the pairwise terms
+
+int lccrf_batch_inference_backward_features(lccrf_batch_handle b, int n_iterations, float relax, const float *d_grad_prob,
+                                            float *d_grad_unary, float *d_grad_weights, float *const *d_grad_features, void *stream)
+{
+    CHECK_H(b);
+    Engine &e = b->eng;
+    if (n_iterations < 0) return fail(LCCRF_E_INVALID, "n_iterations < 0");
+    if (!std::isfinite(relax)) return fail(LCCRF_E_INVALID, "relax must be finite");
+    const int K = (int)e.kernels.size(), T = n_iterations;
+    const size_t nl = (size_t)e.F * e.maxN * e.L;
+    { int rc = check_device_array(e, d_grad_prob, nl * sizeof(float), "d_grad_prob"); if (rc) return rc; }
+    if (d_grad_unary) { int rc = check_device_array(e, d_grad_unary, nl * sizeof(float), "d_grad_unary"); if (rc) return rc; }
+    if (d_grad_weights) { int rc = check_device_array(e, d_grad_weights, (size_t)e.F * K * sizeof(float), "d_grad_weights"); if (rc) return rc; }
+    for (int k = 0; k < K && d_grad_features; ++k)
+        if (d_grad_features[k]) {
+            int rc = check_device_array(e, d_grad_features[k], (size_t)e.F * e.maxN * e.kernels[k].dev.d * sizeof(float), "d_grad_features[k]");
+            if (rc) return rc;
+        }
+    if (!b->inputs_set || !(e.built || e.started)) return fail(LCCRF_E_STATE, "lccrf_batch_build or lccrf_batch_run has not run for these inputs");
+    return timed_batch_call(e, stream, e.ev[2], e.ev[3], e.timed_inf, [&] {
+        int rc = e.resolve_late();
+        if (rc) return rc;
+        if ((rc = e.ensure_backward_area(e.backward_need(nl, e.maxN, T, !d_grad_unary, d_grad_features)))) return rc;
+        if ((rc = e.ensure_plain_batch())) return rc;
+        return e.backward(nl, nl, e.maxN, T, relax, d_grad_prob, d_grad_unary, d_grad_weights, d_grad_features);
     });
 }
 

@@ -186,8 +186,14 @@ void launch_exp_and_normalize(const CrfDev &c, const float *in, float *out, floa
 void launch_step_init(const CrfDev &c, float *out, hipStream_t s);
 // reverse = 1: the blur passes in reverse axis order (d .. 0) -- the TRANSPOSED filter alpha S^T B_0 .. B_d S of the one the
 // forward applies (alpha S^T B_d .. B_0 S; every pass is symmetric, their product is not).  `out` may be `in` (the splat reads it first).
+// blurred (optional): receives the kernel's value buffer (val0 or val1) that the slice read -- (B S in)[v][l] at
+// [f * vstride + vbase + v * L + l], valid until the kernel's next splat (the feature gradient's corner dots read it there)
 void launch_filter(const KernelDev &kd, const CrfDev &c, int maxV, const float *in, float *out, int accumulate, hipStream_t s,
-                   int reverse = 0);
+                   int reverse = 0, const float **blurred = nullptr);
+// the same for a value width of 1 and without the slice: in [F][in_stride] (null: all ones, the normalisation's input); returns
+// the blurred values, (B S in)[v] at [f * vstride + vbase + v]
+const float *launch_filter_values1(const KernelDev &kd, const CrfDev &c, int maxV, const float *in, int in_stride, hipStream_t s,
+                                   int reverse);
 hipError_t time_blur_pass(const KernelDev &kd, int F, int maxV, int L, int reps, hipStream_t s, float *ms_per_launch);
 // object API, device inputs (device_inputs.hip): dst[i][0..d) for i < n from a caller's [n][d] array (copy), from the pixel position
 // (x, y) / posdev of point i = y * width + x (position), or from that plus an RGB pixel [n][3] / featuredev (uint8 or float image)
@@ -209,14 +215,22 @@ struct BackwardArea {
     float *phi;           // [K][slice]
     float *G;             // [slice]
     float *partial;       // [max(T,1)][K][F][backward_blocks(rows, L)]
+    // the feature part (sections 1d and 2d), per term whose feature gradient is asked for, else null: dL/d(corner weight) of every
+    // entry, laid out as KernelDev::bary, and the per-point sum behind the norm's gradient -- backward_feature_floats() per term,
+    // zeroed by the caller before every sweep
+    float *gb[LCCRF_MAX_KERNELS];   // [F][Epad]
+    float *gn[LCCRF_MAX_KERNELS];   // [F][maxNpad]
 };
 int backward_blocks(int n, int L);
 size_t backward_stride(int n, int L);
 size_t backward_bytes(size_t slice, int F, int rows, int L, int K, int T);
+inline size_t backward_feature_floats(const KernelDev &kd, int F) { return (size_t)F * ((size_t)kd.Epad + kd.maxNpad); }
 // the reverse sweep over the F = c.F frames of up to `rows` points each (the replay has filled ar.hist and ar.G = dL/dQ_T);
-// grad_unary [F][c.maxN][L] (rows [n_points[f], rows) written 0), grad_weights [F][K] or null
+// grad_unary [F][c.maxN][L] (rows [n_points[f], rows) written 0), grad_weights [F][K] or null;
+// grad_features (or null): K pointers, [F][c.maxN][d_k] each or null (rows [n_points[f], rows) written 0) -- for every one given,
+// ar.gb[k] / ar.gn[k] are set.  Without any, the launches are those of sections 1c / 2c.
 void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int rows, int T, float relax, const BackwardArea &ar,
-                           float *grad_unary, float *grad_weights, hipStream_t s);
+                           float *grad_unary, float *grad_weights, hipStream_t s, float *const *grad_features = nullptr);
 
 // ---- fused build (SLAM sizes; one workgroup per (frame, kernel), hash table in LDS) ------
 bool build_small_supported(const KernelDev *kds, int n, int max_points);

@@ -13,6 +13,18 @@
 // batch gets the bits a handle of its n_points[f] points gets (the weight gradient's partials included: backward_blocks(n_points[f])
 // of them per iteration, reduced in the handle's order).
 //
+// The feature part (sections 1d and 2d: dL/d features of every term asked for) rides in the same sweep.  Inside a simplex the corner
+// weights b_ic are linear in the point's features, and for any product <y, Phi(x)>
+//   d<y, Phi(x)> / d b_ic = alpha (<y_i, (B S x)[v_ic]> + <x_i, (B^T S y)[v_ic]>)
+// -- the blurred vertex values of the forward filter dotted with the upstream row, and those of the transposed filter dotted with the
+// input row.  Both are in term k's own value buffer when they are needed (launch_filter hands the buffer out), so per (t, k) the
+// sweep adds two k_corner_dot launches: x = Q_{t-1}, y = w_k n_k gamma_t.  The norm n_k = 1 / (Phi_k(1) + 1e-20) depends on the
+// features too: k_softmax_bwd<G, true> also accumulates g_n[k][i] = sum_t w_k <gamma_t,i, Phi_k(Q_{t-1})_i>, and after the loop one
+// width-1 filter pair per term gives the corner dots of <a_k, Phi_k(1)>, a_k = -n_k^2 g_n[k].  k_corner_to_feature then maps
+// dL/db to dL/df through the simplex of the point (recomputed from the features with the build's own lattice_simplex: the ranks
+// of the one-workgroup build never reach HBM).  Every g_b[i][c] has one owner and one order of additions (t = T .. 1, slice side,
+// splat side; the norm part last): the same bits from run to run, and for a frame of a batch those of a handle.
+//
 // Rows at or beyond n_points[f] (the phantom points of quirk Q1 among them) are never read: every lattice build lists real points
 // only in its splat rows (k_csr_count / k_eoffsets in stream_engine.hip, E = N (d+1) in build_small.hip), the slice writes rows
 // i < n_points[f] only, and the kernels below stop at n_points[f].  A batch rebound with fewer points than an earlier call leaves
@@ -42,6 +54,8 @@ struct BwdArgs {
     float *partial;              // [K][F][gridDim.x] or null
     const float *norm[kBwdMaxK];
     float w[kBwdMaxK];
+    float *gn[kBwdMaxK];         // k_softmax_bwd<G, true>: [F][gnstride] per term, or null (BackwardArea::gn)
+    int gnstride;
 };
 
 // lanes per row: one row per lane up to 4 labels, then four labels per lane over a power-of-two group of lanes
@@ -68,7 +82,8 @@ __device__ __forceinline__ float row_sum_ordered(const float (&v)[4], int L, int
 //   gU  = -gam (first) or gU - gam
 //   phi_k <- n_k * gam (in place: the transposed filter's input), partial[k][f][block] = sum over the block of n_k * gam * Phi_k
 // K = 0: x = -U (the start, densecrf_base.h:78-80, or a CRF without terms).
-template <int G>
+// FEAT: also gn[k][i] += w_k * <gam_i, Phi_k,i> (labels in order) for every term with a gn -- nothing else changes.
+template <int G, bool FEAT>
 __global__ void __launch_bounds__(kBwdBlock) k_softmax_bwd(BwdArgs a)
 {
     const int f = blockIdx.y;
@@ -141,12 +156,14 @@ __global__ void __launch_bounds__(kBwdBlock) k_softmax_bwd(BwdArgs a)
     }
     const float dev = row_sum_ordered<G>(gp, L, first);
     float wsum[kBwdMaxK];
+    float gamv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
     for (int k = 0; k < kBwdMaxK; ++k) wsum[k] = 0.0f;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         if (!has[u]) continue;
         const float gam = a.relax * (p[u] * ((g[u] - ga) - dev));
+        if (FEAT) gamv[u] = gam;
         a.gU[q + u] = a.first ? -gam : a.gU[q + u] - gam;
 #pragma unroll
         for (int k = 0; k < kBwdMaxK; ++k)
@@ -155,6 +172,20 @@ __global__ void __launch_bounds__(kBwdBlock) k_softmax_bwd(BwdArgs a)
                 wsum[k] += gn * ph[k][u];
                 a.phi[k * a.slice + q + u] = gn;
             }
+    }
+    if (FEAT) {
+#pragma unroll
+        for (int k = 0; k < kBwdMaxK; ++k) {
+            if (k >= K || !a.gn[k]) continue;             // (uniform)
+            float v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = gamv[u] * ph[k][u];
+            const float sk = row_sum_ordered<G>(v, L, first);
+            if (live && sub == 0) {
+                float *gp = a.gn[k] + (size_t)f * a.gnstride + i;
+                *gp = *gp + a.w[k] * sk;
+            }
+        }
     }
     if (!a.partial) return;
     // per-workgroup partials: a fixed butterfly over the wavefront, then the four wavefronts in order
@@ -212,16 +243,163 @@ __global__ void __launch_bounds__(kBwdBlock) k_bwd_reduce(const float *__restric
     if (threadIdx.x == 0) out[(size_t)f * K + k] = s[0];
 }
 
+template <bool FEAT>
 void launch_softmax_bwd(const BwdArgs &a, int F, hipStream_t s)
 {
     const int G = bwd_lanes(a.L);
     const dim3 grid((unsigned)std::max(backward_blocks(a.rows, a.L), 1), (unsigned)F);
     switch (G) {
-    case 1: k_softmax_bwd<1><<<grid, kBwdBlock, 0, s>>>(a); break;
-    case 2: k_softmax_bwd<2><<<grid, kBwdBlock, 0, s>>>(a); break;
-    case 4: k_softmax_bwd<4><<<grid, kBwdBlock, 0, s>>>(a); break;
-    case 8: k_softmax_bwd<8><<<grid, kBwdBlock, 0, s>>>(a); break;
-    default: k_softmax_bwd<16><<<grid, kBwdBlock, 0, s>>>(a); break;
+    case 1: k_softmax_bwd<1, FEAT><<<grid, kBwdBlock, 0, s>>>(a); break;
+    case 2: k_softmax_bwd<2, FEAT><<<grid, kBwdBlock, 0, s>>>(a); break;
+    case 4: k_softmax_bwd<4, FEAT><<<grid, kBwdBlock, 0, s>>>(a); break;
+    case 8: k_softmax_bwd<8, FEAT><<<grid, kBwdBlock, 0, s>>>(a); break;
+    default: k_softmax_bwd<16, FEAT><<<grid, kBwdBlock, 0, s>>>(a); break;
+    }
+}
+
+// ---- the feature part (sections 1d and 2d) ----------------------------------------------------------------------------------
+// gb[i][c] += scale * <row_i, val[v_ic]> for every point i < n_points[f] and corner c: a slice without the sum over the corners.
+// A row is G lanes as in k_softmax_bwd (lane c of the row holds labels 4c .. 4c+3); every id first, then every gather, then the
+// dot products, each summed over the labels in order 0 .. L-1.  row == null: all ones (the norm part, L = 1).
+struct CornerArgs {
+    const int *n_points;
+    int L;
+    size_t fs;                   // floats between frames of row
+    const float *row;            // [F][.][L]
+    const float *val;            // the kernel's blurred values (launch_filter / launch_filter_values1)
+    float scale;
+    float *gb;                   // [F][Epad]
+};
+
+template <int G>
+__global__ void __launch_bounds__(kBwdBlock) k_corner_dot(KernelDev kd, CornerArgs a)
+{
+    const int f = blockIdx.y;
+    const int N = a.n_points[f], L = a.L, D1 = kd.D1;
+    const int lane = threadIdx.x & 63;
+    const int sub = lane % G, first = lane - sub;
+    const int i = blockIdx.x * (kBwdBlock / G) + (int)threadIdx.x / G;
+    const bool live = i < N;
+    const int l0 = sub * 4;
+    const size_t e0 = (size_t)f * kd.Epad + (size_t)(live ? i : 0) * D1;
+    const float *vf = a.val + (size_t)f * kd.vstride + kd.vbase + l0;
+    bool has[4];
+    float r[4];
+    int o[kMaxD + 1];
+    float x[kMaxD + 1][4];
+#pragma unroll
+    for (int j = 0; j <= kMaxD; ++j)
+        if (j < D1) o[j] = live ? kd.offset[e0 + j] : 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        has[u] = live && l0 + u < L;
+        r[u] = has[u] ? (a.row ? a.row[f * a.fs + (size_t)i * L + l0 + u] : 1.0f) : 0.0f;
+    }
+#pragma unroll
+    for (int j = 0; j <= kMaxD; ++j)
+        if (j < D1) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) x[j][u] = has[u] ? vf[(long)o[j] * L + u] : 0.0f;
+        }
+#pragma unroll
+    for (int j = 0; j <= kMaxD; ++j)
+        if (j < D1) {                                       // (uniform: the shuffles of the row sum see every lane)
+            float v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = r[u] * x[j][u];
+            const float sj = row_sum_ordered<G>(v, L, first);
+            if (live && sub == 0) a.gb[e0 + j] = a.gb[e0 + j] + a.scale * sj;
+        }
+}
+
+void launch_corner_dot(const KernelDev &kd, const CrfDev &c, int rows, int L, const float *row, size_t fs, const float *val, float scale,
+                       float *gb, hipStream_t s)
+{
+    CornerArgs a{c.n_points, L, fs, row, val, scale, gb};
+    const int G = bwd_lanes(L);
+    const dim3 grid((unsigned)std::max(backward_blocks(rows, L), 1), (unsigned)c.F);
+    switch (G) {
+    case 1: k_corner_dot<1><<<grid, kBwdBlock, 0, s>>>(kd, a); break;
+    case 2: k_corner_dot<2><<<grid, kBwdBlock, 0, s>>>(kd, a); break;
+    case 4: k_corner_dot<4><<<grid, kBwdBlock, 0, s>>>(kd, a); break;
+    case 8: k_corner_dot<8><<<grid, kBwdBlock, 0, s>>>(kd, a); break;
+    default: k_corner_dot<16><<<grid, kBwdBlock, 0, s>>>(kd, a); break;
+    }
+}
+
+// gn[i] <- a_i = -n_i^2 gn[i]: dL/d Phi_k(1)_i, the input of the norm part's filter pair
+__global__ void __launch_bounds__(kBwdBlock) k_norm_adjoint(KernelDev kd, const int *__restrict__ n_points, float *__restrict__ gn)
+{
+    const int f = blockIdx.y;
+    const int i = blockIdx.x * kBwdBlock + threadIdx.x;
+    if (i >= n_points[f]) return;
+    const float n = kd.norm[(size_t)f * kd.maxN + i];
+    float *g = gn + (size_t)f * kd.maxNpad + i;
+    *g = -(n * n) * *g;
+}
+
+// dL/df [F][maxN][D] from dL/db (gb, laid out as KernelDev::bary).  With v_j = (el_j - rem0_j) / (D+1) and p_j = D - rank_j, corner
+// q receives +v of the coordinate with p = q and -v of the one with p = q - 1, cell D+1 folding into corner 0 (point_record), so
+// dL/dv_j = gb[p_j] - gb[(p_j + 1) mod (D+1)]; el_0 = sum_m cf_m, el_j = sum_{m >= j} cf_m - j cf_{j-1}, cf_m = f_m scale_m, so
+// dL/df_m = scale_m ((dL/del_0 + .. + dL/del_m) - (m+1) dL/del_{m+1}).  The simplex is the build's (lattice_simplex on the same
+// features: the same ranks).  Rows [n_points[f], rows) are written 0.
+template <int D>
+__global__ void __launch_bounds__(kBwdBlock) k_corner_to_feature(KernelDev kd, const int *__restrict__ n_points, int rows,
+                                                               const float *__restrict__ gb, float *__restrict__ out)
+{
+    constexpr int D1 = D + 1;
+    const int f = blockIdx.y;
+    const int i = blockIdx.x * kBwdBlock + threadIdx.x;
+    if (i >= rows) return;
+    float *op = out + ((size_t)f * kd.maxN + i) * D;
+    if (i >= n_points[f]) {
+#pragma unroll
+        for (int m = 0; m < D; ++m) op[m] = 0.0f;
+        return;
+    }
+    float feat[D], g[D1];
+    const float *fp = kd.feat + ((size_t)f * kd.maxN + i) * D;
+    const float *gp = gb + (size_t)f * kd.Epad + (size_t)i * D1;
+#pragma unroll
+    for (int m = 0; m < D; ++m) feat[m] = fp[m];
+#pragma unroll
+    for (int q = 0; q < D1; ++q) g[q] = gp[q];
+    float el[D1], rem0[D1], rank[D1];
+    lattice_simplex<D>(feat, kd.scale, kd.inv_dp1, el, rem0, rank);
+    float gel[D1];
+#pragma unroll
+    for (int j = 0; j < D1; ++j) {
+        const int p = (int)((float)D - rank[j]);
+        const int pn = p == D ? 0 : p + 1;
+        float gp0 = 0.0f, gp1 = 0.0f;                       // (selects, so that g stays in registers)
+#pragma unroll
+        for (int q = 0; q < D1; ++q) {
+            gp0 = q == p ? g[q] : gp0;
+            gp1 = q == pn ? g[q] : gp1;
+        }
+        gel[j] = (gp0 - gp1) * kd.inv_dp1;
+    }
+    float run = gel[0];
+#pragma unroll
+    for (int m = 0; m < D; ++m) {
+        if (m) run += gel[m];
+        op[m] = (run - (float)(m + 1) * gel[m + 1]) * kd.scale[m];
+    }
+}
+
+void launch_corner_to_feature(const KernelDev &kd, const CrfDev &c, int rows, const float *gb, float *out, hipStream_t s)
+{
+    const dim3 grid((unsigned)std::max((rows + kBwdBlock - 1) / kBwdBlock, 1), (unsigned)c.F);
+    switch (kd.d) {
+    case 1: k_corner_to_feature<1><<<grid, kBwdBlock, 0, s>>>(kd, c.n_points, rows, gb, out); break;
+    case 2: k_corner_to_feature<2><<<grid, kBwdBlock, 0, s>>>(kd, c.n_points, rows, gb, out); break;
+    case 3: k_corner_to_feature<3><<<grid, kBwdBlock, 0, s>>>(kd, c.n_points, rows, gb, out); break;
+    case 4: k_corner_to_feature<4><<<grid, kBwdBlock, 0, s>>>(kd, c.n_points, rows, gb, out); break;
+    case 5: k_corner_to_feature<5><<<grid, kBwdBlock, 0, s>>>(kd, c.n_points, rows, gb, out); break;
+    case 6: k_corner_to_feature<6><<<grid, kBwdBlock, 0, s>>>(kd, c.n_points, rows, gb, out); break;
+    case 7: k_corner_to_feature<7><<<grid, kBwdBlock, 0, s>>>(kd, c.n_points, rows, gb, out); break;
+    case 8: k_corner_to_feature<8><<<grid, kBwdBlock, 0, s>>>(kd, c.n_points, rows, gb, out); break;
+    default: break;
     }
 }
 
@@ -237,7 +415,7 @@ size_t backward_bytes(size_t slice, int F, int rows, int L, int K, int T)
 }
 
 void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int rows, int T, float relax, const BackwardArea &ar,
-                           float *grad_unary, float *grad_weights, hipStream_t s)
+                           float *grad_unary, float *grad_weights, hipStream_t s, float *const *grad_features)
 {
     const int K = c.K, L = c.L, F = c.F;
     const size_t slice = ar.slice, fs = (size_t)c.maxN * L;
@@ -258,16 +436,34 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
         a.norm[k] = kds[k].norm;
         a.w[k] = wk.w[k] = kds[k].w;
     }
+    // the feature part: terms with a gradient array (T >= 1; the caller has zeroed their ar.gb / ar.gn)
+    bool feat = false;
+    float *gf[kBwdMaxK] = {};
+    for (int k = 0; k < K && grad_features && T >= 1; ++k)
+        if (grad_features[k]) {
+            gf[k] = grad_features[k];
+            a.gn[k] = ar.gn[k];
+            a.gnstride = kds[k].maxNpad;
+            feat = true;
+        }
     const dim3 cgrid((unsigned)std::max<size_t>(((size_t)rows * L + kBwdBlock - 1) / kBwdBlock, 1), (unsigned)F);
     for (int t = T; t >= 1; --t) {
         const float *qprev = ar.hist + (size_t)(t - 1) * slice;
-        for (int k = 0; k < K; ++k) launch_filter(kds[k], c, maxV[k], qprev, ar.phi + k * slice, 0, s);
+        const float *val[kBwdMaxK];                        // (B S Q_{t-1}) of every term, in the term's own value buffer
+        for (int k = 0; k < K; ++k) launch_filter(kds[k], c, maxV[k], qprev, ar.phi + k * slice, 0, s, 0, &val[k]);
         a.K = K;
         a.relax = relax;
         a.first = t == T;
         a.partial = K ? ar.partial + (size_t)(t - 1) * K * F * nblk : nullptr;
-        launch_softmax_bwd(a, F, s);
-        for (int k = 0; k < K; ++k) launch_filter(kds[k], c, maxV[k], ar.phi + k * slice, ar.phi + k * slice, 0, s, 1);
+        if (feat) launch_softmax_bwd<true>(a, F, s);
+        else launch_softmax_bwd<false>(a, F, s);
+        for (int k = 0; k < K; ++k) {
+            const float cs = kds[k].alpha * kds[k].w;
+            if (gf[k]) launch_corner_dot(kds[k], c, rows, L, ar.phi + k * slice, fs, val[k], cs, ar.gb[k], s);    // slice side
+            const float *valt;                             // (B^T S n_k gamma_t)
+            launch_filter(kds[k], c, maxV[k], ar.phi + k * slice, ar.phi + k * slice, 0, s, 1, &valt);
+            if (gf[k]) launch_corner_dot(kds[k], c, rows, L, qprev, fs, valt, cs, ar.gb[k], s);                    // splat side
+        }
         k_bwd_combine<<<cgrid, kBwdBlock, 0, s>>>(c.n_points, L, K, ar.phi, slice, fs, wk, 1.0f - relax, ar.G);
     }
     // dL/dU -= P_0 (G_0 - <G_0, P_0>), P_0 = Q_0 = softmax(-U)
@@ -275,7 +471,18 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
     a.relax = 1.0f;
     a.first = T == 0;
     a.partial = nullptr;
-    launch_softmax_bwd(a, F, s);
+    launch_softmax_bwd<false>(a, F, s);
+    // the norm part, <a_k, Phi_k(1)> with a_k = -n_k^2 g_n[k] (value width 1), and dL/db -> dL/df
+    for (int k = 0; k < K; ++k) {
+        if (!gf[k]) continue;
+        const KernelDev &kd = kds[k];
+        k_norm_adjoint<<<dim3((unsigned)std::max((rows + kBwdBlock - 1) / kBwdBlock, 1), (unsigned)F), kBwdBlock, 0, s>>>(kd, c.n_points, ar.gn[k]);
+        const float *ones = launch_filter_values1(kd, c, maxV[k], nullptr, 0, s, 0);
+        launch_corner_dot(kd, c, rows, 1, ar.gn[k], (size_t)kd.maxNpad, ones, kd.alpha, ar.gb[k], s);
+        const float *adj = launch_filter_values1(kd, c, maxV[k], ar.gn[k], kd.maxNpad, s, 1);
+        launch_corner_dot(kd, c, rows, 1, nullptr, 0, adj, kd.alpha, ar.gb[k], s);
+        launch_corner_to_feature(kd, c, rows, ar.gb[k], gf[k], s);
+    }
     if (grad_weights && K)
         k_bwd_reduce<<<dim3((unsigned)K, (unsigned)F), kBwdBlock, 0, s>>>(ar.partial, c.n_points, K, T, kBwdBlock / bwd_lanes(L), nblk,
                                                                        grad_weights);

@@ -2415,7 +2415,7 @@ void launch_step_init(const CrfDev &c, float *out, hipStream_t s)
 // out (+)= [w * norm *] compute(in) with value width c.L: PairwisePotential::apply (accumulate = 1, pairwise3d.h:73-78)
 // or the bare PermutohedralLatticeCPU::compute (accumulate = 0, permutohedral_cpu.h:634-699); reverse = 1: its transpose (engine.h)
 void launch_filter(const KernelDev &kd, const CrfDev &c, int maxV, const float *in, float *out, int accumulate, hipStream_t s,
-                   int reverse)
+                   int reverse, const float **blurred)
 {
     const int L = c.L;
     launch_splat(kd, in, c.maxN * L, L, c.F, maxV, s);
@@ -2424,6 +2424,17 @@ void launch_filter(const KernelDev &kd, const CrfDev &c, int maxV, const float *
     CrfDev c2 = c;
     c2.next = out;
     k_slice<<<grid_for((long)c.maxN * L, c.F), kBlock, 0, s>>>(kd, c2, res, L, accumulate ? SLICE_APPLY : SLICE_PLAIN);
+    if (blurred) *blurred = res;
+}
+
+// the splat and the blur passes of a width-1 filter without the slice (engine.h)
+const float *launch_filter_values1(const KernelDev &kd, const CrfDev &c, int maxV, const float *in, int in_stride, hipStream_t s,
+                                   int reverse)
+{
+    launch_splat(kd, in, in_stride, 1, c.F, maxV, s);
+    const float *res;
+    filter_passes(kd, c.F, maxV, 1, s, &res, reverse);
+    return res;
 }
 
 }  // namespace lccrf
