@@ -319,6 +319,59 @@ int  lccrf_inference_backward_features(lccrf_handle h, int n_iterations, float r
                                        float *d_grad_weights, float *const *d_grad_features);
 
 /* ======================================================================================
+ * 1e. Label-compatibility matrices -- a per-term matrix mu_k [L][L] in place of the Potts term's identity: the semimetric / matrix
+ *     compatibilities of the dense-CRF formulation, the learnt compatibility transform of CRF-as-RNN
+ *     (lc-crf-slam_amd/autograd.py: mean_field_compat, CompatMeanFieldCRF).  Added WITHOUT a step of LCCRF_ABI_VERSION (it stays
+ *     3): probe for these three by symbol.
+ *
+ * Meaning.  Term k with matrix mu_k contributes
+ *      next[i][l] += w_k . n_k[i] . sum_{l'} mu_k[l][l'] . Phi_k(Q)[i][l']
+ * where a Potts term adds w_k . n_k[i] . Phi_k(Q)[i][l] (PairwisePotential::apply, pairwise3d.h:73-78).  Lattice, norm and weight
+ * are those of the Potts term.  Arithmetic, per point and label, in fp32 with every product and every sum rounded on its own (no
+ * FMA):   s = 0;  for l' = 0 .. L-1:  s = s + mu[l][l'] * t[l'];   next = base + w * norm * s,   t[l'] the sliced value the Potts
+ * term forms.  A term whose matrix is the identity therefore gives, bit for bit, what the term gives without a matrix.
+ *
+ * Honoured by lccrf_inference (locality mode at >= 8192 points included), lccrf_start_inference / lccrf_step_inference,
+ * lccrf_pairwise_apply / _device (the `apply` of that term), lccrf_inference_backward (dL/dU and dL/dw are then those of the forward
+ * with the matrices) and lccrf_inference_backward_compat.  While any term of a handle has a matrix, inference runs on the streaming
+ * engine -- the one-launch frame kernel and the fused engine hard-wire Potts -- with the matrix applied inside the slice kernel,
+ * which takes the Potts slice kernel's place: the step issues no launch more than the streaming engine's general, L-label step
+ * (at L = 2 that is more than the two-label specialisation issues).  Not covered: the batch API has no setter;
+ * lccrf_inference_backward_features on a handle with any matrix returns LCCRF_E_STATE and leaves the handle as it was; the C++
+ * mirrors (lccrf_densecrf.hpp, lccrf_densecrf_gpu.hpp) are unchanged.                                                          */
+
+/* compat: HOST [L][L], row-major (row = the label that receives, column = the label of the filtered distribution), copied during
+ * the call and uploaded on the handle's stream; NULL removes the matrix (the term is Potts again).  Entries must be finite and
+ * `kernel` a term of the handle, else LCCRF_E_INVALID.  May be called before or after the lattices are built and between
+ * inferences: no lattice, norm or prepared launch record changes, and once the last matrix is removed the handle takes the fast
+ * engines again and returns the bits it returned before.  A handle from lccrf_create -- a recycled one too -- has no matrices.  */
+int  lccrf_set_pairwise_compatibility(lccrf_handle h, int kernel, const float *compat);
+/* *is_set = 1 if term `kernel` has a matrix, else 0; compat_out (HOST [L][L], may be NULL) receives it -- the identity for a Potts
+ * term.  No device work.                                                                                                        */
+int  lccrf_get_pairwise_compatibility(lccrf_handle h, int kernel, float *compat_out, int *is_set);
+/* lccrf_inference_backward plus d_grad_compat, DEVICE [K][L][L] (overwritten) = dL/dmu_k.  With section 1c's notation and
+ * Phi~_k = Phi_k(Q_{t-1}):
+ *      x_t               = -U + sum_k w_k n_k . (Phi~_k mu_k^T)
+ *      dL/dw_k          += sum_{i,l} gamma_t[i][l] . n_k[i] . sum_{l'} mu_k[l][l'] Phi~_k[i][l']
+ *      dL/dmu_k[l][l']  += sum_i w_k . gamma_t[i][l] . n_k[i] . Phi~_k[i][l']
+ *      G_{t-1}           = (1-r) G_t + sum_k w_k Phi_k^T( n_k . (mu_k^T gamma_t) )
+ * For a term without a matrix d_grad_compat[k] is the derivative at mu_k = I (where learning starts from a Potts model).  At
+ * n_iterations = 0 it is exactly 0.  d_grad_compat == NULL makes the call lccrf_inference_backward; d_grad_unary and d_grad_weights
+ * may be NULL otherwise; they receive the bits lccrf_inference_backward gives on the same handle.  Everything else is section 1c's
+ * contract: self-contained, device arrays checked as in section 1b, on the handle's stream, Q afterwards as
+ * lccrf_inference(h, T, 0, relax) leaves it, the same errors.
+ *   - Deterministic: no float atomics.  A frame's points are cut into C = min(ceil(N / 256), 128) contiguous chunks, one workgroup
+ *     each; an entry of a chunk's partial has one owner and is added to in the order of the points, t = T .. 1, and the C partials
+ *     are summed in order: the same bits from run to run.
+ *   - Launches: per iteration and term one kernel more than section 1c (mu^T gamma and the partials of dL/dmu), one reduction at
+ *     the end.
+ *   - Memory: section 1c's area grows by 4 * (N4*L + K*C*L*L) bytes (gamma_t and the partials), plus 4 * N4*L when d_grad_unary
+ *     is NULL: 4 * (N4*L*(T + K + 2) + max(T,1)*K*B + K*C*L*L) bytes in all (320 x 240, L = 21, K = 2, T = 10: 90 MB + 0.5 MB).
+ *     lccrf_inference_backward on a handle with a matrix takes the same area.  Allocated as section 1c's.                      */
+int  lccrf_inference_backward_compat(lccrf_handle h, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
+                                     float *d_grad_weights, float *d_grad_compat);
+
+/* ======================================================================================
  * 2. Batch API -- many independent frames in flight on one GPU.
  *    Every frame is one CRF of the object API; frames never interact.  Inputs may be
  *    handed over as host buffers (uploaded) or bound as DEVICE pointers (zero copy), so

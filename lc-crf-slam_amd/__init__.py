@@ -118,6 +118,9 @@ def lib():
     L.lccrf_set_pairwise_weight.argtypes = [vp, C.c_int, C.c_float]
     L.lccrf_inference_backward.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp]
     L.lccrf_inference_backward_features.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, C.POINTER(vp)]
+    L.lccrf_set_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p]
+    L.lccrf_get_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p, C.POINTER(C.c_int)]
+    L.lccrf_inference_backward_compat.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, vp]
     L.lccrf_batch_create.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(BatchDesc)]
     L.lccrf_batch_destroy.argtypes = [vp]
     L.lccrf_batch_destroy.restype = None
@@ -364,6 +367,31 @@ class DenseCRFHIP:
         entries (that term is skipped); d_grad_unary / d_grad_weights may be None (include/lccrf.h section 1d)."""
         _check(lib().lccrf_inference_backward_features(self.h, int(n_iterations), float(relax), C.c_void_p(d_grad_prob),
                                                        _addr(d_grad_unary), _addr(d_grad_weights), _addr_list(d_grad_features)))
+
+    # -- label-compatibility matrices (include/lccrf.h section 1e) -----------------------------------------------------------
+    def set_pairwise_compatibility(self, k, compat):
+        """The [L][L] matrix mu of term k: next[i][l] += w * norm[i] * sum_l' mu[l][l'] * Phi(Q)[i][l'].  None: Potts again."""
+        if compat is None:
+            _check(lib().lccrf_set_pairwise_compatibility(self.h, int(k), None))
+            return
+        m = _f32(compat).reshape(-1)
+        if m.size != self.L * self.L:
+            raise ValueError("compat must have L*L entries")
+        _check(lib().lccrf_set_pairwise_compatibility(self.h, int(k), _p(m, _f32p)))
+
+    def get_pairwise_compatibility(self, k):
+        """(matrix [L][L], is_set) of term k; the identity for a term without a matrix."""
+        out = np.empty((self.L, self.L), np.float32)
+        flag = C.c_int(0)
+        _check(lib().lccrf_get_pairwise_compatibility(self.h, int(k), _p(out, _f32p), C.byref(flag)))
+        return out, bool(flag.value)
+
+    def inference_backward_compat_device(self, n_iterations, relax, d_grad_prob, d_grad_unary=None, d_grad_weights=None,
+                                         d_grad_compat=None):
+        """inference_backward_device plus dL/dmu: d_grad_compat is the device address of a [K][L][L] array (None: the call is
+        inference_backward_device); d_grad_unary / d_grad_weights may then be None."""
+        _check(lib().lccrf_inference_backward_compat(self.h, int(n_iterations), float(relax), C.c_void_p(d_grad_prob),
+                                                     _addr(d_grad_unary), _addr(d_grad_weights), _addr(d_grad_compat)))
 
     # -- results -----------------------------------------------------------------------
     def map(self):

@@ -1,4 +1,4 @@
-"""torch autograd through DenseCRF::inference on the HIP path (include/lccrf.h sections 1c, 1d and 2c).
+"""torch autograd through DenseCRF::inference on the HIP path (include/lccrf.h sections 1c, 1d, 1e and 2c).
 
     Q = mean_field(crf, unary, weights, n_iterations=5, relax=1.0)
     Q.backward(g)      # -> unary.grad = dL/dU, weights.grad = dL/dw
@@ -8,6 +8,9 @@
 
     Q = mean_field_features(unary, [f_0, f_1, ..], weights, n_iterations=5, relax=1.0)        # the features are inputs too
     Q.backward(g)      # -> also f_k.grad = dL/d features [N, d_k] (section 1d); LearnedKernelCRF fits kernel bandwidths with it
+
+    Q = mean_field_compat(crf, unary, weights, compat, n_iterations=5, relax=1.0)             # a [K, L, L] label compatibility
+    Q.backward(g)      # -> also compat.grad = dL/dmu (section 1e); CompatMeanFieldCRF learns it, starting from the Potts model
 
 `crf` is a DenseCRFHIP whose pairwise terms are already added (their features fix the lattices; only the weights are
 inputs here).  Forward: lccrf_set_pairwise_weight + lccrf_set_unary_device + lccrf_inference.  Backward:
@@ -326,3 +329,96 @@ class LearnedKernelCRF(torch.nn.Module):
 
     def forward(self, unary):
         return mean_field_features(unary, self.features(), self.weights, self.n_iterations, self.relax, self.device)
+
+
+class _MeanFieldCompat(torch.autograd.Function):
+    @staticmethod
+    def _arm(crf, weights, compat):
+        for k, w in enumerate(weights.cpu().tolist()):
+            crf.set_pairwise_weight(k, w)
+        m = compat.cpu().numpy()
+        for k in range(m.shape[0]):
+            crf.set_pairwise_compatibility(k, m[k])
+
+    @staticmethod
+    def forward(ctx, crf, unary, weights, compat, n_iterations, relax):
+        if not unary.is_cuda or unary.dtype != torch.float32 or tuple(unary.shape) != (crf.N, crf.L):
+            raise ValueError("unary must be a float32 GPU tensor of shape [%d, %d]" % (crf.N, crf.L))
+        K = len(crf._d)
+        if weights.dtype != torch.float32 or tuple(weights.shape) != (K,):
+            raise ValueError("weights must be a float32 tensor of shape [%d]" % K)
+        if compat.dtype != torch.float32 or tuple(compat.shape) != (K, crf.L, crf.L):
+            raise ValueError("compat must be a float32 tensor of shape [%d, %d, %d]" % (K, crf.L, crf.L))
+        if n_iterations < 0:
+            raise ValueError("n_iterations must be >= 0")
+        dev = unary.device
+        u = unary.detach().contiguous()
+        w, m = weights.detach().clone(), compat.detach().clone().contiguous()
+        cur = torch.cuda.current_stream(dev)
+        ext = _handle_stream(crf, dev)
+        ext.wait_stream(cur)
+        _MeanFieldCompat._arm(crf, w, m)
+        crf.set_unary_device(u.data_ptr())
+        crf.inference(int(n_iterations), False, float(relax))
+        crf.synchronize()                                     # the completion rule of inference() results
+        with torch.cuda.stream(ext):
+            q = _device_view(crf.device_buffers()["current"], (crf.N, crf.L), dev).clone()
+        cur.wait_stream(ext)
+        q.record_stream(cur)
+        ctx.crf, ctx.n_iterations, ctx.relax = crf, int(n_iterations), float(relax)
+        ctx.weights_device, ctx.compat_device = weights.device, compat.device
+        ctx.save_for_backward(u, w, m)
+        return q
+
+    @staticmethod
+    def backward(ctx, grad_q):
+        u, w, m = ctx.saved_tensors
+        crf = ctx.crf
+        dev = u.device
+        g = grad_q.detach().to(device=dev, dtype=torch.float32).contiguous()
+        cur = torch.cuda.current_stream(dev)
+        K, L = int(w.numel()), crf.L
+        grad_u = torch.empty_like(u)
+        grad_w = torch.empty(max(K, 1), dtype=torch.float32, device=dev)
+        grad_m = torch.zeros((max(K, 1), L, L), dtype=torch.float32, device=dev)
+        ext = _handle_stream(crf, dev)
+        ext.wait_stream(cur)
+        # the handle is re-armed with the inputs of this forward (it may have run other inputs since)
+        _MeanFieldCompat._arm(crf, w, m)
+        crf.set_unary_device(u.data_ptr())
+        crf.inference_backward_compat_device(ctx.n_iterations, ctx.relax, g.data_ptr(), grad_u.data_ptr(),
+                                             grad_w.data_ptr() if K else None, grad_m.data_ptr())
+        cur.wait_stream(ext)
+        if K == 0:
+            grad_w = torch.zeros(0, dtype=torch.float32, device=dev)
+        return None, grad_u, grad_w[:K].to(ctx.weights_device), grad_m[:K].to(ctx.compat_device), None, None
+
+
+def mean_field_compat(crf, unary, weights, compat, n_iterations=5, relax=1.0):
+    """mean_field with a label-compatibility matrix per term (include/lccrf.h section 1e): `compat` [K, L, L] (float32, any
+    device), term k adding w_k * norm_k * (Phi_k(Q) @ compat[k].T); differentiable in unary, weights and compat.  The matrices
+    are left set on `crf`."""
+    return _MeanFieldCompat.apply(crf, unary, weights, compat, n_iterations, relax)
+
+
+class CompatMeanFieldCRF(torch.nn.Module):
+    """MeanFieldCRF whose terms carry a learnt label-compatibility matrix: parameters `weights` [K] and `compat` [K, L, L], the
+    latter initialised to identities (the Potts model).  forward(unary [N, L]) -> Q [N, L]."""
+
+    def __init__(self, n_points, n_labels, features, weights, n_iterations=5, relax=1.0, device=0):
+        super().__init__()
+        if len(features) != len(weights):
+            raise ValueError("one weight per feature array")
+        self.crf = _pkg.DenseCRFHIP(n_points, n_labels, device=device)
+        for f, w in zip(features, weights):
+            f = f.detach().cpu().numpy() if isinstance(f, torch.Tensor) else np.asarray(f)
+            self.crf.add_pairwise(np.ascontiguousarray(f, np.float32), float(w))
+        self.weights = torch.nn.Parameter(torch.tensor([float(w) for w in weights], dtype=torch.float32))
+        self.compat = torch.nn.Parameter(torch.eye(n_labels, dtype=torch.float32).repeat(len(weights), 1, 1))
+        self.n_iterations, self.relax = int(n_iterations), float(relax)
+
+    def forward(self, unary):
+        return mean_field_compat(self.crf, unary, self.weights, self.compat, self.n_iterations, self.relax)
+
+    def close(self):
+        self.crf.close()

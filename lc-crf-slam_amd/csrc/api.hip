@@ -177,6 +177,46 @@ struct Engine {
     // demand and freed with the handle's use (recycle) -- a parked handle does not keep it -- or with the batch
     unsigned char *bwd_area = nullptr;
     size_t bwd_area_bytes = 0;
+    // section 1e (object API; a batch has none): the terms' label-compatibility matrices.  One device array for all of them,
+    // allocated by the first setter and kept with the handle; compat_ptr[k] is term k's [L][L] slice of it, or null (Potts).
+    // While n_compat > 0 the one-launch frame kernel and the fused engine, which hard-wire Potts, are not taken.
+    float *compat_dev = nullptr;       // [LCCRF_MAX_KERNELS][L][L]
+    float *compat_host = nullptr;      // pinned, the same shape: the matrices as set (the getter's answer and the uploads' source)
+    hipEvent_t compat_ev = nullptr;    // behind the last upload: a setter waits for it before it rewrites a source that may be in flight
+    const float *compat_ptr[LCCRF_MAX_KERNELS] = {};
+    int n_compat = 0;
+    bool fused_fits = false;           // learn_sizes(): the lattices now in HBM fit the fused engine
+    const float *const *compat_arg() const { return n_compat ? compat_ptr : nullptr; }
+    void choose_sized_engine() { sized_engine = fused_fits && !n_compat ? 2 : 1; }
+    void clear_compat()
+    {
+        for (int k = 0; k < LCCRF_MAX_KERNELS; ++k) compat_ptr[k] = nullptr;
+        n_compat = 0;
+        choose_sized_engine();
+    }
+    // m: host [L][L] (finite, checked by the caller) or null.  Touches no lattice, norm or prepared record.
+    int set_compat(int k, const float *m)
+    {
+        const size_t ll = (size_t)L * L;
+        if (m) {
+            if (!compat_dev) {
+                int rc = mem.alloc_pinned(&compat_host, (size_t)LCCRF_MAX_KERNELS * ll);
+                if (!rc) rc = mem.alloc(&compat_dev, (size_t)LCCRF_MAX_KERNELS * ll);
+                if (rc) { compat_dev = nullptr; return rc; }
+                HIP_TRY(hipEventCreateWithFlags(&compat_ev, hipEventDisableTiming));
+                HIP_TRY(hipEventRecord(compat_ev, stream));
+            }
+            HIP_TRY(hipEventSynchronize(compat_ev));        // (an earlier upload may still be reading the pinned copy)
+            memcpy(compat_host + k * ll, m, ll * sizeof(float));   // (the caller's array is free again when the call returns)
+            HIP_TRY(hipMemcpyAsync(compat_dev + k * ll, compat_host + k * ll, ll * sizeof(float), hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipEventRecord(compat_ev, stream));
+        }
+        const float *p = m ? compat_dev + k * ll : nullptr;
+        n_compat += (p != nullptr) - (compat_ptr[k] != nullptr);
+        compat_ptr[k] = p;
+        choose_sized_engine();
+        return LCCRF_OK;
+    }
     void free_backward_area()
     {
         if (!bwd_area) return;
@@ -207,16 +247,18 @@ struct Engine {
     // iteration in arrays of `slice` floats, dL/dQ_T copied in, then the reverse sweep over frames of up to `rows` points.
     // grad_features (sections 1d / 2d): K device pointers or null; grad_unary may then be null (the area holds one more array).
     // backward_need() is the area this takes.
-    size_t backward_need(size_t slice, int rows, int T, bool scratch_unary, float *const *grad_features) const
+    size_t backward_need(size_t slice, int rows, int T, bool scratch_unary, float *const *grad_features, bool compat_part = false) const
     {
         const int K = (int)kernels.size();
         size_t extra = scratch_unary ? slice : 0;
+        if (compat_part) extra += backward_compat_floats(slice, F, rows, L, K);
         for (int k = 0; k < K && grad_features; ++k)
             if (grad_features[k]) extra += backward_feature_floats(kernels[k].dev, F);
         return backward_bytes(slice, F, rows, L, K, T) + extra * sizeof(float);
     }
+    // compat_part (section 1e): the sweep honours the terms' matrices and, with grad_compat [K][L][L], returns dL/dmu
     int backward(size_t slice, size_t count, int rows, int T, float relax, const float *grad_prob, float *grad_unary, float *grad_weights,
-                 float *const *grad_features = nullptr)
+                 float *const *grad_features = nullptr, bool compat_part = false, float *grad_compat = nullptr)
     {
         const int K = (int)kernels.size();
         BackwardArea ar{};
@@ -237,6 +279,8 @@ struct Engine {
             if (count) HIP_TRY(hipMemcpyAsync(ar.hist + (size_t)t * slice, crf.Q, count * sizeof(float), hipMemcpyDeviceToDevice, stream));
             if ((rc = step(relax))) return rc;
         }
+        if (grad_compat && K && (!count || T == 0))       // nothing depends on the matrices: exactly 0
+            HIP_TRY(hipMemsetAsync(grad_compat, 0, (size_t)K * L * L * sizeof(float), stream));
         if (!count) {                                     // nothing to differentiate: dL/dw = 0
             if (grad_weights && K) HIP_TRY(hipMemsetAsync(grad_weights, 0, (size_t)F * K * sizeof(float), stream));
             return LCCRF_OK;
@@ -253,8 +297,13 @@ struct Engine {
             HIP_TRY(hipMemsetAsync(extra, 0, backward_feature_floats(kd, F) * sizeof(float), stream));
             extra += backward_feature_floats(kd, F);
         }
+        if (compat_part) {
+            ar.gam = extra;
+            ar.cpart = extra + slice;
+        }
         HIP_TRY(hipMemcpyAsync(ar.G, grad_prob, count * sizeof(float), hipMemcpyDeviceToDevice, stream));
-        launch_backward_sweep(crf, kdevs.data(), maxV.data(), rows, T, relax, ar, grad_unary, grad_weights, stream, grad_features);
+        launch_backward_sweep(crf, kdevs.data(), maxV.data(), rows, T, relax, ar, grad_unary, grad_weights, stream, grad_features,
+                              compat_arg(), grad_compat);
         HIP_TRY(hipGetLastError());
         return LCCRF_OK;
     }
@@ -446,6 +495,9 @@ struct Engine {
         for (auto &e : ev)
             if (e) (void)hipEventDestroy(e);
         if (ev_order) (void)hipEventDestroy(ev_order);
+        if (compat_ev) (void)hipEventDestroy(compat_ev);
+        compat_ev = nullptr;
+        compat_dev = compat_host = nullptr;
         if (lean_prep.ev0) (void)hipEventDestroy(lean_prep.ev0);
         if (lean_prep.ev1) (void)hipEventDestroy(lean_prep.ev1);
         lean_prep = LeanPrep{};
@@ -587,6 +639,7 @@ struct Engine {
         invalidate_lattices();
         engine_pref = 0;
         engine_used = 1;
+        clear_compat();                                   // (the next user's terms start as Potts terms)
         sync_views();
     }
 
@@ -773,9 +826,9 @@ struct Engine {
         sync_views();
         sizes_known = true;
         invalidate_lean_prep();                            // (every path that changes a lattice clears sizes_known and so comes through here)
-        sized_engine = 1;
-        if (engine_pref != 1 && !perm_on && fused_supported(crf, kdevs.data(), maxV.data(), maxRow.data(), &fused_lds)) sized_engine = 2;
-        if (engine_pref == 2 && sized_engine != 2)
+        fused_fits = engine_pref != 1 && !perm_on && fused_supported(crf, kdevs.data(), maxV.data(), maxRow.data(), &fused_lds);
+        choose_sized_engine();
+        if (engine_pref == 2 && !fused_fits)
             return fail(LCCRF_E_CAPACITY, "fused engine requested but the problem does not fit one workgroup's LDS");
         return LCCRF_OK;
     }
@@ -844,7 +897,7 @@ struct Engine {
         rc = learn_sizes();
         if (rc) return rc;
         if ((rc = ensure_unary())) return rc;             // (label-derived energies follow the lattices' point order: re-derived after a re-build)
-        launch_step_stream(crf, kdevs.data(), maxV.data(), relax, stream);
+        launch_step_stream(crf, kdevs.data(), maxV.data(), relax, stream, compat_arg());
         return LCCRF_OK;
     }
 
@@ -852,7 +905,7 @@ struct Engine {
     bool frame_ok() const
     {
         static const bool no_frame = ab_env("LCCRF_NO_FRAME") != nullptr;   // cross-check switch: two-kernel path, same results
-        return !no_frame && engine_pref == 0 && !kernels.empty() && frame_supported(crf, kdevs.data());
+        return !no_frame && engine_pref == 0 && !n_compat && !kernels.empty() && frame_supported(crf, kdevs.data());
     }
 
     // One launch per frame; whether every frame fitted the kernel's LDS plan is known at the next
@@ -982,7 +1035,7 @@ struct Engine {
                 cp.unary = unary_p;
             }
             launch_start(cp, stream);
-            for (int it = 0; it < n_iter; ++it) launch_step_stream(cp, kdevs.data(), maxV.data(), relax, stream);
+            for (int it = 0; it < n_iter; ++it) launch_step_stream(cp, kdevs.data(), maxV.data(), relax, stream, compat_arg());
             launch_permute_rows(crf, crf.Q, Qp, L, 0, stream);
             if (with_map) launch_map(crf, stream);
             started = true;
@@ -1011,7 +1064,7 @@ struct Engine {
             started = true;
         } else {
             if ((rc = start())) return rc;
-            for (int it = 0; it < n_iter; ++it) launch_step_stream(crf, kdevs.data(), maxV.data(), relax, stream);
+            for (int it = 0; it < n_iter; ++it) launch_step_stream(crf, kdevs.data(), maxV.data(), relax, stream, compat_arg());
             if (with_map) launch_map(crf, stream);
         }
         HIP_TRY(hipGetLastError());
@@ -1640,7 +1693,7 @@ static int pairwise_apply_on(lccrf_crf *h, int kernel, float *d_out, const float
     if (!rc) rc = e.ensure_plain();
     if (!rc) rc = e.learn_sizes();                        // builds the lattice if it only exists as staged features
     if (rc || !h->N) return rc;
-    launch_filter(e.kdevs[kernel], e.crf, e.maxV[kernel], d_in, d_out, accumulate, e.stream);
+    launch_filter(e.kdevs[kernel], e.crf, e.maxV[kernel], d_in, d_out, accumulate, e.stream, 0, nullptr, e.compat_ptr[kernel]);
     HIP_TRY(hipGetLastError());
     return LCCRF_OK;
 }
@@ -2104,8 +2157,9 @@ int lccrf_inference_backward(lccrf_handle h, int n_iterations, float relax, cons
     { int rl = e.resolve_late(); if (rl) return rl; }
     // the area first: a handle that cannot have it is left as it was
     const size_t ns = backward_stride(h->N, e.L);
-    { int ra = e.ensure_backward_area(backward_bytes(ns, 1, h->N, e.L, K, T)); if (ra) return ra; }   // (the phantom rows stay zero: engine.h)
-    return e.backward(ns, nl, h->N, T, relax, d_grad_prob, d_grad_unary, d_grad_weights);
+    const bool cp = e.n_compat > 0;                       // (section 1e: the gradients of the forward with the matrices)
+    { int ra = e.ensure_backward_area(e.backward_need(ns, h->N, T, false, nullptr, cp)); if (ra) return ra; }   // (the phantom rows stay zero: engine.h)
+    return e.backward(ns, nl, h->N, T, relax, d_grad_prob, d_grad_unary, d_grad_weights, nullptr, cp);
 }
 
 // --------------------------------------------------------------------------------------
@@ -2116,6 +2170,7 @@ int lccrf_inference_backward_features(lccrf_handle h, int n_iterations, float re
 {
     CHECK_H(h);
     Engine &e = h->eng;
+    if (e.n_compat) return fail(LCCRF_E_STATE, "feature gradients are not available while a term has a label-compatibility matrix");
     if (n_iterations < 0) return fail(LCCRF_E_INVALID, "n_iterations < 0");
     if (!std::isfinite(relax)) return fail(LCCRF_E_INVALID, "relax must be finite");
     const int K = (int)e.kernels.size(), T = n_iterations;
@@ -2133,6 +2188,53 @@ int lccrf_inference_backward_features(lccrf_handle h, int n_iterations, float re
     const size_t ns = backward_stride(h->N, e.L);
     { int ra = e.ensure_backward_area(e.backward_need(ns, h->N, T, !d_grad_unary, d_grad_features)); if (ra) return ra; }
     return e.backward(ns, nl, h->N, T, relax, d_grad_prob, d_grad_unary, d_grad_weights, d_grad_features);
+}
+
+// --------------------------------------------------------------------------------------
+// section 1e: label-compatibility matrices of the pairwise terms
+
+int lccrf_set_pairwise_compatibility(lccrf_handle h, int kernel, const float *compat)
+{
+    CHECK_H(h);
+    CHECK_K(h, kernel);
+    Engine &e = h->eng;
+    for (int i = 0; compat && i < e.L * e.L; ++i)
+        if (!std::isfinite(compat[i])) return fail(LCCRF_E_INVALID, "compat[%d][%d] is not finite", i / e.L, i % e.L);
+    { int rl = e.resolve_late(); if (rl) return rl; }   // (a pending one-launch inference may still be re-run: as a Potts model)
+    return e.set_compat(kernel, compat);
+}
+
+int lccrf_get_pairwise_compatibility(lccrf_handle h, int kernel, float *compat_out, int *is_set)
+{
+    CHECK_H(h);
+    CHECK_K(h, kernel);
+    const Engine &e = h->eng;
+    const bool set = e.compat_ptr[kernel] != nullptr;
+    if (is_set) *is_set = set ? 1 : 0;
+    for (int i = 0; compat_out && i < e.L * e.L; ++i)     // (a Potts term reads as the identity it is)
+        compat_out[i] = set ? e.compat_host[(size_t)kernel * e.L * e.L + i] : (i / e.L == i % e.L ? 1.0f : 0.0f);
+    return LCCRF_OK;
+}
+
+int lccrf_inference_backward_compat(lccrf_handle h, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
+                                    float *d_grad_weights, float *d_grad_compat)
+{
+    if (!d_grad_compat) return lccrf_inference_backward(h, n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights);
+    CHECK_H(h);
+    Engine &e = h->eng;
+    if (n_iterations < 0) return fail(LCCRF_E_INVALID, "n_iterations < 0");
+    if (!std::isfinite(relax)) return fail(LCCRF_E_INVALID, "relax must be finite");
+    const int K = (int)e.kernels.size(), T = n_iterations;
+    const size_t nl = (size_t)h->N * e.L;
+    { int rc = check_device_array(h, d_grad_prob, nl * sizeof(float), "d_grad_prob"); if (rc) return rc; }
+    if (d_grad_unary) { int rc = check_device_array(h, d_grad_unary, nl * sizeof(float), "d_grad_unary"); if (rc) return rc; }
+    if (d_grad_weights) { int rc = check_device_array(h, d_grad_weights, (size_t)K * sizeof(float), "d_grad_weights"); if (rc) return rc; }
+    if (K) { int rc = check_device_array(h, d_grad_compat, (size_t)K * e.L * e.L * sizeof(float), "d_grad_compat"); if (rc) return rc; }
+    if (!e.unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
+    { int rl = e.resolve_late(); if (rl) return rl; }
+    const size_t ns = backward_stride(h->N, e.L);
+    { int ra = e.ensure_backward_area(e.backward_need(ns, h->N, T, !d_grad_unary, nullptr, true)); if (ra) return ra; }
+    return e.backward(ns, nl, h->N, T, relax, d_grad_prob, d_grad_unary, d_grad_weights, nullptr, true, d_grad_compat);
 }
 
 // --------------------------------------------------------------------------------------

@@ -178,8 +178,10 @@ void launch_norm(const KernelDev &kd, const CrfDev &c, int maxV, hipStream_t s);
 struct UnaryTable { float v[2 * LCCRF_MAX_LABELS + 1]; };
 void launch_unary_from_label_tbl(const CrfDev &c, const int16_t *label, const UnaryTable &tbl, hipStream_t s);
 void launch_start(const CrfDev &c, hipStream_t s);
+// compat (include/lccrf.h section 1e; null: every term is Potts): K device pointers, compat[k] the [L][L] label-compatibility matrix
+// of term k or null.  The batch paths pass null.
 void launch_step_stream(const CrfDev &c, const KernelDev *kds, const int *maxV, float relax,
-                        hipStream_t s);
+                        hipStream_t s, const float *const *compat = nullptr);
 void launch_map(const CrfDev &c, hipStream_t s);
 void launch_map_of(const CrfDev &c, const float *prob, int16_t *map, hipStream_t s);
 void launch_exp_and_normalize(const CrfDev &c, const float *in, float *out, float scale, float relax, hipStream_t s);
@@ -188,8 +190,9 @@ void launch_step_init(const CrfDev &c, float *out, hipStream_t s);
 // forward applies (alpha S^T B_d .. B_0 S; every pass is symmetric, their product is not).  `out` may be `in` (the splat reads it first).
 // blurred (optional): receives the kernel's value buffer (val0 or val1) that the slice read -- (B S in)[v][l] at
 // [f * vstride + vbase + v * L + l], valid until the kernel's next splat (the feature gradient's corner dots read it there)
+// compat (accumulate = 1 only): the term's [L][L] label-compatibility matrix or null -- out += w * norm * (compute(in) mu^T)
 void launch_filter(const KernelDev &kd, const CrfDev &c, int maxV, const float *in, float *out, int accumulate, hipStream_t s,
-                   int reverse = 0, const float **blurred = nullptr);
+                   int reverse = 0, const float **blurred = nullptr, const float *compat = nullptr);
 // the same for a value width of 1 and without the slice: in [F][in_stride] (null: all ones, the normalisation's input); returns
 // the blurred values, (B S in)[v] at [f * vstride + vbase + v]
 const float *launch_filter_values1(const KernelDev &kd, const CrfDev &c, int maxV, const float *in, int in_stride, hipStream_t s,
@@ -220,17 +223,26 @@ struct BackwardArea {
     // zeroed by the caller before every sweep
     float *gb[LCCRF_MAX_KERNELS];   // [F][Epad]
     float *gn[LCCRF_MAX_KERNELS];   // [F][maxNpad]
+    // the compatibility part (section 1e), when a term has a matrix or dL/dmu is asked for, else null: gamma_t of the current
+    // iteration, and the per-workgroup partials of dL/dmu accumulated over the iterations -- backward_compat_floats() in all
+    float *gam;           // [slice]
+    float *cpart;         // [K][F][backward_compat_blocks(rows)][L][L]
 };
 int backward_blocks(int n, int L);
 size_t backward_stride(int n, int L);
 size_t backward_bytes(size_t slice, int F, int rows, int L, int K, int T);
+int backward_compat_blocks(int n);
+size_t backward_compat_floats(size_t slice, int F, int rows, int L, int K);
 inline size_t backward_feature_floats(const KernelDev &kd, int F) { return (size_t)F * ((size_t)kd.Epad + kd.maxNpad); }
 // the reverse sweep over the F = c.F frames of up to `rows` points each (the replay has filled ar.hist and ar.G = dL/dQ_T);
 // grad_unary [F][c.maxN][L] (rows [n_points[f], rows) written 0), grad_weights [F][K] or null;
 // grad_features (or null): K pointers, [F][c.maxN][d_k] each or null (rows [n_points[f], rows) written 0) -- for every one given,
 // ar.gb[k] / ar.gn[k] are set.  Without any, the launches are those of sections 1c / 2c.
+// compat (or null): K device pointers, the terms' [L][L] matrices or null; grad_compat (or null): [K][L][L], overwritten (F = 1).
+// With ar.gam set the sweep takes section 1e's form: one k_compat_bwd launch per iteration and term more.
 void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int rows, int T, float relax, const BackwardArea &ar,
-                           float *grad_unary, float *grad_weights, hipStream_t s, float *const *grad_features = nullptr);
+                           float *grad_unary, float *grad_weights, hipStream_t s, float *const *grad_features = nullptr,
+                           const float *const *compat = nullptr, float *grad_compat = nullptr);
 
 // ---- fused build (SLAM sizes; one workgroup per (frame, kernel), hash table in LDS) ------
 bool build_small_supported(const KernelDev *kds, int n, int max_points);

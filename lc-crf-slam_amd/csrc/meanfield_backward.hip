@@ -56,7 +56,11 @@ struct BwdArgs {
     float w[kBwdMaxK];
     float *gn[kBwdMaxK];         // k_softmax_bwd<G, true>: [F][gnstride] per term, or null (BackwardArea::gn)
     int gnstride;
+    const float *compat[kBwdMaxK];   // k_compat_softmax<G>: the term's [L][L] matrix mu_k, or null (Potts)
+    float *gam;                  // ... and [F][maxN][L]: receives gamma_t (phi is left as it came: k_compat_bwd turns it over)
 };
+
+enum { kBwdPlain = 0, kBwdFeat = 1, kBwdCompat = 2 };   // what k_softmax_bwd does besides section 1c's work
 
 // lanes per row: one row per lane up to 4 labels, then four labels per lane over a power-of-two group of lanes
 inline int bwd_lanes(int L) { return L <= 4 ? 1 : L <= 8 ? 2 : L <= 16 ? 4 : L <= 32 ? 8 : 16; }
@@ -82,10 +86,17 @@ __device__ __forceinline__ float row_sum_ordered(const float (&v)[4], int L, int
 //   gU  = -gam (first) or gU - gam
 //   phi_k <- n_k * gam (in place: the transposed filter's input), partial[k][f][block] = sum over the block of n_k * gam * Phi_k
 // K = 0: x = -U (the start, densecrf_base.h:78-80, or a CRF without terms).
-// FEAT: also gn[k][i] += w_k * <gam_i, Phi_k,i> (labels in order) for every term with a gn -- nothing else changes.
-template <int G, bool FEAT>
-__global__ void __launch_bounds__(kBwdBlock) k_softmax_bwd(BwdArgs a)
+// k_softmax_bwd<G, true> (kBwdFeat): also gn[k][i] += w_k * <gam_i, Phi_k,i> (labels in order) for every term with a gn -- nothing else changes.
+// k_compat_softmax<G> (kBwdCompat, section 1e): a term with a matrix enters x and the weight dot as mu_k Phi_k -- per label l the forward's own sum
+// s = 0; s = s + mu[l][l'] * Phi[l'], l' = 0 .. L-1 (k_slice_compat) -- gamma_t goes to a.gam and phi stays Phi_k(Q_{t-1}):
+// k_compat_bwd needs both for dL/dmu and writes the transposed filter's input itself.
+// mu is read from global memory here, L x 4 loads per lane and term, all lanes of a wavefront within a few rows of one matrix of
+// at most 16 KB (cache hits after the first touch): up to eight matrices do not fit this kernel's LDS next to each other, and
+// staging them one by one would put 2 K barriers into a kernel whose rows are otherwise independent.
+template <int G, int MODE>
+__device__ __forceinline__ void softmax_bwd(const BwdArgs &a)
 {
+    constexpr bool FEAT = MODE == kBwdFeat, COMPAT = MODE == kBwdCompat;
     const int f = blockIdx.y;
     const int N = a.n_points[f], L = a.L, K = a.K;
     const int lane = threadIdx.x & 63;
@@ -119,10 +130,22 @@ __global__ void __launch_bounds__(kBwdBlock) k_softmax_bwd(BwdArgs a)
             nk[k] = live ? a.norm[k][(size_t)f * a.nstride + i] : 0.0f;
             const float wn = a.w[k] * nk[k];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                ph[k][u] = has[u] ? a.phi[k * a.slice + q + u] : 0.0f;
-                x[u] = x[u] + wn * ph[k][u];
+            for (int u = 0; u < 4; ++u) ph[k][u] = has[u] ? a.phi[k * a.slice + q + u] : 0.0f;
+            if (COMPAT && a.compat[k]) {                    // (uniform: the shuffles see every lane of the row)
+                const float *mu = a.compat[k];
+                float m[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                for (int t = 0; t < L; ++t) {
+                    const int v = t & 3;
+                    const float src = v == 0 ? ph[k][0] : v == 1 ? ph[k][1] : v == 2 ? ph[k][2] : ph[k][3];
+                    const float pt = G == 1 ? src : __shfl(src, first + (t >> 2), 64);
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) m[u] = m[u] + mu[min(l0 + u, L - 1) * L + t] * pt;
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) ph[k][u] = has[u] ? m[u] : 0.0f;
             }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) x[u] = x[u] + wn * ph[k][u];
         }
     }
     // row maximum (order-free), exponentials, the row sum in label order
@@ -165,12 +188,13 @@ __global__ void __launch_bounds__(kBwdBlock) k_softmax_bwd(BwdArgs a)
         const float gam = a.relax * (p[u] * ((g[u] - ga) - dev));
         if (FEAT) gamv[u] = gam;
         a.gU[q + u] = a.first ? -gam : a.gU[q + u] - gam;
+        if (COMPAT) a.gam[q + u] = gam;
 #pragma unroll
         for (int k = 0; k < kBwdMaxK; ++k)
             if (k < K) {
                 const float gn = nk[k] * gam;
                 wsum[k] += gn * ph[k][u];
-                a.phi[k * a.slice + q + u] = gn;
+                if (!COMPAT) a.phi[k * a.slice + q + u] = gn;
             }
     }
     if (FEAT) {
@@ -204,6 +228,18 @@ __global__ void __launch_bounds__(kBwdBlock) k_softmax_bwd(BwdArgs a)
         for (int w = 0; w < kBwdBlock / 64; ++w) s += red[threadIdx.x][w];
         a.partial[((size_t)threadIdx.x * gridDim.y + f) * gridDim.x + blockIdx.x] = s;
     }
+}
+
+template <int G, bool FEAT>
+__global__ void __launch_bounds__(kBwdBlock) k_softmax_bwd(BwdArgs a)
+{
+    softmax_bwd<G, FEAT ? kBwdFeat : kBwdPlain>(a);
+}
+
+template <int G>
+__global__ void __launch_bounds__(kBwdBlock) k_compat_softmax(BwdArgs a)
+{
+    softmax_bwd<G, kBwdCompat>(a);
 }
 
 // G = keep * G + sum_k w_k * buf_k, element by element (keep = 1 - relax); frame blockIdx.y
@@ -243,11 +279,22 @@ __global__ void __launch_bounds__(kBwdBlock) k_bwd_reduce(const float *__restric
     if (threadIdx.x == 0) out[(size_t)f * K + k] = s[0];
 }
 
-template <bool FEAT>
+template <int MODE>
 void launch_softmax_bwd(const BwdArgs &a, int F, hipStream_t s)
 {
     const int G = bwd_lanes(a.L);
     const dim3 grid((unsigned)std::max(backward_blocks(a.rows, a.L), 1), (unsigned)F);
+    if (MODE == kBwdCompat) {
+        switch (G) {
+        case 1: k_compat_softmax<1><<<grid, kBwdBlock, 0, s>>>(a); break;
+        case 2: k_compat_softmax<2><<<grid, kBwdBlock, 0, s>>>(a); break;
+        case 4: k_compat_softmax<4><<<grid, kBwdBlock, 0, s>>>(a); break;
+        case 8: k_compat_softmax<8><<<grid, kBwdBlock, 0, s>>>(a); break;
+        default: k_compat_softmax<16><<<grid, kBwdBlock, 0, s>>>(a); break;
+        }
+        return;
+    }
+    constexpr bool FEAT = MODE == kBwdFeat;
     switch (G) {
     case 1: k_softmax_bwd<1, FEAT><<<grid, kBwdBlock, 0, s>>>(a); break;
     case 2: k_softmax_bwd<2, FEAT><<<grid, kBwdBlock, 0, s>>>(a); break;
@@ -255,6 +302,99 @@ void launch_softmax_bwd(const BwdArgs &a, int F, hipStream_t s)
     case 8: k_softmax_bwd<8, FEAT><<<grid, kBwdBlock, 0, s>>>(a); break;
     default: k_softmax_bwd<16, FEAT><<<grid, kBwdBlock, 0, s>>>(a); break;
     }
+}
+
+// ---- the compatibility part (section 1e) ---------------------------------------------------------------------------------------
+// One term, behind k_compat_softmax<G>: with y_i = n_k[i] gamma_t[i] and Phi = Phi_k(Q_{t-1}) (phi, as the filter left it)
+//   cpart[f][b][l][l'] (+)= w_k * sum over workgroup b's rows of y_i[l] * Phi_i[l']        the partial of dL/dmu_k (cpart != null)
+//   phi[i][l']           = sum_l mu[l][l'] * y_i[l]  (labels in order; y_i[l'] for a Potts term)   the transposed filter's input
+// A frame's rows are cut into gridDim.x contiguous chunks, one per workgroup, walked in tiles of R = 256 / L rows: lane r * L + l
+// puts y and Phi of row r into LDS, lane p (and p + 256, ...) adds the tile's rows in order to its entries (l, l') of the outer
+// product, kept in registers over the whole chunk, and lane r * L + l' forms row r of mu^T y.  No atomics: an entry has one owner and
+// one order of additions (rows ascending; t = T .. 1 across the sweep's launches), the same bits from run to run.
+constexpr int kCompatMaxBlocks = 128;
+constexpr int kCompatTileB = kBwdBlock + kBwdBlock / 2;   // R * (L | 1) <= 256 + R floats
+constexpr int kCompatPairs = (LCCRF_MAX_LABELS * LCCRF_MAX_LABELS + kBwdBlock - 1) / kBwdBlock;   // entries of mu per lane
+struct CompatArgs {
+    const int *n_points;
+    int L, first;                // first: the sweep's first iteration writes cpart, the others add to it
+    int nstride;
+    size_t fs;
+    const float *gam;            // [F][maxN][L]
+    const float *norm;           // [F][nstride]
+    float *phi;                  // [F][maxN][L]
+    const float *mu;             // [L][L] or null
+    float w;
+    float *cpart;                // [F][gridDim.x][L * L] or null
+};
+
+__global__ void __launch_bounds__(kBwdBlock) k_compat_bwd(CompatArgs a)
+{
+    __shared__ float mu[LCCRF_MAX_LABELS * (LCCRF_MAX_LABELS + 1)];
+    __shared__ float ys[kCompatTileB], ps[kCompatTileB];
+    const int f = blockIdx.y, L = a.L, N = a.n_points[f];
+    const int R = kBwdBlock / L, st = L == 1 ? 1 : (L | 1), tid = threadIdx.x;
+    const int r = tid / L, l = tid - r * L;
+    const int chunk = (N + (int)gridDim.x - 1) / (int)gridDim.x;
+    const int i_begin = min((int)blockIdx.x * chunk, N), i_end = min(i_begin + chunk, N);
+    if (a.mu)
+        for (int idx = tid; idx < L * L; idx += kBwdBlock) {
+            const int x = idx / L;
+            mu[x * st + (idx - x * L)] = a.mu[idx];
+        }
+    float acc[kCompatPairs];
+#pragma unroll
+    for (int j = 0; j < kCompatPairs; ++j) acc[j] = 0.0f;
+    for (int base = i_begin; base < i_end; base += R) {   // (uniform bounds: every lane meets every barrier)
+        const int i = base + r;
+        const bool live = r < R && i < i_end;
+        if (r < R) {
+            const size_t q = f * a.fs + (size_t)(live ? i : 0) * L + l;
+            ys[r * st + l] = live ? a.norm[(size_t)f * a.nstride + i] * a.gam[q] : 0.0f;
+            ps[r * st + l] = live ? a.phi[q] : 0.0f;
+        }
+        __syncthreads();
+        if (a.cpart) {
+            const int nr = min(R, i_end - base);
+#pragma unroll
+            for (int j = 0; j < kCompatPairs; ++j) {
+                const int p = tid + j * kBwdBlock;
+                if (p < L * L) {
+                    const int x = p / L, y = p - x * L;
+                    float s = acc[j];
+                    for (int rr = 0; rr < nr; ++rr) s += ys[rr * st + x] * ps[rr * st + y];
+                    acc[j] = s;
+                }
+            }
+        }
+        if (live) {
+            float o = ys[r * st + l];
+            if (a.mu) {
+                o = 0.0f;
+                for (int x = 0; x < L; ++x) o = o + mu[x * st + l] * ys[r * st + x];
+            }
+            a.phi[f * a.fs + (size_t)i * L + l] = o;
+        }
+        __syncthreads();
+    }
+    if (!a.cpart) return;
+    float *cp = a.cpart + ((size_t)f * gridDim.x + blockIdx.x) * L * L;
+#pragma unroll
+    for (int j = 0; j < kCompatPairs; ++j) {
+        const int p = tid + j * kBwdBlock;
+        if (p < L * L) cp[p] = a.first ? a.w * acc[j] : cp[p] + a.w * acc[j];
+    }
+}
+
+// out[k][l][l'] = sum over the workgroups b = 0 .. B-1, in that order, of cpart[k][0][b][l][l'] (a handle is one frame)
+__global__ void __launch_bounds__(kBwdBlock) k_compat_reduce(const float *__restrict__ cpart, int K, int B, int LL, float *__restrict__ out)
+{
+    const int idx = blockIdx.x * kBwdBlock + threadIdx.x;
+    if (idx >= K * LL) return;
+    const int k = idx / LL, p = idx - k * LL;
+    float s = 0.0f;
+    for (int b = 0; b < B; ++b) s += cpart[((size_t)k * B + b) * LL + p];
+    out[idx] = s;
 }
 
 // ---- the feature part (sections 1d and 2d) ----------------------------------------------------------------------------------
@@ -409,13 +549,21 @@ size_t backward_stride(int n, int L) { return (size_t)((n + 3) & ~3) * L; }
 
 int backward_blocks(int n, int L) { return (n + kBwdBlock / bwd_lanes(L) - 1) / (kBwdBlock / bwd_lanes(L)); }
 
+int backward_compat_blocks(int n) { return std::min(std::max((n + kBwdBlock - 1) / kBwdBlock, 1), kCompatMaxBlocks); }
+
+size_t backward_compat_floats(size_t slice, int F, int rows, int L, int K)
+{
+    return slice + (size_t)K * F * backward_compat_blocks(rows) * L * L;
+}
+
 size_t backward_bytes(size_t slice, int F, int rows, int L, int K, int T)
 {
     return sizeof(float) * (slice * ((size_t)T + K + 1) + (size_t)std::max(T, 1) * K * F * std::max(backward_blocks(rows, L), 1));
 }
 
 void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int rows, int T, float relax, const BackwardArea &ar,
-                           float *grad_unary, float *grad_weights, hipStream_t s, float *const *grad_features)
+                           float *grad_unary, float *grad_weights, hipStream_t s, float *const *grad_features,
+                           const float *const *compat, float *grad_compat)
 {
     const int K = c.K, L = c.L, F = c.F;
     const size_t slice = ar.slice, fs = (size_t)c.maxN * L;
@@ -436,6 +584,11 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
         a.norm[k] = kds[k].norm;
         a.w[k] = wk.w[k] = kds[k].w;
     }
+    // the compatibility part (section 1e): some term has a matrix, or dL/dmu is asked for -- ar.gam (and ar.cpart) are set
+    const bool cmode = ar.gam != nullptr;
+    const int cblk = backward_compat_blocks(rows);
+    for (int k = 0; k < K && cmode; ++k) a.compat[k] = compat ? compat[k] : nullptr;
+    a.gam = ar.gam;
     // the feature part: terms with a gradient array (T >= 1; the caller has zeroed their ar.gb / ar.gn)
     bool feat = false;
     float *gf[kBwdMaxK] = {};
@@ -455,9 +608,15 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
         a.relax = relax;
         a.first = t == T;
         a.partial = K ? ar.partial + (size_t)(t - 1) * K * F * nblk : nullptr;
-        if (feat) launch_softmax_bwd<true>(a, F, s);
-        else launch_softmax_bwd<false>(a, F, s);
+        if (cmode) launch_softmax_bwd<kBwdCompat>(a, F, s);
+        else if (feat) launch_softmax_bwd<kBwdFeat>(a, F, s);
+        else launch_softmax_bwd<kBwdPlain>(a, F, s);
         for (int k = 0; k < K; ++k) {
+            if (cmode) {                                   // phi_k: Phi_k(Q_{t-1}) -> mu_k^T (n_k gamma_t); dL/dmu_k's partials
+                CompatArgs ca{c.n_points, L, t == T, c.maxN, fs, ar.gam, kds[k].norm, ar.phi + k * slice, a.compat[k], kds[k].w,
+                              grad_compat ? ar.cpart + (size_t)k * F * cblk * L * L : nullptr};
+                k_compat_bwd<<<dim3((unsigned)cblk, (unsigned)F), kBwdBlock, 0, s>>>(ca);
+            }
             const float cs = kds[k].alpha * kds[k].w;
             if (gf[k]) launch_corner_dot(kds[k], c, rows, L, ar.phi + k * slice, fs, val[k], cs, ar.gb[k], s);    // slice side
             const float *valt;                             // (B^T S n_k gamma_t)
@@ -471,7 +630,9 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
     a.relax = 1.0f;
     a.first = T == 0;
     a.partial = nullptr;
-    launch_softmax_bwd<false>(a, F, s);
+    launch_softmax_bwd<kBwdPlain>(a, F, s);
+    if (grad_compat && K && T >= 1)
+        k_compat_reduce<<<(unsigned)((K * L * L + kBwdBlock - 1) / kBwdBlock), kBwdBlock, 0, s>>>(ar.cpart, K, cblk, L * L, grad_compat);
     // the norm part, <a_k, Phi_k(1)> with a_k = -n_k^2 g_n[k] (value width 1), and dL/db -> dL/df
     for (int k = 0; k < K; ++k) {
         if (!gf[k]) continue;

@@ -1417,18 +1417,9 @@ __global__ void __launch_bounds__(kBlock) k_blur1x4(KernelDev kd, const float *_
 
 enum SliceMode { SLICE_NORM = 0, SLICE_APPLY_FIRST = 1, SLICE_APPLY = 2, SLICE_PLAIN = 3 };
 
-// slice (+ what the caller does with it).  ref: :684-694, pairwise3d.h:25-27,73-78,
-// densecrf3d.h:154-158.
-__global__ void __launch_bounds__(kBlock) k_slice(KernelDev kd, CrfDev c, const float *__restrict__ val,
-                                                  int L, int mode)
+// the sliced value of (point i, label l): sum over the point's corners of (bary * alpha) * value.  ref: :684-694.
+__device__ __forceinline__ float slice_value(const KernelDev &kd, const float *__restrict__ vf, size_t fe, int i, int l, int L)
 {
-    const int f = blockIdx.y;
-    const int N = c.n_points[f];
-    const int idx = blockIdx.x * kBlock + threadIdx.x;
-    if (idx >= N * L) return;
-    const int i = idx / L, l = idx - i * L;
-    const size_t fe = (size_t)f * kd.Epad;
-    const float *vf = val + (size_t)f * kd.vstride + kd.vbase;
     float t = 0.0f;
     // (every corner's id and weight, then every gather, before the first use: one round trip per level instead of one per corner)
     int o[kMaxD + 1];
@@ -1442,6 +1433,22 @@ __global__ void __launch_bounds__(kBlock) k_slice(KernelDev kd, CrfDev c, const 
 #pragma unroll
     for (int j = 0; j <= kMaxD; ++j)
         if (j < kd.D1) t += wgt[j] * x[j];
+    return t;
+}
+
+// slice (+ what the caller does with it).  ref: :684-694, pairwise3d.h:25-27,73-78,
+// densecrf3d.h:154-158.
+__global__ void __launch_bounds__(kBlock) k_slice(KernelDev kd, CrfDev c, const float *__restrict__ val,
+                                                  int L, int mode)
+{
+    const int f = blockIdx.y;
+    const int N = c.n_points[f];
+    const int idx = blockIdx.x * kBlock + threadIdx.x;
+    if (idx >= N * L) return;
+    const int i = idx / L, l = idx - i * L;
+    const size_t fe = (size_t)f * kd.Epad;
+    const float *vf = val + (size_t)f * kd.vstride + kd.vbase;
+    const float t = slice_value(kd, vf, fe, i, l, L);
     if (mode == SLICE_NORM) {
         kd.norm[(size_t)f * kd.maxN + i] = 1.0f / (t + 1e-20f);
     } else if (mode == SLICE_PLAIN) {                      // the bare filter: out = compute(in), permutohedral_cpu.h:634-699
@@ -1450,6 +1457,63 @@ __global__ void __launch_bounds__(kBlock) k_slice(KernelDev kd, CrfDev c, const 
         const size_t q = ((size_t)f * c.maxN + i) * L + l;
         const float base = (mode == SLICE_APPLY_FIRST) ? -c.unary[q] : c.next[q];
         c.next[q] = base + kd.w * kd.norm[(size_t)f * kd.maxN + i] * t;
+    }
+}
+
+// The slice of a term with a label-compatibility matrix mu [L][L] (include/lccrf.h section 1e), in the same launch:
+//   next[i][l] = base + w * norm[i] * s,   s = 0; for l' = 0 .. L-1: s = s + mu[l][l'] * t[i][l']
+// with t[i][l'] the value k_slice forms (slice_value) and every product and sum rounded on its own (-ffp-contract=off): an identity
+// matrix gives k_slice's bits.  The sliced values never go to HBM: a workgroup owns kCompatGroups groups of R = 256 / L consecutive
+// points, lane r * L + l of a group forms t[r][l] into LDS, and behind one barrier the same lane sums row l of mu (in LDS too)
+// against the point's L values.  Row strides of mu and of the tile are odd (L | 1): ds_read_b32 serves 32 lanes per cycle from 32
+// banks, lanes with the same l (or the same point) read one address (a broadcast), and the up to 32 different rows a lane group
+// walks at one column l' fall on different banks.
+constexpr int kCompatGroups = 4;
+constexpr int kCompatTile = kBlock + kBlock / 2;           // R * (L | 1) <= 256 + R, R <= 128 (L = 2; L = 1: R = 256 rows of one)
+__global__ void __launch_bounds__(kBlock) k_slice_compat(KernelDev kd, CrfDev c, const float *__restrict__ val,
+                                                         const float *__restrict__ compat, int L, int mode)
+{
+    __shared__ float mu[LCCRF_MAX_LABELS * (LCCRF_MAX_LABELS + 1)];
+    __shared__ float tile[kCompatGroups][kCompatTile];
+    const int f = blockIdx.y;
+    const int N = c.n_points[f];
+    const int R = kBlock / L, ms = L | 1, ts = L == 1 ? 1 : (L | 1);
+    const int tid = threadIdx.x;
+    const int r = tid / L, l = tid - r * L;
+    const int i0 = blockIdx.x * (kCompatGroups * R) + r;
+    if (i0 - r >= N) return;                              // (the whole workgroup: no barrier is left behind)
+    for (int idx = tid; idx < L * L; idx += kBlock) {
+        const int a = idx / L;
+        mu[a * ms + (idx - a * L)] = compat[idx];
+    }
+    const size_t fe = (size_t)f * kd.Epad;
+    const float *vf = val + (size_t)f * kd.vstride + kd.vbase;
+#pragma unroll
+    for (int g = 0; g < kCompatGroups; ++g) {
+        const int i = i0 + g * R;
+        if (r < R && i < N) tile[g][r * ts + l] = slice_value(kd, vf, fe, i, l, L);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int g = 0; g < kCompatGroups; ++g) {
+        const int i = i0 + g * R;
+        if (r >= R || i >= N) continue;
+        const float *m = mu + l * ms, *t = tile[g] + r * ts;
+        float s = 0.0f;
+        for (int lp = 0; lp < L; ++lp) s = s + m[lp] * t[lp];
+        const size_t q = ((size_t)f * c.maxN + i) * L + l;
+        const float base = (mode == SLICE_APPLY_FIRST) ? -c.unary[q] : c.next[q];
+        c.next[q] = base + kd.w * kd.norm[(size_t)f * kd.maxN + i] * s;
+    }
+}
+
+inline void launch_slice_apply(const KernelDev &kd, const CrfDev &c, const float *res, int L, int mode, const float *compat, hipStream_t s)
+{
+    if (compat) {
+        const long per = (long)kCompatGroups * (kBlock / L);
+        k_slice_compat<<<dim3((unsigned)std::max((c.maxN + per - 1) / per, 1L), (unsigned)c.F), kBlock, 0, s>>>(kd, c, res, compat, L, mode);
+    } else {
+        k_slice<<<grid_for((long)c.maxN * L, c.F), kBlock, 0, s>>>(kd, c, res, L, mode);
     }
 }
 
@@ -2191,15 +2255,17 @@ void launch_start(const CrfDev &c, hipStream_t s)   // densecrf_base.h:78-80
     launch_softmax(c, c.unary, c.Q, -1.0f, 1.0f, s);
 }
 
-void launch_step_stream(const CrfDev &c, const KernelDev *kds, const int *maxV, float relax, hipStream_t s)
+void launch_step_stream(const CrfDev &c, const KernelDev *kds, const int *maxV, float relax, hipStream_t s, const float *const *compat)
 {                                                    // densecrf_base.h:82-91
     const int L = c.L;
+    bool any_compat = false;                             // (section 1e: the two-label kernels below hard-wire Potts; a CRF with a matrix
+    for (int k = 0; k < c.K && compat; ++k) any_compat |= compat[k] != nullptr;   //  takes the generic branch at L = 2 as well)
     if (c.K == 0) {
         // stepInit only: next = -unary, then softmax.  Done by the softmax with scale -1.
         launch_softmax(c, c.unary, c.Q, -1.0f, relax, s);
         return;
     }
-    if (L == 2) {
+    if (L == 2 && !any_compat) {
         for (int k = 0; k < c.K; ++k) {
             const KernelDev &kd = kds[k];
             XcdMap nb;
@@ -2293,8 +2359,7 @@ void launch_step_stream(const CrfDev &c, const KernelDev *kds, const int *maxV, 
         launch_splat(kd, c.Q, c.maxN * L, L, c.F, maxV[k], s);
         const float *res;
         filter_passes(kd, c.F, maxV[k], L, s, &res);
-        k_slice<<<grid_for((long)c.maxN * L, c.F), kBlock, 0, s>>>(kd, c, res, L,
-                                                                 k == 0 ? SLICE_APPLY_FIRST : SLICE_APPLY);
+        launch_slice_apply(kd, c, res, L, k == 0 ? SLICE_APPLY_FIRST : SLICE_APPLY, compat ? compat[k] : nullptr, s);
     }
     launch_softmax(c, c.next, c.Q, 1.0f, relax, s);
 }
@@ -2415,7 +2480,7 @@ void launch_step_init(const CrfDev &c, float *out, hipStream_t s)
 // out (+)= [w * norm *] compute(in) with value width c.L: PairwisePotential::apply (accumulate = 1, pairwise3d.h:73-78)
 // or the bare PermutohedralLatticeCPU::compute (accumulate = 0, permutohedral_cpu.h:634-699); reverse = 1: its transpose (engine.h)
 void launch_filter(const KernelDev &kd, const CrfDev &c, int maxV, const float *in, float *out, int accumulate, hipStream_t s,
-                   int reverse, const float **blurred)
+                   int reverse, const float **blurred, const float *compat)
 {
     const int L = c.L;
     launch_splat(kd, in, c.maxN * L, L, c.F, maxV, s);
@@ -2423,7 +2488,7 @@ void launch_filter(const KernelDev &kd, const CrfDev &c, int maxV, const float *
     filter_passes(kd, c.F, maxV, L, s, &res, reverse);
     CrfDev c2 = c;
     c2.next = out;
-    k_slice<<<grid_for((long)c.maxN * L, c.F), kBlock, 0, s>>>(kd, c2, res, L, accumulate ? SLICE_APPLY : SLICE_PLAIN);
+    launch_slice_apply(kd, c2, res, L, accumulate ? SLICE_APPLY : SLICE_PLAIN, accumulate ? compat : nullptr, s);
     if (blurred) *blurred = res;
 }
 
