@@ -358,14 +358,14 @@ class DenseCRFHIP:
 
     def inference_backward_device(self, n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights=None):
         """dL/dU [N][L] and dL/dw [K] of inference(n_iterations, relax) from dL/dQ [N][L]; device addresses, on stream()."""
-        _check(lib().lccrf_inference_backward(self.h, int(n_iterations), float(relax), C.c_void_p(d_grad_prob),
-                                              C.c_void_p(d_grad_unary), C.c_void_p(d_grad_weights) if d_grad_weights else None))
+        _check(lib().lccrf_inference_backward(self.h, int(n_iterations), float(relax), _addr(d_grad_prob), _addr(d_grad_unary),
+                                              _addr(d_grad_weights)))
 
     def inference_backward_features_device(self, n_iterations, relax, d_grad_prob, d_grad_unary=None, d_grad_weights=None,
                                            d_grad_features=None):
         """inference_backward_device plus dL/d features: d_grad_features is a list of K device addresses ([N][d_k] each) or None
         entries (that term is skipped); d_grad_unary / d_grad_weights may be None (include/lccrf.h section 1d)."""
-        _check(lib().lccrf_inference_backward_features(self.h, int(n_iterations), float(relax), C.c_void_p(d_grad_prob),
+        _check(lib().lccrf_inference_backward_features(self.h, int(n_iterations), float(relax), _addr(d_grad_prob),
                                                        _addr(d_grad_unary), _addr(d_grad_weights), _addr_list(d_grad_features)))
 
     # -- label-compatibility matrices (include/lccrf.h section 1e) -----------------------------------------------------------
@@ -390,7 +390,7 @@ class DenseCRFHIP:
                                          d_grad_compat=None):
         """inference_backward_device plus dL/dmu: d_grad_compat is the device address of a [K][L][L] array (None: the call is
         inference_backward_device); d_grad_unary / d_grad_weights may then be None."""
-        _check(lib().lccrf_inference_backward_compat(self.h, int(n_iterations), float(relax), C.c_void_p(d_grad_prob),
+        _check(lib().lccrf_inference_backward_compat(self.h, int(n_iterations), float(relax), _addr(d_grad_prob),
                                                      _addr(d_grad_unary), _addr(d_grad_weights), _addr(d_grad_compat)))
 
     # -- results -----------------------------------------------------------------------

@@ -21,6 +21,7 @@ incoming gradient are produced there); on exit torch's current stream waits for 
 results are complete behind lccrf_synchronize, so the forward synchronises the handle before it copies Q out.  The batch
 layer follows the same pattern on the batch's own stream (lccrf_batch_inference leaves nothing to settle).
 """
+import contextlib
 import importlib
 
 import numpy as np
@@ -36,34 +37,85 @@ def _device_view(ptr, shape, device):
     return torch.as_tensor(_View(), device=device)
 
 
-def _handle_stream(crf, device):
-    return torch.cuda.ExternalStream(crf.stream(), device=device)
+def _check_unary_weights(unary, shape, weights, K):
+    """unary: float32, on the GPU, of `shape` (None: any [N, L]); weights: float32 [K]"""
+    shape_ok = unary.dim() == 2 if shape is None else tuple(unary.shape) == tuple(shape)
+    if not unary.is_cuda or unary.dtype != torch.float32 or not shape_ok:
+        wanted = "N, L" if shape is None else ", ".join("%d" % n for n in shape)
+        raise ValueError("unary must be a float32 GPU tensor of shape [%s]" % wanted)
+    if weights.dtype != torch.float32 or tuple(weights.shape) != (K,):
+        raise ValueError("weights must be a float32 tensor of shape [%d]" % K)
+
+
+def _check_iterations(n_iterations):
+    if n_iterations < 0:
+        raise ValueError("n_iterations must be >= 0")
+
+
+@contextlib.contextmanager
+def _on_stream(raw_stream, device):
+    """The stream hand-off around calls on a handle's (or batch's) stream: it waits for torch's current stream on entry, and
+    torch's current stream waits for it on exit.  Yields (the stream as a torch stream, torch's current stream)."""
+    cur = torch.cuda.current_stream(device)
+    ext = torch.cuda.ExternalStream(raw_stream, device=device)
+    ext.wait_stream(cur)
+    yield ext, cur
+    cur.wait_stream(ext)
+
+
+def _clone_q(ptr, shape, device, ext, cur):
+    """Q out of the handle's own buffer, copied on the handle's stream `ext` (inside _on_stream)"""
+    with torch.cuda.stream(ext):
+        q = _device_view(ptr, shape, device).clone()
+    q.record_stream(cur)
+    return q
+
+
+def _forward_q(crf, u, n_iterations, relax, ext, cur):
+    """run inference on the handle (its unaries `u` and terms are set), clone Q out (inside _on_stream)"""
+    crf.inference(int(n_iterations), False, float(relax))
+    crf.synchronize()                                         # the completion rule of inference() results
+    return _clone_q(crf.device_buffers()["current"], tuple(u.shape), u.device, ext, cur)
+
+
+def _arm(crf, weights, compat=None):
+    """the term weights (and label-compatibility matrices) of a forward, set on the handle or batch"""
+    for k, w in enumerate(weights.detach().cpu().tolist()):
+        crf.set_pairwise_weight(k, w)
+    if compat is not None:
+        m = compat.cpu().numpy()
+        for k in range(m.shape[0]):
+            crf.set_pairwise_compatibility(k, m[k])
+
+
+def _grad_w_buffer(K, device, frames=None):
+    """(buffer, the address to pass) for dL/dw: [K], or [frames, K] for a batch; K = 0: a dummy row and NULL"""
+    shape = (max(K, 1),) if frames is None else (frames, max(K, 1))
+    buf = torch.empty(shape, dtype=torch.float32, device=device)
+    return buf, (buf.data_ptr() if K else None)
+
+
+def _grad_w_result(buf, K, device):
+    """dL/dw [K] of a handle from its buffer (K = 0: an empty tensor), on the device the weights came from"""
+    if K == 0:
+        buf = torch.zeros(0, dtype=torch.float32, device=buf.device)
+    return buf[:K].to(device)
+
+
+def _grad_in(grad_q, device):
+    return grad_q.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
 class _MeanField(torch.autograd.Function):
     @staticmethod
     def forward(ctx, crf, unary, weights, n_iterations, relax):
-        if not unary.is_cuda or unary.dtype != torch.float32 or tuple(unary.shape) != (crf.N, crf.L):
-            raise ValueError("unary must be a float32 GPU tensor of shape [%d, %d]" % (crf.N, crf.L))
-        K = len(crf._d)
-        if weights.dtype != torch.float32 or tuple(weights.shape) != (K,):
-            raise ValueError("weights must be a float32 tensor of shape [%d]" % K)
-        if n_iterations < 0:
-            raise ValueError("n_iterations must be >= 0")
-        dev = unary.device
+        _check_unary_weights(unary, (crf.N, crf.L), weights, len(crf._d))
+        _check_iterations(n_iterations)
         u = unary.detach().contiguous()
-        for k, w in enumerate(weights.detach().cpu().tolist()):
-            crf.set_pairwise_weight(k, w)
-        cur = torch.cuda.current_stream(dev)
-        ext = _handle_stream(crf, dev)
-        ext.wait_stream(cur)
-        crf.set_unary_device(u.data_ptr())
-        crf.inference(int(n_iterations), False, float(relax))
-        crf.synchronize()                                     # the completion rule of inference() results
-        with torch.cuda.stream(ext):
-            q = _device_view(crf.device_buffers()["current"], (crf.N, crf.L), dev).clone()
-        cur.wait_stream(ext)
-        q.record_stream(cur)
+        _arm(crf, weights)
+        with _on_stream(crf.stream(), u.device) as (ext, cur):
+            crf.set_unary_device(u.data_ptr())
+            q = _forward_q(crf, u, n_iterations, relax, ext, cur)
         ctx.crf, ctx.n_iterations, ctx.relax = crf, int(n_iterations), float(relax)
         ctx.weights_device = weights.device
         ctx.save_for_backward(u, weights.detach().clone())
@@ -72,25 +124,15 @@ class _MeanField(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_q):
         u, w = ctx.saved_tensors
-        crf = ctx.crf
-        dev = u.device
-        g = grad_q.detach().to(device=dev, dtype=torch.float32).contiguous()
-        cur = torch.cuda.current_stream(dev)
-        K = int(w.numel())
-        # the handle is re-armed with the inputs of this forward (it may have run other inputs since)
-        for k, wk in enumerate(w.cpu().tolist()):
-            crf.set_pairwise_weight(k, wk)
+        crf, dev, K = ctx.crf, u.device, int(w.numel())
+        g = _grad_in(grad_q, dev)
+        _arm(crf, w)                                          # the inputs of this forward (the handle may have run others since)
         grad_u = torch.empty_like(u)
-        grad_w = torch.empty(max(K, 1), dtype=torch.float32, device=dev)
-        ext = _handle_stream(crf, dev)
-        ext.wait_stream(cur)
-        crf.set_unary_device(u.data_ptr())
-        crf.inference_backward_device(ctx.n_iterations, ctx.relax, g.data_ptr(), grad_u.data_ptr(),
-                                      grad_w.data_ptr() if K else None)
-        cur.wait_stream(ext)
-        if K == 0:
-            grad_w = torch.zeros(0, dtype=torch.float32, device=dev)
-        return None, grad_u, grad_w[:K].to(ctx.weights_device), None, None
+        grad_w, grad_w_ptr = _grad_w_buffer(K, dev)
+        with _on_stream(crf.stream(), dev):
+            crf.set_unary_device(u.data_ptr())
+            crf.inference_backward_device(ctx.n_iterations, ctx.relax, g.data_ptr(), grad_u.data_ptr(), grad_w_ptr)
+        return None, grad_u, _grad_w_result(grad_w, K, ctx.weights_device), None, None
 
 
 def mean_field(crf, unary, weights, n_iterations=5, relax=1.0):
@@ -99,13 +141,10 @@ def mean_field(crf, unary, weights, n_iterations=5, relax=1.0):
     return _MeanField.apply(crf, unary, weights, n_iterations, relax)
 
 
-class MeanFieldCRF(torch.nn.Module):
-    """A dense CRF layer: a DenseCRFHIP handle over fixed features, its term weights an nn.Parameter.
+class _HandleCRF(torch.nn.Module):
+    """what MeanFieldCRF and CompatMeanFieldCRF share: a DenseCRFHIP handle over fixed features, the term weights an nn.Parameter"""
 
-    features: list of [N, d_k] arrays (already divided by the kernel's standard deviation, as lccrf_add_pairwise takes
-    them); weights: their initial weights.  forward(unary [N, L]) -> Q [N, L]."""
-
-    def __init__(self, n_points, n_labels, features, weights, n_iterations=5, relax=1.0, device=0):
+    def __init__(self, n_points, n_labels, features, weights, n_iterations, relax, device):
         super().__init__()
         if len(features) != len(weights):
             raise ValueError("one weight per feature array")
@@ -116,37 +155,36 @@ class MeanFieldCRF(torch.nn.Module):
         self.weights = torch.nn.Parameter(torch.tensor([float(w) for w in weights], dtype=torch.float32))
         self.n_iterations, self.relax = int(n_iterations), float(relax)
 
-    def forward(self, unary):
-        return mean_field(self.crf, unary, self.weights, self.n_iterations, self.relax)
-
     def close(self):
         self.crf.close()
+
+
+class MeanFieldCRF(_HandleCRF):
+    """A dense CRF layer: a DenseCRFHIP handle over fixed features, its term weights an nn.Parameter.
+
+    features: list of [N, d_k] arrays (already divided by the kernel's standard deviation, as lccrf_add_pairwise takes
+    them); weights: their initial weights.  forward(unary [N, L]) -> Q [N, L]."""
+
+    def __init__(self, n_points, n_labels, features, weights, n_iterations=5, relax=1.0, device=0):
+        super().__init__(n_points, n_labels, features, weights, n_iterations, relax, device)
+
+    def forward(self, unary):
+        return mean_field(self.crf, unary, self.weights, self.n_iterations, self.relax)
 
 
 class _MeanFieldBatch(torch.autograd.Function):
     @staticmethod
     def forward(ctx, batch, unary, weights, n_iterations, relax, n_points):
         F, N, L = batch.n_frames, batch.maxN, batch.L
-        if not unary.is_cuda or unary.dtype != torch.float32 or tuple(unary.shape) != (F, N, L):
-            raise ValueError("unary must be a float32 GPU tensor of shape [%d, %d, %d]" % (F, N, L))
-        K = len(batch.dims)
-        if weights.dtype != torch.float32 or tuple(weights.shape) != (K,):
-            raise ValueError("weights must be a float32 tensor of shape [%d]" % K)
-        if n_iterations < 0:
-            raise ValueError("n_iterations must be >= 0")
+        _check_unary_weights(unary, (F, N, L), weights, len(batch.dims))
+        _check_iterations(n_iterations)
         dev = unary.device
         u = unary.detach().contiguous()
-        for k, w in enumerate(weights.detach().cpu().tolist()):
-            batch.set_pairwise_weight(k, w)
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(batch.own_stream(), device=dev)
-        ext.wait_stream(cur)
-        batch.set_unary_device(u.data_ptr())
-        batch.inference(int(n_iterations), False, float(relax))
-        with torch.cuda.stream(ext):
-            q = _device_view(batch.device_buffers()[1], (F, N, L), dev).clone()
-        cur.wait_stream(ext)
-        q.record_stream(cur)
+        _arm(batch, weights)
+        with _on_stream(batch.own_stream(), dev) as (ext, cur):
+            batch.set_unary_device(u.data_ptr())
+            batch.inference(int(n_iterations), False, float(relax))      # (leaves nothing to settle)
+            q = _clone_q(batch.device_buffers()[1], (F, N, L), dev, ext, cur)
         live = torch.arange(N, device=dev)[None, :] < torch.as_tensor(n_points, device=dev)[:, None]
         q = torch.where(live[:, :, None], q, torch.zeros((), device=dev))    # rows beyond a frame's points: 0
         ctx.batch, ctx.n_iterations, ctx.relax = batch, int(n_iterations), float(relax)
@@ -157,22 +195,14 @@ class _MeanFieldBatch(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_q):
         u, w = ctx.saved_tensors
-        batch = ctx.batch
-        dev = u.device
-        g = grad_q.detach().to(device=dev, dtype=torch.float32).contiguous()
-        cur = torch.cuda.current_stream(dev)
-        K = int(w.numel())
-        # the batch is re-armed with the inputs of this forward (it may have run other unaries or weights since)
-        for k, wk in enumerate(w.cpu().tolist()):
-            batch.set_pairwise_weight(k, wk)
+        batch, dev, K = ctx.batch, u.device, int(w.numel())
+        g = _grad_in(grad_q, dev)
+        _arm(batch, w)                                        # the inputs of this forward (the batch may have run others since)
         grad_u = torch.empty_like(u)
-        grad_w = torch.empty((batch.n_frames, max(K, 1)), dtype=torch.float32, device=dev)
-        ext = torch.cuda.ExternalStream(batch.own_stream(), device=dev)
-        ext.wait_stream(cur)
-        batch.set_unary_device(u.data_ptr())
-        batch.inference_backward_device(ctx.n_iterations, ctx.relax, g.data_ptr(), grad_u.data_ptr(),
-                                        grad_w.data_ptr() if K else None)
-        cur.wait_stream(ext)
+        grad_w, grad_w_ptr = _grad_w_buffer(K, dev, batch.n_frames)
+        with _on_stream(batch.own_stream(), dev):
+            batch.set_unary_device(u.data_ptr())
+            batch.inference_backward_device(ctx.n_iterations, ctx.relax, g.data_ptr(), grad_u.data_ptr(), grad_w_ptr)
         return None, grad_u, grad_w[:, :K].sum(0).to(ctx.weights_device), None, None, None
 
 
@@ -217,34 +247,21 @@ class BatchMeanFieldCRF(torch.nn.Module):
 class _MeanFieldFeatures(torch.autograd.Function):
     @staticmethod
     def forward(ctx, unary, weights, n_iterations, relax, device, *features):
-        if not unary.is_cuda or unary.dtype != torch.float32 or unary.dim() != 2:
-            raise ValueError("unary must be a float32 GPU tensor of shape [N, L]")
+        _check_unary_weights(unary, None, weights, len(features))
         N, L = (int(x) for x in unary.shape)
-        K = len(features)
-        if weights.dtype != torch.float32 or tuple(weights.shape) != (K,):
-            raise ValueError("weights must be a float32 tensor of shape [%d]" % K)
         for f in features:
             if not f.is_cuda or f.dtype != torch.float32 or f.dim() != 2 or int(f.shape[0]) != N:
                 raise ValueError("every feature array must be a float32 GPU tensor of shape [%d, d_k]" % N)
-        if n_iterations < 0:
-            raise ValueError("n_iterations must be >= 0")
-        dev = unary.device
+        _check_iterations(n_iterations)
         u = unary.detach().contiguous()
         fs = [f.detach().contiguous() for f in features]
         # the lattices depend on the features: a handle per forward (lccrf_create re-uses parked handles), closed by the backward
         crf = _pkg.DenseCRFHIP(N, L, device=device)
-        cur = torch.cuda.current_stream(dev)
-        ext = _handle_stream(crf, dev)
-        ext.wait_stream(cur)
-        crf.set_unary_device(u.data_ptr())
-        for f, w in zip(fs, weights.detach().cpu().tolist()):
-            crf.add_pairwise_device(f.data_ptr(), int(f.shape[1]), w)
-        crf.inference(int(n_iterations), False, float(relax))
-        crf.synchronize()                                     # the completion rule of inference() results
-        with torch.cuda.stream(ext):
-            q = _device_view(crf.device_buffers()["current"], (N, L), dev).clone()
-        cur.wait_stream(ext)
-        q.record_stream(cur)
+        with _on_stream(crf.stream(), u.device) as (ext, cur):
+            crf.set_unary_device(u.data_ptr())
+            for f, w in zip(fs, weights.detach().cpu().tolist()):
+                crf.add_pairwise_device(f.data_ptr(), int(f.shape[1]), w)
+            q = _forward_q(crf, u, n_iterations, relax, ext, cur)
         ctx.crf, ctx.n_iterations, ctx.relax = crf, int(n_iterations), float(relax)
         ctx.weights_device = weights.device
         ctx.save_for_backward(u, *fs)
@@ -256,26 +273,19 @@ class _MeanFieldFeatures(torch.autograd.Function):
         crf = ctx.crf
         if crf is None:
             raise RuntimeError("mean_field_features: backward a second time (the handle is closed by the first)")
-        dev = u.device
-        g = grad_q.detach().to(device=dev, dtype=torch.float32).contiguous()
-        cur = torch.cuda.current_stream(dev)
-        K = len(fs)
+        dev, K = u.device, len(fs)
+        g = _grad_in(grad_q, dev)
         need = ctx.needs_input_grad
         grad_u = torch.empty_like(u)
-        grad_w = torch.empty(max(K, 1), dtype=torch.float32, device=dev)
+        grad_w, grad_w_ptr = _grad_w_buffer(K, dev)
         grad_f = [torch.empty_like(f) if need[5 + k] else None for k, f in enumerate(fs)]
-        ext = _handle_stream(crf, dev)
-        ext.wait_stream(cur)
-        crf.inference_backward_features_device(ctx.n_iterations, ctx.relax, g.data_ptr(), grad_u.data_ptr(),
-                                               grad_w.data_ptr() if K else None,
-                                               [t.data_ptr() if t is not None else None for t in grad_f])
-        cur.wait_stream(ext)
+        with _on_stream(crf.stream(), dev):
+            crf.inference_backward_features_device(ctx.n_iterations, ctx.relax, g.data_ptr(), grad_u.data_ptr(), grad_w_ptr,
+                                                   [t.data_ptr() if t is not None else None for t in grad_f])
         crf.synchronize()                                     # (the handle goes back to the cache: nothing of this call may be in flight)
         crf.close()
         ctx.crf = None
-        if K == 0:
-            grad_w = torch.zeros(0, dtype=torch.float32, device=dev)
-        return (grad_u, grad_w[:K].to(ctx.weights_device), None, None, None) + tuple(grad_f)
+        return (grad_u, _grad_w_result(grad_w, K, ctx.weights_device), None, None, None) + tuple(grad_f)
 
 
 def mean_field_features(unary, features, weights, n_iterations=5, relax=1.0, device=0):
@@ -333,38 +343,18 @@ class LearnedKernelCRF(torch.nn.Module):
 
 class _MeanFieldCompat(torch.autograd.Function):
     @staticmethod
-    def _arm(crf, weights, compat):
-        for k, w in enumerate(weights.cpu().tolist()):
-            crf.set_pairwise_weight(k, w)
-        m = compat.cpu().numpy()
-        for k in range(m.shape[0]):
-            crf.set_pairwise_compatibility(k, m[k])
-
-    @staticmethod
     def forward(ctx, crf, unary, weights, compat, n_iterations, relax):
-        if not unary.is_cuda or unary.dtype != torch.float32 or tuple(unary.shape) != (crf.N, crf.L):
-            raise ValueError("unary must be a float32 GPU tensor of shape [%d, %d]" % (crf.N, crf.L))
         K = len(crf._d)
-        if weights.dtype != torch.float32 or tuple(weights.shape) != (K,):
-            raise ValueError("weights must be a float32 tensor of shape [%d]" % K)
+        _check_unary_weights(unary, (crf.N, crf.L), weights, K)
         if compat.dtype != torch.float32 or tuple(compat.shape) != (K, crf.L, crf.L):
             raise ValueError("compat must be a float32 tensor of shape [%d, %d, %d]" % (K, crf.L, crf.L))
-        if n_iterations < 0:
-            raise ValueError("n_iterations must be >= 0")
-        dev = unary.device
+        _check_iterations(n_iterations)
         u = unary.detach().contiguous()
         w, m = weights.detach().clone(), compat.detach().clone().contiguous()
-        cur = torch.cuda.current_stream(dev)
-        ext = _handle_stream(crf, dev)
-        ext.wait_stream(cur)
-        _MeanFieldCompat._arm(crf, w, m)
-        crf.set_unary_device(u.data_ptr())
-        crf.inference(int(n_iterations), False, float(relax))
-        crf.synchronize()                                     # the completion rule of inference() results
-        with torch.cuda.stream(ext):
-            q = _device_view(crf.device_buffers()["current"], (crf.N, crf.L), dev).clone()
-        cur.wait_stream(ext)
-        q.record_stream(cur)
+        with _on_stream(crf.stream(), u.device) as (ext, cur):
+            _arm(crf, w, m)
+            crf.set_unary_device(u.data_ptr())
+            q = _forward_q(crf, u, n_iterations, relax, ext, cur)
         ctx.crf, ctx.n_iterations, ctx.relax = crf, int(n_iterations), float(relax)
         ctx.weights_device, ctx.compat_device = weights.device, compat.device
         ctx.save_for_backward(u, w, m)
@@ -373,25 +363,18 @@ class _MeanFieldCompat(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_q):
         u, w, m = ctx.saved_tensors
-        crf = ctx.crf
-        dev = u.device
-        g = grad_q.detach().to(device=dev, dtype=torch.float32).contiguous()
-        cur = torch.cuda.current_stream(dev)
+        crf, dev = ctx.crf, u.device
+        g = _grad_in(grad_q, dev)
         K, L = int(w.numel()), crf.L
         grad_u = torch.empty_like(u)
-        grad_w = torch.empty(max(K, 1), dtype=torch.float32, device=dev)
+        grad_w, grad_w_ptr = _grad_w_buffer(K, dev)
         grad_m = torch.zeros((max(K, 1), L, L), dtype=torch.float32, device=dev)
-        ext = _handle_stream(crf, dev)
-        ext.wait_stream(cur)
-        # the handle is re-armed with the inputs of this forward (it may have run other inputs since)
-        _MeanFieldCompat._arm(crf, w, m)
-        crf.set_unary_device(u.data_ptr())
-        crf.inference_backward_compat_device(ctx.n_iterations, ctx.relax, g.data_ptr(), grad_u.data_ptr(),
-                                             grad_w.data_ptr() if K else None, grad_m.data_ptr())
-        cur.wait_stream(ext)
-        if K == 0:
-            grad_w = torch.zeros(0, dtype=torch.float32, device=dev)
-        return None, grad_u, grad_w[:K].to(ctx.weights_device), grad_m[:K].to(ctx.compat_device), None, None
+        with _on_stream(crf.stream(), dev):
+            _arm(crf, w, m)                                   # the inputs of this forward (the handle may have run others since)
+            crf.set_unary_device(u.data_ptr())
+            crf.inference_backward_compat_device(ctx.n_iterations, ctx.relax, g.data_ptr(), grad_u.data_ptr(), grad_w_ptr,
+                                                 grad_m.data_ptr())
+        return None, grad_u, _grad_w_result(grad_w, K, ctx.weights_device), grad_m[:K].to(ctx.compat_device), None, None
 
 
 def mean_field_compat(crf, unary, weights, compat, n_iterations=5, relax=1.0):
@@ -401,24 +384,13 @@ def mean_field_compat(crf, unary, weights, compat, n_iterations=5, relax=1.0):
     return _MeanFieldCompat.apply(crf, unary, weights, compat, n_iterations, relax)
 
 
-class CompatMeanFieldCRF(torch.nn.Module):
+class CompatMeanFieldCRF(_HandleCRF):
     """MeanFieldCRF whose terms carry a learnt label-compatibility matrix: parameters `weights` [K] and `compat` [K, L, L], the
     latter initialised to identities (the Potts model).  forward(unary [N, L]) -> Q [N, L]."""
 
     def __init__(self, n_points, n_labels, features, weights, n_iterations=5, relax=1.0, device=0):
-        super().__init__()
-        if len(features) != len(weights):
-            raise ValueError("one weight per feature array")
-        self.crf = _pkg.DenseCRFHIP(n_points, n_labels, device=device)
-        for f, w in zip(features, weights):
-            f = f.detach().cpu().numpy() if isinstance(f, torch.Tensor) else np.asarray(f)
-            self.crf.add_pairwise(np.ascontiguousarray(f, np.float32), float(w))
-        self.weights = torch.nn.Parameter(torch.tensor([float(w) for w in weights], dtype=torch.float32))
+        super().__init__(n_points, n_labels, features, weights, n_iterations, relax, device)
         self.compat = torch.nn.Parameter(torch.eye(n_labels, dtype=torch.float32).repeat(len(weights), 1, 1))
-        self.n_iterations, self.relax = int(n_iterations), float(relax)
 
     def forward(self, unary):
         return mean_field_compat(self.crf, unary, self.weights, self.compat, self.n_iterations, self.relax)
-
-    def close(self):
-        self.crf.close()

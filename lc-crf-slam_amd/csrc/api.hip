@@ -243,67 +243,41 @@ struct Engine {
         HIP_TRY(hipMemsetAsync(p, 0, need, stream));
         return LCCRF_OK;
     }
-    // The backward on the area: inference(T, 0, relax) replayed on the step path (start + T x step), `count` floats of Q kept per
-    // iteration in arrays of `slice` floats, dL/dQ_T copied in, then the reverse sweep over frames of up to `rows` points.
-    // grad_features (sections 1d / 2d): K device pointers or null; grad_unary may then be null (the area holds one more array).
-    // backward_need() is the area this takes.
-    size_t backward_need(size_t slice, int rows, int T, bool scratch_unary, float *const *grad_features, bool compat_part = false) const
+    // The area request `rq` takes on frames of up to `rows` points, in bytes (engine.h: backward_layout) ...
+    size_t backward_need(const BackwardRequest &rq, size_t slice, int rows) const
     {
-        const int K = (int)kernels.size();
-        size_t extra = scratch_unary ? slice : 0;
-        if (compat_part) extra += backward_compat_floats(slice, F, rows, L, K);
-        for (int k = 0; k < K && grad_features; ++k)
-            if (grad_features[k]) extra += backward_feature_floats(kernels[k].dev, F);
-        return backward_bytes(slice, F, rows, L, K, T) + extra * sizeof(float);
+        return backward_layout(rq, crf, kdevs.data(), slice, rows, nullptr, nullptr);
     }
-    // compat_part (section 1e): the sweep honours the terms' matrices and, with grad_compat [K][L][L], returns dL/dmu
-    int backward(size_t slice, size_t count, int rows, int T, float relax, const float *grad_prob, float *grad_unary, float *grad_weights,
-                 float *const *grad_features = nullptr, bool compat_part = false, float *grad_compat = nullptr)
+    // ... and the backward on it: inference(T, 0, relax) replayed on the step path (start + T x step), the F * rows * L floats of Q
+    // kept per iteration in arrays of `slice` floats, dL/dQ_T copied in, then the reverse sweep over frames of up to `rows` points.
+    int backward(const BackwardRequest &rq, size_t slice, int rows)
     {
-        const int K = (int)kernels.size();
+        const int K = (int)kernels.size(), T = rq.T;
+        const size_t count = (size_t)F * rows * L;
         BackwardArea ar{};
-        ar.slice = slice;
-        ar.hist = reinterpret_cast<float *>(bwd_area);
-        ar.phi = ar.hist + (size_t)T * slice;
-        ar.G = ar.phi + (size_t)K * slice;
-        ar.partial = ar.G + slice;
-        float *extra = ar.partial + (size_t)std::max(T, 1) * K * F * std::max(backward_blocks(rows, L), 1);
-        if (!grad_unary) {
-            grad_unary = extra;
-            extra += slice;
-        }
+        backward_layout(rq, crf, kdevs.data(), slice, rows, reinterpret_cast<float *>(bwd_area), &ar);
         int rc = start();                                 // (ensure_plain: a handle's frames in locality mode are re-built the plain way once)
         if (!rc) rc = learn_sizes();
         if (rc) return rc;
         for (int t = 0; t < T; ++t) {
             if (count) HIP_TRY(hipMemcpyAsync(ar.hist + (size_t)t * slice, crf.Q, count * sizeof(float), hipMemcpyDeviceToDevice, stream));
-            if ((rc = step(relax))) return rc;
+            if ((rc = step(rq.relax))) return rc;
         }
-        if (grad_compat && K && (!count || T == 0))       // nothing depends on the matrices: exactly 0
-            HIP_TRY(hipMemsetAsync(grad_compat, 0, (size_t)K * L * L * sizeof(float), stream));
+        if (rq.grad_compat && K && (!count || T == 0))    // nothing depends on the matrices: exactly 0
+            HIP_TRY(hipMemsetAsync(rq.grad_compat, 0, (size_t)K * L * L * sizeof(float), stream));
         if (!count) {                                     // nothing to differentiate: dL/dw = 0
-            if (grad_weights && K) HIP_TRY(hipMemsetAsync(grad_weights, 0, (size_t)F * K * sizeof(float), stream));
+            if (rq.grad_weights && K) HIP_TRY(hipMemsetAsync(rq.grad_weights, 0, (size_t)F * K * sizeof(float), stream));
             return LCCRF_OK;
         }
-        for (int k = 0; k < K && grad_features; ++k) {
-            if (!grad_features[k]) continue;
-            const KernelDev &kd = kernels[k].dev;
-            if (T == 0) {                                 // nothing depends on the features: exactly 0
-                HIP_TRY(hipMemsetAsync(grad_features[k], 0, (size_t)F * rows * kd.d * sizeof(float), stream));
-                continue;
-            }
-            ar.gb[k] = extra;
-            ar.gn[k] = extra + (size_t)F * kd.Epad;
-            HIP_TRY(hipMemsetAsync(extra, 0, backward_feature_floats(kd, F) * sizeof(float), stream));
-            extra += backward_feature_floats(kd, F);
+        for (int k = 0; k < K && rq.grad_features; ++k) {
+            if (!rq.grad_features[k]) continue;
+            if (T == 0)                                   // nothing depends on the features: exactly 0
+                HIP_TRY(hipMemsetAsync(rq.grad_features[k], 0, (size_t)F * rows * kernels[k].dev.d * sizeof(float), stream));
+            else
+                HIP_TRY(hipMemsetAsync(ar.gb[k], 0, ar.feat_floats[k] * sizeof(float), stream));
         }
-        if (compat_part) {
-            ar.gam = extra;
-            ar.cpart = extra + slice;
-        }
-        HIP_TRY(hipMemcpyAsync(ar.G, grad_prob, count * sizeof(float), hipMemcpyDeviceToDevice, stream));
-        launch_backward_sweep(crf, kdevs.data(), maxV.data(), rows, T, relax, ar, grad_unary, grad_weights, stream, grad_features,
-                              compat_arg(), grad_compat);
+        HIP_TRY(hipMemcpyAsync(ar.G, rq.grad_prob, count * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        launch_backward_sweep(crf, kdevs.data(), maxV.data(), rows, rq, ar, compat_arg(), stream);
         HIP_TRY(hipGetLastError());
         return LCCRF_OK;
     }
@@ -2141,25 +2115,33 @@ int lccrf_set_pairwise_weight(lccrf_handle h, int kernel, float w)
     return LCCRF_OK;
 }
 
+// Every backward entry point, of a handle (sections 1c - 1e) and of a batch (2c, 2d), fills a BackwardRequest (engine.h), says where
+// it runs and what it allows, and calls backward_call (defined with the batch's, below).  A handle is a batch of one whose area
+// has its own row stride.
+struct BackwardTarget {
+    Engine &e;
+    int rows;                  // points per frame: N of a handle, maxN of a batch (the caller's arrays are [F][rows][.])
+    size_t slice;              // floats per array of the area: backward_stride(N, L), or F * maxN * L
+    bool ready;                // the state the call needs ...
+    const char *not_ready;     // ... and what it says without it
+    bool batch;                // a batch's call: timed, on `stream`, every frame's lattices in HBM and built the plain way
+    void *stream;
+};
+constexpr bool kGradUnaryRequired = true, kGradUnaryOptional = false;   // may the entry point's d_grad_unary be NULL?
+static int backward_call(const BackwardTarget &t, const BackwardRequest &rq, bool need_grad_unary);
+
+static BackwardTarget backward_target(lccrf_crf *h)
+{
+    return {h->eng, h->N, backward_stride(h->N, h->eng.L), h->eng.unary_set, "unary energies not set", false, nullptr};
+}
+
 int lccrf_inference_backward(lccrf_handle h, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
                              float *d_grad_weights)
 {
     CHECK_H(h);
-    Engine &e = h->eng;
-    if (n_iterations < 0) return fail(LCCRF_E_INVALID, "n_iterations < 0");
-    if (!std::isfinite(relax)) return fail(LCCRF_E_INVALID, "relax must be finite");
-    const int K = (int)e.kernels.size(), T = n_iterations;
-    const size_t nl = (size_t)h->N * e.L;
-    { int rc = check_device_array(h, d_grad_prob, nl * sizeof(float), "d_grad_prob"); if (rc) return rc; }
-    { int rc = check_device_array(h, d_grad_unary, nl * sizeof(float), "d_grad_unary"); if (rc) return rc; }
-    if (d_grad_weights) { int rc = check_device_array(h, d_grad_weights, (size_t)K * sizeof(float), "d_grad_weights"); if (rc) return rc; }
-    if (!e.unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
-    { int rl = e.resolve_late(); if (rl) return rl; }
-    // the area first: a handle that cannot have it is left as it was
-    const size_t ns = backward_stride(h->N, e.L);
-    const bool cp = e.n_compat > 0;                       // (section 1e: the gradients of the forward with the matrices)
-    { int ra = e.ensure_backward_area(e.backward_need(ns, h->N, T, false, nullptr, cp)); if (ra) return ra; }   // (the phantom rows stay zero: engine.h)
-    return e.backward(ns, nl, h->N, T, relax, d_grad_prob, d_grad_unary, d_grad_weights, nullptr, cp);
+    BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
+    rq.compat_form = h->eng.n_compat > 0;                 // (section 1e: the gradients of the forward with the matrices)
+    return backward_call(backward_target(h), rq, kGradUnaryRequired);
 }
 
 // --------------------------------------------------------------------------------------
@@ -2169,25 +2151,10 @@ int lccrf_inference_backward_features(lccrf_handle h, int n_iterations, float re
                                       float *d_grad_weights, float *const *d_grad_features)
 {
     CHECK_H(h);
-    Engine &e = h->eng;
-    if (e.n_compat) return fail(LCCRF_E_STATE, "feature gradients are not available while a term has a label-compatibility matrix");
-    if (n_iterations < 0) return fail(LCCRF_E_INVALID, "n_iterations < 0");
-    if (!std::isfinite(relax)) return fail(LCCRF_E_INVALID, "relax must be finite");
-    const int K = (int)e.kernels.size(), T = n_iterations;
-    const size_t nl = (size_t)h->N * e.L;
-    { int rc = check_device_array(h, d_grad_prob, nl * sizeof(float), "d_grad_prob"); if (rc) return rc; }
-    if (d_grad_unary) { int rc = check_device_array(h, d_grad_unary, nl * sizeof(float), "d_grad_unary"); if (rc) return rc; }
-    if (d_grad_weights) { int rc = check_device_array(h, d_grad_weights, (size_t)K * sizeof(float), "d_grad_weights"); if (rc) return rc; }
-    for (int k = 0; k < K && d_grad_features; ++k)
-        if (d_grad_features[k]) {
-            int rc = check_device_array(h, d_grad_features[k], (size_t)h->N * e.kernels[k].dev.d * sizeof(float), "d_grad_features[k]");
-            if (rc) return rc;
-        }
-    if (!e.unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
-    { int rl = e.resolve_late(); if (rl) return rl; }
-    const size_t ns = backward_stride(h->N, e.L);
-    { int ra = e.ensure_backward_area(e.backward_need(ns, h->N, T, !d_grad_unary, d_grad_features)); if (ra) return ra; }
-    return e.backward(ns, nl, h->N, T, relax, d_grad_prob, d_grad_unary, d_grad_weights, d_grad_features);
+    if (h->eng.n_compat) return fail(LCCRF_E_STATE, "feature gradients are not available while a term has a label-compatibility matrix");
+    BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
+    rq.grad_features = d_grad_features;
+    return backward_call(backward_target(h), rq, kGradUnaryOptional);
 }
 
 // --------------------------------------------------------------------------------------
@@ -2221,20 +2188,10 @@ int lccrf_inference_backward_compat(lccrf_handle h, int n_iterations, float rela
 {
     if (!d_grad_compat) return lccrf_inference_backward(h, n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights);
     CHECK_H(h);
-    Engine &e = h->eng;
-    if (n_iterations < 0) return fail(LCCRF_E_INVALID, "n_iterations < 0");
-    if (!std::isfinite(relax)) return fail(LCCRF_E_INVALID, "relax must be finite");
-    const int K = (int)e.kernels.size(), T = n_iterations;
-    const size_t nl = (size_t)h->N * e.L;
-    { int rc = check_device_array(h, d_grad_prob, nl * sizeof(float), "d_grad_prob"); if (rc) return rc; }
-    if (d_grad_unary) { int rc = check_device_array(h, d_grad_unary, nl * sizeof(float), "d_grad_unary"); if (rc) return rc; }
-    if (d_grad_weights) { int rc = check_device_array(h, d_grad_weights, (size_t)K * sizeof(float), "d_grad_weights"); if (rc) return rc; }
-    if (K) { int rc = check_device_array(h, d_grad_compat, (size_t)K * e.L * e.L * sizeof(float), "d_grad_compat"); if (rc) return rc; }
-    if (!e.unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
-    { int rl = e.resolve_late(); if (rl) return rl; }
-    const size_t ns = backward_stride(h->N, e.L);
-    { int ra = e.ensure_backward_area(e.backward_need(ns, h->N, T, !d_grad_unary, nullptr, true)); if (ra) return ra; }
-    return e.backward(ns, nl, h->N, T, relax, d_grad_prob, d_grad_unary, d_grad_weights, nullptr, true, d_grad_compat);
+    BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
+    rq.grad_compat = d_grad_compat;
+    rq.compat_form = true;
+    return backward_call(backward_target(h), rq, kGradUnaryOptional);
 }
 
 // --------------------------------------------------------------------------------------
@@ -2784,27 +2741,50 @@ int lccrf_batch_set_unary_device(lccrf_batch_handle b, const float *d_unary)
     return LCCRF_OK;
 }
 
+// The one path of every backward call.  In this order: the arguments (which outputs may be NULL is the entry point's to say:
+// need_grad_unary, and what it leaves out of the request), the state, a pending one-launch inference, the area -- before anything
+// runs, so that a handle that cannot have it is left as it was -- and then the replay and the sweep (Engine::backward).
+static int backward_call(const BackwardTarget &t, const BackwardRequest &rq, bool need_grad_unary)
+{
+    Engine &e = t.e;
+    if (rq.T < 0) return fail(LCCRF_E_INVALID, "n_iterations < 0");
+    if (!std::isfinite(rq.relax)) return fail(LCCRF_E_INVALID, "relax must be finite");
+    const size_t K = e.kernels.size(), points = (size_t)e.F * t.rows, nl = points * e.L;
+    int rc;
+    if ((rc = check_device_array(e, rq.grad_prob, nl * sizeof(float), "d_grad_prob"))) return rc;
+    if ((need_grad_unary || rq.grad_unary) && (rc = check_device_array(e, rq.grad_unary, nl * sizeof(float), "d_grad_unary"))) return rc;
+    if (rq.grad_weights && (rc = check_device_array(e, rq.grad_weights, e.F * K * sizeof(float), "d_grad_weights"))) return rc;
+    for (size_t k = 0; k < K && rq.grad_features; ++k)
+        if (rq.grad_features[k] &&
+            (rc = check_device_array(e, rq.grad_features[k], points * e.kernels[k].dev.d * sizeof(float), "d_grad_features[k]")))
+            return rc;
+    // (K = 0: zero bytes, nothing to check)
+    if (rq.grad_compat && (rc = check_device_array(e, rq.grad_compat, K * e.L * e.L * sizeof(float), "d_grad_compat"))) return rc;
+    if (!t.ready) return fail(LCCRF_E_STATE, "%s", t.not_ready);
+    auto run = [&] {
+        int rr = e.resolve_late();
+        if (rr) return rr;
+        if ((rr = e.ensure_backward_area(e.backward_need(rq, t.slice, t.rows)))) return rr;   // (a handle's phantom rows stay zero: engine.h)
+        if (t.batch && (rr = e.ensure_plain_batch())) return rr;
+        return e.backward(rq, t.slice, t.rows);
+    };
+    return t.batch ? timed_batch_call(e, t.stream, e.ev[2], e.ev[3], e.timed_inf, run) : run();
+}
+
+static BackwardTarget backward_target(lccrf_batch *b, void *stream)
+{
+    Engine &e = b->eng;
+    // (started: lccrf_batch_run on the one-launch kernel leaves no lattice in HBM -- they are built here)
+    return {e, e.maxN, (size_t)e.F * e.maxN * e.L, b->inputs_set && (e.built || e.started),
+            "lccrf_batch_build or lccrf_batch_run has not run for these inputs", true, stream};
+}
+
 int lccrf_batch_inference_backward(lccrf_batch_handle b, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
                                    float *d_grad_weights, void *stream)
 {
     CHECK_H(b);
-    Engine &e = b->eng;
-    if (n_iterations < 0) return fail(LCCRF_E_INVALID, "n_iterations < 0");
-    if (!std::isfinite(relax)) return fail(LCCRF_E_INVALID, "relax must be finite");
-    const int K = (int)e.kernels.size(), T = n_iterations;
-    const size_t nl = (size_t)e.F * e.maxN * e.L;
-    { int rc = check_device_array(e, d_grad_prob, nl * sizeof(float), "d_grad_prob"); if (rc) return rc; }
-    { int rc = check_device_array(e, d_grad_unary, nl * sizeof(float), "d_grad_unary"); if (rc) return rc; }
-    if (d_grad_weights) { int rc = check_device_array(e, d_grad_weights, (size_t)e.F * K * sizeof(float), "d_grad_weights"); if (rc) return rc; }
-    // (started: lccrf_batch_run on the one-launch kernel leaves no lattice in HBM -- they are built here)
-    if (!b->inputs_set || !(e.built || e.started)) return fail(LCCRF_E_STATE, "lccrf_batch_build or lccrf_batch_run has not run for these inputs");
-    return timed_batch_call(e, stream, e.ev[2], e.ev[3], e.timed_inf, [&] {
-        int rc = e.resolve_late();
-        if (rc) return rc;
-        if ((rc = e.ensure_backward_area(backward_bytes(nl, e.F, e.maxN, e.L, K, T)))) return rc;
-        if ((rc = e.ensure_plain_batch())) return rc;
-        return e.backward(nl, nl, e.maxN, T, relax, d_grad_prob, d_grad_unary, d_grad_weights);
-    });
+    const BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
+    return backward_call(backward_target(b, stream), rq, kGradUnaryRequired);
 }
 
 // --------------------------------------------------------------------------------------
@@ -2814,27 +2794,9 @@ int lccrf_batch_inference_backward_features(lccrf_batch_handle b, int n_iteratio
                                             float *d_grad_unary, float *d_grad_weights, float *const *d_grad_features, void *stream)
 {
     CHECK_H(b);
-    Engine &e = b->eng;
-    if (n_iterations < 0) return fail(LCCRF_E_INVALID, "n_iterations < 0");
-    if (!std::isfinite(relax)) return fail(LCCRF_E_INVALID, "relax must be finite");
-    const int K = (int)e.kernels.size(), T = n_iterations;
-    const size_t nl = (size_t)e.F * e.maxN * e.L;
-    { int rc = check_device_array(e, d_grad_prob, nl * sizeof(float), "d_grad_prob"); if (rc) return rc; }
-    if (d_grad_unary) { int rc = check_device_array(e, d_grad_unary, nl * sizeof(float), "d_grad_unary"); if (rc) return rc; }
-    if (d_grad_weights) { int rc = check_device_array(e, d_grad_weights, (size_t)e.F * K * sizeof(float), "d_grad_weights"); if (rc) return rc; }
-    for (int k = 0; k < K && d_grad_features; ++k)
-        if (d_grad_features[k]) {
-            int rc = check_device_array(e, d_grad_features[k], (size_t)e.F * e.maxN * e.kernels[k].dev.d * sizeof(float), "d_grad_features[k]");
-            if (rc) return rc;
-        }
-    if (!b->inputs_set || !(e.built || e.started)) return fail(LCCRF_E_STATE, "lccrf_batch_build or lccrf_batch_run has not run for these inputs");
-    return timed_batch_call(e, stream, e.ev[2], e.ev[3], e.timed_inf, [&] {
-        int rc = e.resolve_late();
-        if (rc) return rc;
-        if ((rc = e.ensure_backward_area(e.backward_need(nl, e.maxN, T, !d_grad_unary, d_grad_features)))) return rc;
-        if ((rc = e.ensure_plain_batch())) return rc;
-        return e.backward(nl, nl, e.maxN, T, relax, d_grad_prob, d_grad_unary, d_grad_weights, d_grad_features);
-    });
+    BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
+    rq.grad_features = d_grad_features;
+    return backward_call(backward_target(b, stream), rq, kGradUnaryOptional);
 }
 
 void lccrf_default_params(lccrf_crf_params *p)       // Examples/RGB-D/TUM3.yaml:78-101

@@ -206,43 +206,57 @@ void launch_stage_features(float *dst, const void *src, int n, int d, int mode, 
 // out[f] = clamp(in[f], 0, maxN); *bad (pinned host memory) is set to 1 if anything had to be clamped
 void launch_validate_npoints(const int *in, int *out, int F, int maxN, int *bad, hipStream_t s);
 
-// ---- mean-field backward (csrc/meanfield_backward.hip; include/lccrf.h sections 1c and 2c) ---------------------------------
-// The area of one lccrf_inference_backward / lccrf_batch_inference_backward, owned by the engine: Q_0 .. Q_{T-1} of the replay, one
-// [F][.][L] array per term, dL/dQ_t and the per-workgroup partials of the weight gradient -- backward_bytes() in all, zeroed when
-// allocated.  Every array is `slice` floats: for a handle backward_stride(N, L) (N rounded up to a multiple of 4 rows, the phantom
-// points' rows of quirk Q1 staying zero), for a batch F * maxN * L (the engine's own [F][maxN][L] layout).  The sweep reads no row at
-// or beyond a frame's n_points (meanfield_backward.hip).
+// ---- mean-field backward (csrc/meanfield_backward.hip; include/lccrf.h sections 1c - 1e and 2c - 2d) ------------------------
+// One backward call, of a handle or of a batch (F frames of up to `rows` points; a handle is a batch of one): what every
+// lccrf_*inference_backward* entry point fills in and hands to the one path behind them (api.hip: backward_call).
+struct BackwardRequest {           // (an aggregate: the members left out of a braced list are null / false)
+    int T;                          // n_iterations
+    float relax;
+    const float *grad_prob;         // [F][rows][L] dL/dQ_T
+    float *grad_unary;              // [F][rows][L] or null: dL/dU is then formed in the area (BackwardArea::gU)
+    float *grad_weights;            // [F][K] or null
+    float *const *grad_features;    // null, or K pointers, [F][rows][d_k] each or null (sections 1d / 2d)
+    float *grad_compat;             // [K][L][L] or null (section 1e; F = 1)
+    bool compat_form;               // the sweep takes section 1e's form: the terms' matrices are honoured (grad_compat needs it)
+};
+// The area of one backward call, owned by the engine and zeroed when allocated: Q_0 .. Q_{T-1} of the replay, one [F][.][L] array
+// per term, dL/dQ_t, the per-workgroup partials of the weight gradient, and the parts the request asks for beyond those.  Every
+// [slice] array is `slice` floats: for a handle backward_stride(N, L) (N rounded up to a multiple of 4 rows, the phantom points'
+// rows of quirk Q1 staying zero), for a batch F * maxN * L (the engine's own [F][maxN][L] layout).  The sweep reads no row at or
+// beyond a frame's n_points (meanfield_backward.hip).  backward_layout() is the one place that knows the order and the sizes.
 struct BackwardArea {
     size_t slice;         // floats per array
     float *hist;          // [T][slice]
     float *phi;           // [K][slice]
     float *G;             // [slice]
-    float *partial;       // [max(T,1)][K][F][backward_blocks(rows, L)]
+    float *partial;       // [max(T,1)][K][F][max(backward_blocks(rows, L), 1)]
+    float *gU;            // [slice] when the request has no grad_unary, else null
     // the feature part (sections 1d and 2d), per term whose feature gradient is asked for, else null: dL/d(corner weight) of every
-    // entry, laid out as KernelDev::bary, and the per-point sum behind the norm's gradient -- backward_feature_floats() per term,
-    // zeroed by the caller before every sweep
+    // entry, laid out as KernelDev::bary, and right behind it the per-point sum behind the norm's gradient -- feat_floats in all,
+    // zeroed by the caller (from gb on) before every sweep
     float *gb[LCCRF_MAX_KERNELS];   // [F][Epad]
     float *gn[LCCRF_MAX_KERNELS];   // [F][maxNpad]
-    // the compatibility part (section 1e), when a term has a matrix or dL/dmu is asked for, else null: gamma_t of the current
-    // iteration, and the per-workgroup partials of dL/dmu accumulated over the iterations -- backward_compat_floats() in all
+    size_t feat_floats[LCCRF_MAX_KERNELS];
+    // the compatibility part (section 1e), with BackwardRequest::compat_form, else null: gamma_t of the current iteration, and the
+    // per-workgroup partials of dL/dmu accumulated over the iterations
     float *gam;           // [slice]
     float *cpart;         // [K][F][backward_compat_blocks(rows)][L][L]
 };
 int backward_blocks(int n, int L);
 size_t backward_stride(int n, int L);
-size_t backward_bytes(size_t slice, int F, int rows, int L, int K, int T);
 int backward_compat_blocks(int n);
-size_t backward_compat_floats(size_t slice, int F, int rows, int L, int K);
-inline size_t backward_feature_floats(const KernelDev &kd, int F) { return (size_t)F * ((size_t)kd.Epad + kd.maxNpad); }
-// the reverse sweep over the F = c.F frames of up to `rows` points each (the replay has filled ar.hist and ar.G = dL/dQ_T);
-// grad_unary [F][c.maxN][L] (rows [n_points[f], rows) written 0), grad_weights [F][K] or null;
-// grad_features (or null): K pointers, [F][c.maxN][d_k] each or null (rows [n_points[f], rows) written 0) -- for every one given,
-// ar.gb[k] / ar.gn[k] are set.  Without any, the launches are those of sections 1c / 2c.
-// compat (or null): K device pointers, the terms' [L][L] matrices or null; grad_compat (or null): [K][L][L], overwritten (F = 1).
-// With ar.gam set the sweep takes section 1e's form: one k_compat_bwd launch per iteration and term more.
-void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int rows, int T, float relax, const BackwardArea &ar,
-                           float *grad_unary, float *grad_weights, hipStream_t s, float *const *grad_features = nullptr,
-                           const float *const *compat = nullptr, float *grad_compat = nullptr);
+// The area of request `rq` on c.F frames of up to `rows` points: returns its size in bytes and, with ar != null, sets *ar to
+// its parts in the area at `base` (sizing: both null).  Sizing and running go through this one function.
+size_t backward_layout(const BackwardRequest &rq, const CrfDev &c, const KernelDev *kds, size_t slice, int rows, float *base,
+                       BackwardArea *ar);
+// the reverse sweep over the F = c.F frames of up to `rows` points each (the replay has filled ar.hist and ar.G = dL/dQ_T):
+// dL/dU [F][c.maxN][L] goes to rq.grad_unary, or ar.gU without one (rows [n_points[f], rows) written 0), rq.grad_weights and
+// rq.grad_features (rows [n_points[f], rows) written 0; the caller has zeroed ar.gb / ar.gn of every term asked for) as the
+// request says.  Without feature gradients and compat_form the launches are those of sections 1c / 2c.
+// compat (or null): K device pointers, the terms' [L][L] matrices or null, read with rq.compat_form only -- the sweep then takes
+// section 1e's form (one k_compat_bwd launch per iteration and term more) and rq.grad_compat, if given, is overwritten.
+void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int rows, const BackwardRequest &rq,
+                           const BackwardArea &ar, const float *const *compat, hipStream_t s);
 
 // ---- fused build (SLAM sizes; one workgroup per (frame, kernel), hash table in LDS) ------
 bool build_small_supported(const KernelDev *kds, int n, int max_points);

@@ -1,8 +1,9 @@
 // meanfield_backward.hip -- reverse-mode gradients of DenseCRF::inference (densecrf_base.h:65-91): include/lccrf.h section 1c.
 //
-// The C-ABI layer (api.hip: lccrf_inference_backward, lccrf_batch_inference_backward) replays the forward on the step path, keeping
-// Q_0 .. Q_{T-1}, and then runs the sweep below on the call's stream, for every frame at once (the frame is blockIdx.y; a handle is a
-// batch of one).  Per iteration t = T .. 1:
+// The C-ABI layer (api.hip: backward_call, behind every lccrf_*inference_backward* entry point) replays the forward on the step
+// path, keeping Q_0 .. Q_{T-1}, and then runs the sweep below on the call's stream, for every frame at once (the frame is
+// blockIdx.y; a handle is a batch of one).  What a call asks for is a BackwardRequest (engine.h); backward_layout() below lays its
+// area out, for the sizing and for the run alike.  Per iteration t = T .. 1:
 //   Phi_k(Q_{t-1})                          launch_filter, forward blur order (the streaming engine's splat / blur / slice)
 //   x_t, P_t, gamma_t, dL/dU, n_k gamma_t   k_softmax_bwd (+ the per-workgroup partials of the K weight-gradient dot products)
 //   Phi_k^T(n_k gamma_t)                    launch_filter, blur passes in REVERSE axis order (each pass is symmetric, their product
@@ -29,6 +30,9 @@
 // only in its splat rows (k_csr_count / k_eoffsets in stream_engine.hip, E = N (d+1) in build_small.hip), the slice writes rows
 // i < n_points[f] only, and the kernels below stop at n_points[f].  A batch rebound with fewer points than an earlier call leaves
 // stale rows in its area; nothing reads them.
+#include <algorithm>
+#include <type_traits>
+
 #include "engine.h"
 #include "device_math.h"
 
@@ -64,6 +68,19 @@ enum { kBwdPlain = 0, kBwdFeat = 1, kBwdCompat = 2 };   // what k_softmax_bwd do
 
 // lanes per row: one row per lane up to 4 labels, then four labels per lane over a power-of-two group of lanes
 inline int bwd_lanes(int L) { return L <= 4 ? 1 : L <= 8 ? 2 : L <= 16 ? 4 : L <= 32 ? 8 : 16; }
+
+// ... and the one dispatch on them: fn(std::integral_constant<int, G>) with G = bwd_lanes(L) as a compile-time constant
+template <typename Fn>
+void with_bwd_lanes(int L, Fn fn)
+{
+    switch (bwd_lanes(L)) {
+    case 1: fn(std::integral_constant<int, 1>{}); break;
+    case 2: fn(std::integral_constant<int, 2>{}); break;
+    case 4: fn(std::integral_constant<int, 4>{}); break;
+    case 8: fn(std::integral_constant<int, 8>{}); break;
+    default: fn(std::integral_constant<int, 16>{}); break;
+    }
+}
 
 // the label-ordered sum of one value per label over the row's lanes (lane first + c holds labels 4c .. 4c+3): every lane of the row
 // ends with the same sum, added one label at a time in label order 0 .. L-1, as densecrf3d.h:80-84 adds the row sum
@@ -282,26 +299,12 @@ __global__ void __launch_bounds__(kBwdBlock) k_bwd_reduce(const float *__restric
 template <int MODE>
 void launch_softmax_bwd(const BwdArgs &a, int F, hipStream_t s)
 {
-    const int G = bwd_lanes(a.L);
     const dim3 grid((unsigned)std::max(backward_blocks(a.rows, a.L), 1), (unsigned)F);
-    if (MODE == kBwdCompat) {
-        switch (G) {
-        case 1: k_compat_softmax<1><<<grid, kBwdBlock, 0, s>>>(a); break;
-        case 2: k_compat_softmax<2><<<grid, kBwdBlock, 0, s>>>(a); break;
-        case 4: k_compat_softmax<4><<<grid, kBwdBlock, 0, s>>>(a); break;
-        case 8: k_compat_softmax<8><<<grid, kBwdBlock, 0, s>>>(a); break;
-        default: k_compat_softmax<16><<<grid, kBwdBlock, 0, s>>>(a); break;
-        }
-        return;
-    }
-    constexpr bool FEAT = MODE == kBwdFeat;
-    switch (G) {
-    case 1: k_softmax_bwd<1, FEAT><<<grid, kBwdBlock, 0, s>>>(a); break;
-    case 2: k_softmax_bwd<2, FEAT><<<grid, kBwdBlock, 0, s>>>(a); break;
-    case 4: k_softmax_bwd<4, FEAT><<<grid, kBwdBlock, 0, s>>>(a); break;
-    case 8: k_softmax_bwd<8, FEAT><<<grid, kBwdBlock, 0, s>>>(a); break;
-    default: k_softmax_bwd<16, FEAT><<<grid, kBwdBlock, 0, s>>>(a); break;
-    }
+    with_bwd_lanes(a.L, [&](auto lanes) {
+        constexpr int G = decltype(lanes)::value;
+        if constexpr (MODE == kBwdCompat) k_compat_softmax<G><<<grid, kBwdBlock, 0, s>>>(a);
+        else k_softmax_bwd<G, MODE == kBwdFeat><<<grid, kBwdBlock, 0, s>>>(a);
+    });
 }
 
 // ---- the compatibility part (section 1e) ---------------------------------------------------------------------------------------
@@ -456,15 +459,8 @@ void launch_corner_dot(const KernelDev &kd, const CrfDev &c, int rows, int L, co
                        float *gb, hipStream_t s)
 {
     CornerArgs a{c.n_points, L, fs, row, val, scale, gb};
-    const int G = bwd_lanes(L);
     const dim3 grid((unsigned)std::max(backward_blocks(rows, L), 1), (unsigned)c.F);
-    switch (G) {
-    case 1: k_corner_dot<1><<<grid, kBwdBlock, 0, s>>>(kd, a); break;
-    case 2: k_corner_dot<2><<<grid, kBwdBlock, 0, s>>>(kd, a); break;
-    case 4: k_corner_dot<4><<<grid, kBwdBlock, 0, s>>>(kd, a); break;
-    case 8: k_corner_dot<8><<<grid, kBwdBlock, 0, s>>>(kd, a); break;
-    default: k_corner_dot<16><<<grid, kBwdBlock, 0, s>>>(kd, a); break;
-    }
+    with_bwd_lanes(L, [&](auto lanes) { k_corner_dot<decltype(lanes)::value><<<grid, kBwdBlock, 0, s>>>(kd, a); });
 }
 
 // gn[i] <- a_i = -n_i^2 gn[i]: dL/d Phi_k(1)_i, the input of the norm part's filter pair
@@ -551,20 +547,45 @@ int backward_blocks(int n, int L) { return (n + kBwdBlock / bwd_lanes(L) - 1) / 
 
 int backward_compat_blocks(int n) { return std::min(std::max((n + kBwdBlock - 1) / kBwdBlock, 1), kCompatMaxBlocks); }
 
-size_t backward_compat_floats(size_t slice, int F, int rows, int L, int K)
+size_t backward_layout(const BackwardRequest &rq, const CrfDev &c, const KernelDev *kds, size_t slice, int rows, float *base,
+                       BackwardArea *ar)
 {
-    return slice + (size_t)K * F * backward_compat_blocks(rows) * L * L;
+    const size_t F = (size_t)c.F, K = (size_t)c.K, LL = (size_t)c.L * c.L;
+    size_t used = 0;
+    auto take = [&](size_t floats) {                      // the next part: its address in the area (null without one)
+        float *p = base ? base + used : nullptr;
+        used += floats;
+        return p;
+    };
+    BackwardArea a{};
+    a.slice = slice;
+    a.hist = take((size_t)rq.T * slice);
+    a.phi = take(K * slice);
+    a.G = take(slice);
+    a.partial = take((size_t)std::max(rq.T, 1) * K * F * std::max(backward_blocks(rows, c.L), 1));
+    if (!rq.grad_unary) a.gU = take(slice);
+    for (size_t k = 0; k < K && rq.grad_features; ++k)
+        if (rq.grad_features[k]) {
+            const size_t nb = F * kds[k].Epad, nn = F * kds[k].maxNpad;
+            a.gb[k] = take(nb);
+            a.gn[k] = take(nn);
+            a.feat_floats[k] = nb + nn;
+        }
+    if (rq.compat_form) {
+        a.gam = take(slice);
+        a.cpart = take(K * F * backward_compat_blocks(rows) * LL);
+    }
+    if (ar) *ar = a;
+    return used * sizeof(float);
 }
 
-size_t backward_bytes(size_t slice, int F, int rows, int L, int K, int T)
+void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int rows, const BackwardRequest &rq,
+                           const BackwardArea &ar, const float *const *compat, hipStream_t s)
 {
-    return sizeof(float) * (slice * ((size_t)T + K + 1) + (size_t)std::max(T, 1) * K * F * std::max(backward_blocks(rows, L), 1));
-}
-
-void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int rows, int T, float relax, const BackwardArea &ar,
-                           float *grad_unary, float *grad_weights, hipStream_t s, float *const *grad_features,
-                           const float *const *compat, float *grad_compat)
-{
+    const int T = rq.T;
+    const float relax = rq.relax;
+    float *const *grad_features = rq.grad_features;
+    float *const grad_weights = rq.grad_weights, *const grad_compat = rq.grad_compat;
     const int K = c.K, L = c.L, F = c.F;
     const size_t slice = ar.slice, fs = (size_t)c.maxN * L;
     const int nblk = std::max(backward_blocks(rows, L), 1);
@@ -578,14 +599,14 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
     a.unary = c.unary;
     a.phi = ar.phi;
     a.G = ar.G;
-    a.gU = grad_unary;
+    a.gU = rq.grad_unary ? rq.grad_unary : ar.gU;
     BwdWeights wk{};
     for (int k = 0; k < K; ++k) {
         a.norm[k] = kds[k].norm;
         a.w[k] = wk.w[k] = kds[k].w;
     }
-    // the compatibility part (section 1e): some term has a matrix, or dL/dmu is asked for -- ar.gam (and ar.cpart) are set
-    const bool cmode = ar.gam != nullptr;
+    // the compatibility part (section 1e): some term has a matrix, or dL/dmu is asked for -- ar.gam and ar.cpart are set
+    const bool cmode = rq.compat_form;
     const int cblk = backward_compat_blocks(rows);
     for (int k = 0; k < K && cmode; ++k) a.compat[k] = compat ? compat[k] : nullptr;
     a.gam = ar.gam;
@@ -608,9 +629,10 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
         a.relax = relax;
         a.first = t == T;
         a.partial = K ? ar.partial + (size_t)(t - 1) * K * F * nblk : nullptr;
+        // (first uses in the order compat, plain, feature: the order of the kernels' instantiation, and so of the code object)
         if (cmode) launch_softmax_bwd<kBwdCompat>(a, F, s);
-        else if (feat) launch_softmax_bwd<kBwdFeat>(a, F, s);
-        else launch_softmax_bwd<kBwdPlain>(a, F, s);
+        else if (!feat) launch_softmax_bwd<kBwdPlain>(a, F, s);
+        else launch_softmax_bwd<kBwdFeat>(a, F, s);
         for (int k = 0; k < K; ++k) {
             if (cmode) {                                   // phi_k: Phi_k(Q_{t-1}) -> mu_k^T (n_k gamma_t); dL/dmu_k's partials
                 CompatArgs ca{c.n_points, L, t == T, c.maxN, fs, ar.gam, kds[k].norm, ar.phi + k * slice, a.compat[k], kds[k].w,
