@@ -1,0 +1,131 @@
+// api_backward.hip -- gradients of mean-field inference: sections 1c, 1d and 1e (a handle) and 2c, 2d (a batch) of include/lccrf.h.
+//
+// One path behind every entry point (backward_call); the replay and the sweep themselves are Engine::backward (host_engine.hip) and
+// meanfield_backward.hip.
+#include "api_common.h"
+
+#include <cmath>
+
+using namespace lccrf;
+
+// Every backward entry point, of a handle (sections 1c - 1e) and of a batch (2c, 2d), fills a BackwardRequest (engine.h), says where
+// it runs and what it allows, and calls backward_call.  A handle is a batch of one whose area has its own row stride.
+struct BackwardTarget {
+    Engine &e;
+    int rows;                  // points per frame: N of a handle, maxN of a batch (the caller's arrays are [F][rows][.])
+    size_t slice;              // floats per array of the area: backward_stride(N, L), or F * maxN * L
+    bool ready;                // the state the call needs ...
+    const char *not_ready;     // ... and what it says without it
+    bool batch;                // a batch's call: timed, on `stream`, every frame's lattices in HBM and built the plain way
+    void *stream;
+};
+constexpr bool kGradUnaryRequired = true, kGradUnaryOptional = false;   // may the entry point's d_grad_unary be NULL?
+
+// The one path of every backward call.  In this order: the arguments (which outputs may be NULL is the entry point's to say:
+// need_grad_unary, and what it leaves out of the request), the state, a pending one-launch inference, the area -- before anything
+// runs, so that a handle that cannot have it is left as it was -- and then the replay and the sweep (Engine::backward).
+static int backward_call(const BackwardTarget &t, const BackwardRequest &rq, bool need_grad_unary)
+{
+    Engine &e = t.e;
+    if (rq.T < 0) return fail(LCCRF_E_INVALID, "n_iterations < 0");
+    if (!std::isfinite(rq.relax)) return fail(LCCRF_E_INVALID, "relax must be finite");
+    const size_t K = e.kernels.size(), points = (size_t)e.F * t.rows, nl = points * e.L;
+    int rc;
+    if ((rc = check_device_array(e, rq.grad_prob, nl * sizeof(float), "d_grad_prob"))) return rc;
+    if ((need_grad_unary || rq.grad_unary) && (rc = check_device_array(e, rq.grad_unary, nl * sizeof(float), "d_grad_unary"))) return rc;
+    if (rq.grad_weights && (rc = check_device_array(e, rq.grad_weights, e.F * K * sizeof(float), "d_grad_weights"))) return rc;
+    for (size_t k = 0; k < K && rq.grad_features; ++k)
+        if (rq.grad_features[k] &&
+            (rc = check_device_array(e, rq.grad_features[k], points * e.kernels[k].dev.d * sizeof(float), "d_grad_features[k]")))
+            return rc;
+    // (K = 0: zero bytes, nothing to check)
+    if (rq.grad_compat && (rc = check_device_array(e, rq.grad_compat, K * e.L * e.L * sizeof(float), "d_grad_compat"))) return rc;
+    if (!t.ready) return fail(LCCRF_E_STATE, "%s", t.not_ready);
+    auto run = [&] {
+        int rr = e.resolve_late();
+        if (rr) return rr;
+        if ((rr = e.ensure_backward_area(e.backward_need(rq, t.slice, t.rows)))) return rr;   // (a handle's phantom rows stay zero: engine.h)
+        if (t.batch && (rr = e.ensure_plain_batch())) return rr;
+        return e.backward(rq, t.slice, t.rows);
+    };
+    return t.batch ? timed_batch_call(e, t.stream, e.ev[2], e.ev[3], e.timed_inf, run) : run();
+}
+
+static BackwardTarget backward_target(lccrf_crf *h)
+{
+    return {h->eng, h->N, backward_stride(h->N, h->eng.L), h->eng.unary_set, "unary energies not set", false, nullptr};
+}
+
+static BackwardTarget backward_target(lccrf_batch *b, void *stream)
+{
+    Engine &e = b->eng;
+    // (started: lccrf_batch_run on the one-launch kernel leaves no lattice in HBM -- they are built here)
+    return {e, e.maxN, (size_t)e.F * e.maxN * e.L, b->inputs_set && (e.built || e.started),
+            "lccrf_batch_build or lccrf_batch_run has not run for these inputs", true, stream};
+}
+
+extern "C" {
+
+// --------------------------------------------------------------------------------------
+// section 1c: gradients of inference()
+
+int lccrf_inference_backward(lccrf_handle h, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
+                             float *d_grad_weights)
+{
+    CHECK_H(h);
+    BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
+    rq.compat_form = h->eng.n_compat > 0;                 // (section 1e: the gradients of the forward with the matrices)
+    return backward_call(backward_target(h), rq, kGradUnaryRequired);
+}
+
+// --------------------------------------------------------------------------------------
+// section 1d: ... and with respect to the features of the pairwise terms
+
+int lccrf_inference_backward_features(lccrf_handle h, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
+                                      float *d_grad_weights, float *const *d_grad_features)
+{
+    CHECK_H(h);
+    if (h->eng.n_compat) return fail(LCCRF_E_STATE, "feature gradients are not available while a term has a label-compatibility matrix");
+    BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
+    rq.grad_features = d_grad_features;
+    return backward_call(backward_target(h), rq, kGradUnaryOptional);
+}
+
+// --------------------------------------------------------------------------------------
+// section 1e: ... and with respect to the label-compatibility matrices
+
+int lccrf_inference_backward_compat(lccrf_handle h, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
+                                    float *d_grad_weights, float *d_grad_compat)
+{
+    if (!d_grad_compat) return lccrf_inference_backward(h, n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights);
+    CHECK_H(h);
+    BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
+    rq.grad_compat = d_grad_compat;
+    rq.compat_form = true;
+    return backward_call(backward_target(h), rq, kGradUnaryOptional);
+}
+
+// --------------------------------------------------------------------------------------
+// section 2c: gradients of a batch's inference
+
+int lccrf_batch_inference_backward(lccrf_batch_handle b, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
+                                   float *d_grad_weights, void *stream)
+{
+    CHECK_H(b);
+    const BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
+    return backward_call(backward_target(b, stream), rq, kGradUnaryRequired);
+}
+
+// --------------------------------------------------------------------------------------
+// section 2d: ... and with respect to the features of the pairwise terms
+
+int lccrf_batch_inference_backward_features(lccrf_batch_handle b, int n_iterations, float relax, const float *d_grad_prob,
+                                            float *d_grad_unary, float *d_grad_weights, float *const *d_grad_features, void *stream)
+{
+    CHECK_H(b);
+    BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
+    rq.grad_features = d_grad_features;
+    return backward_call(backward_target(b, stream), rq, kGradUnaryOptional);
+}
+
+}  // extern "C"

@@ -208,7 +208,7 @@ void launch_validate_npoints(const int *in, int *out, int F, int maxN, int *bad,
 
 // ---- mean-field backward (csrc/meanfield_backward.hip; include/lccrf.h sections 1c - 1e and 2c - 2d) ------------------------
 // One backward call, of a handle or of a batch (F frames of up to `rows` points; a handle is a batch of one): what every
-// lccrf_*inference_backward* entry point fills in and hands to the one path behind them (api.hip: backward_call).
+// lccrf_*inference_backward* entry point fills in and hands to the one path behind them (api_backward.hip: backward_call).
 struct BackwardRequest {           // (an aggregate: the members left out of a braced list are null / false)
     int T;                          // n_iterations
     float relax;

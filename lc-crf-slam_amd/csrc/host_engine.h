@@ -1,0 +1,270 @@
+// host_engine.h -- the host-side state machine behind the C-ABI: one Engine per handle or batch.
+//
+// Host code only (no kernel): device memory, lattice builds, locality mode, engine choice, the late-bound one-launch run with its
+// per-frame fallback, the done-word protocol, the backward area and the compatibility matrices.  The bodies are in
+// host_engine.hip; the entry points of include/lccrf.h (api_*.hip) read and write the fields below directly.
+#pragma once
+
+#include "engine.h"
+
+#include <vector>
+
+namespace lccrf {
+
+// Sets the calling thread's error text (lccrf_last_error) and returns `code`.  Defined once, in api_tools.hip.
+int fail(int code, const char *fmt, ...);
+
+#define HIP_TRY(expr)                                                                        \
+    do {                                                                                     \
+        hipError_t e_ = (expr);                                                              \
+        if (e_ != hipSuccess)                                                                \
+            return fail(e_ == hipErrorOutOfMemory ? LCCRF_E_NOMEM : LCCRF_E_HIP, "%s: %s",  \
+                        #expr, hipGetErrorString(e_));                                       \
+    } while (0)
+
+// spin-wait hint of the host polls (the library must build on non-x86 ROCm hosts too)
+inline void cpu_relax()
+{
+#if defined(__x86_64__) || defined(__i386__)
+    __builtin_ia32_pause();
+#elif defined(__aarch64__)
+    asm volatile("yield" ::: "memory");
+#endif
+}
+
+// Owns every device / pinned allocation of one engine.
+struct Arena {
+    std::vector<void *> dev, pinned;
+    // Allocations are zeroed ON THE STREAM THE OWNER'S WORK IS ISSUED ON (StreamScope retargets this together with
+    // Engine::stream while a batch call runs on a caller's stream: a lazily allocated buffer zeroed on the engine's
+    // own stream would be unordered with the kernels of that call -- ADVICE r3).  hipMemset on the null stream is
+    // asynchronous and the engine streams are non-blocking, i.e. unordered with the null stream: a null-stream
+    // memset could land after the first copy into the new buffer (seen as a one-in-hundreds lattice
+    // of all-zero features).
+    hipStream_t stream = nullptr;
+    template <typename T>
+    int alloc(T **out, size_t count, bool zero = true)
+    {
+        void *p = nullptr;
+        const size_t bytes = (count ? count : 1) * sizeof(T);
+        HIP_TRY(hipMalloc(&p, bytes));
+        dev.push_back(p);
+        if (zero) {
+            HIP_TRY(hipMemsetAsync(p, 0, bytes, stream));
+            if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
+        }
+        *out = static_cast<T *>(p);
+        return LCCRF_OK;
+    }
+    template <typename T>
+    int alloc_pinned(T **out, size_t count)
+    {
+        void *p = nullptr;
+        // fine-grained (coherent) on purpose, not left to HIP_HOST_COHERENT: kernels publish status words, done words and labels
+        // here and the host reads them while the kernel is still running
+        HIP_TRY(hipHostMalloc(&p, (count ? count : 1) * sizeof(T), hipHostMallocCoherent));
+        pinned.push_back(p);
+        *out = static_cast<T *>(p);
+        return LCCRF_OK;
+    }
+    void release()
+    {
+        for (void *p : dev) (void)hipFree(p);
+        for (void *p : pinned) (void)hipHostFree(p);
+        dev.clear();
+        pinned.clear();
+    }
+};
+
+struct KernelState {
+    KernelDev dev{};
+    float *feat_own = nullptr;    // device copy of host-provided features
+    float *feat_stage = nullptr;  // pinned staging for the object API
+    int maxV = 0;                 // max over frames of V once known, else Epad
+    int maxRow = 0;               // max over frames of the longest CSR row
+};
+
+// One CRF problem set: F frames x maxN points x L labels, K kernels.
+struct Engine {
+    // ---- shape and buffers ----
+    int device = 0;
+    hipStream_t stream = nullptr;
+    Arena mem;
+    int Fcap = 0, F = 0, maxN = 0, maxNpad = 0, L = 0;
+    int activeN = 0;                   // largest frame of the current inputs if known on the host, else 0
+    CrfDev crf{};
+    int *npoints_own = nullptr;
+    float *unary_own = nullptr;
+    int16_t *label_own = nullptr;
+    hipEvent_t ev_order = nullptr;     // orders a caller-supplied stream against the engine's own (StreamScope)
+    int *npoints_bad = nullptr;        // pinned: set by the validation kernel when a bound n_points[f] is outside [0, maxN]
+    float *io_a = nullptr, *io_b = nullptr;   // device [Fcap][maxN][L] each: caller buffers of apply / expAndNormalize / ... (lazy)
+    int16_t *io_map = nullptr;
+    bool unary_set = false, built = false, sizes_known = false, started = false;
+
+    // ---- lattices and their sizes ----
+    int *V_host = nullptr;             // pinned [K][Fcap]
+    int *row_host = nullptr;           // pinned [K][Fcap]
+    int *long_host = nullptr;          // pinned [K][Fcap]: rows beyond kLongRowMin entries per frame (KernelDev::longcnt)
+    std::vector<KernelState> kernels;
+    std::vector<KernelState> spare;    // allocated lattices of earlier uses of this (recycled) engine
+    std::vector<KernelDev> kdevs;      // contiguous copy handed to the launchers
+    std::vector<int> maxV, maxRow;
+    int built_upto = 0;                // kernels [0, built_upto) have their lattice
+
+    // ---- engine choice ----
+    int engine_pref = 0, engine_used = 1;   // engine_used is REPORT-only state (lccrf_batch_get_engine): 1 streaming, 2 fused, 3 one launch per frame
+    int sized_engine = 1;              // what learn_sizes() chose for inference on lattices that sit in HBM (1 or 2)
+    int last_with_map = 0;             // did the last inference produce MAP labels?
+    size_t fused_lds = 0;
+    int fused_shape = 0;               // report only: what the last fused inference launched (launch_inference_fused)
+    LeanPrep lean_prep;                // prepared launch records of the two-frames-per-CU inference kernel (engine.h)
+    bool fused_fits = false;           // learn_sizes(): the lattices now in HBM fit the fused engine
+
+    // ---- deferred unaries ----
+    // setUnaryEnergyFromLabel is deferred: the labels wait in pinned memory and either the late-bound
+    // fused kernel derives the energies itself or ensure_unary() launches the small kernel.
+    bool unary_deferred = false;
+    const int16_t *deferred_label = nullptr;
+    UnaryTable deferred_tbl{};
+    bool unary_is_label = false;       // the unaries come from labels (re-derivable in any order) rather than from a raw array
+
+    // ---- the late-bound one-launch run, the done word and the label polling ----
+    // Late-bound fused inference (object API): queued right behind the build, before the host has seen
+    // the lattice sizes; `late_status` (pinned) tells afterwards whether the frame fitted.
+    int *late_status = nullptr;
+    bool late_ok = false;              // set by the object API: single frame, automatic engine choice
+    bool late_pending = false;
+    int late_iter = 0, late_map = 0;
+    float late_relax = 1.0f;
+    // Called by resolve_late() right behind a re-run of flagged frames (before its final synchronisation): the owner of host-side
+    // copies of the results (the batch's download pipe) re-queues them, whichever entry point happened to settle the run.
+    int (*after_rerun)(void *) = nullptr;
+    void *after_rerun_ctx = nullptr;
+    static constexpr int kDualMaxFrames = 64;    // (measured, `scripts/small_batch_latency.py`: 4 frames 98 -> 86 us, 32 frames 93 -> 83 us, 128 frames 112 -> 114 us)
+    bool opt_single_wg = false;        // LCCRF_OPT_SINGLE_WORKGROUP: never the two-workgroup form (lccrf_set_option)
+    unsigned *dual_area = nullptr;     // hand-off area of the two-workgroup form of the frame kernel (batches of up to kDualMaxFrames frames)
+    unsigned dual_epoch = 0;
+    // object API: the frame kernel's last act is a store of `done_epoch` into this pinned word, behind its results; the host
+    // polls it instead of waiting for the runtime's completion signal (which arrives a few microseconds later)
+    unsigned *done_word = nullptr;
+    unsigned done_epoch = 0;
+    bool done_armed = false;
+    // ... and with_map launches of the object API do not even wait for that word: the host pre-fills the pinned label array
+    // with -1 and takes each label as it arrives (the kernel's last stores; no fence, no acknowledgement round trip)
+    int16_t *map_host = nullptr;       // the handle's pinned label array (= crf.map), or null
+    bool labels_armed = false;
+    bool idle_by_done = false;         // the last call on the handle was a getMap() that saw the done word: nothing is in flight
+    bool idle_needs_done = false;      //   ... or every label (the stores right before the done word): the word itself is still to come
+    bool park_check = false;           // parked with that word still unseen: ensure_parked_idle() settles it for the next user
+
+    // ---- per-frame fallback ----
+    // Per-frame fallback of the one-launch kernel: k_frame leaves 1 in frame_status[f] for a frame whose lattices do not
+    // fit its LDS plan; resolve_late() gathers exactly those frames into the sub-engine `fb`, runs the two-kernel path
+    // there and scatters Q / labels / V back.
+    int *frame_status = nullptr;       // device [Fcap]
+    int *frame_status_host = nullptr;  // pinned [Fcap]
+    int *fb_list = nullptr;            // device [Fcap]: frames being re-run
+    int *fb_list_host = nullptr;       // pinned [Fcap]
+    Engine *fb = nullptr;
+    int fallback_frames = 0;           // frames the last one-launch run had to re-run (report only)
+    bool frame_small_ok = true;        // small frames may run as 512-lane workgroups (two per CU); turned off for this engine when
+    bool frame_small_used = false;     //   more than 1/8 of a batch's frames did not fit that plan
+    bool frame_lean_ok = true;         // ... and so may batches of full-size frames (frame_lean.hip), under the same rule
+    bool frame_lean_used = false;
+    unsigned char *lean_rec = nullptr; //   [lean_rec_frames][kLeanRecBytes] per-point records of that kernel (lazy, sized for the frames bound)
+    int lean_rec_frames = 0;
+
+    // ---- locality mode and the sorted build ----
+    // Locality mode (batch engines, frames of >= kPermMinPoints points on the streaming engine): the lattices are built
+    // with the points in an internal Z-order of their lattice cells (stream_engine.hip: launch_sort_points); Q, next and
+    // the unaries of the iteration live in that order (Qp, unary_p / unary_own) and Q is un-permuted on the way out.
+    static constexpr int kPermMinPointsDefault = 8192;
+    bool allow_perm = false;           // set by lccrf_batch_create, and by lccrf_create for handles of >= kPermMinPoints points ...
+    bool perm_scoped = false;          // ... where it only applies to lattices that are first asked for by inference() (perm_scope): every
+    bool perm_scope = false;           //   other entry point of the object API (stepwise inference, PairwisePotential::apply, the lattice
+    bool perm_banned = false;          //   probes) works on the caller's point order -- such a handle is built, or re-built once, the plain way
+    bool perm_on = false;              // the lattices now in HBM were built in locality mode
+    bool unary_p_valid = false;        // unary_p holds the raw unaries in the current internal order
+    SortScratch sort{};
+    float *Qp = nullptr, *unary_p = nullptr;   // [Fcap][maxN][L]
+    bool sort_scratch_complete = false;
+    int opt_vertex_order = 0;          // LCCRF_OPT_VERTEX_ORDER: 0 automatic (= on), 1 on, 2 off -- locality mode's sorted build
+    bool vorder_on = false;            // ... as decided by the last build of every kernel
+    bool vorder_broken = false;        // a frame's code space overflowed (*sort.vbad): this engine keeps to the hash build
+    int *ndist_host = nullptr;         // pinned [K][kNdistAxes]: the sorted build's largest neighbour distances (KernelDev::ndist)
+    int *tbl_bad = nullptr;            // pinned [2]: what the sorted build found wrong with its tables (KernelDev::tbl_bad)
+
+    // ---- backward area ----
+    // the area of lccrf_inference_backward / lccrf_batch_inference_backward (engine.h: BackwardArea): its own allocation, grown on
+    // demand and freed with the handle's use (recycle) -- a parked handle does not keep it -- or with the batch
+    unsigned char *bwd_area = nullptr;
+    size_t bwd_area_bytes = 0;
+
+    // ---- compatibility matrices ----
+    // section 1e (object API; a batch has none): the terms' label-compatibility matrices.  One device array for all of them,
+    // allocated by the first setter and kept with the handle; compat_ptr[k] is term k's [L][L] slice of it, or null (Potts).
+    // While n_compat > 0 the one-launch frame kernel and the fused engine, which hard-wire Potts, are not taken.
+    float *compat_dev = nullptr;       // [LCCRF_MAX_KERNELS][L][L]
+    float *compat_host = nullptr;      // pinned, the same shape: the matrices as set (the getter's answer and the uploads' source)
+    hipEvent_t compat_ev = nullptr;    // behind the last upload: a setter waits for it before it rewrites a source that may be in flight
+    const float *compat_ptr[LCCRF_MAX_KERNELS] = {};
+    int n_compat = 0;
+
+    // ---- timing ----
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // build begin/end, inference begin/end
+    bool timed_build = false, timed_inf = false;
+    bool event_timing = true;          // LCCRF_OPT_EVENT_TIMING: HIP events around every build / inference / run of the batch API
+
+    // ---- methods (host_engine.hip, in this order; the short ones here) ----
+    int init(int device_id, int frames, int max_points, int n_labels);
+    void destroy();
+    int add_kernel(int d, float w, bool own_features, bool stage);
+    void ensure_parked_idle();
+    void recycle();
+    void sync_views();
+    int need_io();
+    // every lattice is re-built (and its sizes learnt) by the next call that needs it; the prepared launch records are rewritten
+    void invalidate_lattices() { built_upto = 0; sizes_known = false; }
+    void invalidate_lean_prep() { lean_prep.valid = false; lean_prep.seen_key = 0; }
+    // new inputs (a batch's next frames, a parked handle's next user): nothing set, built or started, every lattice stale
+    void forget_inputs() { unary_set = built = started = false; invalidate_lattices(); }
+    // term k gets the weight w (settle a pending inference first): whatever was prepared for the old weights is rewritten
+    void set_weight(int k, float w) { kernels[k].dev.w = w; sync_views(); invalidate_lean_prep(); }
+
+    static int perm_min_points();
+    int ensure_sort_scratch();
+    int build_kernels(int k0, int n);
+    int build_kernel(int k) { return build_kernels(k, 1); }
+    int flush_builds();
+    int learn_sizes();
+    int ensure_plain();
+    int ensure_plain_batch();
+
+    UnaryTable label_table(const float *conf) const;
+    void defer_unary_from_label(const int16_t *label, const float *conf);
+    void bind_unary(const float *p);
+    int ensure_unary();
+
+    int start();
+    int step(float relax);
+    bool frame_ok() const;
+    int run_frame(int n_iter, int with_map, float relax);
+    int inference(int n_iter, int with_map, float relax);
+    int run(int n_iter, int with_map, float relax);
+    int inference_sized(int n_iter, int with_map, float relax);
+    int resolve_late(bool *seen_done = nullptr);
+    int rerun_frames(int n);
+
+    const float *const *compat_arg() const { return n_compat ? compat_ptr : nullptr; }
+    void choose_sized_engine() { sized_engine = fused_fits && !n_compat ? 2 : 1; }
+    void clear_compat();
+    int set_compat(int k, const float *m);
+
+    void free_backward_area();
+    int ensure_backward_area(size_t need);
+    size_t backward_need(const BackwardRequest &rq, size_t slice, int rows) const;
+    int backward(const BackwardRequest &rq, size_t slice, int rows);
+};
+
+}  // namespace lccrf

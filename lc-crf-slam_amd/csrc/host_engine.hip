@@ -1,0 +1,948 @@
+// host_engine.hip -- the bodies of host_engine.h: the host-side state machine of one handle or batch.
+//
+// Host-side glue only: device memory, pinned staging, launch order.  All arithmetic of the path runs in the kernels
+// (stream_engine.hip / fused_engine.hip); the only numbers computed here are the per-kernel constants of
+// permutohedral_cpu.h:249,282-285,681 and the 2L+1 unary energies of densecrf3d.h:109-115, which the reference also computes
+// once, outside its loops.
+#include "host_engine.h"
+
+#include <cmath>
+#include <algorithm>
+#include <cstring>
+#include <new>
+#include <atomic>
+#include <chrono>
+
+namespace lccrf {
+
+namespace {
+
+// Bounded spin on a pinned done word: true once it shows `epoch` (the frame kernel's last store), false after `limit`; the clock is
+// read every `check_every` spins (a power of two).  Either way an acquire fence orders the reads that follow behind the word.
+inline bool poll_done_word(const unsigned *word, unsigned epoch, std::chrono::microseconds limit, unsigned check_every)
+{
+    const volatile unsigned *w = word;
+    const auto t0 = std::chrono::steady_clock::now();
+    bool seen = false;
+    for (unsigned spins = 1; !(seen = (*w == epoch)); ++spins) {
+        if ((spins & (check_every - 1)) == 0 && std::chrono::steady_clock::now() - t0 > limit) break;
+        cpu_relax();
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return seen;
+}
+
+int next_pow2(long v)
+{
+    long p = 16;
+    while (p < v) p <<= 1;
+    return (int)p;
+}
+}  // namespace
+
+void Engine::clear_compat()
+{
+    for (int k = 0; k < LCCRF_MAX_KERNELS; ++k) compat_ptr[k] = nullptr;
+    n_compat = 0;
+    choose_sized_engine();
+}
+
+// m: host [L][L] (finite, checked by the caller) or null.  Touches no lattice, norm or prepared record.
+int Engine::set_compat(int k, const float *m)
+{
+    const size_t ll = (size_t)L * L;
+    if (m) {
+        if (!compat_dev) {
+            int rc = mem.alloc_pinned(&compat_host, (size_t)LCCRF_MAX_KERNELS * ll);
+            if (!rc) rc = mem.alloc(&compat_dev, (size_t)LCCRF_MAX_KERNELS * ll);
+            if (rc) { compat_dev = nullptr; return rc; }
+            HIP_TRY(hipEventCreateWithFlags(&compat_ev, hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(compat_ev, stream));
+        }
+        HIP_TRY(hipEventSynchronize(compat_ev));        // (an earlier upload may still be reading the pinned copy)
+        memcpy(compat_host + k * ll, m, ll * sizeof(float));   // (the caller's array is free again when the call returns)
+        HIP_TRY(hipMemcpyAsync(compat_dev + k * ll, compat_host + k * ll, ll * sizeof(float), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipEventRecord(compat_ev, stream));
+    }
+    const float *p = m ? compat_dev + k * ll : nullptr;
+    n_compat += (p != nullptr) - (compat_ptr[k] != nullptr);
+    compat_ptr[k] = p;
+    choose_sized_engine();
+    return LCCRF_OK;
+}
+
+void Engine::free_backward_area()
+{
+    if (!bwd_area) return;
+    if (stream) (void)hipStreamSynchronize(stream);
+    (void)hipFree(bwd_area);
+    bwd_area = nullptr;
+    bwd_area_bytes = 0;
+}
+
+// at least `need` bytes of area, zeroed on the call's stream when (re)allocated; a failed allocation leaves the engine without one
+// and changes nothing else
+int Engine::ensure_backward_area(size_t need)
+{
+    if (need <= bwd_area_bytes) return LCCRF_OK;
+    free_backward_area();
+    void *p = nullptr;
+    const hipError_t ea = hipMalloc(&p, need);
+    if (ea != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ea == hipErrorOutOfMemory ? LCCRF_E_NOMEM : LCCRF_E_HIP, "hipMalloc(%zu bytes) for the backward area: %s", need,
+                    hipGetErrorString(ea));
+    }
+    bwd_area = static_cast<unsigned char *>(p);
+    bwd_area_bytes = need;
+    HIP_TRY(hipMemsetAsync(p, 0, need, stream));
+    return LCCRF_OK;
+}
+
+// The area request `rq` takes on frames of up to `rows` points, in bytes (engine.h: backward_layout) ...
+size_t Engine::backward_need(const BackwardRequest &rq, size_t slice, int rows) const
+{
+    return backward_layout(rq, crf, kdevs.data(), slice, rows, nullptr, nullptr);
+}
+
+// ... and the backward on it: inference(T, 0, relax) replayed on the step path (start + T x step), the F * rows * L floats of Q
+// kept per iteration in arrays of `slice` floats, dL/dQ_T copied in, then the reverse sweep over frames of up to `rows` points.
+int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
+{
+    const int K = (int)kernels.size(), T = rq.T;
+    const size_t count = (size_t)F * rows * L;
+    BackwardArea ar{};
+    backward_layout(rq, crf, kdevs.data(), slice, rows, reinterpret_cast<float *>(bwd_area), &ar);
+    int rc = start();                                 // (ensure_plain: a handle's frames in locality mode are re-built the plain way once)
+    if (!rc) rc = learn_sizes();
+    if (rc) return rc;
+    for (int t = 0; t < T; ++t) {
+        if (count) HIP_TRY(hipMemcpyAsync(ar.hist + (size_t)t * slice, crf.Q, count * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        if ((rc = step(rq.relax))) return rc;
+    }
+    if (rq.grad_compat && K && (!count || T == 0))    // nothing depends on the matrices: exactly 0
+        HIP_TRY(hipMemsetAsync(rq.grad_compat, 0, (size_t)K * L * L * sizeof(float), stream));
+    if (!count) {                                     // nothing to differentiate: dL/dw = 0
+        if (rq.grad_weights && K) HIP_TRY(hipMemsetAsync(rq.grad_weights, 0, (size_t)F * K * sizeof(float), stream));
+        return LCCRF_OK;
+    }
+    for (int k = 0; k < K && rq.grad_features; ++k) {
+        if (!rq.grad_features[k]) continue;
+        if (T == 0)                                   // nothing depends on the features: exactly 0
+            HIP_TRY(hipMemsetAsync(rq.grad_features[k], 0, (size_t)F * rows * kernels[k].dev.d * sizeof(float), stream));
+        else
+            HIP_TRY(hipMemsetAsync(ar.gb[k], 0, ar.feat_floats[k] * sizeof(float), stream));
+    }
+    HIP_TRY(hipMemcpyAsync(ar.G, rq.grad_prob, count * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    launch_backward_sweep(crf, kdevs.data(), maxV.data(), rows, rq, ar, compat_arg(), stream);
+    HIP_TRY(hipGetLastError());
+    return LCCRF_OK;
+}
+
+int Engine::need_io()
+{
+    if (io_a) return LCCRF_OK;
+    const size_t nl = (size_t)Fcap * maxN * L;
+    int rc;
+    if ((rc = mem.alloc(&io_a, nl))) return rc;
+    if ((rc = mem.alloc(&io_b, nl))) return rc;
+    if ((rc = mem.alloc(&io_map, (size_t)Fcap * maxN))) return rc;
+    HIP_TRY(hipStreamSynchronize(stream));
+    return LCCRF_OK;
+}
+
+int Engine::perm_min_points()
+{
+    static const char *e = ab_env("LCCRF_PERM_MIN");                         // A/B switch (same results): locality mode from this many points
+    static const int v = e ? std::max(atoi(e), 64) : kPermMinPointsDefault;
+    return v;
+}
+
+int Engine::ensure_sort_scratch()
+{
+    // (complete or nothing: an allocation that fails half way -- E_NOMEM -- must not leave a later build with some of the
+    // arrays null; what a failed attempt did allocate stays with the arena until the engine goes -- ADVICE r4)
+    if (sort_scratch_complete) return LCCRF_OK;
+    int bits = 8;
+    while (bits < 16 && (1 << bits) < 2 * maxN) ++bits;
+    sort.bits = bits;
+    const size_t nbk = ((size_t)1 << bits) + 1, Fz = (size_t)Fcap;
+    int rc;
+    if ((rc = mem.alloc(&sort.cells, Fz * maxNpad * kMaxD))) return rc;
+    if ((rc = mem.alloc(&sort.partial, Fz * ((maxNpad + 255) / 256 + 1) * 2 * kMaxD))) return rc;
+    if ((rc = mem.alloc(&sort.plan, Fz * 3 * kMaxD))) return rc;
+    if ((rc = mem.alloc(&sort.code, Fz * maxNpad))) return rc;
+    if ((rc = mem.alloc(&sort.hist, Fz * nbk))) return rc;
+    if ((rc = mem.alloc(&sort.start, Fz * nbk))) return rc;
+    if ((rc = mem.alloc(&sort.tiles, Fz * ((nbk + 4095) / 4096 + 1)))) return rc;
+    if ((rc = mem.alloc(&sort.perm, Fz * maxNpad))) return rc;
+    if ((rc = mem.alloc(&sort.iperm, Fz * maxNpad))) return rc;
+    if ((rc = mem.alloc(&Qp, Fz * maxN * L))) return rc;
+    if ((rc = mem.alloc(&unary_p, Fz * maxN * L))) return rc;
+    // the vertex order of every kernel (one kernel at a time on the engine's stream: one set of arrays sized for the largest)
+    int vcap = 0;
+    for (auto &ks : kernels) vcap = std::max(vcap, ks.dev.Epad);
+    for (auto &ks : spare) vcap = std::max(vcap, ks.dev.Epad);
+    sort.vcap = vcap;
+    int vbits = 10;
+    while (vbits < 21 && (1 << vbits) < 4 * vcap) ++vbits;
+    sort.vbits = vbits;
+    const size_t vnbk = ((size_t)1 << vbits) + 1;
+    if ((rc = mem.alloc(&sort.vcode, Fz * vcap))) return rc;
+    if ((rc = mem.alloc(&sort.vkey, Fz * vcap))) return rc;
+    if ((rc = mem.alloc(&sort.vph, Fz * 64))) return rc;
+    if ((rc = mem.alloc_pinned(&sort.vbad, 1))) return rc;
+    *sort.vbad = 0;
+    if ((rc = mem.alloc(&sort.vhist, Fz * vnbk))) return rc;
+    if ((rc = mem.alloc(&sort.vstart, Fz * vnbk))) return rc;
+    if ((rc = mem.alloc(&sort.vtiles, Fz * ((vnbk + 4095) / 4096 + 1)))) return rc;
+    if ((rc = mem.alloc(&sort.vpartial, Fz * ((maxNpad + 255) / 256 + 1) * 2 * kMaxD))) return rc;
+    if ((rc = mem.alloc(&sort.vplan, Fz * (2 * kMaxD + 3)))) return rc;
+    sort_scratch_complete = true;
+    return LCCRF_OK;
+}
+
+int Engine::init(int device_id, int frames, int max_points, int n_labels)
+{
+    device = device_id;
+    Fcap = F = frames;
+    maxN = max_points;
+    maxNpad = (max_points + 3) & ~3;
+    L = n_labels;
+    HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    mem.stream = stream;
+    for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventCreateWithFlags(&ev_order, hipEventDisableTiming));
+    const size_t nl = (size_t)Fcap * maxN * L;
+    int rc;
+    if ((rc = mem.alloc(&npoints_own, Fcap))) return rc;
+    if ((rc = mem.alloc(&unary_own, nl))) return rc;
+    if ((rc = mem.alloc(&crf.Q, nl))) return rc;
+    if ((rc = mem.alloc(&crf.next, nl))) return rc;
+    if ((rc = mem.alloc(&crf.map, (size_t)Fcap * maxN))) return rc;
+    crf.bits_stride = (maxN + 63) / 64;
+    if (n_labels == 2 && (rc = mem.alloc(&crf.map_bits, (size_t)Fcap * std::max(crf.bits_stride, 1)))) return rc;
+    if ((rc = mem.alloc(&label_own, (size_t)Fcap * maxN))) return rc;
+    if ((rc = mem.alloc_pinned(&V_host, (size_t)LCCRF_MAX_KERNELS * Fcap))) return rc;
+    if ((rc = mem.alloc_pinned(&row_host, (size_t)LCCRF_MAX_KERNELS * Fcap))) return rc;
+    if ((rc = mem.alloc_pinned(&long_host, (size_t)LCCRF_MAX_KERNELS * Fcap))) return rc;
+    if ((rc = mem.alloc_pinned(&late_status, 1))) return rc;
+    *late_status = 0;
+    if ((rc = mem.alloc_pinned(&done_word, 1))) return rc;
+    *done_word = 0;
+    if ((rc = mem.alloc(&frame_status, Fcap))) return rc;
+    if ((rc = mem.alloc(&fb_list, Fcap))) return rc;
+    if ((rc = mem.alloc_pinned(&frame_status_host, Fcap))) return rc;
+    if ((rc = mem.alloc_pinned(&fb_list_host, Fcap))) return rc;
+    if ((rc = mem.alloc_pinned(&npoints_bad, 1))) return rc;
+    *npoints_bad = 0;
+    crf.F = F;
+    crf.maxN = maxN;
+    crf.L = L;
+    crf.K = 0;
+    crf.n_points = npoints_own;
+    crf.unary = unary_own;
+    return LCCRF_OK;
+}
+
+void Engine::destroy()
+{
+    park_check = false;
+    if (stream) (void)hipStreamSynchronize(stream);
+    free_backward_area();
+    if (fb) {
+        fb->destroy();
+        delete fb;
+        fb = nullptr;
+    }
+    mem.release();
+    for (auto &e : ev)
+        if (e) (void)hipEventDestroy(e);
+    if (ev_order) (void)hipEventDestroy(ev_order);
+    if (compat_ev) (void)hipEventDestroy(compat_ev);
+    compat_ev = nullptr;
+    compat_dev = compat_host = nullptr;
+    if (lean_prep.ev0) (void)hipEventDestroy(lean_prep.ev0);
+    if (lean_prep.ev1) (void)hipEventDestroy(lean_prep.ev1);
+    lean_prep = LeanPrep{};
+    if (stream) (void)hipStreamDestroy(stream);
+    stream = nullptr;
+}
+
+// Allocate the lattice of one more pairwise kernel (all frames).
+int Engine::add_kernel(int d, float w, bool own_features, bool stage)
+{
+    if ((int)kernels.size() >= LCCRF_MAX_KERNELS)
+        return fail(LCCRF_E_CAPACITY, "at most %d pairwise kernels", LCCRF_MAX_KERNELS);
+    if (d < 1 || d > LCCRF_MAX_DIMS) return fail(LCCRF_E_INVALID, "feature dims %d not in [1,%d]", d, LCCRF_MAX_DIMS);
+    for (size_t i = 0; i < spare.size(); ++i) {     // a recycled engine already owns a lattice of this shape
+        if (spare[i].dev.d == d && (!stage || spare[i].feat_stage) && (!own_features || spare[i].feat_own)) {
+            KernelState ks = spare[i];
+            spare.erase(spare.begin() + i);
+            ks.dev.w = w;
+            ks.dev.feat = ks.feat_own;
+            ks.maxV = ks.dev.Epad;
+            ks.maxRow = 0;
+            kernels.push_back(ks);
+            sync_views();
+            return LCCRF_OK;
+        }
+    }
+    KernelState ks;
+    KernelDev &k = ks.dev;
+    k.d = d;
+    k.D1 = d + 1;
+    k.maxN = maxN;
+    k.maxNpad = maxNpad;
+    k.Epad = maxNpad * k.D1;
+    k.cap = next_pow2(2L * k.Epad);
+    // lattice values of a frame: [0, L) unused, [L, 2L) the all-zero "absent neighbour" (vertex -1), vertex v at
+    // vbase + v*L; with L = 2 and an even stride, vertex pairs (2t, 2t+1) are 16-byte aligned (k_blur2)
+    k.vstride = (k.Epad + 2) * L;
+    k.vbase = 2 * L;
+    k.w = w;
+    // permutohedral_cpu.h:681 / :249 / :282-285 (quirk Q4): same expressions, same types
+    k.alpha = 1.0f / (1 + powf(2, -d));
+    k.inv_dp1 = 1.0f / (d + 1);
+    const float inv_std_dev = sqrt(2.0 / 3.0) * (d + 1);
+    for (int i = 0; i < d; ++i) k.scale[i] = (float)(1.0 / sqrt((double)((i + 2) * (i + 1))) * inv_std_dev);
+    const size_t Fz = (size_t)Fcap, E = (size_t)k.Epad;
+    int rc;
+    if ((rc = mem.alloc(&k.rem0, Fz * maxNpad * d))) return rc;
+    if ((rc = mem.alloc(&k.rank, Fz * maxNpad * d))) return rc;
+    if ((rc = mem.alloc(&k.bary, Fz * E))) return rc;
+    if ((rc = mem.alloc(&k.offset, Fz * E))) return rc;
+    if ((rc = mem.alloc(&k.slot, Fz * k.cap))) return rc;
+    if ((rc = mem.alloc(&k.slot_of, Fz * E))) return rc;
+    if ((rc = mem.alloc(&k.flag, Fz * (E + 1)))) return rc;
+    if ((rc = mem.alloc(&k.prefix, Fz * (E + 1)))) return rc;
+    if ((rc = mem.alloc(&k.rep, Fz * E))) return rc;
+    if ((rc = mem.alloc(&k.V, Fz))) return rc;
+    if ((rc = mem.alloc(&k.rowmax, Fz))) return rc;
+    if ((rc = mem.alloc(&k.nbr, Fz * k.D1 * E * 2))) return rc;
+    // one frame in flight, large frames (the object API's handles are sized for SLAM frames, which run on the one-workgroup engines):
+    // the blur passes go two per launch and read a two-hop neighbour table
+    if (Fcap == 1 && L == 2 && allow_perm && (rc = mem.alloc(&k.nbr2, (size_t)(k.D1 / 2) * E * 8))) return rc;
+    if (L == 2 && allow_perm && maxN >= perm_min_points()) {
+        if (!tbl_bad) {
+            if ((rc = mem.alloc_pinned(&tbl_bad, 2))) return rc;
+            tbl_bad[0] = tbl_bad[1] = 0;
+        }
+        k.tbl_bad = tbl_bad;
+        if ((rc = mem.alloc(&k.fastn, Fz * E))) return rc;
+        if ((rc = mem.alloc(&k.ndist, (size_t)kNdistAxes))) return rc;
+        if ((rc = mem.alloc(&k.nearoff, Fz * 2 * E * 2))) return rc;
+        if (!ndist_host && (rc = mem.alloc_pinned(&ndist_host, (size_t)LCCRF_MAX_KERNELS * kNdistAxes))) return rc;
+    }
+    // large frames, a few in flight: the sorted build also leaves the neighbour table in its compact form (16-bit offsets), for
+    // the batches of kNbrcMinFrames..kNbrcMaxFrames frames this engine may see
+    if (k.tbl_bad && Fcap >= kNbrcMinFrames) {
+        const size_t Fc = (size_t)std::min(Fcap, kNbrcMaxFrames);
+        if ((rc = mem.alloc(&k.nbrc, Fc * k.D1 * E * 2))) return rc;
+        if ((rc = mem.alloc(&k.nbrc_base, Fc * k.D1 * (E / kNbrcBlock + 1) * 2))) return rc;
+    }
+    if ((rc = mem.alloc(&k.rowptr, Fz * (E + 1)))) return rc;
+    // (frames of the one-workgroup engines' range keep their rows in LDS there; on the streaming engine they are summed in line: a
+    // batch engine for 16 384 SLAM frames would carry 270 MB of lists per kernel)
+    if (maxN > kLongRowListMinPoints) {
+        if ((rc = mem.alloc(&k.longrow, Fz * kLongRowCap))) return rc;
+        if ((rc = mem.alloc(&k.longcnt, Fz))) return rc;
+    }
+    if ((rc = mem.alloc(&k.csr_pt, Fz * E))) return rc;
+    if ((rc = mem.alloc(&k.csr_w, Fz * E))) return rc;
+    if ((rc = mem.alloc(&k.csr_pos, Fz * E))) return rc;
+    if ((rc = mem.alloc(&k.pk, Fz * E))) return rc;
+    if ((rc = mem.alloc(&k.nbr16, Fz * k.D1 * E))) return rc;
+    if ((rc = mem.alloc(&k.norm, Fz * maxN))) return rc;
+    if ((rc = mem.alloc(&k.val0, Fz * k.vstride))) return rc;
+    if ((rc = mem.alloc(&k.val1, Fz * k.vstride))) return rc;
+    if (own_features) {
+        if ((rc = mem.alloc(&ks.feat_own, Fz * maxN * d))) return rc;
+        k.feat = ks.feat_own;
+    }
+    if (stage)
+        if ((rc = mem.alloc_pinned(&ks.feat_stage, Fz * maxN * d))) return rc;
+    ks.maxV = k.Epad;
+    kernels.push_back(ks);
+    sync_views();
+    return LCCRF_OK;
+}
+
+// A parked engine whose last frame was taken label by label: its kernel is over once the done word shows this frame's epoch
+// (the kernel's very last store); normally that happened long ago, otherwise wait for the stream the ordinary way.
+void Engine::ensure_parked_idle()
+{
+    if (!park_check) return;
+    park_check = false;
+    if (!poll_done_word(done_word, done_epoch, std::chrono::microseconds(50), 64) && stream) (void)hipStreamSynchronize(stream);
+}
+
+// Park everything for the next user of this engine (object API handle cache).
+void Engine::recycle()
+{
+    // (a synchronisation that starts after the kernel has ended costs ~10 us: the runtime queues a barrier packet and
+    // waits for its round trip; the done word has already told us that nothing is in flight)
+    // getMap() saw every label land: the kernel's last stores (V_out, frame_status, the done word) follow within a microsecond or
+    // two.  Nobody waits for them here (the tracker's next frame is 33 ms away); the next user of this handle settles it before it
+    // touches anything the kernel could still read or write (ensure_parked_idle, called by lccrf_create).
+    if (stream && idle_by_done && idle_needs_done) park_check = true;
+    else if (stream && !idle_by_done) (void)hipStreamSynchronize(stream);
+    idle_by_done = idle_needs_done = false;
+    labels_armed = done_armed = false;
+    free_backward_area();
+    for (auto &ks : kernels) spare.push_back(ks);
+    kernels.clear();
+    F = Fcap;
+    crf.unary = unary_own;
+    crf.n_points = npoints_own;
+    forget_inputs();
+    late_pending = false;
+    unary_deferred = false;
+    perm_on = vorder_on = perm_banned = perm_scope = false;      // (the next user's lattices decide afresh)
+    unary_is_label = unary_p_valid = false;
+    engine_pref = 0;
+    engine_used = 1;
+    clear_compat();                                   // (the next user's terms start as Potts terms)
+    sync_views();
+}
+
+void Engine::sync_views()
+{
+    kdevs.resize(kernels.size());
+    maxV.resize(kernels.size());
+    maxRow.resize(kernels.size());
+    for (size_t i = 0; i < kernels.size(); ++i) {
+        kernels[i].dev.V_host = V_host + i * Fcap;
+        kernels[i].dev.rowmax_host = row_host + i * Fcap;
+        kernels[i].dev.perm = perm_on ? sort.perm : nullptr;
+        kernels[i].dev.iperm = perm_on ? sort.iperm : nullptr;
+        kernels[i].dev.vorder = (perm_on && vorder_on && sort.vkey && kernels[i].dev.Epad <= sort.vcap) ? 1 : 0;
+        kdevs[i] = kernels[i].dev;
+        maxV[i] = kernels[i].maxV;
+        maxRow[i] = kernels[i].maxRow;
+    }
+    crf.K = (int)kernels.size();
+    crf.F = F;
+    crf.activeN = activeN;
+    crf.perm = perm_on ? sort.perm : nullptr;
+    crf.perm_stride = maxNpad;
+}
+
+// Lattice + normalisation of kernels [k0, k0+n) for every frame (PottsPotential3D ctor).
+// SLAM-size frames take the fused build (one launch for all of them when they share d);
+// anything else the streaming build (19 launches per kernel).
+int Engine::build_kernels(int k0, int n)
+{
+    for (int k = k0; k < k0 + n; ++k) kernels[k].maxV = kernels[k].dev.Epad;
+    if (k0 == 0) {                                     // a build of every kernel decides the internal point order afresh
+        static const bool no_perm = ab_env("LCCRF_NO_PERM") != nullptr;   // A/B and cross-check switch: same results either way
+        const int NAp = activeN > 0 ? activeN : maxN;
+        const bool want = allow_perm && !no_perm && !perm_banned && (!perm_scoped || perm_scope) && n > 0 && n == (int)kernels.size() && NAp >= perm_min_points();
+        if (want || perm_on) {                         // whatever was derived in the old order is stale
+            if (unary_is_label) unary_deferred = true;
+            unary_p_valid = false;
+        }
+        perm_on = false;
+        // ... and, with the points permuted, whether the lattices are built by SORTING the entries on the row-major code of their
+        // vertex (ids along the lattice's axes: the blur pass touches half as many lines) -- yes unless switched off: with the
+        // points in row-major order too it wins at every number of frames in flight (notes/r4_experiments.md section 2)
+        static const char *env_vo = ab_env("LCCRF_VERTEX_ORDER");               // A/B switch: 1 on, 0 off (same results)
+        const int vo = env_vo ? (atoi(env_vo) ? 1 : 2) : opt_vertex_order;
+        vorder_on = want && !vorder_broken && vo != 2;
+        sync_views();
+        if (want) {
+            int rcs = ensure_sort_scratch();
+            if (rcs) return rcs;
+            int src = 0;                               // one order for the whole CRF (Q is shared): the kernel with most dimensions decides
+            for (int k = 1; k < n; ++k)
+                if (kernels[k].dev.d > kernels[src].dev.d) src = k;
+            // with the sorted build the points follow the vertices: (coarse) row-major order of their cells in the lattice's own basis
+            // instead of the Z-order curve (C5 x 8: splat 30.5 -> 27.7, slice 24.2 -> 19.5 us, build 1.93 -> 1.76 ms)
+            sort.rm_points = vorder_on ? 1 : 0;
+            launch_sort_points(kdevs[src], crf, sort, stream);
+            HIP_TRY(hipGetLastError());
+            perm_on = true;
+        }
+    }
+    sync_views();
+    const bool no_small = ab_env("LCCRF_NO_FUSED_BUILD") != nullptr;   // debug / cross-check switch
+    int k = k0;
+    while (k < k0 + n) {
+        int m = 1;
+        const int NA = activeN > 0 ? activeN : maxN;
+        // (locality mode: the one-workgroup build knows nothing of the internal point order -- ADVICE r4: with the threshold lowered
+        // below its range it would have built in the caller's order under an engine that iterates in the permuted one)
+        const bool small_ok = !no_small && !perm_on;
+        if (small_ok && k + 1 < k0 + n && build_small_supported(&kdevs[k], 2, NA)) m = 2;
+        if (small_ok && build_small_supported(&kdevs[k], m, NA)) {
+            for (int u = 0; u < m; ++u) kernels[k + u].dev.nbr2_ok = kernels[k + u].dev.nbrc_ok = kernels[k + u].dev.fast0_ok = kernels[k + u].dev.longrow_ok = 0;
+            launch_build_small(&kdevs[k], m, NA, crf, stream);   // writes V / rowmax to the pinned mirrors itself
+        } else {
+            m = 1;
+            kernels[k].dev.nbr2_ok = kernels[k].dev.nbr2 != nullptr;      // (the streaming build fills the two-hop table when there is one)
+            kernels[k].dev.longrow_ok = kdevs[k].longrow_ok = kernels[k].dev.longrow != nullptr;   // (... and lists the long rows: the normalisation below reads the list)
+            kernels[k].dev.nbrc_ok = kernels[k].dev.nbrc != nullptr && kernels[k].dev.vorder && F >= kNbrcMinFrames && F <= kNbrcMaxFrames;   // (... and the sorted build the compact one)
+            kernels[k].dev.fast0_ok = kernels[k].dev.tbl_bad != nullptr && kernels[k].dev.vorder;
+            kernels[k].dev.nbr2_first = kernels[k].dev.fast0_ok;              // (what build_kernel_d derives from the same two fields)
+            launch_build_kernel(kdevs[k], crf, kernels[k].maxV, stream, perm_on ? &sort : nullptr);
+            launch_norm(kdevs[k], crf, kernels[k].maxV, stream);
+            HIP_TRY(hipMemcpyAsync(V_host + (size_t)k * Fcap, kernels[k].dev.V, sizeof(int) * F, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(row_host + (size_t)k * Fcap, kernels[k].dev.rowmax, sizeof(int) * F, hipMemcpyDeviceToHost, stream));
+            if (kernels[k].dev.longrow)
+                HIP_TRY(hipMemcpyAsync(long_host + (size_t)k * Fcap, kernels[k].dev.longcnt, sizeof(int) * F, hipMemcpyDeviceToHost, stream));
+            if (kernels[k].dev.fast0_ok)
+                HIP_TRY(hipMemcpyAsync(ndist_host + (size_t)k * kNdistAxes, kernels[k].dev.ndist, sizeof(int) * kNdistAxes, hipMemcpyDeviceToHost, stream));
+        }
+        k += m;
+    }
+    HIP_TRY(hipGetLastError());
+    sync_views();                                       // (nbr2_ok)
+    sizes_known = false;
+    return LCCRF_OK;
+}
+
+// After the builds: learn max V per kernel so inference grids are sized to the lattice.
+// Build every kernel added since the last build (object API: add_pairwise only stages features).
+int Engine::flush_builds()
+{
+    const int n = (int)kernels.size();
+    if (built_upto >= n) return LCCRF_OK;
+    const int k0 = built_upto;
+    built_upto = n;
+    return build_kernels(k0, n - k0);
+}
+
+int Engine::learn_sizes()
+{
+    int rc0 = flush_builds();
+    if (rc0) return rc0;
+    if (sizes_known) return LCCRF_OK;
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (*npoints_bad) {
+        *npoints_bad = 0;
+        return fail(LCCRF_E_CAPACITY, "a bound n_points[f] lies outside [0, max_points=%d] (the kernels clamped it)", maxN);
+    }
+    if (sort.vbad && *sort.vbad) {                     // a frame's vertices do not fit a 62-bit row-major code: hash build from now on
+        *sort.vbad = 0;
+        vorder_broken = true;
+        int rcb = build_kernels(0, (int)kernels.size());
+        if (rcb) return rcb;
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+#if LCCRF_INSTRUMENT
+    if (tbl_bad && ab_env("LCCRF_FAST0_BREAK")) tbl_bad[1] = 1;      // test hook: as if the build had found an axis-0 neighbour elsewhere
+#endif
+    if (tbl_bad && (tbl_bad[0] || tbl_bad[1])) {
+        // [0] a block's neighbours span more than 16 bits: the blur reads the 32-bit table; [1] an axis-0 neighbour that is not the
+        // next / previous id (cannot happen with exact codes -- checked all the same): the first blur pass keeps its own launch
+        for (auto &ks : kernels) {
+            if (tbl_bad[0]) ks.dev.nbrc_ok = 0;
+            if (tbl_bad[1]) ks.dev.fast0_ok = 0;
+        }
+#if LCCRF_INSTRUMENT
+        if (tbl_bad[0]) fprintf(stderr, "lccrf: compact neighbour table abandoned (a block's neighbours span more than its offsets hold)\n");
+        if (tbl_bad[1]) fprintf(stderr, "lccrf: first blur pass keeps its own launch (an axis-0 neighbour is not an adjacent id)\n");
+#endif
+        tbl_bad[0] = tbl_bad[1] = 0;
+    }
+    for (size_t k = 0; k < kernels.size(); ++k) {
+        // how many blur passes ride in the splat (sorted build): pass 0 always (adjacent ids); passes 1 and 2 when the largest id
+        // distances of their neighbours fit the halo of a window of up to 1024 vertices that keeps >= 3/4 of its lanes productive
+        KernelDev &kd = kernels[k].dev;
+        kd.splat_passes = kd.fast0_ok ? 1 : 0;
+        kd.splat_halo = 1;
+        kd.splat_block = 0;
+        static const char *env_sp = ab_env("LCCRF_SPLAT_PASSES");               // A/B switch (same results): at most this many
+        const int cap = env_sp ? atoi(env_sp) : 3;
+        if (kd.fast0_ok && cap >= 2) {
+            const int *nd = ndist_host + k * kNdistAxes;
+            int halo = 1;
+            for (int j = 1; j < std::min(kd.D1, std::min(cap, 3)); ++j) {
+                if (nd[j] < 1 || nd[j] > 127 || halo + nd[j] > 1024 / 8) break;
+                halo += nd[j];
+                kd.splat_passes = j + 1;
+                kd.splat_halo = halo;
+            }
+            // single frames pair the passes behind the splat off a two-hop table built for the pairs (1,2), (3,4) ...: 1 or 3 passes
+            if (kd.splat_passes == 2 && kd.nbr2 && kd.D1 > 3) { kd.splat_passes = 1; kd.splat_halo = 1; }
+            if (kd.splat_passes >= 2) kd.splat_block = kd.splat_halo * 8 <= 256 ? 256 : kd.splat_halo * 8 <= 512 ? 512 : 1024;
+        }
+        int m = 0, r = 0, nlong = 0;
+        for (int f = 0; f < F; ++f) {
+            m = std::max(m, V_host[k * Fcap + f]);
+            r = std::max(r, row_host[k * Fcap + f]);
+            if (kd.longrow_ok) nlong = std::max(nlong, long_host[k * Fcap + f]);
+        }
+        // a coarse kernel over many points (listed rows, or more than ~4 entries per row on average): the row-walking splat with
+        // its loads up front + a workgroup per listed row, no blur pass in the splat
+        const int NAr = activeN > 0 ? activeN : maxN;
+        kd.long_mode = kd.longrow_ok && (nlong > 0 || (long)NAr * kd.D1 > 4L * std::max(m, 1));
+        if (kd.long_mode && (long)NAr * kd.D1 >= 16L * std::max(m, 1)) kd.long_mode = 2;       // ... a wavefront per vertex from ~16 entries per row
+        kernels[k].maxV = m;
+        kernels[k].maxRow = r;
+    }
+    sync_views();
+    sizes_known = true;
+    invalidate_lean_prep();                            // (every path that changes a lattice clears sizes_known and so comes through here)
+    fused_fits = engine_pref != 1 && !perm_on && fused_supported(crf, kdevs.data(), maxV.data(), maxRow.data(), &fused_lds);
+    choose_sized_engine();
+    if (engine_pref == 2 && !fused_fits)
+        return fail(LCCRF_E_CAPACITY, "fused engine requested but the problem does not fit one workgroup's LDS");
+    return LCCRF_OK;
+}
+
+// setUnaryEnergyFromLabel (densecrf3d.h:100-130) is deferred: the 2L+1 energies travel as a kernel
+// argument and either the one-launch-per-frame kernel derives the unaries itself or ensure_unary()
+// launches the small kernel when somebody needs the array.  `label` must stay readable until then.
+UnaryTable Engine::label_table(const float *conf) const
+{
+    // densecrf3d.h:109-115.  log(float) binds to the float overload at the reference's call
+    // site (src/Tracking.cc:21-43 sees `using namespace std` from include/Tracking.h:55).
+    UnaryTable tb;
+    tb.v[0] = -logf(1.0f / L);
+    for (int i = 0; i < L; ++i) {
+        tb.v[1 + i] = -logf((1.0f - conf[i]) / (L - 1));
+        tb.v[1 + L + i] = -logf(conf[i]);
+    }
+    return tb;
+}
+
+void Engine::defer_unary_from_label(const int16_t *label, const float *conf)
+{
+    const UnaryTable tb = label_table(conf);
+    crf.unary = unary_own;
+    unary_deferred = true;
+    unary_is_label = true;
+    deferred_label = label;
+    deferred_tbl = tb;
+    unary_set = true;
+}
+
+// raw unary energies [F][maxN][L] at `p` (the engine's own array, filled by the caller's copy, or a bound device array: read only)
+void Engine::bind_unary(const float *p)
+{
+    crf.unary = const_cast<float *>(p);
+    unary_deferred = unary_is_label = unary_p_valid = false;
+    unary_set = true;
+}
+
+int Engine::ensure_unary()
+{
+    if (!unary_deferred) return LCCRF_OK;
+    unary_deferred = false;
+    launch_unary_from_label_tbl(crf, deferred_label, deferred_tbl, stream);
+    HIP_TRY(hipGetLastError());
+    return LCCRF_OK;
+}
+
+int Engine::start()
+{
+    if (!unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
+    { int rl = resolve_late(); if (rl) return rl; }
+    { int rp = ensure_plain(); if (rp) return rp; }   // (object API after a locality-mode inference(): label-derived energies sit in that order)
+    { int ru = ensure_unary(); if (ru) return ru; }
+    launch_start(crf, stream);
+    started = true;
+    return LCCRF_OK;
+}
+
+int Engine::step(float relax)
+{
+    if (!started) return fail(LCCRF_E_STATE, "stepInference before startInference");
+    int rc = resolve_late();
+    if (rc) return rc;
+    if ((rc = ensure_plain())) return rc;
+    rc = learn_sizes();
+    if (rc) return rc;
+    if ((rc = ensure_unary())) return rc;             // (label-derived energies follow the lattices' point order: re-derived after a re-build)
+    launch_step_stream(crf, kdevs.data(), maxV.data(), relax, stream, compat_arg());
+    return LCCRF_OK;
+}
+
+// Can the whole frame (lattices + normalisation + inference) run as ONE launch (frame_engine.hip)?
+bool Engine::frame_ok() const
+{
+    static const bool no_frame = ab_env("LCCRF_NO_FRAME") != nullptr;   // cross-check switch: two-kernel path, same results
+    return !no_frame && engine_pref == 0 && !n_compat && !kernels.empty() && frame_supported(crf, kdevs.data());
+}
+
+// One launch per frame; whether every frame fitted the kernel's LDS plan is known at the next
+// synchronisation point (resolve_late), which re-runs the batch on the two-kernel path if not.
+int Engine::run_frame(int n_iter, int with_map, float relax)
+{
+    *late_status = 0;
+    // (label-derived energies already written for lattices in locality mode sit in the INTERNAL point order: the frame kernel, which
+    //  works in the caller's order, derives them from the labels again)
+    const bool from_label = (unary_deferred || (unary_is_label && perm_on)) && L == 2;
+    unsigned *dual = nullptr;
+    // The tracker's case (one frame, 255 idle CUs) and small batches (a quarter as many frames as CUs, or fewer): every
+    // frame gets two workgroups, one per lattice build.
+    if (crf.K == 2 && F <= kDualMaxFrames && !opt_single_wg) {
+        if (!dual_area) {
+            int rc = mem.alloc(reinterpret_cast<char **>(&dual_area), frame_dual_bytes(std::min(Fcap, kDualMaxFrames)));
+            if (rc) return rc;
+        }
+        dual = dual_area;
+        if (++dual_epoch == 0) dual_epoch = 1;
+    }
+    static const bool no_done_word = ab_env("LCCRF_NO_DONE_WORD") != nullptr;   // A/B switch: wait on the stream instead
+    done_armed = late_ok && F == 1 && !no_done_word;
+    if (done_armed && ++done_epoch == 0) done_epoch = 1;
+    labels_armed = done_armed && with_map && L == 2 && map_host && map_host == crf.map && activeN > 0;
+    if (labels_armed) memset(map_host, 0xff, (size_t)activeN * sizeof(int16_t));
+    // full-size frames, two per CU (frame_lean.hip): the record area its loop re-reads is allocated when a batch first wants it
+    // (sized for the frames BOUND, not for the handle's capacity -- 96 KB per frame: a handle created for 16384 frames that runs 1024 takes
+    //  0.1 GB, not 1.6; a later, larger batch gets a new area, the old one stays with the handle until it is destroyed -- ADVICE r5)
+    if (frame_lean_ok && lean_rec_frames < F && frame_lean_wanted(crf)) {
+        // (no memory for the area: the batch keeps the one-frame-per-CU kernel, which needs none)
+        lean_rec = nullptr;
+        lean_rec_frames = 0;
+        const int want = std::min(Fcap, std::max(F, 256));
+        if (mem.alloc(reinterpret_cast<char **>(&lean_rec), frame_lean_rec_bytes(want), false)) {   // (written before it is read: no zeroing)
+            lean_rec = nullptr;
+            frame_lean_ok = false;
+            (void)hipGetLastError();
+        } else {
+            lean_rec_frames = want;
+        }
+    }
+    const int shape = launch_frame(crf, kdevs.data(), n_iter, with_map, relax, late_status, frame_status,
+                                   from_label ? deferred_label : nullptr, deferred_tbl.v, stream, frame_small_ok, dual, dual_epoch,
+                                   done_armed ? done_word : nullptr, done_epoch, frame_lean_ok ? lean_rec : nullptr);
+    HIP_TRY(hipGetLastError());
+    frame_small_used = shape == 1;
+    frame_lean_used = shape == 2;
+    fused_shape = shape == 0 ? (1024 | 1 << 16) : (512 | 2 << 16);       // lanes per frame | frames per CU
+
+    late_pending = true;
+    late_iter = n_iter;
+    late_map = with_map;
+    late_relax = relax;
+    started = true;
+    engine_used = 3;
+    last_with_map = with_map;
+    fallback_frames = 0;
+    return LCCRF_OK;
+}
+
+int Engine::inference(int n_iter, int with_map, float relax)
+{
+    if (n_iter < 0) return fail(LCCRF_E_INVALID, "n_iterations < 0");
+    if (!unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
+    int rc = resolve_late();
+    if (rc) return rc;
+    // Object API: nothing has been built yet (add_pairwise only stages features) -> do not build, run the
+    // frame in one launch.  If a probe already forced the lattices into HBM, iterate on those instead.
+    if (late_ok && frame_ok() && !(built_upto == (int)kernels.size() && sizes_known)) return run_frame(n_iter, with_map, relax);
+    perm_scope = true;                                // (large frames: lattices built from here may use locality mode)
+    rc = inference_sized(n_iter, with_map, relax);
+    perm_scope = false;
+    return rc;
+}
+
+// Object API, large frames: DenseCRF::inference() runs in locality mode (internal point order, sorted build); the entry points
+// that expose or continue from per-point lattice state in the CALLER's order -- stepInference, PairwisePotential::apply, the
+// lattice / norm / unary probes -- get the plain build instead: built that way if they come first, re-built once if not.
+int Engine::ensure_plain()
+{
+    if (!perm_on || !perm_scoped) return LCCRF_OK;
+    perm_banned = true;
+    invalidate_lattices();
+    return flush_builds();
+}
+
+// ... and the same for a batch's backward (lccrf_batch_inference_backward): every frame's lattices in HBM, built the plain way --
+// re-built if they are in locality mode.  For this call only: the next lccrf_batch_build / _run decides the point order afresh.
+int Engine::ensure_plain_batch()
+{
+    perm_banned = true;
+    if (perm_on) invalidate_lattices();
+    const int rc = learn_sizes();
+    perm_banned = false;
+    return rc;
+}
+
+// lccrf_batch_run: per frame the PottsPotential ctors + inference(n, with_map)
+int Engine::run(int n_iter, int with_map, float relax)
+{
+    if (n_iter < 0) return fail(LCCRF_E_INVALID, "n_iterations < 0");
+    if (!unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
+    int rc = resolve_late();
+    if (rc) return rc;
+    if (frame_ok()) return run_frame(n_iter, with_map, relax);
+    invalidate_lattices();                            // two-kernel path: rebuild for the current inputs, then infer
+    return inference_sized(n_iter, with_map, relax);
+}
+
+int Engine::inference_sized(int n_iter, int with_map, float relax)
+{
+    int rc = learn_sizes();                            // (builds what is pending: the internal point order is known after this)
+    if (rc) return rc;
+    rc = ensure_unary();
+    if (rc) return rc;
+    engine_used = sized_engine;
+    last_with_map = with_map;
+    if (perm_on) {
+        // locality mode: iterate on the internal-order view, un-permute Q on the way out (densecrf_base.h:65-73 otherwise)
+        CrfDev cp = crf;
+        cp.Q = Qp;
+        if (!unary_is_label) {
+            // a BOUND unary array ("bound, not copied") may have been updated in place since the last call: permute it
+            // afresh every time, as the other engines read it live; only the engine's own copy is cached
+            if (!unary_p_valid || crf.unary != unary_own) launch_permute_rows(crf, unary_p, crf.unary, L, 1, stream);
+            unary_p_valid = true;
+            cp.unary = unary_p;
+        }
+        launch_start(cp, stream);
+        for (int it = 0; it < n_iter; ++it) launch_step_stream(cp, kdevs.data(), maxV.data(), relax, stream, compat_arg());
+        launch_permute_rows(crf, crf.Q, Qp, L, 0, stream);
+        if (with_map) launch_map(crf, stream);
+        started = true;
+    } else if (sized_engine == 2) {
+        // the two-frames-per-CU kernel runs from prepared launch records (fused_lean.h: LeanPrepPlan): one block per frame, owned
+        // here, (re)written by the first inference behind a build -- learn_sizes() clears `valid` whenever a lattice has changed
+        const size_t prep_need = lean_prep_bytes(crf, kdevs.data(), maxV.data(), maxRow.data());
+        if (prep_need > lean_prep.bytes) {
+            lean_prep.valid = false;
+            lean_prep.buf = nullptr;                       // (an outgrown block stays with the arena until the handle goes)
+            lean_prep.bytes = 0;
+            unsigned char *p = nullptr;
+            if (mem.alloc(&p, prep_need, false) == LCCRF_OK) {
+                lean_prep.buf = p;
+                lean_prep.bytes = prep_need;
+            } else {
+                (void)hipGetLastError();                   // no room: the self-contained kernel runs instead, same results
+            }
+            if (!lean_prep.ev0) {
+                (void)hipEventCreate(&lean_prep.ev0);
+                (void)hipEventCreate(&lean_prep.ev1);
+            }
+        }
+        fused_shape = launch_inference_fused(crf, kdevs.data(), maxV.data(), maxRow.data(), n_iter, with_map, relax, stream,
+                                             prep_need ? &lean_prep : nullptr);
+        started = true;
+    } else {
+        if ((rc = start())) return rc;
+        for (int it = 0; it < n_iter; ++it) launch_step_stream(crf, kdevs.data(), maxV.data(), relax, stream, compat_arg());
+        if (with_map) launch_map(crf, stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return LCCRF_OK;
+}
+
+// Before anything looks at (or continues from) the results of a late-bound inference.
+// *seen_done (optional): the frame's results were observed through the done word -- the caller may read the pinned
+// outputs without a stream synchronisation of its own.
+int Engine::resolve_late(bool *seen_done)
+{
+    if (seen_done) *seen_done = false;
+    if (!late_pending) return LCCRF_OK;
+    late_pending = false;
+    labels_armed = false;
+    bool seen = false;
+    if (done_armed) {                                  // bounded poll; a word that never comes is waited for the ordinary way
+        done_armed = false;
+        seen = poll_done_word(done_word, done_epoch, std::chrono::milliseconds(2), 1024);
+    }
+    if (!seen) HIP_TRY(hipStreamSynchronize(stream));
+    if (*npoints_bad) {                                // (the one-launch path never passes through learn_sizes())
+        *npoints_bad = 0;
+        return fail(LCCRF_E_CAPACITY, "a bound n_points[f] lies outside [0, max_points=%d] (the kernels clamped it)", maxN);
+    }
+    if (*late_status == 0) {
+        if (seen_done) *seen_done = seen;
+        return LCCRF_OK;
+    }
+    *late_status = 0;                                  // some frame did not fit the one-launch kernel
+    if (seen) HIP_TRY(hipStreamSynchronize(stream));   // (the kernel has nothing left to do; the stream formally still holds it)
+    HIP_TRY(hipMemcpy(frame_status_host, frame_status, sizeof(int) * F, hipMemcpyDeviceToHost));
+    int n = 0;
+    for (int f = 0; f < F; ++f)
+        if (frame_status_host[f]) fb_list_host[n++] = f;
+    fallback_frames = n;
+    if (frame_small_used && 8 * n > F) frame_small_ok = false;   // these lattices want the whole CU: 1024 lanes from now on
+    if (frame_lean_used && 8 * n > F) frame_lean_ok = false;
+    int rc = LCCRF_OK;
+    if (n >= F || n == 0) {                            // every frame (always so for the object API): two-kernel path in place
+        invalidate_lattices();
+        rc = inference_sized(late_iter, late_map, late_relax);
+    } else {
+        rc = rerun_frames(n);                          // the batch stays a one-launch batch; only the flagged frames pay twice
+        engine_used = 3;
+    }
+    if (rc) return rc;
+    if (timed_inf) HIP_TRY(hipEventRecord(ev[3], stream));   // the timed region now ends behind the re-run
+    if (after_rerun && (rc = after_rerun(after_rerun_ctx))) return rc;
+    HIP_TRY(hipStreamSynchronize(stream));             // callers read borrowed device buffers right behind a synchronisation point
+    return LCCRF_OK;
+}
+
+// Two-kernel path for the frames fb_list_host[0, n) only, in a compact sub-engine; results scattered back.
+int Engine::rerun_frames(int n)
+{
+    if (fb && fb->Fcap < n) {
+        fb->destroy();
+        delete fb;
+        fb = nullptr;
+    }
+    if (!fb) {
+        fb = new (std::nothrow) Engine;
+        if (!fb) return fail(LCCRF_E_NOMEM, "host allocation failed");
+        int rc = fb->init(device, std::min(Fcap, std::max(8, next_pow2(n))), maxN, L);
+        for (size_t k = 0; k < kernels.size() && !rc; ++k) rc = fb->add_kernel(kernels[k].dev.d, kernels[k].dev.w, true, false);
+        if (!rc && hipStreamSynchronize(fb->stream) != hipSuccess) rc = fail(LCCRF_E_HIP, "hipStreamSynchronize after allocation failed");
+        if (rc) {
+            fb->destroy();
+            delete fb;
+            fb = nullptr;
+            return rc;
+        }
+    }
+    Engine &g = *fb;
+    const hipStream_t g_own = g.stream;
+    g.stream = g.mem.stream = stream;                  // everything below (lazy allocations' zeroing included) is ordered on this engine's stream
+    struct Restore { Engine &g; hipStream_t s; ~Restore() { g.stream = g.mem.stream = s; } } restore{g, g_own};
+    g.F = n;
+    g.activeN = activeN;
+    g.engine_pref = engine_pref == 1 ? 1 : 0;
+    HIP_TRY(hipMemcpyAsync(fb_list, fb_list_host, sizeof(int) * n, hipMemcpyHostToDevice, stream));
+    launch_copy_frames(g.npoints_own, 4, crf.n_points, 4, fb_list, n, 4, 1, stream);
+    g.crf.n_points = g.npoints_own;
+    for (size_t k = 0; k < kernels.size(); ++k) {
+        const size_t row = (size_t)maxN * kernels[k].dev.d * sizeof(float);
+        launch_copy_frames(g.kernels[k].feat_own, row, kernels[k].dev.feat, row, fb_list, n, row, 1, stream);
+        g.kernels[k].dev.feat = g.kernels[k].feat_own;
+        g.kernels[k].dev.w = kernels[k].dev.w;
+    }
+    g.crf.unary = g.unary_own;
+    if (unary_deferred || (unary_is_label && perm_on)) {   // (see run_frame: energies written in the internal point order are of no use here)
+        launch_copy_frames(g.label_own, (size_t)maxN * 2, deferred_label, (size_t)maxN * 2, fb_list, n, (size_t)maxN * 2, 1, stream);
+        g.unary_deferred = true;
+        g.deferred_label = g.label_own;
+        g.deferred_tbl = deferred_tbl;
+    } else {
+        const size_t row = (size_t)maxN * L * sizeof(float);
+        launch_copy_frames(g.unary_own, row, crf.unary, row, fb_list, n, row, 1, stream);
+        g.unary_deferred = false;
+    }
+    g.unary_set = true;
+    g.invalidate_lattices();
+    g.sync_views();
+    HIP_TRY(hipGetLastError());
+    int rc = g.inference_sized(late_iter, late_map, late_relax);
+    if (rc) return rc;
+    const size_t qrow = (size_t)maxN * L * sizeof(float);
+    launch_copy_frames(crf.Q, qrow, g.crf.Q, qrow, fb_list, n, qrow, 0, stream);
+    if (late_map) {
+        launch_copy_frames(crf.map, (size_t)maxN * 2, g.crf.map, (size_t)maxN * 2, fb_list, n, (size_t)maxN * 2, 0, stream);
+        if (crf.map_bits && g.crf.map_bits)
+            launch_copy_frames(crf.map_bits, (size_t)crf.bits_stride * 8, g.crf.map_bits, (size_t)crf.bits_stride * 8, fb_list, n,
+                               (size_t)crf.bits_stride * 8, 0, stream);
+    }
+    for (size_t k = 0; k < kernels.size(); ++k)
+        launch_copy_frames(kernels[k].dev.V, 4, g.kernels[k].dev.V, 4, fb_list, n, 4, 0, stream);
+    HIP_TRY(hipGetLastError());
+    return LCCRF_OK;
+}
+
+}  // namespace lccrf

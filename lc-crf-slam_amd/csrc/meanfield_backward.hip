@@ -1,6 +1,6 @@
 // meanfield_backward.hip -- reverse-mode gradients of DenseCRF::inference (densecrf_base.h:65-91): include/lccrf.h section 1c.
 //
-// The C-ABI layer (api.hip: backward_call, behind every lccrf_*inference_backward* entry point) replays the forward on the step
+// The C-ABI layer (api_backward.hip: backward_call, behind every lccrf_*inference_backward* entry point) replays the forward on the step
 // path, keeping Q_0 .. Q_{T-1}, and then runs the sweep below on the call's stream, for every frame at once (the frame is
 // blockIdx.y; a handle is a batch of one).  What a call asks for is a BackwardRequest (engine.h); backward_layout() below lays its
 // area out, for the sizing and for the run alike.  Per iteration t = T .. 1:
