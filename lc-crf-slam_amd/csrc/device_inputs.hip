@@ -3,7 +3,7 @@
 // are written into the handle's own feature buffer (KernelState::feat_own), [N][d] AoS -- the layout every lattice build reads.
 //
 // Only N*d values are written.  The builds never read a point at or beyond N for its value: the phantom points of quirk Q1 get
-// their zeros inside the builds (stream_engine.hip, build_small.hip, frame_build.h: "phantom lanes, :299"), exactly as for the
+// their zeros inside the builds (stream_build.hip, build_small.hip, frame_build.h: "phantom lanes, :299"), exactly as for the
 // host path, which uploads N*d values as well.  This kernel is the only reader of the caller's array, and it reads [0, N) only.
 //
 // Bit parity with the reference's host loop rests on two things: `(float)` of a pixel coordinate below 2^24 is exact, and the

@@ -73,7 +73,7 @@ struct KernelDev {
     int *rowmax;          // [F]               longest CSR row (splat contributions of one vertex)
     int *nbr;             // [F][D1][Epad][2]  blur neighbours {n1,n2} per (axis, vertex), -1 absent
     int *nbr2;            // [F][D1/2][Epad][8] or null: two-hop table of the pass pairs (2p, 2p+1) for single-frame engines (one
-                          //   launch per TWO blur passes, stream_engine.hip: k_blur2x2t): {v1, v2, a, b, a1, a2, b1, b2} with
+                          //   launch per TWO blur passes, stream_filter.hip: k_blur2x2t): {v1, v2, a, b, a1, a2, b1, b2} with
                           //   (v1, v2) = axis-2p neighbours of v, (a, b) = its axis-(2p+1) neighbours, (a1, a2) / (b1, b2) = the
                           //   axis-2p neighbours of a / b; -1 absent
     int nbr2_ok;          // the streaming build filled nbr2 for the lattices now in HBM ...
@@ -120,7 +120,7 @@ struct KernelDev {
     // not depend on it: CSR rows stay ordered by ORIGINAL point index (quirk Q6), vertices are matched by key.  Null = off.
     const int *perm;      // [F][maxNpad]      position -> original point (identity on the phantom lanes)
     const int *iperm;     // [F][maxNpad]      original point -> position
-    // ... and the VERTICES are numbered along the lattice's own axes (round 4; stream_engine.hip: the sorted build): in the basis of
+    // ... and the VERTICES are numbered along the lattice's own axes (round 4; stream_build.hip: the sorted build): in the basis of
     // the blur directions the lattice is the integer grid Z^d, and ids in row-major order of those coordinates make the two
     // neighbours a blur gather wants consecutive ids of another row.
     int vorder;           // the lattice is built by sorting the entries on the row-major code of their vertex (no hash table)
@@ -171,7 +171,7 @@ struct SortScratch {
 void launch_sort_points(const KernelDev &kd, const CrfDev &c, const SortScratch &ss, hipStream_t s);
 // dst[f][i][0..width) = src[f][perm[i]][0..width) (gather = 1) or dst[f][perm[i]][..] = src[f][i][..] (gather = 0), i < n_points[f]
 void launch_permute_rows(const CrfDev &c, float *dst, const float *src, int width, int gather, hipStream_t s);
-void launch_build_kernel(const KernelDev &kd, const CrfDev &c, int maxV_hint, hipStream_t s, const SortScratch *vsort = nullptr);
+void launch_build_kernel(const KernelDev &kd, const CrfDev &c, hipStream_t s, const SortScratch *vsort = nullptr);
 void launch_norm(const KernelDev &kd, const CrfDev &c, int maxV, hipStream_t s);
 // unary[i][:] from labels (densecrf3d.h:116-129); the 2L+1 energies {u, n[L], p[L]} are passed by value (no table
 // upload; `label` may be device or pinned host memory)

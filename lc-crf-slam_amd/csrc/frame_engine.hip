@@ -9,7 +9,7 @@
 // (and any frame whose lattices do not fit the LDS plan below) runs on the two-kernel / streaming path with
 // identical results.
 //
-// Lattice construction here is NOT the streaming build's algorithm (stream_engine.hip / build_small.hip keep
+// Lattice construction here is NOT the streaming build's algorithm (stream_build.hip / build_small.hip keep
 // the reference's vertex numbering because the parity probes compare offset_/blur_neighbors_ verbatim).  The
 // mean-field result does not depend on how vertices are numbered -- a vertex's value is a sum over its OWN
 // row in ascending point order, and blur neighbours are found by key -- so this kernel uses whatever

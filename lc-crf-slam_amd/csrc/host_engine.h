@@ -177,7 +177,7 @@ struct Engine {
 
     // ---- locality mode and the sorted build ----
     // Locality mode (batch engines, frames of >= kPermMinPoints points on the streaming engine): the lattices are built
-    // with the points in an internal Z-order of their lattice cells (stream_engine.hip: launch_sort_points); Q, next and
+    // with the points in an internal Z-order of their lattice cells (stream_build.hip: launch_sort_points); Q, next and
     // the unaries of the iteration live in that order (Qp, unary_p / unary_own) and Q is un-permuted on the way out.
     static constexpr int kPermMinPointsDefault = 8192;
     bool allow_perm = false;           // set by lccrf_batch_create, and by lccrf_create for handles of >= kPermMinPoints points ...

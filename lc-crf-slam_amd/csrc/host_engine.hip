@@ -1,7 +1,7 @@
 // host_engine.hip -- the bodies of host_engine.h: the host-side state machine of one handle or batch.
 //
 // Host-side glue only: device memory, pinned staging, launch order.  All arithmetic of the path runs in the kernels
-// (stream_engine.hip / fused_engine.hip); the only numbers computed here are the per-kernel constants of
+// (stream_*.hip / fused_engine.hip); the only numbers computed here are the per-kernel constants of
 // permutohedral_cpu.h:249,282-285,681 and the 2L+1 unary energies of densecrf3d.h:109-115, which the reference also computes
 // once, outside its loops.
 #include "host_engine.h"
@@ -484,7 +484,7 @@ int Engine::build_kernels(int k0, int n)
             kernels[k].dev.nbrc_ok = kernels[k].dev.nbrc != nullptr && kernels[k].dev.vorder && F >= kNbrcMinFrames && F <= kNbrcMaxFrames;   // (... and the sorted build the compact one)
             kernels[k].dev.fast0_ok = kernels[k].dev.tbl_bad != nullptr && kernels[k].dev.vorder;
             kernels[k].dev.nbr2_first = kernels[k].dev.fast0_ok;              // (what build_kernel_d derives from the same two fields)
-            launch_build_kernel(kdevs[k], crf, kernels[k].maxV, stream, perm_on ? &sort : nullptr);
+            launch_build_kernel(kdevs[k], crf, stream, perm_on ? &sort : nullptr);
             launch_norm(kdevs[k], crf, kernels[k].maxV, stream);
             HIP_TRY(hipMemcpyAsync(V_host + (size_t)k * Fcap, kernels[k].dev.V, sizeof(int) * F, hipMemcpyDeviceToHost, stream));
             HIP_TRY(hipMemcpyAsync(row_host + (size_t)k * Fcap, kernels[k].dev.rowmax, sizeof(int) * F, hipMemcpyDeviceToHost, stream));

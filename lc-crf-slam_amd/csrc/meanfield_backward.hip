@@ -27,7 +27,7 @@
 // splat side; the norm part last): the same bits from run to run, and for a frame of a batch those of a handle.
 //
 // Rows at or beyond n_points[f] (the phantom points of quirk Q1 among them) are never read: every lattice build lists real points
-// only in its splat rows (k_csr_count / k_eoffsets in stream_engine.hip, E = N (d+1) in build_small.hip), the slice writes rows
+// only in its splat rows (k_csr_count / k_eoffsets in stream_build.hip, E = N (d+1) in build_small.hip), the slice writes rows
 // i < n_points[f] only, and the kernels below stop at n_points[f].  A batch rebound with fewer points than an earlier call leaves
 // stale rows in its area; nothing reads them.
 #include <algorithm>
@@ -35,6 +35,7 @@
 
 #include "engine.h"
 #include "device_math.h"
+#include "stream_common.h"   // with_dims
 
 namespace lccrf {
 namespace {
@@ -526,17 +527,7 @@ __global__ void __launch_bounds__(kBwdBlock) k_corner_to_feature(KernelDev kd, c
 void launch_corner_to_feature(const KernelDev &kd, const CrfDev &c, int rows, const float *gb, float *out, hipStream_t s)
 {
     const dim3 grid((unsigned)std::max((rows + kBwdBlock - 1) / kBwdBlock, 1), (unsigned)c.F);
-    switch (kd.d) {
-    case 1: k_corner_to_feature<1><<<grid, kBwdBlock, 0, s>>>(kd, c.n_points, rows, gb, out); break;
-    case 2: k_corner_to_feature<2><<<grid, kBwdBlock, 0, s>>>(kd, c.n_points, rows, gb, out); break;
-    case 3: k_corner_to_feature<3><<<grid, kBwdBlock, 0, s>>>(kd, c.n_points, rows, gb, out); break;
-    case 4: k_corner_to_feature<4><<<grid, kBwdBlock, 0, s>>>(kd, c.n_points, rows, gb, out); break;
-    case 5: k_corner_to_feature<5><<<grid, kBwdBlock, 0, s>>>(kd, c.n_points, rows, gb, out); break;
-    case 6: k_corner_to_feature<6><<<grid, kBwdBlock, 0, s>>>(kd, c.n_points, rows, gb, out); break;
-    case 7: k_corner_to_feature<7><<<grid, kBwdBlock, 0, s>>>(kd, c.n_points, rows, gb, out); break;
-    case 8: k_corner_to_feature<8><<<grid, kBwdBlock, 0, s>>>(kd, c.n_points, rows, gb, out); break;
-    default: break;
-    }
+    with_dims<1, 8>(kd.d, [&](auto d) { k_corner_to_feature<decltype(d)::value><<<grid, kBwdBlock, 0, s>>>(kd, c.n_points, rows, gb, out); });
 }
 
 }  // namespace

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate tests/golden/large.npz from the REFERENCE itself (oracle/_ref: the reference's own DenseCRF headers compiled in
 place): frames above the 8192-point threshold at which the streaming engine switches to LOCALITY MODE (an internal Z-order
-of the points, csrc/stream_engine.hip).  Results must not depend on that order -- these vectors pin that against the
+of the points, csrc/stream_build.hip).  Results must not depend on that order -- these vectors pin that against the
 reference directly, not through the restatement.
 
     python tests/golden/make_golden_large.py

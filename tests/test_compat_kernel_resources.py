@@ -37,10 +37,10 @@ def _one(use, key):
 @pytest.mark.skipif(shutil.which(HIPCC) is None, reason="hipcc not installed")
 def test_compat_slice_uses_no_scratch_and_its_planned_lds():
     """k_slice_compat: 64 x 65 floats of mu + four tiles of 384 floats in LDS = 22 784 bytes (seven workgroups in a CU's 160 KB)."""
-    r = _one(resource_usage("stream_engine.hip"), "k_slice_compat")
+    r = _one(resource_usage("stream_filter.hip"), "k_slice_compat")
     assert r["ScratchSize [bytes/lane]"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, r
     assert r["VGPRs"] + r.get("AGPRs", 0) <= 64, r          # (eight wavefronts per SIMD by registers: LDS sets the occupancy)
-    assert _one(lds_bytes("stream_engine.hip"), "k_slice_compat") == 4 * (64 * 65 + 4 * 384)
+    assert _one(lds_bytes("stream_filter.hip"), "k_slice_compat") == 4 * (64 * 65 + 4 * 384)
 
 
 @pytest.mark.skipif(shutil.which(HIPCC) is None, reason="hipcc not installed")

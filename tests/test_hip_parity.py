@@ -746,7 +746,7 @@ def test_large_ragged_batch_matches_oracle(po, wl, d_list, L):
         assert cc.same_bits(Q[f, :n], o.probability()), f
         assert np.array_equal(M[f, :n], o.map()), f
         o.close()
-    # frames of this size are built in LOCALITY MODE (an internal Z-order of the points, csrc/stream_engine.hip:
+    # frames of this size are built in LOCALITY MODE (an internal Z-order of the points, csrc/stream_build.hip:
     # launch_sort_points): what the caller sees stays in the caller's point order -- norm included
     for k in range(len(d_list)):
         nm = b.norm(k)
