@@ -140,6 +140,8 @@ struct CrfDev {
     const int *perm;      // [F][perm_stride] or null: locality mode (see KernelDev::perm); unary / Q / next of THIS view are then
     int perm_stride;      //   in permuted order and the caller un-permutes Q on the way out
 };
+// points per frame that sizes a launch: the largest frame when the host knows it, else the capacity
+inline int active_points(const CrfDev &c) { return c.activeN > 0 ? c.activeN : c.maxN; }
 
 // scratch of the point sort (locality mode), owned by the engine
 struct SortScratch {
@@ -263,6 +265,8 @@ bool build_small_supported(const KernelDev *kds, int n, int max_points);
 void launch_build_small(const KernelDev *kds, int n, int max_points, const CrfDev &c, hipStream_t s);
 
 // ---- fused engine (SLAM sizes; one workgroup per frame, lattice values in LDS) --------
+// the CRF both one-workgroup engines are written for: L = 2, one or two 2-D kernels (u16_tables: and Epad < 65535 in each)
+bool slam_shaped(const CrfDev &c, const KernelDev *kds, bool u16_tables);
 bool fused_supported(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow,
                      size_t *lds_bytes);
 // returns the shape it launched: lanes per workgroup (= per frame) | workgroups per CU << 16 (0: nothing launched)

@@ -34,7 +34,7 @@
 #include "fused_loop.h"
 #include "frame_build.h"
 #include "fused_lean.h"
-#include <type_traits>
+#include "dispatch.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -757,39 +757,19 @@ int frame_hcap(int NA)
     return h;
 }
 
-template <int NT, int PPT, int K>
-void launch_frame_ppt(const CrfDev &c, const FrameArgs &a, hipStream_t s)
-{
-    auto fn = k_frame<NT, PPT, K>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit);
-    fn<<<dim3(c.F), dim3(NT), a.lds_total, s>>>(c, a);
-}
-
-template <int PPT>
-void launch_frame_dual(const CrfDev &c, const FrameArgs &a, hipStream_t s)
-{
-    auto fn = k_frame<kNT, PPT, 2, true>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit);
-    fn<<<dim3(2 * c.F), dim3(kNT), a.lds_total, s>>>(c, a);
-}
-
 }  // namespace
 
 bool frame_supported(const CrfDev &c, const KernelDev *kds)
 {
-    const int NA = c.activeN > 0 ? c.activeN : c.maxN;
-    if (c.L != 2 || c.K < 1 || c.K > kMaxFusedK || NA < 1 || NA > 4 * kNT) return false;
-    for (int k = 0; k < c.K; ++k)
-        if (kds[k].d != 2) return false;
-    return true;
+    const int NA = active_points(c);
+    return slam_shaped(c, kds, false) && NA >= 1 && NA <= 4 * kNT;   // (it builds its own tables: any Epad)
 }
 
 size_t frame_dual_bytes(int frames) { return (size_t)frames * kDualWords * sizeof(unsigned); }
 
 bool frame_lean_wanted(const CrfDev &c)
 {
-    const int NA = c.activeN > 0 ? c.activeN : c.maxN;
-    return frame_lean_plausible(NA, c.K, c.F);
+    return frame_lean_plausible(active_points(c), c.K, c.F);
 }
 size_t frame_lean_rec_bytes(int frames) { return (size_t)frames * kLeanRecBytes; }
 
@@ -816,7 +796,7 @@ int launch_frame(const CrfDev &c, const KernelDev *kds, int n_iter, int with_map
     a.relax = relax;
     a.omr = 1 - relax;
     a.rec = lean_rec;
-    const int NA = c.activeN > 0 ? c.activeN : c.maxN;
+    const int NA = active_points(c);
     a.hcap = frame_hcap(NA);
     a.lds_total = (int)kLdsLimit;
     a.status = status;
@@ -830,13 +810,8 @@ int launch_frame(const CrfDev &c, const KernelDev *kds, int n_iter, int with_map
 #endif
     a.n_single = (c.F == 1 && done && c.activeN > 0) ? c.activeN : -1;   // (object API: activeN IS the frame's count)
     a.done_epoch = done_epoch;
-    static long long *timing_buf = nullptr;
-    static const bool want_timing = kInstr && ab_env("LCCRF_FRAME_TIMING") != nullptr;
-    if (want_timing && !timing_buf) (void)hipMalloc(&timing_buf, 64 * sizeof(long long));
-    a.timing = want_timing ? timing_buf : nullptr;
-    a.timing_block = want_timing ? std::max(atoi(ab_env("LCCRF_FRAME_TIMING")) - 1, 0) : 0;
-    if (a.timing_block >= (dual ? 2 : 1) * c.F) a.timing_block = 0;     // (two-workgroup form: block 2f is frame f's main workgroup, 2f + 1 its helper)
-    a.timing_lane = (want_timing && ab_env("LCCRF_FRAME_TIMING_LANE")) ? atoi(ab_env("LCCRF_FRAME_TIMING_LANE")) & (kNT - 1) : 0;
+    static StampBuffer stamps("LCCRF_FRAME_TIMING", "LCCRF_FRAME_TIMING_LANE", "frame");
+    stamps.arm((dual ? 2 : 1) * c.F, kNT, &a.timing, &a.timing_block, &a.timing_lane);   // (two-workgroup form: block 2f is frame f's main workgroup, 2f + 1 its helper)
     // Small frames: 512 lanes and half the CU's LDS per frame, so that two frames share a CU.  A frame whose lattices
     // do not fit that plan (or whose long rows need more chain lanes than four wavefront pairs have) flags itself
     // and is re-run like any other frame that does not fit.
@@ -856,11 +831,6 @@ int launch_frame(const CrfDev &c, const KernelDev *kds, int n_iter, int with_map
         const int build_bytes = kHdr + tables + 8 * vest[c.K - 1] + 6 * frame_hcap(NA) + 64;   // tables + vertex keys + counters + hash table
         small = layout_core(NA, c.K, vest, 1 << 20, &est, kNTSmall, kLdsHalf) && build_bytes <= (int)kLdsHalf;
     }
-#define FRAME_CASE(NT, P)                                      \
-    case P:                                                    \
-        if (c.K == 1) launch_frame_ppt<NT, P, 1>(c, a, s);     \
-        else launch_frame_ppt<NT, P, 2>(c, a, s);              \
-        break;
     static const bool no_dual = ab_env("LCCRF_NO_DUAL") != nullptr;         // A/B switch: same results either way
     // Full-size frames (1025 .. 2048 points, the two-kernel SLAM configuration): 512 lanes and half the CU's LDS per frame as well
     // (frame_lean.hip) -- flagged frames and the engine's give-up rule as for the small shape.
@@ -871,38 +841,18 @@ int launch_frame(const CrfDev &c, const KernelDev *kds, int n_iter, int with_map
         a.lds_total = (int)kLdsHalf;
         launch_frame_lean(c, a, NA, s);
     } else if (dual && !no_dual && c.K == 2 && !small) {                           // a frame alone: two workgroups, one per lattice build
-        switch ((NA + kNT - 1) / kNT) {
-        case 1: launch_frame_dual<1>(c, a, s); break;
-        case 2: launch_frame_dual<2>(c, a, s); break;
-        case 3: launch_frame_dual<3>(c, a, s); break;
-        case 4: launch_frame_dual<4>(c, a, s); break;
-        default: break;
-        }
-    } else if (small) {
-        a.lds_total = (int)kLdsHalf;
-        switch ((NA + kNTSmall - 1) / kNTSmall) {
-            FRAME_CASE(kNTSmall, 1)
-            FRAME_CASE(kNTSmall, 2)
-        default: break;
-        }
+        with_dims<1, 4>((NA + kNT - 1) / kNT, [&](auto p) { launch_workgroups(k_frame<kNT, decltype(p)::value, 2, true>, 2 * c.F, kNT, a.lds_total, s, c, a); });
     } else {
-        switch ((NA + kNT - 1) / kNT) {
-            FRAME_CASE(kNT, 1)
-            FRAME_CASE(kNT, 2)
-            FRAME_CASE(kNT, 3)
-            FRAME_CASE(kNT, 4)
-        default: break;
-        }
+        if (small) a.lds_total = (int)kLdsHalf;
+        const int nt = small ? kNTSmall : kNT;
+        with_dims<1, kMaxFusedK>(c.K, [&](auto kk) {
+            constexpr int K = decltype(kk)::value;
+            auto go = [&](auto fn) { launch_workgroups(fn, c.F, nt, a.lds_total, s, c, a); };
+            if (small) with_dims<1, 2>((NA + nt - 1) / nt, [&](auto p) { go(k_frame<kNTSmall, decltype(p)::value, K>); });
+            else with_dims<1, 4>((NA + nt - 1) / nt, [&](auto p) { go(k_frame<kNT, decltype(p)::value, K>); });
+        });
     }
-#undef FRAME_CASE
-    if (a.timing) {                       // instrumented builds: synchronous read-back of one workgroup's stamps
-        long long h[64];
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpy(h, a.timing, sizeof(h), hipMemcpyDeviceToHost);
-        fprintf(stderr, "[lccrf frame timing] %lld stamps, deltas (shader clocks):", h[63]);
-        for (int i = 1; i < h[63] && i < 63; ++i) fprintf(stderr, " %lld", h[i] - h[i - 1]);
-        fprintf(stderr, "\n");
-    }
+    stamps.print(s);                      // instrumented builds: synchronous read-back of one workgroup's stamps
     return lean ? 2 : small ? 1 : 0;
 }
 

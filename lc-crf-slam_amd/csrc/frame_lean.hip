@@ -22,6 +22,7 @@
 // mean-field result does not depend on it (frame_engine.hip), V is reported and tested against the reference's M_.
 #include "frame_build.h"
 #include "fused_lean.h"
+#include "dispatch.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -244,14 +245,6 @@ __global__ void __launch_bounds__(kNTSmall, 4) k_frame_lean(CrfDev c, FrameArgs 
     if (kInstr && al.timing && (int)blockIdx.x == al.timing_block && t == al.timing_lane) al.timing[63] = ins.n;
 }
 
-template <int PPT>
-void launch_lean_ppt(const CrfDev &c, const FrameArgs &a, hipStream_t s)
-{
-    auto fn = k_frame_lean<PPT>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit);
-    fn<<<dim3(c.F), dim3(kNTSmall), a.lds_total, s>>>(c, a);
-}
-
 }  // namespace
 
 // Is the half-CU form worth asking for?  Frames of NA points with lattices of the usual SLAM proportions (frame_engine.hip: an appearance
@@ -268,10 +261,7 @@ bool frame_lean_plausible(int NA, int K, int F)
 
 void launch_frame_lean(const CrfDev &c, const FrameArgs &a, int NA, hipStream_t s)
 {
-    if (NA <= kNTSmall) launch_lean_ppt<1>(c, a, s);
-    else if (NA <= 2 * kNTSmall) launch_lean_ppt<2>(c, a, s);
-    else if (NA <= 3 * kNTSmall) launch_lean_ppt<3>(c, a, s);
-    else launch_lean_ppt<4>(c, a, s);
+    with_dims<1, 4>((NA + kNTSmall - 1) / kNTSmall, [&](auto p) { launch_workgroups(k_frame_lean<decltype(p)::value>, c.F, kNTSmall, a.lds_total, s, c, a); });
 }
 
 }  // namespace fb

@@ -22,6 +22,7 @@
 #include "device_math.h"
 #include "fused_loop.h"
 #include "fused_lean.h"
+#include "dispatch.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -290,7 +291,7 @@ __global__ void __launch_bounds__(NT, 4) k_fused(CrfDev c, FusedArgs a)
 //         1: that prologue ONLY -- its results go to the frame's prepared block (fused_lean.h: LeanPrepPlan), once per build;
 //         2: the prologue is a handful of coalesced loads of that block (what an inference runs from the second launch on)
 template <int NT, int PPT, int K, int CH, bool RELOAD, int MODE>
-__global__ void __launch_bounds__(NT, NT == 384 ? 3 : 4) k_fused_lean(CrfDev c, FusedArgs a)
+__global__ void __launch_bounds__(NT, 4) k_fused_lean(CrfDev c, FusedArgs a)
 {
     constexpr int D1 = kD1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -527,18 +528,16 @@ __global__ void __launch_bounds__(NT, NT == 384 ? 3 : 4) k_fused_lean(CrfDev c, 
 bool make_layout(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, FusedLayout *lay, int nt = kNT,
                  size_t lds_limit = kLdsLimit)
 {
-    if (c.L != 2 || c.K < 1 || c.K > kMaxFusedK) return false;
-    const int NA = c.activeN > 0 ? c.activeN : c.maxN;   // size LDS and the points-per-lane variant by the frames' real size
-    for (int k = 0; k < c.K; ++k)
-        if (kds[k].d != 2 || kds[k].Epad >= 65535) return false;       // u16 row pointers / neighbour ids / slots
-    return layout_core(NA, c.K, maxV, maxRow ? maxRow[0] : 0, lay, nt, lds_limit);
+    if (!slam_shaped(c, kds, true)) return false;
+    // size LDS and the points-per-lane variant by the frames' real size
+    return layout_core(active_points(c), c.K, maxV, maxRow ? maxRow[0] : 0, lay, nt, lds_limit);
 }
 
 // Two frames per CU?  Up to 2 points per lane of a 512-lane workgroup, the whole plan in half the CU's LDS, and -- if
 // kernel 0 has long rows -- few enough vertices for the chain lanes of four wavefront pairs.
 bool small_layout(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, FusedLayout *lay)
 {
-    const int NA = c.activeN > 0 ? c.activeN : c.maxN;
+    const int NA = active_points(c);
     if (c.F < kSmallMinFrames || NA > 2 * kNTSmall || maxV[0] > kNTSmall) return false;
     const int row0 = maxRow ? maxRow[0] : 0;
     if (row0 >= kChainMinRow && !chain_wanted(NA, maxV[0], row0, kNTSmall)) return false;   // long rows need the chain path: keep 1024 lanes
@@ -559,23 +558,19 @@ int lean_shape()
     return v;
 }
 
-bool lean_layout(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, FusedLayout *lay, int *nt_out)
+bool lean_layout(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, FusedLayout *lay)
 {
-    const int shape = lean_shape();
-    if (shape != 2) return false;
+    if (lean_shape() != 2) return false;
     const int nt = kNTSmall, max_ppt = 4;
-    const int NA = c.activeN > 0 ? c.activeN : c.maxN;
+    const int NA = active_points(c);
     // Frames of 513 .. 1024 points take the plan too (two points per lane, everything in registers -- no re-reads): C1 6.47 -> 7.03e7
     // iterations/s against the half-CU form of the 137 KB plan (shared product buffer there as well, but no fused X + P and no
     // overlapped blur schedule).  Up to 512 points both kernels' products fit half a CU with buffers of their OWN: 9.94e7 against 9.05e7
     // on this plan -- those keep small_layout().
-    if (c.L != 2 || c.K < 1 || c.K > kMaxFusedK || c.F < kSmallMinFrames || NA <= kNTSmall || NA > max_ppt * nt) return false;
-    for (int k = 0; k < c.K; ++k)
-        if (kds[k].d != 2 || kds[k].Epad >= 65535) return false;
+    if (!slam_shaped(c, kds, true) || c.F < kSmallMinFrames || NA <= kNTSmall || NA > max_ppt * nt) return false;
     FusedLayout L;
     if (!layout_lean(NA, c.K, maxV, maxRow ? maxRow[0] : 0, &L, nt, kLdsHalf)) return false;
     *lay = L;
-    *nt_out = nt;
     return true;
 }
 
@@ -583,93 +578,58 @@ bool lean_layout(const CrfDev &c, const KernelDev *kds, const int *maxV, const i
 // buffer in fused_loop.h's loop as well: 2.04e7 against 2.42e7 iterations/s.  With nobody else on the CU the re-reads' latency and the
 // seven barriers are all exposed; the plan pays through co-residency, not through its schedule alone.)
 
-template <int NT, int PPT, int K, int CH, bool RELOAD, int MODE>
-void launch_lean_mode(const CrfDev &c, const FusedArgs &a, hipStream_t s)
+// the shape decision of launch_inference_fused
+struct FusedShape {
+    bool ok, small, lean;
+    int nt, ppt, points;                  // lanes per workgroup, points per lane, points per frame (active_points)
+    int report() const { return nt | ((small || lean) ? 2 : 1) << 16; }   // what launch_inference_fused returns: lanes | frames per CU << 16
+};
+FusedShape choose_shape(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, FusedLayout *lay)
 {
-    auto fn = k_fused_lean<NT, PPT, K, CH, RELOAD, MODE>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit);
-    fn<<<dim3(c.F), dim3(NT), a.lay.total, s>>>(c, a);
+    FusedShape sh{false, false, false, kNT, 1, active_points(c)};
+    const bool lean_first = sh.points <= 2 * kNTSmall && lean_layout(c, kds, maxV, maxRow, lay);      // (513 .. 1024 points: lean before small)
+    sh.small = !lean_first && small_layout(c, kds, maxV, maxRow, lay);
+    sh.lean = lean_first || (!sh.small && lean_layout(c, kds, maxV, maxRow, lay));
+    if (!sh.small && !sh.lean && !make_layout(c, kds, maxV, maxRow, lay)) return sh;
+    sh.ok = true;
+    sh.nt = (sh.small || sh.lean) ? kNTSmall : kNT;
+    sh.ppt = std::max((sh.points + sh.nt - 1) / sh.nt, 1);
+    return sh;
 }
 
-// mode: 0 the self-contained kernel, 1 prepare, 2 run from the prepared blocks
-template <int NT, int PPT, int K, int CH, bool RELOAD>
-void launch_lean(const CrfDev &c, const FusedArgs &a, hipStream_t s, int mode)
-{
-    if (mode == 2) launch_lean_mode<NT, PPT, K, CH, RELOAD, 2>(c, a, s);
-    else if (mode == 1) launch_lean_mode<NT, PPT, K, CH, RELOAD, 1>(c, a, s);
-    else launch_lean_mode<NT, PPT, K, CH, RELOAD, 0>(c, a, s);
-}
+static_assert((int)kLdsLimit == kWorkgroupLdsMax, "launch_workgroups raises every kernel's LDS ceiling to the plans' limit");
 
-template <int NT, int PPT, bool RELOAD>
-void launch_lean_ppt(const CrfDev &c, const FusedArgs &a, hipStream_t s, int mode)
+// The shape choose_shape has chosen, in one of the three modes: 0 the self-contained kernel, 1 prepare, 2 run from the prepared blocks.
+// Every run-time value becomes a template argument here: the mode, K, kernel 0 short-row / chain and the points per lane -- 1 .. 4 at
+// 1024 lanes, 1 .. 2 at 512 (small_layout), RELOAD from 3 on the lean plan.  (No batch reaches the lean plan's 1-point-per-lane
+// kernels -- lean_layout starts at 513 points -- but they stay instantiated: without them the compiler lays out the tail of the eight
+// k_fused<512, 1, ..> kernels of modes 0 and 2 differently.)
+void launch_shape(const CrfDev &c, const FusedArgs &a, hipStream_t s, int mode, const FusedShape &sh)
 {
-    if (c.K == 1) {
-        if (a.lay.chain0) launch_lean<NT, PPT, 1, 1, RELOAD>(c, a, s, mode);
-        else launch_lean<NT, PPT, 1, 0, RELOAD>(c, a, s, mode);
-    } else {
-        if (a.lay.chain0) launch_lean<NT, PPT, 2, 1, RELOAD>(c, a, s, mode);
-        else launch_lean<NT, PPT, 2, 0, RELOAD>(c, a, s, mode);
-    }
-}
-
-void launch_lean_any(const CrfDev &c, const FusedArgs &a, hipStream_t s, int mode, int NAp)
-{
-    if (NAp <= 512) launch_lean_ppt<512, 1, false>(c, a, s, mode);
-    else if (NAp <= 2 * 512) launch_lean_ppt<512, 2, false>(c, a, s, mode);
-    else if (NAp <= 3 * 512) launch_lean_ppt<512, 3, true>(c, a, s, mode);
-    else launch_lean_ppt<512, 4, true>(c, a, s, mode);
-}
-
-template <int NT, int PPT, int K, int CH, int MODE>
-void launch_fused_mode(const CrfDev &c, const FusedArgs &a, hipStream_t s)
-{
-    auto fn = k_fused<NT, PPT, K, CH, MODE>;
-    // per (function, device); cheap enough to repeat and safe with several devices in one process
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)kLdsLimit);
-    fn<<<dim3(c.F), dim3(NT), a.lay.total, s>>>(c, a);
-}
-
-template <int NT, int PPT, int K, int CH>
-void launch_fused(const CrfDev &c, const FusedArgs &a, hipStream_t s, int mode)
-{
-    if (mode == 2) launch_fused_mode<NT, PPT, K, CH, 2>(c, a, s);
-    else if (mode == 1) launch_fused_mode<NT, PPT, K, CH, 1>(c, a, s);
-    else launch_fused_mode<NT, PPT, K, CH, 0>(c, a, s);
-}
-
-template <int NT, int PPT>
-void launch_fused_ppt(const CrfDev &c, const FusedArgs &a, hipStream_t s, int mode)
-{
-    if (c.K == 1) {
-        if (a.lay.chain0) launch_fused<NT, PPT, 1, 1>(c, a, s, mode);
-        else launch_fused<NT, PPT, 1, 0>(c, a, s, mode);
-    } else {
-        if (a.lay.chain0) launch_fused<NT, PPT, 2, 1>(c, a, s, mode);
-        else launch_fused<NT, PPT, 2, 0>(c, a, s, mode);
-    }
-}
-
-// the shape launch_inference_fused has chosen, in one of the three modes
-void launch_shape(const CrfDev &c, const FusedArgs &a, hipStream_t s, int mode, int NAp, bool small, bool lean)
-{
-    if (small) {
-        if (NAp <= kNTSmall) launch_fused_ppt<kNTSmall, 1>(c, a, s, mode);
-        else launch_fused_ppt<kNTSmall, 2>(c, a, s, mode);
-    } else if (lean) {
-        launch_lean_any(c, a, s, mode, NAp);
-    } else {
-        switch ((NAp + kNT - 1) / kNT) {
-        case 1: launch_fused_ppt<kNT, 1>(c, a, s, mode); break;
-        case 2: launch_fused_ppt<kNT, 2>(c, a, s, mode); break;
-        case 3: launch_fused_ppt<kNT, 3>(c, a, s, mode); break;
-        case 4: launch_fused_ppt<kNT, 4>(c, a, s, mode); break;
-        default: break;
-        }
-    }
+    auto go = [&](auto fn) { launch_workgroups(fn, c.F, sh.nt, a.lay.total, s, c, a); };
+    with_dims<0, 2>(mode, [&](auto m) {
+        with_dims<1, kMaxFusedK>(c.K, [&](auto kk) {
+            with_dims<0, 1>(a.lay.chain0 ? 1 : 0, [&](auto ch) {
+                constexpr int M = decltype(m)::value, K = decltype(kk)::value, CH = decltype(ch)::value;
+                if (sh.lean) with_dims<1, 4>(sh.ppt, [&](auto p) { go(k_fused_lean<kNTSmall, decltype(p)::value, K, CH, (decltype(p)::value >= 3), M>); });
+                else if (sh.small) with_dims<1, 2>(sh.ppt, [&](auto p) { go(k_fused<kNTSmall, decltype(p)::value, K, CH, M>); });
+                else with_dims<1, 4>(sh.ppt, [&](auto p) { go(k_fused<kNT, decltype(p)::value, K, CH, M>); });
+            });
+        });
+    });
 }
 
 }  // namespace
+
+// The SLAM-shaped CRF the one-workgroup engines are specialised for: two labels, one or two 2-D kernels; u16_tables: ... whose entries
+// fit the u16 row pointers / neighbour ids / slots of the records the fused engine reads (the frame engine builds its own)
+bool slam_shaped(const CrfDev &c, const KernelDev *kds, bool u16_tables)
+{
+    if (c.L != 2 || c.K < 1 || c.K > kMaxFusedK) return false;
+    for (int k = 0; k < c.K; ++k)
+        if (kds[k].d != 2 || (u16_tables && kds[k].Epad >= 65535)) return false;
+    return true;
+}
 
 bool fused_supported(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, size_t *lds_bytes)
 {
@@ -677,26 +637,6 @@ bool fused_supported(const CrfDev &c, const KernelDev *kds, const int *maxV, con
     const bool ok = make_layout(c, kds, maxV, maxRow, &lay);
     if (lds_bytes) *lds_bytes = ok ? (size_t)lay.total : 0;
     return ok;
-}
-
-// the shape decision of launch_inference_fused
-struct FusedShape {
-    bool ok, small, lean;
-    int nt, ppt;
-};
-static FusedShape choose_shape(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, FusedLayout *lay)
-{
-    FusedShape sh{false, false, false, kNT, 1};
-    int lean_nt = 0;
-    const int NAp = c.activeN > 0 ? c.activeN : c.maxN;
-    const bool lean_first = NAp <= 2 * kNTSmall && lean_layout(c, kds, maxV, maxRow, lay, &lean_nt);      // (513 .. 1024 points: lean before small)
-    sh.small = !lean_first && small_layout(c, kds, maxV, maxRow, lay);
-    sh.lean = lean_first || (!sh.small && lean_layout(c, kds, maxV, maxRow, lay, &lean_nt));
-    if (!sh.small && !sh.lean && !make_layout(c, kds, maxV, maxRow, lay)) return sh;
-    sh.ok = true;
-    sh.nt = (sh.small || sh.lean) ? kNTSmall : kNT;
-    sh.ppt = std::max((NAp + sh.nt - 1) / sh.nt, 1);
-    return sh;
 }
 
 size_t lean_prep_bytes(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow)
@@ -714,22 +654,15 @@ int launch_inference_fused(const CrfDev &c, const KernelDev *kds, const int *max
     FusedArgs a{};
     const FusedShape sh = choose_shape(c, kds, maxV, maxRow, &a.lay);
     if (!sh.ok) return 0;
-    const bool small = sh.small, lean = sh.lean;
     for (int k = 0; k < c.K; ++k) a.kd[k] = kds[k];
     a.n_iter = n_iter;
     a.with_map = with_map;
     a.relax = relax;
     a.omr = 1 - relax;
-    static long long *timing_buf = nullptr;
-    static const bool want_timing = kInstr && ab_env("LCCRF_FUSED_TIMING") != nullptr;
-    if (want_timing && !timing_buf) (void)hipMalloc(&timing_buf, 64 * sizeof(long long));
-    a.timing = want_timing ? timing_buf : nullptr;
-    a.timing_block = want_timing ? std::max(atoi(ab_env("LCCRF_FUSED_TIMING")) - 1, 0) : 0;
-    if (a.timing_block >= c.F) a.timing_block = 0;
-    a.timing_lane = (want_timing && ab_env("LCCRF_FUSED_TIMING_LANE")) ? atoi(ab_env("LCCRF_FUSED_TIMING_LANE")) & (kNT - 1) : 0;
+    static StampBuffer stamps("LCCRF_FUSED_TIMING", "LCCRF_FUSED_TIMING_LANE", "fused");
+    stamps.arm(c.F, kNT, &a.timing, &a.timing_block, &a.timing_lane);
     static const int dbg = (kInstr && ab_env("LCCRF_FUSED_DBG")) ? atoi(ab_env("LCCRF_FUSED_DBG")) : 0;
     a.dbg = dbg;
-    const int NAp = c.activeN > 0 ? c.activeN : c.maxN;
     // Prepared launch records (fused_lean.h: LeanPrepPlan): what the prologue derives from the lattices and the plan alone.  The FIRST
     // inference behind a build runs the self-contained kernel (a caller with one inference per lattice pays nothing); the second one
     // writes the blocks (MODE 1) and every inference from then on starts from them (MODE 2).
@@ -737,15 +670,16 @@ int launch_inference_fused(const CrfDev &c, const KernelDev *kds, const int *max
     const LeanPrepPlan pp = lean_prep_plan(a.lay, c.K, a.Vcap, sh.nt, sh.ppt);
     static const bool no_prep = ab_env("LCCRF_NO_LEAN_PREP") != nullptr;    // A/B switch (instrumented library): same results either way
     int mode = 0;
-    bool pieces_ok = true;                           // (the run kernels move every table with one (lean) / two 16-byte loads per lane)
-    for (int k = 0; k < c.K; ++k) pieces_ok = pieces_ok && pp.row_bytes[k] <= (lean ? 1 : 2) * sh.nt * 16 && pp.nbr_bytes[k] <= (lean ? 1 : 2) * sh.nt * 16;
+    const int pieces = (sh.lean ? 1 : 2) * sh.nt * 16;   // (the run kernels move every table with one (lean) / two 16-byte loads per lane)
+    bool pieces_ok = true;
+    for (int k = 0; k < c.K; ++k) pieces_ok = pieces_ok && pp.row_bytes[k] <= pieces && pp.nbr_bytes[k] <= pieces;
     if (prep && prep->buf && !no_prep && pieces_ok && c.F >= kPrepMinFrames && (size_t)pp.total * (size_t)c.F <= prep->bytes) {
         // what the blocks depend on besides the lattices themselves: the plan, the shape, the frame count
         unsigned long long key = 1469598103934665603ull;
         auto mix = [&](const void *p, size_t n) { for (size_t i = 0; i < n; ++i) key = (key ^ static_cast<const unsigned char *>(p)[i]) * 1099511628211ull; };
         mix(&a.lay, sizeof(a.lay));
         mix(a.Vcap, sizeof(int) * c.K);
-        const int shape[6] = {c.F, c.K, sh.ppt, NAp, sh.nt, lean ? 2 : small ? 1 : 0};
+        const int shape[6] = {c.F, c.K, sh.ppt, sh.points, sh.nt, sh.lean ? 2 : sh.small ? 1 : 0};
         mix(shape, sizeof(shape));
         a.prep = prep->buf;
         a.prep_stride = pp.total;
@@ -753,7 +687,7 @@ int launch_inference_fused(const CrfDev &c, const KernelDev *kds, const int *max
             mode = 2;
         } else if (prep->seen_key == key) {      // the second inference on these lattices: write the blocks, then run from them
             if (prep->ev0) (void)hipEventRecord(prep->ev0, s);
-            launch_shape(c, a, s, 1, NAp, small, lean);
+            launch_shape(c, a, s, 1, sh);
             if (prep->ev1) (void)hipEventRecord(prep->ev1, s);
             prep->timed = prep->ev0 && prep->ev1;
             prep->valid = true;
@@ -764,16 +698,9 @@ int launch_inference_fused(const CrfDev &c, const KernelDev *kds, const int *max
             prep->seen_key = key;                            // the first one
         }
     }
-    launch_shape(c, a, s, mode, NAp, small, lean);
-    if (a.timing) {                       // debug only: synchronous read-back of workgroup 0's phase stamps
-        long long h[64];
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpy(h, a.timing, sizeof(h), hipMemcpyDeviceToHost);
-        fprintf(stderr, "[lccrf fused timing] %lld stamps, deltas (shader clocks):", h[63]);
-        for (int i = 1; i < h[63] && i < 63; ++i) fprintf(stderr, " %lld", h[i] - h[i - 1]);
-        fprintf(stderr, "\n");
-    }
-    return small ? (kNTSmall | 2 << 16) : lean ? (kNTSmall | 2 << 16) : (kNT | 1 << 16);
+    launch_shape(c, a, s, mode, sh);
+    stamps.print(s);                      // debug only: synchronous read-back of one workgroup's phase stamps
+    return sh.report();
 }
 
 }  // namespace lccrf

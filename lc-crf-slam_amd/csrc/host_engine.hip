@@ -436,7 +436,7 @@ int Engine::build_kernels(int k0, int n)
     for (int k = k0; k < k0 + n; ++k) kernels[k].maxV = kernels[k].dev.Epad;
     if (k0 == 0) {                                     // a build of every kernel decides the internal point order afresh
         static const bool no_perm = ab_env("LCCRF_NO_PERM") != nullptr;   // A/B and cross-check switch: same results either way
-        const int NAp = activeN > 0 ? activeN : maxN;
+        const int NAp = active_points(crf);
         const bool want = allow_perm && !no_perm && !perm_banned && (!perm_scoped || perm_scope) && n > 0 && n == (int)kernels.size() && NAp >= perm_min_points();
         if (want || perm_on) {                         // whatever was derived in the old order is stale
             if (unary_is_label) unary_deferred = true;
@@ -469,7 +469,7 @@ int Engine::build_kernels(int k0, int n)
     int k = k0;
     while (k < k0 + n) {
         int m = 1;
-        const int NA = activeN > 0 ? activeN : maxN;
+        const int NA = active_points(crf);
         // (locality mode: the one-workgroup build knows nothing of the internal point order -- ADVICE r4: with the threshold lowered
         // below its range it would have built in the caller's order under an engine that iterates in the permuted one)
         const bool small_ok = !no_small && !perm_on;
@@ -575,7 +575,7 @@ int Engine::learn_sizes()
         }
         // a coarse kernel over many points (listed rows, or more than ~4 entries per row on average): the row-walking splat with
         // its loads up front + a workgroup per listed row, no blur pass in the splat
-        const int NAr = activeN > 0 ? activeN : maxN;
+        const int NAr = active_points(crf);
         kd.long_mode = kd.longrow_ok && (nlong > 0 || (long)NAr * kd.D1 > 4L * std::max(m, 1));
         if (kd.long_mode && (long)NAr * kd.D1 >= 16L * std::max(m, 1)) kd.long_mode = 2;       // ... a wavefront per vertex from ~16 entries per row
         kernels[k].maxV = m;

@@ -4,8 +4,8 @@
 //   stream_filter.hip      splat / blur / slice, the normalisation and the schedule of a mean-field step
 //   stream_pointwise.hip   the kernels with a thread per point or per (point, label): unary, softmax, MAP, row copies
 #pragma once
-#include <type_traits>
 #include "engine.h"
+#include "dispatch.h"   // with_dims
 
 namespace lccrf {
 namespace {
@@ -57,16 +57,6 @@ inline dim3 grid_for(long work, int F)
 {
     const long nb = (work + kBlock - 1) / kBlock;
     return dim3((unsigned)(nb > 0 ? nb : 1), (unsigned)F);   // empty frames still get a (no-op) block
-}
-
-// The one dispatch on a dimension known at compile time: fn(std::integral_constant<int, D>) for the D in [Lo, Hi] that equals d;
-// returns whether there was one
-template <int Lo, int Hi, typename Fn>
-bool with_dims(int d, Fn fn)
-{
-    if constexpr (Lo > Hi) return false;
-    else if (d == Lo) return fn(std::integral_constant<int, Lo>{}), true;
-    else return with_dims<Lo + 1, Hi>(d, fn);
 }
 
 }  // namespace
