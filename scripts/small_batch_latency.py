@@ -7,10 +7,7 @@ pkg = importlib.import_module("lc-crf-slam_amd"); wl = importlib.import_module("
 import crf_cases as cc
 for F in (4, 32, 128):
     pbs = [wl.slam_problem(2000, seed=700 + i) for i in range(F)]
-    b = cc.batch_of(pkg, pbs) if hasattr(cc, "batch_of") else None
-    if b is None:
-        from test_frame_engine import _batch_of
-        b = _batch_of(pbs)
+    b = cc.batch_of(pbs)
     for _ in range(5): b.run(5, True); b.map()
     ts = []
     for _ in range(40):

@@ -150,9 +150,7 @@ def small_case(rng):
     maxN = int(rng.integers(40, 1025))
     base = [wl.slam_problem(int(rng.integers(0, maxN + 1)), seed=int(rng.integers(1, 1 << 30))) for _ in range(6)]
     base[0] = wl.slam_problem(maxN, seed=int(rng.integers(1, 1 << 30)))
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from test_hip_parity import _shaped_problem
-    odd = _shaped_problem(wl, maxN, "sparse", seed=5) if maxN >= 300 else base[1]
+    odd = cc.shaped_problem(wl, maxN, "sparse", seed=5) if maxN >= 300 else base[1]
     where = set(int(x) for x in rng.integers(0, F, 3))
     pbs = [odd if f in where else base[f % 6] for f in range(F)]
     sizes = [pb["N"] for pb in pbs]

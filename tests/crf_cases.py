@@ -5,6 +5,7 @@ A "backend" is any class with the reference's operator surface on numpy arrays
   cls(N, L); set_unary | set_unary_from_label; add_pairwise(features, w);
   start_inference(); step_inference(relax); build_map(); probability(); map(); kernel(k)
 """
+import importlib
 import os
 
 import numpy as np
@@ -132,3 +133,116 @@ def label_problem(N, L, dims, seed, label=False, spread=3.0):
         u[:, L - 1] = u[:, 0]
         pb["unary"] = u
     return pb
+
+
+def shaped_problem(wl, N, shape, seed):
+    """SLAM-shaped frames whose lattices stress one code path of the fused engine each."""
+    pb = wl.slam_problem(N, seed=seed)
+    rng = np.random.default_rng(seed)
+    f0, f1 = pb["kernels"][0][0].copy(), pb["kernels"][1][0].copy()
+    if shape == "one_cell":            # every point in one lattice cell: 3 vertices, rows of N products
+        f0[:] = f0[0]
+        f1[:] = f1[0]
+    elif shape == "two_clusters":      # two very long rows per kernel plus stragglers
+        half = N // 2
+        f0[:half], f0[half:] = f0[0], f0[-1] + np.float32(7.5)
+        f0[::97] += rng.normal(0, 3, f0[::97].shape).astype(np.float32)
+    elif shape == "rows_of_8":         # row lengths around the 8-product units of chain_rows
+        cells = max(N // 8, 1)
+        f0 = (np.stack([np.arange(N) % cells, np.arange(N) % cells], 1) * np.float32(4.0)).astype(np.float32)
+    elif shape == "sparse":            # every point its own cell: V = 3N, far beyond the chain's vertex limit
+        f0 = (np.stack([np.arange(N), (np.arange(N) * 7) % 1013], 1) * np.float32(9.0)).astype(np.float32)
+    pb["kernels"] = [(f0, pb["kernels"][0][1]), (f1, pb["kernels"][1][1])]
+    return pb
+
+
+def large_case(z, name):
+    """(problem, iterations, relax) of one case of tests/golden/large.npz"""
+    pb = dict(N=int(z[name + "_features"].shape[0]), L=int(z[name + "_Q"].shape[1]),
+              kernels=[(z[name + "_features"], np.float32(z[name + "_w"]))])
+    if name + "_unary" in z.files:
+        pb["unary"] = z[name + "_unary"]
+    else:
+        pb["label"], pb["conf"] = z[name + "_label"], np.float32(z[name + "_conf"])
+    return pb, int(z[name + "_iters"]), float(z[name + "_relax"])
+
+
+def golden_problem(golden, name):
+    group, case = name.split(":")
+    if group == "labels":                                       # (not among conftest's fixtures)
+        return case_problem(np.load(os.path.join(os.path.dirname(__file__), "golden", "labels.npz")), case)
+    z = golden[group]
+    if group == "large":
+        pb, _, _ = large_case(z, case)
+        return pb
+    return case_problem(z, case)
+
+
+def crop_problem(golden, po):
+    """64 x 48 crop of the reference's image example: 21 labels, the position and RGB image terms."""
+    z = golden["example_im1"]
+    W, H = 64, 48
+    im = np.ascontiguousarray(z["im"][:H, :W], np.uint8)
+    lab = np.ascontiguousarray(z["label"].reshape(240, 320)[:H, :W].reshape(-1), np.int16)
+    pb = dict(N=W * H, L=21, label=lab, conf=np.float32(0.5),
+              kernels=[(po.oracle_image_features(W, H, 3.0), np.float32(3.0)),
+                       (po.oracle_image_features(W, H, 60.0, im, 20.0), np.float32(10.0))])
+    return pb, (W, H, im)
+
+
+# the cases of test_gradients_match_the_checker (tests/test_meanfield_backward.py)
+CASES = ["slam:N5", "slam:N1001", "slam:C3", "generic:d1_L3", "generic:d3_L21", "generic:d5_L2", "generic:d6_L3", "generic:multi",
+         "bilateral:c5", "large:c5", "image64x48", "c2"]
+
+
+def case(name, golden, po, wl):
+    """(problem, image or None)"""
+    if name == "image64x48":
+        return crop_problem(golden, po)
+    if name.startswith("K8_L"):                                  # eight terms of d = 1 .. 8
+        return label_problem(900, int(name[4:]), list(range(1, 9)), seed=6), None
+    if name == "c2":
+        return wl.slam_problem(2000, seed=12), None
+    return golden_problem(golden, name), None
+
+
+def batch_of(pbs, maxN=None, use_unary=False):
+    """two-label SLAM frames as one BatchCRF with its inputs set"""
+    pkg = importlib.import_module("lc-crf-slam_amd")
+    F = len(pbs)
+    maxN = maxN or max(max(pb["N"] for pb in pbs), 1)
+    K = len(pbs[0]["kernels"])
+    feats = [np.zeros((F, maxN, 2), np.float32) for _ in range(K)]
+    label = np.full((F, maxN), -1, np.int16)
+    unary = np.zeros((F, maxN, 2), np.float32)
+    for f, pb in enumerate(pbs):
+        n = pb["N"]
+        if "label" in pb:
+            label[f, :n] = pb["label"]
+        if "unary" in pb:
+            unary[f, :n] = pb["unary"]
+        for k in range(K):
+            feats[k][f, :n] = pb["kernels"][k][0]
+    b = pkg.BatchCRF(F, maxN, 2, [2] * K, [float(pbs[0]["kernels"][k][1]) for k in range(K)])
+    if use_unary:
+        b.set_inputs_host([pb["N"] for pb in pbs], feats, unary=unary)
+    else:
+        b.set_inputs_host([pb["N"] for pb in pbs], feats, label=label, conf=pbs[0].get("conf", 0.7))
+    return b
+
+
+def raw_unary(pb):
+    """raw unary energies [N][L] of a problem (from its labels by the formula of densecrf3d.h:109-129 where it has no raw ones)"""
+    if "unary" in pb:
+        return np.ascontiguousarray(pb["unary"], np.float32).reshape(pb["N"], pb["L"])
+    N, L, c = pb["N"], pb["L"], np.float32(pb["conf"])
+    lab = np.asarray(pb["label"], np.int64)
+    U = np.full((N, L), -np.log((np.float32(1) - c) / np.float32(L - 1)), np.float32)
+    has = lab >= 0
+    U[np.nonzero(has)[0], lab[has]] = -np.log(c)
+    U[~has] = -np.log(np.float32(1.0) / np.float32(L))
+    return U
+
+
+def empty_problem(L, dims):
+    return dict(N=0, L=L, unary=np.zeros((0, L), np.float32), kernels=[(np.zeros((0, d), np.float32), 1.0) for d in dims])

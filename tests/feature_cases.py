@@ -2,9 +2,9 @@
 the ones built with deliberate lattice ties (the derivative is one-sided there), plus tie-free generic frames of the same
 dimensions so that every compiled d = 1 .. 8 is covered (257 points drawn with spread 1.5: at the
 golden cases' spread of 4 the points of a d = 8 frame sit alone on their vertices and every feature gradient is rounding noise)."""
-import test_meanfield_backward as tb
+import crf_cases as cc
 
-# generic:d1_L3, d3_L21, d5_L2, d6_L3 of tb.CASES are generic_problem(..., lattice_ties=True): replaced by the nt: cases
+# generic:d1_L3, d3_L21, d5_L2, d6_L3 of cc.CASES are generic_problem(..., lattice_ties=True): replaced by the nt: cases
 CASES = ["slam:N5", "slam:N1001", "slam:C3", "generic:multi", "bilateral:c5", "large:c5", "image64x48", "c2",
          "nt:d1_L3", "nt:d3_L21", "nt:d5_L2", "nt:d6_L3", "nt:d4_L5", "nt:d7_L2", "nt:d8_L33", "nt:d2-5-3_L9"]
 
@@ -14,4 +14,4 @@ def case(name, golden, po, wl):
     if name.startswith("nt:"):
         dims, L = name[3:].split("_L")
         return wl.generic_problem(257, [int(d) for d in dims[1:].split("-")], int(L), seed=7, spread=1.5), None
-    return tb._case(name, golden, po, wl)
+    return cc.case(name, golden, po, wl)

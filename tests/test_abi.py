@@ -2,25 +2,17 @@
 declares, and fails LOUDLY (no CPU fallback) when no GPU is usable.  No compute here."""
 import ctypes as C
 import importlib
-import os
 import re
 
 import pytest
 
+from abi_support import header_source, lib  # noqa: F401
+
 pkg = importlib.import_module("lc-crf-slam_amd")
 
 
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(pkg.LIB_PATH):
-        pkg.build_library()
-    return pkg.lib()
-
-
 def declared_symbols():
-    src = open(pkg.HEADER_PATH).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(lccrf_[a-z0-9_]+)\s*\(", src)))
+    return sorted(set(re.findall(r"\b(lccrf_[a-z0-9_]+)\s*\(", header_source())))
 
 
 def test_header_declares_the_reference_operator_surface():

@@ -5,34 +5,23 @@ frame (bit for bit) and against the float64 checker, its state, determinism, reb
 lccrf_batch_set_pairwise_weight / lccrf_batch_set_unary_device against freshly bound batches, and the torch layer."""
 import ctypes as C
 import importlib
-import os
-import re
 
 import numpy as np
 import pytest
 
+import batch_cases as bc
 import crf_cases as cc
+import grad_support as gs
 import meanfield_f64 as mf
+from abi_support import assert_declared_exported_bound, dev, hip_malloc, lib  # noqa: F401
 
 pkg = importlib.import_module("lc-crf-slam_amd")
 NEW_SYMBOLS = ("lccrf_batch_set_pairwise_weight", "lccrf_batch_set_unary_device", "lccrf_batch_inference_backward")
-GRAD_TOL = 1e-4
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(pkg.LIB_PATH):
-        pkg.build_library()
-    return pkg.lib()
 
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------------
 def test_batch_backward_symbols_are_declared_exported_and_bound(lib):
-    src = re.sub(r"/\*.*?\*/", "", open(pkg.HEADER_PATH).read(), flags=re.S)
-    for n in NEW_SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % n, src), n
-        assert hasattr(lib, n), n
-        assert getattr(lib, n).argtypes is not None, n
+    assert_declared_exported_bound(lib, NEW_SYMBOLS)
     assert lib.lccrf_abi_version() == 3
     for m in ("set_pairwise_weight", "set_unary_device", "inference_backward_device"):
         assert hasattr(pkg.BatchCRF, m), m
@@ -47,91 +36,6 @@ def test_batch_backward_rejects_a_null_handle(lib):
 
 
 # ---- helpers ----------------------------------------------------------------------------------------------------------------
-def _unary(pb):
-    """raw unary energies [N][L] of a problem (from its labels by the formula of densecrf3d.h:109-129 where it has no raw ones)"""
-    if "unary" in pb:
-        return np.ascontiguousarray(pb["unary"], np.float32).reshape(pb["N"], pb["L"])
-    N, L, c = pb["N"], pb["L"], np.float32(pb["conf"])
-    lab = np.asarray(pb["label"], np.int64)
-    U = np.full((N, L), -np.log((np.float32(1) - c) / np.float32(L - 1)), np.float32)
-    has = lab >= 0
-    U[np.nonzero(has)[0], lab[has]] = -np.log(c)
-    U[~has] = -np.log(np.float32(1.0) / np.float32(L))
-    return U
-
-
-def _empty(L, dims):
-    return dict(N=0, L=L, unary=np.zeros((0, L), np.float32), kernels=[(np.zeros((0, d), np.float32), 1.0) for d in dims])
-
-
-class Frames:
-    """Problems laid out as one batch's inputs: [F][max_points][.] arrays, rows beyond a frame's points 0."""
-
-    def __init__(self, probs, weights, max_points=None):
-        self.probs, self.w = probs, [float(w) for w in weights]
-        self.L = probs[0]["L"]
-        self.N = np.array([pb["N"] for pb in probs], np.int32)
-        self.maxN = int(max_points or self.N.max())
-        self.dims = [f.shape[1] for f, _ in probs[0]["kernels"]]
-        F = len(probs)
-        self.U = np.zeros((F, self.maxN, self.L), np.float32)
-        self.feats = [np.zeros((F, self.maxN, d), np.float32) for d in self.dims]
-        for f, pb in enumerate(probs):
-            self.U[f, :pb["N"]] = _unary(pb)
-            for k, (ft, _) in enumerate(pb["kernels"]):
-                self.feats[k][f, :pb["N"]] = ft
-        self.K = len(self.dims)
-
-    def batch(self, weights=None, max_frames=None, build=True):
-        b = pkg.BatchCRF(max_frames or len(self.probs), self.maxN, self.L, self.dims, weights or self.w)
-        b.set_inputs_host(self.N, self.feats, unary=self.U)
-        if build:
-            b.build()
-        return b
-
-    def handle(self, f):
-        h = pkg.DenseCRFHIP(int(self.N[f]), self.L)
-        h.set_unary(self.U[f, :self.N[f]])
-        for k, (ft, _) in enumerate(self.probs[f]["kernels"]):
-            h.add_pairwise(ft, self.w[k])
-        return h
-
-    def grad_prob(self, seed):
-        """dL/dQ [F][max_points][L]; NaN beyond every frame's points (read there, it would poison the frame)"""
-        G = np.random.default_rng(seed).standard_normal((len(self.probs), self.maxN, self.L)).astype(np.float32)
-        for f, n in enumerate(self.N):
-            G[f, n:] = np.nan
-        return G
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _batch_backward(b, T, relax, G, K, stream=None):
-    import torch
-    g = _dev(G)
-    gu = torch.full(G.shape, float("nan"), device="cuda")
-    gw = torch.full((G.shape[0], max(K, 1)), float("nan"), device="cuda")
-    torch.cuda.synchronize()
-    b.inference_backward_device(T, relax, g.data_ptr(), gu.data_ptr(), gw.data_ptr() if K else None, stream=stream)
-    b.synchronize()
-    torch.cuda.synchronize()
-    return gu.cpu().numpy(), gw[:, :K].cpu().numpy()
-
-
-def _handle_backward(h, T, relax, G, K):
-    import torch
-    g = _dev(G)
-    gu = torch.full(G.shape, float("nan"), device="cuda")
-    gw = torch.full((max(K, 1),), float("nan"), device="cuda")
-    torch.cuda.synchronize()
-    h.inference_backward_device(T, relax, g.data_ptr(), gu.data_ptr(), gw.data_ptr() if K else None)
-    h.synchronize()
-    return gu.cpu().numpy(), gw[:K].cpu().numpy()
-
-
 def _check_parity(fr, handles, gu, gw, T, relax, G):
     """every frame: the handle's bits; zero rows beyond its points; a frame of 0 points all zeros"""
     for f, n in enumerate(fr.N):
@@ -139,7 +43,7 @@ def _check_parity(fr, handles, gu, gw, T, relax, G):
         if n == 0:
             assert np.all(gw[f] == 0), "frame %d (0 points): weight gradient not 0" % f
             continue
-        hu, hw = _handle_backward(handles[f], T, relax, G[f, :n], fr.K)
+        hu, hw = gs.backward(handles[f], T, relax, G[f, :n], fr.K)
         assert cc.same_bits(gu[f, :n], hu), "frame %d (N=%d) T=%d relax=%g: dL/dU differs from the handle's" % (f, n, T, relax)
         assert cc.same_bits(gw[f], hw), "frame %d (N=%d) T=%d relax=%g: dL/dw %s, handle %s" % (f, n, T, relax, gw[f], hw)
 
@@ -152,32 +56,6 @@ def _same_valid(a, b, N):
     return all(cc.same_bits(a[f, :n], b[f, :n]) for f, n in enumerate(N))
 
 
-def _slam_frames(golden, wl, Ns=(0, 5, 7, 1000, 1001, 2000, 2002, 3000)):
-    """SLAM frames (two terms, L = 2): the golden slam cases where they exist, else wl.slam_problem; the TUM3 weights"""
-    probs = []
-    for i, n in enumerate(Ns):
-        if n == 0:
-            probs.append(_empty(2, [2, 2]))
-        elif "N%d_N" % n in golden["slam"].files:
-            probs.append(cc.case_problem(golden["slam"], "N%d" % n))
-        else:
-            probs.append(wl.slam_problem(n, seed=20 + i))
-    return Frames(probs, [wl.TUM3["w1"], wl.TUM3["w2"]])
-
-
-def _generic_frames(wl, Ns=(300, 0, 1500, 77, 2500)):
-    probs = [wl.generic_problem(n, [3], 3, seed=40 + i) if n else _empty(3, [3]) for i, n in enumerate(Ns)]
-    return Frames(probs, [2.5])
-
-
-def _label_frames(L, Ns, seed):
-    """ragged frames of eight terms (d = 1 .. 8, tests/crf_cases.py: label_problem) with the first frame's weights"""
-    EIGHT = list(range(1, 9))
-    probs = [cc.label_problem(n, L, EIGHT, seed=seed + i) if n else _empty(L, EIGHT) for i, n in enumerate(Ns)]
-    w = [float(x) for _, x in probs[0]["kernels"]]
-    return Frames([dict(pb, kernels=[(f, x) for (f, _), x in zip(pb["kernels"], w)]) for pb in probs], w)
-
-
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind", ["slam", "generic", "K8_L9", "K8_L33", "K8_L64"])
@@ -185,18 +63,18 @@ def test_every_frame_has_the_bits_of_its_handle(wl, golden, kind):
     """every frame of a ragged batch (0-point frames among them) gets the bits of a handle of its own points; the K8_L* kinds:
     eight terms of d = 1 .. 8 at 9, 33 and 64 labels (the backward's lane groups of 4 and 16 lanes, its partials at K = 8)"""
     if kind == "slam":
-        fr = _slam_frames(golden, wl)
+        fr = bc.slam_frames(golden, wl)
     elif kind == "generic":
-        fr = _generic_frames(wl)
+        fr = bc.generic_frames(wl)
     else:
-        fr = _label_frames(int(kind[4:]), (300, 0, 1100, 77, 650), seed=400)
+        fr = bc.label_frames(int(kind[4:]), (300, 0, 1100, 77, 650), seed=400)
     assert fr.K == {"slam": 2, "generic": 1}.get(kind, 8)
     b = fr.batch()
     handles = {f: fr.handle(f) for f, n in enumerate(fr.N) if n}
     for T in (0, 1, 5, 10):
         for relax in (1.0, 0.7):
             G = fr.grad_prob(100 * T + int(relax * 10))
-            gu, gw = _batch_backward(b, T, relax, G, fr.K)
+            gu, gw = gs.batch_backward(b, T, relax, G, fr.K)
             _check_parity(fr, handles, gu, gw, T, relax, G)
             if T == 0:
                 assert np.all(gw == 0)
@@ -208,11 +86,11 @@ def test_every_frame_has_the_bits_of_its_handle(wl, golden, kind):
 @pytest.mark.gpu
 @pytest.mark.parametrize("relax", [1.0, 0.7])
 def test_batch_gradients_match_the_checker(po, wl, golden, relax):
-    fr = _slam_frames(golden, wl, Ns=(1000, 0, 2000))
+    fr = bc.slam_frames(golden, wl, Ns=(1000, 0, 2000))
     b = fr.batch()
     T = 5
     G = fr.grad_prob(7)
-    gu, gw = _batch_backward(b, T, relax, G, fr.K)
+    gu, gw = gs.batch_backward(b, T, relax, G, fr.K)
     for f in (0, 2):
         n = fr.N[f]
         pb = dict(fr.probs[f], kernels=[(ft, w) for (ft, _), w in zip(fr.probs[f]["kernels"], fr.w)])
@@ -222,14 +100,14 @@ def test_batch_gradients_match_the_checker(po, wl, golden, relax):
         eu = np.linalg.norm(gu[f, :n] - ref_u) / max(np.linalg.norm(ref_u), 1e-6 * np.linalg.norm(G[f, :n]))
         ew = np.linalg.norm(gw[f] - ref_w) / max(np.linalg.norm(ref_w), 1e-6 * np.linalg.norm(G[f, :n]))
         print("frame N=%d relax=%g: relative L2 error dL/dU %.3g dL/dw %.3g" % (n, relax, eu, ew))
-        assert eu <= GRAD_TOL and ew <= GRAD_TOL, (eu, ew)
+        assert eu <= gs.GRAD_TOL and ew <= gs.GRAD_TOL, (eu, ew)
     b.close()
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("how", ["engine1", "engine2", "pending_run"])
 def test_backward_leaves_what_inference_leaves(wl, golden, how):
-    fr = _slam_frames(golden, wl, Ns=(5, 1000, 0, 2000, 1500))
+    fr = bc.slam_frames(golden, wl, Ns=(5, 1000, 0, 2000, 1500))
     T, relax = 5, 0.7
     b = fr.batch()
     b.set_engine(1 if how == "engine1" else 2 if how == "engine2" else 0)
@@ -238,7 +116,7 @@ def test_backward_leaves_what_inference_leaves(wl, golden, how):
     if how == "pending_run":
         b.run(T, True, relax)                                   # one launch per frame, left pending: the backward settles it
     G = fr.grad_prob(3)
-    _batch_backward(b, T, relax, G, fr.K)
+    gs.batch_backward(b, T, relax, G, fr.K)
     assert _same_valid(b.probability(), q_ref, fr.N)
     if how == "engine2":
         assert b.engine() == 2
@@ -249,21 +127,21 @@ def test_backward_leaves_what_inference_leaves(wl, golden, how):
 
 @pytest.mark.gpu
 def test_backward_is_deterministic_and_survives_rebinding(wl, golden):
-    big = _slam_frames(golden, wl, Ns=(2002, 2002))
+    big = bc.slam_frames(golden, wl, Ns=(2002, 2002))
     b = big.batch()
     G = big.grad_prob(11)
-    a1 = _batch_backward(b, 5, 1.0, G, 2)
-    a2 = _batch_backward(b, 5, 1.0, G, 2)
+    a1 = gs.batch_backward(b, 5, 1.0, G, 2)
+    a2 = gs.batch_backward(b, 5, 1.0, G, 2)
     assert cc.same_bits(a1[0], a2[0]) and cc.same_bits(a1[1], a2[1])
     # the same batch rebound to fewer points per frame: stale rows of the larger frames stay in its area and must not be read
-    small = _slam_frames(golden, wl, Ns=(1001, 5))
-    small = Frames(small.probs, small.w, max_points=2002)
+    small = bc.slam_frames(golden, wl, Ns=(1001, 5))
+    small = bc.Frames(small.probs, small.w, max_points=2002)
     b.set_inputs_host(small.N, small.feats, unary=small.U)
     b.build()
     handles = {f: small.handle(f) for f in range(2)}
     for T, relax in ((5, 1.0), (10, 0.7), (1, 1.0)):
         G = small.grad_prob(T)
-        gu, gw = _batch_backward(b, T, relax, G, 2)
+        gu, gw = gs.batch_backward(b, T, relax, G, 2)
         _check_parity(small, handles, gu, gw, T, relax, G)
     for h in handles.values():
         h.close()
@@ -274,7 +152,7 @@ def test_backward_is_deterministic_and_survives_rebinding(wl, golden):
 @pytest.mark.parametrize("how", ["engine1", "engine2", "run"])
 def test_batch_set_pairwise_weight_equals_a_fresh_batch(wl, how):
     rng = np.random.default_rng(5)
-    fr = Frames([wl.slam_problem(int(n), seed=60 + i) for i, n in enumerate(rng.integers(513, 2049, 64))], [1.0, 2.0], max_points=2048)
+    fr = bc.Frames([wl.slam_problem(int(n), seed=60 + i) for i, n in enumerate(rng.integers(513, 2049, 64))], [1.0, 2.0], max_points=2048)
     new = [7.25, 21.5]
     b, fresh = fr.batch(), fr.batch(weights=new)
     for x in (b, fresh):
@@ -303,7 +181,7 @@ def test_batch_set_unary_device_equals_a_fresh_batch(wl):
     import torch
     # inputs from labels, then raw unaries
     probs = [wl.slam_problem(n, seed=80 + i) for i, n in enumerate((1500, 700, 2000))]
-    fr = Frames(probs, [wl.TUM3["w1"], wl.TUM3["w2"]])
+    fr = bc.Frames(probs, [wl.TUM3["w1"], wl.TUM3["w2"]])
     b = pkg.BatchCRF(3, fr.maxN, 2, fr.dims, fr.w)
     lab = np.full((3, fr.maxN), -1, np.int16)
     for f, pb in enumerate(probs):
@@ -312,12 +190,12 @@ def test_batch_set_unary_device_equals_a_fresh_batch(wl):
     b.build()
     b.inference(5, True)
     U1 = fr.U + np.random.default_rng(1).standard_normal(fr.U.shape).astype(np.float32)
-    d = _dev(U1)
+    d = dev(U1)
     torch.cuda.synchronize()
     b.set_unary_device(d.data_ptr())
     del d                                                        # copied: the caller's array may go
     torch.cuda.synchronize()
-    fresh = Frames(probs, fr.w)
+    fresh = bc.Frames(probs, fr.w)
     fresh.U = U1
     f2 = fresh.batch()
     for x in (b, f2):
@@ -332,24 +210,24 @@ def test_batch_set_unary_device_equals_a_fresh_batch(wl):
 @pytest.mark.gpu
 def test_locality_mode_frame_has_the_bits_of_its_handle(wl):
     import torch
-    fr = Frames([wl.slam_problem(9000, seed=90), wl.slam_problem(1200, seed=91)], [wl.TUM3["w1"], wl.TUM3["w2"]])
+    fr = bc.Frames([wl.slam_problem(9000, seed=90), wl.slam_problem(1200, seed=91)], [wl.TUM3["w1"], wl.TUM3["w2"]])
     b = fr.batch()
     b.inference(5, True)
     assert b.locality_mode()[0], "the 9000-point frame should be in locality mode"
     handles = {f: fr.handle(f) for f in range(2)}
     for T, relax in ((5, 1.0), (2, 0.7)):
         G = fr.grad_prob(T)
-        gu, gw = _batch_backward(b, T, relax, G, 2)
+        gu, gw = gs.batch_backward(b, T, relax, G, 2)
         _check_parity(fr, handles, gu, gw, T, relax, G)
     # set_unary_device on a batch whose lattices were built in locality mode
     U1 = fr.U * np.float32(0.5)
     b.build()
     b.inference(5, True)
-    d = _dev(U1)
+    d = dev(U1)
     torch.cuda.synchronize()
     b.set_unary_device(d.data_ptr())
     b.inference(5, True)
-    fresh = Frames(fr.probs, fr.w)
+    fresh = bc.Frames(fr.probs, fr.w)
     fresh.U = U1
     f2 = fresh.batch()
     f2.inference(5, True)
@@ -359,27 +237,20 @@ def test_locality_mode_frame_has_the_bits_of_its_handle(wl):
     b.close(), f2.close()
 
 
-def _hip_malloc(nbytes):
-    lib = C.CDLL("libamdhip64.so")
-    p = C.c_void_p()
-    assert lib.hipMalloc(C.byref(p), C.c_size_t(nbytes)) == 0
-    return lib, p
-
-
 @pytest.mark.gpu
 def test_batch_backward_argument_checks_leave_the_batch_usable(wl, golden):
     import torch
-    fr = _slam_frames(golden, wl, Ns=(1000, 5, 2000))
+    fr = bc.slam_frames(golden, wl, Ns=(1000, 5, 2000))
     b = fr.batch()
     G = fr.grad_prob(21)
-    ref = _batch_backward(b, 5, 1.0, G, 2)
+    ref = gs.batch_backward(b, 5, 1.0, G, 2)
     q_ref = b.probability()
     L = pkg.lib()
     shape = (3, fr.maxN, 2)
-    g, gu, gw = _dev(G), torch.zeros(shape, device="cuda"), torch.zeros((3, 2), device="cuda")
+    g, gu, gw = dev(G), torch.zeros(shape, device="cuda"), torch.zeros((3, 2), device="cuda")
     host = np.zeros(shape, np.float32)
-    hl, small = _hip_malloc(64)
-    _, small4 = _hip_malloc(4)
+    hl, small = hip_malloc(64)
+    _, small4 = hip_malloc(4)
     vp = C.c_void_p
     try:
         for args in ((5, 1.0, None, vp(gu.data_ptr()), None),
@@ -406,7 +277,7 @@ def test_batch_backward_argument_checks_leave_the_batch_usable(wl, golden):
         hl.hipFree(small4)
     torch.cuda.synchronize()
     assert _same_valid(b.probability(), q_ref, fr.N)
-    again = _batch_backward(b, 5, 1.0, G, 2)
+    again = gs.batch_backward(b, 5, 1.0, G, 2)
     assert cc.same_bits(again[0], ref[0]) and cc.same_bits(again[1], ref[1])
     handles = {f: fr.handle(f) for f in range(3)}
     _check_parity(fr, handles, again[0], again[1], 5, 1.0, G)
@@ -419,13 +290,13 @@ def test_batch_backward_argument_checks_leave_the_batch_usable(wl, golden):
 def test_mean_field_batch_matches_the_c_abi_and_streams(wl, golden):
     import torch
     ag = importlib.import_module("lc-crf-slam_amd.autograd")
-    fr = _slam_frames(golden, wl, Ns=(1200, 0, 2000, 7))
+    fr = bc.slam_frames(golden, wl, Ns=(1200, 0, 2000, 7))
     T, relax = 5, 0.7
     ref = fr.batch()
     ref.inference(T, False, relax)
     q_ref = ref.probability()
     G = np.nan_to_num(fr.grad_prob(31), nan=0.0)
-    ref_u, ref_w = _batch_backward(ref, T, relax, G, 2)
+    ref_u, ref_w = gs.batch_backward(ref, T, relax, G, 2)
     ref.close()
     b = fr.batch()
 
@@ -454,7 +325,7 @@ def test_fitting_the_weights_over_many_frames_lowers_the_nll(wl):
     ag = importlib.import_module("lc-crf-slam_amd.autograd")
     rng = np.random.default_rng(17)
     probs = [wl.slam_problem(int(n), seed=200 + i) for i, n in enumerate(rng.integers(300, 1200, 64))]
-    fr = Frames(probs, [1.0, 3.0])
+    fr = bc.Frames(probs, [1.0, 3.0])
     layer = ag.BatchMeanFieldCRF(fr.N, fr.feats, fr.w, n_iterations=5)
     U = torch.from_numpy(fr.U).cuda()
     truth = np.zeros((64, fr.maxN), np.int64)

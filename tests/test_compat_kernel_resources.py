@@ -1,31 +1,11 @@
 """Compile-time figures of the label-compatibility kernels (include/lccrf.h section 1e), in the manner of
 tests/test_kernel_resources.py: no scratch memory, registers that allow eight wavefronts per SIMD in the forward slice, and the LDS
 footprint the kernels were designed to (several workgroups per CU)."""
-import os
-import re
 import shutil
-import subprocess
 
 import pytest
 
-from test_kernel_resources import HIPCC, ROOT, resource_usage
-
-
-def lds_bytes(src):
-    """{kernel name: LDS bytes per workgroup} (resource_usage does not read that remark)"""
-    cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "--cuda-device-only",
-           "-I" + os.path.join(ROOT, "lc-crf-slam_amd", "csrc"), "-I" + os.path.join(ROOT, "include"),
-           "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "lc-crf-slam_amd", "csrc", src), "-o", os.devnull]
-    err = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
-    out, cur = {}, None
-    for line in err.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-        m = re.search(r"LDS Size \[bytes/block\]: (\d+)", line)
-        if m and cur is not None:
-            out[cur] = int(m.group(1))
-    return out
+from kernel_resources import HIPCC, lds_bytes, resource_usage
 
 
 def _one(use, key):

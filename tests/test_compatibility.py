@@ -6,27 +6,19 @@ matrix give the fast engines' bits); lccrf_inference_backward_compat against the
 tests/test_meanfield_backward.py, its determinism and state contract; the torch layer."""
 import ctypes as C
 import importlib
-import os
-import re
 
 import numpy as np
 import pytest
 
 import compat_checker as ck
 import crf_cases as cc
+import grad_support as gs
 import meanfield_f64 as mf
-from test_meanfield_backward import GRAD_TOL, _case, _checker, _dev, _gpu_handle, _rel, _weights
+from abi_support import assert_declared_exported_bound, dev, lib  # noqa: F401
 
 pkg = importlib.import_module("lc-crf-slam_amd")
 NEW_SYMBOLS = ("lccrf_set_pairwise_compatibility", "lccrf_get_pairwise_compatibility", "lccrf_inference_backward_compat")
 E_INVALID, E_STATE = -1, -5
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(pkg.LIB_PATH):
-        pkg.build_library()
-    return pkg.lib()
 
 
 def _dense(K, L, seed=77):
@@ -60,11 +52,7 @@ def _unary(po, pb):
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------------
 def test_compat_symbols_are_declared_exported_and_bound(lib):
-    src = re.sub(r"/\*.*?\*/", "", open(pkg.HEADER_PATH).read(), flags=re.S)
-    for n in NEW_SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % n, src), n
-        assert hasattr(lib, n), n
-        assert getattr(lib, n).argtypes is not None, n
+    assert_declared_exported_bound(lib, NEW_SYMBOLS)
     assert lib.lccrf_abi_version() == 3
     for m in ("set_pairwise_compatibility", "get_pairwise_compatibility", "inference_backward_compat_device"):
         assert hasattr(pkg.DenseCRFHIP, m), m
@@ -90,8 +78,8 @@ def test_restatement_with_identities_is_the_oracle(po, wl, N, L, dims, relax):
 def test_f64_checker_with_identities_is_the_potts_checker(po, wl):
     import torch
     pb = wl.generic_problem(200, [2, 3], 4, seed=5)
-    o, lats, U = _checker(po, pb)
-    u, w = torch.as_tensor(U), torch.as_tensor(_weights(pb))
+    o, lats, U = gs.checker(po, pb)
+    u, w = torch.as_tensor(U), torch.as_tensor(gs.weights(pb))
     mu = torch.eye(4, dtype=torch.float64).repeat(2, 1, 1)
     for relax in (1.0, 0.7):
         a, b = ck.forward_f64(u, w, mu, lats, 5, relax), mf.forward(u, w, lats, 5, relax)
@@ -101,8 +89,8 @@ def test_f64_checker_with_identities_is_the_potts_checker(po, wl):
 def test_f64_checker_gradcheck_in_the_matrices(po, wl):
     import torch
     pb = wl.generic_problem(40, [2, 3], 3, seed=4)
-    o, lats, U = _checker(po, pb)
-    u, w = torch.as_tensor(U), torch.as_tensor(_weights(pb))
+    o, lats, U = gs.checker(po, pb)
+    u, w = torch.as_tensor(U), torch.as_tensor(gs.weights(pb))
     mu = torch.as_tensor(np.stack(_dense(2, 3)).astype(np.float64)).requires_grad_(True)
     for relax in (1.0, 0.7):
         assert torch.autograd.gradcheck(lambda m: ck.forward_f64(u, w, m, lats, 3, relax), (mu,), eps=1e-6, atol=1e-7)
@@ -115,7 +103,7 @@ FORWARD_CASES = ["generic:d3_L21", "generic:d1_L3", "generic:multi", "slam:N1001
 def _fcase(name, golden, po, wl):
     if name == "locality9000":                                   # >= 8192 points: lccrf_inference runs in locality mode
         return wl.generic_problem(9000, [2, 3], 3, seed=31), None
-    return _case(name, golden, po, wl)
+    return cc.case(name, golden, po, wl)
 
 
 def _set_all(h, mats):
@@ -131,7 +119,7 @@ def test_inference_is_the_restatement(po, wl, golden, name, kind):
     K, L = len(pb["kernels"]), pb["L"]
     mats = _dense(K, L) if kind == "dense" else _potts_penalty(K, L)
     U = _unary(po, pb)
-    h, keep = _gpu_handle(pb, image)
+    h, keep = gs.gpu_handle(pb, image)
     _set_all(h, mats)
     for T in (0, 1, 5):
         for relax in (1.0, 0.7):
@@ -146,11 +134,11 @@ def test_inference_is_the_restatement(po, wl, golden, name, kind):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["generic:multi", "slam:N1001", "image64x48"])
 def test_one_term_with_a_matrix_and_one_without(po, wl, golden, name):
-    pb, image = _case(name, golden, po, wl)
+    pb, image = cc.case(name, golden, po, wl)
     K, L = len(pb["kernels"]), pb["L"]
     mats = [m if k % 2 == 0 else None for k, m in enumerate(_dense(K, L))]
     U = _unary(po, pb)
-    h, keep = _gpu_handle(pb, image)
+    h, keep = gs.gpu_handle(pb, image)
     _set_all(h, mats)
     for T, relax in ((1, 1.0), (5, 0.7)):
         ref = ck.restate_f32(U, _feats(pb), _w32(pb), mats, T, relax)
@@ -162,7 +150,7 @@ def test_one_term_with_a_matrix_and_one_without(po, wl, golden, name):
 def _identity_problem(name, golden, po, wl):
     if name == "L64":
         return cc.label_problem(900, 64, [2, 3], seed=6), None
-    return _case(name, golden, po, wl)
+    return cc.case(name, golden, po, wl)
 
 
 @pytest.mark.gpu
@@ -170,8 +158,8 @@ def _identity_problem(name, golden, po, wl):
 def test_identity_matrices_and_a_cleared_matrix_give_the_fast_engines_bits(po, wl, golden, name):
     pb, image = _identity_problem(name, golden, po, wl)
     K, L = len(pb["kernels"]), pb["L"]
-    fresh, keep = _gpu_handle(pb, image)
-    h, keep2 = _gpu_handle(pb, image)
+    fresh, keep = gs.gpu_handle(pb, image)
+    h, keep2 = gs.gpu_handle(pb, image)
     _set_all(h, _eyes(K, L))
     for T, relax in ((5, 1.0), (5, 0.7), (0, 1.0)):
         fresh.inference(T, True, relax)
@@ -194,10 +182,10 @@ def test_identity_matrices_and_a_cleared_matrix_give_the_fast_engines_bits(po, w
 @pytest.mark.parametrize("name", ["generic:d3_L21", "slam:N1001", "generic:multi"])
 def test_steps_equal_inference_and_apply_is_one_term(po, wl, golden, name):
     import torch
-    pb, image = _case(name, golden, po, wl)
+    pb, image = cc.case(name, golden, po, wl)
     K, L, N = len(pb["kernels"]), pb["L"], pb["N"]
     mats = _dense(K, L)
-    h, keep = _gpu_handle(pb, image)
+    h, keep = gs.gpu_handle(pb, image)
     _set_all(h, mats)
     for relax in (1.0, 0.7):
         h.inference(4, False, relax)
@@ -214,7 +202,7 @@ def test_steps_equal_inference_and_apply_is_one_term(po, wl, golden, name):
     for k in range(K):
         ref = ck.term_f32(out, _feats(pb)[k], _w32(pb)[k], nrm[k], mats[k], x)
         assert cc.same_bits(h.apply(k, out, x), ref), k
-        d_out, d_x = _dev(out), _dev(x)
+        d_out, d_x = dev(out), dev(x)
         torch.cuda.synchronize()
         h.pairwise_apply_device(k, d_out.data_ptr(), d_x.data_ptr())
         h.synchronize()
@@ -282,7 +270,7 @@ def test_feature_gradients_are_refused_while_a_matrix_is_set(po, wl, lib):
 # ---- GPU: gradients ---------------------------------------------------------------------------------------------------------
 def _backward_compat(h, T, relax, G, K, L, with_u=True, with_w=True):
     import torch
-    g = _dev(G.astype(np.float32))
+    g = dev(G.astype(np.float32))
     gu = torch.full(G.shape, float("nan"), device="cuda")
     gw = torch.full((max(K, 1),), float("nan"), device="cuda")
     gm = torch.full((max(K, 1), L, L), float("nan"), device="cuda")
@@ -294,7 +282,7 @@ def _backward_compat(h, T, relax, G, K, L, with_u=True, with_w=True):
 
 
 def assert_matches_compat_checker(got, U, w, mats, lats, T, relax, G, name=""):
-    """The bar of tests/test_meanfield_backward.py (assert_matches_checker), applied to dL/dmu as to dL/dU and dL/dw: relative L2
+    """The bar of tests/grad_support.py (assert_matches_checker), applied to dL/dmu as to dL/dU and dL/dw: relative L2
     error against the float64 checker <= max(1e-4, 10 x that of the float32 checker); gradients below 1e-6 |dL/dQ| (x max(|w|, 1)
     for dL/dw and dL/dmu) are compared in absolute terms against that floor."""
     import torch
@@ -304,8 +292,8 @@ def assert_matches_compat_checker(got, U, w, mats, lats, T, relax, G, name=""):
     fl_u = 1e-6 * np.linalg.norm(G)
     fl_w = fl_u * max(np.linalg.norm(w), 1.0)
     floors = (fl_u, fl_w, fl_w)
-    errs = [_rel(a, b, fl) for a, b, fl in zip(got, ref, floors)]
-    bars = [max(GRAD_TOL, 10 * _rel(a, b, fl)) for a, b, fl in zip(f32, ref, floors)]
+    errs = [gs.rel(a, b, fl) for a, b, fl in zip(got, ref, floors)]
+    bars = [max(gs.GRAD_TOL, 10 * gs.rel(a, b, fl)) for a, b, fl in zip(f32, ref, floors)]
     print("relative L2 error %s T=%d relax=%g: dL/dU %.3g dL/dw %.3g dL/dmu %.3g (bars %.3g %.3g %.3g)"
           % ((name, T, relax) + tuple(errs) + tuple(bars)))
     assert all(e <= b for e, b in zip(errs, bars)), (errs, bars)
@@ -321,20 +309,20 @@ GRAD_CASES = ["generic:d1_L3", "generic:d3_L21", "generic:multi", "slam:N1001", 
 @pytest.mark.parametrize("relax", [1.0, 0.7])
 def test_compat_gradients_match_the_checker(po, wl, golden, name, T, relax):
     """Measured on the MI355X: notes/compatibility.md lists the largest error per case."""
-    pb, image = _case(name, golden, po, wl)
+    pb, image = cc.case(name, golden, po, wl)
     K, L = len(pb["kernels"]), pb["L"]
     mats = _dense(K, L)
-    o, lats, U = _checker(po, pb)
+    o, lats, U = gs.checker(po, pb)
     G = np.random.default_rng(1234).standard_normal((pb["N"], L))
-    h, keep = _gpu_handle(pb, image)
+    h, keep = gs.gpu_handle(pb, image)
     _set_all(h, mats)
     got = _backward_compat(h, T, relax, G, K, L)
-    assert_matches_compat_checker(got, U, _weights(pb), mats, lats, T, relax, G, name)
+    assert_matches_compat_checker(got, U, gs.weights(pb), mats, lats, T, relax, G, name)
     if T == 0:
         assert np.all(got[2] == 0) and np.all(got[1] == 0)
     # lccrf_inference_backward on the same handle: the same dL/dU and dL/dw
     import torch
-    g = _dev(G.astype(np.float32))
+    g = dev(G.astype(np.float32))
     gu = torch.full(G.shape, float("nan"), device="cuda")
     gw = torch.full((K,), float("nan"), device="cuda")
     torch.cuda.synchronize()
@@ -347,20 +335,20 @@ def test_compat_gradients_match_the_checker(po, wl, golden, name, T, relax):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["generic:d3_L21", "slam:N1001"])
 def test_gradient_at_a_potts_term_is_that_at_the_identity(po, wl, golden, name):
-    pb, image = _case(name, golden, po, wl)
+    pb, image = cc.case(name, golden, po, wl)
     K, L = len(pb["kernels"]), pb["L"]
-    o, lats, U = _checker(po, pb)
+    o, lats, U = gs.checker(po, pb)
     G = np.random.default_rng(4).standard_normal((pb["N"], L))
     T, relax = 5, 0.7
-    h, keep = _gpu_handle(pb, image)
+    h, keep = gs.gpu_handle(pb, image)
     a = _backward_compat(h, T, relax, G, K, L)
-    _, bars, floors = assert_matches_compat_checker(a, U, _weights(pb), _eyes(K, L), lats, T, relax, G, name + " (no matrix)")
-    h2, keep2 = _gpu_handle(pb, image)
+    _, bars, floors = assert_matches_compat_checker(a, U, gs.weights(pb), _eyes(K, L), lats, T, relax, G, name + " (no matrix)")
+    h2, keep2 = gs.gpu_handle(pb, image)
     _set_all(h2, _eyes(K, L))
     b = _backward_compat(h2, T, relax, G, K, L)
-    assert_matches_compat_checker(b, U, _weights(pb), _eyes(K, L), lats, T, relax, G, name + " (identity)")
+    assert_matches_compat_checker(b, U, gs.weights(pb), _eyes(K, L), lats, T, relax, G, name + " (identity)")
     assert cc.same_bits(a[0], b[0]) and cc.same_bits(a[1], b[1])
-    between = _rel(a[2], b[2], floors[2])                       # ... and one against the other, to the same bar
+    between = gs.rel(a[2], b[2], floors[2])                       # ... and one against the other, to the same bar
     print("dL/dmu without a matrix against an explicit identity, %s: relative L2 difference %.3g (bar %.3g)" % (name, between, bars[2]))
     assert between <= bars[2]
     h.close(), h2.close()
@@ -369,12 +357,12 @@ def test_gradient_at_a_potts_term_is_that_at_the_identity(po, wl, golden, name):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["generic:d3_L21", "slam:N1001", "image64x48"])
 def test_compat_backward_is_deterministic_and_leaves_the_inference_state(po, wl, golden, name):
-    pb, image = _case(name, golden, po, wl)
+    pb, image = cc.case(name, golden, po, wl)
     K, L = len(pb["kernels"]), pb["L"]
     mats = _dense(K, L)
     G = np.random.default_rng(9).standard_normal((pb["N"], L))
     T, relax = 5, 0.7
-    h, keep = _gpu_handle(pb, image)
+    h, keep = gs.gpu_handle(pb, image)
     _set_all(h, mats)
     h.inference(T, False, relax)
     q = h.probability()
@@ -422,7 +410,7 @@ def test_three_sgd_steps_on_the_image_crop_lower_the_cross_entropy(po, wl, golde
     falls 1.48302 -> 1.48284 -> 1.48271 -> 1.48259, thousands of float32 ulps per step (a step of 5 overshoots)."""
     import torch
     ag = importlib.import_module("lc-crf-slam_amd.autograd")
-    pb, _ = _case("image64x48", golden, po, wl)
+    pb, _ = cc.case("image64x48", golden, po, wl)
     K, L = 2, pb["L"]
     U = torch.from_numpy(_unary(po, pb)).cuda()
     weights = [float(w) / 10 for w in _w32(pb)]

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import crf_cases as cc
+from abi_support import assert_declared_exported_bound, dev, lib  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pkg = importlib.import_module("lc-crf-slam_amd")
@@ -22,13 +23,6 @@ NEW_SYMBOLS = ("lccrf_get_stream", "lccrf_synchronize", "lccrf_set_unary_device"
                "lccrf_exp_and_normalize_device", "lccrf_step_init_device", "lccrf_map_of_device")
 
 
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(pkg.LIB_PATH):
-        pkg.build_library()
-    return pkg.lib()
-
-
 def _has_gpu():
     import torch
     return torch.cuda.is_available()
@@ -36,11 +30,7 @@ def _has_gpu():
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------------
 def test_device_entry_points_are_declared_exported_and_bound(lib):
-    src = re.sub(r"/\*.*?\*/", "", open(pkg.HEADER_PATH).read(), flags=re.S)
-    for n in NEW_SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % n, src), n
-        assert hasattr(lib, n), n
-        assert getattr(lib, n).argtypes is not None, n
+    src = assert_declared_exported_bound(lib, NEW_SYMBOLS)
     for name, v in (("LCCRF_IMAGE_NONE", pkg.IMAGE_NONE), ("LCCRF_IMAGE_U8", pkg.IMAGE_U8), ("LCCRF_IMAGE_F32", pkg.IMAGE_F32)):
         assert re.search(r"#define %s\s+%d\b" % (name, v), src), name
     assert lib.lccrf_abi_version() == 3
@@ -123,11 +113,6 @@ def test_gpu_header_needs_no_hip_header(tmp_path):
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def _host_view(ptr, shape, typestr):
     import torch
 
@@ -156,7 +141,7 @@ def test_image_example_through_device_inputs_gives_the_known_answer(golden, vari
     import torch
     z, img, fmt = _image_inputs(golden, variant)
     H, W, _ = z["im"].shape
-    d_lab, d_img = _dev(z["label"].astype(np.int16)), _dev(img)
+    d_lab, d_img = dev(z["label"].astype(np.int16)), dev(img)
     torch.cuda.synchronize()
     h = pkg.DenseCRFHIP(W * H, 21)
     h.set_unary_from_label_device(d_lab.data_ptr(), 0.5)
@@ -202,7 +187,7 @@ def test_image_features_formed_on_the_device_match_host_features(po, golden, var
         f_app[:, 1] = (i // W).astype(np.float32) / np.float32(60.0)
         f_app[:, 2:] = img.reshape(N, 3) / np.float32(20.0)
     f_pos = po.oracle_image_features(W, H, 3.0)
-    d_img = _dev(img)
+    d_img = dev(img)
     torch.cuda.synchronize()
     hd, hh = pkg.DenseCRFHIP(N, 21), pkg.DenseCRFHIP(N, 21)
     hd.add_image_kernel(W, H, 3.0, 3.0)
@@ -227,8 +212,8 @@ def test_slam_sizes_through_device_inputs_match_the_oracle(po, wl, N, mode):
     pb = wl.slam_problem(N, seed=21)
     o = cc.setup(po.OracleCRF, pb)
     (fa, w1), (fs, w2) = pb["kernels"]
-    d_lab, d_fa, d_fs = _dev(pb["label"].astype(np.int16)), _dev(fa.astype(np.float32)), _dev(fs.astype(np.float32))
-    d_u = _dev(o.unary().astype(np.float32))
+    d_lab, d_fa, d_fs = dev(pb["label"].astype(np.int16)), dev(fa.astype(np.float32)), dev(fs.astype(np.float32))
+    d_u = dev(o.unary().astype(np.float32))
     torch.cuda.synchronize()
     h = pkg.DenseCRFHIP(N, 2)
     if mode == "unary":
@@ -308,7 +293,7 @@ def test_a_cached_handle_starts_in_host_mode(po, wl):
     import torch
     N = 1500
     pb = wl.slam_problem(N, seed=9)
-    d_lab = _dev(pb["label"].astype(np.int16))
+    d_lab = dev(pb["label"].astype(np.int16))
     torch.cuda.synchronize()
     pkg.lib().lccrf_trim_cache()                              # (the next create of this size takes the handle parked below)
     h = pkg.DenseCRFHIP(N, 2)

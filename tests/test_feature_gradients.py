@@ -14,32 +14,22 @@ import shutil
 import numpy as np
 import pytest
 
+import batch_cases as bc
 import crf_cases as cc
 import feature_cases as fc
+import grad_support as gs
+import kernel_resources as kr
 import meanfield_f64_features as mff
-import test_batch_backward as tbb
-import test_kernel_resources as tkr
-import test_meanfield_backward as tb
+from abi_support import assert_declared_exported_bound, dev, hip_malloc, lib  # noqa: F401
 
 pkg = importlib.import_module("lc-crf-slam_amd")
 NEW_SYMBOLS = ("lccrf_inference_backward_features", "lccrf_batch_inference_backward_features")
-GRAD_TOL = tb.GRAD_TOL
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(pkg.LIB_PATH):
-        pkg.build_library()
-    return pkg.lib()
+GRAD_TOL = gs.GRAD_TOL
 
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------------
 def test_feature_gradient_symbols_are_declared_exported_and_bound(lib):
-    src = re.sub(r"/\*.*?\*/", "", open(pkg.HEADER_PATH).read(), flags=re.S)
-    for n in NEW_SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % n, src), n
-        assert hasattr(lib, n), n
-        assert getattr(lib, n).argtypes is not None, n
+    assert_declared_exported_bound(lib, NEW_SYMBOLS)
     assert lib.lccrf_abi_version() == 3                         # sections 1d / 2d came without a version step
     assert hasattr(pkg.DenseCRFHIP, "inference_backward_features_device")
     assert hasattr(pkg.BatchCRF, "inference_backward_features_device")
@@ -52,12 +42,12 @@ def test_feature_gradient_entry_points_reject_a_null_handle(lib):
     assert lib.lccrf_batch_inference_backward_features(None, 1, 1.0, None, None, None, None, None) == -1
 
 
-@pytest.mark.skipif(shutil.which(tkr.HIPCC) is None, reason="hipcc not installed")
+@pytest.mark.skipif(shutil.which(kr.HIPCC) is None, reason="hipcc not installed")
 def test_backward_kernels_use_no_scratch():
     """The sweep's kernels are small; scratch there is an accident (a register array indexed at run time).  Every kernel of
     meanfield_backward.hip -- the corner dots (five lane groups), the corner-to-feature kernel (d = 1 .. 8), the norm adjoint
     and both forms of the softmax backward -- compiles without it."""
-    use = tkr.resource_usage("meanfield_backward.hip")
+    use = kr.resource_usage("meanfield_backward.hip")
     names = {k: v for k, v in use.items() if re.search(r"k_(corner_dot|corner_to_feature|norm_adjoint|softmax_bwd|bwd_)", k)}
     assert sum("k_corner_dot" in k for k in names) == 5
     assert sum("k_corner_to_feature" in k for k in names) == 8
@@ -67,11 +57,6 @@ def test_backward_kernels_use_no_scratch():
 
 
 # ---- helpers ----------------------------------------------------------------------------------------------------------------
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def _dims(pb, image):
     return [2, 5] if image is not None else [int(f.shape[1]) for f, _ in pb["kernels"]]
 
@@ -80,7 +65,7 @@ def _backward_features(h, dims, T, relax, G, skip=(), unary=True, weights=True):
     """(dL/dU, dL/dw, [dL/df_k or None]) from lccrf_inference_backward_features; every output pre-filled with NaN"""
     import torch
     K, N = len(dims), G.shape[0]
-    g = _dev(G.astype(np.float32))
+    g = dev(G.astype(np.float32))
     gu = torch.full(G.shape, float("nan"), device="cuda")
     gw = torch.full((max(K, 1),), float("nan"), device="cuda")
     gf = [None if k in skip else torch.full((N, d), float("nan"), device="cuda") for k, d in enumerate(dims)]
@@ -103,9 +88,9 @@ def assert_features_match_checker(gf, U, w, lats, T, relax, G, name=""):
     for k, (a, r, s) in enumerate(zip(gf, ref_f, f32_f)):
         if a is None:
             continue
-        e, bar = tb._rel(a, r, floor), max(GRAD_TOL, 10 * tb._rel(s, r, floor))
+        e, bar = gs.rel(a, r, floor), max(GRAD_TOL, 10 * gs.rel(s, r, floor))
         print("relative L2 error %s T=%d relax=%g term %d: dL/df %.3g (bar %.3g, float32 checker %.3g, |dL/df| %.3g)"
-              % (name, T, relax, k, e, bar, tb._rel(s, r, floor), np.linalg.norm(r)))
+              % (name, T, relax, k, e, bar, gs.rel(s, r, floor), np.linalg.norm(r)))
         if not e <= bar:
             bad.append("term %d: %.3g (bar %.3g)" % (k, e, bar))
         if T == 0:
@@ -135,12 +120,12 @@ def test_feature_gradients_match_the_checker(po, wl, golden, name, T, relax):
     pb, image = fc.case(name, golden, po, wl)
     o, lats, U = _checker(po, pb)
     G = np.random.default_rng(1234).standard_normal((pb["N"], pb["L"]))
-    h, keep = tb._gpu_handle(pb, image)
+    h, keep = gs.gpu_handle(pb, image)
     gu, gw, gf = _backward_features(h, _dims(pb, image), T, relax, G)
     h.close()
     assert all(np.isfinite(a).all() for a in gf)
-    assert_features_match_checker(gf, U, tb._weights(pb), lats, T, relax, G, name)
-    tb.assert_matches_checker(gu, gw, U, tb._weights(pb), lats, T, relax, G, name)
+    assert_features_match_checker(gf, U, gs.weights(pb), lats, T, relax, G, name)
+    gs.assert_matches_checker(gu, gw, U, gs.weights(pb), lats, T, relax, G, name)
 
 
 @pytest.mark.gpu
@@ -153,9 +138,9 @@ def test_bits_of_section_1c_determinism_null_entries_and_state(po, wl, golden, n
     dims = _dims(pb, image)
     K = len(dims)
     G = np.random.default_rng(9).standard_normal((pb["N"], pb["L"]))
-    h, keep = tb._gpu_handle(pb, image)
+    h, keep = gs.gpu_handle(pb, image)
     T, relax = 5, 0.7
-    ru, rw = tb._backward(h, T, relax, G, K)
+    ru, rw = gs.backward(h, T, relax, G, K)
     a = _backward_features(h, dims, T, relax, G)
     q_after = h.probability()
     b = _backward_features(h, dims, T, relax, G)
@@ -175,13 +160,13 @@ def test_bits_of_section_1c_determinism_null_entries_and_state(po, wl, golden, n
     assert np.isnan(c[0]).all() and np.isnan(c[1]).all()        # (untouched)
     assert all(cc.same_bits(x, y) for x, y in zip(a[2], c[2]))
     import torch
-    g, gu = _dev(G.astype(np.float32)), torch.full(G.shape, float("nan"), device="cuda")
+    g, gu = dev(G.astype(np.float32)), torch.full(G.shape, float("nan"), device="cuda")
     torch.cuda.synchronize()
     h.inference_backward_features_device(T, relax, g.data_ptr(), gu.data_ptr(), None, None)
     h.synchronize()
     assert cc.same_bits(gu.cpu().numpy(), ru)
     # a fresh handle whose first call is this one gives the same bits
-    h2, keep2 = tb._gpu_handle(pb, image)
+    h2, keep2 = gs.gpu_handle(pb, image)
     d = _backward_features(h2, dims, T, relax, G)
     assert cc.same_bits(d[0], ru) and all(cc.same_bits(x, y) for x, y in zip(a[2], d[2]))
     h.close(), h2.close()
@@ -192,7 +177,7 @@ def test_t0_is_exactly_zero_and_k0_is_legal(wl):
     pb = wl.slam_problem(700, seed=2)
     G = np.random.default_rng(5).standard_normal((pb["N"], 2))
     h = cc.setup(pkg.DenseCRFHIP, pb)
-    ru, rw = tb._backward(h, 0, 1.0, G, 2)
+    ru, rw = gs.backward(h, 0, 1.0, G, 2)
     gu, gw, gf = _backward_features(h, [2, 2], 0, 1.0, G)
     assert cc.same_bits(gu, ru) and np.all(gw == 0) and all(np.all(a == 0) for a in gf)
     h.close()
@@ -200,7 +185,7 @@ def test_t0_is_exactly_zero_and_k0_is_legal(wl):
     h0 = pkg.DenseCRFHIP(300, 5)
     h0.set_unary(gen["unary"])
     G5 = np.random.default_rng(6).standard_normal((300, 5))
-    ru, _ = tb._backward(h0, 3, 0.7, G5, 0)
+    ru, _ = gs.backward(h0, 3, 0.7, G5, 0)
     gu, _, gf = _backward_features(h0, [], 3, 0.7, G5)
     assert cc.same_bits(gu, ru) and gf == []
     h0.close()
@@ -209,7 +194,7 @@ def test_t0_is_exactly_zero_and_k0_is_legal(wl):
 def _batch_backward_features(b, fr, T, relax, G, skip=()):
     import torch
     F = len(fr.probs)
-    g = _dev(G)
+    g = dev(G)
     gu = torch.full(G.shape, float("nan"), device="cuda")
     gw = torch.full((F, max(fr.K, 1)), float("nan"), device="cuda")
     gf = [None if k in skip else torch.full((F, fr.maxN, d), float("nan"), device="cuda") for k, d in enumerate(fr.dims)]
@@ -228,17 +213,17 @@ def test_every_frame_of_a_batch_has_the_bits_of_its_handle(wl, golden, kind):
     holding that frame; rows beyond a frame's points and frames of 0 points come back 0 from arrays pre-filled with NaN; the
     batch's dL/dU and dL/dw are lccrf_batch_inference_backward's bits"""
     if kind == "slam":
-        fr = tbb._slam_frames(golden, wl, Ns=(0, 1, 5, 1000, 1001, 2002, 3000))
+        fr = bc.slam_frames(golden, wl, Ns=(0, 1, 5, 1000, 1001, 2002, 3000))
     elif kind == "generic":
-        fr = tbb._generic_frames(wl, Ns=(300, 0, 1, 1500, 77, 2500))
+        fr = bc.generic_frames(wl, Ns=(300, 0, 1, 1500, 77, 2500))
     else:
-        fr = tbb._label_frames(int(kind[4:]), (300, 0, 1100, 1, 650), seed=400)
+        fr = bc.label_frames(int(kind[4:]), (300, 0, 1100, 1, 650), seed=400)
     assert fr.maxN == max(fr.N)
     b = fr.batch()
     handles = {f: fr.handle(f) for f, n in enumerate(fr.N) if n}
     for T, relax in ((0, 1.0), (1, 1.0), (5, 0.7), (10, 1.0)):
         G = fr.grad_prob(100 * T + int(relax * 10))
-        ru, rw = tbb._batch_backward(b, T, relax, G, fr.K)
+        ru, rw = gs.batch_backward(b, T, relax, G, fr.K)
         gu, gw, gf = _batch_backward_features(b, fr, T, relax, G)
         assert cc.same_bits(gu, ru) and cc.same_bits(gw, rw)
         for f, n in enumerate(fr.N):
@@ -270,7 +255,7 @@ def test_locality_mode_frame_gives_the_gradient_in_the_callers_order(po, golden)
     h = cc.setup(pkg.DenseCRFHIP, pb)
     h.inference(5, True)                                         # locality mode
     gu, gw, gf = _backward_features(h, dims, 5, 1.0, G)
-    assert_features_match_checker(gf, U, tb._weights(pb), lats, 5, 1.0, G, "large:c5 after inference()")
+    assert_features_match_checker(gf, U, gs.weights(pb), lats, 5, 1.0, G, "large:c5 after inference()")
     h2 = cc.setup(pkg.DenseCRFHIP, pb)
     d = _backward_features(h2, dims, 5, 1.0, G)
     assert cc.same_bits(gu, d[0]) and all(cc.same_bits(x, y) for x, y in zip(gf, d[2]))
@@ -287,7 +272,7 @@ def test_argument_checks_leave_the_handle_usable(po, wl):
     gu = torch.zeros((2000, 2), device="cuda")
     gf = [torch.zeros((2000, 2), device="cuda") for _ in range(2)]
     host = np.zeros((2000, 2), np.float32)
-    hl, small = tb._hip_malloc(64)
+    hl, small = hip_malloc(64)
     vp = C.c_void_p
 
     def arr(*ps):
@@ -318,9 +303,9 @@ def test_argument_checks_leave_the_handle_usable(po, wl):
     assert np.all(gu.cpu().numpy() == 0) and all(np.all(t.cpu().numpy() == 0) for t in gf)      # dL/dQ = 0
     h.close()
     # the batch entry point: the same checks
-    fr = tbb._slam_frames({"slam": np.load(os.path.join(os.path.dirname(__file__), "golden", "slam.npz"))}, wl, Ns=(5, 1000))
+    fr = bc.slam_frames({"slam": np.load(os.path.join(os.path.dirname(__file__), "golden", "slam.npz"))}, wl, Ns=(5, 1000))
     b = fr.batch()
-    G = _dev(np.zeros((2, fr.maxN, 2), np.float32))
+    G = dev(np.zeros((2, fr.maxN, 2), np.float32))
     gub = torch.zeros((2, fr.maxN, 2), device="cuda")
     gfb = [torch.zeros((2, fr.maxN, 2), device="cuda") for _ in range(2)]
     goodb = arr(vp(gfb[0].data_ptr()), vp(gfb[1].data_ptr()))
@@ -347,7 +332,7 @@ def test_torch_mean_field_features_matches_the_checker(po, wl, golden, name):
     ag = importlib.import_module("lc-crf-slam_amd.autograd")
     pb, _ = fc.case(name, golden, po, wl)
     o, lats, U = _checker(po, pb)
-    w = tb._weights(pb)
+    w = gs.weights(pb)
     G = np.random.default_rng(21).standard_normal((pb["N"], pb["L"]))
     u = torch.from_numpy(U.astype(np.float32)).cuda().requires_grad_(True)
     wt = torch.tensor(w, dtype=torch.float32, requires_grad=True)
@@ -361,7 +346,7 @@ def test_torch_mean_field_features_matches_the_checker(po, wl, golden, name):
     q.backward(torch.from_numpy(G.astype(np.float32)).cuda())
     torch.cuda.synchronize()
     assert_features_match_checker([f.grad.cpu().numpy() for f in fs], U, w, lats, T, relax, G, name)
-    tb.assert_matches_checker(u.grad.cpu().numpy(), wt.grad.numpy(), U, w, lats, T, relax, G, name)
+    gs.assert_matches_checker(u.grad.cpu().numpy(), wt.grad.numpy(), U, w, lats, T, relax, G, name)
 
 
 @pytest.mark.gpu
@@ -394,7 +379,7 @@ def test_learned_kernel_crf_chain_rule_and_fit(po, wl):
     def chain(gf):
         return [-(gf[0] * feats[0].astype(np.float64)).sum(0), np.array([-(gf[1] * feats[1].astype(np.float64)).sum()])]
     for k, (got, r, s) in enumerate(zip([x.grad.cpu().numpy() for x in layer.log_sd], chain(ref_f), chain(f32_f))):
-        e, bar = tb._rel(got, r), max(GRAD_TOL, 10 * tb._rel(s, r))
+        e, bar = gs.rel(got, r), max(GRAD_TOL, 10 * gs.rel(s, r))
         print("relative error of log_sd.grad term %d: %.3g (bar %.3g); grad %s checker %s" % (k, e, bar, got, r))
         assert e <= bar
     # fit: targets from the true bandwidths, a start at wrong ones

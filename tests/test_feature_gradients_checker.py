@@ -7,9 +7,9 @@ import pytest
 
 import crf_cases as cc
 import feature_cases as fc
+import grad_support as gs
 import meanfield_f64 as mf
 import meanfield_f64_features as mff
-import test_meanfield_backward as tb
 
 BARY_BAR = 4 * 2.6e-6          # test_bary_is_the_oracles: 4 x the largest difference measured
 
@@ -55,7 +55,7 @@ def test_feature_checker_forward_matches_the_oracle(po, wl, golden, name, T, rel
     pb, _ = fc.case(name, golden, po, wl)
     o, lats, U = _checker(po, pb)
     o.inference_native(T, False, relax)
-    q = mf.forward(torch.as_tensor(U), torch.as_tensor(tb._weights(pb)), lats, T, relax).numpy()
+    q = mf.forward(torch.as_tensor(U), torch.as_tensor(gs.weights(pb)), lats, T, relax).numpy()
     err = np.abs(q - o.probability()).max()
     print("largest |Q - oracle| %s T=%d relax=%g: %.3g" % (name, T, relax, err))
     assert err <= (5e-5 if name in ("generic:multi", "nt:d2-5-3_L9") else 1e-5)     # (several terms of different d on one CRF)
@@ -66,7 +66,7 @@ def test_feature_checker_gradcheck(po, wl):
     pb = wl.generic_problem(40, [2, 3], 3, seed=4)
     o, lats, U = _checker(po, pb)
     u = torch.as_tensor(U)
-    w = torch.as_tensor(tb._weights(pb))
+    w = torch.as_tensor(gs.weights(pb))
     G = torch.as_tensor(np.random.default_rng(0).standard_normal(U.shape))
     fs = [torch.as_tensor(lat.feat32.astype(np.float64)).clone().requires_grad_(True) for lat in lats]
 
@@ -83,7 +83,7 @@ def test_feature_checker_gradcheck(po, wl):
 def _fd_problem(wl, name):
     if name == "slam":
         pb = wl.slam_problem(300, seed=5)
-        w = tb._weights(pb) / 10                                 # (the TUM3 weights saturate most rows: their gradient is ~0)
+        w = gs.weights(pb) / 10                                 # (the TUM3 weights saturate most rows: their gradient is ~0)
         return pb, w
     d, N, L = {"d2": (2, 300, 2), "d3": (3, 200, 3), "d5": (5, 152, 2)}[name]       # (multiples of 4: no phantom points, quirk Q1, which the builder does not make)
     pb = wl.generic_problem(N, [d], L, seed=3, spread=1.5)
@@ -127,7 +127,7 @@ def test_hand_written_sweep_equals_autograd(po, wl, golden, name, T, relax):
     term."""
     pb, _ = fc.case(name, golden, po, wl)
     o, lats, U = _checker(po, pb)
-    w = tb._weights(pb) / (10 if name in ("slam:N1001", "c2") else 1)
+    w = gs.weights(pb) / (10 if name in ("slam:N1001", "c2") else 1)
     G = np.random.default_rng(7).standard_normal(U.shape)
     _, _, ref, _ = mff.feature_gradients(U, w, lats, T, relax, G)
     got = mff.sweep_feature_gradients(U, w, lats, T, relax, G)
@@ -141,5 +141,5 @@ def test_feature_gradient_is_zero_at_t0(po, wl):
     pb = wl.generic_problem(60, [3], 3, seed=2)
     o, lats, U = _checker(po, pb)
     G = np.random.default_rng(1).standard_normal(U.shape)
-    assert np.all(mff.sweep_feature_gradients(U, tb._weights(pb), lats, 0, 1.0, G)[0] == 0)
-    assert np.all(mff.feature_gradients(U, tb._weights(pb), lats, 0, 1.0, G)[2][0] == 0)
+    assert np.all(mff.sweep_feature_gradients(U, gs.weights(pb), lats, 0, 1.0, G)[0] == 0)
+    assert np.all(mff.feature_gradients(U, gs.weights(pb), lats, 0, 1.0, G)[2][0] == 0)

@@ -16,34 +16,10 @@ import numpy as np
 import pytest
 
 import crf_cases as cc
-from test_hip_parity import _shaped_problem
 
 pkg = importlib.import_module("lc-crf-slam_amd")
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _batch_of(pbs, maxN=None, use_unary=False):
-    F = len(pbs)
-    maxN = maxN or max(max(pb["N"] for pb in pbs), 1)
-    K = len(pbs[0]["kernels"])
-    feats = [np.zeros((F, maxN, 2), np.float32) for _ in range(K)]
-    label = np.full((F, maxN), -1, np.int16)
-    unary = np.zeros((F, maxN, 2), np.float32)
-    for f, pb in enumerate(pbs):
-        n = pb["N"]
-        if "label" in pb:
-            label[f, :n] = pb["label"]
-        if "unary" in pb:
-            unary[f, :n] = pb["unary"]
-        for k in range(K):
-            feats[k][f, :n] = pb["kernels"][k][0]
-    b = pkg.BatchCRF(F, maxN, 2, [2] * K, [float(pbs[0]["kernels"][k][1]) for k in range(K)])
-    if use_unary:
-        b.set_inputs_host([pb["N"] for pb in pbs], feats, unary=unary)
-    else:
-        b.set_inputs_host([pb["N"] for pb in pbs], feats, label=label, conf=pbs[0].get("conf", 0.7))
-    return b
 
 
 def _check_vs_oracle(po, pbs, b, n_iter, relax=1.0, expect_engine=3):
@@ -73,7 +49,7 @@ def test_frame_kernel_on_reference_fixtures(golden, case):
     recorded t, each as one launch."""
     z = golden["slam"]
     pb, exp = cc.case_problem(z, case), cc.case_expected(z, case)
-    b = _batch_of([pb, pb])
+    b = cc.batch_of([pb, pb])
     for t in sorted(exp["Q"]):
         b.run(t, True, relax=exp["relax"])
         Q, M = b.probability(), b.map()
@@ -89,7 +65,7 @@ def test_frame_kernel_on_reference_fixtures(golden, case):
 @pytest.mark.parametrize("N", [1, 2, 3, 4, 5, 63, 64, 65, 511, 1000, 1001, 1024, 1025, 2000, 2002, 2047, 2999, 3000, 3073, 4096])
 def test_frame_kernel_matches_oracle_sizes(po, wl, N):
     pbs = [wl.slam_problem(N, seed=700 + N), wl.slam_problem(max(N - 1, 1), seed=701 + N)]
-    b = _batch_of(pbs)
+    b = cc.batch_of(pbs)
     _check_vs_oracle(po, pbs, b, 5)
     b.close()
 
@@ -97,7 +73,7 @@ def test_frame_kernel_matches_oracle_sizes(po, wl, N):
 def test_frame_kernel_ragged_batch_and_idempotence(po, wl):
     sizes = [2000, 0, 1, 777, 1999, 5, 1024, 2000, 0, 333]
     pbs = [wl.slam_problem(n, seed=40 + i) for i, n in enumerate(sizes)]
-    b = _batch_of(pbs, maxN=2000)
+    b = cc.batch_of(pbs, maxN=2000)
     _check_vs_oracle(po, pbs, b, 5)
     Q, M = b.probability(), b.map()
     b.run(5, True)                                         # running the same batch again changes nothing
@@ -108,12 +84,12 @@ def test_frame_kernel_ragged_batch_and_idempotence(po, wl):
 @pytest.mark.parametrize("shape,N", [("one_cell", 2000), ("one_cell", 4096), ("one_cell", 70), ("two_clusters", 2047),
                                      ("two_clusters", 2600), ("rows_of_8", 2000), ("rows_of_8", 1030)])
 def test_frame_kernel_on_adversarial_lattices(po, wl, shape, N):
-    pb = _shaped_problem(wl, N, shape, seed=5)
-    b = _batch_of([pb])
+    pb = cc.shaped_problem(wl, N, shape, seed=5)
+    b = cc.batch_of([pb])
     _check_vs_oracle(po, [pb], b, 4)
     b.close()
     pb1 = dict(pb, kernels=pb["kernels"][:1])              # and as the only kernel (K = 1), damped
-    b = _batch_of([pb1])
+    b = cc.batch_of([pb1])
     _check_vs_oracle(po, [pb1], b, 3, relax=0.8)
     b.close()
 
@@ -122,8 +98,8 @@ def test_frame_kernel_falls_back_when_a_lattice_does_not_fit(po, wl):
     """Every point in its own cell: V = 3N vertices per kernel cannot live in one workgroup's LDS.  The launch flags
     that FRAME; the library re-runs exactly the flagged frames on the build + inference kernels and scatters their
     results back: same answers, the batch stays a one-launch batch (engine 3)."""
-    pbs = [_shaped_problem(wl, 1200, "sparse", seed=5), wl.slam_problem(1200, seed=9)]
-    b = _batch_of(pbs)
+    pbs = [cc.shaped_problem(wl, 1200, "sparse", seed=5), wl.slam_problem(1200, seed=9)]
+    b = cc.batch_of(pbs)
     b.run(4, True)
     Q, M = b.probability(), b.map()
     assert b.engine() == 3 and b.fallback_frames() == 1
@@ -134,7 +110,7 @@ def test_frame_kernel_falls_back_when_a_lattice_does_not_fit(po, wl):
         assert cc.same_bits(Q[f, :pb["N"]], o.probability()) and np.array_equal(M[f, :pb["N"]], o.map())
         assert [Vs[k][f] for k in range(2)] == [o.kernel(k)["V"] for k in range(2)]
     b.close()
-    b = _batch_of(pbs[:1])                                 # every frame flagged: the whole batch takes the two-kernel path in place
+    b = cc.batch_of(pbs[:1])                                 # every frame flagged: the whole batch takes the two-kernel path in place
     b.run(4, True)
     assert b.engine() in (1, 2) and b.fallback_frames() == 1
     o = cc.setup(po.OracleCRF, pbs[0])
@@ -149,10 +125,10 @@ def test_one_outlier_frame_costs_one_frame(po, wl):
     import time
     F, N = 1024, 1200
     base = [wl.slam_problem(N, seed=3100 + i) for i in range(4)]
-    odd = _shaped_problem(wl, N, "sparse", seed=5)
+    odd = cc.shaped_problem(wl, N, "sparse", seed=5)
     where = 517
     pbs = [odd if f == where else base[f % 4] for f in range(F)]
-    b, ball = _batch_of(pbs), _batch_of([base[f % 4] for f in range(F)])
+    b, ball = cc.batch_of(pbs), cc.batch_of([base[f % 4] for f in range(F)])
     for x in (b, ball):
         x.run(5, True); x.synchronize(); x.run(5, True); x.synchronize()      # warm: allocations, the fallback sub-engine
     ts = {}
@@ -197,10 +173,10 @@ def test_small_frames_share_a_cu_and_give_the_same_bits(po, wl):
     re-run alone); every frame against the oracle, and against the same frames in a batch too small for that shape."""
     sizes = [1024, 0, 1, 5, 511, 512, 513, 333, 64, 1000, 1023, 129]
     base = [wl.slam_problem(n, seed=2300 + i) for i, n in enumerate(sizes)]
-    odd = _shaped_problem(wl, 900, "sparse", seed=5)
+    odd = cc.shaped_problem(wl, 900, "sparse", seed=5)
     F = 300
     pbs = [odd if f == 77 else base[f % len(base)] for f in range(F)]
-    b = _batch_of(pbs, maxN=1024)
+    b = cc.batch_of(pbs, maxN=1024)
     b.run(5, True)
     q1, m1 = b.probability(), b.map()
     assert b.engine() == 3 and b.fallback_frames() == 1
@@ -223,7 +199,7 @@ def test_small_frames_share_a_cu_and_give_the_same_bits(po, wl):
         assert cc.same_bits(q2[f, :n], q) and np.array_equal(m2[f, :n], m), f
         assert [int(v1[k][f]) for k in range(2)] == V, f
     # without the outlier the built lattices fit the half-LDS plan: the inference kernel takes the 512-lane shape too
-    b = _batch_of([base[f % len(base)] for f in range(F)], maxN=1024)
+    b = cc.batch_of([base[f % len(base)] for f in range(F)], maxN=1024)
     b.build(); b.inference(5, True)
     assert b.engine() == 2
     q3 = b.probability()
@@ -231,7 +207,7 @@ def test_small_frames_share_a_cu_and_give_the_same_bits(po, wl):
         n = base[f % len(base)]["N"]
         assert cc.same_bits(q3[f, :n], refs[f % len(base)][0]), f
     b.close()
-    small = _batch_of(base, maxN=1024)                      # 12 frames: the 1024-lane shape
+    small = cc.batch_of(base, maxN=1024)                      # 12 frames: the 1024-lane shape
     small.run(5, True)
     for f in range(len(base)):
         assert cc.same_bits(small.probability()[f, :sizes[f]], refs[f][0])
@@ -242,7 +218,7 @@ def test_inference_after_run_uses_the_sized_engine(po, wl):
     """build -> inference -> run -> inference.  The second inference must run on the engine learn_sizes chose
     (the fused kernel here), not silently on the streaming engine because a one-launch run came in between."""
     pbs = [wl.slam_problem(1500, seed=77), wl.slam_problem(900, seed=78)]
-    b = _batch_of(pbs)
+    b = cc.batch_of(pbs)
     b.build(); b.inference(5, True)
     assert b.engine() == 2
     q0 = b.probability()
@@ -264,12 +240,12 @@ def test_frame_kernel_with_raw_unaries_and_unknown_labels(po, wl):
     del pu["label"]
     pu["unary"] = rng.uniform(0.05, 3.0, (1500, 2)).astype(np.float32)
     pu["unary"][::50] = np.float32([0.0, 45.0])             # beyond fast_exp's cut-off
-    b = _batch_of([pu], use_unary=True)
+    b = cc.batch_of([pu], use_unary=True)
     _check_vs_oracle(po, [pu], b, 5)
     b.close()
     pl = dict(pb, label=pb["label"].copy())
     pl["label"][::7] = -1                                   # unknown labels: uniform energies (densecrf3d.h:119)
-    b = _batch_of([pl])
+    b = cc.batch_of([pl])
     _check_vs_oracle(po, [pl], b, 5)
     b.close()
 
@@ -278,7 +254,7 @@ def test_frame_kernel_equals_two_kernel_path_bitwise(wl):
     """lccrf_batch_run (one launch) vs lccrf_batch_build + lccrf_batch_inference (build_small + fused)."""
     sizes = [2000, 1999, 1000, 2000, 0, 7, 3000, 2500]
     pbs = [wl.slam_problem(n, seed=60 + i) for i, n in enumerate(sizes)]
-    b = _batch_of(pbs, maxN=3000)
+    b = cc.batch_of(pbs, maxN=3000)
     b.run(5, True)
     q1, m1 = b.probability(), b.map()
     assert b.engine() == 3
@@ -337,7 +313,7 @@ def test_object_api_labels_are_taken_as_they_land(po, wl):
 def test_object_api_frame_that_does_not_fit_is_seen_through_the_label_array(po, wl):
     """A frame whose lattices do not fit the one-launch kernel writes -2 where its first label would go: getMap() leaves the
     early path and the two-kernel path re-runs the frame, same answers; the next frame on the cached handle is a normal one."""
-    for pb in (_shaped_problem(wl, 1200, "sparse", seed=5), wl.slam_problem(1200, seed=9), _shaped_problem(wl, 900, "sparse", seed=6)):
+    for pb in (cc.shaped_problem(wl, 1200, "sparse", seed=5), wl.slam_problem(1200, seed=9), cc.shaped_problem(wl, 900, "sparse", seed=6)):
         o, h = cc.setup(po.OracleCRF, pb), cc.setup(pkg.DenseCRFHIP, pb)
         o.inference_native(4, True)
         h.inference(4, True)
@@ -402,7 +378,7 @@ def test_two_workgroup_form_gives_the_same_bits(wl):
 import importlib, sys, numpy as np
 sys.path.insert(0, %r); sys.path.insert(0, %r)
 pkg = importlib.import_module("lc-crf-slam_amd"); wl = importlib.import_module("lc-crf-slam_amd.workloads")
-from test_hip_parity import _shaped_problem
+import crf_cases as cc
 out = []
 for rep in range(3):
     for N in (5, 700, 2000, 1024, 3000, 4096, 2047, 1):
@@ -410,18 +386,17 @@ for rep in range(3):
         h = pkg.DenseCRFHIP(pb["N"], pb["L"]); h.set_unary_from_label(pb["label"], pb["conf"])
         for f, w in pb["kernels"]: h.add_pairwise(f, w)
         h.inference(5, True); out.append(h.probability()); out.append(h.map().astype(np.float32)); h.close()
-for pb in (_shaped_problem(wl, 1200, "sparse", seed=5), _shaped_problem(wl, 2000, "one_cell", seed=5)):
+for pb in (cc.shaped_problem(wl, 1200, "sparse", seed=5), cc.shaped_problem(wl, 2000, "one_cell", seed=5)):
     h = pkg.DenseCRFHIP(pb["N"], pb["L"]); h.set_unary_from_label(pb["label"], pb["conf"])
     for f, w in pb["kernels"]: h.add_pairwise(f, w)
     h.inference(4, True); out.append(h.probability()); h.close()
     h = pkg.DenseCRFHIP(pb["N"], pb["L"]); h.set_unary_from_label(pb["label"], pb["conf"])
     h.add_pairwise(*pb["kernels"][1]); h.inference(3, True); out.append(h.probability()); h.close()
 # small batches take the same form (up to 64 frames); 65 frames do not
-from test_frame_engine import _batch_of
 for F in (3, 64, 65):
     pbs = [wl.slam_problem(int(n), seed=900 + i) for i, n in enumerate(np.random.default_rng(F).integers(1, 2300, F))]
-    if F == 3: pbs[1] = _shaped_problem(wl, 1200, "sparse", seed=7)      # one frame of the batch falls back
-    b = _batch_of(pbs); b.run(5, True); out.append(b.probability()); out.append(b.map().astype(np.float32)); b.close()
+    if F == 3: pbs[1] = cc.shaped_problem(wl, 1200, "sparse", seed=7)      # one frame of the batch falls back
+    b = cc.batch_of(pbs); b.run(5, True); out.append(b.probability()); out.append(b.map().astype(np.float32)); b.close()
 np.save(sys.argv[1], np.concatenate([o.ravel() for o in out]))
 """ % (ROOT, os.path.join(ROOT, "tests"))
     res = []
@@ -605,7 +580,6 @@ def test_full_size_frames_share_a_cu_and_give_the_same_bits(po, wl, shape):
 import importlib, sys, numpy as np
 sys.path.insert(0, %r); sys.path.insert(0, %r); sys.path.insert(0, %r)
 import crf_cases as cc, pyoracle as po
-from test_frame_engine import _batch_of
 wl = importlib.import_module("lc-crf-slam_amd.workloads")
 shape = %r
 noprep = shape == "2-noprep"
@@ -617,7 +591,7 @@ F = 272
 pbs = [base[f %% len(base)] for f in range(F)]
 refs = []
 for n_iter, relax in ((5, 1.0), (3, 0.5)):
-    b = _batch_of(pbs, maxN=top)
+    b = cc.batch_of(pbs, maxN=top)
     b.build(); b.inference(n_iter, True, relax=relax)
     Q, M = b.probability(), b.map()
     assert b.engine() == 2 and b.fused_shape() == (lanes, 2), (b.engine(), b.fused_shape())
@@ -638,7 +612,7 @@ for n_iter, relax in ((5, 1.0), (3, 0.5)):
 # frames of 513 .. 1024 points take the plan too (two points per lane, everything in registers)
 small = [wl.slam_problem(n, seed=5300 + i) for i, n in enumerate([1024, 513, 700, 1000, 0, 640, 1023, 514])]
 pbs2 = [small[f %% len(small)] for f in range(F)]
-b = _batch_of(pbs2, maxN=1024)
+b = cc.batch_of(pbs2, maxN=1024)
 b.build(); b.inference(5, True)
 Q, M = b.probability(), b.map()
 assert b.engine() == 2 and b.fused_shape() == (512, 2), (b.engine(), b.fused_shape())
@@ -658,7 +632,7 @@ for pick in ((0,), (1,), (1, 1)):
     for pb in base:
         q = dict(pb); q["kernels"] = [pb["kernels"][k] for k in pick]; pb1.append(q)
     pbs1 = [pb1[f %% len(pb1)] for f in range(F)]
-    b = _batch_of(pbs1, maxN=top)
+    b = cc.batch_of(pbs1, maxN=top)
     b.build(); b.inference(4, True)
     Q = b.probability()
     for again in range(2):
@@ -709,7 +683,7 @@ def test_prepared_launch_records_follow_the_lattices_and_not_the_unaries(po, wl)
             o.close()
 
     pbs = batch(9100)
-    b = _batch_of(pbs, maxN=maxN)
+    b = cc.batch_of(pbs, maxN=maxN)
     assert b.last_prepare()[1] == 0
     b.build()
     b.inference(5, True)                                     # the first inference behind a build: the self-contained kernel
@@ -761,7 +735,7 @@ def test_repeated_inference_runs_from_prepared_records_in_every_fused_shape(po, 
         base = [wl.slam_problem(n, seed=9500 + i) for i, n in enumerate(sizes)]
     elif case == "sparse":                                   # large lattices: the tables take two 16-byte pieces per lane
         top, shape = 850, (1024, 1)                          # (V = 3 N for the first kernel: ~30 KB of neighbour words at 820 points)
-        base = [_shaped_problem(wl, n, "sparse", seed=20 + i) for i, n in enumerate([700, 760, 820, 640])] + [wl.slam_problem(850, seed=9600)]
+        base = [cc.shaped_problem(wl, n, "sparse", seed=20 + i) for i, n in enumerate([700, 760, 820, 640])] + [wl.slam_problem(850, seed=9600)]
     elif case in ("k1_chain", "k1_short"):
         top, shape = 3000, (1024, 1)
         base = []
@@ -776,7 +750,7 @@ def test_repeated_inference_runs_from_prepared_records_in_every_fused_shape(po, 
         sizes, top, shape, F = [3000, 2500, 2800], 3000, (1024, 1), 8
         base = [wl.slam_problem(n, seed=9900 + i) for i, n in enumerate(sizes)]
     pbs = [base[f % len(base)] for f in range(F)]
-    b = _batch_of(pbs, maxN=top)
+    b = cc.batch_of(pbs, maxN=top)
     b.build()
     b.inference(5, True)
     assert b.engine() == 2 and b.fused_shape() == shape, (case, b.engine(), b.fused_shape())
@@ -799,7 +773,7 @@ def test_event_timing_option_only_switches_the_events_off(po, wl):
     """LCCRF_OPT_EVENT_TIMING = 0: no HIP events around build / inference / run (a packet less between two launches), timings read 0,
     results unchanged; 1 brings them back."""
     pbs = [wl.slam_problem(700, seed=9950 + i) for i in range(4)]
-    b = _batch_of(pbs)
+    b = cc.batch_of(pbs)
     b.build(); b.inference(5, True)
     Q = b.probability().copy()
     assert b.last_timing()["inference_ms"] > 0 and b.last_timing()["build_ms"] > 0
@@ -821,7 +795,7 @@ def test_two_handles_on_their_own_streams_give_each_its_results(po, wl):
     its own frames' results -- against the oracle, after many interleaved launches, through inference and through the one-launch path."""
     F, maxN = 264, 2048
     sets = [[wl.slam_problem(n, seed=9960 + 10 * h + i) for i, n in enumerate([2000, 1300, 1999, 1100, 2048, 1537, 3, 0])] for h in range(2)]
-    bs = [_batch_of([sets[h][f % 8] for f in range(F)], maxN=maxN) for h in range(2)]
+    bs = [cc.batch_of([sets[h][f % 8] for f in range(F)], maxN=maxN) for h in range(2)]
     streams = [b.own_stream() for b in bs]
     assert all(streams) and streams[0] != streams[1]
     for b in bs:
@@ -891,7 +865,7 @@ def test_full_size_frames_share_a_cu_in_the_one_launch_kernel(po, wl):
     every frame against the oracle bit for bit, V against the reference's M_; then build + inference on the same handle."""
     sizes = [2000, 1025, 1536, 1537, 1999, 2048, 1100, 1920, 1921, 2047, 0, 700, 1152, 3, 2001, 1300]
     base = [wl.slam_problem(n, seed=6100 + i) for i, n in enumerate(sizes)]
-    odd = _shaped_problem(wl, 1800, "sparse", seed=7)
+    odd = cc.shaped_problem(wl, 1800, "sparse", seed=7)
     F = 272
     refs = {}
     rng = np.random.default_rng(12)
@@ -904,7 +878,7 @@ def test_full_size_frames_share_a_cu_in_the_one_launch_kernel(po, wl):
                 return pu
             base, odd = [raw(pb) for pb in base], raw(odd)
         pbs = [odd if f == 99 else base[f % len(base)] for f in range(F)]
-        b = _batch_of(pbs, maxN=2048, use_unary=use_unary)
+        b = cc.batch_of(pbs, maxN=2048, use_unary=use_unary)
         b.run(n_iter, True, relax=relax)
         Q, M = b.probability(), b.map()
         assert b.engine() == 3 and b.fused_shape() == (512, 2) and b.fallback_frames() == 1, (b.engine(), b.fused_shape(), b.fallback_frames())
@@ -931,7 +905,7 @@ def test_full_size_frames_share_a_cu_in_the_one_launch_kernel(po, wl):
         b.close()
     # a batch whose frames mostly do NOT fit: the engine stops asking for the shape
     pbs = [odd if f % 2 else base[0] for f in range(F)]
-    b = _batch_of(pbs, maxN=2048, use_unary=True)
+    b = cc.batch_of(pbs, maxN=2048, use_unary=True)
     b.run(2, True)
     q = b.probability()
     assert b.fallback_frames() == F // 2 and b.fused_shape() == (512, 2)
@@ -946,10 +920,9 @@ def test_frame_lean_switch_gives_the_same_bits(wl):
 import importlib, sys, numpy as np
 sys.path.insert(0, %r); sys.path.insert(0, %r)
 import crf_cases as cc
-from test_frame_engine import _batch_of
 wl = importlib.import_module("lc-crf-slam_amd.workloads")
 pbs = [wl.slam_problem(n, seed=6200 + i) for i, n in enumerate([2000, 1500, 1900, 1026] * 64)]
-b = _batch_of(pbs, maxN=2000)
+b = cc.batch_of(pbs, maxN=2000)
 b.run(5, True)
 np.save(sys.argv[1], np.concatenate([b.probability().ravel().view(np.uint32), np.asarray(b.fused_shape(), np.uint32)]))
 """ % (ROOT, os.path.join(ROOT, "tests"))
@@ -980,7 +953,7 @@ def test_half_cu_frame_kernel_corner_calls(po, wl):
             pb["label"] = pb["label"].copy()
             pb["label"][::9] = -1
         pbs = [base[f % 5] for f in range(F)]
-        b = _batch_of(pbs, maxN=2048)
+        b = cc.batch_of(pbs, maxN=2048)
         refs = []
         for pb in pbs[:5]:
             o = cc.setup(po.OracleCRF, pb)
@@ -1010,7 +983,7 @@ def test_half_cu_frame_kernel_corner_calls(po, wl):
     # one handle, a batch of large frames, then a batch of small ones
     big = [wl.slam_problem(2000, seed=6500 + f % 3) for f in range(F)]
     small = [wl.slam_problem(300 + f % 3, seed=6600 + f % 3) for f in range(F)]
-    b = _batch_of(big, maxN=2048)
+    b = cc.batch_of(big, maxN=2048)
     b.run(3, True)
     feats = [np.zeros((F, 2048, 2), np.float32) for _ in range(2)]
     label = np.full((F, 2048), -1, np.int16)

@@ -79,27 +79,6 @@ def test_hip_matches_oracle_slam_sizes(po, wl, N):
     assert np.array_equal(o.map(), h.map())
 
 
-def _shaped_problem(wl, N, shape, seed):
-    """SLAM-shaped frames whose lattices stress one code path of the fused engine each."""
-    pb = wl.slam_problem(N, seed=seed)
-    rng = np.random.default_rng(seed)
-    f0, f1 = pb["kernels"][0][0].copy(), pb["kernels"][1][0].copy()
-    if shape == "one_cell":            # every point in one lattice cell: 3 vertices, rows of N products
-        f0[:] = f0[0]
-        f1[:] = f1[0]
-    elif shape == "two_clusters":      # two very long rows per kernel plus stragglers
-        half = N // 2
-        f0[:half], f0[half:] = f0[0], f0[-1] + np.float32(7.5)
-        f0[::97] += rng.normal(0, 3, f0[::97].shape).astype(np.float32)
-    elif shape == "rows_of_8":         # row lengths around the 8-product units of chain_rows
-        cells = max(N // 8, 1)
-        f0 = (np.stack([np.arange(N) % cells, np.arange(N) % cells], 1) * np.float32(4.0)).astype(np.float32)
-    elif shape == "sparse":            # every point its own cell: V = 3N, far beyond the chain's vertex limit
-        f0 = (np.stack([np.arange(N), (np.arange(N) * 7) % 1013], 1) * np.float32(9.0)).astype(np.float32)
-    pb["kernels"] = [(f0, pb["kernels"][0][1]), (f1, pb["kernels"][1][1])]
-    return pb
-
-
 @pytest.mark.parametrize("shape,N", [("one_cell", 2000), ("one_cell", 4096), ("one_cell", 70), ("two_clusters", 2047),
                                      ("two_clusters", 2600), ("rows_of_8", 2000), ("rows_of_8", 1030),
                                      ("sparse", 1200)])
@@ -107,7 +86,7 @@ def test_fused_engine_on_adversarial_lattices(po, wl, shape, N):
     """Very long rows (chain path, also with the shared product buffer and 3-4 points per lane), row
     lengths on the chain's unit boundaries, and lattices too large for the chain path: the engine
     the library picks must still reproduce the oracle bit for bit."""
-    pb = _shaped_problem(wl, N, shape, seed=5)
+    pb = cc.shaped_problem(wl, N, shape, seed=5)
     o, h = cc.setup(po.OracleCRF, pb), cc.setup(pkg.DenseCRFHIP, pb)
     o.inference_native(4, True)
     h.inference(4, True)
@@ -394,7 +373,7 @@ def test_batch_mixing_long_row_and_short_row_frames(po, wl):
     """One batch, one launch: the chain decision is made once for the batch (longest row over all
     frames), so frames with short rows ride the chain path of their long-row neighbours and vice versa."""
     shapes = [("one_cell", 1800), (None, 2000), ("rows_of_8", 1999), ("two_clusters", 2048), (None, 7), ("one_cell", 64)]
-    pbs = [wl.slam_problem(n, seed=90 + i) if sh is None else _shaped_problem(wl, n, sh, seed=90 + i)
+    pbs = [wl.slam_problem(n, seed=90 + i) if sh is None else cc.shaped_problem(wl, n, sh, seed=90 + i)
            for i, (sh, n) in enumerate(shapes)]
     F, maxn = len(pbs), max(pb["N"] for pb in pbs)
     feats = [np.zeros((F, maxn, 2), np.float32) for _ in range(2)]
@@ -784,9 +763,8 @@ def test_locality_mode_on_reference_vectors(golden, name, vertex_order):
     points are processed in an internal order -- and the lattice built by sorting the entries on the row-major code of their vertex
     (round 4: the sorted build, no hash table; LCCRF_OPT_VERTEX_ORDER 0 = automatic: the eight copies, 1 = on: the single frame
     too, 2 = off: the hash build for both; results must not depend on how vertices are found or numbered)."""
-    from test_oracle_golden import _large_case
     z = golden["large"]
-    pb, n_iter, relax = _large_case(z, name)
+    pb, n_iter, relax = cc.large_case(z, name)
     N, L = pb["N"], pb["L"]
     f, w = pb["kernels"][0]
     for F in (1, 8):

@@ -15,7 +15,6 @@ import numpy as np
 import pytest
 
 import crf_cases as cc
-from test_hip_parity import _shaped_problem
 
 pkg = importlib.import_module("lc-crf-slam_amd")
 pytestmark = pytest.mark.gpu
@@ -140,7 +139,7 @@ def test_three_handles_round_robin_keep_every_batch_apart(wl):
 
 def test_a_frame_that_falls_back_is_settled_by_wait_download(po, wl):
     pbs = [wl.slam_problem(900, seed=8300 + i) for i in range(40)]
-    pbs[17] = _shaped_problem(wl, 900, "sparse", seed=5)    # lattices too large for the one-launch kernel: re-run at the wait
+    pbs[17] = cc.shaped_problem(wl, 900, "sparse", seed=5)    # lattices too large for the one-launch kernel: re-run at the wait
     maxN = 900
     npts, feats, label = _arrays(pbs, maxN)
     b = _new_batch(pbs, maxN)
@@ -164,7 +163,7 @@ def test_a_fallback_settled_before_wait_download_still_refreshes_the_host_copies
     """any call between download_async and wait_download that settles the flagged frames (and clears the pending state)
     used to leave the pinned copies at their pre-re-run bits.  The re-run itself now queues the copies again."""
     pbs = [wl.slam_problem(900, seed=8300 + i) for i in range(40)]
-    pbs[17] = _shaped_problem(wl, 900, "sparse", seed=5)
+    pbs[17] = cc.shaped_problem(wl, 900, "sparse", seed=5)
     maxN = 900
     npts, feats, label = _arrays(pbs, maxN)
     b = _new_batch(pbs, maxN)
@@ -198,7 +197,7 @@ def test_pipeline_of_256_frame_batches_runs_two_frames_per_cu_and_settles_its_fa
     batch comes back with its own bits, the flagged frame's included, and the handles report the shape."""
     maxN, F = 2048, 256
     base = [wl.slam_problem(1500 + 61 * i, seed=8600 + i) for i in range(8)]
-    odd = _shaped_problem(wl, 1700, "sparse", seed=9)
+    odd = cc.shaped_problem(wl, 1700, "sparse", seed=9)
     batches = [[odd if f == 40 + i else base[(f + i) % 8] for f in range(F)] for i in range(3)]
     refs = {}
     for pb in base + [odd]:

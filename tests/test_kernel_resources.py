@@ -4,32 +4,12 @@ The one-workgroup-per-frame kernels' SLAM variants must not spill: scratch traff
 mean-field loop costs more than any optimisation in those files gains, and
 chain_rows' hand-written ring relies on v96..v127 being free around it.  The fused build must not
 spill vector registers either."""
-import os
 import re
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-
-
-def resource_usage(src):
-    cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "--cuda-device-only",
-           "-I" + os.path.join(ROOT, "lc-crf-slam_amd", "csrc"), "-I" + os.path.join(ROOT, "include"),
-           "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "lc-crf-slam_amd", "csrc", src), "-o", os.devnull]
-    err = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
-    out, cur = {}, None
-    for line in err.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1)] = int(m.group(2))
-    return out
+from kernel_resources import HIPCC, resource_usage
 
 
 @pytest.mark.skipif(shutil.which(HIPCC) is None, reason="hipcc not installed")

@@ -15,10 +15,11 @@ import os
 import numpy as np
 import pytest
 
+import batch_cases as bc
 import crf_cases as cc
+import grad_support as gs
 import meanfield_f64 as mf
-from test_batch_backward import _batch_backward, _label_frames
-from test_meanfield_backward import _backward, _checker, _weights, assert_matches_checker
+from abi_support import lib  # noqa: F401
 
 pkg = importlib.import_module("lc-crf-slam_amd")
 LABELS_NPZ = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "labels.npz")
@@ -31,13 +32,6 @@ def _fixture():
 
 
 CASES = [str(c) for c in _fixture()["cases"]]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(pkg.LIB_PATH):
-        pkg.build_library()
-    return pkg.lib()
 
 
 def _check_fixture_case(c, z, name):
@@ -92,11 +86,11 @@ def test_checker_forward_matches_the_labels_fixture(po, name):
     import torch
     z = _fixture()
     pb = cc.case_problem(z, name)
-    o, lats, U = _checker(po, pb)
+    o, lats, U = gs.checker(po, pb)
     tol = 5e-5 if len(pb["kernels"]) > 1 else 1e-5
     trace = z[name + "_trace"]
     for t in range(1, len(trace)):
-        q = mf.forward(torch.as_tensor(U), torch.as_tensor(_weights(pb)), lats, t, float(z["relax"])).numpy()
+        q = mf.forward(torch.as_tensor(U), torch.as_tensor(gs.weights(pb)), lats, t, float(z["relax"])).numpy()
         assert np.abs(q - trace[t]).max() <= tol, (name, t, np.abs(q - trace[t]).max())
     o.close()
 
@@ -262,7 +256,7 @@ def test_locality_mode_at_large_label_counts(po, L):
 @pytest.mark.parametrize("L", [9, 33, 64])
 def test_ragged_batch_with_eight_terms_at_large_label_counts(po, L):
     sizes = [700, 0, 1500, 77, 1201]
-    fr = _label_frames(L, sizes, seed=300 + L)
+    fr = bc.label_frames(L, sizes, seed=300 + L)
     probs = fr.probs
     b = fr.batch()
     b.inference(3, True, relax=0.75)
@@ -333,12 +327,12 @@ def test_gradients_match_the_checker_in_every_lane_group(po, L, K, T, relax):
     the bar of test_gradients_match_the_checker.  The weights of label_problem keep the rows unsaturated, so the gradients compared
     are far above that test's floor."""
     pb = cc.label_problem(400, L, [3] if K == 1 else EIGHT, seed=500 + L)
-    o, lats, U = _checker(po, pb)
+    o, lats, U = gs.checker(po, pb)
     G = np.random.default_rng(L * 10 + K).standard_normal((pb["N"], L))
     h = cc.setup(pkg.DenseCRFHIP, pb)
-    gu, gw = _backward(h, T, relax, G, K)
+    gu, gw = gs.backward(h, T, relax, G, K)
     h.close(), o.close()
-    ref_u, ref_w = assert_matches_checker(gu, gw, U, _weights(pb), lats, T, relax, G, "L=%d K=%d" % (L, K))
+    ref_u, ref_w = gs.assert_matches_checker(gu, gw, U, gs.weights(pb), lats, T, relax, G, "L=%d K=%d" % (L, K))
     assert np.linalg.norm(ref_u) > 1e-3 * np.linalg.norm(G)
 
 
@@ -351,13 +345,13 @@ def test_gradients_without_terms_in_every_lane_group(po, L):
     U = pb["unary"].astype(np.float64)
     for T in (0, 1, 5):
         for relax in (1.0, 0.7):
-            gu, _ = _backward(h, T, relax, G, 0)
-            assert_matches_checker(gu, np.zeros(0), U, np.zeros(0), [], T, relax, G, "L=%d K=0" % L)
+            gu, _ = gs.backward(h, T, relax, G, 0)
+            gs.assert_matches_checker(gu, np.zeros(0), U, np.zeros(0), [], T, relax, G, "L=%d K=0" % L)
     h.close()
 
 
 def _k8_frames(L):
-    return _label_frames(L, [300, 0, 1100, 77, 650], seed=700 + L)
+    return bc.label_frames(L, [300, 0, 1100, 77, 650], seed=700 + L)
 
 
 @pytest.mark.gpu
@@ -367,14 +361,14 @@ def test_batch_gradients_with_eight_terms_match_the_checker(po, L):
     b = fr.batch()
     G = fr.grad_prob(L)
     for T, relax in ((5, 0.7), (1, 1.0)):
-        gu, gw = _batch_backward(b, T, relax, G, fr.K)
+        gu, gw = gs.batch_backward(b, T, relax, G, fr.K)
         for f, n in enumerate(fr.N):
             if n == 0:
                 assert np.all(gu[f] == 0) and np.all(gw[f] == 0)
                 continue
-            o, lats, U = _checker(po, fr.probs[f])
-            assert_matches_checker(gu[f, :n], gw[f], U, np.array(fr.w), lats, T, relax, G[f, :n].astype(np.float64),
-                                   "frame %d L=%d" % (f, L))
+            o, lats, U = gs.checker(po, fr.probs[f])
+            gs.assert_matches_checker(gu[f, :n], gw[f], U, np.array(fr.w), lats, T, relax, G[f, :n].astype(np.float64),
+                                      "frame %d L=%d" % (f, L))
             o.close()
     b.close()
 
@@ -387,11 +381,11 @@ def test_torch_layers_at_64_labels_and_eight_terms_give_the_bits_of_the_c_abi():
     pb = cc.label_problem(900, 64, EIGHT, seed=800)
     h = cc.setup(pkg.DenseCRFHIP, pb)
     G = np.random.default_rng(8).standard_normal((900, 64)).astype(np.float32)
-    ref_u, ref_w = _backward(h, T, relax, G, 8)
+    ref_u, ref_w = gs.backward(h, T, relax, G, 8)
     h.inference(T, False, relax)
     ref_q = h.probability()
     u = torch.from_numpy(h.unary()).cuda().requires_grad_(True)
-    w = torch.tensor(_weights(pb).astype(np.float32), requires_grad=True)
+    w = torch.tensor(gs.weights(pb).astype(np.float32), requires_grad=True)
     q = ag.mean_field(h, u, w, T, relax)
     q.backward(torch.from_numpy(G).cuda())
     torch.cuda.synchronize()
@@ -404,7 +398,7 @@ def test_torch_layers_at_64_labels_and_eight_terms_give_the_bits_of_the_c_abi():
     ref.inference(T, False, relax)
     q_ref = ref.probability()
     Gb = np.nan_to_num(fr.grad_prob(9), nan=0.0)
-    bu, bw = _batch_backward(ref, T, relax, Gb, 8)
+    bu, bw = gs.batch_backward(ref, T, relax, Gb, 8)
     ref.close()
     b = fr.batch()
     u = torch.from_numpy(fr.U).cuda().requires_grad_(True)

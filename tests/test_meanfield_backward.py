@@ -5,47 +5,17 @@ asymmetry of Phi that makes the order matter, and the new symbols.  GPU: lccrf_i
 autograd gradients, its state and determinism contract, lccrf_set_pairwise_weight, argument checks and the torch layer."""
 import ctypes as C
 import importlib
-import os
-import re
 
 import numpy as np
 import pytest
 
 import crf_cases as cc
+import grad_support as gs
 import meanfield_f64 as mf
+from abi_support import assert_declared_exported_bound, hip_malloc, lib  # noqa: F401
 
 pkg = importlib.import_module("lc-crf-slam_amd")
 NEW_SYMBOLS = ("lccrf_set_pairwise_weight", "lccrf_inference_backward")
-GRAD_TOL = 1e-4
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(pkg.LIB_PATH):
-        pkg.build_library()
-    return pkg.lib()
-
-
-def _weights(pb):
-    return np.array([float(w) for _, w in pb["kernels"]], np.float64)
-
-
-def _checker(po, pb):
-    """(oracle CRF, its lattices, U as float64)"""
-    o = cc.setup(po.OracleCRF, pb)
-    return o, mf.lattices(o, len(pb["kernels"])), o.unary().astype(np.float64)
-
-
-def _golden_problem(golden, name):
-    group, case = name.split(":")
-    if group == "labels":                                       # (not among conftest's fixtures)
-        return cc.case_problem(np.load(os.path.join(os.path.dirname(__file__), "golden", "labels.npz")), case)
-    z = golden[group]
-    if group == "large":
-        from test_oracle_golden import _large_case
-        pb, _, _ = _large_case(z, case)
-        return pb
-    return cc.case_problem(z, case)
 
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------------
@@ -55,10 +25,10 @@ def _golden_problem(golden, name):
 @pytest.mark.parametrize("relax", [1.0, 0.7])
 def test_checker_forward_matches_the_oracle(po, golden, name, T, relax):
     import torch
-    pb = _golden_problem(golden, name)
-    o, lats, U = _checker(po, pb)
+    pb = cc.golden_problem(golden, name)
+    o, lats, U = gs.checker(po, pb)
     o.inference_native(T, False, relax)
-    q = mf.forward(torch.as_tensor(U), torch.as_tensor(_weights(pb)), lats, T, relax).numpy()
+    q = mf.forward(torch.as_tensor(U), torch.as_tensor(gs.weights(pb)), lats, T, relax).numpy()
     # generic:multi (several terms of different d on one CRF) drifts furthest from the float32 oracle: 3.2e-5 measured at T = 5,
     # relax = 0.7 (every other case and setting <= 1e-5) -- float32 rounding carried through five iterations, not the method
     tol = 5e-5 if name == "generic:multi" else 1e-5
@@ -68,9 +38,9 @@ def test_checker_forward_matches_the_oracle(po, golden, name, T, relax):
 def test_checker_gradcheck(po, wl):
     import torch
     pb = wl.generic_problem(40, [2, 3], 3, seed=4)
-    o, lats, U = _checker(po, pb)
+    o, lats, U = gs.checker(po, pb)
     u = torch.as_tensor(U).clone().requires_grad_(True)
-    w = torch.as_tensor(_weights(pb)).clone().requires_grad_(True)
+    w = torch.as_tensor(gs.weights(pb)).clone().requires_grad_(True)
     for relax in (1.0, 0.7):
         assert torch.autograd.gradcheck(lambda a, b: mf.forward(a, b, lats, 3, relax), (u, w), eps=1e-6, atol=1e-7)
 
@@ -79,8 +49,8 @@ def test_checker_gradcheck(po, wl):
 def test_reverse_order_filter_is_the_adjoint(po, golden, name):
     """<y, Phi x> = <Phi^T y, x> with Phi^T the same splat and slice and the blur passes in reverse axis order."""
     import torch
-    pb = _golden_problem(golden, name)
-    o, lats, _ = _checker(po, pb)
+    pb = cc.golden_problem(golden, name)
+    o, lats, _ = gs.checker(po, pb)
     rng = np.random.default_rng(0)
     for lat in lats:
         x = torch.as_tensor(rng.standard_normal((pb["N"], 3)))
@@ -94,8 +64,8 @@ def test_phi_is_not_symmetric(po, golden, name):
     """On cases the GPU tests use, the transpose formed with the FORWARD blur order (i.e. Phi itself) is far from Phi^T: a backward
     that reused the forward order would miss the gradient bar by orders of magnitude."""
     import torch
-    pb = _golden_problem(golden, name)
-    o, lats, _ = _checker(po, pb)
+    pb = cc.golden_problem(golden, name)
+    o, lats, _ = gs.checker(po, pb)
     eye = torch.eye(pb["N"], dtype=torch.float64)
     phi = lats[0].apply(eye)                                 # column j = Phi e_j
     assert torch.allclose(lats[0].apply(eye, reverse=True), phi.T, rtol=0, atol=1e-12)
@@ -103,11 +73,7 @@ def test_phi_is_not_symmetric(po, golden, name):
 
 
 def test_backward_symbols_are_declared_exported_and_bound(lib):
-    src = re.sub(r"/\*.*?\*/", "", open(pkg.HEADER_PATH).read(), flags=re.S)
-    for n in NEW_SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % n, src), n
-        assert hasattr(lib, n), n
-        assert getattr(lib, n).argtypes is not None, n
+    assert_declared_exported_bound(lib, NEW_SYMBOLS)
     assert lib.lccrf_abi_version() == 3
     assert hasattr(pkg.DenseCRFHIP, "set_pairwise_weight") and hasattr(pkg.DenseCRFHIP, "inference_backward_device")
 
@@ -118,70 +84,8 @@ def test_backward_rejects_a_null_handle(lib):
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _crop_problem(golden, po):
-    """64 x 48 crop of the reference's image example: 21 labels, the position and RGB image terms."""
-    z = golden["example_im1"]
-    W, H = 64, 48
-    im = np.ascontiguousarray(z["im"][:H, :W], np.uint8)
-    lab = np.ascontiguousarray(z["label"].reshape(240, 320)[:H, :W].reshape(-1), np.int16)
-    pb = dict(N=W * H, L=21, label=lab, conf=np.float32(0.5),
-              kernels=[(po.oracle_image_features(W, H, 3.0), np.float32(3.0)),
-                       (po.oracle_image_features(W, H, 60.0, im, 20.0), np.float32(10.0))])
-    return pb, (W, H, im)
-
-
-def _gpu_handle(pb, image=None):
-    import torch
-    if image is None:
-        return cc.setup(pkg.DenseCRFHIP, pb), []
-    W, H, im = image
-    d_lab, d_img = _dev(pb["label"]), _dev(im)
-    torch.cuda.synchronize()
-    h = pkg.DenseCRFHIP(pb["N"], pb["L"])
-    h.set_unary_from_label_device(d_lab.data_ptr(), pb["conf"])
-    h.add_image_kernel(W, H, 3.0, 3.0)
-    h.add_image_kernel(W, H, 10.0, 60.0, d_img.data_ptr(), pkg.IMAGE_U8, 20.0)
-    return h, [d_lab, d_img]
-
-
-def _backward(h, T, relax, G, K):
-    import torch
-    g = _dev(G.astype(np.float32))
-    gu = torch.full(G.shape, float("nan"), device="cuda")
-    gw = torch.full((max(K, 1),), float("nan"), device="cuda")
-    torch.cuda.synchronize()
-    h.inference_backward_device(T, relax, g.data_ptr(), gu.data_ptr(), gw.data_ptr() if K else None)
-    h.synchronize()
-    return gu.cpu().numpy(), gw[:K].cpu().numpy()
-
-
-def _rel(a, b, floor=0.0):
-    """relative L2 error; gradients smaller than `floor` are compared in absolute terms against it"""
-    nb = max(np.linalg.norm(b), floor)
-    return np.linalg.norm(a - b) / (nb if nb > 0 else 1.0)
-
-
-CASES = ["slam:N5", "slam:N1001", "slam:C3", "generic:d1_L3", "generic:d3_L21", "generic:d5_L2", "generic:d6_L3", "generic:multi",
-         "bilateral:c5", "large:c5", "image64x48", "c2"]
-
-
-def _case(name, golden, po, wl):
-    if name == "image64x48":
-        return _crop_problem(golden, po)
-    if name.startswith("K8_L"):                                  # eight terms of d = 1 .. 8
-        return cc.label_problem(900, int(name[4:]), list(range(1, 9)), seed=6), None
-    if name == "c2":
-        return wl.slam_problem(2000, seed=12), None
-    return _golden_problem(golden, name), None
-
-
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", CASES)
+@pytest.mark.parametrize("name", cc.CASES)
 @pytest.mark.parametrize("T", [0, 1, 5, 10])
 @pytest.mark.parametrize("relax", [1.0, 0.7])
 def test_gradients_match_the_checker(po, wl, golden, name, T, relax):
@@ -192,45 +96,26 @@ def test_gradients_match_the_checker(po, wl, golden, name, T, relax):
     conditioning of those iterations in fp32, not the kernels; every other case and setting is <= 6e-5.  Gradients below 1e-6 of
     |dL/dQ| (slam:N5 from T = 5: |dL/dU| ~ 1e-17, every row saturated; the forward's fast_exp gives exactly 0 beyond e^-20, so by the
     section 1c convention the gradient is exactly 0) are compared in absolute terms against that floor."""
-    pb, image = _case(name, golden, po, wl)
-    o, lats, U = _checker(po, pb)
+    pb, image = cc.case(name, golden, po, wl)
+    o, lats, U = gs.checker(po, pb)
     G = np.random.default_rng(1234).standard_normal((pb["N"], pb["L"]))
-    h, keep = _gpu_handle(pb, image)
-    gu, gw = _backward(h, T, relax, G, len(pb["kernels"]))
+    h, keep = gs.gpu_handle(pb, image)
+    gu, gw = gs.backward(h, T, relax, G, len(pb["kernels"]))
     h.close()
-    assert_matches_checker(gu, gw, U, _weights(pb), lats, T, relax, G, name)
-
-
-def assert_matches_checker(gu, gw, U, w, lats, T, relax, G, name=""):
-    """The bar of test_gradients_match_the_checker: relative L2 error against the float64 checker <= max(1e-4, 10 x that of the
-    float32 checker), gradients below 1e-6 of |dL/dQ| compared in absolute terms against that floor; at T = 0 dL/dw is 0.
-    Returns the checker's (dL/dU, dL/dw)."""
-    import torch
-    ref_u, ref_w = mf.gradients(U, w, lats, T, relax, G)
-    floor_u = 1e-6 * np.linalg.norm(G)
-    floor_w = 1e-6 * np.linalg.norm(G) * max(np.linalg.norm(w), 1.0)
-    eu, ew = _rel(gu, ref_u, floor_u), _rel(gw, ref_w, floor_w)
-    f32_u, f32_w = mf.gradients(U, w, lats, T, relax, G, dtype=torch.float32)
-    bu = max(GRAD_TOL, 10 * _rel(f32_u, ref_u, floor_u))
-    bw = max(GRAD_TOL, 10 * _rel(f32_w, ref_w, floor_w))
-    print("relative L2 error %s T=%d relax=%g: dL/dU %.3g dL/dw %.3g (bars %.3g %.3g)" % (name, T, relax, eu, ew, bu, bw))
-    assert eu <= bu and ew <= bw, "relative L2 error dL/dU %.3g (bar %.3g), dL/dw %.3g (bar %.3g)" % (eu, bu, ew, bw)
-    if T == 0:
-        assert np.all(gw == 0)
-    return ref_u, ref_w
+    gs.assert_matches_checker(gu, gw, U, gs.weights(pb), lats, T, relax, G, name)
 
 
 @pytest.mark.gpu
 def test_t0_is_the_softmax_backward_and_k0_works(po, wl):
     import torch
     pb = wl.slam_problem(700, seed=2)
-    o, lats, U = _checker(po, pb)
+    o, lats, U = gs.checker(po, pb)
     G = np.random.default_rng(5).standard_normal((pb["N"], 2))
     P0 = torch.softmax(-torch.as_tensor(U), 1).numpy()
     h = cc.setup(pkg.DenseCRFHIP, pb)
-    gu, gw = _backward(h, 0, 1.0, G, 2)
+    gu, gw = gs.backward(h, 0, 1.0, G, 2)
     assert np.all(gw == 0)
-    assert _rel(gu, -(P0 * (G - (G * P0).sum(1, keepdims=True)))) <= GRAD_TOL
+    assert gs.rel(gu, -(P0 * (G - (G * P0).sum(1, keepdims=True)))) <= gs.GRAD_TOL
     h.close()
     # a CRF without pairwise terms: the weight gradient is empty, the unary gradient still exact to the bar
     gen = wl.generic_problem(300, [2], 5, seed=3)
@@ -238,9 +123,9 @@ def test_t0_is_the_softmax_backward_and_k0_works(po, wl):
     h0.set_unary(gen["unary"])
     G5 = np.random.default_rng(6).standard_normal((300, 5))
     for T, relax in ((5, 1.0), (3, 0.7)):
-        gu, _ = _backward(h0, T, relax, G5, 0)
+        gu, _ = gs.backward(h0, T, relax, G5, 0)
         ref_u, _ = mf.gradients(gen["unary"].astype(np.float64), np.zeros(0), [], T, relax, G5)
-        assert _rel(gu, ref_u) <= GRAD_TOL
+        assert gs.rel(gu, ref_u) <= gs.GRAD_TOL
         h0.inference(T, False, relax)
         o0 = po.OracleCRF(300, 5)
         o0.set_unary(gen["unary"])
@@ -252,16 +137,16 @@ def test_t0_is_the_softmax_backward_and_k0_works(po, wl):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["c2", "generic:d3_L21", "large:c5", "K8_L33", "K8_L64"])
 def test_backward_is_deterministic_and_leaves_the_inference_state(po, wl, golden, name):
-    pb, image = _case(name, golden, po, wl)
+    pb, image = cc.case(name, golden, po, wl)
     K = len(pb["kernels"])
     G = np.random.default_rng(9).standard_normal((pb["N"], pb["L"]))
-    h, keep = _gpu_handle(pb, image)
+    h, keep = gs.gpu_handle(pb, image)
     T, relax = 5, 0.7
     h.inference(T, False, relax)
     q_before = h.probability()
-    a = _backward(h, T, relax, G, K)
+    a = gs.backward(h, T, relax, G, K)
     q_after = h.probability()
-    b = _backward(h, T, relax, G, K)
+    b = gs.backward(h, T, relax, G, K)
     assert cc.same_bits(a[0], b[0]) and cc.same_bits(a[1], b[1])
     assert cc.same_bits(q_after, q_before)                      # Q is what inference(T, 0, relax) leaves
     o = cc.setup(po.OracleCRF, pb)
@@ -271,8 +156,8 @@ def test_backward_is_deterministic_and_leaves_the_inference_state(po, wl, golden
     o.inference_native(T, True, relax)
     assert cc.same_bits(h.probability(), o.probability()) and np.array_equal(h.map(), o.map())
     # a fresh handle whose first call is the backward gives the same bits
-    h2, keep2 = _gpu_handle(pb, image)
-    c = _backward(h2, T, relax, G, K)
+    h2, keep2 = gs.gpu_handle(pb, image)
+    c = gs.backward(h2, T, relax, G, K)
     assert cc.same_bits(a[0], c[0]) and cc.same_bits(a[1], c[1])
     assert cc.same_bits(h2.probability(), q_before)
     h.close(), h2.close()
@@ -302,17 +187,10 @@ def test_set_pairwise_weight_equals_a_fresh_handle(po, wl, prepared):
         assert np.array_equal(h.map(), o.map())
         if rnd == 0:                                             # round two: lattices in HBM behind a backward
             G = np.random.default_rng(3).standard_normal((pb["N"], 2))
-            _backward(h, 2, 1.0, G, 2)
+            gs.backward(h, 2, 1.0, G, 2)
             h.set_pairwise_weight(0, 99.0)
             h.set_pairwise_weight(0, new[0])
     h.close(), fresh.close()
-
-
-def _hip_malloc(nbytes):
-    lib = C.CDLL("libamdhip64.so")
-    p = C.c_void_p()
-    assert lib.hipMalloc(C.byref(p), C.c_size_t(nbytes)) == 0
-    return lib, p
 
 
 @pytest.mark.gpu
@@ -325,7 +203,7 @@ def test_backward_argument_checks_leave_the_handle_usable(po, wl):
     gu = torch.zeros((2000, 2), device="cuda")
     gw = torch.zeros(2, device="cuda")
     host = np.zeros((2000, 2), np.float32)
-    hl, small = _hip_malloc(64)
+    hl, small = hip_malloc(64)
     try:
         vp = C.c_void_p
         for args in ((1, 1.0, None, vp(gu.data_ptr()), None),                      # NULL
@@ -338,7 +216,7 @@ def test_backward_argument_checks_leave_the_handle_usable(po, wl):
             assert L.lccrf_inference_backward(h.h, *args) == -1, args
         assert L.lccrf_set_pairwise_weight(h.h, 2, 1.0) == -1
         assert L.lccrf_set_pairwise_weight(h.h, -1, 1.0) == -1
-        hl2, small4 = _hip_malloc(4)
+        hl2, small4 = hip_malloc(4)
         assert L.lccrf_inference_backward(h.h, 1, 1.0, vp(g.data_ptr()), vp(gu.data_ptr()), small4) == -1   # [K] undersized
         hl2.hipFree(small4)
         h0 = pkg.DenseCRFHIP(2000, 2)                            # no unary yet
@@ -366,7 +244,7 @@ def test_torch_layer_matches_the_c_abi_and_streams(wl):
     h = cc.setup(pkg.DenseCRFHIP, pb)
     U = h.unary()
     G = np.random.default_rng(2).standard_normal((pb["N"], 2)).astype(np.float32)
-    ref_u, ref_w = _backward(h, 5, 0.7, G, 2)
+    ref_u, ref_w = gs.backward(h, 5, 0.7, G, 2)
     h.inference(5, False, 0.7)
     ref_q = h.probability()
 

@@ -123,10 +123,9 @@ def test_batch_pose_after_a_run_with_a_fallback_frame_and_extra_edges(po, wl):
     CRF skipped (observs == 0, Tracking.cc:1857-1859) ride behind the CRF's points and count as static."""
     import torch
     import crf_cases as cc
-    from test_hip_parity import _shaped_problem
     F, N, NX = 3, 1200, 100                               # NX extra non-CRF edges per frame
     dev = torch.device("cuda", 0)
-    pbs = [wl.slam_problem(N, seed=400), _shaped_problem(wl, N, "sparse", seed=5), wl.slam_problem(N, seed=402)]
+    pbs = [wl.slam_problem(N, seed=400), cc.shaped_problem(wl, N, "sparse", seed=5), wl.slam_problem(N, seed=402)]
     scenes = [wl.pose_scene(N + NX, seed=650 + f) for f in range(F)]
     maxN = N + NX
     feats = [np.zeros((F, maxN, 2), np.float32) for _ in range(2)]
