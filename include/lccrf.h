@@ -336,9 +336,10 @@ int  lccrf_inference_backward_features(lccrf_handle h, int n_iterations, float r
  * with the matrices) and lccrf_inference_backward_compat.  While any term of a handle has a matrix, inference runs on the streaming
  * engine -- the one-launch frame kernel and the fused engine hard-wire Potts -- with the matrix applied inside the slice kernel,
  * which takes the Potts slice kernel's place: the step issues no launch more than the streaming engine's general, L-label step
- * (at L = 2 that is more than the two-label specialisation issues).  Not covered: the batch API has no setter;
- * lccrf_inference_backward_features on a handle with any matrix returns LCCRF_E_STATE and leaves the handle as it was; the C++
- * mirrors (lccrf_densecrf.hpp, lccrf_densecrf_gpu.hpp) are unchanged.                                                          */
+ * (at L = 2 that is more than the two-label specialisation issues).  Not covered: the batch API has no setter; the C++
+ * mirrors (lccrf_densecrf.hpp, lccrf_densecrf_gpu.hpp) are unchanged.  lccrf_inference_backward_features itself still returns
+ * LCCRF_E_STATE on a handle with any matrix and leaves the handle as it was: the feature gradients of such a handle are
+ * lccrf_inference_backward_all's (section 1f).                                                                                 */
 
 /* compat: HOST [L][L], row-major (row = the label that receives, column = the label of the filtered distribution), copied during
  * the call and uploaded on the handle's stream; NULL removes the matrix (the term is Potts again).  Entries must be finite and
@@ -370,6 +371,42 @@ int  lccrf_get_pairwise_compatibility(lccrf_handle h, int kernel, float *compat_
  *     lccrf_inference_backward on a handle with a matrix takes the same area.  Allocated as section 1c's.                      */
 int  lccrf_inference_backward_compat(lccrf_handle h, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
                                      float *d_grad_weights, float *d_grad_compat);
+
+/* ======================================================================================
+ * 1f. Everything at once: the gradients of inference() with respect to the unary, the weights, the FEATURES and the MATRICES of a
+ *     handle whose terms may carry label-compatibility matrices, from one replay and one sweep -- what a CRF-as-RNN layer with
+ *     learnt kernel bandwidths AND a learnt compatibility transform needs (lc-crf-slam_amd/autograd.py: mean_field_learned,
+ *     LearnedCRF).  Added WITHOUT a step of LCCRF_ABI_VERSION (it stays 3): probe for it by symbol.
+ *
+ * The gradients of lccrf_inference(h, n_iterations, -, relax) on the handle's current unary, terms and matrices.  With the notation
+ * of sections 1c - 1e, Phi~_k = Phi_k(Q_{t-1}) and mu_k the term's matrix (I for a Potts term), dL/dU, dL/dw_k, dL/dmu_k and G_{t-1}
+ * are section 1e's, and section 1d's formulas hold with two replacements:
+ *      upstream row of the corner dots:   y = n_k . (mu_k^T gamma_t)                        in place of n_k . gamma_t
+ *          g_b[k][i][c] += alpha_k w_k (<y_i, (B S Q_{t-1})[v_ic]> + <Q_{t-1},i, (B^T S y)[v_ic]>)
+ *      norm adjoint:                      g_n[k][i] += w_k <gamma_t,i, (mu_k Phi~_k)_i>     in place of w_k <gamma_t,i, Phi~_k,i>
+ * where (mu_k Phi~_k)_i[l] is the forward's own per-label sum, s = 0; s = s + mu[l][l'] * t[l'], l' = 0 .. L-1 (section 1e), and the
+ * dot over l adds the labels in order 0 .. L-1.  The norm part after the loop (a_k = -n_k^2 . g_n[k]) and the map from dL/db to dL/df
+ * are section 1d's, unchanged.  At n_iterations = 0 dL/df and dL/dmu are exactly 0.
+ *
+ * d_grad_features: HOST array of K device pointers, [N][d_k] each, overwritten; entries, or the array itself, may be NULL (that
+ * term's feature gradient and its extra launches are skipped; the other outputs' bits do not change).  d_grad_compat: DEVICE
+ * [K][L][L], overwritten, or NULL; for a term without a matrix it is the derivative at mu_k = I.  d_grad_unary and d_grad_weights
+ * may be NULL.  On a handle with a matrix dL/dU, dL/dw and dL/dmu are, bit for bit, lccrf_inference_backward_compat's, and with
+ * d_grad_features == NULL the call is that call.  On a handle without matrices and with d_grad_compat == NULL every output is, bit
+ * for bit, lccrf_inference_backward_features's.  (Explicit identity matrices take the compatibility form: dL/df then agrees with the
+ * Potts handle's to rounding, not by contract to the bit.)  Everything else is the contract of sections 1c - 1e: self-contained (the
+ * forward is replayed), device arrays checked as in section 1b before anything is enqueued, on the handle's stream, no float atomics
+ * and the same bits from run to run (every g_b, g_n and partial of dL/dmu keeps its one owner and its order of additions), Q
+ * afterwards as lccrf_inference(h, T, 0, relax) leaves it, the same errors, a rejected call leaves the handle as it was, frames in
+ * locality mode are re-built the plain way and return results in the caller's point order.  K = 0 is legal.
+ *   - Launches: per iteration and term, the one kernel section 1e adds to section 1c and the two corner-dot kernels section 1d
+ *     adds -- the slice-side one between that kernel (which leaves n_k . (mu_k^T gamma_t) where Phi~_k was) and the transposed
+ *     filter; after the loop section 1d's norm part per term and section 1e's one reduction.
+ *   - Memory: the union of the areas of sections 1d and 1e,
+ *     4 * (N4*L*(T + K + 2) + max(T,1)*K*B + K*C*L*L + sum over the terms asked for of N4*(d_k + 2)) bytes, plus 4 * N4*L when
+ *     d_grad_unary is NULL (N = 2000, L = 2, K = 2 of d = 2, T = 5: 144 KB + 0.3 KB + 64 KB = 209 KB).  Allocated as section 1c's. */
+int  lccrf_inference_backward_all(lccrf_handle h, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
+                                  float *d_grad_weights, float *const *d_grad_features, float *d_grad_compat);
 
 /* ======================================================================================
  * 2. Batch API -- many independent frames in flight on one GPU.

@@ -121,6 +121,7 @@ def lib():
     L.lccrf_set_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p]
     L.lccrf_get_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p, C.POINTER(C.c_int)]
     L.lccrf_inference_backward_compat.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, vp]
+    L.lccrf_inference_backward_all.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, C.POINTER(vp), vp]
     L.lccrf_batch_create.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(BatchDesc)]
     L.lccrf_batch_destroy.argtypes = [vp]
     L.lccrf_batch_destroy.restype = None
@@ -392,6 +393,14 @@ class DenseCRFHIP:
         inference_backward_device); d_grad_unary / d_grad_weights may then be None."""
         _check(lib().lccrf_inference_backward_compat(self.h, int(n_iterations), float(relax), _addr(d_grad_prob),
                                                      _addr(d_grad_unary), _addr(d_grad_weights), _addr(d_grad_compat)))
+
+    # -- features and matrices in one sweep (include/lccrf.h section 1f) ----------------------------------------------------------
+    def inference_backward_all_device(self, n_iterations, relax, d_grad_prob, d_grad_unary=None, d_grad_weights=None,
+                                      d_grad_features=None, d_grad_compat=None):
+        """inference_backward_device plus dL/d features and dL/dmu of the forward with the handle's matrices: d_grad_features as
+        inference_backward_features_device takes it, d_grad_compat as inference_backward_compat_device; any output may be None."""
+        _check(lib().lccrf_inference_backward_all(self.h, int(n_iterations), float(relax), _addr(d_grad_prob), _addr(d_grad_unary),
+                                                  _addr(d_grad_weights), _addr_list(d_grad_features), _addr(d_grad_compat)))
 
     # -- results -----------------------------------------------------------------------
     def map(self):

@@ -1,4 +1,4 @@
-"""torch autograd through DenseCRF::inference on the HIP path (include/lccrf.h sections 1c, 1d, 1e and 2c).
+"""torch autograd through DenseCRF::inference on the HIP path (include/lccrf.h sections 1c - 1f and 2c).
 
     Q = mean_field(crf, unary, weights, n_iterations=5, relax=1.0)
     Q.backward(g)      # -> unary.grad = dL/dU, weights.grad = dL/dw
@@ -11,6 +11,9 @@
 
     Q = mean_field_compat(crf, unary, weights, compat, n_iterations=5, relax=1.0)             # a [K, L, L] label compatibility
     Q.backward(g)      # -> also compat.grad = dL/dmu (section 1e); CompatMeanFieldCRF learns it, starting from the Potts model
+
+    Q = mean_field_learned(unary, [f_0, f_1, ..], weights, compat, n_iterations=5, relax=1.0)   # features and matrices together
+    Q.backward(g)      # -> unary.grad, weights.grad, f_k.grad and compat.grad from one sweep (section 1f); LearnedCRF learns both
 
 `crf` is a DenseCRFHIP whose pairwise terms are already added (their features fix the lattices; only the weights are
 inputs here).  Forward: lccrf_set_pairwise_weight + lccrf_set_unary_device + lccrf_inference.  Backward:
@@ -244,24 +247,36 @@ class BatchMeanFieldCRF(torch.nn.Module):
         self.batch.close()
 
 
+def _forward_on_own_handle(unary, features, weights, compat, n_iterations, relax, device):
+    """The forward of mean_field_features and mean_field_learned: the lattices depend on the features, so a handle per forward
+    (lccrf_create re-uses parked handles), which the backward closes.  compat: [K, L, L] or None (Potts terms).
+    Returns (handle, Q, the detached unary, the detached features)."""
+    _check_unary_weights(unary, None, weights, len(features))
+    N, L = (int(x) for x in unary.shape)
+    for f in features:
+        if not f.is_cuda or f.dtype != torch.float32 or f.dim() != 2 or int(f.shape[0]) != N:
+            raise ValueError("every feature array must be a float32 GPU tensor of shape [%d, d_k]" % N)
+    if compat is not None and (compat.dtype != torch.float32 or tuple(compat.shape) != (len(features), L, L)):
+        raise ValueError("compat must be a float32 tensor of shape [%d, %d, %d]" % (len(features), L, L))
+    _check_iterations(n_iterations)
+    u = unary.detach().contiguous()
+    fs = [f.detach().contiguous() for f in features]
+    crf = _pkg.DenseCRFHIP(N, L, device=device)
+    with _on_stream(crf.stream(), u.device) as (ext, cur):
+        crf.set_unary_device(u.data_ptr())
+        for f, w in zip(fs, weights.detach().cpu().tolist()):
+            crf.add_pairwise_device(f.data_ptr(), int(f.shape[1]), w)
+        if compat is not None:
+            for k, m in enumerate(compat.detach().cpu().numpy()):
+                crf.set_pairwise_compatibility(k, m)
+        q = _forward_q(crf, u, n_iterations, relax, ext, cur)
+    return crf, q, u, fs
+
+
 class _MeanFieldFeatures(torch.autograd.Function):
     @staticmethod
     def forward(ctx, unary, weights, n_iterations, relax, device, *features):
-        _check_unary_weights(unary, None, weights, len(features))
-        N, L = (int(x) for x in unary.shape)
-        for f in features:
-            if not f.is_cuda or f.dtype != torch.float32 or f.dim() != 2 or int(f.shape[0]) != N:
-                raise ValueError("every feature array must be a float32 GPU tensor of shape [%d, d_k]" % N)
-        _check_iterations(n_iterations)
-        u = unary.detach().contiguous()
-        fs = [f.detach().contiguous() for f in features]
-        # the lattices depend on the features: a handle per forward (lccrf_create re-uses parked handles), closed by the backward
-        crf = _pkg.DenseCRFHIP(N, L, device=device)
-        with _on_stream(crf.stream(), u.device) as (ext, cur):
-            crf.set_unary_device(u.data_ptr())
-            for f, w in zip(fs, weights.detach().cpu().tolist()):
-                crf.add_pairwise_device(f.data_ptr(), int(f.shape[1]), w)
-            q = _forward_q(crf, u, n_iterations, relax, ext, cur)
+        crf, q, u, fs = _forward_on_own_handle(unary, features, weights, None, n_iterations, relax, device)
         ctx.crf, ctx.n_iterations, ctx.relax = crf, int(n_iterations), float(relax)
         ctx.weights_device = weights.device
         ctx.save_for_backward(u, *fs)
@@ -339,6 +354,58 @@ class LearnedKernelCRF(torch.nn.Module):
 
     def forward(self, unary):
         return mean_field_features(unary, self.features(), self.weights, self.n_iterations, self.relax, self.device)
+
+
+class _MeanFieldLearned(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, unary, weights, compat, n_iterations, relax, device, *features):
+        crf, q, u, fs = _forward_on_own_handle(unary, features, weights, compat, n_iterations, relax, device)
+        ctx.crf, ctx.n_iterations, ctx.relax = crf, int(n_iterations), float(relax)
+        ctx.weights_device, ctx.compat_device = weights.device, compat.device
+        ctx.save_for_backward(u, *fs)
+        return q
+
+    @staticmethod
+    def backward(ctx, grad_q):
+        u, fs = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        crf = ctx.crf
+        if crf is None:
+            raise RuntimeError("mean_field_learned: backward a second time (the handle is closed by the first)")
+        dev, K, L = u.device, len(fs), int(u.shape[1])
+        g = _grad_in(grad_q, dev)
+        need = ctx.needs_input_grad
+        grad_u = torch.empty_like(u)
+        grad_w, grad_w_ptr = _grad_w_buffer(K, dev)
+        grad_m = torch.zeros((max(K, 1), L, L), dtype=torch.float32, device=dev)
+        grad_f = [torch.empty_like(f) if need[6 + k] else None for k, f in enumerate(fs)]
+        with _on_stream(crf.stream(), dev):                   # (the handle still holds this forward's unary, weights and matrices)
+            crf.inference_backward_all_device(ctx.n_iterations, ctx.relax, g.data_ptr(), grad_u.data_ptr(), grad_w_ptr,
+                                              [t.data_ptr() if t is not None else None for t in grad_f], grad_m.data_ptr())
+        crf.synchronize()                                     # (the handle goes back to the cache: nothing of this call may be in flight)
+        crf.close()
+        ctx.crf = None
+        return (grad_u, _grad_w_result(grad_w, K, ctx.weights_device), grad_m[:K].to(ctx.compat_device), None, None, None) + tuple(grad_f)
+
+
+def mean_field_learned(unary, features, weights, compat, n_iterations=5, relax=1.0, device=0):
+    """mean_field_features with a label-compatibility matrix per term (include/lccrf.h section 1f): `compat` [K, L, L] (float32,
+    any device), term k adding w_k * norm_k * (Phi_k(Q) @ compat[k].T); differentiable in unary, features, weights and compat, all
+    four from one reverse sweep.  Every forward builds the lattices afresh on a handle of its own, which its backward closes: one
+    backward per forward."""
+    return _MeanFieldLearned.apply(unary, weights, compat, n_iterations, relax, device, *features)
+
+
+class LearnedCRF(LearnedKernelCRF):
+    """LearnedKernelCRF whose terms also carry a learnt label-compatibility matrix: parameters log_sd[k], `weights` [K] and `compat`
+    [K, n_labels, n_labels], the latter initialised to identities (the Potts model).  sd and groups as LearnedKernelCRF takes them.
+    forward(unary [N, n_labels]) -> Q [N, n_labels] through mean_field_learned."""
+
+    def __init__(self, raw_features, sd, weights, groups=None, n_labels=2, n_iterations=5, relax=1.0, device=0):
+        super().__init__(raw_features, sd, weights, groups, n_iterations, relax, device)
+        self.compat = torch.nn.Parameter(torch.eye(int(n_labels), dtype=torch.float32).repeat(len(weights), 1, 1))
+
+    def forward(self, unary):
+        return mean_field_learned(unary, self.features(), self.weights, self.compat, self.n_iterations, self.relax, self.device)
 
 
 class _MeanFieldCompat(torch.autograd.Function):

@@ -1,4 +1,4 @@
-// api_backward.hip -- gradients of mean-field inference: sections 1c, 1d and 1e (a handle) and 2c, 2d (a batch) of include/lccrf.h.
+// api_backward.hip -- gradients of mean-field inference: sections 1c - 1f (a handle) and 2c, 2d (a batch) of include/lccrf.h.
 //
 // One path behind every entry point (backward_call); the replay and the sweep themselves are Engine::backward (host_engine.hip) and
 // meanfield_backward.hip.
@@ -8,7 +8,7 @@
 
 using namespace lccrf;
 
-// Every backward entry point, of a handle (sections 1c - 1e) and of a batch (2c, 2d), fills a BackwardRequest (engine.h), says where
+// Every backward entry point, of a handle (sections 1c - 1f) and of a batch (2c, 2d), fills a BackwardRequest (engine.h), says where
 // it runs and what it allows, and calls backward_call.  A handle is a batch of one whose area has its own row stride.
 struct BackwardTarget {
     Engine &e;
@@ -102,6 +102,20 @@ int lccrf_inference_backward_compat(lccrf_handle h, int n_iterations, float rela
     BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
     rq.grad_compat = d_grad_compat;
     rq.compat_form = true;
+    return backward_call(backward_target(h), rq, kGradUnaryOptional);
+}
+
+// --------------------------------------------------------------------------------------
+// section 1f: ... and with respect to the features and the matrices in one sweep
+
+int lccrf_inference_backward_all(lccrf_handle h, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
+                                 float *d_grad_weights, float *const *d_grad_features, float *d_grad_compat)
+{
+    CHECK_H(h);
+    BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
+    rq.grad_features = d_grad_features;
+    rq.grad_compat = d_grad_compat;
+    rq.compat_form = h->eng.n_compat > 0 || d_grad_compat;
     return backward_call(backward_target(h), rq, kGradUnaryOptional);
 }
 

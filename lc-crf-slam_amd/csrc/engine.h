@@ -208,7 +208,7 @@ void launch_stage_features(float *dst, const void *src, int n, int d, int mode, 
 // out[f] = clamp(in[f], 0, maxN); *bad (pinned host memory) is set to 1 if anything had to be clamped
 void launch_validate_npoints(const int *in, int *out, int F, int maxN, int *bad, hipStream_t s);
 
-// ---- mean-field backward (csrc/meanfield_backward.hip; include/lccrf.h sections 1c - 1e and 2c - 2d) ------------------------
+// ---- mean-field backward (csrc/meanfield_backward.hip; include/lccrf.h sections 1c - 1f and 2c - 2d) ------------------------
 // One backward call, of a handle or of a batch (F frames of up to `rows` points; a handle is a batch of one): what every
 // lccrf_*inference_backward* entry point fills in and hands to the one path behind them (api_backward.hip: backward_call).
 struct BackwardRequest {           // (an aggregate: the members left out of a braced list are null / false)
@@ -218,7 +218,7 @@ struct BackwardRequest {           // (an aggregate: the members left out of a b
     float *grad_unary;              // [F][rows][L] or null: dL/dU is then formed in the area (BackwardArea::gU)
     float *grad_weights;            // [F][K] or null
     float *const *grad_features;    // null, or K pointers, [F][rows][d_k] each or null (sections 1d / 2d)
-    float *grad_compat;             // [K][L][L] or null (section 1e; F = 1)
+    float *grad_compat;             // [K][L][L] or null (sections 1e / 1f; F = 1)
     bool compat_form;               // the sweep takes section 1e's form: the terms' matrices are honoured (grad_compat needs it)
 };
 // The area of one backward call, owned by the engine and zeroed when allocated: Q_0 .. Q_{T-1} of the replay, one [F][.][L] array
@@ -257,6 +257,7 @@ size_t backward_layout(const BackwardRequest &rq, const CrfDev &c, const KernelD
 // request says.  Without feature gradients and compat_form the launches are those of sections 1c / 2c.
 // compat (or null): K device pointers, the terms' [L][L] matrices or null, read with rq.compat_form only -- the sweep then takes
 // section 1e's form (one k_compat_bwd launch per iteration and term more) and rq.grad_compat, if given, is overwritten.
+// compat_form and grad_features together are section 1f: section 1e's form plus the launches section 1d adds.
 void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int rows, const BackwardRequest &rq,
                            const BackwardArea &ar, const float *const *compat, hipStream_t s);
 

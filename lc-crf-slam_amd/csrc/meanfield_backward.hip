@@ -26,6 +26,10 @@
 // of the one-workgroup build never reach HBM).  Every g_b[i][c] has one owner and one order of additions (t = T .. 1, slice side,
 // splat side; the norm part last): the same bits from run to run, and for a frame of a batch those of a handle.
 //
+// Both parts together (section 1f): the sweep takes section 1e's form and adds section 1d's launches to it.  Per (t, k) the slice-side
+// k_corner_dot runs after k_compat_bwd has turned phi_k into mu_k^T (n_k gamma_t) and before the transposed filter overwrites it; the
+// splat side runs on the transposed filter's values as before, and g_n is formed from mu_k Phi_k (k_joint_softmax<G>).
+//
 // Rows at or beyond n_points[f] (the phantom points of quirk Q1 among them) are never read: every lattice build lists real points
 // only in its splat rows (k_csr_count / k_eoffsets in stream_build.hip, E = N (d+1) in build_small.hip), the slice writes rows
 // i < n_points[f] only, and the kernels below stop at n_points[f].  A batch rebound with fewer points than an earlier call leaves
@@ -65,7 +69,7 @@ struct BwdArgs {
     float *gam;                  // ... and [F][maxN][L]: receives gamma_t (phi is left as it came: k_compat_bwd turns it over)
 };
 
-enum { kBwdPlain = 0, kBwdFeat = 1, kBwdCompat = 2 };   // what k_softmax_bwd does besides section 1c's work
+enum { kBwdPlain = 0, kBwdFeat = 1, kBwdCompat = 2, kBwdCompatFeat = 3 };   // what k_softmax_bwd does besides section 1c's work (bits: feature, compat)
 
 // lanes per row: one row per lane up to 4 labels, then four labels per lane over a power-of-two group of lanes
 inline int bwd_lanes(int L) { return L <= 4 ? 1 : L <= 8 ? 2 : L <= 16 ? 4 : L <= 32 ? 8 : 16; }
@@ -108,13 +112,15 @@ __device__ __forceinline__ float row_sum_ordered(const float (&v)[4], int L, int
 // k_compat_softmax<G> (kBwdCompat, section 1e): a term with a matrix enters x and the weight dot as mu_k Phi_k -- per label l the forward's own sum
 // s = 0; s = s + mu[l][l'] * Phi[l'], l' = 0 .. L-1 (k_slice_compat) -- gamma_t goes to a.gam and phi stays Phi_k(Q_{t-1}):
 // k_compat_bwd needs both for dL/dmu and writes the transposed filter's input itself.
+// k_joint_softmax<G> (kBwdCompatFeat, section 1f: k_compat_softmax<G> with the feature part, under a name of its own) does both -- gn[k][i] += w_k * <gam_i, (mu_k Phi_k)_i>, the dot formed from the row sums
+// mu_k Phi_k this kernel has anyway (Phi_k itself for a Potts term), accumulated as k_softmax_bwd<G, true> does; nothing else changes.
 // mu is read from global memory here, L x 4 loads per lane and term, all lanes of a wavefront within a few rows of one matrix of
 // at most 16 KB (cache hits after the first touch): up to eight matrices do not fit this kernel's LDS next to each other, and
 // staging them one by one would put 2 K barriers into a kernel whose rows are otherwise independent.
 template <int G, int MODE>
 __device__ __forceinline__ void softmax_bwd(const BwdArgs &a)
 {
-    constexpr bool FEAT = MODE == kBwdFeat, COMPAT = MODE == kBwdCompat;
+    constexpr bool FEAT = (MODE & kBwdFeat) != 0, COMPAT = (MODE & kBwdCompat) != 0;
     const int f = blockIdx.y;
     const int N = a.n_points[f], L = a.L, K = a.K;
     const int lane = threadIdx.x & 63;
@@ -260,6 +266,12 @@ __global__ void __launch_bounds__(kBwdBlock) k_compat_softmax(BwdArgs a)
     softmax_bwd<G, kBwdCompat>(a);
 }
 
+template <int G>
+__global__ void __launch_bounds__(kBwdBlock) k_joint_softmax(BwdArgs a)
+{
+    softmax_bwd<G, kBwdCompatFeat>(a);
+}
+
 // G = keep * G + sum_k w_k * buf_k, element by element (keep = 1 - relax); frame blockIdx.y
 __global__ void __launch_bounds__(kBwdBlock) k_bwd_combine(const int *__restrict__ n_points, int L, int K, const float *__restrict__ buf,
                                                          size_t slice, size_t fs, BwdWeights wk, float keep, float *__restrict__ G)
@@ -303,7 +315,8 @@ void launch_softmax_bwd(const BwdArgs &a, int F, hipStream_t s)
     const dim3 grid((unsigned)std::max(backward_blocks(a.rows, a.L), 1), (unsigned)F);
     with_bwd_lanes(a.L, [&](auto lanes) {
         constexpr int G = decltype(lanes)::value;
-        if constexpr (MODE == kBwdCompat) k_compat_softmax<G><<<grid, kBwdBlock, 0, s>>>(a);
+        if constexpr (MODE == kBwdCompatFeat) k_joint_softmax<G><<<grid, kBwdBlock, 0, s>>>(a);
+        else if constexpr (MODE == kBwdCompat) k_compat_softmax<G><<<grid, kBwdBlock, 0, s>>>(a);
         else k_softmax_bwd<G, MODE == kBwdFeat><<<grid, kBwdBlock, 0, s>>>(a);
     });
 }
@@ -620,16 +633,18 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
         a.relax = relax;
         a.first = t == T;
         a.partial = K ? ar.partial + (size_t)(t - 1) * K * F * nblk : nullptr;
-        // (first uses in the order compat, plain, feature: the order of the kernels' instantiation, and so of the code object)
-        if (cmode) launch_softmax_bwd<kBwdCompat>(a, F, s);
+        // (first uses in the order compat, plain, feature, both: the order of the kernels' instantiation, and so of the code object)
+        if (cmode && !feat) launch_softmax_bwd<kBwdCompat>(a, F, s);
         else if (!feat) launch_softmax_bwd<kBwdPlain>(a, F, s);
-        else launch_softmax_bwd<kBwdFeat>(a, F, s);
+        else if (!cmode) launch_softmax_bwd<kBwdFeat>(a, F, s);
+        else launch_softmax_bwd<kBwdCompatFeat>(a, F, s);
         for (int k = 0; k < K; ++k) {
             if (cmode) {                                   // phi_k: Phi_k(Q_{t-1}) -> mu_k^T (n_k gamma_t); dL/dmu_k's partials
                 CompatArgs ca{c.n_points, L, t == T, c.maxN, fs, ar.gam, kds[k].norm, ar.phi + k * slice, a.compat[k], kds[k].w,
                               grad_compat ? ar.cpart + (size_t)k * F * cblk * L * L : nullptr};
                 k_compat_bwd<<<dim3((unsigned)cblk, (unsigned)F), kBwdBlock, 0, s>>>(ca);
             }
+            // (section 1f: the slice side's upstream row is what k_compat_bwd has just left in phi_k, n_k (mu_k^T gamma_t))
             const float cs = kds[k].alpha * kds[k].w;
             if (gf[k]) launch_corner_dot(kds[k], c, rows, L, ar.phi + k * slice, fs, val[k], cs, ar.gb[k], s);    // slice side
             const float *valt;                             // (B^T S n_k gamma_t)

@@ -1,0 +1,164 @@
+"""The checker of lccrf_inference_backward_all (include/lccrf.h section 1f) and what its tests share.
+
+The checker is tests/compat_checker.py's forward_f64 run over tests/meanfield_f64_features.py's FeatureLattice lattices bound to
+feature tensors that require gradients: torch autograd gives (dL/dU, dL/dw, dL/dmu, [dL/df_k]) in float64 and, with
+dtype=torch.float32, in single precision.  The bar every output is held to is that of the sections it joins: relative L2 error
+against the float64 checker <= max(GRAD_TOL, 10 x the float32 checker's error), with the floors of assert_matches_compat_checker
+(dL/dU, dL/dw, dL/dmu) and assert_features_match_checker (dL/df).  Not product code."""
+import numpy as np
+import torch
+
+import compat_checker as ck
+import crf_cases as cc
+import feature_cases as fc
+import grad_support as gs
+import meanfield_f64_features as mff
+from abi_support import dev
+
+D = torch.float64
+
+
+def dense(K, L, seed=77):
+    """I + 0.3 N(0, 1), seeded: the matrices of the section 1e tests"""
+    rng = np.random.default_rng([seed, K, L])
+    return [(np.eye(L) + 0.3 * rng.standard_normal((L, L))).astype(np.float32) for _ in range(K)]
+
+
+def eyes(K, L):
+    return [np.eye(L, dtype=np.float32) for _ in range(K)]
+
+
+def checker_mu(mats, L):
+    """[K, L, L] float64 for the checker: a term without a matrix is the identity (its dL/dmu is the derivative there)"""
+    return np.stack([np.eye(L) if m is None else np.asarray(m, np.float64) for m in mats]) if len(mats) else np.zeros((0, L, L))
+
+
+def checker(po, pb):
+    """(oracle CRF, its FeatureLattice lattices, U as float64)"""
+    o = cc.setup(po.OracleCRF, pb)
+    return o, mff.lattices(o, pb), o.unary().astype(np.float64)
+
+
+def joint_gradients(U, w, mu, lats, n_iterations, relax, G, dtype=D):
+    """(dL/dU, dL/dw, dL/dmu, [dL/df_k]) of L = <G, Q_T> by autograd through compat_checker.forward_f64 over the lattices bound to
+    their own features, the topology fixed; float64 numpy arrays.  dtype=torch.float32: the same computation in single precision."""
+    t = lambda a: torch.as_tensor(np.asarray(a, np.float64)).to(dtype).clone().requires_grad_(True)
+    U, w, mu = t(U), t(w), t(mu)
+    fs = [t(lat.feat32) for lat in lats]
+    for lat, f in zip(lats, fs):
+        lat.bind(f)
+    Q = ck.forward_f64(U, w, mu, lats, n_iterations, relax)
+    (Q * torch.as_tensor(np.asarray(G, np.float64)).to(dtype)).sum().backward()
+    for lat in lats:                                             # leave the lattices bound to plain float64 features
+        lat.bind(torch.as_tensor(lat.feat32.astype(np.float64)))
+    z = lambda x: x.grad.double().numpy() if x.grad is not None else np.zeros(tuple(x.shape))
+    return z(U), z(w), z(mu), [z(f) for f in fs]
+
+
+def errors(got, ref, w, G):
+    """relative L2 error of (dL/dU, dL/dw, dL/dmu, [dL/df_k]) against `ref`, under the floors of the two sections' bars; an entry
+    of got[3] may be None (not asked for)"""
+    fl_u = 1e-6 * np.linalg.norm(G)
+    fl_w = fl_u * max(np.linalg.norm(w), 1.0)
+    return (gs.rel(got[0], ref[0], fl_u), gs.rel(got[1], ref[1], fl_w), gs.rel(got[2], ref[2], fl_w),
+            [None if a is None else gs.rel(a, r, fl_u) for a, r in zip(got[3], ref[3])])
+
+
+def bars_of(U, w, mu, lats, T, relax, G):
+    """(the float64 checker's gradients, the bars (dL/dU, dL/dw, dL/dmu, [dL/df_k]), the float32 checker's own errors)"""
+    ref = joint_gradients(U, w, mu, lats, T, relax, G)
+    f32 = errors(joint_gradients(U, w, mu, lats, T, relax, G, dtype=torch.float32), ref, w, G)
+    bar = lambda e: max(gs.GRAD_TOL, 10 * e)
+    return ref, (bar(f32[0]), bar(f32[1]), bar(f32[2]), [bar(e) for e in f32[3]]), f32
+
+
+def grad_prob(pb):
+    return np.random.default_rng(1234).standard_normal((pb["N"], pb["L"]))
+
+
+_REFS = {}
+
+
+def reference_for(po, wl, golden, name, T, relax, kind="dense"):
+    """What a (case, T, relax) setting is checked against, computed once and shared (leave it unchanged): the problem, its image,
+    the matrices handed to the handle (kind "dense": every term; "mixed": even terms only, the others Potts; "potts": none, the
+    checker at identities), G, the weights and the checker's gradients, bars and float32 errors."""
+    key = (name, T, relax, kind)
+    if key not in _REFS:
+        pb, image = fc.case(name, golden, po, wl)
+        K, L = len(pb["kernels"]), pb["L"]
+        mats = dense(K, L)
+        if kind != "dense":
+            mats = [m if k % 2 == 0 and kind == "mixed" else None for k, m in enumerate(mats)]
+        o, lats, U = checker(po, pb)
+        G = grad_prob(pb)
+        w = gs.weights(pb)
+        ref, bars, f32 = bars_of(U, w, checker_mu(mats, L), lats, T, relax, G)
+        o.close()
+        _REFS[key] = dict(pb=pb, image=image, mats=mats, G=G, w=w, ref=ref, bars=bars, f32=f32)
+    return _REFS[key]
+
+
+def dims_of(pb, image):
+    return [2, 5] if image is not None else [int(f.shape[1]) for f, _ in pb["kernels"]]
+
+
+def set_all(h, mats):
+    for k, m in enumerate(mats):
+        h.set_pairwise_compatibility(k, m)
+
+
+def backward_all(h, dims, L, T, relax, G, skip=(), unary=True, weights=True, compat=True, features=True):
+    """(dL/dU, dL/dw, dL/dmu, [dL/df_k or None]) from lccrf_inference_backward_all; every output pre-filled with NaN.  An output
+    that is not asked for (unary / weights / compat False, a term in skip, features False: a NULL array) comes back as filled."""
+    K, N = len(dims), G.shape[0]
+    g = dev(G.astype(np.float32))
+    gu = torch.full(G.shape, float("nan"), device="cuda")
+    gw = torch.full((max(K, 1),), float("nan"), device="cuda")
+    gm = torch.full((max(K, 1), L, L), float("nan"), device="cuda")
+    gf = [None if k in skip else torch.full((N, d), float("nan"), device="cuda") for k, d in enumerate(dims)]
+    torch.cuda.synchronize()
+    h.inference_backward_all_device(T, relax, g.data_ptr(), gu.data_ptr() if unary else None, gw.data_ptr() if K and weights else None,
+                                    [t.data_ptr() if t is not None else None for t in gf] if features else None,
+                                    gm.data_ptr() if compat else None)
+    h.synchronize()
+    return gu.cpu().numpy(), gw[:K].cpu().numpy(), gm[:K].cpu().numpy(), [t.cpu().numpy() if t is not None else None for t in gf]
+
+
+def backward_compat(h, K, L, T, relax, G):
+    """(dL/dU, dL/dw, dL/dmu) from lccrf_inference_backward_compat (section 1e); every output pre-filled with NaN"""
+    g = dev(G.astype(np.float32))
+    gu = torch.full(G.shape, float("nan"), device="cuda")
+    gw = torch.full((max(K, 1),), float("nan"), device="cuda")
+    gm = torch.full((max(K, 1), L, L), float("nan"), device="cuda")
+    torch.cuda.synchronize()
+    h.inference_backward_compat_device(T, relax, g.data_ptr(), gu.data_ptr(), gw.data_ptr() if K else None, gm.data_ptr())
+    h.synchronize()
+    return gu.cpu().numpy(), gw[:K].cpu().numpy(), gm[:K].cpu().numpy()
+
+
+def backward_features(h, dims, T, relax, G):
+    """(dL/dU, dL/dw, [dL/df_k]) from lccrf_inference_backward_features (section 1d); every output pre-filled with NaN"""
+    K, N = len(dims), G.shape[0]
+    g = dev(G.astype(np.float32))
+    gu = torch.full(G.shape, float("nan"), device="cuda")
+    gw = torch.full((max(K, 1),), float("nan"), device="cuda")
+    gf = [torch.full((N, d), float("nan"), device="cuda") for d in dims]
+    torch.cuda.synchronize()
+    h.inference_backward_features_device(T, relax, g.data_ptr(), gu.data_ptr(), gw.data_ptr() if K else None, [t.data_ptr() for t in gf])
+    h.synchronize()
+    return gu.cpu().numpy(), gw[:K].cpu().numpy(), [t.cpu().numpy() for t in gf]
+
+
+def assert_within_bars(got, r, name, T, relax):
+    """every output of `got` against the reference `r` (reference_for); prints one line of figures per setting first"""
+    err = errors(got, r["ref"], r["w"], r["G"])
+    bars = r["bars"]
+    flat = lambda e: list(e[:3]) + [x for x in e[3] if x is not None]
+    fmt = lambda e: "dL/dU %.3g dL/dw %.3g dL/dmu %.3g dL/df %s" % (e[0], e[1], e[2], " ".join("%.3g" % x for x in e[3] if x is not None))
+    print("relative L2 error %s T=%d relax=%g: %s (bars %s)" % (name, T, relax, fmt(err), fmt(bars)))
+    fb = list(bars[:3]) + [b for b, x in zip(bars[3], err[3]) if x is not None]
+    assert all(e <= b for e, b in zip(flat(err), fb)), (flat(err), fb)
+    if T == 0:
+        assert np.all(got[1] == 0) and np.all(got[2] == 0) and all(np.all(a == 0) for a in got[3] if a is not None)
+    return err
