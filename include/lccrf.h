@@ -409,6 +409,60 @@ int  lccrf_inference_backward_all(lccrf_handle h, int n_iterations, float relax,
                                   float *d_grad_weights, float *const *d_grad_features, float *d_grad_compat);
 
 /* ======================================================================================
+ * 1g. Normalisation modes -- where a pairwise term applies its norm n_k = 1 / (Phi_k(1) + 1e-20): AFTER the filter (the reference's
+ *     PottsPotential3D, pairwise3d.h:73-78, and the default), BEFORE it, SYMMETRICally (n^1/2 on either side: the form that keeps the
+ *     effective kernel symmetric, and the default of the dense-CRF formulation this code descends from), or not at all
+ *     (lc-crf-slam_amd/autograd.py: MeanFieldCRF / CompatMeanFieldCRF take `normalization`).  Added WITHOUT a step of
+ *     LCCRF_ABI_VERSION (it stays 3): probe for these two by symbol.
+ *
+ * Meaning.  n is the term's norm exactly as before (lccrf_get_norm is the same in every mode), s[i] = sqrtf(n[i]) correctly rounded:
+ *      mode         pre[i]    post[i]
+ *      AFTER        -         n[i]
+ *      BEFORE       n[i]      -
+ *      SYMMETRIC    s[i]      s[i]
+ *      NONE         -         -
+ * Arithmetic, in fp32 with every product and every sum rounded on its own (no FMA): the filter's input is x[i][l] = pre[i] * Q[i][l],
+ * rounded once (Q itself without a pre); t = Phi(x) is the unchanged splat, blur and slice; a term with a label-compatibility matrix
+ * turns t into section 1e's sum s = s + mu[l][l'] * t[l']; then next = base + (w * post[i]) * t with a post, next = base + w * t
+ * without one.  A term explicitly set to AFTER gives, bit for bit, what it gave before the call existed.
+ *
+ * Honoured by lccrf_inference (locality mode at >= 8192 points included: the factors follow the internal point order the norm
+ * has), lccrf_start_inference / lccrf_step_inference, lccrf_pairwise_apply / _device (the `apply` of that term is
+ * out += (w * post) * Phi(pre * in)), lccrf_inference_backward and lccrf_inference_backward_compat.  While any term of a handle is not
+ * AFTER, inference runs on the streaming engine's general L-label step, at L = 2 too -- exactly what a matrix of section 1e does:
+ * the pre factor is applied inside the splat where it loads its input (no launch more, no scaled copy of Q), the post factor is the
+ * array the slice reads in the norm's place.  Once every term is AFTER again the handle takes the fast engines and returns the bits
+ * it returned before.
+ *
+ * Gradients.  With a_k the term's post and b_k its pre, each 1 where the mode has none, and section 1e's notation:
+ *      x_t        = -U + sum_k w_k . a_k . (mu_k applied to Phi_k(b_k . Q_{t-1}))
+ *      dL/dw_k   += sum_{i,l} gamma_t . a_k . (mu_k Phi_k(b_k . Q_{t-1}))
+ *      dL/dmu_k  += sum_i w_k . gamma_t[i][l] . a_k[i] . Phi_k(b_k . Q_{t-1})[i][l']
+ *      G_{t-1}    = (1-r) G_t + sum_k w_k . b_k . Phi_k^T( a_k . (mu_k^T gamma_t) )
+ * Determinism, memory and the contracts "self-contained" and "Q afterwards as lccrf_inference leaves it" are those of sections 1c
+ * and 1e.  NOT differentiated: s and n with respect to the features -- lccrf_inference_backward_features, and
+ * lccrf_inference_backward_all with a non-NULL d_grad_features, return LCCRF_E_STATE on a handle with any term that is not AFTER and
+ * leave the handle as it was.
+ *
+ * Not covered: the batch API has no setter (sections 2c and 2d keep every term AFTER); the C++ mirrors (lccrf_densecrf.hpp,
+ * lccrf_densecrf_gpu.hpp) are unchanged.
+ *   - Memory: one [N] float array per SYMMETRIC term (s, formed from n on the handle's stream when first needed after a build or a
+ *     mode change) and one [N] array of 1.0f per handle with a BEFORE or NONE term (what the slice reads where such a term has no
+ *     post: w * 1.0f is exact); both stay with the handle.  Nothing is allocated for a handle that never calls the setter.      */
+typedef enum lccrf_normalization {
+    LCCRF_NORMALIZE_AFTER     = 0,   /* default: the reference, pairwise3d.h:73-78 */
+    LCCRF_NORMALIZE_BEFORE    = 1,
+    LCCRF_NORMALIZE_SYMMETRIC = 2,
+    LCCRF_NORMALIZE_NONE      = 3
+} lccrf_normalization;
+/* mode: an lccrf_normalization; LCCRF_E_INVALID for a NULL handle, a `kernel` that is not a term of the handle, or a mode outside
+ * 0 .. 3.  May be called before or after the lattices are built and between inferences: no lattice, norm or prepared launch record
+ * changes.  A handle from lccrf_create -- a recycled one too -- has every term at LCCRF_NORMALIZE_AFTER.                          */
+int  lccrf_set_pairwise_normalization(lccrf_handle h, int kernel, int mode);
+/* *mode = the lccrf_normalization of term `kernel`.  No device work.                                                             */
+int  lccrf_get_pairwise_normalization(lccrf_handle h, int kernel, int *mode);
+
+/* ======================================================================================
  * 2. Batch API -- many independent frames in flight on one GPU.
  *    Every frame is one CRF of the object API; frames never interact.  Inputs may be
  *    handed over as host buffers (uploaded) or bound as DEVICE pointers (zero copy), so

@@ -26,6 +26,7 @@ MAX_KERNELS = 8
 OPT_SINGLE_WORKGROUP = 1        # lccrf_option (include/lccrf.h)
 OPT_VERTEX_ORDER = 2
 IMAGE_NONE, IMAGE_U8, IMAGE_F32 = 0, 1, 2   # lccrf_add_image_kernel's image formats
+NORMALIZE_AFTER, NORMALIZE_BEFORE, NORMALIZE_SYMMETRIC, NORMALIZE_NONE = 0, 1, 2, 3   # lccrf_normalization (section 1g)
 OK = 0
 _STATUS = {0: "OK", -1: "E_INVALID", -2: "E_NO_DEVICE", -3: "E_HIP", -4: "E_NOMEM", -5: "E_STATE",
            -6: "E_CAPACITY"}
@@ -122,6 +123,8 @@ def lib():
     L.lccrf_get_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p, C.POINTER(C.c_int)]
     L.lccrf_inference_backward_compat.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, vp]
     L.lccrf_inference_backward_all.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, C.POINTER(vp), vp]
+    L.lccrf_set_pairwise_normalization.argtypes = [vp, C.c_int, C.c_int]
+    L.lccrf_get_pairwise_normalization.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
     L.lccrf_batch_create.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(BatchDesc)]
     L.lccrf_batch_destroy.argtypes = [vp]
     L.lccrf_batch_destroy.restype = None
@@ -401,6 +404,16 @@ class DenseCRFHIP:
         inference_backward_features_device takes it, d_grad_compat as inference_backward_compat_device; any output may be None."""
         _check(lib().lccrf_inference_backward_all(self.h, int(n_iterations), float(relax), _addr(d_grad_prob), _addr(d_grad_unary),
                                                   _addr(d_grad_weights), _addr_list(d_grad_features), _addr(d_grad_compat)))
+
+    # -- normalisation modes (include/lccrf.h section 1g) ------------------------------------------------------------------------
+    def set_normalization(self, k, mode):
+        """Where term k applies its norm: NORMALIZE_AFTER (the reference, the default), _BEFORE, _SYMMETRIC or _NONE."""
+        _check(lib().lccrf_set_pairwise_normalization(self.h, int(k), int(mode)))
+
+    def get_normalization(self, k):
+        mode = C.c_int(0)
+        _check(lib().lccrf_get_pairwise_normalization(self.h, int(k), C.byref(mode)))
+        return mode.value
 
     # -- results -----------------------------------------------------------------------
     def map(self):

@@ -147,14 +147,17 @@ def mean_field(crf, unary, weights, n_iterations=5, relax=1.0):
 class _HandleCRF(torch.nn.Module):
     """what MeanFieldCRF and CompatMeanFieldCRF share: a DenseCRFHIP handle over fixed features, the term weights an nn.Parameter"""
 
-    def __init__(self, n_points, n_labels, features, weights, n_iterations, relax, device):
+    def __init__(self, n_points, n_labels, features, weights, n_iterations, relax, device, normalization=None):
         super().__init__()
         if len(features) != len(weights):
             raise ValueError("one weight per feature array")
+        modes = [] if normalization is None else np.broadcast_to(np.asarray(normalization, np.int64), (len(features),)).tolist()
         self.crf = _pkg.DenseCRFHIP(n_points, n_labels, device=device)
         for f, w in zip(features, weights):
             f = f.detach().cpu().numpy() if isinstance(f, torch.Tensor) else np.asarray(f)
             self.crf.add_pairwise(np.ascontiguousarray(f, np.float32), float(w))
+        for k, mode in enumerate(modes):                      # (include/lccrf.h section 1g; None: every term AFTER, the reference's form)
+            self.crf.set_normalization(k, mode)
         self.weights = torch.nn.Parameter(torch.tensor([float(w) for w in weights], dtype=torch.float32))
         self.n_iterations, self.relax = int(n_iterations), float(relax)
 
@@ -166,10 +169,11 @@ class MeanFieldCRF(_HandleCRF):
     """A dense CRF layer: a DenseCRFHIP handle over fixed features, its term weights an nn.Parameter.
 
     features: list of [N, d_k] arrays (already divided by the kernel's standard deviation, as lccrf_add_pairwise takes
-    them); weights: their initial weights.  forward(unary [N, L]) -> Q [N, L]."""
+    them); weights: their initial weights; normalization: None (the reference's form), or one of the package's NORMALIZE_* modes
+    for every term, or one per term (include/lccrf.h section 1g).  forward(unary [N, L]) -> Q [N, L]."""
 
-    def __init__(self, n_points, n_labels, features, weights, n_iterations=5, relax=1.0, device=0):
-        super().__init__(n_points, n_labels, features, weights, n_iterations, relax, device)
+    def __init__(self, n_points, n_labels, features, weights, n_iterations=5, relax=1.0, device=0, normalization=None):
+        super().__init__(n_points, n_labels, features, weights, n_iterations, relax, device, normalization)
 
     def forward(self, unary):
         return mean_field(self.crf, unary, self.weights, self.n_iterations, self.relax)
@@ -453,10 +457,10 @@ def mean_field_compat(crf, unary, weights, compat, n_iterations=5, relax=1.0):
 
 class CompatMeanFieldCRF(_HandleCRF):
     """MeanFieldCRF whose terms carry a learnt label-compatibility matrix: parameters `weights` [K] and `compat` [K, L, L], the
-    latter initialised to identities (the Potts model).  forward(unary [N, L]) -> Q [N, L]."""
+    latter initialised to identities (the Potts model); normalization as MeanFieldCRF takes it.  forward(unary [N, L]) -> Q [N, L]."""
 
-    def __init__(self, n_points, n_labels, features, weights, n_iterations=5, relax=1.0, device=0):
-        super().__init__(n_points, n_labels, features, weights, n_iterations, relax, device)
+    def __init__(self, n_points, n_labels, features, weights, n_iterations=5, relax=1.0, device=0, normalization=None):
+        super().__init__(n_points, n_labels, features, weights, n_iterations, relax, device, normalization)
         self.compat = torch.nn.Parameter(torch.eye(n_labels, dtype=torch.float32).repeat(len(weights), 1, 1))
 
     def forward(self, unary):

@@ -86,6 +86,7 @@ int lccrf_inference_backward_features(lccrf_handle h, int n_iterations, float re
 {
     CHECK_H(h);
     if (h->eng.n_compat) return fail(LCCRF_E_STATE, "feature gradients are not available while a term has a label-compatibility matrix");
+    if (h->eng.n_modes) return fail(LCCRF_E_STATE, "feature gradients are not available while a term is not normalised AFTER the filter");
     BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
     rq.grad_features = d_grad_features;
     return backward_call(backward_target(h), rq, kGradUnaryOptional);
@@ -112,6 +113,8 @@ int lccrf_inference_backward_all(lccrf_handle h, int n_iterations, float relax, 
                                  float *d_grad_weights, float *const *d_grad_features, float *d_grad_compat)
 {
     CHECK_H(h);
+    if (d_grad_features && h->eng.n_modes)                // (section 1g: the norm's factors are not differentiated in the features)
+        return fail(LCCRF_E_STATE, "feature gradients are not available while a term is not normalised AFTER the filter");
     BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
     rq.grad_features = d_grad_features;
     rq.grad_compat = d_grad_compat;

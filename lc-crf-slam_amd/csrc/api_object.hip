@@ -1,4 +1,5 @@
-// api_object.hip -- the object API of include/lccrf.h: sections 1, 1a and 1b, the weights of 1c and the matrices of 1e.
+// api_object.hip -- the object API of include/lccrf.h: sections 1, 1a and 1b, the weights of 1c, the matrices of 1e and the
+// normalisation modes of 1g.
 //
 // Argument checks, pinned staging and launch order of one handle; the state machine behind it is the Engine (host_engine.h).
 #include "api_common.h"
@@ -374,8 +375,10 @@ static int pairwise_apply_on(lccrf_crf *h, int kernel, float *d_out, const float
     int rc = e.resolve_late();
     if (!rc) rc = e.ensure_plain();
     if (!rc) rc = e.learn_sizes();                        // builds the lattice if it only exists as staged features
+    if (!rc) rc = e.ensure_factors();
     if (rc || !h->N) return rc;
-    launch_filter(e.kdevs[kernel], e.crf, e.maxV[kernel], d_in, d_out, accumulate, e.stream, 0, nullptr, e.compat_ptr[kernel]);
+    launch_filter(e.step_kdevs()[kernel], e.crf, e.maxV[kernel], d_in, d_out, accumulate, e.stream, 0, nullptr, e.compat_ptr[kernel],
+                  e.n_modes ? e.pre_ptr[kernel] : nullptr);
     HIP_TRY(hipGetLastError());
     return LCCRF_OK;
 }
@@ -749,6 +752,30 @@ int lccrf_get_pairwise_compatibility(lccrf_handle h, int kernel, float *compat_o
     if (is_set) *is_set = set ? 1 : 0;
     for (int i = 0; compat_out && i < e.L * e.L; ++i)     // (a Potts term reads as the identity it is)
         compat_out[i] = set ? e.compat_host[(size_t)kernel * e.L * e.L + i] : (i / e.L == i % e.L ? 1.0f : 0.0f);
+    return LCCRF_OK;
+}
+
+// --------------------------------------------------------------------------------------
+// section 1g: where each pairwise term applies its norm
+
+int lccrf_set_pairwise_normalization(lccrf_handle h, int kernel, int mode)
+{
+    CHECK_H(h);
+    CHECK_K(h, kernel);
+    if (mode < LCCRF_NORMALIZE_AFTER || mode > LCCRF_NORMALIZE_NONE)
+        return fail(LCCRF_E_INVALID, "normalization mode %d is none of LCCRF_NORMALIZE_AFTER / _BEFORE / _SYMMETRIC / _NONE", mode);
+    Engine &e = h->eng;
+    { int rl = e.resolve_late(); if (rl) return rl; }   // (a pending one-launch inference may still be re-run: with the modes it was asked with)
+    e.set_norm_mode(kernel, mode);
+    return LCCRF_OK;
+}
+
+int lccrf_get_pairwise_normalization(lccrf_handle h, int kernel, int *mode)
+{
+    CHECK_H(h);
+    CHECK_K(h, kernel);
+    if (!mode) return fail(LCCRF_E_INVALID, "mode is NULL");
+    *mode = h->eng.norm_mode[kernel];
     return LCCRF_OK;
 }
 

@@ -182,8 +182,16 @@ void launch_unary_from_label_tbl(const CrfDev &c, const int16_t *label, const Un
 void launch_start(const CrfDev &c, hipStream_t s);
 // compat (include/lccrf.h section 1e; null: every term is Potts): K device pointers, compat[k] the [L][L] label-compatibility matrix
 // of term k or null.  The batch paths pass null.
+// pre (include/lccrf.h section 1g; null: every term is normalised AFTER the filter, as the reference's): K device pointers, pre[k]
+// the [F][maxN] factor of term k's filter INPUT (its norm, or the square root of it) or null.  A non-null `pre` says that some term
+// of the CRF is not normalised AFTER: the step then takes the general L-label branch at L = 2 as well, and `kds` are the caller's
+// copies whose `norm` points at each term's factor behind the filter (the norm, its square root, or ones).  The batch paths pass null.
 void launch_step_stream(const CrfDev &c, const KernelDev *kds, const int *maxV, float relax,
-                        hipStream_t s, const float *const *compat = nullptr);
+                        hipStream_t s, const float *const *compat = nullptr, const float *const *pre = nullptr);
+// section 1g's per-point factors, out [F][maxN]: sqrtf(norm) of the frame's points (root = 1; correctly rounded), or 1.0f everywhere
+void launch_norm_factor(const CrfDev &c, const float *norm, float *out, int root, hipStream_t s);
+// the generic splat with its input rows multiplied by pre [F][kd.maxN] where they are loaded (stream_scaled.hip; in != null)
+void launch_splat_scaled(const KernelDev &kd, const float *in, int in_stride, int L, int F, int maxV, const float *pre, hipStream_t s);
 void launch_map(const CrfDev &c, hipStream_t s);
 void launch_map_of(const CrfDev &c, const float *prob, int16_t *map, hipStream_t s);
 void launch_exp_and_normalize(const CrfDev &c, const float *in, float *out, float scale, float relax, hipStream_t s);
@@ -193,8 +201,9 @@ void launch_step_init(const CrfDev &c, float *out, hipStream_t s);
 // blurred (optional): receives the kernel's value buffer (val0 or val1) that the slice read -- (B S in)[v][l] at
 // [f * vstride + vbase + v * L + l], valid until the kernel's next splat (the feature gradient's corner dots read it there)
 // compat (accumulate = 1 only): the term's [L][L] label-compatibility matrix or null -- out += w * norm * (compute(in) mu^T)
+// pre: the [F][maxN] factor of the input rows or null (section 1g) -- compute(pre . in), formed inside the splat
 void launch_filter(const KernelDev &kd, const CrfDev &c, int maxV, const float *in, float *out, int accumulate, hipStream_t s,
-                   int reverse = 0, const float **blurred = nullptr, const float *compat = nullptr);
+                   int reverse = 0, const float **blurred = nullptr, const float *compat = nullptr, const float *pre = nullptr);
 // the same for a value width of 1 and without the slice: in [F][in_stride] (null: all ones, the normalisation's input); returns
 // the blurred values, (B S in)[v] at [f * vstride + vbase + v]
 const float *launch_filter_values1(const KernelDev &kd, const CrfDev &c, int maxV, const float *in, int in_stride, hipStream_t s,
@@ -258,8 +267,11 @@ size_t backward_layout(const BackwardRequest &rq, const CrfDev &c, const KernelD
 // compat (or null): K device pointers, the terms' [L][L] matrices or null, read with rq.compat_form only -- the sweep then takes
 // section 1e's form (one k_compat_bwd launch per iteration and term more) and rq.grad_compat, if given, is overwritten.
 // compat_form and grad_features together are section 1f: section 1e's form plus the launches section 1d adds.
+// pre (or null): as launch_step_stream takes it (section 1g) -- kds[k].norm is then a_k, the factor behind the filter, the forward
+// filters of the sweep scale their input rows by pre[k] = b_k, and k_bwd_combine multiplies the transposed filter's result by it.
+// Without grad_features only (the entry points refuse the combination).
 void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int rows, const BackwardRequest &rq,
-                           const BackwardArea &ar, const float *const *compat, hipStream_t s);
+                           const BackwardArea &ar, const float *const *compat, hipStream_t s, const float *const *pre = nullptr);
 
 // ---- fused build (SLAM sizes; one workgroup per (frame, kernel), hash table in LDS) ------
 bool build_small_supported(const KernelDev *kds, int n, int max_points);

@@ -1,7 +1,7 @@
 // host_engine.h -- the host-side state machine behind the C-ABI: one Engine per handle or batch.
 //
 // Host code only (no kernel): device memory, lattice builds, locality mode, engine choice, the late-bound one-launch run with its
-// per-frame fallback, the done-word protocol, the backward area and the compatibility matrices.  The bodies are in
+// per-frame fallback, the done-word protocol, the backward area, the compatibility matrices and the normalisation modes.  The bodies are in
 // host_engine.hip; the entry points of include/lccrf.h (api_*.hip) read and write the fields below directly.
 #pragma once
 
@@ -82,6 +82,10 @@ struct KernelState {
     float *feat_stage = nullptr;  // pinned staging for the object API
     int maxV = 0;                 // max over frames of V once known, else Epad
     int maxRow = 0;               // max over frames of the longest CSR row
+    float *norm_root = nullptr;   // [F][maxN] sqrtf(norm) of a term normalised SYMMETRICally (section 1g; lazy, kept with the lattice)
+    bool root_valid = false;      // ... holds the roots of the norm now in HBM.  Invariant: whatever writes KernelDev::norm in HBM clears
+                                  //   this -- today that is Engine::build_kernels alone (the streaming and the one-workgroup build; the
+                                  //   one-launch frame kernel keeps its norm in LDS and leaves built_upto as it was)
 };
 
 // One CRF problem set: F frames x maxN points x L labels, K kernels.
@@ -211,6 +215,18 @@ struct Engine {
     const float *compat_ptr[LCCRF_MAX_KERNELS] = {};
     int n_compat = 0;
 
+    // ---- normalisation modes ----
+    // section 1g (object API; a batch has none): where each term applies its norm -- after the filter (the reference's form and the
+    // default), before it, half on either side, or not at all.  While n_modes > 0 the one-launch frame kernel and the fused engine
+    // are not taken and the streaming engine's general branch runs on kdevs_post, the copy of kdevs whose `norm` points at each
+    // term's factor BEHIND the filter, with pre_ptr[k] the factor of its input (ensure_factors(), behind learn_sizes()).
+    int norm_mode[LCCRF_MAX_KERNELS] = {};   // lccrf_normalization of every term
+    int n_modes = 0;                   // terms that are not LCCRF_NORMALIZE_AFTER
+    float *ones = nullptr;             // [Fcap][maxN] of 1.0f: the factor behind the filter of a BEFORE or NONE term (lazy)
+    std::vector<KernelDev> kdevs_post;
+    const float *pre_ptr[LCCRF_MAX_KERNELS] = {};
+    bool factors_dirty = true;         // kdevs_post / pre_ptr are behind kdevs or the modes (raised by sync_views and set_norm_mode)
+
     // ---- timing ----
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // build begin/end, inference begin/end
     bool timed_build = false, timed_inf = false;
@@ -257,7 +273,13 @@ struct Engine {
     int rerun_frames(int n);
 
     const float *const *compat_arg() const { return n_compat ? compat_ptr : nullptr; }
-    void choose_sized_engine() { sized_engine = fused_fits && !n_compat ? 2 : 1; }
+    void choose_sized_engine() { sized_engine = fused_fits && !n_compat && !n_modes ? 2 : 1; }
+    // what the streaming step, the plug-in filter and the backward sweep are handed (valid behind ensure_factors())
+    const KernelDev *step_kdevs() const { return n_modes ? kdevs_post.data() : kdevs.data(); }
+    const float *const *pre_arg() const { return n_modes ? pre_ptr : nullptr; }
+    void clear_norm_modes();
+    void set_norm_mode(int k, int mode);
+    int ensure_factors();
     void clear_compat();
     int set_compat(int k, const float *m);
 

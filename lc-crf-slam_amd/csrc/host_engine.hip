@@ -71,6 +71,58 @@ int Engine::set_compat(int k, const float *m)
     return LCCRF_OK;
 }
 
+void Engine::clear_norm_modes()
+{
+    for (int k = 0; k < LCCRF_MAX_KERNELS; ++k) norm_mode[k] = LCCRF_NORMALIZE_AFTER;
+    n_modes = 0;
+    choose_sized_engine();
+}
+
+// mode: 0 .. 3, checked by the caller.  Touches no lattice, norm or prepared record.
+void Engine::set_norm_mode(int k, int mode)
+{
+    n_modes += (mode != LCCRF_NORMALIZE_AFTER) - (norm_mode[k] != LCCRF_NORMALIZE_AFTER);
+    norm_mode[k] = mode;
+    factors_dirty = true;
+    choose_sized_engine();
+}
+
+// Behind learn_sizes(), before anything reads step_kdevs() / pre_arg(): the factors the terms' modes need -- the square roots of a
+// SYMMETRIC term's norm, formed on the stream right behind the norm itself (in its point order, locality mode included) when a build
+// or a mode change has left them stale, and the array of ones -- and the views that point at them.
+int Engine::ensure_factors()
+{
+    if (!n_modes || !factors_dirty) return LCCRF_OK;   // (a build clears root_valid and goes through sync_views: dirty again)
+    const size_t np = (size_t)Fcap * maxN;
+    kdevs_post = kdevs;
+    for (size_t k = 0; k < kernels.size(); ++k) {
+        KernelState &ks = kernels[k];
+        const int mode = norm_mode[k];
+        pre_ptr[k] = nullptr;
+        if (mode == LCCRF_NORMALIZE_SYMMETRIC) {
+            if (!ks.norm_root) {
+                int rc = mem.alloc(&ks.norm_root, np);
+                if (rc) { ks.norm_root = nullptr; return rc; }
+                ks.root_valid = false;
+            }
+            if (!ks.root_valid) launch_norm_factor(crf, ks.dev.norm, ks.norm_root, 1, stream);
+            ks.root_valid = true;
+            pre_ptr[k] = kdevs_post[k].norm = ks.norm_root;
+        } else if (mode != LCCRF_NORMALIZE_AFTER) {
+            if (!ones) {
+                int rc = mem.alloc(&ones, np, false);
+                if (rc) { ones = nullptr; return rc; }
+                launch_norm_factor(crf, nullptr, ones, 0, stream);
+            }
+            if (mode == LCCRF_NORMALIZE_BEFORE) pre_ptr[k] = ks.dev.norm;
+            kdevs_post[k].norm = ones;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    factors_dirty = false;
+    return LCCRF_OK;
+}
+
 void Engine::free_backward_area()
 {
     if (!bwd_area) return;
@@ -115,6 +167,7 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
     backward_layout(rq, crf, kdevs.data(), slice, rows, reinterpret_cast<float *>(bwd_area), &ar);
     int rc = start();                                 // (ensure_plain: a handle's frames in locality mode are re-built the plain way once)
     if (!rc) rc = learn_sizes();
+    if (!rc) rc = ensure_factors();
     if (rc) return rc;
     for (int t = 0; t < T; ++t) {
         if (count) HIP_TRY(hipMemcpyAsync(ar.hist + (size_t)t * slice, crf.Q, count * sizeof(float), hipMemcpyDeviceToDevice, stream));
@@ -134,7 +187,7 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
             HIP_TRY(hipMemsetAsync(ar.gb[k], 0, ar.feat_floats[k] * sizeof(float), stream));
     }
     HIP_TRY(hipMemcpyAsync(ar.G, rq.grad_prob, count * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    launch_backward_sweep(crf, kdevs.data(), maxV.data(), rows, rq, ar, compat_arg(), stream);
+    launch_backward_sweep(crf, step_kdevs(), maxV.data(), rows, rq, ar, compat_arg(), stream, pre_arg());
     HIP_TRY(hipGetLastError());
     return LCCRF_OK;
 }
@@ -283,6 +336,7 @@ int Engine::add_kernel(int d, float w, bool own_features, bool stage)
             ks.dev.feat = ks.feat_own;
             ks.maxV = ks.dev.Epad;
             ks.maxRow = 0;
+            ks.root_valid = false;
             kernels.push_back(ks);
             sync_views();
             return LCCRF_OK;
@@ -402,7 +456,8 @@ void Engine::recycle()
     unary_is_label = unary_p_valid = false;
     engine_pref = 0;
     engine_used = 1;
-    clear_compat();                                   // (the next user's terms start as Potts terms)
+    clear_compat();                                   // (the next user's terms start as Potts terms ...
+    clear_norm_modes();                               //  ... normalised AFTER the filter)
     sync_views();
 }
 
@@ -421,6 +476,7 @@ void Engine::sync_views()
         maxV[i] = kernels[i].maxV;
         maxRow[i] = kernels[i].maxRow;
     }
+    factors_dirty = true;                              // (section 1g: the views derived from kdevs are rebuilt by ensure_factors())
     crf.K = (int)kernels.size();
     crf.F = F;
     crf.activeN = activeN;
@@ -433,7 +489,10 @@ void Engine::sync_views()
 // anything else the streaming build (19 launches per kernel).
 int Engine::build_kernels(int k0, int n)
 {
-    for (int k = k0; k < k0 + n; ++k) kernels[k].maxV = kernels[k].dev.Epad;
+    for (int k = k0; k < k0 + n; ++k) {
+        kernels[k].maxV = kernels[k].dev.Epad;
+        kernels[k].root_valid = false;                  // (section 1g: the roots of the norm this build replaces)
+    }
     if (k0 == 0) {                                     // a build of every kernel decides the internal point order afresh
         static const bool no_perm = ab_env("LCCRF_NO_PERM") != nullptr;   // A/B and cross-check switch: same results either way
         const int NAp = active_points(crf);
@@ -655,7 +714,8 @@ int Engine::step(float relax)
     rc = learn_sizes();
     if (rc) return rc;
     if ((rc = ensure_unary())) return rc;             // (label-derived energies follow the lattices' point order: re-derived after a re-build)
-    launch_step_stream(crf, kdevs.data(), maxV.data(), relax, stream, compat_arg());
+    if ((rc = ensure_factors())) return rc;
+    launch_step_stream(crf, step_kdevs(), maxV.data(), relax, stream, compat_arg(), pre_arg());
     return LCCRF_OK;
 }
 
@@ -663,7 +723,7 @@ int Engine::step(float relax)
 bool Engine::frame_ok() const
 {
     static const bool no_frame = ab_env("LCCRF_NO_FRAME") != nullptr;   // cross-check switch: two-kernel path, same results
-    return !no_frame && engine_pref == 0 && !n_compat && !kernels.empty() && frame_supported(crf, kdevs.data());
+    return !no_frame && engine_pref == 0 && !n_compat && !n_modes && !kernels.empty() && frame_supported(crf, kdevs.data());
 }
 
 // One launch per frame; whether every frame fitted the kernel's LDS plan is known at the next
@@ -780,6 +840,7 @@ int Engine::inference_sized(int n_iter, int with_map, float relax)
     if (rc) return rc;
     rc = ensure_unary();
     if (rc) return rc;
+    if ((rc = ensure_factors())) return rc;
     engine_used = sized_engine;
     last_with_map = with_map;
     if (perm_on) {
@@ -794,7 +855,7 @@ int Engine::inference_sized(int n_iter, int with_map, float relax)
             cp.unary = unary_p;
         }
         launch_start(cp, stream);
-        for (int it = 0; it < n_iter; ++it) launch_step_stream(cp, kdevs.data(), maxV.data(), relax, stream, compat_arg());
+        for (int it = 0; it < n_iter; ++it) launch_step_stream(cp, step_kdevs(), maxV.data(), relax, stream, compat_arg(), pre_arg());
         launch_permute_rows(crf, crf.Q, Qp, L, 0, stream);
         if (with_map) launch_map(crf, stream);
         started = true;
@@ -823,7 +884,7 @@ int Engine::inference_sized(int n_iter, int with_map, float relax)
         started = true;
     } else {
         if ((rc = start())) return rc;
-        for (int it = 0; it < n_iter; ++it) launch_step_stream(crf, kdevs.data(), maxV.data(), relax, stream, compat_arg());
+        for (int it = 0; it < n_iter; ++it) launch_step_stream(crf, step_kdevs(), maxV.data(), relax, stream, compat_arg(), pre_arg());
         if (with_map) launch_map(crf, stream);
     }
     HIP_TRY(hipGetLastError());

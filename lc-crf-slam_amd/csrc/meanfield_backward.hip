@@ -273,15 +273,31 @@ __global__ void __launch_bounds__(kBwdBlock) k_joint_softmax(BwdArgs a)
 }
 
 // G = keep * G + sum_k w_k * buf_k, element by element (keep = 1 - relax); frame blockIdx.y
+// PRE (section 1g): a term whose filter input is scaled by b_k (pre.p[k], [F][nstride]; null: 1) adds w_k * (b_k[i] * buf_k) -- the
+// transposed filter's result goes back through the input's factor.  PRE = false is the code it was.
+struct BwdPre { const float *p[kBwdMaxK]; int nstride; };
+template <bool PRE>
 __global__ void __launch_bounds__(kBwdBlock) k_bwd_combine(const int *__restrict__ n_points, int L, int K, const float *__restrict__ buf,
-                                                         size_t slice, size_t fs, BwdWeights wk, float keep, float *__restrict__ G)
+                                                         size_t slice, size_t fs, BwdWeights wk, float keep, float *__restrict__ G,
+                                                         BwdPre pre)
 {
     const int f = blockIdx.y;
     const long idx = (long)blockIdx.x * kBwdBlock + threadIdx.x;
     if (idx >= (long)n_points[f] * L) return;
     const size_t o = f * fs + idx;
     float acc = keep * G[o];
-    for (int k = 0; k < K; ++k) acc = acc + wk.w[k] * buf[k * slice + o];
+    if constexpr (PRE) {
+        const size_t i = (size_t)f * pre.nstride + idx / L;
+#pragma unroll
+        for (int k = 0; k < kBwdMaxK; ++k) {
+            if (k >= K) break;
+            float v = buf[k * slice + o];
+            if (pre.p[k]) v = pre.p[k][i] * v;
+            acc = acc + wk.w[k] * v;
+        }
+    } else {
+        for (int k = 0; k < K; ++k) acc = acc + wk.w[k] * buf[k * slice + o];
+    }
     G[o] = acc;
 }
 
@@ -584,7 +600,7 @@ size_t backward_layout(const BackwardRequest &rq, const CrfDev &c, const KernelD
 }
 
 void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int rows, const BackwardRequest &rq,
-                           const BackwardArea &ar, const float *const *compat, hipStream_t s)
+                           const BackwardArea &ar, const float *const *compat, hipStream_t s, const float *const *pre)
 {
     const int T = rq.T;
     const float relax = rq.relax;
@@ -605,9 +621,12 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
     a.G = ar.G;
     a.gU = rq.grad_unary ? rq.grad_unary : ar.gU;
     BwdWeights wk{};
+    BwdPre bp{};
+    bp.nstride = c.maxN;
     for (int k = 0; k < K; ++k) {
-        a.norm[k] = kds[k].norm;
+        a.norm[k] = kds[k].norm;                            // (section 1g: the caller's copy points it at a_k)
         a.w[k] = wk.w[k] = kds[k].w;
+        bp.p[k] = pre ? pre[k] : nullptr;
     }
     // the compatibility part (section 1e): some term has a matrix, or dL/dmu is asked for -- ar.gam and ar.cpart are set
     const bool cmode = rq.compat_form;
@@ -628,7 +647,7 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
     for (int t = T; t >= 1; --t) {
         const float *qprev = ar.hist + (size_t)(t - 1) * slice;
         const float *val[kBwdMaxK];                        // (B S Q_{t-1}) of every term, in the term's own value buffer
-        for (int k = 0; k < K; ++k) launch_filter(kds[k], c, maxV[k], qprev, ar.phi + k * slice, 0, s, 0, &val[k]);
+        for (int k = 0; k < K; ++k) launch_filter(kds[k], c, maxV[k], qprev, ar.phi + k * slice, 0, s, 0, &val[k], nullptr, bp.p[k]);
         a.K = K;
         a.relax = relax;
         a.first = t == T;
@@ -651,7 +670,8 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
             launch_filter(kds[k], c, maxV[k], ar.phi + k * slice, ar.phi + k * slice, 0, s, 1, &valt);
             if (gf[k]) launch_corner_dot(kds[k], c, rows, L, qprev, fs, valt, cs, ar.gb[k], s);                    // splat side
         }
-        k_bwd_combine<<<cgrid, kBwdBlock, 0, s>>>(c.n_points, L, K, ar.phi, slice, fs, wk, 1.0f - relax, ar.G);
+        if (pre) k_bwd_combine<true><<<cgrid, kBwdBlock, 0, s>>>(c.n_points, L, K, ar.phi, slice, fs, wk, 1.0f - relax, ar.G, bp);
+        else k_bwd_combine<false><<<cgrid, kBwdBlock, 0, s>>>(c.n_points, L, K, ar.phi, slice, fs, wk, 1.0f - relax, ar.G, bp);
     }
     // dL/dU -= P_0 (G_0 - <G_0, P_0>), P_0 = Q_0 = softmax(-U)
     a.K = 0;

@@ -3,6 +3,7 @@
 //   stream_build.hip       lattice construction: the hash build, the sorted build of locality mode, CSR rows, neighbour tables
 //   stream_filter.hip      splat / blur / slice, the normalisation and the schedule of a mean-field step
 //   stream_pointwise.hip   the kernels with a thread per point or per (point, label): unary, softmax, MAP, row copies
+//   stream_scaled.hip      the scaled instantiations of the generic splat (stream_splat.h) and the factors of the normalisation modes
 #pragma once
 #include "engine.h"
 #include "dispatch.h"   // with_dims

@@ -8,6 +8,7 @@
 //   apply                  pairwise3d.h:73-78            -> k_slice (mode APPLY)
 //   stepInit               densecrf3d.h:154-158          -> k_slice (first kernel)
 #include "stream_common.h"
+#include "stream_splat.h"
 #include "device_math.h"
 #include <algorithm>
 
@@ -18,164 +19,19 @@ namespace {
 // splat / blur / slice  (value width L at run time; one thread per (vertex|point, label))
 // ---------------------------------------------------------------------------------------
 
-// val0[v+1][l] = sum over the vertex's contributions, ascending point order.  in == nullptr
-// means the all-ones input of the normalisation pass (pairwise3d.h:23-24).
-constexpr int kSplatUnroll = 16;
-typedef float lccrf_f4u __attribute__((ext_vector_type(4), aligned(4)));     // four labels of a row, wherever L puts them
-__global__ void __launch_bounds__(kBlock) k_splat(KernelDev kd, const float *__restrict__ in,
-                                                  int in_stride, int L)
-{
-    const int f = blockIdx.y;
-    const int V = kd.V[f];
-    const int idx = blockIdx.x * kBlock + threadIdx.x;
-    if (idx >= V * L) return;
-    const int v = idx / L, l = idx - v * L;
-    const size_t fe = (size_t)f * kd.Epad, f1 = (size_t)f * (kd.Epad + 1);
-    const int s = kd.rowptr[f1 + v], t = kd.rowptr[f1 + v + 1];
-    if (kd.longrow_ok && t - s > kLongRowMin && kd.longcnt[f] <= kLongRowCap) return;   // k_splat_long's
-    const float *x = in ? in + (size_t)f * in_stride : nullptr;
-    float acc = 0.0f;
-    int p = s;
-    // long rows (a coarse kernel over many points: the reference's image demo has rows of ~900 entries): the adds must go one by one
-    // in point order, the LOADS need not -- kSplatUnroll entries' indices, weights and inputs in flight per round trip instead of one
-    // (the demo's splat 944 -> ~100 us per launch)
-    for (; p + kSplatUnroll <= t; p += kSplatUnroll) {
-        int pt[kSplatUnroll];
-        float w[kSplatUnroll], xv[kSplatUnroll];
-#pragma unroll
-        for (int i = 0; i < kSplatUnroll; ++i) { pt[i] = kd.csr_pt[fe + p + i]; w[i] = kd.csr_w[fe + p + i]; }
-#pragma unroll
-        for (int i = 0; i < kSplatUnroll; ++i) xv[i] = x ? x[(size_t)pt[i] * L + l] : 1.0f;
-#pragma unroll
-        for (int i = 0; i < kSplatUnroll; ++i) acc += w[i] * xv[i];
-    }
-    for (; p < t; ++p) {
-        const float xv = x ? x[(size_t)kd.csr_pt[fe + p] * L + l] : 1.0f;
-        acc += kd.csr_w[fe + p] * xv;
-    }
-    kd.val0[(size_t)f * kd.vstride + kd.vbase + (long)v * L + l] = acc;
-}
-
-// ... four labels per thread from L = 4 on: a row's indices and weights are read once per four labels, the inputs as 16-byte loads
-__global__ void __launch_bounds__(kBlock) k_splat4(KernelDev kd, const float *__restrict__ in, int in_stride, int L, int C)
-{
-    const int f = blockIdx.y;
-    const int V = kd.V[f];
-    const int idx = blockIdx.x * kBlock + threadIdx.x;
-    if (idx >= V * C) return;
-    const int v = idx / C, l = (idx - v * C) * 4, nl = min(4, L - l);
-    const size_t fe = (size_t)f * kd.Epad, f1 = (size_t)f * (kd.Epad + 1);
-    const int s = kd.rowptr[f1 + v], t = kd.rowptr[f1 + v + 1];
-    if (kd.longrow_ok && t - s > kLongRowMin && kd.longcnt[f] <= kLongRowCap) return;   // k_splat_long's
-    const float *x = in + (size_t)f * in_stride + l;
-    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    constexpr int U = 8;
-    int p = s;
-    if (nl == 4) {
-        for (; p + U <= t; p += U) {
-            int pt[U];
-            float w[U];
-            lccrf_f4u xv[U];
-#pragma unroll
-            for (int i = 0; i < U; ++i) { pt[i] = kd.csr_pt[fe + p + i]; w[i] = kd.csr_w[fe + p + i]; }
-#pragma unroll
-            for (int i = 0; i < U; ++i) xv[i] = *reinterpret_cast<const lccrf_f4u *>(x + (size_t)pt[i] * L);
-#pragma unroll
-            for (int i = 0; i < U; ++i) { acc[0] += w[i] * xv[i].x; acc[1] += w[i] * xv[i].y; acc[2] += w[i] * xv[i].z; acc[3] += w[i] * xv[i].w; }
-        }
-        for (; p < t; ++p) {
-            const float w = kd.csr_w[fe + p];
-            const lccrf_f4u xv = *reinterpret_cast<const lccrf_f4u *>(x + (size_t)kd.csr_pt[fe + p] * L);
-            acc[0] += w * xv.x; acc[1] += w * xv.y; acc[2] += w * xv.z; acc[3] += w * xv.w;
-        }
-    } else {
-        for (; p < t; ++p) {
-            const float w = kd.csr_w[fe + p];
-            const float *xp = x + (size_t)kd.csr_pt[fe + p] * L;
-            for (int u = 0; u < nl; ++u) acc[u] += w * xp[u];
-        }
-    }
-    float *d = kd.val0 + (size_t)f * kd.vstride + kd.vbase + (long)v * L + l;
-    for (int u = 0; u < nl; ++u) d[u] = acc[u];
-}
-
-// Rows of thousands of entries (a coarse kernel over many points -- the appearance kernel of the reference's image demo puts whole
-// uniformly coloured regions on one vertex): the adds of a row must still go one by one in point order (quirk Q6), but nothing says
-// the LOADS must.  A workgroup per listed row (KernelDev::longrow, filled by the build): all lanes form the products
-// w[p] * in[pt[p]][l] of a tile of entries in LDS, then lane l < L adds its label's column top to bottom -- the same products, the
-// same order, the same bits as the in-line walk.
-constexpr int kLongTile = 8192;          // products per tile (floats); two tiles in LDS
-__global__ void __launch_bounds__(kBlock) k_splat_long(KernelDev kd, const float *__restrict__ in, int in_stride, int L)
-{
-    __shared__ __attribute__((aligned(16))) float prod[2][kLongTile];
-    const int f = blockIdx.y;
-    const int *lr = kd.longrow + (size_t)f * kLongRowCap;
-    const int n = kd.longcnt[f];
-    if (n > kLongRowCap) return;
-    const size_t fe = (size_t)f * kd.Epad, f1 = (size_t)f * (kd.Epad + 1);
-    const float *x = in ? in + (size_t)f * in_stride : nullptr;
-    // a tile holds ec entries of every label, label-major: prod[l * ecp + e] (ecp = ec + 4, a multiple of 4: the adder reads its
-    // label's column four entries per 16-byte LDS load; the loaders' stores land ecp words apart -- a few ways of bank conflict)
-    const int tid = threadIdx.x, ec = (kLongTile / L - 4) & ~3, ecp = ec + 4;
-    constexpr int kLoaders = kBlock - 64;                 // wavefront 0 adds, the other three load: the tile being added and the tile
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {     // being loaded are different halves of `prod`, one barrier per tile
-        const int v = lr[i];
-        const int s = kd.rowptr[f1 + v], t = kd.rowptr[f1 + v + 1];
-        const int ntiles = (t - s + ec - 1) / ec;
-        float acc = 0.0f;
-        for (int k = -1; k < ntiles; ++k) {
-            if (tid >= 64) {                              // load tile k + 1
-                const int p0 = s + (k + 1) * ec;
-                const int m = k + 1 < ntiles ? min(ec, t - p0) * L : 0;
-                float *dst = prod[(k + 1) & 1];
-                int idx = tid - 64;
-                for (; idx + 7 * kLoaders < m; idx += 8 * kLoaders) {        // eight products per lane and round trip
-                    int pt[8], l[8], e[8];
-                    float w[8], xv[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        e[u] = (idx + u * kLoaders) / L;
-                        l[u] = idx + u * kLoaders - e[u] * L;
-                        pt[u] = kd.csr_pt[fe + p0 + e[u]];
-                        w[u] = kd.csr_w[fe + p0 + e[u]];
-                    }
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) xv[u] = x ? x[(size_t)pt[u] * L + l[u]] : 1.0f;
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) dst[l[u] * ecp + e[u]] = w[u] * xv[u];
-                }
-                for (; idx < m; idx += kLoaders) {
-                    const int e = idx / L, l = idx - e * L;
-                    const float xv = x ? x[(size_t)kd.csr_pt[fe + p0 + e] * L + l] : 1.0f;
-                    dst[l * ecp + e] = kd.csr_w[fe + p0 + e] * xv;
-                }
-            } else if (k >= 0 && tid < L) {               // add tile k: label tid's column, top to bottom
-                const int p0 = s + k * ec;
-                const int m = min(ec, t - p0);
-                const float *src = prod[k & 1] + tid * ecp;
-                int e = 0;
-                for (; e + 8 <= m; e += 8) {
-                    const float4 q0 = *reinterpret_cast<const float4 *>(src + e), q1 = *reinterpret_cast<const float4 *>(src + e + 4);
-                    acc += q0.x; acc += q0.y; acc += q0.z; acc += q0.w;
-                    acc += q1.x; acc += q1.y; acc += q1.z; acc += q1.w;
-                }
-                for (; e < m; ++e) acc += src[e];
-            }
-            __syncthreads();
-        }
-        if (tid < L) kd.val0[(size_t)f * kd.vstride + kd.vbase + (long)v * L + tid] = acc;
-    }
-}
-
 // the generic splat: rows in line, the long ones by a workgroup each
-inline void launch_splat(const KernelDev &kd, const float *in, int in_stride, int L, int F, int maxV, hipStream_t s)
+// pre (optional; with `in` only): the per-point factor of the input rows, [F][kd.maxN] (section 1g) -- the scaled instantiations,
+// which live in stream_scaled.hip
+inline void launch_splat(const KernelDev &kd, const float *in, int in_stride, int L, int F, int maxV, hipStream_t s,
+                         const float *pre = nullptr)
 {
     // four labels per thread where the rows are short (a fine lattice: about one entry per vertex at d = 5 or 6); a coarse kernel's
     // rows of tens to hundreds of entries want every (vertex, label) walk in flight on its own (the image demo: 344 vs 554 us)
-    const bool short_rows = (long)kd.maxN * kd.D1 <= 4L * std::max(maxV, 1);
-    if (L >= 4 && in && short_rows) k_splat4<<<grid_for((long)maxV * ((L + 3) / 4), F), kBlock, 0, s>>>(kd, in, in_stride, L, (L + 3) / 4);
-    else k_splat<<<grid_for((long)maxV * L, F), kBlock, 0, s>>>(kd, in, in_stride, L);
-    if (kd.longrow_ok) k_splat_long<<<dim3((unsigned)std::max(256 / std::max(F, 1), 8), (unsigned)F), kBlock, 0, s>>>(kd, in, in_stride, L);
+    const bool short_rows = splat_short_rows(kd, maxV);
+    if (in && pre) { launch_splat_scaled(kd, in, in_stride, L, F, maxV, pre, s); return; }
+    if (L >= 4 && in && short_rows) k_splat4<false><<<grid_for((long)maxV * ((L + 3) / 4), F), kBlock, 0, s>>>(kd, in, in_stride, L, (L + 3) / 4, nullptr);
+    else k_splat<false><<<grid_for((long)maxV * L, F), kBlock, 0, s>>>(kd, in, in_stride, L, nullptr);
+    if (kd.longrow_ok) k_splat_long<false><<<splat_long_grid(F), kBlock, 0, s>>>(kd, in, in_stride, L, nullptr);
 }
 
 // One Jacobi blur pass along axis j.  ref: :663-679.
@@ -891,7 +747,7 @@ int splat2_term(const CrfDev &c, const KernelDev &kd, int maxV, hipStream_t s)
             const dim3 g = grid_xcd(maxV, c.F, &nb, kBlock);
             k_splat2l<<<g, kBlock, 0, s>>>(kd, reinterpret_cast<const float2 *>(c.Q), c.maxN, c.F, nb);
         }
-        if (kd.longrow_ok) k_splat_long<<<dim3((unsigned)std::max(256 / std::max(c.F, 1), 8), (unsigned)c.F), kBlock, 0, s>>>(kd, c.Q, c.maxN * 2, 2);
+        if (kd.longrow_ok) k_splat_long<false><<<dim3((unsigned)std::max(256 / std::max(c.F, 1), 8), (unsigned)c.F), kBlock, 0, s>>>(kd, c.Q, c.maxN * 2, 2, nullptr);
     } else {
         const dim3 g = grid_xcd(maxV, c.F, &nb, blk);
         k_splat2<false><<<g, blk, 0, s>>>(kd, reinterpret_cast<const float2 *>(c.Q), c.maxN, c.F, nb);
@@ -949,17 +805,20 @@ void launch_norm(const KernelDev &kd, const CrfDev &c, int maxV, hipStream_t s)
         k_slice<<<g, kBlock, 0, s>>>(kd, c, res, 1, SLICE_NORM);
 }
 
-void launch_step_stream(const CrfDev &c, const KernelDev *kds, const int *maxV, float relax, hipStream_t s, const float *const *compat)
+void launch_step_stream(const CrfDev &c, const KernelDev *kds, const int *maxV, float relax, hipStream_t s, const float *const *compat,
+                        const float *const *pre)
 {                                                    // densecrf_base.h:82-91
     const int L = c.L;
-    bool any_compat = false;                             // (section 1e: the two-label kernels hard-wire Potts; a CRF with a matrix
-    for (int k = 0; k < c.K && compat; ++k) any_compat |= compat[k] != nullptr;   //  takes the generic branch at L = 2 as well)
+    // the two-label kernels hard-wire Potts terms normalised AFTER the filter: a CRF with a matrix (section 1e) or with a term in
+    // another normalisation mode (section 1g: `pre` is not null) takes the general branch at L = 2 as well
+    bool general = pre != nullptr;
+    for (int k = 0; k < c.K && compat; ++k) general |= compat[k] != nullptr;
     if (c.K == 0) {
         // stepInit only: next = -unary, then softmax.  Done by the softmax with scale -1.
         launch_exp_and_normalize(c, c.unary, c.Q, -1.0f, relax, s);
         return;
     }
-    if (L == 2 && !any_compat) {
+    if (L == 2 && !general) {
         for (int k = 0; k < c.K; ++k) {
             const KernelDev &kd = kds[k];
             const bool pairs = pair_fuse(c.F, maxV[k]);
@@ -973,7 +832,7 @@ void launch_step_stream(const CrfDev &c, const KernelDev *kds, const int *maxV, 
     }
     for (int k = 0; k < c.K; ++k) {
         const KernelDev &kd = kds[k];
-        launch_splat(kd, c.Q, c.maxN * L, L, c.F, maxV[k], s);
+        launch_splat(kd, c.Q, c.maxN * L, L, c.F, maxV[k], s, pre ? pre[k] : nullptr);
         launch_slice_apply(kd, c, filter_passes(kd, c.F, maxV[k], L, s), L, k == 0 ? SLICE_APPLY_FIRST : SLICE_APPLY, compat ? compat[k] : nullptr, s);
     }
     launch_exp_and_normalize(c, c.next, c.Q, 1.0f, relax, s);
@@ -1009,10 +868,10 @@ hipError_t time_blur_pass(const KernelDev &kd, int F, int maxV, int L, int reps,
 // out (+)= [w * norm *] compute(in) with value width c.L: PairwisePotential::apply (accumulate = 1, pairwise3d.h:73-78)
 // or the bare PermutohedralLatticeCPU::compute (accumulate = 0, permutohedral_cpu.h:634-699); reverse = 1: its transpose (engine.h)
 void launch_filter(const KernelDev &kd, const CrfDev &c, int maxV, const float *in, float *out, int accumulate, hipStream_t s,
-                   int reverse, const float **blurred, const float *compat)
+                   int reverse, const float **blurred, const float *compat, const float *pre)
 {
     const int L = c.L;
-    launch_splat(kd, in, c.maxN * L, L, c.F, maxV, s);
+    launch_splat(kd, in, c.maxN * L, L, c.F, maxV, s, pre);
     const float *res = filter_passes(kd, c.F, maxV, L, s, reverse);
     CrfDev c2 = c;
     c2.next = out;
