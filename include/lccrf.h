@@ -142,6 +142,19 @@ int  lccrf_inference(lccrf_handle h, int n_iterations, int with_map, float relax
 int  lccrf_get_map(lccrf_handle h, int16_t *map_out);
 int  lccrf_get_probability(lccrf_handle h, float *prob_out);
 
+/* Which engine the last lccrf_inference on the handle ran on (no reference counterpart; as lccrf_batch_get_engine for batches).
+ * Added WITHOUT a step of LCCRF_ABI_VERSION (it stays 3): probe for it by symbol.
+ *   *engine   1 the streaming engine (one launch per phase); 2 the fused engine (lattices in HBM, inference in one launch);
+ *             3 one launch per frame (lattice build + inference); 4 the fused engine's kernel for terms with a label-compatibility
+ *             matrix (section 1e) or a normalisation mode other than AFTER (section 1g).  For 3 it is the value after a late-bound
+ *             run has settled: a frame that did not fit the one-launch kernel's plan reports what it was re-run on.  A handle
+ *             that has not run lccrf_inference reports 1.
+ *   *shape    (may be NULL) for engines 2 and 4: lanes per workgroup in bits 0-15, points per lane in bits 16-19, and 1 in bit 20
+ *             when the first term's splat rows took the chain path; otherwise 0.
+ * Report only: nothing depends on the value, and the call does no device work beyond settling a pending one-launch run.
+ * LCCRF_E_INVALID for a NULL handle or a NULL `engine`.                                                                          */
+int  lccrf_get_engine(lccrf_handle h, int *engine, int *shape);
+
 /* ---- the reference's two plug-in points, on HOST arrays (device in, device out behind the call) ------------------
  * PairwisePotential::apply(out_values, in_values, tmp)        densecrf_base.h:18, pairwise3d.h:73-78
  *   out_values[i][k] += w * norm[i] * compute(in_values)[i][k] for pairwise term `kernel` of this CRF (both
@@ -333,11 +346,15 @@ int  lccrf_inference_backward_features(lccrf_handle h, int n_iterations, float r
  *
  * Honoured by lccrf_inference (locality mode at >= 8192 points included), lccrf_start_inference / lccrf_step_inference,
  * lccrf_pairwise_apply / _device (the `apply` of that term), lccrf_inference_backward (dL/dU and dL/dw are then those of the forward
- * with the matrices) and lccrf_inference_backward_compat.  While any term of a handle has a matrix, inference runs on the streaming
- * engine -- the one-launch frame kernel and the fused engine hard-wire Potts -- with the matrix applied inside the slice kernel,
- * which takes the Potts slice kernel's place: the step issues no launch more than the streaming engine's general, L-label step
- * (at L = 2 that is more than the two-label specialisation issues).  Not covered: the batch API has no setter; the C++
- * mirrors (lccrf_densecrf.hpp, lccrf_densecrf_gpu.hpp) are unchanged.  lccrf_inference_backward_features itself still returns
+ * with the matrices) and lccrf_inference_backward_compat.  While any term of a handle has a matrix, the one-launch frame kernel and
+ * the fused engine, which hard-wire Potts, are not taken.  lccrf_inference on the shape the project exists for -- L = 2, one or two
+ * 2-D terms, a frame of up to 2048 points whose lattices fit the fused engine's plan -- then runs in ONE launch on the fused
+ * engine's kernel for such terms (lccrf_get_engine reports 4), with the same bits.  Everything else -- other L, d or K, 2049 points
+ * and more, locality mode, lccrf_start_inference / lccrf_step_inference, the plug-in entry points, every backward call's replay --
+ * runs on the streaming engine with the matrix applied inside the slice kernel, which takes the Potts slice kernel's place: the
+ * step issues no launch more than the streaming engine's general, L-label step (at L = 2 that is more than the two-label
+ * specialisation issues).  The C++ mirror lccrf_densecrf.hpp sets a matrix per potential (PottsPotentialHIP::setCompatibility).
+ * Not covered: the batch API has no setter; lccrf_densecrf_gpu.hpp is unchanged.  lccrf_inference_backward_features itself still returns
  * LCCRF_E_STATE on a handle with any matrix and leaves the handle as it was: the feature gradients of such a handle are
  * lccrf_inference_backward_all's (section 1f).                                                                                 */
 
@@ -429,10 +446,13 @@ int  lccrf_inference_backward_all(lccrf_handle h, int n_iterations, float relax,
  * Honoured by lccrf_inference (locality mode at >= 8192 points included: the factors follow the internal point order the norm
  * has), lccrf_start_inference / lccrf_step_inference, lccrf_pairwise_apply / _device (the `apply` of that term is
  * out += (w * post) * Phi(pre * in)), lccrf_inference_backward and lccrf_inference_backward_compat.  While any term of a handle is not
- * AFTER, inference runs on the streaming engine's general L-label step, at L = 2 too -- exactly what a matrix of section 1e does:
- * the pre factor is applied inside the splat where it loads its input (no launch more, no scaled copy of Q), the post factor is the
- * array the slice reads in the norm's place.  Once every term is AFTER again the handle takes the fast engines and returns the bits
- * it returned before.
+ * AFTER, the one-launch frame kernel and the fused engine are not taken -- exactly what a matrix of section 1e does.  lccrf_inference
+ * on L = 2, one or two 2-D terms and a frame of up to 2048 points whose lattices fit the fused engine's plan runs in ONE launch on
+ * the fused engine's kernel for such terms (lccrf_get_engine reports 4): the pre factors sit in registers beside w * post.
+ * Everything else (section 1e lists it) runs on the streaming engine's general L-label step, at L = 2 too: the pre factor is applied
+ * inside the splat where it loads its input (no launch more, no scaled copy of Q), the post factor is the array the slice reads in
+ * the norm's place.  Both give the same bits.  Once every term is AFTER again the handle takes the fast engines and returns the
+ * bits it returned before.
  *
  * Gradients.  With a_k the term's post and b_k its pre, each 1 where the mode has none, and section 1e's notation:
  *      x_t        = -U + sum_k w_k . a_k . (mu_k applied to Phi_k(b_k . Q_{t-1}))
@@ -444,8 +464,8 @@ int  lccrf_inference_backward_all(lccrf_handle h, int n_iterations, float relax,
  * lccrf_inference_backward_all with a non-NULL d_grad_features, return LCCRF_E_STATE on a handle with any term that is not AFTER and
  * leave the handle as it was.
  *
- * Not covered: the batch API has no setter (sections 2c and 2d keep every term AFTER); the C++ mirrors (lccrf_densecrf.hpp,
- * lccrf_densecrf_gpu.hpp) are unchanged.
+ * The C++ mirror lccrf_densecrf.hpp sets a mode per potential (PottsPotentialHIP::setNormalization).  Not covered: the batch API has
+ * no setter (sections 2c and 2d keep every term AFTER); lccrf_densecrf_gpu.hpp is unchanged.
  *   - Memory: one [N] float array per SYMMETRIC term (s, formed from n on the handle's stream when first needed after a build or a
  *     mode change) and one [N] array of 1.0f per handle with a BEFORE or NONE term (what the slice reads where such a term has no
  *     post: w * 1.0f is exact); both stay with the handle.  Nothing is allocated for a handle that never calls the setter.      */

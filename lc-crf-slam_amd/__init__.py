@@ -96,6 +96,7 @@ def lib():
     L.lccrf_inference.argtypes = [vp, C.c_int, C.c_int, C.c_float]
     L.lccrf_get_map.argtypes = [vp, _i16p]
     L.lccrf_get_probability.argtypes = [vp, _f32p]
+    L.lccrf_get_engine.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lccrf_get_unary.argtypes = [vp, _f32p]
     L.lccrf_get_lattice_size.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
     L.lccrf_pairwise_apply.argtypes = [vp, C.c_int, _f32p, _f32p]
@@ -425,6 +426,14 @@ class DenseCRFHIP:
         out = np.empty((self.N, self.L), np.float32)
         _check(lib().lccrf_get_probability(self.h, _p(out, _f32p)))
         return out
+
+    def engine(self):
+        """(engine, shape) of the last inference(): 1 streaming, 2 fused, 3 one launch per frame, 4 the fused engine's kernel for
+        terms with a matrix or a normalisation mode; shape (engines 2 and 4, else 0): lanes per workgroup | points per lane << 16 |
+        first term on chain rows << 20.  Report only (include/lccrf.h: lccrf_get_engine)."""
+        e, s = C.c_int(0), C.c_int(0)
+        _check(lib().lccrf_get_engine(self.h, C.byref(e), C.byref(s)))
+        return e.value, s.value
 
     def unary(self):
         out = np.empty((self.N, self.L), np.float32)

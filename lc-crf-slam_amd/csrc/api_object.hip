@@ -305,6 +305,19 @@ int lccrf_inference(lccrf_handle h, int n_iterations, int with_map, float relax)
     return h->eng.inference(n_iterations, with_map, relax);
 }
 
+int lccrf_get_engine(lccrf_handle h, int *engine, int *shape)
+{
+    if (!h || !engine) return fail(LCCRF_E_INVALID, "handle / engine is NULL");
+    if (h->eng.late_pending) {                          // (a frame that did not fit the one-launch kernel reports what it was re-run on)
+        CHECK_H(h);
+        int rl = h->eng.resolve_late();
+        if (rl) return rl;
+    }
+    *engine = h->eng.engine_used;
+    if (shape) *shape = (h->eng.engine_used == 2 || h->eng.engine_used == 4) ? h->eng.engine_shape : 0;
+    return LCCRF_OK;
+}
+
 int lccrf_get_map(lccrf_handle h, int16_t *map_out)
 {
     CHECK_H(h);

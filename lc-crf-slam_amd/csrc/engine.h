@@ -295,8 +295,20 @@ struct LeanPrep {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 size_t lean_prep_bytes(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow);
+// report (optional): receives fused_report() of the launch, the shape word of lccrf_get_engine.
 int launch_inference_fused(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow,
-                           int n_iter, int with_map, float relax, hipStream_t s, LeanPrep *prep = nullptr);
+                           int n_iter, int with_map, float relax, hipStream_t s, LeanPrep *prep = nullptr, int *report = nullptr);
+// lccrf_get_engine's shape word: lanes per workgroup | points per lane << 16 | kernel 0 took the chain path << 20
+inline int fused_report(int lanes, int ppt, int chain0) { return lanes | ppt << 16 | (chain0 ? 1 << 20 : 0); }
+
+// ---- the fused engine's inference with per-term matrices and factors (fused_general.hip; include/lccrf.h sections 1e and 1g) ----
+// One frame (c.F == 1) of at most 2048 active points, L = 2, one or two 2-D terms on lattices that fit the fused plan, in ONE launch.
+//   kds     the caller's copies whose `norm` points at each term's factor behind the filter (as launch_step_stream takes them)
+//   compat  null, or K HOST pointers: term k's [2][2] matrix or null -- passed to the kernel by value
+//   pre     null, or K device pointers: the [F][maxN] factor of term k's filter input or null
+// Returns fused_report() of what it launched, or 0 when the frame is not one it takes (nothing launched).
+int launch_inference_general(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const float *const *compat,
+                             const float *const *pre, int n_iter, int with_map, float relax, hipStream_t s);
 
 // ---- frame engine (SLAM sizes; lattice build + normalisation + inference of a frame in ONE launch) ---------
 bool frame_supported(const CrfDev &c, const KernelDev *kds);

@@ -649,7 +649,7 @@ size_t lean_prep_bytes(const CrfDev &c, const KernelDev *kds, const int *maxV, c
 }
 
 int launch_inference_fused(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, int n_iter,
-                           int with_map, float relax, hipStream_t s, LeanPrep *prep)
+                           int with_map, float relax, hipStream_t s, LeanPrep *prep, int *report)
 {
     FusedArgs a{};
     const FusedShape sh = choose_shape(c, kds, maxV, maxRow, &a.lay);
@@ -700,6 +700,7 @@ int launch_inference_fused(const CrfDev &c, const KernelDev *kds, const int *max
     }
     launch_shape(c, a, s, mode, sh);
     stamps.print(s);                      // debug only: synchronous read-back of one workgroup's phase stamps
+    if (report) *report = fused_report(sh.nt, sh.ppt, a.lay.chain0);
     return sh.report();
 }
 

@@ -1,0 +1,197 @@
+// fused_general.hip -- the fused engine's inference (fused_engine.hip: one launch, one 1024-lane workgroup, the mean-field state on
+// chip) for the two-label handle whose terms are not all Potts terms normalised AFTER the filter: per term an optional 2 x 2
+// label-compatibility matrix (include/lccrf.h section 1e), a per-point factor in front of the filter and one behind it (section 1g).
+//
+// Why: such a handle used to leave the one-workgroup engines for the streaming engine's general L-label step -- one splat, d + 1
+// blur passes and one slice per term plus a softmax, 11 launches per iteration for the tracker's two 2-D terms, 57 for
+// inference(5, true) -- where a launch-per-phase design is bound by launch gaps.  notes/fused_general.md.
+//
+// The loop is fused_loop.h's, in its GEN form: ordered row sums, chain rows, blur, softmax2, relax blending, store_results and the
+// label bits are the fused engine's code.  The arithmetic is what the streaming kernels do (k_splat<true>, k_slice_compat), every
+// product and every sum rounded on its own (-ffp-contract=off):
+//     x    = pre[i] * Q[i][l], rounded once, then bary * x          (Q itself without a pre)
+//     s_l  = 0; s_l = s_l + mu[l][0] * t[0]; s_l = s_l + mu[l][1] * t[1]   behind the slice t of a term with a matrix
+//     next_l += wn * s_l,  wn = w * post[i]                           (post: n, sqrtf(n), or 1.0f for BEFORE / NONE)
+//
+// Scope: a handle's single frame of up to 2 x 1024 active points, K in {1, 2} 2-D terms, kernel 0 with short rows or chain rows,
+// the self-contained prologue only (prepared launch records are the batches', which have no setters): 8 instantiations, kept in a
+// unit of their own so that the fused engine's kernels compile exactly as they did.
+#include "engine.h"
+#include "device_math.h"
+#include "fused_loop.h"
+#include "dispatch.h"
+
+namespace lccrf {
+
+namespace {
+
+using namespace fl;
+
+constexpr int kGeneralMaxPPT = 2;         // points per lane: the loop keeps PPT * K pre factors in registers beside w * post
+
+struct GeneralArgs {
+    KernelDev kd[kMaxFusedK];             // Engine::step_kdevs(): `norm` is the factor behind the filter
+    const float *pre[kMaxFusedK];         // Engine::pre_arg()[k]: [F][maxN] factor in front of term k's filter, or null
+    float mu[kMaxFusedK][4];              // term k's matrix, row-major, by value: uniform in the kernel
+    int has_mu;                           // bit k: term k has a matrix
+    FusedLayout lay;
+    int n_iter, with_map;
+    float relax;
+};
+
+// k_fused<1024, PPT, K, CH, 0> (fused_engine.hip) with the terms of GeneralTerms: the same self-contained prologue -- every global
+// load issued before anything waits, indices clamped instead of branched on -- plus the pre factors beside the norms.
+template <int PPT, int K, int CH>
+__global__ void __launch_bounds__(kNT, 4) k_general(CrfDev c, GeneralArgs a)
+{
+    constexpr int D1 = kD1, NT = kNT;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int f = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int N = c.n_points[f];
+    Instr ins{nullptr, 0, 0, 0, 0};
+
+    PointRegs<PPT, K> pr;
+    GeneralTerms<PPT, K> gt;
+    int V[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) V[k] = a.kd[k].V[f];
+    const FusedLayout &lay = a.lay;
+
+    if (N <= 0) {                         // nothing to infer (and nothing below may index an empty frame)
+        if (a.with_map) clear_label_bits<NT>(c, f, 0, tid);
+        return;
+    }
+
+    constexpr int kNbrRounds = 4096 / NT, kRowRounds = 2048 / NT;   // covers V <= 1365 in registers; larger lattices finish in copy loops
+    unsigned g_nbr[K][kNbrRounds];
+    int g_row[K][kRowRounds];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const KernelDev &kd = a.kd[k];
+        const unsigned *gn = kd.nbr16 + (size_t)f * D1 * kd.Epad;            // already (n1+1) | (n2+1) << 16
+        const int *gr = kd.rowptr + (size_t)f * (kd.Epad + 1);
+#pragma unroll
+        for (int r = 0; r < kNbrRounds; ++r) {            // element idx = j*V + v, j-major like the LDS copy
+            const int idx = min(tid + r * NT, D1 * V[k] - 1);
+            const int j = idx >= 2 * V[k] ? 2 : (idx >= V[k] ? 1 : 0);
+            g_nbr[k][r] = gn[(size_t)j * kd.Epad + (idx - j * V[k])];
+        }
+#pragma unroll
+        for (int r = 0; r < kRowRounds; ++r) g_row[k][r] = gr[min(tid + r * NT, V[k])];
+    }
+    gt.has_pre = 0;
+    gt.has_mu = a.has_mu;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        if (a.pre[k]) gt.has_pre |= 1 << k;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) gt.mu[k][e] = a.mu[k][e];
+    }
+    unsigned pk[PPT][K][D1];              // (vertex id + 1) | place in the row << 16
+#pragma unroll
+    for (int s = 0; s < PPT; ++s) {
+        const int ic = min(tid + s * NT, N - 1);
+        pr.un[s] = reinterpret_cast<const float2 *>(c.unary)[(size_t)f * c.maxN + ic];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const KernelDev &kd = a.kd[k];
+            const size_t e0 = (size_t)f * kd.Epad + (size_t)ic * D1;
+#pragma unroll
+            for (int j = 0; j < D1; ++j) {
+                pk[s][k][j] = kd.pk[e0 + j];
+                pr.bary[s][k][j] = kd.bary[e0 + j];
+            }
+            pr.wn[s][k] = kd.norm[(size_t)f * kd.maxN + ic];
+            gt.pre[s][k] = a.pre[k] ? a.pre[k][(size_t)f * kd.maxN + ic] : 1.0f;
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < PPT; ++s)
+#pragma unroll
+        for (int k = 0; k < K; ++k) pr.wn[s][k] = a.kd[k].w * pr.wn[s][k];   // w * post[i]: w * n, w * sqrtf(n) or w * 1.0f (section 1g)
+
+    // ---- per-frame lattice tables into LDS --------------------------------------------
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        unsigned *nbr = reinterpret_cast<unsigned *>(smem + lay.nbr[k]);
+        unsigned short *row = reinterpret_cast<unsigned short *>(smem + lay.row[k]);
+#pragma unroll
+        for (int r = 0; r < kNbrRounds; ++r) {
+            const int idx = tid + r * NT;
+            if (idx < D1 * V[k]) nbr[idx] = g_nbr[k][r];
+        }
+#pragma unroll
+        for (int r = 0; r < kRowRounds; ++r)
+            if (tid + r * NT <= V[k]) row[tid + r * NT] = (unsigned short)g_row[k][r];
+        // lattices with more vertices than the register rounds cover (sparse frames): plain copy loops
+        const KernelDev &kd = a.kd[k];
+        const unsigned *gn = kd.nbr16 + (size_t)f * D1 * kd.Epad;
+        for (int idx = tid + kNbrRounds * NT; idx < D1 * V[k]; idx += NT) {
+            const int j = idx >= 2 * V[k] ? 2 : (idx >= V[k] ? 1 : 0);
+            nbr[idx] = gn[(size_t)j * kd.Epad + (idx - j * V[k])];
+        }
+        const int *gr = kd.rowptr + (size_t)f * (kd.Epad + 1);
+        for (int v = tid + kRowRounds * NT; v <= V[k]; v += NT) row[v] = (unsigned short)gr[v];
+    }
+    if (tid < 16) reinterpret_cast<float *>(smem + lay.zero)[tid] = 0.0f;
+    if (tid == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            reinterpret_cast<float2 *>(smem + lay.val[k][0])[0] = make_float2(0.f, 0.f);
+            reinterpret_cast<float2 *>(smem + lay.val[k][1])[0] = make_float2(0.f, 0.f);
+        }
+    }
+    __syncthreads();
+
+    ChainLane cl{0u, 0u};
+    if (CH != 0 && chain_k<CH>(lay, 0)) cl = chain_setup(smem, lay, V[0], tid);
+    start_inference<PPT, K, NT>(pr, N, tid);
+    place_products<PPT, K, CH, NT>(smem, lay, N, tid, pk, pr);
+
+    float alpha[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) alpha[k] = a.kd[k].alpha;
+    mean_field<PPT, K, CH, NT, true, true>(smem, lay, V, N, tid, pr, cl, alpha, a.n_iter, a.relax, ins, -1, &gt);
+
+    store_results<PPT, K, NT>(c, f, N, tid, pr, a.with_map);
+}
+
+}  // namespace
+
+// One frame (c.F == 1) of at most 2048 active points on lattices that fit the fused plan, with per-term matrices / factors:
+//   kds      Engine::step_kdevs() -- `norm` is each term's factor behind the filter
+//   compat   K host pointers: term k's [2][2] matrix as it was set, or null (null: no term has one)
+//   pre      K device pointers: term k's factor in front of the filter, or null (null: no term has one)
+// Returns the shape it launched -- lanes | points per lane << 16 | kernel 0 on chain rows << 20 -- or 0 when the frame is not one
+// this kernel takes (nothing launched).
+int launch_inference_general(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const float *const *compat,
+                             const float *const *pre, int n_iter, int with_map, float relax, hipStream_t s)
+{
+    GeneralArgs a{};
+    const int NA = active_points(c);
+    if (c.F != 1 || NA > kGeneralMaxPPT * kNT || !slam_shaped(c, kds, true)) return 0;
+    if (!layout_core(NA, c.K, maxV, maxRow ? maxRow[0] : 0, &a.lay)) return 0;
+    for (int k = 0; k < c.K; ++k) {
+        a.kd[k] = kds[k];
+        a.pre[k] = pre ? pre[k] : nullptr;
+        if (compat && compat[k]) {
+            a.has_mu |= 1 << k;
+            for (int e = 0; e < 4; ++e) a.mu[k][e] = compat[k][e];
+        }
+    }
+    a.n_iter = n_iter;
+    a.with_map = with_map;
+    a.relax = relax;
+    const int ppt = std::max((NA + kNT - 1) / kNT, 1);
+    with_dims<1, kMaxFusedK>(c.K, [&](auto kk) {
+        with_dims<0, 1>(a.lay.chain0 ? 1 : 0, [&](auto ch) {
+            with_dims<1, kGeneralMaxPPT>(ppt, [&](auto p) {
+                launch_workgroups(k_general<decltype(p)::value, decltype(kk)::value, decltype(ch)::value>, c.F, kNT, a.lay.total, s, c, a);
+            });
+        });
+    });
+    return fused_report(kNT, ppt, a.lay.chain0);
+}
+
+}  // namespace lccrf

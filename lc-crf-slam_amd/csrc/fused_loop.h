@@ -219,6 +219,25 @@ struct PointRegs {
     float wn[PPT][K];                     // w * norm                            pairwise3d.h:77
 };
 
+// What the loop's GEN form (fused_general.hip) knows beyond PointRegs: terms with a label-compatibility matrix (include/lccrf.h
+// section 1e) or normalised elsewhere than AFTER the filter (section 1g).  PointRegs::wn is then w * post, the factor behind the
+// filter (the norm, its square root, or 1.0f).  Every other instantiation of the loop takes GEN = false and never reads one.
+template <int PPT, int K>
+struct GeneralTerms {
+    float pre[PPT][K];                    // the factor in front of term k's filter, per point (bit k of has_pre; unread otherwise)
+    float mu[K][4];                       // term k's 2 x 2 matrix, row-major (bit k of has_mu; unread otherwise) -- uniform
+    int has_pre, has_mu;
+};
+
+// The input of term k's filter at point slot s for the GEN form: Q itself, or -- a term with a pre factor -- x = pre * Q, rounded
+// once (what k_splat<true> forms where it loads its input, stream_splat.h).
+template <int PPT, int K>
+__device__ __forceinline__ float2 filter_input(const PointRegs<PPT, K> &pr, const GeneralTerms<PPT, K> &gt, int s, int k)
+{
+    if ((gt.has_pre >> k) & 1) return make_float2(gt.pre[s][k] * pr.q[s].x, gt.pre[s][k] * pr.q[s].y);
+    return pr.q[s];
+}
+
 // What a chain lane knows about the row it sums:  a = row address | wavefront max units << 18 ;
 // b = 8-product units | (padded length is 8n+4) << 13 | pad slots << 14 | output index << 16
 struct ChainLane {
@@ -329,26 +348,42 @@ __device__ __forceinline__ ChainLane chain_setup(unsigned char *smem, const Fuse
 // ---- splat = products (P) + ordered row sums (S), then the d+1 Jacobi blur passes ---------------
 // On return val[k][kD1 & 1] holds the blurred lattice values of every kernel and every lane has passed
 // the barrier behind the last blur pass.  permutohedral_cpu.h:653-679.
-// Phase P for one point slot: the 3 products bary * Q per label of point (tid + s * 1024) into their rows of kernel k.
+// Phase P for one point slot: the 3 products bary * x per label of point (tid + s * 1024) into their rows of kernel k; x is the
+// filter's input at that point (filter_input: Q, unless the term has a pre factor).
 template <int PPT, int K, int CH>
-__device__ __forceinline__ void point_products(unsigned char *smem, const FusedLayout &lay, const PointRegs<PPT, K> &pr, int s, int k)
+__device__ __forceinline__ void point_products(unsigned char *smem, const FusedLayout &lay, const PointRegs<PPT, K> &pr, int s, int k,
+                                               const float2 &x)
 {
     float *p0 = reinterpret_cast<float *>(smem + lay.prod[k]);
     float *p1 = p0 + lay.Ecap[k];
     float2 *p2 = reinterpret_cast<float2 *>(p0);
     const unsigned s0 = pr.ix[s][k][1] >> 16, s1 = pr.ix[s][k][2] & 0xffffu, s2 = pr.ix[s][k][2] >> 16;
     if (chain_k<CH>(lay, k)) {                             // chain kernel: one plane per label
-        p0[s0] = pr.bary[s][k][0] * pr.q[s].x;
-        p1[s0] = pr.bary[s][k][0] * pr.q[s].y;
-        p0[s1] = pr.bary[s][k][1] * pr.q[s].x;
-        p1[s1] = pr.bary[s][k][1] * pr.q[s].y;
-        p0[s2] = pr.bary[s][k][2] * pr.q[s].x;
-        p1[s2] = pr.bary[s][k][2] * pr.q[s].y;
+        p0[s0] = pr.bary[s][k][0] * x.x;
+        p1[s0] = pr.bary[s][k][0] * x.y;
+        p0[s1] = pr.bary[s][k][1] * x.x;
+        p1[s1] = pr.bary[s][k][1] * x.y;
+        p0[s2] = pr.bary[s][k][2] * x.x;
+        p1[s2] = pr.bary[s][k][2] * x.y;
     } else {                                              // short rows: labels interleaved
-        p2[s0] = make_float2(pr.bary[s][k][0] * pr.q[s].x, pr.bary[s][k][0] * pr.q[s].y);
-        p2[s1] = make_float2(pr.bary[s][k][1] * pr.q[s].x, pr.bary[s][k][1] * pr.q[s].y);
-        p2[s2] = make_float2(pr.bary[s][k][2] * pr.q[s].x, pr.bary[s][k][2] * pr.q[s].y);
+        p2[s0] = make_float2(pr.bary[s][k][0] * x.x, pr.bary[s][k][0] * x.y);
+        p2[s1] = make_float2(pr.bary[s][k][1] * x.x, pr.bary[s][k][1] * x.y);
+        p2[s2] = make_float2(pr.bary[s][k][2] * x.x, pr.bary[s][k][2] * x.y);
     }
+}
+
+template <int PPT, int K, int CH>
+__device__ __forceinline__ void point_products(unsigned char *smem, const FusedLayout &lay, const PointRegs<PPT, K> &pr, int s, int k)
+{
+    point_products<PPT, K, CH>(smem, lay, pr, s, k, pr.q[s]);
+}
+// ... of the loop's GEN form (gt) or its plain form
+template <bool GEN, int PPT, int K, int CH>
+__device__ __forceinline__ void point_products(unsigned char *smem, const FusedLayout &lay, const PointRegs<PPT, K> &pr,
+                                               const GeneralTerms<PPT, K> *gt, int s, int k)
+{
+    if constexpr (GEN) point_products<PPT, K, CH>(smem, lay, pr, s, k, filter_input(pr, *gt, s, k));
+    else point_products<PPT, K, CH>(smem, lay, pr, s, k);
 }
 
 // behind a chain row: +0 up to a multiple of 4, then eight +0 (what chain_rows reads past the end of the row)
@@ -367,16 +402,17 @@ __device__ __forceinline__ void chain_pads(unsigned char *smem, const ChainLane 
 // iteration's products point by point right behind each point's softmax.
 // KMASK: the kernels that take part (bit k) -- all of them in the loop; the frame kernel's two-workgroup form normalises
 // its kernels one at a time (frame_engine.hip).
-// REV: see the blur passes.
-template <int PPT, int K, int CH, bool WITH_P = true, int NT = kNT, int KMASK = (1 << K) - 1, bool REV = false>
+// REV: see the blur passes.  GEN: phase P takes its input through filter_input (gt; see GeneralTerms).
+template <int PPT, int K, int CH, bool WITH_P = true, int NT = kNT, int KMASK = (1 << K) - 1, bool REV = false, bool GEN = false>
 __device__ __forceinline__ void splat_blur(unsigned char *smem, const FusedLayout &lay, const int (&V)[K], int N, int tid,
-                                           const PointRegs<PPT, K> &pr, const ChainLane &cl, Instr &ins)
+                                           const PointRegs<PPT, K> &pr, const ChainLane &cl, Instr &ins,
+                                           const GeneralTerms<PPT, K> *gt = nullptr)
 {
     constexpr int D1 = kD1;
     auto phase_P = [&](int k) {
 #pragma unroll
         for (int s = 0; s < PPT; ++s)
-            if (tid + s * NT < N) point_products<PPT, K, CH>(smem, lay, pr, s, k);
+            if (tid + s * NT < N) point_products<GEN, PPT, K, CH>(smem, lay, pr, gt, s, k);
         if (chain_k<CH>(lay, k)) chain_pads(smem, cl);    // (the buffer may have held another kernel's products)
     };
     // lanes [s_lo, NT) share the short-row kernels; the wavefronts that own the chain kernel's
@@ -527,17 +563,31 @@ __device__ __forceinline__ void start_inference(PointRegs<PPT, K> &pr, int N, in
 // already put kernel k's in place (the frame kernel's two-workgroup form, while it waits for the other lattice) clears bit k.
 // No barrier is needed behind X: the next P only writes the product buffers, whose readers finished
 // two barriers ago.
-template <int PPT, int K, int CH, int NT = kNT, bool REV = false>
+// GEN (with gt): the terms of GeneralTerms -- the filter's input through filter_input, and behind the slice section 1e's sum for a
+// term with a matrix: s = 0; s = s + mu[l][0] * t[0]; s = s + mu[l][1] * t[1], every product and sum rounded on its own as in
+// k_slice_compat (stream_filter.hip).  The sum starts at 0 literally: slice_point's shortcut is not valid here, 0 + (-0) is +0.
+template <int PPT, int K, int CH, int NT = kNT, bool REV = false, bool GEN = false>
 __device__ __forceinline__ void mean_field(unsigned char *smem, const FusedLayout &lay, const int (&V)[K], int N, int tid,
                                            PointRegs<PPT, K> &pr, const ChainLane &cl, const float (&alpha)[K], int n_iter,
-                                           float relax, Instr &ins, int first_p = -1)
+                                           float relax, Instr &ins, int first_p = -1, const GeneralTerms<PPT, K> *gt = nullptr)
 {
     // slice + apply + softmax of point slot s (X)
     auto point_update = [&](int s) {
         float nx[2] = {-pr.un[s].x, -pr.un[s].y};                 // stepInit, densecrf3d.h:154-158
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            const float2 t = slice_point(smem, lay, pr, s, k, alpha[k]);
+            float2 t = slice_point(smem, lay, pr, s, k, alpha[k]);
+            if constexpr (GEN) {
+                if ((gt->has_mu >> k) & 1) {
+                    const float *m = gt->mu[k];
+                    float s0 = 0.0f, s1 = 0.0f;
+                    s0 = s0 + m[0] * t.x;
+                    s0 = s0 + m[1] * t.y;
+                    s1 = s1 + m[2] * t.x;
+                    s1 = s1 + m[3] * t.y;
+                    t = make_float2(s0, s1);
+                }
+            }
             nx[0] += pr.wn[s][k] * t.x;                           // pairwise3d.h:77
             nx[1] += pr.wn[s][k] * t.y;
         }
@@ -554,13 +604,13 @@ __device__ __forceinline__ void mean_field(unsigned char *smem, const FusedLayou
                 if (!((first_p >> k) & 1)) continue;
 #pragma unroll
                 for (int s = 0; s < PPT; ++s)
-                    if (tid + s * NT < N) point_products<PPT, K, CH>(smem, lay, pr, s, k);
+                    if (tid + s * NT < N) point_products<GEN, PPT, K, CH>(smem, lay, pr, gt, s, k);
                 if (chain_k<CH>(lay, k)) chain_pads(smem, cl);
             }
         }
         for (int it = 0; it < n_iter; ++it) {
             opaque(pr);
-            splat_blur<PPT, K, CH, false, NT, (1 << K) - 1, REV>(smem, lay, V, N, tid, pr, cl, ins);
+            splat_blur<PPT, K, CH, false, NT, (1 << K) - 1, REV, GEN>(smem, lay, V, N, tid, pr, cl, ins, gt);
             const bool more = it + 1 < n_iter;
 #pragma unroll
             for (int s = 0; s < PPT; ++s) {
@@ -568,7 +618,7 @@ __device__ __forceinline__ void mean_field(unsigned char *smem, const FusedLayou
                     point_update(s);
                     if (more) {
 #pragma unroll
-                        for (int k = 0; k < K; ++k) point_products<PPT, K, CH>(smem, lay, pr, s, k);
+                        for (int k = 0; k < K; ++k) point_products<GEN, PPT, K, CH>(smem, lay, pr, gt, s, k);
                     }
                 }
             }
@@ -578,7 +628,7 @@ __device__ __forceinline__ void mean_field(unsigned char *smem, const FusedLayou
     }
     for (int it = 0; it < n_iter; ++it) {
         opaque(pr);
-        splat_blur<PPT, K, CH, true, NT, (1 << K) - 1, REV>(smem, lay, V, N, tid, pr, cl, ins);
+        splat_blur<PPT, K, CH, true, NT, (1 << K) - 1, REV, GEN>(smem, lay, V, N, tid, pr, cl, ins, gt);
 #pragma unroll
         for (int s = 0; s < PPT; ++s)
             if (tid + s * NT < N) point_update(s);

@@ -117,8 +117,10 @@ struct Engine {
     int built_upto = 0;                // kernels [0, built_upto) have their lattice
 
     // ---- engine choice ----
-    int engine_pref = 0, engine_used = 1;   // engine_used is REPORT-only state (lccrf_batch_get_engine): 1 streaming, 2 fused, 3 one launch per frame
-    int sized_engine = 1;              // what learn_sizes() chose for inference on lattices that sit in HBM (1 or 2)
+    int engine_pref = 0, engine_used = 1;   // engine_used is REPORT-only state (lccrf_batch_get_engine, lccrf_get_engine): 1 streaming, 2 fused,
+                                            //   3 one launch per frame, 4 the fused engine's kernel with matrices and factors (fused_general.hip)
+    int sized_engine = 1;              // what choose_sized_engine() chose for inference on lattices that sit in HBM (1, 2 or 4)
+    int engine_shape = 0;              // report only (lccrf_get_engine): fused_report() of the last inference on engine 2 or 4, else 0
     int last_with_map = 0;             // did the last inference produce MAP labels?
     size_t fused_lds = 0;
     int fused_shape = 0;               // report only: what the last fused inference launched (launch_inference_fused)
@@ -208,7 +210,8 @@ struct Engine {
     // ---- compatibility matrices ----
     // section 1e (object API; a batch has none): the terms' label-compatibility matrices.  One device array for all of them,
     // allocated by the first setter and kept with the handle; compat_ptr[k] is term k's [L][L] slice of it, or null (Potts).
-    // While n_compat > 0 the one-launch frame kernel and the fused engine, which hard-wire Potts, are not taken.
+    // While n_compat > 0 the one-launch frame kernel and the fused engine, which hard-wire Potts, are not taken; the frames
+    // choose_sized_engine() names run on the fused engine's general kernel, which takes the matrices by value from compat_host.
     float *compat_dev = nullptr;       // [LCCRF_MAX_KERNELS][L][L]
     float *compat_host = nullptr;      // pinned, the same shape: the matrices as set (the getter's answer and the uploads' source)
     hipEvent_t compat_ev = nullptr;    // behind the last upload: a setter waits for it before it rewrites a source that may be in flight
@@ -218,8 +221,9 @@ struct Engine {
     // ---- normalisation modes ----
     // section 1g (object API; a batch has none): where each term applies its norm -- after the filter (the reference's form and the
     // default), before it, half on either side, or not at all.  While n_modes > 0 the one-launch frame kernel and the fused engine
-    // are not taken and the streaming engine's general branch runs on kdevs_post, the copy of kdevs whose `norm` points at each
-    // term's factor BEHIND the filter, with pre_ptr[k] the factor of its input (ensure_factors(), behind learn_sizes()).
+    // are not taken and the streaming engine's general branch -- or the fused engine's general kernel -- runs on kdevs_post, the
+    // copy of kdevs whose `norm` points at each term's factor BEHIND the filter, with pre_ptr[k] the factor of its input
+    // (ensure_factors(), behind learn_sizes()).
     int norm_mode[LCCRF_MAX_KERNELS] = {};   // lccrf_normalization of every term
     int n_modes = 0;                   // terms that are not LCCRF_NORMALIZE_AFTER
     float *ones = nullptr;             // [Fcap][maxN] of 1.0f: the factor behind the filter of a BEFORE or NONE term (lazy)
@@ -273,7 +277,14 @@ struct Engine {
     int rerun_frames(int n);
 
     const float *const *compat_arg() const { return n_compat ? compat_ptr : nullptr; }
-    void choose_sized_engine() { sized_engine = fused_fits && !n_compat && !n_modes ? 2 : 1; }
+    // Lattices that fit the fused plan: Potts terms normalised AFTER run on the fused engine; a handle's single frame of up to
+    // kGeneralMaxPoints active points with a matrix or another mode on the general kernel; anything else streams.
+    static constexpr int kGeneralMaxPoints = 2048;
+    void choose_sized_engine()
+    {
+        const bool general = n_compat || n_modes;
+        sized_engine = !fused_fits ? 1 : !general ? 2 : (F == 1 && active_points(crf) <= kGeneralMaxPoints) ? 4 : 1;
+    }
     // what the streaming step, the plug-in filter and the backward sweep are handed (valid behind ensure_factors())
     const KernelDev *step_kdevs() const { return n_modes ? kdevs_post.data() : kdevs.data(); }
     const float *const *pre_arg() const { return n_modes ? pre_ptr : nullptr; }

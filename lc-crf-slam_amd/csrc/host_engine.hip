@@ -456,6 +456,7 @@ void Engine::recycle()
     unary_is_label = unary_p_valid = false;
     engine_pref = 0;
     engine_used = 1;
+    engine_shape = 0;
     clear_compat();                                   // (the next user's terms start as Potts terms ...
     clear_norm_modes();                               //  ... normalised AFTER the filter)
     sync_views();
@@ -773,6 +774,7 @@ int Engine::run_frame(int n_iter, int with_map, float relax)
     frame_small_used = shape == 1;
     frame_lean_used = shape == 2;
     fused_shape = shape == 0 ? (1024 | 1 << 16) : (512 | 2 << 16);       // lanes per frame | frames per CU
+    engine_shape = 0;
 
     late_pending = true;
     late_iter = n_iter;
@@ -842,6 +844,7 @@ int Engine::inference_sized(int n_iter, int with_map, float relax)
     if (rc) return rc;
     if ((rc = ensure_factors())) return rc;
     engine_used = sized_engine;
+    engine_shape = 0;
     last_with_map = with_map;
     if (perm_on) {
         // locality mode: iterate on the internal-order view, un-permute Q on the way out (densecrf_base.h:65-73 otherwise)
@@ -880,7 +883,16 @@ int Engine::inference_sized(int n_iter, int with_map, float relax)
             }
         }
         fused_shape = launch_inference_fused(crf, kdevs.data(), maxV.data(), maxRow.data(), n_iter, with_map, relax, stream,
-                                             prep_need ? &lean_prep : nullptr);
+                                             prep_need ? &lean_prep : nullptr, &engine_shape);
+        started = true;
+    } else if (sized_engine == 4) {
+        // the fused engine's general kernel (fused_general.hip), behind ensure_factors(): one launch on the factors' views; the
+        // matrices travel by value, from the pinned copies the setters keep
+        const float *mats[LCCRF_MAX_KERNELS] = {};
+        for (size_t k = 0; k < kernels.size(); ++k) mats[k] = compat_ptr[k] ? compat_host + k * (size_t)L * L : nullptr;
+        engine_shape = launch_inference_general(crf, step_kdevs(), maxV.data(), maxRow.data(), n_compat ? mats : nullptr, pre_arg(),
+                                                n_iter, with_map, relax, stream);
+        if (!engine_shape) return fail(LCCRF_E_STATE, "the fused engine's general kernel was chosen for a frame it does not take");
         started = true;
     } else {
         if ((rc = start())) return rc;
