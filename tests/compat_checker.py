@@ -76,23 +76,29 @@ def map_of(Q):
     return np.argmax(Q, 1).astype(np.int16)
 
 
-def forward_f64(U, w, mu, lats, n_iterations, relax=1.0):
-    """Q_T for unary U [N, L], weights w [K] and matrices mu [K, L, L] (tensors of one dtype)"""
-    Q = torch.softmax(-U, 1)
-    for _ in range(n_iterations):
+def compat_product(t, m):
+    """mu applied to the filter's output: out[i][l] = sum_l' m[l][l'] t[i][l'].  The one door the float64 forwards go through, so
+    a test may swap it for a product with a planted fault (tests/grad_support.py: planted)."""
+    return t @ m.T
+
+
+def forward_f64(U, w, mu, lats, n_iterations, relax=1.0, at=None):
+    """Q_T for unary U [N, L], weights w [K] and matrices mu [K, L, L] (tensors of one dtype); at: meanfield_f64.pinned"""
+    Q = mf.pinned(torch.softmax(-U, 1), at, 0)
+    for t in range(n_iterations):
         x = -U
         for k, lat in enumerate(lats):
-            x = x + w[k] * lat.norm.to(U.dtype)[:, None] * (lat.apply(Q) @ mu[k].T)
+            x = x + w[k] * lat.norm.to(U.dtype)[:, None] * compat_product(lat.apply(Q), mu[k])
         P = torch.softmax(x, 1)
-        Q = P if relax == 1.0 else (1.0 - relax) * Q + relax * P
+        Q = mf.pinned(P if relax == 1.0 else (1.0 - relax) * Q + relax * P, at, t + 1)
     return Q
 
 
-def gradients_f64(U, w, mu, lats, n_iterations, relax, G, dtype=mf.D):
+def gradients_f64(U, w, mu, lats, n_iterations, relax, G, dtype=mf.D, at=None):
     """(dL/dU, dL/dw, dL/dmu) of L = <G, Q_T> as float64 numpy arrays; dtype=torch.float32: the same computation in single precision"""
     t = lambda a: torch.as_tensor(np.asarray(a, np.float64)).to(dtype).clone().requires_grad_(True)
     U, w, mu = t(U), t(w), t(mu)
-    Q = forward_f64(U, w, mu, lats, n_iterations, relax)
+    Q = forward_f64(U, w, mu, lats, n_iterations, relax, at)
     (Q * torch.as_tensor(np.asarray(G, np.float64)).to(dtype)).sum().backward()
     z = lambda x, like: x.grad.double().numpy() if x.grad is not None else np.zeros(tuple(like.shape))
     return z(U, U), z(w, w), z(mu, mu)

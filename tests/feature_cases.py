@@ -9,6 +9,12 @@ CASES = ["slam:N5", "slam:N1001", "slam:C3", "generic:multi", "bilateral:c5", "l
          "nt:d1_L3", "nt:d3_L21", "nt:d5_L2", "nt:d6_L3", "nt:d4_L5", "nt:d7_L2", "nt:d8_L33", "nt:d2-5-3_L9"]
 
 
+def gradient_case(name, golden, po, wl):
+    """(problem, image or None) of a case of the gradient lists: its twin (crf_cases.GRADIENT_TWINS) where it has one"""
+    twin = cc.GRADIENT_TWINS.get(name)
+    return twin(golden, po, wl) if twin else case(name, golden, po, wl)
+
+
 def case(name, golden, po, wl):
     """(problem, image or None)"""
     if name.startswith("nt:"):

@@ -1,0 +1,202 @@
+"""Every setting the gradient tests hold the device to, and what each is held to: the lists the GPU tests are parametrised with and,
+per list, the function that builds a setting's inputs and its grad_support.Reference.  The GPU tests call these functions and so
+does tests/test_gradient_bars.py, which needs no GPU: what it measures on the checkers is what the device is measured against."""
+import numpy as np
+
+import batch_cases as bc
+import crf_cases as cc
+import feature_cases as fc
+import grad_support as gs
+import meanfield_f64_features as mff
+import normalization_checker as nc
+from joint_checker import dense                                 # I + 0.3 N(0, 1), seeded: the matrices of the section 1e - 1g tests
+
+T_SET, RELAX_SET = [0, 1, 5, 10], [1.0, 0.7]                      # test_meanfield_backward, test_feature_gradients
+T_SHORT = [0, 1, 5]                                               # test_compatibility, test_joint_gradients, test_normalization, test_labels
+
+
+def grad_prob(pb, seed=1234):
+    return np.random.default_rng(seed).standard_normal((pb["N"], pb["L"]))
+
+
+# The cases whose checker is linearised at the device's own iterates (meanfield_f64.pinned) in every list, from T = 1 on: those that
+# no seed alone brings under the cap with room to spare (notes/gradient_bars.md names each with its bars before and after)
+LINEARISED = {"generic:multi", "slam:N1001", "slam:C3", "c2", "bilateral:c5", "large:c5", "slam1001:s38", "L21:d3_d5", "batch:slam",
+              "nt:d2-5-3_L9"}                                   # a row-metric finding: notes/gradient_bars.md, device errors
+
+
+def linearised(lst, name, T, relax):
+    return name in LINEARISED and T >= 1
+
+
+# Settings that no seed and no linearisation rescues, per list: (case, T, relax) -> why (the figures: notes/gradient_bars.md)
+DROPPED = {
+    "meanfield": {("slam:N5", 1, 1.0): "five points under the SLAM weights: |dL/dU| = 3e-6 |dL/dQ|, the float32 checker is 40 % off: bars 4 and 6.9"},
+    "features": {("slam:N5", 1, 1.0): "as in the meanfield list: bars 4 and 6.9",
+                 ("large:c5", 10, 1.0): "row bar of dL/df 1.0e-2 on the MI355X host's CPU with the linearised checker (0.21 without)",
+                 ("large:c5", 10, 0.7): "row bar of dL/df 8.2e-3 on the MI355X host's CPU with the linearised checker: no room"},
+    "compat": {("generic:d1_L3", 5, 1.0): "mu for mu^T moves dL/dU by 0.03 of its bar (dL/dw, dL/dmu: 595 x)"},
+    "normalization": {("d1_L3:s3", nc.AFTER, 5, 1.0): "the same problem and mode as compat's generic:d1_L3, T = 5, relax 1"},
+}
+
+
+def product(lst, cases, Ts):
+    """the (case, T, relax) settings of a list, and their ids in the form pytest gave the stacked parametrisation"""
+    settings = [(n, T, r) for n in cases for T in Ts for r in RELAX_SET if (n, T, r) not in DROPPED.get(lst, {})]
+    return settings, ["%r-%d-%s" % (r, T, n) for n, T, r in settings]
+
+
+def device_iterates(po, pb, T, relax, mats=None, modes=None, weights=None, nrm=None):
+    """[Q_0 .. Q_T] float32 as the device forms them: the oracle's step path, or with matrices / modes the float32 restatement the
+    forward tests hold the device to bit for bit (normalization_checker.restate_trace_f32)"""
+    o = cc.setup(po.OracleCRF, pb)
+    try:
+        if mats is None and modes is None:
+            o.start_inference()
+            out = [o.probability().copy()]
+            for _ in range(T):
+                o.step_inference(relax)
+                out.append(o.probability().copy())
+            return out
+        K = len(pb["kernels"])
+        w = [np.float32(x) for _, x in pb["kernels"]] if weights is None else weights
+        return nc.restate_trace_f32(o.unary(), nc.feats(pb), w, mats or [None] * K, modes or [nc.AFTER] * K, T, relax, nrm)
+    finally:
+        o.close()
+
+
+# ---- test_meanfield_backward.py: cc.CASES x T_SET x RELAX_SET less DROPPED ----------------------------------------------------------
+MEANFIELD_SETTINGS, MEANFIELD_IDS = product("meanfield", cc.CASES, T_SET)
+
+
+def meanfield(po, wl, golden, name, T, relax):
+    pb, image = cc.gradient_case(name, golden, po, wl)
+    o, lats, U = gs.checker(po, pb)
+    o.close()
+    G = grad_prob(pb)
+    at = device_iterates(po, pb, T, relax) if linearised("meanfield", name, T, relax) else None
+    return dict(pb=pb, image=image, G=G, dims=[lat.d for lat in lats], ref=gs.reference(U, gs.weights(pb), lats, T, relax, G, name, at))
+
+
+# ---- test_feature_gradients.py: fc.CASES x T_SET x RELAX_SET less DROPPED -------------------------------------------------------------
+FEATURE_SETTINGS, FEATURE_IDS = product("features", fc.CASES, T_SET)
+
+
+def features(po, wl, golden, name, T, relax):
+    """`ref`: dL/df_k over the FeatureLattice lattices; `ref_1c`: dL/dU and dL/dw of the same call"""
+    pb, image = fc.gradient_case(name, golden, po, wl)
+    o = cc.setup(po.OracleCRF, pb)
+    lats, U = mff.lattices(o, pb), o.unary().astype(np.float64)
+    G, w = grad_prob(pb), gs.weights(pb)
+    at = device_iterates(po, pb, T, relax) if linearised("features", name, T, relax) else None
+    s = dict(pb=pb, image=image, G=G, dims=[lat.d for lat in lats], ref=gs.feature_reference(U, w, lats, T, relax, G, name, at),
+             ref_1c=gs.reference(U, w, lats, T, relax, G, name, at))
+    o.close()
+    return s
+
+
+# ---- test_compatibility.py: COMPAT_CASES x T_SHORT x RELAX_SET -------------------------------------------------------------------------
+COMPAT_CASES = ["generic:d1_L3", "generic:d3_L21", "generic:multi", "slam:N1001", "image64x48"]
+# with matrices the fixtures generic:d1_L3 and slam:N1001 have bars beyond 1e-2 (notes/normalization.md section 4): here the names
+# stand for the seeds the normalisation tests found for the same shapes
+COMPAT_TWINS = {"generic:d1_L3": "d1_L3:s3", "slam:N1001": "slam1001:s38"}
+
+
+COMPAT_SETTINGS, COMPAT_IDS = product("compat", COMPAT_CASES, T_SHORT)
+
+
+def compat_case(name, golden, po, wl):
+    """(problem, image or None, the name the case goes by in LINEARISED)"""
+    if name in COMPAT_TWINS:
+        return nc.case(COMPAT_TWINS[name], golden, po, wl), None, COMPAT_TWINS[name]
+    return cc.gradient_case(name, golden, po, wl) + (name,)
+
+
+def compat(po, wl, golden, name, T, relax):
+    pb, image, known_as = compat_case(name, golden, po, wl)
+    K, L = len(pb["kernels"]), pb["L"]
+    mats = dense(K, L)
+    o, lats, U = gs.checker(po, pb)
+    o.close()
+    G = grad_prob(pb)
+    at = device_iterates(po, pb, T, relax, mats) if linearised("compat", known_as, T, relax) else None
+    return dict(pb=pb, image=image, G=G, mats=mats, dims=[lat.d for lat in lats],
+                ref=gs.compat_reference(U, gs.weights(pb), mats, lats, T, relax, G, name, at=at))
+
+
+# ---- test_normalization.py: NORM_SETTINGS ------------------------------------------------------------------------------------------
+# L = 2 (1001 points, two 2-D terms: the SLAM shape), L = 3 with d = 1, L = 21 with d = 3 and d = 5.  A setting whose bar exceeds
+# 1e-2 checks nothing; the cases' seeds were chosen so that none does (notes/normalization.md section 4: the fixtures slam:N1001 and
+# generic:d1_L3 each have such settings, and their bars move by a factor of four between CPUs).
+NORM_CASES = ["slam1001:s38", "d1_L3:s3", "L21:d3_d5"]
+NORM_SETTINGS = [(n, m, T, r) for n in NORM_CASES for m in nc.MODES for T in T_SHORT for r in RELAX_SET
+                 if (n, m, T, r) not in DROPPED["normalization"]]
+
+_PREPARED = {}
+
+
+def norm_prepared(name, golden, po, wl):
+    """(problem, raw unary, norms) of a case of normalization_checker.case: computed once, shared by the tests, never changed"""
+    if name not in _PREPARED:
+        pb = nc.case(name, golden, po, wl)
+        o = cc.setup(po.OracleCRF, pb)
+        U = o.unary()
+        nrm = [o.kernel(k)["norm"] for k in range(len(pb["kernels"]))]
+        o.close()
+        _PREPARED[name] = (pb, U, nrm)
+    return _PREPARED[name]
+
+
+def normalization(po, wl, golden, name, mode, T, relax):
+    """every term in `mode`, with the matrices I + 0.3 N(0, 1)"""
+    pb, U, nrm = norm_prepared(name, golden, po, wl)
+    K, L = len(pb["kernels"]), pb["L"]
+    modes, mats = [mode] * K, dense(K, L)
+    w = nc.weights_f32(pb, nrm, modes)
+    o, lats, U64 = gs.checker(po, pb)
+    o.close()
+    G = grad_prob(pb)
+    at = device_iterates(po, pb, T, relax, mats, modes, w, nrm) if linearised("normalization", name, T, relax) else None
+    ref = gs.compat_reference(U64, np.array([float(x) for x in w]), mats, lats, T, relax, G, "%s %s" % (name, nc.MODE_NAMES[mode]), modes, at)
+    return dict(pb=pb, U=U, nrm=nrm, modes=modes, mats=mats, w=w, G=G, dims=[lat.d for lat in lats], ref=ref)
+
+
+# ---- test_labels.py ----------------------------------------------------------------------------------------------------------------
+LANE_LABELS, LANE_TERMS = [4, 5, 8, 9, 16, 17, 32, 33, 64], [1, 8]   # the edges of bwd_lanes' groups; one and eight terms
+TERMLESS_LABELS = [4, 8, 16, 32, 64]
+K8_BATCH_LABELS, K8_BATCH_SETTINGS = [9, 33, 64], ((5, 0.7), (1, 1.0))
+EIGHT = list(range(1, 9))
+LANE_SEEDS = {(4, 1): 3504}                                       # (L, K): seed, where 500 + L leaves a bar beyond the cap (dL/dw 1.7e-2)
+
+
+def lane_group(po, L, K, T, relax):
+    pb = cc.label_problem(400, L, [3] if K == 1 else EIGHT, seed=LANE_SEEDS.get((L, K), 500 + L))
+    o, lats, U = gs.checker(po, pb)
+    o.close()
+    G = grad_prob(pb, L * 10 + K)
+    return dict(pb=pb, G=G, dims=[lat.d for lat in lats], ref=gs.reference(U, gs.weights(pb), lats, T, relax, G, "L=%d K=%d" % (L, K)))
+
+
+def termless(L, T, relax):
+    pb = cc.label_problem(400, L, [], seed=600 + L)
+    G = grad_prob(pb, L)
+    return dict(pb=pb, G=G, dims=[], ref=gs.reference(pb["unary"].astype(np.float64), np.zeros(0), [], T, relax, G, "L=%d K=0" % L))
+
+
+def k8_frames(L):
+    return bc.label_frames(L, [300, 0, 1100, 77, 650], seed=700 + L)
+
+
+def batch_frame(po, fr, G, f, T, relax, name, known_as=""):
+    """frame f (of more than 0 points) of the ragged batch `fr` under the batch's weights, G = fr.grad_prob(..)"""
+    n = int(fr.N[f])
+    pb = dict(fr.probs[f], kernels=[(ft, w) for (ft, _), w in zip(fr.probs[f]["kernels"], fr.w)])
+    o, lats, _ = gs.checker(po, pb)
+    o.close()
+    at = device_iterates(po, dict(pb, unary=fr.U[f, :n]), T, relax) if linearised("batch", known_as, T, relax) else None
+    return dict(pb=pb, dims=[lat.d for lat in lats],
+                ref=gs.reference(fr.U[f, :n].astype(np.float64), np.array(fr.w), lats, T, relax, G[f, :n].astype(np.float64), name, at))
+
+
+# ---- test_batch_backward.py ----------------------------------------------------------------------------------------------------------
+BATCH_FRAMES, BATCH_T, BATCH_GRAD_SEED = (1000, 0, 2000), 5, 7

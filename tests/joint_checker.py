@@ -3,8 +3,8 @@
 The checker is tests/compat_checker.py's forward_f64 run over tests/meanfield_f64_features.py's FeatureLattice lattices bound to
 feature tensors that require gradients: torch autograd gives (dL/dU, dL/dw, dL/dmu, [dL/df_k]) in float64 and, with
 dtype=torch.float32, in single precision.  The bar every output is held to is that of the sections it joins: relative L2 error
-against the float64 checker <= max(GRAD_TOL, 10 x the float32 checker's error), with the floors of assert_matches_compat_checker
-(dL/dU, dL/dw, dL/dmu) and assert_features_match_checker (dL/df).  Not product code."""
+against the float64 checker and the worst row of the per-point outputs, each <= its bar (grad_support.assert_within_bar), with the
+floors of sections 1e (dL/dU, dL/dw, dL/dmu) and 1d (dL/df).  Not product code."""
 import numpy as np
 import torch
 
@@ -39,7 +39,7 @@ def checker(po, pb):
     return o, mff.lattices(o, pb), o.unary().astype(np.float64)
 
 
-def joint_gradients(U, w, mu, lats, n_iterations, relax, G, dtype=D):
+def joint_gradients(U, w, mu, lats, n_iterations, relax, G, dtype=D, at=None):
     """(dL/dU, dL/dw, dL/dmu, [dL/df_k]) of L = <G, Q_T> by autograd through compat_checker.forward_f64 over the lattices bound to
     their own features, the topology fixed; float64 numpy arrays.  dtype=torch.float32: the same computation in single precision."""
     t = lambda a: torch.as_tensor(np.asarray(a, np.float64)).to(dtype).clone().requires_grad_(True)
@@ -47,7 +47,7 @@ def joint_gradients(U, w, mu, lats, n_iterations, relax, G, dtype=D):
     fs = [t(lat.feat32) for lat in lats]
     for lat, f in zip(lats, fs):
         lat.bind(f)
-    Q = ck.forward_f64(U, w, mu, lats, n_iterations, relax)
+    Q = ck.forward_f64(U, w, mu, lats, n_iterations, relax, at)
     (Q * torch.as_tensor(np.asarray(G, np.float64)).to(dtype)).sum().backward()
     for lat in lats:                                             # leave the lattices bound to plain float64 features
         lat.bind(torch.as_tensor(lat.feat32.astype(np.float64)))
@@ -55,26 +55,33 @@ def joint_gradients(U, w, mu, lats, n_iterations, relax, G, dtype=D):
     return z(U), z(w), z(mu), [z(f) for f in fs]
 
 
-def errors(got, ref, w, G):
-    """relative L2 error of (dL/dU, dL/dw, dL/dmu, [dL/df_k]) against `ref`, under the floors of the two sections' bars; an entry
-    of got[3] may be None (not asked for)"""
-    fl_u = 1e-6 * np.linalg.norm(G)
-    fl_w = fl_u * max(np.linalg.norm(w), 1.0)
-    return (gs.rel(got[0], ref[0], fl_u), gs.rel(got[1], ref[1], fl_w), gs.rel(got[2], ref[2], fl_w),
-            [None if a is None else gs.rel(a, r, fl_u) for a, r in zip(got[3], ref[3])])
+def joint_reference(U, w, mu, lats, T, relax, G, name="", at=None):
+    """lccrf_inference_backward_all's outputs against joint_gradients: the floors of the two sections' bars"""
+    fl_u, fl_w = gs.floors_of(G, w)
+    floors = {"dL/dU": fl_u, "dL/dw": fl_w, "dL/dmu": fl_w}
+    floors.update(("dL/df%d" % k, fl_u) for k in range(len(lats)))
 
-
-def bars_of(U, w, mu, lats, T, relax, G):
-    """(the float64 checker's gradients, the bars (dL/dU, dL/dw, dL/dmu, [dL/df_k]), the float32 checker's own errors)"""
-    ref = joint_gradients(U, w, mu, lats, T, relax, G)
-    f32 = errors(joint_gradients(U, w, mu, lats, T, relax, G, dtype=torch.float32), ref, w, G)
-    bar = lambda e: max(gs.GRAD_TOL, 10 * e)
-    return ref, (bar(f32[0]), bar(f32[1]), bar(f32[2]), [bar(e) for e in f32[3]]), f32
+    def grads(dtype):
+        g = joint_gradients(U, w, mu, lats, T, relax, G, dtype=dtype, at=at)
+        return gs._named(g[:3], g[3])
+    return gs.Reference("%s T=%d relax=%g" % (name, T, relax), grads, floors)
 
 
 def grad_prob(pb):
     return np.random.default_rng(1234).standard_normal((pb["N"], pb["L"]))
 
+
+# ---- the settings of test_joint_gradients_match_the_checker --------------------------------------------------------------------------
+CHECK_CASES = ["slam:N1001", "nt:d4_L5", "nt:d2-5-3_L9", "nt:d3_L21", "nt:d8_L33", "nt:d1_L3", "image64x48"]
+# the settings whose bar, computed on the CPU before any GPU run, exceeds 1e-2 for some output (notes/compatibility.md section 6
+# lists the bars): such a setting checks nothing.  (The float32 checker's error, and so the bar, moves with the machine's CPU and
+# thread count: the list is fixed here, the bar is formed where the test runs.)
+DROPPED = {("nt:d1_L3", 5, 1.0),                               # dL/df bar 1.3e-2 (image64x48 is back: another window of the image)
+           ("large:c5", 2, 1.0)}                               # linearised and at 12 seeds alike: row bar of dL/df 9.0e-3 .. 1.1e-2
+SETTINGS = [(n, T, r) for n in CHECK_CASES for T in (0, 1, 5) for r in (1.0, 0.7) if (n, T, r) not in DROPPED] + \
+           [("large:c5", T, r) for T in (1, 2) for r in (1.0, 0.7) if ("large:c5", T, r) not in DROPPED]
+MIXED_CASES, MIXED_SETTINGS = ["generic:multi", "slam:N1001"], [(1, 1.0), (5, 0.7)]      # test_one_term_with_a_matrix_and_one_without
+POTTS_CASES, POTTS_SETTING = ["slam:N1001", "nt:d3_L21"], (5, 0.7)                        # test_potts_handles_give_section_1d_...
 
 _REFS = {}
 
@@ -82,10 +89,10 @@ _REFS = {}
 def reference_for(po, wl, golden, name, T, relax, kind="dense"):
     """What a (case, T, relax) setting is checked against, computed once and shared (leave it unchanged): the problem, its image,
     the matrices handed to the handle (kind "dense": every term; "mixed": even terms only, the others Potts; "potts": none, the
-    checker at identities), G, the weights and the checker's gradients, bars and float32 errors."""
+    checker at identities), G, the weights and the grad_support.Reference of the checker's gradients."""
     key = (name, T, relax, kind)
     if key not in _REFS:
-        pb, image = fc.case(name, golden, po, wl)
+        pb, image = fc.gradient_case(name, golden, po, wl)
         K, L = len(pb["kernels"]), pb["L"]
         mats = dense(K, L)
         if kind != "dense":
@@ -93,9 +100,11 @@ def reference_for(po, wl, golden, name, T, relax, kind="dense"):
         o, lats, U = checker(po, pb)
         G = grad_prob(pb)
         w = gs.weights(pb)
-        ref, bars, f32 = bars_of(U, w, checker_mu(mats, L), lats, T, relax, G)
+        import gradient_settings as gset
+        at = gset.device_iterates(po, pb, T, relax, mats) if gset.linearised("joint" if kind == "dense" else "joint-" + kind, name, T, relax) else None
+        ref = joint_reference(U, w, checker_mu(mats, L), lats, T, relax, G, name if kind == "dense" else "%s (%s)" % (name, kind), at)
         o.close()
-        _REFS[key] = dict(pb=pb, image=image, mats=mats, G=G, w=w, ref=ref, bars=bars, f32=f32)
+        _REFS[key] = dict(pb=pb, image=image, mats=mats, G=G, w=w, ref=ref, dims=[lat.d for lat in lats])
     return _REFS[key]
 
 
@@ -150,15 +159,8 @@ def backward_features(h, dims, T, relax, G):
     return gu.cpu().numpy(), gw[:K].cpu().numpy(), [t.cpu().numpy() for t in gf]
 
 
-def assert_within_bars(got, r, name, T, relax):
-    """every output of `got` against the reference `r` (reference_for); prints one line of figures per setting first"""
-    err = errors(got, r["ref"], r["w"], r["G"])
-    bars = r["bars"]
-    flat = lambda e: list(e[:3]) + [x for x in e[3] if x is not None]
-    fmt = lambda e: "dL/dU %.3g dL/dw %.3g dL/dmu %.3g dL/df %s" % (e[0], e[1], e[2], " ".join("%.3g" % x for x in e[3] if x is not None))
-    print("relative L2 error %s T=%d relax=%g: %s (bars %s)" % (name, T, relax, fmt(err), fmt(bars)))
-    fb = list(bars[:3]) + [b for b, x in zip(bars[3], err[3]) if x is not None]
-    assert all(e <= b for e, b in zip(flat(err), fb)), (flat(err), fb)
+def assert_within_bars(got, r, T):
+    """every output of `got` = (dL/dU, dL/dw, dL/dmu, [dL/df_k or None]) against the reference `r` (reference_for)"""
+    r["ref"].check(gs._named(got[:3], got[3]))
     if T == 0:
         assert np.all(got[1] == 0) and np.all(got[2] == 0) and all(np.all(a == 0) for a in got[3] if a is not None)
-    return err

@@ -113,7 +113,7 @@ def lattices(crf, pb):
     return [FeatureLattice(crf.kernel(k), f) for k, (f, _) in enumerate(pb["kernels"])]
 
 
-def feature_gradients(U, w, lats, n_iterations, relax, G, dtype=D, feats=None):
+def feature_gradients(U, w, lats, n_iterations, relax, G, dtype=D, feats=None, at=None):
     """(dL/dU, dL/dw, [dL/df_k]) of L = <G, Q_T> by autograd, the topology fixed, as float64 numpy arrays.  dtype=torch.float32
     runs the same computation in single precision.  feats: float64 features to evaluate at (default: the lattices' own)."""
     U = torch.as_tensor(np.asarray(U, np.float64)).to(dtype).clone().requires_grad_(True)
@@ -123,14 +123,14 @@ def feature_gradients(U, w, lats, n_iterations, relax, G, dtype=D, feats=None):
         f = np.asarray(lat.feat32 if feats is None else feats[k], np.float64)
         fs.append(torch.as_tensor(f).to(dtype).clone().requires_grad_(True))
         lat.bind(fs[-1])
-    Q = mf.forward(U, w, lats, n_iterations, relax)
+    Q = mf.forward(U, w, lats, n_iterations, relax, at)
     loss = (Q * torch.as_tensor(np.asarray(G, np.float64)).to(dtype)).sum()
     loss.backward()
     for lat in lats:                                             # leave the lattices bound to plain float64 features
         lat.bind(torch.as_tensor(lat.feat32.astype(np.float64)))
     zero = lambda t: np.zeros(tuple(t.shape))
     return (U.grad.double().numpy(), w.grad.double().numpy() if w.grad is not None else np.zeros(len(lats)),
-            [f.grad.double().numpy() if f.grad is not None else zero(f) for f in fs], float(loss))
+            [f.grad.double().numpy() if f.grad is not None else zero(f) for f in fs], float(loss.detach()))
 
 
 def corner_to_feature(gb, scale, rank):

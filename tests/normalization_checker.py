@@ -83,25 +83,25 @@ def factors_f64(lat, mode, dtype):
     return None, None
 
 
-def forward_f64(U, w, mu, lats, modes, n_iterations, relax=1.0):
-    """Q_T for unary U [N, L], weights w [K] and matrices mu [K, L, L] (tensors of one dtype)"""
-    Q = torch.softmax(-U, 1)
-    for _ in range(n_iterations):
+def forward_f64(U, w, mu, lats, modes, n_iterations, relax=1.0, at=None):
+    """Q_T for unary U [N, L], weights w [K] and matrices mu [K, L, L] (tensors of one dtype); at: meanfield_f64.pinned"""
+    Q = mf.pinned(torch.softmax(-U, 1), at, 0)
+    for it in range(n_iterations):
         x = -U
         for k, lat in enumerate(lats):
             a, b = factors_f64(lat, modes[k], U.dtype)
-            t = lat.apply(Q if b is None else b[:, None] * Q) @ mu[k].T
+            t = ck.compat_product(lat.apply(Q if b is None else b[:, None] * Q), mu[k])
             x = x + w[k] * (t if a is None else a[:, None] * t)
         P = torch.softmax(x, 1)
-        Q = P if relax == 1.0 else (1.0 - relax) * Q + relax * P
+        Q = mf.pinned(P if relax == 1.0 else (1.0 - relax) * Q + relax * P, at, it + 1)
     return Q
 
 
-def gradients_f64(U, w, mu, lats, modes, n_iterations, relax, G, dtype=mf.D):
+def gradients_f64(U, w, mu, lats, modes, n_iterations, relax, G, dtype=mf.D, at=None):
     """(dL/dU, dL/dw, dL/dmu) of L = <G, Q_T> as float64 numpy arrays; dtype=torch.float32: the same computation in single precision"""
     t = lambda a: torch.as_tensor(np.asarray(a, np.float64)).to(dtype).clone().requires_grad_(True)
     U, w, mu = t(U), t(w), t(mu)
-    Q = forward_f64(U, w, mu, lats, modes, n_iterations, relax)
+    Q = forward_f64(U, w, mu, lats, modes, n_iterations, relax, at)
     (Q * torch.as_tensor(np.asarray(G, np.float64)).to(dtype)).sum().backward()
     z = lambda x, like: x.grad.double().numpy() if x.grad is not None else np.zeros(tuple(like.shape))
     return z(U, U), z(w, w), z(mu, mu)

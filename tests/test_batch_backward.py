@@ -12,7 +12,7 @@ import pytest
 import batch_cases as bc
 import crf_cases as cc
 import grad_support as gs
-import meanfield_f64 as mf
+import gradient_settings as gset
 from abi_support import assert_declared_exported_bound, dev, hip_malloc, lib  # noqa: F401
 
 pkg = importlib.import_module("lc-crf-slam_amd")
@@ -84,22 +84,22 @@ def test_every_frame_has_the_bits_of_its_handle(wl, golden, kind):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("relax", [1.0, 0.7])
+@pytest.mark.parametrize("relax", gset.RELAX_SET)
 def test_batch_gradients_match_the_checker(po, wl, golden, relax):
-    fr = bc.slam_frames(golden, wl, Ns=(1000, 0, 2000))
+    """every frame of more than 0 points under the bars of grad_support.assert_within_bar (L2 and worst row) and, as before them,
+    the L2 errors of dL/dU and dL/dw under GRAD_TOL itself, dL/dw against a floor of 1e-6 |dL/dQ|"""
+    fr = bc.slam_frames(golden, wl, Ns=gset.BATCH_FRAMES)
     b = fr.batch()
-    T = 5
-    G = fr.grad_prob(7)
+    T = gset.BATCH_T
+    G = fr.grad_prob(gset.BATCH_GRAD_SEED)
     gu, gw = gs.batch_backward(b, T, relax, G, fr.K)
-    for f in (0, 2):
-        n = fr.N[f]
-        pb = dict(fr.probs[f], kernels=[(ft, w) for (ft, _), w in zip(fr.probs[f]["kernels"], fr.w)])
-        o = cc.setup(po.OracleCRF, pb)
-        lats = mf.lattices(o, fr.K)
-        ref_u, ref_w = mf.gradients(fr.U[f, :n].astype(np.float64), np.array(fr.w), lats, T, relax, G[f, :n].astype(np.float64))
-        eu = np.linalg.norm(gu[f, :n] - ref_u) / max(np.linalg.norm(ref_u), 1e-6 * np.linalg.norm(G[f, :n]))
-        ew = np.linalg.norm(gw[f] - ref_w) / max(np.linalg.norm(ref_w), 1e-6 * np.linalg.norm(G[f, :n]))
-        print("frame N=%d relax=%g: relative L2 error dL/dU %.3g dL/dw %.3g" % (n, relax, eu, ew))
+    for f, n in enumerate(fr.N):
+        if n == 0:
+            continue
+        r = gset.batch_frame(po, fr, G, f, T, relax, "frame N=%d" % n, "batch:slam")["ref"]
+        r.check({"dL/dU": gu[f, :n], "dL/dw": gw[f]})
+        eu = gs.rel(gu[f, :n], r.ref["dL/dU"], r.floors["dL/dU"])
+        ew = gs.rel(gw[f], r.ref["dL/dw"], r.floors["dL/dU"])
         assert eu <= gs.GRAD_TOL and ew <= gs.GRAD_TOL, (eu, ew)
     b.close()
 

@@ -13,6 +13,7 @@ import pytest
 import compat_checker as ck
 import crf_cases as cc
 import grad_support as gs
+import gradient_settings as gset
 import meanfield_f64 as mf
 from abi_support import assert_declared_exported_bound, dev, lib  # noqa: F401
 
@@ -282,42 +283,27 @@ def _backward_compat(h, T, relax, G, K, L, with_u=True, with_w=True):
 
 
 def assert_matches_compat_checker(got, U, w, mats, lats, T, relax, G, name=""):
-    """The bar of tests/grad_support.py (assert_matches_checker), applied to dL/dmu as to dL/dU and dL/dw: relative L2
-    error against the float64 checker <= max(1e-4, 10 x that of the float32 checker); gradients below 1e-6 |dL/dQ| (x max(|w|, 1)
-    for dL/dw and dL/dmu) are compared in absolute terms against that floor."""
-    import torch
-    mu = np.stack(mats).astype(np.float64)
-    ref = ck.gradients_f64(U, w, mu, lats, T, relax, G)
-    f32 = ck.gradients_f64(U, w, mu, lats, T, relax, G, dtype=torch.float32)
-    fl_u = 1e-6 * np.linalg.norm(G)
-    fl_w = fl_u * max(np.linalg.norm(w), 1.0)
-    floors = (fl_u, fl_w, fl_w)
-    errs = [gs.rel(a, b, fl) for a, b, fl in zip(got, ref, floors)]
-    bars = [max(gs.GRAD_TOL, 10 * gs.rel(a, b, fl)) for a, b, fl in zip(f32, ref, floors)]
-    print("relative L2 error %s T=%d relax=%g: dL/dU %.3g dL/dw %.3g dL/dmu %.3g (bars %.3g %.3g %.3g)"
-          % ((name, T, relax) + tuple(errs) + tuple(bars)))
-    assert all(e <= b for e, b in zip(errs, bars)), (errs, bars)
-    return ref, bars, floors
+    """The bar of tests/grad_support.py (assert_within_bar), applied to dL/dmu as to dL/dU and dL/dw; gradients below 1e-6 |dL/dQ|
+    (x max(|w|, 1) for dL/dw and dL/dmu) are compared in absolute terms against that floor.  Returns the grad_support.Reference."""
+    r = gs.compat_reference(U, w, mats, lats, T, relax, G, name)
+    r.check(dict(zip(("dL/dU", "dL/dw", "dL/dmu"), got)))
+    return r
 
 
-GRAD_CASES = ["generic:d1_L3", "generic:d3_L21", "generic:multi", "slam:N1001", "image64x48"]
+GRAD_CASES = gset.COMPAT_CASES
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", GRAD_CASES)
-@pytest.mark.parametrize("T", [0, 1, 5])
-@pytest.mark.parametrize("relax", [1.0, 0.7])
+@pytest.mark.parametrize("name,T,relax", gset.COMPAT_SETTINGS, ids=gset.COMPAT_IDS)
 def test_compat_gradients_match_the_checker(po, wl, golden, name, T, relax):
-    """Measured on the MI355X: notes/compatibility.md lists the largest error per case."""
-    pb, image = cc.case(name, golden, po, wl)
+    """Measured on the MI355X: notes/gradient_bars.md lists the largest error per case."""
+    s = gset.compat(po, wl, golden, name, T, relax)
+    pb, image, G, mats = s["pb"], s["image"], s["G"], s["mats"]
     K, L = len(pb["kernels"]), pb["L"]
-    mats = _dense(K, L)
-    o, lats, U = gs.checker(po, pb)
-    G = np.random.default_rng(1234).standard_normal((pb["N"], L))
     h, keep = gs.gpu_handle(pb, image)
     _set_all(h, mats)
     got = _backward_compat(h, T, relax, G, K, L)
-    assert_matches_compat_checker(got, U, gs.weights(pb), mats, lats, T, relax, G, name)
+    s["ref"].check(dict(zip(("dL/dU", "dL/dw", "dL/dmu"), got)))
     if T == 0:
         assert np.all(got[2] == 0) and np.all(got[1] == 0)
     # lccrf_inference_backward on the same handle: the same dL/dU and dL/dw
@@ -335,22 +321,23 @@ def test_compat_gradients_match_the_checker(po, wl, golden, name, T, relax):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["generic:d3_L21", "slam:N1001"])
 def test_gradient_at_a_potts_term_is_that_at_the_identity(po, wl, golden, name):
-    pb, image = cc.case(name, golden, po, wl)
+    pb, image, _ = gset.compat_case(name, golden, po, wl)
     K, L = len(pb["kernels"]), pb["L"]
     o, lats, U = gs.checker(po, pb)
     G = np.random.default_rng(4).standard_normal((pb["N"], L))
     T, relax = 5, 0.7
     h, keep = gs.gpu_handle(pb, image)
     a = _backward_compat(h, T, relax, G, K, L)
-    _, bars, floors = assert_matches_compat_checker(a, U, gs.weights(pb), _eyes(K, L), lats, T, relax, G, name + " (no matrix)")
+    r = assert_matches_compat_checker(a, U, gs.weights(pb), _eyes(K, L), lats, T, relax, G, name + " (no matrix)")
+    bar, floor = r.bars()["dL/dmu"][0], r.floors["dL/dmu"]
     h2, keep2 = gs.gpu_handle(pb, image)
     _set_all(h2, _eyes(K, L))
     b = _backward_compat(h2, T, relax, G, K, L)
     assert_matches_compat_checker(b, U, gs.weights(pb), _eyes(K, L), lats, T, relax, G, name + " (identity)")
     assert cc.same_bits(a[0], b[0]) and cc.same_bits(a[1], b[1])
-    between = gs.rel(a[2], b[2], floors[2])                       # ... and one against the other, to the same bar
-    print("dL/dmu without a matrix against an explicit identity, %s: relative L2 difference %.3g (bar %.3g)" % (name, between, bars[2]))
-    assert between <= bars[2]
+    between = gs.rel(a[2], b[2], floor)                           # ... and one against the other, to the same bar
+    print("dL/dmu without a matrix against an explicit identity, %s: relative L2 difference %.3g (bar %.3g)" % (name, between, bar))
+    assert between <= bar
     h.close(), h2.close()
 
 

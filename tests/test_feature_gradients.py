@@ -18,13 +18,13 @@ import batch_cases as bc
 import crf_cases as cc
 import feature_cases as fc
 import grad_support as gs
+import gradient_settings as gset
 import kernel_resources as kr
 import meanfield_f64_features as mff
 from abi_support import assert_declared_exported_bound, dev, hip_malloc, lib  # noqa: F401
 
 pkg = importlib.import_module("lc-crf-slam_amd")
 NEW_SYMBOLS = ("lccrf_inference_backward_features", "lccrf_batch_inference_backward_features")
-GRAD_TOL = gs.GRAD_TOL
 
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------------
@@ -76,29 +76,6 @@ def _backward_features(h, dims, T, relax, G, skip=(), unary=True, weights=True):
     return gu.cpu().numpy(), gw[:K].cpu().numpy(), [t.cpu().numpy() if t is not None else None for t in gf]
 
 
-def assert_features_match_checker(gf, U, w, lats, T, relax, G, name=""):
-    """The bar of test_gradients_match_the_checker, per term: relative L2 error against the float64 checker <= max(1e-4, 10 x
-    that of the same autograd computation in float32), gradients below 1e-6 of |dL/dQ| compared in absolute terms against
-    that floor.  Returns the checker's (dL/dU, dL/dw, [dL/df])."""
-    import torch
-    ref_u, ref_w, ref_f, _ = mff.feature_gradients(U, w, lats, T, relax, G)
-    _, _, f32_f, _ = mff.feature_gradients(U, w, lats, T, relax, G, dtype=torch.float32)
-    floor = 1e-6 * np.linalg.norm(G)
-    bad = []
-    for k, (a, r, s) in enumerate(zip(gf, ref_f, f32_f)):
-        if a is None:
-            continue
-        e, bar = gs.rel(a, r, floor), max(GRAD_TOL, 10 * gs.rel(s, r, floor))
-        print("relative L2 error %s T=%d relax=%g term %d: dL/df %.3g (bar %.3g, float32 checker %.3g, |dL/df| %.3g)"
-              % (name, T, relax, k, e, bar, gs.rel(s, r, floor), np.linalg.norm(r)))
-        if not e <= bar:
-            bad.append("term %d: %.3g (bar %.3g)" % (k, e, bar))
-        if T == 0:
-            assert np.all(a == 0)
-    assert not bad, "relative L2 error of dL/df: " + ", ".join(bad)
-    return ref_u, ref_w, ref_f
-
-
 def _checker(po, pb):
     o = cc.setup(po.OracleCRF, pb)
     return o, mff.lattices(o, pb), o.unary().astype(np.float64)
@@ -106,26 +83,24 @@ def _checker(po, pb):
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", fc.CASES)
-@pytest.mark.parametrize("T", [0, 1, 5, 10])
-@pytest.mark.parametrize("relax", [1.0, 0.7])
+@pytest.mark.parametrize("name,T,relax", gset.FEATURE_SETTINGS, ids=gset.FEATURE_IDS)
 def test_feature_gradients_match_the_checker(po, wl, golden, name, T, relax):
     """dL/df of every term against the float64 checker on the cases of test_gradients_match_the_checker without the tie cases
-    (tests/feature_cases.py; large:c5 runs in locality mode: 8704 points), under that test's bar.  dL/dU and dL/dw of the same
-    call are held to the same checker too.  Measured on the MI355X (the figures are printed, -s): beyond 1e-4 are generic:multi
-    (worst T = 5, relax 1: terms 0 / 2 1.04e-3 / 1.05e-3, the float32 checker 1.4e-4 / 1.5e-4; T = 5 and 10, relax 0.7: 8.0e-4,
-    float32 checker 9.0e-4; term 1 up to 1.9e-4 against 7.6e-3) and image64x48 at T = 1 (relax 1 / 0.7: RGB term 9.5e-4 / 6.7e-4,
-    float32 checker 6.2e-4 / 4.3e-4; position term 1.8e-4 against 1.4e-4) -- all inside 10 x the float32 checker's error; every
-    other case and setting is <= 4e-5."""
-    pb, image = fc.case(name, golden, po, wl)
-    o, lats, U = _checker(po, pb)
-    G = np.random.default_rng(1234).standard_normal((pb["N"], pb["L"]))
-    h, keep = gs.gpu_handle(pb, image)
-    gu, gw, gf = _backward_features(h, _dims(pb, image), T, relax, G)
+    (tests/feature_cases.py; large:c5 runs in locality mode), under that test's bars: relative L2 error and worst row, every bar
+    capped at 1e-2 (grad_support.assert_within_bar).  dL/dU and dL/dw of the same call are held to the same checker too.  The
+    settings, the seeds behind the names and the three settings dropped: tests/gradient_settings.py.  Measured on the MI355X (the
+    figures are printed, -s; notes/gradient_bars.md section 4): every L2 error of dL/df is <= 6e-5 (nt:d8_L33, bar 4.2e-4) and
+    every worst row <= 5.1e-4 (nt:d2-5-3_L9, T = 5, relax 1, bar 1.8e-3); the largest bar is the row bar of image64x48, T = 10,
+    relax 1, RGB term: 5.5e-3."""
+    s = gset.features(po, wl, golden, name, T, relax)
+    h, keep = gs.gpu_handle(s["pb"], s["image"])
+    gu, gw, gf = _backward_features(h, _dims(s["pb"], s["image"]), T, relax, s["G"])
     h.close()
     assert all(np.isfinite(a).all() for a in gf)
-    assert_features_match_checker(gf, U, gs.weights(pb), lats, T, relax, G, name)
-    gs.assert_matches_checker(gu, gw, U, gs.weights(pb), lats, T, relax, G, name)
+    s["ref"].check({"dL/df%d" % k: a for k, a in enumerate(gf)})
+    s["ref_1c"].check({"dL/dU": gu, "dL/dw": gw})
+    if T == 0:
+        assert np.all(gw == 0) and all(np.all(a == 0) for a in gf)
 
 
 @pytest.mark.gpu
@@ -247,15 +222,14 @@ def test_every_frame_of_a_batch_has_the_bits_of_its_handle(wl, golden, kind):
 def test_locality_mode_frame_gives_the_gradient_in_the_callers_order(po, golden):
     """one frame of >= 8192 points after a locality-mode inference(): the lattices are re-built the plain way, the gradient comes
     in the caller's point order (same bar), and a handle that never ran in locality mode gives the same bits"""
-    pb, _ = fc.case("large:c5", golden, po, None)
+    s = gset.features(po, None, golden, "large:c5", 5, 1.0)      # (the setting of test_feature_gradients_match_the_checker)
+    pb, G = s["pb"], s["G"]
     assert pb["N"] >= 8192
     dims = _dims(pb, None)
-    o, lats, U = _checker(po, pb)
-    G = np.random.default_rng(3).standard_normal((pb["N"], pb["L"]))
     h = cc.setup(pkg.DenseCRFHIP, pb)
     h.inference(5, True)                                         # locality mode
     gu, gw, gf = _backward_features(h, dims, 5, 1.0, G)
-    assert_features_match_checker(gf, U, gs.weights(pb), lats, 5, 1.0, G, "large:c5 after inference()")
+    s["ref"].check({"dL/df%d" % k: a for k, a in enumerate(gf)})
     h2 = cc.setup(pkg.DenseCRFHIP, pb)
     d = _backward_features(h2, dims, 5, 1.0, G)
     assert cc.same_bits(gu, d[0]) and all(cc.same_bits(x, y) for x, y in zip(gf, d[2]))
@@ -330,14 +304,13 @@ def test_torch_mean_field_features_matches_the_checker(po, wl, golden, name):
     """mean_field_features: unary, features and weights at once against the checker (same bar), Q against the handle's bits"""
     import torch
     ag = importlib.import_module("lc-crf-slam_amd.autograd")
-    pb, _ = fc.case(name, golden, po, wl)
-    o, lats, U = _checker(po, pb)
-    w = gs.weights(pb)
-    G = np.random.default_rng(21).standard_normal((pb["N"], pb["L"]))
+    T, relax = 5, 0.7
+    s = gset.features(po, wl, golden, name, T, relax)            # (the setting of test_feature_gradients_match_the_checker)
+    pb, G = s["pb"], s["G"]
+    U, w = cc.setup(po.OracleCRF, pb).unary(), gs.weights(pb)
     u = torch.from_numpy(U.astype(np.float32)).cuda().requires_grad_(True)
     wt = torch.tensor(w, dtype=torch.float32, requires_grad=True)
     fs = [torch.from_numpy(np.ascontiguousarray(f, np.float32)).cuda().requires_grad_(True) for f, _ in pb["kernels"]]
-    T, relax = 5, 0.7
     q = ag.mean_field_features(u, fs, wt, T, relax)
     h = cc.setup(pkg.DenseCRFHIP, pb)
     h.inference(T, False, relax)
@@ -345,8 +318,8 @@ def test_torch_mean_field_features_matches_the_checker(po, wl, golden, name):
     h.close()
     q.backward(torch.from_numpy(G.astype(np.float32)).cuda())
     torch.cuda.synchronize()
-    assert_features_match_checker([f.grad.cpu().numpy() for f in fs], U, w, lats, T, relax, G, name)
-    gs.assert_matches_checker(u.grad.cpu().numpy(), wt.grad.numpy(), U, w, lats, T, relax, G, name)
+    s["ref"].check({"dL/df%d" % k: f.grad.cpu().numpy() for k, f in enumerate(fs)})
+    s["ref_1c"].check({"dL/dU": u.grad.cpu().numpy(), "dL/dw": wt.grad.numpy()})
 
 
 @pytest.mark.gpu
@@ -379,9 +352,7 @@ def test_learned_kernel_crf_chain_rule_and_fit(po, wl):
     def chain(gf):
         return [-(gf[0] * feats[0].astype(np.float64)).sum(0), np.array([-(gf[1] * feats[1].astype(np.float64)).sum()])]
     for k, (got, r, s) in enumerate(zip([x.grad.cpu().numpy() for x in layer.log_sd], chain(ref_f), chain(f32_f))):
-        e, bar = gs.rel(got, r), max(GRAD_TOL, 10 * gs.rel(s, r))
-        print("relative error of log_sd.grad term %d: %.3g (bar %.3g); grad %s checker %s" % (k, e, bar, got, r))
-        assert e <= bar
+        gs.assert_within_bar("log_sd.grad of term %d (grad %s checker %s)" % (k, got, r), got, r, s)
     # fit: targets from the true bandwidths, a start at wrong ones
     with torch.no_grad():
         target = layer(U).clone()

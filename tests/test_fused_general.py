@@ -14,6 +14,7 @@ import pytest
 import compat_checker as ck
 import crf_cases as cc
 import grad_support as gs
+import gradient_settings as gset
 import normalization_checker as nc
 from abi_support import lib  # noqa: F401
 
@@ -270,13 +271,6 @@ def test_compat_layer_forward_is_the_restatement_and_its_backward_matches_the_ch
     got = (u.grad.cpu().numpy(), layer.weights.grad.numpy(), layer.compat.grad.numpy())
     o, lats, U64 = gs.checker(po, pb)
     o.close()
-    mu = np.stack(mats).astype(np.float64)
-    want = ck.gradients_f64(U64, np.array(w0), mu, lats, T, relax, G)
-    f32 = ck.gradients_f64(U64, np.array(w0), mu, lats, T, relax, G, dtype=torch.float32)
-    fl_u = 1e-6 * np.linalg.norm(G)
-    fl_w = fl_u * max(np.linalg.norm(w0), 1.0)
-    for what, a, b, c, fl in zip(("dL/dU", "dL/dw", "dL/dmu"), got, want, f32, (fl_u, fl_w, fl_w)):
-        err, bar = gs.rel(a, b, fl), max(gs.GRAD_TOL, 10 * gs.rel(c, b, fl))
-        print("layer, relative L2 error %s: %.3g (bar %.3g)" % (what, err, bar))
-        assert err <= bar, (what, err, bar)
+    at = gset.device_iterates(po, pb, T, relax, mats)            # (the fixture's bars need it: tests/gradient_settings.py, LINEARISED)
+    gs.compat_reference(U64, np.array(w0), mats, lats, T, relax, G, "layer", at=at).check(dict(zip(("dL/dU", "dL/dw", "dL/dmu"), got)))
     layer.close()

@@ -91,13 +91,7 @@ def test_joint_softmax_kernels_use_no_scratch():
 
 
 # ---- GPU: against the checker ---------------------------------------------------------------------------------------------
-CHECK_CASES = ["slam:N1001", "nt:d4_L5", "nt:d2-5-3_L9", "nt:d3_L21", "nt:d8_L33", "nt:d1_L3", "image64x48"]
-# the settings whose bar, computed on the CPU before any GPU run, exceeds 1e-2 for some output (notes/compatibility.md section 6
-# lists the bars): such a setting checks nothing.  (The float32 checker's error, and so the bar, moves with the machine's CPU and
-# thread count: the list is fixed here, the bar is formed where the test runs.)
-DROPPED = {("nt:d1_L3", 5, 1.0), ("image64x48", 1, 1.0), ("image64x48", 5, 1.0), ("image64x48", 5, 0.7)}
-SETTINGS = [(n, T, r) for n in CHECK_CASES for T in (0, 1, 5) for r in (1.0, 0.7) if (n, T, r) not in DROPPED] + \
-           [("large:c5", T, r) for T in (1, 2) for r in (1.0, 0.7)]
+SETTINGS = jc.SETTINGS
 
 
 def _handle(r):
@@ -121,17 +115,17 @@ def test_joint_gradients_match_the_checker(po, wl, golden, name, T, relax):
     r = jc.reference_for(po, wl, golden, name, T, relax)
     got = _run(r, T, relax)
     assert all(np.isfinite(a).all() for a in got[:3]) and all(np.isfinite(a).all() for a in got[3])
-    jc.assert_within_bars(got, r, name, T, relax)
+    jc.assert_within_bars(got, r, T)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["generic:multi", "slam:N1001"])
-@pytest.mark.parametrize("T,relax", [(1, 1.0), (5, 0.7)])
+@pytest.mark.parametrize("name", jc.MIXED_CASES)
+@pytest.mark.parametrize("T,relax", jc.MIXED_SETTINGS)
 def test_one_term_with_a_matrix_and_one_without(po, wl, golden, name, T, relax):
     """even terms carry a matrix, odd terms are Potts: d_grad_compat[k] of a Potts term is the derivative at the identity"""
     r = jc.reference_for(po, wl, golden, name, T, relax, "mixed")
     assert any(m is None for m in r["mats"]) and any(m is not None for m in r["mats"])
-    jc.assert_within_bars(_run(r, T, relax), r, name + " (mixed)", T, relax)
+    jc.assert_within_bars(_run(r, T, relax), r, T)
 
 
 # ---- GPU: bits ------------------------------------------------------------------------------------------------------------
@@ -179,12 +173,12 @@ def test_bits_of_section_1e_determinism_null_outputs_and_state(po, wl, golden, n
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["slam:N1001", "nt:d3_L21"])
+@pytest.mark.parametrize("name", jc.POTTS_CASES)
 def test_potts_handles_give_section_1d_and_identities_stay_within_the_bar(po, wl, golden, name):
     """Without matrices and without d_grad_compat the call is section 1d's, bit for bit.  With explicit identity matrices dL/df is
     held to the bar against the Potts handle's; whether the two are in fact the same bits is printed (notes/compatibility.md
     section 6 records it), not asserted."""
-    T, relax = 5, 0.7
+    T, relax = jc.POTTS_SETTING
     r = jc.reference_for(po, wl, golden, name, T, relax, "potts")
     pb, image, G = r["pb"], r["image"], r["G"]
     K, L, dims = len(pb["kernels"]), pb["L"], jc.dims_of(pb, image)
@@ -193,17 +187,17 @@ def test_potts_handles_give_section_1d_and_identities_stay_within_the_bar(po, wl
     a = jc.backward_all(h, dims, L, T, relax, G, compat=False)
     assert cc.same_bits(a[0], f[0]) and cc.same_bits(a[1], f[1]) and _same(a[3], f[2]) and np.isnan(a[2]).all()
     b = jc.backward_all(h, dims, L, T, relax, G)                 # ... and with dL/dmu at the identity: every output within the bar
-    jc.assert_within_bars(b, r, name + " (no matrix)", T, relax)
+    jc.assert_within_bars(b, r, T)
     h2, keep2 = gs.gpu_handle(pb, image)
     jc.set_all(h2, jc.eyes(K, L))
     c = jc.backward_all(h2, dims, L, T, relax, G)
-    jc.assert_within_bars(c, r, name + " (identity)", T, relax)
-    floor = 1e-6 * np.linalg.norm(G)
+    jc.assert_within_bars(c, r, T)
+    floor, bars = 1e-6 * np.linalg.norm(G), r["ref"].bars()
     for k in range(K):
-        between = gs.rel(c[3][k], a[3][k], floor)
+        between, bar = gs.rel(c[3][k], a[3][k], floor), bars["dL/df%d" % k][0]
         print("dL/df of term %d with explicit identities against the Potts handle's, %s: relative L2 difference %.3g (bar %.3g), "
-              "bit-identical: %s" % (k, name, between, r["bars"][3][k], cc.same_bits(c[3][k], a[3][k])))
-        assert between <= r["bars"][3][k]
+              "bit-identical: %s" % (k, name, between, bar, cc.same_bits(c[3][k], a[3][k])))
+        assert between <= bar
     h.close(), h2.close()
 
 

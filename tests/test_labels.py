@@ -18,6 +18,7 @@ import pytest
 import batch_cases as bc
 import crf_cases as cc
 import grad_support as gs
+import gradient_settings as gset
 import meanfield_f64 as mf
 from abi_support import lib  # noqa: F401
 
@@ -318,58 +319,53 @@ def test_ninth_term_and_ninth_dimension_are_rejected_and_the_handle_stays_usable
 
 # ---- GPU: backward --------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
-@pytest.mark.parametrize("L", [4, 5, 8, 9, 16, 17, 32, 33, 64])
-@pytest.mark.parametrize("K", [1, 8])
-@pytest.mark.parametrize("T", [0, 1, 5])
-@pytest.mark.parametrize("relax", [1.0, 0.7])
+@pytest.mark.parametrize("L", gset.LANE_LABELS)
+@pytest.mark.parametrize("K", gset.LANE_TERMS)
+@pytest.mark.parametrize("T", gset.T_SHORT)
+@pytest.mark.parametrize("relax", gset.RELAX_SET)
 def test_gradients_match_the_checker_in_every_lane_group(po, L, K, T, relax):
     """lccrf_inference_backward at the edges of its lane groups (bwd_lanes: 1, 2, 4, 8, 16 lanes per row), one and eight terms, at
     the bar of test_gradients_match_the_checker.  The weights of label_problem keep the rows unsaturated, so the gradients compared
     are far above that test's floor."""
-    pb = cc.label_problem(400, L, [3] if K == 1 else EIGHT, seed=500 + L)
-    o, lats, U = gs.checker(po, pb)
-    G = np.random.default_rng(L * 10 + K).standard_normal((pb["N"], L))
-    h = cc.setup(pkg.DenseCRFHIP, pb)
-    gu, gw = gs.backward(h, T, relax, G, K)
-    h.close(), o.close()
-    ref_u, ref_w = gs.assert_matches_checker(gu, gw, U, gs.weights(pb), lats, T, relax, G, "L=%d K=%d" % (L, K))
-    assert np.linalg.norm(ref_u) > 1e-3 * np.linalg.norm(G)
+    s = gset.lane_group(po, L, K, T, relax)
+    h = cc.setup(pkg.DenseCRFHIP, s["pb"])
+    gu, gw = gs.backward(h, T, relax, s["G"], K)
+    h.close()
+    s["ref"].check({"dL/dU": gu, "dL/dw": gw})
+    if T == 0:
+        assert np.all(gw == 0)
+    assert np.linalg.norm(s["ref"].ref["dL/dU"]) > 1e-3 * np.linalg.norm(s["G"])
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("L", [4, 8, 16, 32, 64])
+@pytest.mark.parametrize("L", gset.TERMLESS_LABELS)
 def test_gradients_without_terms_in_every_lane_group(po, L):
-    pb = cc.label_problem(400, L, [], seed=600 + L)
-    h = cc.setup(pkg.DenseCRFHIP, pb)
-    G = np.random.default_rng(L).standard_normal((400, L))
-    U = pb["unary"].astype(np.float64)
-    for T in (0, 1, 5):
-        for relax in (1.0, 0.7):
-            gu, _ = gs.backward(h, T, relax, G, 0)
-            gs.assert_matches_checker(gu, np.zeros(0), U, np.zeros(0), [], T, relax, G, "L=%d K=0" % L)
+    h = None
+    for T in gset.T_SHORT:
+        for relax in gset.RELAX_SET:
+            s = gset.termless(L, T, relax)
+            h = h or cc.setup(pkg.DenseCRFHIP, s["pb"])
+            gu, _ = gs.backward(h, T, relax, s["G"], 0)
+            s["ref"].check({"dL/dU": gu})
     h.close()
 
 
-def _k8_frames(L):
-    return bc.label_frames(L, [300, 0, 1100, 77, 650], seed=700 + L)
+_k8_frames = gset.k8_frames
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("L", [9, 33, 64])
+@pytest.mark.parametrize("L", gset.K8_BATCH_LABELS)
 def test_batch_gradients_with_eight_terms_match_the_checker(po, L):
     fr = _k8_frames(L)
     b = fr.batch()
     G = fr.grad_prob(L)
-    for T, relax in ((5, 0.7), (1, 1.0)):
+    for T, relax in gset.K8_BATCH_SETTINGS:
         gu, gw = gs.batch_backward(b, T, relax, G, fr.K)
         for f, n in enumerate(fr.N):
             if n == 0:
                 assert np.all(gu[f] == 0) and np.all(gw[f] == 0)
                 continue
-            o, lats, U = gs.checker(po, fr.probs[f])
-            gs.assert_matches_checker(gu[f, :n], gw[f], U, np.array(fr.w), lats, T, relax, G[f, :n].astype(np.float64),
-                                      "frame %d L=%d" % (f, L))
-            o.close()
+            gset.batch_frame(po, fr, G, f, T, relax, "frame %d L=%d" % (f, L))["ref"].check({"dL/dU": gu[f, :n], "dL/dw": gw[f]})
     b.close()
 
 

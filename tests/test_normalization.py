@@ -13,6 +13,7 @@ import pytest
 import compat_checker as ck
 import crf_cases as cc
 import grad_support as gs
+import gradient_settings as gset
 import normalization_checker as nc
 from abi_support import assert_declared_exported_bound, dev, lib  # noqa: F401
 
@@ -27,19 +28,7 @@ def _dense(K, L, seed=77):
     return [(np.eye(L) + 0.3 * rng.standard_normal((L, L))).astype(np.float32) for _ in range(K)]
 
 
-_PREPARED = {}
-
-
-def _prepared(name, golden, po, wl):
-    """(problem, raw unary, norms) of a case: computed once, shared by the tests, never changed"""
-    if name not in _PREPARED:
-        pb = nc.case(name, golden, po, wl)
-        o = cc.setup(po.OracleCRF, pb)
-        U = o.unary()
-        nrm = [o.kernel(k)["norm"] for k in range(len(pb["kernels"]))]
-        o.close()
-        _PREPARED[name] = (pb, U, nrm)
-    return _PREPARED[name]
+_prepared = gset.norm_prepared
 
 
 def _handle(pb, weights, modes, mats=None):
@@ -250,26 +239,7 @@ def _backward_compat(h, T, relax, G, K, L):
     return gu.cpu().numpy(), gw[:K].cpu().numpy(), gm[:K].cpu().numpy()
 
 
-def _errors_and_bars(got, U, w, mats, lats, modes, T, relax, G):
-    """relative L2 errors against the float64 checker and their bars, max(1e-4, 10 x the float32 checker's own error) -- the rule
-    of tests/test_compatibility.py, floors included"""
-    import torch
-    mu = np.stack(mats).astype(np.float64)
-    ref = nc.gradients_f64(U, w, mu, lats, modes, T, relax, G)
-    f32 = nc.gradients_f64(U, w, mu, lats, modes, T, relax, G, dtype=torch.float32)
-    fl_u = 1e-6 * np.linalg.norm(G)
-    fl_w = fl_u * max(np.linalg.norm(w), 1.0)
-    floors = (fl_u, fl_w, fl_w)
-    errs = [gs.rel(a, b, fl) for a, b, fl in zip(got, ref, floors)]
-    bars = [max(gs.GRAD_TOL, 10 * gs.rel(a, b, fl)) for a, b, fl in zip(f32, ref, floors)]
-    return errs, bars
-
-
-# L = 2 (1001 points, two 2-D terms: the SLAM shape), L = 3 with d = 1, L = 21 with d = 3 and d = 5.  A setting whose bar exceeds
-# 1e-2 checks nothing and would be dropped; the cases' seeds were chosen so that none is (notes/normalization.md section 4: the
-# fixtures slam:N1001 and generic:d1_L3 each have such settings, and their bars move by a factor of four between CPUs).
-GRAD_CASES = ["slam1001:s38", "d1_L3:s3", "L21:d3_d5"]
-GRAD_SETTINGS = [(n, m, T, r) for n in GRAD_CASES for m in nc.MODES for T in (0, 1, 5) for r in (1.0, 0.7)]
+GRAD_SETTINGS = gset.NORM_SETTINGS                               # (the cases and why: tests/gradient_settings.py)
 
 
 @pytest.mark.gpu
@@ -278,21 +248,12 @@ GRAD_SETTINGS = [(n, m, T, r) for n in GRAD_CASES for m in nc.MODES for T in (0,
 def test_gradients_match_the_checker(po, wl, golden, name, mode, T, relax):
     """Every term in `mode`, with the matrices I + 0.3 N(0, 1).  Measured on the MI355X: notes/normalization.md section 5 lists the
     largest error per case and mode."""
-    pb, U, nrm = _prepared(name, golden, po, wl)
+    s = gset.normalization(po, wl, golden, name, mode, T, relax)
+    pb, U, nrm, modes, mats, w, G = (s[x] for x in ("pb", "U", "nrm", "modes", "mats", "w", "G"))
     K, L = len(pb["kernels"]), pb["L"]
-    modes = [mode] * K
-    mats = _dense(K, L)
-    w = nc.weights_f32(pb, nrm, modes)
-    o, lats, U64 = gs.checker(po, pb)
-    o.close()
-    G = np.random.default_rng(1234).standard_normal((pb["N"], L))
     h = _handle(pb, w, modes, mats)
     got = _backward_compat(h, T, relax, G, K, L)
-    errs, bars = _errors_and_bars(got, U64, np.array([float(x) for x in w]), mats, lats, modes, T, relax, G)
-    print("relative L2 error %s %s T=%d relax=%g: dL/dU %.3g dL/dw %.3g dL/dmu %.3g (bars %.3g %.3g %.3g)"
-          % ((name, nc.MODE_NAMES[mode], T, relax) + tuple(errs) + tuple(bars)))
-    assert max(bars) <= 1e-2, bars                               # (beyond that the setting would check nothing)
-    assert all(e <= b for e, b in zip(errs, bars)), (errs, bars)
+    s["ref"].check(dict(zip(("dL/dU", "dL/dw", "dL/dmu"), got)))  # (a bar beyond 1e-2 fails there: it would check nothing)
     if T == 0:
         assert np.all(got[1] == 0) and np.all(got[2] == 0)
     again = _backward_compat(h, T, relax, G, K, L)               # the same bits from run to run
@@ -360,10 +321,9 @@ def test_layer_gradients_match_the_checker_and_sgd_lowers_the_loss(po, wl, golde
     o, lats, U64 = gs.checker(po, pb)
     o.close()
     eyes = [np.eye(L, dtype=np.float32)] * K
-    got = (u.grad.cpu().numpy(), layer.weights.grad.numpy(), np.zeros((K, L, L)))
-    errs, bars = _errors_and_bars(got, U64, np.array(w0), eyes, lats, [nc.SYMMETRIC] * K, 5, 0.7, G)
-    print("layer, relative L2 error: dL/dU %.3g dL/dw %.3g (bars %.3g %.3g)" % (errs[0], errs[1], bars[0], bars[1]))
-    assert errs[0] <= bars[0] and errs[1] <= bars[1], (errs, bars)
+    at = gset.device_iterates(po, pb, 5, 0.7, None, [nc.SYMMETRIC] * K, [np.float32(x) for x in w0], nrm)
+    r = gs.compat_reference(U64, np.array(w0), eyes, lats, 5, 0.7, G, "layer", [nc.SYMMETRIC] * K, at)
+    r.check({"dL/dU": u.grad.cpu().numpy(), "dL/dw": layer.weights.grad.numpy()})
     layer.close()
 
     student = ag.MeanFieldCRF(N, L, nc.feats(pb), w0, n_iterations=5, normalization=[pkg.NORMALIZE_SYMMETRIC] * K)
