@@ -335,8 +335,15 @@ __global__ void __launch_bounds__(NT, 4) k_fused_lean(CrfDev c, FusedArgs a)
         }
         src.unary = lean_rsrc(c.unary + (size_t)f * c.maxN * 2, (size_t)c.maxN * 8);
         src.off_unary = 0;
-        const LeanPrepPlan pp = lean_prep_plan(lay, K, a.Vcap, NT, PPT);
+        const LeanPrepPlan pp = lean_prep_plan(lay, K, a.Vcap, NT, PPT, true);
         const __amdgpu_buffer_rsrc_t rp = lean_rsrc(a.prep + (size_t)f * a.prep_stride, (size_t)a.prep_stride);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            if (!chain_k<CH>(lay, k)) {                   // renumbered by row length: the block's table instead of the build's
+                src.nbr[k] = lean_rsrc(a.prep + (size_t)f * a.prep_stride + pp.snbr_off[k], (size_t)D1 * pp.snbr_axis[k]);
+                src.nbr_axis_bytes[k] = pp.snbr_axis[k];
+            }
+        }
         typedef unsigned lean_u2 __attribute__((ext_vector_type(2)));
         typedef unsigned lean_u4 __attribute__((ext_vector_type(4)));
 #pragma unroll
@@ -487,12 +494,21 @@ __global__ void __launch_bounds__(NT, 4) k_fused_lean(CrfDev c, FusedArgs a)
     if (CH != 0 && chain_k<CH>(lay, 0)) cl = chain_setup_lean<NT>(smem, lay, V[0], tid);
     FL_PSTAMP();
     if (MODE != 1) start_inference<PPT, K, NT>(pr, N, tid);
+    [[maybe_unused]] const LeanPrepPlan pp = lean_prep_plan(lay, K, a.Vcap, NT, PPT, true);   // (MODE 1 only: the frame's prepared block)
+    [[maybe_unused]] unsigned char *pf = a.prep + (size_t)fo * a.prep_stride;
+    if constexpr (MODE == 1) {
+        // the short-row kernels' vertices numbered by row length: pk and the row table in LDS change to the new numbering before the
+        // words are placed, the neighbour table goes to the block in it
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            if (!chain_k<CH>(lay, k))
+                sort_short_rows<PPT, K, NT>(smem, lay, k, V[k], tid, pk, gnbr[k], a.kd[k].Epad,
+                                            reinterpret_cast<unsigned *>(pf + pp.snbr_off[k]), pp.snbr_axis[k] >> 2);
+    }
     place_products_lean<PPT, K, CH, NT>(smem, lay, N, tid, pk, pr);
     FL_STAMP();
     if constexpr (MODE == 1) {
         // ---- the prepared block of this frame: ix words, chain lanes, LDS tables (LeanPrepPlan) ---------------------------------------
-        const LeanPrepPlan pp = lean_prep_plan(lay, K, a.Vcap, NT, PPT);
-        unsigned char *pf = a.prep + (size_t)fo * a.prep_stride;
 #pragma unroll
         for (int s = 0; s < PPT; ++s)
 #pragma unroll
@@ -644,7 +660,7 @@ size_t lean_prep_bytes(const CrfDev &c, const KernelDev *kds, const int *maxV, c
     FusedLayout lay;
     const FusedShape sh = choose_shape(c, kds, maxV, maxRow, &lay);
     if (!sh.ok || c.F < kPrepMinFrames) return 0;
-    const LeanPrepPlan pp = lean_prep_plan(lay, c.K, maxV, sh.nt, sh.ppt);
+    const LeanPrepPlan pp = lean_prep_plan(lay, c.K, maxV, sh.nt, sh.ppt, sh.lean);
     return (size_t)pp.total * (size_t)c.F;
 }
 
@@ -667,7 +683,7 @@ int launch_inference_fused(const CrfDev &c, const KernelDev *kds, const int *max
     // inference behind a build runs the self-contained kernel (a caller with one inference per lattice pays nothing); the second one
     // writes the blocks (MODE 1) and every inference from then on starts from them (MODE 2).
     for (int k = 0; k < c.K; ++k) a.Vcap[k] = maxV[k];
-    const LeanPrepPlan pp = lean_prep_plan(a.lay, c.K, a.Vcap, sh.nt, sh.ppt);
+    const LeanPrepPlan pp = lean_prep_plan(a.lay, c.K, a.Vcap, sh.nt, sh.ppt, sh.lean);
     static const bool no_prep = ab_env("LCCRF_NO_LEAN_PREP") != nullptr;    // A/B switch (instrumented library): same results either way
     int mode = 0;
     const int pieces = (sh.lean ? 1 : 2) * sh.nt * 16;   // (the run kernels move every table with one (lean) / two 16-byte loads per lane)
@@ -681,6 +697,8 @@ int launch_inference_fused(const CrfDev &c, const KernelDev *kds, const int *max
         mix(a.Vcap, sizeof(int) * c.K);
         const int shape[6] = {c.F, c.K, sh.ppt, sh.points, sh.nt, sh.lean ? 2 : sh.small ? 1 : 0};
         mix(shape, sizeof(shape));
+        mix(&kLeanPrepFormat, sizeof(kLeanPrepFormat));
+        mix(&pp, sizeof(pp));                                // (the regions of the block, the renumbered tables among them)
         a.prep = prep->buf;
         a.prep_stride = pp.total;
         if (prep->valid && prep->key == key) {

@@ -372,6 +372,111 @@ __device__ __forceinline__ void place_products_lean(unsigned char *smem, const F
     }
 }
 
+// ---- short rows numbered by length (round 7) -----------------------------------------------------------------------------------
+// A vertex's number is a label: the value arrays, the blur and the slice go through the tables, which can carry any numbering.  The
+// short-row sums, though, deal vertex t + r * NT to lane t in round r, and a wavefront walks its 64 rows as far as the longest of
+// them.  In the build's numbering every wavefront-round holds a row of 9+ products among mostly 1-8; numbered by DESCENDING row length,
+// a wavefront-round holds rows of nearly one length.  Rank q (stable in the build's vertex order) gets the number below: wavefront
+// chunks in rank order round after round, every other FULL round dealt to the wavefronts backwards so that their totals even out.
+__host__ __device__ inline int lean_sorted_vertex(int q, int V, int nt)
+{
+    const int r = q / nt;
+    int w = (q % nt) >> 6;
+    if ((r & 1) && (r + 1) * nt <= V) w = (nt >> 6) - 1 - w;
+    return r * nt + (w << 6) + (q & 63);
+}
+
+// exclusive scan of one int per lane over the workgroup in lane order; ws: [NT / 64] ints of scratch, which the caller may reuse after
+// its NEXT barrier (the function ends with every lane's reads of ws, not with a barrier).
+template <int NT>
+__device__ __forceinline__ int block_excl_scan(int x, int tid, int *ws)
+{
+    int incl = x;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(incl, o, 64);
+        if ((tid & 63) >= o) incl += y;
+    }
+    if ((tid & 63) == 63) ws[tid >> 6] = incl;
+    __syncthreads();
+    int before = 0;
+#pragma unroll
+    for (int w = 0; w < NT / 64; ++w) {
+        const int s = ws[w];
+        if (w < (tid >> 6)) before += s;
+    }
+    return before + incl - x;
+}
+
+// Prepare (MODE 1), for one short-row kernel: rank the vertices by row length -- a counting sort on min(length, 63), longest first,
+// stable: lane (bucket b, segment s) counts and later numbers the vertices of its eighth of the vertex range, in vertex order, so
+// nothing depends on the order atomics arrive in -- then rewrite, in the new numbering, the row table in LDS (prefix sum of the sorted
+// lengths), the lane's pk words (vertex + 1 | product slot << 16: the new row start + the unchanged place in the row) and, into
+// `out` (u32 [D1][axis_words], the frame's prepared block), the neighbour table: entry p(v) = (p(n1) + 1) | (p(n2) + 1) << 16, 0 stays 0.
+// Scratch: the product buffer.  Every lane of the workgroup calls it; starts and ends with a barrier.
+template <int PPT, int K, int NT>
+__device__ __forceinline__ void sort_short_rows(unsigned char *smem, const FusedLayout &lay, int k, int Vk, int tid,
+                                                unsigned (&pk)[PPT][K][kD1], const unsigned *gnbr, int Epad, unsigned *out, int axis_words)
+{
+    constexpr int VM = (lean_max_v(NT) + 8 + 7) & ~7;                   // u16 entries per scratch array
+    static_assert(NT == 512, "one lane per (bucket, segment): 64 x 8");
+    static_assert(4 * VM * 2 + 64 <= ((NT * kD1 + 63) & ~63) * 8, "the scratch fits the smallest product buffer of the plan");
+    unsigned short *row = reinterpret_cast<unsigned short *>(smem + lay.row[k]);
+    unsigned short *key = reinterpret_cast<unsigned short *>(smem + lay.prod[k]);
+    unsigned short *perm = key + VM, *nlen = perm + VM, *nrow = nlen + VM;
+    int *ws = reinterpret_cast<int *>(nrow + VM);
+    __syncthreads();
+    for (int v = tid; v < Vk; v += NT) key[v] = (unsigned short)(63 - min((int)row[v + 1] - (int)row[v], 63));
+    __syncthreads();
+    const int b = tid >> 3, seg_len = (Vk + 7) >> 3, lo = min((tid & 7) * seg_len, Vk), hi = min(lo + seg_len, Vk);
+    int cnt = 0;
+    for (int v = lo; v < hi; ++v) cnt += key[v] == b ? 1 : 0;
+    int q = block_excl_scan<NT>(cnt, tid, ws);               // lane order = bucket-major, segment-minor: the stable rank
+    for (int v = lo; v < hi; ++v) {
+        if (key[v] == b) {
+            const int nv = lean_sorted_vertex(q++, Vk, NT);
+            perm[v] = (unsigned short)nv;
+            nlen[nv] = (unsigned short)((int)row[v + 1] - (int)row[v]);
+        }
+    }
+    __syncthreads();
+    {   // the new row table: entries 3 t .. 3 t + 2 by lane t (entry Vk = the total)
+        int l[3], sum = 0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            l[i] = tid * 3 + i < Vk ? (int)nlen[tid * 3 + i] : 0;
+            sum += l[i];
+        }
+        int at = block_excl_scan<NT>(sum, tid, ws + NT / 64);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            if (tid * 3 + i <= Vk) nrow[tid * 3 + i] = (unsigned short)at;
+            at += l[i];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < PPT; ++s) {
+#pragma unroll
+        for (int j = 0; j < kD1; ++j) {
+            const unsigned w = pk[s][k][j], id = w & 0xffffu;
+            if (id) {
+                const int v = (int)id - 1, nv = perm[v];
+                pk[s][k][j] = (unsigned)(nv + 1) | ((unsigned)((int)nrow[nv] + ((int)(w >> 16) - (int)row[v])) << 16);
+            }
+        }
+    }
+    for (int j = 0; j < kD1; ++j) {
+        for (int v = tid; v < Vk; v += NT) {
+            const unsigned n = gnbr[(size_t)j * Epad + v], n1 = n & 0xffffu, n2 = n >> 16;
+            out[j * axis_words + perm[v]] = (n1 ? (unsigned)perm[n1 - 1] + 1u : 0u) | ((n2 ? (unsigned)perm[n2 - 1] + 1u : 0u) << 16);
+        }
+    }
+    __syncthreads();
+    for (int v = tid; v <= Vk; v += NT) row[v] = nrow[v];
+    __syncthreads();
+}
+
 // This frame's slices of the per-kernel arrays the loop reads from HBM / L2, as buffer resources: a load takes a 32-bit lane
 // offset + a scalar offset (no 64-bit address registers to keep or spill), and a lane past the end of the slice reads 0.
 typedef unsigned lean_u3 __attribute__((ext_vector_type(3)));
@@ -425,9 +530,15 @@ struct LeanPrepPlan {
     int cl_off;
     int row_off[kMaxFusedK], row_bytes[kMaxFusedK];
     int nbr_off[kMaxFusedK], nbr_bytes[kMaxFusedK];     // nbr_bytes = 0: the kernel's table is not in LDS
+    int snbr_off[kMaxFusedK], snbr_axis[kMaxFusedK];    // sorted short rows: the renumbered neighbour table the loop reads from HBM / L2,
+                                                         //   u32 [D1][snbr_axis / 4]; snbr_axis = 0: the kernel keeps the build's numbering
     int total;                                           // multiple of 256
 };
-__host__ __device__ inline LeanPrepPlan lean_prep_plan(const FusedLayout &lay, int K, const int *Vcap, int nt, int ppt)
+constexpr unsigned kLeanPrepFormat = 7;                  // (mixed into the blocks' validity key)
+// sorted (k_fused_lean only; k_fused's blocks keep the round-6 format): every kernel but the chain kernel -- whose table is the only
+// one in LDS -- is renumbered by row length (sort_short_rows): its ix words and row table hold the new numbers, and its neighbour
+// table in the new numbering follows the LDS tables
+__host__ __device__ inline LeanPrepPlan lean_prep_plan(const FusedLayout &lay, int K, const int *Vcap, int nt, int ppt, bool sorted = false)
 {
     LeanPrepPlan p{};
     int o = K * ppt * nt * 12;
@@ -440,6 +551,11 @@ __host__ __device__ inline LeanPrepPlan lean_prep_plan(const FusedLayout &lay, i
         p.nbr_off[k] = o;
         p.nbr_bytes[k] = lay.nbr[k] >= 0 ? ((kD1 * Vcap[k] * 4 + 15) & ~15) : 0;
         o += p.nbr_bytes[k];
+    }
+    for (int k = 0; k < K; ++k) {
+        p.snbr_off[k] = o;
+        p.snbr_axis[k] = (sorted && lay.nbr[k] < 0) ? ((Vcap[k] + 3) & ~3) * 4 : 0;
+        o += kD1 * p.snbr_axis[k];
     }
     p.total = (o + 255) & ~255;
     return p;
@@ -533,6 +649,9 @@ __device__ __forceinline__ void mean_field_lean(unsigned char *smem, const Fused
         // end of its row reads the zero block (x + 0 is exact, see chain_rows).  This lane's rows (vertices t, t + NT, ...) are walked
         // TOGETHER: every row's pointers first, then every row's first eight products -- most rows of a smoothness kernel end there --
         // so the phase waits for two rounds of LDS latency instead of two per row; each row is still added strictly left to right.
+        // From prepared records (k_fused_lean MODE 2) the vertices are numbered by descending row length (sort_short_rows): only the
+        // wavefronts that hold rows of more than eight products walk the second trip below (derived from the row lengths of C2's
+        // lattices: two wavefronts of eight; a phase with wave-uniform trip counts lost its A/B, notes/r7_experiments.md).
         if (LEAN_SKIP(32)) return;
         const float2 *pl = reinterpret_cast<const float2 *>(smem + lay.prod[k]);
         const float2 *zero = reinterpret_cast<const float2 *>(smem + lay.zero);
