@@ -708,15 +708,16 @@ def lattice_filter(features, x, device=0):
     return out, V.value
 
 
-def pose_optimization(Xw, kp, u_right, inv_sigma2, K4, bf, Tcw, valid=None, label=None, device=0):
-    """Optimizer::PoseOptimization on the GPU (lccrf_pose_optimization): (Tcw_out [4,4], outlier u8[n], n_inliers)."""
+def pose_optimization(Xw, kp, u_right, inv_sigma2, K4, bf, Tcw, valid=None, label=None, device=0, outlier=None):
+    """Optimizer::PoseOptimization on the GPU (lccrf_pose_optimization): (Tcw_out [4,4], outlier u8[n], n_inliers).
+    `outlier`: what mvbOutlier holds before the call (default zeros); entries of points without an edge come back as given."""
     Xw, kp = _f32(Xw).reshape(-1, 3), _f32(kp).reshape(-1, 2)
     n = Xw.shape[0]
     ur, is2, K, T = _f32(u_right), _f32(inv_sigma2), _f32(K4), _f32(Tcw).reshape(16)
     va = None if valid is None else np.ascontiguousarray(valid, np.uint8)
     la = None if label is None else np.ascontiguousarray(label, np.int16)
     out = np.empty(16, np.float32)
-    outl = np.zeros(n, np.uint8)
+    outl = np.zeros(n, np.uint8) if outlier is None else np.array(outlier, np.uint8).reshape(n)
     ninl = np.zeros(1, np.int32)
     _check(lib().lccrf_pose_optimization(int(device), n, _p(Xw, _f32p), _p(kp, _f32p), _p(ur, _f32p), _p(is2, _f32p),
                                          va.ctypes.data if va is not None else None, _p(la, _i16p) if la is not None else None,

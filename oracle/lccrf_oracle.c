@@ -699,7 +699,10 @@ static void pq_normalize(pq_t *q)                     /* se3quat.h:280-285 */
     q->w /= n; q->x /= n; q->y /= n; q->z /= n;
 }
 
-static pq_t pq_from_matrix(const double m[3][3])      /* Eigen::Quaterniond(Matrix3d) */
+/* Slots of orc_pose_optimization_traced's counters (lccrf_oracle.h: ORC_POSE_TRACE_*); `tr` may be NULL everywhere. */
+#define POSE_COUNT(tr, slot) do { if (tr) (tr)[slot]++; } while (0)
+
+static pq_t pq_from_matrix(const double m[3][3], int *tr)      /* Eigen::Quaterniond(Matrix3d) */
 {
     pq_t q;
     double t = m[0][0] + m[1][1] + m[2][2];
@@ -716,6 +719,7 @@ static pq_t pq_from_matrix(const double m[3][3])      /* Eigen::Quaterniond(Matr
         if (m[2][2] > m[i][i]) i = 2;
         const int j = (i + 1) % 3, k = (j + 1) % 3;
         double v[3];
+        POSE_COUNT(tr, ORC_POSE_TRACE_QUAT_X + i);
         t = sqrt(m[i][i] - m[j][j] - m[k][k] + 1.0);
         v[i] = 0.5 * t;
         t = 0.5 / t;
@@ -747,7 +751,7 @@ static pq_t pq_mul(const pq_t *a, const pq_t *b)      /* Eigen quaternion produc
 }
 
 /* estimate <- SE3Quat::exp(update) * estimate     (VertexSE3Expmap::oplusImpl, se3quat.h:214-256,104-110) */
-static void pose_oplus(const double upd[6], pq_t *q, double t[3])
+static void pose_oplus(const double upd[6], pq_t *q, double t[3], int *tr)
 {
     const double om[3] = {upd[0], upd[1], upd[2]}, up[3] = {upd[3], upd[4], upd[5]};
     const double theta = sqrt(om[0] * om[0] + om[1] * om[1] + om[2] * om[2]);
@@ -756,6 +760,7 @@ static void pose_oplus(const double upd[6], pq_t *q, double t[3])
     for (int i = 0; i < 3; i++)
         for (int j = 0; j < 3; j++) O2[i][j] = O[i][0] * O[0][j] + O[i][1] * O[1][j] + O[i][2] * O[2][j];
     if (theta < 0.00001) {
+        POSE_COUNT(tr, ORC_POSE_TRACE_THETA_SMALL);
         for (int i = 0; i < 3; i++)
             for (int j = 0; j < 3; j++) { R[i][j] = ((i == j) ? 1.0 : 0.0) + O[i][j] + O2[i][j]; V[i][j] = R[i][j]; }
     } else {
@@ -767,7 +772,7 @@ static void pose_oplus(const double upd[6], pq_t *q, double t[3])
                 V[i][j] = I + b * O[i][j] + c * O2[i][j];
             }
     }
-    pq_t dq = pq_from_matrix(R);
+    pq_t dq = pq_from_matrix(R, tr);
     pq_normalize(&dq);
     const double dt[3] = {V[0][0] * up[0] + V[0][1] * up[1] + V[0][2] * up[2], V[1][0] * up[0] + V[1][1] * up[1] + V[1][2] * up[2],
                           V[2][0] * up[0] + V[2][1] * up[1] + V[2][2] * up[2]};
@@ -862,10 +867,11 @@ static double pose_active_chi2(const pose_prob *p, const uint8_t *level1, const 
     return chi;
 }
 
-int orc_pose_optimization(int n, const float *Xw, const float *kp, const float *u_right, const float *inv_sigma2,
-                          const uint8_t *valid, const float *K4, float bf, const float *Tcw_in, float *Tcw_out,
-                          uint8_t *outlier, int *n_initial)
+int orc_pose_optimization_traced(int n, const float *Xw, const float *kp, const float *u_right, const float *inv_sigma2,
+                                 const uint8_t *valid, const float *K4, float bf, const float *Tcw_in, float *Tcw_out,
+                                 uint8_t *outlier, int *n_initial, int *trace)
 {
+    if (trace) memset(trace, 0, ORC_POSE_TRACE_SLOTS * sizeof(int));
     pose_prob P = {n, Xw, kp, u_right, inv_sigma2, K4[0], K4[1], K4[2], K4[3], bf};
     int n_init = 0;
     uint8_t *level1 = (uint8_t *)calloc((size_t)n + 1, 1);
@@ -878,7 +884,7 @@ int orc_pose_optimization(int n, const float *Xw, const float *kp, const float *
     if (n_init < 3) { free(level1); free(edge_chi2); return 0; }          /* Optimizer.cc:361-362 */
     double R0[3][3], t0[3];
     for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) R0[i][j] = Tcw_in[4 * i + j]; t0[i] = Tcw_in[4 * i + 3]; }
-    pq_t q0 = pq_from_matrix(R0);                         /* Converter::toSE3Quat, Converter.cc:37-47 */
+    pq_t q0 = pq_from_matrix(R0, trace);                         /* Converter::toSE3Quat, Converter.cc:37-47 */
     pq_normalize(&q0);
     /* deltaMono / deltaStereo are `const float sqrt(5.991)` / `sqrt(7.815)` (Optimizer.cc:274-275) */
     const double dMono = (double)(float)sqrt(5.991), dStereo = (double)(float)sqrt(7.815);
@@ -891,7 +897,8 @@ int orc_pose_optimization(int n, const float *Xw, const float *kp, const float *
         q = q0; t[0] = t0[0]; t[1] = t0[1]; t[2] = t0[2]; /* vSE3->setEstimate(toSE3Quat(pFrame->mTcw)), :374 */
         double lambda = 0, ni = 2;
         int nBadLM = 0;
-        for (int iter = 0; iter < 10; iter++) {           /* optimizer.optimize(10) */
+        int iter;
+        for (iter = 0; iter < 10; iter++) {               /* optimizer.optimize(10) */
             double H[6][6] = {{0}}, b[6] = {0}, currentChi = 0;
             for (int i = 0; i < n; i++) {
                 if (!valid[i] || level1[i]) continue;
@@ -925,9 +932,11 @@ int orc_pose_optimization(int n, const float *Xw, const float *kp, const float *
                 pq_t qb = q;
                 double tb[3] = {t[0], t[1], t[2]}, x[6] = {0, 0, 0, 0, 0, 0};
                 const int ok2 = solve6(H, lambda, b, x);
-                pose_oplus(x, &q, t);
+                if (!ok2) POSE_COUNT(trace, ORC_POSE_TRACE_SOLVE_FAIL);
+                pose_oplus(x, &q, t, trace);
                 double tempChi = pose_active_chi2(&P, level1, valid, robust, dMono, dStereo, &q, t, edge_chi2);
                 if (!ok2) tempChi = DBL_MAX;
+                if (!isfinite(tempChi)) POSE_COUNT(trace, ORC_POSE_TRACE_NONFINITE);
                 rho_gain = currentChi - tempChi;
                 double scale = 0;
                 for (int j = 0; j < 6; j++) scale += x[j] * (lambda * x[j] + b[j]);
@@ -939,16 +948,22 @@ int orc_pose_optimization(int n, const float *Xw, const float *kp, const float *
                     lambda *= fmax(1. / 3., alpha);
                     ni = 2;
                     currentChi = tempChi;
+                    POSE_COUNT(trace, ORC_POSE_TRACE_ACCEPTED);
                 } else {
+                    POSE_COUNT(trace, ORC_POSE_TRACE_REJECTED);
                     lambda *= ni; ni *= 2;
                     q = qb; t[0] = tb[0]; t[1] = tb[1]; t[2] = tb[2];
                 }
                 qmax++;
             } while (rho_gain < 0 && qmax < 10);
-            if (qmax == 10 || rho_gain == 0) break;      /* Terminate */
+            if (qmax == 10 || rho_gain == 0) {           /* Terminate */
+                POSE_COUNT(trace, qmax == 10 ? ORC_POSE_TRACE_STOP_QMAX : ORC_POSE_TRACE_STOP_RHO_ZERO);
+                break;
+            }
             if ((iniChi - currentChi) * 1e3 < iniChi) nBadLM++; else nBadLM = 0;
-            if (nBadLM >= 3) break;
+            if (nBadLM >= 3) { POSE_COUNT(trace, ORC_POSE_TRACE_STOP_BADLM); break; }
         }
+        if (iter == 10) POSE_COUNT(trace, ORC_POSE_TRACE_FULL_ROUND);
         nBad = 0;                                         /* Optimizer.cc:378-432 */
         for (int i = 0; i < n; i++) {
             if (!valid[i]) continue;
@@ -959,7 +974,7 @@ int orc_pose_optimization(int n, const float *Xw, const float *kp, const float *
             if (outlier[i]) edge_chi2[i] = pose_edge_error(&P, i, &q, t, e, pc);
             const float chi2 = (float)edge_chi2[i];                           /* `const float chi2 = e->chi2()` */
             if (chi2 > (u_right[i] < 0 ? chi2Mono : chi2Stereo)) { outlier[i] = 1; level1[i] = 1; nBad++; }
-            else { outlier[i] = 0; level1[i] = 0; }
+            else { if (outlier[i]) POSE_COUNT(trace, ORC_POSE_TRACE_READMITTED); outlier[i] = 0; level1[i] = 0; }
         }
         if (n_init < 10) break;                           /* optimizer.edges().size() < 10, :434-435 */
     }
@@ -972,4 +987,11 @@ int orc_pose_optimization(int n, const float *Xw, const float *kp, const float *
     free(level1);
     free(edge_chi2);
     return n_init - nBad;
+}
+
+int orc_pose_optimization(int n, const float *Xw, const float *kp, const float *u_right, const float *inv_sigma2,
+                          const uint8_t *valid, const float *K4, float bf, const float *Tcw_in, float *Tcw_out,
+                          uint8_t *outlier, int *n_initial)
+{
+    return orc_pose_optimization_traced(n, Xw, kp, u_right, inv_sigma2, valid, K4, bf, Tcw_in, Tcw_out, outlier, n_initial, NULL);
 }

@@ -134,6 +134,28 @@ int orc_pose_optimization(int n, const float *Xw, const float *kp, const float *
                           const uint8_t *valid, const float *K4, float bf, const float *Tcw_in, float *Tcw_out,
                           uint8_t *outlier, int *n_initial);
 
+/* The same call with its branches counted: trace [ORC_POSE_TRACE_SLOTS] (or NULL) is zeroed and then receives, per slot, how
+ * often the schedule went that way.  The arithmetic is orc_pose_optimization's: that function is this one with trace = NULL. */
+enum {
+    ORC_POSE_TRACE_ACCEPTED = 0,      /* LM trials taken (rho > 0 and a finite chi2) */
+    ORC_POSE_TRACE_REJECTED,          /* LM trials dropped, the estimate popped */
+    ORC_POSE_TRACE_SOLVE_FAIL,        /* H + lambda I not positive definite: tempChi = DBL_MAX */
+    ORC_POSE_TRACE_NONFINITE,         /* tempChi infinite or NaN where the trial is judged */
+    ORC_POSE_TRACE_STOP_QMAX,         /* an iteration ended after ten rejected trials */
+    ORC_POSE_TRACE_STOP_RHO_ZERO,     /* ... on rho == 0 */
+    ORC_POSE_TRACE_STOP_BADLM,        /* a round ended on three iterations without 0.1 % gain */
+    ORC_POSE_TRACE_FULL_ROUND,        /* a round ran all ten iterations */
+    ORC_POSE_TRACE_THETA_SMALL,       /* SE3Quat::exp below theta = 1e-5 */
+    ORC_POSE_TRACE_QUAT_X,            /* quaternion from a matrix of trace <= 0: largest diagonal element m00 */
+    ORC_POSE_TRACE_QUAT_Y,            /* ... m11 */
+    ORC_POSE_TRACE_QUAT_Z,            /* ... m22 */
+    ORC_POSE_TRACE_READMITTED,        /* edges flagged after one round and cleared after a later one */
+    ORC_POSE_TRACE_SLOTS
+};
+int orc_pose_optimization_traced(int n, const float *Xw, const float *kp, const float *u_right, const float *inv_sigma2,
+                                 const uint8_t *valid, const float *K4, float bf, const float *Tcw_in, float *Tcw_out,
+                                 uint8_t *outlier, int *n_initial, int *trace);
+
 #ifdef __cplusplus
 }
 #endif

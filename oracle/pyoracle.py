@@ -106,6 +106,7 @@ def oracle_lib():
         lib.orc_bf_match.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_double, _i32p, _i32p]
         lib.orc_pose_optimization.argtypes = [C.c_int, _f32p, _f32p, _f32p, _f32p, C.c_void_p, _f32p, C.c_float, _f32p, _f32p,
                                               C.c_void_p, C.POINTER(C.c_int)]
+        lib.orc_pose_optimization_traced.argtypes = lib.orc_pose_optimization.argtypes + [_i32p]
         _olib = lib
     return _olib
 
@@ -427,9 +428,14 @@ def oracle_bf_match(desc_query, desc_train, ratio=0.6):
     return out, int(nm[0])
 
 
-def oracle_pose_optimization(Xw, kp, u_right, inv_sigma2, valid, K4, bf, Tcw):
+# the slots of orc_pose_optimization_traced, in the order of lccrf_oracle.h: ORC_POSE_TRACE_*
+POSE_TRACE = ("accepted", "rejected", "solve6_failed", "tempchi_nonfinite", "stop_qmax", "stop_rho_zero", "stop_bad_lm", "full_round",
+              "theta_small", "quat_x", "quat_y", "quat_z", "readmitted")
+
+
+def oracle_pose_optimization(Xw, kp, u_right, inv_sigma2, valid, K4, bf, Tcw, trace=False):
     """Optimizer::PoseOptimization restated (parity unpinned, see lccrf_oracle.c): returns (Tcw_out [4,4] f32, outlier
-    u8[n], n_inliers, n_initial)."""
+    u8[n], n_inliers, n_initial) and, with trace=True, as a fifth entry the dict of the call's branch counts (POSE_TRACE)."""
     lib = oracle_lib()
     Xw, kp = _f32(Xw).reshape(-1, 3), _f32(kp).reshape(-1, 2)
     n = Xw.shape[0]
@@ -439,6 +445,10 @@ def oracle_pose_optimization(Xw, kp, u_right, inv_sigma2, valid, K4, bf, Tcw):
     out = np.empty(16, np.float32)
     outl = np.zeros(n, np.uint8)
     ninit = C.c_int(0)
-    r = lib.orc_pose_optimization(n, _ptr(Xw, _f32p), _ptr(kp, _f32p), _ptr(ur, _f32p), _ptr(is2, _f32p), va.ctypes.data,
-                                  _ptr(K, _f32p), float(bf), _ptr(T, _f32p), _ptr(out, _f32p), outl.ctypes.data, C.byref(ninit))
-    return out.reshape(4, 4), outl, int(r), ninit.value
+    args = (n, _ptr(Xw, _f32p), _ptr(kp, _f32p), _ptr(ur, _f32p), _ptr(is2, _f32p), va.ctypes.data,
+            _ptr(K, _f32p), float(bf), _ptr(T, _f32p), _ptr(out, _f32p), outl.ctypes.data, C.byref(ninit))
+    if not trace:
+        return out.reshape(4, 4), outl, int(lib.orc_pose_optimization(*args)), ninit.value
+    counts = np.zeros(len(POSE_TRACE), np.int32)
+    r = lib.orc_pose_optimization_traced(*args, _ptr(counts, _i32p))
+    return out.reshape(4, 4), outl, int(r), ninit.value, dict(zip(POSE_TRACE, (int(c) for c in counts)))

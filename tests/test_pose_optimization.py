@@ -15,7 +15,18 @@ import sys
 import numpy as np
 import pytest
 
+import pose_cases as pc
+
 pkg = importlib.import_module("lc-crf-slam_amd")
+
+
+def _arrays_ready():
+    """The arrays handed to lccrf_batch_pose_optimization are filled on torch's stream; the call runs on the batch's own non-blocking
+    stream, and nothing orders the two.  The caller of an asynchronous entry point owes it finished arrays: this waits for torch's
+    stream alone, and is called BEFORE lccrf_batch_run, so that run and pose stay back to back with no synchronisation in between --
+    that the pose kernel is ordered behind the CRF on the batch's stream is part of what the batch tests check."""
+    import torch
+    torch.cuda.current_stream().synchronize()
 
 
 def _run_oracle(po, s, valid=None):
@@ -93,16 +104,19 @@ def test_hip_pose_optimization_reads_the_crf_labels_on_the_device(po, wl):
     b = pkg.BatchCRF(F, N, 2, [2, 2], [10.0, 30.0])
     b.set_inputs_host([N] * F, [np.stack([pb["kernels"][k][0] for pb in pbs]) for k in range(2)],
                       label=np.stack([pb["label"] for pb in pbs]), conf=0.7)
-    b.run(5, True)
     t = lambda key, dt: torch.from_numpy(np.stack([np.ascontiguousarray(s[key]) for s in scenes]).astype(dt)).to(dev)
     dX, dk, du, di, dTi = t("Xw", np.float32), t("kp", np.float32), t("u_right", np.float32), t("inv_sigma2", np.float32), t("T_init", np.float32)
     dTo = torch.zeros((F, 16), dtype=torch.float32, device=dev)
     dout = torch.zeros((F, N), dtype=torch.uint8, device=dev)
     dni, dn0 = torch.zeros(F, dtype=torch.int32, device=dev), torch.zeros(F, dtype=torch.int32, device=dev)
+    _arrays_ready()
+    b.run(5, True)                                        # asynchronous; the pose right behind it, no synchronisation by the caller
     b.pose_optimization(dX.data_ptr(), dk.data_ptr(), du.data_ptr(), di.data_ptr(), scenes[0]["K4"], scenes[0]["bf"], dTi.data_ptr(),
                         dTo.data_ptr(), dout.data_ptr(), dni.data_ptr(), dn0.data_ptr())
     b.synchronize()
     labels = b.map()
+    print("n_initial", dn0.cpu().numpy(), "n_inliers", dni.cpu().numpy(), "static labels", (labels != 0).sum(1),
+          "pose moved", [not np.array_equal(dTo[f].cpu().numpy(), dTi[f].cpu().numpy()) for f in range(F)])
     for f in range(F):
         o = cc.setup(po.OracleCRF, pbs[f])
         o.inference_native(5, True)
@@ -143,6 +157,7 @@ def test_batch_pose_after_a_run_with_a_fallback_frame_and_extra_edges(po, wl):
     dni, dn0 = torch.zeros(F, dtype=torch.int32, device=dev), torch.zeros(F, dtype=torch.int32, device=dev)
     args = (dX.data_ptr(), dk.data_ptr(), du.data_ptr(), di.data_ptr(), scenes[0]["K4"], scenes[0]["bf"], dTi.data_ptr(),
             dTo.data_ptr(), dout.data_ptr(), dni.data_ptr(), dn0.data_ptr())
+    _arrays_ready()
     b.run(5, False)
     with pytest.raises(pkg.LccrfError) as ei:
         b.pose_optimization(*args)
@@ -155,6 +170,7 @@ def test_batch_pose_after_a_run_with_a_fallback_frame_and_extra_edges(po, wl):
         o.close()
     for extra in (False, True):
         dtot = torch.full((F,), N + NX, dtype=torch.int32, device=dev)
+        _arrays_ready()
         b.pose_set_crf_counts(dtot.data_ptr() if extra else None)
         b.run(5, True)                                    # asynchronous; frame 1 is flagged for the re-run
         b.pose_optimization(*args)                        # no synchronisation in between by the caller
@@ -191,6 +207,9 @@ def test_hip_pose_optimization_survives_trim_and_growth(po, wl):
     assert out[1][2] == no and np.array_equal(out[1][1][s["valid"] == 1], oo[s["valid"] == 1])
 
 
+TWIN_FAR_SCENE = "far:500:2.5:010:dt1"                    # the pose moves, from a matrix whose largest diagonal element is m11
+
+
 @pytest.mark.gpu
 def test_instrumented_twin_runs_the_same_pose_kernel(po, wl):
     """Round 6: the instrumented library (liblccrf_hip_instr.so) differs from the release one by profiling hooks only -- and its pose kernel's
@@ -203,18 +222,177 @@ def test_instrumented_twin_runs_the_same_pose_kernel(po, wl):
 import importlib, sys, numpy as np
 sys.path.insert(0, %r)
 pkg = importlib.import_module("lc-crf-slam_amd"); wl = importlib.import_module("lc-crf-slam_amd.workloads")
-for n in (2000, 500, 64, 9):
-    s = wl.pose_scene(n, seed=n + 1, noise=0.7, outlier_frac=0.15, mono_frac=0.2, n_invalid=0)
+sys.path.insert(0, %r)
+import pose_cases as pc
+# ... and the form that reads its edges from global memory (4097), and a start off the trace > 0 branch of the quaternion
+for n in (2000, 500, 64, 9, 4097, %r):
+    s = pc.scene(n) if isinstance(n, str) else wl.pose_scene(n, seed=n + 1, noise=0.7, outlier_frac=0.15, mono_frac=0.2, n_invalid=0)
     T, o, ninl = pkg.pose_optimization(s["Xw"], s["kp"], s["u_right"], s["inv_sigma2"], s["K4"], s["bf"], s["T_init"], valid=s["valid"])
     print(n, ninl, int(o.sum()), " ".join("%%08x" %% x for x in np.asarray(T, np.float32).reshape(-1).view(np.uint32)))
-""" % root
+""" % (root, os.path.join(root, "tests"), TWIN_FAR_SCENE)
+    assert pc.oracle(po, TWIN_FAR_SCENE)[4]["quat_y"] > 0 and not np.array_equal(pc.oracle(po, TWIN_FAR_SCENE)[0], pc.scene(TWIN_FAR_SCENE)["T_init"])
     outs = []
     for env in (dict(os.environ), cc.switch_env(LCCRF_POSE_TWIN="1")):     # (any switch selects the twin)
         env.pop("LCCRF_LIB", None) if env.get("LCCRF_POSE_TWIN") is None else None
         r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
-        outs.append(r.stdout.strip().splitlines()[-4:])
+        outs.append(r.stdout.strip().splitlines()[-6:])
     assert outs[0] == outs[1], (outs[0], outs[1])
     s = wl.pose_scene(2000, seed=2001, noise=0.7, outlier_frac=0.15, mono_frac=0.2, n_invalid=0)
     To, oo, no, _ = _run_oracle(po, s)
     assert int(outs[0][0].split()[1]) == no                  # ... and it is the restatement's answer
+
+
+# ---- the scene list of tests/pose_cases.py (checked on the CPU by tests/test_pose_cases.py) ------------------------------------------
+def _assert_matches(Th, oh, nh, To, oo, no, edge, what):
+    """the assertions of test_hip_pose_optimization_matches_the_restatement, the figures printed first"""
+    ulp, dist = pc.pose_distance(Th, To)
+    print("%s: inliers %d / %d, flags differing %d, pose %d ulp %.3g abs" % (what, nh, no, int((oh[edge] != oo[edge]).sum()), ulp, dist))
+    assert nh == no and np.array_equal(oh[edge], oo[edge])
+    assert ulp <= 2 or dist < 1e-7, (ulp, dist)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", pc.NAMES)
+def test_hip_pose_optimization_matches_the_restatement_on_the_scene_list(po, name):
+    """Every shape class of tests/pose_cases.py: frames of more than 4096 keypoints (the kernel form that reads its edges from global
+    memory, up to the cap of 16384), the thresholds of the schedule and of compact_level0, few valid points among many, initial poses
+    far from the truth (a system that is not positive definite, the quaternion of a matrix of trace <= 0, rho == 0, ten iterations),
+    points behind the camera (re-admitted edges), a chi2 that is not finite.  Same bar as above: equal counts, equal flags, 2 ulp."""
+    s = pc.scene(name)
+    To, oo, no, _, _ = pc.oracle(po, name)
+    Th, oh, nh = pkg.pose_optimization(s["Xw"], s["kp"], s["u_right"], s["inv_sigma2"], s["K4"], s["bf"], s["T_init"], valid=s["valid"])
+    _assert_matches(Th, oh, nh, To, oo, no, s["valid"] == 1, name)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [600, 5000])
+@pytest.mark.parametrize("with_valid", [False, True], ids=["label", "label+valid"])
+def test_hip_pose_optimization_label_argument_gates_edges(po, wl, n, with_valid):
+    """the single-frame entry point's `label`: a point labelled 0 has no edge, alone and together with `valid` -- the restatement
+    run with valid & (label != 0); 600 and 5000 points: both kernel forms read the labels"""
+    s = wl.pose_scene(n, seed=n + 1, n_invalid=n // 7 if with_valid else 0)
+    label = np.where(np.arange(n) % 3 == 1, 0, np.where(np.arange(n) % 2, 1, 2)).astype(np.int16)    # a third moving; static as 1 or 2
+    gate = (s["valid"] & (label != 0)).astype(np.uint8)
+    assert 0 < int(gate.sum()) < int(s["valid"].sum())
+    To, oo, no, _ = _run_oracle(po, s, gate)
+    Th, oh, nh = pkg.pose_optimization(s["Xw"], s["kp"], s["u_right"], s["inv_sigma2"], s["K4"], s["bf"], s["T_init"],
+                                       valid=s["valid"] if with_valid else None, label=label)
+    _assert_matches(Th, oh, nh, To, oo, no, gate == 1, "n = %d" % n)
+    assert not oh[gate == 0].any()                          # the wrapper's zeros, untouched
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [600, 5000])
+def test_hip_pose_optimization_leaves_flags_of_points_without_an_edge(po, wl, n):
+    """include/lccrf.h: entries of outlier_out of points without an edge are left as they were -- preset to 7, in both kernel
+    forms, with points gated by `valid` and by `label`; the flags of the edges are the restatement's whatever they held before"""
+    s = wl.pose_scene(n, seed=n + 1, n_invalid=n // 7)
+    label = np.where(np.arange(n) % 5 == 2, 0, 1).astype(np.int16)
+    gate = (s["valid"] & (label != 0)).astype(np.uint8)
+    To, oo, no, _ = _run_oracle(po, s, gate)
+    Th, oh, nh = pkg.pose_optimization(s["Xw"], s["kp"], s["u_right"], s["inv_sigma2"], s["K4"], s["bf"], s["T_init"], valid=s["valid"],
+                                       label=label, outlier=np.full(n, 7, np.uint8))
+    assert (gate == 0).sum() > n // 7 and np.all(oh[gate == 0] == 7)
+    _assert_matches(Th, oh, nh, To, oo, no, gate == 1, "n = %d" % n)
+
+
+def _run_then_pose(b, scenes, maxN, preset=7):
+    """lccrf_batch_run(5, with_map) and, right behind it with no synchronisation in between, lccrf_batch_pose_optimization of one scene
+    per frame (device arrays strided by maxN, built and settled before the run) -> (Tcw_in, Tcw_out, outlier, n_inliers, n_initial) on
+    the host; the outputs are preset (Tcw_out 9.0, outlier 7, counts -1) so that what the kernel leaves alone shows"""
+    import torch
+    dev = torch.device("cuda", 0)
+    F = len(scenes)
+
+    def t(key, tail):
+        a = np.zeros((F, maxN) + tail, np.float32)
+        for f, s in enumerate(scenes):
+            if s is not None:
+                a[f, :s[key].shape[0]] = s[key].reshape((-1,) + tail)
+        return torch.from_numpy(a).to(dev)
+    dX, dk, du, di = t("Xw", (3,)), t("kp", (2,)), t("u_right", ()), t("inv_sigma2", ())
+    some = next(s for s in scenes if s is not None)
+    Tin = np.stack([(s or some)["T_init"] for s in scenes]).astype(np.float32).reshape(F, 16)
+    dTi = torch.from_numpy(Tin).to(dev)
+    dTo = torch.full((F, 16), 9.0, dtype=torch.float32, device=dev)
+    dout = torch.full((F, maxN), preset, dtype=torch.uint8, device=dev)
+    dni, dn0 = torch.full((F,), -1, dtype=torch.int32, device=dev), torch.full((F,), -1, dtype=torch.int32, device=dev)
+    _arrays_ready()
+    b.run(5, True)
+    b.pose_optimization(dX.data_ptr(), dk.data_ptr(), du.data_ptr(), di.data_ptr(), some["K4"], some["bf"], dTi.data_ptr(),
+                        dTo.data_ptr(), dout.data_ptr(), dni.data_ptr(), dn0.data_ptr())
+    b.synchronize()
+    return Tin.reshape(F, 4, 4), dTo.cpu().numpy().reshape(F, 4, 4), dout.cpu().numpy(), dni.cpu().numpy(), dn0.cpu().numpy()
+
+
+def _oracle_static(po, pb):
+    import crf_cases as cc
+    o = cc.setup(po.OracleCRF, pb)
+    o.inference_native(5, True)
+    m = o.map().copy()
+    o.close()
+    return m
+
+
+@pytest.mark.gpu
+def test_batch_pose_of_a_ragged_batch(po, wl):
+    """F = 6, maxN = 1300, frames of 1300, 0, 2, 9, 10 and 777 points: every frame the restatement of that frame alone on the points the
+    oracle's CRF labels static (1e-6 on the pose, the batch tests' bar); a frame with fewer than three edges -- its workgroup
+    returns early, next to full frames -- hands Tcw_in back untouched with n_inliers = 0; nothing is written beyond a frame's
+    points or on points without an edge."""
+    import crf_cases as cc
+    sizes, maxN = (1300, 0, 2, 9, 10, 777), 1300
+    pbs = [wl.slam_problem(n, seed=1000 + n) if n else cc.empty_problem(2, [2, 2]) for n in sizes]
+    scenes = [wl.pose_scene(n, seed=1100 + n) if n else None for n in sizes]
+    b = cc.batch_of(pbs, maxN=maxN)
+    Tin, Tout, outl, ninl, n0 = _run_then_pose(b, scenes, maxN)
+    labels = b.map()
+    b.close()
+    early = 0
+    for f, n in enumerate(sizes):
+        ref = _oracle_static(po, pbs[f]) if n else np.zeros(0, np.int16)
+        assert np.array_equal(labels[f, :n], ref), f
+        static = (ref != 0).astype(np.uint8)
+        assert np.all(outl[f, n:] == 7) and np.all(outl[f, :n][static == 0] == 7), f
+        assert int(n0[f]) == int(static.sum()), f
+        if static.sum() < 3:
+            early += 1
+            assert int(ninl[f]) == 0 and np.array_equal(Tout[f].view(np.int32), Tin[f].view(np.int32)), f
+            assert not outl[f, :n][static == 1].any(), f
+            continue
+        s = scenes[f]
+        To, oo, no, _ = _run_oracle(po, s, static)
+        assert int(ninl[f]) == no and np.array_equal(outl[f, :n][static == 1], oo[static == 1]), f
+        assert np.abs(Tout[f] - To).max() < 1e-6, f
+    assert early >= 2
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("extra", [0, 100], ids=["4200+4100:crf_points_only", "4200+4100:extra_edges"])
+def test_batch_pose_beyond_the_staged_size(po, wl, extra):
+    """F = 2, maxN = 4200, frames of 4200 and 4100 keypoints: the kernel form that reads its edges from global memory, behind the
+    streaming engine's CRF -- once with every point a CRF point, once with the last 100 of each frame riding behind the CRF's
+    points as extra edges (lccrf_batch_pose_set_crf_counts: static whatever the label word holds)."""
+    import torch
+    import crf_cases as cc
+    totals, maxN = (4200, 4100), 4200
+    pbs = [wl.slam_problem(n - extra, seed=1200 + f) for f, n in enumerate(totals)]
+    scenes = [wl.pose_scene(n, seed=1300 + f) for f, n in enumerate(totals)]
+    b = cc.batch_of(pbs, maxN=maxN)
+    dtot = torch.tensor(totals, dtype=torch.int32, device=torch.device("cuda", 0))
+    b.pose_set_crf_counts(dtot.data_ptr() if extra else None)
+    Tin, Tout, outl, ninl, n0 = _run_then_pose(b, scenes, maxN)          # (settles dtot with its own arrays before the run)
+    labels, engine = b.map(), b.engine()
+    b.close()
+    assert engine == 1, engine                             # the streaming engine: frames of this size fit no one-launch kernel
+    for f, n in enumerate(totals):
+        ref = _oracle_static(po, pbs[f])
+        assert np.array_equal(labels[f, :n - extra], ref), f
+        gate = np.ones(n, np.uint8)
+        gate[:n - extra] = ref != 0
+        To, oo, no, ninit = _run_oracle(po, scenes[f], gate)
+        assert int(n0[f]) == ninit == int(gate.sum()) and int(ninl[f]) == no, f
+        assert np.array_equal(outl[f, :n][gate == 1], oo[gate == 1]), f
+        assert np.all(outl[f, n:] == 7) and np.all(outl[f, :n][gate == 0] == 7), f
+        assert np.abs(Tout[f] - To).max() < 1e-6, f
