@@ -64,7 +64,9 @@ int  lccrf_create(lccrf_handle *out, int device_id, int n_points, int n_labels);
  * The reference constructs and destroys one CRF per frame (src/Tracking.cc:1920); to keep that
  * pattern cheap a destroyed handle's device memory, stream and pinned staging are parked and
  * reused by the next lccrf_create of a compatible size.  lccrf_trim_cache() frees the parked
- * handles (returns how many).                                                             */
+ * handles (returns how many), and with them the staging areas (pinned host and device memory,
+ * stream) that lccrf_pose_optimization, lccrf_unary_build and lccrf_bf_match keep between calls
+ * and only ever grow; the next call of each tool allocates what it needs afresh.            */
 void lccrf_destroy(lccrf_handle h);
 int  lccrf_trim_cache(void);
 

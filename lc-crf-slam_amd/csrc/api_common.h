@@ -72,6 +72,8 @@ namespace lccrf {
 int use_device(int device_id);                                  // api_tools.hip
 bool default_single_wg();                                       // LCCRF_OPT_SINGLE_WORKGROUP's process-wide default (lccrf_set_default_option)
 void trim_pose_stages();                                        // frees lccrf_pose_optimization's staging areas (lccrf_trim_cache)
+void trim_unary_stage();                                        // unary_builder.hip: frees lccrf_unary_build's staging (lccrf_trim_cache)
+void trim_bf_stage();                                           // bf_match.hip: frees lccrf_bf_match's staging (lccrf_trim_cache)
 int apply_option(Engine &e, int option, int value);             // api_object.hip: the options a handle and a batch share
 // api_object.hip (section 1b): is `p` device memory of the engine's device, or pinned host memory, with `bytes` inside its allocation?
 int check_device_array(const Engine &eng, const void *p, size_t bytes, const char *what);

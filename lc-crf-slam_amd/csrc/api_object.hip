@@ -180,6 +180,8 @@ int lccrf_trim_cache(void)
         delete h;
     }
     trim_pose_stages();
+    trim_unary_stage();
+    trim_bf_stage();
     return (int)v.size();
 }
 

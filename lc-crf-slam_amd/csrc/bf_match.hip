@@ -83,7 +83,27 @@ struct Scratch {
     hipStream_t stream = nullptr;
 } g_bf;
 
+void release_bf()
+{
+    if (g_bf.host) (void)hipHostFree(g_bf.host);
+    if (g_bf.dev) (void)hipFree(g_bf.dev);
+    if (g_bf.stream) (void)hipStreamDestroy(g_bf.stream);
+    g_bf.host = g_bf.dev = nullptr;
+    g_bf.host_cap = g_bf.dev_cap = 0;
+    g_bf.stream = nullptr;
+}
+
 }  // namespace
+
+// lccrf_trim_cache: the matcher's staging (pinned arena, device buffer, stream); the next call allocates afresh
+void trim_bf_stage()
+{
+    std::lock_guard<std::mutex> g(g_bf.m);
+    if (!g_bf.host && !g_bf.dev && !g_bf.stream) return;
+    (void)hipSetDevice(g_bf.device);
+    if (g_bf.stream) (void)hipStreamSynchronize(g_bf.stream);
+    release_bf();
+}
 
 hipError_t run_bf_match(int device_id, int n_query, const uint8_t *desc_query, int n_train, const uint8_t *desc_train,
                         double ratio, int32_t *train_of_query_out, int32_t *n_matches_out)
@@ -91,12 +111,7 @@ hipError_t run_bf_match(int device_id, int n_query, const uint8_t *desc_query, i
     std::lock_guard<std::mutex> g(g_bf.m);
     hipError_t e;
     if (g_bf.device != device_id) {                       // the staging belongs to one device at a time
-        if (g_bf.host) (void)hipHostFree(g_bf.host);
-        if (g_bf.dev) (void)hipFree(g_bf.dev);
-        if (g_bf.stream) (void)hipStreamDestroy(g_bf.stream);
-        g_bf.host = g_bf.dev = nullptr;
-        g_bf.host_cap = g_bf.dev_cap = 0;
-        g_bf.stream = nullptr;
+        release_bf();
         g_bf.device = device_id;
     }
     if (!g_bf.stream && (e = hipStreamCreateWithFlags(&g_bf.stream, hipStreamNonBlocking)) != hipSuccess) return e;

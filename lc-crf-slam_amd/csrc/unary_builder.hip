@@ -120,6 +120,16 @@ void release_scratch()
 
 }  // namespace
 
+// lccrf_trim_cache: the unary builder's staging (pinned arena, device buffer, stream); the next call allocates afresh
+void trim_unary_stage()
+{
+    std::lock_guard<std::mutex> g(g_scratch.m);
+    if (!g_scratch.host && !g_scratch.dev && !g_scratch.stream) return;
+    (void)hipSetDevice(g_scratch.device);
+    if (g_scratch.stream) (void)hipStreamSynchronize(g_scratch.stream);
+    release_scratch();
+}
+
 // returns hipSuccess or the failing call's error
 hipError_t run_unary_build(int device_id, int n_points, const float *Xw, const int32_t *obs_ptr, const int32_t *obs_kf,
                            const double *obs_kp, int n_kf, const float *kf_pose, const float *kf_intr,
