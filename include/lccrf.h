@@ -485,6 +485,45 @@ int  lccrf_set_pairwise_normalization(lccrf_handle h, int kernel, int mode);
 int  lccrf_get_pairwise_normalization(lccrf_handle h, int kernel, int *mode);
 
 /* ======================================================================================
+ * 1h. Convergence-driven inference -- "run until converged, at most max_iterations" in place of a fixed iteration count.
+ *
+ * Definitions.  Q_0 is what lccrf_start_inference leaves, Q_t is one lccrf_step_inference(relax) applied to Q_{t-1}, and
+ *     d_t = max over i < N and l < L of fabsf(Q_t[i][l] - Q_{t-1}[i][l])      (fp32: one subtraction, one abs; a maximum of
+ *                                                                              non-negative floats does not depend on the order
+ *                                                                              it is taken in, so d_t is a defined bit pattern)
+ *     c_t = the number of points whose MAP label differs between Q_t and Q_{t-1} (buildMap's rule, densecrf3d.h:136-151: the
+ *           first maximum wins).
+ * `criterion` is a mask of the bits below; with both set, both conditions must hold.  The run stops behind the first t in
+ * 1 .. max_iterations at which every selected condition holds, else at t = max_iterations.  Per frame:
+ *     Q, the labels and label bits (with_map)   those of Q_t -- bit for bit what lccrf_inference(h, t, with_map, relax) leaves
+ *     iterations = t, delta = d_t, changed = c_t, converged = 1 when the criterion was met at t (at the cap too), 0 when the cap
+ *     ended the run.
+ * max_iterations == 0, or a frame of 0 points, gives Q_0 (nothing for the empty frame) and reports 0 / 0.0f / 0 / 0.
+ * LCCRF_E_INVALID for a criterion outside 1 .. 3, max_iterations < 0, a tol that is negative or not finite, or a relax that is not
+ * finite -- checked before the handle is looked at.  With non-finite Q the only promise is that the run ends no later than the cap.
+ *
+ * Engines.  A two-label handle with one or two 2-D Potts terms normalised AFTER, up to 4096 points and lattices that fit one
+ * workgroup's LDS runs the whole call in ONE launch (csrc/fused_converge.hip): the stop decision falls inside the kernel, and
+ * lccrf_get_engine reports 2 with the shape word.  Everything else -- other label counts or dimensions, more terms or points, a
+ * term with a matrix (1e) or a normalisation mode (1g), locality mode, lattices beyond LDS -- runs the streaming engine's step
+ * unchanged with a small comparison kernel behind each step; the host then reads ONE word per iteration (the number of frames still
+ * running) behind a synchronisation of the call's stream.  lccrf_get_engine reports 1.  The lattices are built and sized exactly as
+ * by lccrf_inference on built lattices; the call never takes the one-launch build + inference kernel and neither reads, writes
+ * nor invalidates prepared launch records.
+ *
+ * Behind the call the handle is as after lccrf_inference(h, t, ...): lccrf_step_inference continues from Q_t, the getters return
+ * Q_t and its labels, and lccrf_inference_backward(h, t, relax, ...) with the reported `iterations` is the gradient of the
+ * converged result (the stop decision itself is piecewise constant and contributes nothing).
+ * Added WITHOUT a step of LCCRF_ABI_VERSION: probe for the entry points by symbol.
+ * ==================================================================================== */
+#define LCCRF_STOP_DELTA  1   /* d_t <= tol  */
+#define LCCRF_STOP_LABELS 2   /* c_t == 0    */
+int  lccrf_inference_converged(lccrf_handle h, int max_iterations, int criterion, float tol, int with_map, float relax);
+/* What the last lccrf_inference_converged on the handle reported; any pointer may be NULL.  Waits for the handle's stream.
+ * LCCRF_E_STATE when no converged inference has run on the handle's current inputs.                                               */
+int  lccrf_get_convergence(lccrf_handle h, int *iterations, float *delta, int *changed, int *converged);
+
+/* ======================================================================================
  * 2. Batch API -- many independent frames in flight on one GPU.
  *    Every frame is one CRF of the object API; frames never interact.  Inputs may be
  *    handed over as host buffers (uploaded) or bound as DEVICE pointers (zero copy), so
@@ -677,6 +716,28 @@ int  lccrf_batch_inference_backward(lccrf_batch_handle b, int n_iterations, floa
  *     a multiple of 4 (plus 4 * F * max_points * L when d_grad_unary is NULL).  Added without a step of LCCRF_ABI_VERSION.         */
 int  lccrf_batch_inference_backward_features(lccrf_batch_handle b, int n_iterations, float relax, const float *d_grad_prob,
                                              float *d_grad_unary, float *d_grad_weights, float *const *d_grad_features, void *stream);
+
+/* ======================================================================================
+ * 2e. Section 1h for every frame of a batch: each frame stops on its own.  On built lattices (behind lccrf_batch_build),
+ * asynchronous on `stream` (NULL: the batch's own) like lccrf_batch_inference.  Batches the fused plan takes (two labels, one or
+ * two 2-D terms, up to 4096 points per frame, lattices that fit one workgroup's LDS) run in ONE launch, one frame per workgroup: a
+ * workgroup whose frame has converged stores its results and leaves its CU to the next frame; lccrf_batch_get_engine reports 2.
+ * Every other batch runs the streaming step for all frames until the last frame has finished (one word read by the host and one
+ * synchronisation of the call's stream per iteration): a finished frame's Q is kept aside at the iteration it finished and put
+ * back before the labels are formed -- stepping it further is wasted work, not a different result.  lccrf_batch_get_engine
+ * reports 1.  LCCRF_E_STATE before lccrf_batch_build; the argument checks of section 1h.
+ * ==================================================================================== */
+int  lccrf_batch_inference_converged(lccrf_batch_handle b, int max_iterations, int criterion, float tol, int with_map, float relax,
+                                     void *stream);
+/* Per frame of the batch, [n_frames] each, any pointer may be NULL: t, d_t, c_t and whether the criterion was met (a FOURTH array
+ * rather than a bit: 1 also when the criterion was met exactly at the cap, which `iterations < max_iterations` cannot tell).
+ * Waits for THIS batch's stream only (as lccrf_batch_synchronize), not for the device.  LCCRF_E_STATE when no converged inference
+ * has run on the current inputs.                                                                                                  */
+int  lccrf_batch_get_convergence_host(lccrf_batch_handle b, int32_t *iterations, float *delta, int32_t *changed, int32_t *converged);
+/* The same four arrays in the batch's HBM ([max_frames] each, owned by the batch, allocated when it is created), for a caller that
+ * stays on the device: valid behind the converged call in stream order.  Any pointer may be NULL.                                 */
+int  lccrf_batch_device_convergence(lccrf_batch_handle b, const int32_t **d_iterations, const float **d_delta,
+                                    const int32_t **d_changed, const int32_t **d_converged);
 
 /* ======================================================================================
  * 3. Unary builder -- the step right before the CRF (first "next" row):

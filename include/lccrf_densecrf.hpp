@@ -270,6 +270,8 @@ protected:
     int n_hip_ = 0;                       // ... of which this many are terms of the handle
     bool mixed_ = false;                  // some potential is not ours: host-array stepping (densecrf_base.h:82-91)
     bool base_sync_ = false;              // keep current_ fresh for readers that only hold a DenseCRF* (non-virtual getProbability)
+    int conv_iterations_ = 0, conv_changed_ = 0, conv_converged_ = 0;   // what the last inferenceConverged() reported
+    float conv_delta_ = 0.0f;
     mutable std::vector<short> map_buf_;
     mutable std::vector<float> cur_buf_, next_buf_, tmp_buf_;
 
@@ -356,6 +358,24 @@ public:
         if (with_map) lccrf_check(lccrf_get_map(h_, map_), "lccrf_get_map");
         if (base_sync_) syncProbability();
     }
+    // Mean-field iterations until converged, at most max_iterations (include/lccrf.h section 1h; no reference counterpart):
+    // criterion is a mask of LCCRF_STOP_DELTA (max |Q_t - Q_t-1| <= tol) and LCCRF_STOP_LABELS (no MAP label changed).  Results as
+    // after inference(iterations(), with_map, relax); what the run reported is in iterations() / delta() / changed() / converged().
+    // Not supported with foreign potentials (mixed()): throws std::runtime_error.
+    void inferenceConverged(int max_iterations, int criterion = LCCRF_STOP_LABELS, float tol = 0.0f, bool with_map = false,
+                            float relax = 1.0)
+    {
+        adopt();
+        if (mixed_) throw std::runtime_error("inferenceConverged: not supported with foreign potentials");
+        lccrf_check(lccrf_inference_converged(h_, max_iterations, criterion, tol, with_map ? 1 : 0, relax), "lccrf_inference_converged");
+        lccrf_check(lccrf_get_convergence(h_, &conv_iterations_, &conv_delta_, &conv_changed_, &conv_converged_), "lccrf_get_convergence");
+        if (with_map) lccrf_check(lccrf_get_map(h_, map_), "lccrf_get_map");
+        if (base_sync_) syncProbability();
+    }
+    int iterations() const { return conv_iterations_; }        // of the last inferenceConverged(): t, d_t, c_t, the criterion was met
+    float delta() const { return conv_delta_; }
+    int changed() const { return conv_changed_; }
+    bool converged() const { return conv_converged_ != 0; }
     void startInference() override                                             // densecrf_base.h:78
     {
         adopt();

@@ -127,6 +127,8 @@ protected:
     int n_terms_ = 0;                     // ... of which this many are terms of the handle
     std::vector<int> term_;               // per pairwise_ entry: its term in the handle, or -1 (a foreign potential)
     bool mixed_ = false;                  // some potential is not ours: stepping through the base class on device arrays
+    int conv_iterations_ = 0, conv_changed_ = 0, conv_converged_ = 0;   // what the last inferenceConverged() reported
+    float conv_delta_ = 0.0f;
 
     void adopt()
     {
@@ -221,6 +223,21 @@ public:
         }
         sync();
     }
+    // Mean-field iterations until converged, at most max_iterations (include/lccrf.h section 1h; DenseCRFHIP::inferenceConverged
+    // on device arrays); ends with a synchronisation like inference().  Not supported with foreign potentials (mixed()): throws.
+    void inferenceConverged(int max_iterations, int criterion = LCCRF_STOP_LABELS, float tol = 0.0f, bool with_map = false,
+                            float relax = 1.0)
+    {
+        adopt();
+        if (mixed_) throw std::runtime_error("inferenceConverged: not supported with foreign potentials");
+        lccrf_check(lccrf_inference_converged(h_, max_iterations, criterion, tol, with_map ? 1 : 0, relax), "lccrf_inference_converged");
+        lccrf_check(lccrf_get_convergence(h_, &conv_iterations_, &conv_delta_, &conv_changed_, &conv_converged_), "lccrf_get_convergence");
+        sync();
+    }
+    int iterations() const { return conv_iterations_; }        // of the last inferenceConverged(): t, d_t, c_t, the criterion was met
+    float delta() const { return conv_delta_; }
+    int changed() const { return conv_changed_; }
+    bool converged() const { return conv_converged_ != 0; }
     void startInference() override                // densecrf_base.h:78-80, unary_ being the handle's device unaries
     {
         adopt();

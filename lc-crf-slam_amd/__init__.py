@@ -27,6 +27,7 @@ OPT_SINGLE_WORKGROUP = 1        # lccrf_option (include/lccrf.h)
 OPT_VERTEX_ORDER = 2
 IMAGE_NONE, IMAGE_U8, IMAGE_F32 = 0, 1, 2   # lccrf_add_image_kernel's image formats
 NORMALIZE_AFTER, NORMALIZE_BEFORE, NORMALIZE_SYMMETRIC, NORMALIZE_NONE = 0, 1, 2, 3   # lccrf_normalization (section 1g)
+STOP_DELTA, STOP_LABELS = 1, 2   # lccrf_inference_converged's criterion bits (section 1h)
 OK = 0
 _STATUS = {0: "OK", -1: "E_INVALID", -2: "E_NO_DEVICE", -3: "E_HIP", -4: "E_NOMEM", -5: "E_STATE",
            -6: "E_CAPACITY"}
@@ -98,6 +99,11 @@ def lib():
     L.lccrf_get_probability.argtypes = [vp, _f32p]
     L.lccrf_get_engine.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lccrf_get_unary.argtypes = [vp, _f32p]
+    L.lccrf_inference_converged.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float]
+    L.lccrf_get_convergence.argtypes = [vp, C.POINTER(C.c_int), _f32p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.lccrf_batch_inference_converged.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, vp]
+    L.lccrf_batch_get_convergence_host.argtypes = [vp, _i32p, _f32p, _i32p, _i32p]
+    L.lccrf_batch_device_convergence.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.lccrf_get_lattice_size.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
     L.lccrf_pairwise_apply.argtypes = [vp, C.c_int, _f32p, _f32p]
     L.lccrf_exp_and_normalize.argtypes = [vp, _f32p, _f32p, C.c_float, C.c_float]
@@ -273,6 +279,19 @@ class DenseCRFHIP:
         _check(lib().lccrf_inference(self.h, int(n_iter), int(bool(with_map)), float(relax)))
 
     inference_native = inference
+
+    def inference_converged(self, max_iterations, criterion=STOP_LABELS, tol=0.0, with_map=False, relax=1.0):
+        """Mean-field iterations until every condition of `criterion` holds (STOP_DELTA: max |Q_t - Q_t-1| <= tol, STOP_LABELS: no
+        MAP label changed), at most max_iterations (include/lccrf.h section 1h).  Returns convergence()."""
+        _check(lib().lccrf_inference_converged(self.h, int(max_iterations), int(criterion), float(tol), int(bool(with_map)),
+                                               float(relax)))
+        return self.convergence()
+
+    def convergence(self):
+        """dict(iterations, delta (np.float32), changed, converged) of the last inference_converged()."""
+        it, ch, cv, d = C.c_int(0), C.c_int(0), C.c_int(0), C.c_float(0)
+        _check(lib().lccrf_get_convergence(self.h, C.byref(it), C.byref(d), C.byref(ch), C.byref(cv)))
+        return dict(iterations=it.value, delta=np.float32(d.value), changed=ch.value, converged=cv.value)
 
     def run_trace(self, n_iter, relax=1.0):
         out = np.empty((n_iter + 1, self.N, self.L), np.float32)
@@ -569,6 +588,26 @@ class BatchCRF:
     def inference(self, n_iter, with_map=True, relax=1.0, stream=None):
         _check(lib().lccrf_batch_inference(self.h, int(n_iter), int(bool(with_map)), float(relax),
                                            C.c_void_p(stream) if stream else None))
+
+    def inference_converged(self, max_iterations, criterion=STOP_LABELS, tol=0.0, with_map=True, relax=1.0, stream=None):
+        """Every frame iterated until ITS criterion holds, at most max_iterations, on built lattices (include/lccrf.h section 2e);
+        asynchronous like inference()."""
+        _check(lib().lccrf_batch_inference_converged(self.h, int(max_iterations), int(criterion), float(tol), int(bool(with_map)),
+                                                     float(relax), C.c_void_p(stream) if stream else None))
+
+    def convergence(self):
+        """dict of [n_frames] arrays: iterations, delta, changed, converged of the last inference_converged() (waits for the batch)."""
+        F = self.n_frames
+        it, ch, cv = (np.zeros(F, np.int32) for _ in range(3))
+        d = np.zeros(F, np.float32)
+        _check(lib().lccrf_batch_get_convergence_host(self.h, _p(it, _i32p), _p(d, _f32p), _p(ch, _i32p), _p(cv, _i32p)))
+        return dict(iterations=it, delta=d, changed=ch, converged=cv)
+
+    def device_convergence(self):
+        """device addresses of the four [max_frames] arrays: iterations (int32), delta (float32), changed (int32), converged (int32)"""
+        p = [C.c_void_p() for _ in range(4)]
+        _check(lib().lccrf_batch_device_convergence(self.h, *[C.byref(x) for x in p]))
+        return dict(zip(("iterations", "delta", "changed", "converged"), (x.value for x in p)))
 
     def run(self, n_iter, with_map=True, relax=1.0, stream=None):
         """Lattice build + normalisation + inference of every frame in one launch (lccrf_batch_run)."""

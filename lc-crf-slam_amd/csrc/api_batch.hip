@@ -471,6 +471,46 @@ int lccrf_batch_inference(lccrf_batch_handle b, int n_iterations, int with_map, 
     return timed_batch_call(e, stream, e.ev[2], e.ev[3], e.timed_inf, [&] { return e.inference(n_iterations, with_map, relax); });
 }
 
+// section 2e (the argument checks come first: they need no handle and no device)
+int lccrf_batch_inference_converged(lccrf_batch_handle b, int max_iterations, int criterion, float tol, int with_map, float relax,
+                                    void *stream)
+{
+    const int ra = Engine::check_converged_args(max_iterations, criterion, tol, relax);
+    if (ra) return ra;
+    CHECK_H(b);
+    Engine &e = b->eng;
+    if (!e.built) return fail(LCCRF_E_STATE, "lccrf_batch_build has not run for these inputs");
+    int rc = e.learn_sizes();
+    if (rc) return rc;
+    return timed_batch_call(e, stream, e.ev[2], e.ev[3], e.timed_inf,
+                            [&] { return e.inference_converged(max_iterations, criterion, tol, with_map, relax); });
+}
+
+int lccrf_batch_get_convergence_host(lccrf_batch_handle b, int32_t *iterations, float *delta, int32_t *changed, int32_t *converged)
+{
+    CHECK_H(b);
+    Engine &e = b->eng;
+    { int rl = e.resolve_late(); if (rl) return rl; }
+    const int rc = e.read_convergence();              // waits for this batch's stream (a caller's stream is ordered into it), not the device
+    if (rc) return rc;
+    void *outs[4] = {iterations, delta, changed, converged};
+    for (int a = 0; a < 4; ++a)
+        if (outs[a]) memcpy(outs[a], e.conv_host + (size_t)a * e.Fcap, sizeof(int32_t) * (size_t)e.F);
+    return LCCRF_OK;
+}
+
+int lccrf_batch_device_convergence(lccrf_batch_handle b, const int32_t **d_iterations, const float **d_delta, const int32_t **d_changed,
+                                   const int32_t **d_converged)
+{
+    CHECK_H(b);
+    const ConvergeOut o = b->eng.conv_out();
+    if (d_iterations) *d_iterations = o.iterations;
+    if (d_delta) *d_delta = o.delta;
+    if (d_changed) *d_changed = o.changed;
+    if (d_converged) *d_converged = o.converged;
+    return LCCRF_OK;
+}
+
 int lccrf_batch_run(lccrf_batch_handle b, int n_iterations, int with_map, float relax, void *stream)
 {
     CHECK_H(b);
@@ -592,6 +632,7 @@ int lccrf_batch_get_engine(lccrf_batch_handle b, int *engine_in_use)
         if (rc) return rc;
         e.engine_used = e.sized_engine;
     }
+    if (e.conv_engine) e.engine_used = e.conv_engine;        // the last inference was a converged one: what it ran on (section 2e)
     *engine_in_use = e.engine_used;
     return LCCRF_OK;
 }

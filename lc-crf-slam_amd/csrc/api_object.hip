@@ -307,6 +307,29 @@ int lccrf_inference(lccrf_handle h, int n_iterations, int with_map, float relax)
     return h->eng.inference(n_iterations, with_map, relax);
 }
 
+// section 1h (the argument checks come first: they need no handle and no device)
+int lccrf_inference_converged(lccrf_handle h, int max_iterations, int criterion, float tol, int with_map, float relax)
+{
+    const int ra = Engine::check_converged_args(max_iterations, criterion, tol, relax);
+    if (ra) return ra;
+    CHECK_H(h);
+    return h->eng.inference_converged(max_iterations, criterion, tol, with_map, relax);
+}
+
+int lccrf_get_convergence(lccrf_handle h, int *iterations, float *delta, int *changed, int *converged)
+{
+    CHECK_H(h);
+    Engine &e = h->eng;
+    { int rl = e.resolve_late(); if (rl) return rl; }
+    const int rc = e.read_convergence();
+    if (rc) return rc;
+    if (iterations) *iterations = e.conv_host[0];
+    if (delta) memcpy(delta, e.conv_host + e.Fcap, sizeof(float));
+    if (changed) *changed = e.conv_host[2 * (size_t)e.Fcap];
+    if (converged) *converged = e.conv_host[3 * (size_t)e.Fcap];
+    return LCCRF_OK;
+}
+
 int lccrf_get_engine(lccrf_handle h, int *engine, int *shape)
 {
     if (!h || !engine) return fail(LCCRF_E_INVALID, "handle / engine is NULL");

@@ -310,6 +310,37 @@ inline int fused_report(int lanes, int ppt, int chain0) { return lanes | ppt << 
 int launch_inference_general(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const float *const *compat,
                              const float *const *pre, int n_iter, int with_map, float relax, hipStream_t s);
 
+// ---- convergence-driven inference (include/lccrf.h sections 1h and 2e) ---------------------------------------------------------
+// what a converged run reports per frame, [F] each in HBM
+struct ConvergeOut {
+    int *iterations;      // t
+    float *delta;         // d_t
+    int *changed;         // c_t
+    int *converged;       // the criterion was met at t
+};
+// The fused engine's loop in its convergence form (fused_converge.hip): every frame of c on lattices that fit the fused plan, one
+// 1024-lane workgroup per frame, the stop decision inside the kernel.  Returns fused_report() of what it launched, or 0 when the
+// frames are not ones it takes -- not slam_shaped, beyond 4096 active points, or a plan that leaves no room for the reduction's
+// words in LDS -- and nothing was launched.
+int launch_inference_converged(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, int max_iter, int criterion,
+                               float tol, int with_map, float relax, const ConvergeOut &out, hipStream_t s);
+// ... and for everything else, the bookkeeping behind each step of the streaming engine (converge_track.hip): per frame the kept
+// copy of the previous Q (`prev`, [F][maxN][L] -- which IS the frame's Q at the iteration it finished, since a finished frame's
+// copy is no longer refreshed), the accumulators of the iteration, and whether the frame has finished.
+struct ConvergeTrack {
+    float *prev;          // [F][maxN][L]
+    unsigned *acc;        // [F][2]: bits of the largest |Q - prev| / flipped labels of the iteration (integer atomics: exact, order-free)
+    int *done;            // [F]
+    int *running;         // pinned host word: frames still running behind the last settle
+    ConvergeOut out;
+};
+// behind launch_start: prev = Q_0, the accumulators and results zeroed, frames without points (or max_iter == 0) finished
+void launch_track_begin(const CrfDev &c, const ConvergeTrack &tk, int max_iter, hipStream_t s);
+// behind step t: compare and refresh the running frames, then settle each of them and count the ones still running
+void launch_track_step(const CrfDev &c, const ConvergeTrack &tk, int t, int max_iter, int criterion, float tol, hipStream_t s);
+// behind the last step t_last: Q = prev for the frames that finished before it
+void launch_track_restore(const CrfDev &c, const ConvergeTrack &tk, int t_last, hipStream_t s);
+
 // ---- frame engine (SLAM sizes; lattice build + normalisation + inference of a frame in ONE launch) ---------
 bool frame_supported(const CrfDev &c, const KernelDev *kds);
 // label != nullptr (L = 2): the unary energies are derived in the kernel from the labels and the 5 table entries

@@ -558,6 +558,50 @@ __device__ __forceinline__ void start_inference(PointRegs<PPT, K> &pr, int N, in
     }
 }
 
+// The loop's convergence form (fused_converge.hip; include/lccrf.h section 1h): the run ends behind the first iteration t at which
+// every condition of `criterion` holds -- d_t = max |Q_t - Q_{t-1}| <= tol (LCCRF_STOP_DELTA), c_t = points whose MAP label changed
+// == 0 (LCCRF_STOP_LABELS) -- or at n_iter.  A maximum of non-negative floats is the maximum of their bit patterns and a count is a
+// sum of integers: both are exact whatever the order, so d_t and c_t are defined values.
+struct Converge {
+    int criterion;                        // LCCRF_STOP_* bits (1 .. 3)
+    float tol;
+    int words;                            // LDS byte offset of the reduction's four words {d bits, c} x iteration parity, behind the plan's
+                                          //   `total`; the caller zeroes them in front of a barrier
+    int iterations, changed, converged;   // out: t, c_t, the criterion was met (0 / 0 / 0 when nothing was iterated)
+    unsigned delta;                       // out: the bits of d_t
+};
+
+// One iteration's decision.  Called by EVERY lane of the workgroup, outside the per-point regions (the cross-lane steps run with
+// all lanes): d / flips are the lane's own maximum (bits) and flipped slots (bit s), 0 for lanes and slots without a point.
+// Wavefront: the maximum by butterfly, the count from the ballots.  Workgroup: one LDS max and one LDS add per wavefront into the
+// words of this iteration's parity, then ONE barrier, then every lane reads the same two words.  Lane 0 clears the other parity's
+// words for the next iteration: their last readers passed the barriers of this iteration's splat_blur long ago.
+template <int PPT>
+__device__ __forceinline__ bool converge_decide(unsigned char *smem, Converge &cv, int it, int tid, unsigned d, unsigned flips)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) d = max(d, (unsigned)__shfl_xor((int)d, o));
+    int c = 0;
+#pragma unroll
+    for (int s = 0; s < PPT; ++s) c += __popcll(__ballot((flips >> s) & 1u));
+    unsigned *w = reinterpret_cast<unsigned *>(smem + cv.words);
+    unsigned *mine = w + 2 * (it & 1), *other = w + 2 * ((it + 1) & 1);
+    if ((tid & 63) == 0) {
+        atomicMax(&mine[0], d);
+        atomicAdd(&mine[1], (unsigned)c);
+    }
+    if (tid == 0) other[0] = other[1] = 0u;
+    __syncthreads();
+    const unsigned dall = mine[0], call = mine[1];
+    const bool met = (!(cv.criterion & LCCRF_STOP_DELTA) || __uint_as_float(dall) <= cv.tol) &&
+                     (!(cv.criterion & LCCRF_STOP_LABELS) || call == 0u);
+    cv.iterations = it + 1;
+    cv.delta = dall;
+    cv.changed = (int)call;
+    cv.converged = met ? 1 : 0;
+    return met;
+}
+
 // n_iter x stepInference (densecrf_base.h:82-91): splat, blur, then slice + apply + softmax per point.
 // first_p (bit k): with own product buffers the loop starts by writing every kernel's products of Q0; a caller that has
 // already put kernel k's in place (the frame kernel's two-workgroup form, while it waits for the other lattice) clears bit k.
@@ -566,11 +610,17 @@ __device__ __forceinline__ void start_inference(PointRegs<PPT, K> &pr, int N, in
 // GEN (with gt): the terms of GeneralTerms -- the filter's input through filter_input, and behind the slice section 1e's sum for a
 // term with a matrix: s = 0; s = s + mu[l][0] * t[0]; s = s + mu[l][1] * t[1], every product and sum rounded on its own as in
 // k_slice_compat (stream_filter.hip).  The sum starts at 0 literally: slice_point's shortcut is not valid here, 0 + (-0) is +0.
-template <int PPT, int K, int CH, int NT = kNT, bool REV = false, bool GEN = false>
+// CONV (with cv): the convergence form -- at the softmax the old and the new Q of a point sit in the same lane, which keeps the
+// maximum of |new - old| and its flipped labels; converge_decide() behind the point phase ends the loop.  The products of the next
+// iteration are already written when the decision falls (`more`): nobody reads them.  Every other instantiation takes CONV = false
+// and compiles as it did.
+template <int PPT, int K, int CH, int NT = kNT, bool REV = false, bool GEN = false, bool CONV = false>
 __device__ __forceinline__ void mean_field(unsigned char *smem, const FusedLayout &lay, const int (&V)[K], int N, int tid,
                                            PointRegs<PPT, K> &pr, const ChainLane &cl, const float (&alpha)[K], int n_iter,
-                                           float relax, Instr &ins, int first_p = -1, const GeneralTerms<PPT, K> *gt = nullptr)
+                                           float relax, Instr &ins, int first_p = -1, const GeneralTerms<PPT, K> *gt = nullptr,
+                                           Converge *cv = nullptr)
 {
+    unsigned cv_d = 0u, cv_flips = 0u;         // CONV: this lane's max |dQ| (bits) and flipped slots of the current iteration
     // slice + apply + softmax of point slot s (X)
     auto point_update = [&](int s) {
         float nx[2] = {-pr.un[s].x, -pr.un[s].y};                 // stepInit, densecrf3d.h:154-158
@@ -591,7 +641,14 @@ __device__ __forceinline__ void mean_field(unsigned char *smem, const FusedLayou
             nx[0] += pr.wn[s][k] * t.x;                           // pairwise3d.h:77
             nx[1] += pr.wn[s][k] * t.y;
         }
-        pr.q[s] = softmax2(nx[0], nx[1], pr.q[s], relax);        // densecrf3d.h:70-98 with L = 2: one exp, not two
+        if constexpr (CONV) {
+            const float2 was = pr.q[s];
+            pr.q[s] = softmax2(nx[0], nx[1], was, relax);
+            cv_d = max(cv_d, max(__float_as_uint(fabsf(pr.q[s].x - was.x)), __float_as_uint(fabsf(pr.q[s].y - was.y))));
+            cv_flips |= (unsigned)((pr.q[s].x < pr.q[s].y) != (was.x < was.y)) << s;   // densecrf3d.h:145 on both
+        } else {
+            pr.q[s] = softmax2(nx[0], nx[1], pr.q[s], relax);    // densecrf3d.h:70-98 with L = 2: one exp, not two
+        }
     };
     if (PPT <= 2 && lay.prod_all) {            // (3-4 points per lane: the fused form costs registers the loop does not have)
         // Every kernel owns its product buffer: a point's next products go out right behind its softmax, so one
@@ -623,6 +680,10 @@ __device__ __forceinline__ void mean_field(unsigned char *smem, const FusedLayou
                 }
             }
             FL_STAMP();
+            if constexpr (CONV) {
+                if (converge_decide<PPT>(smem, *cv, it, tid, cv_d, cv_flips)) break;
+                cv_d = cv_flips = 0u;
+            }
         }
         return;
     }
@@ -633,6 +694,10 @@ __device__ __forceinline__ void mean_field(unsigned char *smem, const FusedLayou
         for (int s = 0; s < PPT; ++s)
             if (tid + s * NT < N) point_update(s);
         FL_STAMP();
+        if constexpr (CONV) {
+            if (converge_decide<PPT>(smem, *cv, it, tid, cv_d, cv_flips)) break;
+            cv_d = cv_flips = 0u;
+        }
     }
 }
 

@@ -231,6 +231,21 @@ struct Engine {
     const float *pre_ptr[LCCRF_MAX_KERNELS] = {};
     bool factors_dirty = true;         // kdevs_post / pre_ptr are behind kdevs or the modes (raised by sync_views and set_norm_mode)
 
+    // ---- convergence-driven inference ----
+    // sections 1h and 2e: what the last converged run reported per frame -- four [Fcap] arrays in HBM, written by the kernel of
+    // fused_converge.hip or by the bookkeeping of converge_track.hip -- with the pinned mirror the host getters copy into, the
+    // streaming path's accumulators / finished flags and its pinned "frames still running" word.  All allocated by init(): a
+    // converged call allocates nothing on the one-launch path (the streaming path's kept copy of Q is io_a, need_io()).
+    int *conv_dev = nullptr;           // device [7][Fcap]: iterations, delta (float), changed, converged, acc [Fcap][2], done
+    int *conv_host = nullptr;          // pinned [4][Fcap]
+    int *conv_running = nullptr;       // pinned [1]
+    bool conv_valid = false;           // a converged run has reported on the current inputs
+    int conv_engine = 0;               // report only (lccrf_batch_get_engine): 2 / 1 when the last inference was a converged one, else 0
+    ConvergeOut conv_out() const
+    {
+        return ConvergeOut{conv_dev, reinterpret_cast<float *>(conv_dev + Fcap), conv_dev + 2 * (size_t)Fcap, conv_dev + 3 * (size_t)Fcap};
+    }
+
     // ---- timing ----
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // build begin/end, inference begin/end
     bool timed_build = false, timed_inf = false;
@@ -248,7 +263,7 @@ struct Engine {
     void invalidate_lattices() { built_upto = 0; sizes_known = false; }
     void invalidate_lean_prep() { lean_prep.valid = false; lean_prep.seen_key = 0; }
     // new inputs (a batch's next frames, a parked handle's next user): nothing set, built or started, every lattice stale
-    void forget_inputs() { unary_set = built = started = false; invalidate_lattices(); }
+    void forget_inputs() { unary_set = built = started = conv_valid = false; conv_engine = 0; invalidate_lattices(); }
     // term k gets the weight w (settle a pending inference first): whatever was prepared for the old weights is rewritten
     void set_weight(int k, float w) { kernels[k].dev.w = w; sync_views(); invalidate_lean_prep(); }
 
@@ -273,6 +288,10 @@ struct Engine {
     int inference(int n_iter, int with_map, float relax);
     int run(int n_iter, int with_map, float relax);
     int inference_sized(int n_iter, int with_map, float relax);
+    static int check_converged_args(int max_iter, int criterion, float tol, float relax);
+    int inference_converged(int max_iter, int criterion, float tol, int with_map, float relax);
+    int converge_stream(int max_iter, int criterion, float tol, int with_map, float relax);
+    int read_convergence();
     int resolve_late(bool *seen_done = nullptr);
     int rerun_frames(int n);
 

@@ -289,6 +289,10 @@ int Engine::init(int device_id, int frames, int max_points, int n_labels)
     if ((rc = mem.alloc_pinned(&fb_list_host, Fcap))) return rc;
     if ((rc = mem.alloc_pinned(&npoints_bad, 1))) return rc;
     *npoints_bad = 0;
+    if ((rc = mem.alloc(&conv_dev, (size_t)7 * Fcap))) return rc;
+    if ((rc = mem.alloc_pinned(&conv_host, (size_t)4 * Fcap))) return rc;
+    if ((rc = mem.alloc_pinned(&conv_running, 1))) return rc;
+    *conv_running = 0;
     crf.F = F;
     crf.maxN = maxN;
     crf.L = L;
@@ -775,6 +779,7 @@ int Engine::run_frame(int n_iter, int with_map, float relax)
     frame_lean_used = shape == 2;
     fused_shape = shape == 0 ? (1024 | 1 << 16) : (512 | 2 << 16);       // lanes per frame | frames per CU
     engine_shape = 0;
+    conv_engine = 0;
 
     late_pending = true;
     late_iter = n_iter;
@@ -846,6 +851,7 @@ int Engine::inference_sized(int n_iter, int with_map, float relax)
     engine_used = sized_engine;
     engine_shape = 0;
     last_with_map = with_map;
+    conv_engine = 0;
     if (perm_on) {
         // locality mode: iterate on the internal-order view, un-permute Q on the way out (densecrf_base.h:65-73 otherwise)
         CrfDev cp = crf;
@@ -900,6 +906,101 @@ int Engine::inference_sized(int n_iter, int with_map, float relax)
         if (with_map) launch_map(crf, stream);
     }
     HIP_TRY(hipGetLastError());
+    return LCCRF_OK;
+}
+
+// ---- convergence-driven inference (include/lccrf.h sections 1h and 2e) ------------------------------------------------------
+int Engine::check_converged_args(int max_iter, int criterion, float tol, float relax)
+{
+    if (criterion < 1 || criterion > (LCCRF_STOP_DELTA | LCCRF_STOP_LABELS))
+        return fail(LCCRF_E_INVALID, "criterion %d is not a mask of LCCRF_STOP_DELTA (1) and LCCRF_STOP_LABELS (2)", criterion);
+    if (max_iter < 0) return fail(LCCRF_E_INVALID, "max_iterations < 0");
+    if (!std::isfinite(tol) || tol < 0.0f) return fail(LCCRF_E_INVALID, "tol must be finite and >= 0");
+    if (!std::isfinite(relax)) return fail(LCCRF_E_INVALID, "relax is not finite");
+    return LCCRF_OK;
+}
+
+// On lattices in HBM, built and sized as inference_sized() does it (never the one-launch build + inference kernel, and the prepared
+// launch records are left alone): the frames the fused plan takes in ONE launch with the stop decision inside the kernel, the rest
+// on the streaming step with the bookkeeping of converge_track.hip behind it.
+int Engine::inference_converged(int max_iter, int criterion, float tol, int with_map, float relax)
+{
+    int rc = check_converged_args(max_iter, criterion, tol, relax);
+    if (rc) return rc;
+    if (!unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
+    if ((rc = resolve_late())) return rc;
+    perm_scope = true;                                // (large frames: lattices built from here may use locality mode)
+    rc = learn_sizes();
+    perm_scope = false;
+    if (!rc) rc = ensure_unary();
+    if (!rc) rc = ensure_factors();
+    if (rc) return rc;
+    last_with_map = with_map;
+    conv_valid = false;
+    if (sized_engine == 2 && !perm_on) {
+        const int shape = launch_inference_converged(crf, kdevs.data(), maxV.data(), maxRow.data(), max_iter, criterion, tol, with_map,
+                                                     relax, conv_out(), stream);
+        if (shape) {
+            HIP_TRY(hipGetLastError());
+            engine_used = conv_engine = 2;
+            engine_shape = shape;
+            started = conv_valid = true;
+            return LCCRF_OK;
+        }
+    }
+    engine_used = conv_engine = 1;
+    engine_shape = 0;
+    if ((rc = converge_stream(max_iter, criterion, tol, with_map, relax))) return rc;
+    conv_valid = true;
+    return LCCRF_OK;
+}
+
+// The streaming path: start, then per iteration the unchanged step, the comparison and the settle kernel, ONE synchronisation of the
+// call's stream and one pinned word read -- the frames still running.  These are the frames where an iteration is many launches
+// anyway.  The kept copy of the previous Q is io_a.
+int Engine::converge_stream(int max_iter, int criterion, float tol, int with_map, float relax)
+{
+    int rc = need_io();
+    if (rc) return rc;
+    CrfDev cp = crf;
+    if (perm_on) {                                    // locality mode: iterate (and compare) in the internal order, as inference_sized()
+        cp.Q = Qp;
+        if (!unary_is_label) {
+            if (!unary_p_valid || crf.unary != unary_own) launch_permute_rows(crf, unary_p, crf.unary, L, 1, stream);
+            unary_p_valid = true;
+            cp.unary = unary_p;
+        }
+        launch_start(cp, stream);
+        started = true;
+    } else if ((rc = start())) {
+        return rc;
+    }
+    const ConvergeTrack tk{io_a, reinterpret_cast<unsigned *>(conv_dev + 4 * (size_t)Fcap), conv_dev + 6 * (size_t)Fcap, conv_running,
+                           conv_out()};
+    launch_track_begin(cp, tk, max_iter, stream);
+    int t_last = 0;
+    for (int t = 1; t <= max_iter; ++t) {
+        launch_step_stream(cp, step_kdevs(), maxV.data(), relax, stream, compat_arg(), pre_arg());
+        launch_track_step(cp, tk, t, max_iter, criterion, tol, stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(stream));
+        t_last = t;
+        if (*conv_running == 0) break;
+    }
+    if (F > 1 && t_last > 1) launch_track_restore(cp, tk, t_last, stream);
+    if (perm_on) launch_permute_rows(crf, crf.Q, Qp, L, 0, stream);
+    if (with_map) launch_map(crf, stream);
+    HIP_TRY(hipGetLastError());
+    return LCCRF_OK;
+}
+
+// the four result arrays of the frames bound into conv_host, behind everything queued on the engine's stream
+int Engine::read_convergence()
+{
+    if (!conv_valid) return fail(LCCRF_E_STATE, "no converged inference has run on the current inputs");
+    for (int a = 0; a < 4; ++a)
+        HIP_TRY(hipMemcpyAsync(conv_host + (size_t)a * Fcap, conv_dev + (size_t)a * Fcap, sizeof(int) * (size_t)F, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     return LCCRF_OK;
 }
 
