@@ -8,7 +8,7 @@
 //   * the large lattice's blur neighbour table (14 KB at V = 1160): read from HBM/L2 pass by pass, coalesced, each pass's words
 //     requested while the pass before is running (a small lattice's table stays in LDS);
 //   * the closed-form placement of the chain rows (14 spare slots per row): rows are placed by a scan over the ranked rows, the
-//     kChainTop longest ones (first wavefront pair: the rows everybody waits for) padded to 4 products + their own eight zeros for
+//     kLeanChainTop longest ones (first chain wavefront: the rows everybody waits for) padded to 4 products + their own eight zeros for
 //     chain_rows' address clamp, every other row padded to 4 only -- chain_rows_sel picks the address of every 16-byte read
 //     (row or a shared zero block) with a compare + select instead of the clamp.
 // Same products, same places in the same rows, every row added strictly left to right: the same bits as fused_loop.h.
@@ -33,14 +33,20 @@
 namespace lccrf {
 namespace fl {
 
+// rows of the first chain wavefront (lean_chain_row); -DLCCRF_CHAIN_TOP=32 fills that wavefront: C2 +0.1 to +1 %, so 16 stays (notes/r8_experiments.md)
+#ifndef LCCRF_CHAIN_TOP
+#define LCCRF_CHAIN_TOP 16
+#endif
+constexpr int kLeanChainTop = LCCRF_CHAIN_TOP;
+static_assert(kLeanChainTop == kChainTop || kLeanChainTop == 32, "16 rows on the lanes chain_top_rank names, or a full wavefront");
 constexpr int kLeanMaxRounds = 4;         // vertices per lane and kernel in the blur passes (register rounds): V <= 1536 in both shapes
 __host__ __device__ constexpr int lean_rounds(int nt) { return nt >= 512 ? 3 : 4; }
 __host__ __device__ constexpr int lean_max_v(int nt) { return 3 * (nt - 64); }   // (the overlapped blur schedule: 3 rounds of nt - 64 lanes)
 
-// product slots per label plane of the chain kernel: rows padded to 4, eight zeros behind each of the kChainTop longest
+// product slots per label plane of the chain kernel: rows padded to 4, eight zeros behind each of the kLeanChainTop longest
 __host__ __device__ inline int lean_plane_floats(int NA, int V0)
 {
-    const int top = V0 < kChainTop ? V0 : kChainTop;
+    const int top = V0 < kLeanChainTop ? V0 : kLeanChainTop;
     return (NA * kD1 + 11 * top + 3 * (V0 - top) + 16 + 63) & ~63;
 }
 
@@ -238,8 +244,27 @@ __device__ __forceinline__ float2 slice_point_lean(const PointRegs<PPT, K> &pr, 
     return make_float2(t0, t1);
 }
 
+// Which chain row lane `tid` of the workgroup sums: rank | label << 16, or -1 for none (a rank >= V0 is no row either).  BOTH labels of
+// a row are summed in ONE wavefront -- a dependent add holds the SIMD's VALU as long for 16 active lanes as for 64, so a second
+// wavefront per rank range (fused_loop.h: wavefront pairs) costs a full ring's issue time for work that fits the idle lanes of the first:
+//   wavefront 0      the kLeanChainTop longest rows: label 0 on the lanes chain_top_rank names, label 1 on those lanes + 16 -- the same
+//                    number of lanes in each of the four 16-lane groups a ds_read_b128 is served in;
+//   wavefront w >= 1 ranks kLeanChainTop + 32 (w - 1) + (lane & 31), label lane >> 5.
+__host__ __device__ constexpr int lean_chain_row(int tid)
+{
+    const int w = tid >> 6, ln = tid & 63;
+    if (w == 0 && kLeanChainTop < 32) {
+        const int r = chain_top_rank(ln & ~16);
+        return r >= 0 ? (r | (((ln >> 4) & 1) << 16)) : -1;
+    }
+    return (w == 0 ? (ln & 31) : kLeanChainTop + ((w - 1) << 5) + (ln & 31)) | ((ln >> 5) << 16);
+}
+// chain wavefronts of a lattice of V0 vertices (chain_max_v(512) = 208 vertices: 1 + 192 / 32 = 7 of the workgroup's 8)
+__host__ __device__ constexpr int lean_chain_waves(int V0) { return 1 + (((V0 > kLeanChainTop ? V0 - kLeanChainTop : 0) + 31) >> 5); }
+static_assert(lean_chain_waves(chain_max_v(kNTSmall)) <= kNTSmall / 64, "every chain row of the plan has a lane");
+
 // Chain lanes of the lean plan.  Ranking as chain_setup (counting sort on the rows' 16-product block count, longest first); then
-// one wavefront places the rows by a scan in rank order -- ceil4(length) slots, + 8 zeros for the kChainTop first -- and leaves
+// one wavefront places the rows by a scan in rank order -- ceil4(length) slots, + 8 zeros for the kLeanChainTop first -- and leaves
 // the starts in lay.pstart.  ChainLane: a = row address | wavefront max quads << 18;  b = quads of the padded row | pad slots << 13 |
 // output index << 16.  Every lane of the workgroup calls it; ends with a barrier (the scratch becomes the product buffer).
 template <int NT>
@@ -282,7 +307,7 @@ __device__ __forceinline__ ChainLane chain_setup_lean(unsigned char *smem, const
             if (r < V0) {
                 const int v = srt[r];
                 const int rl = (int)row[v + 1] - (int)row[v];
-                sz[u] = ((rl + 3) & ~3) + (r < kChainTop ? 8 : 0);
+                sz[u] = ((rl + 3) & ~3) + (r < kLeanChainTop ? 8 : 0);
             }
             sum += sz[u];
         }
@@ -301,9 +326,9 @@ __device__ __forceinline__ ChainLane chain_setup_lean(unsigned char *smem, const
         }
     }
     __syncthreads();
-    // wavefront pair p = (2p, 2p+1) owns labels 0 and 1 of a rank range (chain_setup): pair 0 the kChainTop longest rows
-    const int l = (tid >> 6) & 1, pr = tid >> 7, ln = tid & 63;
-    const int r = pr == 0 ? (chain_top_rank(ln) >= 0 ? chain_top_rank(ln) : V0) : kChainTop + ((pr - 1) << 6) + ln;
+    // one wavefront per rank range, both labels of a row in it (lean_chain_row): wavefront 0 the kLeanChainTop longest rows
+    const int cr = lean_chain_row(tid);
+    const int l = cr >> 16, r = cr < 0 ? V0 : (cr & 0xffff);
     unsigned quads = 0, addr = 0;
     if (r < V0) {
         const int v = srt[r];
@@ -320,14 +345,14 @@ __device__ __forceinline__ ChainLane chain_setup_lean(unsigned char *smem, const
     return cl;
 }
 
-// behind a chain row: +0 up to a multiple of 4; the first wavefront pair's rows also get the eight +0 chain_rows reads past the end
+// behind a chain row: +0 up to a multiple of 4; the first wavefront's rows also get the eight +0 chain_rows reads past the end
 __device__ __forceinline__ void chain_pads_lean(unsigned char *smem, const ChainLane &cl, int tid)
 {
     if (cl.b >> 16) {
         float *e = reinterpret_cast<float *>(smem + (cl.a & 0x3ffffu)) + (cl.b & 0x1fffu) * 4u;
         const unsigned npad = (cl.b >> 13) & 3u;
         for (unsigned z = 1; z <= npad; ++z) e[-(int)z] = 0.0f;
-        if ((tid >> 7) == 0) {
+        if ((tid >> 6) == 0) {
             reinterpret_cast<float4 *>(e)[0] = make_float4(0.f, 0.f, 0.f, 0.f);
             reinterpret_cast<float4 *>(e)[1] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
@@ -534,7 +559,7 @@ struct LeanPrepPlan {
                                                          //   u32 [D1][snbr_axis / 4]; snbr_axis = 0: the kernel keeps the build's numbering
     int total;                                           // multiple of 256
 };
-constexpr unsigned kLeanPrepFormat = 7;                  // (mixed into the blocks' validity key)
+constexpr unsigned kLeanPrepFormat = 8;                  // (mixed into the blocks' validity key)
 // sorted (k_fused_lean only; k_fused's blocks keep the round-6 format): every kernel but the chain kernel -- whose table is the only
 // one in LDS -- is renumbered by row length (sort_short_rows): its ix words and row table hold the new numbers, and its neighbour
 // table in the new numbering follows the LDS tables
@@ -623,24 +648,24 @@ __device__ __forceinline__ void mean_field_lean(unsigned char *smem, const Fused
     auto phase_S = [&](int k) {
         float *val = reinterpret_cast<float *>(smem + lay.val[k][0]);
         if (chain_k<CH>(lay, k)) {
-            const int npairs = 1 + ((max(V[k] - kChainTop, 0) + 63) >> 6);
+            const int nwaves = lean_chain_waves(V[k]);
             // (marked likely: the register allocator weighs spill code by block frequency, and values it parks in v96..v127 -- which
             // the rings clobber -- would be spilled around this block if it looked cold)
-            if (__builtin_expect((t >> 7) < npairs, 1)) {                            // whole wavefronts
+            if (__builtin_expect((t >> 6) < nwaves, 1)) {                            // whole wavefronts
                 FL_PSTAMP();
-                if ((t >> 7) == 0) __builtin_amdgcn_s_setprio(3);
+                if ((t >> 6) == 0) __builtin_amdgcn_s_setprio(3);
                 // (opaque: the row's address, end and trip counts are formed HERE -- hoisted out of the loop they would sit in
                 // registers, or scratch, for the whole launch; the two words themselves ride through the ring as operands)
                 asm volatile("" : "+v"(cl.a), "+v"(cl.b));
                 if (__builtin_expect((cl.b >> 16) != 0, 1) && !LEAN_SKIP(2)) {     // (LEAN_SKIP: timing experiments, see the top of the file)
                     const unsigned row_addr = cl.a & 0x3ffffu, row_end = row_addr + (cl.b & 0x1fffu) * 16u;
                     const unsigned m = (unsigned)__builtin_amdgcn_readfirstlane((int)(cl.a >> 18));       // the wavefront's longest row, quads
-                    const float acc = (t >> 7) == 0 ? chain_rows_keep(row_addr, row_end, (((m + 1u) >> 1) + 3u) >> 2, cl.a, cl.b)
+                    const float acc = (t >> 6) == 0 ? chain_rows_keep(row_addr, row_end, (((m + 1u) >> 1) + 3u) >> 2, cl.a, cl.b)
                                                       : chain_rows_sel(row_addr, (int)((cl.b & 0x1fffu) * 16u), (m + 7u) >> 3, cl.a, cl.b);
                     val[cl.b >> 16] = acc;
                 }
                 LEAN_FRESH_T();                               // (nothing of the lane id was kept across the ring)
-                if ((t >> 7) == 0) __builtin_amdgcn_s_setprio(0);
+                if ((t >> 6) == 0) __builtin_amdgcn_s_setprio(0);
                 FL_PSTAMP();
             }
             return;
@@ -736,21 +761,23 @@ __device__ __forceinline__ void mean_field_lean(unsigned char *smem, const Fused
         }
     };
     // ---- K = 2 with a chain kernel (the SLAM configuration): the blur passes are dealt to the wavefronts so that they hide ------
-    //   under the chain (S of kernel 0): the wavefronts behind the first pair, once their own chain rows are summed, run blur
-    //       pass 0 of kernel 1 -- its row sums were complete two barriers ago -- beside the pair that adds the longest rows;
+    //   under the chain (S of kernel 0): the wavefronts behind the first, once their own chain rows are summed, run blur
+    //       pass 0 of kernel 1 -- its row sums were complete two barriers ago -- beside the wavefront that adds the longest rows;
     //   behind the next barrier: the last wavefront alone runs the passes of kernel 0's small lattice (one wavefront's LDS operations
     //       execute in order, so its passes need no workgroup barrier between them) -- passes 0 and 1 while the others run pass 1 of
     //       kernel 1, pass 2 beside their pass 2.  Three barriers from the chain to X instead of four, kernel 0's passes and a third of kernel 1's
     //   off the critical path.  Same operations on the same values per vertex: only who executes them, and when, differs.
     constexpr bool OVL = K == 2 && CH == 1;
-    constexpr int NA0 = NT - 128, RA = 4;                 // pass 0 of kernel 1: lanes 128 .. NT-1, vertex (t - 128) + r * NA0
+    constexpr int A0 = 64;                                // pass 0 of kernel 1: lanes 64 .. NT-1 (behind the top chain wavefront), vertex (t - 64) + r * NA0
+    constexpr int NA0 = NT - A0, RA = 3;                  //   (behind the first TWO wavefronts, four rounds: C2 +0.6 %, C1 +1 %, notes/r8_experiments.md)
+    static_assert(RA * NA0 >= lean_max_v(NT), "three rounds cover the plan's largest lattice");
     constexpr int NB = NT - 64, RB = 3;                   // passes 1, 2 of kernel 1: lanes 0 .. NT-65, vertex t + r * NB
     auto load_nbr_ovl = [&](unsigned (&wa)[RA], unsigned (&wb)[2][RB]) {
 #pragma unroll
         for (int r = 0; r < RA; ++r) {
             wa[r] = 0;
             if ((r == 0 || r * NA0 < V[K - 1]) && !LEAN_SKIP(512))
-                wa[r] = __builtin_amdgcn_raw_buffer_load_b32(src.nbr[K - 1], (t - 128 + r * NA0) * 4, src.off_nbr[K - 1], 0);      // (lanes < 128: out of range reads 0, unused)
+                wa[r] = __builtin_amdgcn_raw_buffer_load_b32(src.nbr[K - 1], (t - A0 + r * NA0) * 4, src.off_nbr[K - 1], 0);      // (lanes < A0: out of range reads 0, unused)
         }
 #pragma unroll
         for (int j = 1; j < D1; ++j) {
@@ -844,7 +871,7 @@ __device__ __forceinline__ void mean_field_lean(unsigned char *smem, const Fused
         }
         if constexpr (OVL) {
             // ---- d+1 Jacobi blur passes, permutohedral_cpu.h:663-679 (D1 = 3), dealt to the wavefronts as described above -----------
-            if (t >= 128) blur_big(0, t - 128, NA0, RA, wa);
+            if (t >= A0) blur_big(0, t - A0, NA0, RA, wa);
             __syncthreads();
             FL_STAMP();
             LEAN_FRESH_T();
