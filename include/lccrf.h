@@ -638,6 +638,18 @@ int  lccrf_batch_get_fused_shape(lccrf_batch_handle b, int *lanes_per_frame, int
  * (LCCRF_OPT_VERTEX_ORDER) or, 0, by the hash table: also what an engine falls back to for good when a frame's vertex codes overflow
  * 62 bits or a feature is wide enough to wrap the reference's int16 keys.  Either pointer may be NULL.                           */
 int  lccrf_batch_get_locality_mode(lccrf_batch_handle b, int *internal_point_order, int *sorted_build);
+/* Report only: how the two-label mean-field step splats term `kernel` for the lattices now in HBM and the frames now bound (after
+ * lccrf_batch_build; on a handle, after lccrf_inference or whatever else built its lattices).  With the sorted build the splat takes
+ * the first blur passes along: `passes` of them (0: none), and from two passes on it works on an overlapped window of `window`
+ * vertices in LDS (256, 512 or 1024) of which `halo` on either side are recomputed by the neighbouring workgroups, launched as
+ * workgroups of `lanes` lanes with `vertices_per_lane` vertices each (window = lanes * vertices_per_lane; all three 0 without a
+ * window).  long_mode: 0, or 1 / 2 for a coarse kernel, whose long rows get the row-walking splat and no pass.  Same results in
+ * every plan.                                                                                                                    */
+typedef struct lccrf_splat_plan {
+    int32_t passes, halo, window, lanes, vertices_per_lane, long_mode;
+} lccrf_splat_plan;
+int  lccrf_batch_get_splat_plan(lccrf_batch_handle b, int kernel, lccrf_splat_plan *out);
+int  lccrf_get_splat_plan(lccrf_handle h, int kernel, lccrf_splat_plan *out);
 
 /* Measurement support for bench.py: HIP-event time of the last lccrf_batch_inference()
  * on its stream, the number of launches of the dominant kernel and their summed

@@ -50,6 +50,14 @@ class CrfParams(C.Structure):
         "point3d_stdev", "point2d_stdev", "u_depth", "pth", "confidence")]
 
 
+class SplatPlan(C.Structure):
+    """lccrf_splat_plan"""
+    _fields_ = [(n, C.c_int32) for n in ("passes", "halo", "window", "lanes", "vertices_per_lane", "long_mode")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class BatchDesc(C.Structure):
     _fields_ = [("max_frames", C.c_int), ("max_points", C.c_int), ("n_labels", C.c_int),
                 ("n_kernels", C.c_int), ("feat_dims", C.c_int * MAX_KERNELS),
@@ -156,6 +164,8 @@ def lib():
     L.lccrf_batch_get_fallback_frames.argtypes = [vp, C.POINTER(C.c_int)]
     L.lccrf_batch_get_fused_shape.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lccrf_batch_get_locality_mode.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.lccrf_batch_get_splat_plan.argtypes = [vp, C.c_int, C.POINTER(SplatPlan)]
+    L.lccrf_get_splat_plan.argtypes = [vp, C.c_int, C.POINTER(SplatPlan)]
     L.lccrf_batch_pose_set_crf_counts.argtypes = [vp, vp]
     L.lccrf_batch_last_timing.argtypes = [vp, _f32p, _f32p]
     L.lccrf_batch_last_prepare.argtypes = [vp, _f32p, C.POINTER(C.c_int)]
@@ -264,6 +274,13 @@ class DenseCRFHIP:
         a = _f32(xy)
         _check(lib().lccrf_add_smooth_kernel(self.h, float(w), _p(a, _f32p), float(sd2d)))
         self._d.append(2)
+
+    def splat_plan(self, k):
+        """How the two-label step splats term k for the lattices now in HBM (lccrf_splat_plan): dict(passes, halo, window, lanes,
+        vertices_per_lane, long_mode)."""
+        p = SplatPlan()
+        _check(lib().lccrf_get_splat_plan(self.h, int(k), C.byref(p)))
+        return p.as_dict()
 
     # -- inference ---------------------------------------------------------------------
     def start_inference(self):
@@ -660,6 +677,13 @@ class BatchCRF:
         a, b = C.c_int(0), C.c_int(0)
         _check(lib().lccrf_batch_get_locality_mode(self.h, C.byref(a), C.byref(b)))
         return bool(a.value), bool(b.value)
+
+    def splat_plan(self, k):
+        """How the two-label step splats term k for the lattices now in HBM (lccrf_splat_plan): dict(passes, halo, window, lanes,
+        vertices_per_lane, long_mode)."""
+        p = SplatPlan()
+        _check(lib().lccrf_batch_get_splat_plan(self.h, int(k), C.byref(p)))
+        return p.as_dict()
 
     def fallback_frames(self):
         """Frames of the last run() that did not fit the one-launch kernel and were re-run on the two-kernel path."""

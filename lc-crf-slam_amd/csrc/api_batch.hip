@@ -659,6 +659,20 @@ int lccrf_batch_get_locality_mode(lccrf_batch_handle b, int *internal_point_orde
     return LCCRF_OK;
 }
 
+int lccrf_batch_get_splat_plan(lccrf_batch_handle b, int kernel, lccrf_splat_plan *out)
+{
+    CHECK_H(b);
+    CHECK_K(b, kernel);
+    if (!out) return fail(LCCRF_E_INVALID, "out is NULL");
+    Engine &e = b->eng;
+    if (e.built) {                                      // (the plan is made from what the build measured: learn_sizes())
+        int rc = e.learn_sizes();
+        if (rc) return rc;
+    }
+    report_splat_plan(e.kernels[kernel].dev, e.crf.F, out);
+    return LCCRF_OK;
+}
+
 int lccrf_batch_get_stream(lccrf_batch_handle b, void **stream)
 {
     CHECK_H(b);

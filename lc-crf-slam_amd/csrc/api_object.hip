@@ -546,6 +546,18 @@ int lccrf_get_lattice_size(lccrf_handle h, int kernel, int *n_vertices)
     return LCCRF_OK;
 }
 
+int lccrf_get_splat_plan(lccrf_handle h, int kernel, lccrf_splat_plan *out)
+{
+    CHECK_H(h);
+    CHECK_K(h, kernel);
+    if (!out) return fail(LCCRF_E_INVALID, "out is NULL");
+    Engine &e = h->eng;
+    { int rl = e.resolve_late(); if (rl) return rl; }
+    { int rc = e.learn_sizes(); if (rc) return rc; }    // (builds a lattice that only exists as staged features, the plain way)
+    report_splat_plan(e.kernels[kernel].dev, e.crf.F, out);
+    return LCCRF_OK;
+}
+
 int lccrf_get_norm(lccrf_handle h, int kernel, float *norm_out)
 {
     CHECK_H(h);

@@ -143,6 +143,42 @@ struct CrfDev {
 // points per frame that sizes a launch: the largest frame when the host knows it, else the capacity
 inline int active_points(const CrfDev &c) { return c.activeN > 0 ? c.activeN : c.maxN; }
 
+// The two-label splat's plan for the lattices now in HBM (set by Engine::learn_sizes(), read by the launcher in stream_filter.hip and
+// by lccrf_get_splat_plan / lccrf_batch_get_splat_plan: one rule for both, so the report cannot drift from what is launched).
+// Blur passes the splat takes along: the window's (KernelDev::splat_passes), at least pass 0 with the sorted build; none for a coarse
+// kernel (long_mode) or a lattice of the hash build.
+inline int splat_passes_taken(const KernelDev &kd)
+{
+    static const bool no_sb = ab_env("LCCRF_NO_SPLAT_BLUR") != nullptr;               // A/B switch: same results either way
+    return (kd.vorder && kd.fast0_ok && !no_sb && !kd.long_mode) ? (kd.splat_passes > 1 ? kd.splat_passes : 1) : 0;
+}
+// the window splat: a lane per vertex up to this many frames in flight (two frames 25.3 / 24.5-25.1 / 25.0-26.4 us per frame-iteration
+// with the threshold at 1 / 2 / 3, three frames 20.6 / 20.7 / 21.1-21.5: notes/r4_experiments.md)
+constexpr int kSplatWideMaxFrames = 2;
+constexpr int kSplatNarrowLanes = 256;
+// ... and the instantiation k_splat2w<lanes, per_lane> of a window of 256 / 512 / 1024 vertices with F frames in flight; the grid is
+// counted in workgroups of `lanes`.  Many frames in flight: 256 lanes x 1 / 2 / 4 vertices (C5 x 8, window 1024: 20.6 -> 18.9 us per
+// frame-iteration against 1024 lanes x 1: workgroups of four wavefronts wait less at the barriers); one or two frames: one or two
+// vertices per lane (a lane's four row walks in a row cost a single frame 33.3 -> 36.1).  One frame, window 1024: 663 workgroups of
+// 1024 lanes are 1.3 rounds of the chip's 512 slots; 512 lanes x 2 vertices all run at once (33.6 -> 32.5 us).
+struct SplatShape { int lanes, per_lane; };
+inline SplatShape splat_window_shape(int window, int F)
+{
+    const int lanes = F > kSplatWideMaxFrames ? kSplatNarrowLanes : (window == 1024 && F == 1) ? 512 : window;
+    return SplatShape{lanes, window / lanes};
+}
+inline void report_splat_plan(const KernelDev &kd, int F, lccrf_splat_plan *out)
+{
+    const int j0 = splat_passes_taken(kd);
+    *out = lccrf_splat_plan{j0, j0 >= 2 ? kd.splat_halo : j0, 0, 0, 0, kd.long_mode};      // (pass 0 alone: one vertex either side)
+    if (j0 >= 2) {
+        const SplatShape sh = splat_window_shape(kd.splat_block, F);
+        out->window = kd.splat_block;
+        out->lanes = sh.lanes;
+        out->vertices_per_lane = sh.per_lane;
+    }
+}
+
 // scratch of the point sort (locality mode), owned by the engine
 struct SortScratch {
     int bits;             // bucket bits of the counting sort (8..16)

@@ -597,9 +597,6 @@ __global__ void __launch_bounds__(kBlock) k_blur2x2t(KernelDev kd, const float *
 }
 
 constexpr int kSliceBlurMaxFrames = 1;       // the last blur pass inside the slice (k_slice2<D1, true>) when passes go one per launch, up to this many frames in flight (with the sorted build: two frames +2 % without it, four and eight +-0)
-// the window splat: a lane per vertex up to this many frames in flight (two frames 25.3 / 24.5-25.1 / 25.0-26.4 us per frame-iteration
-// with the threshold at 1 / 2 / 3, three frames 20.6 / 20.7 / 21.1-21.5: notes/r4_experiments.md)
-constexpr int kSplatWideMaxFrames = 2;
 constexpr int kPairFuseMaxFrames = 1;        // (measured: one C5 frame 52.5 -> 45.2 us per iteration; two or four frames in flight: +-0)
 // ... or, whatever the number of frames, when the launch is SMALL: up to ~0.7 M vertices over all frames (one C5 frame: 0.59 M; two: +-0)
 // the passes are launch- and latency-bound, e.g. 8 frames of 5000 points (30 000 vertices each): 9 launches of ~3.8 us per iteration
@@ -714,28 +711,21 @@ int splat2_term(const CrfDev &c, const KernelDev &kd, int maxV, hipStream_t s)
     XcdMap nb;
     const int blk = iter_block(c.F);
     // sorted build, one pass per launch: the first pass (axis 0 = the code's fastest coordinate) rides in the splat
-    static const bool no_sb = ab_env("LCCRF_NO_SPLAT_BLUR") != nullptr;               // A/B switch: same results either way
-    const int j0 = (kd.vorder && kd.fast0_ok && !no_sb && !kd.long_mode) ? std::max(kd.splat_passes, 1) : 0;   // passes the splat takes along
+    const int j0 = splat_passes_taken(kd);
     if (j0 >= 2) {
         const int B = kd.splat_block, core = B - 2 * kd.splat_halo;
         const float2 *q2 = reinterpret_cast<const float2 *>(c.Q);
-        // many frames in flight: 256 lanes x 1 / 2 / 4 vertices (C5 x 8, window 1024: 20.6 -> 18.9 us per frame-iteration against
-        // 1024 lanes x 1: workgroups of four wavefronts wait less at the barriers); one or two frames: one or two vertices per lane
-        // (a lane's four row walks in a row cost a single frame 33.3 -> 36.1)
-        const bool wide = c.F <= kSplatWideMaxFrames;
-        const int lanes = wide ? B : kBlock;
-        const dim3 g = grid_xcd(((long)maxV + core - 1) / core * lanes, c.F, &nb, lanes);
+        const SplatShape sh = splat_window_shape(B, c.F);                             // (engine.h: which instantiation and why)
+        const dim3 g = grid_xcd(((long)maxV + core - 1) / core * sh.lanes, c.F, &nb, sh.lanes);
         // (one 16-byte record per vertex in place of seven loads, and 512 lanes x 2 vertices with many frames in flight: both
         // +-noise, notes/r5_experiments.md section 3)
-        if (B == 256) k_splat2w<256, 1><<<g, 256, 0, s>>>(kd, q2, c.maxN, c.F, nb, j0, kd.splat_halo);
-        else if (B == 512 && wide) k_splat2w<512, 1><<<g, 512, 0, s>>>(kd, q2, c.maxN, c.F, nb, j0, kd.splat_halo);
-        else if (B == 512) k_splat2w<256, 2><<<g, 256, 0, s>>>(kd, q2, c.maxN, c.F, nb, j0, kd.splat_halo);
-        else if (c.F == 1) {                      // (one frame: 663 workgroups of 1024 lanes are 1.3 rounds of the chip's 512 slots;
-            const dim3 g5 = grid_xcd(((long)maxV + core - 1) / core * 512, c.F, &nb, 512);    //  512 lanes x 2 vertices all run at once: 33.6 -> 32.5 us)
-            k_splat2w<512, 2><<<g5, 512, 0, s>>>(kd, q2, c.maxN, c.F, nb, j0, kd.splat_halo);
-        }
-        else if (wide) k_splat2w<1024, 1><<<g, 1024, 0, s>>>(kd, q2, c.maxN, c.F, nb, j0, kd.splat_halo);
-        else k_splat2w<256, 4><<<g, 256, 0, s>>>(kd, q2, c.maxN, c.F, nb, j0, kd.splat_halo);
+        const int halo = kd.splat_halo;
+        if (sh.lanes == 256 && sh.per_lane == 1) k_splat2w<256, 1><<<g, 256, 0, s>>>(kd, q2, c.maxN, c.F, nb, j0, halo);
+        else if (sh.lanes == 512 && sh.per_lane == 1) k_splat2w<512, 1><<<g, 512, 0, s>>>(kd, q2, c.maxN, c.F, nb, j0, halo);
+        else if (sh.lanes == 256 && sh.per_lane == 2) k_splat2w<256, 2><<<g, 256, 0, s>>>(kd, q2, c.maxN, c.F, nb, j0, halo);
+        else if (sh.lanes == 512 && sh.per_lane == 2) k_splat2w<512, 2><<<g, 512, 0, s>>>(kd, q2, c.maxN, c.F, nb, j0, halo);
+        else if (sh.lanes == 1024 && sh.per_lane == 1) k_splat2w<1024, 1><<<g, 1024, 0, s>>>(kd, q2, c.maxN, c.F, nb, j0, halo);
+        else k_splat2w<256, 4><<<g, 256, 0, s>>>(kd, q2, c.maxN, c.F, nb, j0, halo);
     } else if (j0 == 1) {
         const dim3 g = grid_xcd(((long)maxV + blk - 3) / (blk - 2) * blk, c.F, &nb, blk);
         k_splat2<true><<<g, blk, 0, s>>>(kd, reinterpret_cast<const float2 *>(c.Q), c.maxN, c.F, nb);
