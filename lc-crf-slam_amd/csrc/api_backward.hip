@@ -45,7 +45,7 @@ static int backward_call(const BackwardTarget &t, const BackwardRequest &rq, boo
         int rr = e.resolve_late();
         if (rr) return rr;
         if ((rr = e.ensure_backward_area(e.backward_need(rq, t.slice, t.rows)))) return rr;   // (a handle's phantom rows stay zero: engine.h)
-        if (t.batch && (rr = e.ensure_plain_batch())) return rr;
+        if (t.batch && (rr = e.make_ready(Engine::kCallerOrder | Engine::kSized))) return rr;
         return e.backward(rq, t.slice, t.rows);
     };
     return t.batch ? timed_batch_call(e, t.stream, e.ev[2], e.ev[3], e.timed_inf, run) : run();

@@ -458,7 +458,7 @@ int lccrf_batch_build(lccrf_batch_handle b, void *stream)
         return rb;
     });
     e.built = !rc;
-    return rc;                                        // (learn_sizes() waits on the own stream, which ~StreamScope orders behind this one)
+    return rc;                                        // (kSized waits on the own stream, which ~StreamScope orders behind this one)
 }
 
 int lccrf_batch_inference(lccrf_batch_handle b, int n_iterations, int with_map, float relax, void *stream)
@@ -466,7 +466,7 @@ int lccrf_batch_inference(lccrf_batch_handle b, int n_iterations, int with_map, 
     CHECK_H(b);
     Engine &e = b->eng;
     if (!e.built) return fail(LCCRF_E_STATE, "lccrf_batch_build has not run for these inputs");
-    int rc = e.learn_sizes();
+    int rc = e.make_ready(Engine::kSized);
     if (rc) return rc;
     return timed_batch_call(e, stream, e.ev[2], e.ev[3], e.timed_inf, [&] { return e.inference(n_iterations, with_map, relax); });
 }
@@ -480,7 +480,7 @@ int lccrf_batch_inference_converged(lccrf_batch_handle b, int max_iterations, in
     CHECK_H(b);
     Engine &e = b->eng;
     if (!e.built) return fail(LCCRF_E_STATE, "lccrf_batch_build has not run for these inputs");
-    int rc = e.learn_sizes();
+    int rc = e.make_ready(Engine::kSized);
     if (rc) return rc;
     return timed_batch_call(e, stream, e.ev[2], e.ev[3], e.timed_inf,
                             [&] { return e.inference_converged(max_iterations, criterion, tol, with_map, relax); });
@@ -580,8 +580,7 @@ int lccrf_batch_get_norm_host(lccrf_batch_handle b, int kernel, float *norm_out)
     CHECK_K(b, kernel);
     if (!norm_out) return fail(LCCRF_E_INVALID, "norm_out is NULL");
     Engine &e = b->eng;
-    { int rl = b->eng.resolve_late(); if (rl) return rl; }
-    { int rf = b->eng.flush_builds(); if (rf) return rf; }   // lccrf_batch_run builds nothing in HBM
+    { int rc = e.make_ready(Engine::kSettled | Engine::kBuilt); if (rc) return rc; }   // lccrf_batch_run builds nothing in HBM
     const float *src = e.kernels[kernel].dev.norm;
     if (e.perm_on) {                                  // the lattice's point arrays are in the internal order: undo it for the caller
         int rc = e.need_io();
@@ -628,7 +627,7 @@ int lccrf_batch_get_engine(lccrf_batch_handle b, int *engine_in_use)
     { int rl = b->eng.resolve_late(); if (rl) return rl; }   // a one-launch run may have fallen back
     Engine &e = b->eng;
     if (e.built && e.engine_used != 3) {                     // lattices in HBM: what an inference on them runs (or ran) on
-        int rc = e.learn_sizes();
+        int rc = e.make_ready(Engine::kSized);
         if (rc) return rc;
         e.engine_used = e.sized_engine;
     }
@@ -651,7 +650,7 @@ int lccrf_batch_get_locality_mode(lccrf_batch_handle b, int *internal_point_orde
     CHECK_H(b);
     Engine &e = b->eng;
     if (e.built) {                                      // (a build that met an overflowing / wrapping frame is redone with the hash here)
-        int rc = e.learn_sizes();
+        int rc = e.make_ready(Engine::kSized);
         if (rc) return rc;
     }
     if (internal_point_order) *internal_point_order = e.perm_on ? 1 : 0;
@@ -665,8 +664,8 @@ int lccrf_batch_get_splat_plan(lccrf_batch_handle b, int kernel, lccrf_splat_pla
     CHECK_K(b, kernel);
     if (!out) return fail(LCCRF_E_INVALID, "out is NULL");
     Engine &e = b->eng;
-    if (e.built) {                                      // (the plan is made from what the build measured: learn_sizes())
-        int rc = e.learn_sizes();
+    if (e.built) {                                      // (the plan is made from what the build measured: kSized)
+        int rc = e.make_ready(Engine::kSized);
         if (rc) return rc;
     }
     report_splat_plan(e.kernels[kernel].dev, e.crf.F, out);
@@ -721,7 +720,7 @@ int lccrf_batch_time_blur_pass(lccrf_batch_handle b, int kernel, int reps, float
     if (reps < 1 || !ms_per_launch) return fail(LCCRF_E_INVALID, "reps < 1 or NULL output");
     Engine &e = b->eng;
     if (!e.built) return fail(LCCRF_E_STATE, "lccrf_batch_build has not run for these inputs");
-    int rc = e.learn_sizes();
+    int rc = e.make_ready(Engine::kSized);
     if (rc) return rc;
     if (vertices_per_launch) {
         int64_t tot = 0;

@@ -58,7 +58,7 @@ struct lccrf_batch {
     do {                                                              \
         if (!(h)) return fail(LCCRF_E_INVALID, "handle is NULL");     \
         HIP_TRY(hipSetDevice((h)->eng.device));                       \
-        (h)->eng.idle_by_done = (h)->eng.idle_needs_done = false;     \
+        (h)->eng.touched();                                           \
     } while (0)
 
 #define CHECK_K(h, k)                                                                      \

@@ -6,8 +6,6 @@
 
 #include <cmath>
 #include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <cstring>
 #include <mutex>
 #include <new>
@@ -333,7 +331,7 @@ int lccrf_get_convergence(lccrf_handle h, int *iterations, float *delta, int *ch
 int lccrf_get_engine(lccrf_handle h, int *engine, int *shape)
 {
     if (!h || !engine) return fail(LCCRF_E_INVALID, "handle / engine is NULL");
-    if (h->eng.late_pending) {                          // (a frame that did not fit the one-launch kernel reports what it was re-run on)
+    if (h->eng.run_pending()) {                         // (a frame that did not fit the one-launch kernel reports what it was re-run on)
         CHECK_H(h);
         int rl = h->eng.resolve_late();
         if (rl) return rl;
@@ -348,33 +346,7 @@ int lccrf_get_map(lccrf_handle h, int16_t *map_out)
     CHECK_H(h);
     if (!map_out && h->N) return fail(LCCRF_E_INVALID, "map_out is NULL");
     Engine &e = h->eng;
-    if (e.late_pending && e.labels_armed) {             // one frame in flight, its labels go straight into map_pin: take them as they land
-        e.labels_armed = false;
-        const volatile int16_t *m = h->map_pin;
-        const auto t0 = std::chrono::steady_clock::now();
-        bool ok = true, timed_out = false;
-        unsigned spins = 0;
-        for (int i = 0; i < h->N && ok; ++i) {
-            int16_t v;
-            while ((v = m[i]) == (int16_t)-1) {           // (bounded: whatever goes wrong is left to the ordinary path below)
-                if ((++spins & 0x3ff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) { ok = false; timed_out = true; break; }
-                cpu_relax();
-            }
-            if (v < 0) ok = false;                        // -2: the frame did not fit the one-launch kernel
-        }
-        if (ok) {
-            std::atomic_thread_fence(std::memory_order_acquire);
-            memcpy(map_out, h->map_pin, (size_t)h->N * sizeof(int16_t));
-            e.late_pending = false;                       // every label is there: the frame fitted and the kernel is past its last read
-            e.done_armed = false;
-            // ... but not formally finished: V_out, frame_status and the done word are stored behind the labels (and a helper
-            // workgroup may be in its epilogue).  The handle counts as idle only once recycle() has seen the done word.
-            e.idle_by_done = true;
-            e.idle_needs_done = true;
-            return LCCRF_OK;
-        }
-        if (timed_out) e.done_armed = false;              // (a delayed frame: do not spin another 2 ms on the done word, wait on the stream)
-    }
+    if (e.take_labels(map_out, h->N)) return LCCRF_OK;   // one frame in flight, its labels go straight into map_pin: taken as they land
     bool seen_done = false;
     { int rl = e.resolve_late(&seen_done); if (rl) return rl; }
     if (e.crf.map != h->map_pin) {                        // device labels (lccrf_device_buffers): a copy through the pinned array
@@ -383,7 +355,7 @@ int lccrf_get_map(lccrf_handle h, int16_t *map_out)
     }
     if (!seen_done) HIP_TRY(hipStreamSynchronize(e.stream));
     if (h->N) memcpy(map_out, h->map_pin, (size_t)h->N * sizeof(int16_t));   // written there by the kernels
-    e.idle_by_done = seen_done;
+    if (seen_done) e.done_seen();
     return LCCRF_OK;
 }
 
@@ -410,10 +382,7 @@ int lccrf_get_probability(lccrf_handle h, float *prob_out)
 static int pairwise_apply_on(lccrf_crf *h, int kernel, float *d_out, const float *d_in, int accumulate)
 {
     Engine &e = h->eng;
-    int rc = e.resolve_late();
-    if (!rc) rc = e.ensure_plain();
-    if (!rc) rc = e.learn_sizes();                        // builds the lattice if it only exists as staged features
-    if (!rc) rc = e.ensure_factors();
+    const int rc = e.make_ready(Engine::kSettled | Engine::kCallerOrder | Engine::kSized | Engine::kStepViews);   // (builds staged lattices)
     if (rc || !h->N) return rc;
     launch_filter(e.step_kdevs()[kernel], e.crf, e.maxV[kernel], d_in, d_out, accumulate, e.stream, 0, nullptr, e.compat_ptr[kernel],
                   e.n_modes ? e.pre_ptr[kernel] : nullptr);
@@ -434,9 +403,7 @@ static int step_init_on(lccrf_crf *h, float *d_next)
 {
     Engine &e = h->eng;
     if (!e.unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
-    int rc = e.resolve_late();
-    if (!rc) rc = e.ensure_plain();
-    if (!rc) rc = e.ensure_unary();
+    const int rc = e.make_ready(Engine::kSettled | Engine::kCallerOrder | Engine::kUnaries);
     if (rc || !h->N) return rc;
     launch_step_init(e.crf, d_next, e.stream);
     HIP_TRY(hipGetLastError());
@@ -540,7 +507,7 @@ int lccrf_get_lattice_size(lccrf_handle h, int kernel, int *n_vertices)
     CHECK_H(h);
     CHECK_K(h, kernel);
     if (!n_vertices) return fail(LCCRF_E_INVALID, "n_vertices is NULL");
-    { int rcf = h->eng.flush_builds(); if (rcf) return rcf; }
+    { int rcf = h->eng.make_ready(Engine::kBuilt); if (rcf) return rcf; }
     HIP_TRY(hipStreamSynchronize(h->eng.stream));
     *n_vertices = h->eng.V_host[(size_t)kernel * h->eng.Fcap];
     return LCCRF_OK;
@@ -552,8 +519,7 @@ int lccrf_get_splat_plan(lccrf_handle h, int kernel, lccrf_splat_plan *out)
     CHECK_K(h, kernel);
     if (!out) return fail(LCCRF_E_INVALID, "out is NULL");
     Engine &e = h->eng;
-    { int rl = e.resolve_late(); if (rl) return rl; }
-    { int rc = e.learn_sizes(); if (rc) return rc; }    // (builds a lattice that only exists as staged features, the plain way)
+    { int rc = e.make_ready(Engine::kSettled | Engine::kSized); if (rc) return rc; }   // (builds staged lattices, the plain way)
     report_splat_plan(e.kernels[kernel].dev, e.crf.F, out);
     return LCCRF_OK;
 }
@@ -563,8 +529,7 @@ int lccrf_get_norm(lccrf_handle h, int kernel, float *norm_out)
     CHECK_H(h);
     CHECK_K(h, kernel);
     if (!norm_out && h->N) return fail(LCCRF_E_INVALID, "norm_out is NULL");
-    { int rp = h->eng.ensure_plain(); if (rp) return rp; }
-    { int rcf = h->eng.flush_builds(); if (rcf) return rcf; }
+    { int rc = h->eng.make_ready(Engine::kCallerOrder | Engine::kBuilt); if (rc) return rc; }
     HIP_TRY(hipStreamSynchronize(h->eng.stream));
     if (h->N) HIP_TRY(hipMemcpy(norm_out, h->eng.kernels[kernel].dev.norm, (size_t)h->N * sizeof(float), hipMemcpyDeviceToHost));
     return LCCRF_OK;
@@ -575,8 +540,7 @@ int lccrf_get_lattice(lccrf_handle h, int kernel, int32_t *offset_out, float *ba
     CHECK_H(h);
     CHECK_K(h, kernel);
     Engine &e = h->eng;
-    { int rp = e.ensure_plain(); if (rp) return rp; }
-    { int rcf = e.flush_builds(); if (rcf) return rcf; }
+    { int rc = e.make_ready(Engine::kCallerOrder | Engine::kBuilt); if (rc) return rc; }
     HIP_TRY(hipStreamSynchronize(e.stream));
     const KernelDev &k = e.kernels[kernel].dev;
     const size_t ne = (size_t)h->N * k.D1;
@@ -595,9 +559,8 @@ int lccrf_get_unary(lccrf_handle h, float *unary_out)
 {
     CHECK_H(h);
     if (!unary_out && h->N) return fail(LCCRF_E_INVALID, "unary_out is NULL");
-    { int rl = h->eng.resolve_late(); if (rl) return rl; }
-    { int rp = h->eng.ensure_plain(); if (rp) return rp; }           // (energies derived from labels live in the lattices' point order)
-    { int ru = h->eng.ensure_unary(); if (ru) return ru; }
+    // (kCallerOrder: energies derived from labels live in the lattices' point order)
+    { int rc = h->eng.make_ready(Engine::kSettled | Engine::kCallerOrder | Engine::kUnaries); if (rc) return rc; }
     return copy_out_f32(h, h->eng.crf.unary, unary_out, (size_t)h->N * h->eng.L);
 }
 

@@ -2,7 +2,8 @@
 //
 // Host code only (no kernel): device memory, lattice builds, locality mode, engine choice, the late-bound one-launch run with its
 // per-frame fallback, the done-word protocol, the backward area, the compatibility matrices and the normalisation modes.  The bodies are in
-// host_engine.hip; the entry points of include/lccrf.h (api_*.hip) read and write the fields below directly.
+// host_engine.hip; the entry points of include/lccrf.h (api_*.hip) read and write the fields below directly -- all but the two things
+// that are the engine's own: what a call relies on is brought up to date by make_ready() alone, what is in flight is `flight`.
 #pragma once
 
 #include "engine.h"
@@ -140,7 +141,6 @@ struct Engine {
     // the lattice sizes; `late_status` (pinned) tells afterwards whether the frame fitted.
     int *late_status = nullptr;
     bool late_ok = false;              // set by the object API: single frame, automatic engine choice
-    bool late_pending = false;
     int late_iter = 0, late_map = 0;
     float late_relax = 1.0f;
     // Called by resolve_late() right behind a re-run of flagged frames (before its final synchronisation): the owner of host-side
@@ -155,14 +155,26 @@ struct Engine {
     // polls it instead of waiting for the runtime's completion signal (which arrives a few microseconds later)
     unsigned *done_word = nullptr;
     unsigned done_epoch = 0;
-    bool done_armed = false;
     // ... and with_map launches of the object API do not even wait for that word: the host pre-fills the pinned label array
     // with -1 and takes each label as it arrives (the kernel's last stores; no fence, no acknowledgement round trip)
     int16_t *map_host = nullptr;       // the handle's pinned label array (= crf.map), or null
-    bool labels_armed = false;
-    bool idle_by_done = false;         // the last call on the handle was a getMap() that saw the done word: nothing is in flight
-    bool idle_needs_done = false;      //   ... or every label (the stores right before the done word): the word itself is still to come
-    bool park_check = false;           // parked with that word still unseen: ensure_parked_idle() settles it for the next user
+    // What is in flight on the stream, as far as the host knows: moved by run_frame() (arm), take_labels(), resolve_late() (settle),
+    // done_seen(), touched(), recycle() (park) and ensure_parked_idle(), and by nothing else.
+    enum class Flight {
+        kUnknown,          // nothing known to be in flight, nothing known to have ended: whoever must know waits for the stream
+        kPending,          // a one-launch run: settled by a stream synchronisation,
+        kPendingDone,      //   ... by its done word,
+        kPendingLabels,    //   ... or label by label (take_labels), the done word behind them
+        kLabelsSeen,       // the last call on the handle was a getMap() that saw every label (the stores right before the done word,
+                           //   which is still to come): the run has fitted and is past its last read
+        kDoneSeen,         // ... or that saw the done word: nothing is in flight
+        kParkedDoneDue,    // parked from kLabelsSeen, the word still unseen: ensure_parked_idle() settles it for the next user
+    } flight = Flight::kUnknown;
+    bool run_pending() const { return flight == Flight::kPending || flight == Flight::kPendingDone || flight == Flight::kPendingLabels; }
+    // another call has touched the handle: whatever the last getMap() saw says nothing about what that call enqueues
+    void touched() { if (flight == Flight::kLabelsSeen || flight == Flight::kDoneSeen) flight = Flight::kUnknown; }
+    void done_seen() { flight = Flight::kDoneSeen; }   // (getMap(): resolve_late() saw the done word and nothing was enqueued since)
+    bool take_labels(int16_t *out, int n);
 
     // ---- per-frame fallback ----
     // Per-frame fallback of the one-launch kernel: k_frame leaves 1 in frame_status[f] for a frame whose lattices do not
@@ -187,8 +199,8 @@ struct Engine {
     // the unaries of the iteration live in that order (Qp, unary_p / unary_own) and Q is un-permuted on the way out.
     static constexpr int kPermMinPointsDefault = 8192;
     bool allow_perm = false;           // set by lccrf_batch_create, and by lccrf_create for handles of >= kPermMinPoints points ...
-    bool perm_scoped = false;          // ... where it only applies to lattices that are first asked for by inference() (perm_scope): every
-    bool perm_scope = false;           //   other entry point of the object API (stepwise inference, PairwisePotential::apply, the lattice
+    bool perm_scoped = false;          // ... where it only applies to lattices that are first asked for by inference() (kMayReorder): every
+                                       //   other entry point of the object API (stepwise inference, PairwisePotential::apply, the lattice
     bool perm_banned = false;          //   probes) works on the caller's point order -- such a handle is built, or re-built once, the plain way
     bool perm_on = false;              // the lattices now in HBM were built in locality mode
     bool unary_p_valid = false;        // unary_p holds the raw unaries in the current internal order
@@ -223,7 +235,7 @@ struct Engine {
     // default), before it, half on either side, or not at all.  While n_modes > 0 the one-launch frame kernel and the fused engine
     // are not taken and the streaming engine's general branch -- or the fused engine's general kernel -- runs on kdevs_post, the
     // copy of kdevs whose `norm` points at each term's factor BEHIND the filter, with pre_ptr[k] the factor of its input
-    // (ensure_factors(), behind learn_sizes()).
+    // (kStepViews, behind kSized).
     int norm_mode[LCCRF_MAX_KERNELS] = {};   // lccrf_normalization of every term
     int n_modes = 0;                   // terms that are not LCCRF_NORMALIZE_AFTER
     float *ones = nullptr;             // [Fcap][maxN] of 1.0f: the factor behind the filter of a BEFORE or NONE term (lazy)
@@ -269,17 +281,25 @@ struct Engine {
 
     static int perm_min_points();
     int ensure_sort_scratch();
-    int build_kernels(int k0, int n);
-    int build_kernel(int k) { return build_kernels(k, 1); }
-    int flush_builds();
-    int learn_sizes();
-    int ensure_plain();
-    int ensure_plain_batch();
+    int build_kernels(int k0, int n, bool may_reorder = false);
+
+    // What a caller is about to rely on.  make_ready() satisfies the needs asked for in the order of the bits: a step may undo what a
+    // later one provides (a re-build leaves label-derived unaries and the step views stale), never what an earlier one did.
+    enum Need : unsigned {
+        kSettled = 1,        // a pending one-launch run has finished, its flagged frames re-run (resolve_late)
+        kCallerOrder = 2,    // no lattice in locality mode's internal point order (re-built the plain way if one is): for good on a
+                             //   handle of large frames; on a batch for this call only, the next build decides afresh
+        kBuilt = 4,          // every term has its lattice in HBM (the object API only stages features)
+        kSized = 8,          // ... and the host knows their sizes: implies kBuilt and a stream synchronisation
+        kUnaries = 16,       // label-derived unaries are written, in the lattices' point order
+        kStepViews = 32,     // step_kdevs() / pre_arg() are valid (section 1g's factors)
+        kMayReorder = 64,    // modifier: lattices built by this call may use locality mode (inference() on a handle of large frames)
+    };
+    int make_ready(unsigned needs);
 
     UnaryTable label_table(const float *conf) const;
     void defer_unary_from_label(const int16_t *label, const float *conf);
     void bind_unary(const float *p);
-    int ensure_unary();
 
     int start();
     int step(float relax);
@@ -287,7 +307,7 @@ struct Engine {
     int run_frame(int n_iter, int with_map, float relax);
     int inference(int n_iter, int with_map, float relax);
     int run(int n_iter, int with_map, float relax);
-    int inference_sized(int n_iter, int with_map, float relax);
+    int inference_sized(int n_iter, int with_map, float relax, unsigned more_needs = 0);   // (more_needs: 0 or kMayReorder)
     static int check_converged_args(int max_iter, int criterion, float tol, float relax);
     int inference_converged(int max_iter, int criterion, float tol, int with_map, float relax);
     int converge_stream(int max_iter, int criterion, float tol, int with_map, float relax);
@@ -304,12 +324,11 @@ struct Engine {
         const bool general = n_compat || n_modes;
         sized_engine = !fused_fits ? 1 : !general ? 2 : (F == 1 && active_points(crf) <= kGeneralMaxPoints) ? 4 : 1;
     }
-    // what the streaming step, the plug-in filter and the backward sweep are handed (valid behind ensure_factors())
+    // what the streaming step, the plug-in filter and the backward sweep are handed (valid behind kStepViews)
     const KernelDev *step_kdevs() const { return n_modes ? kdevs_post.data() : kdevs.data(); }
     const float *const *pre_arg() const { return n_modes ? pre_ptr : nullptr; }
     void clear_norm_modes();
     void set_norm_mode(int k, int mode);
-    int ensure_factors();
     void clear_compat();
     int set_compat(int k, const float *m);
 
@@ -317,6 +336,15 @@ struct Engine {
     int ensure_backward_area(size_t need);
     size_t backward_need(const BackwardRequest &rq, size_t slice, int rows) const;
     int backward(const BackwardRequest &rq, size_t slice, int rows);
+
+private:
+    // the steps of make_ready(), and the view a streaming iteration runs on
+    int flush_builds(bool may_reorder = false);
+    int learn_sizes(bool may_reorder = false);
+    int ensure_unary();
+    int ensure_factors();
+    CrfDev begin_iteration();
+    void end_iteration(int with_map);
 };
 
 }  // namespace lccrf

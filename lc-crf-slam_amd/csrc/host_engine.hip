@@ -87,7 +87,7 @@ void Engine::set_norm_mode(int k, int mode)
     choose_sized_engine();
 }
 
-// Behind learn_sizes(), before anything reads step_kdevs() / pre_arg(): the factors the terms' modes need -- the square roots of a
+// Behind kSized, before anything reads step_kdevs() / pre_arg(): the factors the terms' modes need -- the square roots of a
 // SYMMETRIC term's norm, formed on the stream right behind the norm itself (in its point order, locality mode included) when a build
 // or a mode change has left them stale, and the array of ones -- and the views that point at them.
 int Engine::ensure_factors()
@@ -165,9 +165,8 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
     const size_t count = (size_t)F * rows * L;
     BackwardArea ar{};
     backward_layout(rq, crf, kdevs.data(), slice, rows, reinterpret_cast<float *>(bwd_area), &ar);
-    int rc = start();                                 // (ensure_plain: a handle's frames in locality mode are re-built the plain way once)
-    if (!rc) rc = learn_sizes();
-    if (!rc) rc = ensure_factors();
+    int rc = start();                                 // (kCallerOrder: a handle's frames in locality mode are re-built the plain way once)
+    if (!rc) rc = make_ready(kSized | kStepViews);
     if (rc) return rc;
     for (int t = 0; t < T; ++t) {
         if (count) HIP_TRY(hipMemcpyAsync(ar.hist + (size_t)t * slice, crf.Q, count * sizeof(float), hipMemcpyDeviceToDevice, stream));
@@ -304,7 +303,7 @@ int Engine::init(int device_id, int frames, int max_points, int n_labels)
 
 void Engine::destroy()
 {
-    park_check = false;
+    flight = Flight::kUnknown;
     if (stream) (void)hipStreamSynchronize(stream);
     free_backward_area();
     if (fb) {
@@ -430,8 +429,8 @@ int Engine::add_kernel(int d, float w, bool own_features, bool stage)
 // (the kernel's very last store); normally that happened long ago, otherwise wait for the stream the ordinary way.
 void Engine::ensure_parked_idle()
 {
-    if (!park_check) return;
-    park_check = false;
+    if (flight != Flight::kParkedDoneDue) return;
+    flight = Flight::kUnknown;
     if (!poll_done_word(done_word, done_epoch, std::chrono::microseconds(50), 64) && stream) (void)hipStreamSynchronize(stream);
 }
 
@@ -443,10 +442,9 @@ void Engine::recycle()
     // getMap() saw every label land: the kernel's last stores (V_out, frame_status, the done word) follow within a microsecond or
     // two.  Nobody waits for them here (the tracker's next frame is 33 ms away); the next user of this handle settles it before it
     // touches anything the kernel could still read or write (ensure_parked_idle, called by lccrf_create).
-    if (stream && idle_by_done && idle_needs_done) park_check = true;
-    else if (stream && !idle_by_done) (void)hipStreamSynchronize(stream);
-    idle_by_done = idle_needs_done = false;
-    labels_armed = done_armed = false;
+    const bool due = stream && flight == Flight::kLabelsSeen;
+    if (stream && !due && flight != Flight::kDoneSeen) (void)hipStreamSynchronize(stream);
+    flight = due ? Flight::kParkedDoneDue : Flight::kUnknown;
     free_backward_area();
     for (auto &ks : kernels) spare.push_back(ks);
     kernels.clear();
@@ -454,9 +452,8 @@ void Engine::recycle()
     crf.unary = unary_own;
     crf.n_points = npoints_own;
     forget_inputs();
-    late_pending = false;
     unary_deferred = false;
-    perm_on = vorder_on = perm_banned = perm_scope = false;      // (the next user's lattices decide afresh)
+    perm_on = vorder_on = perm_banned = false;        // (the next user's lattices decide afresh)
     unary_is_label = unary_p_valid = false;
     engine_pref = 0;
     engine_used = 1;
@@ -492,7 +489,7 @@ void Engine::sync_views()
 // Lattice + normalisation of kernels [k0, k0+n) for every frame (PottsPotential3D ctor).
 // SLAM-size frames take the fused build (one launch for all of them when they share d);
 // anything else the streaming build (19 launches per kernel).
-int Engine::build_kernels(int k0, int n)
+int Engine::build_kernels(int k0, int n, bool may_reorder)
 {
     for (int k = k0; k < k0 + n; ++k) {
         kernels[k].maxV = kernels[k].dev.Epad;
@@ -501,7 +498,7 @@ int Engine::build_kernels(int k0, int n)
     if (k0 == 0) {                                     // a build of every kernel decides the internal point order afresh
         static const bool no_perm = ab_env("LCCRF_NO_PERM") != nullptr;   // A/B and cross-check switch: same results either way
         const int NAp = active_points(crf);
-        const bool want = allow_perm && !no_perm && !perm_banned && (!perm_scoped || perm_scope) && n > 0 && n == (int)kernels.size() && NAp >= perm_min_points();
+        const bool want = allow_perm && !no_perm && !perm_banned && (!perm_scoped || may_reorder) && n > 0 && n == (int)kernels.size() && NAp >= perm_min_points();
         if (want || perm_on) {                         // whatever was derived in the old order is stale
             if (unary_is_label) unary_deferred = true;
             unary_p_valid = false;
@@ -567,18 +564,18 @@ int Engine::build_kernels(int k0, int n)
 
 // After the builds: learn max V per kernel so inference grids are sized to the lattice.
 // Build every kernel added since the last build (object API: add_pairwise only stages features).
-int Engine::flush_builds()
+int Engine::flush_builds(bool may_reorder)
 {
     const int n = (int)kernels.size();
     if (built_upto >= n) return LCCRF_OK;
     const int k0 = built_upto;
     built_upto = n;
-    return build_kernels(k0, n - k0);
+    return build_kernels(k0, n - k0, may_reorder);
 }
 
-int Engine::learn_sizes()
+int Engine::learn_sizes(bool may_reorder)
 {
-    int rc0 = flush_builds();
+    int rc0 = flush_builds(may_reorder);
     if (rc0) return rc0;
     if (sizes_known) return LCCRF_OK;
     HIP_TRY(hipStreamSynchronize(stream));
@@ -589,7 +586,7 @@ int Engine::learn_sizes()
     if (sort.vbad && *sort.vbad) {                     // a frame's vertices do not fit a 62-bit row-major code: hash build from now on
         *sort.vbad = 0;
         vorder_broken = true;
-        int rcb = build_kernels(0, (int)kernels.size());
+        int rcb = build_kernels(0, (int)kernels.size(), may_reorder);
         if (rcb) return rcb;
         HIP_TRY(hipStreamSynchronize(stream));
     }
@@ -702,9 +699,8 @@ int Engine::ensure_unary()
 int Engine::start()
 {
     if (!unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
-    { int rl = resolve_late(); if (rl) return rl; }
-    { int rp = ensure_plain(); if (rp) return rp; }   // (object API after a locality-mode inference(): label-derived energies sit in that order)
-    { int ru = ensure_unary(); if (ru) return ru; }
+    // (kCallerOrder: object API after a locality-mode inference(): label-derived energies sit in that order)
+    if (int rc = make_ready(kSettled | kCallerOrder | kUnaries)) return rc;
     launch_start(crf, stream);
     started = true;
     return LCCRF_OK;
@@ -713,13 +709,9 @@ int Engine::start()
 int Engine::step(float relax)
 {
     if (!started) return fail(LCCRF_E_STATE, "stepInference before startInference");
-    int rc = resolve_late();
+    // (kUnaries: label-derived energies follow the lattices' point order: re-derived after a re-build)
+    const int rc = make_ready(kSettled | kCallerOrder | kSized | kUnaries | kStepViews);
     if (rc) return rc;
-    if ((rc = ensure_plain())) return rc;
-    rc = learn_sizes();
-    if (rc) return rc;
-    if ((rc = ensure_unary())) return rc;             // (label-derived energies follow the lattices' point order: re-derived after a re-build)
-    if ((rc = ensure_factors())) return rc;
     launch_step_stream(crf, step_kdevs(), maxV.data(), relax, stream, compat_arg(), pre_arg());
     return LCCRF_OK;
 }
@@ -751,10 +743,10 @@ int Engine::run_frame(int n_iter, int with_map, float relax)
         if (++dual_epoch == 0) dual_epoch = 1;
     }
     static const bool no_done_word = ab_env("LCCRF_NO_DONE_WORD") != nullptr;   // A/B switch: wait on the stream instead
-    done_armed = late_ok && F == 1 && !no_done_word;
-    if (done_armed && ++done_epoch == 0) done_epoch = 1;
-    labels_armed = done_armed && with_map && L == 2 && map_host && map_host == crf.map && activeN > 0;
-    if (labels_armed) memset(map_host, 0xff, (size_t)activeN * sizeof(int16_t));
+    const bool by_word = late_ok && F == 1 && !no_done_word;
+    if (by_word && ++done_epoch == 0) done_epoch = 1;
+    const bool by_label = by_word && with_map && L == 2 && map_host && map_host == crf.map && activeN > 0;
+    if (by_label) memset(map_host, 0xff, (size_t)activeN * sizeof(int16_t));
     // full-size frames, two per CU (frame_lean.hip): the record area its loop re-reads is allocated when a batch first wants it
     // (sized for the frames BOUND, not for the handle's capacity -- 96 KB per frame: a handle created for 16384 frames that runs 1024 takes
     //  0.1 GB, not 1.6; a later, larger batch gets a new area, the old one stays with the handle until it is destroyed -- ADVICE r5)
@@ -773,7 +765,7 @@ int Engine::run_frame(int n_iter, int with_map, float relax)
     }
     const int shape = launch_frame(crf, kdevs.data(), n_iter, with_map, relax, late_status, frame_status,
                                    from_label ? deferred_label : nullptr, deferred_tbl.v, stream, frame_small_ok, dual, dual_epoch,
-                                   done_armed ? done_word : nullptr, done_epoch, frame_lean_ok ? lean_rec : nullptr);
+                                   by_word ? done_word : nullptr, done_epoch, frame_lean_ok ? lean_rec : nullptr);
     HIP_TRY(hipGetLastError());
     frame_small_used = shape == 1;
     frame_lean_used = shape == 2;
@@ -781,7 +773,7 @@ int Engine::run_frame(int n_iter, int with_map, float relax)
     engine_shape = 0;
     conv_engine = 0;
 
-    late_pending = true;
+    flight = by_label ? Flight::kPendingLabels : by_word ? Flight::kPendingDone : Flight::kPending;
     late_iter = n_iter;
     late_map = with_map;
     late_relax = relax;
@@ -801,31 +793,34 @@ int Engine::inference(int n_iter, int with_map, float relax)
     // Object API: nothing has been built yet (add_pairwise only stages features) -> do not build, run the
     // frame in one launch.  If a probe already forced the lattices into HBM, iterate on those instead.
     if (late_ok && frame_ok() && !(built_upto == (int)kernels.size() && sizes_known)) return run_frame(n_iter, with_map, relax);
-    perm_scope = true;                                // (large frames: lattices built from here may use locality mode)
-    rc = inference_sized(n_iter, with_map, relax);
-    perm_scope = false;
-    return rc;
+    return inference_sized(n_iter, with_map, relax, kMayReorder);   // (large frames: lattices built from here may use locality mode)
 }
 
-// Object API, large frames: DenseCRF::inference() runs in locality mode (internal point order, sorted build); the entry points
-// that expose or continue from per-point lattice state in the CALLER's order -- stepInference, PairwisePotential::apply, the
-// lattice / norm / unary probes -- get the plain build instead: built that way if they come first, re-built once if not.
-int Engine::ensure_plain()
+// The one place where an engine's lazily made state is brought up to date (host_engine.h: Need), in the order of the bits.
+// kCallerOrder -- object API, large frames: DenseCRF::inference() runs in locality mode (internal point order, sorted build); the entry
+// points that expose or continue from per-point lattice state in the CALLER's order -- stepInference, PairwisePotential::apply, the
+// lattice / norm / unary probes -- get the plain build instead: built that way if they come first (they never ask for kMayReorder),
+// re-built once, and the handle banned from locality mode, if not.  A batch's backward (lccrf_batch_inference_backward) wants the
+// same of every frame's lattices, but for this call only: whatever it builds is built under the ban, which is lifted again on the
+// way out -- the next lccrf_batch_build / _run decides the point order afresh.  "A batch" is read off !perm_scoped, which small handles
+// and the sub-engine `fb` share: harmless, as lccrf_create sets allow_perm and perm_scoped together, so nothing there is ever in
+// locality mode.  start() and step() on a batch find nothing to re-build: backward_call has made the batch plain before them.
+int Engine::make_ready(unsigned needs)
 {
-    if (!perm_on || !perm_scoped) return LCCRF_OK;
-    perm_banned = true;
-    invalidate_lattices();
-    return flush_builds();
-}
-
-// ... and the same for a batch's backward (lccrf_batch_inference_backward): every frame's lattices in HBM, built the plain way --
-// re-built if they are in locality mode.  For this call only: the next lccrf_batch_build / _run decides the point order afresh.
-int Engine::ensure_plain_batch()
-{
-    perm_banned = true;
-    if (perm_on) invalidate_lattices();
-    const int rc = learn_sizes();
-    perm_banned = false;
+    const bool call_ban = (needs & kCallerOrder) && !perm_scoped, reorder = (needs & kMayReorder) != 0;
+    int rc = (needs & kSettled) ? resolve_late() : LCCRF_OK;
+    if (!rc && (needs & kCallerOrder) && (perm_on || call_ban)) {
+        perm_banned = true;
+        if (perm_on) {
+            invalidate_lattices();
+            rc = flush_builds();
+        }
+    }
+    if (!rc && (needs & kSized)) rc = learn_sizes(reorder);   // (builds what is pending: the internal point order is known after this)
+    else if (!rc && (needs & kBuilt)) rc = flush_builds(reorder);
+    if (!rc && (needs & kUnaries)) rc = ensure_unary();
+    if (!rc && (needs & kStepViews)) rc = ensure_factors();
+    if (call_ban) perm_banned = false;
     return rc;
 }
 
@@ -841,33 +836,18 @@ int Engine::run(int n_iter, int with_map, float relax)
     return inference_sized(n_iter, with_map, relax);
 }
 
-int Engine::inference_sized(int n_iter, int with_map, float relax)
+int Engine::inference_sized(int n_iter, int with_map, float relax, unsigned more_needs)
 {
-    int rc = learn_sizes();                            // (builds what is pending: the internal point order is known after this)
+    const int rc = make_ready(kSized | kUnaries | kStepViews | more_needs);
     if (rc) return rc;
-    rc = ensure_unary();
-    if (rc) return rc;
-    if ((rc = ensure_factors())) return rc;
     engine_used = sized_engine;
     engine_shape = 0;
     last_with_map = with_map;
     conv_engine = 0;
-    if (perm_on) {
-        // locality mode: iterate on the internal-order view, un-permute Q on the way out (densecrf_base.h:65-73 otherwise)
-        CrfDev cp = crf;
-        cp.Q = Qp;
-        if (!unary_is_label) {
-            // a BOUND unary array ("bound, not copied") may have been updated in place since the last call: permute it
-            // afresh every time, as the other engines read it live; only the engine's own copy is cached (ADVICE r3)
-            if (!unary_p_valid || crf.unary != unary_own) launch_permute_rows(crf, unary_p, crf.unary, L, 1, stream);
-            unary_p_valid = true;
-            cp.unary = unary_p;
-        }
-        launch_start(cp, stream);
-        for (int it = 0; it < n_iter; ++it) launch_step_stream(cp, step_kdevs(), maxV.data(), relax, stream, compat_arg(), pre_arg());
-        launch_permute_rows(crf, crf.Q, Qp, L, 0, stream);
-        if (with_map) launch_map(crf, stream);
-        started = true;
+    if (perm_on || sized_engine == 1) {
+        const CrfDev v = begin_iteration();
+        for (int it = 0; it < n_iter; ++it) launch_step_stream(v, step_kdevs(), maxV.data(), relax, stream, compat_arg(), pre_arg());
+        end_iteration(with_map);
     } else if (sized_engine == 2) {
         // the two-frames-per-CU kernel runs from prepared launch records (fused_lean.h: LeanPrepPlan): one block per frame, owned
         // here, (re)written by the first inference behind a build -- learn_sizes() clears `valid` whenever a lattice has changed
@@ -900,13 +880,35 @@ int Engine::inference_sized(int n_iter, int with_map, float relax)
                                                 n_iter, with_map, relax, stream);
         if (!engine_shape) return fail(LCCRF_E_STATE, "the fused engine's general kernel was chosen for a frame it does not take");
         started = true;
-    } else {
-        if ((rc = start())) return rc;
-        for (int it = 0; it < n_iter; ++it) launch_step_stream(crf, step_kdevs(), maxV.data(), relax, stream, compat_arg(), pre_arg());
-        if (with_map) launch_map(crf, stream);
     }
     HIP_TRY(hipGetLastError());
     return LCCRF_OK;
+}
+
+// The view a streaming iteration runs on, behind kSized | kUnaries, with Q started on it.  In locality mode that is the internal-order
+// view (Qp, and the raw unaries permuted); end_iteration() un-permutes Q on the way out (densecrf_base.h:65-73 otherwise), then the map.
+CrfDev Engine::begin_iteration()
+{
+    CrfDev v = crf;
+    if (perm_on) {
+        v.Q = Qp;
+        if (!unary_is_label) {
+            // a BOUND unary array ("bound, not copied") may have been updated in place since the last call: permute it
+            // afresh every time, as the other engines read it live; only the engine's own copy is cached (ADVICE r3)
+            if (!unary_p_valid || crf.unary != unary_own) launch_permute_rows(crf, unary_p, crf.unary, L, 1, stream);
+            unary_p_valid = true;
+            v.unary = unary_p;
+        }
+    }
+    launch_start(v, stream);
+    started = true;
+    return v;
+}
+
+void Engine::end_iteration(int with_map)
+{
+    if (perm_on) launch_permute_rows(crf, crf.Q, Qp, L, 0, stream);
+    if (with_map) launch_map(crf, stream);
 }
 
 // ---- convergence-driven inference (include/lccrf.h sections 1h and 2e) ------------------------------------------------------
@@ -928,13 +930,7 @@ int Engine::inference_converged(int max_iter, int criterion, float tol, int with
     int rc = check_converged_args(max_iter, criterion, tol, relax);
     if (rc) return rc;
     if (!unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
-    if ((rc = resolve_late())) return rc;
-    perm_scope = true;                                // (large frames: lattices built from here may use locality mode)
-    rc = learn_sizes();
-    perm_scope = false;
-    if (!rc) rc = ensure_unary();
-    if (!rc) rc = ensure_factors();
-    if (rc) return rc;
+    if ((rc = make_ready(kSettled | kSized | kMayReorder | kUnaries | kStepViews))) return rc;   // (large frames: may use locality mode)
     last_with_map = with_map;
     conv_valid = false;
     if (sized_engine == 2 && !perm_on) {
@@ -962,19 +958,7 @@ int Engine::converge_stream(int max_iter, int criterion, float tol, int with_map
 {
     int rc = need_io();
     if (rc) return rc;
-    CrfDev cp = crf;
-    if (perm_on) {                                    // locality mode: iterate (and compare) in the internal order, as inference_sized()
-        cp.Q = Qp;
-        if (!unary_is_label) {
-            if (!unary_p_valid || crf.unary != unary_own) launch_permute_rows(crf, unary_p, crf.unary, L, 1, stream);
-            unary_p_valid = true;
-            cp.unary = unary_p;
-        }
-        launch_start(cp, stream);
-        started = true;
-    } else if ((rc = start())) {
-        return rc;
-    }
+    const CrfDev cp = begin_iteration();              // (locality mode: iterate and compare in the internal order, as inference_sized())
     const ConvergeTrack tk{io_a, reinterpret_cast<unsigned *>(conv_dev + 4 * (size_t)Fcap), conv_dev + 6 * (size_t)Fcap, conv_running,
                            conv_out()};
     launch_track_begin(cp, tk, max_iter, stream);
@@ -988,8 +972,7 @@ int Engine::converge_stream(int max_iter, int criterion, float tol, int with_map
         if (*conv_running == 0) break;
     }
     if (F > 1 && t_last > 1) launch_track_restore(cp, tk, t_last, stream);
-    if (perm_on) launch_permute_rows(crf, crf.Q, Qp, L, 0, stream);
-    if (with_map) launch_map(crf, stream);
+    end_iteration(with_map);
     HIP_TRY(hipGetLastError());
     return LCCRF_OK;
 }
@@ -1004,20 +987,46 @@ int Engine::read_convergence()
     return LCCRF_OK;
 }
 
+// getMap() with one frame in flight whose labels go straight into map_host: take them as they land.  True: `out` holds the n labels
+// and the run counts as settled -- every label is there, so the frame fitted and the kernel is past its last read -- but not as
+// formally finished: V_out, frame_status and the done word are stored behind the labels (and a helper workgroup may be in its
+// epilogue): the handle counts as idle only once recycle() has seen the done word.  False: the ordinary path (resolve_late) is to run.
+bool Engine::take_labels(int16_t *out, int n)
+{
+    if (flight != Flight::kPendingLabels) return false;
+    flight = Flight::kPendingDone;
+    const volatile int16_t *m = map_host;
+    const auto t0 = std::chrono::steady_clock::now();
+    bool ok = true, timed_out = false;
+    unsigned spins = 0;
+    for (int i = 0; i < n && ok; ++i) {
+        int16_t v;
+        while ((v = m[i]) == (int16_t)-1) {               // (bounded: whatever goes wrong is left to the ordinary path)
+            if ((++spins & 0x3ff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) { ok = false; timed_out = true; break; }
+            cpu_relax();
+        }
+        if (v < 0) ok = false;                            // -2: the frame did not fit the one-launch kernel
+    }
+    if (ok) {
+        std::atomic_thread_fence(std::memory_order_acquire);
+        memcpy(out, map_host, (size_t)n * sizeof(int16_t));
+        flight = Flight::kLabelsSeen;
+        return true;
+    }
+    if (timed_out) flight = Flight::kPending;             // (a delayed frame: do not spin another 2 ms on the done word, wait on the stream)
+    return false;
+}
+
 // Before anything looks at (or continues from) the results of a late-bound inference.
 // *seen_done (optional): the frame's results were observed through the done word -- the caller may read the pinned
 // outputs without a stream synchronisation of its own.
 int Engine::resolve_late(bool *seen_done)
 {
     if (seen_done) *seen_done = false;
-    if (!late_pending) return LCCRF_OK;
-    late_pending = false;
-    labels_armed = false;
-    bool seen = false;
-    if (done_armed) {                                  // bounded poll; a word that never comes is waited for the ordinary way
-        done_armed = false;
-        seen = poll_done_word(done_word, done_epoch, std::chrono::milliseconds(2), 1024);
-    }
+    if (!run_pending()) return LCCRF_OK;
+    // bounded poll; a word that never comes is waited for the ordinary way
+    const bool seen = flight != Flight::kPending && poll_done_word(done_word, done_epoch, std::chrono::milliseconds(2), 1024);
+    flight = Flight::kUnknown;
     if (!seen) HIP_TRY(hipStreamSynchronize(stream));
     if (*npoints_bad) {                                // (the one-launch path never passes through learn_sizes())
         *npoints_bad = 0;
