@@ -508,8 +508,8 @@ int  lccrf_get_pairwise_normalization(lccrf_handle h, int kernel, int *mode);
  * term with a matrix (1e) or a normalisation mode (1g), locality mode, lattices beyond LDS -- runs the streaming engine's step
  * unchanged with a small comparison kernel behind each step; the host then reads ONE word per iteration (the number of frames still
  * running) behind a synchronisation of the call's stream.  lccrf_get_engine reports 1.  The lattices are built and sized exactly as
- * by lccrf_inference on built lattices; the call never takes the one-launch build + inference kernel and neither reads, writes
- * nor invalidates prepared launch records.
+ * by lccrf_inference on built lattices; THIS call never takes the one-launch build + inference kernel (section 1i's
+ * lccrf_run_converged does) and neither reads, writes nor invalidates prepared launch records.
  *
  * Behind the call the handle is as after lccrf_inference(h, t, ...): lccrf_step_inference continues from Q_t, the getters return
  * Q_t and its labels, and lccrf_inference_backward(h, t, relax, ...) with the reported `iterations` is the gradient of the
@@ -522,6 +522,23 @@ int  lccrf_inference_converged(lccrf_handle h, int max_iterations, int criterion
 /* What the last lccrf_inference_converged on the handle reported; any pointer may be NULL.  Waits for the handle's stream.
  * LCCRF_E_STATE when no converged inference has run on the handle's current inputs.                                               */
 int  lccrf_get_convergence(lccrf_handle h, int *iterations, float *delta, int *changed, int *converged);
+
+/* ======================================================================================
+ * 1i. Convergence-driven inference on a fresh frame in ONE launch -- section 1h's call for the tracker's sequence "build both
+ * lattices, infer once, read the labels" (src/Tracking.cc:1920-1929).  Needs inputs only (unaries and every term's features).  A
+ * handle lccrf_inference would run in one launch -- two labels, one or two 2-D Potts terms normalised AFTER, up to 4096 points,
+ * automatic engine choice -- builds both lattices in LDS, normalises, and infers until converged in ONE kernel launch
+ * (csrc/frame_converge.hip: one 1024-lane workgroup, as with LCCRF_OPT_SINGLE_WORKGROUP); the lattices never reach HBM, with_map
+ * labels arrive in the handle's pinned array (lccrf_get_map right behind the call takes them as they land) and
+ * lccrf_get_convergence returns the report.  lccrf_get_engine reports 3.
+ *     Q, labels, label bits, report   bit for bit what lccrf_inference_converged leaves, i.e. what lccrf_inference(h, t, ...)
+ *                                     leaves at the reported t; max_iterations == 0 and the empty frame as in section 1h
+ * A frame the kernel cannot take -- lattices beyond one workgroup's LDS -- is found at the next synchronisation point and re-run
+ * there with lccrf_inference_converged's engines; lccrf_get_engine then reports what it was re-run on (2 or 1).  A handle whose
+ * lattices are already built and sized, or that lccrf_inference would not run in one launch, takes lccrf_inference_converged at
+ * once.  Errors and the state behind the call: section 1h's.  Added WITHOUT a step of LCCRF_ABI_VERSION: probe by symbol.
+ * ==================================================================================== */
+int  lccrf_run_converged(lccrf_handle h, int max_iterations, int criterion, float tol, int with_map, float relax);
 
 /* ======================================================================================
  * 2. Batch API -- many independent frames in flight on one GPU.
@@ -750,6 +767,19 @@ int  lccrf_batch_get_convergence_host(lccrf_batch_handle b, int32_t *iterations,
  * stays on the device: valid behind the converged call in stream order.  Any pointer may be NULL.                                 */
 int  lccrf_batch_device_convergence(lccrf_batch_handle b, const int32_t **d_iterations, const float **d_delta,
                                     const int32_t **d_changed, const int32_t **d_converged);
+
+/* ======================================================================================
+ * 2f. Section 1i for every frame of a batch: lccrf_batch_run with section 2e's stop rule.  Needs inputs only; asynchronous on
+ * `stream` (NULL: the batch's own).  Per frame Q, labels, label bits and the report are bit for bit what lccrf_batch_build followed
+ * by lccrf_batch_inference_converged leaves; every frame stops on its own.  Batches lccrf_batch_run takes in one launch run one
+ * 1024-lane workgroup per frame (csrc/frame_converge.hip), lccrf_batch_get_engine reports 3; frames the kernel cannot take are
+ * decided per frame at the next synchronisation point, re-run there with lccrf_batch_inference_converged's engines and counted by
+ * lccrf_batch_get_fallback_frames, as for lccrf_batch_run.  The getters of section 2e settle a pending run first
+ * (lccrf_batch_device_convergence: the arrays are complete behind lccrf_batch_synchronize).  Every other batch builds its lattices
+ * and takes lccrf_batch_inference_converged.  The argument checks of section 1h.  Added without a step of LCCRF_ABI_VERSION.
+ * ==================================================================================== */
+int  lccrf_batch_run_converged(lccrf_batch_handle b, int max_iterations, int criterion, float tol, int with_map, float relax,
+                               void *stream);
 
 /* ======================================================================================
  * 3. Unary builder -- the step right before the CRF (first "next" row):

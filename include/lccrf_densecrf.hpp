@@ -372,7 +372,19 @@ public:
         if (with_map) lccrf_check(lccrf_get_map(h_, map_), "lccrf_get_map");
         if (base_sync_) syncProbability();
     }
-    int iterations() const { return conv_iterations_; }        // of the last inferenceConverged(): t, d_t, c_t, the criterion was met
+    // The tracker's sequence -- construct, unaries, addPairwiseEnergy twice, infer, read the labels -- with inferenceConverged's stop
+    // rule in place of a fixed count (include/lccrf.h section 1i): on a fresh frame ONE kernel launch; with_map labels are taken as
+    // they arrive, the report right behind them.  Results and accessors as inferenceConverged's.
+    void runConverged(int max_iterations, int criterion = LCCRF_STOP_LABELS, float tol = 0.0f, bool with_map = false, float relax = 1.0)
+    {
+        adopt();
+        if (mixed_) throw std::runtime_error("runConverged: not supported with foreign potentials");
+        lccrf_check(lccrf_run_converged(h_, max_iterations, criterion, tol, with_map ? 1 : 0, relax), "lccrf_run_converged");
+        if (with_map) lccrf_check(lccrf_get_map(h_, map_), "lccrf_get_map");
+        lccrf_check(lccrf_get_convergence(h_, &conv_iterations_, &conv_delta_, &conv_changed_, &conv_converged_), "lccrf_get_convergence");
+        if (base_sync_) syncProbability();
+    }
+    int iterations() const { return conv_iterations_; }        // of the last inferenceConverged() / runConverged(): t, d_t, c_t, the criterion was met
     float delta() const { return conv_delta_; }
     int changed() const { return conv_changed_; }
     bool converged() const { return conv_converged_ != 0; }

@@ -234,7 +234,17 @@ public:
         lccrf_check(lccrf_get_convergence(h_, &conv_iterations_, &conv_delta_, &conv_changed_, &conv_converged_), "lccrf_get_convergence");
         sync();
     }
-    int iterations() const { return conv_iterations_; }        // of the last inferenceConverged(): t, d_t, c_t, the criterion was met
+    // inferenceConverged() from inputs alone (include/lccrf.h section 1i): a fresh frame is built, normalised and inferred until
+    // converged in ONE kernel launch.  Results and accessors as inferenceConverged's; ends with a synchronisation.
+    void runConverged(int max_iterations, int criterion = LCCRF_STOP_LABELS, float tol = 0.0f, bool with_map = false, float relax = 1.0)
+    {
+        adopt();
+        if (mixed_) throw std::runtime_error("runConverged: not supported with foreign potentials");
+        lccrf_check(lccrf_run_converged(h_, max_iterations, criterion, tol, with_map ? 1 : 0, relax), "lccrf_run_converged");
+        lccrf_check(lccrf_get_convergence(h_, &conv_iterations_, &conv_delta_, &conv_changed_, &conv_converged_), "lccrf_get_convergence");
+        sync();
+    }
+    int iterations() const { return conv_iterations_; }        // of the last inferenceConverged() / runConverged(): t, d_t, c_t, the criterion was met
     float delta() const { return conv_delta_; }
     int changed() const { return conv_changed_; }
     bool converged() const { return conv_converged_ != 0; }

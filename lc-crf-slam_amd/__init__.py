@@ -110,6 +110,8 @@ def lib():
     L.lccrf_inference_converged.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float]
     L.lccrf_get_convergence.argtypes = [vp, C.POINTER(C.c_int), _f32p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lccrf_batch_inference_converged.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, vp]
+    L.lccrf_run_converged.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float]
+    L.lccrf_batch_run_converged.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, vp]
     L.lccrf_batch_get_convergence_host.argtypes = [vp, _i32p, _f32p, _i32p, _i32p]
     L.lccrf_batch_device_convergence.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.lccrf_get_lattice_size.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
@@ -304,8 +306,14 @@ class DenseCRFHIP:
                                                float(relax)))
         return self.convergence()
 
+    def run_converged(self, max_iterations, criterion=STOP_LABELS, tol=0.0, with_map=False, relax=1.0):
+        """inference_converged() from inputs alone (include/lccrf.h section 1i): a fresh frame is built, normalised and inferred
+        until converged in ONE launch.  Asynchronous: map() right behind it takes the labels as they arrive, convergence() the
+        report."""
+        _check(lib().lccrf_run_converged(self.h, int(max_iterations), int(criterion), float(tol), int(bool(with_map)), float(relax)))
+
     def convergence(self):
-        """dict(iterations, delta (np.float32), changed, converged) of the last inference_converged()."""
+        """dict(iterations, delta (np.float32), changed, converged) of the last inference_converged() / run_converged()."""
         it, ch, cv, d = C.c_int(0), C.c_int(0), C.c_int(0), C.c_float(0)
         _check(lib().lccrf_get_convergence(self.h, C.byref(it), C.byref(d), C.byref(ch), C.byref(cv)))
         return dict(iterations=it.value, delta=np.float32(d.value), changed=ch.value, converged=cv.value)
@@ -612,8 +620,15 @@ class BatchCRF:
         _check(lib().lccrf_batch_inference_converged(self.h, int(max_iterations), int(criterion), float(tol), int(bool(with_map)),
                                                      float(relax), C.c_void_p(stream) if stream else None))
 
+    def run_converged(self, max_iterations, criterion=STOP_LABELS, tol=0.0, with_map=True, relax=1.0, stream=None):
+        """run() with inference_converged()'s stop rule (include/lccrf.h section 2f): from inputs alone, every frame built and
+        inferred until ITS criterion holds in one launch; asynchronous like run()."""
+        _check(lib().lccrf_batch_run_converged(self.h, int(max_iterations), int(criterion), float(tol), int(bool(with_map)),
+                                               float(relax), C.c_void_p(stream) if stream else None))
+
     def convergence(self):
-        """dict of [n_frames] arrays: iterations, delta, changed, converged of the last inference_converged() (waits for the batch)."""
+        """dict of [n_frames] arrays: iterations, delta, changed, converged of the last inference_converged() / run_converged()
+        (waits for the batch)."""
         F = self.n_frames
         it, ch, cv = (np.zeros(F, np.int32) for _ in range(3))
         d = np.zeros(F, np.float32)

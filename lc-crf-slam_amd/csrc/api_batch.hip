@@ -503,6 +503,7 @@ int lccrf_batch_device_convergence(lccrf_batch_handle b, const int32_t **d_itera
                                    const int32_t **d_converged)
 {
     CHECK_H(b);
+    { int rl = b->eng.resolve_late(); if (rl) return rl; }   // (section 2f: a pending one-launch run's flagged frames are re-run first)
     const ConvergeOut o = b->eng.conv_out();
     if (d_iterations) *d_iterations = o.iterations;
     if (d_delta) *d_delta = o.delta;
@@ -517,6 +518,20 @@ int lccrf_batch_run(lccrf_batch_handle b, int n_iterations, int with_map, float 
     if (!b->inputs_set) return fail(LCCRF_E_STATE, "inputs not set");
     Engine &e = b->eng;
     const int rc = timed_batch_call(e, stream, e.ev[2], e.ev[3], e.timed_inf, [&] { return e.run(n_iterations, with_map, relax); });
+    e.built = e.built_upto == (int)e.kernels.size() && !e.kernels.empty();
+    return rc;
+}
+
+// section 2f (the argument checks come first, as in 2e)
+int lccrf_batch_run_converged(lccrf_batch_handle b, int max_iterations, int criterion, float tol, int with_map, float relax, void *stream)
+{
+    const int ra = Engine::check_converged_args(max_iterations, criterion, tol, relax);
+    if (ra) return ra;
+    CHECK_H(b);
+    if (!b->inputs_set) return fail(LCCRF_E_STATE, "inputs not set");
+    Engine &e = b->eng;
+    const int rc = timed_batch_call(e, stream, e.ev[2], e.ev[3], e.timed_inf,
+                                    [&] { return e.run_converged(max_iterations, criterion, tol, with_map, relax); });
     e.built = e.built_upto == (int)e.kernels.size() && !e.kernels.empty();
     return rc;
 }

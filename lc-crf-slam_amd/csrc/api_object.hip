@@ -314,6 +314,15 @@ int lccrf_inference_converged(lccrf_handle h, int max_iterations, int criterion,
     return h->eng.inference_converged(max_iterations, criterion, tol, with_map, relax);
 }
 
+// section 1i
+int lccrf_run_converged(lccrf_handle h, int max_iterations, int criterion, float tol, int with_map, float relax)
+{
+    const int ra = Engine::check_converged_args(max_iterations, criterion, tol, relax);
+    if (ra) return ra;
+    CHECK_H(h);
+    return h->eng.run_converged(max_iterations, criterion, tol, with_map, relax);
+}
+
 int lccrf_get_convergence(lccrf_handle h, int *iterations, float *delta, int *changed, int *converged)
 {
     CHECK_H(h);

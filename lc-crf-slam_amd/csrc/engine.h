@@ -393,6 +393,12 @@ bool frame_supported(const CrfDev &c, const KernelDev *kds);
 int launch_frame(const CrfDev &c, const KernelDev *kds, int n_iter, int with_map, float relax, int *status, int *frame_status,
                  const int16_t *label, const float *tbl5, hipStream_t s, bool allow_small = true, unsigned *dual = nullptr,
                  unsigned dual_epoch = 0, unsigned *done = nullptr, unsigned done_epoch = 0, unsigned char *lean_rec = nullptr);
+// The same launch with the inference run until converged, at most max_iter iterations (frame_converge.hip; include/lccrf.h sections
+// 1i and 2f): one 1024-lane workgroup per frame, never the two-workgroup or a half-CU shape.  `out` receives every frame's report; a
+// frame that does not fit -- its lattices, or the reduction's 16 bytes behind its loop plan -- is flagged exactly as launch_frame's.
+void launch_frame_converged(const CrfDev &c, const KernelDev *kds, int max_iter, int criterion, float tol, int with_map, float relax,
+                            int *status, int *frame_status, const int16_t *label, const float *tbl5, const ConvergeOut &out,
+                            hipStream_t s, unsigned *done = nullptr, unsigned done_epoch = 0);
 bool frame_lean_wanted(const CrfDev &c);              // would launch_frame take the lean shape for this batch, given the area?
 size_t frame_lean_rec_bytes(int frames);
 size_t frame_dual_bytes(int frames);

@@ -143,6 +143,11 @@ struct Engine {
     bool late_ok = false;              // set by the object API: single frame, automatic engine choice
     int late_iter = 0, late_map = 0;
     float late_relax = 1.0f;
+    // ... and whether the pending run is a converged one (run_converged: late_iter is then its cap): its flagged frames are re-run
+    // with inference_converged() on these, and their reports scattered back beside Q and the labels
+    bool late_conv = false;
+    int late_criterion = 0;
+    float late_tol = 0.0f;
     // Called by resolve_late() right behind a re-run of flagged frames (before its final synchronisation): the owner of host-side
     // copies of the results (the batch's download pipe) re-queues them, whichever entry point happened to settle the run.
     int (*after_rerun)(void *) = nullptr;
@@ -252,7 +257,7 @@ struct Engine {
     int *conv_host = nullptr;          // pinned [4][Fcap]
     int *conv_running = nullptr;       // pinned [1]
     bool conv_valid = false;           // a converged run has reported on the current inputs
-    int conv_engine = 0;               // report only (lccrf_batch_get_engine): 2 / 1 when the last inference was a converged one, else 0
+    int conv_engine = 0;               // report only (lccrf_batch_get_engine): 3 / 2 / 1 when the last inference was a converged one, else 0
     ConvergeOut conv_out() const
     {
         return ConvergeOut{conv_dev, reinterpret_cast<float *>(conv_dev + Fcap), conv_dev + 2 * (size_t)Fcap, conv_dev + 3 * (size_t)Fcap};
@@ -304,12 +309,15 @@ struct Engine {
     int start();
     int step(float relax);
     bool frame_ok() const;
-    int run_frame(int n_iter, int with_map, float relax);
+    struct StopRule { int criterion; float tol; };   // (run_frame: a converged run's criterion and tol; n_iter is then its cap)
+    int run_frame(int n_iter, int with_map, float relax, const StopRule *stop = nullptr);
     int inference(int n_iter, int with_map, float relax);
     int run(int n_iter, int with_map, float relax);
     int inference_sized(int n_iter, int with_map, float relax, unsigned more_needs = 0);   // (more_needs: 0 or kMayReorder)
     static int check_converged_args(int max_iter, int criterion, float tol, float relax);
     int inference_converged(int max_iter, int criterion, float tol, int with_map, float relax);
+    int run_converged(int max_iter, int criterion, float tol, int with_map, float relax);
+    int rerun_on(Engine &e);
     int converge_stream(int max_iter, int criterion, float tol, int with_map, float relax);
     int read_convergence();
     int resolve_late(bool *seen_done = nullptr);

@@ -725,7 +725,7 @@ bool Engine::frame_ok() const
 
 // One launch per frame; whether every frame fitted the kernel's LDS plan is known at the next
 // synchronisation point (resolve_late), which re-runs the batch on the two-kernel path if not.
-int Engine::run_frame(int n_iter, int with_map, float relax)
+int Engine::run_frame(int n_iter, int with_map, float relax, const StopRule *stop)
 {
     *late_status = 0;
     // (label-derived energies already written for lattices in locality mode sit in the INTERNAL point order: the frame kernel, which
@@ -734,7 +734,7 @@ int Engine::run_frame(int n_iter, int with_map, float relax)
     unsigned *dual = nullptr;
     // The tracker's case (one frame, 255 idle CUs) and small batches (a quarter as many frames as CUs, or fewer): every
     // frame gets two workgroups, one per lattice build.
-    if (crf.K == 2 && F <= kDualMaxFrames && !opt_single_wg) {
+    if (crf.K == 2 && F <= kDualMaxFrames && !opt_single_wg && !stop) {
         if (!dual_area) {
             int rc = mem.alloc(reinterpret_cast<char **>(&dual_area), frame_dual_bytes(std::min(Fcap, kDualMaxFrames)));
             if (rc) return rc;
@@ -750,7 +750,7 @@ int Engine::run_frame(int n_iter, int with_map, float relax)
     // full-size frames, two per CU (frame_lean.hip): the record area its loop re-reads is allocated when a batch first wants it
     // (sized for the frames BOUND, not for the handle's capacity -- 96 KB per frame: a handle created for 16384 frames that runs 1024 takes
     //  0.1 GB, not 1.6; a later, larger batch gets a new area, the old one stays with the handle until it is destroyed -- ADVICE r5)
-    if (frame_lean_ok && lean_rec_frames < F && frame_lean_wanted(crf)) {
+    if (!stop && frame_lean_ok && lean_rec_frames < F && frame_lean_wanted(crf)) {
         // (no memory for the area: the batch keeps the one-frame-per-CU kernel, which needs none)
         lean_rec = nullptr;
         lean_rec_frames = 0;
@@ -763,15 +763,27 @@ int Engine::run_frame(int n_iter, int with_map, float relax)
             lean_rec_frames = want;
         }
     }
-    const int shape = launch_frame(crf, kdevs.data(), n_iter, with_map, relax, late_status, frame_status,
-                                   from_label ? deferred_label : nullptr, deferred_tbl.v, stream, frame_small_ok, dual, dual_epoch,
-                                   by_word ? done_word : nullptr, done_epoch, frame_lean_ok ? lean_rec : nullptr);
+    int shape = 0;
+    if (stop) {
+        // until converged (frame_converge.hip): always one 1024-lane workgroup per frame; the report leaves with the results
+        launch_frame_converged(crf, kdevs.data(), n_iter, stop->criterion, stop->tol, with_map, relax, late_status, frame_status,
+                               from_label ? deferred_label : nullptr, deferred_tbl.v, conv_out(), stream,
+                               by_word ? done_word : nullptr, done_epoch);
+    } else {
+        shape = launch_frame(crf, kdevs.data(), n_iter, with_map, relax, late_status, frame_status,
+                             from_label ? deferred_label : nullptr, deferred_tbl.v, stream, frame_small_ok, dual, dual_epoch,
+                             by_word ? done_word : nullptr, done_epoch, frame_lean_ok ? lean_rec : nullptr);
+    }
     HIP_TRY(hipGetLastError());
     frame_small_used = shape == 1;
     frame_lean_used = shape == 2;
     fused_shape = shape == 0 ? (1024 | 1 << 16) : (512 | 2 << 16);       // lanes per frame | frames per CU
     engine_shape = 0;
-    conv_engine = 0;
+    conv_engine = stop ? 3 : 0;
+    if (stop) conv_valid = true;
+    late_conv = stop != nullptr;
+    late_criterion = stop ? stop->criterion : 0;
+    late_tol = stop ? stop->tol : 0.0f;
 
     flight = by_label ? Flight::kPendingLabels : by_word ? Flight::kPendingDone : Flight::kPending;
     late_iter = n_iter;
@@ -951,6 +963,26 @@ int Engine::inference_converged(int max_iter, int criterion, float tol, int with
     return LCCRF_OK;
 }
 
+// lccrf_run_converged / lccrf_batch_run_converged (sections 1i and 2f): from inputs alone.  A frame the one-launch kernel takes is
+// built, normalised and inferred until converged in ONE launch (run_frame with a stop rule: what it leaves is run_frame's, plus the
+// report); whether every frame fitted is known at the next synchronisation point, where resolve_late() re-runs the flagged ones with
+// inference_converged().  Anything else builds into HBM and takes inference_converged() at once -- as does a handle whose lattices
+// are already built and sized (a probe put them there), the rule of Engine::inference.
+int Engine::run_converged(int max_iter, int criterion, float tol, int with_map, float relax)
+{
+    int rc = check_converged_args(max_iter, criterion, tol, relax);
+    if (rc) return rc;
+    if (!unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
+    if ((rc = resolve_late())) return rc;
+    if (late_ok && built_upto == (int)kernels.size() && sizes_known) return inference_converged(max_iter, criterion, tol, with_map, relax);
+    if (frame_ok()) {
+        const StopRule stop{criterion, tol};
+        return run_frame(max_iter, with_map, relax, &stop);
+    }
+    invalidate_lattices();                            // two-kernel path: rebuild for the current inputs, then infer
+    return inference_converged(max_iter, criterion, tol, with_map, relax);
+}
+
 // The streaming path: start, then per iteration the unchanged step, the comparison and the settle kernel, ONE synchronisation of the
 // call's stream and one pinned word read -- the frames still running.  These are the frames where an iteration is many launches
 // anyway.  The kept copy of the previous Q is io_a.
@@ -1048,7 +1080,7 @@ int Engine::resolve_late(bool *seen_done)
     int rc = LCCRF_OK;
     if (n >= F || n == 0) {                            // every frame (always so for the object API): two-kernel path in place
         invalidate_lattices();
-        rc = inference_sized(late_iter, late_map, late_relax);
+        rc = rerun_on(*this);
     } else {
         rc = rerun_frames(n);                          // the batch stays a one-launch batch; only the flagged frames pay twice
         engine_used = 3;
@@ -1058,6 +1090,14 @@ int Engine::resolve_late(bool *seen_done)
     if (after_rerun && (rc = after_rerun(after_rerun_ctx))) return rc;
     HIP_TRY(hipStreamSynchronize(stream));             // callers read borrowed device buffers right behind a synchronisation point
     return LCCRF_OK;
+}
+
+// What the pending one-launch run is re-run with on the two-kernel path of `e` (this engine, or the sub-engine holding its flagged
+// frames): the fixed count, or -- behind run_converged() -- the same stop rule.
+int Engine::rerun_on(Engine &e)
+{
+    if (late_conv) return e.inference_converged(late_iter, late_criterion, late_tol, late_map, late_relax);
+    return e.inference_sized(late_iter, late_map, late_relax);
 }
 
 // Two-kernel path for the frames fb_list_host[0, n) only, in a compact sub-engine; results scattered back.
@@ -1112,7 +1152,7 @@ int Engine::rerun_frames(int n)
     g.invalidate_lattices();
     g.sync_views();
     HIP_TRY(hipGetLastError());
-    int rc = g.inference_sized(late_iter, late_map, late_relax);
+    int rc = rerun_on(g);
     if (rc) return rc;
     const size_t qrow = (size_t)maxN * L * sizeof(float);
     launch_copy_frames(crf.Q, qrow, g.crf.Q, qrow, fb_list, n, qrow, 0, stream);
@@ -1124,6 +1164,9 @@ int Engine::rerun_frames(int n)
     }
     for (size_t k = 0; k < kernels.size(); ++k)
         launch_copy_frames(kernels[k].dev.V, 4, g.kernels[k].dev.V, 4, fb_list, n, 4, 0, stream);
+    if (late_conv)                                    // the re-run frames' reports: iterations, delta, changed, converged
+        for (int a = 0; a < 4; ++a)
+            launch_copy_frames(conv_dev + (size_t)a * Fcap, 4, g.conv_dev + (size_t)a * g.Fcap, 4, fb_list, n, 4, 0, stream);
     HIP_TRY(hipGetLastError());
     return LCCRF_OK;
 }
