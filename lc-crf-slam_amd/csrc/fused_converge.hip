@@ -17,7 +17,7 @@
 #include "engine.h"
 #include "device_math.h"
 #include "fused_loop.h"
-#include "dispatch.h"
+#include "fused_variant.h"
 
 namespace lccrf {
 
@@ -164,27 +164,17 @@ int launch_inference_converged(const CrfDev &c, const KernelDev *kds, const int 
                                float tol, int with_map, float relax, const ConvergeOut &out, hipStream_t s)
 {
     ConvergeArgs a{};
-    const int NA = active_points(c);
-    if (NA > kConvergeMaxPPT * kNT || !slam_shaped(c, kds, true)) return 0;
-    if (!layout_core(NA, c.K, maxV, maxRow ? maxRow[0] : 0, &a.lay)) return 0;
-    if ((size_t)a.lay.total + kConvergeLds > kLdsLimit) return 0;          // no room for the reduction's words: the caller streams
-    for (int k = 0; k < c.K; ++k) a.kd[k] = kds[k];
     a.max_iter = max_iter;
     a.with_map = with_map;
     a.criterion = criterion;
     a.relax = relax;
     a.tol = tol;
     a.out = out;
-    const int ppt = std::max((NA + kNT - 1) / kNT, 1);
-    with_dims<1, kMaxFusedK>(c.K, [&](auto kk) {
-        with_dims<0, 1>(a.lay.chain0 ? 1 : 0, [&](auto ch) {
-            with_dims<1, kConvergeMaxPPT>(ppt, [&](auto p) {
-                launch_workgroups(k_converge<decltype(p)::value, decltype(kk)::value, decltype(ch)::value>, c.F, kNT,
-                                  a.lay.total + kConvergeLds, s, c, a);
-            });
-        });
+    // (a plan that leaves no room for the reduction's words: the caller streams)
+    return plan_variant<kConvergeMaxPPT>(c, kds, maxV, maxRow, kConvergeLds, a, [&](auto p, auto kk, auto ch) {
+        launch_workgroups(k_converge<decltype(p)::value, decltype(kk)::value, decltype(ch)::value>, c.F, kNT,
+                          a.lay.total + kConvergeLds, s, c, a);
     });
-    return fused_report(kNT, ppt, a.lay.chain0);
 }
 
 }  // namespace lccrf

@@ -19,7 +19,7 @@
 #include "engine.h"
 #include "device_math.h"
 #include "fused_loop.h"
-#include "dispatch.h"
+#include "fused_variant.h"
 
 namespace lccrf {
 
@@ -169,29 +169,20 @@ int launch_inference_general(const CrfDev &c, const KernelDev *kds, const int *m
                              const float *const *pre, int n_iter, int with_map, float relax, hipStream_t s)
 {
     GeneralArgs a{};
-    const int NA = active_points(c);
-    if (c.F != 1 || NA > kGeneralMaxPPT * kNT || !slam_shaped(c, kds, true)) return 0;
-    if (!layout_core(NA, c.K, maxV, maxRow ? maxRow[0] : 0, &a.lay)) return 0;
-    for (int k = 0; k < c.K; ++k) {
-        a.kd[k] = kds[k];
-        a.pre[k] = pre ? pre[k] : nullptr;
-        if (compat && compat[k]) {
-            a.has_mu |= 1 << k;
-            for (int e = 0; e < 4; ++e) a.mu[k][e] = compat[k][e];
-        }
-    }
+    if (c.F != 1) return 0;
     a.n_iter = n_iter;
     a.with_map = with_map;
     a.relax = relax;
-    const int ppt = std::max((NA + kNT - 1) / kNT, 1);
-    with_dims<1, kMaxFusedK>(c.K, [&](auto kk) {
-        with_dims<0, 1>(a.lay.chain0 ? 1 : 0, [&](auto ch) {
-            with_dims<1, kGeneralMaxPPT>(ppt, [&](auto p) {
-                launch_workgroups(k_general<decltype(p)::value, decltype(kk)::value, decltype(ch)::value>, c.F, kNT, a.lay.total, s, c, a);
-            });
-        });
+    return plan_variant<kGeneralMaxPPT>(c, kds, maxV, maxRow, 0, a, [&](auto p, auto kk, auto ch) {
+        for (int k = 0; k < c.K; ++k) {                   // (behind the plan's guard: c.K <= kMaxFusedK)
+            a.pre[k] = pre ? pre[k] : nullptr;
+            if (compat && compat[k]) {
+                a.has_mu |= 1 << k;
+                for (int e = 0; e < 4; ++e) a.mu[k][e] = compat[k][e];
+            }
+        }
+        launch_workgroups(k_general<decltype(p)::value, decltype(kk)::value, decltype(ch)::value>, c.F, kNT, a.lay.total, s, c, a);
     });
-    return fused_report(kNT, ppt, a.lay.chain0);
 }
 
 }  // namespace lccrf

@@ -1,0 +1,35 @@
+// fused_variant.h -- the launch plan that the fused engine's variants in units of their own (k_general, k_converge) share.
+//
+// Their kernels open with the text of k_fused's self-contained prologue (MODE 0 / 1, fused_engine.hip:166-240), each copied by hand: a
+// change to one of the three places is to be made in all.  As two shared __forceinline__ functions the prologue compiled within every
+// pinned figure, but on an MI355X the c2 frame then ran k_converge in 38.75 / 38.75 / 38.78 us against 38.57 / 38.63 / 38.57 and
+// k_general (matrices) in 35.85 / 35.86 / 35.93 against 35.65 / 35.73 / 35.78 -- outside the parent's spread -- so the text stays.
+#pragma once
+
+#include "fused_loop.h"
+#include "dispatch.h"
+
+namespace lccrf {
+namespace {
+
+// Frames of up to MaxPPT x 1024 active points on lattices that fit the fused plan with `extra_lds` bytes behind it: fills a.lay and
+// a.kd, then calls launch(points per lane, K, kernel 0 on chain rows) -- three integral_constants -- which names the kernel.
+// Returns fused_report() of the shape, or 0 with `launch` not called.
+template <int MaxPPT, typename Args, typename Launch>
+int plan_variant(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, size_t extra_lds, Args &a, Launch launch)
+{
+    using namespace fl;
+    const int NA = active_points(c);
+    if (NA > MaxPPT * kNT || !slam_shaped(c, kds, true)) return 0;
+    if (!layout_core(NA, c.K, maxV, maxRow ? maxRow[0] : 0, &a.lay)) return 0;
+    if ((size_t)a.lay.total + extra_lds > kLdsLimit) return 0;
+    for (int k = 0; k < c.K; ++k) a.kd[k] = kds[k];
+    const int ppt = std::max((NA + kNT - 1) / kNT, 1);
+    with_dims<1, kMaxFusedK>(c.K, [&](auto kk) {
+        with_dims<0, 1>(a.lay.chain0 ? 1 : 0, [&](auto ch) { with_dims<1, MaxPPT>(ppt, [&](auto p) { launch(p, kk, ch); }); });
+    });
+    return fused_report(kNT, ppt, a.lay.chain0);
+}
+
+}  // namespace
+}  // namespace lccrf

@@ -4,6 +4,8 @@
 // per-frame fallback, the done-word protocol, the backward area, the compatibility matrices and the normalisation modes.  The bodies are in
 // host_engine.hip; the entry points of include/lccrf.h (api_*.hip) read and write the fields below directly -- all but the two things
 // that are the engine's own: what a call relies on is brought up to date by make_ready() alone, what is in flight is `flight`.
+// A one-launch run is armed by run_frame() alone, which takes the run as one Schedule -- from inference() and run() a fixed count,
+// from run_converged() a cap with its criterion and tol -- and keeps it as `late`, what resolve_late() re-runs flagged frames with.
 #pragma once
 
 #include "engine.h"
@@ -141,13 +143,11 @@ struct Engine {
     // the lattice sizes; `late_status` (pinned) tells afterwards whether the frame fitted.
     int *late_status = nullptr;
     bool late_ok = false;              // set by the object API: single frame, automatic engine choice
-    int late_iter = 0, late_map = 0;
-    float late_relax = 1.0f;
-    // ... and whether the pending run is a converged one (run_converged: late_iter is then its cap): its flagged frames are re-run
-    // with inference_converged() on these, and their reports scattered back beside Q and the labels
-    bool late_conv = false;
-    int late_criterion = 0;
-    float late_tol = 0.0f;
+    // One run: a fixed count of n_iter iterations, or -- until_converged -- at most n_iter under (criterion, tol).
+    struct Schedule { int n_iter; int with_map; float relax; bool until_converged; int criterion; float tol; };
+    // the pending run's (run_frame): its flagged frames are re-run with it on the two-kernel path (rerun_on) -- a converged one with
+    // inference_converged(), their reports scattered back beside Q and the labels
+    Schedule late{0, 0, 1.0f, false, 0, 0.0f};
     // Called by resolve_late() right behind a re-run of flagged frames (before its final synchronisation): the owner of host-side
     // copies of the results (the batch's download pipe) re-queues them, whichever entry point happened to settle the run.
     int (*after_rerun)(void *) = nullptr;
@@ -309,8 +309,7 @@ struct Engine {
     int start();
     int step(float relax);
     bool frame_ok() const;
-    struct StopRule { int criterion; float tol; };   // (run_frame: a converged run's criterion and tol; n_iter is then its cap)
-    int run_frame(int n_iter, int with_map, float relax, const StopRule *stop = nullptr);
+    int run_frame(const Schedule &run);
     int inference(int n_iter, int with_map, float relax);
     int run(int n_iter, int with_map, float relax);
     int inference_sized(int n_iter, int with_map, float relax, unsigned more_needs = 0);   // (more_needs: 0 or kMayReorder)

@@ -725,8 +725,10 @@ bool Engine::frame_ok() const
 
 // One launch per frame; whether every frame fitted the kernel's LDS plan is known at the next
 // synchronisation point (resolve_late), which re-runs the batch on the two-kernel path if not.
-int Engine::run_frame(int n_iter, int with_map, float relax, const StopRule *stop)
+int Engine::run_frame(const Schedule &run)
 {
+    const int with_map = run.with_map;
+    const bool stop = run.until_converged;
     *late_status = 0;
     // (label-derived energies already written for lattices in locality mode sit in the INTERNAL point order: the frame kernel, which
     //  works in the caller's order, derives them from the labels again)
@@ -766,11 +768,11 @@ int Engine::run_frame(int n_iter, int with_map, float relax, const StopRule *sto
     int shape = 0;
     if (stop) {
         // until converged (frame_converge.hip): always one 1024-lane workgroup per frame; the report leaves with the results
-        launch_frame_converged(crf, kdevs.data(), n_iter, stop->criterion, stop->tol, with_map, relax, late_status, frame_status,
+        launch_frame_converged(crf, kdevs.data(), run.n_iter, run.criterion, run.tol, with_map, run.relax, late_status, frame_status,
                                from_label ? deferred_label : nullptr, deferred_tbl.v, conv_out(), stream,
                                by_word ? done_word : nullptr, done_epoch);
     } else {
-        shape = launch_frame(crf, kdevs.data(), n_iter, with_map, relax, late_status, frame_status,
+        shape = launch_frame(crf, kdevs.data(), run.n_iter, with_map, run.relax, late_status, frame_status,
                              from_label ? deferred_label : nullptr, deferred_tbl.v, stream, frame_small_ok, dual, dual_epoch,
                              by_word ? done_word : nullptr, done_epoch, frame_lean_ok ? lean_rec : nullptr);
     }
@@ -781,14 +783,9 @@ int Engine::run_frame(int n_iter, int with_map, float relax, const StopRule *sto
     engine_shape = 0;
     conv_engine = stop ? 3 : 0;
     if (stop) conv_valid = true;
-    late_conv = stop != nullptr;
-    late_criterion = stop ? stop->criterion : 0;
-    late_tol = stop ? stop->tol : 0.0f;
+    late = run;
 
     flight = by_label ? Flight::kPendingLabels : by_word ? Flight::kPendingDone : Flight::kPending;
-    late_iter = n_iter;
-    late_map = with_map;
-    late_relax = relax;
     started = true;
     engine_used = 3;
     last_with_map = with_map;
@@ -804,7 +801,8 @@ int Engine::inference(int n_iter, int with_map, float relax)
     if (rc) return rc;
     // Object API: nothing has been built yet (add_pairwise only stages features) -> do not build, run the
     // frame in one launch.  If a probe already forced the lattices into HBM, iterate on those instead.
-    if (late_ok && frame_ok() && !(built_upto == (int)kernels.size() && sizes_known)) return run_frame(n_iter, with_map, relax);
+    if (late_ok && frame_ok() && !(built_upto == (int)kernels.size() && sizes_known))
+        return run_frame({n_iter, with_map, relax, false, 0, 0.0f});
     return inference_sized(n_iter, with_map, relax, kMayReorder);   // (large frames: lattices built from here may use locality mode)
 }
 
@@ -843,7 +841,7 @@ int Engine::run(int n_iter, int with_map, float relax)
     if (!unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
     int rc = resolve_late();
     if (rc) return rc;
-    if (frame_ok()) return run_frame(n_iter, with_map, relax);
+    if (frame_ok()) return run_frame({n_iter, with_map, relax, false, 0, 0.0f});
     invalidate_lattices();                            // two-kernel path: rebuild for the current inputs, then infer
     return inference_sized(n_iter, with_map, relax);
 }
@@ -964,7 +962,7 @@ int Engine::inference_converged(int max_iter, int criterion, float tol, int with
 }
 
 // lccrf_run_converged / lccrf_batch_run_converged (sections 1i and 2f): from inputs alone.  A frame the one-launch kernel takes is
-// built, normalised and inferred until converged in ONE launch (run_frame with a stop rule: what it leaves is run_frame's, plus the
+// built, normalised and inferred until converged in ONE launch (run_frame with until_converged: what it leaves is run_frame's, plus the
 // report); whether every frame fitted is known at the next synchronisation point, where resolve_late() re-runs the flagged ones with
 // inference_converged().  Anything else builds into HBM and takes inference_converged() at once -- as does a handle whose lattices
 // are already built and sized (a probe put them there), the rule of Engine::inference.
@@ -975,10 +973,7 @@ int Engine::run_converged(int max_iter, int criterion, float tol, int with_map, 
     if (!unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
     if ((rc = resolve_late())) return rc;
     if (late_ok && built_upto == (int)kernels.size() && sizes_known) return inference_converged(max_iter, criterion, tol, with_map, relax);
-    if (frame_ok()) {
-        const StopRule stop{criterion, tol};
-        return run_frame(max_iter, with_map, relax, &stop);
-    }
+    if (frame_ok()) return run_frame({max_iter, with_map, relax, true, criterion, tol});
     invalidate_lattices();                            // two-kernel path: rebuild for the current inputs, then infer
     return inference_converged(max_iter, criterion, tol, with_map, relax);
 }
@@ -1096,8 +1091,8 @@ int Engine::resolve_late(bool *seen_done)
 // frames): the fixed count, or -- behind run_converged() -- the same stop rule.
 int Engine::rerun_on(Engine &e)
 {
-    if (late_conv) return e.inference_converged(late_iter, late_criterion, late_tol, late_map, late_relax);
-    return e.inference_sized(late_iter, late_map, late_relax);
+    if (late.until_converged) return e.inference_converged(late.n_iter, late.criterion, late.tol, late.with_map, late.relax);
+    return e.inference_sized(late.n_iter, late.with_map, late.relax);
 }
 
 // Two-kernel path for the frames fb_list_host[0, n) only, in a compact sub-engine; results scattered back.
@@ -1156,7 +1151,7 @@ int Engine::rerun_frames(int n)
     if (rc) return rc;
     const size_t qrow = (size_t)maxN * L * sizeof(float);
     launch_copy_frames(crf.Q, qrow, g.crf.Q, qrow, fb_list, n, qrow, 0, stream);
-    if (late_map) {
+    if (late.with_map) {
         launch_copy_frames(crf.map, (size_t)maxN * 2, g.crf.map, (size_t)maxN * 2, fb_list, n, (size_t)maxN * 2, 0, stream);
         if (crf.map_bits && g.crf.map_bits)
             launch_copy_frames(crf.map_bits, (size_t)crf.bits_stride * 8, g.crf.map_bits, (size_t)crf.bits_stride * 8, fb_list, n,
@@ -1164,7 +1159,7 @@ int Engine::rerun_frames(int n)
     }
     for (size_t k = 0; k < kernels.size(); ++k)
         launch_copy_frames(kernels[k].dev.V, 4, g.kernels[k].dev.V, 4, fb_list, n, 4, 0, stream);
-    if (late_conv)                                    // the re-run frames' reports: iterations, delta, changed, converged
+    if (late.until_converged)                         // the re-run frames' reports: iterations, delta, changed, converged
         for (int a = 0; a < 4; ++a)
             launch_copy_frames(conv_dev + (size_t)a * Fcap, 4, g.conv_dev + (size_t)a * g.Fcap, 4, fb_list, n, 4, 0, stream);
     HIP_TRY(hipGetLastError());

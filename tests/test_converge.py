@@ -174,6 +174,37 @@ def test_handle_stops_where_the_oracle_does(po, wl, name):
     h.close()
 
 
+# The self-contained prologue (csrc/fused_converge.hip, as in k_fused and k_general) keeps a lattice's tables in registers between its loads and its LDS stores: the neighbour table
+# of up to 4096 / 3 = 1365 vertices, the row pointers of up to 2047; what lies beyond is copied by two plain loops.  The SLAM frames
+# above stay below both (the smooth term's lattice stops growing near 1180 vertices: the image has no more cells), so one frame with
+# every point of its first term in a cell of its own (V = 3 N) is there for the loops: 683 points, the smallest with V > 2047.
+LARGE_N, LARGE_V = 683, (1365, 2047)
+
+
+def _vertices(po, pb):
+    o = cc.setup(po.OracleCRF, pb)
+    out = [o.kernel(k)["V"] for k in range(len(pb["kernels"]))]
+    o.close()
+    return out
+
+
+def test_lattices_lie_on_both_sides_of_the_prologues_register_rounds(po, wl):
+    assert all(max(_vertices(po, cv.problem(wl, name))) <= LARGE_V[0] for name in NAMES)
+    V = _vertices(po, cc.shaped_problem(wl, LARGE_N, "sparse", 5))
+    assert V[0] == 3 * LARGE_N > LARGE_V[1] >= 3 * (LARGE_N - 1) and V[1] <= LARGE_V[0], V
+
+
+@pytest.mark.gpu
+def test_handle_on_a_lattice_beyond_the_prologues_register_rounds(po, wl):
+    pb = cc.shaped_problem(wl, LARGE_N, "sparse", 5)
+    h = cc.setup(pkg.DenseCRFHIP, pb)
+    for relax in cv.RELAX:
+        tr = cv.oracle_trace(po, pb, relax, 2)
+        for crit in (cv.DELTA, cv.LABELS):
+            _check(h, tr, crit, F32(0), 2, relax, (2, 1024 | 1 << 16), "sparse:N%d" % LARGE_N)
+    h.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("N", (700, 2500))
 def test_one_point_decides_wherever_it_sits(po, wl, N):

@@ -166,6 +166,14 @@ def test_cases_are_there_for_both_row_paths_and_both_points_per_lane(po, wl, gol
     assert _prepared("N1025", golden, po, wl)[0]["N"] % LANES == 1 and _prepared("N5", golden, po, wl)[0]["N"] % 4 == 1
 
 
+def test_lattices_lie_on_both_sides_of_the_prologues_register_rounds(po, wl, golden):
+    """the self-contained prologue (csrc/fused_general.hip) keeps the neighbour table of up to 4096 / 3 = 1365 vertices and the row pointers of up to 2047 in
+    registers; two copy loops take what lies beyond: sparse:N1100 is there for both, every other case stays within both"""
+    V = {name: _prepared(name, golden, po, wl)[3][2] for name in {**CASES, **EXTRA}}
+    assert V["sparse:N1100"][0] > 2047 and V["sparse:N1100"][1] <= 1365, V["sparse:N1100"]
+    assert all(max(v) <= 1365 for name, v in V.items() if name != "sparse:N1100"), V
+
+
 # ---- GPU --------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("setting", SETTINGS)
