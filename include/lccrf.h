@@ -356,7 +356,8 @@ int  lccrf_inference_backward_features(lccrf_handle h, int n_iterations, float r
  * runs on the streaming engine with the matrix applied inside the slice kernel, which takes the Potts slice kernel's place: the
  * step issues no launch more than the streaming engine's general, L-label step (at L = 2 that is more than the two-label
  * specialisation issues).  The C++ mirror lccrf_densecrf.hpp sets a matrix per potential (PottsPotentialHIP::setCompatibility).
- * Not covered: the batch API has no setter; lccrf_densecrf_gpu.hpp is unchanged.  lccrf_inference_backward_features itself still returns
+ * The batch API has the same setter, one matrix per term shared by every frame (section 2g); the gradients of such a batch are not
+ * covered (sections 2c and 2d refuse it), and lccrf_densecrf_gpu.hpp is unchanged.  lccrf_inference_backward_features itself still returns
  * LCCRF_E_STATE on a handle with any matrix and leaves the handle as it was: the feature gradients of such a handle are
  * lccrf_inference_backward_all's (section 1f).                                                                                 */
 
@@ -466,8 +467,9 @@ int  lccrf_inference_backward_all(lccrf_handle h, int n_iterations, float relax,
  * lccrf_inference_backward_all with a non-NULL d_grad_features, return LCCRF_E_STATE on a handle with any term that is not AFTER and
  * leave the handle as it was.
  *
- * The C++ mirror lccrf_densecrf.hpp sets a mode per potential (PottsPotentialHIP::setNormalization).  Not covered: the batch API has
- * no setter (sections 2c and 2d keep every term AFTER); lccrf_densecrf_gpu.hpp is unchanged.
+ * The C++ mirror lccrf_densecrf.hpp sets a mode per potential (PottsPotentialHIP::setNormalization).  The batch API has the same
+ * setter, one mode per term shared by every frame (section 2g); the gradients of such a batch are not covered (sections 2c and 2d
+ * refuse a batch with a term that is not AFTER), and lccrf_densecrf_gpu.hpp is unchanged.
  *   - Memory: one [N] float array per SYMMETRIC term (s, formed from n on the handle's stream when first needed after a build or a
  *     mode change) and one [N] array of 1.0f per handle with a BEFORE or NONE term (what the slice reads where such a term has no
  *     post: w * 1.0f is exact); both stay with the handle.  Nothing is allocated for a handle that never calls the setter.      */
@@ -507,7 +509,10 @@ int  lccrf_get_pairwise_normalization(lccrf_handle h, int kernel, int *mode);
  * lccrf_get_engine reports 2 with the shape word.  Everything else -- other label counts or dimensions, more terms or points, a
  * term with a matrix (1e) or a normalisation mode (1g), locality mode, lattices beyond LDS -- runs the streaming engine's step
  * unchanged with a small comparison kernel behind each step; the host then reads ONE word per iteration (the number of frames still
- * running) behind a synchronisation of the call's stream.  lccrf_get_engine reports 1.  The lattices are built and sized exactly as
+ * running) behind a synchronisation of the call's stream.  lccrf_get_engine reports 1.  A HANDLE with a matrix or a mode takes this
+ * streaming step even where lccrf_inference runs it in one launch (engine 4): the one-launch kernel for such terms run until
+ * converged (csrc/fused_general_converge.hip) is taken by batches only (section 2g; a batch of max_frames = 1 included), and moving
+ * the handle's converged call onto it is the follow-up.  The lattices are built and sized exactly as
  * by lccrf_inference on built lattices; THIS call never takes the one-launch build + inference kernel (section 1i's
  * lccrf_run_converged does) and neither reads, writes nor invalidates prepared launch records.
  *
@@ -641,13 +646,15 @@ int  lccrf_batch_device_label_bits(lccrf_batch_handle b, const uint64_t **d_bits
 /* Engine selection for the inference loop (all give bit-identical results):
  *   0 = automatic, 1 = streaming kernels over HBM (any size), 2 = fused one-workgroup-
  *   per-frame kernel with the lattice values in LDS (SLAM sizes only).  lccrf_batch_get_engine
- *   also reports 3 = the one-launch-per-frame kernel of lccrf_batch_run.                */
+ *   also reports 3 = the one-launch-per-frame kernel of lccrf_batch_run, and 4 = the fused
+ *   engine's kernels for terms with a label-compatibility matrix or a normalisation mode
+ *   (section 2g: one 1024-lane workgroup per frame, fixed count or until converged).     */
 int  lccrf_batch_set_engine(lccrf_batch_handle b, int engine);
 int  lccrf_batch_get_engine(lccrf_batch_handle b, int *engine_in_use);
-/* Report only: the workgroup shape of the last one-workgroup-per-frame launch -- lccrf_batch_inference on the fused engine (engine 2)
- * or lccrf_batch_run's one-launch kernel (engine 3), whichever ran last -- as lanes per frame (1024 or 512) and how many frames
- * share a CU (1; 2 for the half-LDS plans: batches of at least 256 frames of up to 2048 points, csrc/fused_lean.h and
- * csrc/frame_lean.hip).  0 / 0 if no such launch happened yet.  Same results in every shape (the order of every row sum is the
+/* Report only: the workgroup shape of the last one-workgroup-per-frame launch -- lccrf_batch_inference on the fused engine (engine 2),
+ * lccrf_batch_run's one-launch kernel (engine 3) or section 2g's kernels (engine 4: always 1024 and 1), whichever ran last -- as
+ * lanes per frame (1024 or 512) and how many frames share a CU (1; 2 for the half-LDS plans: batches of at least 256 frames of up to
+ * 2048 points, csrc/fused_lean.h and csrc/frame_lean.hip).  0 / 0 if no such launch happened yet.  Same results in every shape (the order of every row sum is the
  * reference's, permutohedral_cpu.h:653-661).                                                                                   */
 int  lccrf_batch_get_fused_shape(lccrf_batch_handle b, int *lanes_per_frame, int *frames_per_cu);
 /* Report only: how the lattices now in HBM were built (after lccrf_batch_build) -- whether the points of a frame are processed in
@@ -730,7 +737,11 @@ int  lccrf_batch_set_unary_device(lccrf_batch_handle b, const float *d_unary);
  *     Zeroed when allocated, grown by the first call that needs more, freed by lccrf_batch_destroy; a failed allocation returns
  *     LCCRF_E_NOMEM and leaves the batch usable.  lccrf_batch_inference / _run never allocate it.
  *   - Errors: LCCRF_E_INVALID for n_iterations < 0, a relax that is not finite, or a device array section 1b refuses; a rejected
- *     call leaves the batch's inputs, lattices and Q as they were.  K = 0 is legal (d_grad_weights then receives nothing).       */
+ *     call leaves the batch's inputs, lattices and Q as they were.  K = 0 is legal (d_grad_weights then receives nothing).
+ *   - Potts terms normalised AFTER only: on a batch with a label-compatibility matrix or a mode other than AFTER (section 2g) this call
+ *     and section 2d's return LCCRF_E_STATE and leave the batch as it was.  The batch sweep has not been checked against a handle's
+ *     section 1e and 1g gradients frame by frame, and a silently wrong gradient is worse than none; the gradients of a learnt model
+ *     are a handle's (sections 1c - 1g).                                                                                          */
 int  lccrf_batch_inference_backward(lccrf_batch_handle b, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
                                     float *d_grad_weights, void *stream);
 
@@ -754,7 +765,9 @@ int  lccrf_batch_inference_backward_features(lccrf_batch_handle b, int n_iterati
  * Every other batch runs the streaming step for all frames until the last frame has finished (one word read by the host and one
  * synchronisation of the call's stream per iteration): a finished frame's Q is kept aside at the iteration it finished and put
  * back before the labels are formed -- stepping it further is wasted work, not a different result.  lccrf_batch_get_engine
- * reports 1.  LCCRF_E_STATE before lccrf_batch_build; the argument checks of section 1h.
+ * reports 1.  A batch whose terms carry a matrix or a mode (section 2g) runs in ONE launch as well where lccrf_batch_inference does
+ * (engine 4: up to 2048 points per frame), on csrc/fused_general_converge.hip; lccrf_batch_get_engine reports 4.
+ * LCCRF_E_STATE before lccrf_batch_build; the argument checks of section 1h.
  * ==================================================================================== */
 int  lccrf_batch_inference_converged(lccrf_batch_handle b, int max_iterations, int criterion, float tol, int with_map, float relax,
                                      void *stream);
@@ -780,6 +793,46 @@ int  lccrf_batch_device_convergence(lccrf_batch_handle b, const int32_t **d_iter
  * ==================================================================================== */
 int  lccrf_batch_run_converged(lccrf_batch_handle b, int max_iterations, int criterion, float tol, int with_map, float relax,
                                void *stream);
+
+/* ======================================================================================
+ * 2g. Label-compatibility matrices and normalisation modes of a batch -- sections 1e and 1g for every frame at once.  A learnt model
+ * (lc-crf-slam_amd/autograd.py: CompatMeanFieldCRF, LearnedCRF) is term weights, a matrix per term and a mode per term; it is global,
+ * so a batch holds ONE matrix and ONE mode per term, shared by every frame.  Meaning, arithmetic, argument checks and error codes are
+ * those of the handle's setters: finite entries, `kernel` a term of the batch, a mode in 0 .. 3, else LCCRF_E_INVALID (a mode outside
+ * 0 .. 3, a kernel index outside 0 .. LCCRF_MAX_KERNELS - 1 and a NULL `mode` are refused before the batch is looked at).  Added
+ * WITHOUT a step of LCCRF_ABI_VERSION (it stays 3): probe for these four by symbol.
+ *
+ * A setter changes no lattice and no norm; it may be called before or after lccrf_batch_build and between inferences, and a pending
+ * one-launch run is settled before it takes effect (as lccrf_batch_set_pairwise_weight does).  It does not touch the prepared
+ * launch records (lccrf_batch_last_prepare): those belong to the Potts, normalised-AFTER path, and a batch with a matrix or a mode
+ * neither reads, writes nor invalidates them.  Taking the last matrix and mode back returns the batch to the fast engines and to the
+ * bits it returned before.  A batch from lccrf_batch_create has no matrix and every term AFTER.
+ *
+ * Engines.  Per frame, Q, the labels and the label bits are bit for bit those of a handle holding that frame with the same settings.
+ *   - lccrf_batch_inference: two labels, one or two 2-D terms, up to 2048 points per frame (the largest n_points the host knows,
+ *     else max_points) and lattices that fit the fused engine's plan run in ONE launch, one 1024-lane workgroup per frame, on the
+ *     kernel a handle takes (csrc/fused_general.hip).  lccrf_batch_get_engine reports 4, lccrf_batch_get_fused_shape 1024 / 1.
+ *   - lccrf_batch_inference_converged (section 2e's contract, unchanged: every frame stops on its own): the same batches in ONE launch
+ *     on csrc/fused_general_converge.hip -- that kernel's loop with the stop decision inside; engine 4.  A batch created with
+ *     max_frames = 1 takes it too; a handle does not (section 1h).
+ *   - Every other batch -- 2049 points and more, other label counts or dimensions, three terms and more, lattices beyond one
+ *     workgroup's LDS, lccrf_batch_set_engine(1) -- runs the streaming engine's general L-label step for all frames (engine 1), the
+ *     converged call with section 2e's bookkeeping behind each step.
+ *   - lccrf_batch_run and lccrf_batch_run_converged on such a batch are lccrf_batch_build followed by the inference call: the
+ *     one-launch build + inference kernels hard-wire Potts.  lccrf_batch_get_fallback_frames reads 0.
+ * Not covered: gradients (lccrf_batch_inference_backward and lccrf_batch_inference_backward_features return LCCRF_E_STATE on such a
+ * batch and leave it as it was: section 2c) and a batched torch layer; the half-CU shapes (512 lanes, two frames per CU) and 3 - 4
+ * points per lane; prepared launch records for such batches; the handle's converged call.
+ * ==================================================================================== */
+/* compat: HOST [L][L], row-major as in section 1e, copied during the call and uploaded on the batch's stream; NULL removes the matrix. */
+int  lccrf_batch_set_pairwise_compatibility(lccrf_batch_handle b, int kernel, const float *compat);
+/* *is_set = 1 if term `kernel` has a matrix, else 0; compat_out (HOST [L][L], may be NULL) receives it -- the identity for a Potts
+ * term.  No device work.                                                                                                        */
+int  lccrf_batch_get_pairwise_compatibility(lccrf_batch_handle b, int kernel, float *compat_out, int *is_set);
+/* mode: an lccrf_normalization (section 1g).                                                                                     */
+int  lccrf_batch_set_pairwise_normalization(lccrf_batch_handle b, int kernel, int mode);
+/* *mode = the lccrf_normalization of term `kernel`.  No device work.                                                             */
+int  lccrf_batch_get_pairwise_normalization(lccrf_batch_handle b, int kernel, int *mode);
 
 /* ======================================================================================
  * 3. Unary builder -- the step right before the CRF (first "next" row):

@@ -177,6 +177,10 @@ def lib():
     L.lccrf_batch_set_unary_device.argtypes = [vp, vp]
     L.lccrf_batch_inference_backward.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, vp]
     L.lccrf_batch_inference_backward_features.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, C.POINTER(vp), vp]
+    L.lccrf_batch_set_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p]
+    L.lccrf_batch_get_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p, C.POINTER(C.c_int)]
+    L.lccrf_batch_set_pairwise_normalization.argtypes = [vp, C.c_int, C.c_int]
+    L.lccrf_batch_get_pairwise_normalization.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
     L.lccrf_bf_match.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_double, _i32p, _i32p]
     L.lccrf_pose_optimization.argtypes = [C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, C.c_void_p, _i16p, _f32p, C.c_float,
                                           _f32p, _f32p, C.c_void_p, _i32p]
@@ -672,6 +676,35 @@ class BatchCRF:
         _check(lib().lccrf_batch_inference_backward_features(self.h, int(n_iterations), float(relax), C.c_void_p(int(d_grad_prob)),
                                                              _addr(d_grad_unary), _addr(d_grad_weights), _addr_list(d_grad_features),
                                                              C.c_void_p(stream) if stream else None))
+
+    # -- label-compatibility matrices and normalisation modes (include/lccrf.h section 2g) ---------------------------------------
+    def set_pairwise_compatibility(self, k, compat):
+        """The [L][L] matrix mu of term k in every frame (DenseCRFHIP.set_pairwise_compatibility).  None: Potts again."""
+        if compat is None:
+            _check(lib().lccrf_batch_set_pairwise_compatibility(self.h, int(k), None))
+            return
+        m = _f32(compat).reshape(-1)
+        if m.size != self.L * self.L:
+            raise ValueError("compat must have L*L entries")
+        _check(lib().lccrf_batch_set_pairwise_compatibility(self.h, int(k), _p(m, _f32p)))
+
+    def pairwise_compatibility(self, k):
+        """(matrix [L][L], is_set) of term k; the identity for a term without a matrix."""
+        out = np.empty((self.L, self.L), np.float32)
+        flag = C.c_int(0)
+        _check(lib().lccrf_batch_get_pairwise_compatibility(self.h, int(k), _p(out, _f32p), C.byref(flag)))
+        return out, bool(flag.value)
+
+    def set_normalization(self, k, mode):
+        """Where term k applies its norm in every frame: NORMALIZE_AFTER (the default), _BEFORE, _SYMMETRIC or _NONE."""
+        _check(lib().lccrf_batch_set_pairwise_normalization(self.h, int(k), int(mode)))
+
+    def normalization(self, k):
+        mode = C.c_int(0)
+        _check(lib().lccrf_batch_get_pairwise_normalization(self.h, int(k), C.byref(mode)))
+        return mode.value
+
+    get_pairwise_compatibility, get_normalization = pairwise_compatibility, normalization   # (DenseCRFHIP's names)
 
     def set_engine(self, engine):
         _check(lib().lccrf_batch_set_engine(self.h, int(engine)))

@@ -64,6 +64,16 @@ static BackwardTarget backward_target(lccrf_batch *b, void *stream)
             "lccrf_batch_build or lccrf_batch_run has not run for these inputs", true, stream};
 }
 
+// Sections 2c and 2d differentiate Potts terms normalised AFTER: nobody has checked that the batch sweep gives each frame the bits of
+// a handle's section 1e and 1g gradients, and a silently wrong gradient is worse than none.  A batch with a matrix or another mode
+// (section 2g) is refused before anything is looked at or touched.
+static int batch_is_plain(const lccrf_batch *b)
+{
+    if (b->eng.n_compat) return fail(LCCRF_E_STATE, "batch gradients are not available while a term has a label-compatibility matrix");
+    if (b->eng.n_modes) return fail(LCCRF_E_STATE, "batch gradients are not available while a term is not normalised AFTER the filter");
+    return LCCRF_OK;
+}
+
 extern "C" {
 
 // --------------------------------------------------------------------------------------
@@ -129,6 +139,7 @@ int lccrf_batch_inference_backward(lccrf_batch_handle b, int n_iterations, float
                                    float *d_grad_weights, void *stream)
 {
     CHECK_H(b);
+    if (int rc = batch_is_plain(b)) return rc;
     const BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
     return backward_call(backward_target(b, stream), rq, kGradUnaryRequired);
 }
@@ -140,6 +151,7 @@ int lccrf_batch_inference_backward_features(lccrf_batch_handle b, int n_iteratio
                                             float *d_grad_unary, float *d_grad_weights, float *const *d_grad_features, void *stream)
 {
     CHECK_H(b);
+    if (int rc = batch_is_plain(b)) return rc;
     BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
     rq.grad_features = d_grad_features;
     return backward_call(backward_target(b, stream), rq, kGradUnaryOptional);

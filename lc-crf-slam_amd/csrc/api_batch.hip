@@ -6,6 +6,7 @@
 #include "api_common.h"
 
 #include <algorithm>
+#include <cmath>
 #include <condition_variable>
 #include <cstring>
 #include <mutex>
@@ -151,6 +152,7 @@ int lccrf_batch_create(lccrf_batch_handle *out, int device_id, const lccrf_batch
     if (!b) return fail(LCCRF_E_NOMEM, "host allocation failed");
     b->desc = *desc;
     b->eng.allow_perm = true;
+    b->eng.batch_owned = true;
     b->eng.opt_single_wg = default_single_wg();
     rc = b->eng.init(device_id, desc->max_frames, desc->max_points, desc->n_labels);
     for (int k = 0; k < desc->n_kernels && !rc; ++k) rc = b->eng.add_kernel(desc->feat_dims[k], desc->weights[k], true, false);
@@ -770,6 +772,64 @@ int lccrf_batch_set_unary_device(lccrf_batch_handle b, const float *d_unary)
     { int rl = e.resolve_late(); if (rl) return rl; }
     if (n) HIP_TRY(hipMemcpyAsync(e.unary_own, d_unary, n * sizeof(float), hipMemcpyDefault, e.stream));
     e.bind_unary(e.unary_own);                            // (drops label-derived and permuted unary state; lattices and records stay)
+    return LCCRF_OK;
+}
+
+// --------------------------------------------------------------------------------------
+// section 2g: the batch's label-compatibility matrices and normalisation modes -- sections 1e and 1g's setters, one matrix and one
+// mode per term for every frame.  Engine::set_compat / set_norm_mode touch no lattice, norm or prepared launch record.  What can be
+// checked without the batch -- a mode outside 0 .. 3, a kernel index no batch can have, a NULL output -- is checked before it is
+// looked at, so those answers need no device.
+#define CHECK_K_ANY(k)                                                                                      \
+    do {                                                                                                    \
+        if ((k) < 0 || (k) >= LCCRF_MAX_KERNELS) return fail(LCCRF_E_INVALID, "kernel index %d out of range", (k)); \
+    } while (0)
+
+int lccrf_batch_set_pairwise_compatibility(lccrf_batch_handle b, int kernel, const float *compat)
+{
+    CHECK_K_ANY(kernel);
+    CHECK_H(b);
+    CHECK_K(b, kernel);
+    Engine &e = b->eng;
+    for (int i = 0; compat && i < e.L * e.L; ++i)
+        if (!std::isfinite(compat[i])) return fail(LCCRF_E_INVALID, "compat[%d][%d] is not finite", i / e.L, i % e.L);
+    { int rl = e.resolve_late(); if (rl) return rl; }   // (a pending one-launch run may still re-run frames: as the Potts model it was asked with)
+    return e.set_compat(kernel, compat);
+}
+
+int lccrf_batch_get_pairwise_compatibility(lccrf_batch_handle b, int kernel, float *compat_out, int *is_set)
+{
+    CHECK_K_ANY(kernel);
+    CHECK_H(b);
+    CHECK_K(b, kernel);
+    const Engine &e = b->eng;
+    const bool set = e.compat_ptr[kernel] != nullptr;
+    if (is_set) *is_set = set ? 1 : 0;
+    for (int i = 0; compat_out && i < e.L * e.L; ++i)     // (a Potts term reads as the identity it is)
+        compat_out[i] = set ? e.compat_host[(size_t)kernel * e.L * e.L + i] : (i / e.L == i % e.L ? 1.0f : 0.0f);
+    return LCCRF_OK;
+}
+
+int lccrf_batch_set_pairwise_normalization(lccrf_batch_handle b, int kernel, int mode)
+{
+    if (mode < LCCRF_NORMALIZE_AFTER || mode > LCCRF_NORMALIZE_NONE)
+        return fail(LCCRF_E_INVALID, "normalization mode %d is none of LCCRF_NORMALIZE_AFTER / _BEFORE / _SYMMETRIC / _NONE", mode);
+    CHECK_K_ANY(kernel);
+    CHECK_H(b);
+    CHECK_K(b, kernel);
+    Engine &e = b->eng;
+    { int rl = e.resolve_late(); if (rl) return rl; }   // (a pending one-launch run may still re-run frames: with the modes it was asked with)
+    e.set_norm_mode(kernel, mode);
+    return LCCRF_OK;
+}
+
+int lccrf_batch_get_pairwise_normalization(lccrf_batch_handle b, int kernel, int *mode)
+{
+    if (!mode) return fail(LCCRF_E_INVALID, "mode is NULL");
+    CHECK_K_ANY(kernel);
+    CHECK_H(b);
+    CHECK_K(b, kernel);
+    *mode = b->eng.norm_mode[kernel];
     return LCCRF_OK;
 }
 

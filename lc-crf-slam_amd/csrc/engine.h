@@ -338,7 +338,8 @@ int launch_inference_fused(const CrfDev &c, const KernelDev *kds, const int *max
 inline int fused_report(int lanes, int ppt, int chain0) { return lanes | ppt << 16 | (chain0 ? 1 << 20 : 0); }
 
 // ---- the fused engine's inference with per-term matrices and factors (fused_general.hip; include/lccrf.h sections 1e and 1g) ----
-// One frame (c.F == 1) of at most 2048 active points, L = 2, one or two 2-D terms on lattices that fit the fused plan, in ONE launch.
+// The c.F frames of a handle (one) or a batch, each of at most 2048 active points, L = 2, one or two 2-D terms on lattices that fit
+// the fused plan, in ONE launch: a 1024-lane workgroup per frame.
 //   kds     the caller's copies whose `norm` points at each term's factor behind the filter (as launch_step_stream takes them)
 //   compat  null, or K HOST pointers: term k's [2][2] matrix or null -- passed to the kernel by value
 //   pre     null, or K device pointers: the [F][maxN] factor of term k's filter input or null
@@ -360,6 +361,11 @@ struct ConvergeOut {
 // words in LDS -- and nothing was launched.
 int launch_inference_converged(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, int max_iter, int criterion,
                                float tol, int with_map, float relax, const ConvergeOut &out, hipStream_t s);
+// The two at once (fused_general_converge.hip): launch_inference_general's frames, terms and arguments under launch_inference_converged's
+// stop rule and report.  Returns fused_report() of what it launched, or 0 -- a plan without room for the reduction's words included.
+int launch_inference_general_converged(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow,
+                                       const float *const *compat, const float *const *pre, int max_iter, int criterion, float tol,
+                                       int with_map, float relax, const ConvergeOut &out, hipStream_t s);
 // ... and for everything else, the bookkeeping behind each step of the streaming engine (converge_track.hip): per frame the kept
 // copy of the previous Q (`prev`, [F][maxN][L] -- which IS the frame's Q at the iteration it finished, since a finished frame's
 // copy is no longer refreshed), the accumulators of the iteration, and whether the frame has finished.

@@ -1,8 +1,8 @@
-// fused_general.hip -- the fused engine's inference (fused_engine.hip: one launch, one 1024-lane workgroup, the mean-field state on
-// chip) for the two-label handle whose terms are not all Potts terms normalised AFTER the filter: per term an optional 2 x 2
+// fused_general.hip -- the fused engine's inference (fused_engine.hip: one launch, one 1024-lane workgroup per frame, the mean-field
+// state on chip) for the two-label handle or batch whose terms are not all Potts terms normalised AFTER the filter: per term an optional 2 x 2
 // label-compatibility matrix (include/lccrf.h section 1e), a per-point factor in front of the filter and one behind it (section 1g).
 //
-// Why: such a handle used to leave the one-workgroup engines for the streaming engine's general L-label step -- one splat, d + 1
+// Why: such a handle (and such a batch, include/lccrf.h section 2g) used to leave the one-workgroup engines for the streaming engine's general L-label step -- one splat, d + 1
 // blur passes and one slice per term plus a softmax, 11 launches per iteration for the tracker's two 2-D terms, 57 for
 // inference(5, true) -- where a launch-per-phase design is bound by launch gaps.  notes/fused_general.md.
 //
@@ -13,9 +13,10 @@
 //     s_l  = 0; s_l = s_l + mu[l][0] * t[0]; s_l = s_l + mu[l][1] * t[1]   behind the slice t of a term with a matrix
 //     next_l += wn * s_l,  wn = w * post[i]                           (post: n, sqrtf(n), or 1.0f for BEFORE / NONE)
 //
-// Scope: a handle's single frame of up to 2 x 1024 active points, K in {1, 2} 2-D terms, kernel 0 with short rows or chain rows,
-// the self-contained prologue only (prepared launch records are the batches', which have no setters): 8 instantiations, kept in a
-// unit of their own so that the fused engine's kernels compile exactly as they did.
+// Scope: frames of up to 2 x 1024 active points -- a handle's one, or every frame of a batch, indexed by blockIdx.x -- K in {1, 2} 2-D
+// terms, kernel 0 with short rows or chain rows, the self-contained prologue only (prepared launch records belong to the batches' Potts
+// path and are neither read nor written here): 8 instantiations, kept in a unit of their own so that the fused engine's kernels compile
+// exactly as they did.  Run until converged: fused_general_converge.hip.
 #include "engine.h"
 #include "device_math.h"
 #include "fused_loop.h"
@@ -159,17 +160,17 @@ __global__ void __launch_bounds__(kNT, 4) k_general(CrfDev c, GeneralArgs a)
 
 }  // namespace
 
-// One frame (c.F == 1) of at most 2048 active points on lattices that fit the fused plan, with per-term matrices / factors:
+// The c.F frames of a handle or a batch, one workgroup each, of at most 2048 active points on lattices that fit the fused plan, with
+// per-term matrices / factors:
 //   kds      Engine::step_kdevs() -- `norm` is each term's factor behind the filter
 //   compat   K host pointers: term k's [2][2] matrix as it was set, or null (null: no term has one)
 //   pre      K device pointers: term k's factor in front of the filter, or null (null: no term has one)
-// Returns the shape it launched -- lanes | points per lane << 16 | kernel 0 on chain rows << 20 -- or 0 when the frame is not one
+// Returns the shape it launched -- lanes | points per lane << 16 | kernel 0 on chain rows << 20 -- or 0 when the frames are not ones
 // this kernel takes (nothing launched).
 int launch_inference_general(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const float *const *compat,
                              const float *const *pre, int n_iter, int with_map, float relax, hipStream_t s)
 {
     GeneralArgs a{};
-    if (c.F != 1) return 0;
     a.n_iter = n_iter;
     a.with_map = with_map;
     a.relax = relax;

@@ -667,6 +667,7 @@ __device__ __forceinline__ void mean_field(unsigned char *smem, const FusedLayou
         }
         for (int it = 0; it < n_iter; ++it) {
             opaque(pr);
+            if constexpr (GEN && CONV) asm volatile("" : "+v"(tid));
             splat_blur<PPT, K, CH, false, NT, (1 << K) - 1, REV, GEN>(smem, lay, V, N, tid, pr, cl, ins, gt);
             const bool more = it + 1 < n_iter;
 #pragma unroll
@@ -689,6 +690,7 @@ __device__ __forceinline__ void mean_field(unsigned char *smem, const FusedLayou
     }
     for (int it = 0; it < n_iter; ++it) {
         opaque(pr);
+        if constexpr (GEN && CONV) asm volatile("" : "+v"(tid));
         splat_blur<PPT, K, CH, true, NT, (1 << K) - 1, REV, GEN>(smem, lay, V, N, tid, pr, cl, ins, gt);
 #pragma unroll
         for (int s = 0; s < PPT; ++s)

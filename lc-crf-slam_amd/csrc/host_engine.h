@@ -121,7 +121,8 @@ struct Engine {
 
     // ---- engine choice ----
     int engine_pref = 0, engine_used = 1;   // engine_used is REPORT-only state (lccrf_batch_get_engine, lccrf_get_engine): 1 streaming, 2 fused,
-                                            //   3 one launch per frame, 4 the fused engine's kernel with matrices and factors (fused_general.hip)
+                                            //   3 one launch per frame, 4 the fused engine's kernels with matrices and factors
+                                            //   (fused_general.hip, fused_general_converge.hip)
     int sized_engine = 1;              // what choose_sized_engine() chose for inference on lattices that sit in HBM (1, 2 or 4)
     int engine_shape = 0;              // report only (lccrf_get_engine): fused_report() of the last inference on engine 2 or 4, else 0
     int last_with_map = 0;             // did the last inference produce MAP labels?
@@ -129,6 +130,7 @@ struct Engine {
     int fused_shape = 0;               // report only: what the last fused inference launched (launch_inference_fused)
     LeanPrep lean_prep;                // prepared launch records of the two-frames-per-CU inference kernel (engine.h)
     bool fused_fits = false;           // learn_sizes(): the lattices now in HBM fit the fused engine
+    bool batch_owned = false;          // set by lccrf_batch_create: the engine of a batch (whatever its frame count), not of a handle
 
     // ---- deferred unaries ----
     // setUnaryEnergyFromLabel is deferred: the labels wait in pinned memory and either the late-bound
@@ -225,10 +227,11 @@ struct Engine {
     size_t bwd_area_bytes = 0;
 
     // ---- compatibility matrices ----
-    // section 1e (object API; a batch has none): the terms' label-compatibility matrices.  One device array for all of them,
-    // allocated by the first setter and kept with the handle; compat_ptr[k] is term k's [L][L] slice of it, or null (Potts).
-    // While n_compat > 0 the one-launch frame kernel and the fused engine, which hard-wire Potts, are not taken; the frames
-    // choose_sized_engine() names run on the fused engine's general kernel, which takes the matrices by value from compat_host.
+    // sections 1e (a handle) and 2g (a batch: one matrix per term, shared by every frame): the terms' label-compatibility matrices.
+    // One device array for all of them, allocated by the first setter and kept with the handle or batch; compat_ptr[k] is term k's
+    // [L][L] slice of it, or null (Potts).  While n_compat > 0 the one-launch frame kernel and the fused engine, which hard-wire
+    // Potts, are not taken (nor their prepared launch records touched); the frames choose_sized_engine() names run on the fused
+    // engine's general kernels, which take the matrices by value from compat_host.
     float *compat_dev = nullptr;       // [LCCRF_MAX_KERNELS][L][L]
     float *compat_host = nullptr;      // pinned, the same shape: the matrices as set (the getter's answer and the uploads' source)
     hipEvent_t compat_ev = nullptr;    // behind the last upload: a setter waits for it before it rewrites a source that may be in flight
@@ -236,9 +239,10 @@ struct Engine {
     int n_compat = 0;
 
     // ---- normalisation modes ----
-    // section 1g (object API; a batch has none): where each term applies its norm -- after the filter (the reference's form and the
-    // default), before it, half on either side, or not at all.  While n_modes > 0 the one-launch frame kernel and the fused engine
-    // are not taken and the streaming engine's general branch -- or the fused engine's general kernel -- runs on kdevs_post, the
+    // sections 1g (a handle) and 2g (a batch: one mode per term, shared by every frame): where each term applies its norm -- after the
+    // filter (the reference's form and the default), before it, half on either side, or not at all.  While n_modes > 0 the one-launch
+    // frame kernel and the fused engine are not taken and the streaming engine's general branch -- or one of the fused engine's
+    // general kernels -- runs on kdevs_post, the
     // copy of kdevs whose `norm` points at each term's factor BEHIND the filter, with pre_ptr[k] the factor of its input
     // (kStepViews, behind kSized).
     int norm_mode[LCCRF_MAX_KERNELS] = {};   // lccrf_normalization of every term
@@ -257,7 +261,7 @@ struct Engine {
     int *conv_host = nullptr;          // pinned [4][Fcap]
     int *conv_running = nullptr;       // pinned [1]
     bool conv_valid = false;           // a converged run has reported on the current inputs
-    int conv_engine = 0;               // report only (lccrf_batch_get_engine): 3 / 2 / 1 when the last inference was a converged one, else 0
+    int conv_engine = 0;               // report only (lccrf_batch_get_engine): 4 / 3 / 2 / 1 when the last inference was a converged one, else 0
     ConvergeOut conv_out() const
     {
         return ConvergeOut{conv_dev, reinterpret_cast<float *>(conv_dev + Fcap), conv_dev + 2 * (size_t)Fcap, conv_dev + 3 * (size_t)Fcap};
@@ -323,13 +327,19 @@ struct Engine {
     int rerun_frames(int n);
 
     const float *const *compat_arg() const { return n_compat ? compat_ptr : nullptr; }
-    // Lattices that fit the fused plan: Potts terms normalised AFTER run on the fused engine; a handle's single frame of up to
-    // kGeneralMaxPoints active points with a matrix or another mode on the general kernel; anything else streams.
+    // Lattices that fit the fused plan: Potts terms normalised AFTER run on the fused engine; frames -- a handle's one or a batch's
+    // F -- of up to kGeneralMaxPoints active points with a matrix or another mode on the general kernel; anything else streams.
     static constexpr int kGeneralMaxPoints = 2048;
     void choose_sized_engine()
     {
         const bool general = n_compat || n_modes;
-        sized_engine = !fused_fits ? 1 : !general ? 2 : (F == 1 && active_points(crf) <= kGeneralMaxPoints) ? 4 : 1;
+        sized_engine = !fused_fits ? 1 : !general ? 2 : active_points(crf) <= kGeneralMaxPoints ? 4 : 1;
+    }
+    // the matrices as the general kernels take them: K host pointers into compat_host (null: a Potts term), or null when no term has one
+    const float *const *host_matrices(const float *(&mats)[LCCRF_MAX_KERNELS]) const
+    {
+        for (size_t k = 0; k < kernels.size(); ++k) mats[k] = compat_ptr[k] ? compat_host + k * (size_t)L * L : nullptr;
+        return n_compat ? mats : nullptr;
     }
     // what the streaming step, the plug-in filter and the backward sweep are handed (valid behind kStepViews)
     const KernelDev *step_kdevs() const { return n_modes ? kdevs_post.data() : kdevs.data(); }

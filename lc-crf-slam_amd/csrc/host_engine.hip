@@ -112,7 +112,9 @@ int Engine::ensure_factors()
             if (!ones) {
                 int rc = mem.alloc(&ones, np, false);
                 if (rc) { ones = nullptr; return rc; }
-                launch_norm_factor(crf, nullptr, ones, 0, stream);
+                CrfDev all = crf;                          // every frame the engine can hold: a batch's next inputs may bind more
+                all.F = Fcap;                              //   frames than its first (a handle has one)
+                launch_norm_factor(all, nullptr, ones, 0, stream);
             }
             if (mode == LCCRF_NORMALIZE_BEFORE) pre_ptr[k] = ks.dev.norm;
             kdevs_post[k].norm = ones;
@@ -882,13 +884,14 @@ int Engine::inference_sized(int n_iter, int with_map, float relax, unsigned more
                                              prep_need ? &lean_prep : nullptr, &engine_shape);
         started = true;
     } else if (sized_engine == 4) {
-        // the fused engine's general kernel (fused_general.hip), behind ensure_factors(): one launch on the factors' views; the
-        // matrices travel by value, from the pinned copies the setters keep
+        // the fused engine's general kernel (fused_general.hip), behind ensure_factors(): one launch on the factors' views, a
+        // workgroup per frame; the matrices travel by value, from the pinned copies the setters keep.  The prepared launch records
+        // (lean_prep) are the Potts path's: not looked at here
         const float *mats[LCCRF_MAX_KERNELS] = {};
-        for (size_t k = 0; k < kernels.size(); ++k) mats[k] = compat_ptr[k] ? compat_host + k * (size_t)L * L : nullptr;
-        engine_shape = launch_inference_general(crf, step_kdevs(), maxV.data(), maxRow.data(), n_compat ? mats : nullptr, pre_arg(),
+        engine_shape = launch_inference_general(crf, step_kdevs(), maxV.data(), maxRow.data(), host_matrices(mats), pre_arg(),
                                                 n_iter, with_map, relax, stream);
         if (!engine_shape) return fail(LCCRF_E_STATE, "the fused engine's general kernel was chosen for a frame it does not take");
+        fused_shape = 1024 | 1 << 16;                      // lanes per frame | frames per CU
         started = true;
     }
     HIP_TRY(hipGetLastError());
@@ -933,8 +936,9 @@ int Engine::check_converged_args(int max_iter, int criterion, float tol, float r
 }
 
 // On lattices in HBM, built and sized as inference_sized() does it (never the one-launch build + inference kernel, and the prepared
-// launch records are left alone): the frames the fused plan takes in ONE launch with the stop decision inside the kernel, the rest
-// on the streaming step with the bookkeeping of converge_track.hip behind it.
+// launch records are left alone): the frames the fused plan takes in ONE launch with the stop decision inside the kernel -- Potts
+// terms normalised AFTER on k_converge, a batch's terms with a matrix or a mode on k_general_converge -- the rest on the streaming
+// step with the bookkeeping of converge_track.hip behind it.
 int Engine::inference_converged(int max_iter, int criterion, float tol, int with_map, float relax)
 {
     int rc = check_converged_args(max_iter, criterion, tol, relax);
@@ -950,6 +954,21 @@ int Engine::inference_converged(int max_iter, int criterion, float tol, int with
             HIP_TRY(hipGetLastError());
             engine_used = conv_engine = 2;
             engine_shape = shape;
+            started = conv_valid = true;
+            return LCCRF_OK;
+        }
+    }
+    // A BATCH whose terms carry a matrix or a mode, on the frames choose_sized_engine() names: fused_general_converge.hip, one launch
+    // on the factors' views (kStepViews above).  A handle's converged call keeps the streaming step (include/lccrf.h section 1h).
+    if (sized_engine == 4 && !perm_on && (F > 1 || batch_owned)) {
+        const float *mats[LCCRF_MAX_KERNELS] = {};
+        const int shape = launch_inference_general_converged(crf, step_kdevs(), maxV.data(), maxRow.data(), host_matrices(mats), pre_arg(),
+                                                             max_iter, criterion, tol, with_map, relax, conv_out(), stream);
+        if (shape) {                                       // (0: a plan without room for the reduction's words streams)
+            HIP_TRY(hipGetLastError());
+            engine_used = conv_engine = 4;
+            engine_shape = shape;
+            fused_shape = 1024 | 1 << 16;
             started = conv_valid = true;
             return LCCRF_OK;
         }
