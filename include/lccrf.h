@@ -674,6 +674,18 @@ typedef struct lccrf_splat_plan {
 } lccrf_splat_plan;
 int  lccrf_batch_get_splat_plan(lccrf_batch_handle b, int kernel, lccrf_splat_plan *out);
 int  lccrf_get_splat_plan(lccrf_handle h, int kernel, lccrf_splat_plan *out);
+/* Report only, under the same conditions: which way each of the d + 1 blur passes of term `kernel` goes in the two-label mean-field
+ * step (Potts terms normalised after the filter), as counts of passes per route -- in_splat (taken along by the splat, = the splat
+ * plan's `passes`), paired_table / paired_plain (two passes per launch, off the two-hop neighbour table or without one; always
+ * even), alone_32bit / alone_compact (a launch per pass, on the 32-bit neighbour ids or the compact 16-bit table of the sorted
+ * build) and in_slice (the last pass, inside the slice: 0 or 1).  The six add up to d + 1.  nontemporal: the alone_32bit passes
+ * load their table non-temporally (0 when there is none).  first_table_pair: index in the two-hop table of the first pair read
+ * from it, -1 when no pass is.  Same results on every route.                                                                  */
+typedef struct lccrf_blur_plan {
+    int32_t in_splat, paired_table, paired_plain, alone_32bit, alone_compact, in_slice, nontemporal, first_table_pair;
+} lccrf_blur_plan;
+int  lccrf_batch_get_blur_plan(lccrf_batch_handle b, int kernel, lccrf_blur_plan *out);
+int  lccrf_get_blur_plan(lccrf_handle h, int kernel, lccrf_blur_plan *out);
 
 /* Measurement support for bench.py: HIP-event time of the last lccrf_batch_inference()
  * on its stream, the number of launches of the dominant kernel and their summed

@@ -58,6 +58,15 @@ class SplatPlan(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class BlurPlan(C.Structure):
+    """lccrf_blur_plan"""
+    _fields_ = [(n, C.c_int32) for n in ("in_splat", "paired_table", "paired_plain", "alone_32bit", "alone_compact", "in_slice",
+                                         "nontemporal", "first_table_pair")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class BatchDesc(C.Structure):
     _fields_ = [("max_frames", C.c_int), ("max_points", C.c_int), ("n_labels", C.c_int),
                 ("n_kernels", C.c_int), ("feat_dims", C.c_int * MAX_KERNELS),
@@ -168,6 +177,8 @@ def lib():
     L.lccrf_batch_get_locality_mode.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lccrf_batch_get_splat_plan.argtypes = [vp, C.c_int, C.POINTER(SplatPlan)]
     L.lccrf_get_splat_plan.argtypes = [vp, C.c_int, C.POINTER(SplatPlan)]
+    L.lccrf_batch_get_blur_plan.argtypes = [vp, C.c_int, C.POINTER(BlurPlan)]
+    L.lccrf_get_blur_plan.argtypes = [vp, C.c_int, C.POINTER(BlurPlan)]
     L.lccrf_batch_pose_set_crf_counts.argtypes = [vp, vp]
     L.lccrf_batch_last_timing.argtypes = [vp, _f32p, _f32p]
     L.lccrf_batch_last_prepare.argtypes = [vp, _f32p, C.POINTER(C.c_int)]
@@ -286,6 +297,13 @@ class DenseCRFHIP:
         vertices_per_lane, long_mode)."""
         p = SplatPlan()
         _check(lib().lccrf_get_splat_plan(self.h, int(k), C.byref(p)))
+        return p.as_dict()
+
+    def blur_plan(self, k):
+        """Which way the d + 1 blur passes of term k go in the two-label step for the lattices now in HBM (lccrf_blur_plan): dict(in_splat,
+        paired_table, paired_plain, alone_32bit, alone_compact, in_slice, nontemporal, first_table_pair)."""
+        p = BlurPlan()
+        _check(lib().lccrf_get_blur_plan(self.h, int(k), C.byref(p)))
         return p.as_dict()
 
     # -- inference ---------------------------------------------------------------------
@@ -731,6 +749,13 @@ class BatchCRF:
         vertices_per_lane, long_mode)."""
         p = SplatPlan()
         _check(lib().lccrf_batch_get_splat_plan(self.h, int(k), C.byref(p)))
+        return p.as_dict()
+
+    def blur_plan(self, k):
+        """Which way the d + 1 blur passes of term k go in the two-label step for the lattices now in HBM (lccrf_blur_plan): dict(in_splat,
+        paired_table, paired_plain, alone_32bit, alone_compact, in_slice, nontemporal, first_table_pair)."""
+        p = BlurPlan()
+        _check(lib().lccrf_batch_get_blur_plan(self.h, int(k), C.byref(p)))
         return p.as_dict()
 
     def fallback_frames(self):

@@ -689,6 +689,20 @@ int lccrf_batch_get_splat_plan(lccrf_batch_handle b, int kernel, lccrf_splat_pla
     return LCCRF_OK;
 }
 
+int lccrf_batch_get_blur_plan(lccrf_batch_handle b, int kernel, lccrf_blur_plan *out)
+{
+    CHECK_H(b);
+    CHECK_K(b, kernel);
+    if (!out) return fail(LCCRF_E_INVALID, "out is NULL");
+    Engine &e = b->eng;
+    if (e.built) {                                      // (the plan is made from what the build measured: kSized)
+        int rc = e.make_ready(Engine::kSized);
+        if (rc) return rc;
+    }
+    *out = blur_plan(e.kernels[kernel].dev, e.crf.F, e.kernels[kernel].maxV).counts;     // (what launch_step_stream is given)
+    return LCCRF_OK;
+}
+
 int lccrf_batch_get_stream(lccrf_batch_handle b, void **stream)
 {
     CHECK_H(b);

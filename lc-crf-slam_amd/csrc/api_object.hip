@@ -533,6 +533,17 @@ int lccrf_get_splat_plan(lccrf_handle h, int kernel, lccrf_splat_plan *out)
     return LCCRF_OK;
 }
 
+int lccrf_get_blur_plan(lccrf_handle h, int kernel, lccrf_blur_plan *out)
+{
+    CHECK_H(h);
+    CHECK_K(h, kernel);
+    if (!out) return fail(LCCRF_E_INVALID, "out is NULL");
+    Engine &e = h->eng;
+    { int rc = e.make_ready(Engine::kSettled | Engine::kSized); if (rc) return rc; }   // (builds staged lattices, the plain way)
+    *out = blur_plan(e.kernels[kernel].dev, e.crf.F, e.kernels[kernel].maxV).counts;     // (what launch_step_stream is given)
+    return LCCRF_OK;
+}
+
 int lccrf_get_norm(lccrf_handle h, int kernel, float *norm_out)
 {
     CHECK_H(h);

@@ -179,6 +179,89 @@ inline void report_splat_plan(const KernelDev &kd, int F, lccrf_splat_plan *out)
     }
 }
 
+// The two-label step's BLUR plan: which way each of the d + 1 blur passes of a term goes, for the lattices now in HBM and F frames in
+// flight with at most maxV vertices each.  launch_step_stream (stream_filter.hip) launches from it and lccrf_get_blur_plan /
+// lccrf_batch_get_blur_plan report it: one rule for both, so the report cannot drift from what is launched.  Same bits on every route.
+constexpr int kSliceBlurMaxFrames = 1;       // the last blur pass inside the slice (k_slice2<D1, true>) when passes go one per launch, up to this many frames in flight (with the sorted build: two frames +2 % without it, four and eight +-0)
+constexpr int kPairFuseMaxFrames = 1;        // two passes per launch (measured: one C5 frame 52.5 -> 45.2 us per iteration; two or four frames in flight: +-0)
+// ... or, whatever the number of frames, when the launch is SMALL: up to ~0.7 M vertices over all frames (one C5 frame: 0.59 M; two: +-0)
+// the passes are launch- and latency-bound, e.g. 8 frames of 5000 points (30 000 vertices each): 9 launches of ~3.8 us per iteration
+constexpr long kPairFuseMaxVertices = 700000;
+// (a pass alone reads its table non-temporally: C5 with 5 / 6 / 7 frames in flight 23.7 -> 26.1 / 26.9 -> 25.7 / 27.0 -> 24.8 us per frame and iteration)
+constexpr int kBlurNtMinFrames = 6;
+static_assert(kNbrcMaxFrames < kBlurNtMinFrames, "the compact table is never read non-temporally: k_blur2c has no such form");
+// the A/B switches of the instrumented library that bear on the plan: same results either way
+struct BlurSwitches { bool no_pair_fuse, no_2hop_table, no_compact_nbr; };
+inline const BlurSwitches &blur_switches()
+{
+    static const BlurSwitches sw{ab_env("LCCRF_NO_PAIR_FUSE") != nullptr, ab_env("LCCRF_NO_2HOP_TABLE") != nullptr,
+                                 ab_env("LCCRF_NO_COMPACT_NBR") != nullptr};
+    return sw;
+}
+inline bool pair_fuse(int F, int maxV)
+{
+    if (blur_switches().no_pair_fuse) return false;
+    return F <= kPairFuseMaxFrames || (long)F * maxV <= kPairFuseMaxVertices;
+}
+// a pass with a launch of its own: off the compact table (sorted build, kNbrcMinFrames..kNbrcMaxFrames frames) or the 32-bit one ...
+inline bool blur_alone_compact(const KernelDev &kd) { return kd.nbrc && kd.nbrc_ok && !blur_switches().no_compact_nbr; }
+// ... which is then loaded non-temporally from this many frames on
+inline bool blur_alone_nontemporal(int F) { return F >= kBlurNtMinFrames; }
+enum BlurRoute : unsigned char {
+    kBlurInSplat,         // rides in the splat (splat_passes_taken)
+    kBlurPairTable,       // one of two passes in one launch off the two-hop table (k_blur2x2t)
+    kBlurPairPlain,       // ... without a table (k_blur2x2)
+    kBlurAlone32,         // a launch of its own on 32-bit ids (k_blur2<NT>)
+    kBlurAloneCompact,    // ... on the compact table (k_blur2c)
+    kBlurInSlice          // the last pass, inside the slice (k_slice2<D1, true>)
+};
+struct BlurPlan {
+    unsigned char route[kMaxD + 1];   // of pass j < D1
+    int table_pair[kMaxD + 1];        // kBlurPairTable, first pass of the pair: its index in KernelDev::nbr2
+    int table_pairs;                  // pairs the table holds per frame (the stride k_blur2x2t is given)
+    bool nontemporal;                 // the passes alone on 32-bit ids load their table non-temporally
+    lccrf_blur_plan counts;
+};
+inline BlurPlan blur_plan(const KernelDev &kd, int F, int maxV)
+{
+    BlurPlan p{};
+    const int D1 = kd.D1, j0 = splat_passes_taken(kd);
+    const bool pairs = pair_fuse(F, maxV);
+    // the pass left over by the pairs rides in the slice; with a few frames in flight (one pass per launch) the last pass does
+    // (j0 == d + 1: a 2-D lattice's three passes can all ride in the splat)
+    const bool in_slice = D1 <= 9 && j0 < D1 && (pairs ? ((D1 - j0) & 1) && D1 >= 3 : F <= kSliceBlurMaxFrames);
+    const int n_own = in_slice ? D1 - 1 : D1;                                      // blur passes with a launch of their own end here
+    const bool table = kd.nbr2 && kd.nbr2_ok && !blur_switches().no_2hop_table;
+    const bool compact = blur_alone_compact(kd);
+    lccrf_blur_plan &c = p.counts;
+    c.first_table_pair = -1;
+    p.table_pairs = (D1 - kd.nbr2_first) / 2;
+    for (int j = 0; j < j0; ++j) p.route[j] = kBlurInSplat;
+    c.in_splat = j0;
+    for (int j = j0; j < n_own;) {
+        if (pairs && j + 1 < n_own) {             // two passes per launch
+            const int jt = j - kd.nbr2_first;     // the table holds the pairs (first, first + 1), (first + 2, first + 3) ...
+            const bool t = table && jt >= 0 && !(jt & 1);
+            p.route[j] = p.route[j + 1] = t ? kBlurPairTable : kBlurPairPlain;
+            p.table_pair[j] = t ? jt / 2 : -1;
+            if (t && c.first_table_pair < 0) c.first_table_pair = jt / 2;
+            (t ? c.paired_table : c.paired_plain) += 2;
+            j += 2;
+        } else {
+            p.route[j] = compact ? kBlurAloneCompact : kBlurAlone32;
+            (compact ? c.alone_compact : c.alone_32bit) += 1;
+            j += 1;
+        }
+    }
+    if (in_slice) {
+        p.route[D1 - 1] = kBlurInSlice;
+        c.in_slice = 1;
+    }
+    p.nontemporal = blur_alone_nontemporal(F);
+    c.nontemporal = c.alone_32bit > 0 && p.nontemporal;
+    return p;
+}
+
 // scratch of the point sort (locality mode), owned by the engine
 struct SortScratch {
     int bits;             // bucket bits of the counting sort (8..16)

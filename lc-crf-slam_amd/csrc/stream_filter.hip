@@ -511,7 +511,7 @@ __global__ void __launch_bounds__(kBlock) k_blur2(KernelDev kd, const float *__r
 
 // The same pass off the COMPACT neighbour table of the sorted build (KernelDev::nbrc): 4 instead of 8 table bytes per vertex, the
 // ids rebuilt as base-of-the-block + 16-bit offset (0xffff = absent -> -1).  Same neighbours, same operations, same bits.
-template <bool NT>
+// (No non-temporal form: the table exists with up to kNbrcMaxFrames frames in flight, below kBlurNtMinFrames -- engine.h.)
 __global__ void __launch_bounds__(kBlock) k_blur2c(KernelDev kd, const float *__restrict__ src,
                                                    float *__restrict__ dst, int j, int F, XcdMap nb)
 {
@@ -528,7 +528,7 @@ __global__ void __launch_bounds__(kBlock) k_blur2c(KernelDev kd, const float *__
     const unsigned *tp = reinterpret_cast<const unsigned *>(kd.nbrc) + fj * kd.Epad + v;            // (v even: 8-byte aligned)
     if (v + 1 < V) {
         typedef unsigned lccrf_v2u __attribute__((ext_vector_type(2)));
-        const lccrf_v2u t = NT ? __builtin_nontemporal_load(reinterpret_cast<const lccrf_v2u *>(tp)) : *reinterpret_cast<const lccrf_v2u *>(tp);
+        const lccrf_v2u t = *reinterpret_cast<const lccrf_v2u *>(tp);
         const unsigned a0 = t.x & 0xffffu, b0 = t.x >> 16, a1 = t.y & 0xffffu, b1 = t.y >> 16;
         const int n0 = a0 == 0xffffu ? -1 : base.x + (int)a0, m0 = b0 == 0xffffu ? -1 : base.y + (int)b0;
         const int n1 = a1 == 0xffffu ? -1 : base.x + (int)a1, m1 = b1 == 0xffffu ? -1 : base.y + (int)b1;
@@ -596,31 +596,14 @@ __global__ void __launch_bounds__(kBlock) k_blur2x2t(KernelDev kd, const float *
     d[v] = make_float2(tv.x + 0.5f * (ta.x + tbv.x), tv.y + 0.5f * (ta.y + tbv.y));
 }
 
-constexpr int kSliceBlurMaxFrames = 1;       // the last blur pass inside the slice (k_slice2<D1, true>) when passes go one per launch, up to this many frames in flight (with the sorted build: two frames +2 % without it, four and eight +-0)
-constexpr int kPairFuseMaxFrames = 1;        // (measured: one C5 frame 52.5 -> 45.2 us per iteration; two or four frames in flight: +-0)
-// ... or, whatever the number of frames, when the launch is SMALL: up to ~0.7 M vertices over all frames (one C5 frame: 0.59 M; two: +-0)
-// the passes are launch- and latency-bound, e.g. 8 frames of 5000 points (30 000 vertices each): 9 launches of ~3.8 us per iteration
-constexpr long kPairFuseMaxVertices = 700000;
-inline bool pair_fuse(int F, int maxV)
-{
-    static const bool off = ab_env("LCCRF_NO_PAIR_FUSE") != nullptr;      // A/B switch: same results either way
-    if (off) return false;
-    return F <= kPairFuseMaxFrames || (long)F * maxV <= kPairFuseMaxVertices;
-}
-
-// (the table non-temporally: C5 with 5 / 6 / 7 frames in flight 23.7 -> 26.1 / 26.9 -> 25.7 / 27.0 -> 24.8 us per frame and iteration)
-constexpr int kBlurNtMinFrames = 6;
-inline void launch_blur2(const KernelDev &kd, const float *src, float *dst, int j, int F, int maxV, hipStream_t s)
+// a blur pass with a launch of its own, off the compact table or the 32-bit one (engine.h: blur_alone_compact, blur_alone_nontemporal)
+inline void launch_blur2(const KernelDev &kd, const float *src, float *dst, int j, int F, int maxV, bool compact, bool nt, hipStream_t s)
 {
     XcdMap nb;
     const int blk = iter_block(F);
     const dim3 g = grid_xcd((maxV + 1) / 2, F, &nb, blk);
-    static const bool no_compact = ab_env("LCCRF_NO_COMPACT_NBR") != nullptr;      // A/B switch: same results either way
-    const bool nt = F >= kBlurNtMinFrames;
-    if (kd.nbrc && kd.nbrc_ok && !no_compact) {
-        if (nt) k_blur2c<true><<<g, blk, 0, s>>>(kd, src, dst, j, F, nb);
-        else k_blur2c<false><<<g, blk, 0, s>>>(kd, src, dst, j, F, nb);
-    } else if (nt) k_blur2<true><<<g, blk, 0, s>>>(kd, src, dst, j, F, nb);
+    if (compact) k_blur2c<<<g, blk, 0, s>>>(kd, src, dst, j, F, nb);
+    else if (nt) k_blur2<true><<<g, blk, 0, s>>>(kd, src, dst, j, F, nb);
     else k_blur2<false><<<g, blk, 0, s>>>(kd, src, dst, j, F, nb);
 }
 
@@ -745,25 +728,27 @@ int splat2_term(const CrfDev &c, const KernelDev &kd, int maxV, hipStream_t s)
     return j0;
 }
 
-// Step 2, the blur passes with a launch of their own (from j0 on; not the last with blur_in_slice): returns the buffer holding the result
-const float *blur2_passes(const CrfDev &c, const KernelDev &kd, int maxV, int j0, bool pairs, bool blur_in_slice, hipStream_t s)
+// Step 2, the blur passes with a launch of their own, each on the route the plan gives it (engine.h: blur_plan; the passes in the
+// splat and the one in the slice have none): returns the buffer holding the result
+const float *blur2_passes(const CrfDev &c, const KernelDev &kd, int maxV, const BlurPlan &plan, hipStream_t s)
 {
     XcdMap nb;
     const int blk = iter_block(c.F);
     const float *src = kd.val0;
     float *dst = kd.val1;
-    const int n_own = blur_in_slice ? kd.D1 - 1 : kd.D1;                           // blur passes with a launch of their own
-    for (int j = j0; j < n_own;) {
-        if (pairs && j + 1 < n_own) {             // one frame in flight: two passes per launch
+    for (int j = 0; j < kd.D1;) {
+        const int route = plan.route[j];
+        if (route == kBlurInSplat || route == kBlurInSlice) {
+            j += 1;
+            continue;
+        }
+        if (route == kBlurPairTable || route == kBlurPairPlain) {                  // two passes per launch
             const dim3 gp = grid_xcd(maxV, c.F, &nb, blk);
-            static const bool no_tbl = ab_env("LCCRF_NO_2HOP_TABLE") != nullptr;      // A/B switch: same results either way
-            const int jt = j - kd.nbr2_first;     // the table holds the pairs (first, first + 1), (first + 2, first + 3) ...
-            if (kd.nbr2 && kd.nbr2_ok && !no_tbl && jt >= 0 && !(jt & 1))
-                k_blur2x2t<<<gp, blk, 0, s>>>(kd, src, dst, jt / 2, (kd.D1 - kd.nbr2_first) / 2, c.F, nb);
+            if (route == kBlurPairTable) k_blur2x2t<<<gp, blk, 0, s>>>(kd, src, dst, plan.table_pair[j], plan.table_pairs, c.F, nb);
             else k_blur2x2<<<gp, blk, 0, s>>>(kd, src, dst, j, c.F, nb);
             j += 2;
         } else {
-            launch_blur2(kd, src, dst, j, c.F, maxV, s);
+            launch_blur2(kd, src, dst, j, c.F, maxV, route == kBlurAloneCompact, plan.nontemporal, s);
             j += 1;
         }
         swap_values(src, dst);
@@ -811,12 +796,10 @@ void launch_step_stream(const CrfDev &c, const KernelDev *kds, const int *maxV, 
     if (L == 2 && !general) {
         for (int k = 0; k < c.K; ++k) {
             const KernelDev &kd = kds[k];
-            const bool pairs = pair_fuse(c.F, maxV[k]);
-            const int j0 = splat2_term(c, kd, maxV[k], s);
-            // the pass left over by the pairs rides in the slice; with a few frames in flight (one pass per launch) the last pass does
-            const bool blur_in_slice = kd.D1 <= 9 && j0 < kd.D1 && (pairs ? ((kd.D1 - j0) & 1) && kd.D1 >= 3 : c.F <= kSliceBlurMaxFrames);   // (j0 == d + 1: a 2-D lattice's three passes can all ride in the splat)
-            const float *res = blur2_passes(c, kd, maxV[k], j0, pairs, blur_in_slice, s);
-            slice2_term(c, kd, res, blur_in_slice, k == 0, k == c.K - 1, relax, s);
+            const BlurPlan plan = blur_plan(kd, c.F, maxV[k]);                    // (engine.h: the one rule, also what the getters report)
+            (void)splat2_term(c, kd, maxV[k], s);                                  // (takes plan.counts.in_splat passes along: splat_passes_taken)
+            const float *res = blur2_passes(c, kd, maxV[k], plan, s);
+            slice2_term(c, kd, res, plan.counts.in_slice != 0, k == 0, k == c.K - 1, relax, s);
         }
         return;
     }
@@ -840,7 +823,7 @@ hipError_t time_blur_pass(const KernelDev &kd, int F, int maxV, int L, int reps,
     auto pass = [&](int i) {
         const float *src = (i & 1) ? kd.val1 : kd.val0;
         float *dst = (i & 1) ? kd.val0 : kd.val1;
-        if (L == 2) launch_blur2(kd, src, dst, i % kd.D1, F, maxV, s);
+        if (L == 2) launch_blur2(kd, src, dst, i % kd.D1, F, maxV, blur_alone_compact(kd), blur_alone_nontemporal(F), s);
         else k_blur<<<grid_for((long)maxV * L, F), kBlock, 0, s>>>(kd, src, dst, i % kd.D1, L);
     };
     for (int i = 0; i < 3; ++i) pass(i);

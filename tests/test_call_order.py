@@ -6,8 +6,8 @@ stale.  The long call sequences of the other tests exercise the transitions out 
 each (state, entry point) pair gets a handle of its own, closed afterwards -- so parked handles are reused, whatever the last call
 left in flight.  Everything is compared bit for bit: with the oracle where it has the call, and with the same call as the first one
 on a fresh handle (inputs set, nothing else) or a fresh batch behind build() otherwise.  Only the answers that report on the state
-itself -- engine(), the splat plan of a handle in locality mode, and engine() / the splat plan of a batch behind run(), which has no
-lattice in HBM -- are compared with the same call behind calls that have settled everything.
+itself -- engine(), the splat and blur plans of a handle in locality mode, and engine() / the two plans of a batch behind run(), which
+has no lattice in HBM -- are compared with the same call behind calls that have settled everything.
 """
 import importlib
 
@@ -87,6 +87,7 @@ CALLS = {
     "unary": (lambda c, pb: [c.unary()], True, True),
     "step_init": (lambda c, pb: [c.step_init()], False, True),
     "splat_plan": (lambda c, pb: [np.int64(list(c.splat_plan(0).values()))], False, True),
+    "blur_plan": (lambda c, pb: [np.int64(list(c.blur_plan(0).values()))], False, True),
     "converged": (_converged, False, False),
     "engine": (lambda c, pb: [np.int64(c.engine())], False, True),
     "backward": (_backward, False, False),
@@ -158,14 +159,14 @@ def _inference_reference(wl, po, state):
 @pytest.mark.parametrize("state", sorted(STATES))
 def test_first_call_on_a_handle_is_history_independent(po, wl, state, call):
     fn, _, keeps_results = CALLS[call]
-    if call == "engine" or (call == "splat_plan" and state == "d_locality"):
+    if call == "engine" or (call in ("splat_plan", "blur_plan") and state == "d_locality"):
         # reports on the state: the same answer as behind calls that have settled and read everything -- and the documented one
         r, _ = _handle(wl, state)
         r.synchronize()
         r.probability()
         want = fn(r, None)
         r.close()
-        if call == "splat_plan":                        # passes >= 1: state (d) IS in locality mode, whatever the threshold becomes
+        if call in ("splat_plan", "blur_plan"):         # passes (in_splat) >= 1: state (d) IS in locality mode, whatever the threshold becomes
             assert int(want[0][0]) >= 1, want
             want_engine = None
         else:
@@ -253,6 +254,7 @@ BATCH_CALLS = {
     "lattice_sizes": (lambda b, pbs: [b.lattice_sizes(0)], "built"),
     "engine": (lambda b, pbs: [np.int64(b.engine())], "settled"),
     "splat_plan": (lambda b, pbs: [np.int64(list(b.splat_plan(0).values()))], "settled"),
+    "blur_plan": (lambda b, pbs: [np.int64(list(b.blur_plan(0).values()))], "settled"),
     "converged": (_batch_converged, "settled"),                   # (wants lccrf_batch_build: LCCRF_E_STATE behind a run)
     "backward": (_batch_backward, "built"),
 }

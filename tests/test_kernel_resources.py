@@ -95,8 +95,8 @@ def test_streaming_iteration_kernels_use_no_scratch():
     slower).  Every splat / blur / slice / softmax variant of the engine's three units must compile without it."""
     units = [resource_usage("stream_%s.hip" % u) for u in ("build", "filter", "pointwise")]
     use = {k: v for unit in units for k, v in unit.items()}
-    assert len(use) == sum(len(unit) for unit in units) == 145      # every kernel of the engine, each in one unit only
+    assert len(use) == sum(len(unit) for unit in units) == 144      # every kernel of the engine, each in one unit only
     it = {k: v for k, v in use.items() if re.search(r"k_(splat|blur|slice|softmax|map|nbr_compact|row_|long_rows)", k)}
-    assert len(it) == 54
+    assert len(it) == 53                                      # (k_blur2c has one form: its table is never loaded non-temporally)
     for name, r in it.items():
         assert r["ScratchSize [bytes/lane]"] == 0 and r.get("VGPRs Spill", 0) == 0, (name, r)
