@@ -356,8 +356,8 @@ int  lccrf_inference_backward_features(lccrf_handle h, int n_iterations, float r
  * runs on the streaming engine with the matrix applied inside the slice kernel, which takes the Potts slice kernel's place: the
  * step issues no launch more than the streaming engine's general, L-label step (at L = 2 that is more than the two-label
  * specialisation issues).  The C++ mirror lccrf_densecrf.hpp sets a matrix per potential (PottsPotentialHIP::setCompatibility).
- * The batch API has the same setter, one matrix per term shared by every frame (section 2g); the gradients of such a batch are not
- * covered (sections 2c and 2d refuse it), and lccrf_densecrf_gpu.hpp is unchanged.  lccrf_inference_backward_features itself still returns
+ * The batch API has the same setter, one matrix per term shared by every frame (section 2g); the gradients of such a batch are
+ * section 2h's (sections 2c and 2d refuse it), and lccrf_densecrf_gpu.hpp is unchanged.  lccrf_inference_backward_features itself still returns
  * LCCRF_E_STATE on a handle with any matrix and leaves the handle as it was: the feature gradients of such a handle are
  * lccrf_inference_backward_all's (section 1f).                                                                                 */
 
@@ -468,7 +468,7 @@ int  lccrf_inference_backward_all(lccrf_handle h, int n_iterations, float relax,
  * leave the handle as it was.
  *
  * The C++ mirror lccrf_densecrf.hpp sets a mode per potential (PottsPotentialHIP::setNormalization).  The batch API has the same
- * setter, one mode per term shared by every frame (section 2g); the gradients of such a batch are not covered (sections 2c and 2d
+ * setter, one mode per term shared by every frame (section 2g); the gradients of such a batch are section 2h's (sections 2c and 2d
  * refuse a batch with a term that is not AFTER), and lccrf_densecrf_gpu.hpp is unchanged.
  *   - Memory: one [N] float array per SYMMETRIC term (s, formed from n on the handle's stream when first needed after a build or a
  *     mode change) and one [N] array of 1.0f per handle with a BEFORE or NONE term (what the slice reads where such a term has no
@@ -751,9 +751,8 @@ int  lccrf_batch_set_unary_device(lccrf_batch_handle b, const float *d_unary);
  *   - Errors: LCCRF_E_INVALID for n_iterations < 0, a relax that is not finite, or a device array section 1b refuses; a rejected
  *     call leaves the batch's inputs, lattices and Q as they were.  K = 0 is legal (d_grad_weights then receives nothing).
  *   - Potts terms normalised AFTER only: on a batch with a label-compatibility matrix or a mode other than AFTER (section 2g) this call
- *     and section 2d's return LCCRF_E_STATE and leave the batch as it was.  The batch sweep has not been checked against a handle's
- *     section 1e and 1g gradients frame by frame, and a silently wrong gradient is worse than none; the gradients of a learnt model
- *     are a handle's (sections 1c - 1g).                                                                                          */
+ *     and section 2d's return LCCRF_E_STATE and leave the batch as it was.  The gradients of such a batch -- of a learnt model, every
+ *     frame with the bits of a handle's section 1e and 1g gradients -- are lccrf_batch_inference_backward_all's (section 2h).       */
 int  lccrf_batch_inference_backward(lccrf_batch_handle b, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
                                     float *d_grad_weights, void *stream);
 
@@ -832,9 +831,10 @@ int  lccrf_batch_run_converged(lccrf_batch_handle b, int max_iterations, int cri
  *     converged call with section 2e's bookkeeping behind each step.
  *   - lccrf_batch_run and lccrf_batch_run_converged on such a batch are lccrf_batch_build followed by the inference call: the
  *     one-launch build + inference kernels hard-wire Potts.  lccrf_batch_get_fallback_frames reads 0.
- * Not covered: gradients (lccrf_batch_inference_backward and lccrf_batch_inference_backward_features return LCCRF_E_STATE on such a
- * batch and leave it as it was: section 2c) and a batched torch layer; the half-CU shapes (512 lanes, two frames per CU) and 3 - 4
- * points per lane; prepared launch records for such batches; the handle's converged call.
+ * Gradients: lccrf_batch_inference_backward_all (section 2h), behind the batched torch layer BatchCompatMeanFieldCRF;
+ * lccrf_batch_inference_backward and lccrf_batch_inference_backward_features still return LCCRF_E_STATE on such a batch and leave it
+ * as it was (section 2c).  Not covered: the half-CU shapes (512 lanes, two frames per CU) and 3 - 4 points per lane; prepared launch
+ * records for such batches; the handle's converged call.
  * ==================================================================================== */
 /* compat: HOST [L][L], row-major as in section 1e, copied during the call and uploaded on the batch's stream; NULL removes the matrix. */
 int  lccrf_batch_set_pairwise_compatibility(lccrf_batch_handle b, int kernel, const float *compat);
@@ -845,6 +845,51 @@ int  lccrf_batch_get_pairwise_compatibility(lccrf_batch_handle b, int kernel, fl
 int  lccrf_batch_set_pairwise_normalization(lccrf_batch_handle b, int kernel, int mode);
 /* *mode = the lccrf_normalization of term `kernel`.  No device work.                                                             */
 int  lccrf_batch_get_pairwise_normalization(lccrf_batch_handle b, int kernel, int *mode);
+
+/* ======================================================================================
+ * 2h. Gradients of a batch's inference for learnt models -- section 1f for every frame of a batch at once, Potts or with matrices
+ *     (section 2g), under any normalisation mode, and the sums over the frames a trainer of the (global) model wants
+ *     (lc-crf-slam_amd/autograd.py: mean_field_batch_compat, BatchCompatMeanFieldCRF).  Added WITHOUT a step of LCCRF_ABI_VERSION
+ *     (it stays 3): probe for it by symbol.  Sections 2c and 2d are unchanged and keep refusing a batch with a matrix or a mode.
+ *
+ * The gradients of lccrf_batch_inference(b, n_iterations, -, relax, -) on the batch's current inputs, weights, matrices and modes.
+ * d_grad_prob [n_frames][max_points][L] = dL/dQ_T.  Outputs, device arrays, each overwritten, each may be NULL:
+ *      d_grad_unary     [n_frames][max_points][L]
+ *      d_grad_weights   [n_frames][n_kernels]
+ *      d_grad_features  HOST array of n_kernels device pointers, [n_frames][max_points][d_k] each; entries may be NULL (section 2d)
+ *      d_grad_compat    [n_frames][n_kernels][L][L]      dL/dmu_k of every frame; for a term without a matrix the derivative at mu_k = I
+ *      d_grad_model     [n_kernels + n_kernels*L*L]      sum over the frames of dL/dw, then of dL/dmu
+ *   - Per frame, the bits of section 1f: d_grad_unary[f], d_grad_weights[f], d_grad_features[k][f] and d_grad_compat[f] are exactly
+ *     what lccrf_inference_backward_all returns for a handle holding frame f's n_points[f] points, unary and features with the batch's
+ *     weights, matrices and modes -- dL/dmu included: a frame's points are cut into C_f = min(max(ceil(n_points[f] / 256), 1), 128)
+ *     chunks, the count section 1e gives a handle of that many points, whatever max_points is, and the C_f partials are summed in
+ *     order.  Rows at or beyond n_points[f] are written 0; a frame of 0 points gets zeros.  At n_iterations = 0 dL/dmu and dL/df are
+ *     exactly 0.  On a batch without matrices or modes and with d_grad_compat == d_grad_model == NULL every output is, bit for bit,
+ *     lccrf_batch_inference_backward_features's.
+ *   - d_grad_model[j] = ((x[0][j] + x[1][j]) + ...) + x[n_frames-1][j] in fp32, the frames in ascending order, x the per-frame values
+ *     of this call: the caller's d_grad_weights / d_grad_compat, or the batch's area where the caller passed NULL.  One owner per
+ *     entry, no float atomics; frames beyond n_frames are never read.  The order is part of the contract: a host loop of fp32 adds
+ *     over the per-frame arrays gives the same bits.
+ *   - With d_grad_features non-NULL and a term that is not normalised AFTER the call returns LCCRF_E_STATE and leaves the batch as it
+ *     was, as section 1f's handle call does (section 1g: the norm's factors are not differentiated in the features).
+ *   - Everything else is section 2c's contract: self-contained (the forward is replayed on the step path), LCCRF_E_STATE before
+ *     lccrf_batch_build or lccrf_batch_run on the current inputs, a pending one-launch run settled first, frames in locality mode
+ *     re-built the plain way, the stream rules, argument checks (LCCRF_E_INVALID) before anything is enqueued, Q afterwards exactly
+ *     what lccrf_batch_inference(b, n_iterations, 0, relax, stream) leaves, the labels untouched, lccrf_batch_last_timing's
+ *     inference_ms timing the call, deterministic.
+ *   - Launches: those of section 1f for one frame (per iteration and term one kernel more than section 2c with matrices in play or
+ *     d_grad_compat / d_grad_model asked for, one reduction at the end), plus two for d_grad_model (K > 0).
+ *   - Memory: section 2c's area (with section 2d's part for the terms asked for) grows, with a matrix set or d_grad_compat /
+ *     d_grad_model given, by 4 * (F*S + K*F*C*L*L) bytes -- gamma_t and the partials of dL/dmu, F = n_frames, S = max_points * L,
+ *     C = min(max(ceil(max_points / 256), 1), 128) -- plus 4 * F*S when d_grad_unary is NULL, and with d_grad_model by 4 * F*K bytes
+ *     when d_grad_weights is NULL and 4 * F*K*L*L bytes when d_grad_compat is NULL:
+ *         4 * (F*S*(T + K + 2) + max(T,1)*K*F*B + K*F*C*L*L) bytes  [+ 4 * F*S] [+ 4 * F*K] [+ 4 * F*K*L*L]
+ *     (16384 frames of max_points = 2000, L = 2, K = 2, T = 5: 2.4 GB, 4.2 MB of it the partials of dL/dmu).  Allocated as section 2c's; a failed
+ *     allocation returns LCCRF_E_NOMEM and leaves the batch usable.
+ * ==================================================================================== */
+int  lccrf_batch_inference_backward_all(lccrf_batch_handle b, int n_iterations, float relax, const float *d_grad_prob,
+                                        float *d_grad_unary, float *d_grad_weights, float *const *d_grad_features, float *d_grad_compat,
+                                        float *d_grad_model, void *stream);
 
 /* ======================================================================================
  * 3. Unary builder -- the step right before the CRF (first "next" row):

@@ -188,6 +188,7 @@ def lib():
     L.lccrf_batch_set_unary_device.argtypes = [vp, vp]
     L.lccrf_batch_inference_backward.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, vp]
     L.lccrf_batch_inference_backward_features.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, C.POINTER(vp), vp]
+    L.lccrf_batch_inference_backward_all.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, C.POINTER(vp), vp, vp, vp]
     L.lccrf_batch_set_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p]
     L.lccrf_batch_get_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p, C.POINTER(C.c_int)]
     L.lccrf_batch_set_pairwise_normalization.argtypes = [vp, C.c_int, C.c_int]
@@ -694,6 +695,16 @@ class BatchCRF:
         _check(lib().lccrf_batch_inference_backward_features(self.h, int(n_iterations), float(relax), C.c_void_p(int(d_grad_prob)),
                                                              _addr(d_grad_unary), _addr(d_grad_weights), _addr_list(d_grad_features),
                                                              C.c_void_p(stream) if stream else None))
+
+    def inference_backward_all_device(self, n_iterations, relax, d_grad_prob, d_grad_unary=None, d_grad_weights=None,
+                                      d_grad_features=None, d_grad_compat=None, d_grad_model=None, stream=None):
+        """The gradients of a batch with or without matrices and modes (include/lccrf.h section 2h): per frame dL/dU, dL/dw [F][K],
+        dL/d features (a list of K device addresses or None entries) and dL/dmu [F][K][L][L], and d_grad_model [K + K*L*L], the
+        sums over the frames of dL/dw and dL/dmu in ascending frame order; device addresses, any output may be None."""
+        _check(lib().lccrf_batch_inference_backward_all(self.h, int(n_iterations), float(relax), C.c_void_p(int(d_grad_prob)),
+                                                        _addr(d_grad_unary), _addr(d_grad_weights), _addr_list(d_grad_features),
+                                                        _addr(d_grad_compat), _addr(d_grad_model),
+                                                        C.c_void_p(stream) if stream else None))
 
     # -- label-compatibility matrices and normalisation modes (include/lccrf.h section 2g) ---------------------------------------
     def set_pairwise_compatibility(self, k, compat):

@@ -6,6 +6,9 @@
     Q = mean_field_batch(batch, unary, weights, n_iterations=5, relax=1.0)     # every frame of a BatchCRF at once
     Q.backward(g)      # -> unary.grad [F, max_points, L], weights.grad = sum over the frames of dL/dw
 
+    Q = mean_field_batch_compat(batch, unary, weights, compat, n_iterations=5, relax=1.0)    # ... with a [K, L, L] compatibility
+    Q.backward(g)      # -> also compat.grad; both sums over the frames come from the batch's own call (section 2h)
+
     Q = mean_field_features(unary, [f_0, f_1, ..], weights, n_iterations=5, relax=1.0)        # the features are inputs too
     Q.backward(g)      # -> also f_k.grad = dL/d features [N, d_k] (section 1d); LearnedKernelCRF fits kernel bandwidths with it
 
@@ -246,6 +249,89 @@ class BatchMeanFieldCRF(torch.nn.Module):
 
     def forward(self, unary):
         return mean_field_batch(self.batch, unary, self.weights, self.n_iterations, self.relax)
+
+    def close(self):
+        self.batch.close()
+
+
+class _MeanFieldBatchCompat(torch.autograd.Function):
+    """_MeanFieldCompat for a batch: the model's gradients are the batch's own ordered sums over the frames (section 2h)"""
+
+    @staticmethod
+    def forward(ctx, batch, unary, weights, compat, n_iterations, relax, n_points):
+        F, N, L, K = batch.n_frames, batch.maxN, batch.L, len(batch.dims)
+        _check_unary_weights(unary, (F, N, L), weights, K)
+        if compat.dtype != torch.float32 or tuple(compat.shape) != (K, L, L):
+            raise ValueError("compat must be a float32 tensor of shape [%d, %d, %d]" % (K, L, L))
+        _check_iterations(n_iterations)
+        dev = unary.device
+        u = unary.detach().contiguous()
+        w, m = weights.detach().clone(), compat.detach().clone().contiguous()
+        with _on_stream(batch.own_stream(), dev) as (ext, cur):
+            _arm(batch, w, m)
+            batch.set_unary_device(u.data_ptr())
+            batch.inference(int(n_iterations), False, float(relax))      # (leaves nothing to settle)
+            q = _clone_q(batch.device_buffers()[1], (F, N, L), dev, ext, cur)
+        live = torch.arange(N, device=dev)[None, :] < torch.as_tensor(n_points, device=dev)[:, None]
+        q = torch.where(live[:, :, None], q, torch.zeros((), device=dev))    # rows beyond a frame's points: 0
+        ctx.batch, ctx.n_iterations, ctx.relax = batch, int(n_iterations), float(relax)
+        ctx.weights_device, ctx.compat_device = weights.device, compat.device
+        ctx.save_for_backward(u, w, m)
+        return q
+
+    @staticmethod
+    def backward(ctx, grad_q):
+        u, w, m = ctx.saved_tensors
+        batch, dev = ctx.batch, u.device
+        K, L = int(w.numel()), batch.L
+        g = _grad_in(grad_q, dev)
+        grad_u = torch.empty_like(u)
+        model = torch.zeros(max(K * (1 + L * L), 1), dtype=torch.float32, device=dev)
+        with _on_stream(batch.own_stream(), dev):
+            _arm(batch, w, m)                                 # the inputs of this forward (the batch may have run others since)
+            batch.set_unary_device(u.data_ptr())
+            batch.inference_backward_all_device(ctx.n_iterations, ctx.relax, g.data_ptr(), grad_u.data_ptr(),
+                                                d_grad_model=model.data_ptr() if K else None)
+        return (None, grad_u, model[:K].to(ctx.weights_device), model[K:K * (1 + L * L)].reshape(K, L, L).to(ctx.compat_device),
+                None, None, None)
+
+
+def mean_field_batch_compat(batch, unary, weights, compat, n_iterations=5, relax=1.0):
+    """mean_field_batch with a label-compatibility matrix per term (include/lccrf.h sections 2g and 2h): `compat` [K, L, L] (float32,
+    any device), shared by every frame; differentiable in unary, weights and compat.  weights.grad and compat.grad are the sums over
+    the frames of dL/dw and dL/dmu, formed by the batch's own call in ascending frame order (no torch reduction).  The matrices are left
+    set on `batch`; its normalisation modes are honoured."""
+    if batch.n_points is None:
+        raise ValueError("the batch's point counts are on the device only (bind_inputs_device): set its inputs from the host")
+    return _MeanFieldBatchCompat.apply(batch, unary, weights, compat, n_iterations, relax, batch.n_points)
+
+
+class BatchCompatMeanFieldCRF(torch.nn.Module):
+    """BatchMeanFieldCRF whose terms carry a learnt label-compatibility matrix: parameters `weights` [K] and `compat` [K, L, L], the
+    latter initialised to identities (the Potts model), both shared by every frame; normalization: None (the reference's form), one of
+    the package's NORMALIZE_* modes for every term, or one per term, set once.  The features are uploaded and the lattices built once,
+    here.  forward(unary [F, max_points, L]) -> Q [F, max_points, L]."""
+
+    def __init__(self, n_points, features, weights, n_iterations=5, relax=1.0, device=0, n_labels=2, normalization=None):
+        super().__init__()
+        if len(features) != len(weights):
+            raise ValueError("one weight per feature array")
+        feats = [np.ascontiguousarray(f.detach().cpu().numpy() if isinstance(f, torch.Tensor) else f, np.float32) for f in features]
+        n_points = np.ascontiguousarray(n_points, np.int32)
+        modes = [] if normalization is None else np.broadcast_to(np.asarray(normalization, np.int64), (len(feats),)).tolist()
+        F = int(n_points.size)
+        N = int(feats[0].shape[1]) if feats else int(n_points.max(initial=0))
+        self.batch = _pkg.BatchCRF(F, N, n_labels, [f.shape[2] for f in feats], [float(w) for w in weights], device=device)
+        for k, mode in enumerate(modes):                      # (include/lccrf.h section 2g; None: every term AFTER)
+            self.batch.set_normalization(k, mode)
+        self.batch.set_inputs_host(n_points, feats, unary=np.zeros((F, N, n_labels), np.float32))
+        self.batch.build()
+        self.weights = torch.nn.Parameter(torch.tensor([float(w) for w in weights], dtype=torch.float32))
+        self.compat = torch.nn.Parameter(torch.eye(int(n_labels), dtype=torch.float32).repeat(len(weights), 1, 1))
+        self.n_iterations, self.relax = int(n_iterations), float(relax)
+
+    def forward(self, unary):
+        return mean_field_batch_compat(self.batch, unary, self.weights, self.compat, self.n_iterations, self.relax)
 
     def close(self):
         self.batch.close()

@@ -1,4 +1,4 @@
-// api_backward.hip -- gradients of mean-field inference: sections 1c - 1f (a handle) and 2c, 2d (a batch) of include/lccrf.h.
+// api_backward.hip -- gradients of mean-field inference: sections 1c - 1f (a handle) and 2c, 2d, 2h (a batch) of include/lccrf.h.
 //
 // One path behind every entry point (backward_call); the replay and the sweep themselves are Engine::backward (host_engine.hip) and
 // meanfield_backward.hip.
@@ -8,7 +8,7 @@
 
 using namespace lccrf;
 
-// Every backward entry point, of a handle (sections 1c - 1f) and of a batch (2c, 2d), fills a BackwardRequest (engine.h), says where
+// Every backward entry point, of a handle (sections 1c - 1f) and of a batch (2c, 2d, 2h), fills a BackwardRequest (engine.h), says where
 // it runs and what it allows, and calls backward_call.  A handle is a batch of one whose area has its own row stride.
 struct BackwardTarget {
     Engine &e;
@@ -39,7 +39,8 @@ static int backward_call(const BackwardTarget &t, const BackwardRequest &rq, boo
             (rc = check_device_array(e, rq.grad_features[k], points * e.kernels[k].dev.d * sizeof(float), "d_grad_features[k]")))
             return rc;
     // (K = 0: zero bytes, nothing to check)
-    if (rq.grad_compat && (rc = check_device_array(e, rq.grad_compat, K * e.L * e.L * sizeof(float), "d_grad_compat"))) return rc;
+    if (rq.grad_compat && (rc = check_device_array(e, rq.grad_compat, e.F * K * e.L * e.L * sizeof(float), "d_grad_compat"))) return rc;
+    if (rq.grad_model && (rc = check_device_array(e, rq.grad_model, K * (1 + (size_t)e.L * e.L) * sizeof(float), "d_grad_model"))) return rc;
     if (!t.ready) return fail(LCCRF_E_STATE, "%s", t.not_ready);
     auto run = [&] {
         int rr = e.resolve_late();
@@ -64,13 +65,13 @@ static BackwardTarget backward_target(lccrf_batch *b, void *stream)
             "lccrf_batch_build or lccrf_batch_run has not run for these inputs", true, stream};
 }
 
-// Sections 2c and 2d differentiate Potts terms normalised AFTER: nobody has checked that the batch sweep gives each frame the bits of
-// a handle's section 1e and 1g gradients, and a silently wrong gradient is worse than none.  A batch with a matrix or another mode
-// (section 2g) is refused before anything is looked at or touched.
+// Sections 2c and 2d differentiate Potts terms normalised AFTER, and keep refusing a batch with a matrix or another mode (section 2g)
+// before anything is looked at or touched: the gradients of such a batch -- every frame with the bits of a handle's section 1e and 1g
+// gradients -- are section 2h's, lccrf_batch_inference_backward_all below.
 static int batch_is_plain(const lccrf_batch *b)
 {
-    if (b->eng.n_compat) return fail(LCCRF_E_STATE, "batch gradients are not available while a term has a label-compatibility matrix");
-    if (b->eng.n_modes) return fail(LCCRF_E_STATE, "batch gradients are not available while a term is not normalised AFTER the filter");
+    if (b->eng.n_compat) return fail(LCCRF_E_STATE, "batch gradients are not available while a term has a label-compatibility matrix: lccrf_batch_inference_backward_all");
+    if (b->eng.n_modes) return fail(LCCRF_E_STATE, "batch gradients are not available while a term is not normalised AFTER the filter: lccrf_batch_inference_backward_all");
     return LCCRF_OK;
 }
 
@@ -154,6 +155,24 @@ int lccrf_batch_inference_backward_features(lccrf_batch_handle b, int n_iteratio
     if (int rc = batch_is_plain(b)) return rc;
     BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
     rq.grad_features = d_grad_features;
+    return backward_call(backward_target(b, stream), rq, kGradUnaryOptional);
+}
+
+// --------------------------------------------------------------------------------------
+// section 2h: section 1f for every frame of a batch, Potts or learnt, and the sums over the frames
+
+int lccrf_batch_inference_backward_all(lccrf_batch_handle b, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
+                                       float *d_grad_weights, float *const *d_grad_features, float *d_grad_compat, float *d_grad_model,
+                                       void *stream)
+{
+    CHECK_H(b);
+    if (d_grad_features && b->eng.n_modes)                // (section 1g: the norm's factors are not differentiated in the features)
+        return fail(LCCRF_E_STATE, "feature gradients are not available while a term is not normalised AFTER the filter");
+    BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
+    rq.grad_features = d_grad_features;
+    rq.grad_compat = d_grad_compat;
+    rq.grad_model = d_grad_model;
+    rq.compat_form = b->eng.n_compat > 0 || d_grad_compat || d_grad_model;   // (the sums hold dL/dmu: section 1e's form)
     return backward_call(backward_target(b, stream), rq, kGradUnaryOptional);
 }
 

@@ -346,8 +346,9 @@ struct BackwardRequest {           // (an aggregate: the members left out of a b
     float *grad_unary;              // [F][rows][L] or null: dL/dU is then formed in the area (BackwardArea::gU)
     float *grad_weights;            // [F][K] or null
     float *const *grad_features;    // null, or K pointers, [F][rows][d_k] each or null (sections 1d / 2d)
-    float *grad_compat;             // [K][L][L] or null (sections 1e / 1f; F = 1)
+    float *grad_compat;             // [F][K][L][L] or null (sections 1e / 1f: F = 1; section 2h)
     bool compat_form;               // the sweep takes section 1e's form: the terms' matrices are honoured (grad_compat needs it)
+    float *grad_model;              // [K + K*L*L] or null (section 2h): the sums over the frames of dL/dw and dL/dmu (needs compat_form)
 };
 // The area of one backward call, owned by the engine and zeroed when allocated: Q_0 .. Q_{T-1} of the replay, one [F][.][L] array
 // per term, dL/dQ_t, the per-workgroup partials of the weight gradient, and the parts the request asks for beyond those.  Every
@@ -371,6 +372,9 @@ struct BackwardArea {
     // per-workgroup partials of dL/dmu accumulated over the iterations
     float *gam;           // [slice]
     float *cpart;         // [K][F][backward_compat_blocks(rows)][L][L]
+    // the per-frame values behind the request's grad_model where the caller left their own array out (section 2h), else null
+    float *gW;            // [F][K]
+    float *gC;            // [F][K][L][L]
 };
 int backward_blocks(int n, int L);
 size_t backward_stride(int n, int L);
@@ -389,6 +393,8 @@ size_t backward_layout(const BackwardRequest &rq, const CrfDev &c, const KernelD
 // pre (or null): as launch_step_stream takes it (section 1g) -- kds[k].norm is then a_k, the factor behind the filter, the forward
 // filters of the sweep scale their input rows by pre[k] = b_k, and k_bwd_combine multiplies the transposed filter's result by it.
 // Without grad_features only (the entry points refuse the combination).
+// rq.grad_model (section 2h; null for a handle: not a launch more): dL/dw and dL/dmu of every frame -- in the caller's arrays, or in
+// ar.gW / ar.gC where the caller left one out -- are summed over the frames in ascending order, one k_sum_frames launch each.
 void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int rows, const BackwardRequest &rq,
                            const BackwardArea &ar, const float *const *compat, hipStream_t s, const float *const *pre = nullptr);
 

@@ -174,10 +174,13 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
         if (count) HIP_TRY(hipMemcpyAsync(ar.hist + (size_t)t * slice, crf.Q, count * sizeof(float), hipMemcpyDeviceToDevice, stream));
         if ((rc = step(rq.relax))) return rc;
     }
-    if (rq.grad_compat && K && (!count || T == 0))    // nothing depends on the matrices: exactly 0
-        HIP_TRY(hipMemsetAsync(rq.grad_compat, 0, (size_t)K * L * L * sizeof(float), stream));
+    // (section 2h: the per-frame values behind grad_model live in the area where the caller left their own array out)
+    float *const grad_weights = rq.grad_weights ? rq.grad_weights : ar.gW, *const grad_compat = rq.grad_compat ? rq.grad_compat : ar.gC;
+    if (grad_compat && K && (!count || T == 0))       // nothing depends on the matrices: exactly 0, in every frame
+        HIP_TRY(hipMemsetAsync(grad_compat, 0, (size_t)F * K * L * L * sizeof(float), stream));
     if (!count) {                                     // nothing to differentiate: dL/dw = 0
-        if (rq.grad_weights && K) HIP_TRY(hipMemsetAsync(rq.grad_weights, 0, (size_t)F * K * sizeof(float), stream));
+        if (grad_weights && K) HIP_TRY(hipMemsetAsync(grad_weights, 0, (size_t)F * K * sizeof(float), stream));
+        if (rq.grad_model && K) HIP_TRY(hipMemsetAsync(rq.grad_model, 0, (size_t)K * (1 + L * L) * sizeof(float), stream));
         return LCCRF_OK;
     }
     for (int k = 0; k < K && rq.grad_features; ++k) {

@@ -30,6 +30,10 @@
 // k_corner_dot runs after k_compat_bwd has turned phi_k into mu_k^T (n_k gamma_t) and before the transposed filter overwrites it; the
 // splat side runs on the transposed filter's values as before, and g_n is formed from mu_k Phi_k (k_joint_softmax<G>).
 //
+// A batch's learnt model (section 2h): the compatibility part is per frame too -- k_compat_bwd cuts a frame's rows into the chunk count
+// of a handle of n_points[f] points, k_compat_reduce sums that frame's chunks in order into d_grad_compat[f] -- and k_sum_frames adds
+// dL/dw and dL/dmu over the frames in ascending order for the (global) model's gradient.
+//
 // Rows at or beyond n_points[f] (the phantom points of quirk Q1 among them) are never read: every lattice build lists real points
 // only in its splat rows (k_csr_count / k_eoffsets in stream_build.hip, E = N (d+1) in build_small.hip), the slice writes rows
 // i < n_points[f] only, and the kernels below stop at n_points[f].  A batch rebound with fewer points than an earlier call leaves
@@ -341,13 +345,21 @@ void launch_softmax_bwd(const BwdArgs &a, int F, hipStream_t s)
 // One term, behind k_compat_softmax<G>: with y_i = n_k[i] gamma_t[i] and Phi = Phi_k(Q_{t-1}) (phi, as the filter left it)
 //   cpart[f][b][l][l'] (+)= w_k * sum over workgroup b's rows of y_i[l] * Phi_i[l']        the partial of dL/dmu_k (cpart != null)
 //   phi[i][l']           = sum_l mu[l][l'] * y_i[l]  (labels in order; y_i[l'] for a Potts term)   the transposed filter's input
-// A frame's rows are cut into gridDim.x contiguous chunks, one per workgroup, walked in tiles of R = 256 / L rows: lane r * L + l
+// A frame's rows are cut into compat_chunks(n_points[f]) contiguous chunks, one per workgroup -- the count a handle of that many points
+// launches, so that a frame of a batch (whose grid is sized for max_points) adds its partials in the handle's order; the workgroups
+// beyond the frame's count leave before the first barrier and write nothing -- walked in tiles of R = 256 / L rows: lane r * L + l
 // puts y and Phi of row r into LDS, lane p (and p + 256, ...) adds the tile's rows in order to its entries (l, l') of the outer
 // product, kept in registers over the whole chunk, and lane r * L + l' forms row r of mu^T y.  No atomics: an entry has one owner and
 // one order of additions (rows ascending; t = T .. 1 across the sweep's launches), the same bits from run to run.
 constexpr int kCompatMaxBlocks = 128;
 constexpr int kCompatTileB = kBwdBlock + kBwdBlock / 2;   // R * (L | 1) <= 256 + R floats
 constexpr int kCompatPairs = (LCCRF_MAX_LABELS * LCCRF_MAX_LABELS + kBwdBlock - 1) / kBwdBlock;   // entries of mu per lane
+// chunks of a frame of n points (backward_compat_blocks: the grid of a handle of n points)
+__host__ __device__ inline int compat_chunks(int n)
+{
+    const int b = (n + kBwdBlock - 1) / kBwdBlock;
+    return b < 1 ? 1 : b > kCompatMaxBlocks ? kCompatMaxBlocks : b;
+}
 struct CompatArgs {
     const int *n_points;
     int L, first;                // first: the sweep's first iteration writes cpart, the others add to it
@@ -366,9 +378,11 @@ __global__ void __launch_bounds__(kBwdBlock) k_compat_bwd(CompatArgs a)
     __shared__ float mu[LCCRF_MAX_LABELS * (LCCRF_MAX_LABELS + 1)];
     __shared__ float ys[kCompatTileB], ps[kCompatTileB];
     const int f = blockIdx.y, L = a.L, N = a.n_points[f];
+    const int B = compat_chunks(N);                       // (a handle: gridDim.x)
+    if ((int)blockIdx.x >= B) return;                     // (the whole workgroup, before any barrier)
     const int R = kBwdBlock / L, st = L == 1 ? 1 : (L | 1), tid = threadIdx.x;
     const int r = tid / L, l = tid - r * L;
-    const int chunk = (N + (int)gridDim.x - 1) / (int)gridDim.x;
+    const int chunk = (N + B - 1) / B;
     const int i_begin = min((int)blockIdx.x * chunk, N), i_end = min(i_begin + chunk, N);
     if (a.mu)
         for (int idx = tid; idx < L * L; idx += kBwdBlock) {
@@ -419,15 +433,56 @@ __global__ void __launch_bounds__(kBwdBlock) k_compat_bwd(CompatArgs a)
     }
 }
 
-// out[k][l][l'] = sum over the workgroups b = 0 .. B-1, in that order, of cpart[k][0][b][l][l'] (a handle is one frame)
-__global__ void __launch_bounds__(kBwdBlock) k_compat_reduce(const float *__restrict__ cpart, int K, int B, int LL, float *__restrict__ out)
+// out[f][k][l][l'] = sum over the frame's chunks b = 0 .. compat_chunks(n_points[f]) - 1, in that order, of cpart[k][f][b][l][l']
+// (bstride: the chunks the partials have room for, the sweep's grid); one owner per (frame, term, entry).  A handle is one frame of
+// bstride chunks.  A frame of 0 points gets 0.
+__global__ void __launch_bounds__(kBwdBlock) k_compat_reduce(const float *__restrict__ cpart, const int *__restrict__ n_points, int K, int F,
+                                                           int bstride, int LL, float *__restrict__ out)
 {
-    const int idx = blockIdx.x * kBwdBlock + threadIdx.x;
-    if (idx >= K * LL) return;
-    const int k = idx / LL, p = idx - k * LL;
+    const long idx = (long)blockIdx.x * kBwdBlock + threadIdx.x;
+    if (idx >= (long)F * K * LL) return;
+    const int f = (int)(idx / ((long)K * LL));
+    const int e = (int)(idx - (long)f * K * LL);
+    const int k = e / LL, p = e - k * LL;
+    const int N = n_points[f], B = N > 0 ? compat_chunks(N) : 0;
+    const float *cp = cpart + ((size_t)k * F + f) * bstride * LL + p;
     float s = 0.0f;
-    for (int b = 0; b < B; ++b) s += cpart[((size_t)k * B + b) * LL + p];
+    for (int b = 0; b < B; ++b) s += cp[(size_t)b * LL];
     out[idx] = s;
+}
+
+// ---- the sums over the frames (section 2h) ---------------------------------------------------------------------------------------
+// out[j] = ((x[0][j] + x[1][j]) + ..) + x[F-1][j], j < n, x [F][n]: the frames in ascending order, in fp32, one owner per entry and no
+// atomics -- the order is part of section 2h's contract (0 for F = 0).  A workgroup owns kSumEntries entries and walks the frames in
+// tiles of kSumFrames: all lanes load the tile (n <= kSumEntries: one contiguous run of the array; else runs of kSumEntries floats),
+// lane j then adds its column of the tile, frame by frame (row stride kSumEntries + 1: the lanes of a row on 64 banks).  Frames at
+// or beyond F are never read.
+constexpr int kSumEntries = 64, kSumFrames = 64;
+__global__ void __launch_bounds__(kBwdBlock) k_sum_frames(const float *__restrict__ x, int F, int n, float *__restrict__ out)
+{
+    __shared__ float tile[kSumFrames * (kSumEntries + 1)];
+    const int tid = threadIdx.x, j0 = blockIdx.x * kSumEntries, ne = min(kSumEntries, n - j0);
+    float acc = 0.0f;
+    for (int f0 = 0; f0 < F; f0 += kSumFrames) {            // (uniform bounds: every lane meets every barrier)
+        const int nf = min(kSumFrames, F - f0);
+        for (int idx = tid; idx < nf * ne; idx += kBwdBlock) {
+            const int fr = idx / ne, e = idx - fr * ne;
+            tile[fr * (kSumEntries + 1) + e] = x[(size_t)(f0 + fr) * n + j0 + e];
+        }
+        __syncthreads();
+        if (tid < ne) {
+            int fr = 0;
+            if (f0 == 0) acc = tile[tid], fr = 1;          // (the sum starts from frame 0's value, not from +0)
+            for (; fr < nf; ++fr) acc = acc + tile[fr * (kSumEntries + 1) + tid];
+        }
+        __syncthreads();
+    }
+    if (tid < ne) out[j0 + tid] = acc;
+}
+
+void launch_sum_frames(const float *x, int F, int n, float *out, hipStream_t s)
+{
+    if (n > 0) k_sum_frames<<<(unsigned)((n + kSumEntries - 1) / kSumEntries), kBwdBlock, 0, s>>>(x, F, n, out);
 }
 
 // ---- the feature part (sections 1d and 2d) ----------------------------------------------------------------------------------
@@ -595,6 +650,10 @@ size_t backward_layout(const BackwardRequest &rq, const CrfDev &c, const KernelD
         a.gam = take(slice);
         a.cpart = take(K * F * backward_compat_blocks(rows) * LL);
     }
+    if (rq.grad_model) {                                  // (section 2h: the per-frame values the sums are formed from)
+        if (!rq.grad_weights) a.gW = take(F * K);
+        if (!rq.grad_compat) a.gC = take(F * K * LL);
+    }
     if (ar) *ar = a;
     return used * sizeof(float);
 }
@@ -605,7 +664,8 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
     const int T = rq.T;
     const float relax = rq.relax;
     float *const *grad_features = rq.grad_features;
-    float *const grad_weights = rq.grad_weights, *const grad_compat = rq.grad_compat;
+    // (section 2h: the per-frame values behind grad_model are formed in the area where the caller left their own array out)
+    float *const grad_weights = rq.grad_weights ? rq.grad_weights : ar.gW, *const grad_compat = rq.grad_compat ? rq.grad_compat : ar.gC;
     const int K = c.K, L = c.L, F = c.F;
     const size_t slice = ar.slice, fs = (size_t)c.maxN * L;
     const int nblk = std::max(backward_blocks(rows, L), 1);
@@ -680,7 +740,8 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
     a.partial = nullptr;
     launch_softmax_bwd<kBwdPlain>(a, F, s);
     if (grad_compat && K && T >= 1)
-        k_compat_reduce<<<(unsigned)((K * L * L + kBwdBlock - 1) / kBwdBlock), kBwdBlock, 0, s>>>(ar.cpart, K, cblk, L * L, grad_compat);
+        k_compat_reduce<<<(unsigned)(((size_t)F * K * L * L + kBwdBlock - 1) / kBwdBlock), kBwdBlock, 0, s>>>(ar.cpart, c.n_points, K, F, cblk,
+                                                                                                            L * L, grad_compat);
     // the norm part, <a_k, Phi_k(1)> with a_k = -n_k^2 g_n[k] (value width 1), and dL/db -> dL/df
     for (int k = 0; k < K; ++k) {
         if (!gf[k]) continue;
@@ -695,6 +756,10 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
     if (grad_weights && K)
         k_bwd_reduce<<<dim3((unsigned)K, (unsigned)F), kBwdBlock, 0, s>>>(ar.partial, c.n_points, K, T, kBwdBlock / bwd_lanes(L), nblk,
                                                                        grad_weights);
+    if (rq.grad_model) {                                  // the sums over the frames: the K weights, then the K * L * L entries
+        launch_sum_frames(grad_weights, F, K, rq.grad_model, s);
+        launch_sum_frames(grad_compat, F, K * L * L, rq.grad_model + K, s);
+    }
 }
 
 }  // namespace lccrf
