@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import crf_cases as cc
+from chain_cases import descending, lattice, shaped_frame
 from kernel_resources import HIPCC, ROOT
 
 F = 256                                                       # (the smallest count that takes the two-frames-per-CU plan)
@@ -22,52 +23,6 @@ SIZES = (600, 1100, 2000)
 TOP, MAX_V = 16, 208                                          # rows of the top wavefront; the most vertices the chain lanes take
 EDGES = [TOP + 32 * j + d for j in range(3) for d in (-1, 0, 1)]
 TRIP_ROWS = [4 * q + d for q in (8, 16) for d in (-1, 0, 1)]  # a ring trip is 8 reads of 4 products: 31 .. 33 and 63 .. 65 products
-
-
-def lattice(po, feat):
-    """(vertex count, row lengths) of the checker's lattice of one kernel's features"""
-    n = feat.shape[0]
-    o = po.OracleCRF(n, 2)
-    o.set_unary_from_label(np.zeros(n, np.int16), np.float32(0.7))
-    o.add_pairwise(feat, 1.0)
-    k = o.kernel(0)
-    o.close()
-    return k["V"], np.bincount(k["offset"].reshape(-1), minlength=k["V"])
-
-
-def cell(c):
-    """a lattice cell far from every other one (crf_cases.shaped_problem's `sparse` placement)"""
-    return np.array([c, (c * 7) % 1013], np.float32) * np.float32(9.0)
-
-
-NEAR = np.float32([[0, 0], [0.3, 0], [0.6, 0.2], [0.9, 0], [1.2, 0.4], [0.3, 0.6], [0.6, 0.9], [0, 0.9]])
-
-
-def shaped_frame(po, wl, clusters, v_target, seed):
-    """A frame whose appearance lattice has exactly `v_target` vertices: `clusters` (point counts) of identical points, their points
-    shuffled among each other, then isolated points: cell after cell, the first k of eight points a little apart (NEAR) -- the first
-    brings its cell's vertices, the others share some of them, so a cell can bring 3, 4, 5 ... vertices: how many for which k is read
-    from the checker, and the cells' counts are chosen to add up.  The smoothness features, labels and confidence are a SLAM frame's.
-    Returns (problem, V0, row lengths, longest first)."""
-    rng = np.random.default_rng(seed)
-    own = rng.permutation(np.repeat(np.arange(len(clusters)), clusters))
-    f0 = np.stack([cell(c) for c in range(len(clusters))])[own]
-    V = lattice(po, f0)[0]
-    brings = {}                                               # vertices a cell brings -> the fewest of its points that do
-    for k in range(1, len(NEAR) + 1):
-        brings.setdefault(lattice(po, np.concatenate([f0, cell(400) + NEAR[:k]]))[0] - V, k)
-    best = {0: []}                                            # vertices still wanted -> the cells' point counts (fewest points)
-    for want in range(1, v_target - V + 1):
-        ways = [best[want - d] + [k] for d, k in brings.items() if d > 0 and want - d in best]
-        if ways:
-            best[want] = min(ways, key=sum)
-    assert v_target - V in best, (clusters, V, v_target, brings)
-    f0 = np.concatenate([f0] + [cell(400 + i) + NEAR[:k] for i, k in enumerate(best[v_target - V])])
-    V, rows = lattice(po, f0)
-    assert V == v_target, (clusters, V, v_target)
-    pb = wl.slam_problem(len(f0), seed=seed)
-    pb["kernels"] = [(np.ascontiguousarray(f0, np.float32), pb["kernels"][0][1]), pb["kernels"][1]]
-    return pb, V, np.sort(rows)[::-1]
 
 
 @pytest.fixture(scope="module")
@@ -84,12 +39,6 @@ def plan_max_v0(tmp_path_factory):
         out = subprocess.run([exe, str(NA), str(V1)], check=True, capture_output=True, text=True).stdout
         return int([ln for ln in out.splitlines() if ln.startswith("P ")][0].split()[1])
     return most
-
-
-def descending(n, total):
-    """n cluster sizes, all different, that add up to at most `total`"""
-    base = total // n
-    return [base - 3 * i for i in range(n)]
 
 
 def batch_frames(po, wl, N, plan_max_v0):

@@ -1,0 +1,462 @@
+"""The chain rows of the 1024-lane loop (csrc/fused_loop.h: chain_wanted, layout_core, pst, place_products, chain_setup, chain_pads,
+chain_rows, phase S of splat_blur), on frames placed on the edges of its rules -- tests/chain_cases.py is the case table, and
+notes/chain_rows_tests.md says which case sits on which edge.  The loop is the one of k_frame (the object API's one launch per frame and
+lccrf_batch_run), k_fused<1024, 1..4> and k_fused<512, 1>, k_converge, k_general and the frame kernel's converged variant.
+
+CPU (no GPU needed): the cases are what their names claim, read from the oracle's lattices; the plans of every frame and batch, and the
+placement of every chain row, from the header's own functions compiled for the host (tests/cpp/chain_plan_test.cpp); which lane sums
+which (rank, label) at every vertex count.  The library reports a chain bit for a handle's engines 2 and 4 only: for k_frame and for a
+batch's k_fused these CPU tests are what ties a case to its path.
+
+GPU: every case through every route that can take it, against the CPU oracle after 3 iterations: Q bit for bit, the MAP labels and the
+vertex count of every term identical.  No tolerance anywhere."""
+import importlib
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import chain_cases as ch
+import compat_checker as ck
+import converge_cases as cv
+import crf_cases as cc
+import normalization_checker as nc
+from kernel_resources import HIPCC, ROOT
+
+pkg = importlib.import_module("lc-crf-slam_amd")
+N_ITER = 3
+LDS, HALF = 160 * 1024, 80 * 1024                             # csrc/fused_loop.h: kLdsLimit, kLdsHalf
+WIDE = [s for s in ch.SHAPES if s[0] == 1024]
+F32 = np.float32
+
+
+def _id(shape):
+    return "%dx%d" % shape
+
+
+@pytest.fixture(scope="module")
+def tables(po, wl):
+    """shape -> name -> Case: every frame and the oracle's lattices of both its terms, computed once"""
+    return {shape: ch.cases(po, wl, shape) for shape in ch.SHAPES}
+
+
+@pytest.fixture(scope="module")
+def plan(tmp_path_factory):
+    """ask(lines) -> the integers of every answer line of tests/cpp/chain_plan_test.cpp (csrc/fused_loop.h compiled for the host)"""
+    exe = str(tmp_path_factory.mktemp("chain_plan") / "chain_plan_test")
+    subprocess.run([HIPCC, "-O1", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "lc-crf-slam_amd", "csrc"),
+                    "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "chain_plan_test.cpp"), "-o", exe],
+                   check=True, capture_output=True)
+
+    def ask(lines):
+        out = subprocess.run([exe], input="\n".join(lines) + "\n", check=True, capture_output=True, text=True).stdout.splitlines()
+        assert len(out) == len(lines)
+        return [[int(w) for w in ln.split()[1:]] for ln in out]
+    return ask
+
+
+def _layout(plan, NA, K, V0, V1, row0, nt=1024, limit=LDS):
+    ok, chain0, prod_all, total, e0, e1, wanted = plan(["L %d %d %d %d %d %d %d" % (NA, K, V0, V1, row0, nt, limit)])[0]
+    return dict(ok=ok, chain0=chain0, prod_all=prod_all, total=total, Ecap=(e0, e1), wanted=wanted)
+
+
+def _group_sizes(table, names):
+    cs = [table[n] for n in names]
+    return max(c.pb["N"] for c in cs), max(c.V0 for c in cs), max(c.V1 for c in cs), max(int(c.rows[0]) for c in cs)
+
+
+# ---- CPU: the cases are what they claim ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", ch.SHAPES, ids=_id)
+def test_the_cases_are_what_their_names_claim(tables, shape):
+    """a condition on the inputs, read from the oracle's lattices"""
+    lanes, ppt = shape
+    tb, top = tables[shape], ch.MAX_V[lanes]
+    for c in tb.values():
+        assert max((c.pb["N"] + lanes - 1) // lanes, 1) == ppt and c.pb["N"] <= ch.MAX_N[shape], (c.name, c.pb["N"])
+        assert c.by_vertex.sum() == 3 * c.pb["N"] and len(c.by_vertex) == c.V0 and np.array_equal(np.sort(c.by_vertex)[::-1], c.rows)
+    # V0 edges: below the top wavefront pair's 16 rows, and a pair full but for one row, full, one row into the next -- up to the limit
+    edges = ch.v0_edges(lanes)
+    assert edges[:2] == [3, 12] and edges[-1] == top and len(edges) == 2 + 3 * (top // 64 + 1) - 1
+    assert {16 + 64 * j + d for j in range(top // 64) for d in (-1, 0, 1)} <= set(edges)
+    for v in edges:
+        assert tb["V%d" % v].V0 == v and tb["V%d" % v].rows[0] >= 64 and ch.chain(tb["V%d" % v], lanes), v
+    over = tb["V%d" % (top + 1)]                               # one vertex more: the long rows go to the short-row lanes
+    assert over.V0 == top + 1 and over.rows[0] >= 64 and not ch.chain(over, lanes)
+    for L in (63, 64, 65):                                     # the longest row on the threshold, the vertex count well inside
+        c = tb["row%d" % L]
+        assert c.rows[0] == L and c.V0 <= top - 48 and ch.chain(c, lanes) == (L >= 64), (L, c.V0)
+    # the ring: every length of the list beside a row of at least 64, and the longest row of a wavefront before, at and behind a trip
+    ring = [c for n, c in tb.items() if n.startswith("ring")]
+    assert set(ch.RING) <= {int(x) for c in ring for x in c.rows} and all(ch.chain(c, lanes) for c in ring)
+    every = set(ch.RING) | set(ch.RING_MORE)                   # (csrc/fused_loop.h:335-338: padded length 8n or 8n + 4, 0 .. 3 pad slots)
+    assert every <= {int(x) for c in ring for x in c.rows}
+    assert {(((x + 3) & ~3) >> 2 & 1, -x % 4) for x in every} == {(flag, pads) for flag in (0, 1) for pads in (0, 1, 2, 3)}
+    for L in ch.TRIPS:                                         # the top pair's longest row: 3 trips less one, 3 exactly, one into the 4th ...
+        c = tb["trip%d" % L]
+        assert c.rows[0] == L and ch.chain(c, lanes)
+    assert {L % 32 for L in ch.TRIPS} == {31, 0, 1}
+    for L in (31, 32, 33):                                     # ... and the second pair's (ranks 16 and 17): one trip less one, one, one more
+        c = tb["wave1_%d" % L]
+        assert c.V0 > 17 and c.rows[14] >= 64 and c.rows[16] == L > c.rows[18] and ch.chain(c, lanes), (L, c.rows[:19])
+    if ppt >= 2:                                               # the counting sort's last bucket: (len + 3) >> 4 saturates at 63
+        c = tb["buckets"]
+        assert {1004, 1005} <= {int(x) for x in c.rows} and ((1004 + 3) >> 4, (1005 + 3) >> 4) == (62, 63) and ch.chain(c, lanes)
+    assert tb["tie"].rows[15] == tb["tie"].rows[16] >= 64 and ch.chain(tb["tie"], lanes)           # the 16th and 17th rows tie
+    assert tb["no_tie"].rows[15] > tb["no_tie"].rows[16] and ch.chain(tb["no_tie"], lanes)         # ... and do not
+    long_rows = {n: int((c.rows >= 64).sum()) for n, c in tb.items() if ch.chain(c, lanes)}
+    assert min(long_rows.values()) < 16 < max(long_rows.values()) and 16 in long_rows.values(), long_rows
+    for r in (0, 1, 2, 3):                                     # rows of no products among the chain rows: the phantom points' vertices
+        c = tb["empty%d" % r]
+        assert c.pb["N"] % 4 == r and int((c.rows == 0).sum()) == (3 if r else 0) and ch.chain(c, lanes), (r, c.rows[-4:])
+    # the batches: whose frame decides for all of them
+    gr = ch.groups(tb, lanes, ppt)
+    most = ch.FITS_MAX_V.get(ppt, top)                          # (frames of 3073 points: what the fused plan has room for, see chain_cases)
+    assert {v for v in edges if v <= most} <= {tb[n].V0 for n in gr["edges"][0]} and all(len(names) + 1 < 64 for names, _ in gr.values())
+    assert most in edges and _group_sizes(tb, gr["edges"][0])[1] == most and _group_sizes(tb, gr["edges"][0])[3] >= 64
+    assert ("beyond" in gr) == (ppt == 4) and (ppt < 4 or _group_sizes(tb, gr["beyond"][0])[1] == top)
+    assert _group_sizes(tb, gr["over"][0])[1] == top + 1 and _group_sizes(tb, gr["over"][0])[3] >= 64
+    assert _group_sizes(tb, gr["row63"][0])[3] == 63 and _group_sizes(tb, gr["row64"][0])[3] == 64
+    assert max(_group_sizes(tb, gr[g][0])[1] for g in ("row63", "row64")) <= top
+
+
+# ---- CPU: plans and placement from the header's own functions ------------------------------------------------------------------
+def test_the_constants_the_cases_are_built_around(plan):
+    assert plan(["C"])[0] == [ch.TOP, ch.MIN_ROW, 14, ch.MAX_V[1024], ch.MAX_V[512], LDS, HALF]
+
+
+@pytest.mark.parametrize("shape", ch.SHAPES, ids=_id)
+def test_plans_of_every_frame_and_batch(tables, plan, shape):
+    """layout_core as the launchers call it: a handle's frame on its own sizes (csrc/fused_variant.h:24, fused_engine.hip:549), a batch on
+    the largest of its frames'; chain_wanted alone is k_frame's decision (csrc/frame_body.inc:612, 693), per frame"""
+    lanes, ppt = shape
+    tb = tables[shape]
+    seen, unfit = set(), set()
+    for c in tb.values():
+        for K in (2, 1):
+            lay = _layout(plan, c.pb["N"], K, c.V0, c.V1 if K == 2 else 0, int(c.rows[0]))
+            if not lay["ok"]:
+                unfit.add((K, c.name))
+                continue
+            assert lay["total"] <= LDS and lay["chain0"] == lay["wanted"] == int(ch.chain(c)), (c.name, K, lay)
+            seen.add((K, lay["chain0"], lay["prod_all"]))
+    # frames of 3073 points with two terms: the V0 edges from 399 on have no room for their chain plane in the 160 KiB
+    assert unfit == ({(2, "V%d" % v) for v in ch.v0_edges(1024) if v > ch.FITS_MAX_V[4]} if ppt == 4 else set()), unfit
+    # two terms with chain rows: a product buffer each up to ~2000 points (prod_all = 1), one for both at ~3000, both within 2049 ..
+    chain2 = {p for K, chain0, p in seen if K == 2 and chain0}
+    assert chain2 == {1: {1}, 2: {1}, 3: {0, 1}, 4: {0}}[ppt] and {(1, 0, 1), (1, 1, 1)} <= seen, seen
+    for g, (names, chain) in ch.groups(tb, lanes, ppt).items():
+        NA, V0, V1, row0 = _group_sizes(tb, names)
+        wide = _layout(plan, NA, 2, V0, V1, row0)
+        if g == "beyond":
+            assert not wide["ok"], (g, wide)                   # (the batch goes to the streaming engine)
+            continue
+        assert wide["ok"] and wide["total"] <= LDS, (g, wide)
+        if lanes == 1024:
+            assert wide["chain0"] == int(chain), (g, wide)
+        else:                                                  # csrc/fused_engine.hip:554-564 small_layout: 512 lanes in half the LDS
+            half = _layout(plan, NA, 2, V0, V1, row0, 512, HALF)
+            assert NA <= 512 and V0 <= 512
+            if g == "over":                                    # long rows that four wavefront pairs cannot take: the batch keeps 1024 lanes
+                assert row0 >= 64 and not half["wanted"] and wide["chain0"] == 1, (g, half, wide)
+            else:
+                assert half["ok"] and half["total"] <= HALF and half["chain0"] == half["wanted"] == int(chain), (g, half)
+
+
+def _placement(plan, queries):
+    for (tag, NA, lens), (slack, aligned, end, ecap) in zip(queries, plan(["P %d %d %s" % (NA, len(lens), " ".join(map(str, lens)))
+                                                                          for _, NA, lens in queries])):
+        # pst(row[v+1], v+1) - pst(row[v], v) >= len_v + 11: the row padded to 4 products and its eight zeros; the last row's end in the plane
+        assert aligned == 1 and (len(lens) < 2 or slack >= 11) and end <= ecap, (tag, slack, aligned, end, ecap)
+
+
+@pytest.mark.parametrize("shape", ch.SHAPES, ids=_id)
+def test_every_chain_row_has_room_for_its_pads(tables, plan, shape):
+    tb = tables[shape]
+    _placement(plan, [(c.name, c.pb["N"], [int(x) for x in c.by_vertex]) for c in tb.values() if c.V0 <= ch.MAX_V[1024]])
+
+
+def test_random_rows_have_room_for_their_pads(plan):
+    """a few thousand row vectors: up to 464 vertices, 3 N <= 12288 products -- spread evenly, piled on a few vertices, all of one
+    length modulo 4, many empty"""
+    rng = np.random.default_rng(464)
+    queries = []
+    for i in range(3000):
+        V = int(rng.integers(1, 465)) if i % 7 else 464
+        N = int(rng.integers(1, 4097)) if i % 5 else 4096
+        kind = i % 4
+        if kind == 0:
+            p = np.full(V, 1.0 / V)
+        elif kind == 1:
+            p = rng.dirichlet(np.full(V, 0.05))
+        elif kind == 2:
+            p = rng.dirichlet(np.full(V, 1.0)) * (rng.random(V) < 0.3)
+            p = p / p.sum() if p.sum() else np.full(V, 1.0 / V)
+        else:
+            p = None
+        if p is None:                                          # lengths of one residue modulo 4, the rest on the last vertex
+            r, each = int(rng.integers(0, 4)), max((3 * N // V) & ~3, 0)
+            lens = np.full(V, each + r if (each + r) * V <= 3 * N else 0, np.int64)
+            lens[-1] += 3 * N - lens.sum()
+        else:
+            lens = rng.multinomial(3 * N, p)
+        assert lens.sum() == 3 * N and lens.min() >= 0
+        queries.append((i, N, [int(x) for x in lens]))
+    _placement(plan, queries)
+
+
+# ---- CPU: which lane sums which row --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("lanes", (1024, 512))
+def test_every_row_and_label_has_one_lane_at_every_vertex_count(plan, lanes):
+    """The two expressions stay where they are in csrc/fused_loop.h -- moved into functions of their own they changed the machine code of
+    four units (notes/chain_rows_tests.md) -- and are restated here: chain_setup, line 331
+        r = pr == 0 ? (chain_top_rank(ln) >= 0 ? chain_top_rank(ln) : V0) : kChainTop + ((pr - 1) << 6) + ln      (pr = tid >> 7, ln = tid & 63)
+    a lane has a row when r < V0 (line 333) and sums label l = (tid >> 6) & 1 of it (lines 330, 336); phase S, lines 423-424, lets lanes with
+        (tid >> 7) < npairs,  npairs = 1 + ((max(V0 - kChainTop, 0) + 63) >> 6)
+    into the chain.  chain_top_rank is the header's own, printed by the host program."""
+    top_rank = plan(["T"])[0]
+    assert len(top_rank) == 64 and sorted(r for r in top_rank if r >= 0) == list(range(ch.TOP))
+
+    def rank(tid, V0):
+        pr, ln = tid >> 7, tid & 63
+        return (top_rank[ln] if top_rank[ln] >= 0 else V0) if pr == 0 else ch.TOP + ((pr - 1) << 6) + ln
+
+    for V0 in range(ch.MAX_V[lanes] + 1):
+        npairs = 1 + ((max(V0 - ch.TOP, 0) + 63) >> 6)
+        assert npairs <= lanes // 128, V0
+        held = [(rank(t, V0), (t >> 6) & 1) for t in range(128 * npairs) if rank(t, V0) < V0]
+        assert sorted(held) == [(r, l) for r in range(V0) for l in (0, 1)], V0              # every (rank, label) on exactly one lane
+        assert all(rank(t, V0) >= V0 for t in range(128 * npairs, lanes)), V0              # and no row on a lane phase S keeps out
+        assert npairs == 1 or ch.TOP + ((npairs - 2) << 6) < V0, V0                         # no pair let in without a row
+
+
+# ---- GPU -------------------------------------------------------------------------------------------------------------------------
+_REFS = {}
+
+
+def _ref(po, shape, c, terms=(0, 1), relax=1.0):
+    """(Q, labels, vertex counts) of the oracle after N_ITER iterations: computed once, shared, never changed"""
+    key = (shape, c.name, terms, relax)
+    if key not in _REFS:
+        o = cc.setup(po.OracleCRF, _terms(c.pb, terms))
+        o.inference_native(N_ITER, True, relax)
+        _REFS[key] = (o.probability().copy(), o.map().copy(), [o.kernel(k)["V"] for k in range(len(terms))])
+        o.close()
+        for a in _REFS[key][:2]:
+            a.setflags(write=False)
+    return _REFS[key]
+
+
+def _terms(pb, terms):
+    return dict(pb, kernels=[pb["kernels"][k] for k in terms])
+
+
+def _same(h, ref, tag):
+    assert np.array_equal(h.map(), ref[1]), tag
+    assert cc.same_bits(h.probability(), ref[0]), tag
+
+
+def _word(c, ppt):
+    return 1024 | ppt << 16 | int(ch.chain(c)) << 20
+
+
+def _fits(plan, c, K=2):
+    """has the fused plan room for the frame?  (layout_core; all but the widest chain planes of 3073 points: chain_cases.FITS_MAX_V)"""
+    return bool(_layout(plan, c.pb["N"], K, c.V0, c.V1 if K == 2 else 0, int(c.rows[0]))["ok"])
+
+
+GROUPS = [(s, g) for s in WIDE for g in ("edges", "over", "row63", "row64") + (("beyond",) if s[1] == 4 else ())]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", WIDE, ids=_id)
+def test_handles_fresh_and_built(po, tables, plan, shape):
+    """inference() right after add_pairwise is k_frame in its two-workgroup form, with LCCRF_OPT_SINGLE_WORKGROUP in one workgroup: the
+    chain decision is the frame's own and nothing reports it (test_plans_of_every_frame_and_batch holds chain_wanted to every case).
+    The probes build the lattices and read their sizes: inference() then runs k_fused on them and lccrf_get_engine reports lanes, points per lane and the
+    chain bit.  The appearance term alone (K = 1), damped, takes both routes as well."""
+    for c in tables[shape].values():
+        for terms, relax in (((0, 1), 1.0), ((0,), 0.8)):
+            ref = _ref(po, shape, c, terms, relax)
+            pb = _terms(c.pb, terms)
+            h = cc.setup(pkg.DenseCRFHIP, pb)
+            h.inference(N_ITER, True, relax)
+            _same(h, ref, (c.name, terms, "fresh"))
+            fits = _fits(plan, c, len(terms))
+            assert h.engine() == (3, 0) or not fits, (c.name, h.engine())
+            assert [h.kernel(k)["V"] for k in range(len(terms))] == ref[2], c.name          # V per term: the lattices are built ...
+            h.splat_plan(0)                                      # ... and a probe of the plan makes their sizes known to the host
+            h.inference(N_ITER, True, relax)
+            _same(h, ref, (c.name, terms, "built"))
+            assert h.engine() == ((2, _word(c, shape[1])) if fits else (1, 0)), (c.name, h.engine(), _word(c, shape[1]))
+            h.close()
+        h = pkg.DenseCRFHIP(c.pb["N"], 2)
+        h.set_option(pkg.OPT_SINGLE_WORKGROUP, 1)
+        h.set_unary_from_label(c.pb["label"], c.pb["conf"])
+        for f, w in c.pb["kernels"]:
+            h.add_pairwise(f, w)
+        h.inference(N_ITER, True)
+        _same(h, _ref(po, shape, c), (c.name, "one workgroup"))
+        assert h.engine() == (3, 0) or not _fits(plan, c), (c.name, h.engine())
+        h.close()
+
+
+def _batch(tb, names, F=None, middle=True):
+    """(batch, the frame index -> case or None): the cases, an empty frame in the middle, tiled to F frames; max_points above the largest"""
+    cs = [tb[n] for n in names]
+    if middle:
+        cs.insert(len(cs) // 2, None)
+    order = [cs[f % len(cs)] for f in range(F or len(cs))]
+    assert order[0] is not None                                # (the first frame names the batch's weights and confidence)
+    pbs = [c.pb if c else cc.empty_problem(2, [2, 2]) for c in order]
+    return cc.batch_of(pbs, maxN=max(c.pb["N"] for c in cs if c) + 5), order
+
+
+def _same_batch(po, shape, b, order, tag, first_and_last=False):
+    Q, M = b.probability(), b.map()
+    Vs = [b.lattice_sizes(k) for k in range(2)]
+    last = {id(c): f for f, c in enumerate(order)}
+    seen = set()
+    for f, c in enumerate(order):
+        if c is None:
+            assert [int(Vs[k][f]) for k in range(2)] == [0, 0], (tag, f)
+            continue
+        if first_and_last and id(c) in seen and last[id(c)] != f:
+            continue
+        seen.add(id(c))
+        ref = _ref(po, shape, c)
+        n = c.pb["N"]
+        assert np.array_equal(M[f, :n], ref[1]), (tag, f, c.name)
+        assert cc.same_bits(Q[f, :n], ref[0]), (tag, f, c.name)
+        assert [int(Vs[k][f]) for k in range(2)] == ref[2], (tag, f, c.name)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape,group", GROUPS, ids=lambda x: x if isinstance(x, str) else _id(x))
+def test_batches_of_a_few_frames(po, tables, shape, group):
+    """below 64 frames: run() is k_frame, a decision per frame; build() + inference() is k_build_small + k_fused<1024> in its self-contained
+    mode, ONE decision for the batch -- the library does not report it: test_plans_of_every_frame_and_batch holds the host's layout_core to
+    chain rows for `edges` and `row64` and to short rows for `over` (one frame one vertex beyond the lanes) and `row63`."""
+    b, order = _batch(tables[shape], ch.groups(tables[shape], 1024, shape[1])[group][0])
+    assert len(order) < 64 and order.count(None) == 1 and 0 < order.index(None) < len(order) - 1
+    b.run(N_ITER, True)
+    assert b.engine() == 3                                     # (a frame the one-launch kernel has no room for is re-run alone)
+    _same_batch(po, shape, b, order, (group, "run"))
+    b.build()
+    b.inference(N_ITER, True)
+    if group == "beyond":                                      # (no room for the plan: test_plans_of_every_frame_and_batch)
+        assert b.engine() == 1
+    else:
+        assert b.engine() == 2 and b.fused_shape() == (1024, 1), (b.engine(), b.fused_shape())
+    assert b.last_prepare()[1] == 0
+    _same_batch(po, shape, b, order, (group, "build + inference"))
+    b.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("group", ("edges", "row64"))
+@pytest.mark.parametrize("shape", WIDE, ids=_id)
+def test_the_same_frames_tiled_to_64(po, tables, shape, group):
+    """64 frames and more run from prepared launch records: inference three times -- self-contained, prepare + run, run from the records"""
+    b, order = _batch(tables[shape], ch.groups(tables[shape], 1024, shape[1])[group][0], F=64)
+    b.build()
+    for tag in ("self-contained", "prepare + run", "from the records"):
+        b.inference(N_ITER, True)
+        assert b.engine() == 2 and b.fused_shape() == (1024, 1), (tag, b.engine(), b.fused_shape())
+        _same_batch(po, shape, b, order, (group, tag), first_and_last=True)
+    assert b.last_prepare()[1] == 1
+    b.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("group", ("edges", "over", "row63", "row64"))
+def test_256_frames_of_at_most_512_points(po, tables, group):
+    """two frames per CU in 512-lane workgroups (k_fused<512, 1>): four wavefront pairs, at most 208 vertices on the chain lanes; the batch
+    with a frame of 209 keeps the 1024-lane shape.  run() on the same batch is the 512-lane k_frame, a decision per frame."""
+    shape = (512, 1)
+    b, order = _batch(tables[shape], ch.groups(tables[shape], 512)[group][0], F=256)
+    b.build()
+    for tag in ("self-contained", "prepare + run", "from the records"):
+        b.inference(N_ITER, True)
+        assert b.engine() == 2 and b.fused_shape() == ((1024, 1) if group == "over" else (512, 2)), (tag, b.engine(), b.fused_shape())
+        _same_batch(po, shape, b, order, (group, tag), first_and_last=True)
+    assert b.last_prepare()[1] == 1
+    b.run(N_ITER, True)
+    assert b.engine() == 3
+    _same_batch(po, shape, b, order, (group, "run"), first_and_last=True)
+    b.close()
+
+
+# ---- GPU: the converged calls ----------------------------------------------------------------------------------------------------
+CAP = 8
+_TRACES = {}
+
+
+def _trace(po, shape, c):
+    if (shape, c.name) not in _TRACES:
+        _TRACES[shape, c.name] = cv.oracle_trace(po, c.pb, 1.0, CAP)
+        _TRACES[shape, c.name].setflags(write=False)
+    return _TRACES[shape, c.name]
+
+
+def _edge_cases(tb):
+    return [tb["V%d" % v] for v in ch.v0_edges(1024)] + [tb["V465"]]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", WIDE[:2], ids=_id)
+def test_converged_calls_on_the_vertex_count_edges(po, tables, shape):  # (one and two points per lane: every frame fits the plan)
+    """k_converge on a handle's built lattices (Potts terms), the batch's inference_converged and the frame kernel's converged variant
+    (run_converged) under a cap: Q, the labels and the report at the iteration the oracle's trace stops at (converge_cases.expect)"""
+    cs = _edge_cases(tables[shape])
+    crit, tol = cv.LABELS, F32(0)                             # (these frames settle slowly: some stop on their labels, most at the cap)
+    wants = []
+    for c in cs:
+        tr = _trace(po, shape, c)
+        want = cv.expect(tr, crit, tol, CAP)
+        wants.append(want)
+        h = cc.setup(pkg.DenseCRFHIP, c.pb)
+        got = h.inference_converged(CAP, crit, tol, True, 1.0)
+        assert h.engine() == (2, _word(c, shape[1])), (c.name, h.engine())
+        assert cv.same_report(got, want), (c.name, got, want)
+        assert cc.same_bits(h.probability(), tr[want[0]]) and np.array_equal(h.map(), cv.labels_of(tr[want[0]])), c.name
+        h.close()
+    assert len({w[0] for w in wants}) >= 2, wants                # (they do not all stop at the cap)
+    b = cc.batch_of([c.pb for c in cs], maxN=max(c.pb["N"] for c in cs) + 5)
+    for tag in ("inference_converged", "run_converged"):
+        if tag == "inference_converged":
+            b.build()
+            b.inference_converged(CAP, crit, tol, True, 1.0)
+            assert b.engine() == 2
+        else:
+            b.run_converged(CAP, crit, tol, True, 1.0)
+        rep, Q, M = b.convergence(), b.probability(), b.map()
+        for f, (c, want) in enumerate(zip(cs, wants)):
+            tr, n = _trace(po, shape, c), c.pb["N"]
+            assert cv.same_report({k: v[f] for k, v in rep.items()}, want), (tag, c.name, want)
+            assert cc.same_bits(Q[f, :n], tr[want[0]]) and np.array_equal(M[f, :n], cv.labels_of(tr[want[0]])), (tag, c.name)
+    b.close()
+
+
+# ---- GPU: terms with a matrix or a normalisation mode ----------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", WIDE[:2], ids=_id)
+def test_general_terms_on_the_vertex_count_edges(po, tables, shape):
+    """k_general: the appearance term with a matrix that is not the identity, the smoothness term SYMMETRIC -- against the float32
+    restatement of tests/normalization_checker.py; engine 4 and its shape word"""
+    rng = np.random.default_rng([77, 2, 2])
+    mats = [(np.eye(2) + 0.3 * rng.standard_normal((2, 2))).astype(F32), None]
+    modes = [nc.AFTER, nc.SYMMETRIC]
+    for c in _edge_cases(tables[shape]):
+        o = cc.setup(po.OracleCRF, c.pb)
+        U, nrm = o.unary(), [o.kernel(k)["norm"] for k in range(2)]
+        o.close()
+        w = nc.weights_f32(c.pb, nrm, modes)
+        want = nc.restate_trace_f32(U, nc.feats(c.pb), w, mats, modes, N_ITER, 1.0, nrm)[N_ITER]
+        h = cc.setup(pkg.DenseCRFHIP, dict(c.pb, kernels=[(f, x) for (f, _), x in zip(c.pb["kernels"], w)]))
+        h.set_normalization(1, modes[1])
+        h.set_pairwise_compatibility(0, mats[0])
+        h.inference(N_ITER, True, 1.0)
+        assert h.engine() == (4, _word(c, shape[1])), (c.name, h.engine())
+        assert cc.same_bits(h.probability(), want) and np.array_equal(h.map(), ck.map_of(want)), c.name
+        h.close()

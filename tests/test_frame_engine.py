@@ -2,8 +2,9 @@
 lattice build + normalisation + mean-field inference of a frame in ONE launch, against
   (1) the committed golden vectors generated from the reference itself (tests/golden/slam.npz),
   (2) the oracle on fresh seeded frames of every size class (every N % 4, 1 .. 4 points per lane),
-  (3) adversarial lattices (one cell, long rows, rows on the chain's unit boundaries, lattices too large
-      for the kernel -> its fallback), ragged batches, raw unaries, relax != 1, a single kernel,
+  (3) adversarial lattices (one cell, long rows, rows of 8 and 9 products -- short rows: the chain's unit
+      boundaries are tests/test_chain_rows.py's --, lattices too large for the kernel -> its fallback),
+      ragged batches, raw unaries, relax != 1, a single kernel,
   (4) the two-kernel path (LCCRF_NO_FRAME) bit for bit.
 Bar: labels identical, Q bit-identical, V equal to the reference's M_.
 """

@@ -84,9 +84,10 @@ def test_hip_matches_oracle_slam_sizes(po, wl, N):
                                      ("two_clusters", 2600), ("rows_of_8", 2000), ("rows_of_8", 1030),
                                      ("sparse", 1200)])
 def test_fused_engine_on_adversarial_lattices(po, wl, shape, N):
-    """Very long rows (chain path, also with the shared product buffer and 3-4 points per lane), row
-    lengths on the chain's unit boundaries, and lattices too large for the chain path: the engine
-    the library picks must still reproduce the oracle bit for bit."""
+    """Very long rows (chain path, also with the shared product buffer and 3-4 points per lane), rows of
+    8 and 9 products (`rows_of_8`: far below the 64 products from which the chain path is taken -- these
+    ride the short-row lanes; the chain's unit boundaries are tests/test_chain_rows.py's), and lattices
+    too large for the chain path: the engine the library picks must still reproduce the oracle bit for bit."""
     pb = cc.shaped_problem(wl, N, shape, seed=5)
     o, h = cc.setup(po.OracleCRF, pb), cc.setup(pkg.DenseCRFHIP, pb)
     o.inference_native(4, True)
