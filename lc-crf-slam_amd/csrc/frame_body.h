@@ -37,14 +37,14 @@ __device__ __forceinline__ unsigned long long dual_load2(const unsigned *p)   //
     return __hip_atomic_load(reinterpret_cast<const unsigned long long *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// CONV: what the convergence form takes beside FrameArgs (whose n_iter is then the cap), and the LDS its reduction needs behind the
-// loop's plan.  A frame whose plan leaves no such room under the launch's LDS flags itself unfit, as one whose lattices do not fit.
+// CONV: what the convergence form takes beside FrameArgs (whose n_iter is then the cap).  Its reduction needs kConvergeLds bytes
+// (fused_loop.h) behind the loop's plan: a frame whose plan leaves no such room under the launch's LDS flags itself unfit, as one
+// whose lattices do not fit.
 struct FrameConv {
     int criterion;                        // LCCRF_STOP_* bits (1 .. 3)
     float tol;
     ConvergeOut out;                      // [F] each: iterations, delta, changed, converged
 };
-constexpr int kFrameConvLds = 16;         // four words: {bits of d, c} x iteration parity
 constexpr int kArgOffConv = (int)((kArgOffA + sizeof(FrameArgs) + alignof(FrameConv) - 1) / alignof(FrameConv) * alignof(FrameConv));
 static_assert(alignof(FrameConv) == 8, "k_frame_converge's arguments (CrfDev, FrameArgs, FrameConv) as the ABI lays them out");
 // A kernel argument as the body reads it where it is used.  LATE (the convergence form): loaded there, through the argument segment's

@@ -54,12 +54,7 @@
             if (tid < K && a.V_out[tid]) a.V_out[tid][f] = 0;
             if (tid == 0 && a.frame_status) a.frame_status[f] = 0;
             if constexpr (CONV) {                         // nothing was iterated: 0 / 0.0f / 0 / 0
-                if (tid == 0) {
-                    fc.out.iterations[f] = 0;
-                    fc.out.delta[f] = 0.0f;
-                    fc.out.changed[f] = 0;
-                    fc.out.converged[f] = 0;
-                }
+                if (tid == 0) report_convergence(fc.out, f, 0, 0.0f, 0, 0);
             }
             publish_done();
         }
@@ -114,6 +109,7 @@
     int V[K], row0max = 0;
     unsigned pk[PPT][K][D1];              // (vertex id + 1) | place in the row << 16, as the HBM records of k_fused
     int cursor = kHdr;
+    auto take = [&](int &o, int bytes) { const int r = o; o += (bytes + 15) & ~15; return r; };
 
 #pragma unroll
     for (int k = 0; k < K; ++k) {
@@ -198,7 +194,6 @@
         V[k] = Vk;
         FL_PSTAMP();
         const int W = (((Npad + 31) >> 5) + 3) & ~3;      // bitmap words per vertex, a multiple of 4
-        auto take = [&](int &o, int bytes) { const int r = o; o += (bytes + 15) & ~15; return r; };
         lay.val[k][0] = take(cursor, (Vk + 1) * 8);
         lay.val[k][1] = take(cursor, (Vk + 1) * 8);
         lay.nbr[k] = take(cursor, D1 * Vk * 4);
@@ -512,7 +507,6 @@
         // do not occupy scalar registers all through kernel 1's build (which is short of them)
         int v0 = V[0], cur = kHdr;
         asm volatile("" : "+s"(v0));
-        auto take = [&](int &o, int bytes) { const int r = o; o += (bytes + 15) & ~15; return r; };
         lay.val[0][0] = take(cur, (v0 + 1) * 8);
         lay.val[0][1] = take(cur, (v0 + 1) * 8);
         lay.nbr[0] = take(cur, D1 * v0 * 4);
@@ -648,7 +642,6 @@
         __syncthreads();
         const int Vk = __builtin_amdgcn_readfirstlane(hdr->dual_V);        // (scalar: every LDS offset below derives from it)
         const int dual_ok = __builtin_amdgcn_readfirstlane(hdr->dual_ok);
-        auto take = [&](int &o, int bytes) { const int r = o; o += (bytes + 15) & ~15; return r; };
         lay.val[1][0] = take(cursor, (Vk + 1) * 8);
         lay.val[1][1] = take(cursor, (Vk + 1) * 8);
         lay.nbr[1] = take(cursor, D1 * Vk * 4);
@@ -707,7 +700,7 @@
                 }
                 lay.prod_all = all;
                 lay.total = o;
-                ok = o + (CONV ? kFrameConvLds : 0) <= al.lds_total;   // (CONV: with room for the reduction's words behind the plan)
+                ok = o + (CONV ? kConvergeLds : 0) <= al.lds_total;   // (CONV: with room for the reduction's words behind the plan)
             }
             if (!ok) {
                 flag_unfit();
@@ -739,12 +732,8 @@
         const FrameConv &fz = args_view<true>(fc, kArgOffConv, kargs);
         Converge cv{fz.criterion, fz.tol, lay.total, 0, 0, 0, 0u};
         mean_field<PPT, K, 2, NT, false, false, true>(smem, lay, V, N, tid, pr, cl, alpha, al.n_iter, al.relax, ins, first_p, nullptr, &cv);
-        if (tid == 0) {                                   // (uniform values: every lane holds them; ordinary vector stores)
-            fz.out.iterations[f] = cv.iterations;
-            fz.out.delta[f] = __uint_as_float(cv.delta);
-            fz.out.changed[f] = cv.changed;
-            fz.out.converged[f] = cv.converged;
-        }
+        // (uniform values: every lane holds them; ordinary vector stores)
+        if (tid == 0) report_convergence(fz.out, f, cv.iterations, __uint_as_float(cv.delta), cv.changed, cv.converged);
     } else {
         mean_field<PPT, K, 2, NT>(smem, lay, V, N, tid, pr, cl, alpha, al.n_iter, al.relax, ins, first_p);
     }

@@ -14,9 +14,10 @@
 //     next_l += wn * s_l,  wn = w * post[i]                           (post: n, sqrtf(n), or 1.0f for BEFORE / NONE)
 //
 // Scope: frames of up to 2 x 1024 active points -- a handle's one, or every frame of a batch, indexed by blockIdx.x -- K in {1, 2} 2-D
-// terms, kernel 0 with short rows or chain rows, the self-contained prologue only (prepared launch records belong to the batches' Potts
-// path and are neither read nor written here): 8 instantiations, kept in a unit of their own so that the fused engine's kernels compile
-// exactly as they did.  Run until converged: fused_general_converge.hip.
+// terms, kernel 0 with short rows or chain rows, the self-contained prologue only (fused_prologue.inc: the one text k_fused includes too;
+// prepared launch records belong to the batches' Potts path and are neither read nor written here): 8 instantiations, kept in a unit of
+// their own so that a change to this kernel leaves the fused engine's kernels the code they are.  Run until converged:
+// fused_general_converge.hip.
 #include "engine.h"
 #include "device_math.h"
 #include "fused_loop.h"
@@ -40,8 +41,16 @@ struct GeneralArgs {
     float relax;
 };
 
-// k_fused<1024, PPT, K, CH, 0> (fused_engine.hip) with the terms of GeneralTerms: the same self-contained prologue -- every global
-// load issued before anything waits, indices clamped instead of branched on -- plus the pre factors beside the norms.
+// k_fused<1024, PPT, K, CH, 0> (fused_engine.hip) with the terms of GeneralTerms: the same self-contained prologue
+// (fused_prologue.inc) plus GeneralTerms' uniform members behind the table loads and the pre factors beside the norms.
+#define FUSED_PROLOGUE_TERMS                                            \
+    gt.has_pre = 0;                                                     \
+    gt.has_mu = a.has_mu;                                               \
+    _Pragma("unroll") for (int k = 0; k < K; ++k) {                     \
+        if (a.pre[k]) gt.has_pre |= 1 << k;                             \
+        _Pragma("unroll") for (int e = 0; e < 4; ++e) gt.mu[k][e] = a.mu[k][e]; \
+    }
+#define FUSED_PROLOGUE_POINT gt.pre[s][k] = a.pre[k] ? a.pre[k][(size_t)f * kd.maxN + ic] : 1.0f;
 template <int PPT, int K, int CH>
 __global__ void __launch_bounds__(kNT, 4) k_general(CrfDev c, GeneralArgs a)
 {
@@ -64,85 +73,8 @@ __global__ void __launch_bounds__(kNT, 4) k_general(CrfDev c, GeneralArgs a)
         return;
     }
 
-    constexpr int kNbrRounds = 4096 / NT, kRowRounds = 2048 / NT;   // covers V <= 1365 in registers; larger lattices finish in copy loops
-    unsigned g_nbr[K][kNbrRounds];
-    int g_row[K][kRowRounds];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const KernelDev &kd = a.kd[k];
-        const unsigned *gn = kd.nbr16 + (size_t)f * D1 * kd.Epad;            // already (n1+1) | (n2+1) << 16
-        const int *gr = kd.rowptr + (size_t)f * (kd.Epad + 1);
-#pragma unroll
-        for (int r = 0; r < kNbrRounds; ++r) {            // element idx = j*V + v, j-major like the LDS copy
-            const int idx = min(tid + r * NT, D1 * V[k] - 1);
-            const int j = idx >= 2 * V[k] ? 2 : (idx >= V[k] ? 1 : 0);
-            g_nbr[k][r] = gn[(size_t)j * kd.Epad + (idx - j * V[k])];
-        }
-#pragma unroll
-        for (int r = 0; r < kRowRounds; ++r) g_row[k][r] = gr[min(tid + r * NT, V[k])];
-    }
-    gt.has_pre = 0;
-    gt.has_mu = a.has_mu;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        if (a.pre[k]) gt.has_pre |= 1 << k;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) gt.mu[k][e] = a.mu[k][e];
-    }
     unsigned pk[PPT][K][D1];              // (vertex id + 1) | place in the row << 16
-#pragma unroll
-    for (int s = 0; s < PPT; ++s) {
-        const int ic = min(tid + s * NT, N - 1);
-        pr.un[s] = reinterpret_cast<const float2 *>(c.unary)[(size_t)f * c.maxN + ic];
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const KernelDev &kd = a.kd[k];
-            const size_t e0 = (size_t)f * kd.Epad + (size_t)ic * D1;
-#pragma unroll
-            for (int j = 0; j < D1; ++j) {
-                pk[s][k][j] = kd.pk[e0 + j];
-                pr.bary[s][k][j] = kd.bary[e0 + j];
-            }
-            pr.wn[s][k] = kd.norm[(size_t)f * kd.maxN + ic];
-            gt.pre[s][k] = a.pre[k] ? a.pre[k][(size_t)f * kd.maxN + ic] : 1.0f;
-        }
-    }
-#pragma unroll
-    for (int s = 0; s < PPT; ++s)
-#pragma unroll
-        for (int k = 0; k < K; ++k) pr.wn[s][k] = a.kd[k].w * pr.wn[s][k];   // w * post[i]: w * n, w * sqrtf(n) or w * 1.0f (section 1g)
-
-    // ---- per-frame lattice tables into LDS --------------------------------------------
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        unsigned *nbr = reinterpret_cast<unsigned *>(smem + lay.nbr[k]);
-        unsigned short *row = reinterpret_cast<unsigned short *>(smem + lay.row[k]);
-#pragma unroll
-        for (int r = 0; r < kNbrRounds; ++r) {
-            const int idx = tid + r * NT;
-            if (idx < D1 * V[k]) nbr[idx] = g_nbr[k][r];
-        }
-#pragma unroll
-        for (int r = 0; r < kRowRounds; ++r)
-            if (tid + r * NT <= V[k]) row[tid + r * NT] = (unsigned short)g_row[k][r];
-        // lattices with more vertices than the register rounds cover (sparse frames): plain copy loops
-        const KernelDev &kd = a.kd[k];
-        const unsigned *gn = kd.nbr16 + (size_t)f * D1 * kd.Epad;
-        for (int idx = tid + kNbrRounds * NT; idx < D1 * V[k]; idx += NT) {
-            const int j = idx >= 2 * V[k] ? 2 : (idx >= V[k] ? 1 : 0);
-            nbr[idx] = gn[(size_t)j * kd.Epad + (idx - j * V[k])];
-        }
-        const int *gr = kd.rowptr + (size_t)f * (kd.Epad + 1);
-        for (int v = tid + kRowRounds * NT; v <= V[k]; v += NT) row[v] = (unsigned short)gr[v];
-    }
-    if (tid < 16) reinterpret_cast<float *>(smem + lay.zero)[tid] = 0.0f;
-    if (tid == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            reinterpret_cast<float2 *>(smem + lay.val[k][0])[0] = make_float2(0.f, 0.f);
-            reinterpret_cast<float2 *>(smem + lay.val[k][1])[0] = make_float2(0.f, 0.f);
-        }
-    }
+#include "fused_prologue.inc"
     __syncthreads();
 
     ChainLane cl{0u, 0u};
@@ -175,13 +107,7 @@ int launch_inference_general(const CrfDev &c, const KernelDev *kds, const int *m
     a.with_map = with_map;
     a.relax = relax;
     return plan_variant<kGeneralMaxPPT>(c, kds, maxV, maxRow, 0, a, [&](auto p, auto kk, auto ch) {
-        for (int k = 0; k < c.K; ++k) {                   // (behind the plan's guard: c.K <= kMaxFusedK)
-            a.pre[k] = pre ? pre[k] : nullptr;
-            if (compat && compat[k]) {
-                a.has_mu |= 1 << k;
-                for (int e = 0; e < 4; ++e) a.mu[k][e] = compat[k][e];
-            }
-        }
+        fill_general_terms(a, c, compat, pre);
         launch_workgroups(k_general<decltype(p)::value, decltype(kk)::value, decltype(ch)::value>, c.F, kNT, a.lay.total, s, c, a);
     });
 }

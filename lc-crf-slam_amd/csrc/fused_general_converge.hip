@@ -12,7 +12,8 @@
 // of LDS behind the plan), so Q_t is bit for bit what k_general leaves after t iterations and the report is k_converge's.
 //
 // Scope: k_general's -- frames of up to 2 x 1024 active points, K in {1, 2} 2-D terms, kernel 0 with short rows or chain rows, the
-// self-contained prologue only: 8 instantiations, in a unit of their own so that k_general and k_converge compile exactly as they did.
+// self-contained prologue only (fused_prologue.inc): 8 instantiations, in a unit of their own so that a change to this kernel leaves
+// k_general and k_converge the code they are.
 //
 // Registers.  <2, 2, 1> (the C2 shape) is the tight one: with k_general's text around the CONV loop it spills 11 vector and 4 scalar
 // registers, 48 bytes of scratch per lane.  Two things bring all eight to none (notes/batch_general.md section 2; the means are
@@ -32,7 +33,6 @@ namespace {
 using namespace fl;
 
 constexpr int kGeneralConvergeMaxPPT = 2; // points per lane: k_general's bound
-constexpr int kGeneralConvergeLds = 16;   // the reduction's four words behind the plan
 
 struct GeneralConvergeArgs {
     KernelDev kd[kMaxFusedK];             // Engine::step_kdevs(): `norm` is the factor behind the filter
@@ -59,7 +59,10 @@ __device__ __forceinline__ const GeneralConvergeArgs &late(const GeneralConverge
 }
 
 // k_general's prologue and GeneralTerms (fused_general.hip) around the loop's GEN + CONV form, k_converge's words and report
-// (fused_converge.hip).
+// (fused_converge.hip).  The prologue is fused_prologue.inc's, with the pre factors beside the norms and the reduction's words,
+// both parities, zeroed behind the plan (GeneralTerms' uniform members are set behind the barrier, where the loop reads them).
+#define FUSED_PROLOGUE_POINT gt.pre[s][k] = a.pre[k] ? a.pre[k][(size_t)f * kd.maxN + ic] : 1.0f;
+#define FUSED_PROLOGUE_WORDS if (tid < 4) reinterpret_cast<unsigned *>(smem + lay.total)[tid] = 0u;
 template <int PPT, int K, int CH>
 __global__ void __launch_bounds__(kNT, 4) k_general_converge(CrfDev c, GeneralConvergeArgs a0)
 {
@@ -82,90 +85,15 @@ __global__ void __launch_bounds__(kNT, 4) k_general_converge(CrfDev c, GeneralCo
     if (N <= 0) {                         // nothing to infer (and nothing below may index an empty frame): 0 / 0.0f / 0 / 0
         const GeneralConvergeArgs &a = late(a0);
         if (a.with_map) clear_label_bits<NT>(c, f, 0, tid);
-        if (tid == 0) {
-            a.out.iterations[f] = 0;
-            a.out.delta[f] = 0.0f;
-            a.out.changed[f] = 0;
-            a.out.converged[f] = 0;
-        }
+        if (tid == 0) report_convergence(a.out, f, 0, 0.0f, 0, 0);
         return;
     }
 
-    constexpr int kNbrRounds = 4096 / NT, kRowRounds = 2048 / NT;   // covers V <= 1365 in registers; larger lattices finish in copy loops
     unsigned pk[PPT][K][D1];              // (vertex id + 1) | place in the row << 16
     {
         const GeneralConvergeArgs &a = late(a0);
         const FusedLayout &lay = a.lay;
-        unsigned g_nbr[K][kNbrRounds];
-        int g_row[K][kRowRounds];
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const KernelDev &kd = a.kd[k];
-            const unsigned *gn = kd.nbr16 + (size_t)f * D1 * kd.Epad;            // already (n1+1) | (n2+1) << 16
-            const int *gr = kd.rowptr + (size_t)f * (kd.Epad + 1);
-#pragma unroll
-            for (int r = 0; r < kNbrRounds; ++r) {            // element idx = j*V + v, j-major like the LDS copy
-                const int idx = min(tid + r * NT, D1 * V[k] - 1);
-                const int j = idx >= 2 * V[k] ? 2 : (idx >= V[k] ? 1 : 0);
-                g_nbr[k][r] = gn[(size_t)j * kd.Epad + (idx - j * V[k])];
-            }
-#pragma unroll
-            for (int r = 0; r < kRowRounds; ++r) g_row[k][r] = gr[min(tid + r * NT, V[k])];
-        }
-#pragma unroll
-        for (int s = 0; s < PPT; ++s) {
-            const int ic = min(tid + s * NT, N - 1);
-            pr.un[s] = reinterpret_cast<const float2 *>(c.unary)[(size_t)f * c.maxN + ic];
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const KernelDev &kd = a.kd[k];
-                const size_t e0 = (size_t)f * kd.Epad + (size_t)ic * D1;
-#pragma unroll
-                for (int j = 0; j < D1; ++j) {
-                    pk[s][k][j] = kd.pk[e0 + j];
-                    pr.bary[s][k][j] = kd.bary[e0 + j];
-                }
-                pr.wn[s][k] = kd.norm[(size_t)f * kd.maxN + ic];
-                gt.pre[s][k] = a.pre[k] ? a.pre[k][(size_t)f * kd.maxN + ic] : 1.0f;
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < PPT; ++s)
-#pragma unroll
-            for (int k = 0; k < K; ++k) pr.wn[s][k] = a.kd[k].w * pr.wn[s][k];   // w * post[i]: w * n, w * sqrtf(n) or w * 1.0f (section 1g)
-
-        // ---- per-frame lattice tables into LDS --------------------------------------------
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            unsigned *nbr = reinterpret_cast<unsigned *>(smem + lay.nbr[k]);
-            unsigned short *row = reinterpret_cast<unsigned short *>(smem + lay.row[k]);
-#pragma unroll
-            for (int r = 0; r < kNbrRounds; ++r) {
-                const int idx = tid + r * NT;
-                if (idx < D1 * V[k]) nbr[idx] = g_nbr[k][r];
-            }
-#pragma unroll
-            for (int r = 0; r < kRowRounds; ++r)
-                if (tid + r * NT <= V[k]) row[tid + r * NT] = (unsigned short)g_row[k][r];
-            // lattices with more vertices than the register rounds cover (sparse frames): plain copy loops
-            const KernelDev &kd = a.kd[k];
-            const unsigned *gn = kd.nbr16 + (size_t)f * D1 * kd.Epad;
-            for (int idx = tid + kNbrRounds * NT; idx < D1 * V[k]; idx += NT) {
-                const int j = idx >= 2 * V[k] ? 2 : (idx >= V[k] ? 1 : 0);
-                nbr[idx] = gn[(size_t)j * kd.Epad + (idx - j * V[k])];
-            }
-            const int *gr = kd.rowptr + (size_t)f * (kd.Epad + 1);
-            for (int v = tid + kRowRounds * NT; v <= V[k]; v += NT) row[v] = (unsigned short)gr[v];
-        }
-        if (tid < 16) reinterpret_cast<float *>(smem + lay.zero)[tid] = 0.0f;
-        if (tid < 4) reinterpret_cast<unsigned *>(smem + lay.total)[tid] = 0u;   // the reduction's words, both parities
-        if (tid == 0) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                reinterpret_cast<float2 *>(smem + lay.val[k][0])[0] = make_float2(0.f, 0.f);
-                reinterpret_cast<float2 *>(smem + lay.val[k][1])[0] = make_float2(0.f, 0.f);
-            }
-        }
+#include "fused_prologue.inc"
     }
     __syncthreads();
 
@@ -194,12 +122,7 @@ __global__ void __launch_bounds__(kNT, 4) k_general_converge(CrfDev c, GeneralCo
 
     const GeneralConvergeArgs &a = late(a0);
     store_results<PPT, K, NT>(c, f, N, tid, pr, a.with_map);
-    if (tid == 0) {                       // (uniform values: every lane holds them)
-        a.out.iterations[f] = cv.iterations;
-        a.out.delta[f] = __uint_as_float(cv.delta);
-        a.out.changed[f] = cv.changed;
-        a.out.converged[f] = cv.converged;
-    }
+    if (tid == 0) report_convergence(a.out, f, cv.iterations, __uint_as_float(cv.delta), cv.changed, cv.converged);   // (uniform values)
 }
 
 }  // namespace
@@ -219,16 +142,10 @@ int launch_inference_general_converged(const CrfDev &c, const KernelDev *kds, co
     a.tol = tol;
     a.out = out;
     // (a plan that leaves no room for the reduction's words: the caller streams)
-    return plan_variant<kGeneralConvergeMaxPPT>(c, kds, maxV, maxRow, kGeneralConvergeLds, a, [&](auto p, auto kk, auto ch) {
-        for (int k = 0; k < c.K; ++k) {                   // (behind the plan's guard: c.K <= kMaxFusedK)
-            a.pre[k] = pre ? pre[k] : nullptr;
-            if (compat && compat[k]) {
-                a.has_mu |= 1 << k;
-                for (int e = 0; e < 4; ++e) a.mu[k][e] = compat[k][e];
-            }
-        }
+    return plan_variant<kGeneralConvergeMaxPPT>(c, kds, maxV, maxRow, kConvergeLds, a, [&](auto p, auto kk, auto ch) {
+        fill_general_terms(a, c, compat, pre);
         launch_workgroups(k_general_converge<decltype(p)::value, decltype(kk)::value, decltype(ch)::value>, c.F, kNT,
-                          a.lay.total + kGeneralConvergeLds, s, c, a);
+                          a.lay.total + kConvergeLds, s, c, a);
     });
 }
 

@@ -570,6 +570,17 @@ struct Converge {
     int iterations, changed, converged;   // out: t, c_t, the criterion was met (0 / 0 / 0 when nothing was iterated)
     unsigned delta;                       // out: the bits of d_t
 };
+constexpr int kConvergeLds = 16;          // the reduction's four words behind the plan: {bits of d, c} x iteration parity
+
+// A frame's four report words (include/lccrf.h sections 1h and 2e).  The values are uniform: the caller picks the lane that stores
+// them.  A frame on which nothing was iterated reports 0 / 0.0f / 0 / 0.
+__device__ __forceinline__ void report_convergence(const ConvergeOut &out, int f, int iterations, float delta, int changed, int converged)
+{
+    out.iterations[f] = iterations;
+    out.delta[f] = delta;
+    out.changed[f] = changed;
+    out.converged[f] = converged;
+}
 
 // One iteration's decision.  Called by EVERY lane of the workgroup, outside the per-point regions (the cross-lane steps run with
 // all lanes): d / flips are the lane's own maximum (bits) and flipped slots (bit s), 0 for lanes and slots without a point.

@@ -1,9 +1,11 @@
-// fused_variant.h -- the launch plan that the fused engine's variants in units of their own (k_general, k_converge) share.
+// fused_variant.h -- the launch plan that the fused engine's variants in units of their own (k_general, k_converge,
+// k_general_converge) share, and the host helper that fills the general kernels' terms.
 //
-// Their kernels open with the text of k_fused's self-contained prologue (MODE 0 / 1, fused_engine.hip:166-240), each copied by hand: a
-// change to one of the three places is to be made in all.  As two shared __forceinline__ functions the prologue compiled within every
-// pinned figure, but on an MI355X the c2 frame then ran k_converge in 38.75 / 38.75 / 38.78 us against 38.57 / 38.63 / 38.57 and
-// k_general (matrices) in 35.85 / 35.86 / 35.93 against 35.65 / 35.73 / 35.78 -- outside the parent's spread -- so the text stays.
+// Their kernels open with k_fused's self-contained prologue (MODE 0 / 1).  It lives once, in fused_prologue.inc, and all four kernels
+// include it as text in front of their first barrier.  Text, not a function: as two shared __forceinline__ functions the prologue
+// compiled within every pinned figure, but on an MI355X the c2 frame then ran k_converge in 38.75 / 38.75 / 38.78 us against
+// 38.57 / 38.63 / 38.57 and k_general (matrices) in 35.85 / 35.86 / 35.93 against 35.65 / 35.73 / 35.78 -- outside the parent's
+// spread.  Included text compiles every one of these kernels to the instructions its own copy gave (notes/fused_general.md section 6).
 #pragma once
 
 #include "fused_loop.h"
@@ -29,6 +31,21 @@ int plan_variant(const CrfDev &c, const KernelDev *kds, const int *maxV, const i
         with_dims<0, 1>(a.lay.chain0 ? 1 : 0, [&](auto ch) { with_dims<1, MaxPPT>(ppt, [&](auto p) { launch(p, kk, ch); }); });
     });
     return fused_report(kNT, ppt, a.lay.chain0);
+}
+
+// The general kernels' terms (GeneralArgs, GeneralConvergeArgs: pre[], has_mu, mu[][]) from what their launchers are given: K host
+// pointers to the terms' [2][2] matrices as they were set and K device pointers to the factors in front of the filter, each null for
+// a term without one, either array null when no term has one.  Called behind the plan's guard: c.K <= kMaxFusedK.
+template <typename Args>
+void fill_general_terms(Args &a, const CrfDev &c, const float *const *compat, const float *const *pre)
+{
+    for (int k = 0; k < c.K; ++k) {
+        a.pre[k] = pre ? pre[k] : nullptr;
+        if (compat && compat[k]) {
+            a.has_mu |= 1 << k;
+            for (int e = 0; e < 4; ++e) a.mu[k][e] = compat[k][e];
+        }
+    }
 }
 
 }  // namespace

@@ -127,8 +127,8 @@ def test_the_constants_the_cases_are_built_around(plan):
 
 @pytest.mark.parametrize("shape", ch.SHAPES, ids=_id)
 def test_plans_of_every_frame_and_batch(tables, plan, shape):
-    """layout_core as the launchers call it: a handle's frame on its own sizes (csrc/fused_variant.h:24, fused_engine.hip:549), a batch on
-    the largest of its frames'; chain_wanted alone is k_frame's decision (csrc/frame_body.inc:612, 693), per frame"""
+    """layout_core as the launchers call it: a handle's frame on its own sizes (csrc/fused_variant.h:26, fused_engine.hip:477), a batch on
+    the largest of its frames'; chain_wanted alone is k_frame's decision (csrc/frame_body.inc:606, 686), per frame"""
     lanes, ppt = shape
     tb = tables[shape]
     seen, unfit = set(), set()
@@ -154,7 +154,7 @@ def test_plans_of_every_frame_and_batch(tables, plan, shape):
         assert wide["ok"] and wide["total"] <= LDS, (g, wide)
         if lanes == 1024:
             assert wide["chain0"] == int(chain), (g, wide)
-        else:                                                  # csrc/fused_engine.hip:554-564 small_layout: 512 lanes in half the LDS
+        else:                                                  # csrc/fused_engine.hip:482-492 small_layout: 512 lanes in half the LDS
             half = _layout(plan, NA, 2, V0, V1, row0, 512, HALF)
             assert NA <= 512 and V0 <= 512
             if g == "over":                                    # long rows that four wavefront pairs cannot take: the batch keeps 1024 lanes

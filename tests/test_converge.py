@@ -174,7 +174,7 @@ def test_handle_stops_where_the_oracle_does(po, wl, name):
     h.close()
 
 
-# The self-contained prologue (csrc/fused_converge.hip, as in k_fused and k_general) keeps a lattice's tables in registers between its loads and its LDS stores: the neighbour table
+# The self-contained prologue (csrc/fused_prologue.inc: one text, included by k_converge as by k_fused and k_general) keeps a lattice's tables in registers between its loads and its LDS stores: the neighbour table
 # of up to 4096 / 3 = 1365 vertices, the row pointers of up to 2047; what lies beyond is copied by two plain loops.  The SLAM frames
 # above stay below both (the smooth term's lattice stops growing near 1180 vertices: the image has no more cells), so one frame with
 # every point of its first term in a cell of its own (V = 3 N) is there for the loops: 683 points, the smallest with V > 2047.

@@ -7,6 +7,7 @@ lccrf_start_inference + T x lccrf_step_inference on the same handle (the streami
 kernel's range; the torch layer."""
 import ctypes as C
 import importlib
+import os
 
 import numpy as np
 import pytest
@@ -167,11 +168,19 @@ def test_cases_are_there_for_both_row_paths_and_both_points_per_lane(po, wl, gol
 
 
 def test_lattices_lie_on_both_sides_of_the_prologues_register_rounds(po, wl, golden):
-    """the self-contained prologue (csrc/fused_general.hip) keeps the neighbour table of up to 4096 / 3 = 1365 vertices and the row pointers of up to 2047 in
+    """the self-contained prologue (csrc/fused_prologue.inc, included by k_general) keeps the neighbour table of up to 4096 / 3 = 1365 vertices and the row pointers of up to 2047 in
     registers; two copy loops take what lies beyond: sparse:N1100 is there for both, every other case stays within both"""
     V = {name: _prepared(name, golden, po, wl)[3][2] for name in {**CASES, **EXTRA}}
     assert V["sparse:N1100"][0] > 2047 and V["sparse:N1100"][1] <= 1365, V["sparse:N1100"]
     assert all(max(v) <= 1365 for name, v in V.items() if name != "sparse:N1100"), V
+
+
+def test_the_prologues_text_lives_in_one_file():
+    """k_fused, k_converge, k_general and k_general_converge include one text: the line that sizes its register rounds is in no other file"""
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lc-crf-slam_amd", "csrc")
+    marker = "constexpr int kNbrRounds = 4096 / NT"
+    holders = sorted(n for n in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, n)) and marker in open(os.path.join(csrc, n), errors="replace").read())
+    assert holders == ["fused_prologue.inc"], holders
 
 
 # ---- GPU --------------------------------------------------------------------------------------------------------------------
