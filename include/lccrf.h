@@ -88,14 +88,26 @@ int  lccrf_trim_cache(void);
  *   LCCRF_OPT_EVENT_TIMING   (batches; default 1) value 0: lccrf_batch_build / _inference / _run record no HIP events around their
  *       work and lccrf_batch_last_timing reads 0.  An event record is a packet of its own between two launches: ~20 us per call on a
  *       stream that is kept busy, 1-2 % of a 1.7 ms batch -- a replay loop that does not read the timings turns them off.
+ *   LCCRF_OPT_FRAME_GENERAL   (default 0) value != 0: a handle or batch whose terms carry a label-compatibility matrix (sections 1e /
+ *       2g) or a normalisation mode other than AFTER (sections 1g / 2g) may take the ONE-launch route of a fresh frame: lattice build,
+ *       normalisation and inference in one kernel launch (csrc/frame_general.hip), the lattices never in HBM.  The four calls that
+ *       take that route are affected -- lccrf_inference on a fresh handle, lccrf_run_converged, lccrf_batch_run and
+ *       lccrf_batch_run_converged -- for two labels, one or two 2-D terms and frames of up to 2048 points (the largest n_points the
+ *       host knows, else max_points): always one 1024-lane workgroup per frame, lccrf_get_engine / lccrf_batch_get_engine report 3,
+ *       lccrf_batch_get_fused_shape 1024 / 1.  Q, the labels, the label bits and the convergence report are bit for bit those of the
+ *       option off; a frame whose lattices do not fit the kernel's LDS is re-run with the same model on the route of the option off
+ *       (lccrf_batch_get_fallback_frames counts it).  Every other call, shape and model -- Potts terms normalised AFTER above all --
+ *       takes exactly the route it takes with the option off.  Off by default: what the route saves for a learnt model is measured in
+ *       notes/frame_general.md, not yet across deployments.
  * lccrf_set_option applies to one handle (set it after lccrf_create: a handle taken from the cache starts from the defaults) and is
  * per handle only for LCCRF_OPT_VERTEX_ORDER and LCCRF_OPT_COPY_THREADS; lccrf_set_default_option applies LCCRF_OPT_SINGLE_WORKGROUP
- * to every handle and batch created afterwards in this process.                                                              */
+ * or LCCRF_OPT_FRAME_GENERAL to every handle and batch created afterwards in this process.                                    */
 typedef enum lccrf_option {
     LCCRF_OPT_SINGLE_WORKGROUP = 1,
     LCCRF_OPT_VERTEX_ORDER     = 2,
     LCCRF_OPT_COPY_THREADS     = 3,
-    LCCRF_OPT_EVENT_TIMING     = 4
+    LCCRF_OPT_EVENT_TIMING     = 4,
+    LCCRF_OPT_FRAME_GENERAL    = 5
 } lccrf_option;
 int  lccrf_set_option(lccrf_handle h, int option, int value);
 int  lccrf_set_default_option(int option, int value);
@@ -349,7 +361,8 @@ int  lccrf_inference_backward_features(lccrf_handle h, int n_iterations, float r
  * Honoured by lccrf_inference (locality mode at >= 8192 points included), lccrf_start_inference / lccrf_step_inference,
  * lccrf_pairwise_apply / _device (the `apply` of that term), lccrf_inference_backward (dL/dU and dL/dw are then those of the forward
  * with the matrices) and lccrf_inference_backward_compat.  While any term of a handle has a matrix, the one-launch frame kernel and
- * the fused engine, which hard-wire Potts, are not taken.  lccrf_inference on the shape the project exists for -- L = 2, one or two
+ * the fused engine, which hard-wire Potts, are not taken (LCCRF_OPT_FRAME_GENERAL: a fresh two-label frame of up to 2048 points takes
+ * the one-launch route's kernel for such terms, engine 3, same bits).  lccrf_inference on the shape the project exists for -- L = 2, one or two
  * 2-D terms, a frame of up to 2048 points whose lattices fit the fused engine's plan -- then runs in ONE launch on the fused
  * engine's kernel for such terms (lccrf_get_engine reports 4), with the same bits.  Everything else -- other L, d or K, 2049 points
  * and more, locality mode, lccrf_start_inference / lccrf_step_inference, the plug-in entry points, every backward call's replay --
@@ -449,7 +462,8 @@ int  lccrf_inference_backward_all(lccrf_handle h, int n_iterations, float relax,
  * Honoured by lccrf_inference (locality mode at >= 8192 points included: the factors follow the internal point order the norm
  * has), lccrf_start_inference / lccrf_step_inference, lccrf_pairwise_apply / _device (the `apply` of that term is
  * out += (w * post) * Phi(pre * in)), lccrf_inference_backward and lccrf_inference_backward_compat.  While any term of a handle is not
- * AFTER, the one-launch frame kernel and the fused engine are not taken -- exactly what a matrix of section 1e does.  lccrf_inference
+ * AFTER, the one-launch frame kernel and the fused engine are not taken -- exactly what a matrix of section 1e does, LCCRF_OPT_FRAME_GENERAL
+ * included (that kernel forms the factors itself, from the norm it holds in a register).  lccrf_inference
  * on L = 2, one or two 2-D terms and a frame of up to 2048 points whose lattices fit the fused engine's plan runs in ONE launch on
  * the fused engine's kernel for such terms (lccrf_get_engine reports 4): the pre factors sit in registers beside w * post.
  * Everything else (section 1e lists it) runs on the streaming engine's general L-label step, at L = 2 too: the pre factor is applied
@@ -541,7 +555,9 @@ int  lccrf_get_convergence(lccrf_handle h, int *iterations, float *delta, int *c
  * A frame the kernel cannot take -- lattices beyond one workgroup's LDS -- is found at the next synchronisation point and re-run
  * there with lccrf_inference_converged's engines; lccrf_get_engine then reports what it was re-run on (2 or 1).  A handle whose
  * lattices are already built and sized, or that lccrf_inference would not run in one launch, takes lccrf_inference_converged at
- * once.  Errors and the state behind the call: section 1h's.  Added WITHOUT a step of LCCRF_ABI_VERSION: probe by symbol.
+ * once -- a handle with a matrix (section 1e) or a mode (section 1g) among them, unless LCCRF_OPT_FRAME_GENERAL is set: then a frame
+ * of up to 2048 points runs in one launch here too (csrc/frame_general.hip, engine 3), re-run on section 1h's engines if it does not
+ * fit.  Errors and the state behind the call: section 1h's.  Added WITHOUT a step of LCCRF_ABI_VERSION: probe by symbol.
  * ==================================================================================== */
 int  lccrf_run_converged(lccrf_handle h, int max_iterations, int criterion, float tol, int with_map, float relax);
 
@@ -800,7 +816,7 @@ int  lccrf_batch_device_convergence(lccrf_batch_handle b, const int32_t **d_iter
  * decided per frame at the next synchronisation point, re-run there with lccrf_batch_inference_converged's engines and counted by
  * lccrf_batch_get_fallback_frames, as for lccrf_batch_run.  The getters of section 2e settle a pending run first
  * (lccrf_batch_device_convergence: the arrays are complete behind lccrf_batch_synchronize).  Every other batch builds its lattices
- * and takes lccrf_batch_inference_converged.  The argument checks of section 1h.  Added without a step of LCCRF_ABI_VERSION.
+ * and takes lccrf_batch_inference_converged (a batch with a matrix or a mode: section 2g, LCCRF_OPT_FRAME_GENERAL).  The argument checks of section 1h.  Added without a step of LCCRF_ABI_VERSION.
  * ==================================================================================== */
 int  lccrf_batch_run_converged(lccrf_batch_handle b, int max_iterations, int criterion, float tol, int with_map, float relax,
                                void *stream);
@@ -830,7 +846,9 @@ int  lccrf_batch_run_converged(lccrf_batch_handle b, int max_iterations, int cri
  *     workgroup's LDS, lccrf_batch_set_engine(1) -- runs the streaming engine's general L-label step for all frames (engine 1), the
  *     converged call with section 2e's bookkeeping behind each step.
  *   - lccrf_batch_run and lccrf_batch_run_converged on such a batch are lccrf_batch_build followed by the inference call: the
- *     one-launch build + inference kernels hard-wire Potts.  lccrf_batch_get_fallback_frames reads 0.
+ *     one-launch build + inference kernels hard-wire Potts.  lccrf_batch_get_fallback_frames reads 0.  With LCCRF_OPT_FRAME_GENERAL
+ *     set, batches of frames of up to 2048 points take the one-launch kernels for such terms instead (csrc/frame_general.hip): engine
+ *     3, shape 1024 / 1, the same bits; frames that do not fit are re-run with the same model and counted.
  * Gradients: lccrf_batch_inference_backward_all (section 2h), behind the batched torch layer BatchCompatMeanFieldCRF;
  * lccrf_batch_inference_backward and lccrf_batch_inference_backward_features still return LCCRF_E_STATE on such a batch and leave it
  * as it was (section 2c).  Not covered: the half-CU shapes (512 lanes, two frames per CU) and 3 - 4 points per lane; prepared launch

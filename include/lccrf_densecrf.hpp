@@ -438,7 +438,8 @@ public:
         lccrf_check(lccrf_get_engine(h_, &e, shape), "lccrf_get_engine");
         return e;
     }
-    // lccrf_set_option (include/lccrf.h), e.g. setOption(LCCRF_OPT_SINGLE_WORKGROUP, 1) for a tracker on a shared GPU
+    // lccrf_set_option (include/lccrf.h), e.g. setOption(LCCRF_OPT_SINGLE_WORKGROUP, 1) for a tracker on a shared GPU.
+    // setOption(LCCRF_OPT_FRAME_GENERAL, 1): a learnt model (setCompatibility / setNormalization) keeps the one-launch route of a fresh frame.
     void setOption(int option, int value) { lccrf_check(lccrf_set_option(h_, option, value), "lccrf_set_option"); }
     // see the header comment: true = every inference call ends with Q in the buffer DenseCRF::getProbability() returns
     void syncThroughBase(bool on) { base_sync_ = on; }

@@ -289,6 +289,7 @@ public:
         lccrf_check(lccrf_get_lattice_size(h_, kernel, &V), "lccrf_get_lattice_size");
         return V;
     }
+    // lccrf_set_option (include/lccrf.h); setOption(LCCRF_OPT_FRAME_GENERAL, 1) keeps a learnt model on the one-launch route of a fresh frame.
     void setOption(int option, int value) { lccrf_check(lccrf_set_option(h_, option, value), "lccrf_set_option"); }
     void synchronize() const { sync(); }
     void *stream() const

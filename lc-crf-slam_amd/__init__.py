@@ -25,6 +25,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "lccrf.h")
 MAX_KERNELS = 8
 OPT_SINGLE_WORKGROUP = 1        # lccrf_option (include/lccrf.h)
 OPT_VERTEX_ORDER = 2
+OPT_FRAME_GENERAL = 5           # a learnt model (matrices, normalisation modes) may take the one-launch route of a fresh frame
 IMAGE_NONE, IMAGE_U8, IMAGE_F32 = 0, 1, 2   # lccrf_add_image_kernel's image formats
 NORMALIZE_AFTER, NORMALIZE_BEFORE, NORMALIZE_SYMMETRIC, NORMALIZE_NONE = 0, 1, 2, 3   # lccrf_normalization (section 1g)
 STOP_DELTA, STOP_LABELS = 1, 2   # lccrf_inference_converged's criterion bits (section 1h)
@@ -569,6 +570,7 @@ class BatchCRF:
     DOWNLOAD_LABEL_BITS, DOWNLOAD_MAP, DOWNLOAD_PROBABILITY = 1, 2, 4
     OPT_COPY_THREADS = 3
     OPT_EVENT_TIMING = 4
+    OPT_FRAME_GENERAL = 5
 
     def set_inputs_host_async(self, n_points, features, unary=None, label=None, conf=None, pinned=False):
         """lccrf_batch_set_inputs_host_async: the arrays are staged and uploaded without a host wait.  The arrays must already be

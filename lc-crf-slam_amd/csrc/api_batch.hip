@@ -154,6 +154,7 @@ int lccrf_batch_create(lccrf_batch_handle *out, int device_id, const lccrf_batch
     b->eng.allow_perm = true;
     b->eng.batch_owned = true;
     b->eng.opt_single_wg = default_single_wg();
+    b->eng.opt_frame_general = default_frame_general();
     rc = b->eng.init(device_id, desc->max_frames, desc->max_points, desc->n_labels);
     for (int k = 0; k < desc->n_kernels && !rc; ++k) rc = b->eng.add_kernel(desc->feat_dims[k], desc->weights[k], true, false);
     if (!rc && hipStreamSynchronize(b->eng.stream) != hipSuccess)      // every allocation is zeroed before the handle is handed out

@@ -71,6 +71,7 @@ namespace lccrf {
 
 int use_device(int device_id);                                  // api_tools.hip
 bool default_single_wg();                                       // LCCRF_OPT_SINGLE_WORKGROUP's process-wide default (lccrf_set_default_option)
+bool default_frame_general();                                   // LCCRF_OPT_FRAME_GENERAL's
 void trim_pose_stages();                                        // frees lccrf_pose_optimization's staging areas (lccrf_trim_cache)
 void trim_unary_stage();                                        // unary_builder.hip: frees lccrf_unary_build's staging (lccrf_trim_cache)
 void trim_bf_stage();                                           // bf_match.hip: frees lccrf_bf_match's staging (lccrf_trim_cache)

@@ -494,6 +494,18 @@ int launch_frame(const CrfDev &c, const KernelDev *kds, int n_iter, int with_map
 void launch_frame_converged(const CrfDev &c, const KernelDev *kds, int max_iter, int criterion, float tol, int with_map, float relax,
                             int *status, int *frame_status, const int16_t *label, const float *tbl5, const ConvergeOut &out,
                             hipStream_t s, unsigned *done = nullptr, unsigned done_epoch = 0);
+// The two launches above for terms with a label-compatibility matrix or a normalisation mode (frame_general.hip; include/lccrf.h
+// LCCRF_OPT_FRAME_GENERAL): frames launch_frame takes of at most 2048 active points, one 1024-lane workgroup per frame, never the
+// two-workgroup or a half-CU shape; the factors of every mode are formed in the kernel from the norm it holds.
+//   compat     null, or K HOST pointers: term k's [2][2] matrix or null -- passed to the kernel by value (Engine::host_matrices)
+//   norm_mode  K lccrf_normalization values
+void launch_frame_general(const CrfDev &c, const KernelDev *kds, int n_iter, int with_map, float relax, int *status, int *frame_status,
+                          const int16_t *label, const float *tbl5, const float *const *compat, const int *norm_mode, hipStream_t s,
+                          unsigned *done = nullptr, unsigned done_epoch = 0);
+void launch_frame_general_converged(const CrfDev &c, const KernelDev *kds, int max_iter, int criterion, float tol, int with_map,
+                                    float relax, int *status, int *frame_status, const int16_t *label, const float *tbl5,
+                                    const float *const *compat, const int *norm_mode, const ConvergeOut &out, hipStream_t s,
+                                    unsigned *done = nullptr, unsigned done_epoch = 0);
 bool frame_lean_wanted(const CrfDev &c);              // would launch_frame take the lean shape for this batch, given the area?
 size_t frame_lean_rec_bytes(int frames);
 size_t frame_dual_bytes(int frames);

@@ -1,6 +1,7 @@
-// frame_body.h -- what the two kernels built on the one-launch frame body share (frame_engine.hip: k_frame, fixed iteration count;
-// frame_converge.hip: k_frame_converge, until converged): the scan scratch in LDS, the hand-off area of the two-workgroup form, the
-// convergence form's arguments, the hash capacity.  The body itself is frame_body.inc.
+// frame_body.h -- what the kernels built on the one-launch frame body share (frame_engine.hip: k_frame, fixed iteration count;
+// frame_converge.hip: k_frame_converge, until converged; frame_general.hip: both for terms with a matrix or a normalisation mode):
+// the scan scratch in LDS, the hand-off area of the two-workgroup form, the convergence and the general form's arguments, the hash
+// capacity.  The body itself is frame_body.inc.
 #pragma once
 
 #include "engine.h"
@@ -47,6 +48,20 @@ struct FrameConv {
 };
 constexpr int kArgOffConv = (int)((kArgOffA + sizeof(FrameArgs) + alignof(FrameConv) - 1) / alignof(FrameConv) * alignof(FrameConv));
 static_assert(alignof(FrameConv) == 8, "k_frame_converge's arguments (CrfDev, FrameArgs, FrameConv) as the ABI lays them out");
+// GEN (frame_general.hip): what the general form takes beside FrameArgs -- and, until converged, FrameConv: the terms' label-
+// compatibility matrices and normalisation modes (include/lccrf.h sections 1e / 1g / 2g), by value as GeneralArgs carries the matrices.
+struct FrameGeneral {
+    float mu[kMaxFusedK][4];              // term k's 2 x 2 matrix, row-major (bit k of has_mu; unread otherwise)
+    int has_mu;                           // bit k: term k has a matrix
+    int mode[kMaxFusedK];                 // lccrf_normalization of term k
+};
+constexpr int arg_behind(size_t end, size_t align) { return (int)((end + align - 1) / align * align); }
+// k_frame_general's arguments are (CrfDev, FrameArgs, FrameGeneral), k_frame_general_converge's (CrfDev, FrameArgs, FrameConv, FrameGeneral)
+constexpr int kArgOffGeneral = arg_behind(kArgOffA + sizeof(FrameArgs), alignof(FrameGeneral));
+constexpr int kArgOffGeneralConv = arg_behind(kArgOffConv + sizeof(FrameConv), alignof(FrameGeneral));
+static_assert(alignof(FrameGeneral) == 4 && sizeof(FrameArgs) % 8 == 0 && sizeof(FrameConv) % 8 == 0 &&
+                  kArgOffGeneral == kArgOffA + (int)sizeof(FrameArgs) && kArgOffGeneralConv == kArgOffConv + (int)sizeof(FrameConv),
+              "the general frame kernels' arguments as the ABI lays them out: FrameGeneral right behind its predecessor");
 // A kernel argument as the body reads it where it is used.  LATE (the convergence form): loaded there, through the argument segment's
 // address -- which itself waits in LDS (Hdr::kargs: every wavefront stores it at the kernel's entry and reads back what it stored
 // itself, so no barrier is involved), not in a pair of scalar registers for the whole kernel; frame_build.h's late_args is the same

@@ -8,29 +8,54 @@
 // CONV = false is k_frame (fixed iteration count a.n_iter).  CONV = true runs the loop in its convergence form (fused_loop.h:
 // mean_field<..., CONV>, converge_decide) with a.n_iter as the cap and writes the four per-frame report words of include/lccrf.h
 // sections 1i and 2f.
+// Five places take a kernel's own text, as macros that keep the body's own lines unless the includer defines them (all five are
+// undefined again at the end of this file) -- frame_general.hip's kernels, whose terms carry a matrix or a normalisation mode:
+//     FRAME_BODY_GEN            the loop's GEN form (fused_loop.h): false
+//     FRAME_BODY_GT             ... and its GeneralTerms: nullptr
+//     FRAME_BODY_DECLS          in front of the normalisation, behind `al` and `cz`: nothing
+//     FRAME_BODY_FACTORS(s,k,n) per point slot s and term k with the point's norm n: pr.wn = w * n (pairwise3d.h:26-27,77)
+//     FRAME_BODY_TERMS          in front of the loop: nothing
+#ifndef FRAME_BODY_GEN
+#define FRAME_BODY_GEN false
+#endif
+#ifndef FRAME_BODY_GT
+#define FRAME_BODY_GT nullptr
+#endif
+#ifndef FRAME_BODY_DECLS
+#define FRAME_BODY_DECLS
+#endif
+#ifndef FRAME_BODY_FACTORS
+#define FRAME_BODY_FACTORS(s, k, n) pr.wn[s][k] = al.w[k] * (n);
+#endif
+#ifndef FRAME_BODY_TERMS
+#define FRAME_BODY_TERMS
+#endif
     constexpr int D1 = kD1;
+    // LATE: the arguments are read where they are used and the lane index is fenced between phases (below) -- the convergence form
+    // and the general form, whose loops leave the builds no scalar registers to hold arguments in
+    constexpr bool LATE = CONV || FRAME_BODY_GEN;
     static_assert(!DUAL || (K == 2 && NT == kNT), "the two-workgroup form splits a two-kernel frame");
     static_assert(!CONV || (!DUAL && NT == kNT), "the convergence form: one 1024-lane workgroup per frame");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int f = DUAL ? (int)(blockIdx.x >> 1) : (int)blockIdx.x;
     int tid = threadIdx.x;
-    // CONV: the lane's index is made opaque between phases.  The compiler otherwise keeps every predicate on it that two phases
+    // LATE: the lane's index is made opaque between phases.  The compiler otherwise keeps every predicate on it that two phases
     // share (tid + s * NT < N, < Npad, tid == 0, tid < 16 ...: a pair of scalar registers each) alive from one use to the next,
     // across both builds; behind a fence each phase forms its own again, one compare each.
     auto phase_fence = [&]() {
-        if constexpr (CONV) asm volatile("" : "+v"(tid));
+        if constexpr (LATE) asm volatile("" : "+v"(tid));
     };
     unsigned *kargs = reinterpret_cast<Hdr *>(smem + 192)->kargs;
-    if constexpr (CONV) park_args(kargs);
+    if constexpr (LATE) park_args(kargs);
     const int role = DUAL ? (int)(blockIdx.x & 1) : 0;    // DUAL: 0 = the frame's main workgroup, 1 = the helper that builds kernel 1
     const int N = a.n_single >= 0 ? a.n_single : c.n_points[f];     // (a single frame's count rides in the kernel arguments:
                                                                     //  c.n_points is pinned host memory there, a PCIe round trip away)
     Instr ins{a.timing, a.timing_block, 8, 0, a.timing_lane};
     FL_STAMP();
     // The last thing the frame's main workgroup does (uniform; every lane): results first, then the word the host polls.
-    // (CONV: what the ways out read of the arguments is read where they are taken -- args_view, frame_body.h -- not kept from the entry)
+    // (LATE: what the ways out read of the arguments is read where they are taken -- args_view, frame_body.h -- not kept from the entry)
     auto publish_done = [&]() {
-        const FrameArgs &ax = args_view<CONV>(a, kArgOffA, kargs);
+        const FrameArgs &ax = args_view<LATE>(a, kArgOffA, kargs);
         if (ax.done) {
             __threadfence_system();                       // this lane's stores have reached host memory ...
             __syncthreads();                              // ... every lane's have
@@ -41,8 +66,8 @@
     // single frame as they arrive -- lccrf_get_map -- finds -2 in place of the first one.)
     auto flag_unfit = [&]() {
         if (tid == 0) {
-            const FrameArgs &ax = args_view<CONV>(a, kArgOffA, kargs);
-            const CrfDev &cx = args_view<CONV>(c, 0, kargs);
+            const FrameArgs &ax = args_view<LATE>(a, kArgOffA, kargs);
+            const CrfDev &cx = args_view<LATE>(c, 0, kargs);
             if (ax.status) *ax.status = 1;
             if (ax.frame_status) ax.frame_status[f] = 1;
             if (ax.done && cx.map) cx.map[(size_t)f * cx.maxN] = (int16_t)-2;
@@ -117,8 +142,8 @@
         phase_fence();
         // ---- A: point records (elevate, round, rank, barycentric) and the keys of their three corners ----
         unsigned key[PPT][D1];
-        const FrameArgs &ab = args_view<CONV>(a, kArgOffA, kargs);               // (CONV: every build reads its arguments when it starts,
-        if constexpr (CONV) {                                             //  the hash table's place among them: none of it is kept
+        const FrameArgs &ab = args_view<LATE>(a, kArgOffA, kargs);               // (LATE: every build reads its arguments when it starts,
+        if constexpr (LATE) {                                             //  the hash table's place among them: none of it is kept
             lds_total = ab.lds_total;                                     //  in scalar registers from one build to the next)
             hcap = ab.hcap;
             mask = (unsigned)hcap - 1u;
@@ -502,7 +527,7 @@
         __syncthreads();                                  // the next kernel's build (or the loop's product buffers) reuses the scratch
         FL_PSTAMP();
     }
-    if constexpr (CONV && K == 2) {
+    if constexpr (LATE && K == 2) {
         // kernel 0's plan is a function of its vertex count alone: formed again here from an opaque copy, so that its four offsets
         // do not occupy scalar registers all through kernel 1's build (which is short of them)
         int v0 = V[0], cur = kHdr;
@@ -516,13 +541,14 @@
     FL_STAMP();
 
     phase_fence();
-    // What is read from here on.  CONV: through args_view (frame_body.h), so that the weights, the cap, the output pointers ... are
+    // What is read from here on.  LATE: through args_view (frame_body.h), so that the weights, the cap, the output pointers ... are
     // loaded here and not kept in scalar registers through both builds; otherwise `a` and `c` themselves.
-    const FrameArgs &al = args_view<CONV>(a, kArgOffA, kargs);
-    const CrfDev &cz = args_view<CONV>(c, 0, kargs);
+    const FrameArgs &al = args_view<LATE>(a, kArgOffA, kargs);
+    const CrfDev &cz = args_view<LATE>(c, 0, kargs);
     // norm = 1 / (compute(ones) + 1e-20), pairwise3d.h:22-27, of the kernels in KM: one pass of the loop's own splat / blur /
     // slice with Q = 1.  Fills pr.wn (= w * norm, pairwise3d.h:77).
     ChainLane cl{0u, 0u};
+    FRAME_BODY_DECLS
     auto normalise = [&](auto km) {
         constexpr int KM = decltype(km)::value;
 #pragma unroll
@@ -536,7 +562,7 @@
                 pr.wn[s][k] = 0.0f;
                 if (tid + s * NT < N) {
                     const float t = slice_point(smem, lay, pr, s, k, al.alpha).x;
-                    pr.wn[s][k] = al.w[k] * (1.0f / (t + 1e-20f));             // pairwise3d.h:26-27,77
+                    FRAME_BODY_FACTORS(s, k, 1.0f / (t + 1e-20f))              // pairwise3d.h:26-27,77
                 }
             }
         }
@@ -726,16 +752,18 @@
     float alpha[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) alpha[k] = al.alpha;
+    FRAME_BODY_TERMS
     if constexpr (CONV) {
         // a.n_iter is the cap.  The stop decision is uniform (every lane reads the same two LDS words behind converge_decide's
         // barrier), so every lane leaves the loop at the same iteration and reaches the barrier of publish_done together.
         const FrameConv &fz = args_view<true>(fc, kArgOffConv, kargs);
         Converge cv{fz.criterion, fz.tol, lay.total, 0, 0, 0, 0u};
-        mean_field<PPT, K, 2, NT, false, false, true>(smem, lay, V, N, tid, pr, cl, alpha, al.n_iter, al.relax, ins, first_p, nullptr, &cv);
+        mean_field<PPT, K, 2, NT, false, FRAME_BODY_GEN, true>(smem, lay, V, N, tid, pr, cl, alpha, al.n_iter, al.relax, ins, first_p,
+                                                               FRAME_BODY_GT, &cv);
         // (uniform values: every lane holds them; ordinary vector stores)
         if (tid == 0) report_convergence(fz.out, f, cv.iterations, __uint_as_float(cv.delta), cv.changed, cv.converged);
     } else {
-        mean_field<PPT, K, 2, NT>(smem, lay, V, N, tid, pr, cl, alpha, al.n_iter, al.relax, ins, first_p);
+        mean_field<PPT, K, 2, NT, false, FRAME_BODY_GEN, false, FRAME_BODY_GEN>(smem, lay, V, N, tid, pr, cl, alpha, al.n_iter, al.relax, ins, first_p, FRAME_BODY_GT);
     }
     store_results<PPT, K, NT>(cz, f, N, tid, pr, al.with_map);
     if (tid < K && al.V_out[tid]) al.V_out[tid][f] = tid == 0 ? V[0] : V[K - 1];
@@ -743,3 +771,8 @@
     publish_done();
     FL_STAMP();
     if (kInstr && a.timing && (int)blockIdx.x == a.timing_block && tid == a.timing_lane) a.timing[63] = ins.n;
+#undef FRAME_BODY_GEN
+#undef FRAME_BODY_GT
+#undef FRAME_BODY_DECLS
+#undef FRAME_BODY_FACTORS
+#undef FRAME_BODY_TERMS

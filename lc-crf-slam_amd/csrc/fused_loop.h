@@ -624,8 +624,10 @@ __device__ __forceinline__ bool converge_decide(unsigned char *smem, Converge &c
 // CONV (with cv): the convergence form -- at the softmax the old and the new Q of a point sit in the same lane, which keeps the
 // maximum of |new - old| and its flipped labels; converge_decide() behind the point phase ends the loop.  The products of the next
 // iteration are already written when the decision falls (`more`): nobody reads them.  Every other instantiation takes CONV = false
-// and compiles as it did.
-template <int PPT, int K, int CH, int NT = kNT, bool REV = false, bool GEN = false, bool CONV = false>
+// and compiles as it did.  FENCE: the lane index is made opaque once per iteration, so that what the phases derive from it is formed
+// where it is used and not kept in registers around the loop -- the GEN + CONV form always; the frame kernel's fixed-count GEN form
+// (frame_general.hip) asks for it too.
+template <int PPT, int K, int CH, int NT = kNT, bool REV = false, bool GEN = false, bool CONV = false, bool FENCE = GEN && CONV>
 __device__ __forceinline__ void mean_field(unsigned char *smem, const FusedLayout &lay, const int (&V)[K], int N, int tid,
                                            PointRegs<PPT, K> &pr, const ChainLane &cl, const float (&alpha)[K], int n_iter,
                                            float relax, Instr &ins, int first_p = -1, const GeneralTerms<PPT, K> *gt = nullptr,
@@ -678,7 +680,7 @@ __device__ __forceinline__ void mean_field(unsigned char *smem, const FusedLayou
         }
         for (int it = 0; it < n_iter; ++it) {
             opaque(pr);
-            if constexpr (GEN && CONV) asm volatile("" : "+v"(tid));
+            if constexpr (FENCE) asm volatile("" : "+v"(tid));
             splat_blur<PPT, K, CH, false, NT, (1 << K) - 1, REV, GEN>(smem, lay, V, N, tid, pr, cl, ins, gt);
             const bool more = it + 1 < n_iter;
 #pragma unroll
@@ -701,7 +703,7 @@ __device__ __forceinline__ void mean_field(unsigned char *smem, const FusedLayou
     }
     for (int it = 0; it < n_iter; ++it) {
         opaque(pr);
-        if constexpr (GEN && CONV) asm volatile("" : "+v"(tid));
+        if constexpr (FENCE) asm volatile("" : "+v"(tid));
         splat_blur<PPT, K, CH, true, NT, (1 << K) - 1, REV, GEN>(smem, lay, V, N, tid, pr, cl, ins, gt);
 #pragma unroll
         for (int s = 0; s < PPT; ++s)

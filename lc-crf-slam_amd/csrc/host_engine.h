@@ -156,6 +156,7 @@ struct Engine {
     void *after_rerun_ctx = nullptr;
     static constexpr int kDualMaxFrames = 64;    // (measured, `scripts/small_batch_latency.py`: 4 frames 98 -> 86 us, 32 frames 93 -> 83 us, 128 frames 112 -> 114 us)
     bool opt_single_wg = false;        // LCCRF_OPT_SINGLE_WORKGROUP: never the two-workgroup form (lccrf_set_option)
+    bool opt_frame_general = false;    // LCCRF_OPT_FRAME_GENERAL: terms with a matrix or a mode may take the one-launch route (frame_general.hip)
     unsigned *dual_area = nullptr;     // hand-off area of the two-workgroup form of the frame kernel (batches of up to kDualMaxFrames frames)
     unsigned dual_epoch = 0;
     // object API: the frame kernel's last act is a store of `done_epoch` into this pinned word, behind its results; the host
@@ -230,7 +231,8 @@ struct Engine {
     // sections 1e (a handle) and 2g (a batch: one matrix per term, shared by every frame): the terms' label-compatibility matrices.
     // One device array for all of them, allocated by the first setter and kept with the handle or batch; compat_ptr[k] is term k's
     // [L][L] slice of it, or null (Potts).  While n_compat > 0 the one-launch frame kernel and the fused engine, which hard-wire
-    // Potts, are not taken (nor their prepared launch records touched); the frames choose_sized_engine() names run on the fused
+    // Potts, are not taken (nor their prepared launch records touched) -- under LCCRF_OPT_FRAME_GENERAL the one-launch route's general
+    // kernels are (frame_ok); the frames choose_sized_engine() names run on the fused
     // engine's general kernels, which take the matrices by value from compat_host.
     float *compat_dev = nullptr;       // [LCCRF_MAX_KERNELS][L][L]
     float *compat_host = nullptr;      // pinned, the same shape: the matrices as set (the getter's answer and the uploads' source)
@@ -241,7 +243,7 @@ struct Engine {
     // ---- normalisation modes ----
     // sections 1g (a handle) and 2g (a batch: one mode per term, shared by every frame): where each term applies its norm -- after the
     // filter (the reference's form and the default), before it, half on either side, or not at all.  While n_modes > 0 the one-launch
-    // frame kernel and the fused engine are not taken and the streaming engine's general branch -- or one of the fused engine's
+    // frame kernel (but for its general form under LCCRF_OPT_FRAME_GENERAL, which forms the factors itself) and the fused engine are not taken and the streaming engine's general branch -- or one of the fused engine's
     // general kernels -- runs on kdevs_post, the
     // copy of kdevs whose `norm` points at each term's factor BEHIND the filter, with pre_ptr[k] the factor of its input
     // (kStepViews, behind kSized).

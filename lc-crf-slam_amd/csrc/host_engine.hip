@@ -725,7 +725,9 @@ int Engine::step(float relax)
 bool Engine::frame_ok() const
 {
     static const bool no_frame = ab_env("LCCRF_NO_FRAME") != nullptr;   // cross-check switch: two-kernel path, same results
-    return !no_frame && engine_pref == 0 && !n_compat && !n_modes && !kernels.empty() && frame_supported(crf, kdevs.data());
+    // terms with a matrix or a mode: only under LCCRF_OPT_FRAME_GENERAL, two labels, frames of the general kernels' size (frame_general.hip)
+    if ((n_compat || n_modes) && !(opt_frame_general && L == 2 && active_points(crf) <= kGeneralMaxPoints)) return false;
+    return !no_frame && engine_pref == 0 && !kernels.empty() && frame_supported(crf, kdevs.data());
 }
 
 // One launch per frame; whether every frame fitted the kernel's LDS plan is known at the next
@@ -734,6 +736,7 @@ int Engine::run_frame(const Schedule &run)
 {
     const int with_map = run.with_map;
     const bool stop = run.until_converged;
+    const bool general = n_compat || n_modes;         // (frame_ok: under LCCRF_OPT_FRAME_GENERAL only) frame_general.hip's kernels
     *late_status = 0;
     // (label-derived energies already written for lattices in locality mode sit in the INTERNAL point order: the frame kernel, which
     //  works in the caller's order, derives them from the labels again)
@@ -741,7 +744,7 @@ int Engine::run_frame(const Schedule &run)
     unsigned *dual = nullptr;
     // The tracker's case (one frame, 255 idle CUs) and small batches (a quarter as many frames as CUs, or fewer): every
     // frame gets two workgroups, one per lattice build.
-    if (crf.K == 2 && F <= kDualMaxFrames && !opt_single_wg && !stop) {
+    if (crf.K == 2 && F <= kDualMaxFrames && !opt_single_wg && !stop && !general) {
         if (!dual_area) {
             int rc = mem.alloc(reinterpret_cast<char **>(&dual_area), frame_dual_bytes(std::min(Fcap, kDualMaxFrames)));
             if (rc) return rc;
@@ -757,7 +760,7 @@ int Engine::run_frame(const Schedule &run)
     // full-size frames, two per CU (frame_lean.hip): the record area its loop re-reads is allocated when a batch first wants it
     // (sized for the frames BOUND, not for the handle's capacity -- 96 KB per frame: a handle created for 16384 frames that runs 1024 takes
     //  0.1 GB, not 1.6; a later, larger batch gets a new area, the old one stays with the handle until it is destroyed -- ADVICE r5)
-    if (!stop && frame_lean_ok && lean_rec_frames < F && frame_lean_wanted(crf)) {
+    if (!stop && !general && frame_lean_ok && lean_rec_frames < F && frame_lean_wanted(crf)) {
         // (no memory for the area: the batch keeps the one-frame-per-CU kernel, which needs none)
         lean_rec = nullptr;
         lean_rec_frames = 0;
@@ -771,7 +774,20 @@ int Engine::run_frame(const Schedule &run)
         }
     }
     int shape = 0;
-    if (stop) {
+    if (general) {
+        // a matrix or a mode on some term: always one 1024-lane workgroup per frame, the matrices by value from the pinned copies
+        // the setters keep, the factors of every mode formed in the kernel (no ensure_factors(): nothing of it is in HBM)
+        const float *mats[LCCRF_MAX_KERNELS] = {};
+        const float *const *compat = host_matrices(mats);
+        const int16_t *label = from_label ? deferred_label : nullptr;
+        if (stop)
+            launch_frame_general_converged(crf, kdevs.data(), run.n_iter, run.criterion, run.tol, with_map, run.relax, late_status,
+                                           frame_status, label, deferred_tbl.v, compat, norm_mode, conv_out(), stream,
+                                           by_word ? done_word : nullptr, done_epoch);
+        else
+            launch_frame_general(crf, kdevs.data(), run.n_iter, with_map, run.relax, late_status, frame_status, label, deferred_tbl.v,
+                                 compat, norm_mode, stream, by_word ? done_word : nullptr, done_epoch);
+    } else if (stop) {
         // until converged (frame_converge.hip): always one 1024-lane workgroup per frame; the report leaves with the results
         launch_frame_converged(crf, kdevs.data(), run.n_iter, run.criterion, run.tol, with_map, run.relax, late_status, frame_status,
                                from_label ? deferred_label : nullptr, deferred_tbl.v, conv_out(), stream,
@@ -1153,6 +1169,15 @@ int Engine::rerun_frames(int n)
         launch_copy_frames(g.kernels[k].feat_own, row, kernels[k].dev.feat, row, fb_list, n, row, 1, stream);
         g.kernels[k].dev.feat = g.kernels[k].feat_own;
         g.kernels[k].dev.w = kernels[k].dev.w;
+    }
+    // the model as it is now (a one-launch run under LCCRF_OPT_FRAME_GENERAL): the setters settle a pending run before they change
+    // it, so this is the model the flagged frames were launched with -- it may differ from the last re-run's
+    g.clear_compat();
+    g.clear_norm_modes();
+    for (size_t k = 0; k < kernels.size(); ++k) {
+        if (compat_ptr[k])
+            if (int rc = g.set_compat((int)k, compat_host + k * (size_t)L * L)) return rc;
+        g.set_norm_mode((int)k, norm_mode[k]);
     }
     g.crf.unary = g.unary_own;
     if (unary_deferred || (unary_is_label && perm_on)) {   // (see run_frame: energies written in the internal point order are of no use here)
