@@ -486,7 +486,7 @@ int lccrf_batch_inference_converged(lccrf_batch_handle b, int max_iterations, in
     int rc = e.make_ready(Engine::kSized);
     if (rc) return rc;
     return timed_batch_call(e, stream, e.ev[2], e.ev[3], e.timed_inf,
-                            [&] { return e.inference_converged(max_iterations, criterion, tol, with_map, relax); });
+                            [&] { return e.inference_converged(converged_run(max_iterations, criterion, tol, with_map, relax)); });
 }
 
 int lccrf_batch_get_convergence_host(lccrf_batch_handle b, int32_t *iterations, float *delta, int32_t *changed, int32_t *converged)
@@ -534,7 +534,7 @@ int lccrf_batch_run_converged(lccrf_batch_handle b, int max_iterations, int crit
     if (!b->inputs_set) return fail(LCCRF_E_STATE, "inputs not set");
     Engine &e = b->eng;
     const int rc = timed_batch_call(e, stream, e.ev[2], e.ev[3], e.timed_inf,
-                                    [&] { return e.run_converged(max_iterations, criterion, tol, with_map, relax); });
+                                    [&] { return e.run_converged(converged_run(max_iterations, criterion, tol, with_map, relax)); });
     e.built = e.built_upto == (int)e.kernels.size() && !e.kernels.empty();
     return rc;
 }

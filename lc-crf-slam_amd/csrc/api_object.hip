@@ -313,7 +313,7 @@ int lccrf_inference_converged(lccrf_handle h, int max_iterations, int criterion,
     const int ra = Engine::check_converged_args(max_iterations, criterion, tol, relax);
     if (ra) return ra;
     CHECK_H(h);
-    return h->eng.inference_converged(max_iterations, criterion, tol, with_map, relax);
+    return h->eng.inference_converged(converged_run(max_iterations, criterion, tol, with_map, relax));
 }
 
 // section 1i
@@ -322,7 +322,7 @@ int lccrf_run_converged(lccrf_handle h, int max_iterations, int criterion, float
     const int ra = Engine::check_converged_args(max_iterations, criterion, tol, relax);
     if (ra) return ra;
     CHECK_H(h);
-    return h->eng.run_converged(max_iterations, criterion, tol, with_map, relax);
+    return h->eng.run_converged(converged_run(max_iterations, criterion, tol, with_map, relax));
 }
 
 int lccrf_get_convergence(lccrf_handle h, int *iterations, float *delta, int *changed, int *converged)

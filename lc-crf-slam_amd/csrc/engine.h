@@ -398,6 +398,43 @@ size_t backward_layout(const BackwardRequest &rq, const CrfDev &c, const KernelD
 void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int rows, const BackwardRequest &rq,
                            const BackwardArea &ar, const float *const *compat, hipStream_t s, const float *const *pre = nullptr);
 
+// ---- one run, its terms, and what a converged one reports: what the launch requests below are made of ---------------------------
+// One run: a fixed count of n_iter iterations, or -- until_converged -- at most n_iter under (criterion, tol) (include/lccrf.h
+// sections 1h and 2e: LCCRF_STOP_* bits).
+struct Schedule { int n_iter; int with_map; float relax; bool until_converged; int criterion; float tol; };
+inline Schedule fixed_run(int n_iter, int with_map, float relax) { return Schedule{n_iter, with_map, relax, false, 0, 0.0f}; }
+inline Schedule converged_run(int max_iter, int criterion, float tol, int with_map, float relax)
+{
+    return Schedule{max_iter, with_map, relax, true, criterion, tol};
+}
+// The terms of a two-label CRF that are not all Potts terms normalised AFTER the filter (include/lccrf.h sections 1e, 1g and 2g).
+// All null: the Potts kernels.  Filled by Engine::term_model(), which owns the array behind `mats`.
+struct TermModel {
+    const float *const *mats;      // null, or K HOST pointers: term k's [2][2] matrix or null -- passed to the kernels by value
+    const float *const *pre;       // null, or K device pointers: the [F][maxN] factor of term k's filter input or null (the kernels on
+                                   //   lattices in HBM, whose `kds` are Engine::step_kdevs(); the one-launch ones form it themselves)
+    const int *norm_mode;          // null (every term AFTER), or K lccrf_normalization values (the one-launch kernels)
+    bool general() const { return mats || pre || norm_mode; }
+};
+// the matrices as the general kernels' arguments carry them: mu[k] = term k's, row-major; returns has_mu (bit k: term k has one)
+inline int copy_matrices(const TermModel &t, int K, float (*mu)[4])
+{
+    int has_mu = 0;
+    for (int k = 0; k < K; ++k)
+        if (t.mats && t.mats[k]) {
+            has_mu |= 1 << k;
+            for (int e = 0; e < 4; ++e) mu[k][e] = t.mats[k][e];
+        }
+    return has_mu;
+}
+// what a converged run reports per frame, [F] each in HBM
+struct ConvergeOut {
+    int *iterations;      // t
+    float *delta;         // d_t
+    int *changed;         // c_t
+    int *converged;       // the criterion was met at t
+};
+
 // ---- fused build (SLAM sizes; one workgroup per (frame, kernel), hash table in LDS) ------
 bool build_small_supported(const KernelDev *kds, int n, int max_points);
 void launch_build_small(const KernelDev *kds, int n, int max_points, const CrfDev &c, hipStream_t s);
@@ -407,10 +444,9 @@ void launch_build_small(const KernelDev *kds, int n, int max_points, const CrfDe
 bool slam_shaped(const CrfDev &c, const KernelDev *kds, bool u16_tables);
 bool fused_supported(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow,
                      size_t *lds_bytes);
-// returns the shape it launched: lanes per workgroup (= per frame) | workgroups per CU << 16 (0: nothing launched)
-// prep (optional): the batch's prepared launch records of the two-frames-per-CU kernel (fused_lean.h: LeanPrepPlan) -- `buf` of
-// `bytes` bytes owned by the caller (lean_prep_bytes(): what the current batch needs, 0 when the plan does not apply); the call
-// fills them when !valid (the caller clears `valid` whenever a lattice changes) and records ev0 / ev1 around that launch.
+// The batch's prepared launch records of the two-frames-per-CU kernel (fused_lean.h: LeanPrepPlan) -- `buf` of `bytes` bytes owned
+// by the caller (lean_prep_bytes(): what the current batch needs, 0 when the plan does not apply); the launch fills them when
+// !valid (the caller clears `valid` whenever a lattice changes) and records ev0 / ev1 around that launch.
 struct LeanPrep {
     unsigned char *buf = nullptr;
     size_t bytes = 0;
@@ -420,42 +456,29 @@ struct LeanPrep {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 size_t lean_prep_bytes(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow);
-// report (optional): receives fused_report() of the launch, the shape word of lccrf_get_engine.
-int launch_inference_fused(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow,
-                           int n_iter, int with_map, float relax, hipStream_t s, LeanPrep *prep = nullptr, int *report = nullptr);
 // lccrf_get_engine's shape word: lanes per workgroup | points per lane << 16 | kernel 0 took the chain path << 20
 inline int fused_report(int lanes, int ppt, int chain0) { return lanes | ppt << 16 | (chain0 ? 1 << 20 : 0); }
-
-// ---- the fused engine's inference with per-term matrices and factors (fused_general.hip; include/lccrf.h sections 1e and 1g) ----
-// The c.F frames of a handle (one) or a batch, each of at most 2048 active points, L = 2, one or two 2-D terms on lattices that fit
-// the fused plan, in ONE launch: a 1024-lane workgroup per frame.
-//   kds     the caller's copies whose `norm` points at each term's factor behind the filter (as launch_step_stream takes them)
-//   compat  null, or K HOST pointers: term k's [2][2] matrix or null -- passed to the kernel by value
-//   pre     null, or K device pointers: the [F][maxN] factor of term k's filter input or null
-// Returns fused_report() of what it launched, or 0 when the frame is not one it takes (nothing launched).
-int launch_inference_general(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const float *const *compat,
-                             const float *const *pre, int n_iter, int with_map, float relax, hipStream_t s);
-
-// ---- convergence-driven inference (include/lccrf.h sections 1h and 2e) ---------------------------------------------------------
-// what a converged run reports per frame, [F] each in HBM
-struct ConvergeOut {
-    int *iterations;      // t
-    float *delta;         // d_t
-    int *changed;         // c_t
-    int *converged;       // the criterion was met at t
+// One inference of the c.F frames of a handle (one) or a batch on lattices in HBM that fit the fused plan, in ONE launch, a workgroup
+// per frame.  Which kernel: Potts terms on k_fused (fused_engine.hip: 1024 lanes, or 512 and two frames per CU) or, until converged,
+// k_converge (fused_converge.hip: frames of up to 4096 active points); terms with a matrix or a factor on k_general / k_general_converge
+// (fused_general.hip, fused_general_converge.hip: up to 2048 active points), whose `kds` are the caller's copies with `norm` pointing
+// at each term's factor behind the filter (as launch_step_stream takes them).  The stop decision of a converged run is made inside
+// the kernel; a plan that leaves no room for its reduction's words in LDS launches nothing.
+struct SizedRequest {
+    Schedule run;
+    TermModel terms;      // (norm_mode is not read: the factors are in HBM, terms.pre and kds[k].norm)
+    ConvergeOut out;      // every frame's report (read only when run.until_converged)
+    LeanPrep *prep;       // or null: k_fused's prepared launch records (no other kernel looks at them)
 };
-// The fused engine's loop in its convergence form (fused_converge.hip): every frame of c on lattices that fit the fused plan, one
-// 1024-lane workgroup per frame, the stop decision inside the kernel.  Returns fused_report() of what it launched, or 0 when the
-// frames are not ones it takes -- not slam_shaped, beyond 4096 active points, or a plan that leaves no room for the reduction's
-// words in LDS -- and nothing was launched.
-int launch_inference_converged(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, int max_iter, int criterion,
-                               float tol, int with_map, float relax, const ConvergeOut &out, hipStream_t s);
-// The two at once (fused_general_converge.hip): launch_inference_general's frames, terms and arguments under launch_inference_converged's
-// stop rule and report.  Returns fused_report() of what it launched, or 0 -- a plan without room for the reduction's words included.
-int launch_inference_general_converged(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow,
-                                       const float *const *compat, const float *const *pre, int max_iter, int criterion, float tol,
-                                       int with_map, float relax, const ConvergeOut &out, hipStream_t s);
-// ... and for everything else, the bookkeeping behind each step of the streaming engine (converge_track.hip): per frame the kept
+struct SizedLaunch {
+    int report;           // fused_report() of what was launched; 0: the frames are not ones the kernel takes and nothing was launched
+    int shape;            // lanes per workgroup (= per frame) | workgroups per CU << 16
+};
+SizedLaunch launch_inference(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const SizedRequest &rq,
+                             hipStream_t s);
+
+// ---- convergence-driven inference on the streaming engine (include/lccrf.h sections 1h and 2e) ---------------------------------
+// For everything the one-launch kernels do not take: the bookkeeping behind each step (converge_track.hip) -- per frame the kept
 // copy of the previous Q (`prev`, [F][maxN][L] -- which IS the frame's Q at the iteration it finished, since a finished frame's
 // copy is no longer refreshed), the accumulators of the iteration, and whether the frame has finished.
 struct ConvergeTrack {
@@ -474,38 +497,32 @@ void launch_track_restore(const CrfDev &c, const ConvergeTrack &tk, int t_last, 
 
 // ---- frame engine (SLAM sizes; lattice build + normalisation + inference of a frame in ONE launch) ---------
 bool frame_supported(const CrfDev &c, const KernelDev *kds);
-// label != nullptr (L = 2): the unary energies are derived in the kernel from the labels and the 5 table entries
-// {u, n0, n1, p0, p1}; otherwise read from c.unary.  `status` (pinned host word, zeroed by the caller) reads 1
-// afterwards if some frame did not fit the kernel's LDS plan; `frame_status` (device [F], or null) then holds 1 for
-// exactly those frames and the caller runs them -- and only them -- on the two-kernel path.
-// allow_small: frames of up to 1024 points may run as 512-lane workgroups in half the CU's LDS (two frames per CU);
-// lean_rec (device memory of frame_lean_rec_bytes(F), or null): so may batches of full-size two-kernel frames (1025 .. 2048 points;
-// frame_lean.hip keeps the per-point records its loop re-reads in that area).
-// Returns the shape it launched: 0 one frame per CU, 1 the small shape, 2 the lean one (a caller that sees many frames of a
-// half-CU shape flagged turns that shape off).
-// dual (device memory of frame_dual_bytes(F), zeroed once) + a launch-unique dual_epoch != 0: two-kernel frames are given
-// two workgroups each -- one per lattice build (single frames: the other 255 CUs are idle anyway).
-int launch_frame(const CrfDev &c, const KernelDev *kds, int n_iter, int with_map, float relax, int *status, int *frame_status,
-                 const int16_t *label, const float *tbl5, hipStream_t s, bool allow_small = true, unsigned *dual = nullptr,
-                 unsigned dual_epoch = 0, unsigned *done = nullptr, unsigned done_epoch = 0, unsigned char *lean_rec = nullptr);
-// The same launch with the inference run until converged, at most max_iter iterations (frame_converge.hip; include/lccrf.h sections
-// 1i and 2f): one 1024-lane workgroup per frame, never the two-workgroup or a half-CU shape.  `out` receives every frame's report; a
-// frame that does not fit -- its lattices, or the reduction's 16 bytes behind its loop plan -- is flagged exactly as launch_frame's.
-void launch_frame_converged(const CrfDev &c, const KernelDev *kds, int max_iter, int criterion, float tol, int with_map, float relax,
-                            int *status, int *frame_status, const int16_t *label, const float *tbl5, const ConvergeOut &out,
-                            hipStream_t s, unsigned *done = nullptr, unsigned done_epoch = 0);
-// The two launches above for terms with a label-compatibility matrix or a normalisation mode (frame_general.hip; include/lccrf.h
-// LCCRF_OPT_FRAME_GENERAL): frames launch_frame takes of at most 2048 active points, one 1024-lane workgroup per frame, never the
-// two-workgroup or a half-CU shape; the factors of every mode are formed in the kernel from the norm it holds.
-//   compat     null, or K HOST pointers: term k's [2][2] matrix or null -- passed to the kernel by value (Engine::host_matrices)
-//   norm_mode  K lccrf_normalization values
-void launch_frame_general(const CrfDev &c, const KernelDev *kds, int n_iter, int with_map, float relax, int *status, int *frame_status,
-                          const int16_t *label, const float *tbl5, const float *const *compat, const int *norm_mode, hipStream_t s,
-                          unsigned *done = nullptr, unsigned done_epoch = 0);
-void launch_frame_general_converged(const CrfDev &c, const KernelDev *kds, int max_iter, int criterion, float tol, int with_map,
-                                    float relax, int *status, int *frame_status, const int16_t *label, const float *tbl5,
-                                    const float *const *compat, const int *norm_mode, const ConvergeOut &out, hipStream_t s,
-                                    unsigned *done = nullptr, unsigned done_epoch = 0);
+// One run of the c.F frames from their inputs.  Which kernel: Potts terms on k_frame (frame_engine.hip, frame_lean.hip) or, until
+// converged, k_frame_converge (frame_converge.hip); terms with a matrix or a mode on k_frame_general / k_frame_general_converge
+// (frame_general.hip: frames of at most 2048 active points -- Engine::frame_ok -- the factors of every mode formed in the kernel from
+// the norm it holds).  All but k_frame run one 1024-lane workgroup per frame and look at none of the shape options.
+struct FrameRequest {
+    Schedule run;
+    TermModel terms;      // (pre is not read)
+    int *status;          // pinned host word, zeroed by the caller: reads 1 afterwards if some frame did not fit the kernel's LDS plan
+                          //   -- its lattices or, until converged, the reduction's 16 bytes behind its loop plan ...
+    int *frame_status;    // device [F], or null: ... and holds 1 for exactly those frames; the caller runs them -- and only them -- on
+                          //   the two-kernel path
+    const int16_t *label; // != null (L = 2): the unary energies are derived in the kernel from the labels and ...
+    const float *tbl5;    //   ... the 5 table entries {u, n0, n1, p0, p1}; otherwise read from c.unary
+    unsigned *done;       // pinned host word or null: a single frame's kernel stores done_epoch there behind its results
+    unsigned done_epoch;
+    ConvergeOut out;      // every frame's report (read only when run.until_converged)
+    // the shapes of k_frame
+    bool allow_small;     // frames of up to 1024 points may run as 512-lane workgroups in half the CU's LDS (two frames per CU)
+    unsigned *dual;       // device memory of frame_dual_bytes(F), zeroed once, or null: two-kernel frames are given two workgroups
+    unsigned dual_epoch;  //   each -- one per lattice build (single frames: the other 255 CUs are idle anyway) -- under a launch-unique epoch != 0
+    unsigned char *lean_rec;   // device memory of frame_lean_rec_bytes(F), or null: batches of full-size two-kernel frames (1025 .. 2048
+                               //   points) may run two per CU as well (frame_lean.hip keeps the per-point records its loop re-reads there)
+};
+// Returns the shape it launched: 0 one frame per CU, 1 the small shape, 2 the lean one (a caller that sees many frames of a half-CU
+// shape flagged turns that shape off).
+int launch_frame(const CrfDev &c, const KernelDev *kds, const FrameRequest &rq, hipStream_t s);
 bool frame_lean_wanted(const CrfDev &c);              // would launch_frame take the lean shape for this batch, given the area?
 size_t frame_lean_rec_bytes(int frames);
 size_t frame_dual_bytes(int frames);

@@ -96,9 +96,8 @@ inline int frame_hcap(int NA)
 }
 
 // The launch arguments every kernel on the frame body takes (host): one frame per workgroup in the whole of a CU's LDS, no hand-off
-// area, no record area -- launch_frame() adds what its other shapes need.
-inline FrameArgs frame_args(const CrfDev &c, const KernelDev *kds, int n_iter, int with_map, float relax, int *status, int *frame_status,
-                            const int16_t *label, const float *tbl5, unsigned *done, unsigned done_epoch)
+// area, no record area -- launch_frame() adds what k_frame's other shapes need.
+inline FrameArgs frame_args(const CrfDev &c, const KernelDev *kds, const FrameRequest &rq)
 {
     FrameArgs a{};
     for (int k = 0; k < c.K; ++k) {
@@ -111,22 +110,38 @@ inline FrameArgs frame_args(const CrfDev &c, const KernelDev *kds, int n_iter, i
     a.inv_dp1 = kds[0].inv_dp1;
     a.alpha = kds[0].alpha;
     a.maxN = c.maxN;
-    a.label = label;
-    if (label)
-        for (int i = 0; i < 5; ++i) a.tbl[i] = tbl5[i];
-    a.n_iter = n_iter;
-    a.with_map = with_map;
-    a.relax = relax;
-    a.omr = 1 - relax;
+    a.label = rq.label;
+    if (rq.label)
+        for (int i = 0; i < 5; ++i) a.tbl[i] = rq.tbl5[i];
+    a.n_iter = rq.run.n_iter;
+    a.with_map = rq.run.with_map;
+    a.relax = rq.run.relax;
+    a.omr = 1 - rq.run.relax;
     a.hcap = frame_hcap(active_points(c));
     a.lds_total = (int)kLdsLimit;
-    a.status = status;
-    a.frame_status = frame_status;
-    a.done = c.F == 1 ? done : nullptr;
-    a.n_single = (c.F == 1 && done && c.activeN > 0) ? c.activeN : -1;   // (object API: activeN IS the frame's count)
-    a.done_epoch = done_epoch;
+    a.status = rq.status;
+    a.frame_status = rq.frame_status;
+    a.done = c.F == 1 ? rq.done : nullptr;
+    a.n_single = (c.F == 1 && rq.done && c.activeN > 0) ? c.activeN : -1;   // (object API: activeN IS the frame's count)
+    a.done_epoch = rq.done_epoch;
     return a;
 }
+// ... and the general form's terms, by value: the matrices and the modes (no mode given: every term AFTER)
+inline FrameGeneral frame_general_terms(const CrfDev &c, const TermModel &t)
+{
+    FrameGeneral g{};
+    const int K = c.K < kMaxFusedK ? c.K : kMaxFusedK;
+    for (int k = 0; k < K; ++k) g.mode[k] = t.norm_mode ? t.norm_mode[k] : LCCRF_NORMALIZE_AFTER;
+    g.has_mu = copy_matrices(t, K, g.mu);
+    return g;
+}
+
+// The units behind launch_frame() (frame_engine.hip), each with its kernels and its ladder over K and the points per lane: the
+// arguments come filled (frame_build.h: launch_frame_lean is the fourth).  One 1024-lane workgroup per frame; the caller has checked
+// the frames (frame_supported(), and for the general form at most 2 x 1024 active points -- Engine::frame_ok).
+void launch_frame_converge(const CrfDev &c, const FrameArgs &a, const FrameConv &fc, hipStream_t s);
+void launch_frame_general(const CrfDev &c, const FrameArgs &a, const FrameGeneral &fg, hipStream_t s);
+void launch_frame_general_converge(const CrfDev &c, const FrameArgs &a, const FrameConv &fc, const FrameGeneral &fg, hipStream_t s);
 
 }  // namespace fb
 }  // namespace lccrf

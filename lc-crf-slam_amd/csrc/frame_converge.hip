@@ -33,17 +33,15 @@ __global__ void __launch_bounds__(NT, 4) k_frame_converge(CrfDev c, FrameArgs a,
 
 }  // namespace
 
-void launch_frame_converged(const CrfDev &c, const KernelDev *kds, int max_iter, int criterion, float tol, int with_map, float relax,
-                            int *status, int *frame_status, const int16_t *label, const float *tbl5, const ConvergeOut &out,
-                            hipStream_t s, unsigned *done, unsigned done_epoch)
+namespace fb {
+void launch_frame_converge(const CrfDev &c, const FrameArgs &a, const FrameConv &fc, hipStream_t s)
 {
-    const FrameArgs a = frame_args(c, kds, max_iter, with_map, relax, status, frame_status, label, tbl5, done, done_epoch);
-    const FrameConv fc{criterion, tol, out};
     with_dims<1, kMaxFusedK>(c.K, [&](auto kk) {
         with_dims<1, 4>((active_points(c) + kNT - 1) / kNT, [&](auto p) {
             launch_workgroups(k_frame_converge<kNT, decltype(p)::value, decltype(kk)::value>, c.F, kNT, a.lds_total, s, c, a, fc);
         });
     });
 }
+}  // namespace fb
 
 }  // namespace lccrf

@@ -74,21 +74,27 @@ bool frame_lean_wanted(const CrfDev &c)
 }
 size_t frame_lean_rec_bytes(int frames) { return (size_t)frames * kLeanRecBytes; }
 
-int launch_frame(const CrfDev &c, const KernelDev *kds, int n_iter, int with_map, float relax, int *status, int *frame_status,
-                 const int16_t *label, const float *tbl5, hipStream_t s, bool allow_small, unsigned *dual, unsigned dual_epoch,
-                 unsigned *done, unsigned done_epoch, unsigned char *lean_rec)
+int launch_frame(const CrfDev &c, const KernelDev *kds, const FrameRequest &rq, hipStream_t s)
 {
-    FrameArgs a = frame_args(c, kds, n_iter, with_map, relax, status, frame_status, label, tbl5, done, done_epoch);
-    a.rec = lean_rec;
+    FrameArgs a = frame_args(c, kds, rq);
+    // the forms in units of their own: always one 1024-lane workgroup per frame
+    if (rq.run.until_converged || rq.terms.general()) {
+        const FrameConv fc{rq.run.criterion, rq.run.tol, rq.out};
+        if (!rq.terms.general()) launch_frame_converge(c, a, fc, s);
+        else if (rq.run.until_converged) launch_frame_general_converge(c, a, fc, frame_general_terms(c, rq.terms), s);
+        else launch_frame_general(c, a, frame_general_terms(c, rq.terms), s);
+        return 0;
+    }
+    a.rec = rq.lean_rec;
     const int NA = active_points(c);
-    a.dual = dual;
-    a.dual_epoch = dual_epoch;
+    a.dual = rq.dual;
+    a.dual_epoch = rq.dual_epoch;
 #if LCCRF_INSTRUMENT
     static const bool drop_helper = ab_env("LCCRF_DUAL_DROP_HELPER") != nullptr;   // fault injection: not compiled into the release library
     a.drop_helper = drop_helper ? 1 : 0;
 #endif
     static StampBuffer stamps("LCCRF_FRAME_TIMING", "LCCRF_FRAME_TIMING_LANE", "frame");
-    stamps.arm((dual ? 2 : 1) * c.F, kNT, &a.timing, &a.timing_block, &a.timing_lane);   // (two-workgroup form: block 2f is frame f's main workgroup, 2f + 1 its helper)
+    stamps.arm((rq.dual ? 2 : 1) * c.F, kNT, &a.timing, &a.timing_block, &a.timing_lane);   // (two-workgroup form: block 2f is frame f's main workgroup, 2f + 1 its helper)
     // Small frames: 512 lanes and half the CU's LDS per frame, so that two frames share a CU.  A frame whose lattices
     // do not fit that plan (or whose long rows need more chain lanes than four wavefront pairs have) flags itself
     // and is re-run like any other frame that does not fit.
@@ -97,7 +103,7 @@ int launch_frame(const CrfDev &c, const KernelDev *kds, int n_iter, int with_map
     // vertices, a smoothness kernel of min(NA + 350, 1150) (734 vertices at 400 points, 985 at 700, 1071 at 1000 on
     // 640x480 images with an 18-pixel kernel) -- i.e. up to 1024 points.  Frames with larger lattices flag themselves and
     // are re-run; an engine that sees more than 1/8 of a batch flagged stops asking for this shape (allow_small).
-    bool small = allow_small && NA <= 2 * kNTSmall && c.F >= kSmallMinFrames;
+    bool small = rq.allow_small && NA <= 2 * kNTSmall && c.F >= kSmallMinFrames;
     if (small) {
         int vest[kMaxFusedK], tables = 0;
         for (int k = 0; k < c.K; ++k) {
@@ -112,12 +118,12 @@ int launch_frame(const CrfDev &c, const KernelDev *kds, int n_iter, int with_map
     // Full-size frames (1025 .. 2048 points, the two-kernel SLAM configuration): 512 lanes and half the CU's LDS per frame as well
     // (frame_lean.hip) -- flagged frames and the engine's give-up rule as for the small shape.
     static const bool no_lean = ab_env("LCCRF_NO_FRAME_LEAN") != nullptr;  // A/B switch: same results either way
-    const bool lean = lean_rec && !no_lean && frame_lean_plausible(NA, c.K, c.F);
+    const bool lean = rq.lean_rec && !no_lean && frame_lean_plausible(NA, c.K, c.F);
     if (lean) {
         small = false;
         a.lds_total = (int)kLdsHalf;
         launch_frame_lean(c, a, NA, s);
-    } else if (dual && !no_dual && c.K == 2 && !small) {                           // a frame alone: two workgroups, one per lattice build
+    } else if (rq.dual && !no_dual && c.K == 2 && !small) {                           // a frame alone: two workgroups, one per lattice build
         with_dims<1, 4>((NA + kNT - 1) / kNT, [&](auto p) { launch_workgroups(k_frame<kNT, decltype(p)::value, 2, true>, 2 * c.F, kNT, a.lds_total, s, c, a); });
     } else {
         if (small) a.lds_total = (int)kLdsHalf;

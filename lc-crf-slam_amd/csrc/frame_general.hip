@@ -107,29 +107,12 @@ __global__ void __launch_bounds__(NT, 4) k_frame_general_converge(CrfDev c, Fram
 #include "frame_body.inc"
 }
 
-// the terms' matrices (K host pointers or null, as Engine::host_matrices() hands them to the general kernels) and modes, by value
-FrameGeneral frame_general_terms(const CrfDev &c, const float *const *compat, const int *norm_mode)
-{
-    FrameGeneral g{};
-    for (int k = 0; k < c.K && k < kMaxFusedK; ++k) {
-        g.mode[k] = norm_mode ? norm_mode[k] : LCCRF_NORMALIZE_AFTER;
-        if (compat && compat[k]) {
-            g.has_mu |= 1 << k;
-            for (int e = 0; e < 4; ++e) g.mu[k][e] = compat[k][e];
-        }
-    }
-    return g;
-}
-
 }  // namespace
 
-// (the caller has checked the frames: frame_supported() and at most kFrameGeneralMaxPPT x 1024 active points -- Engine::frame_ok)
-void launch_frame_general(const CrfDev &c, const KernelDev *kds, int n_iter, int with_map, float relax, int *status, int *frame_status,
-                          const int16_t *label, const float *tbl5, const float *const *compat, const int *norm_mode, hipStream_t s,
-                          unsigned *done, unsigned done_epoch)
+// (two ladders, not one that picks the kernel inside: that instantiates the kernels in another order and the unit's code object changes)
+namespace fb {
+void launch_frame_general(const CrfDev &c, const FrameArgs &a, const FrameGeneral &fg, hipStream_t s)
 {
-    const FrameArgs a = frame_args(c, kds, n_iter, with_map, relax, status, frame_status, label, tbl5, done, done_epoch);
-    const FrameGeneral fg = frame_general_terms(c, compat, norm_mode);
     with_dims<1, kMaxFusedK>(c.K, [&](auto kk) {
         with_dims<1, kFrameGeneralMaxPPT>((active_points(c) + kNT - 1) / kNT, [&](auto p) {
             launch_workgroups(k_frame_general<kNT, decltype(p)::value, decltype(kk)::value>, c.F, kNT, a.lds_total, s, c, a, fg);
@@ -137,14 +120,8 @@ void launch_frame_general(const CrfDev &c, const KernelDev *kds, int n_iter, int
     });
 }
 
-void launch_frame_general_converged(const CrfDev &c, const KernelDev *kds, int max_iter, int criterion, float tol, int with_map,
-                                    float relax, int *status, int *frame_status, const int16_t *label, const float *tbl5,
-                                    const float *const *compat, const int *norm_mode, const ConvergeOut &out, hipStream_t s,
-                                    unsigned *done, unsigned done_epoch)
+void launch_frame_general_converge(const CrfDev &c, const FrameArgs &a, const FrameConv &fc, const FrameGeneral &fg, hipStream_t s)
 {
-    const FrameArgs a = frame_args(c, kds, max_iter, with_map, relax, status, frame_status, label, tbl5, done, done_epoch);
-    const FrameConv fc{criterion, tol, out};
-    const FrameGeneral fg = frame_general_terms(c, compat, norm_mode);
     with_dims<1, kMaxFusedK>(c.K, [&](auto kk) {
         with_dims<1, kFrameGeneralMaxPPT>((active_points(c) + kNT - 1) / kNT, [&](auto p) {
             launch_workgroups(k_frame_general_converge<kNT, decltype(p)::value, decltype(kk)::value>, c.F, kNT, a.lds_total, s, c, a, fc,
@@ -152,5 +129,6 @@ void launch_frame_general_converged(const CrfDev &c, const KernelDev *kds, int m
         });
     });
 }
+}  // namespace fb
 
 }  // namespace lccrf

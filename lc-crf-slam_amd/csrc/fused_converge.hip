@@ -81,17 +81,11 @@ __global__ void __launch_bounds__(kNT, 4) k_converge(CrfDev c, ConvergeArgs a)
 
 }  // namespace
 
-int launch_inference_converged(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, int max_iter, int criterion,
-                               float tol, int with_map, float relax, const ConvergeOut &out, hipStream_t s)
+// frames that are not slam_shaped, beyond 4096 active points, or whose plan leaves no room for the reduction's words: 0
+int launch_converge(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const SizedRequest &rq, hipStream_t s)
 {
     ConvergeArgs a{};
-    a.max_iter = max_iter;
-    a.with_map = with_map;
-    a.criterion = criterion;
-    a.relax = relax;
-    a.tol = tol;
-    a.out = out;
-    // (a plan that leaves no room for the reduction's words: the caller streams)
+    fill_converge_run(a, rq);
     return plan_variant<kConvergeMaxPPT>(c, kds, maxV, maxRow, kConvergeLds, a, [&](auto p, auto kk, auto ch) {
         launch_workgroups(k_converge<decltype(p)::value, decltype(kk)::value, decltype(ch)::value>, c.F, kNT,
                           a.lay.total + kConvergeLds, s, c, a);

@@ -22,6 +22,7 @@
 #include "device_math.h"
 #include "fused_loop.h"
 #include "fused_lean.h"
+#include "fused_variant.h"
 #include "dispatch.h"
 
 #include <algorithm>
@@ -103,7 +104,7 @@ __global__ void __launch_bounds__(NT, 4) k_fused(CrfDev c, FusedArgs a)
             }
         }
         const pf_u2 clw = __builtin_amdgcn_raw_buffer_load_b64(rp, tid * 8, pp.cl_off, 0);
-        // the LDS tables: at most two 16-byte pieces per lane and table (launch_inference_fused checks the plan), all requested before any is stored
+        // the LDS tables: at most two 16-byte pieces per lane and table (launch_inference checks the plan), all requested before any is stored
         pf_u4 trow[K][2], tnbr[K][2];
 #pragma unroll
         for (int k = 0; k < K; ++k)
@@ -293,7 +294,7 @@ __global__ void __launch_bounds__(NT, 4) k_fused_lean(CrfDev c, FusedArgs a)
             }
         }
         const lean_u2 clw = __builtin_amdgcn_raw_buffer_load_b64(rp, tid * 8, pp.cl_off, 0);
-        // the LDS tables: every piece is at most 16 bytes per lane (launch_inference_fused checks the plan), all requested before any is stored
+        // the LDS tables: every piece is at most 16 bytes per lane (launch_inference checks the plan), all requested before any is stored
         lean_u4 trow[K], tnbr[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -522,11 +523,11 @@ bool lean_layout(const CrfDev &c, const KernelDev *kds, const int *maxV, const i
 // buffer in fused_loop.h's loop as well: 2.04e7 against 2.42e7 iterations/s.  With nobody else on the CU the re-reads' latency and the
 // seven barriers are all exposed; the plan pays through co-residency, not through its schedule alone.)
 
-// the shape decision of launch_inference_fused
+// the shape decision of launch_inference for k_fused
 struct FusedShape {
     bool ok, small, lean;
     int nt, ppt, points;                  // lanes per workgroup, points per lane, points per frame (active_points)
-    int report() const { return nt | ((small || lean) ? 2 : 1) << 16; }   // what launch_inference_fused returns: lanes | frames per CU << 16
+    int report() const { return nt | ((small || lean) ? 2 : 1) << 16; }   // SizedLaunch::shape: lanes | frames per CU << 16
 };
 FusedShape choose_shape(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, FusedLayout *lay)
 {
@@ -592,17 +593,23 @@ size_t lean_prep_bytes(const CrfDev &c, const KernelDev *kds, const int *maxV, c
     return (size_t)pp.total * (size_t)c.F;
 }
 
-int launch_inference_fused(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, int n_iter,
-                           int with_map, float relax, hipStream_t s, LeanPrep *prep, int *report)
+SizedLaunch launch_inference(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const SizedRequest &rq,
+                             hipStream_t s)
 {
+    if (rq.run.until_converged || rq.terms.general()) {      // the variants in units of their own: 1024 lanes, a frame per CU
+        const auto unit = !rq.terms.general() ? launch_converge : rq.run.until_converged ? launch_general_converge : launch_general;
+        const int report = unit(c, kds, maxV, maxRow, rq, s);
+        return SizedLaunch{report, report ? kNT | 1 << 16 : 0};
+    }
+    LeanPrep *const prep = rq.prep;
     FusedArgs a{};
     const FusedShape sh = choose_shape(c, kds, maxV, maxRow, &a.lay);
-    if (!sh.ok) return 0;
+    if (!sh.ok) return SizedLaunch{0, 0};
     for (int k = 0; k < c.K; ++k) a.kd[k] = kds[k];
-    a.n_iter = n_iter;
-    a.with_map = with_map;
-    a.relax = relax;
-    a.omr = 1 - relax;
+    a.n_iter = rq.run.n_iter;
+    a.with_map = rq.run.with_map;
+    a.relax = rq.run.relax;
+    a.omr = 1 - rq.run.relax;
     static StampBuffer stamps("LCCRF_FUSED_TIMING", "LCCRF_FUSED_TIMING_LANE", "fused");
     stamps.arm(c.F, kNT, &a.timing, &a.timing_block, &a.timing_lane);
     static const int dbg = (kInstr && ab_env("LCCRF_FUSED_DBG")) ? atoi(ab_env("LCCRF_FUSED_DBG")) : 0;
@@ -646,8 +653,7 @@ int launch_inference_fused(const CrfDev &c, const KernelDev *kds, const int *max
     }
     launch_shape(c, a, s, mode, sh);
     stamps.print(s);                      // debug only: synchronous read-back of one workgroup's phase stamps
-    if (report) *report = fused_report(sh.nt, sh.ppt, a.lay.chain0);
-    return sh.report();
+    return SizedLaunch{fused_report(sh.nt, sh.ppt, a.lay.chain0), sh.report()};
 }
 
 }  // namespace lccrf

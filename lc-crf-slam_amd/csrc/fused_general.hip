@@ -92,22 +92,15 @@ __global__ void __launch_bounds__(kNT, 4) k_general(CrfDev c, GeneralArgs a)
 
 }  // namespace
 
-// The c.F frames of a handle or a batch, one workgroup each, of at most 2048 active points on lattices that fit the fused plan, with
-// per-term matrices / factors:
-//   kds      Engine::step_kdevs() -- `norm` is each term's factor behind the filter
-//   compat   K host pointers: term k's [2][2] matrix as it was set, or null (null: no term has one)
-//   pre      K device pointers: term k's factor in front of the filter, or null (null: no term has one)
-// Returns the shape it launched -- lanes | points per lane << 16 | kernel 0 on chain rows << 20 -- or 0 when the frames are not ones
-// this kernel takes (nothing launched).
-int launch_inference_general(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const float *const *compat,
-                             const float *const *pre, int n_iter, int with_map, float relax, hipStream_t s)
+// kds: Engine::step_kdevs() -- `norm` is each term's factor behind the filter.  Frames beyond 2048 active points: 0.
+int launch_general(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const SizedRequest &rq, hipStream_t s)
 {
     GeneralArgs a{};
-    a.n_iter = n_iter;
-    a.with_map = with_map;
-    a.relax = relax;
+    a.n_iter = rq.run.n_iter;
+    a.with_map = rq.run.with_map;
+    a.relax = rq.run.relax;
     return plan_variant<kGeneralMaxPPT>(c, kds, maxV, maxRow, 0, a, [&](auto p, auto kk, auto ch) {
-        fill_general_terms(a, c, compat, pre);
+        fill_general_terms(a, c, rq.terms);
         launch_workgroups(k_general<decltype(p)::value, decltype(kk)::value, decltype(ch)::value>, c.F, kNT, a.lay.total, s, c, a);
     });
 }

@@ -127,23 +127,15 @@ __global__ void __launch_bounds__(kNT, 4) k_general_converge(CrfDev c, GeneralCo
 
 }  // namespace
 
-// The frames of a batch (or a handle-sized one) of at most 2048 active points on lattices that fit the fused plan with room for the
-// reduction's words, with per-term matrices / factors, until converged: kds, compat and pre as launch_inference_general takes them,
-// the stop rule and `out` as launch_inference_converged.  Returns the shape it launched, or 0 with nothing launched.
-int launch_inference_general_converged(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow,
-                                       const float *const *compat, const float *const *pre, int max_iter, int criterion, float tol,
-                                       int with_map, float relax, const ConvergeOut &out, hipStream_t s)
+// launch_general's frames and terms (fused_general.hip) under launch_converge's stop rule and report (fused_converge.hip); a plan
+// without room for the reduction's words: 0
+int launch_general_converge(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const SizedRequest &rq,
+                            hipStream_t s)
 {
     GeneralConvergeArgs a{};
-    a.max_iter = max_iter;
-    a.with_map = with_map;
-    a.criterion = criterion;
-    a.relax = relax;
-    a.tol = tol;
-    a.out = out;
-    // (a plan that leaves no room for the reduction's words: the caller streams)
+    fill_converge_run(a, rq);
     return plan_variant<kGeneralConvergeMaxPPT>(c, kds, maxV, maxRow, kConvergeLds, a, [&](auto p, auto kk, auto ch) {
-        fill_general_terms(a, c, compat, pre);
+        fill_general_terms(a, c, rq.terms);
         launch_workgroups(k_general_converge<decltype(p)::value, decltype(kk)::value, decltype(ch)::value>, c.F, kNT,
                           a.lay.total + kConvergeLds, s, c, a);
     });

@@ -33,20 +33,33 @@ int plan_variant(const CrfDev &c, const KernelDev *kds, const int *maxV, const i
     return fused_report(kNT, ppt, a.lay.chain0);
 }
 
-// The general kernels' terms (GeneralArgs, GeneralConvergeArgs: pre[], has_mu, mu[][]) from what their launchers are given: K host
-// pointers to the terms' [2][2] matrices as they were set and K device pointers to the factors in front of the filter, each null for
-// a term without one, either array null when no term has one.  Called behind the plan's guard: c.K <= kMaxFusedK.
+// The general kernels' terms (GeneralArgs, GeneralConvergeArgs: pre[], has_mu, mu[][]) from the request's: the factors in front of
+// the filter and the matrices, each null for a term without one.  Called behind the plan's guard: c.K <= kMaxFusedK.
 template <typename Args>
-void fill_general_terms(Args &a, const CrfDev &c, const float *const *compat, const float *const *pre)
+void fill_general_terms(Args &a, const CrfDev &c, const TermModel &t)
 {
-    for (int k = 0; k < c.K; ++k) {
-        a.pre[k] = pre ? pre[k] : nullptr;
-        if (compat && compat[k]) {
-            a.has_mu |= 1 << k;
-            for (int e = 0; e < 4; ++e) a.mu[k][e] = compat[k][e];
-        }
-    }
+    for (int k = 0; k < c.K; ++k) a.pre[k] = t.pre ? t.pre[k] : nullptr;
+    a.has_mu = copy_matrices(t, c.K, a.mu);
+}
+// ... and the converged kernels' run and report (ConvergeArgs, GeneralConvergeArgs)
+template <typename Args>
+void fill_converge_run(Args &a, const SizedRequest &rq)
+{
+    a.max_iter = rq.run.n_iter;
+    a.with_map = rq.run.with_map;
+    a.criterion = rq.run.criterion;
+    a.relax = rq.run.relax;
+    a.tol = rq.run.tol;
+    a.out = rq.out;
 }
 
 }  // namespace
+
+// The variants' units behind launch_inference() (fused_engine.hip): k_general, k_converge, k_general_converge.  Each returns
+// fused_report() of what it launched, or 0 with nothing launched.
+int launch_general(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const SizedRequest &rq, hipStream_t s);
+int launch_converge(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const SizedRequest &rq, hipStream_t s);
+int launch_general_converge(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const SizedRequest &rq,
+                            hipStream_t s);
+
 }  // namespace lccrf

@@ -4,8 +4,9 @@
 // per-frame fallback, the done-word protocol, the backward area, the compatibility matrices and the normalisation modes.  The bodies are in
 // host_engine.hip; the entry points of include/lccrf.h (api_*.hip) read and write the fields below directly -- all but the two things
 // that are the engine's own: what a call relies on is brought up to date by make_ready() alone, what is in flight is `flight`.
-// A one-launch run is armed by run_frame() alone, which takes the run as one Schedule -- from inference() and run() a fixed count,
-// from run_converged() a cap with its criterion and tol -- and keeps it as `late`, what resolve_late() re-runs flagged frames with.
+// Every run is one Schedule (engine.h) -- a fixed count, or a cap with its criterion and tol -- built by the entry points.  A
+// one-launch run is armed by run_frame() alone, which keeps it as `late`, what resolve_late() re-runs flagged frames with; the fused
+// engine's kernels on lattices in HBM are launched, and what the engine reports of them recorded, by launch_sized() alone.
 #pragma once
 
 #include "engine.h"
@@ -127,7 +128,7 @@ struct Engine {
     int engine_shape = 0;              // report only (lccrf_get_engine): fused_report() of the last inference on engine 2 or 4, else 0
     int last_with_map = 0;             // did the last inference produce MAP labels?
     size_t fused_lds = 0;
-    int fused_shape = 0;               // report only: what the last fused inference launched (launch_inference_fused)
+    int fused_shape = 0;               // report only: what the last fused inference launched (SizedLaunch::shape)
     LeanPrep lean_prep;                // prepared launch records of the two-frames-per-CU inference kernel (engine.h)
     bool fused_fits = false;           // learn_sizes(): the lattices now in HBM fit the fused engine
     bool batch_owned = false;          // set by lccrf_batch_create: the engine of a batch (whatever its frame count), not of a handle
@@ -145,8 +146,6 @@ struct Engine {
     // the lattice sizes; `late_status` (pinned) tells afterwards whether the frame fitted.
     int *late_status = nullptr;
     bool late_ok = false;              // set by the object API: single frame, automatic engine choice
-    // One run: a fixed count of n_iter iterations, or -- until_converged -- at most n_iter under (criterion, tol).
-    struct Schedule { int n_iter; int with_map; float relax; bool until_converged; int criterion; float tol; };
     // the pending run's (run_frame): its flagged frames are re-run with it on the two-kernel path (rerun_on) -- a converged one with
     // inference_converged(), their reports scattered back beside Q and the labels
     Schedule late{0, 0, 1.0f, false, 0, 0.0f};
@@ -318,12 +317,12 @@ struct Engine {
     int run_frame(const Schedule &run);
     int inference(int n_iter, int with_map, float relax);
     int run(int n_iter, int with_map, float relax);
-    int inference_sized(int n_iter, int with_map, float relax, unsigned more_needs = 0);   // (more_needs: 0 or kMayReorder)
+    int inference_sized(const Schedule &run, unsigned more_needs = 0);   // (a fixed count; more_needs: 0 or kMayReorder)
     static int check_converged_args(int max_iter, int criterion, float tol, float relax);
-    int inference_converged(int max_iter, int criterion, float tol, int with_map, float relax);
-    int run_converged(int max_iter, int criterion, float tol, int with_map, float relax);
+    int inference_converged(const Schedule &run);
+    int run_converged(const Schedule &run);
     int rerun_on(Engine &e);
-    int converge_stream(int max_iter, int criterion, float tol, int with_map, float relax);
+    int converge_stream(const Schedule &run);
     int read_convergence();
     int resolve_late(bool *seen_done = nullptr);
     int rerun_frames(int n);
@@ -337,15 +336,17 @@ struct Engine {
         const bool general = n_compat || n_modes;
         sized_engine = !fused_fits ? 1 : !general ? 2 : active_points(crf) <= kGeneralMaxPoints ? 4 : 1;
     }
-    // the matrices as the general kernels take them: K host pointers into compat_host (null: a Potts term), or null when no term has one
-    const float *const *host_matrices(const float *(&mats)[LCCRF_MAX_KERNELS]) const
-    {
-        for (size_t k = 0; k < kernels.size(); ++k) mats[k] = compat_ptr[k] ? compat_host + k * (size_t)L * L : nullptr;
-        return n_compat ? mats : nullptr;
-    }
     // what the streaming step, the plug-in filter and the backward sweep are handed (valid behind kStepViews)
     const KernelDev *step_kdevs() const { return n_modes ? kdevs_post.data() : kdevs.data(); }
     const float *const *pre_arg() const { return n_modes ? pre_ptr : nullptr; }
+    // the terms as the one-workgroup engines' launch requests take them (engine.h: TermModel; all null without a matrix or a mode):
+    // the matrices by value from the pinned copies the setters keep -- K host pointers into compat_host, null for a Potts term
+    const float *host_mats[LCCRF_MAX_KERNELS] = {};
+    TermModel term_model()
+    {
+        for (size_t k = 0; k < kernels.size(); ++k) host_mats[k] = compat_ptr[k] ? compat_host + k * (size_t)L * L : nullptr;
+        return TermModel{n_compat ? host_mats : nullptr, pre_arg(), n_modes ? norm_mode : nullptr};
+    }
     void clear_norm_modes();
     void set_norm_mode(int k, int mode);
     void clear_compat();
@@ -364,6 +365,7 @@ private:
     int ensure_factors();
     CrfDev begin_iteration();
     void end_iteration(int with_map);
+    bool launch_sized(const Schedule &run, LeanPrep *prep);
 };
 
 }  // namespace lccrf

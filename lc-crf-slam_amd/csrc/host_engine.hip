@@ -741,10 +741,11 @@ int Engine::run_frame(const Schedule &run)
     // (label-derived energies already written for lattices in locality mode sit in the INTERNAL point order: the frame kernel, which
     //  works in the caller's order, derives them from the labels again)
     const bool from_label = (unary_deferred || (unary_is_label && perm_on)) && L == 2;
+    const bool one_shape = stop || general;           // one 1024-lane workgroup per frame: no hand-off area, no record area
     unsigned *dual = nullptr;
     // The tracker's case (one frame, 255 idle CUs) and small batches (a quarter as many frames as CUs, or fewer): every
     // frame gets two workgroups, one per lattice build.
-    if (crf.K == 2 && F <= kDualMaxFrames && !opt_single_wg && !stop && !general) {
+    if (crf.K == 2 && F <= kDualMaxFrames && !opt_single_wg && !one_shape) {
         if (!dual_area) {
             int rc = mem.alloc(reinterpret_cast<char **>(&dual_area), frame_dual_bytes(std::min(Fcap, kDualMaxFrames)));
             if (rc) return rc;
@@ -760,7 +761,7 @@ int Engine::run_frame(const Schedule &run)
     // full-size frames, two per CU (frame_lean.hip): the record area its loop re-reads is allocated when a batch first wants it
     // (sized for the frames BOUND, not for the handle's capacity -- 96 KB per frame: a handle created for 16384 frames that runs 1024 takes
     //  0.1 GB, not 1.6; a later, larger batch gets a new area, the old one stays with the handle until it is destroyed -- ADVICE r5)
-    if (!stop && !general && frame_lean_ok && lean_rec_frames < F && frame_lean_wanted(crf)) {
+    if (!one_shape && frame_lean_ok && lean_rec_frames < F && frame_lean_wanted(crf)) {
         // (no memory for the area: the batch keeps the one-frame-per-CU kernel, which needs none)
         lean_rec = nullptr;
         lean_rec_frames = 0;
@@ -773,30 +774,12 @@ int Engine::run_frame(const Schedule &run)
             lean_rec_frames = want;
         }
     }
-    int shape = 0;
-    if (general) {
-        // a matrix or a mode on some term: always one 1024-lane workgroup per frame, the matrices by value from the pinned copies
-        // the setters keep, the factors of every mode formed in the kernel (no ensure_factors(): nothing of it is in HBM)
-        const float *mats[LCCRF_MAX_KERNELS] = {};
-        const float *const *compat = host_matrices(mats);
-        const int16_t *label = from_label ? deferred_label : nullptr;
-        if (stop)
-            launch_frame_general_converged(crf, kdevs.data(), run.n_iter, run.criterion, run.tol, with_map, run.relax, late_status,
-                                           frame_status, label, deferred_tbl.v, compat, norm_mode, conv_out(), stream,
-                                           by_word ? done_word : nullptr, done_epoch);
-        else
-            launch_frame_general(crf, kdevs.data(), run.n_iter, with_map, run.relax, late_status, frame_status, label, deferred_tbl.v,
-                                 compat, norm_mode, stream, by_word ? done_word : nullptr, done_epoch);
-    } else if (stop) {
-        // until converged (frame_converge.hip): always one 1024-lane workgroup per frame; the report leaves with the results
-        launch_frame_converged(crf, kdevs.data(), run.n_iter, run.criterion, run.tol, with_map, run.relax, late_status, frame_status,
-                               from_label ? deferred_label : nullptr, deferred_tbl.v, conv_out(), stream,
-                               by_word ? done_word : nullptr, done_epoch);
-    } else {
-        shape = launch_frame(crf, kdevs.data(), run.n_iter, with_map, run.relax, late_status, frame_status,
-                             from_label ? deferred_label : nullptr, deferred_tbl.v, stream, frame_small_ok, dual, dual_epoch,
-                             by_word ? done_word : nullptr, done_epoch, frame_lean_ok ? lean_rec : nullptr);
-    }
+    // a matrix or a mode on some term: the matrices travel by value from the pinned copies the setters keep, the factors of every
+    // mode are formed in the kernel (no ensure_factors(): nothing of it is in HBM); until converged: the report leaves with the results
+    const FrameRequest rq{run, term_model(), late_status, frame_status, from_label ? deferred_label : nullptr, deferred_tbl.v,
+                          by_word ? done_word : nullptr, done_epoch, conv_out(), frame_small_ok, dual, dual_epoch,
+                          !one_shape && frame_lean_ok ? lean_rec : nullptr};
+    const int shape = launch_frame(crf, kdevs.data(), rq, stream);
     HIP_TRY(hipGetLastError());
     frame_small_used = shape == 1;
     frame_lean_used = shape == 2;
@@ -823,8 +806,8 @@ int Engine::inference(int n_iter, int with_map, float relax)
     // Object API: nothing has been built yet (add_pairwise only stages features) -> do not build, run the
     // frame in one launch.  If a probe already forced the lattices into HBM, iterate on those instead.
     if (late_ok && frame_ok() && !(built_upto == (int)kernels.size() && sizes_known))
-        return run_frame({n_iter, with_map, relax, false, 0, 0.0f});
-    return inference_sized(n_iter, with_map, relax, kMayReorder);   // (large frames: lattices built from here may use locality mode)
+        return run_frame(fixed_run(n_iter, with_map, relax));
+    return inference_sized(fixed_run(n_iter, with_map, relax), kMayReorder);   // (large frames: lattices built from here may use locality mode)
 }
 
 // The one place where an engine's lazily made state is brought up to date (host_engine.h: Need), in the order of the bits.
@@ -862,57 +845,64 @@ int Engine::run(int n_iter, int with_map, float relax)
     if (!unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
     int rc = resolve_late();
     if (rc) return rc;
-    if (frame_ok()) return run_frame({n_iter, with_map, relax, false, 0, 0.0f});
+    if (frame_ok()) return run_frame(fixed_run(n_iter, with_map, relax));
     invalidate_lattices();                            // two-kernel path: rebuild for the current inputs, then infer
-    return inference_sized(n_iter, with_map, relax);
+    return inference_sized(fixed_run(n_iter, with_map, relax));
 }
 
-int Engine::inference_sized(int n_iter, int with_map, float relax, unsigned more_needs)
+// The fused engine's kernels on the lattices in HBM (behind kSized | kStepViews): the one launch, and what the engine records of it.
+// False: the frames are not ones the kernel takes and nothing was launched.  (The k_converge route leaves fused_shape as it was.)
+bool Engine::launch_sized(const Schedule &run, LeanPrep *prep)
+{
+    const SizedRequest rq{run, term_model(), conv_out(), prep};
+    const SizedLaunch r = launch_inference(crf, step_kdevs(), maxV.data(), maxRow.data(), rq, stream);
+    if (!r.report) return false;
+    engine_used = sized_engine;
+    conv_engine = run.until_converged ? sized_engine : 0;
+    engine_shape = r.report;
+    if (!run.until_converged || rq.terms.general()) fused_shape = r.shape;
+    started = true;
+    if (run.until_converged) conv_valid = true;
+    return true;
+}
+
+int Engine::inference_sized(const Schedule &run, unsigned more_needs)
 {
     const int rc = make_ready(kSized | kUnaries | kStepViews | more_needs);
     if (rc) return rc;
     engine_used = sized_engine;
     engine_shape = 0;
-    last_with_map = with_map;
+    last_with_map = run.with_map;
     conv_engine = 0;
     if (perm_on || sized_engine == 1) {
         const CrfDev v = begin_iteration();
-        for (int it = 0; it < n_iter; ++it) launch_step_stream(v, step_kdevs(), maxV.data(), relax, stream, compat_arg(), pre_arg());
-        end_iteration(with_map);
-    } else if (sized_engine == 2) {
-        // the two-frames-per-CU kernel runs from prepared launch records (fused_lean.h: LeanPrepPlan): one block per frame, owned
-        // here, (re)written by the first inference behind a build -- learn_sizes() clears `valid` whenever a lattice has changed
-        const size_t prep_need = lean_prep_bytes(crf, kdevs.data(), maxV.data(), maxRow.data());
-        if (prep_need > lean_prep.bytes) {
-            lean_prep.valid = false;
-            lean_prep.buf = nullptr;                       // (an outgrown block stays with the arena until the handle goes)
-            lean_prep.bytes = 0;
-            unsigned char *p = nullptr;
-            if (mem.alloc(&p, prep_need, false) == LCCRF_OK) {
-                lean_prep.buf = p;
-                lean_prep.bytes = prep_need;
-            } else {
-                (void)hipGetLastError();                   // no room: the self-contained kernel runs instead, same results
-            }
-            if (!lean_prep.ev0) {
-                (void)hipEventCreate(&lean_prep.ev0);
-                (void)hipEventCreate(&lean_prep.ev1);
-            }
-        }
-        fused_shape = launch_inference_fused(crf, kdevs.data(), maxV.data(), maxRow.data(), n_iter, with_map, relax, stream,
-                                             prep_need ? &lean_prep : nullptr, &engine_shape);
-        started = true;
-    } else if (sized_engine == 4) {
-        // the fused engine's general kernel (fused_general.hip), behind ensure_factors(): one launch on the factors' views, a
-        // workgroup per frame; the matrices travel by value, from the pinned copies the setters keep.  The prepared launch records
-        // (lean_prep) are the Potts path's: not looked at here
-        const float *mats[LCCRF_MAX_KERNELS] = {};
-        engine_shape = launch_inference_general(crf, step_kdevs(), maxV.data(), maxRow.data(), host_matrices(mats), pre_arg(),
-                                                n_iter, with_map, relax, stream);
-        if (!engine_shape) return fail(LCCRF_E_STATE, "the fused engine's general kernel was chosen for a frame it does not take");
-        fused_shape = 1024 | 1 << 16;                      // lanes per frame | frames per CU
-        started = true;
+        for (int it = 0; it < run.n_iter; ++it) launch_step_stream(v, step_kdevs(), maxV.data(), run.relax, stream, compat_arg(), pre_arg());
+        end_iteration(run.with_map);
+        HIP_TRY(hipGetLastError());
+        return LCCRF_OK;
     }
+    // Potts terms (sized_engine 2): the two-frames-per-CU kernel runs from prepared launch records (fused_lean.h: LeanPrepPlan): one
+    // block per frame, owned here, (re)written by the first inference behind a build -- learn_sizes() clears `valid` whenever a lattice
+    // has changed.  The general kernel (4; fused_general.hip, on the factors' views of ensure_factors()) does not look at them.
+    const size_t prep_need = sized_engine == 2 ? lean_prep_bytes(crf, kdevs.data(), maxV.data(), maxRow.data()) : 0;
+    if (prep_need > lean_prep.bytes) {
+        lean_prep.valid = false;
+        lean_prep.buf = nullptr;                       // (an outgrown block stays with the arena until the handle goes)
+        lean_prep.bytes = 0;
+        unsigned char *p = nullptr;
+        if (mem.alloc(&p, prep_need, false) == LCCRF_OK) {
+            lean_prep.buf = p;
+            lean_prep.bytes = prep_need;
+        } else {
+            (void)hipGetLastError();                   // no room: the self-contained kernel runs instead, same results
+        }
+        if (!lean_prep.ev0) {
+            (void)hipEventCreate(&lean_prep.ev0);
+            (void)hipEventCreate(&lean_prep.ev1);
+        }
+    }
+    if (!launch_sized(run, prep_need ? &lean_prep : nullptr))
+        return fail(LCCRF_E_STATE, "the fused engine's %s was chosen for a frame it does not take", sized_engine == 4 ? "general kernel" : "kernel");
     HIP_TRY(hipGetLastError());
     return LCCRF_OK;
 }
@@ -958,43 +948,24 @@ int Engine::check_converged_args(int max_iter, int criterion, float tol, float r
 // launch records are left alone): the frames the fused plan takes in ONE launch with the stop decision inside the kernel -- Potts
 // terms normalised AFTER on k_converge, a batch's terms with a matrix or a mode on k_general_converge -- the rest on the streaming
 // step with the bookkeeping of converge_track.hip behind it.
-int Engine::inference_converged(int max_iter, int criterion, float tol, int with_map, float relax)
+int Engine::inference_converged(const Schedule &run)
 {
-    int rc = check_converged_args(max_iter, criterion, tol, relax);
+    int rc = check_converged_args(run.n_iter, run.criterion, run.tol, run.relax);
     if (rc) return rc;
     if (!unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
     if ((rc = make_ready(kSettled | kSized | kMayReorder | kUnaries | kStepViews))) return rc;   // (large frames: may use locality mode)
-    last_with_map = with_map;
+    last_with_map = run.with_map;
     conv_valid = false;
-    if (sized_engine == 2 && !perm_on) {
-        const int shape = launch_inference_converged(crf, kdevs.data(), maxV.data(), maxRow.data(), max_iter, criterion, tol, with_map,
-                                                     relax, conv_out(), stream);
-        if (shape) {
-            HIP_TRY(hipGetLastError());
-            engine_used = conv_engine = 2;
-            engine_shape = shape;
-            started = conv_valid = true;
-            return LCCRF_OK;
-        }
-    }
-    // A BATCH whose terms carry a matrix or a mode, on the frames choose_sized_engine() names: fused_general_converge.hip, one launch
-    // on the factors' views (kStepViews above).  A handle's converged call keeps the streaming step (include/lccrf.h section 1h).
-    if (sized_engine == 4 && !perm_on && (F > 1 || batch_owned)) {
-        const float *mats[LCCRF_MAX_KERNELS] = {};
-        const int shape = launch_inference_general_converged(crf, step_kdevs(), maxV.data(), maxRow.data(), host_matrices(mats), pre_arg(),
-                                                             max_iter, criterion, tol, with_map, relax, conv_out(), stream);
-        if (shape) {                                       // (0: a plan without room for the reduction's words streams)
-            HIP_TRY(hipGetLastError());
-            engine_used = conv_engine = 4;
-            engine_shape = shape;
-            fused_shape = 1024 | 1 << 16;
-            started = conv_valid = true;
-            return LCCRF_OK;
-        }
+    // Potts terms on k_converge; a BATCH whose terms carry a matrix or a mode, on the frames choose_sized_engine() names, on
+    // k_general_converge (the factors' views: kStepViews above) -- a handle's converged call keeps the streaming step (include/lccrf.h
+    // section 1h).  Nothing launched (a plan without room for the reduction's words): the streaming step as well.
+    if (!perm_on && (sized_engine == 2 || (sized_engine == 4 && (F > 1 || batch_owned))) && launch_sized(run, nullptr)) {
+        HIP_TRY(hipGetLastError());
+        return LCCRF_OK;
     }
     engine_used = conv_engine = 1;
     engine_shape = 0;
-    if ((rc = converge_stream(max_iter, criterion, tol, with_map, relax))) return rc;
+    if ((rc = converge_stream(run))) return rc;
     conv_valid = true;
     return LCCRF_OK;
 }
@@ -1004,23 +975,24 @@ int Engine::inference_converged(int max_iter, int criterion, float tol, int with
 // report); whether every frame fitted is known at the next synchronisation point, where resolve_late() re-runs the flagged ones with
 // inference_converged().  Anything else builds into HBM and takes inference_converged() at once -- as does a handle whose lattices
 // are already built and sized (a probe put them there), the rule of Engine::inference.
-int Engine::run_converged(int max_iter, int criterion, float tol, int with_map, float relax)
+int Engine::run_converged(const Schedule &run)
 {
-    int rc = check_converged_args(max_iter, criterion, tol, relax);
+    int rc = check_converged_args(run.n_iter, run.criterion, run.tol, run.relax);
     if (rc) return rc;
     if (!unary_set) return fail(LCCRF_E_STATE, "unary energies not set");
     if ((rc = resolve_late())) return rc;
-    if (late_ok && built_upto == (int)kernels.size() && sizes_known) return inference_converged(max_iter, criterion, tol, with_map, relax);
-    if (frame_ok()) return run_frame({max_iter, with_map, relax, true, criterion, tol});
+    if (late_ok && built_upto == (int)kernels.size() && sizes_known) return inference_converged(run);
+    if (frame_ok()) return run_frame(run);
     invalidate_lattices();                            // two-kernel path: rebuild for the current inputs, then infer
-    return inference_converged(max_iter, criterion, tol, with_map, relax);
+    return inference_converged(run);
 }
 
 // The streaming path: start, then per iteration the unchanged step, the comparison and the settle kernel, ONE synchronisation of the
 // call's stream and one pinned word read -- the frames still running.  These are the frames where an iteration is many launches
 // anyway.  The kept copy of the previous Q is io_a.
-int Engine::converge_stream(int max_iter, int criterion, float tol, int with_map, float relax)
+int Engine::converge_stream(const Schedule &run)
 {
+    const int max_iter = run.n_iter;
     int rc = need_io();
     if (rc) return rc;
     const CrfDev cp = begin_iteration();              // (locality mode: iterate and compare in the internal order, as inference_sized())
@@ -1029,15 +1001,15 @@ int Engine::converge_stream(int max_iter, int criterion, float tol, int with_map
     launch_track_begin(cp, tk, max_iter, stream);
     int t_last = 0;
     for (int t = 1; t <= max_iter; ++t) {
-        launch_step_stream(cp, step_kdevs(), maxV.data(), relax, stream, compat_arg(), pre_arg());
-        launch_track_step(cp, tk, t, max_iter, criterion, tol, stream);
+        launch_step_stream(cp, step_kdevs(), maxV.data(), run.relax, stream, compat_arg(), pre_arg());
+        launch_track_step(cp, tk, t, max_iter, run.criterion, run.tol, stream);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(stream));
         t_last = t;
         if (*conv_running == 0) break;
     }
     if (F > 1 && t_last > 1) launch_track_restore(cp, tk, t_last, stream);
-    end_iteration(with_map);
+    end_iteration(run.with_map);
     HIP_TRY(hipGetLastError());
     return LCCRF_OK;
 }
@@ -1129,8 +1101,7 @@ int Engine::resolve_late(bool *seen_done)
 // frames): the fixed count, or -- behind run_converged() -- the same stop rule.
 int Engine::rerun_on(Engine &e)
 {
-    if (late.until_converged) return e.inference_converged(late.n_iter, late.criterion, late.tol, late.with_map, late.relax);
-    return e.inference_sized(late.n_iter, late.with_map, late.relax);
+    return late.until_converged ? e.inference_converged(late) : e.inference_sized(late);
 }
 
 // Two-kernel path for the frames fb_list_host[0, n) only, in a compact sub-engine; results scattered back.

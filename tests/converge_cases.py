@@ -145,6 +145,35 @@ def settings(tr, N):
     return out
 
 
+# ---- a plan with no room for the reduction's words ---------------------------------------------------------------------------
+# The converged kernels want 16 bytes of LDS behind the loop's plan (csrc/fused_loop.h: layout_core, kConvergeLds); a frame whose
+# plan fills a workgroup's 160 KiB to the byte is one the fixed-count kernels take and the converged ones do not: their launchers
+# return 0 and the call falls through to the streaming step.  Plans are multiples of 16 bytes, so that frame has to be built: 1025
+# points (two per lane) dealt round robin over m far-apart sites per term -- every site a lattice cell of its own, V = 3 m, rows of
+# at most two products -- with two product buffers of 8 * ceil64(3 * 1025) bytes.  (629, 631) sites: 163 840 bytes, the limit;
+# (628, 631): 96 bytes below it, the nearest plan that still has room.
+EDGE_N, EDGE_FULL, EDGE_ROOM, LDS_LIMIT = 1025, (629, 631), (628, 631), 160 * 1024
+
+
+def edge_plan_bytes(N, V):
+    """layout_core's total for lattices of V[k] vertices, every term with a product buffer of its own, no chain rows"""
+    a16 = lambda b: (b + 15) & ~15
+    tables = sum(2 * a16(8 * (v + 1)) + a16(12 * v) + a16(2 * (v + 2)) for v in V)
+    return 128 + 64 + tables + len(V) * 8 * ((3 * N + 63) & ~63)
+
+
+def edge_problem(sites, seed=11):
+    """EDGE_N points, term k's features on sites[k] sites of a grid eight lattice units apart; random labels"""
+    rng = np.random.default_rng([seed, EDGE_N])
+    kernels = []
+    for m in sites:
+        side = int(np.ceil(np.sqrt(m)))
+        site = np.arange(EDGE_N) % m
+        f = np.stack([site % side, site // side], 1).astype(F32) * F32(8) + F32(0.25)
+        kernels.append((f, F32(3.0)))
+    return dict(N=EDGE_N, L=2, label=rng.integers(0, 2, EDGE_N).astype(np.int16), conf=F32(0.7), kernels=kernels)
+
+
 # ---- the reduction's reach: cases in which ONE point decides -----------------------------------------------------------------
 def deciding(tr, cap=8):
     """(t, point, tol) such that at iteration t the largest per-point change is alone above tol -- tol lies between it and the

@@ -10,6 +10,7 @@ CPU: the entry points, the argument checks that need no device, that the batches
 the stop profile of the convergence batches, and that one point decides in the frames the reach test picks.  GPU: the rest."""
 import ctypes as C
 import importlib
+import types
 
 import numpy as np
 import pytest
@@ -487,6 +488,44 @@ def test_a_handle_sized_batch_takes_the_kernel_and_the_sparse_plan_has_room(po, 
     for crit, tol, cap in ((cv.LABELS, F32(0), bg.CAP), (cv.DELTA, F32(1e-2), bg.CAP), (cv.LABELS, F32(0), 2)):
         b.inference_converged(cap, crit, tol, True, 0.5)
         _check_converged(b, sp, trs, crit, tol, cap, 4, ("sparse+N1025", crit, cap))
+    b.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sites,engine", [(cv.EDGE_FULL, 1), (cv.EDGE_ROOM, 4)], ids=["full", "room"])
+def test_a_plan_without_room_for_the_reductions_words_streams(po, sites, engine):
+    """three frames -- the frame whose plan fills the workgroup's LDS to the byte (tests/converge_cases.py: edge_problem; or the one
+    96 bytes short of it), its first five points, the frame again -- with a matrix and the SYMMETRIC mode on the first term: k_general
+    takes the batch either way (lccrf_batch_inference: engine 4); k_general_converge takes it only with 16 bytes to spare -- without
+    them its launcher returns 0 and the converged call runs on the streaming step (engine 1), with the same results"""
+    pb = cv.edge_problem(sites)
+    modes, mats = [nc.SYMMETRIC, nc.AFTER], [(np.eye(2) + 0.3 * np.random.default_rng(5).standard_normal((2, 2))).astype(F32), None]
+    w = [F32(x) for _, x in pb["kernels"]]
+    N = np.array([cv.EDGE_N, 5, cv.EDGE_N], np.int32)
+    maxN = cv.EDGE_N + bg.MAX_POINTS_SLACK
+    feats, unary, frames = [np.zeros((3, maxN, 2), F32) for _ in range(2)], np.zeros((3, maxN, 2), F32), {}
+    for n in (cv.EDGE_N, 5):
+        p = dict(pb, N=n, label=pb["label"][:n], kernels=[(f[:n], x) for f, x in pb["kernels"]])
+        o = cc.setup(po.OracleCRF, p)
+        frames[n] = (o.unary(), nc.feats(p), [o.kernel(k)["norm"] for k in range(2)])
+        o.close()
+    for f, n in enumerate(N):
+        unary[f, :n] = frames[n][0]
+        for k in range(2):
+            feats[k][f, :n] = frames[n][1][k]
+    b = pkg.BatchCRF(3, maxN, 2, [2, 2], [float(x) for x in w])
+    bg.apply(b, modes, mats)
+    b.set_inputs_host(N, feats, unary=unary)
+    b.build()
+    shape = types.SimpleNamespace(N=N)                            # (what _check_converged and check_frames read of a Batch)
+    for relax in cv.RELAX:
+        trs = [nc.restate_trace_f32(frames[n][0], frames[n][1], w, mats, modes, bg.CAP, relax, frames[n][2]) for n in N]
+        for crit, tol, cap in ((cv.LABELS, F32(0), bg.CAP), (cv.DELTA, F32(1e-3), bg.CAP), (cv.DELTA, F32(0), 2)):
+            b.inference_converged(cap, crit, tol, True, relax)
+            _check_converged(b, shape, trs, crit, tol, cap, engine, (sites, crit, cap, relax))
+    b.inference(2, True, 1.0)                                     # the fixed count on the same lattices: k_general takes both
+    assert b.engine() == 4 and b.fused_shape() == (1024, 1)
+    bg.check_frames(b, shape, [nc.restate_trace_f32(frames[n][0], frames[n][1], w, mats, modes, 2, 1.0, frames[n][2])[2] for n in N], sites)
     b.close()
 
 

@@ -205,6 +205,34 @@ def test_handle_on_a_lattice_beyond_the_prologues_register_rounds(po, wl):
     h.close()
 
 
+def test_edge_frames_fill_the_plan_to_the_byte_and_96_bytes_short_of_it(po):
+    for sites, want in ((cv.EDGE_FULL, cv.LDS_LIMIT), (cv.EDGE_ROOM, cv.LDS_LIMIT - 96)):
+        pb = cv.edge_problem(sites)
+        o = cc.setup(po.OracleCRF, pb)
+        ks = [o.kernel(k) for k in range(2)]
+        o.close()
+        assert [k["V"] for k in ks] == [3 * m for m in sites]
+        assert max(int(np.bincount(k["offset"].reshape(-1)).max()) for k in ks) == 2          # short rows: no chain path
+        assert cv.edge_plan_bytes(cv.EDGE_N, [k["V"] for k in ks]) == want
+    assert want + 16 <= cv.LDS_LIMIT < cv.edge_plan_bytes(cv.EDGE_N, [3 * m for m in cv.EDGE_FULL]) + 16
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sites,engine", [(cv.EDGE_FULL, 1), (cv.EDGE_ROOM, 2)], ids=["full", "room"])
+def test_a_plan_without_room_for_the_reductions_words_streams(po, sites, engine):
+    """the fused engine takes the frame (lccrf_inference: engine 2); k_converge takes it only with 16 bytes to spare -- without them
+    its launcher returns 0 and the converged call runs on the streaming step (engine 1, shape word 0), with the same results"""
+    pb = cv.edge_problem(sites)
+    h = cc.setup(pkg.DenseCRFHIP, pb)
+    for relax in cv.RELAX:
+        tr = cv.oracle_trace(po, pb, relax)
+        for crit, tol, cap in ((cv.LABELS, F32(0), cv.CAP), (cv.DELTA, F32(1e-3), cv.CAP), (cv.DELTA, F32(0), 2), (cv.LABELS, F32(0), 0)):
+            _check(h, tr, crit, tol, cap, relax, (1, 0) if engine == 1 else (2, 1024 | 2 << 16), sites)
+    h.inference(2, True, 1.0)                                     # the fixed count on the same lattices: the fused engine takes both
+    assert h.engine() == (2, 1024 | 2 << 16) and cc.same_bits(h.probability(), cv.oracle_trace(po, pb, 1.0, 2)[2])
+    h.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("N", (700, 2500))
 def test_one_point_decides_wherever_it_sits(po, wl, N):
