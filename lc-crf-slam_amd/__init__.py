@@ -242,25 +242,81 @@ def _p(a, t):
     return a.ctypes.data_as(t)
 
 
-class DenseCRFHIP:
+class _Handle:
+    """What DenseCRFHIP and BatchCRF share: the calls of sections 1 and 2 that differ in the C name's prefix alone (_PREFIX:
+    lccrf_ / lccrf_batch_), on the handle self.h of self.L labels.  For a batch they act on every frame."""
+    _PREFIX = None
+
+    def _c(self, name):
+        return getattr(lib(), self._PREFIX + name)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._c("destroy")(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set_option(self, option, value):
+        _check(self._c("set_option")(self.h, int(option), int(value)))
+
+    def set_pairwise_weight(self, k, w):
+        """PottsPotential3D::w_ of term k; the next inference equals that of a handle or batch created with weight w."""
+        _check(self._c("set_pairwise_weight")(self.h, int(k), float(w)))
+
+    # -- label-compatibility matrices (include/lccrf.h sections 1e and 2g) ----------------------------------------------------------
+    def set_pairwise_compatibility(self, k, compat):
+        """The [L][L] matrix mu of term k: next[i][l] += w * norm[i] * sum_l' mu[l][l'] * Phi(Q)[i][l'].  None: Potts again."""
+        m = None
+        if compat is not None:
+            m = _f32(compat).reshape(-1)
+            if m.size != self.L * self.L:
+                raise ValueError("compat must have L*L entries")
+        _check(self._c("set_pairwise_compatibility")(self.h, int(k), None if m is None else _p(m, _f32p)))
+
+    def get_pairwise_compatibility(self, k):
+        """(matrix [L][L], is_set) of term k; the identity for a term without a matrix."""
+        out = np.empty((self.L, self.L), np.float32)
+        flag = C.c_int(0)
+        _check(self._c("get_pairwise_compatibility")(self.h, int(k), _p(out, _f32p), C.byref(flag)))
+        return out, bool(flag.value)
+
+    # -- normalisation modes (include/lccrf.h sections 1g and 2g) -------------------------------------------------------------------
+    def set_normalization(self, k, mode):
+        """Where term k applies its norm: NORMALIZE_AFTER (the reference, the default), _BEFORE, _SYMMETRIC or _NONE."""
+        _check(self._c("set_pairwise_normalization")(self.h, int(k), int(mode)))
+
+    def get_normalization(self, k):
+        mode = C.c_int(0)
+        _check(self._c("get_pairwise_normalization")(self.h, int(k), C.byref(mode)))
+        return mode.value
+
+    # -- what the two-label step does for the lattices now in HBM -------------------------------------------------------------------
+    def splat_plan(self, k):
+        """How the two-label step splats term k for the lattices now in HBM (lccrf_splat_plan): dict(passes, halo, window, lanes,
+        vertices_per_lane, long_mode)."""
+        p = SplatPlan()
+        _check(self._c("get_splat_plan")(self.h, int(k), C.byref(p)))
+        return p.as_dict()
+
+    def blur_plan(self, k):
+        """Which way the d + 1 blur passes of term k go in the two-label step for the lattices now in HBM (lccrf_blur_plan): dict(in_splat,
+        paired_table, paired_plain, alone_32bit, alone_compact, in_slice, nontemporal, first_table_pair)."""
+        p = BlurPlan()
+        _check(self._c("get_blur_plan")(self.h, int(k), C.byref(p)))
+        return p.as_dict()
+
+
+class DenseCRFHIP(_Handle):
     """Mirror of DenseCRF3D<M> + PottsPotential3D<M,F> (densecrf3d.h, pairwise3d.h) on the
     HIP path.  Same method meaning and call order as the reference; host arrays in/out."""
+    _PREFIX = "lccrf_"
 
     def __init__(self, N, L, device=0):
         self.N, self.L = int(N), int(L)
         self._d = []
         self.h = C.c_void_p()
         _check(lib().lccrf_create(C.byref(self.h), int(device), self.N, self.L))
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().lccrf_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
-    def set_option(self, option, value):
-        _check(lib().lccrf_set_option(self.h, int(option), int(value)))
 
     # -- unary -------------------------------------------------------------------------
     def set_unary(self, unary):
@@ -293,20 +349,6 @@ class DenseCRFHIP:
         a = _f32(xy)
         _check(lib().lccrf_add_smooth_kernel(self.h, float(w), _p(a, _f32p), float(sd2d)))
         self._d.append(2)
-
-    def splat_plan(self, k):
-        """How the two-label step splats term k for the lattices now in HBM (lccrf_splat_plan): dict(passes, halo, window, lanes,
-        vertices_per_lane, long_mode)."""
-        p = SplatPlan()
-        _check(lib().lccrf_get_splat_plan(self.h, int(k), C.byref(p)))
-        return p.as_dict()
-
-    def blur_plan(self, k):
-        """Which way the d + 1 blur passes of term k go in the two-label step for the lattices now in HBM (lccrf_blur_plan): dict(in_splat,
-        paired_table, paired_plain, alone_32bit, alone_compact, in_slice, nontemporal, first_table_pair)."""
-        p = BlurPlan()
-        _check(lib().lccrf_get_blur_plan(self.h, int(k), C.byref(p)))
-        return p.as_dict()
 
     # -- inference ---------------------------------------------------------------------
     def start_inference(self):
@@ -403,7 +445,7 @@ class DenseCRFHIP:
     def add_image_kernel(self, width, height, w, posdev, d_image=None, image_format=IMAGE_NONE, featuredev=0.0):
         """PottsPotentialCPU<M,F>::FromImage with the image (uint8 or float RGB, HWC) on the device."""
         _check(lib().lccrf_add_image_kernel(self.h, int(width), int(height), float(w), float(posdev),
-                                            C.c_void_p(d_image) if d_image else None, int(image_format), float(featuredev)))
+                                            _addr(d_image), int(image_format), float(featuredev)))
         self._d.append(2 if image_format == IMAGE_NONE else 5)
 
     def device_buffers(self):
@@ -425,10 +467,6 @@ class DenseCRFHIP:
         _check(lib().lccrf_map_of_device(self.h, C.c_void_p(d_prob), C.c_void_p(d_map)))
 
     # -- gradients of inference() (include/lccrf.h section 1c; the torch layer: autograd.py) ----------------------------------
-    def set_pairwise_weight(self, k, w):
-        """PottsPotential3D::w_ of term k; the next inference equals that of a handle built with weight w."""
-        _check(lib().lccrf_set_pairwise_weight(self.h, int(k), float(w)))
-
     def inference_backward_device(self, n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights=None):
         """dL/dU [N][L] and dL/dw [K] of inference(n_iterations, relax) from dL/dQ [N][L]; device addresses, on stream()."""
         _check(lib().lccrf_inference_backward(self.h, int(n_iterations), float(relax), _addr(d_grad_prob), _addr(d_grad_unary),
@@ -441,24 +479,7 @@ class DenseCRFHIP:
         _check(lib().lccrf_inference_backward_features(self.h, int(n_iterations), float(relax), _addr(d_grad_prob),
                                                        _addr(d_grad_unary), _addr(d_grad_weights), _addr_list(d_grad_features)))
 
-    # -- label-compatibility matrices (include/lccrf.h section 1e) -----------------------------------------------------------
-    def set_pairwise_compatibility(self, k, compat):
-        """The [L][L] matrix mu of term k: next[i][l] += w * norm[i] * sum_l' mu[l][l'] * Phi(Q)[i][l'].  None: Potts again."""
-        if compat is None:
-            _check(lib().lccrf_set_pairwise_compatibility(self.h, int(k), None))
-            return
-        m = _f32(compat).reshape(-1)
-        if m.size != self.L * self.L:
-            raise ValueError("compat must have L*L entries")
-        _check(lib().lccrf_set_pairwise_compatibility(self.h, int(k), _p(m, _f32p)))
-
-    def get_pairwise_compatibility(self, k):
-        """(matrix [L][L], is_set) of term k; the identity for a term without a matrix."""
-        out = np.empty((self.L, self.L), np.float32)
-        flag = C.c_int(0)
-        _check(lib().lccrf_get_pairwise_compatibility(self.h, int(k), _p(out, _f32p), C.byref(flag)))
-        return out, bool(flag.value)
-
+    # -- ... with respect to the label-compatibility matrices (include/lccrf.h section 1e) -------------------------------------
     def inference_backward_compat_device(self, n_iterations, relax, d_grad_prob, d_grad_unary=None, d_grad_weights=None,
                                          d_grad_compat=None):
         """inference_backward_device plus dL/dmu: d_grad_compat is the device address of a [K][L][L] array (None: the call is
@@ -473,16 +494,6 @@ class DenseCRFHIP:
         inference_backward_features_device takes it, d_grad_compat as inference_backward_compat_device; any output may be None."""
         _check(lib().lccrf_inference_backward_all(self.h, int(n_iterations), float(relax), _addr(d_grad_prob), _addr(d_grad_unary),
                                                   _addr(d_grad_weights), _addr_list(d_grad_features), _addr(d_grad_compat)))
-
-    # -- normalisation modes (include/lccrf.h section 1g) ------------------------------------------------------------------------
-    def set_normalization(self, k, mode):
-        """Where term k applies its norm: NORMALIZE_AFTER (the reference, the default), _BEFORE, _SYMMETRIC or _NONE."""
-        _check(lib().lccrf_set_pairwise_normalization(self.h, int(k), int(mode)))
-
-    def get_normalization(self, k):
-        mode = C.c_int(0)
-        _check(lib().lccrf_get_pairwise_normalization(self.h, int(k), C.byref(mode)))
-        return mode.value
 
     # -- results -----------------------------------------------------------------------
     def map(self):
@@ -522,8 +533,9 @@ class DenseCRFHIP:
         return dict(d=d, V=V, norm=norm, offset=off, bary=bary, nbr=nbr)
 
 
-class BatchCRF:
+class BatchCRF(_Handle):
     """Frames-in-flight: F independent CRFs with a common stride (include/lccrf.h section 2)."""
+    _PREFIX = "lccrf_batch_"
 
     def __init__(self, max_frames, max_points, n_labels, feat_dims, weights, device=0):
         self.F, self.maxN, self.L = int(max_frames), int(max_points), int(n_labels)
@@ -539,16 +551,6 @@ class BatchCRF:
         self.n_frames, self.n_points = 0, None        # n_points: the host counts of the inputs bound, when they came from the host
         _check(lib().lccrf_batch_create(C.byref(self.h), int(device), C.byref(d)))
         self._keep = None
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().lccrf_batch_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
-    def set_option(self, option, value):
-        _check(lib().lccrf_batch_set_option(self.h, int(option), int(value)))
 
     def set_inputs_host(self, n_points, features, unary=None, label=None, conf=None):
         npts = np.ascontiguousarray(n_points, np.int32)
@@ -626,30 +628,27 @@ class BatchCRF:
         if d_label is not None:
             cf = _f32(np.broadcast_to(np.asarray(conf, np.float32), (self.L,)))
         _check(lib().lccrf_batch_bind_inputs_device(
-            self.h, int(n_frames), C.c_void_p(int(d_n_points)),
-            C.c_void_p(int(d_unary)) if d_unary is not None else None,
-            C.c_void_p(int(d_label)) if d_label is not None else None,
+            self.h, int(n_frames), C.c_void_p(int(d_n_points)), _addr(d_unary), _addr(d_label),
             _p(cf, _f32p) if cf is not None else None, arr))
         self.n_frames, self.n_points = int(n_frames), None        # (the counts live on the device)
 
     def build(self, stream=None):
-        _check(lib().lccrf_batch_build(self.h, C.c_void_p(stream) if stream else None))
+        _check(lib().lccrf_batch_build(self.h, _addr(stream)))
 
     def inference(self, n_iter, with_map=True, relax=1.0, stream=None):
-        _check(lib().lccrf_batch_inference(self.h, int(n_iter), int(bool(with_map)), float(relax),
-                                           C.c_void_p(stream) if stream else None))
+        _check(lib().lccrf_batch_inference(self.h, int(n_iter), int(bool(with_map)), float(relax), _addr(stream)))
 
     def inference_converged(self, max_iterations, criterion=STOP_LABELS, tol=0.0, with_map=True, relax=1.0, stream=None):
         """Every frame iterated until ITS criterion holds, at most max_iterations, on built lattices (include/lccrf.h section 2e);
         asynchronous like inference()."""
         _check(lib().lccrf_batch_inference_converged(self.h, int(max_iterations), int(criterion), float(tol), int(bool(with_map)),
-                                                     float(relax), C.c_void_p(stream) if stream else None))
+                                                     float(relax), _addr(stream)))
 
     def run_converged(self, max_iterations, criterion=STOP_LABELS, tol=0.0, with_map=True, relax=1.0, stream=None):
         """run() with inference_converged()'s stop rule (include/lccrf.h section 2f): from inputs alone, every frame built and
         inferred until ITS criterion holds in one launch; asynchronous like run()."""
         _check(lib().lccrf_batch_run_converged(self.h, int(max_iterations), int(criterion), float(tol), int(bool(with_map)),
-                                               float(relax), C.c_void_p(stream) if stream else None))
+                                               float(relax), _addr(stream)))
 
     def convergence(self):
         """dict of [n_frames] arrays: iterations, delta, changed, converged of the last inference_converged() / run_converged()
@@ -668,15 +667,10 @@ class BatchCRF:
 
     def run(self, n_iter, with_map=True, relax=1.0, stream=None):
         """Lattice build + normalisation + inference of every frame in one launch (lccrf_batch_run)."""
-        _check(lib().lccrf_batch_run(self.h, int(n_iter), int(bool(with_map)), float(relax),
-                                     C.c_void_p(stream) if stream else None))
+        _check(lib().lccrf_batch_run(self.h, int(n_iter), int(bool(with_map)), float(relax), _addr(stream)))
 
     def synchronize(self):
         _check(lib().lccrf_batch_synchronize(self.h))
-
-    def set_pairwise_weight(self, k, w):
-        """The weight of term k in every frame; the next inference equals that of a batch created with weight w."""
-        _check(lib().lccrf_batch_set_pairwise_weight(self.h, int(k), float(w)))
 
     def set_unary_device(self, d_unary):
         """Unaries [n_frames][max_points][L] of the frames now bound, copied from a device address on the batch's stream."""
@@ -686,9 +680,7 @@ class BatchCRF:
         """Per frame dL/dU [n_frames][max_points][L] and dL/dw [n_frames][K] of inference(n_iterations, relax) from dL/dQ
         [n_frames][max_points][L]; device addresses (include/lccrf.h section 2c)."""
         _check(lib().lccrf_batch_inference_backward(self.h, int(n_iterations), float(relax), C.c_void_p(int(d_grad_prob)),
-                                                    C.c_void_p(int(d_grad_unary)),
-                                                    C.c_void_p(int(d_grad_weights)) if d_grad_weights else None,
-                                                    C.c_void_p(stream) if stream else None))
+                                                    C.c_void_p(int(d_grad_unary)), _addr(d_grad_weights), _addr(stream)))
 
     def inference_backward_features_device(self, n_iterations, relax, d_grad_prob, d_grad_unary=None, d_grad_weights=None,
                                            d_grad_features=None, stream=None):
@@ -696,7 +688,7 @@ class BatchCRF:
         ([n_frames][max_points][d_k] each) or None entries (include/lccrf.h section 2d)."""
         _check(lib().lccrf_batch_inference_backward_features(self.h, int(n_iterations), float(relax), C.c_void_p(int(d_grad_prob)),
                                                              _addr(d_grad_unary), _addr(d_grad_weights), _addr_list(d_grad_features),
-                                                             C.c_void_p(stream) if stream else None))
+                                                             _addr(stream)))
 
     def inference_backward_all_device(self, n_iterations, relax, d_grad_prob, d_grad_unary=None, d_grad_weights=None,
                                       d_grad_features=None, d_grad_compat=None, d_grad_model=None, stream=None):
@@ -705,37 +697,9 @@ class BatchCRF:
         sums over the frames of dL/dw and dL/dmu in ascending frame order; device addresses, any output may be None."""
         _check(lib().lccrf_batch_inference_backward_all(self.h, int(n_iterations), float(relax), C.c_void_p(int(d_grad_prob)),
                                                         _addr(d_grad_unary), _addr(d_grad_weights), _addr_list(d_grad_features),
-                                                        _addr(d_grad_compat), _addr(d_grad_model),
-                                                        C.c_void_p(stream) if stream else None))
+                                                        _addr(d_grad_compat), _addr(d_grad_model), _addr(stream)))
 
-    # -- label-compatibility matrices and normalisation modes (include/lccrf.h section 2g) ---------------------------------------
-    def set_pairwise_compatibility(self, k, compat):
-        """The [L][L] matrix mu of term k in every frame (DenseCRFHIP.set_pairwise_compatibility).  None: Potts again."""
-        if compat is None:
-            _check(lib().lccrf_batch_set_pairwise_compatibility(self.h, int(k), None))
-            return
-        m = _f32(compat).reshape(-1)
-        if m.size != self.L * self.L:
-            raise ValueError("compat must have L*L entries")
-        _check(lib().lccrf_batch_set_pairwise_compatibility(self.h, int(k), _p(m, _f32p)))
-
-    def pairwise_compatibility(self, k):
-        """(matrix [L][L], is_set) of term k; the identity for a term without a matrix."""
-        out = np.empty((self.L, self.L), np.float32)
-        flag = C.c_int(0)
-        _check(lib().lccrf_batch_get_pairwise_compatibility(self.h, int(k), _p(out, _f32p), C.byref(flag)))
-        return out, bool(flag.value)
-
-    def set_normalization(self, k, mode):
-        """Where term k applies its norm in every frame: NORMALIZE_AFTER (the default), _BEFORE, _SYMMETRIC or _NONE."""
-        _check(lib().lccrf_batch_set_pairwise_normalization(self.h, int(k), int(mode)))
-
-    def normalization(self, k):
-        mode = C.c_int(0)
-        _check(lib().lccrf_batch_get_pairwise_normalization(self.h, int(k), C.byref(mode)))
-        return mode.value
-
-    get_pairwise_compatibility, get_normalization = pairwise_compatibility, normalization   # (DenseCRFHIP's names)
+    pairwise_compatibility, normalization = _Handle.get_pairwise_compatibility, _Handle.get_normalization   # (the batch's own names)
 
     def set_engine(self, engine):
         _check(lib().lccrf_batch_set_engine(self.h, int(engine)))
@@ -757,20 +721,6 @@ class BatchCRF:
         _check(lib().lccrf_batch_get_locality_mode(self.h, C.byref(a), C.byref(b)))
         return bool(a.value), bool(b.value)
 
-    def splat_plan(self, k):
-        """How the two-label step splats term k for the lattices now in HBM (lccrf_splat_plan): dict(passes, halo, window, lanes,
-        vertices_per_lane, long_mode)."""
-        p = SplatPlan()
-        _check(lib().lccrf_batch_get_splat_plan(self.h, int(k), C.byref(p)))
-        return p.as_dict()
-
-    def blur_plan(self, k):
-        """Which way the d + 1 blur passes of term k go in the two-label step for the lattices now in HBM (lccrf_blur_plan): dict(in_splat,
-        paired_table, paired_plain, alone_32bit, alone_compact, in_slice, nontemporal, first_table_pair)."""
-        p = BlurPlan()
-        _check(lib().lccrf_batch_get_blur_plan(self.h, int(k), C.byref(p)))
-        return p.as_dict()
-
     def fallback_frames(self):
         """Frames of the last run() that did not fit the one-launch kernel and were re-run on the two-kernel path."""
         n = C.c_int(0)
@@ -779,7 +729,7 @@ class BatchCRF:
 
     def pose_set_crf_counts(self, d_n_total):
         """lccrf_batch_pose_set_crf_counts: device int32[F] of CRF points + extra non-CRF edges per frame (None: off)."""
-        _check(lib().lccrf_batch_pose_set_crf_counts(self.h, C.c_void_p(int(d_n_total)) if d_n_total else None))
+        _check(lib().lccrf_batch_pose_set_crf_counts(self.h, _addr(d_n_total)))
 
     def map(self):
         out = np.empty((self.n_frames, self.maxN), np.int16)
@@ -821,11 +771,10 @@ class BatchCRF:
     def pose_optimization(self, d_Xw, d_kp, d_u_right, d_inv_sigma2, K4, bf, d_Tcw_in, d_Tcw_out, d_outlier, d_n_inliers,
                           d_n_initial, d_valid=None, stream=None):
         """lccrf_batch_pose_optimization: raw device addresses; consumes the labels of the last inference on the device."""
-        K = _f32(K4)
-        v = lambda p: C.c_void_p(int(p)) if p is not None else None
+        K, v = _f32(K4), _addr
         _check(lib().lccrf_batch_pose_optimization(self.h, v(d_Xw), v(d_kp), v(d_u_right), v(d_inv_sigma2), v(d_valid), _p(K, _f32p),
                                                    float(bf), v(d_Tcw_in), v(d_Tcw_out), v(d_outlier), v(d_n_inliers),
-                                                   v(d_n_initial), C.c_void_p(stream) if stream else None))
+                                                   v(d_n_initial), _addr(stream)))
 
     def last_timing(self):
         a, b = C.c_float(0), C.c_float(0)
