@@ -99,15 +99,21 @@ int  lccrf_trim_cache(void);
  *       (lccrf_batch_get_fallback_frames counts it).  Every other call, shape and model -- Potts terms normalised AFTER above all --
  *       takes exactly the route it takes with the option off.  Off by default: what the route saves for a learnt model is measured in
  *       notes/frame_general.md, not yet across deployments.
+ *   LCCRF_OPT_FUSED_BACKWARD   (default 0) value != 0: a backward call that asks for dL/dU and / or dL/dw alone (sections 1c and 2c,
+ *       and the calls of sections 1d - 1f, 2d and 2h when nothing else is asked for) on two-label frames of up to 2048 points with one
+ *       or two 2-D Potts terms normalised AFTER runs the replay and the sweep in ONE kernel launch (section 1j; csrc/fused_backward.hip).
+ *       The gradients and the Q left behind are bit for bit those of the option off; everything else takes the route it takes today.
  * lccrf_set_option applies to one handle (set it after lccrf_create: a handle taken from the cache starts from the defaults) and is
- * per handle only for LCCRF_OPT_VERTEX_ORDER and LCCRF_OPT_COPY_THREADS; lccrf_set_default_option applies LCCRF_OPT_SINGLE_WORKGROUP
- * or LCCRF_OPT_FRAME_GENERAL to every handle and batch created afterwards in this process.                                    */
+ * per handle (or batch) only for LCCRF_OPT_VERTEX_ORDER, LCCRF_OPT_COPY_THREADS, LCCRF_OPT_EVENT_TIMING and LCCRF_OPT_FUSED_BACKWARD;
+ * lccrf_set_default_option applies LCCRF_OPT_SINGLE_WORKGROUP or LCCRF_OPT_FRAME_GENERAL to every handle and batch created afterwards
+ * in this process.                                                                                                             */
 typedef enum lccrf_option {
     LCCRF_OPT_SINGLE_WORKGROUP = 1,
     LCCRF_OPT_VERTEX_ORDER     = 2,
     LCCRF_OPT_COPY_THREADS     = 3,
     LCCRF_OPT_EVENT_TIMING     = 4,
-    LCCRF_OPT_FRAME_GENERAL    = 5
+    LCCRF_OPT_FRAME_GENERAL    = 5,
+    LCCRF_OPT_FUSED_BACKWARD  = 6
 } lccrf_option;
 int  lccrf_set_option(lccrf_handle h, int option, int value);
 int  lccrf_set_default_option(int option, int value);
@@ -562,6 +568,40 @@ int  lccrf_get_convergence(lccrf_handle h, int *iterations, float *delta, int *c
 int  lccrf_run_converged(lccrf_handle h, int max_iterations, int criterion, float tol, int with_map, float relax);
 
 /* ======================================================================================
+ * 1j. The gradients of a tracker-sized frame in ONE launch -- LCCRF_OPT_FUSED_BACKWARD (off by default; per handle or batch).
+ *
+ * Section 1c's sweep is a launch per phase: about 150 launches of a few microseconds each for two 2-D terms and T = 5, which a frame
+ * of 2000 keypoints cannot fill.  With the option set, a backward call runs the replay of the forward AND the reverse sweep in one
+ * kernel launch, one 1024-lane workgroup per frame with the lattices' values in LDS (csrc/fused_backward.hip), when
+ *   - the call asks for dL/dU and / or dL/dw only: lccrf_inference_backward and lccrf_batch_inference_backward, and the calls of
+ *     sections 1d - 1f, 2d and 2h with neither feature gradients, nor d_grad_compat, nor d_grad_model, on a handle or batch without
+ *     a label-compatibility matrix;
+ *   - every term is a Potts term normalised AFTER the filter;
+ *   - the frames are ones the fused engine's plan takes: two labels, one or two 2-D terms, at most 2048 active points (the largest
+ *     n_points the host knows, else max_points), lattices inside one workgroup's LDS.  A batch decides once for all its frames, over
+ *     its largest frame and lattices: one frame that does not fit, and the whole batch takes section 1c's sweep.
+ * Everything else -- other label counts, dimensions and sizes, matrices, modes, feature and model gradients -- takes section 1c's
+ * sweep as with the option off.  n_iterations = 0 may take either route.
+ *   - Bit for bit: d_grad_unary (the zero rows beyond a frame's points included), d_grad_weights and the Q left behind are exactly
+ *     those of the option off -- every product and sum of sections 1c / 2c is formed in the same order, the weight gradient's
+ *     partials over the same 256-point blocks, reduced by the same walk and tree.  The option changes speed only.
+ *   - Memory: section 1c's (2c's) area, nothing more; the per-term arrays of it are not touched on this route.
+ *   - Argument checks, LCCRF_E_STATE, LCCRF_E_NOMEM and "a rejected call leaves the handle as it was" are section 1c's: the route is
+ *     chosen behind them.  The lattices are built in HBM as section 1c needs them (a pending one-launch run is settled, a
+ *     locality-mode build made plain).
+ * lccrf_get_backward_route / lccrf_batch_get_backward_route (section 2c) report which route the last successful backward call of any
+ * section took; NULL arguments return LCCRF_E_INVALID and write nothing.  Added WITHOUT a step of LCCRF_ABI_VERSION: probe by symbol.
+ * Not covered (notes/fused_backward.md): matrices and normalisation modes, feature gradients, d_grad_model, frames of 2049 points
+ * and more, the half-CU shapes; the route is not the default.
+ * ==================================================================================== */
+typedef enum lccrf_backward_route {
+    LCCRF_BACKWARD_NONE   = 0,   /* no backward call yet */
+    LCCRF_BACKWARD_STREAM = 1,   /* section 1c's sweep on the streaming engine */
+    LCCRF_BACKWARD_FUSED  = 2    /* one launch */
+} lccrf_backward_route;
+int  lccrf_get_backward_route(lccrf_handle h, int *route);
+
+/* ======================================================================================
  * 2. Batch API -- many independent frames in flight on one GPU.
  *    Every frame is one CRF of the object API; frames never interact.  Inputs may be
  *    handed over as host buffers (uploaded) or bound as DEVICE pointers (zero copy), so
@@ -771,6 +811,8 @@ int  lccrf_batch_set_unary_device(lccrf_batch_handle b, const float *d_unary);
  *     frame with the bits of a handle's section 1e and 1g gradients -- are lccrf_batch_inference_backward_all's (section 2h).       */
 int  lccrf_batch_inference_backward(lccrf_batch_handle b, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
                                     float *d_grad_weights, void *stream);
+/* Section 1j's report for a batch: the route of its last successful backward call (an lccrf_backward_route). */
+int  lccrf_batch_get_backward_route(lccrf_batch_handle b, int *route);
 
 /* ======================================================================================
  * 2d. Section 1d for every frame of a batch at once, in the launches section 1d takes for one frame.  d_grad_features: host array of

@@ -441,6 +441,14 @@ public:
     // lccrf_set_option (include/lccrf.h), e.g. setOption(LCCRF_OPT_SINGLE_WORKGROUP, 1) for a tracker on a shared GPU.
     // setOption(LCCRF_OPT_FRAME_GENERAL, 1): a learnt model (setCompatibility / setNormalization) keeps the one-launch route of a fresh frame.
     void setOption(int option, int value) { lccrf_check(lccrf_set_option(h_, option, value), "lccrf_set_option"); }
+    // lccrf_get_backward_route (include/lccrf.h section 1j): the route of the last successful backward call on this handle -- 0 none yet,
+    // 1 the streaming sweep, 2 one launch (setOption(LCCRF_OPT_FUSED_BACKWARD, 1)).  Report only.
+    int backwardRoute() const
+    {
+        int r = 0;
+        lccrf_check(lccrf_get_backward_route(h_, &r), "lccrf_get_backward_route");
+        return r;
+    }
     // see the header comment: true = every inference call ends with Q in the buffer DenseCRF::getProbability() returns
     void syncThroughBase(bool on) { base_sync_ = on; }
     bool syncsThroughBase() const { return base_sync_; }

@@ -291,6 +291,14 @@ public:
     }
     // lccrf_set_option (include/lccrf.h); setOption(LCCRF_OPT_FRAME_GENERAL, 1) keeps a learnt model on the one-launch route of a fresh frame.
     void setOption(int option, int value) { lccrf_check(lccrf_set_option(h_, option, value), "lccrf_set_option"); }
+    // lccrf_get_backward_route (include/lccrf.h section 1j): the route of the last successful backward call on this handle -- 0 none yet,
+    // 1 the streaming sweep, 2 one launch (setOption(LCCRF_OPT_FUSED_BACKWARD, 1)).  Report only.
+    int backwardRoute() const
+    {
+        int r = 0;
+        lccrf_check(lccrf_get_backward_route(h_, &r), "lccrf_get_backward_route");
+        return r;
+    }
     void synchronize() const { sync(); }
     void *stream() const
     {

@@ -26,6 +26,8 @@ MAX_KERNELS = 8
 OPT_SINGLE_WORKGROUP = 1        # lccrf_option (include/lccrf.h)
 OPT_VERTEX_ORDER = 2
 OPT_FRAME_GENERAL = 5           # a learnt model (matrices, normalisation modes) may take the one-launch route of a fresh frame
+OPT_FUSED_BACKWARD = 6          # gradients of tracker-sized two-label frames in one launch (include/lccrf.h section 1j)
+BACKWARD_NONE, BACKWARD_STREAM, BACKWARD_FUSED = 0, 1, 2   # lccrf_backward_route
 IMAGE_NONE, IMAGE_U8, IMAGE_F32 = 0, 1, 2   # lccrf_add_image_kernel's image formats
 NORMALIZE_AFTER, NORMALIZE_BEFORE, NORMALIZE_SYMMETRIC, NORMALIZE_NONE = 0, 1, 2, 3   # lccrf_normalization (section 1g)
 STOP_DELTA, STOP_LABELS = 1, 2   # lccrf_inference_converged's criterion bits (section 1h)
@@ -146,6 +148,9 @@ def lib():
     L.lccrf_set_pairwise_weight.argtypes = [vp, C.c_int, C.c_float]
     L.lccrf_inference_backward.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp]
     L.lccrf_inference_backward_features.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, C.POINTER(vp)]
+    for name in ("lccrf_get_backward_route", "lccrf_batch_get_backward_route"):   # (section 1j: probe by symbol -- a library from before
+        if hasattr(L, name):                                                      #  the route, named through LCCRF_LIB, has neither)
+            getattr(L, name).argtypes = [vp, C.POINTER(C.c_int)]
     L.lccrf_set_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p]
     L.lccrf_get_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p, C.POINTER(C.c_int)]
     L.lccrf_inference_backward_compat.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, vp]
@@ -514,6 +519,13 @@ class DenseCRFHIP(_Handle):
         _check(lib().lccrf_get_engine(self.h, C.byref(e), C.byref(s)))
         return e.value, s.value
 
+    def backward_route(self):
+        """the route of the last successful backward call: BACKWARD_NONE, BACKWARD_STREAM or BACKWARD_FUSED (OPT_FUSED_BACKWARD).
+        Report only (include/lccrf.h section 1j)."""
+        r = C.c_int(0)
+        _check(lib().lccrf_get_backward_route(self.h, C.byref(r)))
+        return r.value
+
     def unary(self):
         out = np.empty((self.N, self.L), np.float32)
         _check(lib().lccrf_get_unary(self.h, _p(out, _f32p)))
@@ -573,6 +585,7 @@ class BatchCRF(_Handle):
     OPT_COPY_THREADS = 3
     OPT_EVENT_TIMING = 4
     OPT_FRAME_GENERAL = 5
+    OPT_FUSED_BACKWARD = 6
 
     def set_inputs_host_async(self, n_points, features, unary=None, label=None, conf=None, pinned=False):
         """lccrf_batch_set_inputs_host_async: the arrays are staged and uploaded without a host wait.  The arrays must already be
@@ -708,6 +721,12 @@ class BatchCRF(_Handle):
         e = C.c_int(0)
         _check(lib().lccrf_batch_get_engine(self.h, C.byref(e)))
         return e.value
+
+    def backward_route(self):
+        """the route of the last successful backward call: BACKWARD_NONE, BACKWARD_STREAM or BACKWARD_FUSED (OPT_FUSED_BACKWARD)"""
+        r = C.c_int(0)
+        _check(lib().lccrf_batch_get_backward_route(self.h, C.byref(r)))
+        return r.value
 
     def fused_shape(self):
         """(lanes per frame, frames per CU) of the last fused-engine launch; (0, 0) if there was none."""

@@ -221,10 +221,15 @@ class MeanFieldCRF(_HandleCRF):
 
     features: list of [N, d_k] arrays (already divided by the kernel's standard deviation, as lccrf_add_pairwise takes
     them); weights: their initial weights; normalization: None (the reference's form), or one of the package's NORMALIZE_* modes
-    for every term, or one per term (include/lccrf.h section 1g).  forward(unary [N, L]) -> Q [N, L]."""
+    for every term, or one per term (include/lccrf.h section 1g); fused_backward: sets OPT_FUSED_BACKWARD on the handle -- the
+    gradients of a frame the one-launch backward takes are then formed in one launch, the same bits (section 1j).
+    forward(unary [N, L]) -> Q [N, L]."""
 
-    def __init__(self, n_points, n_labels, features, weights, n_iterations=5, relax=1.0, device=0, normalization=None):
+    def __init__(self, n_points, n_labels, features, weights, n_iterations=5, relax=1.0, device=0, normalization=None,
+                 fused_backward=False):
         super().__init__(n_points, n_labels, features, weights, n_iterations, relax, device, normalization)
+        if fused_backward:
+            self.crf.set_option(_pkg.OPT_FUSED_BACKWARD, 1)
 
     def forward(self, unary):
         return mean_field(self.crf, unary, self.weights, self.n_iterations, self.relax)
@@ -344,10 +349,13 @@ class BatchMeanFieldCRF(_BatchCRF):
     nn.Parameter.  The features are uploaded and the lattices built once, here; forward() only sets weights and unaries.
 
     n_points: [F] points per frame; features: list of [F, max_points, d_k] arrays (already divided by the kernel's standard
-    deviation); weights: their initial weights.  forward(unary [F, max_points, L]) -> Q [F, max_points, L]."""
+    deviation); weights: their initial weights; fused_backward: sets OPT_FUSED_BACKWARD on the batch (include/lccrf.h section 1j: the
+    same gradients, in one launch where the frames fit).  forward(unary [F, max_points, L]) -> Q [F, max_points, L]."""
 
-    def __init__(self, n_points, features, weights, n_iterations=5, relax=1.0, device=0, n_labels=2):
+    def __init__(self, n_points, features, weights, n_iterations=5, relax=1.0, device=0, n_labels=2, fused_backward=False):
         super().__init__(n_points, features, weights, n_iterations, relax, device, n_labels)
+        if fused_backward:
+            self.batch.set_option(_pkg.OPT_FUSED_BACKWARD, 1)
 
     def forward(self, unary):
         return mean_field_batch(self.batch, unary, self.weights, self.n_iterations, self.relax)

@@ -90,6 +90,23 @@ int lccrf_inference_backward(lccrf_handle h, int n_iterations, float relax, cons
 }
 
 // --------------------------------------------------------------------------------------
+// section 1j: which route the last successful backward call took (report only: no device is selected, nothing is settled)
+
+int lccrf_get_backward_route(lccrf_handle h, int *route)
+{
+    if (!h || !route) return fail(LCCRF_E_INVALID, "handle / route is NULL");
+    *route = h->eng.backward_route;
+    return LCCRF_OK;
+}
+
+int lccrf_batch_get_backward_route(lccrf_batch_handle b, int *route)
+{
+    if (!b || !route) return fail(LCCRF_E_INVALID, "handle / route is NULL");
+    *route = b->eng.backward_route;
+    return LCCRF_OK;
+}
+
+// --------------------------------------------------------------------------------------
 // section 1d: ... and with respect to the features of the pairwise terms
 
 int lccrf_inference_backward_features(lccrf_handle h, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,

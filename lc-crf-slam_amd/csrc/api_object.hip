@@ -35,6 +35,7 @@ int lccrf::apply_option(Engine &e, int option, int value)
     switch (option) {
     case LCCRF_OPT_SINGLE_WORKGROUP: e.opt_single_wg = value != 0; return LCCRF_OK;
     case LCCRF_OPT_FRAME_GENERAL: e.opt_frame_general = value != 0; return LCCRF_OK;    // (takes effect with the next inference / run)
+    case LCCRF_OPT_FUSED_BACKWARD: e.opt_fused_backward = value != 0; return LCCRF_OK;  // (takes effect with the next backward call)
     case LCCRF_OPT_VERTEX_ORDER:                                                         // (takes effect with the next build)
         if (value < 0 || value > 2) return fail(LCCRF_E_INVALID, "LCCRF_OPT_VERTEX_ORDER takes 0 (automatic), 1 (on) or 2 (off)");
         e.opt_vertex_order = value;
@@ -126,6 +127,8 @@ int lccrf_create(lccrf_handle *out, int device_id, int n_points, int n_labels)
     h->N = n_points;
     h->eng.opt_single_wg = default_single_wg();           // (a recycled handle does not inherit its last user's options)
     h->eng.opt_frame_general = default_frame_general();
+    h->eng.opt_fused_backward = false;
+    h->eng.backward_route = LCCRF_BACKWARD_NONE;
     h->eng.opt_vertex_order = 0;
     h->eng.activeN = n_points;
     h->eng.crf.map = h->map_pin;

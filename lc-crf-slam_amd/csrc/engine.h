@@ -397,6 +397,13 @@ size_t backward_layout(const BackwardRequest &rq, const CrfDev &c, const KernelD
 // ar.gW / ar.gC where the caller left one out -- are summed over the frames in ascending order, one k_sum_frames launch each.
 void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int rows, const BackwardRequest &rq,
                            const BackwardArea &ar, const float *const *compat, hipStream_t s, const float *const *pre = nullptr);
+// The replay AND the sweep of a request for dL/dU and / or dL/dw alone in ONE launch, a 1024-lane workgroup per frame
+// (csrc/fused_backward.hip; include/lccrf.h section 1j): two labels, Potts terms normalised AFTER on lattices in HBM that fit the fused
+// plan, frames of up to 2048 active points.  Reads rq.grad_prob itself (no copy into ar.G beforehand), keeps Q_0 .. Q_{T-1} in
+// ar.hist, leaves Q_T in c.Q and writes what launch_backward_sweep would have, bit for bit.  Returns fused_report() of the shape it
+// launched, or 0 with nothing launched: the frames are not ones the plan takes.
+int launch_fused_backward(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, int rows, const BackwardRequest &rq,
+                          const BackwardArea &ar, hipStream_t s);
 
 // ---- one run, its terms, and what a converged one reports: what the launch requests below are made of ---------------------------
 // One run: a fixed count of n_iter iterations, or -- until_converged -- at most n_iter under (criterion, tol) (include/lccrf.h

@@ -403,7 +403,10 @@ __device__ __forceinline__ void chain_pads(unsigned char *smem, const ChainLane 
 // KMASK: the kernels that take part (bit k) -- all of them in the loop; the frame kernel's two-workgroup form normalises
 // its kernels one at a time (frame_engine.hip).
 // REV: see the blur passes.  GEN: phase P takes its input through filter_input (gt; see GeneralTerms).
-template <int PPT, int K, int CH, bool WITH_P = true, int NT = kNT, int KMASK = (1 << K) - 1, bool REV = false, bool GEN = false>
+// TRANSPOSE (fused_backward.hip): the blur passes along the axes in reverse order (2, 1, 0), each with the forward's pass arithmetic --
+// the transposed filter of include/lccrf.h section 1c.  Every other instantiation takes false and compiles as it did.
+template <int PPT, int K, int CH, bool WITH_P = true, int NT = kNT, int KMASK = (1 << K) - 1, bool REV = false, bool GEN = false,
+          bool TRANSPOSE = false>
 __device__ __forceinline__ void splat_blur(unsigned char *smem, const FusedLayout &lay, const int (&V)[K], int N, int tid,
                                            const PointRegs<PPT, K> &pr, const ChainLane &cl, Instr &ins,
                                            const GeneralTerms<PPT, K> *gt = nullptr)
@@ -489,7 +492,7 @@ __device__ __forceinline__ void splat_blur(unsigned char *smem, const FusedLayou
             if (!on(k)) continue;
             const float2 *src = reinterpret_cast<const float2 *>(smem + lay.val[k][j & 1]);
             float2 *dst = reinterpret_cast<float2 *>(smem + lay.val[k][(j & 1) ^ 1]);
-            const unsigned *nbr = reinterpret_cast<const unsigned *>(smem + lay.nbr[k]) + j * V[k];
+            const unsigned *nbr = reinterpret_cast<const unsigned *>(smem + lay.nbr[k]) + (TRANSPOSE ? D1 - 1 - j : j) * V[k];
             // REV (k_fused, 1024 lanes, two kernels): the small lattice (kernel 0, ~120 vertices) goes to the LAST lanes -- the first
             // ones have a second vertex of the large lattice (~1160), and a pass is as long as its busiest lane (+0.6 % C2, +1 % C4;
             // with 512 lanes every lane has two or three vertices anyway and the reversal lost 5 % on C1; in k_frame the extra

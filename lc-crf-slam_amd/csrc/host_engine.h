@@ -225,6 +225,8 @@ struct Engine {
     // demand and freed with the handle's use (recycle) -- a parked handle does not keep it -- or with the batch
     unsigned char *bwd_area = nullptr;
     size_t bwd_area_bytes = 0;
+    bool opt_fused_backward = false;   // LCCRF_OPT_FUSED_BACKWARD: dL/dU and dL/dw of frames the fused plan takes run in one launch (fused_backward.hip)
+    int backward_route = 0;            // report only (lccrf_get_backward_route): LCCRF_BACKWARD_* of the last successful backward call
 
     // ---- compatibility matrices ----
     // sections 1e (a handle) and 2g (a batch: one matrix per term, shared by every frame): the terms' label-compatibility matrices.

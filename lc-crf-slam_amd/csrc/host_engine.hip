@@ -170,6 +170,17 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
     int rc = start();                                 // (kCallerOrder: a handle's frames in locality mode are re-built the plain way once)
     if (!rc) rc = make_ready(kSized | kStepViews);
     if (rc) return rc;
+    // LCCRF_OPT_FUSED_BACKWARD (include/lccrf.h section 1j): dL/dU and / or dL/dw of Potts terms normalised AFTER, on frames the fused
+    // plan takes -- the replay and the sweep in one launch, the same bits (fused_backward.hip).  Decided for the whole batch, over its
+    // largest frame and lattices; behind every check and the area, so a rejected call leaves the handle as it was either way.
+    bool dU_dw_only = !rq.compat_form && !rq.grad_compat && !rq.grad_model;
+    for (int k = 0; k < K && rq.grad_features; ++k) dU_dw_only &= rq.grad_features[k] == nullptr;
+    if (opt_fused_backward && dU_dw_only && count && !n_compat && !n_modes && !perm_on &&
+        launch_fused_backward(crf, kdevs.data(), maxV.data(), maxRow.data(), rows, rq, ar, stream)) {
+        HIP_TRY(hipGetLastError());
+        backward_route = LCCRF_BACKWARD_FUSED;
+        return LCCRF_OK;
+    }
     for (int t = 0; t < T; ++t) {
         if (count) HIP_TRY(hipMemcpyAsync(ar.hist + (size_t)t * slice, crf.Q, count * sizeof(float), hipMemcpyDeviceToDevice, stream));
         if ((rc = step(rq.relax))) return rc;
@@ -181,6 +192,7 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
     if (!count) {                                     // nothing to differentiate: dL/dw = 0
         if (grad_weights && K) HIP_TRY(hipMemsetAsync(grad_weights, 0, (size_t)F * K * sizeof(float), stream));
         if (rq.grad_model && K) HIP_TRY(hipMemsetAsync(rq.grad_model, 0, (size_t)K * (1 + L * L) * sizeof(float), stream));
+        backward_route = LCCRF_BACKWARD_STREAM;
         return LCCRF_OK;
     }
     for (int k = 0; k < K && rq.grad_features; ++k) {
@@ -193,6 +205,7 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
     HIP_TRY(hipMemcpyAsync(ar.G, rq.grad_prob, count * sizeof(float), hipMemcpyDeviceToDevice, stream));
     launch_backward_sweep(crf, step_kdevs(), maxV.data(), rows, rq, ar, compat_arg(), stream, pre_arg());
     HIP_TRY(hipGetLastError());
+    backward_route = LCCRF_BACKWARD_STREAM;
     return LCCRF_OK;
 }
 
