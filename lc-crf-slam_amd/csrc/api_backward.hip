@@ -1,7 +1,7 @@
 // api_backward.hip -- gradients of mean-field inference: sections 1c - 1f (a handle) and 2c, 2d, 2h (a batch) of include/lccrf.h.
 //
 // One path behind every entry point (backward_call); the replay and the sweep themselves are Engine::backward (host_engine.hip) and
-// meanfield_backward.hip.
+// meanfield_backward.hip; the route getters of section 1j are in api_model.hip.
 #include "api_common.h"
 
 #include <cmath>
@@ -70,8 +70,8 @@ static BackwardTarget backward_target(lccrf_batch *b, void *stream)
 // gradients -- are section 2h's, lccrf_batch_inference_backward_all below.
 static int batch_is_plain(const lccrf_batch *b)
 {
-    if (b->eng.n_compat) return fail(LCCRF_E_STATE, "batch gradients are not available while a term has a label-compatibility matrix: lccrf_batch_inference_backward_all");
-    if (b->eng.n_modes) return fail(LCCRF_E_STATE, "batch gradients are not available while a term is not normalised AFTER the filter: lccrf_batch_inference_backward_all");
+    if (b->eng.model.n_compat) return fail(LCCRF_E_STATE, "batch gradients are not available while a term has a label-compatibility matrix: lccrf_batch_inference_backward_all");
+    if (b->eng.model.n_modes) return fail(LCCRF_E_STATE, "batch gradients are not available while a term is not normalised AFTER the filter: lccrf_batch_inference_backward_all");
     return LCCRF_OK;
 }
 
@@ -85,25 +85,8 @@ int lccrf_inference_backward(lccrf_handle h, int n_iterations, float relax, cons
 {
     CHECK_H(h);
     BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
-    rq.compat_form = h->eng.n_compat > 0;                 // (section 1e: the gradients of the forward with the matrices)
+    rq.compat_form = h->eng.model.n_compat > 0;                 // (section 1e: the gradients of the forward with the matrices)
     return backward_call(backward_target(h), rq, kGradUnaryRequired);
-}
-
-// --------------------------------------------------------------------------------------
-// section 1j: which route the last successful backward call took (report only: no device is selected, nothing is settled)
-
-int lccrf_get_backward_route(lccrf_handle h, int *route)
-{
-    if (!h || !route) return fail(LCCRF_E_INVALID, "handle / route is NULL");
-    *route = h->eng.backward_route;
-    return LCCRF_OK;
-}
-
-int lccrf_batch_get_backward_route(lccrf_batch_handle b, int *route)
-{
-    if (!b || !route) return fail(LCCRF_E_INVALID, "handle / route is NULL");
-    *route = b->eng.backward_route;
-    return LCCRF_OK;
 }
 
 // --------------------------------------------------------------------------------------
@@ -113,8 +96,8 @@ int lccrf_inference_backward_features(lccrf_handle h, int n_iterations, float re
                                       float *d_grad_weights, float *const *d_grad_features)
 {
     CHECK_H(h);
-    if (h->eng.n_compat) return fail(LCCRF_E_STATE, "feature gradients are not available while a term has a label-compatibility matrix");
-    if (h->eng.n_modes) return fail(LCCRF_E_STATE, "feature gradients are not available while a term is not normalised AFTER the filter");
+    if (h->eng.model.n_compat) return fail(LCCRF_E_STATE, "feature gradients are not available while a term has a label-compatibility matrix");
+    if (h->eng.model.n_modes) return fail(LCCRF_E_STATE, "feature gradients are not available while a term is not normalised AFTER the filter");
     BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
     rq.grad_features = d_grad_features;
     return backward_call(backward_target(h), rq, kGradUnaryOptional);
@@ -141,12 +124,12 @@ int lccrf_inference_backward_all(lccrf_handle h, int n_iterations, float relax, 
                                  float *d_grad_weights, float *const *d_grad_features, float *d_grad_compat)
 {
     CHECK_H(h);
-    if (d_grad_features && h->eng.n_modes)                // (section 1g: the norm's factors are not differentiated in the features)
+    if (d_grad_features && h->eng.model.n_modes)                // (section 1g: the norm's factors are not differentiated in the features)
         return fail(LCCRF_E_STATE, "feature gradients are not available while a term is not normalised AFTER the filter");
     BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
     rq.grad_features = d_grad_features;
     rq.grad_compat = d_grad_compat;
-    rq.compat_form = h->eng.n_compat > 0 || d_grad_compat;
+    rq.compat_form = h->eng.model.n_compat > 0 || d_grad_compat;
     return backward_call(backward_target(h), rq, kGradUnaryOptional);
 }
 
@@ -183,13 +166,13 @@ int lccrf_batch_inference_backward_all(lccrf_batch_handle b, int n_iterations, f
                                        void *stream)
 {
     CHECK_H(b);
-    if (d_grad_features && b->eng.n_modes)                // (section 1g: the norm's factors are not differentiated in the features)
+    if (d_grad_features && b->eng.model.n_modes)                // (section 1g: the norm's factors are not differentiated in the features)
         return fail(LCCRF_E_STATE, "feature gradients are not available while a term is not normalised AFTER the filter");
     BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
     rq.grad_features = d_grad_features;
     rq.grad_compat = d_grad_compat;
     rq.grad_model = d_grad_model;
-    rq.compat_form = b->eng.n_compat > 0 || d_grad_compat || d_grad_model;   // (the sums hold dL/dmu: section 1e's form)
+    rq.compat_form = b->eng.model.n_compat > 0 || d_grad_compat || d_grad_model;   // (the sums hold dL/dmu: section 1e's form)
     return backward_call(backward_target(b, stream), rq, kGradUnaryOptional);
 }
 

@@ -1,5 +1,5 @@
-// api_batch.hip -- the batch API of include/lccrf.h: section 2 and the batch calls of section 5; its gradients (2c, 2d) are in
-// api_backward.hip.
+// api_batch.hip -- the batch API of include/lccrf.h: section 2 and the batch calls of section 5; its gradients (2c, 2d, 2h) are in
+// api_backward.hip, its weights, matrices and modes (2c, 2g) and its plans in api_model.hip.
 //
 // Argument checks, the three input paths with their pinned staging, the timed calls and the read-backs of one batch; the state
 // machine behind it is the Engine (host_engine.h).
@@ -153,8 +153,7 @@ int lccrf_batch_create(lccrf_batch_handle *out, int device_id, const lccrf_batch
     b->desc = *desc;
     b->eng.allow_perm = true;
     b->eng.batch_owned = true;
-    b->eng.opt_single_wg = default_single_wg();
-    b->eng.opt_frame_general = default_frame_general();
+    b->eng.opt = Engine::Options::fresh();
     rc = b->eng.init(device_id, desc->max_frames, desc->max_points, desc->n_labels);
     for (int k = 0; k < desc->n_kernels && !rc; ++k) rc = b->eng.add_kernel(desc->feat_dims[k], desc->weights[k], true, false);
     if (!rc && hipStreamSynchronize(b->eng.stream) != hipSuccess)      // every allocation is zeroed before the handle is handed out
@@ -188,7 +187,7 @@ int lccrf_batch_set_option(lccrf_batch_handle b, int option, int value)
         return LCCRF_OK;
     }
     if (option == LCCRF_OPT_EVENT_TIMING) {
-        b->eng.event_timing = value != 0;
+        b->eng.opt.event_timing = value != 0;
         if (!value) b->eng.timed_build = b->eng.timed_inf = false;
         return LCCRF_OK;
     }
@@ -544,7 +543,7 @@ int lccrf_batch_get_fallback_frames(lccrf_batch_handle b, int *n_frames)
     CHECK_H(b);
     if (!n_frames) return fail(LCCRF_E_INVALID, "n_frames is NULL");
     { int rl = b->eng.resolve_late(); if (rl) return rl; }
-    *n_frames = b->eng.fallback_frames;
+    *n_frames = b->eng.report.fallback_frames;
     return LCCRF_OK;
 }
 
@@ -643,23 +642,15 @@ int lccrf_batch_get_engine(lccrf_batch_handle b, int *engine_in_use)
     CHECK_H(b);
     if (!engine_in_use) return fail(LCCRF_E_INVALID, "engine_in_use is NULL");
     { int rl = b->eng.resolve_late(); if (rl) return rl; }   // a one-launch run may have fallen back
-    Engine &e = b->eng;
-    if (e.built && e.engine_used != 3) {                     // lattices in HBM: what an inference on them runs (or ran) on
-        int rc = e.make_ready(Engine::kSized);
-        if (rc) return rc;
-        e.engine_used = e.sized_engine;
-    }
-    if (e.conv_engine) e.engine_used = e.conv_engine;        // the last inference was a converged one: what it ran on (section 2e)
-    *engine_in_use = e.engine_used;
-    return LCCRF_OK;
+    return b->eng.engine_in_use(engine_in_use);
 }
 
 int lccrf_batch_get_fused_shape(lccrf_batch_handle b, int *lanes_per_frame, int *frames_per_cu)
 {
     CHECK_H(b);
     if (!lanes_per_frame || !frames_per_cu) return fail(LCCRF_E_INVALID, "output pointer is NULL");
-    *lanes_per_frame = b->eng.fused_shape & 0xffff;
-    *frames_per_cu = b->eng.fused_shape >> 16;
+    *lanes_per_frame = b->eng.report.fused_shape & 0xffff;
+    *frames_per_cu = b->eng.report.fused_shape >> 16;
     return LCCRF_OK;
 }
 
@@ -673,34 +664,6 @@ int lccrf_batch_get_locality_mode(lccrf_batch_handle b, int *internal_point_orde
     }
     if (internal_point_order) *internal_point_order = e.perm_on ? 1 : 0;
     if (sorted_build) *sorted_build = (e.perm_on && e.vorder_on && !e.vorder_broken) ? 1 : 0;
-    return LCCRF_OK;
-}
-
-int lccrf_batch_get_splat_plan(lccrf_batch_handle b, int kernel, lccrf_splat_plan *out)
-{
-    CHECK_H(b);
-    CHECK_K(b, kernel);
-    if (!out) return fail(LCCRF_E_INVALID, "out is NULL");
-    Engine &e = b->eng;
-    if (e.built) {                                      // (the plan is made from what the build measured: kSized)
-        int rc = e.make_ready(Engine::kSized);
-        if (rc) return rc;
-    }
-    report_splat_plan(e.kernels[kernel].dev, e.crf.F, out);
-    return LCCRF_OK;
-}
-
-int lccrf_batch_get_blur_plan(lccrf_batch_handle b, int kernel, lccrf_blur_plan *out)
-{
-    CHECK_H(b);
-    CHECK_K(b, kernel);
-    if (!out) return fail(LCCRF_E_INVALID, "out is NULL");
-    Engine &e = b->eng;
-    if (e.built) {                                      // (the plan is made from what the build measured: kSized)
-        int rc = e.make_ready(Engine::kSized);
-        if (rc) return rc;
-    }
-    *out = blur_plan(e.kernels[kernel].dev, e.crf.F, e.kernels[kernel].maxV).counts;     // (what launch_step_stream is given)
     return LCCRF_OK;
 }
 
@@ -764,19 +727,7 @@ int lccrf_batch_time_blur_pass(lccrf_batch_handle b, int kernel, int reps, float
     return LCCRF_OK;
 }
 
-// --------------------------------------------------------------------------------------
-// section 2c: the batch's weights and unaries (the gradients of its inference are in api_backward.hip)
-
-int lccrf_batch_set_pairwise_weight(lccrf_batch_handle b, int kernel, float w)
-{
-    CHECK_H(b);
-    CHECK_K(b, kernel);
-    Engine &e = b->eng;
-    { int rl = e.resolve_late(); if (rl) return rl; }   // (a pending one-launch run may still re-run frames with the old weight)
-    e.set_weight(kernel, w);
-    return LCCRF_OK;
-}
-
+// section 2c: the batch's unaries (its weights are in api_model.hip, the gradients of its inference in api_backward.hip)
 int lccrf_batch_set_unary_device(lccrf_batch_handle b, const float *d_unary)
 {
     CHECK_H(b);
@@ -787,64 +738,6 @@ int lccrf_batch_set_unary_device(lccrf_batch_handle b, const float *d_unary)
     { int rl = e.resolve_late(); if (rl) return rl; }
     if (n) HIP_TRY(hipMemcpyAsync(e.unary_own, d_unary, n * sizeof(float), hipMemcpyDefault, e.stream));
     e.bind_unary(e.unary_own);                            // (drops label-derived and permuted unary state; lattices and records stay)
-    return LCCRF_OK;
-}
-
-// --------------------------------------------------------------------------------------
-// section 2g: the batch's label-compatibility matrices and normalisation modes -- sections 1e and 1g's setters, one matrix and one
-// mode per term for every frame.  Engine::set_compat / set_norm_mode touch no lattice, norm or prepared launch record.  What can be
-// checked without the batch -- a mode outside 0 .. 3, a kernel index no batch can have, a NULL output -- is checked before it is
-// looked at, so those answers need no device.
-#define CHECK_K_ANY(k)                                                                                      \
-    do {                                                                                                    \
-        if ((k) < 0 || (k) >= LCCRF_MAX_KERNELS) return fail(LCCRF_E_INVALID, "kernel index %d out of range", (k)); \
-    } while (0)
-
-int lccrf_batch_set_pairwise_compatibility(lccrf_batch_handle b, int kernel, const float *compat)
-{
-    CHECK_K_ANY(kernel);
-    CHECK_H(b);
-    CHECK_K(b, kernel);
-    Engine &e = b->eng;
-    for (int i = 0; compat && i < e.L * e.L; ++i)
-        if (!std::isfinite(compat[i])) return fail(LCCRF_E_INVALID, "compat[%d][%d] is not finite", i / e.L, i % e.L);
-    { int rl = e.resolve_late(); if (rl) return rl; }   // (a pending one-launch run may still re-run frames: as the Potts model it was asked with)
-    return e.set_compat(kernel, compat);
-}
-
-int lccrf_batch_get_pairwise_compatibility(lccrf_batch_handle b, int kernel, float *compat_out, int *is_set)
-{
-    CHECK_K_ANY(kernel);
-    CHECK_H(b);
-    CHECK_K(b, kernel);
-    const Engine &e = b->eng;
-    const bool set = e.compat_ptr[kernel] != nullptr;
-    if (is_set) *is_set = set ? 1 : 0;
-    for (int i = 0; compat_out && i < e.L * e.L; ++i)     // (a Potts term reads as the identity it is)
-        compat_out[i] = set ? e.compat_host[(size_t)kernel * e.L * e.L + i] : (i / e.L == i % e.L ? 1.0f : 0.0f);
-    return LCCRF_OK;
-}
-
-int lccrf_batch_set_pairwise_normalization(lccrf_batch_handle b, int kernel, int mode)
-{
-    if (mode < LCCRF_NORMALIZE_AFTER || mode > LCCRF_NORMALIZE_NONE)
-        return fail(LCCRF_E_INVALID, "normalization mode %d is none of LCCRF_NORMALIZE_AFTER / _BEFORE / _SYMMETRIC / _NONE", mode);
-    CHECK_K_ANY(kernel);
-    CHECK_H(b);
-    CHECK_K(b, kernel);
-    Engine &e = b->eng;
-    { int rl = e.resolve_late(); if (rl) return rl; }   // (a pending one-launch run may still re-run frames: with the modes it was asked with)
-    e.set_norm_mode(kernel, mode);
-    return LCCRF_OK;
-}
-
-int lccrf_batch_get_pairwise_normalization(lccrf_batch_handle b, int kernel, int *mode)
-{
-    if (!mode) return fail(LCCRF_E_INVALID, "mode is NULL");
-    CHECK_K_ANY(kernel);
-    CHECK_H(b);
-    CHECK_K(b, kernel);
-    *mode = b->eng.norm_mode[kernel];
     return LCCRF_OK;
 }
 

@@ -67,11 +67,15 @@ struct lccrf_batch {
             return fail(LCCRF_E_INVALID, "kernel index %d out of range", (k));             \
     } while (0)
 
+// ... and the same of an index no handle or batch can have: checked before the handle is looked at, so the answer needs no device
+#define CHECK_K_ANY(k)                                                                                      \
+    do {                                                                                                    \
+        if ((k) < 0 || (k) >= LCCRF_MAX_KERNELS) return fail(LCCRF_E_INVALID, "kernel index %d out of range", (k)); \
+    } while (0)
+
 namespace lccrf {
 
 int use_device(int device_id);                                  // api_tools.hip
-bool default_single_wg();                                       // LCCRF_OPT_SINGLE_WORKGROUP's process-wide default (lccrf_set_default_option)
-bool default_frame_general();                                   // LCCRF_OPT_FRAME_GENERAL's
 void trim_pose_stages();                                        // frees lccrf_pose_optimization's staging areas (lccrf_trim_cache)
 void trim_unary_stage();                                        // unary_builder.hip: frees lccrf_unary_build's staging (lccrf_trim_cache)
 void trim_bf_stage();                                           // bf_match.hip: frees lccrf_bf_match's staging (lccrf_trim_cache)
@@ -115,13 +119,13 @@ int timed_batch_call(Engine &e, void *stream, hipEvent_t begin, hipEvent_t end, 
     StreamScope scope(e, stream);
     int rc = scope.enter();
     if (rc) return rc;
-    if (e.event_timing) HIP_TRY(hipEventRecord(begin, e.stream));
+    if (e.opt.event_timing) HIP_TRY(hipEventRecord(begin, e.stream));
     rc = body();
-    if (!rc && e.event_timing) {
+    if (!rc && e.opt.event_timing) {
         hipError_t er = hipEventRecord(end, e.stream);
         if (er != hipSuccess) rc = fail(LCCRF_E_HIP, "hipEventRecord: %s", hipGetErrorString(er));
     }
-    timed = !rc && e.event_timing;
+    timed = !rc && e.opt.event_timing;
     return rc;
 }
 

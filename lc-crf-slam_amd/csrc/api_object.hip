@@ -1,5 +1,5 @@
-// api_object.hip -- the object API of include/lccrf.h: sections 1, 1a and 1b, the weights of 1c, the matrices of 1e and the
-// normalisation modes of 1g.
+// api_object.hip -- the object API of include/lccrf.h: sections 1, 1a and 1b (what a handle shares word for word with a batch --
+// weights, matrices, normalisation modes, plans -- is in api_model.hip).
 //
 // Argument checks, pinned staging and launch order of one handle; the state machine behind it is the Engine (host_engine.h).
 #include "api_common.h"
@@ -33,12 +33,12 @@ int capacity_for(int n) { return std::max(1024, ((n + n / 4 + 511) / 512) * 512)
 int lccrf::apply_option(Engine &e, int option, int value)
 {
     switch (option) {
-    case LCCRF_OPT_SINGLE_WORKGROUP: e.opt_single_wg = value != 0; return LCCRF_OK;
-    case LCCRF_OPT_FRAME_GENERAL: e.opt_frame_general = value != 0; return LCCRF_OK;    // (takes effect with the next inference / run)
-    case LCCRF_OPT_FUSED_BACKWARD: e.opt_fused_backward = value != 0; return LCCRF_OK;  // (takes effect with the next backward call)
+    case LCCRF_OPT_SINGLE_WORKGROUP: e.opt.single_wg = value != 0; return LCCRF_OK;
+    case LCCRF_OPT_FRAME_GENERAL: e.opt.frame_general = value != 0; return LCCRF_OK;    // (takes effect with the next inference / run)
+    case LCCRF_OPT_FUSED_BACKWARD: e.opt.fused_backward = value != 0; return LCCRF_OK;  // (takes effect with the next backward call)
     case LCCRF_OPT_VERTEX_ORDER:                                                         // (takes effect with the next build)
         if (value < 0 || value > 2) return fail(LCCRF_E_INVALID, "LCCRF_OPT_VERTEX_ORDER takes 0 (automatic), 1 (on) or 2 (off)");
-        e.opt_vertex_order = value;
+        e.opt.vertex_order = value;
         return LCCRF_OK;
     default: return fail(LCCRF_E_INVALID, "unknown option %d", option);
     }
@@ -125,11 +125,8 @@ int lccrf_create(lccrf_handle *out, int device_id, int n_points, int n_labels)
     }
     h->eng.ensure_parked_idle();                          // (a reused handle: its last kernel has stored its done word, or we wait for it)
     h->N = n_points;
-    h->eng.opt_single_wg = default_single_wg();           // (a recycled handle does not inherit its last user's options)
-    h->eng.opt_frame_general = default_frame_general();
-    h->eng.opt_fused_backward = false;
-    h->eng.backward_route = LCCRF_BACKWARD_NONE;
-    h->eng.opt_vertex_order = 0;
+    h->eng.opt = Engine::Options::fresh();                // (a recycled handle does not inherit its last user's options ...
+    h->eng.report = Engine::RunReport{};                  //  ... nor what its last run was)
     h->eng.activeN = n_points;
     h->eng.crf.map = h->map_pin;
     h->eng.map_host = h->map_pin;
@@ -350,8 +347,9 @@ int lccrf_get_engine(lccrf_handle h, int *engine, int *shape)
         int rl = h->eng.resolve_late();
         if (rl) return rl;
     }
-    *engine = h->eng.engine_used;
-    if (shape) *shape = (h->eng.engine_used == 2 || h->eng.engine_used == 4) ? h->eng.engine_shape : 0;
+    const Engine::RunReport &r = h->eng.report;
+    *engine = r.engine;
+    if (shape) *shape = (r.engine == 2 || r.engine == 4) ? r.shape : 0;
     return LCCRF_OK;
 }
 
@@ -398,8 +396,8 @@ static int pairwise_apply_on(lccrf_crf *h, int kernel, float *d_out, const float
     Engine &e = h->eng;
     const int rc = e.make_ready(Engine::kSettled | Engine::kCallerOrder | Engine::kSized | Engine::kStepViews);   // (builds staged lattices)
     if (rc || !h->N) return rc;
-    launch_filter(e.step_kdevs()[kernel], e.crf, e.maxV[kernel], d_in, d_out, accumulate, e.stream, 0, nullptr, e.compat_ptr[kernel],
-                  e.n_modes ? e.pre_ptr[kernel] : nullptr);
+    launch_filter(e.step_kdevs()[kernel], e.crf, e.maxV[kernel], d_in, d_out, accumulate, e.stream, 0, nullptr, e.model.compat_ptr[kernel],
+                  e.model.pre_arg() ? e.model.pre_arg()[kernel] : nullptr);
     HIP_TRY(hipGetLastError());
     return LCCRF_OK;
 }
@@ -524,28 +522,6 @@ int lccrf_get_lattice_size(lccrf_handle h, int kernel, int *n_vertices)
     { int rcf = h->eng.make_ready(Engine::kBuilt); if (rcf) return rcf; }
     HIP_TRY(hipStreamSynchronize(h->eng.stream));
     *n_vertices = h->eng.V_host[(size_t)kernel * h->eng.Fcap];
-    return LCCRF_OK;
-}
-
-int lccrf_get_splat_plan(lccrf_handle h, int kernel, lccrf_splat_plan *out)
-{
-    CHECK_H(h);
-    CHECK_K(h, kernel);
-    if (!out) return fail(LCCRF_E_INVALID, "out is NULL");
-    Engine &e = h->eng;
-    { int rc = e.make_ready(Engine::kSettled | Engine::kSized); if (rc) return rc; }   // (builds staged lattices, the plain way)
-    report_splat_plan(e.kernels[kernel].dev, e.crf.F, out);
-    return LCCRF_OK;
-}
-
-int lccrf_get_blur_plan(lccrf_handle h, int kernel, lccrf_blur_plan *out)
-{
-    CHECK_H(h);
-    CHECK_K(h, kernel);
-    if (!out) return fail(LCCRF_E_INVALID, "out is NULL");
-    Engine &e = h->eng;
-    { int rc = e.make_ready(Engine::kSettled | Engine::kSized); if (rc) return rc; }   // (builds staged lattices, the plain way)
-    *out = blur_plan(e.kernels[kernel].dev, e.crf.F, e.kernels[kernel].maxV).counts;     // (what launch_step_stream is given)
     return LCCRF_OK;
 }
 
@@ -752,69 +728,6 @@ int lccrf_map_of_device(lccrf_handle h, const float *d_prob, int16_t *d_map)
     { int rc = check_device_array(h, d_prob, (size_t)h->N * h->eng.L * sizeof(float), "d_prob"); if (rc) return rc; }
     { int rc = check_device_array(h, d_map, (size_t)h->N * sizeof(int16_t), "d_map"); if (rc) return rc; }
     return map_of_on(h, d_prob, d_map);
-}
-
-// --------------------------------------------------------------------------------------
-// section 1c: the terms' weights (the gradients of inference() are in api_backward.hip)
-
-int lccrf_set_pairwise_weight(lccrf_handle h, int kernel, float w)
-{
-    CHECK_H(h);
-    CHECK_K(h, kernel);
-    Engine &e = h->eng;
-    { int rl = e.resolve_late(); if (rl) return rl; }   // (a pending one-launch inference may still be re-run with the old weight)
-    e.set_weight(kernel, w);
-    return LCCRF_OK;
-}
-
-// --------------------------------------------------------------------------------------
-// section 1e: label-compatibility matrices of the pairwise terms
-
-int lccrf_set_pairwise_compatibility(lccrf_handle h, int kernel, const float *compat)
-{
-    CHECK_H(h);
-    CHECK_K(h, kernel);
-    Engine &e = h->eng;
-    for (int i = 0; compat && i < e.L * e.L; ++i)
-        if (!std::isfinite(compat[i])) return fail(LCCRF_E_INVALID, "compat[%d][%d] is not finite", i / e.L, i % e.L);
-    { int rl = e.resolve_late(); if (rl) return rl; }   // (a pending one-launch inference may still be re-run: as a Potts model)
-    return e.set_compat(kernel, compat);
-}
-
-int lccrf_get_pairwise_compatibility(lccrf_handle h, int kernel, float *compat_out, int *is_set)
-{
-    CHECK_H(h);
-    CHECK_K(h, kernel);
-    const Engine &e = h->eng;
-    const bool set = e.compat_ptr[kernel] != nullptr;
-    if (is_set) *is_set = set ? 1 : 0;
-    for (int i = 0; compat_out && i < e.L * e.L; ++i)     // (a Potts term reads as the identity it is)
-        compat_out[i] = set ? e.compat_host[(size_t)kernel * e.L * e.L + i] : (i / e.L == i % e.L ? 1.0f : 0.0f);
-    return LCCRF_OK;
-}
-
-// --------------------------------------------------------------------------------------
-// section 1g: where each pairwise term applies its norm
-
-int lccrf_set_pairwise_normalization(lccrf_handle h, int kernel, int mode)
-{
-    CHECK_H(h);
-    CHECK_K(h, kernel);
-    if (mode < LCCRF_NORMALIZE_AFTER || mode > LCCRF_NORMALIZE_NONE)
-        return fail(LCCRF_E_INVALID, "normalization mode %d is none of LCCRF_NORMALIZE_AFTER / _BEFORE / _SYMMETRIC / _NONE", mode);
-    Engine &e = h->eng;
-    { int rl = e.resolve_late(); if (rl) return rl; }   // (a pending one-launch inference may still be re-run: with the modes it was asked with)
-    e.set_norm_mode(kernel, mode);
-    return LCCRF_OK;
-}
-
-int lccrf_get_pairwise_normalization(lccrf_handle h, int kernel, int *mode)
-{
-    CHECK_H(h);
-    CHECK_K(h, kernel);
-    if (!mode) return fail(LCCRF_E_INVALID, "mode is NULL");
-    *mode = h->eng.norm_mode[kernel];
-    return LCCRF_OK;
 }
 
 }  // extern "C"

@@ -1,9 +1,11 @@
 // host_engine.h -- the host-side state machine behind the C-ABI: one Engine per handle or batch.
 //
 // Host code only (no kernel): device memory, lattice builds, locality mode, engine choice, the late-bound one-launch run with its
-// per-frame fallback, the done-word protocol, the backward area, the compatibility matrices and the normalisation modes.  The bodies are in
-// host_engine.hip; the entry points of include/lccrf.h (api_*.hip) read and write the fields below directly -- all but the two things
-// that are the engine's own: what a call relies on is brought up to date by make_ready() alone, what is in flight is `flight`.
+// per-frame fallback, the done-word protocol, the backward area and the learnt model.  The bodies are in host_engine.hip (lifecycle,
+// readiness, builds, run routes), host_late.hip (settling a one-launch run) and host_model.hip (LearntModel); the entry points of
+// include/lccrf.h (api_*.hip) read and write the fields below directly -- all but what has one owner: what a call relies on is brought
+// up to date by make_ready() alone, what is in flight is `flight`, a user's options are `opt` (reset as a whole), what the last run
+// was is `report` (written by its recorders alone) and the terms' matrices and modes are `model` (changed by its methods alone).
 // Every run is one Schedule (engine.h) -- a fixed count, or a cap with its criterion and tol -- built by the entry points.  A
 // one-launch run is armed by run_frame() alone, which keeps it as `late`, what resolve_late() re-runs flagged frames with; the fused
 // engine's kernels on lattices in HBM are launched, and what the engine reports of them recorded, by launch_sized() alone.
@@ -17,6 +19,7 @@ namespace lccrf {
 
 // Sets the calling thread's error text (lccrf_last_error) and returns `code`.  Defined once, in api_tools.hip.
 int fail(int code, const char *fmt, ...);
+bool default_single_wg(), default_frame_general();   // LCCRF_OPT_SINGLE_WORKGROUP's and LCCRF_OPT_FRAME_GENERAL's process-wide defaults (api_tools.hip)
 
 #define HIP_TRY(expr)                                                                        \
     do {                                                                                     \
@@ -34,6 +37,13 @@ inline void cpu_relax()
 #elif defined(__aarch64__)
     asm volatile("yield" ::: "memory");
 #endif
+}
+
+inline int next_pow2(long v)
+{
+    long p = 16;
+    while (p < v) p <<= 1;
+    return (int)p;
 }
 
 // Owns every device / pinned allocation of one engine.
@@ -121,14 +131,10 @@ struct Engine {
     int built_upto = 0;                // kernels [0, built_upto) have their lattice
 
     // ---- engine choice ----
-    int engine_pref = 0, engine_used = 1;   // engine_used is REPORT-only state (lccrf_batch_get_engine, lccrf_get_engine): 1 streaming, 2 fused,
-                                            //   3 one launch per frame, 4 the fused engine's kernels with matrices and factors
-                                            //   (fused_general.hip, fused_general_converge.hip)
+    int engine_pref = 0;
     int sized_engine = 1;              // what choose_sized_engine() chose for inference on lattices that sit in HBM (1, 2 or 4)
-    int engine_shape = 0;              // report only (lccrf_get_engine): fused_report() of the last inference on engine 2 or 4, else 0
     int last_with_map = 0;             // did the last inference produce MAP labels?
     size_t fused_lds = 0;
-    int fused_shape = 0;               // report only: what the last fused inference launched (SizedLaunch::shape)
     LeanPrep lean_prep;                // prepared launch records of the two-frames-per-CU inference kernel (engine.h)
     bool fused_fits = false;           // learn_sizes(): the lattices now in HBM fit the fused engine
     bool batch_owned = false;          // set by lccrf_batch_create: the engine of a batch (whatever its frame count), not of a handle
@@ -154,8 +160,6 @@ struct Engine {
     int (*after_rerun)(void *) = nullptr;
     void *after_rerun_ctx = nullptr;
     static constexpr int kDualMaxFrames = 64;    // (measured, `scripts/small_batch_latency.py`: 4 frames 98 -> 86 us, 32 frames 93 -> 83 us, 128 frames 112 -> 114 us)
-    bool opt_single_wg = false;        // LCCRF_OPT_SINGLE_WORKGROUP: never the two-workgroup form (lccrf_set_option)
-    bool opt_frame_general = false;    // LCCRF_OPT_FRAME_GENERAL: terms with a matrix or a mode may take the one-launch route (frame_general.hip)
     unsigned *dual_area = nullptr;     // hand-off area of the two-workgroup form of the frame kernel (batches of up to kDualMaxFrames frames)
     unsigned dual_epoch = 0;
     // object API: the frame kernel's last act is a store of `done_epoch` into this pinned word, behind its results; the host
@@ -192,7 +196,6 @@ struct Engine {
     int *fb_list = nullptr;            // device [Fcap]: frames being re-run
     int *fb_list_host = nullptr;       // pinned [Fcap]
     Engine *fb = nullptr;
-    int fallback_frames = 0;           // frames the last one-launch run had to re-run (report only)
     bool frame_small_ok = true;        // small frames may run as 512-lane workgroups (two per CU); turned off for this engine when
     bool frame_small_used = false;     //   more than 1/8 of a batch's frames did not fit that plan
     bool frame_lean_ok = true;         // ... and so may batches of full-size frames (frame_lean.hip), under the same rule
@@ -214,8 +217,7 @@ struct Engine {
     SortScratch sort{};
     float *Qp = nullptr, *unary_p = nullptr;   // [Fcap][maxN][L]
     bool sort_scratch_complete = false;
-    int opt_vertex_order = 0;          // LCCRF_OPT_VERTEX_ORDER: 0 automatic (= on), 1 on, 2 off -- locality mode's sorted build
-    bool vorder_on = false;            // ... as decided by the last build of every kernel
+    bool vorder_on = false;            // the sorted build (Options::vertex_order), as decided by the last build of every kernel
     bool vorder_broken = false;        // a frame's code space overflowed (*sort.vbad): this engine keeps to the hash build
     int *ndist_host = nullptr;         // pinned [K][kNdistAxes]: the sorted build's largest neighbour distances (KernelDev::ndist)
     int *tbl_bad = nullptr;            // pinned [2]: what the sorted build found wrong with its tables (KernelDev::tbl_bad)
@@ -225,35 +227,96 @@ struct Engine {
     // demand and freed with the handle's use (recycle) -- a parked handle does not keep it -- or with the batch
     unsigned char *bwd_area = nullptr;
     size_t bwd_area_bytes = 0;
-    bool opt_fused_backward = false;   // LCCRF_OPT_FUSED_BACKWARD: dL/dU and dL/dw of frames the fused plan takes run in one launch (fused_backward.hip)
-    int backward_route = 0;            // report only (lccrf_get_backward_route): LCCRF_BACKWARD_* of the last successful backward call
 
-    // ---- compatibility matrices ----
-    // sections 1e (a handle) and 2g (a batch: one matrix per term, shared by every frame): the terms' label-compatibility matrices.
-    // One device array for all of them, allocated by the first setter and kept with the handle or batch; compat_ptr[k] is term k's
-    // [L][L] slice of it, or null (Potts).  While n_compat > 0 the one-launch frame kernel and the fused engine, which hard-wire
-    // Potts, are not taken (nor their prepared launch records touched) -- under LCCRF_OPT_FRAME_GENERAL the one-launch route's general
-    // kernels are (frame_ok); the frames choose_sized_engine() names run on the fused
-    // engine's general kernels, which take the matrices by value from compat_host.
-    float *compat_dev = nullptr;       // [LCCRF_MAX_KERNELS][L][L]
-    float *compat_host = nullptr;      // pinned, the same shape: the matrices as set (the getter's answer and the uploads' source)
-    hipEvent_t compat_ev = nullptr;    // behind the last upload: a setter waits for it before it rewrites a source that may be in flight
-    const float *compat_ptr[LCCRF_MAX_KERNELS] = {};
-    int n_compat = 0;
+    // ---- a user's options ----
+    // lccrf_set_option / lccrf_batch_set_option write here and nowhere else; lccrf_create (new and recycled handles alike) and
+    // lccrf_batch_create assign fresh(), so a recycled handle inherits none of its last user's.
+    struct Options {
+        bool single_wg = false;        // LCCRF_OPT_SINGLE_WORKGROUP: never the two-workgroup form of the frame kernel
+        bool frame_general = false;    // LCCRF_OPT_FRAME_GENERAL: terms with a matrix or a mode may take the one-launch route (frame_general.hip)
+        bool fused_backward = false;   // LCCRF_OPT_FUSED_BACKWARD: dL/dU and dL/dw of frames the fused plan takes run in one launch (fused_backward.hip)
+        int vertex_order = 0;          // LCCRF_OPT_VERTEX_ORDER: 0 automatic (= on), 1 on, 2 off -- locality mode's sorted build
+        bool event_timing = true;      // LCCRF_OPT_EVENT_TIMING: HIP events around every build / inference / run of the batch API
+        static Options fresh() { Options o; o.single_wg = default_single_wg(); o.frame_general = default_frame_general(); return o; }
+    } opt;
 
-    // ---- normalisation modes ----
-    // sections 1g (a handle) and 2g (a batch: one mode per term, shared by every frame): where each term applies its norm -- after the
-    // filter (the reference's form and the default), before it, half on either side, or not at all.  While n_modes > 0 the one-launch
-    // frame kernel (but for its general form under LCCRF_OPT_FRAME_GENERAL, which forms the factors itself) and the fused engine are not taken and the streaming engine's general branch -- or one of the fused engine's
-    // general kernels -- runs on kdevs_post, the
-    // copy of kdevs whose `norm` points at each term's factor BEHIND the filter, with pre_ptr[k] the factor of its input
-    // (kStepViews, behind kSized).
-    int norm_mode[LCCRF_MAX_KERNELS] = {};   // lccrf_normalization of every term
-    int n_modes = 0;                   // terms that are not LCCRF_NORMALIZE_AFTER
-    float *ones = nullptr;             // [Fcap][maxN] of 1.0f: the factor behind the filter of a BEFORE or NONE term (lazy)
-    std::vector<KernelDev> kdevs_post;
-    const float *pre_ptr[LCCRF_MAX_KERNELS] = {};
-    bool factors_dirty = true;         // kdevs_post / pre_ptr are behind kdevs or the modes (raised by sync_views and set_norm_mode)
+    // ---- what the last run was ----
+    // Report only (lccrf_get_engine, lccrf_batch_get_engine / _fused_shape / _fallback_frames, lccrf_get_backward_route): nothing
+    // decides on it.  Written by the recorders below, one per route, and reset as a whole (recycle, lccrf_create).
+    struct RunReport {
+        int engine = 1;                // 1 streaming, 2 fused, 3 one launch per frame, 4 the fused engine's kernels with matrices and factors
+        int shape = 0;                 // fused_report() of the last inference on engine 2 or 4, else 0
+        int fused_shape = 0;           // what the last one-workgroup inference launched: lanes per frame | frames per CU << 16
+        int conv_engine = 0;           // 4 / 3 / 2 / 1 when the last inference was a converged one, else 0
+        int fallback_frames = 0;       // frames the last one-launch run had to re-run
+        int backward_route = 0;        // LCCRF_BACKWARD_* of the last successful backward call
+        void ran_on(int e, bool until_converged) { engine = e; shape = 0; conv_engine = until_converged ? e : 0; }
+        void frame_run(int launch_shape, bool until_converged)   // run_frame: launch_frame()'s 0, 1 (small) or 2 (lean)
+        {
+            ran_on(3, until_converged);
+            fallback_frames = 0;
+            fused_shape = launch_shape == 0 ? (1024 | 1 << 16) : (512 | 2 << 16);
+        }
+        void sized_run(int e, const SizedLaunch &r, bool until_converged, bool general)   // launch_sized (k_converge leaves fused_shape)
+        {
+            ran_on(e, until_converged);
+            shape = r.report;
+            if (!until_converged || general) fused_shape = r.shape;
+        }
+        void settled(int flagged, bool partial) { fallback_frames = flagged; if (partial) engine = 3; }   // resolve_late
+        void backward(int route) { backward_route = route; }
+        void new_inputs() { conv_engine = 0; }
+        // lccrf_batch_get_engine's answer, kept: `sized` (or 0) is what lattices in HBM run on now; a converged run overrides it
+        int in_use(int sized) { if (sized) engine = sized; if (conv_engine) engine = conv_engine; return engine; }
+    } report;
+    int engine_in_use(int *out);
+
+    // ---- the learnt model ----
+    // Sections 1e / 1g (a handle) and 2g (a batch: one matrix and one mode per term, shared by every frame).  The matrices live in one
+    // device array, allocated by the first setter and kept with the handle or batch; compat_ptr[k] is term k's [L][L] slice of it, or
+    // null (Potts).  The modes say where each term applies its norm: after the filter (the reference's form and the default), before
+    // it, half on either side, or not at all.  While general() the one-launch frame kernel (but for its general form under
+    // LCCRF_OPT_FRAME_GENERAL: frame_ok) and the fused engine, which hard-wire Potts terms normalised AFTER, are not taken (nor their
+    // prepared launch records touched): the frames choose_sized_engine() names run on the fused engine's general kernels, the rest on
+    // the streaming engine's general branch -- with modes, on kdevs_post, the copy of kdevs whose `norm` points at each term's factor
+    // BEHIND the filter, with pre_ptr[k] the factor of its input (kStepViews, behind kSized).  Bodies in host_model.hip; the counters,
+    // compat_ptr and factors_dirty are written there alone.  No setter touches a lattice, a norm or a prepared record.
+    struct LearntModel {
+        float *compat_dev = nullptr;       // [LCCRF_MAX_KERNELS][L][L]
+        float *compat_host = nullptr;      // pinned, the same shape: the matrices as set (the getter's answer and the uploads' source)
+        hipEvent_t compat_ev = nullptr;    // behind the last upload: a setter waits for it before it rewrites a source that may be in flight
+        const float *compat_ptr[LCCRF_MAX_KERNELS] = {};
+        size_t ll = 0;                     // L * L (known once a matrix is set)
+        int n_compat = 0;
+        int norm_mode[LCCRF_MAX_KERNELS] = {};   // lccrf_normalization of every term
+        int n_modes = 0;                   // terms that are not LCCRF_NORMALIZE_AFTER
+        float *ones = nullptr;             // [Fcap][maxN] of 1.0f: the factor behind the filter of a BEFORE or NONE term (lazy)
+        std::vector<KernelDev> kdevs_post;
+        const float *pre_ptr[LCCRF_MAX_KERNELS] = {};
+        const float *host_mats[LCCRF_MAX_KERNELS] = {};
+        bool factors_dirty = true;         // kdevs_post / pre_ptr are behind kdevs or the modes (raised by views_changed and set_mode)
+
+        bool general() const { return n_compat || n_modes; }
+        bool has_matrix(int k) const { return compat_ptr[k] != nullptr; }
+        const float *matrix(int k) const { return compat_host + k * ll; }      // (the pinned copy; valid while has_matrix(k))
+        int mode(int k) const { return norm_mode[k]; }
+        const float *const *compat_arg() const { return n_compat ? compat_ptr : nullptr; }
+        const float *const *pre_arg() const { return n_modes ? pre_ptr : nullptr; }   // (valid behind kStepViews)
+        // the terms as the one-workgroup engines' launch requests take them (engine.h: TermModel; all null without a matrix or a mode):
+        TermModel terms(size_t K)
+        {
+            for (size_t k = 0; k < K; ++k) host_mats[k] = compat_ptr[k] ? matrix((int)k) : nullptr;
+            return TermModel{n_compat ? host_mats : nullptr, pre_arg(), n_modes ? norm_mode : nullptr};
+        }
+        void views_changed();                            // (sync_views: the views derived from kdevs are rebuilt by ensure_factors())
+        // `e` is the engine this model is the `model` of: its arena, stream, kernels and engine choice
+        void clear(Engine &e);                           // every term a Potts term normalised AFTER the filter
+        int set_matrix(Engine &e, int k, const float *m);
+        void set_mode(Engine &e, int k, int mode);
+        int ensure_factors(Engine &e);
+        int put_on(Engine &g, int K) const;              // g's model becomes this one (the sub-engine of rerun_frames)
+        void release() { if (compat_ev) (void)hipEventDestroy(compat_ev); compat_ev = nullptr; compat_dev = compat_host = nullptr; }   // (destroy)
+    } model;
 
     // ---- convergence-driven inference ----
     // sections 1h and 2e: what the last converged run reported per frame -- four [Fcap] arrays in HBM, written by the kernel of
@@ -264,7 +327,6 @@ struct Engine {
     int *conv_host = nullptr;          // pinned [4][Fcap]
     int *conv_running = nullptr;       // pinned [1]
     bool conv_valid = false;           // a converged run has reported on the current inputs
-    int conv_engine = 0;               // report only (lccrf_batch_get_engine): 4 / 3 / 2 / 1 when the last inference was a converged one, else 0
     ConvergeOut conv_out() const
     {
         return ConvergeOut{conv_dev, reinterpret_cast<float *>(conv_dev + Fcap), conv_dev + 2 * (size_t)Fcap, conv_dev + 3 * (size_t)Fcap};
@@ -273,9 +335,8 @@ struct Engine {
     // ---- timing ----
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // build begin/end, inference begin/end
     bool timed_build = false, timed_inf = false;
-    bool event_timing = true;          // LCCRF_OPT_EVENT_TIMING: HIP events around every build / inference / run of the batch API
 
-    // ---- methods (host_engine.hip, in this order; the short ones here) ----
+    // ---- methods (host_engine.hip, in this order, but for the late-run ones -- host_late.hip; the short ones here) ----
     int init(int device_id, int frames, int max_points, int n_labels);
     void destroy();
     int add_kernel(int d, float w, bool own_features, bool stage);
@@ -287,7 +348,7 @@ struct Engine {
     void invalidate_lattices() { built_upto = 0; sizes_known = false; }
     void invalidate_lean_prep() { lean_prep.valid = false; lean_prep.seen_key = 0; }
     // new inputs (a batch's next frames, a parked handle's next user): nothing set, built or started, every lattice stale
-    void forget_inputs() { unary_set = built = started = conv_valid = false; conv_engine = 0; invalidate_lattices(); }
+    void forget_inputs() { unary_set = built = started = conv_valid = false; report.new_inputs(); invalidate_lattices(); }
     // term k gets the weight w (settle a pending inference first): whatever was prepared for the old weights is rewritten
     void set_weight(int k, float w) { kernels[k].dev.w = w; sync_views(); invalidate_lean_prep(); }
 
@@ -329,30 +390,15 @@ struct Engine {
     int resolve_late(bool *seen_done = nullptr);
     int rerun_frames(int n);
 
-    const float *const *compat_arg() const { return n_compat ? compat_ptr : nullptr; }
     // Lattices that fit the fused plan: Potts terms normalised AFTER run on the fused engine; frames -- a handle's one or a batch's
     // F -- of up to kGeneralMaxPoints active points with a matrix or another mode on the general kernel; anything else streams.
     static constexpr int kGeneralMaxPoints = 2048;
     void choose_sized_engine()
     {
-        const bool general = n_compat || n_modes;
-        sized_engine = !fused_fits ? 1 : !general ? 2 : active_points(crf) <= kGeneralMaxPoints ? 4 : 1;
+        sized_engine = !fused_fits ? 1 : !model.general() ? 2 : active_points(crf) <= kGeneralMaxPoints ? 4 : 1;
     }
     // what the streaming step, the plug-in filter and the backward sweep are handed (valid behind kStepViews)
-    const KernelDev *step_kdevs() const { return n_modes ? kdevs_post.data() : kdevs.data(); }
-    const float *const *pre_arg() const { return n_modes ? pre_ptr : nullptr; }
-    // the terms as the one-workgroup engines' launch requests take them (engine.h: TermModel; all null without a matrix or a mode):
-    // the matrices by value from the pinned copies the setters keep -- K host pointers into compat_host, null for a Potts term
-    const float *host_mats[LCCRF_MAX_KERNELS] = {};
-    TermModel term_model()
-    {
-        for (size_t k = 0; k < kernels.size(); ++k) host_mats[k] = compat_ptr[k] ? compat_host + k * (size_t)L * L : nullptr;
-        return TermModel{n_compat ? host_mats : nullptr, pre_arg(), n_modes ? norm_mode : nullptr};
-    }
-    void clear_norm_modes();
-    void set_norm_mode(int k, int mode);
-    void clear_compat();
-    int set_compat(int k, const float *m);
+    const KernelDev *step_kdevs() const { return model.n_modes ? model.kdevs_post.data() : kdevs.data(); }
 
     void free_backward_area();
     int ensure_backward_area(size_t need);
@@ -364,7 +410,6 @@ private:
     int flush_builds(bool may_reorder = false);
     int learn_sizes(bool may_reorder = false);
     int ensure_unary();
-    int ensure_factors();
     CrfDev begin_iteration();
     void end_iteration(int with_map);
     bool launch_sized(const Schedule &run, LeanPrep *prep);

@@ -9,121 +9,8 @@
 #include <cmath>
 #include <algorithm>
 #include <cstring>
-#include <new>
-#include <atomic>
-#include <chrono>
 
 namespace lccrf {
-
-namespace {
-
-// Bounded spin on a pinned done word: true once it shows `epoch` (the frame kernel's last store), false after `limit`; the clock is
-// read every `check_every` spins (a power of two).  Either way an acquire fence orders the reads that follow behind the word.
-inline bool poll_done_word(const unsigned *word, unsigned epoch, std::chrono::microseconds limit, unsigned check_every)
-{
-    const volatile unsigned *w = word;
-    const auto t0 = std::chrono::steady_clock::now();
-    bool seen = false;
-    for (unsigned spins = 1; !(seen = (*w == epoch)); ++spins) {
-        if ((spins & (check_every - 1)) == 0 && std::chrono::steady_clock::now() - t0 > limit) break;
-        cpu_relax();
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return seen;
-}
-
-int next_pow2(long v)
-{
-    long p = 16;
-    while (p < v) p <<= 1;
-    return (int)p;
-}
-}  // namespace
-
-void Engine::clear_compat()
-{
-    for (int k = 0; k < LCCRF_MAX_KERNELS; ++k) compat_ptr[k] = nullptr;
-    n_compat = 0;
-    choose_sized_engine();
-}
-
-// m: host [L][L] (finite, checked by the caller) or null.  Touches no lattice, norm or prepared record.
-int Engine::set_compat(int k, const float *m)
-{
-    const size_t ll = (size_t)L * L;
-    if (m) {
-        if (!compat_dev) {
-            int rc = mem.alloc_pinned(&compat_host, (size_t)LCCRF_MAX_KERNELS * ll);
-            if (!rc) rc = mem.alloc(&compat_dev, (size_t)LCCRF_MAX_KERNELS * ll);
-            if (rc) { compat_dev = nullptr; return rc; }
-            HIP_TRY(hipEventCreateWithFlags(&compat_ev, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(compat_ev, stream));
-        }
-        HIP_TRY(hipEventSynchronize(compat_ev));        // (an earlier upload may still be reading the pinned copy)
-        memcpy(compat_host + k * ll, m, ll * sizeof(float));   // (the caller's array is free again when the call returns)
-        HIP_TRY(hipMemcpyAsync(compat_dev + k * ll, compat_host + k * ll, ll * sizeof(float), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipEventRecord(compat_ev, stream));
-    }
-    const float *p = m ? compat_dev + k * ll : nullptr;
-    n_compat += (p != nullptr) - (compat_ptr[k] != nullptr);
-    compat_ptr[k] = p;
-    choose_sized_engine();
-    return LCCRF_OK;
-}
-
-void Engine::clear_norm_modes()
-{
-    for (int k = 0; k < LCCRF_MAX_KERNELS; ++k) norm_mode[k] = LCCRF_NORMALIZE_AFTER;
-    n_modes = 0;
-    choose_sized_engine();
-}
-
-// mode: 0 .. 3, checked by the caller.  Touches no lattice, norm or prepared record.
-void Engine::set_norm_mode(int k, int mode)
-{
-    n_modes += (mode != LCCRF_NORMALIZE_AFTER) - (norm_mode[k] != LCCRF_NORMALIZE_AFTER);
-    norm_mode[k] = mode;
-    factors_dirty = true;
-    choose_sized_engine();
-}
-
-// Behind kSized, before anything reads step_kdevs() / pre_arg(): the factors the terms' modes need -- the square roots of a
-// SYMMETRIC term's norm, formed on the stream right behind the norm itself (in its point order, locality mode included) when a build
-// or a mode change has left them stale, and the array of ones -- and the views that point at them.
-int Engine::ensure_factors()
-{
-    if (!n_modes || !factors_dirty) return LCCRF_OK;   // (a build clears root_valid and goes through sync_views: dirty again)
-    const size_t np = (size_t)Fcap * maxN;
-    kdevs_post = kdevs;
-    for (size_t k = 0; k < kernels.size(); ++k) {
-        KernelState &ks = kernels[k];
-        const int mode = norm_mode[k];
-        pre_ptr[k] = nullptr;
-        if (mode == LCCRF_NORMALIZE_SYMMETRIC) {
-            if (!ks.norm_root) {
-                int rc = mem.alloc(&ks.norm_root, np);
-                if (rc) { ks.norm_root = nullptr; return rc; }
-                ks.root_valid = false;
-            }
-            if (!ks.root_valid) launch_norm_factor(crf, ks.dev.norm, ks.norm_root, 1, stream);
-            ks.root_valid = true;
-            pre_ptr[k] = kdevs_post[k].norm = ks.norm_root;
-        } else if (mode != LCCRF_NORMALIZE_AFTER) {
-            if (!ones) {
-                int rc = mem.alloc(&ones, np, false);
-                if (rc) { ones = nullptr; return rc; }
-                CrfDev all = crf;                          // every frame the engine can hold: a batch's next inputs may bind more
-                all.F = Fcap;                              //   frames than its first (a handle has one)
-                launch_norm_factor(all, nullptr, ones, 0, stream);
-            }
-            if (mode == LCCRF_NORMALIZE_BEFORE) pre_ptr[k] = ks.dev.norm;
-            kdevs_post[k].norm = ones;
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    factors_dirty = false;
-    return LCCRF_OK;
-}
 
 void Engine::free_backward_area()
 {
@@ -175,10 +62,10 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
     // largest frame and lattices; behind every check and the area, so a rejected call leaves the handle as it was either way.
     bool dU_dw_only = !rq.compat_form && !rq.grad_compat && !rq.grad_model;
     for (int k = 0; k < K && rq.grad_features; ++k) dU_dw_only &= rq.grad_features[k] == nullptr;
-    if (opt_fused_backward && dU_dw_only && count && !n_compat && !n_modes && !perm_on &&
+    if (opt.fused_backward && dU_dw_only && count && !model.general() && !perm_on &&
         launch_fused_backward(crf, kdevs.data(), maxV.data(), maxRow.data(), rows, rq, ar, stream)) {
         HIP_TRY(hipGetLastError());
-        backward_route = LCCRF_BACKWARD_FUSED;
+        report.backward(LCCRF_BACKWARD_FUSED);
         return LCCRF_OK;
     }
     for (int t = 0; t < T; ++t) {
@@ -192,7 +79,7 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
     if (!count) {                                     // nothing to differentiate: dL/dw = 0
         if (grad_weights && K) HIP_TRY(hipMemsetAsync(grad_weights, 0, (size_t)F * K * sizeof(float), stream));
         if (rq.grad_model && K) HIP_TRY(hipMemsetAsync(rq.grad_model, 0, (size_t)K * (1 + L * L) * sizeof(float), stream));
-        backward_route = LCCRF_BACKWARD_STREAM;
+        report.backward(LCCRF_BACKWARD_STREAM);
         return LCCRF_OK;
     }
     for (int k = 0; k < K && rq.grad_features; ++k) {
@@ -203,9 +90,9 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
             HIP_TRY(hipMemsetAsync(ar.gb[k], 0, ar.feat_floats[k] * sizeof(float), stream));
     }
     HIP_TRY(hipMemcpyAsync(ar.G, rq.grad_prob, count * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    launch_backward_sweep(crf, step_kdevs(), maxV.data(), rows, rq, ar, compat_arg(), stream, pre_arg());
+    launch_backward_sweep(crf, step_kdevs(), maxV.data(), rows, rq, ar, model.compat_arg(), stream, model.pre_arg());
     HIP_TRY(hipGetLastError());
-    backward_route = LCCRF_BACKWARD_STREAM;
+    report.backward(LCCRF_BACKWARD_STREAM);
     return LCCRF_OK;
 }
 
@@ -333,9 +220,7 @@ void Engine::destroy()
     for (auto &e : ev)
         if (e) (void)hipEventDestroy(e);
     if (ev_order) (void)hipEventDestroy(ev_order);
-    if (compat_ev) (void)hipEventDestroy(compat_ev);
-    compat_ev = nullptr;
-    compat_dev = compat_host = nullptr;
+    model.release();
     if (lean_prep.ev0) (void)hipEventDestroy(lean_prep.ev0);
     if (lean_prep.ev1) (void)hipEventDestroy(lean_prep.ev1);
     lean_prep = LeanPrep{};
@@ -443,15 +328,6 @@ int Engine::add_kernel(int d, float w, bool own_features, bool stage)
     return LCCRF_OK;
 }
 
-// A parked engine whose last frame was taken label by label: its kernel is over once the done word shows this frame's epoch
-// (the kernel's very last store); normally that happened long ago, otherwise wait for the stream the ordinary way.
-void Engine::ensure_parked_idle()
-{
-    if (flight != Flight::kParkedDoneDue) return;
-    flight = Flight::kUnknown;
-    if (!poll_done_word(done_word, done_epoch, std::chrono::microseconds(50), 64) && stream) (void)hipStreamSynchronize(stream);
-}
-
 // Park everything for the next user of this engine (object API handle cache).
 void Engine::recycle()
 {
@@ -474,10 +350,8 @@ void Engine::recycle()
     perm_on = vorder_on = perm_banned = false;        // (the next user's lattices decide afresh)
     unary_is_label = unary_p_valid = false;
     engine_pref = 0;
-    engine_used = 1;
-    engine_shape = 0;
-    clear_compat();                                   // (the next user's terms start as Potts terms ...
-    clear_norm_modes();                               //  ... normalised AFTER the filter)
+    report = RunReport{};
+    model.clear(*this);                               // (the next user's terms start as Potts terms normalised AFTER the filter)
     sync_views();
 }
 
@@ -496,7 +370,7 @@ void Engine::sync_views()
         maxV[i] = kernels[i].maxV;
         maxRow[i] = kernels[i].maxRow;
     }
-    factors_dirty = true;                              // (section 1g: the views derived from kdevs are rebuilt by ensure_factors())
+    model.views_changed();
     crf.K = (int)kernels.size();
     crf.F = F;
     crf.activeN = activeN;
@@ -526,7 +400,7 @@ int Engine::build_kernels(int k0, int n, bool may_reorder)
         // vertex (ids along the lattice's axes: the blur pass touches half as many lines) -- yes unless switched off: with the
         // points in row-major order too it wins at every number of frames in flight (notes/r4_experiments.md section 2)
         static const char *env_vo = ab_env("LCCRF_VERTEX_ORDER");               // A/B switch: 1 on, 0 off (same results)
-        const int vo = env_vo ? (atoi(env_vo) ? 1 : 2) : opt_vertex_order;
+        const int vo = env_vo ? (atoi(env_vo) ? 1 : 2) : opt.vertex_order;
         vorder_on = want && !vorder_broken && vo != 2;
         sync_views();
         if (want) {
@@ -730,7 +604,7 @@ int Engine::step(float relax)
     // (kUnaries: label-derived energies follow the lattices' point order: re-derived after a re-build)
     const int rc = make_ready(kSettled | kCallerOrder | kSized | kUnaries | kStepViews);
     if (rc) return rc;
-    launch_step_stream(crf, step_kdevs(), maxV.data(), relax, stream, compat_arg(), pre_arg());
+    launch_step_stream(crf, step_kdevs(), maxV.data(), relax, stream, model.compat_arg(), model.pre_arg());
     return LCCRF_OK;
 }
 
@@ -739,7 +613,7 @@ bool Engine::frame_ok() const
 {
     static const bool no_frame = ab_env("LCCRF_NO_FRAME") != nullptr;   // cross-check switch: two-kernel path, same results
     // terms with a matrix or a mode: only under LCCRF_OPT_FRAME_GENERAL, two labels, frames of the general kernels' size (frame_general.hip)
-    if ((n_compat || n_modes) && !(opt_frame_general && L == 2 && active_points(crf) <= kGeneralMaxPoints)) return false;
+    if (model.general() && !(opt.frame_general && L == 2 && active_points(crf) <= kGeneralMaxPoints)) return false;
     return !no_frame && engine_pref == 0 && !kernels.empty() && frame_supported(crf, kdevs.data());
 }
 
@@ -749,7 +623,7 @@ int Engine::run_frame(const Schedule &run)
 {
     const int with_map = run.with_map;
     const bool stop = run.until_converged;
-    const bool general = n_compat || n_modes;         // (frame_ok: under LCCRF_OPT_FRAME_GENERAL only) frame_general.hip's kernels
+    const bool general = model.general();             // (frame_ok: under LCCRF_OPT_FRAME_GENERAL only) frame_general.hip's kernels
     *late_status = 0;
     // (label-derived energies already written for lattices in locality mode sit in the INTERNAL point order: the frame kernel, which
     //  works in the caller's order, derives them from the labels again)
@@ -758,7 +632,7 @@ int Engine::run_frame(const Schedule &run)
     unsigned *dual = nullptr;
     // The tracker's case (one frame, 255 idle CUs) and small batches (a quarter as many frames as CUs, or fewer): every
     // frame gets two workgroups, one per lattice build.
-    if (crf.K == 2 && F <= kDualMaxFrames && !opt_single_wg && !one_shape) {
+    if (crf.K == 2 && F <= kDualMaxFrames && !opt.single_wg && !one_shape) {
         if (!dual_area) {
             int rc = mem.alloc(reinterpret_cast<char **>(&dual_area), frame_dual_bytes(std::min(Fcap, kDualMaxFrames)));
             if (rc) return rc;
@@ -789,24 +663,20 @@ int Engine::run_frame(const Schedule &run)
     }
     // a matrix or a mode on some term: the matrices travel by value from the pinned copies the setters keep, the factors of every
     // mode are formed in the kernel (no ensure_factors(): nothing of it is in HBM); until converged: the report leaves with the results
-    const FrameRequest rq{run, term_model(), late_status, frame_status, from_label ? deferred_label : nullptr, deferred_tbl.v,
+    const FrameRequest rq{run, model.terms(kernels.size()), late_status, frame_status, from_label ? deferred_label : nullptr, deferred_tbl.v,
                           by_word ? done_word : nullptr, done_epoch, conv_out(), frame_small_ok, dual, dual_epoch,
                           !one_shape && frame_lean_ok ? lean_rec : nullptr};
     const int shape = launch_frame(crf, kdevs.data(), rq, stream);
     HIP_TRY(hipGetLastError());
     frame_small_used = shape == 1;
     frame_lean_used = shape == 2;
-    fused_shape = shape == 0 ? (1024 | 1 << 16) : (512 | 2 << 16);       // lanes per frame | frames per CU
-    engine_shape = 0;
-    conv_engine = stop ? 3 : 0;
+    report.frame_run(shape, stop);
     if (stop) conv_valid = true;
     late = run;
 
     flight = by_label ? Flight::kPendingLabels : by_word ? Flight::kPendingDone : Flight::kPending;
     started = true;
-    engine_used = 3;
     last_with_map = with_map;
-    fallback_frames = 0;
     return LCCRF_OK;
 }
 
@@ -846,7 +716,7 @@ int Engine::make_ready(unsigned needs)
     if (!rc && (needs & kSized)) rc = learn_sizes(reorder);   // (builds what is pending: the internal point order is known after this)
     else if (!rc && (needs & kBuilt)) rc = flush_builds(reorder);
     if (!rc && (needs & kUnaries)) rc = ensure_unary();
-    if (!rc && (needs & kStepViews)) rc = ensure_factors();
+    if (!rc && (needs & kStepViews)) rc = model.ensure_factors(*this);
     if (call_ban) perm_banned = false;
     return rc;
 }
@@ -863,17 +733,24 @@ int Engine::run(int n_iter, int with_map, float relax)
     return inference_sized(fixed_run(n_iter, with_map, relax));
 }
 
+// lccrf_batch_get_engine (behind kSettled): lattices in HBM and the last run not the one-launch route -> what an inference on them
+// runs (or ran) on, sized_engine behind kSized; a converged run overrides that (RunReport::in_use).
+int Engine::engine_in_use(int *out)
+{
+    const bool hbm = built && report.engine != 3;
+    if (int rc = hbm ? make_ready(kSized) : LCCRF_OK) return rc;
+    *out = report.in_use(hbm ? sized_engine : 0);
+    return LCCRF_OK;
+}
+
 // The fused engine's kernels on the lattices in HBM (behind kSized | kStepViews): the one launch, and what the engine records of it.
 // False: the frames are not ones the kernel takes and nothing was launched.  (The k_converge route leaves fused_shape as it was.)
 bool Engine::launch_sized(const Schedule &run, LeanPrep *prep)
 {
-    const SizedRequest rq{run, term_model(), conv_out(), prep};
+    const SizedRequest rq{run, model.terms(kernels.size()), conv_out(), prep};
     const SizedLaunch r = launch_inference(crf, step_kdevs(), maxV.data(), maxRow.data(), rq, stream);
     if (!r.report) return false;
-    engine_used = sized_engine;
-    conv_engine = run.until_converged ? sized_engine : 0;
-    engine_shape = r.report;
-    if (!run.until_converged || rq.terms.general()) fused_shape = r.shape;
+    report.sized_run(sized_engine, r, run.until_converged, rq.terms.general());
     started = true;
     if (run.until_converged) conv_valid = true;
     return true;
@@ -883,13 +760,11 @@ int Engine::inference_sized(const Schedule &run, unsigned more_needs)
 {
     const int rc = make_ready(kSized | kUnaries | kStepViews | more_needs);
     if (rc) return rc;
-    engine_used = sized_engine;
-    engine_shape = 0;
+    report.ran_on(sized_engine, false);
     last_with_map = run.with_map;
-    conv_engine = 0;
     if (perm_on || sized_engine == 1) {
         const CrfDev v = begin_iteration();
-        for (int it = 0; it < run.n_iter; ++it) launch_step_stream(v, step_kdevs(), maxV.data(), run.relax, stream, compat_arg(), pre_arg());
+        for (int it = 0; it < run.n_iter; ++it) launch_step_stream(v, step_kdevs(), maxV.data(), run.relax, stream, model.compat_arg(), model.pre_arg());
         end_iteration(run.with_map);
         HIP_TRY(hipGetLastError());
         return LCCRF_OK;
@@ -976,8 +851,7 @@ int Engine::inference_converged(const Schedule &run)
         HIP_TRY(hipGetLastError());
         return LCCRF_OK;
     }
-    engine_used = conv_engine = 1;
-    engine_shape = 0;
+    report.ran_on(1, true);
     if ((rc = converge_stream(run))) return rc;
     conv_valid = true;
     return LCCRF_OK;
@@ -1014,7 +888,7 @@ int Engine::converge_stream(const Schedule &run)
     launch_track_begin(cp, tk, max_iter, stream);
     int t_last = 0;
     for (int t = 1; t <= max_iter; ++t) {
-        launch_step_stream(cp, step_kdevs(), maxV.data(), run.relax, stream, compat_arg(), pre_arg());
+        launch_step_stream(cp, step_kdevs(), maxV.data(), run.relax, stream, model.compat_arg(), model.pre_arg());
         launch_track_step(cp, tk, t, max_iter, run.criterion, run.tol, stream);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(stream));
@@ -1034,166 +908,6 @@ int Engine::read_convergence()
     for (int a = 0; a < 4; ++a)
         HIP_TRY(hipMemcpyAsync(conv_host + (size_t)a * Fcap, conv_dev + (size_t)a * Fcap, sizeof(int) * (size_t)F, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    return LCCRF_OK;
-}
-
-// getMap() with one frame in flight whose labels go straight into map_host: take them as they land.  True: `out` holds the n labels
-// and the run counts as settled -- every label is there, so the frame fitted and the kernel is past its last read -- but not as
-// formally finished: V_out, frame_status and the done word are stored behind the labels (and a helper workgroup may be in its
-// epilogue): the handle counts as idle only once recycle() has seen the done word.  False: the ordinary path (resolve_late) is to run.
-bool Engine::take_labels(int16_t *out, int n)
-{
-    if (flight != Flight::kPendingLabels) return false;
-    flight = Flight::kPendingDone;
-    const volatile int16_t *m = map_host;
-    const auto t0 = std::chrono::steady_clock::now();
-    bool ok = true, timed_out = false;
-    unsigned spins = 0;
-    for (int i = 0; i < n && ok; ++i) {
-        int16_t v;
-        while ((v = m[i]) == (int16_t)-1) {               // (bounded: whatever goes wrong is left to the ordinary path)
-            if ((++spins & 0x3ff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) { ok = false; timed_out = true; break; }
-            cpu_relax();
-        }
-        if (v < 0) ok = false;                            // -2: the frame did not fit the one-launch kernel
-    }
-    if (ok) {
-        std::atomic_thread_fence(std::memory_order_acquire);
-        memcpy(out, map_host, (size_t)n * sizeof(int16_t));
-        flight = Flight::kLabelsSeen;
-        return true;
-    }
-    if (timed_out) flight = Flight::kPending;             // (a delayed frame: do not spin another 2 ms on the done word, wait on the stream)
-    return false;
-}
-
-// Before anything looks at (or continues from) the results of a late-bound inference.
-// *seen_done (optional): the frame's results were observed through the done word -- the caller may read the pinned
-// outputs without a stream synchronisation of its own.
-int Engine::resolve_late(bool *seen_done)
-{
-    if (seen_done) *seen_done = false;
-    if (!run_pending()) return LCCRF_OK;
-    // bounded poll; a word that never comes is waited for the ordinary way
-    const bool seen = flight != Flight::kPending && poll_done_word(done_word, done_epoch, std::chrono::milliseconds(2), 1024);
-    flight = Flight::kUnknown;
-    if (!seen) HIP_TRY(hipStreamSynchronize(stream));
-    if (*npoints_bad) {                                // (the one-launch path never passes through learn_sizes())
-        *npoints_bad = 0;
-        return fail(LCCRF_E_CAPACITY, "a bound n_points[f] lies outside [0, max_points=%d] (the kernels clamped it)", maxN);
-    }
-    if (*late_status == 0) {
-        if (seen_done) *seen_done = seen;
-        return LCCRF_OK;
-    }
-    *late_status = 0;                                  // some frame did not fit the one-launch kernel
-    if (seen) HIP_TRY(hipStreamSynchronize(stream));   // (the kernel has nothing left to do; the stream formally still holds it)
-    HIP_TRY(hipMemcpy(frame_status_host, frame_status, sizeof(int) * F, hipMemcpyDeviceToHost));
-    int n = 0;
-    for (int f = 0; f < F; ++f)
-        if (frame_status_host[f]) fb_list_host[n++] = f;
-    fallback_frames = n;
-    if (frame_small_used && 8 * n > F) frame_small_ok = false;   // these lattices want the whole CU: 1024 lanes from now on
-    if (frame_lean_used && 8 * n > F) frame_lean_ok = false;
-    int rc = LCCRF_OK;
-    if (n >= F || n == 0) {                            // every frame (always so for the object API): two-kernel path in place
-        invalidate_lattices();
-        rc = rerun_on(*this);
-    } else {
-        rc = rerun_frames(n);                          // the batch stays a one-launch batch; only the flagged frames pay twice
-        engine_used = 3;
-    }
-    if (rc) return rc;
-    if (timed_inf) HIP_TRY(hipEventRecord(ev[3], stream));   // the timed region now ends behind the re-run
-    if (after_rerun && (rc = after_rerun(after_rerun_ctx))) return rc;
-    HIP_TRY(hipStreamSynchronize(stream));             // callers read borrowed device buffers right behind a synchronisation point
-    return LCCRF_OK;
-}
-
-// What the pending one-launch run is re-run with on the two-kernel path of `e` (this engine, or the sub-engine holding its flagged
-// frames): the fixed count, or -- behind run_converged() -- the same stop rule.
-int Engine::rerun_on(Engine &e)
-{
-    return late.until_converged ? e.inference_converged(late) : e.inference_sized(late);
-}
-
-// Two-kernel path for the frames fb_list_host[0, n) only, in a compact sub-engine; results scattered back.
-int Engine::rerun_frames(int n)
-{
-    if (fb && fb->Fcap < n) {
-        fb->destroy();
-        delete fb;
-        fb = nullptr;
-    }
-    if (!fb) {
-        fb = new (std::nothrow) Engine;
-        if (!fb) return fail(LCCRF_E_NOMEM, "host allocation failed");
-        int rc = fb->init(device, std::min(Fcap, std::max(8, next_pow2(n))), maxN, L);
-        for (size_t k = 0; k < kernels.size() && !rc; ++k) rc = fb->add_kernel(kernels[k].dev.d, kernels[k].dev.w, true, false);
-        if (!rc && hipStreamSynchronize(fb->stream) != hipSuccess) rc = fail(LCCRF_E_HIP, "hipStreamSynchronize after allocation failed");
-        if (rc) {
-            fb->destroy();
-            delete fb;
-            fb = nullptr;
-            return rc;
-        }
-    }
-    Engine &g = *fb;
-    const hipStream_t g_own = g.stream;
-    g.stream = g.mem.stream = stream;                  // everything below (lazy allocations' zeroing included) is ordered on this engine's stream
-    struct Restore { Engine &g; hipStream_t s; ~Restore() { g.stream = g.mem.stream = s; } } restore{g, g_own};
-    g.F = n;
-    g.activeN = activeN;
-    g.engine_pref = engine_pref == 1 ? 1 : 0;
-    HIP_TRY(hipMemcpyAsync(fb_list, fb_list_host, sizeof(int) * n, hipMemcpyHostToDevice, stream));
-    launch_copy_frames(g.npoints_own, 4, crf.n_points, 4, fb_list, n, 4, 1, stream);
-    g.crf.n_points = g.npoints_own;
-    for (size_t k = 0; k < kernels.size(); ++k) {
-        const size_t row = (size_t)maxN * kernels[k].dev.d * sizeof(float);
-        launch_copy_frames(g.kernels[k].feat_own, row, kernels[k].dev.feat, row, fb_list, n, row, 1, stream);
-        g.kernels[k].dev.feat = g.kernels[k].feat_own;
-        g.kernels[k].dev.w = kernels[k].dev.w;
-    }
-    // the model as it is now (a one-launch run under LCCRF_OPT_FRAME_GENERAL): the setters settle a pending run before they change
-    // it, so this is the model the flagged frames were launched with -- it may differ from the last re-run's
-    g.clear_compat();
-    g.clear_norm_modes();
-    for (size_t k = 0; k < kernels.size(); ++k) {
-        if (compat_ptr[k])
-            if (int rc = g.set_compat((int)k, compat_host + k * (size_t)L * L)) return rc;
-        g.set_norm_mode((int)k, norm_mode[k]);
-    }
-    g.crf.unary = g.unary_own;
-    if (unary_deferred || (unary_is_label && perm_on)) {   // (see run_frame: energies written in the internal point order are of no use here)
-        launch_copy_frames(g.label_own, (size_t)maxN * 2, deferred_label, (size_t)maxN * 2, fb_list, n, (size_t)maxN * 2, 1, stream);
-        g.unary_deferred = true;
-        g.deferred_label = g.label_own;
-        g.deferred_tbl = deferred_tbl;
-    } else {
-        const size_t row = (size_t)maxN * L * sizeof(float);
-        launch_copy_frames(g.unary_own, row, crf.unary, row, fb_list, n, row, 1, stream);
-        g.unary_deferred = false;
-    }
-    g.unary_set = true;
-    g.invalidate_lattices();
-    g.sync_views();
-    HIP_TRY(hipGetLastError());
-    int rc = rerun_on(g);
-    if (rc) return rc;
-    const size_t qrow = (size_t)maxN * L * sizeof(float);
-    launch_copy_frames(crf.Q, qrow, g.crf.Q, qrow, fb_list, n, qrow, 0, stream);
-    if (late.with_map) {
-        launch_copy_frames(crf.map, (size_t)maxN * 2, g.crf.map, (size_t)maxN * 2, fb_list, n, (size_t)maxN * 2, 0, stream);
-        if (crf.map_bits && g.crf.map_bits)
-            launch_copy_frames(crf.map_bits, (size_t)crf.bits_stride * 8, g.crf.map_bits, (size_t)crf.bits_stride * 8, fb_list, n,
-                               (size_t)crf.bits_stride * 8, 0, stream);
-    }
-    for (size_t k = 0; k < kernels.size(); ++k)
-        launch_copy_frames(kernels[k].dev.V, 4, g.kernels[k].dev.V, 4, fb_list, n, 4, 0, stream);
-    if (late.until_converged)                         // the re-run frames' reports: iterations, delta, changed, converged
-        for (int a = 0; a < 4; ++a)
-            launch_copy_frames(conv_dev + (size_t)a * Fcap, 4, g.conv_dev + (size_t)a * g.Fcap, 4, fb_list, n, 4, 0, stream);
-    HIP_TRY(hipGetLastError());
     return LCCRF_OK;
 }
 
