@@ -7,6 +7,7 @@ import batch_cases as bc
 import crf_cases as cc
 import feature_cases as fc
 import grad_support as gs
+import lattice_tie_cases as tc
 import meanfield_f64_features as mff
 import normalization_checker as nc
 from joint_checker import dense                                 # I + 0.3 N(0, 1), seeded: the matrices of the section 1e - 1g tests
@@ -82,17 +83,30 @@ def meanfield(po, wl, golden, name, T, relax):
 FEATURE_SETTINGS, FEATURE_IDS = product("features", fc.CASES, T_SET)
 
 
-def features(po, wl, golden, name, T, relax):
+def features(po, wl, golden, name, T, relax, lst="features"):
     """`ref`: dL/df_k over the FeatureLattice lattices; `ref_1c`: dL/dU and dL/dw of the same call"""
-    pb, image = fc.gradient_case(name, golden, po, wl)
+    pb, image = (tc.problem(name), None) if lst == "ties" else fc.gradient_case(name, golden, po, wl)
     o = cc.setup(po.OracleCRF, pb)
     lats, U = mff.lattices(o, pb), o.unary().astype(np.float64)
     G, w = grad_prob(pb), gs.weights(pb)
-    at = device_iterates(po, pb, T, relax) if linearised("features", name, T, relax) else None
+    at = device_iterates(po, pb, T, relax) if linearised(lst, name, T, relax) else None
     s = dict(pb=pb, image=image, G=G, dims=[lat.d for lat in lats], ref=gs.feature_reference(U, w, lats, T, relax, G, name, at),
              ref_1c=gs.reference(U, w, lats, T, relax, G, name, at))
     o.close()
     return s
+
+
+# ---- test_feature_gradients.py, at exact lattice ties: TIES_CASES x TIES_T, relax 1 ------------------------------------------------------
+# Frames of tests/lattice_tie_cases.py: points ON the rounding and rank ties of the lattice build, where the derivative is one-sided and
+# the simplex the device recomputes in its backward (k_corner_to_feature: lattice_simplex) must be the oracle's, the one the checker
+# differentiates through.  Same checker, same bars, same cap as the `features` list.
+TIES_CASES, TIES_T = ["ties:slam256", "ties:d5"], (1, 5)
+TIES = [(n, T, 1.0) for n in TIES_CASES for T in TIES_T if (n, T, 1.0) not in DROPPED.get("ties", {})]
+TIES_IDS = ["%r-%d-%s" % (r, T, n) for n, T, r in TIES]
+
+
+def ties(po, wl, golden, name, T, relax):
+    return features(po, wl, golden, name, T, relax, lst="ties")
 
 
 # ---- test_compatibility.py: COMPAT_CASES x T_SHORT x RELAX_SET -------------------------------------------------------------------------

@@ -2,7 +2,8 @@
 lccrf_inference_backward_features (include/lccrf.h section 1d).
 
 The topology is the oracle's and is held fixed (offset, nbr, V of pyoracle.OracleCRF.kernel(k); the simplex of a point from the
-key of its remainder-0 corner; the ranks from the order of el - rem0); inside it the weights are linear in the features
+key of its remainder-0 corner; the ranks from the keys of its other corners, so that a point ON a float32 rank tie keeps the oracle's
+side); inside it the weights are linear in the features
 (permutohedral_cpu.h:304-366) and the norm 1 / (Phi(1) + 1e-20) is part of the graph.  torch.autograd through
 meanfield_f64.forward with these lattices gives the reference dL/d features.  The file also holds the hand-written reverse sweep
 the kernels implement (no autograd) and a small float64 lattice builder of its own, for the finite-difference test.
@@ -41,6 +42,23 @@ def ranks_of(diff):
     return rank
 
 
+def ranks_of_corners(keys, off, rem0):
+    """The ranks of the ORACLE's simplex, read off its corners' keys: corner c has the key rem0_i + c where rank_i <= d - c, else
+    rem0_i + c - (d + 1) (permutohedral_cpu.h:274-279,373), so coordinate i < d keeps the offset +c on d + 1 - rank_i of the d + 1
+    corners; the ranks are a permutation, which gives the last one.  At an exact float32 rank tie the float64 order of el - rem0 is
+    not the build's (ranks_of would pick the simplex across the boundary, whose one-sided derivative is another); rows whose keys
+    wrapped int16 give no permutation here and are returned as -1."""
+    N, D1 = off.shape
+    d = D1 - 1
+    cnt = np.zeros((N, d), np.int64)
+    for c in range(D1):
+        cnt += (keys[off[:, c]] - rem0[:, :d]) == c
+    rank = np.concatenate([D1 - cnt, (d * D1 // 2 - (D1 - cnt).sum(1))[:, None]], 1)
+    ok = (np.sort(rank, 1) == np.arange(D1)).all(1)
+    rank[~ok] = -1
+    return rank
+
+
 def bary_of(f, scale, rem0, rank):
     """b [N, d+1] of features f [N, d] inside the simplex (rem0, rank): corner q receives +v of the coordinate with
     p = d - rank = q and -v of the one with p = q - 1 (cell d+1 folds into corner 0), v = (el - rem0) / (d+1)"""
@@ -74,7 +92,10 @@ class FeatureLattice(mf.Lattice):
         r0 = keys[off[:, 0]] if len(off) else np.zeros((0, self.d), np.int64)
         self.rem0 = np.concatenate([r0, -r0.sum(1, keepdims=True)], 1)
         el = elevate(torch.as_tensor(self.feat32.astype(np.float64)), torch.as_tensor(self.scale.astype(np.float64))).numpy()
-        self.rank = ranks_of(el - self.rem0)
+        self.el64 = el
+        self.rank = ranks_of_corners(keys, off, self.rem0) if len(off) else np.zeros((0, self.d + 1), np.int64)
+        lost = (self.rank < 0).any(1)                            # (wrapped keys: the order of el - rem0, tie-free there)
+        self.rank[lost] = ranks_of(el - self.rem0)[lost]
         self.keys, self.off0 = keys, off
         # The oracle's weights are the linear form ROUNDED in float32 (v = (el - rem0) / (d+1) with |el| up to a few hundred: a few
         # 1e-6 of b).  The rounding does not move with the features, so it enters as a constant: at the case's own features the
@@ -235,7 +256,10 @@ class BuiltLattice(FeatureLattice):
         r0 = keys[off[:, 0]]
         self.rem0 = np.concatenate([r0, -r0.sum(1, keepdims=True)], 1)
         el = elevate(torch.as_tensor(f), torch.as_tensor(self.scale.astype(np.float64))).numpy()
-        self.rank = ranks_of(el - self.rem0)
+        self.el64 = el
+        self.rank = ranks_of_corners(keys, off, self.rem0) if len(off) else np.zeros((0, self.d + 1), np.int64)
+        lost = (self.rank < 0).any(1)                            # (wrapped keys: the order of el - rem0, tie-free there)
+        self.rank[lost] = ranks_of(el - self.rem0)[lost]
         self.keys, self.off0 = keys, off
         self.residual = torch.zeros(f.shape[0], self.d + 1, dtype=D)
         self.bind(torch.as_tensor(f))

@@ -104,6 +104,23 @@ def test_feature_gradients_match_the_checker(po, wl, golden, name, T, relax):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("name,T,relax", gset.TIES, ids=gset.TIES_IDS)
+def test_feature_gradients_at_exact_lattice_ties(po, wl, golden, name, T, relax):
+    """Frames whose points sit ON the lattice build's rounding ties and rank ties (tests/lattice_tie_cases.py): the derivative is
+    one-sided there, the side is the simplex, and the backward recomputes the simplex itself (k_corner_to_feature through
+    lattice_simplex).  Held to the float64 checker over the ORACLE's simplex under the bars and the cap of every other list
+    (gradient_settings.TIES; tests/test_gradient_bars.py covers the list): a device that rounds a tie or ranks a tie another way
+    differentiates another simplex's weights."""
+    s = gset.ties(po, wl, golden, name, T, relax)
+    h, keep = gs.gpu_handle(s["pb"], None)
+    gu, gw, gf = _backward_features(h, _dims(s["pb"], None), T, relax, s["G"])
+    h.close()
+    assert all(np.isfinite(a).all() for a in gf)
+    s["ref"].check({"dL/df%d" % k: a for k, a in enumerate(gf)})
+    s["ref_1c"].check({"dL/dU": gu, "dL/dw": gw})
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("name", ["c2", "nt:d3_L21", "nt:d2-5-3_L9", "large:c5", "image64x48"])
 def test_bits_of_section_1c_determinism_null_entries_and_state(po, wl, golden, name):
     """dL/dU and dL/dw are bit for bit lccrf_inference_backward's; Q afterwards is lccrf_inference(h, T, 0, relax)'s; two runs

@@ -8,6 +8,8 @@ import pytest
 import crf_cases as cc
 import feature_cases as fc
 import grad_support as gs
+import gradient_settings as gset
+import lattice_tie_cases as tc
 import meanfield_f64 as mf
 import meanfield_f64_features as mff
 
@@ -36,6 +38,23 @@ def test_bary_is_the_oracles(po, wl, golden, name):
         assert np.array_equal(lat.bary.numpy(), lat.oracle_bary)
     print("largest |b - bary| %s: %.3g" % (name, worst))
     assert worst <= BARY_BAR
+
+
+@pytest.mark.parametrize("name", gset.TIES_CASES)
+def test_simplex_is_the_oracles_at_exact_ties(po, name):
+    """Points ON a float32 rank tie (tests/lattice_tie_cases.py): the float64 order of el - rem0 is not the build's there and would
+    give the simplex across the boundary (7 + 3 points of ties:slam256 and 12 of ties:d5 did before the ranks were read off the
+    oracle's corner keys: the one-sided derivative is another).  The checks of test_bary_is_the_oracles under its bar."""
+    pb = tc.problem(name)
+    o, lats, _ = _checker(po, pb)
+    for lat, (f, _) in zip(lats, pb["kernels"]):
+        s = tc.simplex_f32(f)
+        assert s["rank_tie"].sum() >= 12 and (mff.ranks_of(lat.el64 - lat.rem0) != lat.rank).any()
+        assert lat.topology_agrees() and np.array_equal(lat.rank, s["rank"].astype(np.int64))
+        assert np.abs(lat.linear_bary - lat.oracle_bary).max() <= BARY_BAR
+        # (a float32 tie is no float64 tie: in float64 the point lies outside the build's simplex by the rounding of el, no more)
+        assert np.abs(lat.linear_bary.sum(1) - 1).max() < 1e-12 and lat.linear_bary.min() >= -BARY_BAR
+        assert np.array_equal(lat.bary.numpy(), lat.oracle_bary)
 
 
 # the cases of test_checker_forward_matches_the_oracle without the tie cases, and the tie-free generic frames

@@ -52,6 +52,8 @@ def groups(po, wl, golden):
     for n, T, r in gset.FEATURE_SETTINGS:
         if n not in BIG or T == 5:
             add("features", n, "T%d-r%g" % (T, r), T, False, lambda n=n, T=T, r=r: gset.features(po, wl, golden, n, T, r))
+    for n, T, r in gset.TIES:
+        add("ties", n, "T%d-r%g" % (T, r), T, False, lambda n=n, T=T, r=r: gset.ties(po, wl, golden, n, T, r))
     for n, T, r in gset.COMPAT_SETTINGS:
         if n not in BIG or T == 5:
             add("compat", n, "T%d-r%g" % (T, r), T, True, lambda n=n, T=T, r=r: gset.compat(po, wl, golden, n, T, r))
@@ -91,7 +93,7 @@ def groups(po, wl, golden):
 
 def group_ids():
     """the (list, case) pairs of groups(), without building anything"""
-    ids = [("meanfield", n) for n in cc.CASES] + [("features", n) for n in fc.CASES] + [("compat", n) for n in gset.COMPAT_CASES]
+    ids = [("meanfield", n) for n in cc.CASES] + [("features", n) for n in fc.CASES] + [("ties", n) for n in dict.fromkeys(n for n, _, _ in gset.TIES)] + [("compat", n) for n in gset.COMPAT_CASES]
     ids += [("joint", n) for n in dict.fromkeys(n for n, _, _ in jc.SETTINGS)]
     ids += [("joint-mixed", n) for n in jc.MIXED_CASES] + [("joint-potts", n) for n in jc.POTTS_CASES]
     ids += [("normalization", n) for n in gset.NORM_CASES]
