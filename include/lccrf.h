@@ -103,8 +103,15 @@ int  lccrf_trim_cache(void);
  *       and the calls of sections 1d - 1f, 2d and 2h when nothing else is asked for) on two-label frames of up to 2048 points with one
  *       or two 2-D Potts terms normalised AFTER runs the replay and the sweep in ONE kernel launch (section 1j; csrc/fused_backward.hip).
  *       The gradients and the Q left behind are bit for bit those of the option off; everything else takes the route it takes today.
+ *   LCCRF_OPT_FUSED_BACKWARD_LEARNT   (default 0) value != 0: the same for the requests LCCRF_OPT_FUSED_BACKWARD leaves out, feature
+ *       gradients apart: a backward call on a handle or batch whose terms carry a label-compatibility matrix or a normalisation mode
+ *       other than AFTER, and every call that asks for d_grad_compat or d_grad_model (Potts terms included) -- dL/dU, dL/dw and dL/dmu
+ *       of two-label frames of up to 2048 points with one or two 2-D terms in ONE kernel launch (section 1k;
+ *       csrc/fused_backward_general.hip), plus the two launches of d_grad_model's sums.  Bit for bit the results of the option off.  A
+ *       Potts / AFTER request for dL/dU and / or dL/dw alone is LCCRF_OPT_FUSED_BACKWARD's and is not affected.
  * lccrf_set_option applies to one handle (set it after lccrf_create: a handle taken from the cache starts from the defaults) and is
- * per handle (or batch) only for LCCRF_OPT_VERTEX_ORDER, LCCRF_OPT_COPY_THREADS, LCCRF_OPT_EVENT_TIMING and LCCRF_OPT_FUSED_BACKWARD;
+ * per handle (or batch) only for LCCRF_OPT_VERTEX_ORDER, LCCRF_OPT_COPY_THREADS, LCCRF_OPT_EVENT_TIMING, LCCRF_OPT_FUSED_BACKWARD and
+ * LCCRF_OPT_FUSED_BACKWARD_LEARNT;
  * lccrf_set_default_option applies LCCRF_OPT_SINGLE_WORKGROUP or LCCRF_OPT_FRAME_GENERAL to every handle and batch created afterwards
  * in this process.                                                                                                             */
 typedef enum lccrf_option {
@@ -113,7 +120,8 @@ typedef enum lccrf_option {
     LCCRF_OPT_COPY_THREADS     = 3,
     LCCRF_OPT_EVENT_TIMING     = 4,
     LCCRF_OPT_FRAME_GENERAL    = 5,
-    LCCRF_OPT_FUSED_BACKWARD  = 6
+    LCCRF_OPT_FUSED_BACKWARD  = 6,
+    LCCRF_OPT_FUSED_BACKWARD_LEARNT = 7
 } lccrf_option;
 int  lccrf_set_option(lccrf_handle h, int option, int value);
 int  lccrf_set_default_option(int option, int value);
@@ -371,7 +379,8 @@ int  lccrf_inference_backward_features(lccrf_handle h, int n_iterations, float r
  * the one-launch route's kernel for such terms, engine 3, same bits).  lccrf_inference on the shape the project exists for -- L = 2, one or two
  * 2-D terms, a frame of up to 2048 points whose lattices fit the fused engine's plan -- then runs in ONE launch on the fused
  * engine's kernel for such terms (lccrf_get_engine reports 4), with the same bits.  Everything else -- other L, d or K, 2049 points
- * and more, locality mode, lccrf_start_inference / lccrf_step_inference, the plug-in entry points, every backward call's replay --
+ * and more, locality mode, lccrf_start_inference / lccrf_step_inference, the plug-in entry points, every backward call's replay (but under
+ * LCCRF_OPT_FUSED_BACKWARD_LEARNT, section 1k: the replay and the sweep of such a frame in one launch) --
  * runs on the streaming engine with the matrix applied inside the slice kernel, which takes the Potts slice kernel's place: the
  * step issues no launch more than the streaming engine's general, L-label step (at L = 2 that is more than the two-label
  * specialisation issues).  The C++ mirror lccrf_densecrf.hpp sets a matrix per potential (PottsPotentialHIP::setCompatibility).
@@ -472,7 +481,8 @@ int  lccrf_inference_backward_all(lccrf_handle h, int n_iterations, float relax,
  * included (that kernel forms the factors itself, from the norm it holds in a register).  lccrf_inference
  * on L = 2, one or two 2-D terms and a frame of up to 2048 points whose lattices fit the fused engine's plan runs in ONE launch on
  * the fused engine's kernel for such terms (lccrf_get_engine reports 4): the pre factors sit in registers beside w * post.
- * Everything else (section 1e lists it) runs on the streaming engine's general L-label step, at L = 2 too: the pre factor is applied
+ * Everything else (section 1e lists it; a backward call's replay under LCCRF_OPT_FUSED_BACKWARD_LEARNT is section 1k's) runs on the
+ * streaming engine's general L-label step, at L = 2 too: the pre factor is applied
  * inside the splat where it loads its input (no launch more, no scaled copy of Q), the post factor is the array the slice reads in
  * the norm's place.  Both give the same bits.  Once every term is AFTER again the handle takes the fast engines and returns the
  * bits it returned before.
@@ -591,8 +601,32 @@ int  lccrf_run_converged(lccrf_handle h, int max_iterations, int criterion, floa
  *     locality-mode build made plain).
  * lccrf_get_backward_route / lccrf_batch_get_backward_route (section 2c) report which route the last successful backward call of any
  * section took; NULL arguments return LCCRF_E_INVALID and write nothing.  Added WITHOUT a step of LCCRF_ABI_VERSION: probe by symbol.
- * Not covered (notes/fused_backward.md): matrices and normalisation modes, feature gradients, d_grad_model, frames of 2049 points
- * and more, the half-CU shapes; the route is not the default.
+ * Not covered by this option (notes/fused_backward.md): matrices, normalisation modes, d_grad_compat and d_grad_model -- section 1k's
+ * LCCRF_OPT_FUSED_BACKWARD_LEARNT --, feature gradients, frames of 2049 points and more, the half-CU shapes; the route is not the
+ * default.
+ *
+ * 1k. ... and of a LEARNT model -- LCCRF_OPT_FUSED_BACKWARD_LEARNT (off by default; per handle or batch).
+ *
+ * The layers that learn the model (sections 1e, 1g, 2g, 2h) call the backward on handles and batches whose terms carry a matrix or a
+ * normalisation mode, and ask for dL/dmu.  With this option set such a call runs the replay and the sweep in one kernel launch too
+ * (csrc/fused_backward_general.hip: one 1024-lane workgroup per frame), when
+ *   - no entry of d_grad_features is non-NULL;
+ *   - some term has a matrix or a mode other than AFTER, or the call is in section 1e's form: d_grad_compat or d_grad_model is asked
+ *     for, also on Potts terms (the derivative at mu = I).  A Potts / AFTER request for dL/dU and / or dL/dw alone is section 1j's and
+ *     is governed by LCCRF_OPT_FUSED_BACKWARD only; LCCRF_OPT_FUSED_BACKWARD selects exactly what it selected before this option;
+ *   - the frames are ones the plan takes, as in section 1j (two labels, one or two 2-D terms, at most 2048 active points, lattices
+ *     inside one workgroup's LDS); when dL/dmu is asked for, also every term with a product buffer of its own in that plan (frames
+ *     whose lattices are so large that the plan shares one buffer take the sweep).  A batch decides once, over its largest frame.
+ * Everything else takes the route it takes with the option off.  n_iterations = 0 may take either route.
+ *   - Bit for bit: d_grad_unary (zero rows included), d_grad_weights, d_grad_compat (exactly +0 for a frame of 0 points and at
+ *     n_iterations = 0) and the Q left behind are those of the option off: the replay forms Q_t as the general step does; the sweep
+ *     forms every product and sum of sections 1e / 1g in their order; dL/dmu's partials are added over the same chunks of
+ *     ceil(n / chunks) rows in ascending row order, accumulated over the iterations and added over the chunks in order.
+ *   - d_grad_model (section 2h): the same two launches of the sums over the frames behind the kernel -- three launches in all.
+ *   - Memory: the area of sections 1e / 2h, nothing more.
+ *   - Argument checks, LCCRF_E_STATE, LCCRF_E_NOMEM and "a rejected call leaves the object as it was": the route is chosen where
+ *     section 1j's is.  lccrf_get_backward_route / lccrf_batch_get_backward_route report LCCRF_BACKWARD_FUSED.
+ * Not covered: feature gradients, frames of 2049 points and more, the half-CU shapes, other label counts and dimensions, K > 2.
  * ==================================================================================== */
 typedef enum lccrf_backward_route {
     LCCRF_BACKWARD_NONE   = 0,   /* no backward call yet */
@@ -891,7 +925,8 @@ int  lccrf_batch_run_converged(lccrf_batch_handle b, int max_iterations, int cri
  *     one-launch build + inference kernels hard-wire Potts.  lccrf_batch_get_fallback_frames reads 0.  With LCCRF_OPT_FRAME_GENERAL
  *     set, batches of frames of up to 2048 points take the one-launch kernels for such terms instead (csrc/frame_general.hip): engine
  *     3, shape 1024 / 1, the same bits; frames that do not fit are re-run with the same model and counted.
- * Gradients: lccrf_batch_inference_backward_all (section 2h), behind the batched torch layer BatchCompatMeanFieldCRF;
+ * Gradients: lccrf_batch_inference_backward_all (section 2h; one launch under LCCRF_OPT_FUSED_BACKWARD_LEARNT, section 1k), behind
+ * the batched torch layer BatchCompatMeanFieldCRF;
  * lccrf_batch_inference_backward and lccrf_batch_inference_backward_features still return LCCRF_E_STATE on such a batch and leave it
  * as it was (section 2c).  Not covered: the half-CU shapes (512 lanes, two frames per CU) and 3 - 4 points per lane; prepared launch
  * records for such batches; the handle's converged call.
@@ -939,6 +974,8 @@ int  lccrf_batch_get_pairwise_normalization(lccrf_batch_handle b, int kernel, in
  *     inference_ms timing the call, deterministic.
  *   - Launches: those of section 1f for one frame (per iteration and term one kernel more than section 2c with matrices in play or
  *     d_grad_compat / d_grad_model asked for, one reduction at the end), plus two for d_grad_model (K > 0).
+ *     Under LCCRF_OPT_FUSED_BACKWARD_LEARNT (section 1k), without feature arrays and on two-label frames of up to 2048 points: ONE
+ *     launch for all frames, plus the two for d_grad_model, the same bits.
  *   - Memory: section 2c's area (with section 2d's part for the terms asked for) grows, with a matrix set or d_grad_compat /
  *     d_grad_model given, by 4 * (F*S + K*F*C*L*L) bytes -- gamma_t and the partials of dL/dmu, F = n_frames, S = max_points * L,
  *     C = min(max(ceil(max_points / 256), 1), 128) -- plus 4 * F*S when d_grad_unary is NULL, and with d_grad_model by 4 * F*K bytes

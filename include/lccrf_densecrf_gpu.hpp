@@ -290,9 +290,10 @@ public:
         return V;
     }
     // lccrf_set_option (include/lccrf.h); setOption(LCCRF_OPT_FRAME_GENERAL, 1) keeps a learnt model on the one-launch route of a fresh frame.
+    // setOption(LCCRF_OPT_FUSED_BACKWARD_LEARNT, 1): the gradients of such a model, dL/dmu included, run in one launch (section 1k).
     void setOption(int option, int value) { lccrf_check(lccrf_set_option(h_, option, value), "lccrf_set_option"); }
     // lccrf_get_backward_route (include/lccrf.h section 1j): the route of the last successful backward call on this handle -- 0 none yet,
-    // 1 the streaming sweep, 2 one launch (setOption(LCCRF_OPT_FUSED_BACKWARD, 1)).  Report only.
+    // 1 the streaming sweep, 2 one launch (setOption(LCCRF_OPT_FUSED_BACKWARD, 1) / (LCCRF_OPT_FUSED_BACKWARD_LEARNT, 1)).  Report only.
     int backwardRoute() const
     {
         int r = 0;

@@ -237,10 +237,16 @@ class MeanFieldCRF(_HandleCRF):
 
 class CompatMeanFieldCRF(_HandleCRF):
     """MeanFieldCRF whose terms carry a learnt label-compatibility matrix: parameters `weights` [K] and `compat` [K, L, L], the
-    latter initialised to identities (the Potts model); normalization as MeanFieldCRF takes it.  forward(unary [N, L]) -> Q [N, L]."""
+    latter initialised to identities (the Potts model); normalization as MeanFieldCRF takes it; fused_backward: sets OPT_FUSED_BACKWARD
+    and OPT_FUSED_BACKWARD_LEARNT on the handle -- the gradients of frames the fused plan takes run in one launch (include/lccrf.h
+    sections 1j and 1k; the same bits).  forward(unary [N, L]) -> Q [N, L]."""
 
-    def __init__(self, n_points, n_labels, features, weights, n_iterations=5, relax=1.0, device=0, normalization=None):
+    def __init__(self, n_points, n_labels, features, weights, n_iterations=5, relax=1.0, device=0, normalization=None,
+                 fused_backward=False):
         super().__init__(n_points, n_labels, features, weights, n_iterations, relax, device, normalization)
+        if fused_backward:
+            self.crf.set_option(_pkg.OPT_FUSED_BACKWARD, 1)
+            self.crf.set_option(_pkg.OPT_FUSED_BACKWARD_LEARNT, 1)
         self.compat = _identities(len(weights), n_labels)
 
     def forward(self, unary):
@@ -364,11 +370,17 @@ class BatchMeanFieldCRF(_BatchCRF):
 class BatchCompatMeanFieldCRF(_BatchCRF):
     """BatchMeanFieldCRF whose terms carry a learnt label-compatibility matrix: parameters `weights` [K] and `compat` [K, L, L], the
     latter initialised to identities (the Potts model), both shared by every frame; normalization: None (the reference's form), one of
-    the package's NORMALIZE_* modes for every term, or one per term, set once.  The features are uploaded and the lattices built once,
-    here.  forward(unary [F, max_points, L]) -> Q [F, max_points, L]."""
+    the package's NORMALIZE_* modes for every term, or one per term, set once; fused_backward: sets OPT_FUSED_BACKWARD and
+    OPT_FUSED_BACKWARD_LEARNT on the batch (include/lccrf.h sections 1j and 1k: the same bits in one launch plus the two of the sums
+    over the frames).  The features are uploaded and the lattices built once, here.
+    forward(unary [F, max_points, L]) -> Q [F, max_points, L]."""
 
-    def __init__(self, n_points, features, weights, n_iterations=5, relax=1.0, device=0, n_labels=2, normalization=None):
+    def __init__(self, n_points, features, weights, n_iterations=5, relax=1.0, device=0, n_labels=2, normalization=None,
+                 fused_backward=False):
         super().__init__(n_points, features, weights, n_iterations, relax, device, n_labels, normalization)
+        if fused_backward:
+            self.batch.set_option(_pkg.OPT_FUSED_BACKWARD, 1)
+            self.batch.set_option(_pkg.OPT_FUSED_BACKWARD_LEARNT, 1)
         self.compat = _identities(len(weights), n_labels)
 
     def forward(self, unary):

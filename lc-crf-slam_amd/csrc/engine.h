@@ -379,6 +379,14 @@ struct BackwardArea {
 int backward_blocks(int n, int L);
 size_t backward_stride(int n, int L);
 int backward_compat_blocks(int n);
+// The chunks a frame of n points is cut into for the partials of dL/dmu (section 1e): one per 256 rows, at least 1, at most 128 --
+// backward_compat_blocks(n), the grid of a handle of n points.  A chunk is ceil(n / chunks) consecutive rows.
+constexpr int kCompatMaxBlocks = 128;
+__host__ __device__ inline int compat_chunks(int n)
+{
+    const int b = (n + 255) / 256;
+    return b < 1 ? 1 : b > kCompatMaxBlocks ? kCompatMaxBlocks : b;
+}
 // The area of request `rq` on c.F frames of up to `rows` points: returns its size in bytes and, with ar != null, sets *ar to
 // its parts in the area at `base` (sizing: both null).  Sizing and running go through this one function.
 size_t backward_layout(const BackwardRequest &rq, const CrfDev &c, const KernelDev *kds, size_t slice, int rows, float *base,
@@ -404,6 +412,16 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
 // launched, or 0 with nothing launched: the frames are not ones the plan takes.
 int launch_fused_backward(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, int rows, const BackwardRequest &rq,
                           const BackwardArea &ar, hipStream_t s);
+struct TermModel;
+// ... and of a learnt model, or of a request in the compat form (csrc/fused_backward_general.hip; include/lccrf.h section 1k): terms
+// with a matrix or a normalisation mode, dL/dU, dL/dw and dL/dmu per frame, no feature gradients.  kds: Engine::step_kdevs() (`norm` is
+// each term's factor behind the filter); terms: Engine's model (matrices by value, the factors in front of the filters).  Writes
+// rq.grad_unary (or ar.gU), rq.grad_weights (or ar.gW under rq.grad_model) and rq.grad_compat (or ar.gC) of every frame; the sums of
+// rq.grad_model are the caller's to launch.  Returns fused_report() of the shape launched, or 0 with nothing launched.
+int launch_fused_backward_general(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, int rows,
+                                  const BackwardRequest &rq, const BackwardArea &ar, const TermModel &terms, hipStream_t s);
+// out[j] = sum over the frames, in ascending order, of x[f][j], j < n (section 2h; meanfield_backward.hip)
+void launch_sum_frames(const float *x, int F, int n, float *out, hipStream_t s);
 
 // ---- one run, its terms, and what a converged one reports: what the launch requests below are made of ---------------------------
 // One run: a fixed count of n_iter iterations, or -- until_converged -- at most n_iter under (criterion, tol) (include/lccrf.h

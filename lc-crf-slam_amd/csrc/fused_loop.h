@@ -405,17 +405,23 @@ __device__ __forceinline__ void chain_pads(unsigned char *smem, const ChainLane 
 // REV: see the blur passes.  GEN: phase P takes its input through filter_input (gt; see GeneralTerms).
 // TRANSPOSE (fused_backward.hip): the blur passes along the axes in reverse order (2, 1, 0), each with the forward's pass arithmetic --
 // the transposed filter of include/lccrf.h section 1c.  Every other instantiation takes false and compiles as it did.
+// XIN (fused_backward_general.hip, with xin): phase P takes term k's input at point slot s from xin[s][k] -- the transposed filter of a
+// term with a matrix has an input of its own, mu_k^T (a_k gamma), which is not "one q times a per-term factor".  Neither pr.q nor gt
+// is read then.  Every other instantiation takes false and compiles as it did.
 template <int PPT, int K, int CH, bool WITH_P = true, int NT = kNT, int KMASK = (1 << K) - 1, bool REV = false, bool GEN = false,
-          bool TRANSPOSE = false>
+          bool TRANSPOSE = false, bool XIN = false>
 __device__ __forceinline__ void splat_blur(unsigned char *smem, const FusedLayout &lay, const int (&V)[K], int N, int tid,
                                            const PointRegs<PPT, K> &pr, const ChainLane &cl, Instr &ins,
-                                           const GeneralTerms<PPT, K> *gt = nullptr)
+                                           const GeneralTerms<PPT, K> *gt = nullptr, const float2 (*xin)[K] = nullptr)
 {
     constexpr int D1 = kD1;
     auto phase_P = [&](int k) {
 #pragma unroll
         for (int s = 0; s < PPT; ++s)
-            if (tid + s * NT < N) point_products<GEN, PPT, K, CH>(smem, lay, pr, gt, s, k);
+            if (tid + s * NT < N) {
+                if constexpr (XIN) point_products<PPT, K, CH>(smem, lay, pr, s, k, xin[s][k]);
+                else point_products<GEN, PPT, K, CH>(smem, lay, pr, gt, s, k);
+            }
         if (chain_k<CH>(lay, k)) chain_pads(smem, cl);    // (the buffer may have held another kernel's products)
     };
     // lanes [s_lo, NT) share the short-row kernels; the wavefronts that own the chain kernel's

@@ -68,6 +68,21 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
         report.backward(LCCRF_BACKWARD_FUSED);
         return LCCRF_OK;
     }
+    // LCCRF_OPT_FUSED_BACKWARD_LEARNT (section 1k): the complement among the requests without feature gradients -- a learnt model
+    // (a matrix, or a mode other than AFTER), or the compat form (dL/dmu, also of Potts terms) -- decided in the same place and the
+    // same way (fused_backward_general.hip).  The sums over the frames (section 2h) are the sweep's two launches, behind the kernel.
+    bool no_features = true;
+    for (int k = 0; k < K && rq.grad_features; ++k) no_features &= rq.grad_features[k] == nullptr;
+    if (opt.fused_backward_learnt && no_features && count && (model.general() || rq.compat_form) && !perm_on &&
+        launch_fused_backward_general(crf, step_kdevs(), maxV.data(), maxRow.data(), rows, rq, ar, model.terms((size_t)K), stream)) {
+        if (rq.grad_model) {
+            launch_sum_frames(rq.grad_weights ? rq.grad_weights : ar.gW, F, K, rq.grad_model, stream);
+            launch_sum_frames(rq.grad_compat ? rq.grad_compat : ar.gC, F, K * L * L, rq.grad_model + K, stream);
+        }
+        HIP_TRY(hipGetLastError());
+        report.backward(LCCRF_BACKWARD_FUSED);
+        return LCCRF_OK;
+    }
     for (int t = 0; t < T; ++t) {
         if (count) HIP_TRY(hipMemcpyAsync(ar.hist + (size_t)t * slice, crf.Q, count * sizeof(float), hipMemcpyDeviceToDevice, stream));
         if ((rc = step(rq.relax))) return rc;

@@ -351,15 +351,9 @@ void launch_softmax_bwd(const BwdArgs &a, int F, hipStream_t s)
 // puts y and Phi of row r into LDS, lane p (and p + 256, ...) adds the tile's rows in order to its entries (l, l') of the outer
 // product, kept in registers over the whole chunk, and lane r * L + l' forms row r of mu^T y.  No atomics: an entry has one owner and
 // one order of additions (rows ascending; t = T .. 1 across the sweep's launches), the same bits from run to run.
-constexpr int kCompatMaxBlocks = 128;
 constexpr int kCompatTileB = kBwdBlock + kBwdBlock / 2;   // R * (L | 1) <= 256 + R floats
 constexpr int kCompatPairs = (LCCRF_MAX_LABELS * LCCRF_MAX_LABELS + kBwdBlock - 1) / kBwdBlock;   // entries of mu per lane
-// chunks of a frame of n points (backward_compat_blocks: the grid of a handle of n points)
-__host__ __device__ inline int compat_chunks(int n)
-{
-    const int b = (n + kBwdBlock - 1) / kBwdBlock;
-    return b < 1 ? 1 : b > kCompatMaxBlocks ? kCompatMaxBlocks : b;
-}
+// (compat_chunks, the chunks of a frame of n points: engine.h -- the one-launch kernel of fused_backward_general.hip cuts the same)
 struct CompatArgs {
     const int *n_points;
     int L, first;                // first: the sweep's first iteration writes cpart, the others add to it
@@ -480,10 +474,15 @@ __global__ void __launch_bounds__(kBwdBlock) k_sum_frames(const float *__restric
     if (tid < ne) out[j0 + tid] = acc;
 }
 
+}  // namespace
+
+// (engine.h: the one-launch route of fused_backward_general.hip forms section 2h's sums with it too)
 void launch_sum_frames(const float *x, int F, int n, float *out, hipStream_t s)
 {
     if (n > 0) k_sum_frames<<<(unsigned)((n + kSumEntries - 1) / kSumEntries), kBwdBlock, 0, s>>>(x, F, n, out);
 }
+
+namespace {
 
 // ---- the feature part (sections 1d and 2d) ----------------------------------------------------------------------------------
 // gb[i][c] += scale * <row_i, val[v_ic]> for every point i < n_points[f] and corner c: a slice without the sum over the corners.
@@ -620,7 +619,7 @@ size_t backward_stride(int n, int L) { return (size_t)((n + 3) & ~3) * L; }
 
 int backward_blocks(int n, int L) { return (n + kBwdBlock / bwd_lanes(L) - 1) / (kBwdBlock / bwd_lanes(L)); }
 
-int backward_compat_blocks(int n) { return std::min(std::max((n + kBwdBlock - 1) / kBwdBlock, 1), kCompatMaxBlocks); }
+int backward_compat_blocks(int n) { return compat_chunks(n); }
 
 size_t backward_layout(const BackwardRequest &rq, const CrfDev &c, const KernelDev *kds, size_t slice, int rows, float *base,
                        BackwardArea *ar)
