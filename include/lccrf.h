@@ -109,9 +109,15 @@ int  lccrf_trim_cache(void);
  *       of two-label frames of up to 2048 points with one or two 2-D terms in ONE kernel launch (section 1k;
  *       csrc/fused_backward_general.hip), plus the two launches of d_grad_model's sums.  Bit for bit the results of the option off.  A
  *       Potts / AFTER request for dL/dU and / or dL/dw alone is LCCRF_OPT_FUSED_BACKWARD's and is not affected.
+ *   LCCRF_OPT_FUSED_BACKWARD_FEATURES   (default 0) value != 0: the same for a backward call WITH feature gradients (sections 1d and 2d,
+ *       and the calls of sections 1f and 2h that reduce to them: at least one non-NULL entry of d_grad_features, neither d_grad_compat
+ *       nor d_grad_model, no matrix) on Potts terms normalised AFTER, n_iterations >= 1 -- dL/dU, dL/dw and every dL/df_k asked for of
+ *       two-label frames of up to 2048 points with one or two 2-D terms in ONE kernel launch (section 1l;
+ *       csrc/fused_backward_features.hip).  Bit for bit the results of the option off.  A request without a feature array is never
+ *       this option's: options 6 and 7 select exactly what they selected.
  * lccrf_set_option applies to one handle (set it after lccrf_create: a handle taken from the cache starts from the defaults) and is
- * per handle (or batch) only for LCCRF_OPT_VERTEX_ORDER, LCCRF_OPT_COPY_THREADS, LCCRF_OPT_EVENT_TIMING, LCCRF_OPT_FUSED_BACKWARD and
- * LCCRF_OPT_FUSED_BACKWARD_LEARNT;
+ * per handle (or batch) only for LCCRF_OPT_VERTEX_ORDER, LCCRF_OPT_COPY_THREADS, LCCRF_OPT_EVENT_TIMING, LCCRF_OPT_FUSED_BACKWARD,
+ * LCCRF_OPT_FUSED_BACKWARD_LEARNT and LCCRF_OPT_FUSED_BACKWARD_FEATURES;
  * lccrf_set_default_option applies LCCRF_OPT_SINGLE_WORKGROUP or LCCRF_OPT_FRAME_GENERAL to every handle and batch created afterwards
  * in this process.                                                                                                             */
 typedef enum lccrf_option {
@@ -121,7 +127,8 @@ typedef enum lccrf_option {
     LCCRF_OPT_EVENT_TIMING     = 4,
     LCCRF_OPT_FRAME_GENERAL    = 5,
     LCCRF_OPT_FUSED_BACKWARD  = 6,
-    LCCRF_OPT_FUSED_BACKWARD_LEARNT = 7
+    LCCRF_OPT_FUSED_BACKWARD_LEARNT = 7,
+    LCCRF_OPT_FUSED_BACKWARD_FEATURES = 8
 } lccrf_option;
 int  lccrf_set_option(lccrf_handle h, int option, int value);
 int  lccrf_set_default_option(int option, int value);
@@ -355,7 +362,8 @@ int  lccrf_inference_backward(lccrf_handle h, int n_iterations, float relax, con
  *     width 1 (splat + d+1 blur passes each), two corner-dot kernels, and two small per-point kernels.
  *   - Memory: section 1c's area grows by 4 * sum over the terms asked for of N4 * (d_k + 2) bytes (g_b and g_n), and by 4 * N4 * L
  *     when d_grad_unary is NULL: 4 * (N4*L*(T + K + 1) + max(T,1)*K*B + sum_k N4*(d_k + 2)) bytes in all (N = 2000, L = 2, K = 2
- *     of d = 2, T = 5: 128 KB + 64 KB).  Allocated as section 1c's: by the first call that needs more, never by lccrf_inference.     */
+ *     of d = 2, T = 5: 128 KB + 64 KB).  Allocated as section 1c's: by the first call that needs more, never by lccrf_inference.
+ *   - In ONE launch under LCCRF_OPT_FUSED_BACKWARD_FEATURES (section 1l): the same bits, the same area, one kernel.                  */
 int  lccrf_inference_backward_features(lccrf_handle h, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
                                        float *d_grad_weights, float *const *d_grad_features);
 
@@ -602,8 +610,8 @@ int  lccrf_run_converged(lccrf_handle h, int max_iterations, int criterion, floa
  * lccrf_get_backward_route / lccrf_batch_get_backward_route (section 2c) report which route the last successful backward call of any
  * section took; NULL arguments return LCCRF_E_INVALID and write nothing.  Added WITHOUT a step of LCCRF_ABI_VERSION: probe by symbol.
  * Not covered by this option (notes/fused_backward.md): matrices, normalisation modes, d_grad_compat and d_grad_model -- section 1k's
- * LCCRF_OPT_FUSED_BACKWARD_LEARNT --, feature gradients, frames of 2049 points and more, the half-CU shapes; the route is not the
- * default.
+ * LCCRF_OPT_FUSED_BACKWARD_LEARNT --, feature gradients -- section 1l's LCCRF_OPT_FUSED_BACKWARD_FEATURES --, frames of 2049 points
+ * and more, the half-CU shapes; the route is not the default.
  *
  * 1k. ... and of a LEARNT model -- LCCRF_OPT_FUSED_BACKWARD_LEARNT (off by default; per handle or batch).
  *
@@ -626,7 +634,31 @@ int  lccrf_run_converged(lccrf_handle h, int max_iterations, int criterion, floa
  *   - Memory: the area of sections 1e / 2h, nothing more.
  *   - Argument checks, LCCRF_E_STATE, LCCRF_E_NOMEM and "a rejected call leaves the object as it was": the route is chosen where
  *     section 1j's is.  lccrf_get_backward_route / lccrf_batch_get_backward_route report LCCRF_BACKWARD_FUSED.
- * Not covered: feature gradients, frames of 2049 points and more, the half-CU shapes, other label counts and dimensions, K > 2.
+ * Not covered: feature gradients (on Potts terms normalised AFTER they are section 1l's; with a matrix or dL/dmu, sections 1f / 2h,
+ * they take the sweep), frames of 2049 points and more, the half-CU shapes, other label counts and dimensions, K > 2.
+ *
+ * 1l. ... and WITH feature gradients -- LCCRF_OPT_FUSED_BACKWARD_FEATURES (off by default; per handle or batch).
+ *
+ * The layers that learn the kernel bandwidths call lccrf_inference_backward_all with feature arrays on a Potts model; sections 1d / 2d
+ * add two corner-dot launches per iteration and term and two width-1 filters per term to section 1c's sweep (203 launches at T = 5
+ * with two 2-D terms).  With this option set such a call runs the replay and the sweep in one kernel launch
+ * (csrc/fused_backward_features.hip: one 1024-lane workgroup per frame), when
+ *   - at least one entry of d_grad_features is non-NULL (a NULL entry's term does no feature work, the other terms' bits do not
+ *     change; a request without a feature array is section 1j's or 1k's and never this option's);
+ *   - the call is not in section 1e's form: neither d_grad_compat nor d_grad_model, no matrix on the handle or batch --
+ *     lccrf_inference_backward_features, lccrf_batch_inference_backward_features, and lccrf_inference_backward_all /
+ *     lccrf_batch_inference_backward_all when they reduce to those;
+ *   - every term is a Potts term normalised AFTER the filter, and n_iterations >= 1 (at 0 the call takes the sweep's memset to +0);
+ *   - the frames are ones the plan takes, as in section 1j.  A batch decides once, over its largest frame and lattices.
+ * Everything else takes the route it takes with the option off; options 6 and 7 select exactly what they selected.
+ *   - Bit for bit: d_grad_unary, d_grad_weights and the Q left behind are section 1j's; every d_grad_features[k] (rows at or beyond a
+ *     frame's n_points written +0, a frame of 0 points all zeros) is that of the option off -- g_b and g_n keep one owner, the lane
+ *     that owns the point, and section 1d's order of additions (t = T .. 1, slice side then splat side, the norm part last).
+ *   - Memory: the area of sections 1d / 2d, nothing more.  The kernel initialises g_b and g_n itself.
+ *   - Argument checks, LCCRF_E_STATE, LCCRF_E_NOMEM and "a rejected call leaves the object as it was": the route is chosen where
+ *     section 1j's is.  lccrf_get_backward_route / lccrf_batch_get_backward_route report LCCRF_BACKWARD_FUSED.
+ * Added WITHOUT a step of LCCRF_ABI_VERSION.  Not covered: feature gradients in the compat form, normalisation modes (the API refuses
+ * feature gradients there), frames of 2049 points and more, the half-CU shapes.
  * ==================================================================================== */
 typedef enum lccrf_backward_route {
     LCCRF_BACKWARD_NONE   = 0,   /* no backward call yet */
@@ -856,7 +888,8 @@ int  lccrf_batch_get_backward_route(lccrf_batch_handle b, int *route);
  *     and everything else is section 2c's contract (streams, state, errors, what is needed beforehand).  The feature arrays the
  *     batch was given (lccrf_batch_bind_inputs_device: the caller's own) are read again by this call.
  *     Memory: section 2c's area plus 4 * F * sum over the terms asked for of P4 * (d_k + 2) bytes, P4 = max_points rounded up to
- *     a multiple of 4 (plus 4 * F * max_points * L when d_grad_unary is NULL).  Added without a step of LCCRF_ABI_VERSION.         */
+ *     a multiple of 4 (plus 4 * F * max_points * L when d_grad_unary is NULL).  Added without a step of LCCRF_ABI_VERSION.
+ *     In ONE launch under LCCRF_OPT_FUSED_BACKWARD_FEATURES (section 1l): the same bits, decided once for the batch.               */
 int  lccrf_batch_inference_backward_features(lccrf_batch_handle b, int n_iterations, float relax, const float *d_grad_prob,
                                              float *d_grad_unary, float *d_grad_weights, float *const *d_grad_features, void *stream);
 

@@ -28,6 +28,7 @@ OPT_VERTEX_ORDER = 2
 OPT_FRAME_GENERAL = 5           # a learnt model (matrices, normalisation modes) may take the one-launch route of a fresh frame
 OPT_FUSED_BACKWARD = 6          # gradients of tracker-sized two-label frames in one launch (include/lccrf.h section 1j)
 OPT_FUSED_BACKWARD_LEARNT = 7   # ... of learnt models (matrices, normalisation modes) and dL/dmu (include/lccrf.h section 1k)
+OPT_FUSED_BACKWARD_FEATURES = 8 # ... with feature gradients on Potts terms normalised AFTER (include/lccrf.h section 1l)
 BACKWARD_NONE, BACKWARD_STREAM, BACKWARD_FUSED = 0, 1, 2   # lccrf_backward_route
 IMAGE_NONE, IMAGE_U8, IMAGE_F32 = 0, 1, 2   # lccrf_add_image_kernel's image formats
 NORMALIZE_AFTER, NORMALIZE_BEFORE, NORMALIZE_SYMMETRIC, NORMALIZE_NONE = 0, 1, 2, 3   # lccrf_normalization (section 1g)
@@ -588,6 +589,7 @@ class BatchCRF(_Handle):
     OPT_FRAME_GENERAL = 5
     OPT_FUSED_BACKWARD = 6
     OPT_FUSED_BACKWARD_LEARNT = 7
+    OPT_FUSED_BACKWARD_FEATURES = 8
 
     def set_inputs_host_async(self, n_points, features, unary=None, label=None, conf=None, pinned=False):
         """lccrf_batch_set_inputs_host_async: the arrays are staged and uploaded without a host wait.  The arrays must already be

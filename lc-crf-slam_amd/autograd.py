@@ -393,7 +393,7 @@ class _MeanFieldFeatures(torch.autograd.Function):
     (lccrf_create re-uses parked handles), which the backward closes"""
 
     @staticmethod
-    def forward(ctx, unary, weights, compat, n_iterations, relax, device, *features):
+    def forward(ctx, unary, weights, compat, n_iterations, relax, device, fused_backward, route_out, *features):
         _check_unary_weights(unary, None, weights, len(features))
         N, L = (int(x) for x in unary.shape)
         for f in features:
@@ -403,6 +403,9 @@ class _MeanFieldFeatures(torch.autograd.Function):
         u = unary.detach().contiguous()
         fs = [f.detach().contiguous() for f in features]
         crf = _pkg.DenseCRFHIP(N, L, device=device)
+        if fused_backward:                                    # (lccrf_create hands out handles with fresh options: nothing leaks)
+            crf.set_option(_pkg.OPT_FUSED_BACKWARD_FEATURES, 1)
+        ctx.route_out = route_out
         with _on_stream(crf.stream(), u.device) as (ext, cur):
             crf.set_unary_device(u.data_ptr())
             for f, w in zip(fs, weights.detach().cpu().tolist()):
@@ -424,25 +427,29 @@ class _MeanFieldFeatures(torch.autograd.Function):
         g = _grad_in(grad_q, dev)
         grad_u = torch.empty_like(u)
         grad_w, grad_w_ptr, grad_m = _grad_buffers(K, int(u.shape[1]), dev, ctx.compat_device is not None)
-        grad_f = [torch.empty_like(f) if ctx.needs_input_grad[6 + k] else None for k, f in enumerate(fs)]
+        grad_f = [torch.empty_like(f) if ctx.needs_input_grad[8 + k] else None for k, f in enumerate(fs)]
         with _on_stream(crf.stream(), dev):                   # (the handle still holds this forward's unary, weights and matrices)
             # (without d_grad_compat, on a handle without matrices, the request is lccrf_inference_backward_features', section 1d)
             crf.inference_backward_all_device(ctx.n_iterations, ctx.relax, g.data_ptr(), grad_u.data_ptr(), grad_w_ptr,
                                               [t.data_ptr() if t is not None else None for t in grad_f],
                                               None if grad_m is None else grad_m.data_ptr())
         crf.synchronize()                                     # (the handle goes back to the cache: nothing of this call may be in flight)
+        if isinstance(ctx.route_out, list):
+            ctx.route_out.append(crf.backward_route())
         crf.close()
         ctx.target = None
-        return (grad_u,) + _model_grads(ctx, grad_w, grad_m, K) + (None, None, None) + tuple(grad_f)
+        return (grad_u,) + _model_grads(ctx, grad_w, grad_m, K) + (None, None, None, None, None) + tuple(grad_f)
 
 
-def mean_field_features(unary, features, weights, n_iterations=5, relax=1.0, device=0):
+def mean_field_features(unary, features, weights, n_iterations=5, relax=1.0, device=0, fused_backward=False, route_out=None):
     """Q_T of DenseCRF::inference(n_iterations, relax) with unary energies `unary` [N, L] (float32, GPU), pairwise terms over
     `features` (a list of [N, d_k] float32 GPU tensors, already divided by the kernels' standard deviations) and their weights
     `weights` [K] (float32, any device); differentiable in all three.  The feature gradient is the exact derivative of the lattice
     filter inside the simplices the points sit in (include/lccrf.h section 1d).  Every forward builds the lattices afresh on a
-    handle of its own, which its backward closes: one backward per forward."""
-    return _MeanFieldFeatures.apply(unary, weights, None, n_iterations, relax, device, *features)
+    handle of its own, which its backward closes: one backward per forward.  fused_backward: sets OPT_FUSED_BACKWARD_FEATURES on that
+    handle -- the gradients of a frame the fused plan takes, dL/d features included, run in one launch with the same bits
+    (include/lccrf.h section 1l).  route_out: a list to which the backward appends the handle's backward_route() before it closes it."""
+    return _MeanFieldFeatures.apply(unary, weights, None, n_iterations, relax, device, fused_backward, route_out, *features)
 
 
 def mean_field_learned(unary, features, weights, compat, n_iterations=5, relax=1.0, device=0):
@@ -450,7 +457,7 @@ def mean_field_learned(unary, features, weights, compat, n_iterations=5, relax=1
     any device), term k adding w_k * norm_k * (Phi_k(Q) @ compat[k].T); differentiable in unary, features, weights and compat, all
     four from one reverse sweep.  Every forward builds the lattices afresh on a handle of its own, which its backward closes: one
     backward per forward."""
-    return _MeanFieldFeatures.apply(unary, weights, compat, n_iterations, relax, device, *features)
+    return _MeanFieldFeatures.apply(unary, weights, compat, n_iterations, relax, device, False, None, *features)
 
 
 class LearnedKernelCRF(torch.nn.Module):
@@ -460,9 +467,10 @@ class LearnedKernelCRF(torch.nn.Module):
     deviations -- one value per feature column, or one per group with `groups` (per term a list of column-index lists, e.g.
     [[0, 1], [2, 3, 4]] so that (x, y) share posdev and (r, g, b) share featuredev; None: every column its own).  The parameters
     are log_sd[k] (one value per group) and weights; forward(unary [N, L]) forms raw * exp(-log_sd) and calls mean_field_features,
-    so autograd carries dL/d features to the bandwidths."""
+    so autograd carries dL/d features to the bandwidths.  fused_backward: passed on to mean_field_features (include/lccrf.h section
+    1l: the same bits in one launch); backward_route is the route of the last backward (BACKWARD_NONE before any)."""
 
-    def __init__(self, raw_features, sd, weights, groups=None, n_iterations=5, relax=1.0, device=0):
+    def __init__(self, raw_features, sd, weights, groups=None, n_iterations=5, relax=1.0, device=0, fused_backward=False):
         super().__init__()
         if not (len(raw_features) == len(sd) == len(weights)):
             raise ValueError("one list of standard deviations and one weight per feature array")
@@ -484,6 +492,12 @@ class LearnedKernelCRF(torch.nn.Module):
             self.log_sd.append(torch.nn.Parameter(torch.tensor(np.log(s), dtype=torch.float32, device=dev)))
         self.weights = _weights_parameter(weights)
         self.n_iterations, self.relax, self.device = int(n_iterations), float(relax), int(device)
+        self.fused_backward = bool(fused_backward)
+        self._routes = []                                     # what the backwards of this layer's forwards reported
+
+    @property
+    def backward_route(self):
+        return self._routes[-1] if self._routes else _pkg.BACKWARD_NONE
 
     def features(self):
         """the features the CRF sees: raw / sd, column by column"""
@@ -493,7 +507,9 @@ class LearnedKernelCRF(torch.nn.Module):
         return [torch.exp(ls.detach()).cpu().numpy() for ls in self.log_sd]
 
     def forward(self, unary):
-        return mean_field_features(unary, self.features(), self.weights, self.n_iterations, self.relax, self.device)
+        del self._routes[:-1]
+        return mean_field_features(unary, self.features(), self.weights, self.n_iterations, self.relax, self.device,
+                                   fused_backward=self.fused_backward, route_out=self._routes)
 
 
 class LearnedCRF(LearnedKernelCRF):

@@ -37,6 +37,7 @@ int lccrf::apply_option(Engine &e, int option, int value)
     case LCCRF_OPT_FRAME_GENERAL: e.opt.frame_general = value != 0; return LCCRF_OK;    // (takes effect with the next inference / run)
     case LCCRF_OPT_FUSED_BACKWARD: e.opt.fused_backward = value != 0; return LCCRF_OK;  // (takes effect with the next backward call)
     case LCCRF_OPT_FUSED_BACKWARD_LEARNT: e.opt.fused_backward_learnt = value != 0; return LCCRF_OK;   // (the next backward call)
+    case LCCRF_OPT_FUSED_BACKWARD_FEATURES: e.opt.fused_backward_features = value != 0; return LCCRF_OK;   // (the next backward call)
     case LCCRF_OPT_VERTEX_ORDER:                                                         // (takes effect with the next build)
         if (value < 0 || value > 2) return fail(LCCRF_E_INVALID, "LCCRF_OPT_VERTEX_ORDER takes 0 (automatic), 1 (on) or 2 (off)");
         e.opt.vertex_order = value;

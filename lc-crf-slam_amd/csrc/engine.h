@@ -420,6 +420,12 @@ struct TermModel;
 // rq.grad_model are the caller's to launch.  Returns fused_report() of the shape launched, or 0 with nothing launched.
 int launch_fused_backward_general(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, int rows,
                                   const BackwardRequest &rq, const BackwardArea &ar, const TermModel &terms, hipStream_t s);
+// ... and of a request WITH feature gradients (csrc/fused_backward_features.hip; include/lccrf.h section 1l): Potts terms normalised
+// AFTER, rq.T >= 1, no compat form, at least one array in rq.grad_features.  Writes what launch_fused_backward writes and
+// rq.grad_features (rows [n_points[f], rows) written 0), bit for bit what launch_backward_sweep would have; ar.gb / ar.gn need no zeroing
+// (the kernel's first iteration writes them).  Returns fused_report() of the shape launched, or 0 with nothing launched.
+int launch_fused_backward_features(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, int rows,
+                                   const BackwardRequest &rq, const BackwardArea &ar, hipStream_t s);
 // out[j] = sum over the frames, in ascending order, of x[f][j], j < n (section 2h; meanfield_backward.hip)
 void launch_sum_frames(const float *x, int F, int n, float *out, hipStream_t s);
 

@@ -1,6 +1,7 @@
-// fused_backward_common.h -- what the two one-launch backward kernels share: k_backward (fused_backward.hip: Potts terms normalised
-// AFTER) and k_backward_general (fused_backward_general.hip: learnt models and dL/dmu).  Device functions and the sizes of the LDS both
-// kernels keep behind the loop's plan; each kernel lives in a unit of its own.
+// fused_backward_common.h -- what the one-launch backward kernels share: k_backward (fused_backward.hip: Potts terms normalised
+// AFTER), k_backward_general (fused_backward_general.hip: learnt models and dL/dmu) and k_backward_features
+// (fused_backward_features.hip: with feature gradients).  Device functions and the sizes of the LDS the kernels keep behind the loop's
+// plan; each kernel lives in a unit of its own.
 #pragma once
 
 #include "engine.h"
@@ -50,6 +51,23 @@ __device__ __forceinline__ float2 slice_signed(const unsigned char *smem, const 
     t0 += w0 * x0.x; t1 += w0 * x0.y;
     t0 += w1 * x1.x; t1 += w1 * x1.y;
     t0 += w2 * x2.x; t1 += w2 * x2.y;
+    return make_float2(t0, t1);
+}
+
+// ... which also hands out the three gathered vertex values x[c] (before alpha): what k_corner_dot dots a row with (k_backward_features)
+template <int PPT, int K>
+__device__ __forceinline__ float2 slice_signed_corners(const unsigned char *smem, const fl::FusedLayout &lay, const fl::PointRegs<PPT, K> &pr,
+                                                       int s, int k, float alpha, float2 (&x)[fl::kD1])
+{
+    const float2 *val = reinterpret_cast<const float2 *>(smem + lay.val[k][fl::kD1 & 1]);
+    x[0] = val[pr.ix[s][k][0] & 0xffffu];
+    x[1] = val[pr.ix[s][k][0] >> 16];
+    x[2] = val[pr.ix[s][k][1] & 0xffffu];
+    const float w0 = pr.bary[s][k][0] * alpha, w1 = pr.bary[s][k][1] * alpha, w2 = pr.bary[s][k][2] * alpha;
+    float t0 = 0.0f, t1 = 0.0f;
+    t0 += w0 * x[0].x; t1 += w0 * x[0].y;
+    t0 += w1 * x[1].x; t1 += w1 * x[1].y;
+    t0 += w2 * x[2].x; t1 += w2 * x[2].y;
     return make_float2(t0, t1);
 }
 

@@ -236,6 +236,7 @@ struct Engine {
         bool frame_general = false;    // LCCRF_OPT_FRAME_GENERAL: terms with a matrix or a mode may take the one-launch route (frame_general.hip)
         bool fused_backward = false;   // LCCRF_OPT_FUSED_BACKWARD: dL/dU and dL/dw of frames the fused plan takes run in one launch (fused_backward.hip)
         bool fused_backward_learnt = false;   // LCCRF_OPT_FUSED_BACKWARD_LEARNT: the same for learnt models and dL/dmu (fused_backward_general.hip)
+        bool fused_backward_features = false; // LCCRF_OPT_FUSED_BACKWARD_FEATURES: the same with feature gradients (fused_backward_features.hip)
         int vertex_order = 0;          // LCCRF_OPT_VERTEX_ORDER: 0 automatic (= on), 1 on, 2 off -- locality mode's sorted build
         bool event_timing = true;      // LCCRF_OPT_EVENT_TIMING: HIP events around every build / inference / run of the batch API
         static Options fresh() { Options o; o.single_wg = default_single_wg(); o.frame_general = default_frame_general(); return o; }

@@ -60,8 +60,10 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
     // LCCRF_OPT_FUSED_BACKWARD (include/lccrf.h section 1j): dL/dU and / or dL/dw of Potts terms normalised AFTER, on frames the fused
     // plan takes -- the replay and the sweep in one launch, the same bits (fused_backward.hip).  Decided for the whole batch, over its
     // largest frame and lattices; behind every check and the area, so a rejected call leaves the handle as it was either way.
-    bool dU_dw_only = !rq.compat_form && !rq.grad_compat && !rq.grad_model;
-    for (int k = 0; k < K && rq.grad_features; ++k) dU_dw_only &= rq.grad_features[k] == nullptr;
+    const bool plain_form = !rq.compat_form && !rq.grad_compat && !rq.grad_model;   // (not the compat form: no dL/dmu, no sums, no matrix)
+    bool no_features = true;
+    for (int k = 0; k < K && rq.grad_features; ++k) no_features &= rq.grad_features[k] == nullptr;
+    const bool dU_dw_only = plain_form && no_features;
     if (opt.fused_backward && dU_dw_only && count && !model.general() && !perm_on &&
         launch_fused_backward(crf, kdevs.data(), maxV.data(), maxRow.data(), rows, rq, ar, stream)) {
         HIP_TRY(hipGetLastError());
@@ -71,14 +73,21 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
     // LCCRF_OPT_FUSED_BACKWARD_LEARNT (section 1k): the complement among the requests without feature gradients -- a learnt model
     // (a matrix, or a mode other than AFTER), or the compat form (dL/dmu, also of Potts terms) -- decided in the same place and the
     // same way (fused_backward_general.hip).  The sums over the frames (section 2h) are the sweep's two launches, behind the kernel.
-    bool no_features = true;
-    for (int k = 0; k < K && rq.grad_features; ++k) no_features &= rq.grad_features[k] == nullptr;
     if (opt.fused_backward_learnt && no_features && count && (model.general() || rq.compat_form) && !perm_on &&
         launch_fused_backward_general(crf, step_kdevs(), maxV.data(), maxRow.data(), rows, rq, ar, model.terms((size_t)K), stream)) {
         if (rq.grad_model) {
             launch_sum_frames(rq.grad_weights ? rq.grad_weights : ar.gW, F, K, rq.grad_model, stream);
             launch_sum_frames(rq.grad_compat ? rq.grad_compat : ar.gC, F, K * L * L, rq.grad_model + K, stream);
         }
+        HIP_TRY(hipGetLastError());
+        report.backward(LCCRF_BACKWARD_FUSED);
+        return LCCRF_OK;
+    }
+    // LCCRF_OPT_FUSED_BACKWARD_FEATURES (section 1l): a request with at least one feature array, not in the compat form, on Potts terms
+    // normalised AFTER and T >= 1 (T = 0 streams: the memset below to exactly 0 is already right) -- decided in the same place and the
+    // same way (fused_backward_features.hip).  The kernel initialises the area's gb / gn itself: no memset in front of it.
+    if (opt.fused_backward_features && !no_features && plain_form && count && T >= 1 && !model.general() && !perm_on &&
+        launch_fused_backward_features(crf, kdevs.data(), maxV.data(), maxRow.data(), rows, rq, ar, stream)) {
         HIP_TRY(hipGetLastError());
         report.backward(LCCRF_BACKWARD_FUSED);
         return LCCRF_OK;
