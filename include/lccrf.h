@@ -503,7 +503,7 @@ int  lccrf_inference_backward_all(lccrf_handle h, int n_iterations, float relax,
  * Determinism, memory and the contracts "self-contained" and "Q afterwards as lccrf_inference leaves it" are those of sections 1c
  * and 1e.  NOT differentiated: s and n with respect to the features -- lccrf_inference_backward_features, and
  * lccrf_inference_backward_all with a non-NULL d_grad_features, return LCCRF_E_STATE on a handle with any term that is not AFTER and
- * leave the handle as it was.
+ * leave the handle as it was.  Section 1m's lccrf_inference_backward_modes differentiates them (section 2i for a batch).
  *
  * The C++ mirror lccrf_densecrf.hpp sets a mode per potential (PottsPotentialHIP::setNormalization).  The batch API has the same
  * setter, one mode per term shared by every frame (section 2g); the gradients of such a batch are section 2h's (sections 2c and 2d
@@ -666,6 +666,49 @@ typedef enum lccrf_backward_route {
     LCCRF_BACKWARD_FUSED  = 2    /* one launch */
 } lccrf_backward_route;
 int  lccrf_get_backward_route(lccrf_handle h, int *route);
+
+/* ======================================================================================
+ * 1m. Feature gradients under EVERY normalisation mode -- section 1f's call without section 1g's refusal: the factors a mode puts
+ *     in front of and behind the filter are functions of the norm, and the norm of the features; here they are differentiated too
+ *     (lc-crf-slam_amd/autograd.py: mean_field_features, mean_field_learned, LearnedKernelCRF and LearnedCRF take `normalization`).
+ *     Added WITHOUT a step of LCCRF_ABI_VERSION (it stays 3): probe for it by symbol.  lccrf_inference_backward_features and
+ *     lccrf_inference_backward_all are unchanged and keep refusing a handle with a term that is not AFTER.
+ *
+ * The gradients of lccrf_inference(h, n_iterations, -, relax) on the handle's current unary, terms, matrices and modes.  With section
+ * 1g's a_k (the factor behind the filter) and b_k (the factor in front of it), each 1 where the mode has none, s = sqrtf(n) as the
+ * handle stores it, and per iteration t = T .. 1 and term k
+ *      x = b_k . Q_{t-1}                  rounded once: the forward's own splat input (Q_{t-1} itself without a pre factor)
+ *      y = a_k . (mu_k^T gamma_t)         (a_k . gamma_t for a Potts term)
+ *      z = Phi_k^T(y)                     the sliced result of the transposed filter, before it is multiplied by b_k
+ * dL/dU, dL/dw_k, dL/dmu_k and G_{t-1} are section 1g's, and for every term with a feature array:
+ *      filter part    g_b[k][i][c] += alpha_k w_k (<y_i, (B S x)[v_ic]> + <x_i, (B^T S y)[v_ic]>)
+ *      post adjoint   g_post[k][i] += w_k <gamma_t,i, (mu_k Phi_k(x))_i>         = dL/da_k[i]; terms with a post factor only
+ *      pre adjoint    g_pre[k][i]  += w_k <Q_{t-1},i, z_i>                       = dL/db_k[i]; terms with a pre factor only
+ * every dot over the labels added in the order 0 .. L-1; within an iteration the post part is added before the pre part.  Then
+ *      AFTER       g_n = g_post                               (a = n)
+ *      BEFORE      g_n = g_pre                                (b = n)
+ *      SYMMETRIC   g_n = (g_post + g_pre) * (0.5f / s[i])     (a = b = s, ds/dn = 1 / (2 s); both adjoints in ONE accumulator)
+ *      NONE        no norm part: the filter part alone
+ * and a_n = -n_k^2 . g_n (n_k the true norm, lccrf_get_norm's), g_b[k][i][c] += alpha_k (a_n,i (B S 1)[v_ic] + (B^T S a_n)[v_ic]) and the
+ * map from dL/db to dL/df are section 1d's, unchanged.  At n_iterations = 0 dL/df is exactly 0.
+ *
+ * Arguments, checks (before anything is enqueued), errors (LCCRF_E_INVALID; LCCRF_E_STATE without unary energies; LCCRF_E_NOMEM),
+ * stream and memory rules are lccrf_inference_backward_all's; a rejected call leaves the handle as it was.
+ *   - Every term AFTER, or d_grad_features == NULL: the call IS lccrf_inference_backward_all -- the same bits in every output and
+ *     the same route, the one-launch routes of sections 1j - 1l included.
+ *   - A term that is not AFTER and at least one non-NULL entry of d_grad_features: the streaming sweep, whatever
+ *     LCCRF_OPT_FUSED_BACKWARD* options are set (lccrf_get_backward_route: LCCRF_BACKWARD_STREAM).  d_grad_unary, d_grad_weights and
+ *     d_grad_compat receive, bit for bit, what lccrf_inference_backward_all gives on the same handle with d_grad_features == NULL.
+ *     A NULL entry of d_grad_features skips that term's feature work; the other outputs keep their bits.
+ *   - Deterministic: no float atomics.  g_b keeps section 1d's owner and order (t = T .. 1, slice side, splat side, the norm part
+ *     last); the one accumulator of g_post and g_pre is owned by its point: the same bits from run to run.
+ *   - Handles in locality mode (8192 points and more) are re-built the plain way, as in section 1c; results in the caller's order.
+ *   - Launches: those of section 1f.  The pre adjoint rides in the kernel that forms G_{t-1} (a row-wise form of it: not a launch
+ *     more); the splat-side corner dot multiplies its row by b_k as it loads it; a NONE term saves the norm part's two width-1
+ *     filters, two corner dots and one per-point kernel.
+ *   - Memory: section 1f's area, not a byte more (g_n is the one accumulator), plus section 1g's factor arrays.                  */
+int  lccrf_inference_backward_modes(lccrf_handle h, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
+                                    float *d_grad_weights, float *const *d_grad_features, float *d_grad_compat);
 
 /* ======================================================================================
  * 2. Batch API -- many independent frames in flight on one GPU.
@@ -1020,6 +1063,23 @@ int  lccrf_batch_get_pairwise_normalization(lccrf_batch_handle b, int kernel, in
 int  lccrf_batch_inference_backward_all(lccrf_batch_handle b, int n_iterations, float relax, const float *d_grad_prob,
                                         float *d_grad_unary, float *d_grad_weights, float *const *d_grad_features, float *d_grad_compat,
                                         float *d_grad_model, void *stream);
+
+/* ======================================================================================
+ * 2i. Section 1m for every frame of a batch at once: section 2h's call without its refusal of feature gradients on a batch with a
+ *     term that is not normalised AFTER.  Added WITHOUT a step of LCCRF_ABI_VERSION (it stays 3): probe for it by symbol.
+ *     lccrf_batch_inference_backward_features and lccrf_batch_inference_backward_all are unchanged and keep refusing.
+ *
+ * Arguments, outputs, checks, errors, stream rules, timing and memory are lccrf_batch_inference_backward_all's.
+ *   - Every term AFTER, or d_grad_features == NULL: the call IS lccrf_batch_inference_backward_all (same bits, same route).
+ *   - Otherwise the streaming sweep of section 1m over all frames (lccrf_batch_get_backward_route: LCCRF_BACKWARD_STREAM under every
+ *     option): every frame's d_grad_unary[f], d_grad_weights[f], d_grad_features[k][f] and d_grad_compat[f] are, bit for bit, what
+ *     lccrf_inference_backward_modes returns for a handle holding frame f; rows at or beyond n_points[f] are written 0, a frame of 0
+ *     points gets zeros; d_grad_model is section 2h's sum, with section 2h's bits.
+ *   - Launches and memory: those of section 2h with feature arrays, as section 1m's are those of section 1f.
+ * ==================================================================================== */
+int  lccrf_batch_inference_backward_modes(lccrf_batch_handle b, int n_iterations, float relax, const float *d_grad_prob,
+                                          float *d_grad_unary, float *d_grad_weights, float *const *d_grad_features, float *d_grad_compat,
+                                          float *d_grad_model, void *stream);
 
 /* ======================================================================================
  * 3. Unary builder -- the step right before the CRF (first "next" row):

@@ -157,6 +157,7 @@ def lib():
     L.lccrf_get_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p, C.POINTER(C.c_int)]
     L.lccrf_inference_backward_compat.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, vp]
     L.lccrf_inference_backward_all.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, C.POINTER(vp), vp]
+    L.lccrf_inference_backward_modes.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, C.POINTER(vp), vp]
     L.lccrf_set_pairwise_normalization.argtypes = [vp, C.c_int, C.c_int]
     L.lccrf_get_pairwise_normalization.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
     L.lccrf_batch_create.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(BatchDesc)]
@@ -197,6 +198,7 @@ def lib():
     L.lccrf_batch_inference_backward.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, vp]
     L.lccrf_batch_inference_backward_features.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, C.POINTER(vp), vp]
     L.lccrf_batch_inference_backward_all.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, C.POINTER(vp), vp, vp, vp]
+    L.lccrf_batch_inference_backward_modes.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, C.POINTER(vp), vp, vp, vp]
     L.lccrf_batch_set_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p]
     L.lccrf_batch_get_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p, C.POINTER(C.c_int)]
     L.lccrf_batch_set_pairwise_normalization.argtypes = [vp, C.c_int, C.c_int]
@@ -502,6 +504,14 @@ class DenseCRFHIP(_Handle):
         _check(lib().lccrf_inference_backward_all(self.h, int(n_iterations), float(relax), _addr(d_grad_prob), _addr(d_grad_unary),
                                                   _addr(d_grad_weights), _addr_list(d_grad_features), _addr(d_grad_compat)))
 
+    # -- ... and under every normalisation mode (include/lccrf.h section 1m) ------------------------------------------------------
+    def inference_backward_modes_device(self, n_iterations, relax, d_grad_prob, d_grad_unary=None, d_grad_weights=None,
+                                        d_grad_features=None, d_grad_compat=None):
+        """inference_backward_all_device without its refusal of feature gradients on a handle with a term that is not normalised
+        AFTER: the norm's factors are differentiated in the features too.  With every term AFTER it is that call."""
+        _check(lib().lccrf_inference_backward_modes(self.h, int(n_iterations), float(relax), _addr(d_grad_prob), _addr(d_grad_unary),
+                                                    _addr(d_grad_weights), _addr_list(d_grad_features), _addr(d_grad_compat)))
+
     # -- results -----------------------------------------------------------------------
     def map(self):
         out = np.empty(self.N, np.int16)
@@ -715,6 +725,14 @@ class BatchCRF(_Handle):
         _check(lib().lccrf_batch_inference_backward_all(self.h, int(n_iterations), float(relax), C.c_void_p(int(d_grad_prob)),
                                                         _addr(d_grad_unary), _addr(d_grad_weights), _addr_list(d_grad_features),
                                                         _addr(d_grad_compat), _addr(d_grad_model), _addr(stream)))
+
+    def inference_backward_modes_device(self, n_iterations, relax, d_grad_prob, d_grad_unary=None, d_grad_weights=None,
+                                        d_grad_features=None, d_grad_compat=None, d_grad_model=None, stream=None):
+        """inference_backward_all_device with the feature gradients of terms in any normalisation mode (include/lccrf.h section 2i);
+        with every term AFTER it is that call."""
+        _check(lib().lccrf_batch_inference_backward_modes(self.h, int(n_iterations), float(relax), C.c_void_p(int(d_grad_prob)),
+                                                          _addr(d_grad_unary), _addr(d_grad_weights), _addr_list(d_grad_features),
+                                                          _addr(d_grad_compat), _addr(d_grad_model), _addr(stream)))
 
     pairwise_compatibility, normalization = _Handle.get_pairwise_compatibility, _Handle.get_normalization   # (the batch's own names)
 

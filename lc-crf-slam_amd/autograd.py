@@ -1,4 +1,4 @@
-"""torch autograd through DenseCRF::inference on the HIP path (include/lccrf.h sections 1c - 1f and 2c).
+"""torch autograd through DenseCRF::inference on the HIP path (include/lccrf.h sections 1c - 1g, 1m and 2c).
 
     Q = mean_field(crf, unary, weights, n_iterations=5, relax=1.0)
     Q.backward(g)      # -> unary.grad = dL/dU, weights.grad = dL/dw
@@ -17,6 +17,9 @@
 
     Q = mean_field_learned(unary, [f_0, f_1, ..], weights, compat, n_iterations=5, relax=1.0)   # features and matrices together
     Q.backward(g)      # -> unary.grad, weights.grad, f_k.grad and compat.grad from one sweep (section 1f); LearnedCRF learns both
+
+    Q = mean_field_features_modes(unary, [f_0, ..], weights, NORMALIZE_SYMMETRIC, n_iterations=5)   # ... under a normalisation mode
+    Q.backward(g)      # -> f_k.grad through the norm's factors too (section 1m); mean_field_learned_modes: with matrices
 
 `crf` is a DenseCRFHIP whose pairwise terms are already added (their features fix the lattices; only the weights are
 inputs here).  Forward: lccrf_set_pairwise_weight + lccrf_set_unary_device + lccrf_inference.  Backward:
@@ -393,7 +396,7 @@ class _MeanFieldFeatures(torch.autograd.Function):
     (lccrf_create re-uses parked handles), which the backward closes"""
 
     @staticmethod
-    def forward(ctx, unary, weights, compat, n_iterations, relax, device, fused_backward, route_out, *features):
+    def forward(ctx, unary, weights, compat, n_iterations, relax, device, fused_backward, route_out, normalization, *features):
         _check_unary_weights(unary, None, weights, len(features))
         N, L = (int(x) for x in unary.shape)
         for f in features:
@@ -406,10 +409,15 @@ class _MeanFieldFeatures(torch.autograd.Function):
         if fused_backward:                                    # (lccrf_create hands out handles with fresh options: nothing leaks)
             crf.set_option(_pkg.OPT_FUSED_BACKWARD_FEATURES, 1)
         ctx.route_out = route_out
+        # (include/lccrf.h sections 1g and 1m: a term that is not AFTER sends the backward to lccrf_inference_backward_modes)
+        modes = _modes(normalization, len(features))
+        ctx.any_mode = any(mode != _pkg.NORMALIZE_AFTER for mode in modes)
         with _on_stream(crf.stream(), u.device) as (ext, cur):
             crf.set_unary_device(u.data_ptr())
             for f, w in zip(fs, weights.detach().cpu().tolist()):
                 crf.add_pairwise_device(f.data_ptr(), int(f.shape[1]), w)
+            for k, mode in enumerate(modes if ctx.any_mode else []):
+                crf.set_normalization(k, mode)
             _set_matrices(crf, compat)
             q = _forward_q(crf, u, n_iterations, relax, ext, cur)
         _remember(ctx, crf, n_iterations, relax, weights, compat)
@@ -427,18 +435,18 @@ class _MeanFieldFeatures(torch.autograd.Function):
         g = _grad_in(grad_q, dev)
         grad_u = torch.empty_like(u)
         grad_w, grad_w_ptr, grad_m = _grad_buffers(K, int(u.shape[1]), dev, ctx.compat_device is not None)
-        grad_f = [torch.empty_like(f) if ctx.needs_input_grad[8 + k] else None for k, f in enumerate(fs)]
-        with _on_stream(crf.stream(), dev):                   # (the handle still holds this forward's unary, weights and matrices)
+        grad_f = [torch.empty_like(f) if ctx.needs_input_grad[9 + k] else None for k, f in enumerate(fs)]
+        with _on_stream(crf.stream(), dev):                   # (the handle still holds this forward's unary, weights, matrices and modes)
             # (without d_grad_compat, on a handle without matrices, the request is lccrf_inference_backward_features', section 1d)
-            crf.inference_backward_all_device(ctx.n_iterations, ctx.relax, g.data_ptr(), grad_u.data_ptr(), grad_w_ptr,
-                                              [t.data_ptr() if t is not None else None for t in grad_f],
-                                              None if grad_m is None else grad_m.data_ptr())
+            call = crf.inference_backward_modes_device if ctx.any_mode else crf.inference_backward_all_device
+            call(ctx.n_iterations, ctx.relax, g.data_ptr(), grad_u.data_ptr(), grad_w_ptr,
+                 [t.data_ptr() if t is not None else None for t in grad_f], None if grad_m is None else grad_m.data_ptr())
         crf.synchronize()                                     # (the handle goes back to the cache: nothing of this call may be in flight)
         if isinstance(ctx.route_out, list):
             ctx.route_out.append(crf.backward_route())
         crf.close()
         ctx.target = None
-        return (grad_u,) + _model_grads(ctx, grad_w, grad_m, K) + (None, None, None, None, None) + tuple(grad_f)
+        return (grad_u,) + _model_grads(ctx, grad_w, grad_m, K) + (None, None, None, None, None, None) + tuple(grad_f)
 
 
 def mean_field_features(unary, features, weights, n_iterations=5, relax=1.0, device=0, fused_backward=False, route_out=None):
@@ -449,7 +457,18 @@ def mean_field_features(unary, features, weights, n_iterations=5, relax=1.0, dev
     handle of its own, which its backward closes: one backward per forward.  fused_backward: sets OPT_FUSED_BACKWARD_FEATURES on that
     handle -- the gradients of a frame the fused plan takes, dL/d features included, run in one launch with the same bits
     (include/lccrf.h section 1l).  route_out: a list to which the backward appends the handle's backward_route() before it closes it."""
-    return _MeanFieldFeatures.apply(unary, weights, None, n_iterations, relax, device, fused_backward, route_out, *features)
+    return _MeanFieldFeatures.apply(unary, weights, None, n_iterations, relax, device, fused_backward, route_out, None, *features)
+
+
+def mean_field_features_modes(unary, features, weights, normalization, n_iterations=5, relax=1.0, device=0, fused_backward=False,
+                              route_out=None):
+    """mean_field_features under normalisation modes (include/lccrf.h sections 1g and 1m).  normalization: None (every term AFTER,
+    the reference's form), one of the package's NORMALIZE_* modes for every term, or one per term.  With a term that is not AFTER the
+    modes are set on the function's own handle before the forward and the backward is lccrf_inference_backward_modes: the norm's
+    factors are differentiated in the features too, on the streaming sweep.  With None or every term AFTER the call is
+    mean_field_features, bit for bit and route for route."""
+    return _MeanFieldFeatures.apply(unary, weights, None, n_iterations, relax, device, fused_backward, route_out, normalization,
+                                    *features)
 
 
 def mean_field_learned(unary, features, weights, compat, n_iterations=5, relax=1.0, device=0):
@@ -457,7 +476,13 @@ def mean_field_learned(unary, features, weights, compat, n_iterations=5, relax=1
     any device), term k adding w_k * norm_k * (Phi_k(Q) @ compat[k].T); differentiable in unary, features, weights and compat, all
     four from one reverse sweep.  Every forward builds the lattices afresh on a handle of its own, which its backward closes: one
     backward per forward."""
-    return _MeanFieldFeatures.apply(unary, weights, compat, n_iterations, relax, device, False, None, *features)
+    return _MeanFieldFeatures.apply(unary, weights, compat, n_iterations, relax, device, False, None, None, *features)
+
+
+def mean_field_learned_modes(unary, features, weights, compat, normalization, n_iterations=5, relax=1.0, device=0):
+    """mean_field_learned under normalisation modes: `normalization` as mean_field_features_modes takes it (include/lccrf.h sections
+    1g and 1m); with None or every term AFTER the call is mean_field_learned."""
+    return _MeanFieldFeatures.apply(unary, weights, compat, n_iterations, relax, device, False, None, normalization, *features)
 
 
 class LearnedKernelCRF(torch.nn.Module):
@@ -468,7 +493,10 @@ class LearnedKernelCRF(torch.nn.Module):
     [[0, 1], [2, 3, 4]] so that (x, y) share posdev and (r, g, b) share featuredev; None: every column its own).  The parameters
     are log_sd[k] (one value per group) and weights; forward(unary [N, L]) forms raw * exp(-log_sd) and calls mean_field_features,
     so autograd carries dL/d features to the bandwidths.  fused_backward: passed on to mean_field_features (include/lccrf.h section
-    1l: the same bits in one launch); backward_route is the route of the last backward (BACKWARD_NONE before any)."""
+    1l: the same bits in one launch); backward_route is the route of the last backward (BACKWARD_NONE before any).
+    The attribute `normalization` (None after construction: the reference's form) may be set to one NORMALIZE_* mode for every term,
+    or to one per term, with the meaning it has in MeanFieldCRF: the next forward runs under those modes and the bandwidths are learnt
+    through the norm's factors too (mean_field_features_modes; include/lccrf.h section 1m)."""
 
     def __init__(self, raw_features, sd, weights, groups=None, n_iterations=5, relax=1.0, device=0, fused_backward=False):
         super().__init__()
@@ -493,6 +521,7 @@ class LearnedKernelCRF(torch.nn.Module):
         self.weights = _weights_parameter(weights)
         self.n_iterations, self.relax, self.device = int(n_iterations), float(relax), int(device)
         self.fused_backward = bool(fused_backward)
+        self.normalization = None                             # None, one NORMALIZE_* mode for every term, or one per term (section 1m)
         self._routes = []                                     # what the backwards of this layer's forwards reported
 
     @property
@@ -508,18 +537,20 @@ class LearnedKernelCRF(torch.nn.Module):
 
     def forward(self, unary):
         del self._routes[:-1]
-        return mean_field_features(unary, self.features(), self.weights, self.n_iterations, self.relax, self.device,
-                                   fused_backward=self.fused_backward, route_out=self._routes)
+        return mean_field_features_modes(unary, self.features(), self.weights, self.normalization, self.n_iterations, self.relax,
+                                         self.device, fused_backward=self.fused_backward, route_out=self._routes)
 
 
 class LearnedCRF(LearnedKernelCRF):
     """LearnedKernelCRF whose terms also carry a learnt label-compatibility matrix: parameters log_sd[k], `weights` [K] and `compat`
     [K, n_labels, n_labels], the latter initialised to identities (the Potts model).  sd and groups as LearnedKernelCRF takes them.
-    forward(unary [N, n_labels]) -> Q [N, n_labels] through mean_field_learned."""
+    The attribute `normalization` as in LearnedKernelCRF.  forward(unary [N, n_labels]) -> Q [N, n_labels] through
+    mean_field_learned_modes (mean_field_learned while `normalization` is None)."""
 
     def __init__(self, raw_features, sd, weights, groups=None, n_labels=2, n_iterations=5, relax=1.0, device=0):
         super().__init__(raw_features, sd, weights, groups, n_iterations, relax, device)
         self.compat = _identities(len(weights), n_labels)
 
     def forward(self, unary):
-        return mean_field_learned(unary, self.features(), self.weights, self.compat, self.n_iterations, self.relax, self.device)
+        return mean_field_learned_modes(unary, self.features(), self.weights, self.compat, self.normalization, self.n_iterations,
+                                        self.relax, self.device)

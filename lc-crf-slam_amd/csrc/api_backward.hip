@@ -1,4 +1,4 @@
-// api_backward.hip -- gradients of mean-field inference: sections 1c - 1f (a handle) and 2c, 2d, 2h (a batch) of include/lccrf.h.
+// api_backward.hip -- gradients of mean-field inference: sections 1c - 1f, 1m (a handle) and 2c, 2d, 2h, 2i (a batch) of include/lccrf.h.
 //
 // One path behind every entry point (backward_call); the replay and the sweep themselves are Engine::backward (host_engine.hip) and
 // meanfield_backward.hip; the route getters of section 1j are in api_model.hip.
@@ -8,7 +8,7 @@
 
 using namespace lccrf;
 
-// Every backward entry point, of a handle (sections 1c - 1f) and of a batch (2c, 2d, 2h), fills a BackwardRequest (engine.h), says where
+// Every backward entry point, of a handle (sections 1c - 1f, 1m) and of a batch (2c, 2d, 2h, 2i), fills a BackwardRequest (engine.h), says where
 // it runs and what it allows, and calls backward_call.  A handle is a batch of one whose area has its own row stride.
 struct BackwardTarget {
     Engine &e;
@@ -173,6 +173,40 @@ int lccrf_batch_inference_backward_all(lccrf_batch_handle b, int n_iterations, f
     rq.grad_compat = d_grad_compat;
     rq.grad_model = d_grad_model;
     rq.compat_form = b->eng.model.n_compat > 0 || d_grad_compat || d_grad_model;   // (the sums hold dL/dmu: section 1e's form)
+    return backward_call(backward_target(b, stream), rq, kGradUnaryOptional);
+}
+
+// --------------------------------------------------------------------------------------
+// sections 1m and 2i: sections 1f and 2h with the feature gradients of terms in any normalisation mode.  The request is section
+// 1f's / 2h's; Engine::backward hands the sweep the modes when a term is not AFTER and a feature array is asked for, and that request
+// streams (no fused route takes feature gradients of a model with a mode).  Every other request IS the other call.
+
+int lccrf_inference_backward_modes(lccrf_handle h, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
+                                   float *d_grad_weights, float *const *d_grad_features, float *d_grad_compat)
+{
+    CHECK_H(h);
+    if (!d_grad_features || !h->eng.model.n_modes)
+        return lccrf_inference_backward_all(h, n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights, d_grad_features, d_grad_compat);
+    BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
+    rq.grad_features = d_grad_features;
+    rq.grad_compat = d_grad_compat;
+    rq.compat_form = h->eng.model.n_compat > 0 || d_grad_compat;
+    return backward_call(backward_target(h), rq, kGradUnaryOptional);
+}
+
+int lccrf_batch_inference_backward_modes(lccrf_batch_handle b, int n_iterations, float relax, const float *d_grad_prob, float *d_grad_unary,
+                                         float *d_grad_weights, float *const *d_grad_features, float *d_grad_compat, float *d_grad_model,
+                                         void *stream)
+{
+    CHECK_H(b);
+    if (!d_grad_features || !b->eng.model.n_modes)
+        return lccrf_batch_inference_backward_all(b, n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights, d_grad_features,
+                                                  d_grad_compat, d_grad_model, stream);
+    BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
+    rq.grad_features = d_grad_features;
+    rq.grad_compat = d_grad_compat;
+    rq.grad_model = d_grad_model;
+    rq.compat_form = b->eng.model.n_compat > 0 || d_grad_compat || d_grad_model;
     return backward_call(backward_target(b, stream), rq, kGradUnaryOptional);
 }
 

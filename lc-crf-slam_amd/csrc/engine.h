@@ -400,11 +400,19 @@ size_t backward_layout(const BackwardRequest &rq, const CrfDev &c, const KernelD
 // compat_form and grad_features together are section 1f: section 1e's form plus the launches section 1d adds.
 // pre (or null): as launch_step_stream takes it (section 1g) -- kds[k].norm is then a_k, the factor behind the filter, the forward
 // filters of the sweep scale their input rows by pre[k] = b_k, and k_bwd_combine multiplies the transposed filter's result by it.
-// Without grad_features only (the entry points refuse the combination).
+// With grad_features only together with `modes` (sections 1m / 2i; the other entry points refuse the combination).
+// modes (or null: every term AFTER): each term's lccrf_normalization and its TRUE norm n_k -- the feature part then differentiates the
+// factors too: the splat side's row is b_k . Q_{t-1}, k_bwd_combine_adjoint (in k_bwd_combine<true>'s place, the same bits in G) adds
+// the pre adjoint to ar.gn[k], and the norm part forms g_n by the term's mode (none for LCCRF_NORMALIZE_NONE).
 // rq.grad_model (section 2h; null for a handle: not a launch more): dL/dw and dL/dmu of every frame -- in the caller's arrays, or in
 // ar.gW / ar.gC where the caller left one out -- are summed over the frames in ascending order, one k_sum_frames launch each.
+struct BackwardModes {
+    int mode[LCCRF_MAX_KERNELS];
+    const float *norm[LCCRF_MAX_KERNELS];   // [F][maxN], KernelDev::norm of the engine's own views (not of step_kdevs())
+};
 void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int rows, const BackwardRequest &rq,
-                           const BackwardArea &ar, const float *const *compat, hipStream_t s, const float *const *pre = nullptr);
+                           const BackwardArea &ar, const float *const *compat, hipStream_t s, const float *const *pre = nullptr,
+                           const BackwardModes *modes = nullptr);
 // The replay AND the sweep of a request for dL/dU and / or dL/dw alone in ONE launch, a 1024-lane workgroup per frame
 // (csrc/fused_backward.hip; include/lccrf.h section 1j): two labels, Potts terms normalised AFTER on lattices in HBM that fit the fused
 // plan, frames of up to 2048 active points.  Reads rq.grad_prob itself (no copy into ar.G beforehand), keeps Q_0 .. Q_{T-1} in

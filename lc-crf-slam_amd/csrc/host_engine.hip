@@ -114,7 +114,11 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
             HIP_TRY(hipMemsetAsync(ar.gb[k], 0, ar.feat_floats[k] * sizeof(float), stream));
     }
     HIP_TRY(hipMemcpyAsync(ar.G, rq.grad_prob, count * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    launch_backward_sweep(crf, step_kdevs(), maxV.data(), rows, rq, ar, model.compat_arg(), stream, model.pre_arg());
+    // (sections 1m / 2i: feature gradients of terms that are not all AFTER -- the sweep is told the modes and the true norms)
+    BackwardModes bm{};
+    for (int k = 0; k < K; ++k) bm.mode[k] = model.mode(k), bm.norm[k] = kdevs[k].norm;
+    launch_backward_sweep(crf, step_kdevs(), maxV.data(), rows, rq, ar, model.compat_arg(), stream, model.pre_arg(),
+                          model.n_modes && !no_features ? &bm : nullptr);
     HIP_TRY(hipGetLastError());
     report.backward(LCCRF_BACKWARD_STREAM);
     return LCCRF_OK;

@@ -30,6 +30,12 @@
 // k_corner_dot runs after k_compat_bwd has turned phi_k into mu_k^T (n_k gamma_t) and before the transposed filter overwrites it; the
 // splat side runs on the transposed filter's values as before, and g_n is formed from mu_k Phi_k (k_joint_softmax<G>).
 //
+// Feature gradients under a normalisation mode (sections 1m and 2i; only with `modes`, i.e. a term that is not AFTER and a feature array):
+// the factors a_k (behind the filter: kds[k].norm) and b_k (in front of it: pre[k]) depend on the features through the norm.  The splat
+// side's row becomes b_k . Q_{t-1}; ar.gn[k] takes dL/da_k from the softmax kernel (terms with a post factor) and dL/db_k =
+// w_k <Q_{t-1}, Phi_k^T(y)> from k_bwd_combine_adjoint, which runs in k_bwd_combine<true>'s place (terms with a pre factor), in that
+// order; k_norm_adjoint turns the sum into dL/dn by the term's mode, with the TRUE norm.  Every other request launches what it launched.
+//
 // A batch's learnt model (section 2h): the compatibility part is per frame too -- k_compat_bwd cuts a frame's rows into the chunk count
 // of a handle of n_points[f] points, k_compat_reduce sums that frame's chunks in order into d_grad_compat[f] -- and k_sum_frames adds
 // dL/dw and dL/dmu over the frames in ascending order for the (global) model's gradient.
@@ -305,6 +311,60 @@ __global__ void __launch_bounds__(kBwdBlock) k_bwd_combine(const int *__restrict
     G[o] = acc;
 }
 
+// k_bwd_combine<true> by rows, with the pre adjoint of section 1m: a row (point) is G lanes as in k_softmax_bwd, lane c of the row holds
+// labels 4c .. 4c+3.  Per element the arithmetic of k_bwd_combine<true>, in its order (the same bits in G); and before buf_k = z_k is
+// scaled by b_k, for every term with an accumulator (adj.gn[k]: a BEFORE or SYMMETRIC term whose feature gradient is asked for)
+//   gn[k][i] += w_k * <Q_{t-1},i, z_k,i>        labels in order 0 .. L-1, one owner per point (the row's first lane)
+// -- dL/d b_k[i] of x = b_k . Q_{t-1}.  It runs behind this iteration's k_softmax_bwd, so the post part is added before the pre part.
+struct BwdPreAdjoint { float *gn[kBwdMaxK]; int gnstride; const float *q; };   // q: Q_{t-1}, [F][.][L] strided as G
+template <int G>
+__global__ void __launch_bounds__(kBwdBlock) k_bwd_combine_adjoint(const int *__restrict__ n_points, int L, int K, const float *__restrict__ buf,
+                                                                 size_t slice, size_t fs, BwdWeights wk, float keep, float *__restrict__ Gd,
+                                                                 BwdPre pre, BwdPreAdjoint adj)
+{
+    const int f = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int sub = lane % G, first = lane - sub;
+    const int i = blockIdx.x * (kBwdBlock / G) + (int)threadIdx.x / G;
+    const bool live = i < n_points[f];
+    const int l0 = sub * 4;
+    const size_t o = f * fs + (size_t)(live ? i : 0) * L + l0;
+    bool has[4];
+    float acc[4], q[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        has[u] = live && l0 + u < L;
+        acc[u] = has[u] ? keep * Gd[o + u] : 0.0f;
+        q[u] = has[u] ? adj.q[o + u] : 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < kBwdMaxK; ++k) {
+        if (k >= K) break;
+        float z[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) z[u] = has[u] ? buf[k * slice + o + u] : 0.0f;
+        if (adj.gn[k]) {                                    // (uniform: the shuffles of the row sum see every lane)
+            float v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = q[u] * z[u];
+            const float sk = row_sum_ordered<G>(v, L, first);
+            if (live && sub == 0) {
+                float *gp = adj.gn[k] + (size_t)f * adj.gnstride + i;
+                *gp = *gp + wk.w[k] * sk;
+            }
+        }
+        const float b = pre.p[k] && live ? pre.p[k][(size_t)f * pre.nstride + i] : 1.0f;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float v = pre.p[k] ? b * z[u] : z[u];
+            acc[u] = acc[u] + wk.w[k] * v;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+        if (has[u]) Gd[o + u] = acc[u];
+}
+
 // out[f][k] = sum over the iterations and the frame's workgroups of partial[t][k][f][b]: one workgroup per (term, frame), a strided
 // walk over the T x backward_blocks(n_points[f]) partials of the frame in a fixed order and a fixed tree in LDS (store and sum: no
 // atomics, the same bits every run, and those of a handle of n_points[f] points).  bstride: the partials' row (the sweep's grid).
@@ -488,6 +548,8 @@ namespace {
 // gb[i][c] += scale * <row_i, val[v_ic]> for every point i < n_points[f] and corner c: a slice without the sum over the corners.
 // A row is G lanes as in k_softmax_bwd (lane c of the row holds labels 4c .. 4c+3); every id first, then every gather, then the
 // dot products, each summed over the labels in order 0 .. L-1.  row == null: all ones (the norm part, L = 1).
+// fac != null (section 1m): the row is fac[f][i] * row_i, every product rounded once -- the splat side's input row b_k . Q_{t-1} of a
+// term with a factor in front of its filter, exactly the row the forward's splat formed.  Without it (a uniform branch) the bits it gave.
 struct CornerArgs {
     const int *n_points;
     int L;
@@ -496,6 +558,8 @@ struct CornerArgs {
     const float *val;            // the kernel's blurred values (launch_filter / launch_filter_values1)
     float scale;
     float *gb;                   // [F][Epad]
+    const float *fac;            // [F][nstride] or null
+    int nstride;
 };
 
 template <int G>
@@ -522,6 +586,11 @@ __global__ void __launch_bounds__(kBwdBlock) k_corner_dot(KernelDev kd, CornerAr
         has[u] = live && l0 + u < L;
         r[u] = has[u] ? (a.row ? a.row[f * a.fs + (size_t)i * L + l0 + u] : 1.0f) : 0.0f;
     }
+    if (a.fac) {
+        const float b = live ? a.fac[(size_t)f * a.nstride + i] : 0.0f;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) r[u] = has[u] ? b * r[u] : 0.0f;
+    }
 #pragma unroll
     for (int j = 0; j <= kMaxD; ++j)
         if (j < D1) {
@@ -540,22 +609,28 @@ __global__ void __launch_bounds__(kBwdBlock) k_corner_dot(KernelDev kd, CornerAr
 }
 
 void launch_corner_dot(const KernelDev &kd, const CrfDev &c, int rows, int L, const float *row, size_t fs, const float *val, float scale,
-                       float *gb, hipStream_t s)
+                       float *gb, hipStream_t s, const float *fac = nullptr)
 {
-    CornerArgs a{c.n_points, L, fs, row, val, scale, gb};
+    CornerArgs a{c.n_points, L, fs, row, val, scale, gb, fac, c.maxN};
     const dim3 grid((unsigned)std::max(backward_blocks(rows, L), 1), (unsigned)c.F);
     with_bwd_lanes(L, [&](auto lanes) { k_corner_dot<decltype(lanes)::value><<<grid, kBwdBlock, 0, s>>>(kd, a); });
 }
 
-// gn[i] <- a_i = -n_i^2 gn[i]: dL/d Phi_k(1)_i, the input of the norm part's filter pair
-__global__ void __launch_bounds__(kBwdBlock) k_norm_adjoint(KernelDev kd, const int *__restrict__ n_points, float *__restrict__ gn)
+// gn[i] <- a_i = -n_i^2 g_n[i]: dL/d Phi_k(1)_i, the input of the norm part's filter pair.  norm: the term's TRUE norm n_k, [F][maxN]
+// (under section 1g's modes kd.norm is the factor behind the filter, not n_k).  g_n = gn as the sweep accumulated it -- the post
+// adjoint of an AFTER term, the pre adjoint of a BEFORE term -- or, root != null (SYMMETRIC, section 1m: both adjoints in the one
+// accumulator, root = s = sqrtf(n)), g_n = gn * (0.5f / s[i]): ds/dn = 1 / (2 s).
+__global__ void __launch_bounds__(kBwdBlock) k_norm_adjoint(KernelDev kd, const int *__restrict__ n_points, const float *__restrict__ norm,
+                                                          const float *__restrict__ root, float *__restrict__ gn)
 {
     const int f = blockIdx.y;
     const int i = blockIdx.x * kBwdBlock + threadIdx.x;
     if (i >= n_points[f]) return;
-    const float n = kd.norm[(size_t)f * kd.maxN + i];
+    const float n = norm[(size_t)f * kd.maxN + i];
     float *g = gn + (size_t)f * kd.maxNpad + i;
-    *g = -(n * n) * *g;
+    float v = *g;
+    if (root) v = v * (0.5f / root[(size_t)f * kd.maxN + i]);
+    *g = -(n * n) * v;
 }
 
 // dL/df [F][maxN][D] from dL/db (gb, laid out as KernelDev::bary).  With v_j = (el_j - rem0_j) / (D+1) and p_j = D - rank_j, corner
@@ -658,7 +733,8 @@ size_t backward_layout(const BackwardRequest &rq, const CrfDev &c, const KernelD
 }
 
 void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *maxV, int rows, const BackwardRequest &rq,
-                           const BackwardArea &ar, const float *const *compat, hipStream_t s, const float *const *pre)
+                           const BackwardArea &ar, const float *const *compat, hipStream_t s, const float *const *pre,
+                           const BackwardModes *modes)
 {
     const int T = rq.T;
     const float relax = rq.relax;
@@ -693,13 +769,18 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
     for (int k = 0; k < K && cmode; ++k) a.compat[k] = compat ? compat[k] : nullptr;
     a.gam = ar.gam;
     // the feature part: terms with a gradient array (T >= 1; the caller has zeroed their ar.gb / ar.gn)
-    bool feat = false;
+    // (section 1m, modes != null: ar.gn[k] takes the post adjoint of an AFTER or SYMMETRIC term from k_softmax_bwd and the pre adjoint
+    // of a BEFORE or SYMMETRIC one from k_bwd_combine_adjoint, which runs in k_bwd_combine<true>'s place while padj is set)
+    bool feat = false, padj = false;
     float *gf[kBwdMaxK] = {};
+    BwdPreAdjoint pa{};
     for (int k = 0; k < K && grad_features && T >= 1; ++k)
         if (grad_features[k]) {
+            const int mode = modes ? modes->mode[k] : LCCRF_NORMALIZE_AFTER;
             gf[k] = grad_features[k];
-            a.gn[k] = ar.gn[k];
-            a.gnstride = kds[k].maxNpad;
+            if (mode == LCCRF_NORMALIZE_AFTER || mode == LCCRF_NORMALIZE_SYMMETRIC) a.gn[k] = ar.gn[k];
+            if (mode == LCCRF_NORMALIZE_BEFORE || mode == LCCRF_NORMALIZE_SYMMETRIC) pa.gn[k] = ar.gn[k], padj = true;
+            a.gnstride = pa.gnstride = kds[k].maxNpad;
             feat = true;
         }
     const dim3 cgrid((unsigned)std::max<size_t>(((size_t)rows * L + kBwdBlock - 1) / kBwdBlock, 1), (unsigned)F);
@@ -727,9 +808,16 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
             if (gf[k]) launch_corner_dot(kds[k], c, rows, L, ar.phi + k * slice, fs, val[k], cs, ar.gb[k], s);    // slice side
             const float *valt;                             // (B^T S n_k gamma_t)
             launch_filter(kds[k], c, maxV[k], ar.phi + k * slice, ar.phi + k * slice, 0, s, 1, &valt);
-            if (gf[k]) launch_corner_dot(kds[k], c, rows, L, qprev, fs, valt, cs, ar.gb[k], s);                    // splat side
+            if (gf[k]) launch_corner_dot(kds[k], c, rows, L, qprev, fs, valt, cs, ar.gb[k], s, bp.p[k]);          // splat side
         }
-        if (pre) k_bwd_combine<true><<<cgrid, kBwdBlock, 0, s>>>(c.n_points, L, K, ar.phi, slice, fs, wk, 1.0f - relax, ar.G, bp);
+        if (padj) {
+            pa.q = qprev;
+            const dim3 rgrid((unsigned)nblk, (unsigned)F);
+            with_bwd_lanes(L, [&](auto lanes) {
+                k_bwd_combine_adjoint<decltype(lanes)::value><<<rgrid, kBwdBlock, 0, s>>>(c.n_points, L, K, ar.phi, slice, fs, wk, 1.0f - relax,
+                                                                                       ar.G, bp, pa);
+            });
+        } else if (pre) k_bwd_combine<true><<<cgrid, kBwdBlock, 0, s>>>(c.n_points, L, K, ar.phi, slice, fs, wk, 1.0f - relax, ar.G, bp);
         else k_bwd_combine<false><<<cgrid, kBwdBlock, 0, s>>>(c.n_points, L, K, ar.phi, slice, fs, wk, 1.0f - relax, ar.G, bp);
     }
     // dL/dU -= P_0 (G_0 - <G_0, P_0>), P_0 = Q_0 = softmax(-U)
@@ -742,10 +830,17 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
         k_compat_reduce<<<(unsigned)(((size_t)F * K * L * L + kBwdBlock - 1) / kBwdBlock), kBwdBlock, 0, s>>>(ar.cpart, c.n_points, K, F, cblk,
                                                                                                             L * L, grad_compat);
     // the norm part, <a_k, Phi_k(1)> with a_k = -n_k^2 g_n[k] (value width 1), and dL/db -> dL/df
+    // (section 1m: g_n from the adjoints by the term's mode, n_k the true norm; a term without a norm factor has no norm part)
     for (int k = 0; k < K; ++k) {
         if (!gf[k]) continue;
         const KernelDev &kd = kds[k];
-        k_norm_adjoint<<<dim3((unsigned)std::max((rows + kBwdBlock - 1) / kBwdBlock, 1), (unsigned)F), kBwdBlock, 0, s>>>(kd, c.n_points, ar.gn[k]);
+        const int mode = modes ? modes->mode[k] : LCCRF_NORMALIZE_AFTER;
+        if (mode == LCCRF_NORMALIZE_NONE) {
+            launch_corner_to_feature(kd, c, rows, ar.gb[k], gf[k], s);
+            continue;
+        }
+        k_norm_adjoint<<<dim3((unsigned)std::max((rows + kBwdBlock - 1) / kBwdBlock, 1), (unsigned)F), kBwdBlock, 0, s>>>(
+            kd, c.n_points, modes ? modes->norm[k] : kd.norm, mode == LCCRF_NORMALIZE_SYMMETRIC ? bp.p[k] : nullptr, ar.gn[k]);
         const float *ones = launch_filter_values1(kd, c, maxV[k], nullptr, 0, s, 0);
         launch_corner_dot(kd, c, rows, 1, ar.gn[k], (size_t)kd.maxNpad, ones, kd.alpha, ar.gb[k], s);
         const float *adj = launch_filter_values1(kd, c, maxV[k], ar.gn[k], kd.maxNpad, s, 1);
