@@ -851,6 +851,36 @@ typedef struct lccrf_blur_plan {
 } lccrf_blur_plan;
 int  lccrf_batch_get_blur_plan(lccrf_batch_handle b, int kernel, lccrf_blur_plan *out);
 int  lccrf_get_blur_plan(lccrf_handle h, int kernel, lccrf_blur_plan *out);
+/* Report only, under the same conditions: what the build kernels themselves counted while they built the lattice of term `kernel`,
+ * frame `frame`, now in HBM (csrc/stream_build.hip; tests/sorted_build_cases.py places a frame on either side of every rule).  All 0
+ * for lattices of the one-workgroup build.  sorted_build: built by sorting the entries on their vertex's row-major code (else by the
+ * hash table, and the next nine fields are 0).  direct_codes: the code is its own sort bucket (the box of the vertices is no larger
+ * than the histogram).  long_buckets: sort buckets of more than 512 entries, each ordered by a workgroup of its own -- by the LDS
+ * bitmap over the original ids (long_by_bitmap: one code, >= 1024 entries, ids spanning at most 15872 words), or by the bitonic
+ * network because it holds one code but fewer than 1024 entries (long_by_network_uniform), several codes (long_by_network_mixed) or
+ * one code whose ids span more than the bitmap (long_by_network_wide); the four add up to long_buckets.  max_buckets_per_workgroup:
+ * the most long buckets one workgroup ordered (more than 1 beyond 64 long buckets).  phantom_entries: entries of the points that pad
+ * the frame to a multiple of four; empty_row_vertices: vertices only they touch.  long_rows: hash build only, rows of more than 128
+ * entries (ordered by a workgroup each).  Per frame rather than per term, locality mode only: point_buckets_over_64, the buckets of
+ * the point sort that kept their arrival order, and largest_point_bucket.  The handle's form reports its one frame.  Added WITHOUT a
+ * step of LCCRF_ABI_VERSION: probe by symbol.                                                                                     */
+typedef struct lccrf_build_report {
+    int32_t sorted_build, direct_codes, long_buckets, long_by_bitmap, long_by_network_uniform, long_by_network_mixed,
+            long_by_network_wide, max_buckets_per_workgroup, phantom_entries, empty_row_vertices, long_rows,
+            point_buckets_over_64, largest_point_bucket;
+} lccrf_build_report;
+int  lccrf_batch_get_build_report(lccrf_batch_handle b, int kernel, int frame, lccrf_build_report *out);
+int  lccrf_get_build_report(lccrf_handle h, int kernel, lccrf_build_report *out);
+/* Parity probe (as lccrf_get_lattice, which re-builds a lattice of locality mode the plain way before it answers): the tables of term
+ * `kernel`, frame `frame` AS BUILT, in the internal order the engine iterates in, copied out without a rebuild.  With Np = the
+ * frame's points rounded up to a multiple of four, N its real points and V its vertices: n_points_padded = Np, n_vertices = V,
+ * perm [Np] (position -> original point; the identity outside locality mode), offset / bary [Np][d+1] by POSITION, rowptr [V+1],
+ * csr_pt (positions) / csr_w [N (d+1)], nbr [d+1][V][2], fastn [V] (1: vertex v + 1 is v's axis-0 neighbour) with *has_fastn = 0 and
+ * fastn untouched where the build keeps no such table.  Any output pointer may be NULL: ask for the two sizes first.  Added WITHOUT
+ * a step of LCCRF_ABI_VERSION: probe by symbol.                                                                                    */
+int  lccrf_batch_get_built_lattice(lccrf_batch_handle b, int kernel, int frame, int32_t *n_points_padded, int32_t *n_vertices,
+                                   int32_t *perm_out, int32_t *offset_out, float *bary_out, int32_t *rowptr_out, int32_t *csr_pt_out,
+                                   float *csr_w_out, int32_t *nbr_out, uint8_t *fastn_out, int *has_fastn);
 
 /* Measurement support for bench.py: HIP-event time of the last lccrf_batch_inference()
  * on its stream, the number of launches of the dominant kernel and their summed

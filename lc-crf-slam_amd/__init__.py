@@ -72,6 +72,16 @@ class BlurPlan(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class BuildReport(C.Structure):
+    """lccrf_build_report"""
+    _fields_ = [(n, C.c_int32) for n in ("sorted_build", "direct_codes", "long_buckets", "long_by_bitmap", "long_by_network_uniform",
+                                         "long_by_network_mixed", "long_by_network_wide", "max_buckets_per_workgroup", "phantom_entries",
+                                         "empty_row_vertices", "long_rows", "point_buckets_over_64", "largest_point_bucket")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class BatchDesc(C.Structure):
     _fields_ = [("max_frames", C.c_int), ("max_points", C.c_int), ("n_labels", C.c_int),
                 ("n_kernels", C.c_int), ("feat_dims", C.c_int * MAX_KERNELS),
@@ -188,6 +198,10 @@ def lib():
     L.lccrf_get_splat_plan.argtypes = [vp, C.c_int, C.POINTER(SplatPlan)]
     L.lccrf_batch_get_blur_plan.argtypes = [vp, C.c_int, C.POINTER(BlurPlan)]
     L.lccrf_get_blur_plan.argtypes = [vp, C.c_int, C.POINTER(BlurPlan)]
+    L.lccrf_batch_get_build_report.argtypes = [vp, C.c_int, C.c_int, C.POINTER(BuildReport)]
+    L.lccrf_get_build_report.argtypes = [vp, C.c_int, C.POINTER(BuildReport)]
+    L.lccrf_batch_get_built_lattice.argtypes = [vp, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, _f32p, _i32p, _i32p, _f32p, _i32p,
+                                                C.POINTER(C.c_uint8), C.POINTER(C.c_int)]
     L.lccrf_batch_pose_set_crf_counts.argtypes = [vp, vp]
     L.lccrf_batch_last_timing.argtypes = [vp, _f32p, _f32p]
     L.lccrf_batch_last_prepare.argtypes = [vp, _f32p, C.POINTER(C.c_int)]
@@ -543,6 +557,12 @@ class DenseCRFHIP(_Handle):
         _check(lib().lccrf_get_unary(self.h, _p(out, _f32p)))
         return out
 
+    def build_report(self, k):
+        """What the build kernels counted while they built term k's lattice now in HBM (lccrf_build_report), as a dict."""
+        r = BuildReport()
+        _check(lib().lccrf_get_build_report(self.h, int(k), C.byref(r)))
+        return r.as_dict()
+
     def kernel(self, k):
         d = self._d[k]
         V = C.c_int(0)
@@ -761,6 +781,39 @@ class BatchCRF(_Handle):
         a, b = C.c_int(0), C.c_int(0)
         _check(lib().lccrf_batch_get_locality_mode(self.h, C.byref(a), C.byref(b)))
         return bool(a.value), bool(b.value)
+
+    def build_report(self, k, frame=0):
+        """What the build kernels counted while they built the lattice of term k, frame `frame`, now in HBM (lccrf_build_report), as a
+        dict; all 0 for lattices of the one-workgroup build."""
+        r = BuildReport()
+        _check(lib().lccrf_batch_get_build_report(self.h, int(k), int(frame), C.byref(r)))
+        return r.as_dict()
+
+    def built_lattice(self, k, frame=0):
+        """Parity probe: the tables of term k, frame `frame` as built, in the engine's internal order and numbering, without a rebuild
+        (lccrf_batch_get_built_lattice): dict(N, V, perm, offset, bary, rowptr, csr_pt, csr_w, nbr, fastn or None)."""
+        d = self.dims[k]
+        npad, nv, has = C.c_int32(0), C.c_int32(0), C.c_int(0)
+        fn = lib().lccrf_batch_get_built_lattice
+        _check(fn(self.h, int(k), int(frame), C.byref(npad), C.byref(nv), None, None, None, None, None, None, None, None, C.byref(has)))
+        Np, V = npad.value, nv.value
+        N = int(self.n_points[frame]) if self.n_points is not None else None
+        perm = np.empty(Np, np.int32)
+        off = np.empty((Np, d + 1), np.int32)
+        bary = np.empty((Np, d + 1), np.float32)
+        rowptr = np.empty(V + 1, np.int32)
+        nbr = np.empty((d + 1, V, 2), np.int32)
+        fastn = np.empty(V, np.uint8)
+        _check(fn(self.h, int(k), int(frame), None, None, _p(perm, _i32p), _p(off, _i32p), _p(bary, _f32p), _p(rowptr, _i32p), None, None,
+                  _p(nbr, _i32p), fastn.ctypes.data_as(C.POINTER(C.c_uint8)), None))
+        nr = int(rowptr[V])                             # (= N (d + 1): the real entries)
+        if N is None:
+            N = nr // (d + 1)
+        csr_pt = np.empty(N * (d + 1), np.int32)
+        csr_w = np.empty(N * (d + 1), np.float32)
+        _check(fn(self.h, int(k), int(frame), None, None, None, None, None, None, _p(csr_pt, _i32p), _p(csr_w, _f32p), None, None, None))
+        return dict(d=d, N=N, V=V, perm=perm, offset=off, bary=bary, rowptr=rowptr, csr_pt=csr_pt, csr_w=csr_w, nbr=nbr,
+                    fastn=fastn if has.value else None)
 
     def fallback_frames(self):
         """Frames of the last run() that did not fit the one-launch kernel and were re-run on the two-kernel path."""

@@ -591,6 +591,45 @@ int lccrf_batch_get_lattice_sizes_host(lccrf_batch_handle b, int kernel, int32_t
     return batch_read_back(b, n_vertices_out, b->eng.kernels[kernel].dev.V, sizeof(int) * b->eng.F);
 }
 
+// parity probe: the tables of one frame's lattice as they sit in HBM (internal point order, the build's own vertex ids); downloads only
+int lccrf_batch_get_built_lattice(lccrf_batch_handle b, int kernel, int frame, int32_t *n_points_padded, int32_t *n_vertices,
+                                  int32_t *perm_out, int32_t *offset_out, float *bary_out, int32_t *rowptr_out, int32_t *csr_pt_out,
+                                  float *csr_w_out, int32_t *nbr_out, uint8_t *fastn_out, int *has_fastn)
+{
+    CHECK_H(b);
+    CHECK_K(b, kernel);
+    Engine &e = b->eng;
+    if (frame < 0 || frame >= e.F) return fail(LCCRF_E_INVALID, "frame %d not in [0, %d)", frame, e.F);
+    { int rc = e.make_ready(Engine::kSettled | Engine::kSized); if (rc) return rc; }
+    HIP_TRY(hipStreamSynchronize(e.stream));
+    const KernelDev &k = e.kernels[kernel].dev;
+    const size_t f = (size_t)frame, fe = f * k.Epad, f1 = f * (k.Epad + 1);
+    int N = 0, V = 0;
+    HIP_TRY(hipMemcpy(&N, e.crf.n_points + f, sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&V, k.V + f, sizeof(int), hipMemcpyDeviceToHost));
+    N = std::min(std::max(N, 0), e.maxN);
+    V = std::min(std::max(V, 0), k.Epad);
+    const int Np = (N + 3) & ~3;
+    const size_t ne = (size_t)Np * k.D1, nr = (size_t)N * k.D1;
+    if (n_points_padded) *n_points_padded = Np;
+    if (n_vertices) *n_vertices = V;
+    if (perm_out) {
+        if (k.perm && Np) HIP_TRY(hipMemcpy(perm_out, k.perm + f * k.maxNpad, (size_t)Np * sizeof(int), hipMemcpyDeviceToHost));
+        for (int i = 0; !k.perm && i < Np; ++i) perm_out[i] = i;
+    }
+    if (offset_out && ne) HIP_TRY(hipMemcpy(offset_out, k.offset + fe, ne * sizeof(int), hipMemcpyDeviceToHost));
+    if (bary_out && ne) HIP_TRY(hipMemcpy(bary_out, k.bary + fe, ne * sizeof(float), hipMemcpyDeviceToHost));
+    if (rowptr_out) HIP_TRY(hipMemcpy(rowptr_out, k.rowptr + f1, ((size_t)V + 1) * sizeof(int), hipMemcpyDeviceToHost));
+    if (csr_pt_out && nr) HIP_TRY(hipMemcpy(csr_pt_out, k.csr_pt + fe, nr * sizeof(int), hipMemcpyDeviceToHost));
+    if (csr_w_out && nr) HIP_TRY(hipMemcpy(csr_w_out, k.csr_w + fe, nr * sizeof(float), hipMemcpyDeviceToHost));
+    for (int j = 0; nbr_out && j < k.D1 && V; ++j)        // device rows are strided by Epad, output by V
+        HIP_TRY(hipMemcpy(nbr_out + (size_t)j * V * 2, k.nbr + (f * k.D1 + j) * k.Epad * 2, (size_t)V * 2 * sizeof(int), hipMemcpyDeviceToHost));
+    const bool fastn = k.fastn != nullptr && k.vorder;    // (written by the sorted build alone)
+    if (has_fastn) *has_fastn = fastn ? 1 : 0;
+    if (fastn_out && fastn && V) HIP_TRY(hipMemcpy(fastn_out, k.fastn + fe, (size_t)V, hipMemcpyDeviceToHost));
+    return LCCRF_OK;
+}
+
 int lccrf_batch_get_norm_host(lccrf_batch_handle b, int kernel, float *norm_out)
 {
     CHECK_H(b);

@@ -89,6 +89,34 @@ int blur_plan_of(Engine &e, int kernel, lccrf_blur_plan *out)
     return LCCRF_OK;
 }
 
+// what the streaming build counted for the lattices now in HBM (engine.h: BuildStat; they came along with the build's copy of rowmax)
+int build_report_of(Engine &e, int kernel, int frame, lccrf_build_report *out)
+{
+    if (frame < 0 || frame >= e.F) return fail(LCCRF_E_INVALID, "frame %d not in [0, %d)", frame, e.F);
+    if (int rc = plan_ready(e)) return rc;
+    *out = lccrf_build_report{};
+    const KernelState &ks = e.kernels[kernel];
+    if (!ks.build_counted) return LCCRF_OK;               // (the one-workgroup build, or no build yet)
+    const int *st = e.row_host + kernel * e.row_stride() + e.Fcap + (size_t)frame * kBuildStats;
+    out->point_buckets_over_64 = st[kBsPtOver64];
+    out->largest_point_bucket = st[kBsPtLargest];
+    if (!ks.dev.vorder) {                                 // the hash build: the sorted build's counters may be those of an abandoned attempt
+        out->long_rows = st[kBsLongRows];
+        return LCCRF_OK;
+    }
+    out->sorted_build = 1;
+    out->direct_codes = st[kBsDirect];
+    out->long_buckets = st[kBsLongBuckets];
+    out->long_by_bitmap = st[kBsBitmap];
+    out->long_by_network_uniform = st[kBsNetUniform];
+    out->long_by_network_mixed = st[kBsNetMixed];
+    out->long_by_network_wide = st[kBsNetWide];
+    out->max_buckets_per_workgroup = st[kBsMaxPerWg];
+    out->phantom_entries = st[kBsPhantom];
+    out->empty_row_vertices = st[kBsEmptyRows];
+    return LCCRF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -118,5 +146,7 @@ int lccrf_get_splat_plan(lccrf_handle h, int kernel, lccrf_splat_plan *out) { HA
 int lccrf_batch_get_splat_plan(lccrf_batch_handle b, int kernel, lccrf_splat_plan *out) { HANDLE_FIRST(b, kernel); CHECK_OUT(out, "out"); return splat_plan(b->eng, kernel, out); }
 int lccrf_get_blur_plan(lccrf_handle h, int kernel, lccrf_blur_plan *out) { HANDLE_FIRST(h, kernel); CHECK_OUT(out, "out"); return blur_plan_of(h->eng, kernel, out); }
 int lccrf_batch_get_blur_plan(lccrf_batch_handle b, int kernel, lccrf_blur_plan *out) { HANDLE_FIRST(b, kernel); CHECK_OUT(out, "out"); return blur_plan_of(b->eng, kernel, out); }
+int lccrf_get_build_report(lccrf_handle h, int kernel, lccrf_build_report *out) { HANDLE_FIRST(h, kernel); CHECK_OUT(out, "out"); return build_report_of(h->eng, kernel, 0, out); }
+int lccrf_batch_get_build_report(lccrf_batch_handle b, int kernel, int frame, lccrf_build_report *out) { HANDLE_FIRST(b, kernel); CHECK_OUT(out, "out"); return build_report_of(b->eng, kernel, frame, out); }
 
 }  // extern "C"

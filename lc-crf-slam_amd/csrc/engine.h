@@ -34,6 +34,13 @@ constexpr int kMaxD = LCCRF_MAX_DIMS;
 constexpr int kEmpty = -1;
 
 constexpr int kNdistAxes = 4;
+// counters of the streaming build: [F][kBuildStats] ints in one allocation with KernelDev::rowmax, behind its Fcap ints, so that one
+// clear and one copy serve both (KernelState::bstat; handed to the build's kernels beside KernelDev, which no inference kernel's
+// argument list may grow by; read by nothing but lccrf_get_build_report / lccrf_batch_get_build_report)
+enum BuildStat {
+    kBsDirect = 0, kBsLongBuckets, kBsBitmap, kBsNetUniform, kBsNetMixed, kBsNetWide, kBsMaxPerWg, kBsPhantom, kBsEmptyRows, kBsLongRows,
+    kBsPtOver64, kBsPtLargest, kBuildStats
+};
 constexpr int kLongRowMin = 512;    // generic (L-label) splat: rows beyond this many entries go to a workgroup of their own (KernelDev::longrow)
 constexpr int kLongRowCap = 4095;   // ... as long as there are no more than this many of them per frame
 constexpr int kLongRowListMinPoints = 4096;   // ... in engines for frames beyond the one-workgroup kernels' range (the lists are 16 KB per frame)
@@ -263,12 +270,14 @@ inline BlurPlan blur_plan(const KernelDev &kd, int F, int maxV)
 }
 
 // scratch of the point sort (locality mode), owned by the engine
+constexpr int kSortPlan = 3 * kMaxD + 2;
 struct SortScratch {
     int bits;             // bucket bits of the counting sort (8..16)
     int rm_points;        // order the points row-major over their cells in the lattice's own basis (with the sorted build) instead of along a Z-order curve
     int *cells;           // [F][maxNpad][kMaxD] lattice cell of every point (int32); later the unordered buckets
     int *partial;         // [F][ceil(maxNpad/256)][2*kMaxD] per-workgroup min / max of the cells
-    int *plan;            // [F][3*kMaxD]        per dimension: lowest cell, span, code bits
+    int *plan;            // [F][kSortPlan]      per dimension: lowest cell, span, code bits; then what k_sort_place counted (report only):
+                          //                       buckets of more than 64 points, the largest bucket
     int *code;            // [F][maxNpad]        Z-order bucket of every point
     int *hist;            // [F][2^bits + 1]     bucket counts
     int *start;           // [F][2^bits + 1]     exclusive scan of hist, advanced to the bucket ends by the scatter
@@ -292,7 +301,8 @@ struct SortScratch {
 void launch_sort_points(const KernelDev &kd, const CrfDev &c, const SortScratch &ss, hipStream_t s);
 // dst[f][i][0..width) = src[f][perm[i]][0..width) (gather = 1) or dst[f][perm[i]][..] = src[f][i][..] (gather = 0), i < n_points[f]
 void launch_permute_rows(const CrfDev &c, float *dst, const float *src, int width, int gather, hipStream_t s);
-void launch_build_kernel(const KernelDev &kd, const CrfDev &c, hipStream_t s, const SortScratch *vsort = nullptr);
+// bstat: [F][kBuildStats] behind kd.rowmax's capacity (BuildStat above), never null
+void launch_build_kernel(const KernelDev &kd, const CrfDev &c, hipStream_t s, const SortScratch *vsort, int *bstat);
 void launch_norm(const KernelDev &kd, const CrfDev &c, int maxV, hipStream_t s);
 // unary[i][:] from labels (densecrf3d.h:116-129); the 2L+1 energies {u, n[L], p[L]} are passed by value (no table
 // upload; `label` may be device or pinned host memory)

@@ -96,6 +96,8 @@ struct KernelState {
     float *feat_stage = nullptr;  // pinned staging for the object API
     int maxV = 0;                 // max over frames of V once known, else Epad
     int maxRow = 0;               // max over frames of the longest CSR row
+    int *bstat = nullptr;         // [Fcap][kBuildStats] device: the streaming build's counters, behind dev.rowmax's Fcap ints (engine.h: BuildStat)
+    bool build_counted = false;   // the lattices now in HBM came from the streaming build, whose counters are in Engine::row_host
     float *norm_root = nullptr;   // [F][maxN] sqrtf(norm) of a term normalised SYMMETRICally (section 1g; lazy, kept with the lattice)
     bool root_valid = false;      // ... holds the roots of the norm now in HBM.  Invariant: whatever writes KernelDev::norm in HBM clears
                                   //   this -- today that is Engine::build_kernels alone (the streaming and the one-workgroup build; the
@@ -122,7 +124,8 @@ struct Engine {
 
     // ---- lattices and their sizes ----
     int *V_host = nullptr;             // pinned [K][Fcap]
-    int *row_host = nullptr;           // pinned [K][Fcap]
+    int *row_host = nullptr;           // pinned [K][row_stride()]: rowmax of every frame, then [Fcap][kBuildStats] the streaming build's counters
+    size_t row_stride() const { return (size_t)Fcap * (1 + kBuildStats); }
     int *long_host = nullptr;          // pinned [K][Fcap]: rows beyond kLongRowMin entries per frame (KernelDev::longcnt)
     std::vector<KernelState> kernels;
     std::vector<KernelState> spare;    // allocated lattices of earlier uses of this (recycled) engine

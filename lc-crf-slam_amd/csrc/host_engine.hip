@@ -155,7 +155,7 @@ int Engine::ensure_sort_scratch()
     int rc;
     if ((rc = mem.alloc(&sort.cells, Fz * maxNpad * kMaxD))) return rc;
     if ((rc = mem.alloc(&sort.partial, Fz * ((maxNpad + 255) / 256 + 1) * 2 * kMaxD))) return rc;
-    if ((rc = mem.alloc(&sort.plan, Fz * 3 * kMaxD))) return rc;
+    if ((rc = mem.alloc(&sort.plan, Fz * kSortPlan))) return rc;
     if ((rc = mem.alloc(&sort.code, Fz * maxNpad))) return rc;
     if ((rc = mem.alloc(&sort.hist, Fz * nbk))) return rc;
     if ((rc = mem.alloc(&sort.start, Fz * nbk))) return rc;
@@ -209,7 +209,7 @@ int Engine::init(int device_id, int frames, int max_points, int n_labels)
     if (n_labels == 2 && (rc = mem.alloc(&crf.map_bits, (size_t)Fcap * std::max(crf.bits_stride, 1)))) return rc;
     if ((rc = mem.alloc(&label_own, (size_t)Fcap * maxN))) return rc;
     if ((rc = mem.alloc_pinned(&V_host, (size_t)LCCRF_MAX_KERNELS * Fcap))) return rc;
-    if ((rc = mem.alloc_pinned(&row_host, (size_t)LCCRF_MAX_KERNELS * Fcap))) return rc;
+    if ((rc = mem.alloc_pinned(&row_host, (size_t)LCCRF_MAX_KERNELS * row_stride()))) return rc;
     if ((rc = mem.alloc_pinned(&long_host, (size_t)LCCRF_MAX_KERNELS * Fcap))) return rc;
     if ((rc = mem.alloc_pinned(&late_status, 1))) return rc;
     *late_status = 0;
@@ -270,6 +270,7 @@ int Engine::add_kernel(int d, float w, bool own_features, bool stage)
             ks.dev.feat = ks.feat_own;
             ks.maxV = ks.dev.Epad;
             ks.maxRow = 0;
+            ks.build_counted = false;
             ks.root_valid = false;
             kernels.push_back(ks);
             sync_views();
@@ -306,7 +307,8 @@ int Engine::add_kernel(int d, float w, bool own_features, bool stage)
     if ((rc = mem.alloc(&k.prefix, Fz * (E + 1)))) return rc;
     if ((rc = mem.alloc(&k.rep, Fz * E))) return rc;
     if ((rc = mem.alloc(&k.V, Fz))) return rc;
-    if ((rc = mem.alloc(&k.rowmax, Fz))) return rc;
+    if ((rc = mem.alloc(&k.rowmax, Fz * (1 + kBuildStats)))) return rc;     // (rowmax, then the build's counters)
+    ks.bstat = k.rowmax + Fz;
     if ((rc = mem.alloc(&k.nbr, Fz * k.D1 * E * 2))) return rc;
     // one frame in flight, large frames (the object API's handles are sized for SLAM frames, which run on the one-workgroup engines):
     // the blur passes go two per launch and read a two-hop neighbour table
@@ -390,7 +392,7 @@ void Engine::sync_views()
     maxRow.resize(kernels.size());
     for (size_t i = 0; i < kernels.size(); ++i) {
         kernels[i].dev.V_host = V_host + i * Fcap;
-        kernels[i].dev.rowmax_host = row_host + i * Fcap;
+        kernels[i].dev.rowmax_host = row_host + i * row_stride();
         kernels[i].dev.perm = perm_on ? sort.perm : nullptr;
         kernels[i].dev.iperm = perm_on ? sort.iperm : nullptr;
         kernels[i].dev.vorder = (perm_on && vorder_on && sort.vkey && kernels[i].dev.Epad <= sort.vcap) ? 1 : 0;
@@ -457,6 +459,7 @@ int Engine::build_kernels(int k0, int n, bool may_reorder)
         if (small_ok && k + 1 < k0 + n && build_small_supported(&kdevs[k], 2, NA)) m = 2;
         if (small_ok && build_small_supported(&kdevs[k], m, NA)) {
             for (int u = 0; u < m; ++u) kernels[k + u].dev.nbr2_ok = kernels[k + u].dev.nbrc_ok = kernels[k + u].dev.fast0_ok = kernels[k + u].dev.longrow_ok = 0;
+            for (int u = 0; u < m; ++u) kernels[k + u].build_counted = false;
             launch_build_small(&kdevs[k], m, NA, crf, stream);   // writes V / rowmax to the pinned mirrors itself
         } else {
             m = 1;
@@ -465,10 +468,12 @@ int Engine::build_kernels(int k0, int n, bool may_reorder)
             kernels[k].dev.nbrc_ok = kernels[k].dev.nbrc != nullptr && kernels[k].dev.vorder && F >= kNbrcMinFrames && F <= kNbrcMaxFrames;   // (... and the sorted build the compact one)
             kernels[k].dev.fast0_ok = kernels[k].dev.tbl_bad != nullptr && kernels[k].dev.vorder;
             kernels[k].dev.nbr2_first = kernels[k].dev.fast0_ok;              // (what build_kernel_d derives from the same two fields)
-            launch_build_kernel(kdevs[k], crf, stream, perm_on ? &sort : nullptr);
+            launch_build_kernel(kdevs[k], crf, stream, perm_on ? &sort : nullptr, kernels[k].bstat);
             launch_norm(kdevs[k], crf, kernels[k].maxV, stream);
             HIP_TRY(hipMemcpyAsync(V_host + (size_t)k * Fcap, kernels[k].dev.V, sizeof(int) * F, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipMemcpyAsync(row_host + (size_t)k * Fcap, kernels[k].dev.rowmax, sizeof(int) * F, hipMemcpyDeviceToHost, stream));
+            // (rowmax and, behind its Fcap ints, the build's counters of the F frames: one copy)
+            HIP_TRY(hipMemcpyAsync(row_host + k * row_stride(), kernels[k].dev.rowmax, sizeof(int) * ((size_t)Fcap + (size_t)F * kBuildStats), hipMemcpyDeviceToHost, stream));
+            kernels[k].build_counted = true;
             if (kernels[k].dev.longrow)
                 HIP_TRY(hipMemcpyAsync(long_host + (size_t)k * Fcap, kernels[k].dev.longcnt, sizeof(int) * F, hipMemcpyDeviceToHost, stream));
             if (kernels[k].dev.fast0_ok)
@@ -551,7 +556,7 @@ int Engine::learn_sizes(bool may_reorder)
         int m = 0, r = 0, nlong = 0;
         for (int f = 0; f < F; ++f) {
             m = std::max(m, V_host[k * Fcap + f]);
-            r = std::max(r, row_host[k * Fcap + f]);
+            r = std::max(r, row_host[k * row_stride() + f]);
             if (kd.longrow_ok) nlong = std::max(nlong, long_host[k * Fcap + f]);
         }
         // a coarse kernel over many points (listed rows, or more than ~4 entries per row on average): the row-walking splat with

@@ -342,7 +342,8 @@ __global__ void __launch_bounds__(kBlock) k_sort_plan(int D, int nblocks, SortSc
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        int *plan = ss.plan + (size_t)f * 3 * kMaxD;
+        int *plan = ss.plan + (size_t)f * kSortPlan;
+        plan[3 * kMaxD] = plan[3 * kMaxD + 1] = 0;         // (k_sort_place's two counters, report only)
         long rem[kMaxD];
         int nb[kMaxD];
         for (int j = 0; j < D; ++j) {
@@ -372,7 +373,7 @@ __global__ void __launch_bounds__(kBlock) k_sort_code(KernelDev kd, const int *_
     const int N = n_points[f];
     const int n = blockIdx.x * kBlock + threadIdx.x;
     if (n >= N) return;
-    const int *plan = ss.plan + (size_t)f * 3 * kMaxD;
+    const int *plan = ss.plan + (size_t)f * kSortPlan;
     const int *cp = ss.cells + ((size_t)f * kd.maxNpad + n) * kMaxD;
     if (ss.rm_points) {
         // points in (coarse) ROW-MAJOR order of their cell in the lattice's own basis -- the order the sorted build gives the vertices:
@@ -424,23 +425,30 @@ __global__ void __launch_bounds__(kBlock) k_sort_place(int maxNpad, const int *_
     const int f = blockIdx.y;
     const int pos = blockIdx.x * kBlock + threadIdx.x;
     int *p = ss.perm + (size_t)f * maxNpad, *ip = ss.iperm + (size_t)f * maxNpad;
-    if (pos >= maxNpad) return;
-    if (pos >= n_points[f]) {                            // phantom lanes and the unused tail: identity
+    int *counted = ss.plan + (size_t)f * kSortPlan + 3 * kMaxD;   // report only: {buckets of more than 64 points, the largest bucket}
+    int len = 0;
+    if (pos < maxNpad && pos >= n_points[f]) {           // phantom lanes and the unused tail: identity
         p[pos] = pos;
         ip[pos] = pos;
-        return;
+    } else if (pos < maxNpad) {
+        const int *tmp = ss.cells + (size_t)f * maxNpad * kMaxD;
+        const int *end = ss.start + (size_t)f * ((1 << ss.bits) + 1);
+        const int i = tmp[pos], c = ss.code[(size_t)f * maxNpad + i];
+        const int lo = c ? end[c - 1] : 0, hi = end[c];
+        int at = pos;
+        len = hi - lo;
+        if (len <= 64) {
+            at = lo;
+            for (int q = lo; q < hi; ++q) at += tmp[q] < i;
+        } else if (pos == lo) {
+            atomicAdd(&counted[0], 1);                   // (one per bucket that keeps its arrival order)
+        }
+        p[at] = i;
+        ip[i] = at;
     }
-    const int *tmp = ss.cells + (size_t)f * maxNpad * kMaxD;
-    const int *end = ss.start + (size_t)f * ((1 << ss.bits) + 1);
-    const int i = tmp[pos], c = ss.code[(size_t)f * maxNpad + i];
-    const int lo = c ? end[c - 1] : 0, hi = end[c];
-    int at = pos;
-    if (hi - lo <= 64) {
-        at = lo;
-        for (int q = lo; q < hi; ++q) at += tmp[q] < i;
-    }
-    p[at] = i;
-    ip[i] = at;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) len = max(len, __shfl_xor(len, o, 64));
+    if ((threadIdx.x & 63) == 0 && len > __builtin_nontemporal_load(&counted[1])) atomicMax(&counted[1], len);   // (a look first, as k_eneighbors)
 }
 
 template <int D>
@@ -472,7 +480,7 @@ void sort_points_d(const KernelDev &kd, const CrfDev &c, const SortScratch &ss, 
 // code to its bucket.  vplan[f] = {lo[kMaxD], stride[kMaxD], bucket scale, usable, range}; a lattice whose bounding box overflows 62 bits
 // (features spread over thousands of cells in every dimension) raises *vbad and is rebuilt with the hash table.
 constexpr int kVPlan = 2 * kMaxD + 3;
-__global__ void __launch_bounds__(kBlock) k_vsort_plan(int D, int nblocks, SortScratch ss)
+__global__ void __launch_bounds__(kBlock) k_vsort_plan(int D, int nblocks, SortScratch ss, int *__restrict__ bstat)
 {
     __shared__ int red[kBlock / 64][2 * kMaxD];
     __shared__ int bnd[2 * kMaxD];
@@ -523,6 +531,11 @@ __global__ void __launch_bounds__(kBlock) k_vsort_plan(int D, int nblocks, SortS
         plan[2 * kMaxD + 1] = ok ? 1 : 0;
         plan[2 * kMaxD + 2] = (long long)reff;             // (unusable plan: whatever k_eneighbors derives from the meaningless strides stays inside too)
         if (!ok && ss.vbad) *ss.vbad = 1;                 // pinned host word: the host rebuilds these lattices with the hash
+        // report only (cleared by the build's first memset): the code is its own bucket, and what the point sort counted for this CRF
+        int *st = bstat + (size_t)f * kBuildStats;
+        st[kBsDirect] = (ok && plan[2 * kMaxD] == 0) ? 1 : 0;
+        st[kBsPtOver64] = ss.plan[(size_t)f * kSortPlan + 3 * kMaxD];
+        st[kBsPtLargest] = ss.plan[(size_t)f * kSortPlan + 3 * kMaxD + 1];
     }
 }
 
@@ -628,7 +641,7 @@ __global__ void __launch_bounds__(kBlock) k_eorder(KernelDev kd, const int *__re
 
 // One workgroup per long bucket: bitonic sort of its entries by (code, original id) in place, then out (as k_csr_sort_long).
 constexpr int kSortBitmapWords = 15872;  // 62 KB of LDS: original ids spanning up to ~508 000
-__global__ void __launch_bounds__(kBlock) k_esort_long(KernelDev kd, SortScratch ss)
+__global__ void __launch_bounds__(kBlock) k_esort_long(KernelDev kd, SortScratch ss, int *__restrict__ bstat)
 {
     __shared__ unsigned bm[kSortBitmapWords];
     __shared__ int chunk_base[kBlock];
@@ -640,7 +653,11 @@ __global__ void __launch_bounds__(kBlock) k_esort_long(KernelDev kd, SortScratch
     int *sorted = kd.slot + (size_t)f * kd.cap;
     const unsigned long long *code = ss.vcode + (size_t)f * ss.vcap;
     const int *start = ss.vstart + (size_t)f * ((1 << ss.vbits) + 1);
+    int *st = bstat + (size_t)f * kBuildStats;            // report only: which way each long bucket went (lane 0: one atomic per bucket)
+    int mine = 0;
+    if (blockIdx.x == 0 && tid == 0) st[kBsLongBuckets] = nlong;
     for (int li = blockIdx.x; li < nlong; li += gridDim.x) {
+        ++mine;
         const int b = sorted[kd.Epad + li];
         const int lo = start[b], n = start[b + 1] - lo;
         int *r = tmp + lo, *ro = toe + lo;
@@ -663,6 +680,8 @@ __global__ void __launch_bounds__(kBlock) k_esort_long(KernelDev kd, SortScratch
         }
         __syncthreads();
         const int base_id = s_min, words = (s_max - s_min) / 32 + 1;
+        if (tid == 0)
+            atomicAdd(&st[s_mixed ? kBsNetMixed : n < 1024 ? kBsNetUniform : words <= kSortBitmapWords ? kBsBitmap : kBsNetWide], 1);
         if (!s_mixed && words <= kSortBitmapWords && n >= 1024) {       // (uniform; below ~1000 entries the network is cheaper than a walk over the span's words)
             for (int w = tid; w < words; w += kBlock) bm[w] = 0u;
             __syncthreads();
@@ -704,6 +723,7 @@ __global__ void __launch_bounds__(kBlock) k_esort_long(KernelDev kd, SortScratch
         for (int i = threadIdx.x; i < n; i += kBlock) sorted[lo + i] = r[i];
         __syncthreads();
     }
+    if (tid == 0 && mine > 0) atomicMax(&st[kBsMaxPerWg], mine);
 }
 
 // flag[pos] = 1 where a run (= a vertex) starts; the (at most 3 (d+1)) entries of the phantom points are listed by position --
@@ -727,7 +747,7 @@ __global__ void __launch_bounds__(kBlock) k_eflag(KernelDev kd, const int *__res
 
 // ids, representatives, and the CSR of splat contributions straight from the sorted runs: a run minus its trailing phantom entries
 // IS the vertex's row in ascending original point order (what k_csr_count / fill / order / sort_long produce for the hash build)
-__global__ void __launch_bounds__(kBlock) k_eoffsets(KernelDev kd, const int *__restrict__ n_points, SortScratch ss)
+__global__ void __launch_bounds__(kBlock) k_eoffsets(KernelDev kd, const int *__restrict__ n_points, SortScratch ss, int *__restrict__ bstat)
 {
     const int f = blockIdx.y;
     const int N = n_points[f], live = ((N + 3) & ~3) * kd.D1;
@@ -747,8 +767,13 @@ __global__ void __launch_bounds__(kBlock) k_eoffsets(KernelDev kd, const int *__
         kd.rep[fe + id] = e;                                              // the run's first element = the vertex's first occurrence
         ss.vkey[(size_t)f * ss.vcap + id] = ss.vcode[(size_t)f * ss.vcap + e];
         kd.rowptr[f1 + id] = cpos;
+        // (report only: a run that STARTS with a phantom entry holds nothing else -- a vertex with an empty row; at most 3 (d+1) of them)
+        if (e >= N * kd.D1) atomicAdd(&bstat[(size_t)f * kBuildStats + kBsEmptyRows], 1);
     }
-    if (pos == 0) kd.rowptr[f1 + kd.V[f]] = live - nph;
+    if (pos == 0) {
+        kd.rowptr[f1 + kd.V[f]] = live - nph;
+        bstat[(size_t)f * kBuildStats + kBsPhantom] = nph;
+    }
     if (e < N * kd.D1) csr_emit(kd, fe, cpos, e, id);
 }
 
@@ -1066,12 +1091,20 @@ __global__ void __launch_bounds__(kBlock) k_csr_order(KernelDev kd, const int *_
 
 // One workgroup per long row: bitonic sort of the row's entry ids in place (global memory, the row belongs to this
 // workgroup alone), O(n log^2 n) compare-exchanges instead of n^2 compares.
-__global__ void __launch_bounds__(kBlock) k_csr_sort_long(KernelDev kd)
+__global__ void __launch_bounds__(kBlock) k_csr_sort_long(KernelDev kd, const int *__restrict__ sort_plan, int *__restrict__ bstat)
 {
     const int f = blockIdx.y;
     const size_t fe = (size_t)f * kd.Epad, f1 = (size_t)f * (kd.Epad + 1);
     const int nlong = kd.flag[f1 + kd.Epad];
     int *rows = kd.slot_of + fe;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        // report only: the hash build's long rows and, in locality mode, what the point sort counted (the sorted build's counters do
+        // not apply to these lattices: the host reports them as 0)
+        int *st = bstat + (size_t)f * kBuildStats;
+        st[kBsLongRows] = nlong;
+        st[kBsPtOver64] = sort_plan ? sort_plan[(size_t)f * kSortPlan + 3 * kMaxD] : 0;
+        st[kBsPtLargest] = sort_plan ? sort_plan[(size_t)f * kSortPlan + 3 * kMaxD + 1] : 0;
+    }
     for (int li = blockIdx.x; li < nlong; li += gridDim.x) {
         const int v = kd.flag[f1 + li];
         const int s = kd.rowptr[f1 + v], n = kd.rowptr[f1 + v + 1] - s;
@@ -1110,7 +1143,7 @@ __global__ void __launch_bounds__(kBlock) k_long_rows(KernelDev kd)
 }
 
 template <int D>
-void build_kernel_d(const KernelDev &kd, const CrfDev &c, hipStream_t s, const SortScratch *vsort)
+void build_kernel_d(const KernelDev &kd, const CrfDev &c, hipStream_t s, const SortScratch *vsort, int *bstat)
 {
     const int F = c.F, D1 = D + 1;
     const dim3 ge = grid_for(kd.Epad, F);
@@ -1118,19 +1151,20 @@ void build_kernel_d(const KernelDev &kd, const CrfDev &c, hipStream_t s, const S
         // the sorted build (locality mode): entries sorted by the row-major code of their vertex
         const SortScratch &ss = *vsort;
         const int nbk = (1 << ss.vbits) + 1;
+        // (rowmax: the count of long buckets, until k_row_max; behind it the build's counters of the F frames, cleared along)
+        (void)hipMemsetAsync(kd.rowmax, 0, ((size_t)(bstat - kd.rowmax) + (size_t)F * kBuildStats) * sizeof(int), s);
         k_points<D, true><<<grid_for(kd.maxNpad, F), kBlock, 0, s>>>(kd, c.n_points, ss.vpartial, ss.vbad);
-        k_vsort_plan<<<F, kBlock, 0, s>>>(D, (int)grid_for(kd.maxNpad, F).x, ss);
+        k_vsort_plan<<<F, kBlock, 0, s>>>(D, (int)grid_for(kd.maxNpad, F).x, ss, bstat);
         (void)hipMemsetAsync(ss.vhist, 0, (size_t)F * nbk * sizeof(int), s);
-        (void)hipMemsetAsync(kd.rowmax, 0, (size_t)F * sizeof(int), s);                 // (the count of long buckets, until k_row_max)
         k_ecode<D><<<ge, kBlock, 0, s>>>(kd, c.n_points, ss);
         scan_frames(ss.vhist, ss.vstart, nbk, nbk, nullptr, ss.vtiles, F, s);
         k_escatter<<<ge, kBlock, 0, s>>>(kd, c.n_points, ss);
         k_eorder<<<ge, kBlock, 0, s>>>(kd, c.n_points, ss);
-        k_esort_long<<<dim3(64, F), kBlock, 0, s>>>(kd, ss);
+        k_esort_long<<<dim3(64, F), kBlock, 0, s>>>(kd, ss, bstat);
         (void)hipMemsetAsync(ss.vph, 0, (size_t)F * kVPh * sizeof(int), s);
         k_eflag<<<grid_for(kd.Epad + 1, F), kBlock, 0, s>>>(kd, c.n_points, ss);
         scan_frames(kd.flag, kd.prefix, kd.Epad + 1, kd.Epad + 1, kd.V, kd.rep, F, s); // (rep: the original ids are no longer needed, k_eoffsets rewrites it)
-        k_eoffsets<<<ge, kBlock, 0, s>>>(kd, c.n_points, ss);
+        k_eoffsets<<<ge, kBlock, 0, s>>>(kd, c.n_points, ss, bstat);
         (void)hipMemsetAsync(kd.nbr, 0xff, (size_t)F * D1 * kd.Epad * 2 * sizeof(int), s);      // every neighbour absent (-1)
         k_ebucket_vertices<<<grid_for(nbk, F), kBlock, 0, s>>>(kd, ss);
         XcdMap nb;
@@ -1174,7 +1208,7 @@ void build_kernel_d(const KernelDev &kd, const CrfDev &c, hipStream_t s, const S
         scan_frames(kd.flag, kd.rowptr, kd.Epad + 1, kd.Epad + 1, nullptr, kd.csr_pos, F, s);   // (csr_pos is written later, by k_csr_order)
         k_csr_fill<<<grid_for(kd.Epad, F), kBlock, 0, s>>>(kd, c.n_points);
         k_csr_order<<<grid_for(kd.Epad, F), kBlock, 0, s>>>(kd, c.n_points);
-        k_csr_sort_long<<<dim3(64, F), kBlock, 0, s>>>(kd);                     // rows of more than kLongRow entries, if any
+        k_csr_sort_long<<<dim3(64, F), kBlock, 0, s>>>(kd, vsort ? vsort->plan : nullptr, bstat);   // rows of more than kLongRow entries, if any
     }
     (void)hipMemsetAsync(kd.rowmax, 0, (size_t)F * sizeof(int), s);
     if (kd.Epad < 65535) k_row_max<<<grid_for(kd.Epad, F), kBlock, 0, s>>>(kd);   // only the one-workgroup engines ask (u16 ids)
@@ -1186,9 +1220,9 @@ void build_kernel_d(const KernelDev &kd, const CrfDev &c, hipStream_t s, const S
 
 }  // namespace
 
-void launch_build_kernel(const KernelDev &kd, const CrfDev &c, hipStream_t s, const SortScratch *vsort)
+void launch_build_kernel(const KernelDev &kd, const CrfDev &c, hipStream_t s, const SortScratch *vsort, int *bstat)
 {
-    with_dims<1, 8>(kd.d, [&](auto d) { build_kernel_d<decltype(d)::value>(kd, c, s, vsort); });
+    with_dims<1, 8>(kd.d, [&](auto d) { build_kernel_d<decltype(d)::value>(kd, c, s, vsort, bstat); });
 }
 
 void launch_sort_points(const KernelDev &kd, const CrfDev &c, const SortScratch &ss, hipStream_t s)
