@@ -1112,6 +1112,42 @@ int  lccrf_batch_inference_backward_modes(lccrf_batch_handle b, int n_iterations
                                           float *d_grad_model, void *stream);
 
 /* ======================================================================================
+ * 2j. Gradients of a batch's CONVERGED inference -- section 2c with one iteration count per frame: what section 1h's recipe
+ *     ("lccrf_inference_backward(h, t, relax, ...) with the reported `iterations` is the gradient of the converged result") is for a
+ *     handle, for every frame of a batch at once, each frame at its own count.  Added WITHOUT a step of LCCRF_ABI_VERSION (it stays
+ *     3): probe for it by symbol.
+ *
+ * d_iterations: device array of [n_frames] int32 (checked as section 1b checks device arrays; NULL: LCCRF_E_INVALID), read in stream
+ * order and never by the host: the array lccrf_batch_device_convergence hands out can be passed straight in, behind a converged call
+ * queued on the same stream, with no host synchronisation in between.  Frame f is differentiated at
+ *     t_f = min(max(d_iterations[f], 0), max_iterations)            (the kernels clamp)
+ * iterations.  d_grad_prob [n_frames][max_points][L] = dL/dQ_{t_f} of every frame; d_grad_unary, d_grad_weights as in section 2c.
+ *   - Per frame, the bits of section 1c at t_f: d_grad_unary[f] and d_grad_weights[f][:] are exactly what
+ *     lccrf_inference_backward(h, t_f, relax, ...) returns for a handle holding frame f under the batch's weights -- the weight
+ *     gradient's reduction over that frame's t_f x B partials included, in the handle's order and tree.  Rows at or beyond
+ *     n_points[f] are written +0; a frame of 0 points gets zeros.  A frame with t_f = 0 gets section 2c's T = 0 results.
+ *   - Afterwards frame f of the batch's Q holds Q_{t_f}: bit for bit what lccrf_batch_inference_converged left when the counts are
+ *     its report.  Labels, label bits and the stored convergence report are not changed.
+ *   - Every count equal to max_iterations: all outputs and the Q left behind are lccrf_batch_inference_backward(b, max_iterations,
+ *     ...)'s, bit for bit.
+ *   - The streaming route replays max_iterations steps for every frame (stepping a finished frame is wasted work, not a different
+ *     result; its Q_{t_f} is put back from the history by one small kernel) and leaves frame f idle in the sweep while t > t_f.  Under
+ *     LCCRF_OPT_FUSED_BACKWARD (section 1j), on the batches the one-launch backward takes, frame f's workgroup loads t_f once, runs t_f
+ *     replays and t_f sweep steps and leaves its CU, the workgroups taking the frames by descending t_f (ranked on the device): the
+ *     same bits.  lccrf_batch_get_backward_route reports the route of this call.
+ *   - Everything else is section 2c's contract: it needs lccrf_batch_build or _run first (LCCRF_E_STATE otherwise); a pending
+ *     one-launch run is settled first; deterministic, no float atomics; the batch-owned area is section 2c's with T = max_iterations
+ *     and is never allocated by inference calls; LCCRF_E_INVALID for max_iterations < 0 or a relax that is not finite (these two and
+ *     the NULL d_iterations are answered before the batch is looked at); a rejected call leaves the batch as it was; d_grad_weights
+ *     may be NULL, K = 0 is legal.
+ *   - Potts terms normalised AFTER only, as section 2c: on a batch with a matrix or a mode other than AFTER the call returns
+ *     LCCRF_E_STATE and leaves the batch as it was.  Not covered (notes/convergence.md section 6): learnt models in section 2h's form,
+ *     feature gradients, the one-launch kernels of sections 1k and 1l.
+ * ==================================================================================== */
+int  lccrf_batch_inference_backward_converged(lccrf_batch_handle b, int max_iterations, float relax, const int32_t *d_iterations,
+                                              const float *d_grad_prob, float *d_grad_unary, float *d_grad_weights, void *stream);
+
+/* ======================================================================================
  * 3. Unary builder -- the step right before the CRF (first "next" row):
  *    Tracking::ComputeMapPointErrAndObserv (src/Tracking.cc:1803-1839) for every candidate map
  *    point, then Tracking::RroughClassify (src/Tracking.cc:1961-2013).  The caller flattens the

@@ -213,6 +213,8 @@ def lib():
     L.lccrf_batch_inference_backward_features.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, C.POINTER(vp), vp]
     L.lccrf_batch_inference_backward_all.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, C.POINTER(vp), vp, vp, vp]
     L.lccrf_batch_inference_backward_modes.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, C.POINTER(vp), vp, vp, vp]
+    if hasattr(L, "lccrf_batch_inference_backward_converged"):                    # (section 2j: probe by symbol)
+        L.lccrf_batch_inference_backward_converged.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, vp, vp]
     L.lccrf_batch_set_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p]
     L.lccrf_batch_get_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p, C.POINTER(C.c_int)]
     L.lccrf_batch_set_pairwise_normalization.argtypes = [vp, C.c_int, C.c_int]
@@ -728,6 +730,15 @@ class BatchCRF(_Handle):
         [n_frames][max_points][L]; device addresses (include/lccrf.h section 2c)."""
         _check(lib().lccrf_batch_inference_backward(self.h, int(n_iterations), float(relax), C.c_void_p(int(d_grad_prob)),
                                                     C.c_void_p(int(d_grad_unary)), _addr(d_grad_weights), _addr(stream)))
+
+    def inference_backward_converged_device(self, max_iterations, relax, d_iterations, d_grad_prob, d_grad_unary, d_grad_weights=None,
+                                            stream=None):
+        """inference_backward_device with every frame at its own iteration count (include/lccrf.h section 2j): d_iterations is the
+        device address of [n_frames] int32 -- device_convergence()["iterations"] behind inference_converged(), or a copy of it --
+        clamped per frame to [0, max_iterations] by the kernels and never read by the host."""
+        _check(lib().lccrf_batch_inference_backward_converged(self.h, int(max_iterations), float(relax), _addr(d_iterations),
+                                                              C.c_void_p(int(d_grad_prob)), C.c_void_p(int(d_grad_unary)),
+                                                              _addr(d_grad_weights), _addr(stream)))
 
     def inference_backward_features_device(self, n_iterations, relax, d_grad_prob, d_grad_unary=None, d_grad_weights=None,
                                            d_grad_features=None, stream=None):

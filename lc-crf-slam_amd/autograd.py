@@ -1,4 +1,4 @@
-"""torch autograd through DenseCRF::inference on the HIP path (include/lccrf.h sections 1c - 1g, 1m and 2c).
+"""torch autograd through DenseCRF::inference on the HIP path (include/lccrf.h sections 1c - 1g, 1m, 2c and 2j).
 
     Q = mean_field(crf, unary, weights, n_iterations=5, relax=1.0)
     Q.backward(g)      # -> unary.grad = dL/dU, weights.grad = dL/dw
@@ -8,6 +8,12 @@
 
     Q = mean_field_batch_compat(batch, unary, weights, compat, n_iterations=5, relax=1.0)    # ... with a [K, L, L] compatibility
     Q.backward(g)      # -> also compat.grad; both sums over the frames come from the batch's own call (section 2h)
+
+    Q, t = mean_field_converged(crf, unary, weights, max_iterations=12)         # "until converged, at most 12" (section 1h)
+    Q.backward(g)      # -> the gradients at the reported count t (section 1h's recipe)
+
+    Q, t = mean_field_batch_converged(batch, unary, weights, max_iterations=12)   # every frame stops on its own; t [F] int32
+    Q.backward(g)      # -> every frame differentiated at ITS count, in one call (section 2j)
 
     Q = mean_field_features(unary, [f_0, f_1, ..], weights, n_iterations=5, relax=1.0)        # the features are inputs too
     Q.backward(g)      # -> also f_k.grad = dL/d features [N, d_k] (section 1d); LearnedKernelCRF fits kernel bandwidths with it
@@ -25,8 +31,8 @@
 inputs here).  Forward: lccrf_set_pairwise_weight + lccrf_set_unary_device + lccrf_inference.  Backward:
 lccrf_inference_backward, which replays the forward itself, so nothing but the inputs is kept between the two.
 
-Three autograd Functions stand behind the six: one bound to a caller's handle, one to a caller's batch, one to a handle of its own
-with the features as inputs; each takes `compat` or None (Potts terms).  notes/torch_layers.md has the entry point each one calls.
+Three autograd Functions stand behind them all: one bound to a caller's handle, one to a caller's batch, one to a handle of its own
+with the features as inputs; each takes `compat` or None (Potts terms), and the first two a stop rule or None (a fixed count).  notes/torch_layers.md has the entry point each one calls.
 
 Streams (the pattern of section 1b): on entry the handle's stream waits for torch's current stream (the inputs and the
 incoming gradient are produced there); on exit torch's current stream waits for the handle's stream.  inference()
@@ -42,10 +48,10 @@ import torch
 _pkg = importlib.import_module("lc-crf-slam_amd")
 
 
-def _device_view(ptr, shape, device):
+def _device_view(ptr, shape, device, typestr="<f4"):
     """A tensor over handle-owned device memory (no copy)."""
     class _View:
-        __cuda_array_interface__ = dict(shape=tuple(shape), typestr="<f4", data=(int(ptr), False), version=2)
+        __cuda_array_interface__ = dict(shape=tuple(shape), typestr=typestr, data=(int(ptr), False), version=2)
     return torch.as_tensor(_View(), device=device)
 
 
@@ -91,6 +97,12 @@ def _forward_q(crf, u, n_iterations, relax, ext, cur):
     crf.inference(int(n_iterations), False, float(relax))
     crf.synchronize()                                         # the completion rule of inference() results
     return _clone_q(crf.device_buffers()["current"], tuple(u.shape), u.device, ext, cur)
+
+
+def _check_stop(stop, compat):
+    """stop: None (a fixed count) or (criterion, tol) of "until converged, at most n_iterations" -- Potts terms only"""
+    if stop is not None and compat is not None:
+        raise ValueError("the converged layers take Potts terms only (include/lccrf.h section 2j)")
 
 
 def _model(weights, compat):
@@ -155,24 +167,34 @@ def _identities(K, L):
 
 # ---- a caller's handle -----------------------------------------------------------------------------------------------------------
 class _MeanField(torch.autograd.Function):
-    """mean_field (compat None) and mean_field_compat on a caller's DenseCRFHIP"""
+    """mean_field (compat None), mean_field_compat and -- with a stop rule -- mean_field_converged on a caller's DenseCRFHIP"""
 
     @staticmethod
-    def forward(ctx, crf, unary, weights, compat, n_iterations, relax):
+    def forward(ctx, crf, unary, weights, compat, n_iterations, relax, stop):
         _check_unary_weights(unary, (crf.N, crf.L), weights, len(crf._d))
         _check_compat_iterations(compat, len(crf._d), crf.L, n_iterations)
+        _check_stop(stop, compat)
         u = unary.detach().contiguous()
         w, m = _model(weights, compat)
         with _on_stream(crf.stream(), u.device) as (ext, cur):
             _arm(crf, w, m)
             crf.set_unary_device(u.data_ptr())
-            q = _forward_q(crf, u, n_iterations, relax, ext, cur)
+            if stop is None:
+                q = _forward_q(crf, u, n_iterations, relax, ext, cur)
+            else:                                             # (section 1h: the backward is the fixed-count one at the reported count)
+                n_iterations = crf.inference_converged(int(n_iterations), int(stop[0]), float(stop[1]), False, float(relax))["iterations"]
+                crf.synchronize()
+                q = _clone_q(crf.device_buffers()["current"], tuple(u.shape), u.device, ext, cur)
         _remember(ctx, crf, n_iterations, relax, weights, compat)
         ctx.save_for_backward(u, w, m)
-        return q
+        if stop is None:
+            return q
+        it = torch.tensor(n_iterations, dtype=torch.int32, device=u.device)
+        ctx.mark_non_differentiable(it)
+        return q, it
 
     @staticmethod
-    def backward(ctx, grad_q):
+    def backward(ctx, grad_q, *_):
         u, w, m = ctx.saved_tensors
         crf, dev, K = ctx.target, u.device, int(w.numel())
         g = _grad_in(grad_q, dev)
@@ -184,20 +206,27 @@ class _MeanField(torch.autograd.Function):
             # (without d_grad_compat the call is lccrf_inference_backward, section 1c)
             crf.inference_backward_compat_device(ctx.n_iterations, ctx.relax, g.data_ptr(), grad_u.data_ptr(), grad_w_ptr,
                                                  None if grad_m is None else grad_m.data_ptr())
-        return (None, grad_u) + _model_grads(ctx, grad_w, grad_m, K) + (None, None)
+        return (None, grad_u) + _model_grads(ctx, grad_w, grad_m, K) + (None, None, None)
 
 
 def mean_field(crf, unary, weights, n_iterations=5, relax=1.0):
     """Q_T of DenseCRF::inference(n_iterations, relax) with unary energies `unary` [N, L] (float32, GPU) and pairwise
     weights `weights` [K] (float32, any device) on the terms of `crf`; differentiable in both."""
-    return _MeanField.apply(crf, unary, weights, None, n_iterations, relax)
+    return _MeanField.apply(crf, unary, weights, None, n_iterations, relax, None)
 
 
 def mean_field_compat(crf, unary, weights, compat, n_iterations=5, relax=1.0):
     """mean_field with a label-compatibility matrix per term (include/lccrf.h section 1e): `compat` [K, L, L] (float32, any
     device), term k adding w_k * norm_k * (Phi_k(Q) @ compat[k].T); differentiable in unary, weights and compat.  The matrices
     are left set on `crf`."""
-    return _MeanField.apply(crf, unary, weights, compat, n_iterations, relax)
+    return _MeanField.apply(crf, unary, weights, compat, n_iterations, relax, None)
+
+
+def mean_field_converged(crf, unary, weights, max_iterations, criterion=_pkg.STOP_LABELS, tol=0.0, relax=1.0):
+    """mean_field "until converged, at most max_iterations" (include/lccrf.h section 1h: criterion a STOP_* bit set, tol for STOP_DELTA):
+    returns (Q_t, t) -- t the reported iteration count, an int32 scalar tensor, not differentiable -- and the backward is mean_field's
+    at t, section 1h's recipe for the gradient of the converged result."""
+    return _MeanField.apply(crf, unary, weights, None, max_iterations, relax, (criterion, tol))
 
 
 class _HandleCRF(torch.nn.Module):
@@ -258,32 +287,46 @@ class CompatMeanFieldCRF(_HandleCRF):
 
 # ---- a caller's batch ------------------------------------------------------------------------------------------------------------
 class _MeanFieldBatch(torch.autograd.Function):
-    """mean_field_batch (compat None) and mean_field_batch_compat on a caller's BatchCRF.  The two backwards are different calls:
-    without matrices section 2c, which refuses a batch that carries matrices or modes, and torch's sum of its [F, K] output; with
-    them section 2h, whose model gradients are the batch's own ordered sums over the frames."""
+    """mean_field_batch (compat None), mean_field_batch_compat and -- with a stop rule -- mean_field_batch_converged on a caller's
+    BatchCRF.  The backwards are different calls: without matrices section 2c, which refuses a batch that carries matrices or modes,
+    and torch's sum of its [F, K] output (under a stop rule section 2j, section 2c at every frame's own count); with them section 2h,
+    whose model gradients are the batch's own ordered sums over the frames."""
 
     @staticmethod
-    def forward(ctx, batch, unary, weights, compat, n_iterations, relax, n_points):
+    def forward(ctx, batch, unary, weights, compat, n_iterations, relax, n_points, stop):
         F, N, L = batch.n_frames, batch.maxN, batch.L
         _check_unary_weights(unary, (F, N, L), weights, len(batch.dims))
         _check_compat_iterations(compat, len(batch.dims), L, n_iterations)
+        _check_stop(stop, compat)
         dev = unary.device
         u = unary.detach().contiguous()
         w, m = _model(weights, compat)
+        it = None
         with _on_stream(batch.own_stream(), dev) as (ext, cur):
             _arm(batch, w, m)
             batch.set_unary_device(u.data_ptr())
-            batch.inference(int(n_iterations), False, float(relax))      # (leaves nothing to settle)
+            if stop is None:
+                batch.inference(int(n_iterations), False, float(relax))      # (leaves nothing to settle)
+            else:
+                batch.inference_converged(int(n_iterations), int(stop[0]), float(stop[1]), False, float(relax))
+                # the counts, CLONED on the batch's stream: the backward re-arms the batch and sets the unaries again, which may
+                # invalidate the stored report
+                with torch.cuda.stream(ext):
+                    it = _device_view(batch.device_convergence()["iterations"], (F,), dev, "<i4").clone()
+                it.record_stream(cur)
             q = _clone_q(batch.device_buffers()[1], (F, N, L), dev, ext, cur)
         live = torch.arange(N, device=dev)[None, :] < torch.as_tensor(n_points, device=dev)[:, None]
         q = torch.where(live[:, :, None], q, torch.zeros((), device=dev))    # rows beyond a frame's points: 0
         _remember(ctx, batch, n_iterations, relax, weights, compat)
-        ctx.save_for_backward(u, w, m)
-        return q
+        ctx.save_for_backward(u, w, m, it)
+        if it is None:
+            return q
+        ctx.mark_non_differentiable(it)
+        return q, it
 
     @staticmethod
-    def backward(ctx, grad_q):
-        u, w, m = ctx.saved_tensors
+    def backward(ctx, grad_q, *_):
+        u, w, m, it = ctx.saved_tensors
         batch, dev = ctx.target, u.device
         K, L = int(w.numel()), batch.L
         g = _grad_in(grad_q, dev)
@@ -295,22 +338,25 @@ class _MeanFieldBatch(torch.autograd.Function):
         with _on_stream(batch.own_stream(), dev):
             _arm(batch, w, m)                                 # the inputs of this forward (the batch may have run others since)
             batch.set_unary_device(u.data_ptr())
-            if m is None:
+            if it is not None:                                # (section 2j: the cap, and every frame's own count from the device)
+                batch.inference_backward_converged_device(ctx.n_iterations, ctx.relax, it.data_ptr(), g.data_ptr(), grad_u.data_ptr(),
+                                                          grad_w.data_ptr() if K else None)
+            elif m is None:
                 batch.inference_backward_device(ctx.n_iterations, ctx.relax, g.data_ptr(), grad_u.data_ptr(),
                                                 grad_w.data_ptr() if K else None)
             else:
                 batch.inference_backward_all_device(ctx.n_iterations, ctx.relax, g.data_ptr(), grad_u.data_ptr(),
                                                     d_grad_model=model.data_ptr() if K else None)
         if m is None:
-            return None, grad_u, grad_w[:, :K].sum(0).to(ctx.weights_device), None, None, None, None
+            return None, grad_u, grad_w[:, :K].sum(0).to(ctx.weights_device), None, None, None, None, None
         return (None, grad_u, model[:K].to(ctx.weights_device), model[K:K * (1 + L * L)].reshape(K, L, L).to(ctx.compat_device),
-                None, None, None)
+                None, None, None, None)
 
 
-def _apply_batch(batch, unary, weights, compat, n_iterations, relax):
+def _apply_batch(batch, unary, weights, compat, n_iterations, relax, stop=None):
     if batch.n_points is None:
         raise ValueError("the batch's point counts are on the device only (bind_inputs_device): set its inputs from the host")
-    return _MeanFieldBatch.apply(batch, unary, weights, compat, n_iterations, relax, batch.n_points)
+    return _MeanFieldBatch.apply(batch, unary, weights, compat, n_iterations, relax, batch.n_points, stop)
 
 
 def mean_field_batch(batch, unary, weights, n_iterations=5, relax=1.0):
@@ -327,6 +373,15 @@ def mean_field_batch_compat(batch, unary, weights, compat, n_iterations=5, relax
     the frames of dL/dw and dL/dmu, formed by the batch's own call in ascending frame order (no torch reduction).  The matrices are left
     set on `batch`; its normalisation modes are honoured."""
     return _apply_batch(batch, unary, weights, compat, n_iterations, relax)
+
+
+def mean_field_batch_converged(batch, unary, weights, max_iterations, criterion=_pkg.STOP_LABELS, tol=0.0, relax=1.0):
+    """mean_field_batch "until converged, at most max_iterations": every frame stops on its own (include/lccrf.h section 2e; criterion
+    a STOP_* bit set, tol for STOP_DELTA).  Returns (Q [F, max_points, L], iterations [F] int32 on the GPU, not differentiable): frame
+    f's rows are Q_{t_f}, t_f = iterations[f], a clone of the batch's device report.  The backward differentiates every frame at its
+    own t_f in one call on those counts, which never visit the host (section 2j); unary.grad and weights.grad as mean_field_batch.
+    Potts terms normalised AFTER only."""
+    return _apply_batch(batch, unary, weights, None, max_iterations, relax, (criterion, tol))
 
 
 class _BatchCRF(torch.nn.Module):
@@ -368,6 +423,23 @@ class BatchMeanFieldCRF(_BatchCRF):
 
     def forward(self, unary):
         return mean_field_batch(self.batch, unary, self.weights, self.n_iterations, self.relax)
+
+
+class BatchConvergedMeanFieldCRF(_BatchCRF):
+    """BatchMeanFieldCRF under the stop rule the model is deployed with: forward(unary [F, max_points, L]) -> (Q [F, max_points, L],
+    iterations [F] int32) through mean_field_batch_converged -- every frame inferred until ITS criterion holds, at most max_iterations,
+    and differentiated at its own count (include/lccrf.h sections 2e and 2j).  criterion, tol: as BatchCRF.inference_converged takes
+    them; fused_backward: sets OPT_FUSED_BACKWARD on the batch (section 1j: the same gradients, in one launch where the frames fit)."""
+
+    def __init__(self, n_points, features, weights, max_iterations=12, criterion=_pkg.STOP_LABELS, tol=0.0, relax=1.0, device=0,
+                 n_labels=2, fused_backward=False):
+        super().__init__(n_points, features, weights, max_iterations, relax, device, n_labels)
+        self.criterion, self.tol = int(criterion), float(tol)
+        if fused_backward:
+            self.batch.set_option(_pkg.OPT_FUSED_BACKWARD, 1)
+
+    def forward(self, unary):
+        return mean_field_batch_converged(self.batch, unary, self.weights, self.n_iterations, self.criterion, self.tol, self.relax)
 
 
 class BatchCompatMeanFieldCRF(_BatchCRF):

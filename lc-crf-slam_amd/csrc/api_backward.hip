@@ -1,4 +1,4 @@
-// api_backward.hip -- gradients of mean-field inference: sections 1c - 1f, 1m (a handle) and 2c, 2d, 2h, 2i (a batch) of include/lccrf.h.
+// api_backward.hip -- gradients of mean-field inference: sections 1c - 1f, 1m (a handle) and 2c, 2d, 2h - 2j (a batch) of include/lccrf.h.
 //
 // One path behind every entry point (backward_call); the replay and the sweep themselves are Engine::backward (host_engine.hip) and
 // meanfield_backward.hip; the route getters of section 1j are in api_model.hip.
@@ -34,6 +34,7 @@ static int backward_call(const BackwardTarget &t, const BackwardRequest &rq, boo
     if ((rc = check_device_array(e, rq.grad_prob, nl * sizeof(float), "d_grad_prob"))) return rc;
     if ((need_grad_unary || rq.grad_unary) && (rc = check_device_array(e, rq.grad_unary, nl * sizeof(float), "d_grad_unary"))) return rc;
     if (rq.grad_weights && (rc = check_device_array(e, rq.grad_weights, e.F * K * sizeof(float), "d_grad_weights"))) return rc;
+    if (rq.counts && (rc = check_device_array(e, rq.counts, e.F * sizeof(int32_t), "d_iterations"))) return rc;
     for (size_t k = 0; k < K && rq.grad_features; ++k)
         if (rq.grad_features[k] &&
             (rc = check_device_array(e, rq.grad_features[k], points * e.kernels[k].dev.d * sizeof(float), "d_grad_features[k]")))
@@ -142,6 +143,24 @@ int lccrf_batch_inference_backward(lccrf_batch_handle b, int n_iterations, float
     CHECK_H(b);
     if (int rc = batch_is_plain(b)) return rc;
     const BackwardRequest rq{n_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
+    return backward_call(backward_target(b, stream), rq, kGradUnaryRequired);
+}
+
+// --------------------------------------------------------------------------------------
+// section 2j: section 2c with one iteration count per frame -- the gradients of lccrf_batch_inference_converged's result.  The counts
+// stay on the device (the kernels clamp them to [0, max_iterations]); what needs no handle is checked before the handle is looked at,
+// so those answers need no device.
+
+int lccrf_batch_inference_backward_converged(lccrf_batch_handle b, int max_iterations, float relax, const int32_t *d_iterations,
+                                             const float *d_grad_prob, float *d_grad_unary, float *d_grad_weights, void *stream)
+{
+    if (max_iterations < 0) return fail(LCCRF_E_INVALID, "max_iterations < 0");
+    if (!std::isfinite(relax)) return fail(LCCRF_E_INVALID, "relax must be finite");
+    if (!d_iterations) return fail(LCCRF_E_INVALID, "d_iterations is NULL");
+    CHECK_H(b);
+    if (int rc = batch_is_plain(b)) return rc;
+    BackwardRequest rq{max_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
+    rq.counts = d_iterations;
     return backward_call(backward_target(b, stream), rq, kGradUnaryRequired);
 }
 

@@ -359,6 +359,9 @@ struct BackwardRequest {           // (an aggregate: the members left out of a b
     float *grad_compat;             // [F][K][L][L] or null (sections 1e / 1f: F = 1; section 2h)
     bool compat_form;               // the sweep takes section 1e's form: the terms' matrices are honoured (grad_compat needs it)
     float *grad_model;              // [K + K*L*L] or null (section 2h): the sums over the frames of dL/dw and dL/dmu (needs compat_form)
+    // [F] int32 on the device or null (section 2j): frame f is differentiated at t_f = min(max(counts[f], 0), T) iterations, T the cap
+    // every [T] part of the area is sized by; the kernels clamp, the host never reads the array.  Only with grad_unary / grad_weights.
+    const int *counts;
 };
 // The area of one backward call, owned by the engine and zeroed when allocated: Q_0 .. Q_{T-1} of the replay, one [F][.][L] array
 // per term, dL/dQ_t, the per-workgroup partials of the weight gradient, and the parts the request asks for beyond those.  Every
@@ -416,6 +419,9 @@ size_t backward_layout(const BackwardRequest &rq, const CrfDev &c, const KernelD
 // the pre adjoint to ar.gn[k], and the norm part forms g_n by the term's mode (none for LCCRF_NORMALIZE_NONE).
 // rq.grad_model (section 2h; null for a handle: not a launch more): dL/dw and dL/dmu of every frame -- in the caller's arrays, or in
 // ar.gW / ar.gC where the caller left one out -- are summed over the frames in ascending order, one k_sum_frames launch each.
+// rq.counts (section 2j; null: the launches and the arithmetic above, untouched): frame f is idle while t > t_f -- its G stays the
+// caller's dL/dQ, nothing is added to its dL/dU, no partial is written for it; its filters run on (phi is scratch) -- its first step
+// is t == t_f, and the weight gradient's reduction walks its t_f x blocks partials: a handle's bits at t_f.
 struct BackwardModes {
     int mode[LCCRF_MAX_KERNELS];
     const float *norm[LCCRF_MAX_KERNELS];   // [F][maxN], KernelDev::norm of the engine's own views (not of step_kdevs())
@@ -446,6 +452,11 @@ int launch_fused_backward_features(const CrfDev &c, const KernelDev *kds, const 
                                    const BackwardRequest &rq, const BackwardArea &ar, hipStream_t s);
 // out[j] = sum over the frames, in ascending order, of x[f][j], j < n (section 2h; meanfield_backward.hip)
 void launch_sum_frames(const float *x, int F, int n, float *out, hipStream_t s);
+// Q of every frame whose count is below the cap <- hist[t_f] (section 2j: the replay steps every frame T times; Q_{t_f} is what stays)
+void launch_restore_counted_q(const CrfDev &c, const BackwardArea &ar, int T, const int *counts, hipStream_t s);
+// order[0 .. F) <- the frames by descending t_f = min(max(counts[f], 0), T), equal counts by ascending frame: a permutation of 0 .. F-1,
+// formed on the device (section 2j: the one-launch backward hands its workgroups the longest frames first)
+void launch_order_by_count(const int *counts, int F, int T, int *order, hipStream_t s);
 
 // ---- one run, its terms, and what a converged one reports: what the launch requests below are made of ---------------------------
 // One run: a fixed count of n_iter iterations, or -- until_converged -- at most n_iter under (criterion, tol) (include/lccrf.h

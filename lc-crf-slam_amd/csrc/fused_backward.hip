@@ -13,6 +13,9 @@
 //                       Phi_k^T(n_k gamma_t)                  splat_blur<.., GEN, TRANSPOSE>: the input n_k * gamma, rounded once
 //                       G_{t-1} = (1 - r) G_t + sum_k w_k .   k_bwd_combine<false>'s arithmetic
 //     the softmax backward of Q_0, and k_bwd_reduce's walk and tree over the frame's T x ceil(N / 256) partials
+// With per-frame counts (section 2j) T above is the frame's own t_f, loaded once per workgroup: a frame that stopped early leaves its CU
+// early, and the Q it leaves is Q_{t_f}.  Workgroup i then takes frame order[i], the frames sorted by descending t_f on the device
+// (k_order_by_count, meanfield_backward.hip): which workgroup runs a frame changes no bit of it.
 //
 // Bit for bit the streaming sweep's results: every product and every sum is the one the streaming kernels form, in their order
 // (-ffp-contract=off).  A row sum starts at +0 and adds the products in ascending point order (k_splat<false>); the slices start
@@ -52,6 +55,8 @@ struct BackwardArgs {
     float *gU;                            // [F][maxN][2]
     float *gW;                            // [F][K] or null
     float *partial;                       // [T][K][F][bstride]
+    const int *counts;                    // [F] or null (section 2j): frame f runs min(max(counts[f], 0), T) iterations, T the layout's
+    const int *order;                     // [F] or null: workgroup i takes frame order[i] (a permutation: the longest counts first)
 };
 
 // (gamma2 and slice_signed, the sweep's row arithmetic: fused_backward_common.h, shared with k_backward_general)
@@ -64,7 +69,7 @@ __global__ void __launch_bounds__(kNT, 4) k_backward(CrfDev c, BackwardArgs a)
 {
     constexpr int D1 = kD1, NT = kNT, ALL = (1 << K) - 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int f = blockIdx.x;
+    const int f = a.order ? a.order[blockIdx.x] : blockIdx.x;
     int tid = threadIdx.x;
     const int N = c.n_points[f];
     Instr ins{nullptr, 0, 0, 0, 0};
@@ -76,6 +81,10 @@ __global__ void __launch_bounds__(kNT, 4) k_backward(CrfDev c, BackwardArgs a)
         if (a.gW && tid < K) a.gW[(size_t)f * K + tid] = 0.0f;
         return;
     }
+
+    // the frame's own iteration count (section 2j): one uniform load per workgroup, so every barrier below stays uniform; hist and
+    // partial keep their [a.T][...] layout
+    const int T = a.counts ? min(max(a.counts[f], 0), a.T) : a.T;
 
     PointRegs<PPT, K> pr;
     GeneralTerms<PPT, K> gt;
@@ -100,7 +109,7 @@ __global__ void __launch_bounds__(kNT, 4) k_backward(CrfDev c, BackwardArgs a)
     // ---- the replay: inference(T, 0, relax), keeping Q_0 .. Q_{T-1} -------------------------------------------------------------
     const size_t hs = a.slice / 2;        // float2 between the iterations of hist
     float2 *hist = reinterpret_cast<float2 *>(a.hist) + fo;
-    for (int t = 0; t < a.T; ++t) {
+    for (int t = 0; t < T; ++t) {
         opaque(pr);
 #pragma unroll
         for (int s = 0; s < PPT; ++s)
@@ -137,11 +146,11 @@ __global__ void __launch_bounds__(kNT, 4) k_backward(CrfDev c, BackwardArgs a)
     // chain kernel has no scalar register left for them
     int pterm = (int)gridDim.x * a.bstride, prow = f * a.bstride;
     asm volatile("" : "+v"(pterm), "+v"(prow));
-    const float2 *hq = hist + (size_t)a.T * hs;
-    for (int t = a.T; t >= 1; --t) {
+    const float2 *hq = hist + (size_t)T * hs;
+    for (int t = T; t >= 1; --t) {
         opaque(pr);
         asm volatile("" : "+v"(tid));
-        const bool first = t == a.T;                                      // dL/dQ_t is the caller's, dL/dU is written
+        const bool first = t == T;                                        // dL/dQ_t is the caller's, dL/dU is written
         hq -= hs;                                                         // Q_{t-1}
         // Phi_k(Q_{t-1})
 #pragma unroll
@@ -230,7 +239,7 @@ __global__ void __launch_bounds__(kNT, 4) k_backward(CrfDev c, BackwardArgs a)
 
     // ---- dL/dU -= P_0 (G_0 - <G_0, P_0>), P_0 = Q_0 = softmax(-U) ---------------------------------------------------------------
     {
-        const bool first = a.T == 0;
+        const bool first = T == 0;
 #pragma unroll
         for (int s = 0; s < PPT; ++s) {
             const int i = tid + s * NT;
@@ -253,7 +262,7 @@ __global__ void __launch_bounds__(kNT, 4) k_backward(CrfDev c, BackwardArgs a)
     const int k = tid / kPartialRows, j = tid - k * kPartialRows;
     if (k < K) {
         const float *row = a.partial + (size_t)k * pterm + prow;             // this frame's partials of term k, iteration 1
-        const int n = a.T * nblk;
+        const int n = T * nblk;
         float acc = 0.0f;
         for (int idx = j; idx < n; idx += kPartialRows) {
             const int t = idx / nblk, b = idx - t * nblk;
@@ -288,7 +297,14 @@ int launch_fused_backward(const CrfDev &c, const KernelDev *kds, const int *maxV
     a.gU = rq.grad_unary ? rq.grad_unary : ar.gU;
     a.gW = rq.grad_weights;
     a.partial = ar.partial;
+    a.counts = rq.counts;
     return plan_variant<kBackwardMaxPPT>(c, kds, maxV, maxRow, kBackwardLds, a, [&](auto p, auto kk, auto ch) {
+        // (section 2j) workgroups start in index order as CUs fall free: with the longest frames first the last CU to finish holds a short
+        // one.  The order lives in the area's `phi`, which this kernel does not touch (K * slice floats: room for F ints).
+        if (rq.counts && (size_t)c.K * ar.slice >= (size_t)c.F) {
+            launch_order_by_count(rq.counts, c.F, rq.T, reinterpret_cast<int *>(ar.phi), s);
+            a.order = reinterpret_cast<const int *>(ar.phi);
+        }
         launch_workgroups(k_backward<decltype(p)::value, decltype(kk)::value, decltype(ch)::value>, c.F, kNT, a.lay.total + kBackwardLds, s, c,
                           a);
     });

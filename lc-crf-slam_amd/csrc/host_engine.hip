@@ -60,6 +60,7 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
     // LCCRF_OPT_FUSED_BACKWARD (include/lccrf.h section 1j): dL/dU and / or dL/dw of Potts terms normalised AFTER, on frames the fused
     // plan takes -- the replay and the sweep in one launch, the same bits (fused_backward.hip).  Decided for the whole batch, over its
     // largest frame and lattices; behind every check and the area, so a rejected call leaves the handle as it was either way.
+    // With rq.counts (section 2j) too: each frame's workgroup then runs its own t_f iterations; the other one-launch kernels take none.
     const bool plain_form = !rq.compat_form && !rq.grad_compat && !rq.grad_model;   // (not the compat form: no dL/dmu, no sums, no matrix)
     bool no_features = true;
     for (int k = 0; k < K && rq.grad_features; ++k) no_features &= rq.grad_features[k] == nullptr;
@@ -73,7 +74,7 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
     // LCCRF_OPT_FUSED_BACKWARD_LEARNT (section 1k): the complement among the requests without feature gradients -- a learnt model
     // (a matrix, or a mode other than AFTER), or the compat form (dL/dmu, also of Potts terms) -- decided in the same place and the
     // same way (fused_backward_general.hip).  The sums over the frames (section 2h) are the sweep's two launches, behind the kernel.
-    if (opt.fused_backward_learnt && no_features && count && (model.general() || rq.compat_form) && !perm_on &&
+    if (opt.fused_backward_learnt && !rq.counts && no_features && count && (model.general() || rq.compat_form) && !perm_on &&
         launch_fused_backward_general(crf, step_kdevs(), maxV.data(), maxRow.data(), rows, rq, ar, model.terms((size_t)K), stream)) {
         if (rq.grad_model) {
             launch_sum_frames(rq.grad_weights ? rq.grad_weights : ar.gW, F, K, rq.grad_model, stream);
@@ -86,7 +87,7 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
     // LCCRF_OPT_FUSED_BACKWARD_FEATURES (section 1l): a request with at least one feature array, not in the compat form, on Potts terms
     // normalised AFTER and T >= 1 (T = 0 streams: the memset below to exactly 0 is already right) -- decided in the same place and the
     // same way (fused_backward_features.hip).  The kernel initialises the area's gb / gn itself: no memset in front of it.
-    if (opt.fused_backward_features && !no_features && plain_form && count && T >= 1 && !model.general() && !perm_on &&
+    if (opt.fused_backward_features && !rq.counts && !no_features && plain_form && count && T >= 1 && !model.general() && !perm_on &&
         launch_fused_backward_features(crf, kdevs.data(), maxV.data(), maxRow.data(), rows, rq, ar, stream)) {
         HIP_TRY(hipGetLastError());
         report.backward(LCCRF_BACKWARD_FUSED);
@@ -96,6 +97,9 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
         if (count) HIP_TRY(hipMemcpyAsync(ar.hist + (size_t)t * slice, crf.Q, count * sizeof(float), hipMemcpyDeviceToDevice, stream));
         if ((rc = step(rq.relax))) return rc;
     }
+    // (section 2j: the replay stepped every frame T times -- wasted work on a frame that stopped earlier, not a different result -- and
+    // the Q left behind is the frame's own Q_{t_f}, out of the history)
+    if (rq.counts && count) launch_restore_counted_q(crf, ar, T, rq.counts, stream);
     // (section 2h: the per-frame values behind grad_model live in the area where the caller left their own array out)
     float *const grad_weights = rq.grad_weights ? rq.grad_weights : ar.gW, *const grad_compat = rq.grad_compat ? rq.grad_compat : ar.gC;
     if (grad_compat && K && (!count || T == 0))       // nothing depends on the matrices: exactly 0, in every frame

@@ -77,7 +77,12 @@ struct BwdArgs {
     int gnstride;
     const float *compat[kBwdMaxK];   // k_compat_softmax<G>: the term's [L][L] matrix mu_k, or null (Potts)
     float *gam;                  // ... and [F][maxN][L]: receives gamma_t (phi is left as it came: k_compat_bwd turns it over)
+    const int *counts;           // [F] or null (section 2j): the frame's own iteration count, clamped to [0, cap] by frame_count
+    int t, cap;                  // ... the sweep's iteration of this launch (0: the softmax backward of Q_0) and the counts' cap
 };
+
+// section 2j: the iterations frame f is differentiated at -- the caller's count clamped to [0, cap]
+__device__ __forceinline__ int frame_count(const int *__restrict__ counts, int f, int cap) { return min(max(counts[f], 0), cap); }
 
 enum { kBwdPlain = 0, kBwdFeat = 1, kBwdCompat = 2, kBwdCompatFeat = 3 };   // what k_softmax_bwd does besides section 1c's work (bits: feature, compat)
 
@@ -138,7 +143,13 @@ __device__ __forceinline__ void softmax_bwd(const BwdArgs &a)
     const int i = blockIdx.x * (kBwdBlock / G) + (int)threadIdx.x / G;
     const bool live = i < N;
     const int l0 = sub * 4;
-    if (a.first && !live && i < a.rows) {                 // rows beyond the frame's points: dL/dU = 0
+    int begins = a.first;                                 // this launch is the frame's first step: dL/dU is written, not added to
+    if (a.counts) {                                       // (section 2j; uniform over the workgroup: blockIdx.y alone decides)
+        const int tf = frame_count(a.counts, f, a.cap);
+        if (a.t > tf) return;                             // an idle frame: nothing written, before any barrier
+        begins = a.t == tf;
+    }
+    if (begins && !live && i < a.rows) {                  // rows beyond the frame's points: dL/dU = 0
         const size_t z = f * a.fs + (size_t)i * L + l0;
 #pragma unroll
         for (int u = 0; u < 4; ++u)
@@ -221,7 +232,7 @@ __device__ __forceinline__ void softmax_bwd(const BwdArgs &a)
         if (!has[u]) continue;
         const float gam = a.relax * (p[u] * ((g[u] - ga) - dev));
         if (FEAT) gamv[u] = gam;
-        a.gU[q + u] = a.first ? -gam : a.gU[q + u] - gam;
+        a.gU[q + u] = begins ? -gam : a.gU[q + u] - gam;
         if (COMPAT) a.gam[q + u] = gam;
 #pragma unroll
         for (int k = 0; k < kBwdMaxK; ++k)
@@ -286,14 +297,18 @@ __global__ void __launch_bounds__(kBwdBlock) k_joint_softmax(BwdArgs a)
 // PRE (section 1g): a term whose filter input is scaled by b_k (pre.p[k], [F][nstride]; null: 1) adds w_k * (b_k[i] * buf_k) -- the
 // transposed filter's result goes back through the input's factor.  PRE = false is the code it was.
 struct BwdPre { const float *p[kBwdMaxK]; int nstride; };
+// cn (section 2j; counts null: every frame takes the step): a frame whose count is below this launch's iteration is idle -- its G
+// stays the caller's dL/dQ.
+struct BwdCounts { const int *counts; int t, cap; };
 template <bool PRE>
 __global__ void __launch_bounds__(kBwdBlock) k_bwd_combine(const int *__restrict__ n_points, int L, int K, const float *__restrict__ buf,
                                                          size_t slice, size_t fs, BwdWeights wk, float keep, float *__restrict__ G,
-                                                         BwdPre pre)
+                                                         BwdPre pre, BwdCounts cn)
 {
     const int f = blockIdx.y;
     const long idx = (long)blockIdx.x * kBwdBlock + threadIdx.x;
     if (idx >= (long)n_points[f] * L) return;
+    if (cn.counts && cn.t > frame_count(cn.counts, f, cn.cap)) return;
     const size_t o = f * fs + idx;
     float acc = keep * G[o];
     if constexpr (PRE) {
@@ -368,13 +383,15 @@ __global__ void __launch_bounds__(kBwdBlock) k_bwd_combine_adjoint(const int *__
 // out[f][k] = sum over the iterations and the frame's workgroups of partial[t][k][f][b]: one workgroup per (term, frame), a strided
 // walk over the T x backward_blocks(n_points[f]) partials of the frame in a fixed order and a fixed tree in LDS (store and sum: no
 // atomics, the same bits every run, and those of a handle of n_points[f] points).  bstride: the partials' row (the sweep's grid).
+// counts != null (section 2j): the frame's own t_f in T's place -- the walk and the tree of a handle at t_f.
 __global__ void __launch_bounds__(kBwdBlock) k_bwd_reduce(const float *__restrict__ partial, const int *__restrict__ n_points, int K,
-                                                        int T, int rows_per_block, int bstride, float *__restrict__ out)
+                                                        int T, int rows_per_block, int bstride, float *__restrict__ out,
+                                                        const int *__restrict__ counts)
 {
     __shared__ float s[kBwdBlock];
     const int k = blockIdx.x, f = blockIdx.y, F = gridDim.y;
     const int nblk = max((n_points[f] + rows_per_block - 1) / rows_per_block, 1);
-    const long n = (long)T * nblk;
+    const long n = (long)(counts ? frame_count(counts, f, T) : T) * nblk;
     float acc = 0.0f;
     for (long idx = threadIdx.x; idx < n; idx += kBwdBlock) {
         const long t = idx / nblk, b = idx - t * nblk;
@@ -540,6 +557,54 @@ __global__ void __launch_bounds__(kBwdBlock) k_sum_frames(const float *__restric
 void launch_sum_frames(const float *x, int F, int n, float *out, hipStream_t s)
 {
     if (n > 0) k_sum_frames<<<(unsigned)((n + kSumEntries - 1) / kSumEntries), kBwdBlock, 0, s>>>(x, F, n, out);
+}
+
+namespace {
+
+// Q[f] <- hist[t_f][f] for every frame with t_f < T, element by element over the frame's maxN x L floats (every hist[t] is a copy of
+// the whole of Q); a frame at the cap keeps the stepped Q.
+__global__ void __launch_bounds__(kBwdBlock) k_restore_counted_q(const int *__restrict__ counts, int T, size_t fs, size_t slice,
+                                                               const float *__restrict__ hist, float *__restrict__ Q)
+{
+    const int f = blockIdx.y;
+    const int tf = frame_count(counts, f, T);
+    const size_t idx = (size_t)blockIdx.x * kBwdBlock + threadIdx.x;
+    if (tf >= T || idx >= fs) return;
+    Q[f * fs + idx] = hist[(size_t)tf * slice + f * fs + idx];
+}
+
+// order[r] = f with r = #{g : t_g > t_f} + #{g < f : t_g == t_f}: every frame's rank among the clamped counts, longest first, ties by
+// frame -- a permutation of 0 .. F-1 whatever the counts hold.  A lane per frame; the counts pass through LDS in tiles of a workgroup.
+__global__ void __launch_bounds__(kBwdBlock) k_order_by_count(const int *__restrict__ counts, int F, int T, int *__restrict__ order)
+{
+    __shared__ int tile[kBwdBlock];
+    const int f = blockIdx.x * kBwdBlock + threadIdx.x;
+    const int tf = f < F ? frame_count(counts, f, T) : 0;
+    int rank = 0;
+    for (int g0 = 0; g0 < F; g0 += kBwdBlock) {            // (uniform bounds: every lane meets every barrier)
+        const int g = g0 + (int)threadIdx.x;
+        tile[threadIdx.x] = g < F ? frame_count(counts, g, T) : -1;
+        __syncthreads();
+        const int n = min(kBwdBlock, F - g0);
+        for (int j = 0; j < n; ++j) rank += tile[j] > tf || (tile[j] == tf && g0 + j < f);
+        __syncthreads();
+    }
+    if (f < F) order[rank] = f;
+}
+
+}  // namespace
+
+void launch_order_by_count(const int *counts, int F, int T, int *order, hipStream_t s)
+{
+    if (F > 0) k_order_by_count<<<(unsigned)((F + kBwdBlock - 1) / kBwdBlock), kBwdBlock, 0, s>>>(counts, F, T, order);
+}
+
+void launch_restore_counted_q(const CrfDev &c, const BackwardArea &ar, int T, const int *counts, hipStream_t s)
+{
+    const size_t fs = (size_t)c.maxN * c.L;
+    if (T <= 0 || !fs || !c.F) return;
+    k_restore_counted_q<<<dim3((unsigned)((fs + kBwdBlock - 1) / kBwdBlock), (unsigned)c.F), kBwdBlock, 0, s>>>(counts, T, fs, ar.slice, ar.hist,
+                                                                                                            c.Q);
 }
 
 namespace {
@@ -768,6 +833,8 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
     const int cblk = backward_compat_blocks(rows);
     for (int k = 0; k < K && cmode; ++k) a.compat[k] = compat ? compat[k] : nullptr;
     a.gam = ar.gam;
+    a.counts = rq.counts;                                   // (section 2j; null: every frame at T)
+    a.cap = T;
     // the feature part: terms with a gradient array (T >= 1; the caller has zeroed their ar.gb / ar.gn)
     // (section 1m, modes != null: ar.gn[k] takes the post adjoint of an AFTER or SYMMETRIC term from k_softmax_bwd and the pre adjoint
     // of a BEFORE or SYMMETRIC one from k_bwd_combine_adjoint, which runs in k_bwd_combine<true>'s place while padj is set)
@@ -791,6 +858,7 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
         a.K = K;
         a.relax = relax;
         a.first = t == T;
+        a.t = t;
         a.partial = K ? ar.partial + (size_t)(t - 1) * K * F * nblk : nullptr;
         // (first uses in the order compat, plain, feature, both: the order of the kernels' instantiation, and so of the code object)
         if (cmode && !feat) launch_softmax_bwd<kBwdCompat>(a, F, s);
@@ -817,13 +885,16 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
                 k_bwd_combine_adjoint<decltype(lanes)::value><<<rgrid, kBwdBlock, 0, s>>>(c.n_points, L, K, ar.phi, slice, fs, wk, 1.0f - relax,
                                                                                        ar.G, bp, pa);
             });
-        } else if (pre) k_bwd_combine<true><<<cgrid, kBwdBlock, 0, s>>>(c.n_points, L, K, ar.phi, slice, fs, wk, 1.0f - relax, ar.G, bp);
-        else k_bwd_combine<false><<<cgrid, kBwdBlock, 0, s>>>(c.n_points, L, K, ar.phi, slice, fs, wk, 1.0f - relax, ar.G, bp);
+        } else if (pre) k_bwd_combine<true><<<cgrid, kBwdBlock, 0, s>>>(c.n_points, L, K, ar.phi, slice, fs, wk, 1.0f - relax, ar.G, bp,
+                                                                        BwdCounts{rq.counts, t, T});
+        else k_bwd_combine<false><<<cgrid, kBwdBlock, 0, s>>>(c.n_points, L, K, ar.phi, slice, fs, wk, 1.0f - relax, ar.G, bp,
+                                                              BwdCounts{rq.counts, t, T});
     }
     // dL/dU -= P_0 (G_0 - <G_0, P_0>), P_0 = Q_0 = softmax(-U)
     a.K = 0;
     a.relax = 1.0f;
     a.first = T == 0;
+    a.t = 0;                                                // (with counts: the first step of the frames with t_f = 0)
     a.partial = nullptr;
     launch_softmax_bwd<kBwdPlain>(a, F, s);
     if (grad_compat && K && T >= 1)
@@ -849,7 +920,7 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
     }
     if (grad_weights && K)
         k_bwd_reduce<<<dim3((unsigned)K, (unsigned)F), kBwdBlock, 0, s>>>(ar.partial, c.n_points, K, T, kBwdBlock / bwd_lanes(L), nblk,
-                                                                       grad_weights);
+                                                                       grad_weights, rq.counts);
     if (rq.grad_model) {                                  // the sums over the frames: the K weights, then the K * L * L entries
         launch_sum_frames(grad_weights, F, K, rq.grad_model, s);
         launch_sum_frames(grad_compat, F, K * L * L, rq.grad_model + K, s);
