@@ -898,7 +898,10 @@ int  lccrf_batch_last_timing(lccrf_batch_handle b, float *inference_ms, float *b
  * FIRST lccrf_batch_inference behind a build, into one block per frame (<= 64 KB; allocated on that call, kept with the handle), and
  * every later inference on those lattices starts from it.  It is part of the lattice construction (the PottsPotential3D ctor,
  * pairwise3d.h:20-28), not of inference(): prepare_ms = HIP-event time of the last such launch (0 if none), runs = how many there
- * were on this handle.  Results are identical with and without the records.                                                         */
+ * were on this handle.  Results are identical with and without the records.
+ * When the batch's unaries come from labels (label + conf), those later inferences also read the points' labels as one byte per point
+ * (0, 1, or 2 for unknown / out of range) instead of the unary array: the library's own copy, max_frames x max_points bytes, written
+ * with the unary array and allocated by the first inference on labels.  The caller's label array is not read again for it.       */
 int  lccrf_batch_last_prepare(lccrf_batch_handle b, float *prepare_ms, int *runs);
 /* Measurement support: average HIP-event duration of `reps` launches of the streaming engine's dominant kernel (one
  * Jacobi blur pass of `kernel` over every frame of the batch, permutohedral_cpu.h:663-679) and the number of lattice

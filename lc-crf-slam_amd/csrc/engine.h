@@ -307,7 +307,9 @@ void launch_norm(const KernelDev &kd, const CrfDev &c, int maxV, hipStream_t s);
 // unary[i][:] from labels (densecrf3d.h:116-129); the 2L+1 energies {u, n[L], p[L]} are passed by value (no table
 // upload; `label` may be device or pinned host memory)
 struct UnaryTable { float v[2 * LCCRF_MAX_LABELS + 1]; };
-void launch_unary_from_label_tbl(const CrfDev &c, const int16_t *label, const UnaryTable &tbl, hipStream_t s);
+// codes / pairs (two labels; both or neither): see LabelCodes below -- written by the same launch, the codes in the unary array's order
+void launch_unary_from_label_tbl(const CrfDev &c, const int16_t *label, const UnaryTable &tbl, hipStream_t s,
+                                 unsigned char *codes = nullptr, float *pairs = nullptr);
 void launch_start(const CrfDev &c, hipStream_t s);
 // compat (include/lccrf.h section 1e; null: every term is Potts): K device pointers, compat[k] the [L][L] label-compatibility matrix
 // of term k or null.  The batch paths pass null.
@@ -524,11 +526,19 @@ inline int fused_report(int lanes, int ppt, int chain0) { return lanes | ppt << 
 // (fused_general.hip, fused_general_converge.hip: up to 2048 active points), whose `kds` are the caller's copies with `norm` pointing
 // at each term's factor behind the filter (as launch_step_stream takes them).  The stop decision of a converged run is made inside
 // the kernel; a plan that leaves no room for its reduction's words in LDS launches nothing.
+// Label-derived unaries as the lean inference kernel reads them (k_fused_lean_lbl): what k_unary_from_label_tbl leaves beside the
+// unary array -- a point's code in the unary array's point order, and the three pairs a code stands for.
+constexpr int kLabelPairFloats = 12;
+struct LabelCodes {
+    const unsigned char *codes;   // [F][maxN]: 0 / 1 the label, 2 unknown or out of range; null: the unaries are not label-derived
+    const float *pairs;           // [kLabelPairFloats]: by code the pair -energy, then by code the pair Q0 = softmax(-energy)
+};
 struct SizedRequest {
     Schedule run;
     TermModel terms;      // (norm_mode is not read: the factors are in HBM, terms.pre and kds[k].norm)
     ConvergeOut out;      // every frame's report (read only when run.until_converged)
     LeanPrep *prep;       // or null: k_fused's prepared launch records (no other kernel looks at them)
+    LabelCodes lbl;       // codes == null: raw unaries (only the lean plan's run from prepared records looks at them)
 };
 struct SizedLaunch {
     int report;           // fused_report() of what was launched; 0: the frames are not ones the kernel takes and nothing was launched

@@ -23,6 +23,7 @@
 #include "fused_loop.h"
 #include "fused_lean.h"
 #include "fused_variant.h"
+#include "fused_lean_label.h"
 #include "dispatch.h"
 
 #include <algorithm>
@@ -651,7 +652,30 @@ SizedLaunch launch_inference(const CrfDev &c, const KernelDev *kds, const int *m
             prep->seen_key = key;                            // the first one
         }
     }
-    launch_shape(c, a, s, mode, sh);
+    // label-derived unaries, a fixed count of Potts iterations on the lean plan, valid blocks: the label-code form of the run kernel
+    // (LCCRF_NO_LABEL_CODES, read at every launch: an A/B switch of the instrumented library, same results either way)
+    if (mode == 2 && sh.lean && rq.lbl.codes && rq.lbl.pairs && !ab_env("LCCRF_NO_LABEL_CODES")) {
+        LeanLabelArgs la{};
+        for (int k = 0; k < c.K; ++k) {
+            la.kd[k] = a.kd[k];
+            la.Vcap[k] = a.Vcap[k];
+        }
+        la.lay = a.lay;
+        la.n_iter = a.n_iter;
+        la.with_map = a.with_map;
+        la.relax = a.relax;
+        la.omr = a.omr;
+        la.timing = a.timing;
+        la.timing_block = a.timing_block;
+        la.timing_lane = a.timing_lane;
+        la.dbg = a.dbg;
+        la.prep = a.prep;
+        la.prep_stride = a.prep_stride;
+        la.lbl = rq.lbl;
+        launch_lean_label(c, la, sh.ppt, s);
+    } else {
+        launch_shape(c, a, s, mode, sh);
+    }
     stamps.print(s);                      // debug only: synchronous read-back of one workgroup's phase stamps
     return SizedLaunch{fused_report(sh.nt, sh.ppt, a.lay.chain0), sh.report()};
 }

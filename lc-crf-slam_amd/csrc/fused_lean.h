@@ -529,6 +529,20 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t lean_rsrc(const void *p, size_
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);   // raw buffer, 32-bit data format (gfx9)
 }
 
+// Label-derived unaries (k_fused_lean_lbl): a point's energy pair is one of three -- label 0, label 1, unknown -- so the loop keeps
+// the points' codes (one byte each, four points in a register) and the three NEGATED pairs in scalar registers instead of re-reading
+// 8 bytes per point and iteration.
+struct LeanLabel {
+    unsigned codes;                           // byte s: the code of point slot s (0, 1, or 2 = unknown)
+    // -energy pair by code (stepInit, densecrf3d.h:154-158; the negation is exact).  Six plain members, picked by VALUE: selects
+    // between elements of an array become loads from a selected address, and the array goes to scratch.
+    float n0x, n0y, n1x, n1y, n2x, n2y;
+};
+__device__ __forceinline__ float lean_pick(unsigned code, float v0, float v1, float v2)
+{
+    return code == 0 ? v0 : code == 1 ? v1 : v2;
+}
+
 template <int PPT, int K>
 __device__ __forceinline__ void opaque_ids(PointRegs<PPT, K> &pr)
 {
@@ -594,10 +608,12 @@ __host__ __device__ inline LeanPrepPlan lean_prep_plan(const FusedLayout &lay, i
 // NORM (the one-launch frame kernel): ONE pass that leaves every kernel's norm = 1 / (K * 1 + 1e-20) (pairwise3d.h:20-28) in src.norm
 // (RELOAD; else w * norm in pr.wn) instead of updating Q -- the caller sets Q = 1; the same splat / row sums / blur / slice as an iteration's, phase by phase.
 // PRELOADED: the caller has the first iteration's records in pr already (k_fused_lean from prepared blocks requests them with everything else).
-template <int PPT, int K, int CH, int NT, bool RELOAD, bool NORM = false, bool PRELOADED = false>
+// LBL: the unary energies are label-derived (LeanLabel): nothing reads or re-reads pr.un.
+template <int PPT, int K, int CH, int NT, bool RELOAD, bool NORM = false, bool PRELOADED = false, bool LBL = false>
 __device__ __forceinline__ void mean_field_lean(unsigned char *smem, const FusedLayout &lay, const int (&V)[K], int N, int &t,
                                                 PointRegs<PPT, K> &pr, ChainLane &cl, const float (&alpha)[K],
-                                                const float (&wk)[K], const LeanSrc &src, int n_iter, float relax, float omr, Instr &ins)
+                                                const float (&wk)[K], const LeanSrc &src, int n_iter, float relax, float omr, Instr &ins,
+                                                const LeanLabel &lb = LeanLabel{})
 {
     constexpr int D1 = kD1;
     constexpr int KF = K - 1;                             // the kernel whose products follow the softmax
@@ -619,7 +635,7 @@ __device__ __forceinline__ void mean_field_lean(unsigned char *smem, const Fused
 #pragma unroll
         for (int s = 0; s < PPT; ++s) {
             const int i = t + s * NT;                   // (a lane without a point in this slot reads the slice's spare rows or 0: unused)
-            if (!NORM) {
+            if (!NORM && !LBL) {
                 typedef unsigned lean_u2 __attribute__((ext_vector_type(2)));
                 const lean_u2 u = __builtin_amdgcn_raw_buffer_load_b64(src.unary, i * 8, src.off_unary, 0);
                 pr.un[s] = make_float2(__uint_as_float(u.x), __uint_as_float(u.y));
@@ -834,7 +850,15 @@ __device__ __forceinline__ void mean_field_lean(unsigned char *smem, const Fused
             }
             return;
         }
-        float nx[2] = {-pr.un[s].x, -pr.un[s].y};                 // stepInit, densecrf3d.h:154-158
+        float nx[2];                                              // stepInit, densecrf3d.h:154-158
+        if constexpr (LBL) {
+            const unsigned code = (lb.codes >> (8 * s)) & 0xffu;
+            nx[0] = lean_pick(code, lb.n0x, lb.n1x, lb.n2x);
+            nx[1] = lean_pick(code, lb.n0y, lb.n1y, lb.n2y);
+        } else {
+            nx[0] = -pr.un[s].x;
+            nx[1] = -pr.un[s].y;
+        }
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const float2 t = slice_point_lean(pr, s, k, alpha[k]);

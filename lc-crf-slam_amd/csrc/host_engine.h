@@ -149,6 +149,11 @@ struct Engine {
     const int16_t *deferred_label = nullptr;
     UnaryTable deferred_tbl{};
     bool unary_is_label = false;       // the unaries come from labels (re-derivable in any order) rather than from a raw array
+    // ... and, for two labels, what ensure_unary() leaves beside the unary array for the lean inference kernel (engine.h: LabelCodes):
+    // the library's own, allocated on first use; valid while the unary array is the one that launch wrote
+    unsigned char *label_codes = nullptr;
+    float *label_pairs = nullptr;
+    bool label_codes_valid = false;
 
     // ---- the late-bound one-launch run, the done word and the label polling ----
     // Late-bound fused inference (object API): queued right behind the build, before the host has seen

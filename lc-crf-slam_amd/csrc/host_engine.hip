@@ -382,7 +382,7 @@ void Engine::recycle()
     forget_inputs();
     unary_deferred = false;
     perm_on = vorder_on = perm_banned = false;        // (the next user's lattices decide afresh)
-    unary_is_label = unary_p_valid = false;
+    unary_is_label = unary_p_valid = label_codes_valid = false;
     engine_pref = 0;
     report = RunReport{};
     model.clear(*this);                               // (the next user's terms start as Potts terms normalised AFTER the filter)
@@ -427,7 +427,7 @@ int Engine::build_kernels(int k0, int n, bool may_reorder)
         const bool want = allow_perm && !no_perm && !perm_banned && (!perm_scoped || may_reorder) && n > 0 && n == (int)kernels.size() && NAp >= perm_min_points();
         if (want || perm_on) {                         // whatever was derived in the old order is stale
             if (unary_is_label) unary_deferred = true;
-            unary_p_valid = false;
+            unary_p_valid = label_codes_valid = false;
         }
         perm_on = false;
         // ... and, with the points permuted, whether the lattices are built by SORTING the entries on the row-major code of their
@@ -603,6 +603,7 @@ void Engine::defer_unary_from_label(const int16_t *label, const float *conf)
     crf.unary = unary_own;
     unary_deferred = true;
     unary_is_label = true;
+    label_codes_valid = false;                        // (until ensure_unary() has written them for these labels and this table)
     deferred_label = label;
     deferred_tbl = tb;
     unary_set = true;
@@ -612,7 +613,7 @@ void Engine::defer_unary_from_label(const int16_t *label, const float *conf)
 void Engine::bind_unary(const float *p)
 {
     crf.unary = const_cast<float *>(p);
-    unary_deferred = unary_is_label = unary_p_valid = false;
+    unary_deferred = unary_is_label = unary_p_valid = label_codes_valid = false;
     unary_set = true;
 }
 
@@ -620,8 +621,22 @@ int Engine::ensure_unary()
 {
     if (!unary_deferred) return LCCRF_OK;
     unary_deferred = false;
-    launch_unary_from_label_tbl(crf, deferred_label, deferred_tbl, stream);
+    // two labels: the points' codes and the three pairs go out with the energies (no memory for them: the energies alone)
+    label_codes_valid = false;
+    if (L == 2 && !label_codes) {
+        unsigned char *pc = nullptr;
+        float *pp = nullptr;
+        if (mem.alloc(&pc, (size_t)Fcap * maxN, false) == LCCRF_OK && mem.alloc(&pp, (size_t)kLabelPairFloats) == LCCRF_OK) {
+            label_codes = pc;
+            label_pairs = pp;
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+    const bool lbl = L == 2 && label_codes && crf.unary == unary_own;
+    launch_unary_from_label_tbl(crf, deferred_label, deferred_tbl, stream, lbl ? label_codes : nullptr, lbl ? label_pairs : nullptr);
     HIP_TRY(hipGetLastError());
+    label_codes_valid = lbl;
     return LCCRF_OK;
 }
 
@@ -784,7 +799,9 @@ int Engine::engine_in_use(int *out)
 // False: the frames are not ones the kernel takes and nothing was launched.  (The k_converge route leaves fused_shape as it was.)
 bool Engine::launch_sized(const Schedule &run, LeanPrep *prep)
 {
-    const SizedRequest rq{run, model.terms(kernels.size()), conv_out(), prep};
+    const bool lbl = label_codes_valid && unary_is_label && !unary_deferred && !perm_on && crf.unary == unary_own;
+    const SizedRequest rq{run, model.terms(kernels.size()), conv_out(), prep,
+                          LabelCodes{lbl ? label_codes : nullptr, lbl ? label_pairs : nullptr}};
     const SizedLaunch r = launch_inference(crf, step_kdevs(), maxV.data(), maxRow.data(), rq, stream);
     if (!r.report) return false;
     report.sized_run(sized_engine, r, run.until_converged, rq.terms.general());

@@ -12,10 +12,21 @@ namespace lccrf {
 namespace {
 
 // unary[i][:] from a label and the three energy tables {u, n[L], p[L]}.  densecrf3d.h:116-129.
-__global__ void __launch_bounds__(kBlock) k_unary_from_label_tbl(CrfDev c, const int16_t *__restrict__ label, UnaryTable tbl)
+// codes (two labels, or null): the point's code -- 0 / 1 its label, 2 unknown -- beside its energies; pairs: by code the negated
+// energy pair, then Q0 = softmax(-energies) with the inference kernels' own arithmetic (softmax2_fresh), kLabelPairFloats floats.
+__global__ void __launch_bounds__(kBlock) k_unary_from_label_tbl(CrfDev c, const int16_t *__restrict__ label, UnaryTable tbl,
+                                                                 unsigned char *__restrict__ codes, float *__restrict__ pairs)
 {
     const int f = blockIdx.y;
     const int idx = blockIdx.x * kBlock + threadIdx.x;
+    if (pairs && f == 0 && idx < 3) {         // (code `idx`; L == 2)
+        const float a = idx == 2 ? tbl.v[0] : idx == 0 ? tbl.v[3] : tbl.v[2], b = idx == 2 ? tbl.v[0] : idx == 0 ? tbl.v[1] : tbl.v[4];
+        const float2 q0 = softmax2_fresh(-a, -b);
+        pairs[2 * idx] = -a;
+        pairs[2 * idx + 1] = -b;
+        pairs[6 + 2 * idx] = q0.x;
+        pairs[6 + 2 * idx + 1] = q0.y;
+    }
     if (idx >= c.n_points[f] * c.L) return;
     const int i = idx / c.L, m = idx - i * c.L;
     const int t = label[(size_t)f * c.maxN + (c.perm ? c.perm[(size_t)f * c.perm_stride + i] : i)];
@@ -23,6 +34,7 @@ __global__ void __launch_bounds__(kBlock) k_unary_from_label_tbl(CrfDev c, const
     if (t < 0 || t >= c.L) u = tbl.v[0];      // -1 = unknown; out-of-range labels (UB in the reference) likewise
     else u = (m == t) ? tbl.v[1 + c.L + t] : tbl.v[1 + t];
     c.unary[((size_t)f * c.maxN + i) * c.L + m] = u;
+    if (codes && m == 0) codes[(size_t)f * c.maxN + i] = (t < 0 || t >= c.L) ? 2 : (unsigned char)t;
 }
 
 // out = softmax_fe(scale * in) (blended with the old out when relax != 1).
@@ -119,9 +131,11 @@ __global__ void __launch_bounds__(kBlock) k_validate_npoints(const int *__restri
 
 }  // namespace
 
-void launch_unary_from_label_tbl(const CrfDev &c, const int16_t *label, const UnaryTable &tbl, hipStream_t s)
+void launch_unary_from_label_tbl(const CrfDev &c, const int16_t *label, const UnaryTable &tbl, hipStream_t s, unsigned char *codes,
+                                 float *pairs)
 {
-    k_unary_from_label_tbl<<<grid_for((long)c.maxN * c.L, c.F), kBlock, 0, s>>>(c, label, tbl);
+    const bool lbl = codes && pairs && c.L == 2;
+    k_unary_from_label_tbl<<<grid_for((long)c.maxN * c.L, c.F), kBlock, 0, s>>>(c, label, tbl, lbl ? codes : nullptr, lbl ? pairs : nullptr);
 }
 
 void launch_exp_and_normalize(const CrfDev &c, const float *in, float *out, float scale, float relax, hipStream_t s)
