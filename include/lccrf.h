@@ -1144,11 +1144,51 @@ int  lccrf_batch_inference_backward_modes(lccrf_batch_handle b, int n_iterations
  *     the NULL d_iterations are answered before the batch is looked at); a rejected call leaves the batch as it was; d_grad_weights
  *     may be NULL, K = 0 is legal.
  *   - Potts terms normalised AFTER only, as section 2c: on a batch with a matrix or a mode other than AFTER the call returns
- *     LCCRF_E_STATE and leaves the batch as it was.  Not covered (notes/convergence.md section 6): learnt models in section 2h's form,
- *     feature gradients, the one-launch kernels of sections 1k and 1l.
+ *     LCCRF_E_STATE and leaves the batch as it was: learnt models in section 2h's form are section 2k's.  Not covered
+ *     (notes/convergence.md sections 6 and 7): feature gradients at per-frame counts, the one-launch kernel of section 1l.
  * ==================================================================================== */
 int  lccrf_batch_inference_backward_converged(lccrf_batch_handle b, int max_iterations, float relax, const int32_t *d_iterations,
                                               const float *d_grad_prob, float *d_grad_unary, float *d_grad_weights, void *stream);
+
+/* ======================================================================================
+ * 2k. Gradients of a batch's CONVERGED inference under a LEARNT model -- section 2h without d_grad_features, with section 2j's
+ *     d_iterations: every frame of a batch with matrices (section 2g) or normalisation modes differentiated at its own iteration
+ *     count, and the sums over the frames (lc-crf-slam_amd/autograd.py: mean_field_batch_compat_converged,
+ *     BatchCompatConvergedMeanFieldCRF).  Added WITHOUT a step of LCCRF_ABI_VERSION (it stays 3): probe for it by symbol.  Sections
+ *     2c, 2d and 2j are unchanged and keep refusing what they refuse.
+ *
+ * The contract is the conjunction of sections 2h and 2j.  d_iterations: section 2j's device array of [n_frames] int32, read in stream
+ * order and never by the host -- lccrf_batch_device_convergence's array goes straight in behind lccrf_batch_inference_converged on
+ * the same stream.  Frame f is differentiated at t_f = min(max(d_iterations[f], 0), max_iterations).  Outputs as section 2h's, each
+ * overwritten, each may be NULL: d_grad_unary, d_grad_weights, d_grad_compat, d_grad_model.
+ *   - Per frame, the bits of section 1f at t_f: d_grad_unary[f], d_grad_weights[f] and d_grad_compat[f] are exactly what
+ *     lccrf_inference_backward_all(h, t_f, relax, ..., NULL, d_grad_compat) returns for a handle holding frame f with the batch's
+ *     weights, matrices and modes -- the chunk count C_f and the chunk order of dL/dmu and the t_f x B walk and tree of dL/dw included;
+ *     a term without a matrix gets the derivative at mu = I.  Rows at or beyond n_points[f] of d_grad_unary are written +0; a frame of
+ *     0 points gets zeros.
+ *   - A frame with t_f = 0: d_grad_compat[f] and d_grad_weights[f] are exactly 0 -- whatever an earlier call left in the batch's
+ *     area -- and dL/dU is section 2c's T = 0 result.
+ *   - d_grad_model is section 2h's ascending-frame fp32 sum of this call's per-frame values (the caller's arrays, or the batch's area
+ *     where the caller passed NULL): the same order, part of the contract; no float atomics.
+ *   - Afterwards frame f of the batch's Q holds Q_{t_f}, bit for bit what lccrf_batch_inference_converged left when the counts are
+ *     its report.  Labels, label bits and the stored convergence report are not changed.
+ *   - Every count equal to max_iterations: every output and the Q left behind are lccrf_batch_inference_backward_all(b,
+ *     max_iterations, relax, ..., NULL, d_grad_compat, d_grad_model, stream)'s, bit for bit.
+ *   - On a batch without matrices or modes, with d_grad_compat == d_grad_model == NULL, the call is section 2j's: same bits, same route.
+ *   - Routes: the streaming sweep leaves frame f idle while t > t_f (section 2j), the kernels of dL/dmu included.  Under
+ *     LCCRF_OPT_FUSED_BACKWARD_LEARNT (section 1k), on the batches its one-launch kernel takes, frame f's workgroup loads t_f once and
+ *     runs t_f replays and t_f sweep steps, the workgroups taking the frames by descending t_f; plus the two launches of
+ *     d_grad_model.  The same bits: which workgroup runs a frame changes none.  lccrf_batch_get_backward_route reports the route.
+ *   - Errors: max_iterations < 0, a relax that is not finite and a NULL d_iterations give LCCRF_E_INVALID before the batch is looked
+ *     at; a device array that section 1b refuses gives LCCRF_E_INVALID; a call before lccrf_batch_build / _run gives LCCRF_E_STATE.
+ *     A rejected call leaves the batch as it was.  K = 0 is legal.
+ *   - Memory: section 2h's area at T = max_iterations.
+ *   - Not covered (notes/convergence.md section 7): feature gradients at per-frame counts (sections 2d / 2i), handle-level entry
+ *     points (a handle's recipe stays lccrf_inference_backward_all at the reported count), the half-CU shapes.
+ * ==================================================================================== */
+int  lccrf_batch_inference_backward_all_converged(lccrf_batch_handle b, int max_iterations, float relax, const int32_t *d_iterations,
+                                                  const float *d_grad_prob, float *d_grad_unary, float *d_grad_weights,
+                                                  float *d_grad_compat, float *d_grad_model, void *stream);
 
 /* ======================================================================================
  * 3. Unary builder -- the step right before the CRF (first "next" row):

@@ -215,6 +215,8 @@ def lib():
     L.lccrf_batch_inference_backward_modes.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, C.POINTER(vp), vp, vp, vp]
     if hasattr(L, "lccrf_batch_inference_backward_converged"):                    # (section 2j: probe by symbol)
         L.lccrf_batch_inference_backward_converged.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, vp, vp]
+    if hasattr(L, "lccrf_batch_inference_backward_all_converged"):                # (section 2k: probe by symbol)
+        L.lccrf_batch_inference_backward_all_converged.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp, vp]
     L.lccrf_batch_set_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p]
     L.lccrf_batch_get_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p, C.POINTER(C.c_int)]
     L.lccrf_batch_set_pairwise_normalization.argtypes = [vp, C.c_int, C.c_int]
@@ -756,6 +758,15 @@ class BatchCRF(_Handle):
         _check(lib().lccrf_batch_inference_backward_all(self.h, int(n_iterations), float(relax), C.c_void_p(int(d_grad_prob)),
                                                         _addr(d_grad_unary), _addr(d_grad_weights), _addr_list(d_grad_features),
                                                         _addr(d_grad_compat), _addr(d_grad_model), _addr(stream)))
+
+    def inference_backward_all_converged_device(self, max_iterations, relax, d_iterations, d_grad_prob, d_grad_unary=None,
+                                                d_grad_weights=None, d_grad_compat=None, d_grad_model=None, stream=None):
+        """inference_backward_all_device without feature gradients, every frame at its own iteration count (include/lccrf.h section
+        2k): d_iterations as inference_backward_converged_device takes it -- device_convergence()["iterations"] behind
+        inference_converged(), or a copy of it, clamped per frame to [0, max_iterations] and never read by the host."""
+        _check(lib().lccrf_batch_inference_backward_all_converged(self.h, int(max_iterations), float(relax), _addr(d_iterations),
+                                                                  _addr(d_grad_prob), _addr(d_grad_unary), _addr(d_grad_weights),
+                                                                  _addr(d_grad_compat), _addr(d_grad_model), _addr(stream)))
 
     def inference_backward_modes_device(self, n_iterations, relax, d_grad_prob, d_grad_unary=None, d_grad_weights=None,
                                         d_grad_features=None, d_grad_compat=None, d_grad_model=None, stream=None):

@@ -1,4 +1,4 @@
-"""torch autograd through DenseCRF::inference on the HIP path (include/lccrf.h sections 1c - 1g, 1m, 2c and 2j).
+"""torch autograd through DenseCRF::inference on the HIP path (include/lccrf.h sections 1c - 1g, 1m, 2c, 2j and 2k).
 
     Q = mean_field(crf, unary, weights, n_iterations=5, relax=1.0)
     Q.backward(g)      # -> unary.grad = dL/dU, weights.grad = dL/dw
@@ -14,6 +14,9 @@
 
     Q, t = mean_field_batch_converged(batch, unary, weights, max_iterations=12)   # every frame stops on its own; t [F] int32
     Q.backward(g)      # -> every frame differentiated at ITS count, in one call (section 2j)
+
+    Q, t = mean_field_batch_compat_converged(batch, unary, weights, compat, max_iterations=12)   # ... under a learnt model
+    Q.backward(g)      # -> also compat.grad; the sums over the frames at every frame's own count (section 2k)
 
     Q = mean_field_features(unary, [f_0, f_1, ..], weights, n_iterations=5, relax=1.0)        # the features are inputs too
     Q.backward(g)      # -> also f_k.grad = dL/d features [N, d_k] (section 1d); LearnedKernelCRF fits kernel bandwidths with it
@@ -99,10 +102,11 @@ def _forward_q(crf, u, n_iterations, relax, ext, cur):
     return _clone_q(crf.device_buffers()["current"], tuple(u.shape), u.device, ext, cur)
 
 
-def _check_stop(stop, compat):
-    """stop: None (a fixed count) or (criterion, tol) of "until converged, at most n_iterations" -- Potts terms only"""
-    if stop is not None and compat is not None:
-        raise ValueError("the converged layers take Potts terms only (include/lccrf.h section 2j)")
+def _check_stop(stop, compat, batch=False):
+    """stop: None (a fixed count) or (criterion, tol) of "until converged, at most n_iterations" -- on a handle for Potts terms only; a
+    batch takes matrices too (include/lccrf.h section 2k)"""
+    if stop is not None and compat is not None and not batch:
+        raise ValueError("the converged handle layer takes Potts terms only (include/lccrf.h section 1h)")
 
 
 def _model(weights, compat):
@@ -287,17 +291,18 @@ class CompatMeanFieldCRF(_HandleCRF):
 
 # ---- a caller's batch ------------------------------------------------------------------------------------------------------------
 class _MeanFieldBatch(torch.autograd.Function):
-    """mean_field_batch (compat None), mean_field_batch_compat and -- with a stop rule -- mean_field_batch_converged on a caller's
-    BatchCRF.  The backwards are different calls: without matrices section 2c, which refuses a batch that carries matrices or modes,
-    and torch's sum of its [F, K] output (under a stop rule section 2j, section 2c at every frame's own count); with them section 2h,
-    whose model gradients are the batch's own ordered sums over the frames."""
+    """mean_field_batch (compat None), mean_field_batch_compat and -- with a stop rule -- mean_field_batch_converged and
+    mean_field_batch_compat_converged on a caller's BatchCRF.  The backwards are different calls: without matrices section 2c, which
+    refuses a batch that carries matrices or modes, and torch's sum of its [F, K] output (under a stop rule section 2j, section 2c at
+    every frame's own count); with them section 2h, whose model gradients are the batch's own ordered sums over the frames (under a
+    stop rule section 2k, section 2h at every frame's own count)."""
 
     @staticmethod
     def forward(ctx, batch, unary, weights, compat, n_iterations, relax, n_points, stop):
         F, N, L = batch.n_frames, batch.maxN, batch.L
         _check_unary_weights(unary, (F, N, L), weights, len(batch.dims))
         _check_compat_iterations(compat, len(batch.dims), L, n_iterations)
-        _check_stop(stop, compat)
+        _check_stop(stop, compat, batch=True)
         dev = unary.device
         u = unary.detach().contiguous()
         w, m = _model(weights, compat)
@@ -338,7 +343,10 @@ class _MeanFieldBatch(torch.autograd.Function):
         with _on_stream(batch.own_stream(), dev):
             _arm(batch, w, m)                                 # the inputs of this forward (the batch may have run others since)
             batch.set_unary_device(u.data_ptr())
-            if it is not None:                                # (section 2j: the cap, and every frame's own count from the device)
+            if it is not None and m is not None:              # (section 2k: section 2h's sums, every frame at its own count)
+                batch.inference_backward_all_converged_device(ctx.n_iterations, ctx.relax, it.data_ptr(), g.data_ptr(), grad_u.data_ptr(),
+                                                              d_grad_model=model.data_ptr() if K else None)
+            elif it is not None:                              # (section 2j: the cap, and every frame's own count from the device)
                 batch.inference_backward_converged_device(ctx.n_iterations, ctx.relax, it.data_ptr(), g.data_ptr(), grad_u.data_ptr(),
                                                           grad_w.data_ptr() if K else None)
             elif m is None:
@@ -382,6 +390,15 @@ def mean_field_batch_converged(batch, unary, weights, max_iterations, criterion=
     own t_f in one call on those counts, which never visit the host (section 2j); unary.grad and weights.grad as mean_field_batch.
     Potts terms normalised AFTER only."""
     return _apply_batch(batch, unary, weights, None, max_iterations, relax, (criterion, tol))
+
+
+def mean_field_batch_compat_converged(batch, unary, weights, compat, max_iterations, criterion=_pkg.STOP_LABELS, tol=0.0, relax=1.0):
+    """mean_field_batch_compat "until converged, at most max_iterations": the learnt model under the stop rule it is deployed with
+    (include/lccrf.h sections 2e and 2k).  Returns (Q [F, max_points, L], iterations [F] int32 on the GPU, not differentiable) as
+    mean_field_batch_converged does.  The backward differentiates every frame at its own t_f in one call on the cloned device counts;
+    weights.grad and compat.grad are the batch's own ordered sums over the frames (no torch reduction).  The matrices are left set on
+    `batch`; its normalisation modes are honoured."""
+    return _apply_batch(batch, unary, weights, compat, max_iterations, relax, (criterion, tol))
 
 
 class _BatchCRF(torch.nn.Module):
@@ -460,6 +477,28 @@ class BatchCompatMeanFieldCRF(_BatchCRF):
 
     def forward(self, unary):
         return mean_field_batch_compat(self.batch, unary, self.weights, self.compat, self.n_iterations, self.relax)
+
+
+class BatchCompatConvergedMeanFieldCRF(_BatchCRF):
+    """BatchCompatMeanFieldCRF under the stop rule the model is deployed with: forward(unary [F, max_points, L]) -> (Q [F, max_points,
+    L], iterations [F] int32) through mean_field_batch_compat_converged -- every frame inferred until ITS criterion holds, at most
+    max_iterations, and differentiated at its own count (include/lccrf.h sections 2e and 2k).  Parameters `weights` [K] and `compat`
+    [K, L, L] (identities at first) and normalization as BatchCompatMeanFieldCRF; criterion, tol as BatchCRF.inference_converged takes
+    them; fused_backward: sets OPT_FUSED_BACKWARD and OPT_FUSED_BACKWARD_LEARNT on the batch (the same bits, in one launch where the
+    frames fit, plus the two of the sums over the frames)."""
+
+    def __init__(self, n_points, features, weights, max_iterations=12, criterion=_pkg.STOP_LABELS, tol=0.0, relax=1.0, device=0,
+                 n_labels=2, normalization=None, fused_backward=False):
+        super().__init__(n_points, features, weights, max_iterations, relax, device, n_labels, normalization)
+        self.criterion, self.tol = int(criterion), float(tol)
+        if fused_backward:
+            self.batch.set_option(_pkg.OPT_FUSED_BACKWARD, 1)
+            self.batch.set_option(_pkg.OPT_FUSED_BACKWARD_LEARNT, 1)
+        self.compat = _identities(len(weights), n_labels)
+
+    def forward(self, unary):
+        return mean_field_batch_compat_converged(self.batch, unary, self.weights, self.compat, self.n_iterations, self.criterion,
+                                                 self.tol, self.relax)
 
 
 # ---- a handle of its own: the features are inputs --------------------------------------------------------------------------------

@@ -362,7 +362,8 @@ struct BackwardRequest {           // (an aggregate: the members left out of a b
     bool compat_form;               // the sweep takes section 1e's form: the terms' matrices are honoured (grad_compat needs it)
     float *grad_model;              // [K + K*L*L] or null (section 2h): the sums over the frames of dL/dw and dL/dmu (needs compat_form)
     // [F] int32 on the device or null (section 2j): frame f is differentiated at t_f = min(max(counts[f], 0), T) iterations, T the cap
-    // every [T] part of the area is sized by; the kernels clamp, the host never reads the array.  Only with grad_unary / grad_weights.
+    // every [T] part of the area is sized by; the kernels clamp, the host never reads the array.  Not with grad_features; with
+    // grad_compat / grad_model it is section 2k.
     const int *counts;
 };
 // The area of one backward call, owned by the engine and zeroed when allocated: Q_0 .. Q_{T-1} of the replay, one [F][.][L] array
@@ -423,7 +424,9 @@ size_t backward_layout(const BackwardRequest &rq, const CrfDev &c, const KernelD
 // ar.gW / ar.gC where the caller left one out -- are summed over the frames in ascending order, one k_sum_frames launch each.
 // rq.counts (section 2j; null: the launches and the arithmetic above, untouched): frame f is idle while t > t_f -- its G stays the
 // caller's dL/dQ, nothing is added to its dL/dU, no partial is written for it; its filters run on (phi is scratch) -- its first step
-// is t == t_f, and the weight gradient's reduction walks its t_f x blocks partials: a handle's bits at t_f.
+// is t == t_f, and the weight gradient's reduction walks its t_f x blocks partials: a handle's bits at t_f.  In the compat form
+// (section 2k) k_compat_bwd leaves an idle frame's cpart and phi alone and writes cpart at t == t_f, and k_compat_reduce gives a frame
+// with t_f = 0 exact zeros without reading its cpart, which no iteration of the call wrote.
 struct BackwardModes {
     int mode[LCCRF_MAX_KERNELS];
     const float *norm[LCCRF_MAX_KERNELS];   // [F][maxN], KernelDev::norm of the engine's own views (not of step_kdevs())
@@ -443,7 +446,9 @@ struct TermModel;
 // with a matrix or a normalisation mode, dL/dU, dL/dw and dL/dmu per frame, no feature gradients.  kds: Engine::step_kdevs() (`norm` is
 // each term's factor behind the filter); terms: Engine's model (matrices by value, the factors in front of the filters).  Writes
 // rq.grad_unary (or ar.gU), rq.grad_weights (or ar.gW under rq.grad_model) and rq.grad_compat (or ar.gC) of every frame; the sums of
-// rq.grad_model are the caller's to launch.  Returns fused_report() of the shape launched, or 0 with nothing launched.
+// rq.grad_model are the caller's to launch.  With rq.counts (section 2k) every frame's workgroup runs its own t_f iterations, the
+// workgroups taking the frames by descending t_f (the order in ar.phi).  Returns fused_report() of the shape launched, or 0 with
+// nothing launched.
 int launch_fused_backward_general(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, int rows,
                                   const BackwardRequest &rq, const BackwardArea &ar, const TermModel &terms, hipStream_t s);
 // ... and of a request WITH feature gradients (csrc/fused_backward_features.hip; include/lccrf.h section 1l): Potts terms normalised

@@ -14,6 +14,11 @@
 //                       Phi_k^T(mu_k^T y_k)  (y_k for a Potts term)   splat_blur<.., TRANSPOSE, XIN>: an input per term
 //                       G_{t-1} = (1 - r) G_t + sum_k w_k (b_k .) Phi_k^T(..)                              k_bwd_combine<PRE>'s arithmetic
 //     the softmax backward of Q_0, k_bwd_reduce's walk and tree, and dL/dmu_k = the chunks' cp added in ascending order (k_compat_reduce)
+// With per-frame counts (section 2k) T above is the frame's own t_f, loaded once per workgroup -- a frame that stopped early leaves its CU
+// early, the Q it leaves is Q_{t_f}, and at t_f = 0 the chains' cp stay the zeros they start as -- and workgroup i takes frame
+// order[i], the frames sorted by descending t_f on the device (k_order_by_count, meanfield_backward.hip), as k_backward does: which
+// workgroup runs a frame changes no bit of it.  The counts and the order are runtime arguments, read once at the kernel's entry and dead
+// behind it (t_f takes a.T's scalar register): no instantiation more, the register figures of the kernel without them.
 //
 // Bit for bit the streaming sweep's results (-ffp-contract=off): every product and every sum is the one the streaming kernels form, in
 // their order.  a_k is what step_kdevs()[k].norm points at (n, sqrtf(n) or ones), b_k is pre_arg()[k] or absent; both are re-read per
@@ -32,7 +37,7 @@
 // phase run outside the per-point predicates, and what decides a barrier (a.gC, a.gW) is uniform.
 //
 // Scope: K in {1, 2} 2-D terms, frames of up to 2 x 1024 active points, kernel 0 with short rows or chain rows: 8 instantiations.
-// Not covered: feature gradients, larger frames, the half-CU shapes.
+// Not covered: feature gradients (at a fixed count or at per-frame counts), larger frames, the half-CU shapes.
 #include "engine.h"
 #include "device_math.h"
 #include "fused_loop.h"
@@ -64,6 +69,8 @@ struct BackwardGeneralArgs {
     float *gW;                            // [F][K] or null
     float *gC;                            // [F][K][2][2] or null
     float *partial;                       // [T][K][F][bstride]
+    const int *counts;                    // [F] or null (section 2k): frame f runs min(max(counts[f], 0), T) iterations, T the layout's
+    const int *order;                     // [F] or null: workgroup i takes frame order[i] (a permutation: the longest counts first)
 };
 
 // The kernel's arguments as the kernarg segment holds them, read where they are used: the 8 matrix words, the factors' pointers and the
@@ -118,7 +125,8 @@ __global__ void __launch_bounds__(kNT, 4) k_backward_general(CrfDev c, BackwardG
 {
     constexpr int D1 = kD1, NT = kNT, ALL = (1 << K) - 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int f = blockIdx.x;
+    // (section 2k) the frame of this workgroup and, below, its own iteration count: uniform values
+    const int f = a.order ? a.order[blockIdx.x] : blockIdx.x;
     int tid = threadIdx.x;
     const int N = c.n_points[f];
     Instr ins{nullptr, 0, 0, 0, 0};
@@ -131,6 +139,10 @@ __global__ void __launch_bounds__(kNT, 4) k_backward_general(CrfDev c, BackwardG
         if (a.gC && tid < K * 4) a.gC[(size_t)f * K * 4 + tid] = 0.0f;
         return;
     }
+
+    // the frame's own iteration count: one uniform load per workgroup, so every barrier below stays uniform; hist and partial keep
+    // their [a.T][...] layout
+    const int T = a.counts ? min(max(a.counts[f], 0), a.T) : a.T;
 
     PointRegs<PPT, K> pr;
     int V[K];
@@ -154,7 +166,7 @@ __global__ void __launch_bounds__(kNT, 4) k_backward_general(CrfDev c, BackwardG
     // ---- the replay: inference(T, 0, relax) under the model, keeping Q_0 .. Q_{T-1} --------------------------------------------------
     const size_t hs = a.slice / 2;        // float2 between the iterations of hist
     float2 *hist = reinterpret_cast<float2 *>(a.hist) + fo;
-    for (int t = 0; t < a.T; ++t) {
+    for (int t = 0; t < T; ++t) {
         opaque(pr);
         asm volatile("" : "+v"(tid));
         float2 xin[PPT][K];
@@ -205,11 +217,11 @@ __global__ void __launch_bounds__(kNT, 4) k_backward_general(CrfDev c, BackwardG
     // (fused_backward.hip: as uniform values they are live around the whole sweep for sixteen lanes' one store per iteration)
     int pterm = (int)gridDim.x * a.bstride, prow = f * a.bstride;
     asm volatile("" : "+v"(pterm), "+v"(prow));
-    const float2 *hq = hist + (size_t)a.T * hs;
-    for (int t = a.T; t >= 1; --t) {
+    const float2 *hq = hist + (size_t)T * hs;
+    for (int t = T; t >= 1; --t) {
         opaque(pr);
         asm volatile("" : "+v"(tid));
-        const bool first = t == a.T;                                      // dL/dQ_t is the caller's, dL/dU is written
+        const bool first = t == T;                                        // dL/dQ_t is the caller's, dL/dU is written
         hq -= hs;                                                         // Q_{t-1}
         float2 xin[PPT][K];
         // Phi_k(b_k . Q_{t-1})
@@ -346,7 +358,7 @@ __global__ void __launch_bounds__(kNT, 4) k_backward_general(CrfDev c, BackwardG
 
     // ---- dL/dU -= P_0 (G_0 - <G_0, P_0>), P_0 = Q_0 = softmax(-U) ---------------------------------------------------------------
     {
-        const bool first = a.T == 0;
+        const bool first = T == 0;
 #pragma unroll
         for (int s = 0; s < PPT; ++s) {
             const int i = tid + s * NT;
@@ -380,7 +392,7 @@ __global__ void __launch_bounds__(kNT, 4) k_backward_general(CrfDev c, BackwardG
     const int k = tid / kPartialRows, j = tid - k * kPartialRows;
     if (k < K) {
         const float *row = a.partial + (size_t)k * pterm + prow;             // this frame's partials of term k, iteration 1
-        const int n = a.T * nblk;
+        const int n = T * nblk;
         float acc = 0.0f;
         for (int idx = j; idx < n; idx += kPartialRows) {
             const int t = idx / nblk, b = idx - t * nblk;
@@ -417,11 +429,18 @@ int launch_fused_backward_general(const CrfDev &c, const KernelDev *kds, const i
     a.gW = rq.grad_weights ? rq.grad_weights : ar.gW;
     a.gC = rq.grad_compat ? rq.grad_compat : ar.gC;
     a.partial = ar.partial;
+    a.counts = rq.counts;
     bool launched = false;
     const int report = plan_variant<kBackwardMaxPPT>(c, kds, maxV, maxRow, kBackwardLds, a, [&](auto p, auto kk, auto ch) {
         if (a.gC && !a.lay.prod_all) return;              // (the staged products of dL/dmu live in the terms' own product buffers)
         for (int k = 0; k < c.K; ++k) a.pre[k] = terms.pre ? terms.pre[k] : nullptr;
         a.has_mu = copy_matrices(terms, c.K, a.mu);
+        // (section 2k) the longest frames first, as k_backward takes them (fused_backward.hip): the order lives in the area's `phi`, which
+        // this kernel does not touch (K * slice floats: room for F ints)
+        if (rq.counts && (size_t)c.K * ar.slice >= (size_t)c.F) {
+            launch_order_by_count(rq.counts, c.F, rq.T, reinterpret_cast<int *>(ar.phi), s);
+            a.order = reinterpret_cast<const int *>(ar.phi);
+        }
         launch_workgroups(k_backward_general<decltype(p)::value, decltype(kk)::value, decltype(ch)::value>, c.F, kNT,
                           a.lay.total + kBackwardLds, s, c, a);
         launched = true;

@@ -60,7 +60,7 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
     // LCCRF_OPT_FUSED_BACKWARD (include/lccrf.h section 1j): dL/dU and / or dL/dw of Potts terms normalised AFTER, on frames the fused
     // plan takes -- the replay and the sweep in one launch, the same bits (fused_backward.hip).  Decided for the whole batch, over its
     // largest frame and lattices; behind every check and the area, so a rejected call leaves the handle as it was either way.
-    // With rq.counts (section 2j) too: each frame's workgroup then runs its own t_f iterations; the other one-launch kernels take none.
+    // With rq.counts (section 2j) too: each frame's workgroup then runs its own t_f iterations; the feature kernel takes none.
     const bool plain_form = !rq.compat_form && !rq.grad_compat && !rq.grad_model;   // (not the compat form: no dL/dmu, no sums, no matrix)
     bool no_features = true;
     for (int k = 0; k < K && rq.grad_features; ++k) no_features &= rq.grad_features[k] == nullptr;
@@ -74,7 +74,8 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
     // LCCRF_OPT_FUSED_BACKWARD_LEARNT (section 1k): the complement among the requests without feature gradients -- a learnt model
     // (a matrix, or a mode other than AFTER), or the compat form (dL/dmu, also of Potts terms) -- decided in the same place and the
     // same way (fused_backward_general.hip).  The sums over the frames (section 2h) are the sweep's two launches, behind the kernel.
-    if (opt.fused_backward_learnt && !rq.counts && no_features && count && (model.general() || rq.compat_form) && !perm_on &&
+    // With rq.counts (section 2k) too, as k_backward takes them: each frame's workgroup runs its own t_f iterations.
+    if (opt.fused_backward_learnt && no_features && count && (model.general() || rq.compat_form) && !perm_on &&
         launch_fused_backward_general(crf, step_kdevs(), maxV.data(), maxRow.data(), rows, rq, ar, model.terms((size_t)K), stream)) {
         if (rq.grad_model) {
             launch_sum_frames(rq.grad_weights ? rq.grad_weights : ar.gW, F, K, rq.grad_model, stream);

@@ -428,6 +428,8 @@ void launch_softmax_bwd(const BwdArgs &a, int F, hipStream_t s)
 // puts y and Phi of row r into LDS, lane p (and p + 256, ...) adds the tile's rows in order to its entries (l, l') of the outer
 // product, kept in registers over the whole chunk, and lane r * L + l' forms row r of mu^T y.  No atomics: an entry has one owner and
 // one order of additions (rows ascending; t = T .. 1 across the sweep's launches), the same bits from run to run.
+// counts != null (section 2k): a frame is idle while t > t_f -- its workgroups leave before the first barrier, on blockIdx.y alone,
+// with nothing written to cpart or phi -- and its first iteration, the one that writes cpart, is t == t_f.
 constexpr int kCompatTileB = kBwdBlock + kBwdBlock / 2;   // R * (L | 1) <= 256 + R floats
 constexpr int kCompatPairs = (LCCRF_MAX_LABELS * LCCRF_MAX_LABELS + kBwdBlock - 1) / kBwdBlock;   // entries of mu per lane
 // (compat_chunks, the chunks of a frame of n points: engine.h -- the one-launch kernel of fused_backward_general.hip cuts the same)
@@ -442,6 +444,8 @@ struct CompatArgs {
     const float *mu;             // [L][L] or null
     float w;
     float *cpart;                // [F][gridDim.x][L * L] or null
+    const int *counts;           // [F] or null (section 2k): the frame's own iteration count, clamped to [0, cap] by frame_count
+    int t, cap;                  // ... the sweep's iteration of this launch and the counts' cap
 };
 
 __global__ void __launch_bounds__(kBwdBlock) k_compat_bwd(CompatArgs a)
@@ -451,6 +455,12 @@ __global__ void __launch_bounds__(kBwdBlock) k_compat_bwd(CompatArgs a)
     const int f = blockIdx.y, L = a.L, N = a.n_points[f];
     const int B = compat_chunks(N);                       // (a handle: gridDim.x)
     if ((int)blockIdx.x >= B) return;                     // (the whole workgroup, before any barrier)
+    int begins = a.first;                                 // this launch is the frame's first step: cpart is written, not added to
+    if (a.counts) {                                       // (uniform over the workgroup: blockIdx.y alone decides)
+        const int tf = frame_count(a.counts, f, a.cap);
+        if (a.t > tf) return;                             // an idle frame: nothing written, before any barrier
+        begins = a.t == tf;
+    }
     const int R = kBwdBlock / L, st = L == 1 ? 1 : (L | 1), tid = threadIdx.x;
     const int r = tid / L, l = tid - r * L;
     const int chunk = (N + B - 1) / B;
@@ -500,22 +510,25 @@ __global__ void __launch_bounds__(kBwdBlock) k_compat_bwd(CompatArgs a)
 #pragma unroll
     for (int j = 0; j < kCompatPairs; ++j) {
         const int p = tid + j * kBwdBlock;
-        if (p < L * L) cp[p] = a.first ? a.w * acc[j] : cp[p] + a.w * acc[j];
+        if (p < L * L) cp[p] = begins ? a.w * acc[j] : cp[p] + a.w * acc[j];
     }
 }
 
 // out[f][k][l][l'] = sum over the frame's chunks b = 0 .. compat_chunks(n_points[f]) - 1, in that order, of cpart[k][f][b][l][l']
 // (bstride: the chunks the partials have room for, the sweep's grid); one owner per (frame, term, entry).  A handle is one frame of
 // bstride chunks.  A frame of 0 points gets 0.
+// counts != null (section 2k): so does a frame with t_f = 0 -- no iteration wrote its cpart, and what an earlier call left there is not
+// read.
 __global__ void __launch_bounds__(kBwdBlock) k_compat_reduce(const float *__restrict__ cpart, const int *__restrict__ n_points, int K, int F,
-                                                           int bstride, int LL, float *__restrict__ out)
+                                                           int bstride, int LL, float *__restrict__ out,
+                                                           const int *__restrict__ counts, int T)
 {
     const long idx = (long)blockIdx.x * kBwdBlock + threadIdx.x;
     if (idx >= (long)F * K * LL) return;
     const int f = (int)(idx / ((long)K * LL));
     const int e = (int)(idx - (long)f * K * LL);
     const int k = e / LL, p = e - k * LL;
-    const int N = n_points[f], B = N > 0 ? compat_chunks(N) : 0;
+    const int N = n_points[f], B = N > 0 && (!counts || frame_count(counts, f, T) > 0) ? compat_chunks(N) : 0;
     const float *cp = cpart + ((size_t)k * F + f) * bstride * LL + p;
     float s = 0.0f;
     for (int b = 0; b < B; ++b) s += cp[(size_t)b * LL];
@@ -868,7 +881,7 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
         for (int k = 0; k < K; ++k) {
             if (cmode) {                                   // phi_k: Phi_k(Q_{t-1}) -> mu_k^T (n_k gamma_t); dL/dmu_k's partials
                 CompatArgs ca{c.n_points, L, t == T, c.maxN, fs, ar.gam, kds[k].norm, ar.phi + k * slice, a.compat[k], kds[k].w,
-                              grad_compat ? ar.cpart + (size_t)k * F * cblk * L * L : nullptr};
+                              grad_compat ? ar.cpart + (size_t)k * F * cblk * L * L : nullptr, rq.counts, t, T};
                 k_compat_bwd<<<dim3((unsigned)cblk, (unsigned)F), kBwdBlock, 0, s>>>(ca);
             }
             // (section 1f: the slice side's upstream row is what k_compat_bwd has just left in phi_k, n_k (mu_k^T gamma_t))
@@ -899,7 +912,7 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
     launch_softmax_bwd<kBwdPlain>(a, F, s);
     if (grad_compat && K && T >= 1)
         k_compat_reduce<<<(unsigned)(((size_t)F * K * L * L + kBwdBlock - 1) / kBwdBlock), kBwdBlock, 0, s>>>(ar.cpart, c.n_points, K, F, cblk,
-                                                                                                            L * L, grad_compat);
+                                                                                                            L * L, grad_compat, rq.counts, T);
     // the norm part, <a_k, Phi_k(1)> with a_k = -n_k^2 g_n[k] (value width 1), and dL/db -> dL/df
     // (section 1m: g_n from the adjoints by the term's mode, n_k the true norm; a term without a norm factor has no norm part)
     for (int k = 0; k < K; ++k) {
