@@ -647,7 +647,8 @@ int  lccrf_run_converged(lccrf_handle h, int max_iterations, int criterion, floa
  *     change; a request without a feature array is section 1j's or 1k's and never this option's);
  *   - the call is not in section 1e's form: neither d_grad_compat nor d_grad_model, no matrix on the handle or batch --
  *     lccrf_inference_backward_features, lccrf_batch_inference_backward_features, and lccrf_inference_backward_all /
- *     lccrf_batch_inference_backward_all when they reduce to those;
+ *     lccrf_batch_inference_backward_all when they reduce to those, and section 2l's
+ *     lccrf_batch_inference_backward_modes_converged on such a batch: every frame's workgroup then runs its own t_f iterations;
  *   - every term is a Potts term normalised AFTER the filter, and n_iterations >= 1 (at 0 the call takes the sweep's memset to +0);
  *   - the frames are ones the plan takes, as in section 1j.  A batch decides once, over its largest frame and lattices.
  * Everything else takes the route it takes with the option off; options 6 and 7 select exactly what they selected.
@@ -1144,8 +1145,8 @@ int  lccrf_batch_inference_backward_modes(lccrf_batch_handle b, int n_iterations
  *     the NULL d_iterations are answered before the batch is looked at); a rejected call leaves the batch as it was; d_grad_weights
  *     may be NULL, K = 0 is legal.
  *   - Potts terms normalised AFTER only, as section 2c: on a batch with a matrix or a mode other than AFTER the call returns
- *     LCCRF_E_STATE and leaves the batch as it was: learnt models in section 2h's form are section 2k's.  Not covered
- *     (notes/convergence.md sections 6 and 7): feature gradients at per-frame counts, the one-launch kernel of section 1l.
+ *     LCCRF_E_STATE and leaves the batch as it was: learnt models in section 2h's form are section 2k's.  Feature gradients at
+ *     per-frame counts, the one-launch kernel of section 1l included, are section 2l's.
  * ==================================================================================== */
 int  lccrf_batch_inference_backward_converged(lccrf_batch_handle b, int max_iterations, float relax, const int32_t *d_iterations,
                                               const float *d_grad_prob, float *d_grad_unary, float *d_grad_weights, void *stream);
@@ -1183,12 +1184,57 @@ int  lccrf_batch_inference_backward_converged(lccrf_batch_handle b, int max_iter
  *     at; a device array that section 1b refuses gives LCCRF_E_INVALID; a call before lccrf_batch_build / _run gives LCCRF_E_STATE.
  *     A rejected call leaves the batch as it was.  K = 0 is legal.
  *   - Memory: section 2h's area at T = max_iterations.
- *   - Not covered (notes/convergence.md section 7): feature gradients at per-frame counts (sections 2d / 2i), handle-level entry
- *     points (a handle's recipe stays lccrf_inference_backward_all at the reported count), the half-CU shapes.
+ *   - Feature gradients at per-frame counts (sections 2d / 2i) are section 2l's.  Not covered (notes/convergence.md section 7):
+ *     handle-level entry points (a handle's recipe stays lccrf_inference_backward_all at the reported count), the half-CU shapes.
  * ==================================================================================== */
 int  lccrf_batch_inference_backward_all_converged(lccrf_batch_handle b, int max_iterations, float relax, const int32_t *d_iterations,
                                                   const float *d_grad_prob, float *d_grad_unary, float *d_grad_weights,
                                                   float *d_grad_compat, float *d_grad_model, void *stream);
+
+/* ======================================================================================
+ * 2l. FEATURE gradients of a batch's CONVERGED inference -- section 2i's call with section 2j's d_iterations: dL/d features of every
+ *     term asked for, under any model (Potts or learnt, any normalisation mode), every frame differentiated at its own iteration
+ *     count (lc-crf-slam_amd/autograd.py: mean_field_batch_features_converged, BatchLearnedKernelCRF).  Added WITHOUT a step of
+ *     LCCRF_ABI_VERSION (it stays 3): probe for it by symbol.  Every other entry point is unchanged and keeps refusing what it refuses.
+ *
+ * The contract is the conjunction of sections 2i and 2j.  d_iterations: section 2j's device array of [n_frames] int32, read in stream
+ * order and never by the host -- lccrf_batch_device_convergence's array goes straight in behind lccrf_batch_inference_converged on
+ * the same stream.  Frame f is differentiated at t_f = min(max(d_iterations[f], 0), max_iterations) (the kernels clamp).  Outputs as
+ * section 2i's, each overwritten, each may be NULL: d_grad_unary, d_grad_weights, d_grad_features (the array, or any entry),
+ * d_grad_compat, d_grad_model.
+ *   - Per frame, the bits of section 1m at t_f: d_grad_unary[f], d_grad_weights[f], d_grad_features[k][f] and d_grad_compat[f] are
+ *     exactly what lccrf_inference_backward_modes(h, t_f, relax, ...) returns for a handle holding frame f with the batch's weights,
+ *     matrices and modes -- the order of the additions into dL/d(corner weight) and the norm's accumulator included: t = t_f .. 1,
+ *     slice side then splat side, post adjoint before pre adjoint, the norm part last.  Rows at or beyond n_points[f] of d_grad_unary
+ *     and of every d_grad_features[k] are written +0; a frame of 0 points gets zeros.
+ *   - A frame with t_f = 0: d_grad_features[k][f] is exactly +0 in every row -- the bits of the handle's memset at n_iterations = 0,
+ *     whatever an earlier call left in the batch's area --, d_grad_weights[f] and d_grad_compat[f] are exactly 0 as in section 2k, and
+ *     dL/dU is section 2c's T = 0 result.
+ *   - d_grad_model is section 2h's ascending-frame fp32 sum of this call's per-frame values, with its bits.
+ *   - Afterwards frame f of the batch's Q holds Q_{t_f}.  Labels, label bits and the stored convergence report are not changed.
+ *   - d_grad_features == NULL, or every entry NULL: the call IS lccrf_batch_inference_backward_all_converged (section 2k): same bits,
+ *     same route.
+ *   - Every count equal to max_iterations: every output and the Q left behind are lccrf_batch_inference_backward_modes(b,
+ *     max_iterations, relax, ...)'s, bit for bit.
+ *   - Routes: the streaming sweep leaves frame f idle while t > t_f, the corner dots and the pre adjoint included -- nothing is added
+ *     to an idle frame's accumulators, its dL/dQ stays the caller's; the norm part behind the sweep runs for every frame (at t_f = 0
+ *     on zeroed accumulators: +0 out).  Under LCCRF_OPT_FUSED_BACKWARD_FEATURES, on the requests section 1l takes (Potts terms
+ *     normalised AFTER, no d_grad_compat / d_grad_model, two labels, one or two 2-D terms, at most 2048 points), frame f's workgroup
+ *     loads t_f once and runs t_f replays and t_f sweep steps, the workgroups taking the frames by descending t_f (ranked on the
+ *     device); a frame with t_f = 0 skips the norm part and writes its dL/df as +0.  The same bits: which workgroup runs a frame
+ *     changes none.  A learnt model with feature arrays streams.  lccrf_batch_get_backward_route reports the route.
+ *   - Errors: max_iterations < 0, a relax that is not finite and a NULL d_iterations give LCCRF_E_INVALID before the batch is looked
+ *     at; a device array that section 1b refuses gives LCCRF_E_INVALID; a call before lccrf_batch_build / _run gives LCCRF_E_STATE.
+ *     A rejected call leaves the batch as it was.  K = 0 is legal.
+ *   - Memory: section 2i's area at T = max_iterations.
+ *   - Not covered (notes/convergence.md section 8): handle-level entry points (a handle's recipe stays
+ *     lccrf_inference_backward_modes at the reported count), feature gradients of learnt models in one launch, the half-CU shapes, a
+ *     streaming replay that stops stepping finished frames.
+ * ==================================================================================== */
+int  lccrf_batch_inference_backward_modes_converged(lccrf_batch_handle b, int max_iterations, float relax, const int32_t *d_iterations,
+                                                    const float *d_grad_prob, float *d_grad_unary, float *d_grad_weights,
+                                                    float *const *d_grad_features, float *d_grad_compat, float *d_grad_model,
+                                                    void *stream);
 
 /* ======================================================================================
  * 3. Unary builder -- the step right before the CRF (first "next" row):

@@ -217,6 +217,8 @@ def lib():
         L.lccrf_batch_inference_backward_converged.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, vp, vp]
     if hasattr(L, "lccrf_batch_inference_backward_all_converged"):                # (section 2k: probe by symbol)
         L.lccrf_batch_inference_backward_all_converged.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "lccrf_batch_inference_backward_modes_converged"):              # (section 2l: probe by symbol)
+        L.lccrf_batch_inference_backward_modes_converged.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, vp, C.POINTER(vp), vp, vp, vp]
     L.lccrf_batch_set_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p]
     L.lccrf_batch_get_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p, C.POINTER(C.c_int)]
     L.lccrf_batch_set_pairwise_normalization.argtypes = [vp, C.c_int, C.c_int]
@@ -597,6 +599,7 @@ class BatchCRF(_Handle):
             d.weights[i] = float(w)
         self.h = C.c_void_p()
         self.n_frames, self.n_points = 0, None        # n_points: the host counts of the inputs bound, when they came from the host
+        self.inputs_serial = 0                        # counts the calls that gave the batch inputs: who bound last can tell (autograd.py)
         _check(lib().lccrf_batch_create(C.byref(self.h), int(device), C.byref(d)))
         self._keep = None
 
@@ -615,6 +618,7 @@ class BatchCRF(_Handle):
             self.h, F, _p(npts, _i32p), _p(u, _f32p) if u is not None else None,
             _p(l, _i16p) if l is not None else None, _p(cf, _f32p) if cf is not None else None, arr))
         self.n_frames, self.n_points = F, npts.copy()
+        self.inputs_serial += 1
 
     HOST_PINNED = 1
     DOWNLOAD_LABEL_BITS, DOWNLOAD_MAP, DOWNLOAD_PROBABILITY = 1, 2, 4
@@ -646,6 +650,7 @@ class BatchCRF(_Handle):
             self.h, F, C.c_void_p(npts.ctypes.data), u, l, _p(cf, _f32p) if cf is not None else None, arr,
             self.HOST_PINNED if pinned else 0))
         self.n_frames, self.n_points = F, npts.copy()
+        self.inputs_serial += 1
 
     def wait_inputs(self):
         _check(lib().lccrf_batch_wait_inputs(self.h))
@@ -682,6 +687,7 @@ class BatchCRF(_Handle):
             self.h, int(n_frames), C.c_void_p(int(d_n_points)), _addr(d_unary), _addr(d_label),
             _p(cf, _f32p) if cf is not None else None, arr))
         self.n_frames, self.n_points = int(n_frames), None        # (the counts live on the device)
+        self.inputs_serial += 1
 
     def build(self, stream=None):
         _check(lib().lccrf_batch_build(self.h, _addr(stream)))
@@ -775,6 +781,18 @@ class BatchCRF(_Handle):
         _check(lib().lccrf_batch_inference_backward_modes(self.h, int(n_iterations), float(relax), C.c_void_p(int(d_grad_prob)),
                                                           _addr(d_grad_unary), _addr(d_grad_weights), _addr_list(d_grad_features),
                                                           _addr(d_grad_compat), _addr(d_grad_model), _addr(stream)))
+
+    def inference_backward_modes_converged_device(self, max_iterations, relax, d_iterations, d_grad_prob, d_grad_unary=None,
+                                                  d_grad_weights=None, d_grad_features=None, d_grad_compat=None, d_grad_model=None,
+                                                  stream=None):
+        """inference_backward_modes_device with every frame at its own iteration count (include/lccrf.h section 2l): d_iterations as
+        inference_backward_converged_device takes it -- device_convergence()["iterations"] behind inference_converged(), or a copy of
+        it, clamped per frame to [0, max_iterations] and never read by the host.  Without a feature array it is
+        inference_backward_all_converged_device."""
+        _check(lib().lccrf_batch_inference_backward_modes_converged(self.h, int(max_iterations), float(relax), _addr(d_iterations),
+                                                                    _addr(d_grad_prob), _addr(d_grad_unary), _addr(d_grad_weights),
+                                                                    _addr_list(d_grad_features), _addr(d_grad_compat),
+                                                                    _addr(d_grad_model), _addr(stream)))
 
     pairwise_compatibility, normalization = _Handle.get_pairwise_compatibility, _Handle.get_normalization   # (the batch's own names)
 

@@ -1,4 +1,4 @@
-"""torch autograd through DenseCRF::inference on the HIP path (include/lccrf.h sections 1c - 1g, 1m, 2c, 2j and 2k).
+"""torch autograd through DenseCRF::inference on the HIP path (include/lccrf.h sections 1c - 1g, 1m, 2c, 2i - 2l).
 
     Q = mean_field(crf, unary, weights, n_iterations=5, relax=1.0)
     Q.backward(g)      # -> unary.grad = dL/dU, weights.grad = dL/dw
@@ -17,6 +17,12 @@
 
     Q, t = mean_field_batch_compat_converged(batch, unary, weights, compat, max_iterations=12)   # ... under a learnt model
     Q.backward(g)      # -> also compat.grad; the sums over the frames at every frame's own count (section 2k)
+
+    Q = mean_field_batch_features(batch, n_points, unary, [f_0, ..], weights, n_iterations=5)   # a batch, the features inputs too
+    Q.backward(g)      # -> also f_k.grad [F, max_points, d_k] (sections 2d / 2i); the lattices are built by the forward
+
+    Q, t = mean_field_batch_features_converged(batch, n_points, unary, [f_0, ..], weights, max_iterations=12)   # ... under the stop rule
+    Q.backward(g)      # -> every frame at ITS count, dL/d features included (section 2l); BatchLearnedKernelCRF fits bandwidths with both
 
     Q = mean_field_features(unary, [f_0, f_1, ..], weights, n_iterations=5, relax=1.0)        # the features are inputs too
     Q.backward(g)      # -> also f_k.grad = dL/d features [N, d_k] (section 1d); LearnedKernelCRF fits kernel bandwidths with it
@@ -295,11 +301,14 @@ class _MeanFieldBatch(torch.autograd.Function):
     mean_field_batch_compat_converged on a caller's BatchCRF.  The backwards are different calls: without matrices section 2c, which
     refuses a batch that carries matrices or modes, and torch's sum of its [F, K] output (under a stop rule section 2j, section 2c at
     every frame's own count); with them section 2h, whose model gradients are the batch's own ordered sums over the frames (under a
-    stop rule section 2k, section 2h at every frame's own count)."""
+    stop rule section 2k, section 2h at every frame's own count).
+    With `bind` and the K feature tensors behind it: mean_field_batch_features and mean_field_batch_features_converged -- the forward
+    binds its own inputs to the batch and builds the lattices, the backward is section 2i's call (under a stop rule section 2l's) with
+    a feature array for every tensor that needs a gradient."""
 
     @staticmethod
-    def forward(ctx, batch, unary, weights, compat, n_iterations, relax, n_points, stop):
-        F, N, L = batch.n_frames, batch.maxN, batch.L
+    def forward(ctx, batch, unary, weights, compat, n_iterations, relax, n_points, stop, bind=False, *features):
+        F, N, L = len(n_points) if bind else batch.n_frames, batch.maxN, batch.L
         _check_unary_weights(unary, (F, N, L), weights, len(batch.dims))
         _check_compat_iterations(compat, len(batch.dims), L, n_iterations)
         _check_stop(stop, compat, batch=True)
@@ -307,7 +316,11 @@ class _MeanFieldBatch(torch.autograd.Function):
         u = unary.detach().contiguous()
         w, m = _model(weights, compat)
         it = None
+        fs = _check_batch_features(features, batch.dims, F, N) if bind else []
         with _on_stream(batch.own_stream(), dev) as (ext, cur):
+            if bind:
+                ctx.n_points = np.ascontiguousarray(n_points, np.int32)
+                ctx.serial = _bind_and_build(batch, ctx.n_points, u, fs)
             _arm(batch, w, m)
             batch.set_unary_device(u.data_ptr())
             if stop is None:
@@ -323,7 +336,8 @@ class _MeanFieldBatch(torch.autograd.Function):
         live = torch.arange(N, device=dev)[None, :] < torch.as_tensor(n_points, device=dev)[:, None]
         q = torch.where(live[:, :, None], q, torch.zeros((), device=dev))    # rows beyond a frame's points: 0
         _remember(ctx, batch, n_iterations, relax, weights, compat)
-        ctx.save_for_backward(u, w, m, it)
+        ctx.bind = bool(bind)
+        ctx.save_for_backward(u, w, m, it, *fs)
         if it is None:
             return q
         ctx.mark_non_differentiable(it)
@@ -331,11 +345,13 @@ class _MeanFieldBatch(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_q, *_):
-        u, w, m, it = ctx.saved_tensors
+        u, w, m, it = ctx.saved_tensors[:4]
         batch, dev = ctx.target, u.device
         K, L = int(w.numel()), batch.L
         g = _grad_in(grad_q, dev)
         grad_u = torch.empty_like(u)
+        if ctx.bind:
+            return _MeanFieldBatch._backward_features(ctx, g, grad_u, u, w, m, it, list(ctx.saved_tensors[4:]))
         if m is None:
             grad_w = torch.empty((batch.n_frames, max(K, 1)), dtype=torch.float32, device=dev)
         else:
@@ -359,6 +375,59 @@ class _MeanFieldBatch(torch.autograd.Function):
             return None, grad_u, grad_w[:, :K].sum(0).to(ctx.weights_device), None, None, None, None, None
         return (None, grad_u, model[:K].to(ctx.weights_device), model[K:K * (1 + L * L)].reshape(K, L, L).to(ctx.compat_device),
                 None, None, None, None)
+
+    @staticmethod
+    def _backward_features(ctx, g, grad_u, u, w, m, it, fs):
+        """the backward of the functions that take the features: section 2i's call, under a stop rule section 2l's.  With matrices the
+        model's gradients are the batch's own ordered sums (d_grad_model, no torch reduction); without them the request stays in the
+        plain form -- per-frame dL/dw, summed by torch as mean_field_batch does -- which is the form OPT_FUSED_BACKWARD_FEATURES takes
+        in one launch (include/lccrf.h section 1l)."""
+        batch, dev = ctx.target, u.device
+        K, L, F = int(w.numel()), batch.L, int(u.shape[0])
+        grad_f = [torch.empty_like(f) if ctx.needs_input_grad[9 + k] else None for k, f in enumerate(fs)]
+        ptrs = [t.data_ptr() if t is not None else None for t in grad_f]
+        model = torch.zeros(max(K * (1 + L * L), 1), dtype=torch.float32, device=dev) if m is not None else None
+        grad_w = torch.empty((F, max(K, 1)), dtype=torch.float32, device=dev) if m is None else None
+        gw_ptr, md_ptr = (grad_w.data_ptr() if K else None, None) if m is None else (None, model.data_ptr() if K else None)
+        with _on_stream(batch.own_stream(), dev):
+            if batch.inputs_serial != ctx.serial:             # the batch has been given other inputs since: this forward's again
+                ctx.serial = _bind_and_build(batch, ctx.n_points, u, fs)
+            _arm(batch, w, m)                                 # (the weights, matrices and unaries may be another forward's too)
+            batch.set_unary_device(u.data_ptr())
+            if it is not None:
+                batch.inference_backward_modes_converged_device(ctx.n_iterations, ctx.relax, it.data_ptr(), g.data_ptr(), grad_u.data_ptr(),
+                                                                gw_ptr, ptrs, None, md_ptr)
+            else:
+                batch.inference_backward_modes_device(ctx.n_iterations, ctx.relax, g.data_ptr(), grad_u.data_ptr(), gw_ptr, ptrs, None,
+                                                      md_ptr)
+        if m is None:
+            gw, gm = grad_w[:, :K].sum(0).to(ctx.weights_device), None
+        else:
+            gw, gm = model[:K].to(ctx.weights_device), model[K:K * (1 + L * L)].reshape(K, L, L).to(ctx.compat_device)
+        return (None, grad_u, gw, gm, None, None, None, None, None) + tuple(grad_f)
+
+
+def _check_batch_features(features, dims, F, N):
+    """the K feature tensors of a batch function: float32, on the GPU, [F, max_points, d_k] -> detached and contiguous"""
+    if len(features) != len(dims):
+        raise ValueError("one feature tensor per term of the batch (%d)" % len(dims))
+    for f, d in zip(features, dims):
+        if not f.is_cuda or f.dtype != torch.float32 or tuple(f.shape) != (F, N, d):
+            raise ValueError("every feature tensor must be a float32 GPU tensor of shape [%d, %d, d_k]" % (F, N))
+    return [f.detach().contiguous() for f in features]
+
+
+def _bind_and_build(batch, n_points, u, fs):
+    """bind one forward's unaries and features to the batch (lccrf_batch_bind_inputs_device: bound, not copied -- the batch keeps
+    them alive) and build the lattices (inside _on_stream); returns the batch's inputs_serial, by which a backward tells whether the
+    batch still holds them.  The point counts go to the device from the host's and are complete before the call, as it demands."""
+    d_np = torch.as_tensor(n_points, dtype=torch.int32).to(u.device)
+    torch.cuda.current_stream(u.device).synchronize()
+    batch.bind_inputs_device(int(n_points.size), d_np.data_ptr(), [f.data_ptr() for f in fs], d_unary=u.data_ptr())
+    batch.n_points = n_points.copy()                          # (known here, although they were bound from the device)
+    batch._bound = (d_np, u, fs)
+    batch.build()
+    return batch.inputs_serial
 
 
 def _apply_batch(batch, unary, weights, compat, n_iterations, relax, stop=None):
@@ -399,6 +468,27 @@ def mean_field_batch_compat_converged(batch, unary, weights, compat, max_iterati
     weights.grad and compat.grad are the batch's own ordered sums over the frames (no torch reduction).  The matrices are left set on
     `batch`; its normalisation modes are honoured."""
     return _apply_batch(batch, unary, weights, compat, max_iterations, relax, (criterion, tol))
+
+
+def mean_field_batch_features(batch, n_points, unary, features, weights, n_iterations=5, relax=1.0, compat=None):
+    """mean_field_batch with the features as inputs: `features` a list of K [F, max_points, d_k] float32 GPU tensors (already divided
+    by the kernels' standard deviations), `n_points` [F] host integers, `unary` [F, max_points, L].  The forward binds the tensors to
+    `batch` (BatchCRF.bind_inputs_device), builds every frame's lattices, sets weights and -- with `compat` [K, L, L] -- matrices, and
+    runs inference(n_iterations, relax); the batch's normalisation modes are honoured.  Differentiable in unary, every features[k],
+    weights and compat: one lccrf_batch_inference_backward_modes call (include/lccrf.h section 2i) with a feature array per tensor
+    that needs a gradient.  With compat, weights.grad and compat.grad are the batch's own ordered sums over the frames (d_grad_model);
+    without, weights.grad is torch's sum of the per-frame dL/dw, and the request is one OPT_FUSED_BACKWARD_FEATURES takes in one
+    launch.  A backward behind another forward on the same batch binds and builds its own inputs again."""
+    return _MeanFieldBatch.apply(batch, unary, weights, compat, n_iterations, relax, n_points, None, True, *features)
+
+
+def mean_field_batch_features_converged(batch, n_points, unary, features, weights, max_iterations, criterion=_pkg.STOP_LABELS, tol=0.0,
+                                        relax=1.0, compat=None):
+    """mean_field_batch_features "until converged, at most max_iterations": every frame stops on its own (include/lccrf.h section 2e).
+    Returns (Q [F, max_points, L], iterations [F] int32 on the GPU, not differentiable), the counts a clone of the batch's device report
+    taken on the batch's stream.  The backward differentiates every frame at its own count, dL/d features included, in one
+    lccrf_batch_inference_backward_modes_converged call on those counts (section 2l); everything else as mean_field_batch_features."""
+    return _MeanFieldBatch.apply(batch, unary, weights, compat, max_iterations, relax, n_points, (criterion, tol), True, *features)
 
 
 class _BatchCRF(torch.nn.Module):
@@ -596,6 +686,18 @@ def mean_field_learned_modes(unary, features, weights, compat, normalization, n_
     return _MeanFieldFeatures.apply(unary, weights, compat, n_iterations, relax, device, False, None, normalization, *features)
 
 
+def _bandwidth_parameter(d, s, g, dev):
+    """one term's bandwidth parameterisation: (log_sd, one value per group, an nn.Parameter; the group of every one of the d columns)"""
+    g = [[c] for c in range(d)] if g is None else [list(x) for x in g]
+    if sorted(c for x in g for c in x) != list(range(d)):
+        raise ValueError("the groups of a term must partition its %d columns" % d)
+    s = np.broadcast_to(np.asarray(s, np.float64), (len(g),))
+    col = np.empty(d, np.int64)
+    for j, x in enumerate(g):
+        col[x] = j
+    return torch.nn.Parameter(torch.tensor(np.log(s), dtype=torch.float32, device=dev)), torch.as_tensor(col, device=dev)
+
+
 class LearnedKernelCRF(torch.nn.Module):
     """A dense CRF layer whose kernel standard deviations are learned with the term weights.
 
@@ -619,16 +721,9 @@ class LearnedKernelCRF(torch.nn.Module):
         self.log_sd = torch.nn.ParameterList()
         self._col = []                                        # per term: group of every column
         for f, s, g in zip(self.raw, sd, groups):
-            d = int(f.shape[1])
-            g = [[c] for c in range(d)] if g is None else [list(x) for x in g]
-            if sorted(c for x in g for c in x) != list(range(d)):
-                raise ValueError("the groups of a term must partition its %d columns" % d)
-            s = np.broadcast_to(np.asarray(s, np.float64), (len(g),))
-            col = np.empty(d, np.int64)
-            for j, x in enumerate(g):
-                col[x] = j
-            self._col.append(torch.as_tensor(col, device=dev))
-            self.log_sd.append(torch.nn.Parameter(torch.tensor(np.log(s), dtype=torch.float32, device=dev)))
+            log_sd, col = _bandwidth_parameter(int(f.shape[1]), s, g, dev)
+            self._col.append(col)
+            self.log_sd.append(log_sd)
         self.weights = _weights_parameter(weights)
         self.n_iterations, self.relax, self.device = int(n_iterations), float(relax), int(device)
         self.fused_backward = bool(fused_backward)
@@ -665,3 +760,62 @@ class LearnedCRF(LearnedKernelCRF):
     def forward(self, unary):
         return mean_field_learned_modes(unary, self.features(), self.weights, self.compat, self.normalization, self.n_iterations,
                                         self.relax, self.device)
+
+
+class BatchLearnedKernelCRF(torch.nn.Module):
+    """LearnedKernelCRF over the frames of a batch: the kernel standard deviations (shared by every frame) are learned with the term
+    weights, at a fixed count or under the stop rule the model is deployed with.
+
+    n_points: [F] points per frame; raw_features: list of [F, max_points, d_k] arrays or tensors, NOT divided by any standard deviation;
+    sd, groups and weights as LearnedKernelCRF takes them.  The parameters are log_sd[k] (one value per group) and weights; forward(unary
+    [F, max_points, L]) forms raw * exp(-log_sd) and calls, on a BatchCRF the layer owns, mean_field_batch_features_converged when
+    max_iterations is given -- it then returns (Q, iterations [F] int32) -- and mean_field_batch_features at n_iterations otherwise (it
+    returns Q): every forward builds the lattices afresh, autograd carries dL/d features to the bandwidths (include/lccrf.h sections 2i
+    and 2l).  normalization: None (the reference's form), one NORMALIZE_* mode for every term, or one per term, set once;
+    fused_backward: sets OPT_FUSED_BACKWARD_FEATURES on the batch (section 1l: the same bits in one launch where the frames fit and
+    every term is normalised AFTER); batch.backward_route() is the route of the last backward."""
+
+    def __init__(self, n_points, raw_features, sd, weights, groups=None, max_iterations=None, n_iterations=5, criterion=_pkg.STOP_LABELS,
+                 tol=0.0, relax=1.0, device=0, n_labels=2, normalization=None, fused_backward=False):
+        super().__init__()
+        if not (len(raw_features) == len(sd) == len(weights)):
+            raise ValueError("one list of standard deviations and one weight per feature array")
+        dev = torch.device("cuda", device)
+        self.raw = [torch.as_tensor(_host_f32(f), device=dev) for f in raw_features]
+        self.n_points = np.ascontiguousarray(n_points, np.int32)
+        if any(f.dim() != 3 or int(f.shape[0]) != self.n_points.size for f in self.raw):
+            raise ValueError("every feature array must be of shape [%d, max_points, d_k]" % self.n_points.size)
+        groups = groups if groups is not None else [None] * len(self.raw)
+        self.log_sd = torch.nn.ParameterList()
+        self._col = []                                        # per term: group of every column
+        for f, s, g in zip(self.raw, sd, groups):
+            log_sd, col = _bandwidth_parameter(int(f.shape[2]), s, g, dev)
+            self._col.append(col)
+            self.log_sd.append(log_sd)
+        self.weights = _weights_parameter(weights)
+        F = int(self.n_points.size)
+        N = int(self.raw[0].shape[1]) if self.raw else int(self.n_points.max(initial=0))
+        self.batch = _pkg.BatchCRF(F, N, n_labels, [int(f.shape[2]) for f in self.raw], [float(w) for w in weights], device=device)
+        for k, mode in enumerate(_modes(normalization, len(self.raw))):      # (include/lccrf.h section 2g)
+            self.batch.set_normalization(k, mode)
+        if fused_backward:
+            self.batch.set_option(_pkg.OPT_FUSED_BACKWARD_FEATURES, 1)
+        self.max_iterations = None if max_iterations is None else int(max_iterations)
+        self.n_iterations, self.relax = int(n_iterations), float(relax)
+        self.criterion, self.tol = int(criterion), float(tol)
+
+    def features(self):
+        """the features the CRF sees: raw / sd, column by column, [F, max_points, d_k]"""
+        return [f * torch.exp(-ls)[col] for f, ls, col in zip(self.raw, self.log_sd, self._col)]
+
+    def sd(self):
+        return [torch.exp(ls.detach()).cpu().numpy() for ls in self.log_sd]
+
+    def forward(self, unary):
+        if self.max_iterations is None:
+            return mean_field_batch_features(self.batch, self.n_points, unary, self.features(), self.weights, self.n_iterations, self.relax)
+        return mean_field_batch_features_converged(self.batch, self.n_points, unary, self.features(), self.weights, self.max_iterations,
+                                                   self.criterion, self.tol, self.relax)
+
+    def close(self):
+        self.batch.close()

@@ -1,4 +1,4 @@
-// api_backward.hip -- gradients of mean-field inference: sections 1c - 1f, 1m (a handle) and 2c, 2d, 2h - 2k (a batch) of include/lccrf.h.
+// api_backward.hip -- gradients of mean-field inference: sections 1c - 1f, 1m (a handle) and 2c, 2d, 2h - 2l (a batch) of include/lccrf.h.
 //
 // One path behind every entry point (backward_call); the replay and the sweep themselves are Engine::backward (host_engine.hip) and
 // meanfield_backward.hip; the route getters of section 1j are in api_model.hip.
@@ -247,6 +247,33 @@ int lccrf_batch_inference_backward_modes(lccrf_batch_handle b, int n_iterations,
     rq.grad_compat = d_grad_compat;
     rq.grad_model = d_grad_model;
     rq.compat_form = b->eng.model.n_compat > 0 || d_grad_compat || d_grad_model;
+    return backward_call(backward_target(b, stream), rq, kGradUnaryOptional);
+}
+
+// --------------------------------------------------------------------------------------
+// section 2l: section 2i with section 2j's count per frame -- the gradients of lccrf_batch_inference_converged's result with respect to
+// the features too, under any model.  The request is section 2i's with `counts` set; without a feature array it IS section 2k's call.
+// What needs no handle is checked first.
+
+int lccrf_batch_inference_backward_modes_converged(lccrf_batch_handle b, int max_iterations, float relax, const int32_t *d_iterations,
+                                                   const float *d_grad_prob, float *d_grad_unary, float *d_grad_weights,
+                                                   float *const *d_grad_features, float *d_grad_compat, float *d_grad_model, void *stream)
+{
+    if (max_iterations < 0) return fail(LCCRF_E_INVALID, "max_iterations < 0");
+    if (!std::isfinite(relax)) return fail(LCCRF_E_INVALID, "relax must be finite");
+    if (!d_iterations) return fail(LCCRF_E_INVALID, "d_iterations is NULL");
+    CHECK_H(b);
+    bool no_features = true;
+    for (size_t k = 0; k < b->eng.kernels.size() && d_grad_features; ++k) no_features &= d_grad_features[k] == nullptr;
+    if (no_features)
+        return lccrf_batch_inference_backward_all_converged(b, max_iterations, relax, d_iterations, d_grad_prob, d_grad_unary,
+                                                            d_grad_weights, d_grad_compat, d_grad_model, stream);
+    BackwardRequest rq{max_iterations, relax, d_grad_prob, d_grad_unary, d_grad_weights};
+    rq.grad_features = d_grad_features;
+    rq.grad_compat = d_grad_compat;
+    rq.grad_model = d_grad_model;
+    rq.compat_form = b->eng.model.n_compat > 0 || d_grad_compat || d_grad_model;   // (as sections 2h and 2i set it)
+    rq.counts = d_iterations;
     return backward_call(backward_target(b, stream), rq, kGradUnaryOptional);
 }
 

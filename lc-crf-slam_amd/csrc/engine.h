@@ -362,8 +362,8 @@ struct BackwardRequest {           // (an aggregate: the members left out of a b
     bool compat_form;               // the sweep takes section 1e's form: the terms' matrices are honoured (grad_compat needs it)
     float *grad_model;              // [K + K*L*L] or null (section 2h): the sums over the frames of dL/dw and dL/dmu (needs compat_form)
     // [F] int32 on the device or null (section 2j): frame f is differentiated at t_f = min(max(counts[f], 0), T) iterations, T the cap
-    // every [T] part of the area is sized by; the kernels clamp, the host never reads the array.  Not with grad_features; with
-    // grad_compat / grad_model it is section 2k.
+    // every [T] part of the area is sized by; the kernels clamp, the host never reads the array.  With grad_compat /
+    // grad_model it is section 2k, with grad_features section 2l.
     const int *counts;
 };
 // The area of one backward call, owned by the engine and zeroed when allocated: Q_0 .. Q_{T-1} of the replay, one [F][.][L] array
@@ -426,7 +426,9 @@ size_t backward_layout(const BackwardRequest &rq, const CrfDev &c, const KernelD
 // caller's dL/dQ, nothing is added to its dL/dU, no partial is written for it; its filters run on (phi is scratch) -- its first step
 // is t == t_f, and the weight gradient's reduction walks its t_f x blocks partials: a handle's bits at t_f.  In the compat form
 // (section 2k) k_compat_bwd leaves an idle frame's cpart and phi alone and writes cpart at t == t_f, and k_compat_reduce gives a frame
-// with t_f = 0 exact zeros without reading its cpart, which no iteration of the call wrote.
+// with t_f = 0 exact zeros without reading its cpart, which no iteration of the call wrote.  In the feature part (section 2l) the sweep's
+// k_corner_dot launches and k_bwd_combine_adjoint leave an idle frame alone -- nothing is added to its ar.gb / ar.gn -- and the norm part
+// runs for every frame: at t_f = 0 on the caller's zeros, which it turns into +0 in every row of dL/df.
 struct BackwardModes {
     int mode[LCCRF_MAX_KERNELS];
     const float *norm[LCCRF_MAX_KERNELS];   // [F][maxN], KernelDev::norm of the engine's own views (not of step_kdevs())
@@ -454,7 +456,9 @@ int launch_fused_backward_general(const CrfDev &c, const KernelDev *kds, const i
 // ... and of a request WITH feature gradients (csrc/fused_backward_features.hip; include/lccrf.h section 1l): Potts terms normalised
 // AFTER, rq.T >= 1, no compat form, at least one array in rq.grad_features.  Writes what launch_fused_backward writes and
 // rq.grad_features (rows [n_points[f], rows) written 0), bit for bit what launch_backward_sweep would have; ar.gb / ar.gn need no zeroing
-// (the kernel's first iteration writes them).  Returns fused_report() of the shape launched, or 0 with nothing launched.
+// (the kernel's first iteration writes them).  With rq.counts (section 2l) every frame's workgroup runs its own t_f iterations, the
+// workgroups taking the frames by descending t_f (the order in ar.phi); a frame with t_f = 0 gets +0 in every row of dL/df.  Returns
+// fused_report() of the shape launched, or 0 with nothing launched.
 int launch_fused_backward_features(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, int rows,
                                    const BackwardRequest &rq, const BackwardArea &ar, hipStream_t s);
 // out[j] = sum over the frames, in ascending order, of x[f][j], j < n (section 2h; meanfield_backward.hip)

@@ -24,8 +24,16 @@
 // kernarg segment where they are used (late(), as k_backward_general does): kept from the kernel's entry they are live around the
 // whole sweep and the two-term instantiations have no scalar register left for them.
 //
+// With per-frame counts (include/lccrf.h section 2l) T above is the frame's own t_f = min(max(counts[f], 0), T), loaded once per
+// workgroup -- a uniform value, so every barrier stays uniform -- and workgroup i takes frame order[i], the frames sorted by descending
+// t_f on the device (k_order_by_count, meanfield_backward.hip), as k_backward and k_backward_general do: which workgroup runs a frame
+// changes no bit of it.  hist and partial keep their [T][..] layout.  A frame with t_f = 0 never initialises its g_b / g_n -- they may
+// hold an earlier call's values -- so it skips the norm part and writes +0 into all `rows` rows of every dL/df_k: the bits of the
+// handle's memset at T = 0.  The counts and the order are runtime arguments read once at the kernel's entry and dead behind it (t_f
+// takes a.T's scalar register): no instantiation more.
+//
 // Scope: Potts terms normalised AFTER, K in {1, 2} 2-D terms, frames of up to 2 x 1024 active points, kernel 0 with short rows or chain
-// rows: 8 instantiations.  T >= 1 (the caller streams T = 0: its memset to exactly 0 is already right).
+// rows: 8 instantiations.  T >= 1 (the caller streams T = 0: its memset to exactly 0 is already right); a frame's own t_f may be 0.
 #include <cstddef>
 
 #include "engine.h"
@@ -56,6 +64,8 @@ struct BackwardFeatureArgs {
     float *gF[kMaxFusedK];                // [F][maxN][2] dL/df_k, or null: term k does no feature work
     float *gb[kMaxFusedK];                // [F][Epad] dL/d(corner weight), laid out as KernelDev::bary (BackwardArea::gb)
     float *gn[kMaxFusedK];                // [F][maxNpad] the per-point sum behind the norm's gradient (BackwardArea::gn)
+    const int *counts;                    // [F] or null (section 2l): frame f runs min(max(counts[f], 0), T) iterations, T the layout's
+    const int *order;                     // [F] or null: workgroup i takes frame order[i] (a permutation: the longest counts first)
 };
 
 struct KernArgs { CrfDev c; BackwardFeatureArgs a; };   // two by-value parameters, each at its natural alignment
@@ -157,18 +167,20 @@ __global__ void __launch_bounds__(kNT, 4) k_backward_features(CrfDev c, Backward
 {
     constexpr int D1 = kD1, NT = kNT, ALL = (1 << K) - 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int f = blockIdx.x;
+    // (section 2l) the frame of this workgroup and its own iteration count: uniform values, one load each per workgroup
+    const int f = a.order ? a.order[blockIdx.x] : blockIdx.x;
     int tid = threadIdx.x;
     const int N = c.n_points[f];
+    const int T = a.counts ? min(max(a.counts[f], 0), a.T) : a.T;
     Instr ins{nullptr, 0, 0, 0, 0};
     const size_t fo = (size_t)f * c.maxN;                 // the frame's first row of every [F][maxN][2] array
     float2 *gU = reinterpret_cast<float2 *>(a.gU) + fo;
 
     for (int i = max(N, 0) + tid; i < a.rows; i += NT) gU[i] = make_float2(0.f, 0.f);   // rows beyond the frame's points: dL/dU = 0
 #pragma unroll
-    for (int k = 0; k < K; ++k)                            // ... and dL/df_k = 0 (k_corner_to_feature)
-        if (a.gF[k])
-            for (int i = max(N, 0) + tid; i < a.rows; i += NT)
+    for (int k = 0; k < K; ++k)                            // ... and dL/df_k = 0 (k_corner_to_feature); at t_f = 0 every row: nothing
+        if (a.gF[k])                                       //     depends on the features, and no norm part runs for the frame
+            for (int i = (T == 0 ? 0 : max(N, 0)) + tid; i < a.rows; i += NT)
                 a.gF[k][((size_t)f * a.kd[k].maxN + i) * 2] = a.gF[k][((size_t)f * a.kd[k].maxN + i) * 2 + 1] = 0.0f;
     if (N <= 0) {                         // nothing to differentiate (and nothing below may index an empty frame)
         if (a.gW && tid < K) a.gW[(size_t)f * K + tid] = 0.0f;
@@ -197,7 +209,7 @@ __global__ void __launch_bounds__(kNT, 4) k_backward_features(CrfDev c, Backward
     // ---- the replay: inference(T, 0, relax), keeping Q_0 .. Q_{T-1} -------------------------------------------------------------
     const size_t hs = a.slice / 2;        // float2 between the iterations of hist
     float2 *hist = reinterpret_cast<float2 *>(a.hist) + fo;
-    for (int t = 0; t < a.T; ++t) {
+    for (int t = 0; t < T; ++t) {
         opaque(pr);
 #pragma unroll
         for (int s = 0; s < PPT; ++s)
@@ -226,13 +238,13 @@ __global__ void __launch_bounds__(kNT, 4) k_backward_features(CrfDev c, Backward
     float *tree = red + kMaxFusedK * kBackwardMaxPPT * kWaves;            // [K][kPartialRows]
     // the frame's partials per iteration and term (N > 0; the clamp: the plan sized the launch for frames of at most PPT x 1024 points)
     const int nblk = min((N + kPartialRows - 1) / kPartialRows, PPT * 4);
-    const float2 *hq = hist + (size_t)a.T * hs;
-    for (int t = a.T; t >= 1; --t) {
+    const float2 *hq = hist + (size_t)T * hs;
+    for (int t = T; t >= 1; --t) {
         opaque(pr);
         // (the lane index and the chain lane's words are made opaque per iteration: what the phases derive from them -- the ring's four
         // clamps, the pads' address -- is formed where it is used and not kept in registers around the sweep)
         asm volatile("" : "+v"(tid), "+v"(cl.a), "+v"(cl.b));
-        const bool first = t == a.T;                                      // dL/dQ_t is the caller's; dL/dU, g_b and g_n are written
+        const bool first = t == T;                                        // dL/dQ_t is the caller's; dL/dU, g_b and g_n are written
         hq -= hs;                                                         // Q_{t-1}
         // Phi_k(Q_{t-1})
 #pragma unroll
@@ -349,7 +361,7 @@ __global__ void __launch_bounds__(kNT, 4) k_backward_features(CrfDev c, Backward
 
     // ---- dL/dU -= P_0 (G_0 - <G_0, P_0>), P_0 = Q_0 = softmax(-U) ---------------------------------------------------------------
     {
-        const bool first = a.T == 0;
+        const bool first = T == 0;
 #pragma unroll
         for (int s = 0; s < PPT; ++s) {
             const int i = tid + s * NT;
@@ -371,7 +383,7 @@ __global__ void __launch_bounds__(kNT, 4) k_backward_features(CrfDev c, Backward
     int fmask = 0;                        // the terms with a feature array (uniform)
 #pragma unroll
     for (int k = 0; k < K; ++k) fmask |= late()->gF[k] ? 1 << k : 0;
-    if (fmask && late()->T >= 1) {
+    if (fmask && T >= 1) {               // (a frame with t_f = 0 has no norm part: its gb / gn are not this launch's)
         opaque(pr);
         asm volatile("" : "+v"(tid));
         float2 xin[PPT][K];
@@ -446,7 +458,7 @@ __global__ void __launch_bounds__(kNT, 4) k_backward_features(CrfDev c, Backward
     if (k < K) {
         const int pterm = (int)gridDim.x * a.bstride, prow = f * a.bstride;
         const float *row = a.partial + (size_t)k * pterm + prow;             // this frame's partials of term k, iteration 1
-        const int n = a.T * nblk;
+        const int n = T * nblk;
         float acc = 0.0f;
         for (int idx = j; idx < n; idx += kPartialRows) {
             const int t = idx / nblk, b = idx - t * nblk;
@@ -466,7 +478,8 @@ __global__ void __launch_bounds__(kNT, 4) k_backward_features(CrfDev c, Backward
 
 // The one-launch backward of request rq WITH feature gradients on area ar (Potts terms normalised AFTER, rq.T >= 1, no compat form):
 // fused_report() of the shape launched, or 0 with nothing launched -- the frames are not ones the plan takes, and the caller runs the
-// streaming sweep.  ar.gb / ar.gn need no zeroing: the kernel's first iteration writes them.
+// streaming sweep.  ar.gb / ar.gn need no zeroing: the kernel's first iteration writes them.  With rq.counts (section 2l) every frame's
+// workgroup runs its own t_f iterations, the workgroups taking the frames by descending t_f (the order in ar.phi).
 int launch_fused_backward_features(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, int rows,
                                    const BackwardRequest &rq, const BackwardArea &ar, hipStream_t s)
 {
@@ -487,7 +500,14 @@ int launch_fused_backward_features(const CrfDev &c, const KernelDev *kds, const 
         a.gb[k] = ar.gb[k];
         a.gn[k] = ar.gn[k];
     }
+    a.counts = rq.counts;
     return plan_variant<kBackwardMaxPPT>(c, kds, maxV, maxRow, kBackwardLds, a, [&](auto p, auto kk, auto ch) {
+        // (section 2l) the longest frames first, as k_backward takes them (fused_backward.hip): the order lives in the area's `phi`, which
+        // this kernel does not touch (K * slice floats: room for F ints)
+        if (rq.counts && (size_t)c.K * ar.slice >= (size_t)c.F) {
+            launch_order_by_count(rq.counts, c.F, rq.T, reinterpret_cast<int *>(ar.phi), s);
+            a.order = reinterpret_cast<const int *>(ar.phi);
+        }
         launch_workgroups(k_backward_features<decltype(p)::value, decltype(kk)::value, decltype(ch)::value>, c.F, kNT,
                           a.lay.total + kBackwardLds, s, c, a);
     });

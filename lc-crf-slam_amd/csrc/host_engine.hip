@@ -60,7 +60,7 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
     // LCCRF_OPT_FUSED_BACKWARD (include/lccrf.h section 1j): dL/dU and / or dL/dw of Potts terms normalised AFTER, on frames the fused
     // plan takes -- the replay and the sweep in one launch, the same bits (fused_backward.hip).  Decided for the whole batch, over its
     // largest frame and lattices; behind every check and the area, so a rejected call leaves the handle as it was either way.
-    // With rq.counts (section 2j) too: each frame's workgroup then runs its own t_f iterations; the feature kernel takes none.
+    // With rq.counts (section 2j) too: each frame's workgroup then runs its own t_f iterations.
     const bool plain_form = !rq.compat_form && !rq.grad_compat && !rq.grad_model;   // (not the compat form: no dL/dmu, no sums, no matrix)
     bool no_features = true;
     for (int k = 0; k < K && rq.grad_features; ++k) no_features &= rq.grad_features[k] == nullptr;
@@ -88,7 +88,8 @@ int Engine::backward(const BackwardRequest &rq, size_t slice, int rows)
     // LCCRF_OPT_FUSED_BACKWARD_FEATURES (section 1l): a request with at least one feature array, not in the compat form, on Potts terms
     // normalised AFTER and T >= 1 (T = 0 streams: the memset below to exactly 0 is already right) -- decided in the same place and the
     // same way (fused_backward_features.hip).  The kernel initialises the area's gb / gn itself: no memset in front of it.
-    if (opt.fused_backward_features && !rq.counts && !no_features && plain_form && count && T >= 1 && !model.general() && !perm_on &&
+    // With rq.counts (section 2l) too: each frame's workgroup runs its own t_f iterations, and one with t_f = 0 writes its dL/df as +0.
+    if (opt.fused_backward_features && !no_features && plain_form && count && T >= 1 && !model.general() && !perm_on &&
         launch_fused_backward_features(crf, kdevs.data(), maxV.data(), maxRow.data(), rows, rq, ar, stream)) {
         HIP_TRY(hipGetLastError());
         report.backward(LCCRF_BACKWARD_FUSED);

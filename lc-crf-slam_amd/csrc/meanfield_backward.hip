@@ -331,13 +331,16 @@ __global__ void __launch_bounds__(kBwdBlock) k_bwd_combine(const int *__restrict
 // scaled by b_k, for every term with an accumulator (adj.gn[k]: a BEFORE or SYMMETRIC term whose feature gradient is asked for)
 //   gn[k][i] += w_k * <Q_{t-1},i, z_k,i>        labels in order 0 .. L-1, one owner per point (the row's first lane)
 // -- dL/d b_k[i] of x = b_k . Q_{t-1}.  It runs behind this iteration's k_softmax_bwd, so the post part is added before the pre part.
+// cn (section 2l) as k_bwd_combine takes it: an idle frame's workgroups leave before the row sums' shuffles, on blockIdx.y alone -- nothing
+// is added to its gn (buf is scratch for it: no softmax kernel wrote this iteration's filter input) and its G stays the caller's dL/dQ.
 struct BwdPreAdjoint { float *gn[kBwdMaxK]; int gnstride; const float *q; };   // q: Q_{t-1}, [F][.][L] strided as G
 template <int G>
 __global__ void __launch_bounds__(kBwdBlock) k_bwd_combine_adjoint(const int *__restrict__ n_points, int L, int K, const float *__restrict__ buf,
                                                                  size_t slice, size_t fs, BwdWeights wk, float keep, float *__restrict__ Gd,
-                                                                 BwdPre pre, BwdPreAdjoint adj)
+                                                                 BwdPre pre, BwdPreAdjoint adj, BwdCounts cn)
 {
     const int f = blockIdx.y;
+    if (cn.counts && cn.t > frame_count(cn.counts, f, cn.cap)) return;   // (uniform over the workgroup)
     const int lane = threadIdx.x & 63;
     const int sub = lane % G, first = lane - sub;
     const int i = blockIdx.x * (kBwdBlock / G) + (int)threadIdx.x / G;
@@ -628,6 +631,9 @@ namespace {
 // dot products, each summed over the labels in order 0 .. L-1.  row == null: all ones (the norm part, L = 1).
 // fac != null (section 1m): the row is fac[f][i] * row_i, every product rounded once -- the splat side's input row b_k . Q_{t-1} of a
 // term with a factor in front of its filter, exactly the row the forward's splat formed.  Without it (a uniform branch) the bits it gave.
+// counts != null (section 2l; the sweep's launches only, the norm part passes none): a frame is idle while t > t_f -- its workgroups
+// leave on blockIdx.y alone, before the row sums' shuffles, with nothing added to gb.  For such a frame phi_k is scratch (k_softmax_bwd
+// returned without writing the transposed filter's input): the slice side's row and the splat side's values would both be garbage.
 struct CornerArgs {
     const int *n_points;
     int L;
@@ -638,12 +644,15 @@ struct CornerArgs {
     float *gb;                   // [F][Epad]
     const float *fac;            // [F][nstride] or null
     int nstride;
+    const int *counts;           // [F] or null (section 2l): the frame's own iteration count, clamped to [0, cap] by frame_count
+    int t, cap;                  // ... the sweep's iteration of this launch and the counts' cap
 };
 
 template <int G>
 __global__ void __launch_bounds__(kBwdBlock) k_corner_dot(KernelDev kd, CornerArgs a)
 {
     const int f = blockIdx.y;
+    if (a.counts && a.t > frame_count(a.counts, f, a.cap)) return;   // an idle frame (uniform over the workgroup)
     const int N = a.n_points[f], L = a.L, D1 = kd.D1;
     const int lane = threadIdx.x & 63;
     const int sub = lane % G, first = lane - sub;
@@ -687,9 +696,9 @@ __global__ void __launch_bounds__(kBwdBlock) k_corner_dot(KernelDev kd, CornerAr
 }
 
 void launch_corner_dot(const KernelDev &kd, const CrfDev &c, int rows, int L, const float *row, size_t fs, const float *val, float scale,
-                       float *gb, hipStream_t s, const float *fac = nullptr)
+                       float *gb, hipStream_t s, const float *fac = nullptr, BwdCounts cn = BwdCounts{nullptr, 0, 0})
 {
-    CornerArgs a{c.n_points, L, fs, row, val, scale, gb, fac, c.maxN};
+    CornerArgs a{c.n_points, L, fs, row, val, scale, gb, fac, c.maxN, cn.counts, cn.t, cn.cap};
     const dim3 grid((unsigned)std::max(backward_blocks(rows, L), 1), (unsigned)c.F);
     with_bwd_lanes(L, [&](auto lanes) { k_corner_dot<decltype(lanes)::value><<<grid, kBwdBlock, 0, s>>>(kd, a); });
 }
@@ -873,6 +882,7 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
         a.first = t == T;
         a.t = t;
         a.partial = K ? ar.partial + (size_t)(t - 1) * K * F * nblk : nullptr;
+        const BwdCounts cn{rq.counts, t, T};               // (sections 2j - 2l; counts null: every frame takes every launch)
         // (first uses in the order compat, plain, feature, both: the order of the kernels' instantiation, and so of the code object)
         if (cmode && !feat) launch_softmax_bwd<kBwdCompat>(a, F, s);
         else if (!feat) launch_softmax_bwd<kBwdPlain>(a, F, s);
@@ -886,22 +896,20 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
             }
             // (section 1f: the slice side's upstream row is what k_compat_bwd has just left in phi_k, n_k (mu_k^T gamma_t))
             const float cs = kds[k].alpha * kds[k].w;
-            if (gf[k]) launch_corner_dot(kds[k], c, rows, L, ar.phi + k * slice, fs, val[k], cs, ar.gb[k], s);    // slice side
+            if (gf[k]) launch_corner_dot(kds[k], c, rows, L, ar.phi + k * slice, fs, val[k], cs, ar.gb[k], s, nullptr, cn);   // slice side
             const float *valt;                             // (B^T S n_k gamma_t)
             launch_filter(kds[k], c, maxV[k], ar.phi + k * slice, ar.phi + k * slice, 0, s, 1, &valt);
-            if (gf[k]) launch_corner_dot(kds[k], c, rows, L, qprev, fs, valt, cs, ar.gb[k], s, bp.p[k]);          // splat side
+            if (gf[k]) launch_corner_dot(kds[k], c, rows, L, qprev, fs, valt, cs, ar.gb[k], s, bp.p[k], cn);      // splat side
         }
         if (padj) {
             pa.q = qprev;
             const dim3 rgrid((unsigned)nblk, (unsigned)F);
             with_bwd_lanes(L, [&](auto lanes) {
                 k_bwd_combine_adjoint<decltype(lanes)::value><<<rgrid, kBwdBlock, 0, s>>>(c.n_points, L, K, ar.phi, slice, fs, wk, 1.0f - relax,
-                                                                                       ar.G, bp, pa);
+                                                                                       ar.G, bp, pa, cn);
             });
-        } else if (pre) k_bwd_combine<true><<<cgrid, kBwdBlock, 0, s>>>(c.n_points, L, K, ar.phi, slice, fs, wk, 1.0f - relax, ar.G, bp,
-                                                                        BwdCounts{rq.counts, t, T});
-        else k_bwd_combine<false><<<cgrid, kBwdBlock, 0, s>>>(c.n_points, L, K, ar.phi, slice, fs, wk, 1.0f - relax, ar.G, bp,
-                                                              BwdCounts{rq.counts, t, T});
+        } else if (pre) k_bwd_combine<true><<<cgrid, kBwdBlock, 0, s>>>(c.n_points, L, K, ar.phi, slice, fs, wk, 1.0f - relax, ar.G, bp, cn);
+        else k_bwd_combine<false><<<cgrid, kBwdBlock, 0, s>>>(c.n_points, L, K, ar.phi, slice, fs, wk, 1.0f - relax, ar.G, bp, cn);
     }
     // dL/dU -= P_0 (G_0 - <G_0, P_0>), P_0 = Q_0 = softmax(-U)
     a.K = 0;
@@ -915,6 +923,11 @@ void launch_backward_sweep(const CrfDev &c, const KernelDev *kds, const int *max
                                                                                                             L * L, grad_compat, rq.counts, T);
     // the norm part, <a_k, Phi_k(1)> with a_k = -n_k^2 g_n[k] (value width 1), and dL/db -> dL/df
     // (section 1m: g_n from the adjoints by the term's mode, n_k the true norm; a term without a norm factor has no norm part)
+    // (section 2l: these launches take no counts.  A frame with t_f = 0 under a cap >= 1 runs through them on the caller's memset:
+    // a_i = -(n * n) * +0 = -0 (times a finite, positive 0.5f / s under SYMMETRIC); the first corner dot forms 0.0f + (-0 * x) = +0 and
+    // adds alpha * +0 to +0; the transposed filter of a field of -0 leaves +-0 in every vertex, whose corner dot is 0.0f + 1.0f * (+-0) =
+    // +0 again; so every gb is +0, every gel (+0 - +0) * inv_dp1 = +0 and every dL/df (+0 - (m + 1) * +0) * scale_m = +0, scale_m > 0:
+    // the bits of the handle's memset at T = 0, with no branch.)
     for (int k = 0; k < K; ++k) {
         if (!gf[k]) continue;
         const KernelDev &kd = kds[k];
