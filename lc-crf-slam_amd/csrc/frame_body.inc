@@ -317,8 +317,8 @@
                     h = (h + 1u) & mask;
                     o = hk[h];
                 }
-                if (o == q) {
-                    const unsigned b = ido[h];
+                if (o == q && q != kEmptyKey) {             // (the reserved key is no vertex of a frame that got here: a query for it ends at an
+                    const unsigned b = ido[h];              //  EMPTY slot, whose ido is not a vertex id -- absent, as the reference finds it)
                     nb16[2 * t + 1] = (unsigned short)(b + 1u);                       // my n2
                     nb16[2 * (j * Vk + (int)b)] = (unsigned short)(v + 1);          // its n1
                 }

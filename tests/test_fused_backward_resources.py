@@ -331,35 +331,37 @@ PARENT = {
         "_ZN5lccrf12_GLOBAL__N_118k_general_convergeILi2ELi2ELi1EEEvNS_6CrfDevENS0_19GeneralConvergeArgsE":
             (128, 0, 0, 0, 0, 0),
     },
+    # (the scalar spill counts of k_frame as of the reserved-key fix in frame_body.inc, notes/hash_build_tests.md: nine of them moved
+    #  by 1 to 8; vector registers, scratch, vector spills and LDS are the earlier ones)
     "frame_engine.hip": {
         "_ZN5lccrf12_GLOBAL__N_17k_frameILi1024ELi1ELi1ELb0EEEvNS_6CrfDevENS_2fb9FrameArgsE":
             (128, 0, 0, 0, 0, 0),
         "_ZN5lccrf12_GLOBAL__N_17k_frameILi1024ELi1ELi2ELb0EEEvNS_6CrfDevENS_2fb9FrameArgsE":
-            (128, 0, 0, 0, 34, 0),
+            (128, 0, 0, 0, 35, 0),
         "_ZN5lccrf12_GLOBAL__N_17k_frameILi1024ELi1ELi2ELb1EEEvNS_6CrfDevENS_2fb9FrameArgsE":
-            (128, 0, 0, 0, 25, 0),
+            (128, 0, 0, 0, 27, 0),
         "_ZN5lccrf12_GLOBAL__N_17k_frameILi1024ELi2ELi1ELb0EEEvNS_6CrfDevENS_2fb9FrameArgsE":
             (128, 0, 0, 0, 0, 0),
         "_ZN5lccrf12_GLOBAL__N_17k_frameILi1024ELi2ELi2ELb0EEEvNS_6CrfDevENS_2fb9FrameArgsE":
             (128, 0, 0, 0, 30, 0),
         "_ZN5lccrf12_GLOBAL__N_17k_frameILi1024ELi2ELi2ELb1EEEvNS_6CrfDevENS_2fb9FrameArgsE":
-            (128, 0, 28, 6, 21, 0),
+            (128, 0, 28, 6, 19, 0),
         "_ZN5lccrf12_GLOBAL__N_17k_frameILi1024ELi3ELi1ELb0EEEvNS_6CrfDevENS_2fb9FrameArgsE":
-            (128, 0, 0, 0, 0, 0),
+            (128, 0, 0, 0, 2, 0),
         "_ZN5lccrf12_GLOBAL__N_17k_frameILi1024ELi3ELi2ELb0EEEvNS_6CrfDevENS_2fb9FrameArgsE":
-            (128, 0, 0, 0, 46, 0),
+            (128, 0, 0, 0, 53, 0),
         "_ZN5lccrf12_GLOBAL__N_17k_frameILi1024ELi3ELi2ELb1EEEvNS_6CrfDevENS_2fb9FrameArgsE":
-            (128, 0, 32, 7, 32, 0),
+            (128, 0, 32, 7, 28, 0),
         "_ZN5lccrf12_GLOBAL__N_17k_frameILi1024ELi4ELi1ELb0EEEvNS_6CrfDevENS_2fb9FrameArgsE":
             (128, 0, 0, 0, 8, 0),
         "_ZN5lccrf12_GLOBAL__N_17k_frameILi1024ELi4ELi2ELb0EEEvNS_6CrfDevENS_2fb9FrameArgsE":
-            (128, 0, 112, 50, 65, 0),
+            (128, 0, 112, 50, 63, 0),
         "_ZN5lccrf12_GLOBAL__N_17k_frameILi1024ELi4ELi2ELb1EEEvNS_6CrfDevENS_2fb9FrameArgsE":
-            (128, 0, 120, 64, 37, 0),
+            (128, 0, 120, 64, 45, 0),
         "_ZN5lccrf12_GLOBAL__N_17k_frameILi512ELi1ELi1ELb0EEEvNS_6CrfDevENS_2fb9FrameArgsE":
             (128, 0, 0, 0, 0, 0),
         "_ZN5lccrf12_GLOBAL__N_17k_frameILi512ELi1ELi2ELb0EEEvNS_6CrfDevENS_2fb9FrameArgsE":
-            (128, 0, 0, 0, 34, 0),
+            (128, 0, 0, 0, 35, 0),
         "_ZN5lccrf12_GLOBAL__N_17k_frameILi512ELi2ELi1ELb0EEEvNS_6CrfDevENS_2fb9FrameArgsE":
             (128, 0, 0, 0, 0, 0),
         "_ZN5lccrf12_GLOBAL__N_17k_frameILi512ELi2ELi2ELb0EEEvNS_6CrfDevENS_2fb9FrameArgsE":
