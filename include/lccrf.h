@@ -115,10 +115,21 @@ int  lccrf_trim_cache(void);
  *       two-label frames of up to 2048 points with one or two 2-D terms in ONE kernel launch (section 1l;
  *       csrc/fused_backward_features.hip).  Bit for bit the results of the option off.  A request without a feature array is never
  *       this option's: options 6 and 7 select exactly what they selected.
+ *   LCCRF_OPT_FUSED_MULTILABEL   (default 0) value != 0: a fixed count of iterations on lattices in HBM -- lccrf_inference on a handle
+ *       whose lattices are built, lccrf_batch_inference, and lccrf_batch_run where it builds into HBM -- of frames with THREE TO EIGHT
+ *       labels runs in ONE kernel launch, one 1024-lane workgroup per frame (csrc/fused_multilabel.hip; notes/fused_multilabel.md),
+ *       instead of the streaming engine's launch per phase: one or two 2-D Potts terms normalised AFTER (no matrix, no mode), 3 or 4
+ *       labels on frames of up to 2048 points, 5 to 8 labels on frames of up to 1024 (the largest n_points the host knows, else the
+ *       capacity), lattices that fit the fused engine's plan, no locality mode.  A batch decides once, over its largest frame and
+ *       lattices.  Q and the labels are bit for bit those of the option off; lccrf_get_engine / lccrf_batch_get_engine report 5 with
+ *       engine 2's shape word, lccrf_batch_get_fused_shape 1024 and the points per lane (1 or 2), and lccrf_batch_set_engine(b, 2) is
+ *       honoured for such a batch.  Everything else -- the converged calls, the gradients (whose replay streams), the stepwise calls,
+ *       two labels, nine and more, matrices, modes, a 3-D term, larger frames -- takes exactly the route it takes with the option
+ *       off.  Label bits exist for two labels only.  Takes effect with the next inference.
  * lccrf_set_option applies to one handle (set it after lccrf_create: a handle taken from the cache starts from the defaults) and is
  * per handle (or batch) only for LCCRF_OPT_VERTEX_ORDER, LCCRF_OPT_COPY_THREADS, LCCRF_OPT_EVENT_TIMING, LCCRF_OPT_FUSED_BACKWARD,
  * LCCRF_OPT_FUSED_BACKWARD_LEARNT and LCCRF_OPT_FUSED_BACKWARD_FEATURES;
- * lccrf_set_default_option applies LCCRF_OPT_SINGLE_WORKGROUP or LCCRF_OPT_FRAME_GENERAL to every handle and batch created afterwards
+ * lccrf_set_default_option applies LCCRF_OPT_SINGLE_WORKGROUP, LCCRF_OPT_FRAME_GENERAL or LCCRF_OPT_FUSED_MULTILABEL to every handle and batch created afterwards
  * in this process.                                                                                                             */
 typedef enum lccrf_option {
     LCCRF_OPT_SINGLE_WORKGROUP = 1,
@@ -128,7 +139,8 @@ typedef enum lccrf_option {
     LCCRF_OPT_FRAME_GENERAL    = 5,
     LCCRF_OPT_FUSED_BACKWARD  = 6,
     LCCRF_OPT_FUSED_BACKWARD_LEARNT = 7,
-    LCCRF_OPT_FUSED_BACKWARD_FEATURES = 8
+    LCCRF_OPT_FUSED_BACKWARD_FEATURES = 8,
+    LCCRF_OPT_FUSED_MULTILABEL = 9
 } lccrf_option;
 int  lccrf_set_option(lccrf_handle h, int option, int value);
 int  lccrf_set_default_option(int option, int value);
@@ -181,10 +193,11 @@ int  lccrf_get_probability(lccrf_handle h, float *prob_out);
  * Added WITHOUT a step of LCCRF_ABI_VERSION (it stays 3): probe for it by symbol.
  *   *engine   1 the streaming engine (one launch per phase); 2 the fused engine (lattices in HBM, inference in one launch);
  *             3 one launch per frame (lattice build + inference); 4 the fused engine's kernel for terms with a label-compatibility
- *             matrix (section 1e) or a normalisation mode other than AFTER (section 1g).  For 3 it is the value after a late-bound
+ *             matrix (section 1e) or a normalisation mode other than AFTER (section 1g); 5 its kernel for frames of three to eight
+ *             labels (LCCRF_OPT_FUSED_MULTILABEL).  For 3 it is the value after a late-bound
  *             run has settled: a frame that did not fit the one-launch kernel's plan reports what it was re-run on.  A handle
  *             that has not run lccrf_inference reports 1.
- *   *shape    (may be NULL) for engines 2 and 4: lanes per workgroup in bits 0-15, points per lane in bits 16-19, and 1 in bit 20
+ *   *shape    (may be NULL) for engines 2, 4 and 5: lanes per workgroup in bits 0-15, points per lane in bits 16-19, and 1 in bit 20
  *             when the first term's splat rows took the chain path; otherwise 0.
  * Report only: nothing depends on the value, and the call does no device work beyond settling a pending one-launch run.
  * LCCRF_E_INVALID for a NULL handle or a NULL `engine`.                                                                          */
@@ -814,13 +827,16 @@ int  lccrf_batch_device_label_bits(lccrf_batch_handle b, const uint64_t **d_bits
  *   per-frame kernel with the lattice values in LDS (SLAM sizes only).  lccrf_batch_get_engine
  *   also reports 3 = the one-launch-per-frame kernel of lccrf_batch_run, and 4 = the fused
  *   engine's kernels for terms with a label-compatibility matrix or a normalisation mode
- *   (section 2g: one 1024-lane workgroup per frame, fixed count or until converged).     */
+ *   (section 2g: one 1024-lane workgroup per frame, fixed count or until converged), and
+ *   5 = its kernel for frames of three to eight labels (LCCRF_OPT_FUSED_MULTILABEL), which
+ *   engine 2 ("fused or fail") accepts for such a batch when the option is on and the plan fits. */
 int  lccrf_batch_set_engine(lccrf_batch_handle b, int engine);
 int  lccrf_batch_get_engine(lccrf_batch_handle b, int *engine_in_use);
 /* Report only: the workgroup shape of the last one-workgroup-per-frame launch -- lccrf_batch_inference on the fused engine (engine 2),
  * lccrf_batch_run's one-launch kernel (engine 3) or section 2g's kernels (engine 4: always 1024 and 1), whichever ran last -- as
  * lanes per frame (1024 or 512) and how many frames share a CU (1; 2 for the half-LDS plans: batches of at least 256 frames of up to
- * 2048 points, csrc/fused_lean.h and csrc/frame_lean.hip).  0 / 0 if no such launch happened yet.  Same results in every shape (the order of every row sum is the
+ * 2048 points, csrc/fused_lean.h and csrc/frame_lean.hip).  LCCRF_OPT_FUSED_MULTILABEL's kernel (engine 5) reports 1024 and, in the second
+ * value, its POINTS PER LANE (1 or 2; a frame per CU always).  0 / 0 if no such launch happened yet.  Same results in every shape (the order of every row sum is the
  * reference's, permutohedral_cpu.h:653-661).                                                                                   */
 int  lccrf_batch_get_fused_shape(lccrf_batch_handle b, int *lanes_per_frame, int *frames_per_cu);
 /* Report only: how the lattices now in HBM were built (after lccrf_batch_build) -- whether the points of a frame are processed in

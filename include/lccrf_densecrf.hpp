@@ -441,6 +441,7 @@ public:
     // lccrf_set_option (include/lccrf.h), e.g. setOption(LCCRF_OPT_SINGLE_WORKGROUP, 1) for a tracker on a shared GPU.
     // setOption(LCCRF_OPT_FRAME_GENERAL, 1): a learnt model (setCompatibility / setNormalization) keeps the one-launch route of a fresh frame.
     // setOption(LCCRF_OPT_FUSED_BACKWARD_LEARNT, 1): the gradients of such a model, dL/dmu included, run in one launch (section 1k).
+    // setOption(LCCRF_OPT_FUSED_MULTILABEL, 1): inference() of a frame of three to eight labels the fused plan takes runs in one launch (engine() reports 5).
     void setOption(int option, int value) { lccrf_check(lccrf_set_option(h_, option, value), "lccrf_set_option"); }
     // lccrf_get_backward_route (include/lccrf.h section 1j): the route of the last successful backward call on this handle -- 0 none yet,
     // 1 the streaming sweep, 2 one launch (setOption(LCCRF_OPT_FUSED_BACKWARD, 1) / (LCCRF_OPT_FUSED_BACKWARD_LEARNT, 1)).  Report only.

@@ -29,6 +29,7 @@ OPT_FRAME_GENERAL = 5           # a learnt model (matrices, normalisation modes)
 OPT_FUSED_BACKWARD = 6          # gradients of tracker-sized two-label frames in one launch (include/lccrf.h section 1j)
 OPT_FUSED_BACKWARD_LEARNT = 7   # ... of learnt models (matrices, normalisation modes) and dL/dmu (include/lccrf.h section 1k)
 OPT_FUSED_BACKWARD_FEATURES = 8 # ... with feature gradients on Potts terms normalised AFTER (include/lccrf.h section 1l)
+OPT_FUSED_MULTILABEL = 9        # frames of three to eight labels on lattices in HBM infer in one launch (csrc/fused_multilabel.hip)
 BACKWARD_NONE, BACKWARD_STREAM, BACKWARD_FUSED = 0, 1, 2   # lccrf_backward_route
 IMAGE_NONE, IMAGE_U8, IMAGE_F32 = 0, 1, 2   # lccrf_add_image_kernel's image formats
 NORMALIZE_AFTER, NORMALIZE_BEFORE, NORMALIZE_SYMMETRIC, NORMALIZE_NONE = 0, 1, 2, 3   # lccrf_normalization (section 1g)
@@ -545,7 +546,8 @@ class DenseCRFHIP(_Handle):
 
     def engine(self):
         """(engine, shape) of the last inference(): 1 streaming, 2 fused, 3 one launch per frame, 4 the fused engine's kernel for
-        terms with a matrix or a normalisation mode; shape (engines 2 and 4, else 0): lanes per workgroup | points per lane << 16 |
+        terms with a matrix or a normalisation mode, 5 its kernel for three to eight labels (OPT_FUSED_MULTILABEL); shape (engines 2, 4
+        and 5, else 0): lanes per workgroup | points per lane << 16 |
         first term on chain rows << 20.  Report only (include/lccrf.h: lccrf_get_engine)."""
         e, s = C.c_int(0), C.c_int(0)
         _check(lib().lccrf_get_engine(self.h, C.byref(e), C.byref(s)))
@@ -628,6 +630,7 @@ class BatchCRF(_Handle):
     OPT_FUSED_BACKWARD = 6
     OPT_FUSED_BACKWARD_LEARNT = 7
     OPT_FUSED_BACKWARD_FEATURES = 8
+    OPT_FUSED_MULTILABEL = 9
 
     def set_inputs_host_async(self, n_points, features, unary=None, label=None, conf=None, pinned=False):
         """lccrf_batch_set_inputs_host_async: the arrays are staged and uploaded without a host wait.  The arrays must already be

@@ -239,6 +239,18 @@ def mean_field_converged(crf, unary, weights, max_iterations, criterion=_pkg.STO
     return _MeanField.apply(crf, unary, weights, None, max_iterations, relax, (criterion, tol))
 
 
+def _option_attribute(owner):
+    """the layers' fused_multilabel: a bool attribute whose assignment puts OPT_FUSED_MULTILABEL on the handle or batch the layer owns
+    (`owner`: the attribute holding it); takes effect with the next forward"""
+    def get(self):
+        return self.__dict__.get("_fused_multilabel", False)
+
+    def put(self, value):
+        getattr(self, owner).set_option(_pkg.OPT_FUSED_MULTILABEL, 1 if value else 0)
+        self.__dict__["_fused_multilabel"] = bool(value)
+    return property(get, put)
+
+
 class _HandleCRF(torch.nn.Module):
     """what MeanFieldCRF and CompatMeanFieldCRF share: a DenseCRFHIP handle over fixed features, the term weights an nn.Parameter"""
 
@@ -264,7 +276,10 @@ class MeanFieldCRF(_HandleCRF):
     features: list of [N, d_k] arrays (already divided by the kernel's standard deviation, as lccrf_add_pairwise takes
     them); weights: their initial weights; normalization: None (the reference's form), or one of the package's NORMALIZE_* modes
     for every term, or one per term (include/lccrf.h section 1g); fused_backward: sets OPT_FUSED_BACKWARD on the handle -- the
-    gradients of a frame the one-launch backward takes are then formed in one launch, the same bits (section 1j).
+    gradients of a frame the one-launch backward takes are then formed in one launch, the same bits (section 1j);
+    the attribute fused_multilabel (False; the constructor's parameter list is kept as it was): set to True, it puts
+    OPT_FUSED_MULTILABEL on the handle -- the forward of a frame of three to eight labels the fused plan takes then runs in one
+    launch, the same bits; the backward is unchanged.
     forward(unary [N, L]) -> Q [N, L]."""
 
     def __init__(self, n_points, n_labels, features, weights, n_iterations=5, relax=1.0, device=0, normalization=None,
@@ -272,6 +287,8 @@ class MeanFieldCRF(_HandleCRF):
         super().__init__(n_points, n_labels, features, weights, n_iterations, relax, device, normalization)
         if fused_backward:
             self.crf.set_option(_pkg.OPT_FUSED_BACKWARD, 1)
+
+    fused_multilabel = _option_attribute("crf")
 
     def forward(self, unary):
         return mean_field(self.crf, unary, self.weights, self.n_iterations, self.relax)
@@ -521,12 +538,17 @@ class BatchMeanFieldCRF(_BatchCRF):
 
     n_points: [F] points per frame; features: list of [F, max_points, d_k] arrays (already divided by the kernel's standard
     deviation); weights: their initial weights; fused_backward: sets OPT_FUSED_BACKWARD on the batch (include/lccrf.h section 1j: the
-    same gradients, in one launch where the frames fit).  forward(unary [F, max_points, L]) -> Q [F, max_points, L]."""
+    same gradients, in one launch where the frames fit); the attribute fused_multilabel (False; the constructor's parameter list is
+    kept as it was): set to True, it puts OPT_FUSED_MULTILABEL on the batch (the forward of frames of three to eight labels in one
+    launch where the plan fits, the same bits; the backward is unchanged).
+    forward(unary [F, max_points, L]) -> Q [F, max_points, L]."""
 
     def __init__(self, n_points, features, weights, n_iterations=5, relax=1.0, device=0, n_labels=2, fused_backward=False):
         super().__init__(n_points, features, weights, n_iterations, relax, device, n_labels)
         if fused_backward:
             self.batch.set_option(_pkg.OPT_FUSED_BACKWARD, 1)
+
+    fused_multilabel = _option_attribute("batch")
 
     def forward(self, unary):
         return mean_field_batch(self.batch, unary, self.weights, self.n_iterations, self.relax)

@@ -38,6 +38,10 @@ int lccrf::apply_option(Engine &e, int option, int value)
     case LCCRF_OPT_FUSED_BACKWARD: e.opt.fused_backward = value != 0; return LCCRF_OK;  // (takes effect with the next backward call)
     case LCCRF_OPT_FUSED_BACKWARD_LEARNT: e.opt.fused_backward_learnt = value != 0; return LCCRF_OK;   // (the next backward call)
     case LCCRF_OPT_FUSED_BACKWARD_FEATURES: e.opt.fused_backward_features = value != 0; return LCCRF_OK;   // (the next backward call)
+    case LCCRF_OPT_FUSED_MULTILABEL:                                                     // (takes effect with the next inference)
+        e.opt.fused_multilabel = value != 0;
+        e.choose_sized_engine();
+        return LCCRF_OK;
     case LCCRF_OPT_VERTEX_ORDER:                                                         // (takes effect with the next build)
         if (value < 0 || value > 2) return fail(LCCRF_E_INVALID, "LCCRF_OPT_VERTEX_ORDER takes 0 (automatic), 1 (on) or 2 (off)");
         e.opt.vertex_order = value;
@@ -351,7 +355,7 @@ int lccrf_get_engine(lccrf_handle h, int *engine, int *shape)
     }
     const Engine::RunReport &r = h->eng.report;
     *engine = r.engine;
-    if (shape) *shape = (r.engine == 2 || r.engine == 4) ? r.shape : 0;
+    if (shape) *shape = (r.engine == 2 || r.engine == 4 || r.engine == 5) ? r.shape : 0;
     return LCCRF_OK;
 }
 

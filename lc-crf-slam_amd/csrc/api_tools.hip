@@ -30,6 +30,7 @@ PoseStage g_pose_stage[kMaxDevices];
 
 std::atomic<int> g_default_single_wg{0};
 std::atomic<int> g_default_frame_general{0};
+std::atomic<int> g_default_fused_multilabel{0};
 }  // namespace
 
 int lccrf::fail(int code, const char *fmt, ...)
@@ -57,6 +58,7 @@ int lccrf::use_device(int device_id)
 
 bool lccrf::default_single_wg() { return g_default_single_wg.load(std::memory_order_relaxed) != 0; }
 bool lccrf::default_frame_general() { return g_default_frame_general.load(std::memory_order_relaxed) != 0; }
+bool lccrf::default_fused_multilabel() { return g_default_fused_multilabel.load(std::memory_order_relaxed) != 0; }
 
 // lccrf_trim_cache: the pose-optimisation staging areas
 void lccrf::trim_pose_stages()
@@ -96,6 +98,7 @@ int lccrf_set_default_option(int option, int value)
     switch (option) {
     case LCCRF_OPT_SINGLE_WORKGROUP: g_default_single_wg.store(value != 0, std::memory_order_relaxed); return LCCRF_OK;
     case LCCRF_OPT_FRAME_GENERAL: g_default_frame_general.store(value != 0, std::memory_order_relaxed); return LCCRF_OK;
+    case LCCRF_OPT_FUSED_MULTILABEL: g_default_fused_multilabel.store(value != 0, std::memory_order_relaxed); return LCCRF_OK;
     default: return fail(LCCRF_E_INVALID, "option %d has no process-wide default", option);
     }
 }

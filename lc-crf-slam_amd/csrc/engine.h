@@ -551,10 +551,15 @@ struct SizedRequest {
 };
 struct SizedLaunch {
     int report;           // fused_report() of what was launched; 0: the frames are not ones the kernel takes and nothing was launched
-    int shape;            // lanes per workgroup (= per frame) | workgroups per CU << 16
+    int shape;            // lanes per workgroup (= per frame) | workgroups per CU << 16 (k_multilabel: | points per lane << 16)
 };
+// Frames of c.L = 3 .. 8 labels (the caller has checked the terms: Potts, normalised AFTER, and a fixed count) go to k_multilabel
+// (fused_multilabel.hip: one 1024-lane workgroup per frame; the caller reports engine 5).
 SizedLaunch launch_inference(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const SizedRequest &rq,
                              hipStream_t s);
+// Would k_multilabel take these frames?  3 .. 8 labels, one or two 2-D kernels whose tables fit the u16 records, at most the plan's
+// active points for that label count, lattices that fit the two-label LDS plan (fused_multilabel.hip has the shipped range).
+bool multilabel_supported(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow);
 
 // ---- convergence-driven inference on the streaming engine (include/lccrf.h sections 1h and 2e) ---------------------------------
 // For everything the one-launch kernels do not take: the bookkeeping behind each step (converge_track.hip) -- per frame the kept

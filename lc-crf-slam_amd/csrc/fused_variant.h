@@ -61,5 +61,7 @@ int launch_general(const CrfDev &c, const KernelDev *kds, const int *maxV, const
 int launch_converge(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const SizedRequest &rq, hipStream_t s);
 int launch_general_converge(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const SizedRequest &rq,
                             hipStream_t s);
+// ... and k_multilabel (fused_multilabel.hip): frames of 3 to 8 labels, a fixed count of Potts iterations; the same return value
+int launch_multilabel(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const SizedRequest &rq, hipStream_t s);
 
 }  // namespace lccrf

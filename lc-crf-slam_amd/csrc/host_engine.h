@@ -20,6 +20,7 @@ namespace lccrf {
 // Sets the calling thread's error text (lccrf_last_error) and returns `code`.  Defined once, in api_tools.hip.
 int fail(int code, const char *fmt, ...);
 bool default_single_wg(), default_frame_general();   // LCCRF_OPT_SINGLE_WORKGROUP's and LCCRF_OPT_FRAME_GENERAL's process-wide defaults (api_tools.hip)
+bool default_fused_multilabel();                      // ... and LCCRF_OPT_FUSED_MULTILABEL's
 
 #define HIP_TRY(expr)                                                                        \
     do {                                                                                     \
@@ -135,11 +136,12 @@ struct Engine {
 
     // ---- engine choice ----
     int engine_pref = 0;
-    int sized_engine = 1;              // what choose_sized_engine() chose for inference on lattices that sit in HBM (1, 2 or 4)
+    int sized_engine = 1;              // what choose_sized_engine() chose for inference on lattices that sit in HBM (1, 2, 4 or 5)
     int last_with_map = 0;             // did the last inference produce MAP labels?
     size_t fused_lds = 0;
     LeanPrep lean_prep;                // prepared launch records of the two-frames-per-CU inference kernel (engine.h)
     bool fused_fits = false;           // learn_sizes(): the lattices now in HBM fit the fused engine
+    bool multi_fits = false;           // ... or, with 3 to 8 labels, the plan of its multi-label kernel (multilabel_supported)
     bool batch_owned = false;          // set by lccrf_batch_create: the engine of a batch (whatever its frame count), not of a handle
 
     // ---- deferred unaries ----
@@ -245,18 +247,20 @@ struct Engine {
         bool fused_backward = false;   // LCCRF_OPT_FUSED_BACKWARD: dL/dU and dL/dw of frames the fused plan takes run in one launch (fused_backward.hip)
         bool fused_backward_learnt = false;   // LCCRF_OPT_FUSED_BACKWARD_LEARNT: the same for learnt models and dL/dmu (fused_backward_general.hip)
         bool fused_backward_features = false; // LCCRF_OPT_FUSED_BACKWARD_FEATURES: the same with feature gradients (fused_backward_features.hip)
+        bool fused_multilabel = false; // LCCRF_OPT_FUSED_MULTILABEL: frames of 3 to 8 labels the fused plan takes run in one launch (fused_multilabel.hip)
         int vertex_order = 0;          // LCCRF_OPT_VERTEX_ORDER: 0 automatic (= on), 1 on, 2 off -- locality mode's sorted build
         bool event_timing = true;      // LCCRF_OPT_EVENT_TIMING: HIP events around every build / inference / run of the batch API
-        static Options fresh() { Options o; o.single_wg = default_single_wg(); o.frame_general = default_frame_general(); return o; }
+        static Options fresh() { Options o; o.single_wg = default_single_wg(); o.frame_general = default_frame_general(); o.fused_multilabel = default_fused_multilabel(); return o; }
     } opt;
 
     // ---- what the last run was ----
     // Report only (lccrf_get_engine, lccrf_batch_get_engine / _fused_shape / _fallback_frames, lccrf_get_backward_route): nothing
     // decides on it.  Written by the recorders below, one per route, and reset as a whole (recycle, lccrf_create).
     struct RunReport {
-        int engine = 1;                // 1 streaming, 2 fused, 3 one launch per frame, 4 the fused engine's kernels with matrices and factors
-        int shape = 0;                 // fused_report() of the last inference on engine 2 or 4, else 0
-        int fused_shape = 0;           // what the last one-workgroup inference launched: lanes per frame | frames per CU << 16
+        int engine = 1;                // 1 streaming, 2 fused, 3 one launch per frame, 4 the fused engine's kernels with matrices and factors,
+                                       //   5 its kernel for 3 to 8 labels
+        int shape = 0;                 // fused_report() of the last inference on engine 2, 4 or 5, else 0
+        int fused_shape = 0;           // what the last one-workgroup inference launched: lanes per frame | frames per CU << 16 (engine 5: | points per lane << 16)
         int conv_engine = 0;           // 4 / 3 / 2 / 1 when the last inference was a converged one, else 0
         int fallback_frames = 0;       // frames the last one-launch run had to re-run
         int backward_route = 0;        // LCCRF_BACKWARD_* of the last successful backward call
@@ -402,10 +406,13 @@ struct Engine {
 
     // Lattices that fit the fused plan: Potts terms normalised AFTER run on the fused engine; frames -- a handle's one or a batch's
     // F -- of up to kGeneralMaxPoints active points with a matrix or another mode on the general kernel; anything else streams.
+    // Under LCCRF_OPT_FUSED_MULTILABEL, Potts terms normalised AFTER over 3 to 8 labels on lattices that fit the multi-label kernel's
+    // plan (multi_fits; never together with fused_fits, which wants two labels) run on that kernel: engine 5.
     static constexpr int kGeneralMaxPoints = 2048;
     void choose_sized_engine()
     {
         sized_engine = !fused_fits ? 1 : !model.general() ? 2 : active_points(crf) <= kGeneralMaxPoints ? 4 : 1;
+        if (opt.fused_multilabel && multi_fits && !model.general()) sized_engine = 5;
     }
     // what the streaming step, the plug-in filter and the backward sweep are handed (valid behind kStepViews)
     const KernelDev *step_kdevs() const { return model.n_modes ? model.kdevs_post.data() : kdevs.data(); }
