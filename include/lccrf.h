@@ -125,7 +125,9 @@ int  lccrf_trim_cache(void);
  *       engine 2's shape word, lccrf_batch_get_fused_shape 1024 and the points per lane (1 or 2), and lccrf_batch_set_engine(b, 2) is
  *       honoured for such a batch.  Everything else -- the converged calls, the gradients (whose replay streams), the stepwise calls,
  *       two labels, nine and more, matrices, modes, a 3-D term, larger frames -- takes exactly the route it takes with the option
- *       off.  Label bits exist for two labels only.  Takes effect with the next inference.
+ *       off.  Label bits exist for two labels only.  Takes effect with the next inference.  The same switch as bit
+ *       LCCRF_MULTILABEL_POTTS of lccrf_set_multilabel_routes, whose other bit, LCCRF_MULTILABEL_LEARNT, moves the frames with
+ *       matrices and modes (engine 6).
  * lccrf_set_option applies to one handle (set it after lccrf_create: a handle taken from the cache starts from the defaults) and is
  * per handle (or batch) only for LCCRF_OPT_VERTEX_ORDER, LCCRF_OPT_COPY_THREADS, LCCRF_OPT_EVENT_TIMING, LCCRF_OPT_FUSED_BACKWARD,
  * LCCRF_OPT_FUSED_BACKWARD_LEARNT and LCCRF_OPT_FUSED_BACKWARD_FEATURES;
@@ -144,6 +146,28 @@ typedef enum lccrf_option {
 } lccrf_option;
 int  lccrf_set_option(lccrf_handle h, int option, int value);
 int  lccrf_set_default_option(int option, int value);
+
+/* Which ONE-launch kernels a fixed count of iterations on frames of THREE TO EIGHT labels may take (lattices in HBM: lccrf_inference on
+ * a handle whose lattices are built, lccrf_batch_inference, lccrf_batch_run where it builds into HBM).  A mask of routes, not an option
+ * number: added WITHOUT a step of LCCRF_ABI_VERSION (it stays 3), probe for the calls by symbol.  The follow-ups of these kernels --
+ * the convergence form, the fresh-frame kernels -- get further BITS here, not option numbers.
+ *   LCCRF_MULTILABEL_POTTS    IS LCCRF_OPT_FUSED_MULTILABEL: setting either is visible through the other; lccrf_set_option(h, 9, v) and
+ *       the process-wide default touch this bit alone.  Potts terms normalised AFTER on k_multilabel, engine 5.
+ *   LCCRF_MULTILABEL_LEARNT   (off by default; no process-wide default, and a handle taken from the cache starts without it) frames
+ *       of which at least one term carries a label-compatibility matrix (sections 1e / 2g) or a normalisation mode other than AFTER
+ *       (sections 1g / 2g) run on k_multilabel_general (csrc/fused_multilabel_general.hip; notes/fused_multilabel.md section 6), one
+ *       1024-lane workgroup per frame: one or two 2-D terms, 3 or 4 labels on frames of up to 2048 points, 5 to 8 labels on frames of
+ *       up to 1024 (the largest n_points the host knows, else the capacity), lattices that fit the fused engine's plan, no locality
+ *       mode; a batch decides once, over its largest frame and lattices.  Q and the labels are bit for bit those of the bit off (the
+ *       streaming engine's general step); lccrf_get_engine / lccrf_batch_get_engine report 6 with engine 5's shape word,
+ *       lccrf_batch_get_fused_shape 1024 and the points per lane, and lccrf_batch_set_engine(b, 2) is honoured for such a batch.
+ * The two bits are independent: each moves its own frames and no others.  Everything else -- the converged and the stepwise calls, the
+ * gradients (whose replay streams), two labels, nine and more, a 3-D term, locality mode, an engine preference of 1, frames beyond the
+ * plan -- keeps its route, bit for bit.  Takes effect with the next inference.
+ * LCCRF_E_INVALID, with nothing written, for a NULL handle, a NULL `routes` or bits beyond the two.                                 */
+enum { LCCRF_MULTILABEL_POTTS = 1, LCCRF_MULTILABEL_LEARNT = 2 };
+int  lccrf_set_multilabel_routes(lccrf_handle h, unsigned routes);
+int  lccrf_get_multilabel_routes(lccrf_handle h, unsigned *routes);
 
 /* DenseCRF::setUnaryEnergy(const float*)        densecrf3d.h:41-43                    */
 int  lccrf_set_unary(lccrf_handle h, const float *unary);
@@ -194,10 +218,11 @@ int  lccrf_get_probability(lccrf_handle h, float *prob_out);
  *   *engine   1 the streaming engine (one launch per phase); 2 the fused engine (lattices in HBM, inference in one launch);
  *             3 one launch per frame (lattice build + inference); 4 the fused engine's kernel for terms with a label-compatibility
  *             matrix (section 1e) or a normalisation mode other than AFTER (section 1g); 5 its kernel for frames of three to eight
- *             labels (LCCRF_OPT_FUSED_MULTILABEL).  For 3 it is the value after a late-bound
+ *             labels (LCCRF_OPT_FUSED_MULTILABEL); 6 that kernel's form for terms with a matrix or a mode
+ *             (LCCRF_MULTILABEL_LEARNT).  For 3 it is the value after a late-bound
  *             run has settled: a frame that did not fit the one-launch kernel's plan reports what it was re-run on.  A handle
  *             that has not run lccrf_inference reports 1.
- *   *shape    (may be NULL) for engines 2, 4 and 5: lanes per workgroup in bits 0-15, points per lane in bits 16-19, and 1 in bit 20
+ *   *shape    (may be NULL) for engines 2, 4, 5 and 6: lanes per workgroup in bits 0-15, points per lane in bits 16-19, and 1 in bit 20
  *             when the first term's splat rows took the chain path; otherwise 0.
  * Report only: nothing depends on the value, and the call does no device work beyond settling a pending one-launch run.
  * LCCRF_E_INVALID for a NULL handle or a NULL `engine`.                                                                          */
@@ -745,6 +770,9 @@ int  lccrf_batch_create(lccrf_batch_handle *out, int device_id, const lccrf_batc
 void lccrf_batch_destroy(lccrf_batch_handle b);
 /* lccrf_set_option for a batch (LCCRF_OPT_SINGLE_WORKGROUP: batches of up to 64 two-kernel frames take two workgroups per frame) */
 int  lccrf_batch_set_option(lccrf_batch_handle b, int option, int value);
+/* lccrf_set_multilabel_routes / lccrf_get_multilabel_routes for a batch (section 1: LCCRF_MULTILABEL_POTTS | LCCRF_MULTILABEL_LEARNT) */
+int  lccrf_batch_set_multilabel_routes(lccrf_batch_handle b, unsigned routes);
+int  lccrf_batch_get_multilabel_routes(lccrf_batch_handle b, unsigned *routes);
 
 /* Host inputs (copied to the device).  n_points[f] <= max_points; arrays are strided by
  * max_points per frame.  Exactly one of unary / label must be non-NULL.                 */
@@ -829,14 +857,16 @@ int  lccrf_batch_device_label_bits(lccrf_batch_handle b, const uint64_t **d_bits
  *   engine's kernels for terms with a label-compatibility matrix or a normalisation mode
  *   (section 2g: one 1024-lane workgroup per frame, fixed count or until converged), and
  *   5 = its kernel for frames of three to eight labels (LCCRF_OPT_FUSED_MULTILABEL), which
- *   engine 2 ("fused or fail") accepts for such a batch when the option is on and the plan fits. */
+ *   engine 2 ("fused or fail") accepts for such a batch when the option is on and the plan fits,
+ *   and 6 = that kernel's form for terms with a matrix or a mode (LCCRF_MULTILABEL_LEARNT), under
+ *   the same rule.                                                                              */
 int  lccrf_batch_set_engine(lccrf_batch_handle b, int engine);
 int  lccrf_batch_get_engine(lccrf_batch_handle b, int *engine_in_use);
 /* Report only: the workgroup shape of the last one-workgroup-per-frame launch -- lccrf_batch_inference on the fused engine (engine 2),
  * lccrf_batch_run's one-launch kernel (engine 3) or section 2g's kernels (engine 4: always 1024 and 1), whichever ran last -- as
  * lanes per frame (1024 or 512) and how many frames share a CU (1; 2 for the half-LDS plans: batches of at least 256 frames of up to
- * 2048 points, csrc/fused_lean.h and csrc/frame_lean.hip).  LCCRF_OPT_FUSED_MULTILABEL's kernel (engine 5) reports 1024 and, in the second
- * value, its POINTS PER LANE (1 or 2; a frame per CU always).  0 / 0 if no such launch happened yet.  Same results in every shape (the order of every row sum is the
+ * 2048 points, csrc/fused_lean.h and csrc/frame_lean.hip).  LCCRF_OPT_FUSED_MULTILABEL's and LCCRF_MULTILABEL_LEARNT's kernels (engines 5 and 6) report 1024 and, in the second
+ * value, their POINTS PER LANE (1 or 2; a frame per CU always).  0 / 0 if no such launch happened yet.  Same results in every shape (the order of every row sum is the
  * reference's, permutohedral_cpu.h:653-661).                                                                                   */
 int  lccrf_batch_get_fused_shape(lccrf_batch_handle b, int *lanes_per_frame, int *frames_per_cu);
 /* Report only: how the lattices now in HBM were built (after lccrf_batch_build) -- whether the points of a frame are processed in

@@ -443,6 +443,16 @@ public:
     // setOption(LCCRF_OPT_FUSED_BACKWARD_LEARNT, 1): the gradients of such a model, dL/dmu included, run in one launch (section 1k).
     // setOption(LCCRF_OPT_FUSED_MULTILABEL, 1): inference() of a frame of three to eight labels the fused plan takes runs in one launch (engine() reports 5).
     void setOption(int option, int value) { lccrf_check(lccrf_set_option(h_, option, value), "lccrf_set_option"); }
+    // lccrf_set_multilabel_routes / lccrf_get_multilabel_routes: a mask of LCCRF_MULTILABEL_POTTS (= LCCRF_OPT_FUSED_MULTILABEL) and
+    // LCCRF_MULTILABEL_LEARNT -- inference() of a frame of three to eight labels under setCompatibility / setNormalization runs in one
+    // launch where the plan fits (engine() reports 6), the same bits.
+    void setMultilabelRoutes(unsigned routes) { lccrf_check(lccrf_set_multilabel_routes(h_, routes), "lccrf_set_multilabel_routes"); }
+    unsigned multilabelRoutes() const
+    {
+        unsigned r = 0;
+        lccrf_check(lccrf_get_multilabel_routes(h_, &r), "lccrf_get_multilabel_routes");
+        return r;
+    }
     // lccrf_get_backward_route (include/lccrf.h section 1j): the route of the last successful backward call on this handle -- 0 none yet,
     // 1 the streaming sweep, 2 one launch (setOption(LCCRF_OPT_FUSED_BACKWARD, 1) / (LCCRF_OPT_FUSED_BACKWARD_LEARNT, 1)).  Report only.
     int backwardRoute() const

@@ -30,6 +30,7 @@ OPT_FUSED_BACKWARD = 6          # gradients of tracker-sized two-label frames in
 OPT_FUSED_BACKWARD_LEARNT = 7   # ... of learnt models (matrices, normalisation modes) and dL/dmu (include/lccrf.h section 1k)
 OPT_FUSED_BACKWARD_FEATURES = 8 # ... with feature gradients on Potts terms normalised AFTER (include/lccrf.h section 1l)
 OPT_FUSED_MULTILABEL = 9        # frames of three to eight labels on lattices in HBM infer in one launch (csrc/fused_multilabel.hip)
+MULTILABEL_POTTS, MULTILABEL_LEARNT = 1, 2   # lccrf_set_multilabel_routes' bits: POTTS is OPT_FUSED_MULTILABEL, LEARNT moves matrices and modes
 BACKWARD_NONE, BACKWARD_STREAM, BACKWARD_FUSED = 0, 1, 2   # lccrf_backward_route
 IMAGE_NONE, IMAGE_U8, IMAGE_F32 = 0, 1, 2   # lccrf_add_image_kernel's image formats
 NORMALIZE_AFTER, NORMALIZE_BEFORE, NORMALIZE_SYMMETRIC, NORMALIZE_NONE = 0, 1, 2, 3   # lccrf_normalization (section 1g)
@@ -164,6 +165,10 @@ def lib():
     for name in ("lccrf_get_backward_route", "lccrf_batch_get_backward_route"):   # (section 1j: probe by symbol -- a library from before
         if hasattr(L, name):                                                      #  the route, named through LCCRF_LIB, has neither)
             getattr(L, name).argtypes = [vp, C.POINTER(C.c_int)]
+    for prefix in ("lccrf_", "lccrf_batch_"):                                     # (added without an ABI step: probe by symbol too)
+        if hasattr(L, prefix + "set_multilabel_routes"):
+            getattr(L, prefix + "set_multilabel_routes").argtypes = [vp, C.c_uint]
+            getattr(L, prefix + "get_multilabel_routes").argtypes = [vp, C.POINTER(C.c_uint)]
     L.lccrf_set_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p]
     L.lccrf_get_pairwise_compatibility.argtypes = [vp, C.c_int, _f32p, C.POINTER(C.c_int)]
     L.lccrf_inference_backward_compat.argtypes = [vp, C.c_int, C.c_float, vp, vp, vp, vp]
@@ -289,6 +294,17 @@ class _Handle:
 
     def set_option(self, option, value):
         _check(self._c("set_option")(self.h, int(option), int(value)))
+
+    def set_multilabel_routes(self, routes):
+        """Which one-launch kernels a fixed count on frames of three to eight labels may take: a mask of MULTILABEL_POTTS (the same
+        switch as OPT_FUSED_MULTILABEL: engine 5) and MULTILABEL_LEARNT (terms with a matrix or a normalisation mode: engine 6).  Same
+        bits on every route (include/lccrf.h: lccrf_set_multilabel_routes)."""
+        _check(self._c("set_multilabel_routes")(self.h, int(routes)))
+
+    def multilabel_routes(self):
+        r = C.c_uint(0)
+        _check(self._c("get_multilabel_routes")(self.h, C.byref(r)))
+        return r.value
 
     def set_pairwise_weight(self, k, w):
         """PottsPotential3D::w_ of term k; the next inference equals that of a handle or batch created with weight w."""
@@ -546,8 +562,8 @@ class DenseCRFHIP(_Handle):
 
     def engine(self):
         """(engine, shape) of the last inference(): 1 streaming, 2 fused, 3 one launch per frame, 4 the fused engine's kernel for
-        terms with a matrix or a normalisation mode, 5 its kernel for three to eight labels (OPT_FUSED_MULTILABEL); shape (engines 2, 4
-        and 5, else 0): lanes per workgroup | points per lane << 16 |
+        terms with a matrix or a normalisation mode, 5 its kernel for three to eight labels (OPT_FUSED_MULTILABEL), 6 that
+        kernel's form for a learnt model (MULTILABEL_LEARNT); shape (engines 2, 4, 5 and 6, else 0): lanes per workgroup | points per lane << 16 |
         first term on chain rows << 20.  Report only (include/lccrf.h: lccrf_get_engine)."""
         e, s = C.c_int(0), C.c_int(0)
         _check(lib().lccrf_get_engine(self.h, C.byref(e), C.byref(s)))
@@ -631,6 +647,7 @@ class BatchCRF(_Handle):
     OPT_FUSED_BACKWARD_LEARNT = 7
     OPT_FUSED_BACKWARD_FEATURES = 8
     OPT_FUSED_MULTILABEL = 9
+    MULTILABEL_POTTS, MULTILABEL_LEARNT = 1, 2
 
     def set_inputs_host_async(self, n_points, features, unary=None, label=None, conf=None, pinned=False):
         """lccrf_batch_set_inputs_host_async: the arrays are staged and uploaded without a host wait.  The arrays must already be

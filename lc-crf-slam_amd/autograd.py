@@ -251,6 +251,20 @@ def _option_attribute(owner):
     return property(get, put)
 
 
+def _route_attribute(owner):
+    """the layers' fused_multilabel_learnt, after _option_attribute's pattern: a bool attribute whose assignment sets or clears
+    MULTILABEL_LEARNT among the multilabel routes of the handle or batch the layer owns (the other route bits stay as they are);
+    takes effect with the next forward"""
+    def get(self):                                            # (the handle's own bit: it cannot drift from a direct set_multilabel_routes)
+        return bool(getattr(self, owner).multilabel_routes() & _pkg.MULTILABEL_LEARNT)
+
+    def put(self, value):
+        crf = getattr(self, owner)
+        routes = crf.multilabel_routes() & ~_pkg.MULTILABEL_LEARNT
+        crf.set_multilabel_routes(routes | (_pkg.MULTILABEL_LEARNT if value else 0))
+    return property(get, put)
+
+
 class _HandleCRF(torch.nn.Module):
     """what MeanFieldCRF and CompatMeanFieldCRF share: a DenseCRFHIP handle over fixed features, the term weights an nn.Parameter"""
 
@@ -279,7 +293,8 @@ class MeanFieldCRF(_HandleCRF):
     gradients of a frame the one-launch backward takes are then formed in one launch, the same bits (section 1j);
     the attribute fused_multilabel (False; the constructor's parameter list is kept as it was): set to True, it puts
     OPT_FUSED_MULTILABEL on the handle -- the forward of a frame of three to eight labels the fused plan takes then runs in one
-    launch, the same bits; the backward is unchanged.
+    launch, the same bits; the backward is unchanged.  The attribute fused_multilabel_learnt (False) does the same with
+    MULTILABEL_LEARNT for a layer with a `normalization` other than AFTER (engine 6).
     forward(unary [N, L]) -> Q [N, L]."""
 
     def __init__(self, n_points, n_labels, features, weights, n_iterations=5, relax=1.0, device=0, normalization=None,
@@ -289,6 +304,7 @@ class MeanFieldCRF(_HandleCRF):
             self.crf.set_option(_pkg.OPT_FUSED_BACKWARD, 1)
 
     fused_multilabel = _option_attribute("crf")
+    fused_multilabel_learnt = _route_attribute("crf")
 
     def forward(self, unary):
         return mean_field(self.crf, unary, self.weights, self.n_iterations, self.relax)
@@ -298,7 +314,9 @@ class CompatMeanFieldCRF(_HandleCRF):
     """MeanFieldCRF whose terms carry a learnt label-compatibility matrix: parameters `weights` [K] and `compat` [K, L, L], the
     latter initialised to identities (the Potts model); normalization as MeanFieldCRF takes it; fused_backward: sets OPT_FUSED_BACKWARD
     and OPT_FUSED_BACKWARD_LEARNT on the handle -- the gradients of frames the fused plan takes run in one launch (include/lccrf.h
-    sections 1j and 1k; the same bits).  forward(unary [N, L]) -> Q [N, L]."""
+    sections 1j and 1k; the same bits); the attribute fused_multilabel_learnt (False; not a constructor argument): set to True, it puts
+    MULTILABEL_LEARNT on the handle -- the forward of a frame of three to eight labels the plan takes then runs in one launch (engine
+    6), the same bits; the backward is unchanged.  forward(unary [N, L]) -> Q [N, L]."""
 
     def __init__(self, n_points, n_labels, features, weights, n_iterations=5, relax=1.0, device=0, normalization=None,
                  fused_backward=False):
@@ -307,6 +325,8 @@ class CompatMeanFieldCRF(_HandleCRF):
             self.crf.set_option(_pkg.OPT_FUSED_BACKWARD, 1)
             self.crf.set_option(_pkg.OPT_FUSED_BACKWARD_LEARNT, 1)
         self.compat = _identities(len(weights), n_labels)
+
+    fused_multilabel_learnt = _route_attribute("crf")
 
     def forward(self, unary):
         return mean_field_compat(self.crf, unary, self.weights, self.compat, self.n_iterations, self.relax)
@@ -540,7 +560,8 @@ class BatchMeanFieldCRF(_BatchCRF):
     deviation); weights: their initial weights; fused_backward: sets OPT_FUSED_BACKWARD on the batch (include/lccrf.h section 1j: the
     same gradients, in one launch where the frames fit); the attribute fused_multilabel (False; the constructor's parameter list is
     kept as it was): set to True, it puts OPT_FUSED_MULTILABEL on the batch (the forward of frames of three to eight labels in one
-    launch where the plan fits, the same bits; the backward is unchanged).
+    launch where the plan fits, the same bits; the backward is unchanged); the attribute fused_multilabel_learnt (False) is the
+    batch's MULTILABEL_LEARNT route, as on BatchCompatMeanFieldCRF.
     forward(unary [F, max_points, L]) -> Q [F, max_points, L]."""
 
     def __init__(self, n_points, features, weights, n_iterations=5, relax=1.0, device=0, n_labels=2, fused_backward=False):
@@ -549,6 +570,7 @@ class BatchMeanFieldCRF(_BatchCRF):
             self.batch.set_option(_pkg.OPT_FUSED_BACKWARD, 1)
 
     fused_multilabel = _option_attribute("batch")
+    fused_multilabel_learnt = _route_attribute("batch")
 
     def forward(self, unary):
         return mean_field_batch(self.batch, unary, self.weights, self.n_iterations, self.relax)
@@ -576,7 +598,9 @@ class BatchCompatMeanFieldCRF(_BatchCRF):
     latter initialised to identities (the Potts model), both shared by every frame; normalization: None (the reference's form), one of
     the package's NORMALIZE_* modes for every term, or one per term, set once; fused_backward: sets OPT_FUSED_BACKWARD and
     OPT_FUSED_BACKWARD_LEARNT on the batch (include/lccrf.h sections 1j and 1k: the same bits in one launch plus the two of the sums
-    over the frames).  The features are uploaded and the lattices built once, here.
+    over the frames); the attribute fused_multilabel_learnt (False; not a constructor argument): set to True, it puts
+    MULTILABEL_LEARNT on the batch -- the forward of frames of three to eight labels the plan takes in one launch (engine 6), the same
+    bits; the backward is unchanged.  The features are uploaded and the lattices built once, here.
     forward(unary [F, max_points, L]) -> Q [F, max_points, L]."""
 
     def __init__(self, n_points, features, weights, n_iterations=5, relax=1.0, device=0, n_labels=2, normalization=None,
@@ -586,6 +610,8 @@ class BatchCompatMeanFieldCRF(_BatchCRF):
             self.batch.set_option(_pkg.OPT_FUSED_BACKWARD, 1)
             self.batch.set_option(_pkg.OPT_FUSED_BACKWARD_LEARNT, 1)
         self.compat = _identities(len(weights), n_labels)
+
+    fused_multilabel_learnt = _route_attribute("batch")
 
     def forward(self, unary):
         return mean_field_batch_compat(self.batch, unary, self.weights, self.compat, self.n_iterations, self.relax)

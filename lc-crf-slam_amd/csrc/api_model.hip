@@ -1,5 +1,6 @@
 // api_model.hip -- the entry points a handle and a batch share word for word: the terms' weights (sections 1c / 2c of include/lccrf.h),
-// label-compatibility matrices (1e / 2g) and normalisation modes (1g / 2g), the backward route (1j) and the splat and blur plans.
+// label-compatibility matrices (1e / 2g) and normalisation modes (1g / 2g), the backward route (1j), the splat and blur plans and the
+// one-launch routes of frames of three to eight labels (lccrf_set_multilabel_routes).
 //
 // One body per entry point, on the Engine (host_engine.h); below them the two extern "C" forms of each, side by side: the checks in
 // the form's own order, then the body.  Every setter settles a pending one-launch run first (it may still be re-run: with the model
@@ -64,6 +65,27 @@ int get_route(const Engine *e, int *route)
 {
     if (!e || !route) return fail(LCCRF_E_INVALID, "handle / route is NULL");
     *route = e->report.backward_route;
+    return LCCRF_OK;
+}
+
+// The one-launch routes of frames of three to eight labels: bit 0 IS Options::fused_multilabel (LCCRF_OPT_FUSED_MULTILABEL), bit 1
+// Options::fused_multilabel_learnt.  Like lccrf_set_option: no device is selected, nothing is settled; the next inference decides.
+constexpr unsigned kMultilabelRoutes = LCCRF_MULTILABEL_POTTS | LCCRF_MULTILABEL_LEARNT;
+int set_routes(Engine *e, unsigned routes)
+{
+    if (!e) return fail(LCCRF_E_INVALID, "handle is NULL");
+    if (routes & ~kMultilabelRoutes)
+        return fail(LCCRF_E_INVALID, "routes 0x%x has bits beyond LCCRF_MULTILABEL_POTTS | LCCRF_MULTILABEL_LEARNT", routes);
+    e->opt.fused_multilabel = (routes & LCCRF_MULTILABEL_POTTS) != 0;
+    e->opt.fused_multilabel_learnt = (routes & LCCRF_MULTILABEL_LEARNT) != 0;
+    e->choose_sized_engine();
+    return LCCRF_OK;
+}
+
+int get_routes(const Engine *e, unsigned *routes)
+{
+    if (!e || !routes) return fail(LCCRF_E_INVALID, "handle / routes is NULL");
+    *routes = (e->opt.fused_multilabel ? LCCRF_MULTILABEL_POTTS : 0u) | (e->opt.fused_multilabel_learnt ? LCCRF_MULTILABEL_LEARNT : 0u);
     return LCCRF_OK;
 }
 
@@ -140,6 +162,12 @@ int lccrf_batch_get_pairwise_normalization(lccrf_batch_handle b, int kernel, int
 // section 1j: which route the last successful backward call took
 int lccrf_get_backward_route(lccrf_handle h, int *route) { return get_route(h ? &h->eng : nullptr, route); }
 int lccrf_batch_get_backward_route(lccrf_batch_handle b, int *route) { return get_route(b ? &b->eng : nullptr, route); }
+
+// which one-launch kernels frames of three to eight labels may take
+int lccrf_set_multilabel_routes(lccrf_handle h, unsigned routes) { return set_routes(h ? &h->eng : nullptr, routes); }
+int lccrf_get_multilabel_routes(lccrf_handle h, unsigned *routes) { return get_routes(h ? &h->eng : nullptr, routes); }
+int lccrf_batch_set_multilabel_routes(lccrf_batch_handle b, unsigned routes) { return set_routes(b ? &b->eng : nullptr, routes); }
+int lccrf_batch_get_multilabel_routes(lccrf_batch_handle b, unsigned *routes) { return get_routes(b ? &b->eng : nullptr, routes); }
 
 // the splat and blur plans of a term's lattices
 int lccrf_get_splat_plan(lccrf_handle h, int kernel, lccrf_splat_plan *out) { HANDLE_FIRST(h, kernel); CHECK_OUT(out, "out"); return splat_plan(h->eng, kernel, out); }

@@ -355,7 +355,7 @@ int lccrf_get_engine(lccrf_handle h, int *engine, int *shape)
     }
     const Engine::RunReport &r = h->eng.report;
     *engine = r.engine;
-    if (shape) *shape = (r.engine == 2 || r.engine == 4 || r.engine == 5) ? r.shape : 0;
+    if (shape) *shape = (r.engine == 2 || r.engine == 4 || r.engine == 5 || r.engine == 6) ? r.shape : 0;
     return LCCRF_OK;
 }
 

@@ -478,13 +478,16 @@ inline Schedule converged_run(int max_iter, int criterion, float tol, int with_m
 {
     return Schedule{max_iter, with_map, relax, true, criterion, tol};
 }
-// The terms of a two-label CRF that are not all Potts terms normalised AFTER the filter (include/lccrf.h sections 1e, 1g and 2g).
-// All null: the Potts kernels.  Filled by Engine::term_model(), which owns the array behind `mats`.
+// The terms of a CRF that are not all Potts terms normalised AFTER the filter (include/lccrf.h sections 1e, 1g and 2g).
+// All null: the Potts kernels.  Filled by Engine::term_model(), which owns the arrays behind `mats` and `mats_dev`.
 struct TermModel {
-    const float *const *mats;      // null, or K HOST pointers: term k's [2][2] matrix or null -- passed to the kernels by value
+    const float *const *mats;      // null, or K HOST pointers: term k's [L][L] matrix or null -- the two-label kernels take the
+                                   //   [2][2] ones by value (copy_matrices)
     const float *const *pre;       // null, or K device pointers: the [F][maxN] factor of term k's filter input or null (the kernels on
                                    //   lattices in HBM, whose `kds` are Engine::step_kdevs(); the one-launch ones form it themselves)
     const int *norm_mode;          // null (every term AFTER), or K lccrf_normalization values (the one-launch kernels)
+    const float *const *mats_dev;  // null exactly when `mats` is, or K DEVICE pointers: term k's [L][L] matrix in HBM or null -- what
+                                   //   k_multilabel_general reads (3 to 8 labels: up to 2 x 64 floats are not passed by value)
     bool general() const { return mats || pre || norm_mode; }
 };
 // the matrices as the general kernels' arguments carry them: mu[k] = term k's, row-major; returns has_mu (bit k: term k has one)
@@ -551,15 +554,18 @@ struct SizedRequest {
 };
 struct SizedLaunch {
     int report;           // fused_report() of what was launched; 0: the frames are not ones the kernel takes and nothing was launched
-    int shape;            // lanes per workgroup (= per frame) | workgroups per CU << 16 (k_multilabel: | points per lane << 16)
+    int shape;            // lanes per workgroup (= per frame) | workgroups per CU << 16 (k_multilabel, k_multilabel_general: | points per lane << 16)
 };
-// Frames of c.L = 3 .. 8 labels (the caller has checked the terms: Potts, normalised AFTER, and a fixed count) go to k_multilabel
-// (fused_multilabel.hip: one 1024-lane workgroup per frame; the caller reports engine 5).
+// Frames of c.L = 3 .. 8 labels and a fixed count (the caller has checked the schedule) go to k_multilabel (fused_multilabel.hip: one
+// 1024-lane workgroup per frame, Potts terms normalised AFTER; the caller reports engine 5) or, with rq.terms.general(), to
+// k_multilabel_general (fused_multilabel_general.hip; kds: Engine::step_kdevs(); engine 6).
 SizedLaunch launch_inference(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const SizedRequest &rq,
                              hipStream_t s);
 // Would k_multilabel take these frames?  3 .. 8 labels, one or two 2-D kernels whose tables fit the u16 records, at most the plan's
 // active points for that label count, lattices that fit the two-label LDS plan (fused_multilabel.hip has the shipped range).
 bool multilabel_supported(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow);
+// ... and k_multilabel_general, whose shipped range is its own (fused_multilabel_general.hip)
+bool multilabel_general_supported(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow);
 
 // ---- convergence-driven inference on the streaming engine (include/lccrf.h sections 1h and 2e) ---------------------------------
 // For everything the one-launch kernels do not take: the bookkeeping behind each step (converge_track.hip) -- per frame the kept

@@ -597,8 +597,9 @@ size_t lean_prep_bytes(const CrfDev &c, const KernelDev *kds, const int *maxV, c
 SizedLaunch launch_inference(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const SizedRequest &rq,
                              hipStream_t s)
 {
-    if (c.L != 2) {                                          // three to eight labels: k_multilabel, a unit of its own as well
-        const int report = launch_multilabel(c, kds, maxV, maxRow, rq, s);
+    if (c.L != 2) {                                          // three to eight labels: k_multilabel, a unit of its own as well,
+        const auto unit = rq.terms.general() ? launch_multilabel_general : launch_multilabel;   // ... or its form for a learnt model
+        const int report = unit(c, kds, maxV, maxRow, rq, s);
         return SizedLaunch{report, report ? kNT | ((report >> 16) & 0xf) << 16 : 0};   // (lanes | points per lane << 16)
     }
     if (rq.run.until_converged || rq.terms.general()) {      // the variants in units of their own: 1024 lanes, a frame per CU

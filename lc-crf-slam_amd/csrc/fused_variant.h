@@ -63,5 +63,9 @@ int launch_general_converge(const CrfDev &c, const KernelDev *kds, const int *ma
                             hipStream_t s);
 // ... and k_multilabel (fused_multilabel.hip): frames of 3 to 8 labels, a fixed count of Potts iterations; the same return value
 int launch_multilabel(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const SizedRequest &rq, hipStream_t s);
+// ... and k_multilabel_general (fused_multilabel_general.hip): the same frames under terms with a matrix or a mode (rq.terms.general();
+// kds: Engine::step_kdevs(), the matrices read from rq.terms.mats_dev); the same return value
+int launch_multilabel_general(const CrfDev &c, const KernelDev *kds, const int *maxV, const int *maxRow, const SizedRequest &rq,
+                              hipStream_t s);
 
 }  // namespace lccrf

@@ -136,12 +136,13 @@ struct Engine {
 
     // ---- engine choice ----
     int engine_pref = 0;
-    int sized_engine = 1;              // what choose_sized_engine() chose for inference on lattices that sit in HBM (1, 2, 4 or 5)
+    int sized_engine = 1;              // what choose_sized_engine() chose for inference on lattices that sit in HBM (1, 2, 4, 5 or 6)
     int last_with_map = 0;             // did the last inference produce MAP labels?
     size_t fused_lds = 0;
     LeanPrep lean_prep;                // prepared launch records of the two-frames-per-CU inference kernel (engine.h)
     bool fused_fits = false;           // learn_sizes(): the lattices now in HBM fit the fused engine
     bool multi_fits = false;           // ... or, with 3 to 8 labels, the plan of its multi-label kernel (multilabel_supported)
+    bool learnt_fits = false;          // ... or that of its kernel for learnt models of 3 to 8 labels (multilabel_general_supported)
     bool batch_owned = false;          // set by lccrf_batch_create: the engine of a batch (whatever its frame count), not of a handle
 
     // ---- deferred unaries ----
@@ -248,6 +249,8 @@ struct Engine {
         bool fused_backward_learnt = false;   // LCCRF_OPT_FUSED_BACKWARD_LEARNT: the same for learnt models and dL/dmu (fused_backward_general.hip)
         bool fused_backward_features = false; // LCCRF_OPT_FUSED_BACKWARD_FEATURES: the same with feature gradients (fused_backward_features.hip)
         bool fused_multilabel = false; // LCCRF_OPT_FUSED_MULTILABEL: frames of 3 to 8 labels the fused plan takes run in one launch (fused_multilabel.hip)
+        bool fused_multilabel_learnt = false;   // LCCRF_MULTILABEL_LEARNT (lccrf_set_multilabel_routes; no option number, no process-wide default):
+                                       //   the same for terms with a matrix or a mode (fused_multilabel_general.hip)
         int vertex_order = 0;          // LCCRF_OPT_VERTEX_ORDER: 0 automatic (= on), 1 on, 2 off -- locality mode's sorted build
         bool event_timing = true;      // LCCRF_OPT_EVENT_TIMING: HIP events around every build / inference / run of the batch API
         static Options fresh() { Options o; o.single_wg = default_single_wg(); o.frame_general = default_frame_general(); o.fused_multilabel = default_fused_multilabel(); return o; }
@@ -258,9 +261,9 @@ struct Engine {
     // decides on it.  Written by the recorders below, one per route, and reset as a whole (recycle, lccrf_create).
     struct RunReport {
         int engine = 1;                // 1 streaming, 2 fused, 3 one launch per frame, 4 the fused engine's kernels with matrices and factors,
-                                       //   5 its kernel for 3 to 8 labels
-        int shape = 0;                 // fused_report() of the last inference on engine 2, 4 or 5, else 0
-        int fused_shape = 0;           // what the last one-workgroup inference launched: lanes per frame | frames per CU << 16 (engine 5: | points per lane << 16)
+                                       //   5 its kernel for 3 to 8 labels, 6 that kernel's form for learnt models (matrices and modes)
+        int shape = 0;                 // fused_report() of the last inference on engine 2, 4, 5 or 6, else 0
+        int fused_shape = 0;           // what the last one-workgroup inference launched: lanes per frame | frames per CU << 16 (engines 5 and 6: | points per lane << 16)
         int conv_engine = 0;           // 4 / 3 / 2 / 1 when the last inference was a converged one, else 0
         int fallback_frames = 0;       // frames the last one-launch run had to re-run
         int backward_route = 0;        // LCCRF_BACKWARD_* of the last successful backward call
@@ -320,7 +323,7 @@ struct Engine {
         TermModel terms(size_t K)
         {
             for (size_t k = 0; k < K; ++k) host_mats[k] = compat_ptr[k] ? matrix((int)k) : nullptr;
-            return TermModel{n_compat ? host_mats : nullptr, pre_arg(), n_modes ? norm_mode : nullptr};
+            return TermModel{n_compat ? host_mats : nullptr, pre_arg(), n_modes ? norm_mode : nullptr, n_compat ? compat_ptr : nullptr};
         }
         void views_changed();                            // (sync_views: the views derived from kdevs are rebuilt by ensure_factors())
         // `e` is the engine this model is the `model` of: its arena, stream, kernels and engine choice
@@ -407,12 +410,15 @@ struct Engine {
     // Lattices that fit the fused plan: Potts terms normalised AFTER run on the fused engine; frames -- a handle's one or a batch's
     // F -- of up to kGeneralMaxPoints active points with a matrix or another mode on the general kernel; anything else streams.
     // Under LCCRF_OPT_FUSED_MULTILABEL, Potts terms normalised AFTER over 3 to 8 labels on lattices that fit the multi-label kernel's
-    // plan (multi_fits; never together with fused_fits, which wants two labels) run on that kernel: engine 5.
+    // plan (multi_fits; never together with fused_fits, which wants two labels) run on that kernel: engine 5.  Under
+    // LCCRF_MULTILABEL_LEARNT, terms with a matrix or a mode over 3 to 8 labels on lattices that fit the plan of
+    // k_multilabel_general (learnt_fits) run on that kernel: engine 6.  The two bits are independent: each moves its own frames only.
     static constexpr int kGeneralMaxPoints = 2048;
     void choose_sized_engine()
     {
         sized_engine = !fused_fits ? 1 : !model.general() ? 2 : active_points(crf) <= kGeneralMaxPoints ? 4 : 1;
         if (opt.fused_multilabel && multi_fits && !model.general()) sized_engine = 5;
+        if (opt.fused_multilabel_learnt && learnt_fits && model.general()) sized_engine = 6;
     }
     // what the streaming step, the plug-in filter and the backward sweep are handed (valid behind kStepViews)
     const KernelDev *step_kdevs() const { return model.n_modes ? model.kdevs_post.data() : kdevs.data(); }

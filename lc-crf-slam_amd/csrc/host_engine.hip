@@ -578,8 +578,9 @@ int Engine::learn_sizes(bool may_reorder)
     invalidate_lean_prep();                            // (every path that changes a lattice clears sizes_known and so comes through here)
     fused_fits = engine_pref != 1 && !perm_on && fused_supported(crf, kdevs.data(), maxV.data(), maxRow.data(), &fused_lds);
     multi_fits = engine_pref != 1 && !perm_on && multilabel_supported(crf, kdevs.data(), maxV.data(), maxRow.data());
+    learnt_fits = engine_pref != 1 && !perm_on && multilabel_general_supported(crf, kdevs.data(), maxV.data(), maxRow.data());
     choose_sized_engine();
-    if (engine_pref == 2 && !fused_fits && sized_engine != 5)
+    if (engine_pref == 2 && !fused_fits && sized_engine != 5 && sized_engine != 6)
         return fail(LCCRF_E_CAPACITY, "fused engine requested but the problem does not fit one workgroup's LDS");
     return LCCRF_OK;
 }
@@ -847,7 +848,7 @@ int Engine::inference_sized(const Schedule &run, unsigned more_needs)
         }
     }
     if (!launch_sized(run, prep_need ? &lean_prep : nullptr))
-        return fail(LCCRF_E_STATE, "the fused engine's %s was chosen for a frame it does not take", sized_engine == 4 ? "general kernel" : sized_engine == 5 ? "multi-label kernel" : "kernel");
+        return fail(LCCRF_E_STATE, "the fused engine's %s was chosen for a frame it does not take", sized_engine == 4 ? "general kernel" : sized_engine == 5 ? "multi-label kernel" : sized_engine == 6 ? "multi-label general kernel" : "kernel");
     HIP_TRY(hipGetLastError());
     return LCCRF_OK;
 }
